@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: GF(2) row-XORs/s + solve wall-time, dense N x N solve_one.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload single|batch] [--n 65536]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload single|batch] [--n 65536] [--dump-outputs DIR]
 
 Workloads, all through the C ABI, inputs resident in HBM before the timed region:
 
@@ -50,6 +50,9 @@ HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 FULL_RANK_SEEDS = {65536: 1234, 32768: 1234, 262144: 1242}
 LDS_BYTES_PER_CLK_CU = 256.0   # ds_read_b128, conflict-free (MI355X_MICROARCH.md, LDS table)
 BATCH_SEED0 = 5000             # system i of the batch workload uses generator seed BATCH_SEED0 + i
+DUMP_BYTES_MAX = 64 * 10 ** 6  # --dump-outputs: all files of one run together
+DUMP_X_BYTES = 32 * 10 ** 6    # --dump-outputs: solution bits of a batch job beyond this are a fixed sample of its systems
+DUMP_SAMPLE_SEED = 0
 
 
 def parse():
@@ -81,7 +84,49 @@ def parse():
     ap.add_argument("--dry-run-ranks", action="store_true",
                     help="print every rank's plan of the multi-GPU batch job (shard bounds, gangs, record offsets, resident bytes) and "
                          "exit WITHOUT solving or touching a GPU: runs under torch.distributed.run with gloo on a CPU box")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="rank 0 writes what the timed path returned in its last timed step as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB): solution bits, status, rank, pivots -- two builds compared output for output "
+                         "(bench_outputs/ is git-ignored)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def bits_f32(words: np.ndarray, cols: int) -> np.ndarray:
+    """64-bit words (bit j = variable j; uint64 or the int64 of a record) -> float32 0/1 per variable, cols of them"""
+    words = np.ascontiguousarray(words)
+    assert words.dtype.itemsize == 8, words.dtype
+    b = np.unpackbits(words.view(np.uint8), axis=-1, bitorder="little")
+    return b[..., :cols].astype(np.float32)
+
+
+def solution_arrays(sol, cols: int) -> dict:
+    """what a caller of solve_one receives, as float arrays: x (the solution bits), status, rank, pivots (column rank profile)"""
+    return {"x": bits_f32(sol.origin, cols), "status": np.array([sol.status], dtype=np.float64),
+            "rank": np.array([sol.rank], dtype=np.float64), "pivots": np.asarray(sol.pivots, dtype=np.float64)}
+
+
+def records_arrays(records: np.ndarray, cols: int) -> dict:
+    """the gathered [status, rank, origin] records of a batch job as float arrays: status and rank of every system; the solution
+    bits of every system, or of a fixed seeded sample of them (ascending `x_systems`) where all of them would exceed DUMP_X_BYTES"""
+    total = records.shape[0]
+    keep = max(1, DUMP_X_BYTES // (4 * cols))
+    idx = np.arange(total) if total <= keep else \
+        np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(total, size=keep, replace=False))
+    return {"status": records[:, 0].astype(np.float64), "rank": records[:, 1].astype(np.float64),
+            "x": bits_f32(records[idx, 2:], cols), "x_systems": idx.astype(np.float64)}
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    nbytes = sum(a.nbytes for a in arrays.values())
+    if nbytes > DUMP_BYTES_MAX:
+        raise SystemExit(f"--dump-outputs: {nbytes} bytes of outputs, the limit is {DUMP_BYTES_MAX}")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def cpu_baseline(n: int, seed: int) -> dict:
@@ -250,7 +295,8 @@ def finish_roofline(roofline: dict, s0: dict, blocks: int):
 
 def timed_single(mat: torch.Tensor, n: int, stride: int, steps: int, warmup: int, device: int, dev, world: int,
                  kernel_events: bool):
-    """W untimed + K timed solve_one steps of the resident system; returns (elapsed seconds over ranks, stats, sols)."""
+    """W untimed + K timed solve_one steps of the resident system; returns (elapsed seconds over ranks, stats, sols):
+    sols = [steps, ceil(n / 64)] int64 solution words per rank, the list the end-of-job gather returns (one entry at N = 1)."""
     stream = torch.cuda.current_stream(dev).cuda_stream
     cw = (n + 63) // 64
     sols = torch.zeros(steps, cw, dtype=torch.int64, device=dev)
@@ -271,12 +317,15 @@ def timed_single(mat: torch.Tensor, n: int, stride: int, steps: int, warmup: int
         s = step()
         stats.append(s)
         sols[k].copy_(torch.from_numpy(s.origin.view(np.int64)))
+    gathered = [sols]
     if world > 1:                                # the single end-of-job gather (RCCL over xGMI)
         if dist.get_backend() == "gloo":         # (tests: ranks sharing one GPU; gloo gathers host memory only)
             host = sols.cpu()
-            dist.all_gather([torch.empty_like(host) for _ in range(world)], host)
+            gathered = [torch.empty_like(host) for _ in range(world)]
+            dist.all_gather(gathered, host)
         else:
-            dist.all_gather([torch.empty_like(sols) for _ in range(world)], sols)
+            gathered = [torch.empty_like(sols) for _ in range(world)]
+            dist.all_gather(gathered, sols)
     torch.cuda.synchronize(dev)
     if world > 1:
         dist.barrier()
@@ -286,7 +335,7 @@ def timed_single(mat: torch.Tensor, n: int, stride: int, steps: int, warmup: int
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    return elapsed, stats, sols
+    return elapsed, stats, gathered
 
 
 def run_single(args, world, rank, local_rank, dev):
@@ -299,8 +348,14 @@ def run_single(args, world, rank, local_rank, dev):
     stream = torch.cuda.current_stream(dev).cuda_stream
     hip.synth_device(mat.data_ptr(), n, n, stride, seed + rank, device=local_rank, stream=stream)
     torch.cuda.synchronize(dev)
-    elapsed, stats, _ = timed_single(mat, n, stride, args.steps, args.warmup, local_rank, dev, world,
-                                     not args.no_kernel_events)
+    elapsed, stats, gathered = timed_single(mat, n, stride, args.steps, args.warmup, local_rank, dev, world,
+                                            not args.no_kernel_events)
+    if args.dump_outputs and rank == 0:
+        # rank 0's solve_one result of the last timed step; at N > 1 also every rank's solution of that step as gathered
+        dumped = solution_arrays(stats[-1], n)
+        if world > 1:
+            dumped["x_gathered"] = bits_f32(torch.stack([g[-1].cpu() for g in gathered]).numpy(), n)
+        dump_outputs(args.dump_outputs, dumped)
 
     # correctness gate on this rank: A x = b on the untouched input, by the independent residual kernel
     bad = hip.residual_device(mat.data_ptr(), n, n, stride, stats[-1].origin, device=local_rank, stream=stream)
@@ -586,9 +641,10 @@ def h2d_leg(n: int, seed: int, device: int, dev) -> dict:
             "x_equals_planted": ok}
 
 
-def batch_job(args, world, rank, local_rank, dev, steps: int, warmup: int):
+def batch_job(args, world, rank, local_rank, dev, steps: int, warmup: int, dump: str | None = None):
     """BASELINE configs[3]: args.batch_total independent n x n systems, contiguous blocks per rank, one gather.
-    `warmup` untimed + `steps` timed passes of the whole job; returns the measurement dict on rank 0, None elsewhere."""
+    `warmup` untimed + `steps` timed passes of the whole job; returns the measurement dict on rank 0, None elsewhere.
+    `dump`: rank 0 writes the gathered records of the last timed pass there (--dump-outputs)."""
     n, total = args.batch_n, args.batch_total
     lo, hi = batch.shard_bounds(total, world, rank)
     seeds = [BATCH_SEED0 + i for i in range(lo, hi)]
@@ -622,6 +678,8 @@ def batch_job(args, world, rank, local_rank, dev, steps: int, warmup: int):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if dump and rank == 0:
+        dump_outputs(dump, records_arrays(allrec.cpu().numpy(), n))
 
     # parity gate: every local system's A x = b on the untouched input (independent kernel); the gathered table must
     # hold this rank's records at its block and report every system of the job solved
@@ -690,7 +748,7 @@ def batch_job(args, world, rank, local_rank, dev, steps: int, warmup: int):
 
 def run_batch(args, world, rank, local_rank, dev):
     """`--workload batch`: the configs[3] job as the line's own value."""
-    job = batch_job(args, world, rank, local_rank, dev, args.steps, args.warmup)
+    job = batch_job(args, world, rank, local_rank, dev, args.steps, args.warmup, dump=args.dump_outputs)
     if rank != 0:
         return None
     out = {"metric": "GF(2) row-XORs/s (batch of independent dense NxN solve_one, sharded)"}
@@ -738,6 +796,8 @@ def run_sharded(args, world, rank, local_rank, dev):
         elapsed = float(t.item())
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, solution_arrays(sols[-1], n))
     bad = hip.residual_device(mat.data_ptr(), n, n, stride, sols[-1].origin, device=local_rank, stream=stream)
     s0 = sols[-1].stats
     return {

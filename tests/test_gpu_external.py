@@ -104,6 +104,45 @@ def test_bench_sharded_mode_single_rank():
     assert line["scaling"] == "strong" and line["parity_gate"]["residual_rows"] == 0 and line["parity_gate"]["all_solved"]
 
 
+def test_bench_dump_outputs_are_the_last_step(tmp_path):
+    """--dump-outputs: what the timed path returned in its last timed step, as float .npy files.  The headline solve_one at a
+    full-rank size (the planted vector is the only solution, the pivots are every column) with --steps 3, and a batch job whose
+    records are checked against the CPU oracle."""
+    import numpy as np
+
+    from gf2bv_amd import hip
+    from oracle import gf2_oracle as O
+    n, seed = 32768, 1234                                    # bench.FULL_RANK_SEEDS
+    single = tmp_path / "single"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--n", str(n), "--steps", "3", "--warmup", "1", "--no-batch-c4",
+           "--no-extra-legs", "--no-cpu-baseline", "--no-plain-leg", "--target-n", "0", "--dump-outputs", str(single)]
+    out = run_child(cmd, 300)
+    assert out.ok, out.report()
+    line = json.loads([ln for ln in out.out.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["config"]["rank"] == n
+    assert sorted(os.listdir(single)) == ["pivots.npy", "rank.npy", "status.npy", "x.npy"]
+    d = {k: np.load(single / (k + ".npy")) for k in ("x", "status", "rank", "pivots")}
+    assert d["x"].dtype == np.float32 and d["status"].dtype == d["rank"].dtype == d["pivots"].dtype == np.float64
+    planted = np.unpackbits(hip.planted_solution(n, seed).view(np.uint8), bitorder="little")[:n]
+    assert np.array_equal(d["x"], planted) and d["status"].tolist() == [0] and d["rank"].tolist() == [n]
+    assert np.array_equal(d["pivots"], np.arange(n))
+
+    nb, total = 2048, 5
+    job = tmp_path / "batch"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "batch", "--steps", "2", "--warmup", "1",
+           "--batch-total", str(total), "--batch-n", str(nb), "--no-cpu-baseline", "--dump-outputs", str(job)]
+    out = run_child(cmd, 300)
+    assert out.ok, out.report()
+    line = json.loads([ln for ln in out.out.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 2 and line["parity_gate"]["all_ranks_ok"]
+    d = {k: np.load(job / (k + ".npy")) for k in ("x", "status", "rank", "x_systems")}
+    assert d["x"].shape == (total, nb) and np.array_equal(d["x_systems"], np.arange(total))
+    for i in (0, total - 1):                                 # system i: generator seed 5000 + i (bench.BATCH_SEED0)
+        want = O.solve_words(O.gen_synthetic(nb, nb, 5000 + i), nb, nb, 0, algo=1)
+        assert d["status"][i] == want["status"] and d["rank"][i] == want["rank"]
+        assert np.array_equal(d["x"][i], np.unpackbits(np.asarray(want["origin"], dtype=np.uint64).view(np.uint8), bitorder="little")[:nb])
+
+
 def test_bench_two_ranks_sharing_the_gpu():
     """bench.py --gpus 2 exactly as the driver launches it (torch.distributed.run, one process per rank): the default line is
     the N = 1 workload on every rank (weak scaling: one system per GPU per step) plus the configs[3] job sharded over the
@@ -127,26 +166,28 @@ def test_bench_two_ranks_sharing_the_gpu():
     assert c4["systems_per_s"] > 0 and c4["roofline"]["achieved"] > 0
 
 
-def test_bench_eight_ranks_sharing_the_gpu():
-    """Multi-GPU readiness without an 8-GPU node (no scaling curve can be taken here: N > 1 is UNMEASURED on hardware):
-    `bench.py --gpus 8` exactly as the driver launches it -- eight ranks under torch.distributed.run -- all pinned to this
-    box's one GPU with gloo standing in for RCCL, at reduced sizes: the shard bounds of configs[3] at world 8 (64 systems
+def test_bench_three_ranks_sharing_the_gpu():
+    """Multi-GPU readiness without a multi-GPU node (no scaling curve can be taken here: N > 1 is UNMEASURED on hardware):
+    `bench.py --gpus 3` exactly as the driver launches it -- three ranks under torch.distributed.run -- all pinned to this
+    box's one GPU with gloo standing in for RCCL, at reduced sizes: the shard bounds of configs[3] at world 3 (24 systems
     -> 8 per rank, what 512 / 8 = 64 per rank exercises), gang sizing for a rank's share, the order of the gathered records,
-    barriers and max-over-ranks timing, one JSON line from rank 0."""
+    barriers and max-over-ranks timing, one JSON line from rank 0.  Three ranks, not eight: the suite keeps at most six
+    processes on a GPU at once, the pytest process and the launcher included (the world-8 plan of the real job:
+    test_distributed_cpu.py)."""
     env = dict(os.environ, GF2BV_BENCH_DEVICE="0", GF2BV_BENCH_BACKEND="gloo")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-           "--master-port", _free_port(), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
-           "--size", "4096", "--batch-total", "64", "--batch-n", "2048"]
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "3", "--master-addr", "127.0.0.1",
+           "--master-port", _free_port(), os.path.join(ROOT, "bench.py"), "--gpus", "3", "--steps", "2", "--warmup", "1",
+           "--size", "4096", "--batch-total", "24", "--batch-n", "2048"]
     out = run_child(cmd, 600, env=env)
     assert out.ok, out.report()
     lines = [ln for ln in out.out.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
     line = json.loads(lines[0])
-    assert line["n_gpus"] == 8 and line["scaling"] == "weak" and line["parity_gate"]["all_ranks_ok"]
+    assert line["n_gpus"] == 3 and line["scaling"] == "weak" and line["parity_gate"]["all_ranks_ok"]
     assert "cpu_baseline" not in line and "c3_mt19937" not in line and line["value"] > 0
     c4 = line["batch_c4"]
-    assert c4["n_gpus"] == 8 and c4["scaling"] == "strong" and c4["config"]["systems_total"] == 64
-    assert c4["config"]["systems_per_gpu"] == 8 and c4["parity_gate"]["all_ranks_ok"] and c4["parity_gate"]["gathered_records"] == 64
+    assert c4["n_gpus"] == 3 and c4["scaling"] == "strong" and c4["config"]["systems_total"] == 24
+    assert c4["config"]["systems_per_gpu"] == 8 and c4["parity_gate"]["all_ranks_ok"] and c4["parity_gate"]["gathered_records"] == 24
     assert c4["systems_per_s"] > 0
 
 
