@@ -674,6 +674,7 @@ def _rank_profile_properties(n, seed):
     for f, v in zip(free, sp.basis):
         top = int(np.flatnonzero(v)[-1])
         assert 64 * top + int(v[top]).bit_length() - 1 == f                 # nothing right of the free column
+        assert [g for g in free if (int(v[g >> 6]) >> (g & 63)) & 1] == [f]  # S4: zero at every other free column
         assert not (int(sp.origin[f >> 6]) >> (f & 63)) & 1
         assert hip.residual_device(buf.ptr, n, n, stride, sp.origin ^ v) == 0
     buf.free()
