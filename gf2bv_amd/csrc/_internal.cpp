@@ -505,6 +505,91 @@ PyObject *py_m4ri_solve(PyObject *, PyObject *const *args, Py_ssize_t nargs)
 	return result_to_py(res, mode, device);
 }
 
+// m4ri_solve_rhs(equations, cols, mode, rhs, device=None) -> list of (None | int | AffineSpace), one per element of `rhs`.
+// New entry (no counterpart in the reference): many systems that share their coefficient matrix -- the reference factors A alone
+// (gf2bv/_internal.c:398-433) and only then solves against B (:438-455) -- eliminated ONCE (gf2bv_solve_rhs_digits).  `equations`
+// as for m4ri_solve, bit 0 (the affine term) ignored; rhs[j] a non-negative int whose bit r is the affine term of equation r in
+// system j (bits >= rows ignored).  Element j is what m4ri_solve returns for `equations` with their affine terms taken from rhs[j].
+PyObject *py_m4ri_solve_rhs(PyObject *, PyObject *const *args, Py_ssize_t nargs)
+{
+	if (nargs != 4 && nargs != 5) { PyErr_SetString(PyExc_TypeError, "m4ri_solve_rhs requires 4 arguments"); return nullptr; }
+	int device = default_device();
+	if (nargs == 5 && !parse_device(args[4], &device)) return nullptr;
+	PyObject *list = args[0], *rhs = args[3];
+	if (!PyList_Check(list)) {
+		PyErr_SetString(PyExc_TypeError, "The first argument equations must be a list");
+		return nullptr;
+	}
+	if (!PyList_Check(rhs)) {
+		PyErr_SetString(PyExc_TypeError, "The right-hand sides must be a list of integers");
+		return nullptr;
+	}
+	Py_ssize_t cols;
+	long mode;
+	if (!parse_cols_mode(args[1], args[2], &cols, &mode)) return nullptr;
+	const Py_ssize_t rows = PyList_GET_SIZE(list);
+	if (rows < cols) {
+		PyErr_SetString(PyExc_ValueError,
+		                "Number of rows must be greater than or equal to number of columns, try pad with zeros.");
+		return nullptr;
+	}
+	const Py_ssize_t nrhs = PyList_GET_SIZE(rhs);
+	if (nrhs == 0) return PyList_New(0);
+	// right-hand sides -> nrhs x ceil(rows / 64) words (bits >= rows dropped)
+	const int64_t rw = (rows + 63) / 64;
+	std::vector<uint64_t> words;
+	try { words.assign((size_t)nrhs * (size_t)rw, 0); } catch (const std::bad_alloc &) { return PyErr_NoMemory(); }
+	PyObject *zero = PyLong_FromLong(0);
+	if (!zero) return nullptr;
+	for (Py_ssize_t j = 0; j < nrhs; j++) {
+		PyObject *item = PyList_GET_ITEM(rhs, j);
+		if (!PyLong_Check(item)) { Py_DECREF(zero); PyErr_SetString(PyExc_TypeError, "The right-hand sides must be a list of integers"); return nullptr; }
+		const int neg = PyObject_RichCompareBool(item, zero, Py_LT);
+		if (neg) Py_DECREF(zero);
+		if (neg < 0) return nullptr;
+		if (neg) { PyErr_SetString(PyExc_ValueError, "The right-hand sides must be non-negative"); return nullptr; }
+		PyLongObject *v = (PyLongObject *)item;
+		uint64_t *w = words.data() + (size_t)j * (size_t)rw;
+		const Py_ssize_t nd = GF2_DIGIT_COUNT(v);
+		for (Py_ssize_t d = 0; d < nd; d++) {
+			const int64_t bit = (int64_t)d * PyLong_SHIFT;
+			if (bit >= rows) break;
+			const uint64_t x = (uint64_t)GF2_DIGITS(v)[d];
+			w[bit >> 6] |= x << (bit & 63);
+			if ((bit & 63) + PyLong_SHIFT > 64 && (bit >> 6) + 1 < rw) w[(bit >> 6) + 1] |= x >> (64 - (bit & 63));
+		}
+		if (rows & 63) w[rw - 1] &= ((uint64_t)1 << (rows & 63)) - 1;
+	}
+	Py_DECREF(zero);
+	DigitGather dg;
+	dg.off.reserve((size_t)rows + 1); dg.src.reserve((size_t)rows);
+	if (!dg.add(list, cols) || !dg.gather()) return nullptr;
+	std::vector<gf2bv_result *> res((size_t)nrhs, nullptr);
+	int rc;
+	Py_BEGIN_ALLOW_THREADS
+	rc = gf2bv_solve_rhs_digits(dg.digits, dg.off.data(), PyLong_SHIFT, rows, cols, words.data(), nrhs, rw, (int)mode, device, res.data());
+	Py_END_ALLOW_THREADS
+	if (rc != GF2BV_OK) {
+		for (gf2bv_result *r : res) if (r) gf2bv_result_free(r);
+		PyErr_Format(rc == GF2BV_ERR_ARG ? PyExc_ValueError : PyExc_RuntimeError,
+		             "gf2bv_amd: HIP solve failed (%d): %s", rc, gf2bv_last_error());
+		return nullptr;
+	}
+	PyObject *out = PyList_New(nrhs);
+	if (!out) { for (gf2bv_result *r : res) gf2bv_result_free(r); return nullptr; }
+	for (Py_ssize_t j = 0; j < nrhs; j++) {
+		PyObject *v = result_to_py(res[(size_t)j], mode, device);       // (frees the handle)
+		res[(size_t)j] = nullptr;
+		if (!v) {
+			for (Py_ssize_t k = j + 1; k < nrhs; k++) gf2bv_result_free(res[(size_t)k]);
+			Py_DECREF(out);
+			return nullptr;
+		}
+		PyList_SET_ITEM(out, j, v);
+	}
+	return out;
+}
+
 // m4ri_solve_packed(buffer, rows, words, cols, mode) -> None | int | AffineSpace.
 // New entry: the equations arrive ALREADY PACKED -- `rows` x `words` little-endian 64-bit words in the
 // bit order of the equation ints (bit 0 = affine term, bit k = coefficient of variable k-1), e.g. the numpy array a
@@ -992,6 +1077,8 @@ PyMethodDef module_methods[] = {
 	 "m4ri_solve(equations, cols, mode, device=None)\n--\n\nSolve the linear system on the MI355X; None when inconsistent."},
 	{"m4ri_solve_packed", FAST(py_m4ri_solve_packed), METH_FASTCALL,
 	 "m4ri_solve_packed(buffer, rows, words, cols, mode, device=None)\n--\n\nm4ri_solve on equations already packed as rows x words 64-bit words (equation-int bit order)."},
+	{"m4ri_solve_rhs", FAST(py_m4ri_solve_rhs), METH_FASTCALL,
+	 "m4ri_solve_rhs(equations, cols, mode, rhs, device=None)\n--\n\nSolve one coefficient matrix against every right-hand side in rhs (bit r = affine term of equation r) with one elimination; list of m4ri_solve results."},
 	{"m4ri_solve_many", FAST(py_m4ri_solve_many), METH_FASTCALL,
 	 "m4ri_solve_many(systems, cols, mode, devices=None)\n--\n\nSolve a list of same-shape systems in one batched call, sharded over the given GPUs (None: the default device, \"all\": every visible one); list of m4ri_solve results."},
 	{"to_bits", FAST(py_to_bits), METH_FASTCALL, "to_bits(n, a)\n--\n\nLow n bits of a, LSB first."},

@@ -3338,6 +3338,83 @@ k_check_rhs(const u64 *__restrict__ M, i64 rows, i64 srows, i64 cols,
 	if (__ballot(bad) && (threadIdx.x & 63) == 0) st->inconsistent = 1;
 }
 
+// ---- many right-hand sides of one matrix (gf2bv_solve_rhs_*) -------------------------------------------------------------
+// Right-hand side j is column cols + j of the working matrix; the nrw = ceil(((cols & 63) + nrhs) / 64) words from word cols >> 6
+// on hold them (the first of them also the last coefficient bits when cols % 64 != 0).
+
+// OR of a wavefront's 64-bit values (every lane gets the result).
+__device__ __forceinline__ u64 wave_or64(u64 v)
+{
+#pragma unroll
+	for (int m = 32; m >= 1; m >>= 1) {
+		const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, m), hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), m);
+		v |= ((u64)hi << 32) | lo;
+	}
+	return v;
+}
+
+// Consistency of every right-hand side at once (the many-RHS form of k_check_rhs): the alive rows' words that hold RHS columns are
+// OR'd (one wavefront-wide OR, then one atomicOr per wavefront and mask word), and bit j of bad[] (ceil(nrhs / 64) words, zeroed by
+// the caller) ends up set iff system j is inconsistent.  Word k of the RHS words feeds mask word k (its bits from cols & 63 up) and
+// mask word k - 1 (its bits below cols & 63).  grid: x = row chunks, y = RHS word k (strided).
+__global__ void __launch_bounds__(256)
+k_check_rhs_many(const u64 *__restrict__ M, i64 rows, i64 srows, i64 cols, i64 nrhs, const int *__restrict__ died,
+                 u64 *__restrict__ bad)
+{
+	const int s = (int)(cols & 63);
+	const i64 nrw = (s + nrhs + 63) / 64, nmw = (nrhs + 63) / 64;
+	for (i64 k = blockIdx.y; k < nrw; k += gridDim.y) {
+		const i64 q = (cols >> 6) + k;
+		u64 acc = 0;
+		for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += (i64)gridDim.x * blockDim.x)
+			if (died[i] == GF2_NEVER) acc |= M[tidx(i, q, srows)];
+		acc = wave_or64(acc);
+		if ((threadIdx.x & 63) == 0) {
+			if (k < nmw && (acc >> s)) atomicOr(&bad[k], acc >> s);
+			if (s && k >= 1 && (acc << (64 - s))) atomicOr(&bad[k - 1], acc << (64 - s));
+		}
+	}
+}
+
+// Right-hand sides into the tile-major matrix: bit r of rhs[j * rhs_words ..] (row r's affine term in system j) becomes column
+// cols + j of row r.  One wavefront per (64 rows, RHS word k): lane t loads the row-block word of right-hand side 64 m + t, and 64
+// ballots transpose the 64 x 64 bit block (lane i receives row i's bits of right-hand sides 64 m .. 64 m + 63).  Word k takes block
+// k shifted up by cols & 63 and the top of block k - 1; its bits below cols & 63 (coefficients, k = 0) are kept, everything else in
+// the RHS words -- an affine term the coefficient pack left at column `cols`, bits above the last right-hand side -- is overwritten.
+// grid: x = groups of 4 row blocks, y = RHS word k (strided).
+__device__ __forceinline__ u64 rhs_block_transposed(const u64 *__restrict__ rhs, i64 nrhs, i64 rhs_words, i64 m, i64 rb, int lane)
+{
+	if (m < 0 || m * 64 >= nrhs) return 0;
+	const i64 j = m * 64 + lane;
+	const u64 x = j < nrhs ? rhs[j * rhs_words + rb] : 0ull;
+	u64 mine = 0;
+	for (int i = 0; i < 64; i++) {
+		const u64 b = __ballot((x >> i) & 1);
+		if (lane == i) mine = b;
+	}
+	return mine;
+}
+
+__global__ void __launch_bounds__(256)
+k_pack_rhs(const u64 *__restrict__ rhs, i64 nrhs, i64 rhs_words, i64 rows, i64 cols, i64 srows, u64 *__restrict__ M)
+{
+	const int lane = threadIdx.x & 63;
+	const i64 rb = (i64)blockIdx.x * 4 + (threadIdx.x >> 6);          // (wavefront-uniform: the ballots need every lane)
+	if (rb * 64 >= rows) return;
+	const int s = (int)(cols & 63);
+	const i64 nrw = (s + nrhs + 63) / 64, r = rb * 64 + lane;
+	for (i64 k = blockIdx.y; k < nrw; k += gridDim.y) {
+		const u64 cur = rhs_block_transposed(rhs, nrhs, rhs_words, k, rb, lane);
+		u64 v = cur << s;
+		if (s) v |= rhs_block_transposed(rhs, nrhs, rhs_words, k - 1, rb, lane) >> (64 - s);
+		if (r < rows) {
+			u64 &w = M[tidx(r, (cols >> 6) + k, srows)];
+			if (k == 0) v |= w & ((1ull << s) - 1);
+			w = v;
+		}
+	}
+}
+
 // ---- single right-hand side (solve_one): blocked parity back-substitution --------------------
 // With every free variable 0, x[c_k] = y_k ^ parity( U[k][words right of k's panel] & X ), and the
 // pivot rows of one panel are mutually reduced, so a panel's 64 unknowns are independent of each

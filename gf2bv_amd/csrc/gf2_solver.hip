@@ -18,6 +18,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <new>
 #include <mutex>
 #include <string>
@@ -553,6 +554,10 @@ struct Solver {
 	bool own_bs = true;           // (a view) Y / ycols / out are its own; false: `out` points into the gang's (enqueue_backward_gang)
 	SysStride ss() const { return SysStride{ m_stride, (i64)arena_stride }; }
 	int mode = 0;
+	// many right-hand sides of one matrix (gf2bv_solve_rhs_*): right-hand side j is column cols + j, k_check_rhs_many leaves
+	// the per-RHS inconsistency bits in rhs_bad (ceil(nrhs / 64) words); nrhs == 1 with rhs_bad == nullptr: every other entry
+	int nrhs = 1;
+	u64 *rhs_bad = nullptr;
 	bool time_kernels = false;
 	int dbg_sync = 0;
 	const UpdateImpl *impl = nullptr;
@@ -777,7 +782,7 @@ void plan_two_level(Solver &S)
 
 int solver_alloc(Solver &S)
 {
-	S.wt = (S.cols + 1 + 63) / 64;
+	S.wt = (S.cols + S.nrhs + 63) / 64;
 	S.cw = (S.cols + 63) / 64;
 	S.npanels = (int)((S.cols + 63) / 64);
 	S.maxr = std::min(S.rows, S.cols);
@@ -1238,7 +1243,13 @@ int enqueue_forward_join(Solver &S)
 int enqueue_check_rhs(Solver &S)
 {
 	int g = (int)std::min<i64>(1024, (S.rows + 255) / 256);
-	k_check_rhs<<<dim3(g, S.nsys), dim3(256), 0, S.sA>>>(S.M, S.rows, S.srows, S.cols, S.died, S.st, S.ss());
+	if (S.rhs_bad) {
+		const i64 nrw = ((S.cols & 63) + S.nrhs + 63) / 64;
+		k_check_rhs_many<<<dim3(g, (unsigned)std::min<i64>(nrw, 65535)), dim3(256), 0, S.sA>>>(S.M, S.rows, S.srows, S.cols, S.nrhs,
+		                                                                                      S.died, S.rhs_bad);
+	} else {
+		k_check_rhs<<<dim3(g, S.nsys), dim3(256), 0, S.sA>>>(S.M, S.rows, S.srows, S.cols, S.died, S.st, S.ss());
+	}
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipEventRecord(S.ev1, S.sA));
 	return GF2BV_OK;
@@ -1631,28 +1642,35 @@ int solver_enqueue(Solver &S)
 
 // Export, first half: (mode 1: rank and pivot columns to the host, kernel-basis back-substitution,)
 // then the asynchronous device-to-host copies of everything the result needs.
+// The kernel basis needs rank and pivot columns on the host (one sync) to lay out the free columns in M4RI's order
+// (_internal.c:348): S.hst and S.free_order.
+int load_free_order(Solver &S)
+{
+	HIPCHK(hipMemcpyAsync(&S.hst, S.st, sizeof S.hst, hipMemcpyDeviceToHost, S.sA));
+	HIPCHK(hipStreamSynchronize(S.sA));
+	std::vector<int32_t> piv(S.hst.rank);
+	if (S.hst.rank)
+		HIPCHK(hipMemcpy(piv.data(), S.pivcol, sizeof(int) * S.hst.rank, hipMemcpyDeviceToHost));
+	std::vector<int> order(S.cols);
+	for (i64 i = 0; i < S.cols; i++) order[i] = (int)i;
+	for (int i = 0; i < S.hst.rank; i++) std::swap(order[i], order[piv[i]]);
+	S.free_order.assign(order.begin() + S.hst.rank, order.end());
+	return GF2BV_OK;
+}
+
 int finish_begin(Solver &S)
 {
 	HIPCHK(pool().event(&S.evx, true));
 	if (S.mode == GF2BV_MODE_AFFINE_SPACE) {
-		// the kernel basis needs rank and pivot columns on the host (one sync) to lay out
-		// the free columns in M4RI's order (_internal.c:348)
-		HIPCHK(hipMemcpyAsync(&S.hst, S.st, sizeof S.hst, hipMemcpyDeviceToHost, S.sA));
-		HIPCHK(hipStreamSynchronize(S.sA));
-		std::vector<int32_t> piv(S.hst.rank);
-		if (S.hst.rank)
-			HIPCHK(hipMemcpy(piv.data(), S.pivcol, sizeof(int) * S.hst.rank, hipMemcpyDeviceToHost));
-		std::vector<int> order(S.cols);
-		for (i64 i = 0; i < S.cols; i++) order[i] = (int)i;
-		for (int i = 0; i < S.hst.rank; i++) std::swap(order[i], order[piv[i]]);
-		S.free_order.assign(order.begin() + S.hst.rank, order.end());
+		int rc = load_free_order(S);
+		if (rc) return rc;
 		std::vector<int> yc;
 		if (!S.hst.inconsistent) yc = S.free_order;
 		yc.push_back((int)S.cols);
 		// up to GF2_BS_MAXRHS right-hand sides (kernel dimensions of the reference's use: solve_all caps at 16): the parity
 		// path, GF2_BSV of them per pass over U; larger bases: the table sweeps over the bit matrix Y (one pass over Y per
 		// panel whatever the dimension)
-		int rc = ((int)yc.size() <= GF2_BS_MAXRHS && !getenv("GF2BV_YSWEEP")) ? enqueue_backward_parity(S, yc) : enqueue_backward(S, yc);
+		rc = ((int)yc.size() <= GF2_BS_MAXRHS && !getenv("GF2BV_YSWEEP")) ? enqueue_backward_parity(S, yc) : enqueue_backward(S, yc);
 		if (rc) return rc;
 	}
 	HIPCHK(hipMemcpyAsync(&S.hst, S.st, sizeof S.hst, hipMemcpyDeviceToHost, S.sA));
@@ -1665,6 +1683,8 @@ int finish_begin(Solver &S)
 	HIPCHK(hipEventRecord(S.evx, S.sA));
 	return GF2BV_OK;
 }
+
+void fill_stats(const Solver &S, gf2bv_result *R);
 
 // Export, second half: wait for the copies and build the result object.
 int finish_end(Solver &S, gf2bv_result **out)
@@ -1680,10 +1700,8 @@ int finish_end(Solver &S, gf2bv_result **out)
 		return GF2BV_RETRY_EVENTS;
 	}
 	const std::vector<u64> &hout = S.hout;
-	const std::vector<PanelRec> &hp = S.hp;
 	S.hpiv.resize(hst.rank);
 	const std::vector<int32_t> &piv = S.hpiv;
-	hipEvent_t evx = S.evx;
 
 	gf2bv_result *R = new gf2bv_result();
 	R->status = hst.inconsistent ? GF2BV_STATUS_INCONSISTENT : GF2BV_STATUS_SOLVED;
@@ -1705,6 +1723,18 @@ int finish_end(Solver &S, gf2bv_result **out)
 			}
 		}
 	}
+	fill_stats(S, R);
+	tr.mark("finish: result");
+	*out = R;
+	return GF2BV_OK;
+}
+
+// The stats of a finished solve (its streams synchronised, S.hst / S.hp on the host) into R, whose status, rank and dimension are set.
+void fill_stats(const Solver &S, gf2bv_result *R)
+{
+	const SolveState &hst = S.hst;
+	const std::vector<PanelRec> &hp = S.hp;
+	const hipEvent_t evx = S.evx;
 	gf2bv_stats &st = R->stats;
 	st.rows = S.rows; st.cols = S.cols; st.stride_words = S.stride;
 	st.rank = R->rank; st.dimension = R->dim; st.status = R->status;
@@ -1764,9 +1794,6 @@ int finish_end(Solver &S, gf2bv_result **out)
 		if (hi >= 0) st.ms_sweep += hi - lo;
 	}
 	st.ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - S.t_begin).count();
-	tr.mark("finish: result");
-	*out = R;
-	return GF2BV_OK;
 }
 
 int solver_finish(Solver &S, gf2bv_result **out)
@@ -2062,6 +2089,172 @@ int small_solve(const SmallInput &in, i64 rows, i64 cols, int mode, int device, 
 	s.small_path = 1;
 	s.ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
 	*out = R;
+	return GF2BV_OK;
+}
+
+// ---- many right-hand sides of one matrix: ONE elimination for all of them ---------------------------------------------------
+// The reference factors A alone -- A (rows x cols) and B (rows x 1) are separate mzd_t, _mzd_pluq(A, P, Q) runs on A
+// (_internal.c:398-433), and only then is B solved against (:438-455) -- so pivots, the origin rule (free variables 0) and the
+// kernel basis depend on A only; a right-hand side decides consistency and the origin.  Here right-hand side j is column cols + j
+// of the working matrix (ceil((cols + nrhs) / 64) words per row): the elimination carries every one of them along, k_check_rhs_many
+// decides every system's consistency, and one back-substitution over U yields every origin (mode 1: and the kernel basis, once).
+// Scope: one system on one device (no gangs, no column slabs); every size takes the blocked path -- k_small_solve's LDS budget
+// assumes one RHS bit.
+struct RhsInput {              // matrix: d_words (device) | h_words (host) | h_digits + h_off (host); right-hand sides: host or device
+	const u64 *d_words = nullptr, *h_words = nullptr;
+	i64 stride = 0;
+	const uint32_t *h_digits = nullptr;
+	const i64 *h_off = nullptr;
+	int bpd = 0;
+	const u64 *rhs = nullptr;
+	bool rhs_on_device = false;
+	i64 nrhs = 0, rhs_words = 0;
+};
+
+// the argument checks every gf2bv_solve_rhs_* entry makes before it touches a device; clears out[0..nrhs)
+int check_rhs_args(i64 rows, i64 cols, int mode, const void *rhs, i64 nrhs, i64 rhs_words, gf2bv_result **out)
+{
+	if (!out || !rhs) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (nrhs < 1) return fail(GF2BV_ERR_ARG, "nrhs must be at least 1");
+	for (i64 j = 0; j < nrhs; j++) out[j] = nullptr;
+	int rc = check_shape(rows, cols, mode);
+	if (rc) return rc;
+	if (nrhs >= (1ll << 31) - 64 - cols) return fail(GF2BV_ERR_ARG, "too many right-hand sides");
+	if (rhs_words < (rows + 63) / 64) return fail(GF2BV_ERR_ARG, "rhs_words does not cover one bit per row");
+	return GF2BV_OK;
+}
+
+int solve_rhs(const RhsInput &in, i64 rows, i64 cols, int mode, int device, hipStream_t stream, bool time_kernels, gf2bv_result **out)
+{
+	const i64 nrhs = in.nrhs, cw = (cols + 63) / 64, cwx = std::max<i64>(1, cw), nmw = (nrhs + 63) / 64;
+	const i64 wt = (cols + nrhs + 63) / 64, ntiles = tiles_for(wt), srows = slab_rows(rows);
+	const i64 rw = (rows + 63) / 64, nrw = ((cols & 63) + nrhs + 63) / 64;
+	Solver S;
+	S.t_begin = std::chrono::steady_clock::now();
+	S.device = device;
+	if (in.d_words) S.sA = stream;
+	else { HIPCHK(pool().stream(&S.sA, device, false)); S.own_sA = true; }
+	S.rows = rows; S.cols = cols; S.mode = mode; S.nrhs = (int)nrhs;
+	S.time_kernels = time_kernels;
+	S.stride = in.h_digits ? ntiles * TW : in.stride;
+	{
+		const hipError_t e = pool().alloc((void **)&S.M, sizeof(u64) * ntiles * TW * srows + kOuterSlackBytes, device);
+		if (e == hipErrorOutOfMemory) {
+			(void)hipGetLastError();
+			return fail(GF2BV_ERR_NOMEM, "the matrix widened by the right-hand sides does not fit on the device");
+		}
+		if (e != hipSuccess) return fail(GF2BV_ERR_HIP, "working matrix", e);
+	}
+	Scratch scratch;                  // (declared after S: released first, after synchronising the solve's stream)
+	scratch.sync_first = S.sA;
+	HIPCHK(scratch.alloc((void **)&S.rhs_bad, sizeof(u64) * nmw, device));
+	hipEvent_t p0, p1;
+	HIPCHK(scratch.event(&p0)); HIPCHK(scratch.event(&p1));
+	HIPCHK(hipEventRecord(p0, S.sA));
+	HIPCHK(hipMemsetAsync(S.rhs_bad, 0, sizeof(u64) * nmw, S.sA));
+	// coefficients: the digits packed straight into tiles (k_pack_digits puts the affine term at column `cols`; k_pack_rhs overwrites
+	// it), or the words that hold coefficients -- and only those -- copied into tiles (the words right of them are zero-filled)
+	if (in.h_digits) {
+		const i64 ndig = in.h_off[rows];
+		uint32_t *d_dig = nullptr;
+		i64 *d_off = nullptr;
+		HIPCHK(scratch.alloc((void **)&d_dig, sizeof(uint32_t) * std::max<i64>(1, ndig), device));
+		HIPCHK(scratch.alloc((void **)&d_off, sizeof(i64) * (rows + 1), device));
+		if (ndig) HIPCHK(hipMemcpyAsync(d_dig, in.h_digits, sizeof(uint32_t) * ndig, hipMemcpyHostToDevice, S.sA));
+		HIPCHK(hipMemcpyAsync(d_off, in.h_off, sizeof(i64) * (rows + 1), hipMemcpyHostToDevice, S.sA));
+		k_pack_digits<<<dim3((unsigned)((ntiles * TW + 255) / 256), (unsigned)std::min<i64>(rows, 65535)), dim3(256), 0, S.sA>>>(
+			d_dig, d_off, in.bpd, rows, cols, ntiles * TW, srows, S.M, SysStride{0, 0}, (i64)0);
+	} else {
+		const u64 *src = in.d_words;
+		i64 sstride = in.stride;
+		if (in.h_words) {
+			sstride = round_up(cw, 2);
+			u64 *tmp = nullptr;
+			HIPCHK(scratch.alloc((void **)&tmp, sizeof(u64) * rows * sstride, device));
+			HIPCHK(hipMemcpy2DAsync(tmp, sstride * 8, in.h_words, in.stride * 8, cw * 8, rows, hipMemcpyHostToDevice, S.sA));
+			src = tmp;
+		}
+		k_to_tiled<<<dim3((unsigned)rw, (unsigned)((ntiles + 15) / 16)), dim3(256), 0, S.sA>>>(src, sstride, rows, ntiles, cw, srows, S.M,
+		                                                                                      (i64)0, SysStride{0, 0});
+	}
+	const u64 *d_rhs = in.rhs;
+	i64 rhs_stride = in.rhs_words;
+	if (!in.rhs_on_device) {          // (only the words that hold rows go up)
+		u64 *d = nullptr;
+		HIPCHK(scratch.alloc((void **)&d, sizeof(u64) * nrhs * rw, device));
+		HIPCHK(hipMemcpy2DAsync(d, rw * 8, in.rhs, in.rhs_words * 8, rw * 8, nrhs, hipMemcpyHostToDevice, S.sA));
+		d_rhs = d; rhs_stride = rw;
+	}
+	k_pack_rhs<<<dim3((unsigned)((rw + 3) / 4), (unsigned)std::min<i64>(nrw, 65535)), dim3(256), 0, S.sA>>>(d_rhs, nrhs, rhs_stride, rows, cols,
+	                                                                                                  srows, S.M);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(p1, S.sA));
+	int rc = solver_alloc(S);         // (S.src is null: the matrix is in place)
+	if (rc) return rc;
+	rc = enqueue_forward(S);
+	if (rc) return rc;
+	// back-substitution: Y columns = [free columns in M4RI order (mode 1, once, when some system is consistent)] + every RHS column
+	std::vector<u64> bad((size_t)nmw, 0);
+	std::vector<int> yc;
+	if (mode == GF2BV_MODE_AFFINE_SPACE) {
+		if ((rc = load_free_order(S))) return rc;            // (synchronises the stream: the mask is complete)
+		HIPCHK(hipMemcpy(bad.data(), S.rhs_bad, sizeof(u64) * nmw, hipMemcpyDeviceToHost));
+		bool any_ok = false;
+		for (i64 j = 0; j < nrhs && !any_ok; j++) any_ok = !((bad[(size_t)(j >> 6)] >> (j & 63)) & 1);
+		if (any_ok) yc = S.free_order;
+	}
+	const i64 nbasis = (i64)yc.size();
+	for (i64 j = 0; j < nrhs; j++) yc.push_back((int)(cols + j));
+	// (the threshold of finish_begin: up to GF2_BS_MAXRHS columns the parity passes, GF2_BSV at a time; beyond, the sweeps over Y)
+	rc = ((i64)yc.size() <= GF2_BS_MAXRHS && !getenv("GF2BV_YSWEEP")) ? enqueue_backward_parity(S, yc) : enqueue_backward(S, yc);
+	if (rc) return rc;
+	// export
+	HIPCHK(pool().event(&S.evx, true));
+	HIPCHK(hipMemcpyAsync(&S.hst, S.st, sizeof S.hst, hipMemcpyDeviceToHost, S.sA));
+	S.hout.resize((size_t)S.ny * cwx);
+	HIPCHK(hipMemcpyAsync(S.hout.data(), S.out, sizeof(u64) * S.hout.size(), hipMemcpyDeviceToHost, S.sA));
+	S.hp.resize(std::max(1, S.npanels));
+	HIPCHK(hipMemcpyAsync(S.hp.data(), S.panels, sizeof(PanelRec) * S.hp.size(), hipMemcpyDeviceToHost, S.sA));
+	S.hpiv.resize(std::max<i64>(1, S.maxr));
+	HIPCHK(hipMemcpyAsync(S.hpiv.data(), S.pivcol, sizeof(int) * S.hpiv.size(), hipMemcpyDeviceToHost, S.sA));
+	HIPCHK(hipMemcpyAsync(bad.data(), S.rhs_bad, sizeof(u64) * nmw, hipMemcpyDeviceToHost, S.sA));
+	HIPCHK(hipEventRecord(S.evx, S.sA));
+	HIPCHK(hipStreamSynchronize(S.sA));
+	HIPCHK(hipStreamSynchronize(S.sB));
+	if (S.hst.gate_timeout) {
+		if (!S.flag_sync) return fail(GF2BV_ERR_HIP, "a stream hand-over gate timed out on the device");
+		forget_concurrency(S.device);
+		return GF2BV_RETRY_EVENTS;
+	}
+	(void)hipEventElapsedTime(&S.ms_pack, p0, p1);
+	S.hpiv.resize(S.hst.rank);
+	std::vector<std::unique_ptr<gf2bv_result>> res((size_t)nrhs);
+	for (i64 j = 0; j < nrhs; j++) {
+		res[(size_t)j].reset(new gf2bv_result());
+		gf2bv_result *R = res[(size_t)j].get();
+		const bool ok = !((bad[(size_t)(j >> 6)] >> (j & 63)) & 1);
+		R->status = ok ? GF2BV_STATUS_SOLVED : GF2BV_STATUS_INCONSISTENT;
+		R->rank = S.hst.rank;
+		R->cw = cw;
+		R->dim = cols - S.hst.rank;
+		R->pivots = S.hpiv;
+		R->origin.assign((size_t)cwx, 0);
+		if (ok) {
+			const u64 *o = S.hout.data() + (size_t)(nbasis + j) * cwx;
+			std::copy(o, o + cw, R->origin.begin());
+			if (mode == GF2BV_MODE_AFFINE_SPACE) {           // (nbasis == dim: some system is consistent)
+				R->basis.assign((size_t)R->dim * cwx, 0);
+				for (i64 t = 0; t < R->dim; t++) {
+					u64 *v = R->basis.data() + (size_t)t * cw;
+					std::copy(S.hout.data() + (size_t)t * cwx, S.hout.data() + (size_t)t * cwx + cw, v);
+					const int f = S.free_order[(size_t)t];
+					v[f >> 6] |= 1ull << (f & 63);
+				}
+			}
+		}
+		fill_stats(S, R);
+	}
+	for (i64 j = 0; j < nrhs; j++) out[j] = res[(size_t)j].release();
 	return GF2BV_OK;
 }
 
@@ -2476,6 +2669,63 @@ int gf2bv_solve_digits(const uint32_t *digits, const int64_t *digit_off, int bit
 		rc = solver_finish(S, out);
 	}
 	return rc;
+	});
+}
+
+// Many right-hand sides of one matrix (_internal.c:398-455: the reference factors A alone, then solves against B): see solve_rhs.
+int gf2bv_solve_rhs_digits(const uint32_t *digits, const int64_t *digit_off, int bits_per_digit, int64_t rows, int64_t cols,
+                           const uint64_t *rhs, int64_t nrhs, int64_t rhs_words, int mode, int device, gf2bv_result **out)
+{
+	return guarded([&]() -> int {
+	int rc = check_rhs_args(rows, cols, mode, rhs, nrhs, rhs_words, out);
+	if (rc) return rc;
+	if (!digit_off) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (bits_per_digit < 1 || bits_per_digit > 32) return fail(GF2BV_ERR_ARG, "bits_per_digit must be 1..32");
+	if (digit_off[0] != 0) return fail(GF2BV_ERR_ARG, "digit offsets must start at 0");
+	for (i64 r = 0; r < rows; r++)
+		if (digit_off[r + 1] < digit_off[r]) return fail(GF2BV_ERR_ARG, "digit offsets must not decrease");
+	if (!digits && digit_off[rows] > 0) return fail(GF2BV_ERR_ARG, "null pointer");
+	rc = check_device(device);
+	if (rc) return rc;
+	RhsInput in;
+	in.h_digits = digits; in.h_off = reinterpret_cast<const i64 *>(digit_off); in.bpd = bits_per_digit;
+	in.rhs = reinterpret_cast<const u64 *>(rhs); in.nrhs = nrhs; in.rhs_words = rhs_words;
+	return solve_rhs(in, rows, cols, mode, device, nullptr, false, out);
+	});
+}
+
+int gf2bv_solve_rhs_words(const uint64_t *aug, int64_t rows, int64_t cols, int64_t stride_words,
+                          const uint64_t *rhs, int64_t nrhs, int64_t rhs_words, int mode, int device, gf2bv_result **out)
+{
+	return guarded([&]() -> int {
+	int rc = check_rhs_args(rows, cols, mode, rhs, nrhs, rhs_words, out);
+	if (rc) return rc;
+	if (!aug) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (stride_words < (cols + 1 + 63) / 64) return fail(GF2BV_ERR_ARG, "stride_words does not cover cols+1 bits");
+	rc = check_device(device);
+	if (rc) return rc;
+	RhsInput in;
+	in.h_words = reinterpret_cast<const u64 *>(aug); in.stride = stride_words;
+	in.rhs = reinterpret_cast<const u64 *>(rhs); in.nrhs = nrhs; in.rhs_words = rhs_words;
+	return solve_rhs(in, rows, cols, mode, device, nullptr, false, out);
+	});
+}
+
+int gf2bv_solve_rhs_device(void *d_aug, int64_t rows, int64_t cols, int64_t stride_words, const void *d_rhs, int64_t nrhs,
+                           int64_t rhs_words, int mode, int device, void *stream, int time_kernels, gf2bv_result **out)
+{
+	return guarded([&]() -> int {
+	int rc = check_rhs_args(rows, cols, mode, d_rhs, nrhs, rhs_words, out);
+	if (rc) return rc;
+	if (!d_aug) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (stride_words % 2 != 0 || stride_words < (cols + 1 + 63) / 64 || ((uintptr_t)d_aug & 15) || ((uintptr_t)d_rhs & 7))
+		return fail(GF2BV_ERR_ARG, "device matrix needs 16-byte alignment and an even stride_words covering cols+1 bits, the right-hand sides 8-byte alignment");
+	rc = check_device(device);
+	if (rc) return rc;
+	RhsInput in;
+	in.d_words = (const u64 *)d_aug; in.stride = stride_words;
+	in.rhs = (const u64 *)d_rhs; in.rhs_on_device = true; in.nrhs = nrhs; in.rhs_words = rhs_words;
+	return solve_rhs(in, rows, cols, mode, device, (hipStream_t)stream, time_kernels != 0, out);
 	});
 }
 

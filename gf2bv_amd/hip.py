@@ -27,6 +27,7 @@ EXPORTS = [
     "gf2bv_version", "gf2bv_build_id", "gf2bv_device_count", "gf2bv_last_error",
     "gf2bv_solve_digits", "gf2bv_solve_words", "gf2bv_solve_device", "gf2bv_solve_batch_device",
     "gf2bv_solve_batch_digits", "gf2bv_solve_batch_digits_multi",
+    "gf2bv_solve_rhs_digits", "gf2bv_solve_rhs_words", "gf2bv_solve_rhs_device",
     "gf2bv_result_status", "gf2bv_result_rank", "gf2bv_result_dimension", "gf2bv_result_words",
     "gf2bv_result_origin", "gf2bv_result_basis", "gf2bv_result_pivots", "gf2bv_result_stats",
     "gf2bv_result_free", "gf2bv_space_combine", "gf2bv_space_open", "gf2bv_space_enumerate", "gf2bv_space_buffer", "gf2bv_space_close",
@@ -83,6 +84,9 @@ def lib():
         L.gf2bv_solve_batch_device.argtypes = [vp, i64, i64, i64, i64, i64, i32, i32, vp, i32, pp]
         L.gf2bv_solve_batch_digits.argtypes = [vp, vp, i32, i64, i64, i64, i32, i32, pp]
         L.gf2bv_solve_batch_digits_multi.argtypes = [vp, vp, i32, i64, i64, i64, i32, vp, i32, pp]
+        L.gf2bv_solve_rhs_digits.argtypes = [vp, vp, i32, i64, i64, vp, i64, i64, i32, i32, pp]
+        L.gf2bv_solve_rhs_words.argtypes = [vp, i64, i64, i64, vp, i64, i64, i32, i32, pp]
+        L.gf2bv_solve_rhs_device.argtypes = [vp, i64, i64, i64, vp, i64, i64, i32, i32, vp, i32, pp]
         for name, res in (("gf2bv_result_status", i32), ("gf2bv_result_rank", i64),
                           ("gf2bv_result_dimension", i64), ("gf2bv_result_words", i64)):
             getattr(L, name).restype = res
@@ -280,6 +284,48 @@ def solve_batch_words(augs, rows: int, cols: int, mode: int = MODE_SINGLE, devic
         return solve_batch_device(buf.ptr, nsys, rows * stride, rows, cols, stride, mode, device)
     finally:
         buf.free()
+
+
+def _rhs_array(rhs: np.ndarray) -> np.ndarray:
+    rhs = np.ascontiguousarray(rhs, dtype=np.uint64)
+    if rhs.ndim == 1:
+        rhs = rhs.reshape(1, -1)
+    return rhs
+
+
+def solve_rhs_words(aug: np.ndarray, rows: int, cols: int, rhs: np.ndarray, mode: int = MODE_SINGLE, device: int = 0) -> list:
+    """Many right-hand sides of one matrix, one elimination (gf2bv_solve_rhs_words).  aug: the augmented matrix as for
+    solve_words (its column `cols` is ignored); rhs: [nrhs, >= ceil(rows / 64)] uint64, bit r of row j = affine term of
+    equation r in system j.  Element j is what solve_words returns for the matrix with right-hand side j."""
+    aug = np.ascontiguousarray(aug, dtype=np.uint64)
+    stride = aug.shape[1] if aug.ndim == 2 else (cols + 1 + 63) // 64
+    rhs = _rhs_array(rhs)
+    nrhs = rhs.shape[0]
+    hs = (ctypes.c_void_p * max(nrhs, 1))()
+    rc = lib().gf2bv_solve_rhs_words(aug.ctypes.data, rows, cols, stride, rhs.ctypes.data, nrhs, rhs.shape[1], mode, device, hs)
+    return _take_all(hs, nrhs, rc, mode)
+
+
+def solve_rhs_digits(digits: np.ndarray, offsets: np.ndarray, bits_per_digit: int, rows: int, cols: int, rhs: np.ndarray,
+                     mode: int = MODE_SINGLE, device: int = 0) -> list:
+    """solve_rhs_words with the matrix given as digit arrays (see solve_digits; bit 0 of every equation is ignored)."""
+    digits = np.ascontiguousarray(digits, dtype=np.uint32)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    rhs = _rhs_array(rhs)
+    nrhs = rhs.shape[0]
+    hs = (ctypes.c_void_p * max(nrhs, 1))()
+    rc = lib().gf2bv_solve_rhs_digits(digits.ctypes.data, offsets.ctypes.data, bits_per_digit, rows, cols, rhs.ctypes.data, nrhs,
+                                      rhs.shape[1], mode, device, hs)
+    return _take_all(hs, nrhs, rc, mode)
+
+
+def solve_rhs_device(d_ptr: int, rows: int, cols: int, stride: int, d_rhs: int, nrhs: int, rhs_words: int,
+                     mode: int = MODE_SINGLE, device: int = 0, stream: int = 0, time_kernels: bool = False) -> list:
+    """solve_rhs_words with matrix and right-hand sides resident in device memory (both left untouched)."""
+    hs = (ctypes.c_void_p * max(nrhs, 1))()
+    rc = lib().gf2bv_solve_rhs_device(d_ptr, rows, cols, stride, d_rhs, nrhs, rhs_words, mode, device, stream or None,
+                                      1 if time_kernels else 0, hs)
+    return _take_all(hs, max(nrhs, 0), rc, mode)
 
 
 def space_enumerate(origin: np.ndarray, basis: np.ndarray, first: int, count: int, gray: bool = True,

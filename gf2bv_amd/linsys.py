@@ -9,7 +9,7 @@ from __future__ import annotations
 
 from typing import Iterable, Optional, Sequence, Union
 
-from ._internal import AffineSpace, eqs_to_sage_mat_helper, m4ri_solve, m4ri_solve_many, mul_bit_quad
+from ._internal import AffineSpace, eqs_to_sage_mat_helper, m4ri_solve, m4ri_solve_many, m4ri_solve_rhs, mul_bit_quad
 from .bitvec import BitVec
 
 Zeros = Sequence[Union[BitVec, int]]
@@ -157,6 +157,62 @@ class LinearSystem:
         return [None if raw is None else self.convert_sol(raw)
                 for raw in self._solve_internal_many(zeros_list, 0, devices)]
 
+    # -- many right-hand sides of one matrix (no counterpart in the reference) -------------------------------------------
+    # Instances that share every coefficient and differ only in constants -- the recovery workloads' outputs enter only as
+    # `expr ^ observed` -- go to the GPU as ONE elimination: _internal.m4ri_solve_rhs -> gf2bv_solve_rhs_digits.  Element i of
+    # the result is exactly what the single-system method returns for [e ^ v for e, v in zip(exprs, values_list[i])].
+    def _rhs_eqs(self, exprs: Zeros, values_list: Sequence[Sequence[int]]):
+        """exprs flattened once into equation ints, and one right-hand-side int per instance: bit r = the constant term of
+        equation r in that instance (exprs[k] ^ values_list[i][k], as BitVec.__xor__ / int ^ would form it).  Rows whose
+        coefficient part is zero are kept: with constant 1 such a row is the equation "1 = 0" and the solver reports exactly
+        that instance inconsistent (_solve_internal's `1 in eqs`), with constant 0 it is the literal zero get_eqs drops --
+        an all-zero row changes no pivot, origin or basis."""
+        eqs: list = []
+        spans: list = []                       # per element of exprs: (first row, width) -- width None: an equation int
+        for e in exprs:
+            if isinstance(e, BitVec):
+                spans.append((len(eqs), len(e._bits)))
+                eqs.extend(e._bits)
+            else:
+                spans.append((len(eqs), None))
+                eqs.append(e)
+        consts = 0
+        for r, e in enumerate(eqs):
+            if e & 1:
+                consts |= 1 << r
+        rhs = []
+        for vals in values_list:
+            vals = list(vals)
+            if len(vals) != len(spans):
+                raise ValueError(f"{len(vals)} values for {len(spans)} expressions")
+            b = consts
+            for (at, width), v in zip(spans, vals):
+                if width is None:
+                    if v not in (0, 1):
+                        raise ValueError("the value of an equation int must be 0 or 1")
+                    b ^= int(v) << at
+                else:
+                    b ^= (abs(v) & ((1 << width) - 1)) << at          # (to_bits: the low `width` bits of |v|)
+            rhs.append(b)
+        return eqs, rhs
+
+    def _solve_internal_rhs(self, exprs: Zeros, values_list: Sequence[Sequence[int]], mode: int) -> list:
+        eqs, rhs = self._rhs_eqs(exprs, values_list)
+        if not rhs:
+            return []
+        if len(eqs) < self._cols:               # the boundary wants rows >= cols (zero rows, constant 0 in every instance)
+            eqs.extend([0] * (self._cols - len(eqs)))
+        return m4ri_solve_rhs(eqs, self._cols, mode, rhs)
+
+    def solve_raw_one_rhs(self, exprs: Zeros, values_list: Sequence[Sequence[int]]) -> list:
+        return self._solve_internal_rhs(exprs, values_list, 0)
+
+    def solve_raw_space_rhs(self, exprs: Zeros, values_list: Sequence[Sequence[int]]) -> list:
+        return self._solve_internal_rhs(exprs, values_list, 1)
+
+    def solve_one_rhs(self, exprs: Zeros, values_list: Sequence[Sequence[int]]) -> list:
+        return [None if raw is None else self.convert_sol(raw) for raw in self._solve_internal_rhs(exprs, values_list, 0)]
+
     def evaluate(self, bv: BitVec, sol: tuple) -> int:
         raw, shift = 0, 0
         for value, width in zip(sol, self._sizes):
@@ -254,6 +310,26 @@ class QuadraticSystem(LinearSystem):
         for sol in self.solve_all(zeros):
             return sol
         return None
+
+    def solve_one_rhs(self, exprs: Zeros, values_list: Sequence[Sequence[int]], *, max_dimension: int = 16) -> list:
+        """solve_one for every instance (the first element of its solve_all that passes convert_sol, None if there is none),
+        from ONE elimination (solve_raw_space_rhs); DimensionTooLargeError as solve_all raises it."""
+        out = []
+        for space in self.solve_raw_space_rhs(exprs, values_list):
+            sol = None
+            if space is not None:
+                if space.dimension > max_dimension:
+                    raise DimensionTooLargeError(
+                        f"Solution space (dim {space.dimension}) is too large, try increase max_dimension "
+                        f"({max_dimension}) if you want (there will be 2**dim solutions)",
+                        space=space,
+                    )
+                for raw in space:
+                    sol = self.convert_sol(raw)
+                    if sol is not None:
+                        break
+            out.append(sol)
+        return out
 
     def evaluate(self, bv: BitVec, sol: tuple) -> int:
         raw, shift = 0, 0

@@ -111,6 +111,28 @@ int gf2bv_solve_words(const uint64_t *aug, int64_t rows, int64_t cols, int64_t s
 int gf2bv_solve_device(void *d_aug, int64_t rows, int64_t cols, int64_t stride_words,
                        int mode, int device, void *stream, int time_kernels, gf2bv_result **out);
 
+/* ---- many right-hand sides of ONE matrix, one elimination (gf2bv/_internal.c:398-455) ------------------------------------
+ * The reference builds A (rows x cols) and B (rows x 1) as separate mzd_t, factors A alone (_mzd_pluq, :429-433) and only then
+ * solves against B (:438-455): pivots, the origin rule (free variables 0) and the kernel basis depend on A only.  These entries
+ * eliminate A once with every right-hand side carried along as an extra column (right-hand side j = column cols + j of the
+ * working matrix, ceil((cols + nrhs) / 64) words per row), then decide each system's consistency and back-substitute all of them
+ * in one pass over U (mode 1: the kernel basis is computed once, when at least one system is consistent).
+ * rhs: nrhs rows of rhs_words >= ceil(rows/64) uint64; bit r of row j = affine term of equation r in system j (bits >= rows
+ * ignored).  The affine term of the matrix input (digit bit 0 / column `cols`) is ignored.  out[0..nrhs) receives one handle
+ * per system, each identical to what gf2bv_solve_digits/_words/_device returns for that system alone (status, rank, pivots,
+ * dimension, origin, basis); every handle carries the shared solve's stats.
+ * Argument errors (null pointers, nrhs < 1, rhs_words < ceil(rows/64), the shape rules of the single entries) return
+ * GF2BV_ERR_ARG before any device is touched; a widened matrix that does not fit on the device returns GF2BV_ERR_NOMEM.
+ * Scope: one system on one device -- no gangs, no column slabs; every size takes the blocked path (no one-launch small path). */
+int gf2bv_solve_rhs_digits(const uint32_t *digits, const int64_t *digit_off, int bits_per_digit, int64_t rows, int64_t cols,
+                           const uint64_t *rhs, int64_t nrhs, int64_t rhs_words, int mode, int device, gf2bv_result **out);
+int gf2bv_solve_rhs_words(const uint64_t *aug, int64_t rows, int64_t cols, int64_t stride_words,
+                          const uint64_t *rhs, int64_t nrhs, int64_t rhs_words, int mode, int device, gf2bv_result **out);
+/* d_aug as in gf2bv_solve_device (16-byte aligned, even stride_words); d_rhs: device memory, 8-byte aligned, read after
+ * everything enqueued on `stream` before the call. */
+int gf2bv_solve_rhs_device(void *d_aug, int64_t rows, int64_t cols, int64_t stride_words, const void *d_rhs, int64_t nrhs,
+                           int64_t rhs_words, int mode, int device, void *stream, int time_kernels, gf2bv_result **out);
+
 /* Batch of `nsys` independent equal-shape systems resident on one device
  * (system s starts at d_aug + s*sys_stride_words words); out[0..nsys) receives handles.
  * The systems run in lock-step "gangs": one set of kernel launches eliminates a whole gang
