@@ -505,6 +505,57 @@ PyObject *py_m4ri_solve(PyObject *, PyObject *const *args, Py_ssize_t nargs)
 	return result_to_py(res, mode, device);
 }
 
+// right-hand sides (a list of non-negative ints, bit r = affine term of equation r) -> len(rhs) x ceil(rows / 64) words, bits >= rows
+// dropped (m4ri_solve_rhs, Factorization.solve)
+bool rhs_list_words(PyObject *rhs, Py_ssize_t rows, std::vector<uint64_t> &words)
+{
+	const Py_ssize_t nrhs = PyList_GET_SIZE(rhs);
+	const int64_t rw = (rows + 63) / 64;
+	try { words.assign((size_t)nrhs * (size_t)rw, 0); } catch (const std::bad_alloc &) { PyErr_NoMemory(); return false; }
+	PyObject *zero = PyLong_FromLong(0);
+	if (!zero) return false;
+	for (Py_ssize_t j = 0; j < nrhs; j++) {
+		PyObject *item = PyList_GET_ITEM(rhs, j);
+		if (!PyLong_Check(item)) { Py_DECREF(zero); PyErr_SetString(PyExc_TypeError, "The right-hand sides must be a list of integers"); return false; }
+		const int neg = PyObject_RichCompareBool(item, zero, Py_LT);
+		if (neg) Py_DECREF(zero);
+		if (neg < 0) return false;
+		if (neg) { PyErr_SetString(PyExc_ValueError, "The right-hand sides must be non-negative"); return false; }
+		PyLongObject *v = (PyLongObject *)item;
+		uint64_t *w = words.data() + (size_t)j * (size_t)rw;
+		const Py_ssize_t nd = GF2_DIGIT_COUNT(v);
+		for (Py_ssize_t d = 0; d < nd; d++) {
+			const int64_t bit = (int64_t)d * PyLong_SHIFT;
+			if (bit >= rows) break;
+			const uint64_t x = (uint64_t)GF2_DIGITS(v)[d];
+			w[bit >> 6] |= x << (bit & 63);
+			if ((bit & 63) + PyLong_SHIFT > 64 && (bit >> 6) + 1 < rw) w[(bit >> 6) + 1] |= x >> (64 - (bit & 63));
+		}
+		if (rows & 63) w[rw - 1] &= ((uint64_t)1 << (rows & 63)) - 1;
+	}
+	Py_DECREF(zero);
+	return true;
+}
+
+// result handles -> list of None / int / AffineSpace; frees every handle (also on failure)
+PyObject *results_to_list(std::vector<gf2bv_result *> &res, long mode, int device)
+{
+	const Py_ssize_t n = (Py_ssize_t)res.size();
+	PyObject *out = PyList_New(n);
+	if (!out) { for (gf2bv_result *r : res) gf2bv_result_free(r); return nullptr; }
+	for (Py_ssize_t j = 0; j < n; j++) {
+		PyObject *v = result_to_py(res[(size_t)j], mode, device);       // (frees the handle)
+		res[(size_t)j] = nullptr;
+		if (!v) {
+			for (Py_ssize_t k = j + 1; k < n; k++) gf2bv_result_free(res[(size_t)k]);
+			Py_DECREF(out);
+			return nullptr;
+		}
+		PyList_SET_ITEM(out, j, v);
+	}
+	return out;
+}
+
 // m4ri_solve_rhs(equations, cols, mode, rhs, device=None) -> list of (None | int | AffineSpace), one per element of `rhs`.
 // New entry (no counterpart in the reference): many systems that share their coefficient matrix -- the reference factors A alone
 // (gf2bv/_internal.c:398-433) and only then solves against B (:438-455) -- eliminated ONCE (gf2bv_solve_rhs_digits).  `equations`
@@ -535,32 +586,9 @@ PyObject *py_m4ri_solve_rhs(PyObject *, PyObject *const *args, Py_ssize_t nargs)
 	}
 	const Py_ssize_t nrhs = PyList_GET_SIZE(rhs);
 	if (nrhs == 0) return PyList_New(0);
-	// right-hand sides -> nrhs x ceil(rows / 64) words (bits >= rows dropped)
 	const int64_t rw = (rows + 63) / 64;
 	std::vector<uint64_t> words;
-	try { words.assign((size_t)nrhs * (size_t)rw, 0); } catch (const std::bad_alloc &) { return PyErr_NoMemory(); }
-	PyObject *zero = PyLong_FromLong(0);
-	if (!zero) return nullptr;
-	for (Py_ssize_t j = 0; j < nrhs; j++) {
-		PyObject *item = PyList_GET_ITEM(rhs, j);
-		if (!PyLong_Check(item)) { Py_DECREF(zero); PyErr_SetString(PyExc_TypeError, "The right-hand sides must be a list of integers"); return nullptr; }
-		const int neg = PyObject_RichCompareBool(item, zero, Py_LT);
-		if (neg) Py_DECREF(zero);
-		if (neg < 0) return nullptr;
-		if (neg) { PyErr_SetString(PyExc_ValueError, "The right-hand sides must be non-negative"); return nullptr; }
-		PyLongObject *v = (PyLongObject *)item;
-		uint64_t *w = words.data() + (size_t)j * (size_t)rw;
-		const Py_ssize_t nd = GF2_DIGIT_COUNT(v);
-		for (Py_ssize_t d = 0; d < nd; d++) {
-			const int64_t bit = (int64_t)d * PyLong_SHIFT;
-			if (bit >= rows) break;
-			const uint64_t x = (uint64_t)GF2_DIGITS(v)[d];
-			w[bit >> 6] |= x << (bit & 63);
-			if ((bit & 63) + PyLong_SHIFT > 64 && (bit >> 6) + 1 < rw) w[(bit >> 6) + 1] |= x >> (64 - (bit & 63));
-		}
-		if (rows & 63) w[rw - 1] &= ((uint64_t)1 << (rows & 63)) - 1;
-	}
-	Py_DECREF(zero);
+	if (!rhs_list_words(rhs, rows, words)) return nullptr;
 	DigitGather dg;
 	dg.off.reserve((size_t)rows + 1); dg.src.reserve((size_t)rows);
 	if (!dg.add(list, cols) || !dg.gather()) return nullptr;
@@ -588,6 +616,201 @@ PyObject *py_m4ri_solve_rhs(PyObject *, PyObject *const *args, Py_ssize_t nargs)
 		PyList_SET_ITEM(out, j, v);
 	}
 	return out;
+}
+
+// ---- Factorization: a kept factorization of one matrix (gf2bv_factor_*; no counterpart in the reference) --------------------
+// m4ri_factor(equations, cols, mode, device=None) factors the coefficient matrix of `equations` (bit 0 ignored) once; its solve(rhs)
+// equals m4ri_solve_rhs(equations, cols, mode, rhs), element for element, for every call.  rhs: a list of non-negative ints (bit r =
+// affine term of equation r) or a C-contiguous 2-D uint64 buffer (numpy array) of nrhs x >= ceil(rows / 64) words.
+struct FactorObject {
+	PyObject_HEAD
+	gf2bv_factor *h;                  // nullptr once closed
+	int64_t rows, cols;
+	long mode;
+	int device;
+};
+
+PyTypeObject *Factorization_Type;
+
+void factor_dealloc(FactorObject *self)
+{
+	PyTypeObject *tp = Py_TYPE(self);
+	if (self->h) {
+		gf2bv_factor *h = self->h;
+		self->h = nullptr;
+		Py_BEGIN_ALLOW_THREADS
+		gf2bv_factor_free(h);
+		Py_END_ALLOW_THREADS
+	}
+	tp->tp_free((PyObject *)self);
+	Py_DECREF(tp);
+}
+
+bool factor_open(FactorObject *self)
+{
+	if (self->h) return true;
+	PyErr_SetString(PyExc_ValueError, "the factorization is closed");
+	return false;
+}
+
+PyObject *factor_rank(FactorObject *self, void *) { return factor_open(self) ? PyLong_FromLongLong(gf2bv_factor_rank(self->h)) : nullptr; }
+PyObject *factor_rows(FactorObject *self, void *) { return PyLong_FromLongLong(self->rows); }
+PyObject *factor_cols(FactorObject *self, void *) { return PyLong_FromLongLong(self->cols); }
+PyObject *factor_mode(FactorObject *self, void *) { return PyLong_FromLong(self->mode); }
+PyObject *factor_device(FactorObject *self, void *) { return PyLong_FromLong(self->device); }
+PyObject *factor_device_bytes(FactorObject *self, void *)
+{
+	return factor_open(self) ? PyLong_FromLongLong(gf2bv_factor_device_bytes(self->h)) : nullptr;
+}
+PyObject *factor_pivots(FactorObject *self, void *)
+{
+	if (!factor_open(self)) return nullptr;
+	const int64_t rank = gf2bv_factor_rank(self->h);
+	std::vector<int32_t> piv((size_t)std::max<int64_t>(1, rank));
+	gf2bv_factor_pivots(self->h, piv.data());
+	PyObject *t = PyTuple_New(rank);
+	if (!t) return nullptr;
+	for (int64_t i = 0; i < rank; i++) {
+		PyObject *v = PyLong_FromLong(piv[(size_t)i]);
+		if (!v) { Py_DECREF(t); return nullptr; }
+		PyTuple_SET_ITEM(t, i, v);
+	}
+	return t;
+}
+
+PyObject *factor_solve(FactorObject *self, PyObject *rhs)
+{
+	if (!factor_open(self)) return nullptr;
+	const int64_t rw = (self->rows + 63) / 64;
+	std::vector<uint64_t> words;
+	const uint64_t *src = nullptr;
+	int64_t nrhs = 0, stride = rw;
+	Py_buffer view{};
+	bool have_view = false;
+	if (PyList_Check(rhs)) {
+		nrhs = PyList_GET_SIZE(rhs);
+		if (nrhs == 0) return PyList_New(0);
+		if (!rhs_list_words(rhs, self->rows, words)) return nullptr;
+		src = words.data();
+	} else if (PyObject_CheckBuffer(rhs)) {
+		if (PyObject_GetBuffer(rhs, &view, PyBUF_C_CONTIGUOUS | PyBUF_FORMAT) < 0) return nullptr;
+		have_view = true;
+		const char *f = view.format ? view.format : "B";
+		if (*f == '<' || *f == '=' || *f == '@') f++;
+		if (view.ndim != 2 || view.itemsize != 8 || !(strcmp(f, "Q") == 0 || strcmp(f, "L") == 0)) {
+			PyBuffer_Release(&view);
+			PyErr_SetString(PyExc_TypeError, "right-hand sides as a buffer: a C-contiguous 2-D uint64 array");
+			return nullptr;
+		}
+		nrhs = view.shape[0];
+		stride = view.shape[1];
+		if (stride < rw) {
+			PyBuffer_Release(&view);
+			PyErr_SetString(PyExc_ValueError, "the right-hand-side array needs ceil(rows / 64) words per row");
+			return nullptr;
+		}
+		if (nrhs == 0) { PyBuffer_Release(&view); return PyList_New(0); }
+		src = static_cast<const uint64_t *>(view.buf);
+	} else {
+		PyErr_SetString(PyExc_TypeError, "The right-hand sides must be a list of integers or a 2-D uint64 array");
+		return nullptr;
+	}
+	std::vector<gf2bv_result *> res((size_t)nrhs, nullptr);
+	int rc;
+	gf2bv_factor *h = self->h;
+	Py_BEGIN_ALLOW_THREADS
+	rc = gf2bv_factor_solve(h, src, nrhs, stride, res.data());
+	Py_END_ALLOW_THREADS
+	if (have_view) PyBuffer_Release(&view);
+	if (rc != GF2BV_OK) {
+		for (gf2bv_result *r : res) if (r) gf2bv_result_free(r);
+		PyErr_Format(rc == GF2BV_ERR_ARG ? PyExc_ValueError : PyExc_RuntimeError,
+		             "gf2bv_amd: HIP solve failed (%d): %s", rc, gf2bv_last_error());
+		return nullptr;
+	}
+	return results_to_list(res, self->mode, self->device);
+}
+
+PyObject *factor_close(FactorObject *self, PyObject *)
+{
+	if (self->h) {
+		gf2bv_factor *h = self->h;
+		self->h = nullptr;
+		Py_BEGIN_ALLOW_THREADS
+		gf2bv_factor_free(h);
+		Py_END_ALLOW_THREADS
+	}
+	Py_RETURN_NONE;
+}
+
+PyObject *factor_enter(FactorObject *self, PyObject *)
+{
+	if (!factor_open(self)) return nullptr;
+	Py_INCREF(self);
+	return (PyObject *)self;
+}
+
+PyObject *factor_exit(FactorObject *self, PyObject *const *, Py_ssize_t) { return factor_close(self, nullptr); }
+
+PyGetSetDef factor_getset[] = {
+	{"rank", (getter)factor_rank, nullptr, "rank of the coefficient matrix", nullptr},
+	{"pivots", (getter)factor_pivots, nullptr, "pivot columns (the column rank profile), a tuple", nullptr},
+	{"rows", (getter)factor_rows, nullptr, "equations", nullptr},
+	{"cols", (getter)factor_cols, nullptr, "unknowns", nullptr},
+	{"mode", (getter)factor_mode, nullptr, "0: solve returns ints, 1: AffineSpace objects", nullptr},
+	{"device", (getter)factor_device, nullptr, "GPU that holds the factorization", nullptr},
+	{"device_bytes", (getter)factor_device_bytes, nullptr, "device memory the factorization holds", nullptr},
+	{nullptr, nullptr, nullptr, nullptr, nullptr}};
+
+PyMethodDef factor_methods[] = {
+	{"solve", (PyCFunction)factor_solve, METH_O,
+	 "solve(rhs)\n--\n\nOne m4ri_solve result per right-hand side (a list of ints, bit r = affine term of equation r, or an nrhs x words uint64 array)."},
+	{"close", (PyCFunction)factor_close, METH_NOARGS, "close()\n--\n\nRelease the device memory; later use raises ValueError."},
+	{"__enter__", (PyCFunction)factor_enter, METH_NOARGS, nullptr},
+	{"__exit__", (PyCFunction)(void (*)(void))factor_exit, METH_FASTCALL, nullptr},
+	{nullptr, nullptr, 0, nullptr}};
+
+PyType_Slot factor_slots[] = {
+	{Py_tp_dealloc, (void *)factor_dealloc}, {Py_tp_methods, (void *)factor_methods}, {Py_tp_getset, (void *)factor_getset}, {0, nullptr}};
+PyType_Spec factor_spec = {"_internal.Factorization", sizeof(FactorObject), 0,
+                           Py_TPFLAGS_DEFAULT | Py_TPFLAGS_DISALLOW_INSTANTIATION, factor_slots};
+
+PyObject *py_m4ri_factor(PyObject *, PyObject *const *args, Py_ssize_t nargs)
+{
+	if (nargs != 3 && nargs != 4) { PyErr_SetString(PyExc_TypeError, "m4ri_factor requires 3 arguments"); return nullptr; }
+	int device = default_device();
+	if (nargs == 4 && !parse_device(args[3], &device)) return nullptr;
+	PyObject *list = args[0];
+	if (!PyList_Check(list)) {
+		PyErr_SetString(PyExc_TypeError, "The first argument equations must be a list");
+		return nullptr;
+	}
+	Py_ssize_t cols;
+	long mode;
+	if (!parse_cols_mode(args[1], args[2], &cols, &mode)) return nullptr;
+	const Py_ssize_t rows = PyList_GET_SIZE(list);
+	if (rows < cols) {
+		PyErr_SetString(PyExc_ValueError,
+		                "Number of rows must be greater than or equal to number of columns, try pad with zeros.");
+		return nullptr;
+	}
+	DigitGather dg;
+	dg.off.reserve((size_t)rows + 1); dg.src.reserve((size_t)rows);
+	if (!dg.add(list, cols) || !dg.gather()) return nullptr;
+	gf2bv_factor *h = nullptr;
+	int rc;
+	Py_BEGIN_ALLOW_THREADS
+	rc = gf2bv_factor_digits(dg.digits, dg.off.data(), PyLong_SHIFT, rows, cols, (int)mode, device, &h);
+	Py_END_ALLOW_THREADS
+	if (rc != GF2BV_OK) {
+		PyErr_Format(rc == GF2BV_ERR_ARG ? PyExc_ValueError : PyExc_RuntimeError,
+		             "gf2bv_amd: HIP factorization failed (%d): %s", rc, gf2bv_last_error());
+		return nullptr;
+	}
+	FactorObject *f = PyObject_New(FactorObject, Factorization_Type);
+	if (!f) { gf2bv_factor_free(h); return nullptr; }
+	f->h = h; f->rows = rows; f->cols = cols; f->mode = mode; f->device = device;
+	return (PyObject *)f;
 }
 
 // m4ri_solve_packed(buffer, rows, words, cols, mode) -> None | int | AffineSpace.
@@ -1079,6 +1302,8 @@ PyMethodDef module_methods[] = {
 	 "m4ri_solve_packed(buffer, rows, words, cols, mode, device=None)\n--\n\nm4ri_solve on equations already packed as rows x words 64-bit words (equation-int bit order)."},
 	{"m4ri_solve_rhs", FAST(py_m4ri_solve_rhs), METH_FASTCALL,
 	 "m4ri_solve_rhs(equations, cols, mode, rhs, device=None)\n--\n\nSolve one coefficient matrix against every right-hand side in rhs (bit r = affine term of equation r) with one elimination; list of m4ri_solve results."},
+	{"m4ri_factor", FAST(py_m4ri_factor), METH_FASTCALL,
+	 "m4ri_factor(equations, cols, mode, device=None)\n--\n\nFactor the coefficient matrix once (bit 0 of every equation ignored); Factorization.solve(rhs) equals m4ri_solve_rhs(equations, cols, mode, rhs)."},
 	{"m4ri_solve_many", FAST(py_m4ri_solve_many), METH_FASTCALL,
 	 "m4ri_solve_many(systems, cols, mode, devices=None)\n--\n\nSolve a list of same-shape systems in one batched call, sharded over the given GPUs (None: the default device, \"all\": every visible one); list of m4ri_solve results."},
 	{"to_bits", FAST(py_to_bits), METH_FASTCALL, "to_bits(n, a)\n--\n\nLow n bits of a, LSB first."},
@@ -1106,9 +1331,11 @@ PyMODINIT_FUNC PyInit__internal(void)
 	AffineSpace_Type = (PyTypeObject *)PyType_FromSpec(&space_spec);
 	SpaceIterGray_Type = (PyTypeObject *)PyType_FromSpec(&gray_spec);
 	SpaceIterSlow_Type = (PyTypeObject *)PyType_FromSpec(&slow_spec);
-	if (!AffineSpace_Type || !SpaceIterGray_Type || !SpaceIterSlow_Type) { Py_DECREF(m); return nullptr; }
-	Py_INCREF(AffineSpace_Type); Py_INCREF(SpaceIterGray_Type); Py_INCREF(SpaceIterSlow_Type);
+	Factorization_Type = (PyTypeObject *)PyType_FromSpec(&factor_spec);
+	if (!AffineSpace_Type || !SpaceIterGray_Type || !SpaceIterSlow_Type || !Factorization_Type) { Py_DECREF(m); return nullptr; }
+	Py_INCREF(AffineSpace_Type); Py_INCREF(SpaceIterGray_Type); Py_INCREF(SpaceIterSlow_Type); Py_INCREF(Factorization_Type);
 	if (PyModule_AddObject(m, "AffineSpace", (PyObject *)AffineSpace_Type) < 0 ||
+	    PyModule_AddObject(m, "Factorization", (PyObject *)Factorization_Type) < 0 ||
 	    PyModule_AddObject(m, "AffineSpaceIterator", (PyObject *)SpaceIterGray_Type) < 0 ||
 	    PyModule_AddObject(m, "AffineSpaceIteratorSlow", (PyObject *)SpaceIterSlow_Type) < 0) {
 		Py_DECREF(m);

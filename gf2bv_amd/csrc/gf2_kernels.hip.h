@@ -3415,6 +3415,78 @@ k_pack_rhs(const u64 *__restrict__ rhs, i64 nrhs, i64 rhs_words, i64 rows, i64 c
 	}
 }
 
+// ---- a kept factorization (gf2bv_factor_*): new right-hand sides against it later ------------------------------------------
+// The factorization eliminates [A | 0 | I]: C zero columns from `cols` on (the slots a solve writes its right-hand sides into)
+// and, from word tw0 on (a whole tile), the identity of the rows -- row r starts with bit r of that area set.  Row operations are
+// linear and blind to every column from `cols` on, so afterwards row r's area holds T[r] with T b = what the elimination would
+// have made of right-hand side b in that row.  A solve forms T b (k_apply_transform), writes it into the slots (k_put_rhs) and
+// goes on as gf2bv_solve_rhs_* does after its elimination.
+
+// The area right of the coefficients before the factorization: slot bits of the first word cleared (its bits below cols & 63
+// are coefficients and stay), every other word up to tw0 zero, then the identity (rw = ceil(rows / 64) words per row).
+// grid: x = rows / 256, y = word chunks (strided)
+__global__ void __launch_bounds__(256)
+k_factor_init(i64 rows, i64 cols, i64 srows, i64 tw0, i64 rw, u64 *__restrict__ M)
+{
+	const i64 r = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+	if (r >= rows) return;
+	const int s = (int)(cols & 63);
+	const i64 q0 = cols >> 6, q1 = tw0 + rw, mine = tw0 + (r >> 6);
+	for (i64 q = q0 + blockIdx.y; q < q1; q += gridDim.y) {
+		u64 &w = M[tidx(r, q, srows)];
+		if (q == q0) w &= (1ull << s) - 1;
+		else w = q == mine ? 1ull << (r & 63) : 0ull;
+	}
+}
+
+// acc[r] ^= bits j < nrhs of T[r] b_j over this workgroup's chunk of GF2_FT_WORDS words of T (acc zeroed by the caller; the
+// chunks of a row meet in atomicXor).  Right-hand side words of the chunk in LDS as 16-byte pairs, read by every lane at the
+// same address (broadcast); one lane = one row, reading its 16-byte tiles of T: a wavefront reads 64 consecutive rows of a tile
+// = 1 KiB contiguous.  Bits of b at rows >= rows meet zero columns of T.  grid: x = rows / 256, y = chunks of T.
+#define GF2_FT_WORDS 64
+__global__ void __launch_bounds__(256)
+k_apply_transform(const u64 *__restrict__ M, i64 rows, i64 srows, i64 tw0, i64 rw, const u64 *__restrict__ rhs, int nrhs,
+                  i64 rhs_stride, u64 *__restrict__ acc)
+{
+	__shared__ ulonglong2 sb[GF2_FT_WORDS / 2][64];
+	const i64 w0 = (i64)blockIdx.y * GF2_FT_WORDS, wn = rw - w0 < GF2_FT_WORDS ? rw - w0 : GF2_FT_WORDS;
+	for (int i = threadIdx.x; i < (GF2_FT_WORDS / 2) * nrhs; i += blockDim.x) {
+		const int j = i / (GF2_FT_WORDS / 2), p = i % (GF2_FT_WORDS / 2);
+		const u64 *b = rhs + (i64)j * rhs_stride + w0;
+		sb[p][j] = make_ulonglong2(2 * p < wn ? b[2 * p] : 0ull, 2 * p + 1 < wn ? b[2 * p + 1] : 0ull);
+	}
+	__syncthreads();
+	const i64 r = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+	if (r >= rows) return;
+	u64 out = 0;
+	for (int p = 0; 2 * p < wn; p++) {
+		const ulonglong2 t = *reinterpret_cast<const ulonglong2 *>(&M[tidx(r, tw0 + w0 + 2 * p, srows)]);
+		for (int j = 0; j < nrhs; j++) {
+			const ulonglong2 b = sb[p][j];
+			out ^= (u64)(__popcll((t.x & b.x) ^ (t.y & b.y)) & 1) << j;
+		}
+	}
+	if (out) atomicXor(&acc[r], out);
+}
+
+// Slot bits of every row: column cols + j = bit j of acc[r], for all 64 slots (bits of acc beyond the pass's right-hand sides are 0,
+// so no slot keeps a value of an earlier pass).  Only slot bits are stored: the coefficient bits below cols & 63 of the first word
+// and the zero columns above the slots in the second stay.  grid: rows / 256.
+__global__ void __launch_bounds__(256)
+k_put_rhs(const u64 *__restrict__ acc, i64 rows, i64 cols, i64 srows, u64 *__restrict__ M)
+{
+	const i64 r = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+	if (r >= rows) return;
+	const int s = (int)(cols & 63);
+	const u64 a = acc[r], low = (1ull << s) - 1;
+	u64 &w0 = M[tidx(r, cols >> 6, srows)];
+	w0 = (w0 & low) | (a << s);
+	if (s) {
+		u64 &w1 = M[tidx(r, (cols >> 6) + 1, srows)];
+		w1 = (w1 & ~low) | (a >> (64 - s));
+	}
+}
+
 // ---- single right-hand side (solve_one): blocked parity back-substitution --------------------
 // With every free variable 0, x[c_k] = y_k ^ parity( U[k][words right of k's panel] & X ), and the
 // pivot rows of one panel are mutually reduced, so a panel's 64 unknowns are independent of each

@@ -2124,6 +2124,40 @@ int check_rhs_args(i64 rows, i64 cols, int mode, const void *rhs, i64 nrhs, i64 
 	return GF2BV_OK;
 }
 
+// The coefficients into the tile-major working matrix S.M (ntiles tiles, srows rows per slab) on S.sA: the digits packed straight into
+// tiles (k_pack_digits puts the affine term at column `cols`; the callers overwrite it), or the words that hold coefficients -- and
+// only those -- copied into tiles (the words right of them are zero-filled)
+int pack_coefficients(const RhsInput &in, i64 rows, i64 cols, i64 ntiles, i64 srows, Solver &S, Scratch &scratch)
+{
+	const int device = S.device;
+	const i64 cw = (cols + 63) / 64, rw = (rows + 63) / 64;
+	if (in.h_digits) {
+		const i64 ndig = in.h_off[rows];
+		uint32_t *d_dig = nullptr;
+		i64 *d_off = nullptr;
+		HIPCHK(scratch.alloc((void **)&d_dig, sizeof(uint32_t) * std::max<i64>(1, ndig), device));
+		HIPCHK(scratch.alloc((void **)&d_off, sizeof(i64) * (rows + 1), device));
+		if (ndig) HIPCHK(hipMemcpyAsync(d_dig, in.h_digits, sizeof(uint32_t) * ndig, hipMemcpyHostToDevice, S.sA));
+		HIPCHK(hipMemcpyAsync(d_off, in.h_off, sizeof(i64) * (rows + 1), hipMemcpyHostToDevice, S.sA));
+		k_pack_digits<<<dim3((unsigned)((ntiles * TW + 255) / 256), (unsigned)std::min<i64>(rows, 65535)), dim3(256), 0, S.sA>>>(
+			d_dig, d_off, in.bpd, rows, cols, ntiles * TW, srows, S.M, SysStride{0, 0}, (i64)0);
+	} else {
+		const u64 *src = in.d_words;
+		i64 sstride = in.stride;
+		if (in.h_words) {
+			sstride = round_up(cw, 2);
+			u64 *tmp = nullptr;
+			HIPCHK(scratch.alloc((void **)&tmp, sizeof(u64) * rows * sstride, device));
+			HIPCHK(hipMemcpy2DAsync(tmp, sstride * 8, in.h_words, in.stride * 8, cw * 8, rows, hipMemcpyHostToDevice, S.sA));
+			src = tmp;
+		}
+		k_to_tiled<<<dim3((unsigned)rw, (unsigned)((ntiles + 15) / 16)), dim3(256), 0, S.sA>>>(src, sstride, rows, ntiles, cw, srows, S.M,
+		                                                                                      (i64)0, SysStride{0, 0});
+	}
+	HIPCHK(hipGetLastError());
+	return GF2BV_OK;
+}
+
 int solve_rhs(const RhsInput &in, i64 rows, i64 cols, int mode, int device, hipStream_t stream, bool time_kernels, gf2bv_result **out)
 {
 	const i64 nrhs = in.nrhs, cw = (cols + 63) / 64, cwx = std::max<i64>(1, cw), nmw = (nrhs + 63) / 64;
@@ -2152,31 +2186,8 @@ int solve_rhs(const RhsInput &in, i64 rows, i64 cols, int mode, int device, hipS
 	HIPCHK(scratch.event(&p0)); HIPCHK(scratch.event(&p1));
 	HIPCHK(hipEventRecord(p0, S.sA));
 	HIPCHK(hipMemsetAsync(S.rhs_bad, 0, sizeof(u64) * nmw, S.sA));
-	// coefficients: the digits packed straight into tiles (k_pack_digits puts the affine term at column `cols`; k_pack_rhs overwrites
-	// it), or the words that hold coefficients -- and only those -- copied into tiles (the words right of them are zero-filled)
-	if (in.h_digits) {
-		const i64 ndig = in.h_off[rows];
-		uint32_t *d_dig = nullptr;
-		i64 *d_off = nullptr;
-		HIPCHK(scratch.alloc((void **)&d_dig, sizeof(uint32_t) * std::max<i64>(1, ndig), device));
-		HIPCHK(scratch.alloc((void **)&d_off, sizeof(i64) * (rows + 1), device));
-		if (ndig) HIPCHK(hipMemcpyAsync(d_dig, in.h_digits, sizeof(uint32_t) * ndig, hipMemcpyHostToDevice, S.sA));
-		HIPCHK(hipMemcpyAsync(d_off, in.h_off, sizeof(i64) * (rows + 1), hipMemcpyHostToDevice, S.sA));
-		k_pack_digits<<<dim3((unsigned)((ntiles * TW + 255) / 256), (unsigned)std::min<i64>(rows, 65535)), dim3(256), 0, S.sA>>>(
-			d_dig, d_off, in.bpd, rows, cols, ntiles * TW, srows, S.M, SysStride{0, 0}, (i64)0);
-	} else {
-		const u64 *src = in.d_words;
-		i64 sstride = in.stride;
-		if (in.h_words) {
-			sstride = round_up(cw, 2);
-			u64 *tmp = nullptr;
-			HIPCHK(scratch.alloc((void **)&tmp, sizeof(u64) * rows * sstride, device));
-			HIPCHK(hipMemcpy2DAsync(tmp, sstride * 8, in.h_words, in.stride * 8, cw * 8, rows, hipMemcpyHostToDevice, S.sA));
-			src = tmp;
-		}
-		k_to_tiled<<<dim3((unsigned)rw, (unsigned)((ntiles + 15) / 16)), dim3(256), 0, S.sA>>>(src, sstride, rows, ntiles, cw, srows, S.M,
-		                                                                                      (i64)0, SysStride{0, 0});
-	}
+	int rc;
+	if ((rc = pack_coefficients(in, rows, cols, ntiles, srows, S, scratch))) return rc;
 	const u64 *d_rhs = in.rhs;
 	i64 rhs_stride = in.rhs_words;
 	if (!in.rhs_on_device) {          // (only the words that hold rows go up)
@@ -2189,7 +2200,7 @@ int solve_rhs(const RhsInput &in, i64 rows, i64 cols, int mode, int device, hipS
 	                                                                                                  srows, S.M);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipEventRecord(p1, S.sA));
-	int rc = solver_alloc(S);         // (S.src is null: the matrix is in place)
+	rc = solver_alloc(S);             // (S.src is null: the matrix is in place)
 	if (rc) return rc;
 	rc = enqueue_forward(S);
 	if (rc) return rc;
@@ -2255,6 +2266,232 @@ int solve_rhs(const RhsInput &in, i64 rows, i64 cols, int mode, int device, hipS
 		fill_stats(S, R);
 	}
 	for (i64 j = 0; j < nrhs; j++) out[j] = res[(size_t)j].release();
+	return GF2BV_OK;
+}
+
+
+// ---- a kept factorization: factor once, solve new right-hand sides later (gf2bv_factor_*) ---------------------------------
+// The reference's own split (_internal.c:431-447: _mzd_pluq on A, then _mzd_pluq_solve_left on B) with the factorization kept.
+// What is kept is the working matrix after eliminating [A | 0 (C slots) | I]: U in the coefficient columns and, in the identity's
+// columns, the transform T that the row operations made of the identity -- rows x rows bits, as much as the matrix again when
+// rows == cols.  Row operations are linear and blind to every column from `cols` on (pivots are searched in columns < cols only),
+// so T b is exactly what the elimination would have left of right-hand side b in every row, whichever path eliminated each block
+// (dense search, sparse search, general panel steps, a poisoned block resumed, outer panels).  A solve pass (up to C right-hand
+// sides) is then one launch for T b over T plus a slot write, followed by what gf2bv_solve_rhs_* does after its elimination:
+// k_check_rhs_many, the back-substitution with ycols = cols + j, the export.  Mode 1: the kernel basis depends on A alone and is
+// computed once, at factor time.
+}  // namespace
+
+struct gf2bv_factor {
+	std::mutex mu;                    // one call on a handle at a time (the binding drops the GIL)
+	Solver S;                         // M = [U | slots | T], arena (pivots, urow, panel records), streams
+	i64 rows = 0, cols = 0, tw0 = 0, rw = 0, cw = 0;
+	int mode = 0, device = 0;
+	i64 rank = 0;
+	std::vector<int32_t> piv;
+	std::vector<u64> basis;           // mode 1: dim x max(1, cw) words, M4RI's order (empty in mode 0)
+	gf2bv_stats fst{};                // the factorization's elimination counters (copied into every result)
+	i64 device_bytes = 0;
+};
+
+namespace {
+
+constexpr i64 kFactorSlots = 64;      // right-hand sides per solve pass (the slot columns cols .. cols + 63)
+
+// what a back-substitution took from the pool goes back (the handle keeps its solver between calls)
+void release_backsub(Solver &S)
+{
+	(void)hipStreamSynchronize(S.sA);
+	for (void *p : { (void *)S.Y, (void *)S.ycols, (void *)S.out, (void *)S.Minv }) pool().release(p);
+	S.Y = nullptr; S.ycols = nullptr; S.out = nullptr; S.Minv = nullptr;
+}
+
+int factor_matrix(const RhsInput &in, i64 rows, i64 cols, int mode, int device, hipStream_t stream, gf2bv_factor **out)
+{
+	const i64 rw = (rows + 63) / 64, cw = (cols + 63) / 64, cwx = std::max<i64>(1, cw);
+	const i64 tw0 = round_up(cols + kFactorSlots, 128) / 64;          // (the identity starts on a whole 16-byte tile)
+	const i64 wt = tw0 + rw, ntiles = tiles_for(wt), srows = slab_rows(rows);
+	std::unique_ptr<gf2bv_factor> h(new gf2bv_factor());
+	h->rows = rows; h->cols = cols; h->mode = mode; h->device = device; h->tw0 = tw0; h->rw = rw; h->cw = cw;
+	Solver &S = h->S;
+	S.t_begin = std::chrono::steady_clock::now();
+	S.device = device;
+	HIPCHK(pool().stream(&S.sA, device, false));
+	S.own_sA = true;
+	S.rows = rows; S.cols = cols; S.mode = mode;
+	S.nrhs = (int)(wt * 64 - cols);   // (solver_alloc: wt words per row)
+	S.stride = in.h_digits ? ntiles * TW : in.stride;
+	if (in.d_words && stream) {       // the caller's matrix is read after what its stream has queued
+		hipEvent_t e = nullptr;
+		HIPCHK(pool().event(&e, false));
+		HIPCHK(hipEventRecord(e, stream));
+		HIPCHK(hipStreamWaitEvent(S.sA, e, 0));
+		pool().release_event(e, false);
+	}
+	{
+		const hipError_t e = pool().alloc((void **)&S.M, sizeof(u64) * ntiles * TW * srows + kOuterSlackBytes, device);
+		if (e == hipErrorOutOfMemory) {
+			(void)hipGetLastError();
+			return fail(GF2BV_ERR_NOMEM, "the factorization (the matrix and its row transform, about twice the matrix) does not fit on the device");
+		}
+		if (e != hipSuccess) return fail(GF2BV_ERR_HIP, "working matrix", e);
+	}
+	Scratch scratch;
+	scratch.sync_first = S.sA;
+	int rc = pack_coefficients(in, rows, cols, ntiles, srows, S, scratch);
+	if (rc) return rc;
+	k_factor_init<<<dim3((unsigned)((rows + 255) / 256), (unsigned)std::min<i64>(wt - (cols >> 6), 64)), dim3(256), 0, S.sA>>>(
+		rows, cols, srows, tw0, rw, S.M);
+	HIPCHK(hipGetLastError());
+	if ((rc = solver_alloc(S))) return rc;
+	if ((rc = enqueue_forward(S))) return rc;
+	// (the slots are zero: k_check_rhs finds the factorization consistent -- nothing reads that)
+	HIPCHK(hipMemcpyAsync(&S.hst, S.st, sizeof S.hst, hipMemcpyDeviceToHost, S.sA));
+	S.hp.resize(std::max(1, S.npanels));
+	HIPCHK(hipMemcpyAsync(S.hp.data(), S.panels, sizeof(PanelRec) * S.hp.size(), hipMemcpyDeviceToHost, S.sA));
+	HIPCHK(hipStreamSynchronize(S.sA));
+	HIPCHK(hipStreamSynchronize(S.sB));
+	if (S.sC) HIPCHK(hipStreamSynchronize(S.sC));
+	if (S.hst.gate_timeout) {
+		if (!S.flag_sync) return fail(GF2BV_ERR_HIP, "a stream hand-over gate timed out on the device");
+		forget_concurrency(S.device);
+		return GF2BV_RETRY_EVENTS;
+	}
+	h->rank = S.hst.rank;
+	h->piv.resize((size_t)h->rank);
+	if (h->rank) HIPCHK(hipMemcpy(h->piv.data(), S.pivcol, sizeof(int) * h->rank, hipMemcpyDeviceToHost));
+	if (mode == GF2BV_MODE_AFFINE_SPACE) {
+		if ((rc = load_free_order(S))) return rc;
+		const i64 dim = cols - h->rank;
+		h->basis.assign((size_t)(dim * cwx), 0);
+		if (dim) {
+			const std::vector<int> &yc = S.free_order;
+			rc = ((i64)yc.size() <= GF2_BS_MAXRHS && !getenv("GF2BV_YSWEEP")) ? enqueue_backward_parity(S, yc) : enqueue_backward(S, yc);
+			if (rc) return rc;
+			std::vector<u64> hout((size_t)(dim * cwx));
+			HIPCHK(hipMemcpyAsync(hout.data(), S.out, sizeof(u64) * hout.size(), hipMemcpyDeviceToHost, S.sA));
+			HIPCHK(hipStreamSynchronize(S.sA));
+			for (i64 t = 0; t < dim; t++) {
+				u64 *v = h->basis.data() + (size_t)t * cwx;
+				std::copy(hout.data() + (size_t)t * cwx, hout.data() + (size_t)t * cwx + cw, v);
+				const int f = S.free_order[(size_t)t];
+				v[f >> 6] |= 1ull << (f & 63);
+			}
+		}
+	}
+	{
+		gf2bv_result R;
+		R.rank = h->rank; R.dim = cols - h->rank;
+		fill_stats(S, &R);
+		(void)hipGetLastError();      // (fill_stats' elapsed times of events a factorization does not record)
+		h->fst = R.stats;
+	}
+	release_backsub(S);
+	h->device_bytes = (i64)(sizeof(u64) * ntiles * TW * srows + kOuterSlackBytes + S.arena_stride);
+	*out = h.release();
+	return GF2BV_OK;
+}
+
+// one solve pass: right-hand sides j0 .. j0 + np of rhs (device, rhs_stride words apart) into results out[0 .. np)
+int factor_pass(gf2bv_factor *h, const u64 *d_rhs, i64 np, i64 rhs_stride, hipEvent_t ev[5], std::chrono::steady_clock::time_point t0,
+                u64 *acc, u64 *bad, gf2bv_result **out)
+{
+	Solver &S = h->S;
+	const i64 rows = h->rows, cols = h->cols, cw = h->cw, cwx = std::max<i64>(1, cw), rw = h->rw;
+	HIPCHK(hipMemsetAsync(acc, 0, sizeof(u64) * std::max<i64>(1, rows), S.sA));
+	HIPCHK(hipMemsetAsync(bad, 0, sizeof(u64), S.sA));
+	HIPCHK(hipEventRecord(ev[1], S.sA));
+	const unsigned gx = (unsigned)((rows + 255) / 256);
+	k_apply_transform<<<dim3(gx, (unsigned)((rw + GF2_FT_WORDS - 1) / GF2_FT_WORDS)), dim3(256), 0, S.sA>>>(S.M, rows, S.srows, h->tw0, rw, d_rhs,
+	                                                                                                     (int)np, rhs_stride, acc);
+	k_put_rhs<<<dim3(gx), dim3(256), 0, S.sA>>>(acc, rows, cols, S.srows, S.M);
+	const i64 nrw = ((cols & 63) + np + 63) / 64;
+	k_check_rhs_many<<<dim3((unsigned)std::min<i64>(1024, gx), (unsigned)nrw), dim3(256), 0, S.sA>>>(S.M, rows, S.srows, cols, np, S.died, bad);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(ev[2], S.sA));
+	std::vector<int> yc((size_t)np);
+	for (i64 j = 0; j < np; j++) yc[(size_t)j] = (int)(cols + j);
+	int rc = ((i64)yc.size() <= GF2_BS_MAXRHS && !getenv("GF2BV_YSWEEP")) ? enqueue_backward_parity(S, yc) : enqueue_backward(S, yc);
+	if (rc) return rc;
+	HIPCHK(hipEventRecord(ev[3], S.sA));
+	std::vector<u64> hout((size_t)(np * cwx));
+	u64 hbad = 0;
+	HIPCHK(hipMemcpyAsync(hout.data(), S.out, sizeof(u64) * hout.size(), hipMemcpyDeviceToHost, S.sA));
+	HIPCHK(hipMemcpyAsync(&hbad, bad, sizeof(u64), hipMemcpyDeviceToHost, S.sA));
+	HIPCHK(hipEventRecord(ev[4], S.sA));
+	HIPCHK(hipStreamSynchronize(S.sA));
+	release_backsub(S);
+	float ms[4] = {0, 0, 0, 0};
+	for (int i = 0; i < 4; i++) (void)hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]);
+	const float total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	for (i64 j = 0; j < np; j++) {
+		std::unique_ptr<gf2bv_result> R(new gf2bv_result());
+		const bool ok = !((hbad >> j) & 1);
+		R->status = ok ? GF2BV_STATUS_SOLVED : GF2BV_STATUS_INCONSISTENT;
+		R->rank = h->rank;
+		R->cw = cw;
+		R->dim = cols - h->rank;
+		R->pivots = h->piv;
+		R->origin.assign((size_t)cwx, 0);
+		if (ok) {
+			const u64 *o = hout.data() + (size_t)j * cwx;
+			std::copy(o, o + cw, R->origin.begin());
+			if (h->mode == GF2BV_MODE_AFFINE_SPACE) R->basis = h->basis;
+		}
+		gf2bv_stats &st = R->stats;
+		st = h->fst;
+		st.rank = R->rank; st.dimension = R->dim; st.status = R->status;
+		st.ms_pack = ms[0]; st.ms_eliminate = ms[1]; st.ms_backsub = ms[2]; st.ms_export = ms[3]; st.ms_total = total;
+		st.ms_sweep = 0;
+		out[j] = R.release();
+	}
+	return GF2BV_OK;
+}
+
+int factor_solve(gf2bv_factor *h, const u64 *rhs, bool on_device, i64 nrhs, i64 rhs_words, hipStream_t stream, gf2bv_result **out)
+{
+	std::lock_guard<std::mutex> lk(h->mu);
+	const auto t0 = std::chrono::steady_clock::now();
+	Solver &S = h->S;
+	HIPCHK(hipSetDevice(h->device));
+	const i64 rw = h->rw, C = kFactorSlots;
+	Scratch scratch;
+	scratch.sync_first = S.sA;
+	u64 *acc = nullptr, *bad = nullptr, *d = nullptr;
+	HIPCHK(scratch.alloc((void **)&acc, sizeof(u64) * std::max<i64>(1, h->rows), h->device));
+	HIPCHK(scratch.alloc((void **)&bad, sizeof(u64), h->device));
+	if (!on_device) HIPCHK(scratch.alloc((void **)&d, sizeof(u64) * C * rw, h->device));
+	hipEvent_t ev[5];
+	for (hipEvent_t &e : ev) HIPCHK(scratch.event(&e));
+	if (on_device && stream) {        // the caller's right-hand sides are read after what its stream has queued
+		HIPCHK(hipEventRecord(ev[0], stream));
+		HIPCHK(hipStreamWaitEvent(S.sA, ev[0], 0));
+	}
+	std::vector<std::unique_ptr<gf2bv_result>> res((size_t)nrhs);
+	std::vector<gf2bv_result *> part((size_t)C);
+	for (i64 j0 = 0; j0 < nrhs; j0 += C) {
+		const i64 np = std::min(C, nrhs - j0);
+		HIPCHK(hipEventRecord(ev[0], S.sA));
+		const u64 *src = rhs + j0 * rhs_words;
+		i64 stride = rhs_words;
+		if (!on_device) {             // (only the words that hold rows go up)
+			HIPCHK(hipMemcpy2DAsync(d, rw * 8, src, rhs_words * 8, rw * 8, np, hipMemcpyHostToDevice, S.sA));
+			src = d; stride = rw;
+		}
+		int rc = factor_pass(h, src, np, stride, ev, t0, acc, bad, part.data());
+		if (rc) return rc;
+		for (i64 j = 0; j < np; j++) res[(size_t)(j0 + j)].reset(part[(size_t)j]);
+	}
+	for (i64 j = 0; j < nrhs; j++) out[j] = res[(size_t)j].release();
+	return GF2BV_OK;
+}
+
+int check_factor_args(const gf2bv_factor *h, const void *rhs, i64 nrhs, i64 rhs_words, gf2bv_result **out)
+{
+	if (!h || !out || !rhs) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (nrhs < 1) return fail(GF2BV_ERR_ARG, "nrhs must be at least 1");
+	for (i64 j = 0; j < nrhs; j++) out[j] = nullptr;
+	if (rhs_words < h->rw) return fail(GF2BV_ERR_ARG, "rhs_words does not cover one bit per row");
 	return GF2BV_OK;
 }
 
@@ -2727,6 +2964,103 @@ int gf2bv_solve_rhs_device(void *d_aug, int64_t rows, int64_t cols, int64_t stri
 	in.rhs = (const u64 *)d_rhs; in.rhs_on_device = true; in.nrhs = nrhs; in.rhs_words = rhs_words;
 	return solve_rhs(in, rows, cols, mode, device, (hipStream_t)stream, time_kernels != 0, out);
 	});
+}
+
+// A kept factorization (_internal.c:431-447: _mzd_pluq on A, then _mzd_pluq_solve_left on B, as two steps): see factor_matrix.
+int gf2bv_factor_digits(const uint32_t *digits, const int64_t *digit_off, int bits_per_digit, int64_t rows, int64_t cols, int mode,
+                        int device, gf2bv_factor **out)
+{
+	return guarded([&]() -> int {
+	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
+	*out = nullptr;
+	int rc = check_shape(rows, cols, mode);
+	if (rc) return rc;
+	if (!digit_off) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (bits_per_digit < 1 || bits_per_digit > 32) return fail(GF2BV_ERR_ARG, "bits_per_digit must be 1..32");
+	if (digit_off[0] != 0) return fail(GF2BV_ERR_ARG, "digit offsets must start at 0");
+	for (i64 r = 0; r < rows; r++)
+		if (digit_off[r + 1] < digit_off[r]) return fail(GF2BV_ERR_ARG, "digit offsets must not decrease");
+	if (!digits && digit_off[rows] > 0) return fail(GF2BV_ERR_ARG, "null pointer");
+	rc = check_device(device);
+	if (rc) return rc;
+	RhsInput in;
+	in.h_digits = digits; in.h_off = reinterpret_cast<const i64 *>(digit_off); in.bpd = bits_per_digit;
+	return factor_matrix(in, rows, cols, mode, device, nullptr, out);
+	});
+}
+
+int gf2bv_factor_words(const uint64_t *aug, int64_t rows, int64_t cols, int64_t stride_words, int mode, int device, gf2bv_factor **out)
+{
+	return guarded([&]() -> int {
+	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
+	*out = nullptr;
+	int rc = check_shape(rows, cols, mode);
+	if (rc) return rc;
+	if (!aug) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (stride_words < (cols + 1 + 63) / 64) return fail(GF2BV_ERR_ARG, "stride_words does not cover cols+1 bits");
+	rc = check_device(device);
+	if (rc) return rc;
+	RhsInput in;
+	in.h_words = reinterpret_cast<const u64 *>(aug); in.stride = stride_words;
+	return factor_matrix(in, rows, cols, mode, device, nullptr, out);
+	});
+}
+
+int gf2bv_factor_device(void *d_aug, int64_t rows, int64_t cols, int64_t stride_words, int mode, int device, void *stream,
+                        gf2bv_factor **out)
+{
+	return guarded([&]() -> int {
+	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
+	*out = nullptr;
+	int rc = check_shape(rows, cols, mode);
+	if (rc) return rc;
+	if (!d_aug) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (stride_words % 2 != 0 || stride_words < (cols + 1 + 63) / 64 || ((uintptr_t)d_aug & 15))
+		return fail(GF2BV_ERR_ARG, "device matrix needs 16-byte alignment and an even stride_words covering cols+1 bits");
+	rc = check_device(device);
+	if (rc) return rc;
+	RhsInput in;
+	in.d_words = (const u64 *)d_aug; in.stride = stride_words;
+	return factor_matrix(in, rows, cols, mode, device, (hipStream_t)stream, out);
+	});
+}
+
+int gf2bv_factor_solve(gf2bv_factor *h, const uint64_t *rhs, int64_t nrhs, int64_t rhs_words, gf2bv_result **out)
+{
+	return guarded([&]() -> int {
+	int rc = check_factor_args(h, rhs, nrhs, rhs_words, out);
+	if (rc) return rc;
+	if ((rc = check_device(h->device))) return rc;
+	return factor_solve(h, reinterpret_cast<const u64 *>(rhs), false, nrhs, rhs_words, nullptr, out);
+	});
+}
+
+int gf2bv_factor_solve_device(gf2bv_factor *h, const void *d_rhs, int64_t nrhs, int64_t rhs_words, void *stream, int time_kernels,
+                              gf2bv_result **out)
+{
+	(void)time_kernels;               // (a solve's phase times come from events either way)
+	return guarded([&]() -> int {
+	int rc = check_factor_args(h, d_rhs, nrhs, rhs_words, out);
+	if (rc) return rc;
+	if ((uintptr_t)d_rhs & 7) return fail(GF2BV_ERR_ARG, "the right-hand sides need 8-byte alignment");
+	if ((rc = check_device(h->device))) return rc;
+	return factor_solve(h, (const u64 *)d_rhs, true, nrhs, rhs_words, (hipStream_t)stream, out);
+	});
+}
+
+int64_t gf2bv_factor_rank(const gf2bv_factor *h) { return h ? h->rank : -1; }
+int gf2bv_factor_pivots(const gf2bv_factor *h, int32_t *o)
+{
+	if (!h || (!o && !h->piv.empty())) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (!h->piv.empty()) memcpy(o, h->piv.data(), sizeof(int32_t) * h->piv.size());
+	return GF2BV_OK;
+}
+int64_t gf2bv_factor_device_bytes(const gf2bv_factor *h) { return h ? h->device_bytes : -1; }
+void gf2bv_factor_free(gf2bv_factor *h)
+{
+	if (!h) return;
+	{ std::lock_guard<std::mutex> lk(h->mu); }      // (a call still running on another thread finishes first)
+	delete h;
 }
 
 // ---- result accessors ----------------------------------------------------------------------------

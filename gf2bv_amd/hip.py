@@ -28,6 +28,8 @@ EXPORTS = [
     "gf2bv_solve_digits", "gf2bv_solve_words", "gf2bv_solve_device", "gf2bv_solve_batch_device",
     "gf2bv_solve_batch_digits", "gf2bv_solve_batch_digits_multi",
     "gf2bv_solve_rhs_digits", "gf2bv_solve_rhs_words", "gf2bv_solve_rhs_device",
+    "gf2bv_factor_digits", "gf2bv_factor_words", "gf2bv_factor_device", "gf2bv_factor_solve", "gf2bv_factor_solve_device",
+    "gf2bv_factor_rank", "gf2bv_factor_pivots", "gf2bv_factor_device_bytes", "gf2bv_factor_free",
     "gf2bv_result_status", "gf2bv_result_rank", "gf2bv_result_dimension", "gf2bv_result_words",
     "gf2bv_result_origin", "gf2bv_result_basis", "gf2bv_result_pivots", "gf2bv_result_stats",
     "gf2bv_result_free", "gf2bv_space_combine", "gf2bv_space_open", "gf2bv_space_enumerate", "gf2bv_space_buffer", "gf2bv_space_close",
@@ -87,6 +89,18 @@ def lib():
         L.gf2bv_solve_rhs_digits.argtypes = [vp, vp, i32, i64, i64, vp, i64, i64, i32, i32, pp]
         L.gf2bv_solve_rhs_words.argtypes = [vp, i64, i64, i64, vp, i64, i64, i32, i32, pp]
         L.gf2bv_solve_rhs_device.argtypes = [vp, i64, i64, i64, vp, i64, i64, i32, i32, vp, i32, pp]
+        L.gf2bv_factor_digits.argtypes = [vp, vp, i32, i64, i64, i32, i32, pp]
+        L.gf2bv_factor_words.argtypes = [vp, i64, i64, i64, i32, i32, pp]
+        L.gf2bv_factor_device.argtypes = [vp, i64, i64, i64, i32, i32, vp, pp]
+        L.gf2bv_factor_solve.argtypes = [vp, vp, i64, i64, pp]
+        L.gf2bv_factor_solve_device.argtypes = [vp, vp, i64, i64, vp, i32, pp]
+        L.gf2bv_factor_rank.argtypes = [vp]
+        L.gf2bv_factor_rank.restype = i64
+        L.gf2bv_factor_pivots.argtypes = [vp, vp]
+        L.gf2bv_factor_device_bytes.argtypes = [vp]
+        L.gf2bv_factor_device_bytes.restype = i64
+        L.gf2bv_factor_free.argtypes = [vp]
+        L.gf2bv_factor_free.restype = None
         for name, res in (("gf2bv_result_status", i32), ("gf2bv_result_rank", i64),
                           ("gf2bv_result_dimension", i64), ("gf2bv_result_words", i64)):
             getattr(L, name).restype = res
@@ -326,6 +340,100 @@ def solve_rhs_device(d_ptr: int, rows: int, cols: int, stride: int, d_rhs: int, 
     rc = lib().gf2bv_solve_rhs_device(d_ptr, rows, cols, stride, d_rhs, nrhs, rhs_words, mode, device, stream or None,
                                       1 if time_kernels else 0, hs)
     return _take_all(hs, max(nrhs, 0), rc, mode)
+
+
+class Factor:
+    """A kept factorization of one matrix (gf2bv_factor_*): solve(rhs) equals solve_rhs_words on the same matrix and right-hand
+    sides, result for result, for every call in any order.  The handle holds its device memory until close()."""
+
+    def __init__(self, handle: ctypes.c_void_p, rows: int, cols: int, mode: int):
+        self._h = handle
+        self.rows, self.cols, self.mode = rows, cols, mode
+
+    def _handle(self):
+        if not self._h:
+            raise ValueError("the factorization is closed")
+        return self._h
+
+    @property
+    def rank(self) -> int:
+        return int(lib().gf2bv_factor_rank(self._handle()))
+
+    @property
+    def pivots(self) -> np.ndarray:
+        piv = np.zeros(max(self.rank, 1), dtype=np.int32)
+        _check(lib().gf2bv_factor_pivots(self._handle(), piv.ctypes.data))
+        return piv[:self.rank]
+
+    @property
+    def device_bytes(self) -> int:
+        return int(lib().gf2bv_factor_device_bytes(self._handle()))
+
+    def solve(self, rhs: np.ndarray) -> list:
+        """rhs: [nrhs, >= ceil(rows / 64)] uint64 (see solve_rhs_words); one Solution per right-hand side"""
+        rhs = _rhs_array(rhs)
+        nrhs = rhs.shape[0]
+        hs = (ctypes.c_void_p * max(nrhs, 1))()
+        rc = lib().gf2bv_factor_solve(self._handle(), rhs.ctypes.data, nrhs, rhs.shape[1], hs)
+        return _take_all(hs, nrhs, rc, self.mode)
+
+    def solve_device(self, d_rhs: int, nrhs: int, rhs_words: int, stream: int = 0) -> list:
+        """solve() with the right-hand sides resident in device memory"""
+        hs = (ctypes.c_void_p * max(nrhs, 1))()
+        rc = lib().gf2bv_factor_solve_device(self._handle(), d_rhs, nrhs, rhs_words, stream or None, 0, hs)
+        return _take_all(hs, max(nrhs, 0), rc, self.mode)
+
+    def close(self) -> None:
+        if self._h:
+            lib().gf2bv_factor_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _factor(rc: int, h: ctypes.c_void_p, rows: int, cols: int, mode: int) -> Factor:
+    if rc != 0:
+        _check(rc)
+    return Factor(h, rows, cols, mode)
+
+
+def factor_words(aug: np.ndarray, rows: int, cols: int, mode: int = MODE_SINGLE, device: int = 0) -> Factor:
+    """Factor the matrix of solve_words' augmented input (its column `cols` is ignored) once; Factor.solve then takes
+    right-hand sides as solve_rhs_words does."""
+    aug = np.ascontiguousarray(aug, dtype=np.uint64)
+    stride = aug.shape[1] if aug.ndim == 2 else (cols + 1 + 63) // 64
+    h = ctypes.c_void_p()
+    rc = lib().gf2bv_factor_words(aug.ctypes.data, rows, cols, stride, mode, device, ctypes.byref(h))
+    return _factor(rc, h, rows, cols, mode)
+
+
+def factor_digits(digits: np.ndarray, offsets: np.ndarray, bits_per_digit: int, rows: int, cols: int,
+                  mode: int = MODE_SINGLE, device: int = 0) -> Factor:
+    """factor_words with the matrix given as digit arrays (see solve_digits; bit 0 of every equation is ignored)."""
+    digits = np.ascontiguousarray(digits, dtype=np.uint32)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    h = ctypes.c_void_p()
+    rc = lib().gf2bv_factor_digits(digits.ctypes.data, offsets.ctypes.data, bits_per_digit, rows, cols, mode, device,
+                                   ctypes.byref(h))
+    return _factor(rc, h, rows, cols, mode)
+
+
+def factor_device(d_ptr: int, rows: int, cols: int, stride: int, mode: int = MODE_SINGLE, device: int = 0,
+                  stream: int = 0) -> Factor:
+    """factor_words with the matrix resident in device memory (left untouched)."""
+    h = ctypes.c_void_p()
+    rc = lib().gf2bv_factor_device(d_ptr, rows, cols, stride, mode, device, stream or None, ctypes.byref(h))
+    return _factor(rc, h, rows, cols, mode)
 
 
 def space_enumerate(origin: np.ndarray, basis: np.ndarray, first: int, count: int, gray: bool = True,

@@ -213,6 +213,12 @@ class LinearSystem:
     def solve_one_rhs(self, exprs: Zeros, values_list: Sequence[Sequence[int]]) -> list:
         return [None if raw is None else self.convert_sol(raw) for raw in self._solve_internal_rhs(exprs, values_list, 0)]
 
+    def factor(self, exprs: Zeros, device=None):
+        """The coefficient matrix of `exprs` factored once on the GPU: a FactoredSystem whose methods take the observed values
+        (one per expression) and equal this system's methods on [e ^ v for e, v in zip(exprs, values)].  Needs numpy."""
+        from .factored import FactoredSystem     # noqa: PLC0415  (numpy on first use only)
+        return FactoredSystem(self, exprs, device)
+
     def evaluate(self, bv: BitVec, sol: tuple) -> int:
         raw, shift = 0, 0
         for value, width in zip(sol, self._sizes):

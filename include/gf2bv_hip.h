@@ -133,6 +133,39 @@ int gf2bv_solve_rhs_words(const uint64_t *aug, int64_t rows, int64_t cols, int64
 int gf2bv_solve_rhs_device(void *d_aug, int64_t rows, int64_t cols, int64_t stride_words, const void *d_rhs, int64_t nrhs,
                            int64_t rhs_words, int mode, int device, void *stream, int time_kernels, gf2bv_result **out);
 
+/* ---- a kept factorization: factor A once, solve right-hand sides against it later (gf2bv/_internal.c:431-447) -----------
+ * The reference's two steps -- _mzd_pluq on A, _mzd_pluq_solve_left on B -- with the factorization kept in a handle.  The matrix
+ * arguments follow gf2bv_solve_rhs_*; column `cols` (the affine term) is ignored.  Each gf2bv_factor_solve* takes right-hand sides
+ * in the format of gf2bv_solve_rhs_*, and result j is bit-identical to what gf2bv_solve_rhs_words returns for the same matrix and
+ * right-hand side j (status, rank, pivots, dimension, origin, basis), for every call on the handle, in any order.  More than 64
+ * right-hand sides run in passes of 64.  Calls on one handle are serialised by a mutex inside it.
+ * Device memory: the handle keeps the eliminated matrix [U | 64 slot columns | T] until gf2bv_factor_free, where T (rows x rows
+ * bits) is what the row operations made of the identity: about twice the matrix for square systems (16 GiB at 262144^2).
+ * gf2bv_pool_trim does not take it.  A factorization that does not fit returns GF2BV_ERR_NOMEM.
+ * A result's stats: ms_pack = upload of the right-hand sides, ms_eliminate = forming T b (the replay of the elimination),
+ * ms_backsub / ms_export / ms_total as usual; the elimination counters (n_panels, fast_blocks, outer_blocks, ...) are the
+ * factorization's (they count the T columns as well).
+ * Argument errors (null pointers, nrhs < 1, rhs_words < ceil(rows/64), the shape rules of the single entries) return
+ * GF2BV_ERR_ARG before any device is touched.  Scope: one system on one device; a handle stays on the device it was made on. */
+typedef struct gf2bv_factor gf2bv_factor;
+int gf2bv_factor_digits(const uint32_t *digits, const int64_t *digit_off, int bits_per_digit, int64_t rows, int64_t cols,
+                        int mode, int device, gf2bv_factor **out);
+int gf2bv_factor_words(const uint64_t *aug, int64_t rows, int64_t cols, int64_t stride_words, int mode, int device,
+                       gf2bv_factor **out);
+/* d_aug as in gf2bv_solve_device; read after everything enqueued on `stream` before the call */
+int gf2bv_factor_device(void *d_aug, int64_t rows, int64_t cols, int64_t stride_words, int mode, int device, void *stream,
+                        gf2bv_factor **out);
+/* out[0..nrhs) receives one result handle per right-hand side (free each with gf2bv_result_free) */
+int gf2bv_factor_solve(gf2bv_factor *h, const uint64_t *rhs, int64_t nrhs, int64_t rhs_words, gf2bv_result **out);
+/* d_rhs: device memory, 8-byte aligned, read after everything enqueued on `stream` before the call; time_kernels is accepted
+ * for symmetry with gf2bv_solve_rhs_device (the phase times are always measured) */
+int gf2bv_factor_solve_device(gf2bv_factor *h, const void *d_rhs, int64_t nrhs, int64_t rhs_words, void *stream,
+                              int time_kernels, gf2bv_result **out);
+int64_t gf2bv_factor_rank(const gf2bv_factor *h);
+int     gf2bv_factor_pivots(const gf2bv_factor *h, int32_t *out);      /* rank entries */
+int64_t gf2bv_factor_device_bytes(const gf2bv_factor *h);              /* device memory the handle holds */
+void    gf2bv_factor_free(gf2bv_factor *h);
+
 /* Batch of `nsys` independent equal-shape systems resident on one device
  * (system s starts at d_aug + s*sys_stride_words words); out[0..nsys) receives handles.
  * The systems run in lock-step "gangs": one set of kernel launches eliminates a whole gang
