@@ -360,7 +360,7 @@ bool parse_devices(PyObject *obj, std::vector<int> *devs)
 	return true;
 }
 
-// cols / mode checks shared by m4ri_solve and m4ri_solve_many (_internal.c:372-395)
+// cols / mode checks of every solve entry (_internal.c:372-395)
 bool parse_cols_mode(PyObject *cols_obj, PyObject *mode_obj, Py_ssize_t *cols, long *mode)
 {
 	*cols = PyLong_AsSsize_t(cols_obj);
@@ -378,6 +378,23 @@ bool parse_cols_mode(PyObject *cols_obj, PyObject *mode_obj, Py_ssize_t *cols, l
 	return true;
 }
 
+// ... and the rows they need (after parse_cols_mode)
+bool rows_cover_cols(Py_ssize_t rows, Py_ssize_t cols)
+{
+	if (rows >= cols) return true;
+	PyErr_SetString(PyExc_ValueError, "Number of rows must be greater than or equal to number of columns, try pad with zeros.");
+	return false;
+}
+
+// A failed library call as a Python exception: ValueError for bad arguments, RuntimeError otherwise.  `msg`: the library's
+// message of this thread by default.
+PyObject *raise_rc(int rc, const char *what, const char *msg = nullptr)
+{
+	PyErr_Format(rc == GF2BV_ERR_ARG ? PyExc_ValueError : PyExc_RuntimeError, "gf2bv_amd: HIP %s failed (%d): %s", what, rc,
+	             msg ? msg : gf2bv_last_error());
+	return nullptr;
+}
+
 // The digits that can hold bits 0..cols of every equation (sign ignored, higher bits ignored), gathered into ONE
 // buffer for the C ABI.  Two phases: offsets + source pointers row by row (type check), then the copy -- into memory
 // that is NOT value-initialised first, and by several threads when it is large (the GIL is held by the caller,
@@ -393,7 +410,7 @@ struct DigitGather {
 	std::vector<int64_t> off = std::vector<int64_t>(1, 0);    // off[r] .. off[r+1]: digits of row r
 	std::vector<const uint32_t *> src;                         // first digit of row r
 	Staging own;
-	uint32_t *digits = nullptr;                                // (gather(): every row, in `own`)
+	uint32_t *digits = nullptr;                                // (gather_list(): every row, in `own`)
 	// `src` points into the ints' ob_digit arrays.  m4ri_solve gathers before it first drops the GIL, so borrowed pointers do;
 	// m4ri_solve_many gathers chunk k + 1 AFTER it dropped the GIL to wait for chunk k - 1 -- another Python thread may have
 	// emptied the caller's lists by then -- and therefore holds a strong reference to every int until the call ends.
@@ -421,9 +438,12 @@ struct DigitGather {
 		}
 		return true;
 	}
-	bool gather()
+	// the digits of one list of equations
+	bool gather_list(PyObject *list, Py_ssize_t cols)
 	{
-		if (!gather_rows(0, src.size(), (size_t)1 << 30, own)) return false;
+		const size_t rows = (size_t)PyList_GET_SIZE(list);
+		off.reserve(rows + 1); src.reserve(rows);
+		if (!add(list, cols) || !gather_rows(0, src.size(), (size_t)1 << 30, own)) return false;
 		digits = own.digits;
 		return true;
 	}
@@ -467,6 +487,18 @@ struct DigitGather {
 	}
 };
 
+// The prologue of the entries that take one list of equations (m4ri_solve, m4ri_solve_rhs, m4ri_factor): the list and its shape.
+// DigitGather::gather_list then collects the digits.
+bool parse_equations(PyObject *list, PyObject *cols_obj, PyObject *mode_obj, Py_ssize_t *rows, Py_ssize_t *cols, long *mode)
+{
+	if (!PyList_Check(list)) {
+		PyErr_SetString(PyExc_TypeError, "The first argument equations must be a list");
+		return false;
+	}
+	*rows = PyList_GET_SIZE(list);
+	return parse_cols_mode(cols_obj, mode_obj, cols, mode) && rows_cover_cols(*rows, *cols);
+}
+
 // ------------------------------------------------------------------------------------------------
 // m4ri_solve(equations, cols, mode) -- gf2bv/_internal.c:359-502
 PyObject *py_m4ri_solve(PyObject *, PyObject *const *args, Py_ssize_t nargs)
@@ -475,33 +507,18 @@ PyObject *py_m4ri_solve(PyObject *, PyObject *const *args, Py_ssize_t nargs)
 	int device = default_device();
 	if (nargs == 4 && !parse_device(args[3], &device)) return nullptr;
 	PyObject *list = args[0];
-	if (!PyList_Check(list)) {
-		PyErr_SetString(PyExc_TypeError, "The first argument equations must be a list");
-		return nullptr;
-	}
-	Py_ssize_t cols;
+	Py_ssize_t rows, cols;
 	long mode;
-	if (!parse_cols_mode(args[1], args[2], &cols, &mode)) return nullptr;
-	const Py_ssize_t rows = PyList_GET_SIZE(list);
-	if (rows < cols) {
-		PyErr_SetString(PyExc_ValueError,
-		                "Number of rows must be greater than or equal to number of columns, try pad with zeros.");
-		return nullptr;
-	}
+	if (!parse_equations(list, args[1], args[2], &rows, &cols, &mode)) return nullptr;
 	DigitGather dg;
-	dg.off.reserve((size_t)rows + 1); dg.src.reserve((size_t)rows);
-	if (!dg.add(list, cols) || !dg.gather()) return nullptr;
+	if (!dg.gather_list(list, cols)) return nullptr;
 
 	gf2bv_result *res = nullptr;
 	int rc;
 	Py_BEGIN_ALLOW_THREADS          // same place the reference drops the GIL (_internal.c:429)
 	rc = gf2bv_solve_digits(dg.digits, dg.off.data(), PyLong_SHIFT, rows, cols, (int)mode, device, &res);
 	Py_END_ALLOW_THREADS
-	if (rc != GF2BV_OK) {
-		PyErr_Format(rc == GF2BV_ERR_ARG ? PyExc_ValueError : PyExc_RuntimeError,
-		             "gf2bv_amd: HIP solve failed (%d): %s", rc, gf2bv_last_error());
-		return nullptr;
-	}
+	if (rc != GF2BV_OK) return raise_rc(rc, "solve");
 	return result_to_py(res, mode, device);
 }
 
@@ -567,31 +584,20 @@ PyObject *py_m4ri_solve_rhs(PyObject *, PyObject *const *args, Py_ssize_t nargs)
 	int device = default_device();
 	if (nargs == 5 && !parse_device(args[4], &device)) return nullptr;
 	PyObject *list = args[0], *rhs = args[3];
-	if (!PyList_Check(list)) {
-		PyErr_SetString(PyExc_TypeError, "The first argument equations must be a list");
-		return nullptr;
-	}
 	if (!PyList_Check(rhs)) {
 		PyErr_SetString(PyExc_TypeError, "The right-hand sides must be a list of integers");
 		return nullptr;
 	}
-	Py_ssize_t cols;
+	Py_ssize_t rows, cols;
 	long mode;
-	if (!parse_cols_mode(args[1], args[2], &cols, &mode)) return nullptr;
-	const Py_ssize_t rows = PyList_GET_SIZE(list);
-	if (rows < cols) {
-		PyErr_SetString(PyExc_ValueError,
-		                "Number of rows must be greater than or equal to number of columns, try pad with zeros.");
-		return nullptr;
-	}
+	if (!parse_equations(list, args[1], args[2], &rows, &cols, &mode)) return nullptr;
 	const Py_ssize_t nrhs = PyList_GET_SIZE(rhs);
 	if (nrhs == 0) return PyList_New(0);
 	const int64_t rw = (rows + 63) / 64;
 	std::vector<uint64_t> words;
 	if (!rhs_list_words(rhs, rows, words)) return nullptr;
 	DigitGather dg;
-	dg.off.reserve((size_t)rows + 1); dg.src.reserve((size_t)rows);
-	if (!dg.add(list, cols) || !dg.gather()) return nullptr;
+	if (!dg.gather_list(list, cols)) return nullptr;
 	std::vector<gf2bv_result *> res((size_t)nrhs, nullptr);
 	int rc;
 	Py_BEGIN_ALLOW_THREADS
@@ -599,23 +605,9 @@ PyObject *py_m4ri_solve_rhs(PyObject *, PyObject *const *args, Py_ssize_t nargs)
 	Py_END_ALLOW_THREADS
 	if (rc != GF2BV_OK) {
 		for (gf2bv_result *r : res) if (r) gf2bv_result_free(r);
-		PyErr_Format(rc == GF2BV_ERR_ARG ? PyExc_ValueError : PyExc_RuntimeError,
-		             "gf2bv_amd: HIP solve failed (%d): %s", rc, gf2bv_last_error());
-		return nullptr;
+		return raise_rc(rc, "solve");
 	}
-	PyObject *out = PyList_New(nrhs);
-	if (!out) { for (gf2bv_result *r : res) gf2bv_result_free(r); return nullptr; }
-	for (Py_ssize_t j = 0; j < nrhs; j++) {
-		PyObject *v = result_to_py(res[(size_t)j], mode, device);       // (frees the handle)
-		res[(size_t)j] = nullptr;
-		if (!v) {
-			for (Py_ssize_t k = j + 1; k < nrhs; k++) gf2bv_result_free(res[(size_t)k]);
-			Py_DECREF(out);
-			return nullptr;
-		}
-		PyList_SET_ITEM(out, j, v);
-	}
-	return out;
+	return results_to_list(res, mode, device);
 }
 
 // ---- Factorization: a kept factorization of one matrix (gf2bv_factor_*; no counterpart in the reference) --------------------
@@ -724,9 +716,7 @@ PyObject *factor_solve(FactorObject *self, PyObject *rhs)
 	if (have_view) PyBuffer_Release(&view);
 	if (rc != GF2BV_OK) {
 		for (gf2bv_result *r : res) if (r) gf2bv_result_free(r);
-		PyErr_Format(rc == GF2BV_ERR_ARG ? PyExc_ValueError : PyExc_RuntimeError,
-		             "gf2bv_amd: HIP solve failed (%d): %s", rc, gf2bv_last_error());
-		return nullptr;
+		return raise_rc(rc, "solve");
 	}
 	return results_to_list(res, self->mode, self->device);
 }
@@ -781,32 +771,17 @@ PyObject *py_m4ri_factor(PyObject *, PyObject *const *args, Py_ssize_t nargs)
 	int device = default_device();
 	if (nargs == 4 && !parse_device(args[3], &device)) return nullptr;
 	PyObject *list = args[0];
-	if (!PyList_Check(list)) {
-		PyErr_SetString(PyExc_TypeError, "The first argument equations must be a list");
-		return nullptr;
-	}
-	Py_ssize_t cols;
+	Py_ssize_t rows, cols;
 	long mode;
-	if (!parse_cols_mode(args[1], args[2], &cols, &mode)) return nullptr;
-	const Py_ssize_t rows = PyList_GET_SIZE(list);
-	if (rows < cols) {
-		PyErr_SetString(PyExc_ValueError,
-		                "Number of rows must be greater than or equal to number of columns, try pad with zeros.");
-		return nullptr;
-	}
+	if (!parse_equations(list, args[1], args[2], &rows, &cols, &mode)) return nullptr;
 	DigitGather dg;
-	dg.off.reserve((size_t)rows + 1); dg.src.reserve((size_t)rows);
-	if (!dg.add(list, cols) || !dg.gather()) return nullptr;
+	if (!dg.gather_list(list, cols)) return nullptr;
 	gf2bv_factor *h = nullptr;
 	int rc;
 	Py_BEGIN_ALLOW_THREADS
 	rc = gf2bv_factor_digits(dg.digits, dg.off.data(), PyLong_SHIFT, rows, cols, (int)mode, device, &h);
 	Py_END_ALLOW_THREADS
-	if (rc != GF2BV_OK) {
-		PyErr_Format(rc == GF2BV_ERR_ARG ? PyExc_ValueError : PyExc_RuntimeError,
-		             "gf2bv_amd: HIP factorization failed (%d): %s", rc, gf2bv_last_error());
-		return nullptr;
-	}
+	if (rc != GF2BV_OK) return raise_rc(rc, "factorization");
 	FactorObject *f = PyObject_New(FactorObject, Factorization_Type);
 	if (!f) { gf2bv_factor_free(h); return nullptr; }
 	f->h = h; f->rows = rows; f->cols = cols; f->mode = mode; f->device = device;
@@ -828,12 +803,7 @@ PyObject *py_m4ri_solve_packed(PyObject *, PyObject *const *args, Py_ssize_t nar
 	if ((rows == -1 || words == -1) && PyErr_Occurred()) return nullptr;
 	Py_ssize_t cols;
 	long mode;
-	if (!parse_cols_mode(args[3], args[4], &cols, &mode)) return nullptr;
-	if (rows < cols) {
-		PyErr_SetString(PyExc_ValueError,
-		                "Number of rows must be greater than or equal to number of columns, try pad with zeros.");
-		return nullptr;
-	}
+	if (!parse_cols_mode(args[3], args[4], &cols, &mode) || !rows_cover_cols(rows, cols)) return nullptr;
 	Py_buffer view;
 	if (PyObject_GetBuffer(args[0], &view, PyBUF_C_CONTIGUOUS) != 0) return nullptr;
 	if (words <= 0 || view.len != rows * words * 8 || words * 64 < cols + 1) {
@@ -850,11 +820,7 @@ PyObject *py_m4ri_solve_packed(PyObject *, PyObject *const *args, Py_ssize_t nar
 	rc = gf2bv_solve_digits(static_cast<const uint32_t *>(view.buf), off.data(), 32, rows, cols, (int)mode, device, &res);
 	Py_END_ALLOW_THREADS
 	PyBuffer_Release(&view);
-	if (rc != GF2BV_OK) {
-		PyErr_Format(rc == GF2BV_ERR_ARG ? PyExc_ValueError : PyExc_RuntimeError,
-		             "gf2bv_amd: HIP solve failed (%d): %s", rc, gf2bv_last_error());
-		return nullptr;
-	}
+	if (rc != GF2BV_OK) return raise_rc(rc, "solve");
 	return result_to_py(res, mode, device);
 }
 
@@ -893,11 +859,7 @@ PyObject *py_m4ri_solve_many(PyObject *, PyObject *const *args, Py_ssize_t nargs
 			PyErr_SetString(PyExc_ValueError, "All systems of a batch need the same number of rows, pad with zeros.");
 			return nullptr;
 		}
-		if (rows < cols) {
-			PyErr_SetString(PyExc_ValueError,
-			                "Number of rows must be greater than or equal to number of columns, try pad with zeros.");
-			return nullptr;
-		}
+		if (!rows_cover_cols(rows, cols)) return nullptr;
 		if (!dg.add(list, cols)) return nullptr;
 	}
 	// The digits go to the library in CHUNKS of whole systems, at most GF2BV_BATCH_CHUNK_MB MiB each (default 2048; an even
@@ -979,10 +941,7 @@ PyObject *py_m4ri_solve_many(PyObject *, PyObject *const *args, Py_ssize_t nargs
 	join(ck[0]); join(ck[1]);
 	if (pyerr || rc != GF2BV_OK) {
 		for (gf2bv_result *r : res) if (r) gf2bv_result_free(r);
-		if (!pyerr)
-			PyErr_Format(rc == GF2BV_ERR_ARG ? PyExc_ValueError : PyExc_RuntimeError,
-			             "gf2bv_amd: HIP solve failed (%d): %s", rc, err.c_str());
-		return nullptr;
+		return pyerr ? nullptr : raise_rc(rc, "solve", err.c_str());
 	}
 	PyObject *out = PyList_New(nsys);
 	Py_ssize_t done = 0;

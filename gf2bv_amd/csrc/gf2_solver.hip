@@ -1616,9 +1616,13 @@ int enqueue_backward_gang(Solver &S)
 	return GF2BV_OK;
 }
 
-int enqueue_backward_single(Solver &S)
+// Back-substitution of the columns ycols: up to GF2_BS_MAXRHS of them (kernel dimensions of the reference's use: solve_all
+// caps at 16) the parity path, GF2_BSV of them per pass over U; more: the table sweeps over the bit matrix Y (one pass over Y
+// per panel whatever the dimension).  GF2BV_YSWEEP sends every count to the sweeps (the general path, for cross-checking).
+int enqueue_backsub(Solver &S, const std::vector<int> &ycols)
 {
-	return enqueue_backward_parity(S, std::vector<int>(1, (int)S.cols));
+	if ((i64)ycols.size() <= GF2_BS_MAXRHS && !getenv("GF2BV_YSWEEP")) return enqueue_backward_parity(S, ycols);
+	return enqueue_backward(S, ycols);
 }
 
 int solver_enqueue(Solver &S)
@@ -1630,20 +1634,22 @@ int solver_enqueue(Solver &S)
 	rc = enqueue_forward(S);
 	tr.mark("enqueue_forward");
 	if (rc) return rc;
-	if (S.mode == GF2BV_MODE_SINGLE) {
-		if (getenv("GF2BV_YSWEEP")) {                  // the general multi-RHS path, for cross-checking
-			std::vector<int> yc(1, (int)S.cols);
-			return enqueue_backward(S, yc);
-		}
-		return enqueue_backward_single(S);
-	}
+	if (S.mode == GF2BV_MODE_SINGLE) return enqueue_backsub(S, { (int)S.cols });
 	return GF2BV_OK;
 }
 
-// Export, first half: (mode 1: rank and pivot columns to the host, kernel-basis back-substitution,)
-// then the asynchronous device-to-host copies of everything the result needs.
-// The kernel basis needs rank and pivot columns on the host (one sync) to lay out the free columns in M4RI's order
-// (_internal.c:348): S.hst and S.free_order.
+// The free columns in M4RI's kernel order (_internal.c:348): positions rank .. cols of the identity
+// permutation after position i was swapped with piv[i], i < rank, in turn
+std::vector<int> m4ri_free_order(const int32_t *piv, i64 rank, i64 cols)
+{
+	std::vector<int> order(cols);
+	for (i64 i = 0; i < cols; i++) order[i] = (int)i;
+	for (i64 i = 0; i < rank; i++) std::swap(order[i], order[piv[i]]);
+	return std::vector<int>(order.begin() + rank, order.end());
+}
+
+// The kernel basis needs rank and pivot columns on the host (one sync) to lay out the free columns in M4RI's order:
+// S.hst and S.free_order.
 int load_free_order(Solver &S)
 {
 	HIPCHK(hipMemcpyAsync(&S.hst, S.st, sizeof S.hst, hipMemcpyDeviceToHost, S.sA));
@@ -1651,28 +1657,15 @@ int load_free_order(Solver &S)
 	std::vector<int32_t> piv(S.hst.rank);
 	if (S.hst.rank)
 		HIPCHK(hipMemcpy(piv.data(), S.pivcol, sizeof(int) * S.hst.rank, hipMemcpyDeviceToHost));
-	std::vector<int> order(S.cols);
-	for (i64 i = 0; i < S.cols; i++) order[i] = (int)i;
-	for (int i = 0; i < S.hst.rank; i++) std::swap(order[i], order[piv[i]]);
-	S.free_order.assign(order.begin() + S.hst.rank, order.end());
+	S.free_order = m4ri_free_order(piv.data(), S.hst.rank, S.cols);
 	return GF2BV_OK;
 }
 
-int finish_begin(Solver &S)
+// The asynchronous device-to-host copies of everything a result needs (state, back-substitution output, panel records,
+// pivot columns), then S.evx.
+int enqueue_export(Solver &S)
 {
 	HIPCHK(pool().event(&S.evx, true));
-	if (S.mode == GF2BV_MODE_AFFINE_SPACE) {
-		int rc = load_free_order(S);
-		if (rc) return rc;
-		std::vector<int> yc;
-		if (!S.hst.inconsistent) yc = S.free_order;
-		yc.push_back((int)S.cols);
-		// up to GF2_BS_MAXRHS right-hand sides (kernel dimensions of the reference's use: solve_all caps at 16): the parity
-		// path, GF2_BSV of them per pass over U; larger bases: the table sweeps over the bit matrix Y (one pass over Y per
-		// panel whatever the dimension)
-		rc = ((int)yc.size() <= GF2_BS_MAXRHS && !getenv("GF2BV_YSWEEP")) ? enqueue_backward_parity(S, yc) : enqueue_backward(S, yc);
-		if (rc) return rc;
-	}
 	HIPCHK(hipMemcpyAsync(&S.hst, S.st, sizeof S.hst, hipMemcpyDeviceToHost, S.sA));
 	S.hout.resize((size_t)S.ny * std::max<i64>(1, S.cw));
 	HIPCHK(hipMemcpyAsync(S.hout.data(), S.out, sizeof(u64) * S.hout.size(), hipMemcpyDeviceToHost, S.sA));
@@ -1684,6 +1677,61 @@ int finish_begin(Solver &S)
 	return GF2BV_OK;
 }
 
+// Export, first half: (mode 1: rank and pivot columns to the host, kernel-basis back-substitution,) the copies.
+int finish_begin(Solver &S)
+{
+	if (S.mode == GF2BV_MODE_AFFINE_SPACE) {
+		int rc = load_free_order(S);
+		if (rc) return rc;
+		std::vector<int> yc;
+		if (!S.hst.inconsistent) yc = S.free_order;
+		yc.push_back((int)S.cols);
+		if ((rc = enqueue_backsub(S, yc))) return rc;
+	}
+	return enqueue_export(S);
+}
+
+// After the streams of a solve are synchronised: an expired stream hand-over gate voids the solve -- an error under flag
+// synchronisation; else the device is marked and the caller runs the solve once more with events.
+int handover_verdict(Solver &S)
+{
+	if (!S.hst.gate_timeout) return GF2BV_OK;
+	if (!S.flag_sync) return fail(GF2BV_ERR_HIP, "a stream hand-over gate timed out on the device");
+	forget_concurrency(S.device);
+	return GF2BV_RETRY_EVENTS;
+}
+
+// The fields every result shares: status, rank (= the pivots' count), cw, dim, pivots, origin (the cw words at `origin`
+// when solved, zero otherwise).  The caller adds the basis and the stats.
+std::unique_ptr<gf2bv_result> new_result(bool solved, i64 cols, const int32_t *piv, i64 rank, const u64 *origin)
+{
+	const i64 cw = (cols + 63) / 64;
+	std::unique_ptr<gf2bv_result> R(new gf2bv_result());
+	R->status = solved ? GF2BV_STATUS_SOLVED : GF2BV_STATUS_INCONSISTENT;
+	R->rank = rank;
+	R->cw = cw;
+	R->dim = cols - rank;
+	R->pivots.assign(piv, piv + rank);
+	R->origin.assign((size_t)std::max<i64>(1, cw), 0);
+	if (solved) std::copy(origin, origin + cw, R->origin.begin());
+	return R;
+}
+
+// The kernel basis out of back-substitution outputs 0 .. dim (max(1, cw) words apart): vector t is output t with the bit of
+// its free column free_order[t] set.
+std::vector<u64> basis_rows(const u64 *hout, i64 cw, const std::vector<int> &free_order, i64 dim)
+{
+	const i64 cwx = std::max<i64>(1, cw);
+	std::vector<u64> basis((size_t)(dim * cwx), 0);
+	for (i64 t = 0; t < dim; t++) {
+		u64 *v = basis.data() + (size_t)(t * cwx);
+		std::copy(hout + (size_t)(t * cwx), hout + (size_t)(t * cwx + cw), v);
+		const int f = free_order[(size_t)t];
+		v[f >> 6] |= 1ull << (f & 63);
+	}
+	return basis;
+}
+
 void fill_stats(const Solver &S, gf2bv_result *R);
 
 // Export, second half: wait for the copies and build the result object.
@@ -1693,39 +1741,16 @@ int finish_end(Solver &S, gf2bv_result **out)
 	HIPCHK(hipStreamSynchronize(S.sA));
 	HIPCHK(hipStreamSynchronize(S.sB));
 	tr.mark("finish: sync");
+	int rc = handover_verdict(S);
+	if (rc) return rc;
 	const SolveState &hst = S.hst;
-	if (hst.gate_timeout) {
-		if (!S.flag_sync) return fail(GF2BV_ERR_HIP, "a stream hand-over gate timed out on the device");
-		forget_concurrency(S.device);
-		return GF2BV_RETRY_EVENTS;
-	}
-	const std::vector<u64> &hout = S.hout;
+	const i64 cwx = std::max<i64>(1, S.cw);
 	S.hpiv.resize(hst.rank);
-	const std::vector<int32_t> &piv = S.hpiv;
-
-	gf2bv_result *R = new gf2bv_result();
-	R->status = hst.inconsistent ? GF2BV_STATUS_INCONSISTENT : GF2BV_STATUS_SOLVED;
-	R->rank = hst.rank;
-	R->cw = S.cw;
-	R->dim = S.cols - hst.rank;
-	R->pivots = piv;
-	R->origin.assign(std::max<i64>(1, S.cw), 0);
-	if (R->status == GF2BV_STATUS_SOLVED) {
-		const u64 *o = hout.data() + (size_t)(S.ny - 1) * std::max<i64>(1, S.cw);
-		std::copy(o, o + S.cw, R->origin.begin());
-		if (S.mode == GF2BV_MODE_AFFINE_SPACE) {
-			R->basis.assign((size_t)R->dim * std::max<i64>(1, S.cw), 0);
-			for (i64 t = 0; t < R->dim; t++) {
-				u64 *v = R->basis.data() + (size_t)t * S.cw;
-				std::copy(hout.data() + (size_t)t * S.cw, hout.data() + (size_t)(t + 1) * S.cw, v);
-				int f = S.free_order[t];
-				v[f >> 6] |= 1ull << (f & 63);
-			}
-		}
-	}
-	fill_stats(S, R);
+	std::unique_ptr<gf2bv_result> R = new_result(!hst.inconsistent, S.cols, S.hpiv.data(), hst.rank, S.hout.data() + (size_t)((S.ny - 1) * cwx));
+	if (!hst.inconsistent && S.mode == GF2BV_MODE_AFFINE_SPACE) R->basis = basis_rows(S.hout.data(), S.cw, S.free_order, R->dim);
+	fill_stats(S, R.get());
 	tr.mark("finish: result");
-	*out = R;
+	*out = R.release();
 	return GF2BV_OK;
 }
 
@@ -1843,7 +1868,7 @@ int solve_gang(Solver &S, gf2bv_result **out)
 		const bool per_system = !S.gang_bs;      // (GF2BV_GANG_BS=0, A/B: one chain per system, as rounds 1-3)
 		if (per_system)
 			for (int s = 0; s < S.nsys; s++) {
-				rc = enqueue_backward_single(V[s]);
+				rc = enqueue_backward_parity(V[s], { (int)S.cols });
 				if (rc) return rc;
 			}
 		else {
@@ -1920,6 +1945,41 @@ int check_shape(i64 rows, i64 cols, int mode)
 	return GF2BV_OK;
 }
 
+// One matrix as the single-system entries take it, in one of three forms: d_words (device, row-major, `stride` words apart)
+// | h_words (host, row-major, `stride` words apart) | h_digits + h_off (host, bpd bits per digit, row r = digits
+// h_off[r] .. h_off[r + 1]).  The form is the one whose pointer is set (the digits form: h_off; h_digits may be null when
+// there are no digits).
+struct MatrixInput {
+	const u64 *d_words = nullptr, *h_words = nullptr;
+	i64 stride = 0;
+	const uint32_t *h_digits = nullptr;
+	const i64 *h_off = nullptr;
+	int bpd = 0;
+};
+
+// The argument checks of a matrix, made before any device is touched: the shape, then those of the form in use (no form
+// pointer set: the caller passed a null matrix)
+int check_matrix_input(const MatrixInput &in, i64 rows, i64 cols, int mode)
+{
+	int rc = check_shape(rows, cols, mode);
+	if (rc) return rc;
+	const i64 wt = (cols + 1 + 63) / 64;
+	if (in.h_off) {
+		if (in.bpd < 1 || in.bpd > 32) return fail(GF2BV_ERR_ARG, "bits_per_digit must be 1..32");
+		if (in.h_off[0] != 0) return fail(GF2BV_ERR_ARG, "digit offsets must start at 0");
+		for (i64 r = 0; r < rows; r++)
+			if (in.h_off[r + 1] < in.h_off[r]) return fail(GF2BV_ERR_ARG, "digit offsets must not decrease");
+		if (!in.h_digits && in.h_off[rows] > 0) return fail(GF2BV_ERR_ARG, "null pointer");
+	} else if (in.h_words) {
+		if (in.stride < wt) return fail(GF2BV_ERR_ARG, "stride_words does not cover cols+1 bits");
+	} else if (in.d_words) {
+		if (in.stride % 2 != 0 || in.stride < wt || ((uintptr_t)in.d_words & 15))
+			return fail(GF2BV_ERR_ARG, "device matrix needs 16-byte alignment and an even stride_words covering cols+1 bits");
+	} else
+		return fail(GF2BV_ERR_ARG, "null pointer");
+	return GF2BV_OK;
+}
+
 // ---- small systems: the whole solve in one launch (k_small_solve) ---------------------------------------------------
 // Eligible: the augmented matrix + two sets of nibble tables fit the LDS of one workgroup ((rows + 512) x odd row pitch <= 18432 words = 144 KiB, cols <= 1023,
 // rows <= 4096).  Per call: ONE host-to-device copy out of a pinned staging buffer (offsets + digits, or the packed words;
@@ -1975,14 +2035,7 @@ int small_stage(SmallStage &G, size_t in_bytes, size_t out_bytes)
 	return GF2BV_OK;
 }
 
-// One of: d_words (device, row-major, d_stride) | h_words (host, row-major, h_stride) | h_digits + h_off (host, bpd bits per digit)
-struct SmallInput {
-	const u64 *d_words = nullptr; i64 d_stride = 0;
-	const u64 *h_words = nullptr; i64 h_stride = 0;
-	const uint32_t *h_digits = nullptr; const i64 *h_off = nullptr; int bpd = 0;
-};
-
-int small_solve(const SmallInput &in, i64 rows, i64 cols, int mode, int device, hipStream_t stream, gf2bv_result **out)
+int small_solve(const MatrixInput &in, i64 rows, i64 cols, int mode, int device, hipStream_t stream, gf2bv_result **out)
 {
 	const auto t_begin = std::chrono::steady_clock::now();
 	const i64 wt = (cols + 1 + 63) / 64, cw = (cols + 63) / 64;
@@ -1993,7 +2046,7 @@ int small_solve(const SmallInput &in, i64 rows, i64 cols, int mode, int device, 
 	const bool probe = getenv("GF2BV_SMALL_PROBE") != nullptr;
 	size_t in_bytes = 0;
 	i64 ndig = 0;
-	if (in.h_digits) { ndig = in.h_off[rows]; in_bytes = sizeof(i64) * (size_t)(rows + 1) + sizeof(uint32_t) * (size_t)std::max<i64>(ndig, 1); }
+	if (in.h_off) { ndig = in.h_off[rows]; in_bytes = sizeof(i64) * (size_t)(rows + 1) + sizeof(uint32_t) * (size_t)std::max<i64>(ndig, 1); }
 	else if (in.h_words) in_bytes = sizeof(u64) * (size_t)(rows * wt);
 	struct Stage { SmallStage *s; ~Stage() { stage_pool().give(s); } } stage{ stage_pool().take(device) };
 	SmallStage &G = *stage.s;
@@ -2006,7 +2059,7 @@ int small_solve(const SmallInput &in, i64 rows, i64 cols, int mode, int device, 
 	if (!st && !in.d_words) { HIPCHK(pool().stream(&st, device, false)); own_stream = true; }
 	struct Back { hipStream_t st; int device; bool own; void *d_in; ~Back() { if (own) pool().release_stream(st, device, false); pool().release(d_in); } } back{ st, device, own_stream, nullptr };
 	const u64 *d_src = in.d_words;
-	i64 d_stride = in.d_stride;
+	i64 d_stride = in.stride;
 	const uint32_t *d_dig = nullptr;
 	const i64 *d_off = nullptr;
 	// inputs up to 32 KiB: no copy at all -- the kernel reads the pinned staging buffer over the link (two batched round trips;
@@ -2016,13 +2069,13 @@ int small_solve(const SmallInput &in, i64 rows, i64 cols, int mode, int device, 
 	if (in_bytes) {
 		if (!zero_copy) HIPCHK(pool().alloc(&back.d_in, in_bytes, device));
 		char *d_base = zero_copy ? G.h_in : (char *)back.d_in;
-		if (in.h_digits) {
+		if (in.h_off) {
 			memcpy(G.h_in, in.h_off, sizeof(i64) * (size_t)(rows + 1));
 			if (ndig) memcpy(G.h_in + sizeof(i64) * (size_t)(rows + 1), in.h_digits, sizeof(uint32_t) * (size_t)ndig);
 			d_off = (const i64 *)d_base;
 			d_dig = (const uint32_t *)(d_base + sizeof(i64) * (size_t)(rows + 1));
 		} else {
-			for (i64 r = 0; r < rows; r++) memcpy(G.h_in + sizeof(u64) * (size_t)(r * wt), in.h_words + r * in.h_stride, sizeof(u64) * (size_t)wt);
+			for (i64 r = 0; r < rows; r++) memcpy(G.h_in + sizeof(u64) * (size_t)(r * wt), in.h_words + r * in.stride, sizeof(u64) * (size_t)wt);
 			d_src = (const u64 *)d_base; d_stride = wt;
 		}
 		if (!zero_copy) HIPCHK(hipMemcpyAsync(back.d_in, G.h_in, in_bytes, hipMemcpyHostToDevice, st));
@@ -2054,32 +2107,24 @@ int small_solve(const SmallInput &in, i64 rows, i64 cols, int mode, int device, 
 	const i64 rank = ho[0];
 	const bool bad = ho[1] != 0;
 	if (rank < 0 || rank > cols) return fail(GF2BV_ERR_HIP, "small solve returned an impossible rank");
-	gf2bv_result *R = new gf2bv_result();
-	R->status = bad ? GF2BV_STATUS_INCONSISTENT : GF2BV_STATUS_SOLVED;
-	R->rank = rank; R->cw = cw; R->dim = cols - rank;
 	const int32_t *pv = (const int32_t *)(G.h_out + 16);
-	R->pivots.assign(pv, pv + rank);
-	R->origin.assign(std::max<i64>(1, cw), 0);
 	const u64 *org = (const u64 *)(G.h_out + head);
-	if (!bad) {
-		std::copy(org, org + cw, R->origin.begin());
-		if (want_basis) {
-			// free columns in M4RI's kernel order (_internal.c:348); the kernel wrote the vectors in ascending column order
-			std::vector<int> order(cols), slot(cols, -1);
-			for (i64 i = 0; i < cols; i++) order[i] = (int)i;
-			for (i64 i = 0; i < rank; i++) std::swap(order[i], order[pv[i]]);
-			std::vector<char> isp(cols, 0);
-			for (i64 i = 0; i < rank; i++) isp[pv[i]] = 1;
-			int j = 0;
-			for (i64 c = 0; c < cols; c++) if (!isp[c]) slot[c] = j++;
-			const u64 *Y = org + cw;
-			R->basis.assign((size_t)R->dim * std::max<i64>(1, cw), 0);
-			for (i64 t = 0; t < R->dim; t++) {
-				const int f = order[rank + t];
-				u64 *v = R->basis.data() + (size_t)t * cw;
-				std::copy(Y + (size_t)slot[f] * cw, Y + (size_t)(slot[f] + 1) * cw, v);
-				v[f >> 6] |= 1ull << (f & 63);
-			}
+	std::unique_ptr<gf2bv_result> R = new_result(!bad, cols, pv, rank, org);
+	if (!bad && want_basis) {
+		// the kernel wrote the vectors in ascending column order: vector t is the one of free column free_order[t]
+		const std::vector<int> free_order = m4ri_free_order(pv, rank, cols);
+		std::vector<int> slot(cols, -1);
+		std::vector<char> isp(cols, 0);
+		for (i64 i = 0; i < rank; i++) isp[pv[i]] = 1;
+		int j = 0;
+		for (i64 c = 0; c < cols; c++) if (!isp[c]) slot[c] = j++;
+		const u64 *Y = org + cw;
+		R->basis.assign((size_t)R->dim * std::max<i64>(1, cw), 0);
+		for (i64 t = 0; t < R->dim; t++) {
+			const int f = free_order[(size_t)t];
+			u64 *v = R->basis.data() + (size_t)t * cw;
+			std::copy(Y + (size_t)slot[f] * cw, Y + (size_t)(slot[f] + 1) * cw, v);
+			v[f >> 6] |= 1ull << (f & 63);
 		}
 	}
 	gf2bv_stats &s = R->stats;
@@ -2088,7 +2133,7 @@ int small_solve(const SmallInput &in, i64 rows, i64 cols, int mode, int device, 
 	s.n_panels = (int)cw; s.gang_systems = 1; s.tile_words = 0;
 	s.small_path = 1;
 	s.ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-	*out = R;
+	*out = R.release();
 	return GF2BV_OK;
 }
 
@@ -2100,38 +2145,26 @@ int small_solve(const SmallInput &in, i64 rows, i64 cols, int mode, int device, 
 // decides every system's consistency, and one back-substitution over U yields every origin (mode 1: and the kernel basis, once).
 // Scope: one system on one device (no gangs, no column slabs); every size takes the blocked path -- k_small_solve's LDS budget
 // assumes one RHS bit.
-struct RhsInput {              // matrix: d_words (device) | h_words (host) | h_digits + h_off (host); right-hand sides: host or device
-	const u64 *d_words = nullptr, *h_words = nullptr;
-	i64 stride = 0;
-	const uint32_t *h_digits = nullptr;
-	const i64 *h_off = nullptr;
-	int bpd = 0;
-	const u64 *rhs = nullptr;
-	bool rhs_on_device = false;
-	i64 nrhs = 0, rhs_words = 0;
-};
-
-// the argument checks every gf2bv_solve_rhs_* entry makes before it touches a device; clears out[0..nrhs)
-int check_rhs_args(i64 rows, i64 cols, int mode, const void *rhs, i64 nrhs, i64 rhs_words, gf2bv_result **out)
+// The argument checks of the right-hand sides of a gf2bv_solve_rhs_* entry, made before any device is touched (the matrix's
+// come first: check_matrix_input)
+int check_rhs_args(i64 rows, i64 cols, const void *rhs, bool on_device, i64 nrhs, i64 rhs_words)
 {
-	if (!out || !rhs) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (!rhs) return fail(GF2BV_ERR_ARG, "null pointer");
 	if (nrhs < 1) return fail(GF2BV_ERR_ARG, "nrhs must be at least 1");
-	for (i64 j = 0; j < nrhs; j++) out[j] = nullptr;
-	int rc = check_shape(rows, cols, mode);
-	if (rc) return rc;
 	if (nrhs >= (1ll << 31) - 64 - cols) return fail(GF2BV_ERR_ARG, "too many right-hand sides");
 	if (rhs_words < (rows + 63) / 64) return fail(GF2BV_ERR_ARG, "rhs_words does not cover one bit per row");
+	if (on_device && ((uintptr_t)rhs & 7)) return fail(GF2BV_ERR_ARG, "the right-hand sides need 8-byte alignment");
 	return GF2BV_OK;
 }
 
 // The coefficients into the tile-major working matrix S.M (ntiles tiles, srows rows per slab) on S.sA: the digits packed straight into
 // tiles (k_pack_digits puts the affine term at column `cols`; the callers overwrite it), or the words that hold coefficients -- and
 // only those -- copied into tiles (the words right of them are zero-filled)
-int pack_coefficients(const RhsInput &in, i64 rows, i64 cols, i64 ntiles, i64 srows, Solver &S, Scratch &scratch)
+int pack_coefficients(const MatrixInput &in, i64 rows, i64 cols, i64 ntiles, i64 srows, Solver &S, Scratch &scratch)
 {
 	const int device = S.device;
 	const i64 cw = (cols + 63) / 64, rw = (rows + 63) / 64;
-	if (in.h_digits) {
+	if (in.h_off) {
 		const i64 ndig = in.h_off[rows];
 		uint32_t *d_dig = nullptr;
 		i64 *d_off = nullptr;
@@ -2158,9 +2191,10 @@ int pack_coefficients(const RhsInput &in, i64 rows, i64 cols, i64 ntiles, i64 sr
 	return GF2BV_OK;
 }
 
-int solve_rhs(const RhsInput &in, i64 rows, i64 cols, int mode, int device, hipStream_t stream, bool time_kernels, gf2bv_result **out)
+int solve_rhs(const MatrixInput &in, const u64 *rhs, bool rhs_on_device, i64 nrhs, i64 rhs_words, i64 rows, i64 cols, int mode, int device,
+              hipStream_t stream, bool time_kernels, gf2bv_result **out)
 {
-	const i64 nrhs = in.nrhs, cw = (cols + 63) / 64, cwx = std::max<i64>(1, cw), nmw = (nrhs + 63) / 64;
+	const i64 cw = (cols + 63) / 64, cwx = std::max<i64>(1, cw), nmw = (nrhs + 63) / 64;
 	const i64 wt = (cols + nrhs + 63) / 64, ntiles = tiles_for(wt), srows = slab_rows(rows);
 	const i64 rw = (rows + 63) / 64, nrw = ((cols & 63) + nrhs + 63) / 64;
 	Solver S;
@@ -2170,7 +2204,7 @@ int solve_rhs(const RhsInput &in, i64 rows, i64 cols, int mode, int device, hipS
 	else { HIPCHK(pool().stream(&S.sA, device, false)); S.own_sA = true; }
 	S.rows = rows; S.cols = cols; S.mode = mode; S.nrhs = (int)nrhs;
 	S.time_kernels = time_kernels;
-	S.stride = in.h_digits ? ntiles * TW : in.stride;
+	S.stride = in.h_off ? ntiles * TW : in.stride;
 	{
 		const hipError_t e = pool().alloc((void **)&S.M, sizeof(u64) * ntiles * TW * srows + kOuterSlackBytes, device);
 		if (e == hipErrorOutOfMemory) {
@@ -2188,12 +2222,12 @@ int solve_rhs(const RhsInput &in, i64 rows, i64 cols, int mode, int device, hipS
 	HIPCHK(hipMemsetAsync(S.rhs_bad, 0, sizeof(u64) * nmw, S.sA));
 	int rc;
 	if ((rc = pack_coefficients(in, rows, cols, ntiles, srows, S, scratch))) return rc;
-	const u64 *d_rhs = in.rhs;
-	i64 rhs_stride = in.rhs_words;
-	if (!in.rhs_on_device) {          // (only the words that hold rows go up)
+	const u64 *d_rhs = rhs;
+	i64 rhs_stride = rhs_words;
+	if (!rhs_on_device) {             // (only the words that hold rows go up)
 		u64 *d = nullptr;
 		HIPCHK(scratch.alloc((void **)&d, sizeof(u64) * nrhs * rw, device));
-		HIPCHK(hipMemcpy2DAsync(d, rw * 8, in.rhs, in.rhs_words * 8, rw * 8, nrhs, hipMemcpyHostToDevice, S.sA));
+		HIPCHK(hipMemcpy2DAsync(d, rw * 8, rhs, rhs_words * 8, rw * 8, nrhs, hipMemcpyHostToDevice, S.sA));
 		d_rhs = d; rhs_stride = rw;
 	}
 	k_pack_rhs<<<dim3((unsigned)((rw + 3) / 4), (unsigned)std::min<i64>(nrw, 65535)), dim3(256), 0, S.sA>>>(d_rhs, nrhs, rhs_stride, rows, cols,
@@ -2216,54 +2250,22 @@ int solve_rhs(const RhsInput &in, i64 rows, i64 cols, int mode, int device, hipS
 	}
 	const i64 nbasis = (i64)yc.size();
 	for (i64 j = 0; j < nrhs; j++) yc.push_back((int)(cols + j));
-	// (the threshold of finish_begin: up to GF2_BS_MAXRHS columns the parity passes, GF2_BSV at a time; beyond, the sweeps over Y)
-	rc = ((i64)yc.size() <= GF2_BS_MAXRHS && !getenv("GF2BV_YSWEEP")) ? enqueue_backward_parity(S, yc) : enqueue_backward(S, yc);
-	if (rc) return rc;
-	// export
-	HIPCHK(pool().event(&S.evx, true));
-	HIPCHK(hipMemcpyAsync(&S.hst, S.st, sizeof S.hst, hipMemcpyDeviceToHost, S.sA));
-	S.hout.resize((size_t)S.ny * cwx);
-	HIPCHK(hipMemcpyAsync(S.hout.data(), S.out, sizeof(u64) * S.hout.size(), hipMemcpyDeviceToHost, S.sA));
-	S.hp.resize(std::max(1, S.npanels));
-	HIPCHK(hipMemcpyAsync(S.hp.data(), S.panels, sizeof(PanelRec) * S.hp.size(), hipMemcpyDeviceToHost, S.sA));
-	S.hpiv.resize(std::max<i64>(1, S.maxr));
-	HIPCHK(hipMemcpyAsync(S.hpiv.data(), S.pivcol, sizeof(int) * S.hpiv.size(), hipMemcpyDeviceToHost, S.sA));
+	if ((rc = enqueue_backsub(S, yc))) return rc;
 	HIPCHK(hipMemcpyAsync(bad.data(), S.rhs_bad, sizeof(u64) * nmw, hipMemcpyDeviceToHost, S.sA));
-	HIPCHK(hipEventRecord(S.evx, S.sA));
+	if ((rc = enqueue_export(S))) return rc;
 	HIPCHK(hipStreamSynchronize(S.sA));
 	HIPCHK(hipStreamSynchronize(S.sB));
-	if (S.hst.gate_timeout) {
-		if (!S.flag_sync) return fail(GF2BV_ERR_HIP, "a stream hand-over gate timed out on the device");
-		forget_concurrency(S.device);
-		return GF2BV_RETRY_EVENTS;
-	}
+	if ((rc = handover_verdict(S))) return rc;
 	(void)hipEventElapsedTime(&S.ms_pack, p0, p1);
 	S.hpiv.resize(S.hst.rank);
+	// (nbasis == dim when some system is consistent in mode 1)
+	const std::vector<u64> basis = basis_rows(S.hout.data(), cw, S.free_order, nbasis);
 	std::vector<std::unique_ptr<gf2bv_result>> res((size_t)nrhs);
 	for (i64 j = 0; j < nrhs; j++) {
-		res[(size_t)j].reset(new gf2bv_result());
-		gf2bv_result *R = res[(size_t)j].get();
 		const bool ok = !((bad[(size_t)(j >> 6)] >> (j & 63)) & 1);
-		R->status = ok ? GF2BV_STATUS_SOLVED : GF2BV_STATUS_INCONSISTENT;
-		R->rank = S.hst.rank;
-		R->cw = cw;
-		R->dim = cols - S.hst.rank;
-		R->pivots = S.hpiv;
-		R->origin.assign((size_t)cwx, 0);
-		if (ok) {
-			const u64 *o = S.hout.data() + (size_t)(nbasis + j) * cwx;
-			std::copy(o, o + cw, R->origin.begin());
-			if (mode == GF2BV_MODE_AFFINE_SPACE) {           // (nbasis == dim: some system is consistent)
-				R->basis.assign((size_t)R->dim * cwx, 0);
-				for (i64 t = 0; t < R->dim; t++) {
-					u64 *v = R->basis.data() + (size_t)t * cw;
-					std::copy(S.hout.data() + (size_t)t * cwx, S.hout.data() + (size_t)t * cwx + cw, v);
-					const int f = S.free_order[(size_t)t];
-					v[f >> 6] |= 1ull << (f & 63);
-				}
-			}
-		}
-		fill_stats(S, R);
+		res[(size_t)j] = new_result(ok, cols, S.hpiv.data(), S.hst.rank, S.hout.data() + (size_t)((nbasis + j) * cwx));
+		if (ok && mode == GF2BV_MODE_AFFINE_SPACE) res[(size_t)j]->basis = basis;
+		fill_stats(S, res[(size_t)j].get());
 	}
 	for (i64 j = 0; j < nrhs; j++) out[j] = res[(size_t)j].release();
 	return GF2BV_OK;
@@ -2306,7 +2308,7 @@ void release_backsub(Solver &S)
 	S.Y = nullptr; S.ycols = nullptr; S.out = nullptr; S.Minv = nullptr;
 }
 
-int factor_matrix(const RhsInput &in, i64 rows, i64 cols, int mode, int device, hipStream_t stream, gf2bv_factor **out)
+int factor_matrix(const MatrixInput &in, i64 rows, i64 cols, int mode, int device, hipStream_t stream, gf2bv_factor **out)
 {
 	const i64 rw = (rows + 63) / 64, cw = (cols + 63) / 64, cwx = std::max<i64>(1, cw);
 	const i64 tw0 = round_up(cols + kFactorSlots, 128) / 64;          // (the identity starts on a whole 16-byte tile)
@@ -2320,7 +2322,7 @@ int factor_matrix(const RhsInput &in, i64 rows, i64 cols, int mode, int device, 
 	S.own_sA = true;
 	S.rows = rows; S.cols = cols; S.mode = mode;
 	S.nrhs = (int)(wt * 64 - cols);   // (solver_alloc: wt words per row)
-	S.stride = in.h_digits ? ntiles * TW : in.stride;
+	S.stride = in.h_off ? ntiles * TW : in.stride;
 	if (in.d_words && stream) {       // the caller's matrix is read after what its stream has queued
 		hipEvent_t e = nullptr;
 		HIPCHK(pool().event(&e, false));
@@ -2352,31 +2354,19 @@ int factor_matrix(const RhsInput &in, i64 rows, i64 cols, int mode, int device, 
 	HIPCHK(hipStreamSynchronize(S.sA));
 	HIPCHK(hipStreamSynchronize(S.sB));
 	if (S.sC) HIPCHK(hipStreamSynchronize(S.sC));
-	if (S.hst.gate_timeout) {
-		if (!S.flag_sync) return fail(GF2BV_ERR_HIP, "a stream hand-over gate timed out on the device");
-		forget_concurrency(S.device);
-		return GF2BV_RETRY_EVENTS;
-	}
+	if ((rc = handover_verdict(S))) return rc;
 	h->rank = S.hst.rank;
 	h->piv.resize((size_t)h->rank);
 	if (h->rank) HIPCHK(hipMemcpy(h->piv.data(), S.pivcol, sizeof(int) * h->rank, hipMemcpyDeviceToHost));
 	if (mode == GF2BV_MODE_AFFINE_SPACE) {
 		if ((rc = load_free_order(S))) return rc;
 		const i64 dim = cols - h->rank;
-		h->basis.assign((size_t)(dim * cwx), 0);
 		if (dim) {
-			const std::vector<int> &yc = S.free_order;
-			rc = ((i64)yc.size() <= GF2_BS_MAXRHS && !getenv("GF2BV_YSWEEP")) ? enqueue_backward_parity(S, yc) : enqueue_backward(S, yc);
-			if (rc) return rc;
+			if ((rc = enqueue_backsub(S, S.free_order))) return rc;
 			std::vector<u64> hout((size_t)(dim * cwx));
 			HIPCHK(hipMemcpyAsync(hout.data(), S.out, sizeof(u64) * hout.size(), hipMemcpyDeviceToHost, S.sA));
 			HIPCHK(hipStreamSynchronize(S.sA));
-			for (i64 t = 0; t < dim; t++) {
-				u64 *v = h->basis.data() + (size_t)t * cwx;
-				std::copy(hout.data() + (size_t)t * cwx, hout.data() + (size_t)t * cwx + cw, v);
-				const int f = S.free_order[(size_t)t];
-				v[f >> 6] |= 1ull << (f & 63);
-			}
+			h->basis = basis_rows(hout.data(), cw, S.free_order, dim);
 		}
 	}
 	{
@@ -2411,7 +2401,7 @@ int factor_pass(gf2bv_factor *h, const u64 *d_rhs, i64 np, i64 rhs_stride, hipEv
 	HIPCHK(hipEventRecord(ev[2], S.sA));
 	std::vector<int> yc((size_t)np);
 	for (i64 j = 0; j < np; j++) yc[(size_t)j] = (int)(cols + j);
-	int rc = ((i64)yc.size() <= GF2_BS_MAXRHS && !getenv("GF2BV_YSWEEP")) ? enqueue_backward_parity(S, yc) : enqueue_backward(S, yc);
+	int rc = enqueue_backsub(S, yc);
 	if (rc) return rc;
 	HIPCHK(hipEventRecord(ev[3], S.sA));
 	std::vector<u64> hout((size_t)(np * cwx));
@@ -2425,19 +2415,9 @@ int factor_pass(gf2bv_factor *h, const u64 *d_rhs, i64 np, i64 rhs_stride, hipEv
 	for (int i = 0; i < 4; i++) (void)hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]);
 	const float total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
 	for (i64 j = 0; j < np; j++) {
-		std::unique_ptr<gf2bv_result> R(new gf2bv_result());
 		const bool ok = !((hbad >> j) & 1);
-		R->status = ok ? GF2BV_STATUS_SOLVED : GF2BV_STATUS_INCONSISTENT;
-		R->rank = h->rank;
-		R->cw = cw;
-		R->dim = cols - h->rank;
-		R->pivots = h->piv;
-		R->origin.assign((size_t)cwx, 0);
-		if (ok) {
-			const u64 *o = hout.data() + (size_t)j * cwx;
-			std::copy(o, o + cw, R->origin.begin());
-			if (h->mode == GF2BV_MODE_AFFINE_SPACE) R->basis = h->basis;
-		}
+		std::unique_ptr<gf2bv_result> R = new_result(ok, cols, h->piv.data(), h->rank, hout.data() + (size_t)(j * cwx));
+		if (ok && h->mode == GF2BV_MODE_AFFINE_SPACE) R->basis = h->basis;
 		gf2bv_stats &st = R->stats;
 		st = h->fst;
 		st.rank = R->rank; st.dimension = R->dim; st.status = R->status;
@@ -2523,18 +2503,13 @@ int gf2bv_solve_device(void *d_aug, int64_t rows, int64_t cols, int64_t stride_w
                        int device, void *stream, int time_kernels, gf2bv_result **out)
 {
 	return guarded([&]() -> int {
-	if (!out || !d_aug) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
 	*out = nullptr;
-	int rc = check_shape(rows, cols, mode);
+	MatrixInput in; in.d_words = (const u64 *)d_aug; in.stride = stride_words;
+	int rc = check_matrix_input(in, rows, cols, mode);
+	if (!rc) rc = check_device(device);
 	if (rc) return rc;
-	if (stride_words % 2 != 0 || stride_words < (cols + 1 + 63) / 64 || ((uintptr_t)d_aug & 15))
-		return fail(GF2BV_ERR_ARG, "device matrix needs 16-byte alignment and an even stride_words covering cols+1 bits");
-	rc = check_device(device);
-	if (rc) return rc;
-	if (small_eligible(rows, cols) && !time_kernels) {
-		SmallInput in; in.d_words = (const u64 *)d_aug; in.d_stride = stride_words;
-		return small_solve(in, rows, cols, mode, device, (hipStream_t)stream, out);
-	}
+	if (small_eligible(rows, cols) && !time_kernels) return small_solve(in, rows, cols, mode, device, (hipStream_t)stream, out);
 	Solver S;
 	S.t_begin = std::chrono::steady_clock::now();
 	S.device = device;
@@ -2646,18 +2621,14 @@ int gf2bv_solve_words(const uint64_t *aug, int64_t rows, int64_t cols, int64_t s
                       int device, gf2bv_result **out)
 {
 	return guarded([&]() -> int {
-	if (!out || (!aug && rows > 0)) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
 	*out = nullptr;
-	int rc = check_shape(rows, cols, mode);
+	MatrixInput in; in.h_words = reinterpret_cast<const u64 *>(aug); in.stride = stride_words;
+	int rc = check_matrix_input(in, rows, cols, mode);
+	if (!rc) rc = check_device(device);
 	if (rc) return rc;
+	if (small_eligible(rows, cols)) return small_solve(in, rows, cols, mode, device, nullptr, out);
 	const i64 wt = (cols + 1 + 63) / 64;
-	if (stride_words < wt) return fail(GF2BV_ERR_ARG, "stride_words does not cover cols+1 bits");
-	rc = check_device(device);
-	if (rc) return rc;
-	if (small_eligible(rows, cols)) {
-		SmallInput in; in.h_words = reinterpret_cast<const u64 *>(aug); in.h_stride = stride_words;
-		return small_solve(in, rows, cols, mode, device, nullptr, out);
-	}
 	Solver S;
 	S.t_begin = std::chrono::steady_clock::now();
 	S.device = device;
@@ -2854,50 +2825,28 @@ int gf2bv_solve_digits(const uint32_t *digits, const int64_t *digit_off, int bit
                        int64_t cols, int mode, int device, gf2bv_result **out)
 {
 	return guarded([&]() -> int {
-	if (!out || !digit_off) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
 	*out = nullptr;
-	int rc = check_shape(rows, cols, mode);
+	MatrixInput in; in.h_digits = digits; in.h_off = reinterpret_cast<const i64 *>(digit_off); in.bpd = bits_per_digit;
+	int rc = check_matrix_input(in, rows, cols, mode);
+	if (!rc) rc = check_device(device);
 	if (rc) return rc;
-	if (bits_per_digit < 1 || bits_per_digit > 32) return fail(GF2BV_ERR_ARG, "bits_per_digit must be 1..32");
-	rc = check_device(device);
-	if (rc) return rc;
-	if (digit_off[0] != 0) return fail(GF2BV_ERR_ARG, "digit offsets must start at 0");
-	for (i64 r = 0; r < rows; r++)
-		if (digit_off[r + 1] < digit_off[r]) return fail(GF2BV_ERR_ARG, "digit offsets must not decrease");
-	if (small_eligible(rows, cols)) {
-		SmallInput in; in.h_digits = digits; in.h_off = reinterpret_cast<const i64 *>(digit_off); in.bpd = bits_per_digit;
-		return small_solve(in, rows, cols, mode, device, nullptr, out);
-	}
+	if (small_eligible(rows, cols)) return small_solve(in, rows, cols, mode, device, nullptr, out);
 	Solver S;
 	S.t_begin = std::chrono::steady_clock::now();
 	S.device = device;
 	HIPCHK(pool().stream(&S.sA, device, false));
 	S.own_sA = true;
 	S.rows = rows; S.cols = cols; S.mode = mode;
-	const i64 wt = (cols + 1 + 63) / 64;
-	const i64 ntiles = tiles_for(wt);
+	const i64 ntiles = tiles_for((cols + 1 + 63) / 64), srows = slab_rows(rows);
 	S.stride = ntiles * TW;
-	HIPCHK(pool().alloc((void **)&S.M, sizeof(u64) * ntiles * TW * slab_rows(rows) + kOuterSlackBytes, device));     // packed straight into tiles
-	const i64 ndig = digit_off[rows];
+	HIPCHK(pool().alloc((void **)&S.M, sizeof(u64) * ntiles * TW * srows + kOuterSlackBytes, device));     // packed straight into tiles
 	Scratch scratch;                  // digits, offsets and the pack events go back to the pool on every path
 	scratch.sync_first = S.sA;
-	uint32_t *d_dig = nullptr;
-	i64 *d_off = nullptr;
-	HIPCHK(scratch.alloc((void **)&d_dig, sizeof(uint32_t) * std::max<i64>(1, ndig), device));
-	HIPCHK(scratch.alloc((void **)&d_off, sizeof(i64) * (rows + 1), device));
 	hipEvent_t p0, p1;
 	HIPCHK(scratch.event(&p0)); HIPCHK(scratch.event(&p1));
 	HIPCHK(hipEventRecord(p0, S.sA));
-	if (ndig) HIPCHK(hipMemcpyAsync(d_dig, digits, sizeof(uint32_t) * ndig, hipMemcpyHostToDevice, S.sA));
-	HIPCHK(hipMemcpyAsync(d_off, digit_off, sizeof(i64) * (rows + 1), hipMemcpyHostToDevice, S.sA));
-	{
-		i64 total = rows * ntiles * TW;
-		if (total > 0)
-			k_pack_digits<<<dim3((unsigned)((ntiles * TW + 255) / 256), (unsigned)std::min<i64>(rows, 65535)), dim3(256), 0, S.sA>>>(d_dig, d_off, bits_per_digit, (i64)rows,
-			                                                                            (i64)cols, ntiles * TW, slab_rows(rows), S.M,
-			                                                                            SysStride{0, 0}, (i64)0);
-	}
-	HIPCHK(hipGetLastError());
+	if ((rc = pack_coefficients(in, rows, cols, ntiles, srows, S, scratch))) return rc;
 	HIPCHK(hipEventRecord(p1, S.sA));
 	rc = solver_enqueue(S);
 	if (rc == GF2BV_OK) {
@@ -2914,20 +2863,14 @@ int gf2bv_solve_rhs_digits(const uint32_t *digits, const int64_t *digit_off, int
                            const uint64_t *rhs, int64_t nrhs, int64_t rhs_words, int mode, int device, gf2bv_result **out)
 {
 	return guarded([&]() -> int {
-	int rc = check_rhs_args(rows, cols, mode, rhs, nrhs, rhs_words, out);
+	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
+	for (i64 j = 0; j < nrhs; j++) out[j] = nullptr;
+	MatrixInput in; in.h_digits = digits; in.h_off = reinterpret_cast<const i64 *>(digit_off); in.bpd = bits_per_digit;
+	int rc = check_matrix_input(in, rows, cols, mode);
+	if (!rc) rc = check_rhs_args(rows, cols, rhs, false, nrhs, rhs_words);
+	if (!rc) rc = check_device(device);
 	if (rc) return rc;
-	if (!digit_off) return fail(GF2BV_ERR_ARG, "null pointer");
-	if (bits_per_digit < 1 || bits_per_digit > 32) return fail(GF2BV_ERR_ARG, "bits_per_digit must be 1..32");
-	if (digit_off[0] != 0) return fail(GF2BV_ERR_ARG, "digit offsets must start at 0");
-	for (i64 r = 0; r < rows; r++)
-		if (digit_off[r + 1] < digit_off[r]) return fail(GF2BV_ERR_ARG, "digit offsets must not decrease");
-	if (!digits && digit_off[rows] > 0) return fail(GF2BV_ERR_ARG, "null pointer");
-	rc = check_device(device);
-	if (rc) return rc;
-	RhsInput in;
-	in.h_digits = digits; in.h_off = reinterpret_cast<const i64 *>(digit_off); in.bpd = bits_per_digit;
-	in.rhs = reinterpret_cast<const u64 *>(rhs); in.nrhs = nrhs; in.rhs_words = rhs_words;
-	return solve_rhs(in, rows, cols, mode, device, nullptr, false, out);
+	return solve_rhs(in, reinterpret_cast<const u64 *>(rhs), false, nrhs, rhs_words, rows, cols, mode, device, nullptr, false, out);
 	});
 }
 
@@ -2935,16 +2878,14 @@ int gf2bv_solve_rhs_words(const uint64_t *aug, int64_t rows, int64_t cols, int64
                           const uint64_t *rhs, int64_t nrhs, int64_t rhs_words, int mode, int device, gf2bv_result **out)
 {
 	return guarded([&]() -> int {
-	int rc = check_rhs_args(rows, cols, mode, rhs, nrhs, rhs_words, out);
+	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
+	for (i64 j = 0; j < nrhs; j++) out[j] = nullptr;
+	MatrixInput in; in.h_words = reinterpret_cast<const u64 *>(aug); in.stride = stride_words;
+	int rc = check_matrix_input(in, rows, cols, mode);
+	if (!rc) rc = check_rhs_args(rows, cols, rhs, false, nrhs, rhs_words);
+	if (!rc) rc = check_device(device);
 	if (rc) return rc;
-	if (!aug) return fail(GF2BV_ERR_ARG, "null pointer");
-	if (stride_words < (cols + 1 + 63) / 64) return fail(GF2BV_ERR_ARG, "stride_words does not cover cols+1 bits");
-	rc = check_device(device);
-	if (rc) return rc;
-	RhsInput in;
-	in.h_words = reinterpret_cast<const u64 *>(aug); in.stride = stride_words;
-	in.rhs = reinterpret_cast<const u64 *>(rhs); in.nrhs = nrhs; in.rhs_words = rhs_words;
-	return solve_rhs(in, rows, cols, mode, device, nullptr, false, out);
+	return solve_rhs(in, reinterpret_cast<const u64 *>(rhs), false, nrhs, rhs_words, rows, cols, mode, device, nullptr, false, out);
 	});
 }
 
@@ -2952,17 +2893,14 @@ int gf2bv_solve_rhs_device(void *d_aug, int64_t rows, int64_t cols, int64_t stri
                            int64_t rhs_words, int mode, int device, void *stream, int time_kernels, gf2bv_result **out)
 {
 	return guarded([&]() -> int {
-	int rc = check_rhs_args(rows, cols, mode, d_rhs, nrhs, rhs_words, out);
+	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
+	for (i64 j = 0; j < nrhs; j++) out[j] = nullptr;
+	MatrixInput in; in.d_words = (const u64 *)d_aug; in.stride = stride_words;
+	int rc = check_matrix_input(in, rows, cols, mode);
+	if (!rc) rc = check_rhs_args(rows, cols, d_rhs, true, nrhs, rhs_words);
+	if (!rc) rc = check_device(device);
 	if (rc) return rc;
-	if (!d_aug) return fail(GF2BV_ERR_ARG, "null pointer");
-	if (stride_words % 2 != 0 || stride_words < (cols + 1 + 63) / 64 || ((uintptr_t)d_aug & 15) || ((uintptr_t)d_rhs & 7))
-		return fail(GF2BV_ERR_ARG, "device matrix needs 16-byte alignment and an even stride_words covering cols+1 bits, the right-hand sides 8-byte alignment");
-	rc = check_device(device);
-	if (rc) return rc;
-	RhsInput in;
-	in.d_words = (const u64 *)d_aug; in.stride = stride_words;
-	in.rhs = (const u64 *)d_rhs; in.rhs_on_device = true; in.nrhs = nrhs; in.rhs_words = rhs_words;
-	return solve_rhs(in, rows, cols, mode, device, (hipStream_t)stream, time_kernels != 0, out);
+	return solve_rhs(in, (const u64 *)d_rhs, true, nrhs, rhs_words, rows, cols, mode, device, (hipStream_t)stream, time_kernels != 0, out);
 	});
 }
 
@@ -2973,18 +2911,10 @@ int gf2bv_factor_digits(const uint32_t *digits, const int64_t *digit_off, int bi
 	return guarded([&]() -> int {
 	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
 	*out = nullptr;
-	int rc = check_shape(rows, cols, mode);
+	MatrixInput in; in.h_digits = digits; in.h_off = reinterpret_cast<const i64 *>(digit_off); in.bpd = bits_per_digit;
+	int rc = check_matrix_input(in, rows, cols, mode);
+	if (!rc) rc = check_device(device);
 	if (rc) return rc;
-	if (!digit_off) return fail(GF2BV_ERR_ARG, "null pointer");
-	if (bits_per_digit < 1 || bits_per_digit > 32) return fail(GF2BV_ERR_ARG, "bits_per_digit must be 1..32");
-	if (digit_off[0] != 0) return fail(GF2BV_ERR_ARG, "digit offsets must start at 0");
-	for (i64 r = 0; r < rows; r++)
-		if (digit_off[r + 1] < digit_off[r]) return fail(GF2BV_ERR_ARG, "digit offsets must not decrease");
-	if (!digits && digit_off[rows] > 0) return fail(GF2BV_ERR_ARG, "null pointer");
-	rc = check_device(device);
-	if (rc) return rc;
-	RhsInput in;
-	in.h_digits = digits; in.h_off = reinterpret_cast<const i64 *>(digit_off); in.bpd = bits_per_digit;
 	return factor_matrix(in, rows, cols, mode, device, nullptr, out);
 	});
 }
@@ -2994,14 +2924,10 @@ int gf2bv_factor_words(const uint64_t *aug, int64_t rows, int64_t cols, int64_t 
 	return guarded([&]() -> int {
 	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
 	*out = nullptr;
-	int rc = check_shape(rows, cols, mode);
+	MatrixInput in; in.h_words = reinterpret_cast<const u64 *>(aug); in.stride = stride_words;
+	int rc = check_matrix_input(in, rows, cols, mode);
+	if (!rc) rc = check_device(device);
 	if (rc) return rc;
-	if (!aug) return fail(GF2BV_ERR_ARG, "null pointer");
-	if (stride_words < (cols + 1 + 63) / 64) return fail(GF2BV_ERR_ARG, "stride_words does not cover cols+1 bits");
-	rc = check_device(device);
-	if (rc) return rc;
-	RhsInput in;
-	in.h_words = reinterpret_cast<const u64 *>(aug); in.stride = stride_words;
 	return factor_matrix(in, rows, cols, mode, device, nullptr, out);
 	});
 }
@@ -3012,15 +2938,10 @@ int gf2bv_factor_device(void *d_aug, int64_t rows, int64_t cols, int64_t stride_
 	return guarded([&]() -> int {
 	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
 	*out = nullptr;
-	int rc = check_shape(rows, cols, mode);
+	MatrixInput in; in.d_words = (const u64 *)d_aug; in.stride = stride_words;
+	int rc = check_matrix_input(in, rows, cols, mode);
+	if (!rc) rc = check_device(device);
 	if (rc) return rc;
-	if (!d_aug) return fail(GF2BV_ERR_ARG, "null pointer");
-	if (stride_words % 2 != 0 || stride_words < (cols + 1 + 63) / 64 || ((uintptr_t)d_aug & 15))
-		return fail(GF2BV_ERR_ARG, "device matrix needs 16-byte alignment and an even stride_words covering cols+1 bits");
-	rc = check_device(device);
-	if (rc) return rc;
-	RhsInput in;
-	in.d_words = (const u64 *)d_aug; in.stride = stride_words;
 	return factor_matrix(in, rows, cols, mode, device, (hipStream_t)stream, out);
 	});
 }
@@ -3144,10 +3065,10 @@ int gf2bv_slab_open(void *d_aug, int64_t rows, int64_t cols, int64_t stride_word
 	return guarded([&]() -> int {
 	if (!out || !d_aug || !d_work || world < 1 || rank < 0 || rank >= world) return fail(GF2BV_ERR_ARG, "bad slab arguments");
 	*out = nullptr;
-	int rc = check_shape(rows, cols, GF2BV_MODE_SINGLE);
+	MatrixInput in; in.d_words = (const u64 *)d_aug; in.stride = stride_words;
+	int rc = check_matrix_input(in, rows, cols, GF2BV_MODE_SINGLE);
 	if (rc) return rc;
-	if (stride_words % 2 != 0 || stride_words < (cols + 1 + 63) / 64 || ((uintptr_t)d_aug & 15) || ((uintptr_t)d_work & 15))
-		return fail(GF2BV_ERR_ARG, "device matrix needs 16-byte alignment and an even stride_words covering cols+1 bits");
+	if ((uintptr_t)d_work & 15) return fail(GF2BV_ERR_ARG, "the working matrix needs 16-byte alignment");
 	if (work_words < gf2bv_slab_work_words(rows, cols)) return fail(GF2BV_ERR_ARG, "working matrix too small (gf2bv_slab_work_words)");
 	rc = check_device(device);
 	if (rc) return rc;
@@ -3318,7 +3239,7 @@ int gf2bv_slab_solve(gf2bv_slab *h, gf2bv_result **out)
 	Solver &S = h->S;
 	HIPCHK(hipSetDevice(S.device));
 	int rc = enqueue_check_rhs(S);
-	if (rc == GF2BV_OK) rc = enqueue_backward_single(S);
+	if (rc == GF2BV_OK) rc = enqueue_backward_parity(S, { (int)S.cols });
 	if (rc) return rc;
 	rc = solver_finish(S, out);
 	// (the elimination state of a slab handle cannot be replayed from here: an expired gate is an error, not a retry)

@@ -52,6 +52,64 @@ def test_argument_validation_precedes_device_use():
     assert L.gf2bv_version() >= 100
 
 
+def test_single_entries_check_arguments_before_device_use():
+    """gf2bv_solve_{words,digits,device} refuse the bad arguments their rhs and factor siblings refuse: GF2BV_ERR_ARG (1) with the
+    same message, on a machine without a GPU too (GF2BV_ERR_NODEVICE would be 2).  So does the matrix check of gf2bv_slab_open."""
+    L = hip.lib()
+    rows, cols = 130, 100
+    aug = np.zeros((rows + 1, 2), dtype=np.uint64)
+    off = np.zeros(rows + 1, dtype=np.int64)
+    dig = np.zeros(4, dtype=np.uint32)
+    A, O, D = aug.ctypes.data, off.ctypes.data, dig.ctypes.data
+    h = ctypes.c_void_p(0)
+    H = ctypes.byref(h)
+
+    def err(rc, what):
+        assert rc == 1, (rc, L.gf2bv_last_error())
+        assert what.encode() in L.gf2bv_last_error(), L.gf2bv_last_error()
+
+    err(L.gf2bv_solve_words(A, rows, cols, 2, 0, 0, None), "null")
+    err(L.gf2bv_solve_words(None, rows, cols, 2, 0, 0, H), "null")
+    err(L.gf2bv_solve_words(A, rows, cols, 1, 0, 0, H), "stride")
+    err(L.gf2bv_solve_words(A, 99, cols, 2, 0, 0, H), "greater than or equal")
+    err(L.gf2bv_solve_words(A, rows, cols, 2, 3, 0, H), "Invalid mode")
+    err(L.gf2bv_solve_words(A, rows, 0, 2, 0, 0, H), "columns must be positive")
+    err(L.gf2bv_solve_digits(D, None, 30, rows, cols, 0, 0, H), "null")
+    err(L.gf2bv_solve_digits(D, O, 0, rows, cols, 0, 0, H), "bits_per_digit")
+    err(L.gf2bv_solve_digits(D, O, 33, rows, cols, 0, 0, H), "bits_per_digit")
+    err(L.gf2bv_solve_digits(D, O, 30, rows, cols, 0, 0, None), "null")
+    err(L.gf2bv_solve_digits(D, O, 30, 99, cols, 0, 0, H), "greater than or equal")
+    err(L.gf2bv_solve_digits(D, O, 30, rows, cols, 3, 0, H), "Invalid mode")
+    err(L.gf2bv_solve_digits(D, O, 30, rows, 0, 0, 0, H), "columns must be positive")
+    bad_off = off.copy()
+    bad_off[0] = 1
+    err(L.gf2bv_solve_digits(D, bad_off.ctypes.data, 30, rows, cols, 0, 0, H), "start at 0")
+    bad_off = off.copy()
+    bad_off[5:] = 3
+    bad_off[9] = 2
+    err(L.gf2bv_solve_digits(D, bad_off.ctypes.data, 30, rows, cols, 0, 0, H), "must not decrease")
+    some_off = np.arange(rows + 1, dtype=np.int64)
+    err(L.gf2bv_solve_digits(None, some_off.ctypes.data, 30, rows, cols, 0, 0, H), "null")
+    err(L.gf2bv_solve_device(None, rows, cols, 2, 0, 0, None, 0, H), "null")
+    err(L.gf2bv_solve_device(A, rows, cols, 2, 0, 0, None, 0, None), "null")
+    err(L.gf2bv_solve_device(A, rows, cols, 3, 0, 0, None, 0, H), "stride")
+    err(L.gf2bv_solve_device(A, rows, cols, 1, 0, 0, None, 0, H), "stride")
+    err(L.gf2bv_solve_device(A + 8, rows, cols, 2, 0, 0, None, 0, H), "16-byte alignment")
+    err(L.gf2bv_solve_device(A, 99, cols, 2, 0, 0, None, 0, H), "greater than or equal")
+    err(L.gf2bv_solve_device(A, rows, cols, 2, 3, 0, None, 0, H), "Invalid mode")
+    err(L.gf2bv_solve_device(A, rows, 0, 2, 0, 0, None, 0, H), "columns must be positive")
+    assert not h.value                                          # nothing was made
+    work = np.zeros(L.gf2bv_slab_work_words(rows, cols) + 2, dtype=np.uint64)
+    W, WW = work.ctypes.data, L.gf2bv_slab_work_words(rows, cols)
+    W = W + (-W % 16)                                          # (a 16-byte aligned working matrix)
+    err(L.gf2bv_slab_open(A, rows, cols, 3, W, WW, 1, 0, 0, H), "stride")
+    err(L.gf2bv_slab_open(A + 8, rows, cols, 2, W, WW, 1, 0, 0, H), "16-byte alignment")
+    err(L.gf2bv_slab_open(A, rows, cols, 2, W + 8, WW, 1, 0, 0, H), "16-byte alignment")
+    err(L.gf2bv_slab_open(A, 99, cols, 2, W, WW, 1, 0, 0, H), "greater than or equal")
+    err(L.gf2bv_slab_open(A, rows, cols, 2, W, WW - 1, 1, 0, 0, H), "too small")
+    assert not h.value
+
+
 def test_no_cpu_fallback():
     if hip.device_count() > 0:
         pytest.skip("a GPU is present")

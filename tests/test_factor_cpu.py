@@ -63,6 +63,16 @@ def test_abi_checks_arguments_before_device_use():
     err(L.gf2bv_factor_device(A, rows, cols, 3, 0, 0, None, H), "stride")
     err(L.gf2bv_factor_device(A, rows, cols, 2, 0, 0, None, None), "null")
     err(L.gf2bv_factor_device(A, rows, 0, 2, 0, 0, None, H), "columns must be positive")
+    err(L.gf2bv_factor_device(A + 8, rows, cols, 2, 0, 0, None, H), "16-byte alignment")
+    err(L.gf2bv_factor_device(A, rows, cols, 2, 3, 0, None, H), "Invalid mode")
+    err(L.gf2bv_factor_digits(D, O, 30, rows, cols, 3, 0, H), "Invalid mode")
+    err(L.gf2bv_factor_digits(D, O, 30, rows, 0, 0, 0, H), "columns must be positive")
+    bad_off[5:] = 3
+    bad_off[0] = 0
+    bad_off[9] = 2
+    err(L.gf2bv_factor_digits(D, bad_off.ctypes.data, 30, rows, cols, 0, 0, H), "must not decrease")
+    some_off = np.arange(rows + 1, dtype=np.int64)
+    err(L.gf2bv_factor_digits(None, some_off.ctypes.data, 30, rows, cols, 0, 0, H), "null")
     assert not h.value                                          # nothing was made
     err(L.gf2bv_factor_solve(None, R, 4, 3, hs), "null")
     err(L.gf2bv_factor_solve_device(None, R, 4, 3, None, 0, hs), "null")

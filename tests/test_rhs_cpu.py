@@ -119,3 +119,18 @@ def test_abi_checks_arguments_before_device_use():
     err(L.gf2bv_solve_rhs_device(None, rows, cols, 2, R, 4, 3, 0, 0, None, 0, hs), "null")
     err(L.gf2bv_solve_rhs_device(A, rows, cols, 3, R, 4, 3, 0, 0, None, 0, hs), "stride")
     err(L.gf2bv_solve_rhs_device(A, rows, 0, 2, R, 4, 3, 0, 0, None, 0, hs), "columns must be positive")
+    err(L.gf2bv_solve_rhs_device(A, rows, cols, 2, R, 4, 3, 0, 0, None, 0, None), "null")
+    err(L.gf2bv_solve_rhs_device(A + 8, rows, cols, 2, R, 4, 3, 0, 0, None, 0, hs), "16-byte alignment")
+    err(L.gf2bv_solve_rhs_device(A, rows, cols, 2, R + 4, 4, 3, 0, 0, None, 0, hs), "8-byte alignment")
+    err(L.gf2bv_solve_rhs_digits(D, O, 33, rows, cols, R, 4, 3, 0, 0, hs), "bits_per_digit")
+    err(L.gf2bv_solve_rhs_digits(D, O, 30, rows, cols, R, 4, 3, 0, 0, None), "null")
+    err(L.gf2bv_solve_rhs_digits(D, O, 30, 99, cols, R, 4, 3, 0, 0, hs), "greater than or equal")
+    bad_off = off.copy()
+    bad_off[0] = 1
+    err(L.gf2bv_solve_rhs_digits(D, bad_off.ctypes.data, 30, rows, cols, R, 4, 3, 0, 0, hs), "start at 0")
+    bad_off = off.copy()
+    bad_off[5:] = 3
+    bad_off[9] = 2
+    err(L.gf2bv_solve_rhs_digits(D, bad_off.ctypes.data, 30, rows, cols, R, 4, 3, 0, 0, hs), "must not decrease")
+    some_off = np.arange(rows + 1, dtype=np.int64)
+    err(L.gf2bv_solve_rhs_digits(None, some_off.ctypes.data, 30, rows, cols, R, 4, 3, 0, 0, hs), "null")
