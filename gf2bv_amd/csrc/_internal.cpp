@@ -721,6 +721,72 @@ PyObject *factor_solve(FactorObject *self, PyObject *rhs)
 	return results_to_list(res, self->mode, self->device);
 }
 
+// append(equations): equations added below the factored ones -- a list of equation ints (bit 0 ignored) or a C-contiguous 2-D
+// uint64 array of n x words words in the same bit order (m4ri_solve_packed's layout); the handle then stands for the stacked matrix
+PyObject *factor_append(FactorObject *self, PyObject *eqs)
+{
+	if (!factor_open(self)) return nullptr;
+	int rc;
+	int64_t n = 0;
+	gf2bv_factor *h = self->h;
+	if (PyList_Check(eqs)) {
+		n = PyList_GET_SIZE(eqs);
+		if (n == 0) Py_RETURN_NONE;
+		DigitGather dg;
+		if (!dg.gather_list(eqs, self->cols)) return nullptr;
+		Py_BEGIN_ALLOW_THREADS
+		rc = gf2bv_factor_append_digits(h, dg.digits, dg.off.data(), PyLong_SHIFT, n);
+		Py_END_ALLOW_THREADS
+	} else if (PyObject_CheckBuffer(eqs)) {
+		Py_buffer view{};
+		if (PyObject_GetBuffer(eqs, &view, PyBUF_C_CONTIGUOUS | PyBUF_FORMAT) < 0) return nullptr;
+		const char *f = view.format ? view.format : "B";
+		if (*f == '<' || *f == '=' || *f == '@') f++;
+		if (view.ndim != 2 || view.itemsize != 8 || !(strcmp(f, "Q") == 0 || strcmp(f, "L") == 0)) {
+			PyBuffer_Release(&view);
+			PyErr_SetString(PyExc_TypeError, "equations as a buffer: a C-contiguous 2-D uint64 array");
+			return nullptr;
+		}
+		n = view.shape[0];
+		const int64_t words = view.shape[1];
+		if (words * 64 < self->cols + 1) {
+			PyBuffer_Release(&view);
+			PyErr_SetString(PyExc_ValueError, "the equation array needs words covering cols + 1 bits");
+			return nullptr;
+		}
+		if (n == 0) { PyBuffer_Release(&view); Py_RETURN_NONE; }
+		std::vector<int64_t> off;
+		try { off.resize((size_t)n + 1); } catch (const std::bad_alloc &) { PyBuffer_Release(&view); return PyErr_NoMemory(); }
+		for (int64_t r = 0; r <= n; r++) off[(size_t)r] = r * words * 2;
+		Py_BEGIN_ALLOW_THREADS
+		rc = gf2bv_factor_append_digits(h, static_cast<const uint32_t *>(view.buf), off.data(), 32, n);
+		Py_END_ALLOW_THREADS
+		PyBuffer_Release(&view);
+	} else {
+		PyErr_SetString(PyExc_TypeError, "The equations must be a list of integers or a 2-D uint64 array");
+		return nullptr;
+	}
+	if (rc != GF2BV_OK) return raise_rc(rc, "append");
+	self->rows = gf2bv_factor_rows(h);
+	Py_RETURN_NONE;
+}
+
+// copy(): an independent Factorization with the same state (a device-to-device copy)
+PyObject *factor_copy(FactorObject *self, PyObject *)
+{
+	if (!factor_open(self)) return nullptr;
+	gf2bv_factor *h = self->h, *c = nullptr;
+	int rc;
+	Py_BEGIN_ALLOW_THREADS
+	rc = gf2bv_factor_copy(h, &c);
+	Py_END_ALLOW_THREADS
+	if (rc != GF2BV_OK) return raise_rc(rc, "copy");
+	FactorObject *f = PyObject_New(FactorObject, Factorization_Type);
+	if (!f) { gf2bv_factor_free(c); return nullptr; }
+	f->h = c; f->rows = self->rows; f->cols = self->cols; f->mode = self->mode; f->device = self->device;
+	return (PyObject *)f;
+}
+
 PyObject *factor_close(FactorObject *self, PyObject *)
 {
 	if (self->h) {
@@ -745,7 +811,7 @@ PyObject *factor_exit(FactorObject *self, PyObject *const *, Py_ssize_t) { retur
 PyGetSetDef factor_getset[] = {
 	{"rank", (getter)factor_rank, nullptr, "rank of the coefficient matrix", nullptr},
 	{"pivots", (getter)factor_pivots, nullptr, "pivot columns (the column rank profile), a tuple", nullptr},
-	{"rows", (getter)factor_rows, nullptr, "equations", nullptr},
+	{"rows", (getter)factor_rows, nullptr, "equations (the factored ones plus every appended one)", nullptr},
 	{"cols", (getter)factor_cols, nullptr, "unknowns", nullptr},
 	{"mode", (getter)factor_mode, nullptr, "0: solve returns ints, 1: AffineSpace objects", nullptr},
 	{"device", (getter)factor_device, nullptr, "GPU that holds the factorization", nullptr},
@@ -755,6 +821,9 @@ PyGetSetDef factor_getset[] = {
 PyMethodDef factor_methods[] = {
 	{"solve", (PyCFunction)factor_solve, METH_O,
 	 "solve(rhs)\n--\n\nOne m4ri_solve result per right-hand side (a list of ints, bit r = affine term of equation r, or an nrhs x words uint64 array)."},
+	{"append", (PyCFunction)factor_append, METH_O,
+	 "append(equations)\n--\n\nAdd equations (a list of ints, bit 0 ignored, or an n x words uint64 array in the same bit order) below the factored ones; later solves take ceil(rows / 64)-word right-hand sides of the stacked system."},
+	{"copy", (PyCFunction)factor_copy, METH_NOARGS, "copy()\n--\n\nAn independent Factorization with the same state (a device-to-device copy, no factorization)."},
 	{"close", (PyCFunction)factor_close, METH_NOARGS, "close()\n--\n\nRelease the device memory; later use raises ValueError."},
 	{"__enter__", (PyCFunction)factor_enter, METH_NOARGS, nullptr},
 	{"__exit__", (PyCFunction)(void (*)(void))factor_exit, METH_FASTCALL, nullptr},

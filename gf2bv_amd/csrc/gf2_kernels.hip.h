@@ -3487,6 +3487,247 @@ k_put_rhs(const u64 *__restrict__ acc, i64 rows, i64 cols, i64 srows, u64 *__res
 	}
 }
 
+// ---- equations appended to a kept factorization (gf2bv_factor_append_*) ---------------------------------------------------
+// k new rows B go below the rows of the handle (rows r0 .. r0 + k - 1 of the same tile slabs).  Pivot rows of the kept U lead at
+// their column; inside their own word only the bits above the pivot column at non-pivot columns are meaningful (the words left of
+// it, and the other pivot bits of that word, are dead storage: the back-substitution never reads them), and the pivot rows of one
+// word are mutually reduced there.  The append keeps exactly these properties.
+
+// The grown working matrix: tile t, row r of the new layout = the old one where it existed, zero elsewhere (new rows, new T
+// columns, pad rows).  One lane per (row, 16-byte tile).  grid: x = rows of the new slab / 256, y = tiles (strided)
+__global__ void __launch_bounds__(256)
+k_append_retile(const u64 *__restrict__ src, i64 srows_old, i64 rows_old, i64 ntiles_old, u64 *__restrict__ dst, i64 srows_new,
+                i64 ntiles_new)
+{
+	const i64 r = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+	if (r >= srows_new) return;
+	for (i64 t = blockIdx.y; t < ntiles_new; t += gridDim.y) {
+		ulonglong2 v = make_ulonglong2(0ull, 0ull);
+		if (t < ntiles_old && r < rows_old) v = reinterpret_cast<const ulonglong2 *>(src)[t * srows_old + r];
+		reinterpret_cast<ulonglong2 *>(dst)[t * srows_new + r] = v;
+	}
+}
+
+// The words of the new rows right of the coefficients, as k_factor_init writes them for a fresh factorization: slot bits of the
+// first word cleared, zero up to the end of the row, the identity bit of row r at T column r.  grid: x = k / 256, y = word chunks
+__global__ void __launch_bounds__(256)
+k_append_init(i64 r0, i64 k, i64 cols, i64 srows, i64 tw0, i64 wend, u64 *__restrict__ M)
+{
+	const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= k) return;
+	const i64 r = r0 + i;
+	const int s = (int)(cols & 63);
+	const i64 q0 = cols >> 6, mine = tw0 + (r >> 6);
+	for (i64 q = q0 + blockIdx.y; q < wend; q += gridDim.y) {
+		u64 &w = M[tidx(r, q, srows)];
+		if (q == q0) w &= (1ull << s) - 1;
+		else w = q == mine ? 1ull << (r & 63) : 0ull;
+	}
+}
+
+// snap[i] = word w of new row i (what the reduction by word w's pivot rows decides on)
+__global__ void __launch_bounds__(256)
+k_append_snap(const u64 *__restrict__ M, i64 srows, i64 r0, i64 k, i64 w, u64 *__restrict__ snap)
+{
+	const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i < k) snap[i] = M[tidx(r0 + i, w, srows)];
+}
+
+// The new rows reduced by the pivot rows of word w: row i ^= pivot row j for every pivot column of w that row i has set (in
+// snap_cur, its word w before this step -- the pivot rows of w are mutually reduced there, so the multipliers are those bits
+// themselves).  Tiles from w's on; in word w only the meaningful bits of the pivot rows are taken and the pivot bits come out
+// zero.  The lane that ends up holding word wnext (the next word with pivots, -1: none) of its row leaves it in snap_next: no
+// other workgroup writes that word in this launch, and the next launch reads only the snapshot.  A wavefront = 64 new rows of
+// one tile (lanes: rows, one contiguous KiB); the pivot rows' tiles are wavefront-uniform loads.
+// grid: x = tiles from w's on / 4 (a wavefront each), y = new rows / 64
+__global__ void __launch_bounds__(256)
+k_append_reduce(u64 *__restrict__ M, i64 srows, i64 r0, i64 k, i64 w, i64 wnext, i64 ntiles, const PanelRec *__restrict__ panels,
+                const int *__restrict__ urow, const int *__restrict__ pivcol, const u64 *__restrict__ snap_cur,
+                u64 *__restrict__ snap_next)
+{
+	__shared__ int srow[64];
+	__shared__ int sbit[64];
+	const PanelRec rec = panels[w];
+	if (threadIdx.x < rec.p) {
+		srow[threadIdx.x] = urow[rec.start + threadIdx.x];
+		sbit[threadIdx.x] = pivcol[rec.start + threadIdx.x] & 63;
+	}
+	__syncthreads();
+	const int lane = threadIdx.x & 63;
+	const i64 t = (w >> 1) + (i64)blockIdx.x * 4 + (threadIdx.x >> 6);
+	const i64 i = (i64)blockIdx.y * 64 + lane;
+	if (t >= ntiles) return;
+	const bool on = i < k;
+	const u64 y = on ? snap_cur[i] : 0ull;
+	const i64 wt0 = t * 2;                           // words wt0, wt0 + 1 of this tile
+	u64 a0 = 0, a1 = 0;
+	// eight pivot rows per round: their loads are issued together, then applied
+	for (int j0 = 0; j0 < rec.p; j0 += 8) {
+		ulonglong2 v[8];
+#pragma unroll
+		for (int u = 0; u < 8; u++)
+			v[u] = reinterpret_cast<const ulonglong2 *>(M)[t * srows + srow[j0 + u < rec.p ? j0 + u : j0]];
+#pragma unroll
+		for (int u = 0; u < 8; u++) {
+			if (j0 + u >= rec.p) break;
+			const int b = sbit[j0 + u];
+			if (!((y >> b) & 1)) continue;
+			const u64 above = ~rec.mask & (~0ull << b << 1);     // meaningful bits of the pivot row in its own word
+			a0 ^= wt0 < w ? 0ull : (wt0 == w ? v[u].x & above : v[u].x);
+			a1 ^= wt0 + 1 == w ? v[u].y & above : v[u].y;
+		}
+	}
+	if (!on) return;
+	ulonglong2 &d = reinterpret_cast<ulonglong2 *>(M)[t * srows + r0 + i];
+	ulonglong2 o = d;
+	o.x ^= a0; o.y ^= a1;
+	if (wt0 == w) o.x &= ~rec.mask;
+	if (wt0 + 1 == w) o.y &= ~rec.mask;
+	d = o;
+	if (wnext == wt0) snap_next[i] = o.x;
+	if (wnext == wt0 + 1) snap_next[i] = o.y;
+}
+
+// The reduced new rows' bits at the free columns fc[0 .. nf) (ascending), packed: W[i][q] bit b = column fc[64 q + b] of new row i,
+// followed by the identity of the k rows (words nfw .. nfw + kw): the row operations of k_append_eliminate land there.
+// grid: x = (k x ldw) / 256
+__global__ void __launch_bounds__(256)
+k_append_gather(const u64 *__restrict__ M, i64 srows, i64 r0, i64 k, const int *__restrict__ fc, i64 nf, i64 nfw, i64 ldw,
+                u64 *__restrict__ W)
+{
+	const i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+	if (e >= k * ldw) return;
+	const i64 i = e / ldw, q = e % ldw;
+	u64 v = 0;
+	if (q < nfw) {
+		const i64 j0 = q * 64, n = nf - j0 < 64 ? nf - j0 : 64;
+		for (i64 b = 0; b < n; b++) {
+			const int c = fc[j0 + b];
+			v |= ((M[tidx(r0 + i, c >> 6, srows)] >> (c & 63)) & 1) << b;
+		}
+	} else if (q - nfw == (i >> 6)) v = 1ull << (i & 63);
+	W[e] = v;
+}
+
+// Gauss-Jordan elimination of the k gathered rows (k <= 1024: one row per thread, one workgroup) in column rank profile order:
+// each step takes the alive row with the lowest leading column (the lowest row index among equal ones), clears that column in
+// every other row (whole rows of W: the identity part records the row operations) and retires the row.  out_col / out_row:
+// the pivots found (compact column index, row index), in column order; *out_n their count.
+__global__ void __launch_bounds__(1024)
+k_append_eliminate(u64 *__restrict__ W, int k, i64 nfw, i64 ldw, int *__restrict__ out_col, int *__restrict__ out_row,
+                   int *__restrict__ out_n)
+{
+	__shared__ unsigned long long best;
+	__shared__ u64 has[16];
+	const int t = threadIdx.x;
+	bool alive = t < k;
+	i64 lq = 0;                                      // the words of row t before lq are zero (in the free-column part)
+	int n = 0;
+	for (;;) {
+		if (t == 0) best = ~0ull;
+		if (t < 16) has[t] = 0;
+		__syncthreads();
+		if (alive) {
+			const u64 *row = W + (i64)t * ldw;
+			while (lq < nfw && row[lq] == 0) lq++;
+			if (lq < nfw) {
+				const u64 lead = (u64)(lq * 64 + __ffsll((long long)row[lq]) - 1);
+				atomicMin(&best, (lead << 10) | (u64)t);
+			}
+		}
+		__syncthreads();
+		const u64 bk = best;
+		if (bk == ~0ull) break;
+		const int p = (int)(bk & 1023);
+		const i64 c = (i64)(bk >> 10), cq = c >> 6;
+		if (t < k && t != p && ((W[(i64)t * ldw + cq] >> (c & 63)) & 1)) atomicOr(&has[t >> 6], 1ull << (t & 63));
+		if (t == p) alive = false;
+		if (t == 0) { out_col[n] = (int)c; out_row[n] = p; }
+		n++;
+		__syncthreads();
+		const i64 span = ldw - cq;
+		const u64 *prow = W + (i64)p * ldw + cq;
+		for (i64 e = t; e < (i64)k * span; e += blockDim.x) {
+			const i64 i = e / span, q = e % span;
+			if ((has[i >> 6] >> (i & 63)) & 1) W[i * ldw + cq + q] ^= prow[q];
+		}
+		__syncthreads();
+	}
+	if (t == 0) *out_n = n;
+}
+
+// The row operations of k_append_eliminate applied to the whole new rows: row i = XOR of rows j of the reduced B for the bits j
+// of E[i] (W's identity part).  One workgroup per tile: the tile of the k rows in LDS, then written back in place.
+// grid: x = tiles (strided)
+__global__ void __launch_bounds__(256)
+k_append_combine(u64 *__restrict__ M, i64 srows, i64 r0, int k, i64 ntiles, const u64 *__restrict__ W, i64 nfw, i64 ldw)
+{
+	__shared__ ulonglong2 B[1024];
+	for (i64 t = blockIdx.x; t < ntiles; t += gridDim.x) {
+		ulonglong2 *tile = reinterpret_cast<ulonglong2 *>(M) + t * srows + r0;
+		for (int i = threadIdx.x; i < k; i += blockDim.x) B[i] = tile[i];
+		__syncthreads();
+		for (int i = threadIdx.x; i < k; i += blockDim.x) {
+			const u64 *e = W + (i64)i * ldw + nfw;
+			ulonglong2 o = make_ulonglong2(0ull, 0ull);
+			for (int q = 0; q * 64 < k; q++) {
+				u64 m = e[q];
+				while (m) {
+					const int j = q * 64 + __ffsll((long long)m) - 1;
+					m &= m - 1;
+					o.x ^= B[j].x; o.y ^= B[j].y;
+				}
+			}
+			tile[i] = o;
+		}
+		__syncthreads();
+	}
+}
+
+// Old pivot rows of the words that gained pivots, reduced by the new pivot rows of their word (which are zero at every old pivot
+// column and mutually reduced): item = { physical row, word, pivot bit, first new pivot of the word, count } (nw[] / nr[]: the
+// new pivots' column bits and rows).  Only bits above the row's own pivot are meaningful, so only new pivots above it count.
+// One workgroup per item, lanes over the tiles from the word's on.  grid: x = items
+__global__ void __launch_bounds__(256)
+k_append_backreduce(u64 *__restrict__ M, i64 srows, i64 ntiles, const int4 *__restrict__ items, const int *__restrict__ nbit,
+                    const int *__restrict__ nrow)
+{
+	const int4 it = items[blockIdx.x];
+	const int row = it.x, w = it.y, b = it.z >> 8, n = it.z & 255, first = it.w;
+	__shared__ u64 ssel;
+	if (threadIdx.x == 0) {                          // (one read of the row's word, before any workgroup thread stores to it)
+		const u64 own = M[tidx(row, w, srows)];
+		u64 sel = 0;                                 // bit j: new pivot first + j is XORed in
+		for (int j = 0; j < n; j++) {
+			const int nb = nbit[first + j];
+			if (nb > b && ((own >> nb) & 1)) sel |= 1ull << j;
+		}
+		ssel = sel;
+	}
+	__syncthreads();
+	const u64 sel = ssel;
+	if (!sel) return;
+	for (i64 t = (w >> 1) + threadIdx.x; t < ntiles; t += blockDim.x) {
+		ulonglong2 &d = reinterpret_cast<ulonglong2 *>(M)[t * srows + row];
+		ulonglong2 o = d;
+		for (u64 m = sel; m; m &= m - 1) {
+			const int j = __ffsll((long long)m) - 1;
+			const ulonglong2 v = reinterpret_cast<const ulonglong2 *>(M)[t * srows + nrow[first + j]];
+			if (t * 2 >= w) o.x ^= v.x;              // (w odd: the tile's first word is left of the row's own word)
+			o.y ^= v.y;
+		}
+		d = o;
+	}
+}
+
+// The new pivot rows retired: died[row[j]] = val[j] (the word of the row's pivot, not GF2_NEVER).  grid: n / 256
+__global__ void __launch_bounds__(256)
+k_append_died(int *__restrict__ died, const int *__restrict__ row, const int *__restrict__ val, int n)
+{
+	const int j = blockIdx.x * blockDim.x + threadIdx.x;
+	if (j < n) died[row[j]] = val[j];
+}
+
 // ---- single right-hand side (solve_one): blocked parity back-substitution --------------------
 // With every free variable 0, x[c_k] = y_k ^ parity( U[k][words right of k's panel] & X ), and the
 // pivot rows of one panel are mutually reduced, so a panel's 64 unknowns are independent of each

@@ -1959,10 +1959,17 @@ struct MatrixInput {
 
 // The argument checks of a matrix, made before any device is touched: the shape, then those of the form in use (no form
 // pointer set: the caller passed a null matrix)
+int check_matrix_form(const MatrixInput &in, i64 rows, i64 cols);
 int check_matrix_input(const MatrixInput &in, i64 rows, i64 cols, int mode)
 {
 	int rc = check_shape(rows, cols, mode);
 	if (rc) return rc;
+	return check_matrix_form(in, rows, cols);
+}
+
+// The checks of the form in use alone (an append has shape rules of its own: check_append_args)
+int check_matrix_form(const MatrixInput &in, i64 rows, i64 cols)
+{
 	const i64 wt = (cols + 1 + 63) / 64;
 	if (in.h_off) {
 		if (in.bpd < 1 || in.bpd > 32) return fail(GF2BV_ERR_ARG, "bits_per_digit must be 1..32");
@@ -2160,9 +2167,11 @@ int check_rhs_args(i64 rows, i64 cols, const void *rhs, bool on_device, i64 nrhs
 // The coefficients into the tile-major working matrix S.M (ntiles tiles, srows rows per slab) on S.sA: the digits packed straight into
 // tiles (k_pack_digits puts the affine term at column `cols`; the callers overwrite it), or the words that hold coefficients -- and
 // only those -- copied into tiles (the words right of them are zero-filled)
-int pack_coefficients(const MatrixInput &in, i64 rows, i64 cols, i64 ntiles, i64 srows, Solver &S, Scratch &scratch)
+// (M: where row 0 goes, S.M when null -- an append packs its rows below the kept ones by passing S.M + row0 x TW)
+int pack_coefficients(const MatrixInput &in, i64 rows, i64 cols, i64 ntiles, i64 srows, Solver &S, Scratch &scratch, u64 *M = nullptr)
 {
 	const int device = S.device;
+	if (!M) M = S.M;
 	const i64 cw = (cols + 63) / 64, rw = (rows + 63) / 64;
 	if (in.h_off) {
 		const i64 ndig = in.h_off[rows];
@@ -2173,7 +2182,7 @@ int pack_coefficients(const MatrixInput &in, i64 rows, i64 cols, i64 ntiles, i64
 		if (ndig) HIPCHK(hipMemcpyAsync(d_dig, in.h_digits, sizeof(uint32_t) * ndig, hipMemcpyHostToDevice, S.sA));
 		HIPCHK(hipMemcpyAsync(d_off, in.h_off, sizeof(i64) * (rows + 1), hipMemcpyHostToDevice, S.sA));
 		k_pack_digits<<<dim3((unsigned)((ntiles * TW + 255) / 256), (unsigned)std::min<i64>(rows, 65535)), dim3(256), 0, S.sA>>>(
-			d_dig, d_off, in.bpd, rows, cols, ntiles * TW, srows, S.M, SysStride{0, 0}, (i64)0);
+			d_dig, d_off, in.bpd, rows, cols, ntiles * TW, srows, M, SysStride{0, 0}, (i64)0);
 	} else {
 		const u64 *src = in.d_words;
 		i64 sstride = in.stride;
@@ -2184,7 +2193,7 @@ int pack_coefficients(const MatrixInput &in, i64 rows, i64 cols, i64 ntiles, i64
 			HIPCHK(hipMemcpy2DAsync(tmp, sstride * 8, in.h_words, in.stride * 8, cw * 8, rows, hipMemcpyHostToDevice, S.sA));
 			src = tmp;
 		}
-		k_to_tiled<<<dim3((unsigned)rw, (unsigned)((ntiles + 15) / 16)), dim3(256), 0, S.sA>>>(src, sstride, rows, ntiles, cw, srows, S.M,
+		k_to_tiled<<<dim3((unsigned)rw, (unsigned)((ntiles + 15) / 16)), dim3(256), 0, S.sA>>>(src, sstride, rows, ntiles, cw, srows, M,
 		                                                                                      (i64)0, SysStride{0, 0});
 	}
 	HIPCHK(hipGetLastError());
@@ -2294,6 +2303,21 @@ struct gf2bv_factor {
 	std::vector<u64> basis;           // mode 1: dim x max(1, cw) words, M4RI's order (empty in mode 0)
 	gf2bv_stats fst{};                // the factorization's elimination counters (copied into every result)
 	i64 device_bytes = 0;
+	// appends (gf2bv_factor_append_*): M has room for cap_rows rows (slab_rows(cap_rows) per slab, T columns for all of them);
+	// the host copies of the panel records and the pivot rows follow every merge
+	i64 cap_rows = 0;
+	std::vector<PanelRec> hp;
+	std::vector<int32_t> urow;
+	int *died_buf = nullptr;          // per row, once the rows have outgrown the arena's (owned; S.died points here then)
+	bool failed = false;              // an append failed after it had started to change the kept state: every later call refuses
+	~gf2bv_factor()
+	{
+		if (died_buf) {
+			(void)hipSetDevice(device);
+			if (S.sA) (void)hipStreamSynchronize(S.sA);
+			pool().release(died_buf);
+		}
+	}
 };
 
 namespace {
@@ -2357,7 +2381,11 @@ int factor_matrix(const MatrixInput &in, i64 rows, i64 cols, int mode, int devic
 	if ((rc = handover_verdict(S))) return rc;
 	h->rank = S.hst.rank;
 	h->piv.resize((size_t)h->rank);
+	h->urow.resize((size_t)h->rank);
 	if (h->rank) HIPCHK(hipMemcpy(h->piv.data(), S.pivcol, sizeof(int) * h->rank, hipMemcpyDeviceToHost));
+	if (h->rank) HIPCHK(hipMemcpy(h->urow.data(), S.urow, sizeof(int) * h->rank, hipMemcpyDeviceToHost));
+	h->hp.assign(S.hp.begin(), S.hp.begin() + S.npanels);
+	h->cap_rows = rows;
 	if (mode == GF2BV_MODE_AFFINE_SPACE) {
 		if ((rc = load_free_order(S))) return rc;
 		const i64 dim = cols - h->rank;
@@ -2471,7 +2499,347 @@ int check_factor_args(const gf2bv_factor *h, const void *rhs, i64 nrhs, i64 rhs_
 	if (!h || !out || !rhs) return fail(GF2BV_ERR_ARG, "null pointer");
 	if (nrhs < 1) return fail(GF2BV_ERR_ARG, "nrhs must be at least 1");
 	for (i64 j = 0; j < nrhs; j++) out[j] = nullptr;
+	if (h->failed) return fail(GF2BV_ERR_ARG, "the handle is unusable: an append failed after it had started to change it");
 	if (rhs_words < h->rw) return fail(GF2BV_ERR_ARG, "rhs_words does not cover one bit per row");
+	return GF2BV_OK;
+}
+
+// ---- equations appended to a kept factorization (gf2bv_factor_append_*) -----------------------------------------------------
+// Appending k rows B keeps every result equal to a fresh factorization of the stacked matrix: the pivots of [A; B] are the column
+// rank profile, a superset of A's, and with the pivot set fixed the origin and the kernel basis are unique.  So the kept U stays,
+// and the new rows only have to be reduced by it and eliminated among themselves:
+//   grow    M is re-tiled into slabs with room for the new rows and T columns for them (capacity in whole kAppendRound rows, so
+//           that small appends mostly find room), B is packed below the kept rows, each new row gets its identity bit in T;
+//   reduce  word by word (the words with pivots, ascending), B ^= (B's bits at the word's pivot columns) x (those pivot rows),
+//           one launch per word over the tiles from that word on (k_append_reduce): B ends zero at every old pivot column;
+//   new     B's bits at the old free columns gathered (k_append_gather), Gauss-Jordan on those in column order with the row
+//           operations recorded (k_append_eliminate, one workgroup), applied to the whole rows, T included (k_append_combine);
+//   merge   old pivot rows of a word that gained pivots reduced by the new ones (k_append_backreduce: the back-substitution
+//           takes the pivot rows of a word as mutually reduced), the pivot lists and panel records rebuilt on the host and
+//           uploaded, new pivot rows retired in `died` (rows without a pivot stay alive: the consistency check reads them);
+//           mode 1 recomputes the kernel basis with one back-substitution, as factor_matrix does.
+// Rows go through reduce / new / merge in chunks of kAppendChunk (one workgroup eliminates a chunk); a later chunk sees the
+// pivots of the earlier ones, exactly as appending them one after the other would.
+constexpr i64 kAppendChunk = 1024, kAppendRound = 1024;
+
+// Everything an append allocates, taken before the kept state is changed (a refusal there leaves the handle as it was): the
+// reduction's snapshots, the gathered rows, the free columns, the elimination's output, the merge's item and pivot lists.
+struct AppendBufs {
+	u64 *snap = nullptr, *W = nullptr;
+	int *fc = nullptr, *out = nullptr, *nb = nullptr, *nr = nullptr, *drow = nullptr, *dval = nullptr;
+	int4 *items = nullptr;
+	hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
+};
+
+const char *kFailedHandle = "the handle is unusable: an append failed after it had started to change it";
+
+int check_append_args(const gf2bv_factor *h, const MatrixInput &in, i64 k)
+{
+	if (!h) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (h->failed) return fail(GF2BV_ERR_ARG, kFailedHandle);
+	if (k < 1) return fail(GF2BV_ERR_ARG, "rows must be at least 1");
+	if (h->rows + k >= (1ll << 31) - 64) return fail(GF2BV_ERR_ARG, "system too large");
+	return check_matrix_form(in, k, h->cols);
+}
+
+// the merged pivot lists of the handle (old pivots + new ones: column, physical row) -> host copies and device arrays
+int append_merge(gf2bv_factor *h, const std::vector<std::pair<int, int>> &add, const AppendBufs &B)
+{
+	Solver &S = h->S;
+	const int np = S.npanels;
+	std::vector<std::pair<int, int>> all;
+	all.reserve(h->piv.size() + add.size());
+	for (size_t i = 0; i < h->piv.size(); i++) all.emplace_back(h->piv[i], h->urow[i]);
+	all.insert(all.end(), add.begin(), add.end());
+	std::sort(all.begin(), all.end());
+	// old pivot rows of the words that gained pivots: reduced by the new pivot rows of their word
+	std::vector<int> nbit(add.size()), nrow(add.size());
+	std::vector<int4> items;
+	{
+		std::vector<std::pair<int, int>> na(add);
+		std::sort(na.begin(), na.end());
+		for (size_t j = 0; j < na.size(); j++) { nbit[j] = na[j].first & 63; nrow[j] = na[j].second; }
+		for (size_t j0 = 0; j0 < na.size();) {
+			const int w = na[j0].first >> 6;
+			size_t j1 = j0;
+			while (j1 < na.size() && (na[j1].first >> 6) == w) j1++;
+			const PanelRec &rec = h->hp[(size_t)w];
+			for (int r = 0; r < rec.p; r++)
+				items.push_back(make_int4(h->urow[(size_t)(rec.start + r)], w, ((h->piv[(size_t)(rec.start + r)] & 63) << 8) | (int)(j1 - j0), (int)j0));
+			j0 = j1;
+		}
+	}
+	const i64 rank = (i64)all.size();
+	std::vector<PanelRec> hp((size_t)np);
+	for (auto &r : hp) { r.start = 0; r.p = 0; r.mask = 0; }
+	std::vector<int32_t> piv((size_t)rank), urow((size_t)rank);
+	for (i64 i = 0; i < rank; i++) {
+		piv[(size_t)i] = all[(size_t)i].first; urow[(size_t)i] = all[(size_t)i].second;
+		PanelRec &r = hp[(size_t)(all[(size_t)i].first >> 6)];
+		r.p++; r.mask |= 1ull << (all[(size_t)i].first & 63);
+	}
+	for (int w = 0, st = 0; w < np; w++) { hp[(size_t)w].start = st; st += hp[(size_t)w].p; }
+	// (items: old pivot rows, at most cols of them; new pivots: at most kAppendChunk -- the sizes of B's arrays)
+	if (!items.empty()) {
+		HIPCHK(hipMemcpyAsync(B.items, items.data(), sizeof(int4) * items.size(), hipMemcpyHostToDevice, S.sA));
+		HIPCHK(hipMemcpyAsync(B.nb, nbit.data(), sizeof(int) * nbit.size(), hipMemcpyHostToDevice, S.sA));
+		HIPCHK(hipMemcpyAsync(B.nr, nrow.data(), sizeof(int) * nrow.size(), hipMemcpyHostToDevice, S.sA));
+		k_append_backreduce<<<dim3((unsigned)items.size()), dim3(256), 0, S.sA>>>(S.M, S.srows, S.ntiles, B.items, B.nb, B.nr);
+		HIPCHK(hipGetLastError());
+	}
+	std::vector<int> drow(add.size()), dval(add.size());
+	for (size_t j = 0; j < add.size(); j++) { drow[j] = add[j].second; dval[j] = add[j].first >> 6; }    // (not GF2_NEVER: a pivot row)
+	HIPCHK(hipMemcpyAsync(S.panels, hp.data(), sizeof(PanelRec) * np, hipMemcpyHostToDevice, S.sA));
+	if (rank) HIPCHK(hipMemcpyAsync(S.pivcol, piv.data(), sizeof(int) * rank, hipMemcpyHostToDevice, S.sA));
+	if (rank) HIPCHK(hipMemcpyAsync(S.urow, urow.data(), sizeof(int) * rank, hipMemcpyHostToDevice, S.sA));
+	const int rank32 = (int)rank;
+	HIPCHK(hipMemcpyAsync(&S.st->rank, &rank32, sizeof(int), hipMemcpyHostToDevice, S.sA));
+	HIPCHK(hipMemcpyAsync(B.drow, drow.data(), sizeof(int) * drow.size(), hipMemcpyHostToDevice, S.sA));
+	HIPCHK(hipMemcpyAsync(B.dval, dval.data(), sizeof(int) * dval.size(), hipMemcpyHostToDevice, S.sA));
+	k_append_died<<<dim3((unsigned)((add.size() + 255) / 256)), dim3(256), 0, S.sA>>>(S.died, B.drow, B.dval, (int)add.size());
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipStreamSynchronize(S.sA));          // (the host sources above live on this frame)
+	h->hp = std::move(hp); h->piv = std::move(piv); h->urow = std::move(urow); h->rank = rank;
+	return GF2BV_OK;
+}
+
+// rows r0 .. r0 + k of M (packed, identity bits set; k <= kAppendChunk) reduced by the kept pivots, eliminated among themselves
+// and merged in
+int append_chunk(gf2bv_factor *h, i64 r0, i64 k, const AppendBufs &B, double ms[3])
+{
+	Solver &S = h->S;
+	const i64 cols = h->cols, ntiles = S.ntiles, srows = S.srows;
+	const hipEvent_t *ev = B.ev;
+	u64 *snap = B.snap, *W = B.W;
+	int *fc_d = B.fc, *out_d = B.out;
+	HIPCHK(hipEventRecord(ev[0], S.sA));
+	// reduce: the words with pivots in turn
+	std::vector<int> pw;
+	for (int w = 0; w < S.npanels; w++) if (h->hp[(size_t)w].p) pw.push_back(w);
+	const unsigned gk = (unsigned)((k + 255) / 256);
+	if (!pw.empty()) k_append_snap<<<dim3(gk), dim3(256), 0, S.sA>>>(S.M, srows, r0, k, pw[0], snap);
+	for (size_t j = 0; j < pw.size(); j++) {
+		const i64 w = pw[j], wn = j + 1 < pw.size() ? pw[j + 1] : -1;
+		const i64 nt = ntiles - (w >> 1);
+		k_append_reduce<<<dim3((unsigned)((nt + 3) / 4), (unsigned)((k + 63) / 64)), dim3(256), 0, S.sA>>>(
+			S.M, srows, r0, k, w, wn, ntiles, S.panels, S.urow, S.pivcol, snap + (j & 1) * kAppendChunk, snap + ((j + 1) & 1) * kAppendChunk);
+	}
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(ev[1], S.sA));
+	// new pivots among the reduced rows, at the free columns
+	std::vector<int> fc;
+	{
+		std::vector<char> isp((size_t)cols, 0);
+		for (int32_t c : h->piv) isp[(size_t)c] = 1;
+		for (i64 c = 0; c < cols; c++) if (!isp[(size_t)c]) fc.push_back((int)c);
+	}
+	const i64 nf = (i64)fc.size(), nfw = (nf + 63) / 64, kw = (k + 63) / 64, ldw = nfw + kw;
+	std::vector<std::pair<int, int>> add;
+	if (nf) {
+		HIPCHK(hipMemcpyAsync(fc_d, fc.data(), sizeof(int) * nf, hipMemcpyHostToDevice, S.sA));
+		k_append_gather<<<dim3((unsigned)((k * ldw + 255) / 256)), dim3(256), 0, S.sA>>>(S.M, srows, r0, k, fc_d, nf, nfw, ldw, W);
+		k_append_eliminate<<<dim3(1), dim3(1024), 0, S.sA>>>(W, (int)k, nfw, ldw, out_d, out_d + kAppendChunk, out_d + 2 * kAppendChunk);
+		k_append_combine<<<dim3((unsigned)std::min<i64>(ntiles, 2048)), dim3(256), 0, S.sA>>>(S.M, srows, r0, (int)k, ntiles, W, nfw, ldw);
+		HIPCHK(hipGetLastError());
+		std::vector<int> out((size_t)(2 * kAppendChunk + 1));
+		HIPCHK(hipMemcpyAsync(out.data(), out_d, sizeof(int) * out.size(), hipMemcpyDeviceToHost, S.sA));
+		HIPCHK(hipStreamSynchronize(S.sA));      // (fc and out live on this frame)
+		const int n = out[2 * kAppendChunk];
+		for (int j = 0; j < n; j++) add.emplace_back(fc[(size_t)out[(size_t)j]], (int)(r0 + out[(size_t)(kAppendChunk + j)]));
+	}
+	HIPCHK(hipEventRecord(ev[2], S.sA));
+	if (!add.empty()) {
+		int rc = append_merge(h, add, B);
+		if (rc) return rc;
+	}
+	HIPCHK(hipEventRecord(ev[3], S.sA));
+	HIPCHK(hipStreamSynchronize(S.sA));
+	for (int i = 0; i < 3; i++) { float t = 0; (void)hipEventElapsedTime(&t, ev[i], ev[i + 1]); ms[i] += t; }
+	return GF2BV_OK;
+}
+
+// times of the phases of the last append (GF2BV_TRACE prints them): grow, reduce, new pivots, merge, basis
+void append_trace(const double ms[5], i64 k)
+{
+	if (!getenv("GF2BV_TRACE")) return;
+	fprintf(stderr, "[gf2bv trace] append %lld rows: grow %.3f reduce %.3f new %.3f merge %.3f basis %.3f ms\n", (long long)k, ms[0], ms[1],
+	        ms[2], ms[3], ms[4]);
+}
+
+int factor_append(gf2bv_factor *h, const MatrixInput &in, i64 k, hipStream_t stream)
+{
+	std::lock_guard<std::mutex> lk(h->mu);
+	Solver &S = h->S;
+	HIPCHK(hipSetDevice(h->device));
+	const i64 rows = h->rows, cols = h->cols, rows2 = rows + k, rw2 = (rows2 + 63) / 64;
+	const bool grow = rows2 > h->cap_rows;
+	const i64 cap = grow ? round_up(rows2, kAppendRound) : h->cap_rows;
+	const i64 srows2 = grow ? slab_rows(cap) : S.srows, ntiles2 = grow ? tiles_for(h->tw0 + (cap + 63) / 64) : S.ntiles;
+	double ms[5] = {0, 0, 0, 0, 0};
+	// everything the append allocates is taken before the handle is touched: an argument error or a refusal leaves it as it was
+	Scratch scratch;
+	scratch.sync_first = S.sA;
+	u64 *M2 = S.M;
+	int *died2 = S.died;
+	if (grow) {
+		M2 = nullptr; died2 = nullptr;
+		const hipError_t e = pool().alloc((void **)&M2, sizeof(u64) * ntiles2 * TW * srows2 + kOuterSlackBytes, h->device);
+		if (e == hipErrorOutOfMemory) {
+			(void)hipGetLastError();
+			return fail(GF2BV_ERR_NOMEM, "the grown factorization does not fit on the device");
+		}
+		if (e != hipSuccess) return fail(GF2BV_ERR_HIP, "grown working matrix", e);
+		const hipError_t e2 = pool().alloc((void **)&died2, sizeof(int) * cap, h->device);
+		if (e2 != hipSuccess) {
+			pool().release(M2);
+			if (e2 == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(GF2BV_ERR_NOMEM, "the grown factorization does not fit on the device"); }
+			return fail(GF2BV_ERR_HIP, "grown row records", e2);
+		}
+	}
+	// (on an error past this point the grown buffers go back to the pool; the kept state is only replaced at the end)
+	struct Grown {
+		u64 *M; int *died; bool own;
+		~Grown() { if (own) { pool().release(M); pool().release(died); } }
+	} grown{ M2, died2, grow };
+	const i64 kc = std::min(k, kAppendChunk);
+	const i64 nfw = (cols + 63) / 64, ldw = nfw + (kc + 63) / 64;
+	AppendBufs B;
+	HIPCHK(scratch.alloc((void **)&B.snap, sizeof(u64) * 2 * kAppendChunk, h->device));
+	HIPCHK(scratch.alloc((void **)&B.W, sizeof(u64) * kc * ldw, h->device));
+	HIPCHK(scratch.alloc((void **)&B.fc, sizeof(int) * cols, h->device));
+	HIPCHK(scratch.alloc((void **)&B.out, sizeof(int) * (2 * kAppendChunk + 1), h->device));
+	HIPCHK(scratch.alloc((void **)&B.items, sizeof(int4) * cols, h->device));
+	for (int **p : { &B.nb, &B.nr, &B.drow, &B.dval }) HIPCHK(scratch.alloc((void **)p, sizeof(int) * kAppendChunk, h->device));
+	for (hipEvent_t &e : B.ev) HIPCHK(scratch.event(&e));
+	hipEvent_t g0, g1;
+	HIPCHK(scratch.event(&g0)); HIPCHK(scratch.event(&g1));
+	if (in.d_words && stream) {       // the caller's matrix is read after what its stream has queued
+		HIPCHK(hipEventRecord(g0, stream));
+		HIPCHK(hipStreamWaitEvent(S.sA, g0, 0));
+	}
+	HIPCHK(hipEventRecord(g0, S.sA));
+	if (grow) {
+		k_append_retile<<<dim3((unsigned)((srows2 + 255) / 256), (unsigned)std::min<i64>(ntiles2, 64)), dim3(256), 0, S.sA>>>(
+			S.M, S.srows, rows, S.ntiles, M2, srows2, ntiles2);
+		HIPCHK(hipMemcpyAsync(died2, S.died, sizeof(int) * rows, hipMemcpyDeviceToDevice, S.sA));
+		HIPCHK(hipGetLastError());
+	}
+	HIPCHK(hipMemsetAsync(died2 + rows, GF2_NEVER & 0xff, sizeof(int) * k, S.sA));
+	{
+		Solver P;                         // (pack_coefficients' stream and device)
+		P.device = h->device; P.sA = S.sA;
+		int rc = pack_coefficients(in, k, cols, ntiles2, srows2, P, scratch, M2 + rows * TW);
+		P.sA = nullptr;
+		if (rc) return rc;
+	}
+	k_append_init<<<dim3((unsigned)((k + 255) / 256), (unsigned)std::min<i64>(h->tw0 + rw2 - (cols >> 6), 64)), dim3(256), 0, S.sA>>>(
+		rows, k, cols, srows2, h->tw0, h->tw0 + rw2, M2);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(g1, S.sA));
+	HIPCHK(hipStreamSynchronize(S.sA));
+	{ float t = 0; (void)hipEventElapsedTime(&t, g0, g1); ms[0] = t; }
+	// the kept state changes from here on: a failure past this point leaves the handle marked unusable (h->failed)
+	if (grow) {
+		pool().release(S.M);
+		S.M = M2;
+		if (h->died_buf) pool().release(h->died_buf);
+		h->died_buf = died2;
+		S.died = died2;
+		grown.own = false;
+		h->cap_rows = cap;
+		S.srows = srows2; S.ntiles = ntiles2; S.m_stride = ntiles2 * TW * srows2;
+	}
+	auto rest = [&]() -> int {
+		for (i64 c0 = 0; c0 < k; c0 += kAppendChunk) {
+			int rc = append_chunk(h, rows + c0, std::min(kAppendChunk, k - c0), B, ms + 1);
+			if (rc) return rc;
+		}
+		std::vector<u64> basis;
+		if (h->mode == GF2BV_MODE_AFFINE_SPACE) {
+			const auto tb = std::chrono::steady_clock::now();
+			int rc = load_free_order(S);
+			if (rc) return rc;
+			const i64 dim = cols - h->rank;
+			if (dim) {
+				if ((rc = enqueue_backsub(S, S.free_order))) return rc;
+				std::vector<u64> hout((size_t)(dim * std::max<i64>(1, h->cw)));
+				HIPCHK(hipMemcpyAsync(hout.data(), S.out, sizeof(u64) * hout.size(), hipMemcpyDeviceToHost, S.sA));
+				HIPCHK(hipStreamSynchronize(S.sA));
+				basis = basis_rows(hout.data(), h->cw, S.free_order, dim);
+				release_backsub(S);
+			}
+			ms[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb).count();
+		}
+		h->basis = std::move(basis);
+		h->rows = rows2; h->rw = rw2;
+		S.rows = rows2; S.wt = h->tw0 + rw2; S.nrhs = (int)(S.wt * 64 - cols);
+		h->fst.rows = rows2; h->fst.stride_words = S.wt; h->fst.rank = h->rank; h->fst.dimension = cols - h->rank;
+		h->device_bytes = (i64)(sizeof(u64) * S.ntiles * TW * S.srows + kOuterSlackBytes + S.arena_stride) + (i64)sizeof(int) * h->cap_rows;
+		return GF2BV_OK;
+	};
+	if (int rc = rest()) {
+		release_backsub(S);
+		h->failed = true;
+		const std::string why = g_err;
+		return fail(GF2BV_ERR_HIP, (std::string(kFailedHandle) + ": " + why).c_str());
+	}
+	append_trace(ms, k);
+	return GF2BV_OK;
+}
+
+// An independent handle: the kept state copied device to device, the host fields as they are
+int factor_copy(gf2bv_factor *h, gf2bv_factor **out)
+{
+	std::lock_guard<std::mutex> lk(h->mu);
+	const Solver &S = h->S;
+	HIPCHK(hipSetDevice(h->device));
+	std::unique_ptr<gf2bv_factor> c(new gf2bv_factor());
+	c->rows = h->rows; c->cols = h->cols; c->tw0 = h->tw0; c->rw = h->rw; c->cw = h->cw;
+	c->mode = h->mode; c->device = h->device; c->rank = h->rank;
+	c->piv = h->piv; c->basis = h->basis; c->fst = h->fst; c->device_bytes = h->device_bytes;
+	c->cap_rows = h->cap_rows; c->hp = h->hp; c->urow = h->urow;
+	Solver &D = c->S;
+	D = S;                            // the scalars and host vectors; every resource below is the copy's own
+	D.M = nullptr; D.tmp_src = nullptr; D.Ybuf = nullptr; D.Minv = nullptr; D.arena = nullptr; D.Y = nullptr; D.ycols = nullptr;
+	D.out = nullptr; D.rhs_bad = nullptr; D.src = nullptr;
+	D.sA = D.sB = D.sC = nullptr; D.own_sA = D.own_sB = false;
+	D.ev0 = D.ev1 = D.ev2 = D.ev3 = D.evx = nullptr;
+	D.evOuter = D.evPri = D.evPanelDone = D.evBig = nullptr;
+	D.kev.clear(); D.evA.clear(); D.evPrio.clear(); D.waitPrio.clear();
+	D.st = nullptr; D.sf = nullptr; D.panels = nullptr; D.aux = nullptr; D.fu = nullptr; D.died = nullptr; D.pivcol = nullptr;
+	D.urow = nullptr; D.blk_first = nullptr; D.mult = nullptr; D.Wb = nullptr; D.Uwin = nullptr; D.Pfast = nullptr; D.oprow = nullptr;
+	D.Tm = nullptr; D.Pc = nullptr; D.wmask = nullptr; D.sf = nullptr;
+	HIPCHK(pool().stream(&D.sA, h->device, false));
+	D.own_sA = true;
+	for (hipEvent_t *e : { &D.ev0, &D.ev1, &D.ev2, &D.ev3 }) HIPCHK(pool().event(e, true));
+	const size_t mbytes = sizeof(u64) * S.ntiles * TW * S.srows + kOuterSlackBytes;
+	{
+		const hipError_t e = pool().alloc((void **)&D.M, mbytes, h->device);
+		if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(GF2BV_ERR_NOMEM, "the copy of the factorization does not fit on the device"); }
+		if (e != hipSuccess) return fail(GF2BV_ERR_HIP, "working matrix", e);
+		const hipError_t e2 = pool().alloc(&D.arena, S.arena_stride, h->device);
+		if (e2 == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(GF2BV_ERR_NOMEM, "the copy of the factorization does not fit on the device"); }
+		if (e2 != hipSuccess) return fail(GF2BV_ERR_HIP, "arena", e2);
+		if (h->died_buf) {
+			const hipError_t e3 = pool().alloc((void **)&c->died_buf, sizeof(int) * h->cap_rows, h->device);
+			if (e3 == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(GF2BV_ERR_NOMEM, "the copy of the factorization does not fit on the device"); }
+			if (e3 != hipSuccess) return fail(GF2BV_ERR_HIP, "row records", e3);
+		}
+	}
+	// the copy starts after what the original's stream has queued
+	HIPCHK(hipStreamSynchronize(S.sA));
+	HIPCHK(hipMemcpyAsync(D.M, S.M, sizeof(u64) * S.ntiles * TW * S.srows, hipMemcpyDeviceToDevice, D.sA));
+	HIPCHK(hipMemcpyAsync(D.arena, S.arena, S.arena_stride, hipMemcpyDeviceToDevice, D.sA));
+	if (h->died_buf) HIPCHK(hipMemcpyAsync(c->died_buf, h->died_buf, sizeof(int) * h->cap_rows, hipMemcpyDeviceToDevice, D.sA));
+	char *ob = (char *)S.arena, *nb = (char *)D.arena;
+	auto rebase = [&](auto *p) { return p ? (decltype(p))(nb + ((const char *)p - ob)) : p; };
+	D.st = rebase(S.st); D.sf = rebase(S.sf); D.panels = rebase(S.panels); D.aux = rebase(S.aux); D.fu = rebase(S.fu);
+	D.pivcol = rebase(S.pivcol); D.urow = rebase(S.urow); D.blk_first = rebase(S.blk_first); D.mult = rebase(S.mult);
+	D.Wb = rebase(S.Wb); D.Uwin = rebase(S.Uwin); D.Pfast = rebase(S.Pfast); D.oprow = rebase(S.oprow); D.Tm = rebase(S.Tm);
+	D.Pc = rebase(S.Pc); D.wmask = rebase(S.wmask);
+	D.died = h->died_buf ? c->died_buf : rebase(S.died);
+	HIPCHK(hipStreamSynchronize(D.sA));
+	*out = c.release();
 	return GF2BV_OK;
 }
 
@@ -2969,10 +3337,11 @@ int gf2bv_factor_solve_device(gf2bv_factor *h, const void *d_rhs, int64_t nrhs, 
 	});
 }
 
-int64_t gf2bv_factor_rank(const gf2bv_factor *h) { return h ? h->rank : -1; }
+int64_t gf2bv_factor_rank(const gf2bv_factor *h) { return h && !h->failed ? h->rank : -1; }
 int gf2bv_factor_pivots(const gf2bv_factor *h, int32_t *o)
 {
 	if (!h || (!o && !h->piv.empty())) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (h->failed) return fail(GF2BV_ERR_ARG, kFailedHandle);
 	if (!h->piv.empty()) memcpy(o, h->piv.data(), sizeof(int32_t) * h->piv.size());
 	return GF2BV_OK;
 }
@@ -2982,6 +3351,53 @@ void gf2bv_factor_free(gf2bv_factor *h)
 	if (!h) return;
 	{ std::lock_guard<std::mutex> lk(h->mu); }      // (a call still running on another thread finishes first)
 	delete h;
+}
+
+// Equations appended to a kept factorization: see factor_append
+int gf2bv_factor_append_words(gf2bv_factor *h, const uint64_t *aug, int64_t rows, int64_t stride_words)
+{
+	return guarded([&]() -> int {
+	MatrixInput in; in.h_words = reinterpret_cast<const u64 *>(aug); in.stride = stride_words;
+	int rc = check_append_args(h, in, rows);
+	if (!rc) rc = check_device(h->device);
+	if (rc) return rc;
+	return factor_append(h, in, rows, nullptr);
+	});
+}
+
+int gf2bv_factor_append_digits(gf2bv_factor *h, const uint32_t *digits, const int64_t *digit_off, int bits_per_digit, int64_t rows)
+{
+	return guarded([&]() -> int {
+	if (!digit_off) return fail(GF2BV_ERR_ARG, "null pointer");
+	MatrixInput in; in.h_digits = digits; in.h_off = reinterpret_cast<const i64 *>(digit_off); in.bpd = bits_per_digit;
+	int rc = check_append_args(h, in, rows);
+	if (!rc) rc = check_device(h->device);
+	if (rc) return rc;
+	return factor_append(h, in, rows, nullptr);
+	});
+}
+
+int gf2bv_factor_append_device(gf2bv_factor *h, const void *d_aug, int64_t rows, int64_t stride_words, void *stream)
+{
+	return guarded([&]() -> int {
+	MatrixInput in; in.d_words = (const u64 *)d_aug; in.stride = stride_words;
+	int rc = check_append_args(h, in, rows);
+	if (!rc) rc = check_device(h->device);
+	if (rc) return rc;
+	return factor_append(h, in, rows, (hipStream_t)stream);
+	});
+}
+
+int64_t gf2bv_factor_rows(const gf2bv_factor *h) { return h && !h->failed ? h->rows : -1; }
+
+int gf2bv_factor_copy(gf2bv_factor *h, gf2bv_factor **out)
+{
+	return guarded([&]() -> int {
+	if (!h || !out) return fail(GF2BV_ERR_ARG, "null pointer");
+	*out = nullptr;
+	if (h->failed) return fail(GF2BV_ERR_ARG, kFailedHandle);
+	return factor_copy(h, out);
+	});
 }
 
 // ---- result accessors ----------------------------------------------------------------------------

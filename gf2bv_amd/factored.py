@@ -4,7 +4,8 @@
 matrix on the GPU (``_internal.m4ri_factor`` -> ``gf2bv_factor_digits``).  An instance is a list of observed values, one per
 expression; each method equals the matching ``LinearSystem`` method on ``[e ^ v for e, v in zip(exprs, values)]``.  The
 right-hand-side words of a batch are built with numpy from spans kept as arrays: bit r of instance i = the constant term of
-equation r xor the bit of values[i][k] that equation r of expression k stands for.
+equation r xor the bit of values[i][k] that equation r of expression k stands for.  ``add(exprs)`` appends expressions to the
+factorizations already made; ``copy()`` makes an independent system (a guess tried on the copy leaves the original as it was).
 """
 from __future__ import annotations
 
@@ -22,35 +23,106 @@ class FactoredSystem:
         self._system = system
         self._quadratic = isinstance(system, QuadraticSystem)
         self._device = device
-        eqs: list = []
-        span_at, span_width = [], []                 # per expression: first row, width (0: an equation int, value 0 / 1)
-        for e in exprs:
-            span_at.append(len(eqs))
-            if isinstance(e, BitVec):
-                span_width.append(len(e._bits))
-                eqs.extend(e._bits)
-            else:
-                span_width.append(0)
-                eqs.append(e)
-        self._nspans = len(span_at)
-        if len(eqs) < system._cols:                  # the boundary wants rows >= cols (zero rows, constant 0 in every instance)
-            eqs.extend([0] * (system._cols - len(eqs)))
-        self._eqs = eqs
-        self.rows = len(eqs)
-        self._rw = (self.rows + 63) // 64
-        self._width = np.array(span_width, dtype=np.int64)
-        # every row that belongs to an expression: which 64-bit chunk of which value it reads, and which bit of it
-        row_span = np.repeat(np.arange(self._nspans), np.maximum(self._width, 1))
-        offs = np.arange(len(row_span)) - np.repeat(np.array(span_at, dtype=np.int64), np.maximum(self._width, 1))
-        self._nchunks = np.maximum(1, (self._width + 63) // 64)
-        first_chunk = np.concatenate(([0], np.cumsum(self._nchunks)[:-1])).astype(np.int64)
-        self._row_col = first_chunk[row_span] + offs // 64        # column of the chunk matrix built per call
-        self._row_bit = (offs % 64).astype(np.uint64)
-        self._nexpr_rows = len(row_span)
-        consts = np.zeros(self._rw * 64, dtype=np.uint8)
-        consts[:len(eqs)] = [e & 1 for e in eqs]
-        self._consts = np.packbits(consts, bitorder="little").view(np.uint64)
+        self._eqs: list = []
+        self._nspans = 0
+        self._width = np.zeros(0, dtype=np.int64)        # per expression: width (0: an equation int, value 0 / 1)
+        self._nchunks = np.zeros(0, dtype=np.int64)      # per expression: 64-bit chunks of its value
+        self._expr_rows = np.zeros(0, dtype=np.int64)    # every row that belongs to an expression: its index,
+        self._row_col = np.zeros(0, dtype=np.int64)      # which column of the chunk matrix built per call it reads,
+        self._row_bit = np.zeros(0, dtype=np.uint64)     # and which bit of it
+        self._extend(exprs)
+        if len(self._eqs) < system._cols:            # the boundary wants rows >= cols (zero rows, constant 0 in every instance)
+            self._eqs.extend([0] * (system._cols - len(self._eqs)))
+        self._set_rows()
         self._handles = {}
+
+    def _extend(self, exprs) -> list:
+        """The span bookkeeping of `exprs`, whose rows follow every current row; returns their equations."""
+        base = len(self._eqs)
+        new: list = []
+        at, widths = [], []
+        for e in exprs:
+            at.append(len(new))
+            if isinstance(e, BitVec):
+                widths.append(len(e._bits))
+                new.extend(e._bits)
+            else:
+                widths.append(0)
+                new.append(e)
+        width = np.array(widths, dtype=np.int64)
+        reps = np.maximum(width, 1)
+        nchunks = np.maximum(1, (width + 63) // 64)
+        first_chunk = int(self._nchunks.sum()) + np.concatenate(([0], np.cumsum(nchunks)[:-1])).astype(np.int64)
+        row_span = np.repeat(np.arange(len(widths), dtype=np.int64), reps)
+        offs = np.arange(len(row_span), dtype=np.int64) - np.repeat(np.array(at, dtype=np.int64), reps)
+        self._expr_rows = np.concatenate((self._expr_rows, base + np.arange(len(row_span), dtype=np.int64)))
+        self._row_col = np.concatenate((self._row_col, first_chunk[row_span] + offs // 64))
+        self._row_bit = np.concatenate((self._row_bit, (offs % 64).astype(np.uint64)))
+        self._width = np.concatenate((self._width, width))
+        self._nchunks = np.concatenate((self._nchunks, nchunks))
+        self._nspans += len(widths)
+        self._eqs.extend(new)
+        return new
+
+    def _set_rows(self) -> None:
+        self.rows = len(self._eqs)
+        self._rw = (self.rows + 63) // 64
+        consts = np.zeros(self._rw * 64, dtype=np.uint8)
+        consts[:self.rows] = [e & 1 for e in self._eqs]
+        self._consts = np.packbits(consts, bitorder="little").view(np.uint64)
+
+    def _check_open(self) -> None:
+        if self._handles.get("closed"):
+            raise ValueError("the factored system is closed")
+
+    # -- new equations -----------------------------------------------------------------------------------------------------
+    def add(self, exprs) -> None:
+        """Append expressions (BitVec or equation int) after every current row; later instances take one value per expression,
+        the earlier expressions' first.  Every factorization already made takes the new rows in (gf2bv_factor_append_*: the
+        cost of the new rows, not of a new factorization); one made later factors the whole row list."""
+        self._check_open()
+        saved = dict(self.__dict__)
+        saved["_eqs"] = list(self._eqs)
+        new = self._extend(exprs)
+        self._set_rows()
+        if not new:
+            return
+        done = []
+        try:
+            for mode in (0, 1):
+                h = self._handles.get(mode)
+                if h is not None:
+                    h.append(new)
+                    done.append(mode)
+        except BaseException:
+            handles = self._handles
+            self.__dict__.clear()
+            self.__dict__.update(saved)
+            for mode in (0, 1):
+                h = handles.get(mode)
+                # those that hold the new rows, and one a failed append left unusable (rank -1), are made again from the old
+                # row list on next use
+                if h is not None and (mode in done or h.rank < 0):
+                    handles.pop(mode).close()
+            self._handles = handles
+            raise
+
+    def copy(self) -> "FactoredSystem":
+        """An independent FactoredSystem: the factorizations made so far copied on the device, the bookkeeping on the host."""
+        self._check_open()
+        c = object.__new__(FactoredSystem)
+        c.__dict__.update(self.__dict__)
+        c._eqs = list(self._eqs)
+        c._handles = {}
+        try:
+            for mode in (0, 1):
+                h = self._handles.get(mode)
+                if h is not None:
+                    c._handles[mode] = h.copy()
+        except BaseException:
+            c.close()
+            raise
+        return c
 
     # -- right-hand sides ------------------------------------------------------------------------------------------------
     def _chunks(self, values_list: Sequence[Sequence[int]]) -> np.ndarray:
@@ -97,8 +169,8 @@ class FactoredSystem:
         C = self._chunks(values_list)
         n = C.shape[0]
         bits = np.zeros((n, self._rw * 64), dtype=np.uint8)
-        if self._nexpr_rows:
-            bits[:, :self._nexpr_rows] = ((C[:, self._row_col] >> self._row_bit) & np.uint64(1)).astype(np.uint8)
+        if len(self._expr_rows):
+            bits[:, self._expr_rows] = ((C[:, self._row_col] >> self._row_bit) & np.uint64(1)).astype(np.uint8)
         out = np.packbits(bits, axis=1, bitorder="little").view(np.uint64).reshape(n, self._rw)
         return out ^ self._consts
 
@@ -106,15 +178,13 @@ class FactoredSystem:
     def _handle(self, mode: int):
         h = self._handles.get(mode)
         if h is None:
-            if self._handles.get("closed"):
-                raise ValueError("the factored system is closed")
+            self._check_open()
             args = (self._eqs, self._system._cols, mode) + (() if self._device is None else (self._device,))
             h = self._handles[mode] = m4ri_factor(*args)
         return h
 
     def _solve(self, values_list, mode: int) -> list:
-        if self._handles.get("closed"):
-            raise ValueError("the factored system is closed")
+        self._check_open()
         rhs = self.rhs_words(values_list)
         if rhs.shape[0] == 0:
             return []

@@ -30,6 +30,8 @@ EXPORTS = [
     "gf2bv_solve_rhs_digits", "gf2bv_solve_rhs_words", "gf2bv_solve_rhs_device",
     "gf2bv_factor_digits", "gf2bv_factor_words", "gf2bv_factor_device", "gf2bv_factor_solve", "gf2bv_factor_solve_device",
     "gf2bv_factor_rank", "gf2bv_factor_pivots", "gf2bv_factor_device_bytes", "gf2bv_factor_free",
+    "gf2bv_factor_append_words", "gf2bv_factor_append_digits", "gf2bv_factor_append_device", "gf2bv_factor_rows",
+    "gf2bv_factor_copy",
     "gf2bv_result_status", "gf2bv_result_rank", "gf2bv_result_dimension", "gf2bv_result_words",
     "gf2bv_result_origin", "gf2bv_result_basis", "gf2bv_result_pivots", "gf2bv_result_stats",
     "gf2bv_result_free", "gf2bv_space_combine", "gf2bv_space_open", "gf2bv_space_enumerate", "gf2bv_space_buffer", "gf2bv_space_close",
@@ -101,6 +103,12 @@ def lib():
         L.gf2bv_factor_device_bytes.restype = i64
         L.gf2bv_factor_free.argtypes = [vp]
         L.gf2bv_factor_free.restype = None
+        L.gf2bv_factor_append_words.argtypes = [vp, vp, i64, i64]
+        L.gf2bv_factor_append_digits.argtypes = [vp, vp, vp, i32, i64]
+        L.gf2bv_factor_append_device.argtypes = [vp, vp, i64, i64, vp]
+        L.gf2bv_factor_rows.argtypes = [vp]
+        L.gf2bv_factor_rows.restype = i64
+        L.gf2bv_factor_copy.argtypes = [vp, pp]
         for name, res in (("gf2bv_result_status", i32), ("gf2bv_result_rank", i64),
                           ("gf2bv_result_dimension", i64), ("gf2bv_result_words", i64)):
             getattr(L, name).restype = res
@@ -348,12 +356,45 @@ class Factor:
 
     def __init__(self, handle: ctypes.c_void_p, rows: int, cols: int, mode: int):
         self._h = handle
-        self.rows, self.cols, self.mode = rows, cols, mode
+        self._rows, self.cols, self.mode = rows, cols, mode
 
     def _handle(self):
         if not self._h:
             raise ValueError("the factorization is closed")
         return self._h
+
+    @property
+    def rows(self) -> int:
+        """the stacked row count: the factored rows plus every appended one"""
+        if self._h:
+            self._rows = int(lib().gf2bv_factor_rows(self._h))
+        return self._rows
+
+    def append_words(self, aug: np.ndarray, rows: int | None = None) -> None:
+        """Append equations in factor_words' layout ([rows, >= ceil((cols + 1) / 64)] uint64, column `cols` ignored): the handle
+        then behaves as a factorization of the stacked matrix"""
+        aug = np.ascontiguousarray(aug, dtype=np.uint64)
+        if aug.ndim != 2:
+            raise ValueError("aug must be a [rows, words] array")
+        rows = aug.shape[0] if rows is None else rows
+        _check(lib().gf2bv_factor_append_words(self._handle(), aug.ctypes.data, rows, aug.shape[1]))
+
+    def append_digits(self, digits: np.ndarray, offsets: np.ndarray, bits_per_digit: int, rows: int) -> None:
+        """append_words with the equations given as digit arrays (see factor_digits)"""
+        digits = np.ascontiguousarray(digits, dtype=np.uint32)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        _check(lib().gf2bv_factor_append_digits(self._handle(), digits.ctypes.data, offsets.ctypes.data, bits_per_digit,
+                                                rows))
+
+    def append_device(self, d_ptr: int, rows: int, stride: int, stream: int = 0) -> None:
+        """append_words with the equations resident in device memory (16-byte aligned, even stride; left untouched)"""
+        _check(lib().gf2bv_factor_append_device(self._handle(), d_ptr, rows, stride, stream or None))
+
+    def copy(self) -> "Factor":
+        """An independent handle with the same state (a device-to-device copy, no factorization)"""
+        h = ctypes.c_void_p()
+        _check(lib().gf2bv_factor_copy(self._handle(), ctypes.byref(h)))
+        return Factor(h, self.rows, self.cols, self.mode)
 
     @property
     def rank(self) -> int:

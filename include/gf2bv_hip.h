@@ -165,6 +165,26 @@ int64_t gf2bv_factor_rank(const gf2bv_factor *h);
 int     gf2bv_factor_pivots(const gf2bv_factor *h, int32_t *out);      /* rank entries */
 int64_t gf2bv_factor_device_bytes(const gf2bv_factor *h);              /* device memory the handle holds */
 void    gf2bv_factor_free(gf2bv_factor *h);
+/* Equations appended to a kept factorization.  After appending B1, ..., Bm to a handle made from A, the handle behaves as
+ * gf2bv_factor_words on the row-stacked matrix [A; B1; ...; Bm] in that order: every later solve, rank, pivots and mode-1 basis is
+ * bit-identical to gf2bv_solve_rhs_words on the stacked matrix, and a right-hand side then has ceil(total_rows / 64) words (bit r =
+ * the constant of stacked row r).  The appended matrices have the handle's cols; their column `cols` is ignored; rows may be fewer
+ * than cols (rows >= 1; the total stays within the size limits of the single entries).  Appends and solves interleave in any
+ * order.  The cost is that of the new rows against the kept U and T, not a new factorization; the handle grows in steps of 1024
+ * rows of capacity.  GF2BV_ERR_ARG (before the device is touched) and GF2BV_ERR_NOMEM (the grown handle or the append's buffers
+ * do not fit; all are taken before the kept state changes) leave the handle as it was.  GF2BV_ERR_HIP means the append failed
+ * after it had started to change the handle (a device error, or a refused allocation of the mode-1 basis's back-substitution):
+ * the handle is then unusable -- rank and rows return -1, every other call GF2BV_ERR_ARG -- and only gf2bv_factor_free remains.
+ * Forms as in gf2bv_factor_words / _digits / _device (d_aug 16-byte aligned, even stride_words, read after everything enqueued
+ * on `stream` before the call). */
+int gf2bv_factor_append_words(gf2bv_factor *h, const uint64_t *aug, int64_t rows, int64_t stride_words);
+int gf2bv_factor_append_digits(gf2bv_factor *h, const uint32_t *digits, const int64_t *digit_off, int bits_per_digit,
+                               int64_t rows);
+int gf2bv_factor_append_device(gf2bv_factor *h, const void *d_aug, int64_t rows, int64_t stride_words, void *stream);
+int64_t gf2bv_factor_rows(const gf2bv_factor *h);                     /* the stacked row count (-1: null or unusable handle) */
+/* An independent handle with the same state: a device-to-device copy of the kept matrix and records (no factorization).  Appends
+ * to either leave the other as it is.  Free it with gf2bv_factor_free. */
+int     gf2bv_factor_copy(gf2bv_factor *h, gf2bv_factor **out);
 
 /* Batch of `nsys` independent equal-shape systems resident on one device
  * (system s starts at d_aug + s*sys_stride_words words); out[0..nsys) receives handles.
