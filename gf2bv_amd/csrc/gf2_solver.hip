@@ -47,17 +47,20 @@ int fail(int code, const char *what, hipError_t e = hipSuccess)
 #define GF2BV_RETRY_EVENTS (-77)
 thread_local int g_attempt = 0;      // attempt of the running C-ABI call (gf2bv_stats::handover_retries)
 template <class F>
+int catching(F &&body)
+{
+	try { return body(); }
+	catch (const std::bad_alloc &) { return fail(GF2BV_ERR_NOMEM, "out of host memory"); }
+	catch (const std::exception &e) { return fail(GF2BV_ERR_HIP, e.what()); }
+}
+template <class F>
 int guarded(F &&body)
 {
 	for (int attempt = 0;; attempt++) {
 		g_attempt = attempt;
-		try {
-			const int rc = body();
-			if (rc != GF2BV_RETRY_EVENTS) return rc;
-			if (attempt) return fail(GF2BV_ERR_HIP, "a stream hand-over gate timed out on the device");
-		}
-		catch (const std::bad_alloc &) { return fail(GF2BV_ERR_NOMEM, "out of host memory"); }
-		catch (const std::exception &e) { return fail(GF2BV_ERR_HIP, e.what()); }
+		const int rc = catching(body);
+		if (rc != GF2BV_RETRY_EVENTS) return rc;
+		if (attempt) return fail(GF2BV_ERR_HIP, "a stream hand-over gate timed out on the device");
 	}
 }
 
@@ -1934,6 +1937,93 @@ i64 pick_gang(i64 nsys, i64 rows, i64 cols, i64 free_bytes = -1)
 	return gang;
 }
 
+// fn(0) on the calling thread, fn(1) .. fn(n - 1) on threads of their own, each under the exception policy of guarded(); returns
+// the first failure with its message.
+template <class F>
+int run_on_threads(int n, F &&fn)
+{
+	std::mutex mu;
+	int rc = GF2BV_OK;
+	std::string why;
+	auto one = [&](int t) {
+		const int r = catching([&] { return fn(t); });
+		std::lock_guard<std::mutex> lk(mu);
+		if (r != GF2BV_OK && rc == GF2BV_OK) { rc = r; why = g_err; }
+	};
+	bool started = true;
+	{
+		std::vector<std::thread> th;
+		struct Join { std::vector<std::thread> &w; ~Join() { for (auto &t : w) t.join(); } } joiner{ th };
+		try { for (int t = 1; t < n; t++) th.emplace_back(one, t); }
+		catch (const std::exception &) { started = false; }
+		if (started && n > 0) one(0);
+	}
+	if (!started) return fail(GF2BV_ERR_NOMEM, "could not start a host thread");
+	return rc == GF2BV_OK ? GF2BV_OK : fail(rc, why.c_str());
+}
+
+// The gangs of a batch call: nsys same-shape systems in gangs of `gang` (the last one may be shorter), results into out[0..nsys),
+// which are null on entry.  Host threads (2 by default, GF2BV_BATCH_THREADS: 1 .. 16) each take a class-2 pool stream that
+// waits for `ready` and, when worker_bytes > 0, that many bytes of device memory; then they claim gangs in order from one
+// counter -- one gang's back-substitution, export and staging overlap another's elimination.  stage(S, s0, ns, buf) puts
+// systems s0 .. s0 + ns into the fresh Solver S on the worker's stream S.sA (shape, mode, and S.src or a filled S.M); solve_gang
+// does the rest, and the stream is synchronised after every gang (stage may reuse buf).  After the first failure no more
+// gangs are claimed and that failure is returned, every out[s] null.
+// Two threads that start together stay in phase for the whole job -- both gangs bulk-bound at once, both in their tails at
+// once.  Starting them apart (the list beginning with part gangs, thread t's first gang (t + 1) / NS of a full one) was built
+// and measured in round 4: 3.56 ms per system against 3.42 in phase on 192 x 32768^2 (profiles/r04_batch_scans.txt) -- the
+// bulk update runs throughout a gang's elimination (its launches are in flight 89 % of the wall time), there is no idle tail
+// to fill, and part gangs only make smaller launches.
+template <class Stage>
+int run_gangs(int device, i64 nsys, i64 gang, hipEvent_t ready, size_t worker_bytes, gf2bv_result **out, Stage &&stage)
+{
+	const i64 ngangs = (nsys + gang - 1) / gang;
+	int nthreads = 2;
+	if (const char *e = getenv("GF2BV_BATCH_THREADS")) { int v = atoi(e); if (v >= 1) nthreads = std::min(v, 16); }
+	std::atomic<i64> next_gang{0};
+	auto work = [&]() -> int {
+		struct Mine {
+			int device; hipStream_t st = nullptr; void *buf = nullptr;
+			~Mine()
+			{
+				if (st) (void)hipStreamSynchronize(st);
+				pool().release(buf);
+				pool().release_stream(st, device, 2);
+			}
+		} W{ device };
+		HIPCHK(hipSetDevice(device));
+		HIPCHK(pool().stream(&W.st, device, 2));
+		HIPCHK(hipStreamWaitEvent(W.st, ready, 0));
+		if (worker_bytes) HIPCHK(pool().alloc(&W.buf, worker_bytes, device));
+		for (i64 q; (q = next_gang.fetch_add(1)) < ngangs;) {
+			const i64 s0 = q * gang;
+			const int ns = (int)std::min<i64>(gang, nsys - s0);
+			// an expired hand-over gate voids THIS gang only: guarded() runs it once more with events (the device is marked by
+			// then; g_attempt is its members' handover_retries), after dropping what the voided attempt built
+			const int rc = guarded([&]() -> int {
+				for (int k = 0; k < ns; k++) { delete out[s0 + k]; out[s0 + k] = nullptr; }
+				Solver S;
+				S.t_begin = std::chrono::steady_clock::now();
+				S.device = device;
+				S.sA = W.st;
+				S.nsys = ns;
+				const int r = stage(S, s0, ns, W.buf);
+				return r ? r : solve_gang(S, &out[s0]);
+			});
+			if (rc) return rc;
+			HIPCHK(hipStreamSynchronize(W.st));
+		}
+		return GF2BV_OK;
+	};
+	const int rc = run_on_threads((int)std::min<i64>(ngangs, nthreads), [&](int) {
+		const int r = work();
+		if (r) next_gang.store(ngangs);
+		return r;
+	});
+	if (rc) for (i64 s = 0; s < nsys; s++) { delete out[s]; out[s] = nullptr; }
+	return rc;
+}
+
 int check_shape(i64 rows, i64 cols, int mode)
 {
 	// mirrors gf2bv/_internal.c:372-395
@@ -1967,17 +2057,25 @@ int check_matrix_input(const MatrixInput &in, i64 rows, i64 cols, int mode)
 	return check_matrix_form(in, rows, cols);
 }
 
+// The digits form of nrows rows: bits per digit, offsets that start at 0 (`from_zero`: a batch's offsets are absolute, a share
+// of a larger batch starts where the one before it ends) and never decrease, and digits wherever the offsets say there are some
+int check_digit_rows(const uint32_t *digits, const i64 *off, i64 nrows, int bpd, bool from_zero)
+{
+	if (bpd < 1 || bpd > 32) return fail(GF2BV_ERR_ARG, "bits_per_digit must be 1..32");
+	if (from_zero && off[0] != 0) return fail(GF2BV_ERR_ARG, "digit offsets must start at 0");
+	for (i64 r = 0; r < nrows; r++)
+		if (off[r + 1] < off[r]) return fail(GF2BV_ERR_ARG, "digit offsets must not decrease");
+	if (!digits && off[nrows] > off[0]) return fail(GF2BV_ERR_ARG, "null pointer");
+	return GF2BV_OK;
+}
+
 // The checks of the form in use alone (an append has shape rules of its own: check_append_args)
 int check_matrix_form(const MatrixInput &in, i64 rows, i64 cols)
 {
 	const i64 wt = (cols + 1 + 63) / 64;
-	if (in.h_off) {
-		if (in.bpd < 1 || in.bpd > 32) return fail(GF2BV_ERR_ARG, "bits_per_digit must be 1..32");
-		if (in.h_off[0] != 0) return fail(GF2BV_ERR_ARG, "digit offsets must start at 0");
-		for (i64 r = 0; r < rows; r++)
-			if (in.h_off[r + 1] < in.h_off[r]) return fail(GF2BV_ERR_ARG, "digit offsets must not decrease");
-		if (!in.h_digits && in.h_off[rows] > 0) return fail(GF2BV_ERR_ARG, "null pointer");
-	} else if (in.h_words) {
+	if (in.h_off)
+		return check_digit_rows(in.h_digits, in.h_off, rows, in.bpd, true);
+	else if (in.h_words) {
 		if (in.stride < wt) return fail(GF2BV_ERR_ARG, "stride_words does not cover cols+1 bits");
 	} else if (in.d_words) {
 		if (in.stride % 2 != 0 || in.stride < wt || ((uintptr_t)in.d_words & 15))
@@ -1985,6 +2083,18 @@ int check_matrix_form(const MatrixInput &in, i64 rows, i64 cols)
 	} else
 		return fail(GF2BV_ERR_ARG, "null pointer");
 	return GF2BV_OK;
+}
+
+// The argument checks of the digits batch entries, in the single entries' order: out (then out[0..nsys) cleared), the shape,
+// the form of all nsys * rows rows
+int check_digits_batch(const uint32_t *digits, const int64_t *off, int bpd, i64 nsys, i64 rows, i64 cols, int mode, gf2bv_result **out)
+{
+	if (!out || nsys < 0) return fail(GF2BV_ERR_ARG, "null pointer");
+	for (i64 s = 0; s < nsys; s++) out[s] = nullptr;
+	const int rc = check_shape(rows, cols, mode);
+	if (rc) return rc;
+	if (!off) return fail(GF2BV_ERR_ARG, "null pointer");
+	return check_digit_rows(digits, reinterpret_cast<const i64 *>(off), nsys * rows, bpd, false);
 }
 
 // ---- small systems: the whole solve in one launch (k_small_solve) ---------------------------------------------------
@@ -2895,37 +3005,19 @@ int gf2bv_solve_batch_device(void *d_aug, int64_t nsys, int64_t sys_stride_words
                              int64_t stride_words, int mode, int device, void *stream, int time_kernels, gf2bv_result **out)
 {
 	return guarded([&]() -> int {
-	if (!out || !d_aug || nsys < 0) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (!out || nsys < 0) return fail(GF2BV_ERR_ARG, "null pointer");
 	for (i64 s = 0; s < nsys; s++) out[s] = nullptr;
-	int rc = check_shape(rows, cols, mode);
+	MatrixInput in; in.d_words = (const u64 *)d_aug; in.stride = stride_words;
+	int rc = check_matrix_input(in, rows, cols, mode);
 	if (rc) return rc;
-	if (stride_words % 2 != 0 || stride_words < (cols + 1 + 63) / 64 || sys_stride_words < rows * stride_words ||
-	    ((uintptr_t)d_aug & 15) || (sys_stride_words & 1))
-		return fail(GF2BV_ERR_ARG, "bad batch layout");
+	if ((sys_stride_words & 1) || sys_stride_words < rows * stride_words)
+		return fail(GF2BV_ERR_ARG, "sys_stride_words must be even and at least rows * stride_words");
 	rc = check_device(device);
 	if (rc) return rc;
 	// Independent systems of one shape run as GANGS: the forward elimination of `gang` systems is one set
 	// of launches (blockIdx.y = system), so the latency-bound panel path and the host's ~3500 launches
 	// per elimination are shared by the whole gang and the bulk updates of all its systems fill the chip.
-	// NS host threads each take every NS-th gang on their own stream pair (one gang's back-substitution
-	// and export then overlap the next gang's elimination).
 	const i64 gang = pick_gang(nsys, rows, cols);
-	// Gangs in flight: NS host threads, each with its own stream pair, take the next gang off a shared list.  Two threads that
-	// start together stay in phase for the whole job -- both gangs bulk-bound at once, both in their tails at once.  Starting them
-	// apart (the list beginning with part gangs, thread t's first gang (t + 1) / NS of a full one) was built and
-	// measured in round 4: 3.56 ms per system against 3.42 in phase on 192 x 32768^2 (profiles/r04_batch_scans.txt) -- the bulk
-	// update runs throughout a gang's elimination (its launches are in flight 89 % of the wall time), there is no idle tail to
-	// fill, and part gangs only make smaller launches.  Not the default.
-	std::vector<std::pair<i64, int>> ranges;       // (first system, systems)
-	int NS = 2;
-	if (const char *e = getenv("GF2BV_BATCH_THREADS")) { int v = atoi(e); if (v >= 1) NS = std::min(v, 16); }
-	{
-		i64 s0 = 0;
-		while (s0 < nsys) { const i64 ns = std::min<i64>(gang, nsys - s0); ranges.emplace_back(s0, (int)ns); s0 += ns; }
-	}
-	const i64 ngangs = (i64)ranges.size();
-	NS = (int)std::min<i64>(ngangs, NS);
-	std::atomic<i64> next_gang{0};
 	// Ordering contract: the matrices are whatever `stream` (the caller's stream, NULL = the null stream) has
 	// produced when this call is made.  The gangs run on the library's own non-blocking streams, which are not
 	// ordered against any other stream by themselves: each waits for an event recorded on `stream` here.
@@ -2935,53 +3027,13 @@ int gf2bv_solve_batch_device(void *d_aug, int64_t nsys, int64_t sys_stride_words
 	} ready;
 	HIPCHK(pool().event(&ready.ev, false));
 	HIPCHK(hipEventRecord(ready.ev, (hipStream_t)stream));
-	std::vector<int> rcs(NS, GF2BV_OK);
-	std::vector<std::string> errs(NS);
-	HIPCHK(hipSetDevice(device));
-	std::vector<std::thread> workers;
-	struct Join { std::vector<std::thread> &w; ~Join() { for (auto &t : w) if (t.joinable()) t.join(); } } joiner{ workers };
-	for (int t = 0; t < NS; t++) {
-		workers.emplace_back([&, t]() {
-			if (hipSetDevice(device) != hipSuccess) { rcs[t] = GF2BV_ERR_HIP; errs[t] = "hipSetDevice"; return; }
-			hipStream_t st = nullptr;
-			const bool own_st = true;
-			if (pool().stream(&st, device, 2) != hipSuccess) { rcs[t] = GF2BV_ERR_HIP; errs[t] = "hipStreamCreate"; return; }
-			if (hipStreamWaitEvent(st, ready.ev, 0) != hipSuccess) { rcs[t] = GF2BV_ERR_HIP; errs[t] = "hipStreamWaitEvent"; }
-			for (i64 q; (q = next_gang.fetch_add(1)) < ngangs && rcs[t] == GF2BV_OK;) {
-				try {
-				const i64 s0 = ranges[(size_t)q].first;
-				const int ns = ranges[(size_t)q].second;
-				int rc = GF2BV_OK;
-				// an expired hand-over gate voids THIS gang only: its results (if any were built) are dropped and the
-				// gang runs once more with events -- the device is marked by then; other gangs' results stay
-				for (int attempt = 0; attempt < 2; attempt++) {
-					g_attempt = attempt;                        // (this worker thread's: gf2bv_stats::handover_retries of the gang)
-					Solver S;
-					S.t_begin = std::chrono::steady_clock::now();
-					S.device = device;
-					S.sA = st;
-					S.nsys = ns;
-					S.src = (const u64 *)d_aug + s0 * sys_stride_words;
-					S.src_sys_words = sys_stride_words;
-					S.rows = rows; S.cols = cols; S.stride = stride_words; S.mode = mode;
-					S.time_kernels = time_kernels != 0;
-					rc = solve_gang(S, &out[s0]);
-					if (rc != GF2BV_RETRY_EVENTS) break;
-					for (int k = 0; k < ns; k++) { delete out[s0 + k]; out[s0 + k] = nullptr; }
-					(void)hipStreamSynchronize(st);
-				}
-				if (rc == GF2BV_RETRY_EVENTS) { rc = GF2BV_ERR_HIP; g_err = "a stream hand-over gate timed out on the device"; }
-				if (rc != GF2BV_OK) { rcs[t] = rc; errs[t] = g_err; }
-				} catch (const std::bad_alloc &) { rcs[t] = GF2BV_ERR_NOMEM; errs[t] = "out of host memory"; }
-				(void)hipStreamSynchronize(st);
-			}
-			if (own_st) pool().release_stream(st, device, 2);
-		});
-	}
-	for (auto &w : workers) w.join();
-	for (int t = 0; t < NS; t++)
-		if (rcs[t] != GF2BV_OK) return fail(rcs[t], errs[t].c_str());
-	return GF2BV_OK;
+	return run_gangs(device, nsys, gang, ready.ev, 0, out, [&](Solver &S, i64 s0, int, void *) -> int {
+		S.src = (const u64 *)d_aug + s0 * sys_stride_words;
+		S.src_sys_words = sys_stride_words;
+		S.rows = rows; S.cols = cols; S.stride = stride_words; S.mode = mode;
+		S.time_kernels = time_kernels != 0;
+		return GF2BV_OK;
+	});
 	});
 }
 
@@ -3026,30 +3078,20 @@ int gf2bv_solve_words(const uint64_t *aug, int64_t rows, int64_t cols, int64_t s
 	});
 }
 
-// One device's share of a digits batch.  digit_off[] holds ABSOLUTE digit positions (a later share of a larger batch does
-// not start at 0): only digits[digit_off[0] .. digit_off[nsys * rows]) are uploaded and the pack kernel sees them through a
-// rebased pointer.
-static int batch_digits_on(const uint32_t *digits, const int64_t *digit_off, int bits_per_digit, int64_t nsys,
-                           int64_t rows, int64_t cols, int mode, int device, gf2bv_result **out)
+// digit_off[] holds ABSOLUTE digit positions (a share of a larger batch, from gf2bv_solve_batch_digits_multi, does not start
+// at 0): only digits[digit_off[0] .. digit_off[nsys * rows]) are uploaded and the pack kernel sees them through a rebased pointer.
+int gf2bv_solve_batch_digits(const uint32_t *digits, const int64_t *digit_off, int bits_per_digit, int64_t nsys,
+                             int64_t rows, int64_t cols, int mode, int device, gf2bv_result **out)
 {
-	bool again = false;
 	return guarded([&]() -> int {
-	if (!out || !digit_off || nsys < 0) return fail(GF2BV_ERR_ARG, "null pointer");
-	for (i64 s = 0; s < nsys; s++) { if (again) delete out[s]; out[s] = nullptr; }      // (a retry drops what the voided attempt built)
-	again = true;
-	int rc = check_shape(rows, cols, mode);
+	int rc = check_digits_batch(digits, digit_off, bits_per_digit, nsys, rows, cols, mode, out);
 	if (rc) return rc;
-	if (bits_per_digit < 1 || bits_per_digit > 32) return fail(GF2BV_ERR_ARG, "bits_per_digit must be 1..32");
 	rc = check_device(device);
 	if (rc) return rc;
 	if (nsys == 0) return GF2BV_OK;
-	HIPCHK(hipSetDevice(device));
 	const i64 wt = (cols + 1 + 63) / 64, ntiles = tiles_for(wt), srows = slab_rows(rows);
 	const i64 m_stride = ntiles * TW * srows;
-	const i64 nrows_all = nsys * rows, dig0 = digit_off[0], ndig = digit_off[nrows_all] - dig0;
-	if (ndig < 0) return fail(GF2BV_ERR_ARG, "digit offsets must not decrease");
-	for (i64 r = 0; r < nrows_all; r++)          // (the pack kernel reads digits[off[r] .. off[r + 1]) of the uploaded share)
-		if (digit_off[r + 1] < digit_off[r]) return fail(GF2BV_ERR_ARG, "digit offsets must not decrease");
+	const i64 nrows_all = nsys * rows;
 	// The offsets go up once; the DIGITS go up gang by gang, each on the stream of the host thread that takes the gang (round 5: two
 	// threads, as in gf2bv_solve_batch_device -- one gang's upload and pack run under the other's elimination, and two latency-bound
 	// gangs of sparse systems overlap; before: one upload of everything, then the gangs one after the other on one stream -- 16 MT19937
@@ -3075,83 +3117,20 @@ static int batch_digits_on(const uint32_t *digits, const int64_t *digit_off, int
 	i64 max_dig = 1;
 	for (i64 q = 0; q < ngangs; q++)
 		max_dig = std::max<i64>(max_dig, digit_off[std::min<i64>(nsys, (q + 1) * gang) * rows] - digit_off[q * gang * rows]);
-	int NS = 2;
-	if (const char *e = getenv("GF2BV_BATCH_THREADS")) { int v = atoi(e); if (v >= 1) NS = std::min(v, 16); }
-	NS = (int)std::min<i64>(ngangs, NS);
-	std::atomic<i64> next_gang{0};
-	std::vector<int> rcs((size_t)NS, GF2BV_OK);
-	std::vector<std::string> errs((size_t)NS);
-	const int attempt0 = g_attempt;                    // (a whole-call retry by guarded() reaches the workers' solvers)
-	auto worker = [&](int t) {
-		struct Mine {
-			hipStream_t st = nullptr; uint32_t *dig = nullptr; int device = 0; bool own = true;
-			~Mine()
-			{
-				if (st) (void)hipStreamSynchronize(st);
-				pool().release(dig);
-				if (st && own) pool().release_stream(st, device, 2);
-			}
-		} W;
-		W.device = device;
-		auto run = [&]() -> int {
-			HIPCHK(hipSetDevice(device));
-			HIPCHK(pool().stream(&W.st, device, 2));
-			HIPCHK(hipStreamWaitEvent(W.st, G.ready, 0));
-			HIPCHK(pool().alloc((void **)&W.dig, sizeof(uint32_t) * max_dig, device));
-			for (i64 q; (q = next_gang.fetch_add(1)) < ngangs;) {
-				const i64 s0 = q * gang;
-				const int ns = (int)std::min<i64>(gang, nsys - s0);
-				const i64 d0 = digit_off[s0 * rows], nd = digit_off[(s0 + ns) * rows] - d0;
-				if (nd) HIPCHK(hipMemcpyAsync(W.dig, digits + d0, sizeof(uint32_t) * nd, hipMemcpyHostToDevice, W.st));
-				int rc = GF2BV_OK;
-				// an expired hand-over gate voids THIS gang only (as in gf2bv_solve_batch_device): packed and solved once more with events
-				for (int attempt = attempt0; attempt < 2; attempt++) {
-					g_attempt = attempt;
-					Solver S;
-					S.t_begin = std::chrono::steady_clock::now();
-					S.device = device;
-					S.sA = W.st;
-					S.nsys = ns;
-					S.rows = rows; S.cols = cols; S.mode = mode;
-					S.stride = ntiles * TW;
-					HIPCHK(pool().alloc((void **)&S.M, sizeof(u64) * m_stride * S.nsys + kOuterSlackBytes, device));
-					if (rows * ntiles * TW > 0)
-						k_pack_digits<<<dim3((unsigned)((ntiles * TW + 255) / 256), (unsigned)std::min<i64>(rows, 65535), S.nsys), dim3(256), 0, S.sA>>>(
-							W.dig, G.off + s0 * rows, bits_per_digit, (i64)rows, (i64)cols, ntiles * TW, srows, S.M, SysStride{m_stride, 0}, d0);
-					HIPCHK(hipGetLastError());
-					rc = solve_gang(S, &out[s0]);
-					if (rc != GF2BV_RETRY_EVENTS) break;
-					for (int k = 0; k < ns; k++) { delete out[s0 + k]; out[s0 + k] = nullptr; }
-					(void)hipStreamSynchronize(W.st);
-				}
-				if (rc == GF2BV_RETRY_EVENTS) return fail(GF2BV_ERR_HIP, "a stream hand-over gate timed out on the device");
-				if (rc != GF2BV_OK) return rc;
-				HIPCHK(hipStreamSynchronize(W.st));          // (the next gang's digits overwrite W.dig)
-			}
-			return GF2BV_OK;
-		};
-		try { rcs[(size_t)t] = run(); }
-		catch (const std::bad_alloc &) { rcs[(size_t)t] = fail(GF2BV_ERR_NOMEM, "out of host memory"); }
-		catch (const std::exception &e) { rcs[(size_t)t] = fail(GF2BV_ERR_HIP, e.what()); }
-		if (rcs[(size_t)t] != GF2BV_OK) { errs[(size_t)t] = g_err; next_gang.store(ngangs); }
-	};
-	{
-		std::vector<std::thread> workers;
-		struct Join { std::vector<std::thread> &w; ~Join() { for (auto &t : w) if (t.joinable()) t.join(); } } joiner{ workers };
-		for (int t = 1; t < NS; t++) workers.emplace_back(worker, t);
-		worker(0);
-	}
-	g_attempt = attempt0;
-	for (int t = 0; t < NS; t++)
-		if (rcs[(size_t)t] != GF2BV_OK) return fail(rcs[(size_t)t], errs[(size_t)t].c_str());
-	return GF2BV_OK;
+	return run_gangs(device, nsys, gang, G.ready, sizeof(uint32_t) * max_dig, out, [&](Solver &S, i64 s0, int ns, void *buf) -> int {
+		uint32_t *dig = (uint32_t *)buf;
+		const i64 d0 = digit_off[s0 * rows], nd = digit_off[(s0 + ns) * rows] - d0;
+		if (nd) HIPCHK(hipMemcpyAsync(dig, digits + d0, sizeof(uint32_t) * nd, hipMemcpyHostToDevice, S.sA));
+		S.rows = rows; S.cols = cols; S.mode = mode;
+		S.stride = ntiles * TW;
+		HIPCHK(pool().alloc((void **)&S.M, sizeof(u64) * m_stride * S.nsys + kOuterSlackBytes, device));
+		if (rows * ntiles * TW > 0)
+			k_pack_digits<<<dim3((unsigned)((ntiles * TW + 255) / 256), (unsigned)std::min<i64>(rows, 65535), S.nsys), dim3(256), 0, S.sA>>>(
+				dig, G.off + s0 * rows, bits_per_digit, (i64)rows, (i64)cols, ntiles * TW, srows, S.M, SysStride{m_stride, 0}, d0);
+		HIPCHK(hipGetLastError());
+		return GF2BV_OK;
 	});
-}
-
-int gf2bv_solve_batch_digits(const uint32_t *digits, const int64_t *digit_off, int bits_per_digit, int64_t nsys,
-                             int64_t rows, int64_t cols, int mode, int device, gf2bv_result **out)
-{
-	return batch_digits_on(digits, digit_off, bits_per_digit, nsys, rows, cols, mode, device, out);
+	});
 }
 
 // The same batch over SEVERAL devices (the reference solves one system per m4ri_solve call on one core; independent
@@ -3163,30 +3142,19 @@ int gf2bv_solve_batch_digits_multi(const uint32_t *digits, const int64_t *digit_
                                    int64_t rows, int64_t cols, int mode, const int *devices, int ndevices,
                                    gf2bv_result **out)
 {
-	if (!out || !digit_off || !devices || nsys < 0 || ndevices < 1) return fail(GF2BV_ERR_ARG, "null pointer");
-	for (i64 s = 0; s < nsys; s++) out[s] = nullptr;
-	for (int k = 0; k < ndevices; k++) { int rc = check_device(devices[k]); if (rc) return rc; }
+	return guarded([&]() -> int {
+	int rc = check_digits_batch(digits, digit_off, bits_per_digit, nsys, rows, cols, mode, out);
+	if (rc) return rc;
+	if (!devices || ndevices < 1) return fail(GF2BV_ERR_ARG, "null pointer");
+	for (int k = 0; k < ndevices; k++) { rc = check_device(devices[k]); if (rc) return rc; }
 	const int nshares = (int)std::min<i64>(ndevices, std::max<i64>(nsys, 1));
-	if (nshares == 1) return batch_digits_on(digits, digit_off, bits_per_digit, nsys, rows, cols, mode, devices[0], out);
-	std::vector<int> rcs((size_t)nshares, GF2BV_OK);
-	std::vector<std::string> errs((size_t)nshares);
-	std::vector<std::thread> th;
-	try {
-		for (int k = 0; k < nshares; k++) {
-			const i64 lo = nsys * k / nshares, hi = nsys * (k + 1) / nshares;
-			th.emplace_back([&, k, lo, hi]() {
-				rcs[k] = batch_digits_on(digits, digit_off + lo * rows, bits_per_digit, hi - lo, rows, cols, mode, devices[k], out + lo);
-				if (rcs[k] != GF2BV_OK) errs[k] = g_err;
-			});
-		}
-	} catch (const std::exception &) { for (auto &t : th) t.join(); for (i64 s = 0; s < nsys; s++) { delete out[s]; out[s] = nullptr; } return fail(GF2BV_ERR_NOMEM, "could not start a host thread per device"); }
-	for (auto &t : th) t.join();
-	for (int k = 0; k < nshares; k++)
-		if (rcs[k] != GF2BV_OK) {
-			for (i64 s = 0; s < nsys; s++) { delete out[s]; out[s] = nullptr; }
-			return fail(rcs[k], errs[k].c_str());
-		}
-	return GF2BV_OK;
+	rc = run_on_threads(nshares, [&](int k) {
+		const i64 lo = nsys * k / nshares, hi = nsys * (k + 1) / nshares;
+		return gf2bv_solve_batch_digits(digits, digit_off + lo * rows, bits_per_digit, hi - lo, rows, cols, mode, devices[k], out + lo);
+	});
+	if (rc) for (i64 s = 0; s < nsys; s++) { delete out[s]; out[s] = nullptr; }
+	return rc;
+	});
 }
 
 int gf2bv_solve_digits(const uint32_t *digits, const int64_t *digit_off, int bits_per_digit, int64_t rows,

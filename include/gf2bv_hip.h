@@ -197,7 +197,10 @@ int     gf2bv_factor_copy(gf2bv_factor *h, gf2bv_factor **out);
  * Ordering: the gangs run on the library's own streams; they start after everything that was
  * enqueued on `stream` (a HIP stream handle, NULL = the null stream) when the call is made -- the stream
  * that produced the matrices -- and the call returns when all systems are solved.
- * Independent systems are the unit that bench.py shards across GPUs (BASELINE configs[3]). */
+ * Independent systems are the unit that bench.py shards across GPUs (BASELINE configs[3]).
+ * Layout: the form of gf2bv_solve_device per system (d_aug 16-byte aligned, even stride_words covering cols+1 bits), and an
+ * even sys_stride_words of at least rows*stride_words.  On any non-zero return every out[s] is null (results of gangs that
+ * had finished are freed), and after the first failing gang no further gang is started. */
 int gf2bv_solve_batch_device(void *d_aug, int64_t nsys, int64_t sys_stride_words,
                              int64_t rows, int64_t cols, int64_t stride_words,
                              int mode, int device, void *stream, int time_kernels, gf2bv_result **out);
@@ -205,7 +208,8 @@ int gf2bv_solve_batch_device(void *d_aug, int64_t nsys, int64_t sys_stride_words
 /* Batch of `nsys` independent equal-shape systems given as digit arrays (see gf2bv_solve_digits):
  * row r of system s is entry s*rows + r of digit_off (nsys*rows + 1 entries).  One upload, lock-step
  * gangs as in gf2bv_solve_batch_device.  This is what a batched m4ri_solve binds
- * (gf2bv_amd._internal.m4ri_solve_many). */
+ * (gf2bv_amd._internal.m4ri_solve_many).  The offsets are absolute (they need not start at 0) and must not decrease;
+ * digits may be null only when there are none.  On any non-zero return every out[s] is null. */
 int gf2bv_solve_batch_digits(const uint32_t *digits, const int64_t *digit_off, int bits_per_digit,
                              int64_t nsys, int64_t rows, int64_t cols, int mode, int device,
                              gf2bv_result **out);
@@ -217,7 +221,8 @@ int gf2bv_solve_batch_digits(const uint32_t *digits, const int64_t *digit_off, i
  * The reference solves one system per m4ri_solve call (gf2bv/_internal.c:359-502): independent systems -- one per
  * output bit / per instance in the recovery examples -- are the natural shard unit; this is what
  * m4ri_solve_many(..., devices) binds: devices=None = the module's default device (as m4ri_solve: a process pinned to one
- * GPU stays on it), devices="all" = every visible device, or an explicit list. */
+ * GPU stays on it), devices="all" = every visible device, or an explicit list.  The arguments are checked as in
+ * gf2bv_solve_batch_digits before any device is; on any non-zero return every out[s] is null. */
 int gf2bv_solve_batch_digits_multi(const uint32_t *digits, const int64_t *digit_off, int bits_per_digit,
                                    int64_t nsys, int64_t rows, int64_t cols, int mode,
                                    const int *devices, int ndevices, gf2bv_result **out);

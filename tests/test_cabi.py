@@ -110,6 +110,62 @@ def test_single_entries_check_arguments_before_device_use():
     assert not h.value
 
 
+def test_batch_entries_check_arguments_before_device_use():
+    """gf2bv_solve_batch_{device,digits,digits_multi} check in the single entries' order -- out, shape, form, then the device --
+    and fail with GF2BV_ERR_ARG (1) and a specific message, on a machine without a GPU too; every out[s] is null afterwards."""
+    L = hip.lib()
+    nsys, rows, cols = 3, 130, 100
+    aug = np.zeros((nsys * rows + 1, 2), dtype=np.uint64)
+    A, SS = aug.ctypes.data, rows * 2
+    off = np.zeros(nsys * rows + 1, dtype=np.int64)
+    dig = np.zeros(4, dtype=np.uint32)
+    O, D = off.ctypes.data, dig.ctypes.data
+    devices = (ctypes.c_int * 1)(0)
+    out = (ctypes.c_void_p * nsys)()
+
+    def err(call, what, cleared=True):
+        for s in range(nsys):
+            out[s] = 0x1000 + s                                 # never a handle: cleared before anything can free it
+        rc = call()
+        assert rc == 1, (rc, L.gf2bv_last_error())
+        assert what.encode() in L.gf2bv_last_error(), L.gf2bv_last_error()
+        if cleared:
+            assert not any(out[s] for s in range(nsys)), list(out)
+
+    def dev(d_aug=A, sys_stride=SS, r=rows, stride=2, mode=0, o=out):
+        return lambda: L.gf2bv_solve_batch_device(d_aug, nsys, sys_stride, r, cols, stride, mode, 0, None, 0, o)
+
+    err(dev(o=None), "null", cleared=False)
+    err(dev(d_aug=None), "null")
+    err(dev(mode=3), "Invalid mode")
+    err(dev(r=99), "greater than or equal")
+    err(dev(stride=3, sys_stride=rows * 4), "stride")
+    err(dev(stride=1), "stride")
+    err(dev(d_aug=A + 8), "16-byte alignment")
+    err(dev(sys_stride=SS + 1), "sys_stride_words")
+    err(dev(sys_stride=SS - 2), "sys_stride_words")
+
+    decreasing = np.arange(nsys * rows + 1, dtype=np.int64) + 7   # (absolute: a share of a larger batch need not start at 0)
+    decreasing[200] = 3
+    some = np.arange(nsys * rows + 1, dtype=np.int64) + 7
+
+    def digs(digits=D, offsets=O, bpd=30, r=rows, mode=0, o=out):
+        return [lambda: L.gf2bv_solve_batch_digits(digits, offsets, bpd, nsys, r, cols, mode, 0, o),
+                lambda: L.gf2bv_solve_batch_digits_multi(digits, offsets, bpd, nsys, r, cols, mode, devices, 1, o)]
+
+    for call in digs(o=None):
+        err(call, "null", cleared=False)
+    checks = [(digs(offsets=None), "null"), (digs(mode=3), "Invalid mode"), (digs(r=99), "greater than or equal"),
+              (digs(bpd=0), "bits_per_digit"), (digs(bpd=33), "bits_per_digit"),
+              (digs(offsets=decreasing.ctypes.data), "must not decrease"),
+              (digs(digits=None, offsets=some.ctypes.data), "null")]
+    for calls, what in checks:
+        for call in calls:
+            err(call, what)
+    err(lambda: L.gf2bv_solve_batch_digits_multi(D, O, 30, nsys, rows, cols, 3, None, 0, out), "Invalid mode")
+    err(lambda: L.gf2bv_solve_batch_digits_multi(D, O, 30, nsys, rows, cols, 0, None, 0, out), "null")
+
+
 def test_no_cpu_fallback():
     if hip.device_count() > 0:
         pytest.skip("a GPU is present")
