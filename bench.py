@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: GF(2) row-XORs/s + solve wall-time, dense N x N solve_one.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload single|batch] [--n 65536] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload single|batch] [--n 65536] [--dump-outputs DIR] [--full]
 
 Workloads, all through the C ABI, inputs resident in HBM before the timed region:
 
@@ -10,10 +10,11 @@ Workloads, all through the C ABI, inputs resident in HBM before the timed region
       back-substitution + export) by gf2bv_solve_device; at N > 1 every rank solves its own system (generator seed +
       rank), one all_gather of the solutions at the end -- per-GPU work is fixed, "scaling" is "weak", and the lines of
       N = 1, 2, 4, 8 are the SAME workload, so the driver's scaling curve compares like with like.
-      Every default line also carries `batch_c4`: BASELINE.json configs[3], the job of 512 independent 32768 x 32768
+      With --full the line also carries `batch_c4`: BASELINE.json configs[3], the job of 512 independent 32768 x 32768
       systems sharded in contiguous blocks over the N ranks (1 warm-up + 1 timed step; at N = 1 all 512 on the one GPU,
       73 GB resident -- the anchor of the strong-scaling curve `batch_c4.systems_per_s` over N), with its own roofline
-      block.  The N = 1 line adds `target_262144` (the north-star size, 2 steps after 1 warm-up) and `cpu_baseline`.
+      block.  The N = 1 line of --full adds `plain_ms_per_step`, `target_262144` (the north-star size, 2 steps after 1
+      warm-up), the example legs `c3_mt19937`, `c5_xoshiro`, `h2d_inclusive` and `cpu_baseline`.
       None of these extras is ever `value`.
   batch  (`--workload batch`; BASELINE.json configs[3] as the line's own `value`): 512 independent 32768 x 32768
       systems, sharded in contiguous blocks over the ranks (gf2bv_amd.batch.shard_bounds), every rank solving its
@@ -21,11 +22,16 @@ Workloads, all through the C ABI, inputs resident in HBM before the timed region
       the fixed-size records [status, rank, origin] (RCCL over xGMI).  One "step" = the whole 512-system job; the total
       is fixed, so "scaling" is "strong".
 
+A plain run (no --full) does what its headline figure needs: set up, warm up, time the steps, --dump-outputs, the
+parity gate on the steps' answers (one residual kernel), the line.  Everything that takes a run of its own -- the
+extra legs above, the CPU baseline, the stream ceiling and the LDS clock probe beside the roofline -- runs with --full
+only; --no-plain-leg, --no-cpu-baseline, --no-batch-c4, --no-extra-legs and --target-n 0 trim a --full run.
+
 Launched for N > 1 as `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (one rank per GPU).
 Rank 0 prints ONE JSON line carrying
   roofline     : the bulk-update kernel (dominant): algorithmic bytes (16 B per active word per pass) / HIP-event time
-                 of its launches, against 8 TB/s HBM
-  cpu_baseline : the CPU oracle (M4RM-style "port", OpenMP) timed on this host on a bounded sample (rank 0, N = 1 only)
+                 of its launches (the timed steps' own), against 8 TB/s HBM; --full adds the same-run stream ceilings
+  cpu_baseline : (--full) the CPU oracle (M4RM-style "port", OpenMP) timed on this host on a bounded sample (rank 0, N = 1 only)
 torch is plumbing here: device memory, the RCCL gather, barriers.
 """
 from __future__ import annotations
@@ -62,23 +68,26 @@ def parse():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", choices=["auto", "single", "batch", "sharded"], default="auto",
                     help="auto = single at every N (configs[1] per GPU, weak scaling) with the configs[3] job as the extra block "
-                         "`batch_c4`; batch = configs[3] as the line itself; sharded = ONE --n system with its columns over "
-                         "the ranks (SURVEY 8f-1, strong scaling)")
+                         "`batch_c4` under --full; batch = configs[3] as the line itself; sharded = ONE --n system with its columns "
+                         "over the ranks (SURVEY 8f-1, strong scaling)")
     ap.add_argument("--n", "--size", dest="n", type=int, default=65536,
                     help="single: system size N (rows = cols); spell it --size under torch.distributed.run, whose own parser "
                          "takes a bare --n for an abbreviation of its options")
     ap.add_argument("--seed", type=int, default=None)
-    ap.add_argument("--no-plain-leg", action="store_true", help="skip the repeat of the timed steps under GF2BV_PLAIN=1 (profiling runs: keeps the kernel statistics to the default path)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: the plain leg, the stream ceiling and LDS clock beside the "
+                         "roofline, target_262144, batch_c4, the example legs and the CPU baseline (a plain run does the headline steps only)")
+    ap.add_argument("--no-plain-leg", action="store_true", help="--full: skip the repeat of the timed steps under GF2BV_PLAIN=1 (profiling runs: keeps the kernel statistics to the default path)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-n", type=int, default=None, help="size of the bounded CPU-baseline sample (default: 65536 single / 32768 batch)")
     ap.add_argument("--batch-total", type=int, default=512, help="batch: systems in the whole job (sharded over the ranks)")
     ap.add_argument("--batch-n", type=int, default=32768)
     ap.add_argument("--no-batch-c4", action="store_true",
-                    help="single: skip the `batch_c4` block (the configs[3] job of --batch-total x --batch-n systems over the ranks)")
+                    help="single, --full: skip the `batch_c4` block (the configs[3] job of --batch-total x --batch-n systems over the ranks)")
     ap.add_argument("--target-n", type=int, default=262144,
-                    help="single: also run the north-star size (1 warm-up + 2 steps) as `target_262144` (0 = skip)")
+                    help="single, --full: also run the north-star size (1 warm-up + 2 steps) as `target_262144` (0 = skip)")
     ap.add_argument("--no-extra-legs", action="store_true",
-                    help="single, N = 1: skip c3_mt19937 (configs[2]), c5_xoshiro (configs[4]) and the host-resident 65536^2 solve")
+                    help="single, N = 1, --full: skip c3_mt19937 (configs[2]), c5_xoshiro (configs[4]) and the host-resident 65536^2 solve")
     ap.add_argument("--no-kernel-events", action="store_true",
                     help="do not bracket bulk-update launches with HIP events (roofline becomes null)")
     ap.add_argument("--dry-run-ranks", action="store_true",
@@ -223,8 +232,10 @@ def lds_clock(device: int) -> dict:
     return _LDS_CLOCK[device]
 
 
-def roofline_block(stats_list, sweep_ms_total: float, n: int, device: int, ceil: dict | None, note: str | None = None):
-    """`stats_list`: the gf2bv_stats of the solves whose bulk-update launches took `sweep_ms_total` (HIP events)."""
+def roofline_block(stats_list, sweep_ms_total: float, n: int, device: int, ceil: dict | None, note: str | None = None,
+                   probe_lds: bool = True):
+    """`stats_list`: the gf2bv_stats of the solves whose bulk-update launches took `sweep_ms_total` (HIP events).
+    `probe_lds`: measure the shader clock under an LDS-bound load for the `lds` block (a run of its own; null without it)."""
     if sweep_ms_total <= 0:
         return None
     s0 = stats_list[0]
@@ -241,7 +252,7 @@ def roofline_block(stats_list, sweep_ms_total: float, n: int, device: int, ceil:
     #  in both cases, so lines of all rounds compare.
     outer_dominant = 2 * s0.get("outer_blocks", 0) > s0["n_sweeps"]
     lds = None
-    if outer_dominant:
+    if outer_dominant and probe_lds:
         clk = lds_clock(device)
         lds_bytes = 8.0 * g * t * float(sum(s["sweep_words"] for s in stats_list))
         lds_rate = lds_bytes / (sweep_ms_total * 1e-3) / 1e9
@@ -362,7 +373,7 @@ def run_single(args, world, rank, local_rank, dev):
     # (round 6) the same steps with GF2BV_PLAIN=1 -- no stream-pair probes, no XCD pinning, events instead of memory gates, no
     # optimistic enqueue -- on rank 0 at N = 1: what a box costs where those heuristics are off; never part of `value`
     plain = None
-    if world == 1 and os.environ.get("GF2BV_PLAIN") is None and not args.no_plain_leg:
+    if args.full and world == 1 and os.environ.get("GF2BV_PLAIN") is None and not args.no_plain_leg:
         os.environ["GF2BV_PLAIN"] = "1"
         try:
             p_elapsed, p_stats, _ = timed_single(mat, n, stride, args.steps, 1, local_rank, dev, world, False)
@@ -378,19 +389,20 @@ def run_single(args, world, rank, local_rank, dev):
     del mat
     # the north-star leg BEFORE the 73 GB batch job: behind it the 8 GiB working copy comes out of a device heap that has just
     # held and released hundreds of buffers, and the same solve reads ~3 % slower (1.308 against 1.271 s on one box)
-    ceil = hip.stream_ceiling(2 << 30, local_rank) if rank == 0 else None
+    ceil = hip.stream_ceiling(2 << 30, local_rank) if args.full and rank == 0 else None
     target = None
-    if world == 1 and args.target_n > 0 and n == 65536:
+    if args.full and world == 1 and args.target_n > 0 and n == 65536:
         torch.cuda.empty_cache()
         target = target_leg(args.target_n, local_rank, dev, ceil)
     c4 = None
-    if not args.no_batch_c4 and args.batch_total > 0:
+    if args.full and not args.no_batch_c4 and args.batch_total > 0:
         torch.cuda.empty_cache()
         c4 = batch_job(args, world, rank, local_rank, dev, steps=1, warmup=1)       # every rank takes part (barriers, gather)
     if rank != 0:
         return None
     s0 = stats[-1].stats
-    rl = roofline_block([s.stats for s in stats], float(sum(s.stats["ms_sweep"] for s in stats)), n, local_rank, ceil)
+    rl = roofline_block([s.stats for s in stats], float(sum(s.stats["ms_sweep"] for s in stats)), n, local_rank, ceil,
+                        probe_lds=args.full)
     roofline = None
     if rl:
         roofline, launches = rl
@@ -430,14 +442,14 @@ def run_single(args, world, rank, local_rank, dev):
         out[f"target_{args.target_n}"] = target
     if c4 is not None:
         out["batch_c4"] = c4
-    if world == 1 and not args.no_extra_legs:
+    if args.full and world == 1 and not args.no_extra_legs:
         # the reference's own example timings (examples/mt.py:16,32,35; examples/xoshiro.py) and the host-resident headline
         # system: extra fields, never `value`
         torch.cuda.empty_cache()
         out["c3_mt19937"] = c3_mt19937_leg(local_rank, not args.no_cpu_baseline)
         out["c5_xoshiro"] = c5_xoshiro_leg(local_rank, not args.no_cpu_baseline)
         out["h2d_inclusive"] = h2d_leg(n, seed, local_rank, dev)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         m = args.cpu_n or 65536
         cb = cpu_baseline(m, seed)
         out["parity_gate"]["gpu_equals_cpu_oracle_on_sample"] = gpu_equals_oracle(cb, m, seed, local_rank)
@@ -706,7 +718,7 @@ def batch_job(args, world, rank, local_rank, dev, steps: int, warmup: int, dump:
         return None
     row_xors, alg_bytes, sweep_ms, launches = (float(x) for x in agg.tolist())
     s0 = sols[0].stats
-    ceil = hip.stream_ceiling(2 << 30, local_rank)
+    ceil = hip.stream_ceiling(2 << 30, local_rank) if args.full else None
     roofline = None
     if sweep_ms > 0:
         achieved = alg_bytes / (sweep_ms * 1e-3) / 1e9
@@ -719,7 +731,7 @@ def batch_job(args, world, rank, local_rank, dev, steps: int, warmup: int, dump:
                       f"{s0.get('gang_systems', 0)} systems x {64 * g} pivots per launch)",
             "launches": launches, "alg_bytes_per_launch": alg_bytes / max(launches, 1),
             "avg_launch_ms": sweep_ms / max(launches, 1),
-            "persistent_rmw_stream_GBs": ceil["rmw_gbs"], "persistent_read_stream_GBs": ceil["read_gbs"],
+            **({"persistent_rmw_stream_GBs": ceil["rmw_gbs"], "persistent_read_stream_GBs": ceil["read_gbs"]} if ceil else {}),
             # end to end: the job's algorithmic bytes over its wall time (all ranks), against N x 8 TB/s
             "end_to_end_frac": alg_bytes / steps / (elapsed / steps) / 1e9 / (HBM_PEAK_GBS * world),
             "note": "summed over all ranks; two gangs are in flight per GPU (a gang's back-substitution and export overlap "
@@ -754,7 +766,7 @@ def run_batch(args, world, rank, local_rank, dev):
     out = {"metric": "GF(2) row-XORs/s (batch of independent dense NxN solve_one, sharded)"}
     out.update(job)
     out.update({"higher_is_better": True, "vs_baseline": None, "dtype": "u64", "data": "synthetic"})
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         m = args.cpu_n or args.batch_n
         cb = cpu_baseline(m, BATCH_SEED0)
         out["parity_gate"]["gpu_equals_cpu_oracle_on_sample"] = gpu_equals_oracle(cb, m, BATCH_SEED0, local_rank)

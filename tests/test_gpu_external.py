@@ -144,14 +144,14 @@ def test_bench_dump_outputs_are_the_last_step(tmp_path):
 
 
 def test_bench_two_ranks_sharing_the_gpu():
-    """bench.py --gpus 2 exactly as the driver launches it (torch.distributed.run, one process per rank): the default line is
-    the N = 1 workload on every rank (weak scaling: one system per GPU per step) plus the configs[3] job sharded over the
-    ranks as `batch_c4` -- shard bounds, barriers, max-over-ranks timing, the gathers and the JSON line -- with both ranks
+    """bench.py --gpus 2 --full as the driver launches it (torch.distributed.run, one process per rank): the default line is
+    the N = 1 workload on every rank (weak scaling: one system per GPU per step) plus, with --full, the configs[3] job sharded
+    over the ranks as `batch_c4` -- shard bounds, barriers, max-over-ranks timing, the gathers and the JSON line -- with both ranks
     pinned to this box's one GPU and gloo standing in for RCCL (which cannot put two ranks on one device)."""
     env = dict(os.environ, GF2BV_BENCH_DEVICE="0", GF2BV_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", _free_port(), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--size", "8192", "--batch-total", "9", "--batch-n", "4096"]
+           "--full", "--size", "8192", "--batch-total", "9", "--batch-n", "4096"]
     out = run_child(cmd, 300, env=env)
     assert out.ok, out.report()
     lines = [ln for ln in out.out.splitlines() if ln.startswith("{")]
@@ -168,7 +168,7 @@ def test_bench_two_ranks_sharing_the_gpu():
 
 def test_bench_three_ranks_sharing_the_gpu():
     """Multi-GPU readiness without a multi-GPU node (no scaling curve can be taken here: N > 1 is UNMEASURED on hardware):
-    `bench.py --gpus 3` exactly as the driver launches it -- three ranks under torch.distributed.run -- all pinned to this
+    `bench.py --gpus 3 --full` as the driver launches it -- three ranks under torch.distributed.run -- all pinned to this
     box's one GPU with gloo standing in for RCCL, at reduced sizes: the shard bounds of configs[3] at world 3 (24 systems
     -> 8 per rank, what 512 / 8 = 64 per rank exercises), gang sizing for a rank's share, the order of the gathered records,
     barriers and max-over-ranks timing, one JSON line from rank 0.  Three ranks, not eight: the suite keeps at most six
@@ -177,7 +177,7 @@ def test_bench_three_ranks_sharing_the_gpu():
     env = dict(os.environ, GF2BV_BENCH_DEVICE="0", GF2BV_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "3", "--master-addr", "127.0.0.1",
            "--master-port", _free_port(), os.path.join(ROOT, "bench.py"), "--gpus", "3", "--steps", "2", "--warmup", "1",
-           "--size", "4096", "--batch-total", "24", "--batch-n", "2048"]
+           "--full", "--size", "4096", "--batch-total", "24", "--batch-n", "2048"]
     out = run_child(cmd, 600, env=env)
     assert out.ok, out.report()
     lines = [ln for ln in out.out.splitlines() if ln.startswith("{")]
@@ -192,8 +192,8 @@ def test_bench_three_ranks_sharing_the_gpu():
 
 
 def test_bench_default_line_carries_the_scale_anchor():
-    """N = 1: the same line shape (headline + `batch_c4` with its roofline), here at reduced sizes."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--n", "8192", "--batch-total", "6",
+    """N = 1, --full: the same line shape (headline + `batch_c4` with its roofline), here at reduced sizes."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--n", "8192", "--batch-total", "6",
            "--batch-n", "4096", "--no-cpu-baseline"]
     out = run_child(cmd, 300)
     assert out.ok, out.report()
@@ -212,3 +212,16 @@ def test_bench_default_line_carries_the_scale_anchor():
     assert h2d["phases_ms"]["pack_h2d"] > 0 and h2d["ms_per_solve"]["second"] > 0
 
 
+def test_bench_plain_line_is_the_headline_only():
+    """Without --full a run sets up, warms up, times its steps and prints the headline line with its parity gate: none of the
+    legs that take runs of their own (plain leg, stream ceiling, north-star size, batch_c4, example legs, CPU baseline)."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--n", "8192"]
+    out = run_child(cmd, 300)
+    assert out.ok, out.report()
+    line = json.loads([ln for ln in out.out.splitlines() if ln.startswith("{")][-1])
+    assert line["unit"] == "row-XORs/s" and line["higher_is_better"] and line["dtype"] == "u64" and line["steps"] == 2
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["n_gpus"] == 1
+    assert line["parity_gate"]["residual_rows"] == 0 and line["parity_gate"]["all_ranks_ok"]
+    assert line["roofline"]["achieved"] > 0 and "persistent_rmw_stream_GBs" not in line["roofline"]
+    for extra in ("plain_ms_per_step", "target_262144", "batch_c4", "c3_mt19937", "c5_xoshiro", "h2d_inclusive", "cpu_baseline"):
+        assert extra not in line, extra
