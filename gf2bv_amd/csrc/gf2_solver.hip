@@ -2457,7 +2457,10 @@ int factor_matrix(const MatrixInput &in, i64 rows, i64 cols, int mode, int devic
 	S.rows = rows; S.cols = cols; S.mode = mode;
 	S.nrhs = (int)(wt * 64 - cols);   // (solver_alloc: wt words per row)
 	S.stride = in.h_off ? ntiles * TW : in.stride;
-	if (in.d_words && stream) {       // the caller's matrix is read after what its stream has queued
+	// Ordering contract: the matrix is whatever `stream` (the caller's stream, NULL = the null stream) has produced when this
+	// call is made.  S.sA is one of the library's own non-blocking streams, which is not ordered against any other stream by
+	// itself: it waits for an event recorded on `stream` here.
+	if (in.d_words) {
 		hipEvent_t e = nullptr;
 		HIPCHK(pool().event(&e, false));
 		HIPCHK(hipEventRecord(e, stream));
@@ -2581,7 +2584,10 @@ int factor_solve(gf2bv_factor *h, const u64 *rhs, bool on_device, i64 nrhs, i64 
 	if (!on_device) HIPCHK(scratch.alloc((void **)&d, sizeof(u64) * C * rw, h->device));
 	hipEvent_t ev[5];
 	for (hipEvent_t &e : ev) HIPCHK(scratch.event(&e));
-	if (on_device && stream) {        // the caller's right-hand sides are read after what its stream has queued
+	// Ordering contract: the right-hand sides are whatever `stream` (the caller's stream, NULL = the null stream) has produced
+	// when this call is made.  S.sA is one of the library's own non-blocking streams, which is not ordered against any other
+	// stream by itself: it waits for an event recorded on `stream` here.
+	if (on_device) {
 		HIPCHK(hipEventRecord(ev[0], stream));
 		HIPCHK(hipStreamWaitEvent(S.sA, ev[0], 0));
 	}
@@ -2823,7 +2829,10 @@ int factor_append(gf2bv_factor *h, const MatrixInput &in, i64 k, hipStream_t str
 	for (hipEvent_t &e : B.ev) HIPCHK(scratch.event(&e));
 	hipEvent_t g0, g1;
 	HIPCHK(scratch.event(&g0)); HIPCHK(scratch.event(&g1));
-	if (in.d_words && stream) {       // the caller's matrix is read after what its stream has queued
+	// Ordering contract: the appended rows are whatever `stream` (the caller's stream, NULL = the null stream) has produced when
+	// this call is made.  S.sA is one of the library's own non-blocking streams, which is not ordered against any other stream by
+	// itself: it waits for an event recorded on `stream` here.
+	if (in.d_words) {
 		HIPCHK(hipEventRecord(g0, stream));
 		HIPCHK(hipStreamWaitEvent(S.sA, g0, 0));
 	}

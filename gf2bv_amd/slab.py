@@ -20,7 +20,8 @@ import torch.distributed as dist
 
 
 class HipSlabEngine:
-    """The gf2bv_slab_* entry points for one rank.  `aug` = the full row-major system on this rank's GPU."""
+    """The gf2bv_slab_* entry points for one rank.  `aug` = the full row-major system on this rank's GPU, as torch's current
+    stream produces it (the engine waits for that stream before gf2bv_slab_open reads it)."""
 
     def __init__(self, aug_ptr: int, rows: int, cols: int, stride: int, world: int, rank: int, device_index: int):
         from . import hip
@@ -30,6 +31,9 @@ class HipSlabEngine:
         self.ntiles = int(self.L.gf2bv_slab_tiles(cols))
         words = int(self.L.gf2bv_slab_work_words(rows, cols))
         self.work = torch.empty(words, dtype=torch.int64, device=self.dev)          # tile-major working matrix
+        # gf2bv_slab_open takes no stream and converts `aug` on the library's own stream: whatever torch's current stream still
+        # has queued (the producer of `aug`) must be finished first
+        torch.cuda.current_stream(self.dev).synchronize()
         h = ctypes.c_void_p()
         hip._check(self.L.gf2bv_slab_open(aug_ptr, rows, cols, stride, self.work.data_ptr(), words, world, rank,
                                           device_index, ctypes.byref(h)))

@@ -152,13 +152,13 @@ int gf2bv_factor_digits(const uint32_t *digits, const int64_t *digit_off, int bi
                         int mode, int device, gf2bv_factor **out);
 int gf2bv_factor_words(const uint64_t *aug, int64_t rows, int64_t cols, int64_t stride_words, int mode, int device,
                        gf2bv_factor **out);
-/* d_aug as in gf2bv_solve_device; read after everything enqueued on `stream` before the call */
+/* d_aug as in gf2bv_solve_device; read after everything enqueued on `stream` (NULL = the null stream) before the call */
 int gf2bv_factor_device(void *d_aug, int64_t rows, int64_t cols, int64_t stride_words, int mode, int device, void *stream,
                         gf2bv_factor **out);
 /* out[0..nrhs) receives one result handle per right-hand side (free each with gf2bv_result_free) */
 int gf2bv_factor_solve(gf2bv_factor *h, const uint64_t *rhs, int64_t nrhs, int64_t rhs_words, gf2bv_result **out);
-/* d_rhs: device memory, 8-byte aligned, read after everything enqueued on `stream` before the call; time_kernels is accepted
- * for symmetry with gf2bv_solve_rhs_device (the phase times are always measured) */
+/* d_rhs: device memory, 8-byte aligned, read after everything enqueued on `stream` (NULL = the null stream) before the call;
+ * time_kernels is accepted for symmetry with gf2bv_solve_rhs_device (the phase times are always measured) */
 int gf2bv_factor_solve_device(gf2bv_factor *h, const void *d_rhs, int64_t nrhs, int64_t rhs_words, void *stream,
                               int time_kernels, gf2bv_result **out);
 int64_t gf2bv_factor_rank(const gf2bv_factor *h);
@@ -176,7 +176,7 @@ void    gf2bv_factor_free(gf2bv_factor *h);
  * after it had started to change the handle (a device error, or a refused allocation of the mode-1 basis's back-substitution):
  * the handle is then unusable -- rank and rows return -1, every other call GF2BV_ERR_ARG -- and only gf2bv_factor_free remains.
  * Forms as in gf2bv_factor_words / _digits / _device (d_aug 16-byte aligned, even stride_words, read after everything enqueued
- * on `stream` before the call). */
+ * on `stream` (NULL = the null stream) before the call). */
 int gf2bv_factor_append_words(gf2bv_factor *h, const uint64_t *aug, int64_t rows, int64_t stride_words);
 int gf2bv_factor_append_digits(gf2bv_factor *h, const uint32_t *digits, const int64_t *digit_off, int bits_per_digit,
                                int64_t rows);
@@ -260,7 +260,9 @@ void gf2bv_space_combine(const uint64_t *origin, const uint64_t *basis, int64_t 
  *     gf2bv_slab_finish_local(h); gather every rank's tiles of d_work on rank 0; gf2bv_slab_solve(h, &result) there
  * payload: gf2bv_slab_payload_bytes(h) bytes of device memory (block records + rows x 32 bytes of multipliers).
  * Results are bit-identical to gf2bv_solve_device on the same matrix (the elimination is the same; only who applies
- * it to which columns differs).  d_aug: the full row-major system on every rank (left untouched). */
+ * it to which columns differs).  d_aug: the full row-major system on every rank (left untouched); gf2bv_slab_open takes no
+ * stream and reads it on the library's own stream, so d_aug must be complete on the device when the call is made (the caller
+ * synchronizes the stream that produced it first). */
 typedef struct gf2bv_slab gf2bv_slab;
 int64_t gf2bv_slab_work_words(int64_t rows, int64_t cols);
 int64_t gf2bv_slab_tiles(int64_t cols);
