@@ -240,6 +240,9 @@ PyObject *iter_next_slow(SpaceIterObject *self)
 	return words_to_pylong(self->cur, sp->words);
 }
 
+PyObject *QuadGaveUp;      // _internal.QuadSearchGaveUp(message, lin_rank)
+PyObject *space_quad_search(AffineSpaceObject *self, PyObject *const *args, Py_ssize_t nargs);
+
 PyGetSetDef space_getset[] = {
 	{"dimension", (getter)space_dimension, nullptr, "Dimension of the affine space", nullptr},
 	{"origin", (getter)space_origin, nullptr, "Origin of the affine space", nullptr},
@@ -250,6 +253,10 @@ PyGetSetDef space_getset[] = {
 PyMethodDef space_methods[] = {
 	{"get", (PyCFunction)(void (*)(void))space_get, METH_FASTCALL,
 	 "get(n)\n--\n\nGet the n-th element of the affine space, should check 0 <= n < 2**(space.dimension) first."},
+	{"quad_search", (PyCFunction)(void (*)(void))space_quad_search, METH_FASTCALL,
+	 "quad_search(n_lin, max_enum=32, max_solutions=65536, first=False)\n--\n\nThe consistent points of a QuadraticSystem space (product "
+	 "coordinates = products of the n_lin linear bits), in iteration order, searched on the GPU (first=True: the first max_solutions of "
+	 "them, however many there are); not in the reference."},
 	{nullptr, nullptr, 0, nullptr}};
 
 PyType_Slot space_slots[] = {
@@ -1274,6 +1281,65 @@ PyObject *py_sage_helper(PyObject *, PyObject *const *args, Py_ssize_t nargs)
 	}
 }
 
+// AffineSpace.quad_search(n_lin, max_enum=32, max_solutions=65536, first=False): the consistent points of the space (every
+// product coordinate the product of its linear bits), in iteration order, found on the device (gf2bv_quad_search_alloc).
+// More than max_solutions points: ValueError -- or, with first=True, the first max_solutions of them.  Not in the reference.
+PyObject *space_quad_search(AffineSpaceObject *self, PyObject *const *args, Py_ssize_t nargs)
+{
+	if (nargs < 1 || nargs > 4) {
+		PyErr_SetString(PyExc_TypeError, "quad_search(n_lin, max_enum=32, max_solutions=65536, first=False)");
+		return nullptr;
+	}
+	const long long n_lin = PyLong_AsLongLong(args[0]);
+	const long long max_enum = nargs > 1 ? PyLong_AsLongLong(args[1]) : 32;
+	const long long max_sol = nargs > 2 ? PyLong_AsLongLong(args[2]) : 65536;
+	if (PyErr_Occurred()) return nullptr;
+	const int first = nargs > 3 ? PyObject_IsTrue(args[3]) : 0;
+	if (first < 0) return nullptr;
+	if (max_enum < 0 || max_enum > 40) { PyErr_SetString(PyExc_ValueError, "max_enum must be 0..40"); return nullptr; }
+	if (max_sol < 0) { PyErr_SetString(PyExc_ValueError, "max_solutions must be >= 0"); return nullptr; }
+	const int device = self->device >= 0 ? self->device : default_device();
+	int64_t count = 0, lin_rank = 0;
+	uint64_t *pts = nullptr;                  // exactly min(count, max_solutions) points, owned by the library
+	int rc;
+	Py_BEGIN_ALLOW_THREADS
+	rc = gf2bv_quad_search_alloc(self->origin, self->basis, self->dim, self->words, n_lin, (int)max_enum, max_sol, device, &count,
+	                             &lin_rank, &pts);
+	Py_END_ALLOW_THREADS
+	if (rc == GF2BV_ERR_NOMEM && count > max_sol) {     // more than 2^22 points: too many to order
+		gf2bv_quad_free(pts);
+		if (first)
+			PyErr_Format(PyExc_ValueError, "%lld consistent points: too many to order (at most 4194304); add equations to narrow "
+			             "the system", (long long)count);
+		else
+			PyErr_Format(PyExc_ValueError, "%lld consistent points, more than max_solutions (%lld)", (long long)count, max_sol);
+		return nullptr;
+	}
+	if (rc != GF2BV_OK) { gf2bv_quad_free(pts); return raise_rc(rc, "quad_search"); }
+	if (count < 0) {
+		gf2bv_quad_free(pts);
+		PyObject *msg = PyUnicode_FromFormat("the search gave up: the space's projection onto the %lld linear coordinates has rank %lld, "
+		                                     "and neither a search (max_enum %lld) nor relinearisation gets below it",
+		                                     n_lin, (long long)lin_rank, max_enum);
+		if (msg) { PyObject *e = Py_BuildValue("(NL)", msg, (long long)lin_rank); if (e) { PyErr_SetObject(QuadGaveUp, e); Py_DECREF(e); } }
+		return nullptr;
+	}
+	if (count > max_sol && !first) {
+		gf2bv_quad_free(pts);
+		PyErr_Format(PyExc_ValueError, "%lld consistent points, more than max_solutions (%lld)", (long long)count, max_sol);
+		return nullptr;
+	}
+	const int64_t n = std::min<int64_t>(count, max_sol);
+	PyObject *t = PyTuple_New((Py_ssize_t)n);
+	for (int64_t k = 0; t && k < n; k++) {
+		PyObject *v = words_to_pylong(pts + k * self->words, self->words);
+		if (!v) { Py_CLEAR(t); break; }
+		PyTuple_SET_ITEM(t, k, v);
+	}
+	gf2bv_quad_free(pts);
+	return t;
+}
+
 // _space_from_ints(cols, origin, basis): build an AffineSpace from host integers.  Not part of the
 // reference surface; lets the CPU test-suite exercise get()/iteration order without a GPU.
 PyObject *py_space_from_ints(PyObject *, PyObject *const *args, Py_ssize_t nargs)
@@ -1362,7 +1428,11 @@ PyMODINIT_FUNC PyInit__internal(void)
 	Factorization_Type = (PyTypeObject *)PyType_FromSpec(&factor_spec);
 	if (!AffineSpace_Type || !SpaceIterGray_Type || !SpaceIterSlow_Type || !Factorization_Type) { Py_DECREF(m); return nullptr; }
 	Py_INCREF(AffineSpace_Type); Py_INCREF(SpaceIterGray_Type); Py_INCREF(SpaceIterSlow_Type); Py_INCREF(Factorization_Type);
-	if (PyModule_AddObject(m, "AffineSpace", (PyObject *)AffineSpace_Type) < 0 ||
+	QuadGaveUp = PyErr_NewException("_internal.QuadSearchGaveUp", PyExc_RuntimeError, nullptr);
+	if (!QuadGaveUp) { Py_DECREF(m); return nullptr; }
+	Py_INCREF(QuadGaveUp);
+	if (PyModule_AddObject(m, "QuadSearchGaveUp", QuadGaveUp) < 0 ||
+	    PyModule_AddObject(m, "AffineSpace", (PyObject *)AffineSpace_Type) < 0 ||
 	    PyModule_AddObject(m, "Factorization", (PyObject *)Factorization_Type) < 0 ||
 	    PyModule_AddObject(m, "AffineSpaceIterator", (PyObject *)SpaceIterGray_Type) < 0 ||
 	    PyModule_AddObject(m, "AffineSpaceIteratorSlow", (PyObject *)SpaceIterSlow_Type) < 0) {

@@ -4608,3 +4608,150 @@ k_read_stream(const uint4 *__restrict__ a, i64 per_wg, unsigned *__restrict__ si
 	if (acc == 0x9E3779B9u) sink[0] = acc;
 }
 
+
+// ==========================================================================================
+// QUADRATIC SEARCH: the consistent points of a linearised quadratic system's solution space
+// ==========================================================================================
+// (host side and the mathematics: gf2bv_quad_search in gf2_solver.hip)
+//
+// k_quad_forms: one workgroup per form t.  A form is the XOR, over the quad coordinates s = (i, j) of its support
+// (sup_idx[sup_off[t] .. sup_off[t + 1])), of the outer product l_i (x) l_j of two affine forms in r variables plus the affine form q_s in row 0.
+// Affine form: W = ceil((r + 1) / 64) words, bit 0 = constant, bit a = variable a (1..r).  The (r + 1) x (r + 1) product
+// matrix M (entry (a, b) = coefficient of x_a x_b, x_0 = 1) is accumulated in LDS, each thread owning fixed cells, the
+// support bits read wave-uniformly; then it is folded into the canonical form: row 0 = constant (bit 0) and linear
+// coefficients (bit b: M[0][b] ^ M[b][0] ^ M[b][b], as x_b^2 = x_b), row a >= 1 = U[a][b] = M[a][b] ^ M[b][a] for b > a.
+// LDS: (r + 1) x W words (dynamic).
+__global__ void __launch_bounds__(256)
+k_quad_forms(const u64 *__restrict__ lin, const u64 *__restrict__ qaff, const int *__restrict__ pair_i,
+             const int *__restrict__ pair_j, const i64 *__restrict__ sup_off, const int *__restrict__ sup_idx, int r, int W,
+             u64 *__restrict__ out)
+{
+	extern __shared__ u64 M[];
+	const i64 t = blockIdx.x;
+	const int cells = (r + 1) * W;
+	for (int e = threadIdx.x; e < cells; e += blockDim.x) M[e] = 0;
+	for (i64 k = sup_off[t]; k < sup_off[t + 1]; k++) {              // (the same index in every lane: scalar loads)
+		const i64 s = sup_idx[k];
+		const u64 *li = lin + (i64)pair_i[s] * W, *lj = lin + (i64)pair_j[s] * W, *qs = qaff + s * W;
+		for (int e = threadIdx.x; e < cells; e += blockDim.x) {
+			const int a = e / W, w = e - a * W;
+			u64 v = ((li[a >> 6] >> (a & 63)) & 1) ? lj[w] : 0;
+			if (a == 0) v ^= qs[w];
+			M[e] ^= v;
+		}
+	}
+	__syncthreads();
+	u64 *o = out + t * (i64)cells;
+	for (int e = threadIdx.x; e < cells; e += blockDim.x) {
+		const int a = e / W, w = e - a * W;
+		u64 tr = 0, diag = 0;                         // bit b of word w: M[b][a] (transpose), M[b][b]
+		for (int k = 0; k < 64; k++) {
+			const int b = w * 64 + k;
+			if (b > r) break;
+			tr |= ((M[b * W + (a >> 6)] >> (a & 63)) & 1) << k;
+			if (a == 0) diag |= ((M[b * W + (b >> 6)] >> (b & 63)) & 1) << k;
+		}
+		u64 v;
+		if (a == 0) {
+			v = M[e] ^ ((tr ^ diag) & (w == 0 ? ~1ull : ~0ull));          // bit 0 = M[0][0] alone
+		} else {
+			const int lo = a + 1 - w * 64;            // keep bits b > a
+			const u64 keep = lo <= 0 ? ~0ull : (lo >= 64 ? 0ull : (~0ull << lo));
+			v = (M[e] ^ tr) & keep;
+		}
+		o[e] = v;
+	}
+}
+
+// k_quad_search: every common zero of 64 quadratic forms in R <= 64 variables, bit-sliced (bit f of a word = form f).
+// tab: [K | Lw[0..R) | Sw[R x R]]: constants, linear coefficients, and the symmetric pair coefficients (Sw[j][k] = Sw[k][j],
+// zero diagonal).  Lane g fixes the high variables L..R-1 to the bits of g and walks the low L variables in Gray order
+// (Bouillaguet et al., CHES 2010): at step i the flipped variable k1 = ctz(i) and the one flipped since k1 was last flipped,
+// k2 = ctz(i & (i - 1)), are the same in every lane, so the second derivative Sw[k1][k2] is a scalar load and a step costs
+// two XORs -- d1[k1] ^= Sw[k1][k2], value ^= d1[k1] -- plus the zero test.  The first derivatives d1 live in LDS, one
+// column per thread (d1[k * blockDim + tid]); every lane starts from its own point (no lane depends on another).
+// A lane at a zero appends its point to `list` (atomic counter `count`; the points beyond `cap` are counted, not stored).
+// With E != nullptr (the fallback when the 64 forms leave too many candidates to store) the lane first tests the point
+// against all m forms of E (layout of k_quad_check) and appends only the common zeros of every form.
+__device__ __forceinline__ bool quad_all_vanish(const u64 *__restrict__ E, i64 m, int R, u64 y)
+{
+	for (i64 f = 0; f < m; f++) {
+		const u64 *e = E + f * (i64)(R + 2);
+		u64 acc = e[0] ^ (u64)__popcll(e[1] & y);
+		for (u64 bits = y; bits; bits &= bits - 1) acc ^= (u64)__popcll(e[2 + ctz64(bits)] & y);
+		if (acc & 1) return false;
+	}
+	return true;
+}
+__global__ void __launch_bounds__(256)
+k_quad_search(const u64 *__restrict__ tab, int R, int L, u64 nlanes, u64 *__restrict__ list, u64 cap,
+              unsigned long long *__restrict__ count, const u64 *__restrict__ E, i64 m)
+{
+	extern __shared__ u64 d1s[];
+	const u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+	if (g >= nlanes) return;                          // (no barrier below)
+	const u64 *Lw = tab + 1, *Sw = tab + 1 + R;
+	const int H = R - L, bd = blockDim.x, tid = threadIdx.x;
+	u64 v = tab[0];
+	for (int j = 0; j < H; j++) {
+		if (!((g >> j) & 1)) continue;
+		v ^= Lw[L + j];
+		for (int j2 = j + 1; j2 < H; j2++)
+			if ((g >> j2) & 1) v ^= Sw[(i64)(L + j) * R + L + j2];
+	}
+	for (int k = 0; k < L; k++) {
+		u64 lam = Lw[k];
+		for (int j = 0; j < H; j++)
+			if ((g >> j) & 1) lam ^= Sw[(i64)(L + j) * R + k];
+		d1s[k * bd + tid] = lam ^ (k ? Sw[(i64)(k - 1) * R + k] : 0);      // the derivative at e_{k-1}, where k is first flipped
+	}
+	const u64 base = L < 64 ? g << L : 0;
+	if (v == 0 && (!E || quad_all_vanish(E, m, R, base))) {
+		const unsigned long long at = atomicAdd(count, 1ull);
+		if (at < cap) list[at] = base;
+	}
+	const u64 steps = 1ull << L;
+	for (u64 i = 1; i < steps; i++) {
+		const int k1 = ctz64(i);
+		const u64 rest = i & (i - 1);
+		u64 d = d1s[k1 * bd + tid];
+		if (rest) {
+			d ^= Sw[(i64)k1 * R + ctz64(rest)];
+			d1s[k1 * bd + tid] = d;
+		}
+		v ^= d;
+		if (v == 0 && (!E || quad_all_vanish(E, m, R, base | (i ^ (i >> 1))))) {
+			const unsigned long long at = atomicAdd(count, 1ull);
+			if (at < cap) list[at] = base | (i ^ (i >> 1));
+		}
+	}
+}
+
+// k_quad_check: the second pass.  One wavefront per candidate point y (R <= 64 variables), lanes over the forms:
+// E holds every form as R + 2 words [constant, linear mask, U row 0 .. U row R-1] (row j: bits k > j), and
+// Q(y) = c ^ parity(lin & y) ^ XOR_{j in y} parity(row_j & y).  A candidate at which every form vanishes is appended to out.
+__global__ void __launch_bounds__(256)
+k_quad_check(const u64 *__restrict__ E, i64 m, int R, const u64 *__restrict__ cand, u64 ncand, u64 *__restrict__ out,
+             u64 cap, unsigned long long *__restrict__ count)
+{
+	const int lane = threadIdx.x & 63;
+	const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((u64)gridDim.x * blockDim.x) >> 6;
+	for (u64 c = wave; c < ncand; c += nwaves) {
+		const u64 y = cand[c];
+		u64 bad = 0;
+		for (i64 f = lane; f < m; f += 64) {
+			const u64 *e = E + f * (i64)(R + 2);
+			u64 acc = e[0] ^ (u64)__popcll(e[1] & y);
+			u64 bits = y;
+			while (bits) {
+				const int j = ctz64(bits); bits &= bits - 1;
+				acc ^= (u64)__popcll(e[2 + j] & y);
+			}
+			bad |= acc & 1;
+		}
+		if (!wave_or(bad) && lane == 0) {
+			const unsigned long long at = atomicAdd(count, 1ull);
+			if (at < cap) out[at] = y;
+		}
+	}
+}

@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <new>
@@ -4041,5 +4042,637 @@ int gf2bv_probe_read(unsigned long long *wg, unsigned long long *un)
 	return GF2BV_OK;
 }
 #endif
+
+}  // extern "C"
+
+// ---- quadratic search: the consistent points of a linearised quadratic system's solution space --------------------------
+//   A space x(c) = o ^ B c over n linear coordinates followed by the n(n-1)/2 product coordinates
+// (pair (i, j), j < i, at n + i(i-1)/2 + j).  Step 1: column operations T split B into A (r vectors, independent linear
+// parts) and K (d - r vectors, zero linear parts, RREF over the product coordinates, pivots P).  Step 2: a choice c_a of the
+// A coefficients extends to a consistent point iff, at every product coordinate t outside P, v_t = XOR_{p in P} v_p K_p[t]
+// where v_s = l_i l_j ^ q_s -- one quadratic form in r variables per such t (k_quad_forms); affine forms are eliminated on
+// the host, one variable each.  Step 3: r_eff <= max_enum: k_quad_search + k_quad_check; above: relinearise (the forms are
+// the equations of a QuadraticSystem of r_eff unknowns, solved by this library) and repeat on that space while r_eff falls.
+namespace {
+
+constexpr i64 kQuadMaxRank = 256;            // larger projection ranks are not reduced (the forms would hold (r + 1)^2 bits each)
+constexpr i64 kQuadMaxPoints = 1ll << 22;    // consistent points collected (and ordered) at most
+constexpr i64 kQuadMaxCand = 1ll << 22;      // candidates of the first search pass kept for the second (more: one fused pass)
+constexpr int kQuadMaxEnum = 40;
+constexpr int kQuadMaxDepth = 8;
+
+inline bool qbit(const u64 *v, i64 i) { return (v[i >> 6] >> (i & 63)) & 1; }
+inline void qflip(u64 *v, i64 i) { v[i >> 6] ^= 1ull << (i & 63); }
+inline void qxor(u64 *d, const u64 *s, i64 n) { for (i64 k = 0; k < n; k++) d[k] ^= s[k]; }
+inline bool qzero(const u64 *v, i64 n) { for (i64 k = 0; k < n; k++) if (v[k]) return false; return true; }
+// d ^= s restricted to the bits above `e` (words of W)
+inline void qxor_above(u64 *d, const u64 *s, i64 e, i64 W)
+{
+	const i64 w0 = (e + 1) >> 6;
+	if (w0 >= W) return;
+	d[w0] ^= s[w0] & (~0ull << ((e + 1) & 63));
+	for (i64 w = w0 + 1; w < W; w++) d[w] ^= s[w];
+}
+
+struct QuadTimes { double reduce = 0, forms = 0, affine = 0, search = 0, relin = 0, total = 0; i64 levels = 0, candidates = 0; };
+thread_local QuadTimes g_quad_times;
+
+inline double ms_since(std::chrono::steady_clock::time_point t0)
+{
+	return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+struct QuadPlan {
+	i64 n = 0, S = 0, N = 0, words = 0, d = 0, dw = 1, r = 0, W = 1;
+	std::vector<u64> origin, V, T;       // V: d x words (A rows 0..r-1, then K rows); T: d x dw (row j = original coefficients of V_j)
+	std::vector<i64> kpiv;               // product coordinate (0..S-1) of the pivot of K row k
+	i64 m0 = 0;                          // forms before the affine elimination: one per product coordinate outside P
+	std::vector<u64> lin, qaff;          // n x W, S x W (inputs of k_quad_forms, with the pair decode and the supports)
+	std::vector<int> pair_i, pair_j, sup_idx;
+	std::vector<i64> sup_off;
+	std::vector<u64> M;                  // m0 x (r + 1) x W canonical forms over matrix variables 1..r
+	bool inconsistent = false;
+	std::vector<int> sub_var;            // affine elimination: variable, and its value as an affine form (W words, bit 0 = 1)
+	std::vector<u64> sub_sigma;
+	std::vector<int> alive;              // matrix variable of effective variable v
+	i64 reff = 0, fw = 1, m = 0;
+	std::vector<u64> forms;              // m x fw, equation-int layout over reff unknowns
+};
+
+// step 1 and the inputs of step 2
+void quad_reduce(QuadPlan &P, const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n)
+{
+	P.n = n; P.S = n * (n - 1) / 2; P.N = n + P.S; P.words = words; P.d = d; P.dw = std::max<i64>(1, (d + 63) / 64);
+	P.origin.assign(origin, origin + words);
+	P.V.assign(basis, basis + d * words);
+	P.T.assign((size_t)(d * P.dw), 0);
+	for (i64 j = 0; j < d; j++) qflip(&P.T[j * P.dw], j);
+	auto row = [&](i64 i) { return &P.V[i * words]; };
+	auto swap_rows = [&](i64 a, i64 b) {
+		std::swap_ranges(row(a), row(a) + words, row(b));
+		std::swap_ranges(&P.T[a * P.dw], &P.T[a * P.dw] + P.dw, &P.T[b * P.dw]);
+	};
+	auto pivot_on = [&](i64 c, i64 at, i64 lo) -> bool {       // pivot of column c at row `at` (rows >= lo searched / cleared)
+		i64 p = -1;
+		for (i64 i = at; i < d; i++) if (qbit(row(i), c)) { p = i; break; }
+		if (p < 0) return false;
+		if (p != at) swap_rows(p, at);
+		const i64 w0 = c >> 6;              // (the pivot row is zero left of c)
+		for (i64 i = lo; i < d; i++)
+			if (i != at && qbit(row(i), c)) { qxor(row(i) + w0, row(at) + w0, words - w0); qxor(&P.T[i * P.dw], &P.T[at * P.dw], P.dw); }
+		return true;
+	};
+	i64 rk = 0;
+	for (i64 c = 0; c < n && rk < d; c++) if (pivot_on(c, rk, 0)) rk++;
+	P.r = rk;
+	for (i64 c = n; c < P.N && rk < d; c++) if (pivot_on(c, rk, P.r)) { P.kpiv.push_back(c - n); rk++; }
+}
+
+void quad_inputs(QuadPlan &P)
+{
+	const i64 n = P.n, S = P.S, r = P.r, words = P.words;
+	P.W = (r + 64) / 64;
+	const i64 W = P.W;
+	P.lin.assign((size_t)(std::max<i64>(n, 1) * W), 0);
+	P.qaff.assign((size_t)(std::max<i64>(S, 1) * W), 0);
+	for (i64 i = 0; i < P.N; i++) {
+		u64 *f = i < n ? &P.lin[i * W] : &P.qaff[(i - n) * W];
+		if (qbit(P.origin.data(), i)) f[0] |= 1;
+		for (i64 a = 0; a < r; a++) if (qbit(&P.V[a * words], i)) qflip(f, a + 1);
+	}
+	P.pair_i.resize((size_t)std::max<i64>(S, 1)); P.pair_j.resize((size_t)std::max<i64>(S, 1));
+	for (i64 i = 1, s = 0; i < n; i++) for (i64 j = 0; j < i; j++, s++) { P.pair_i[s] = (int)i; P.pair_j[s] = (int)j; }
+	// forms: one per product coordinate t outside P, numbered in coordinate order; support of form t = {t} and the pivots p
+	// of the K rows that have a bit at t (a list per form: sup_idx[sup_off[t] .. sup_off[t + 1]))
+	std::vector<i64> form_of((size_t)std::max<i64>(S, 1), 0);
+	for (i64 p : P.kpiv) form_of[p] = -1;
+	P.m0 = 0;
+	for (i64 s = 0; s < S; s++) if (form_of[s] == 0) form_of[s] = P.m0++;
+	std::vector<std::pair<i64, int>> hits;          // (form, pivot coordinate) for every K bit outside P
+	for (size_t k = 0; k < P.kpiv.size(); k++) {
+		const u64 *kv = &P.V[(r + (i64)k) * words];
+		for (i64 w = n >> 6; w < words; w++) {
+			for (u64 bits = kv[w]; bits; bits &= bits - 1) {
+				const i64 c = w * 64 + __builtin_ctzll(bits);
+				if (c < n || c >= P.N) continue;
+				const i64 t = form_of[c - n];
+				if (t >= 0) hits.push_back({t, (int)P.kpiv[k]});
+			}
+		}
+	}
+	P.sup_off.assign((size_t)(P.m0 + 1), 0);
+	for (i64 t = 0; t < P.m0; t++) P.sup_off[t + 1] = 1;
+	for (auto &h : hits) P.sup_off[h.first + 1]++;
+	for (i64 t = 0; t < P.m0; t++) P.sup_off[t + 1] += P.sup_off[t];
+	P.sup_idx.assign((size_t)std::max<i64>(1, P.sup_off[P.m0]), 0);
+	std::vector<i64> at(P.sup_off.begin(), P.sup_off.end() - 1);
+	for (i64 s = 0; s < S; s++) if (form_of[s] >= 0) P.sup_idx[at[form_of[s]]++] = (int)s;
+	for (auto &h : hits) P.sup_idx[at[h.first]++] = h.second;
+}
+
+// the host twin of k_quad_forms (gf2bv_quad_plan never touches a device)
+void quad_forms_host(QuadPlan &P)
+{
+	const i64 r = P.r, W = P.W, cells = (r + 1) * W;
+	P.M.assign((size_t)(std::max<i64>(P.m0, 1) * cells), 0);
+	std::vector<u64> acc((size_t)cells);
+	for (i64 t = 0; t < P.m0; t++) {
+		std::fill(acc.begin(), acc.end(), 0);
+		for (i64 k = P.sup_off[t]; k < P.sup_off[t + 1]; k++) {
+			const i64 s = P.sup_idx[k];
+			const u64 *li = &P.lin[(i64)P.pair_i[s] * W], *lj = &P.lin[(i64)P.pair_j[s] * W];
+			for (i64 a = 0; a <= r; a++) if (qbit(li, a)) qxor(&acc[a * W], lj, W);
+			qxor(&acc[0], &P.qaff[s * W], W);
+		}
+		u64 *o = &P.M[t * cells];
+		for (i64 a = 0; a <= r; a++)
+			for (i64 b = a; b <= r; b++) {
+				if (a == 0) {
+					const bool v = b == 0 ? qbit(&acc[0], 0) : (qbit(&acc[0], b) ^ qbit(&acc[b * W], 0) ^ qbit(&acc[b * W], b));
+					if (v) qflip(&o[0], b);
+				} else if (b > a && (qbit(&acc[a * W], b) ^ qbit(&acc[b * W], a))) {
+					qflip(&o[a * W], b);
+				}
+			}
+	}
+}
+
+// the affine elimination of step 2 and the final forms (equation-int layout over the r_eff variables left)
+void quad_affine(QuadPlan &P)
+{
+	const i64 r = P.r, W = P.W, cells = (r + 1) * W;
+	std::vector<char> live((size_t)std::max<i64>(P.m0, 1), 1), quad((size_t)std::max<i64>(P.m0, 1), 0);
+	auto F = [&](i64 f) { return &P.M[f * cells]; };
+	auto classify = [&](i64 f) -> bool {           // false: the constant 1 (no point at all)
+		quad[f] = !qzero(F(f) + W, r * W);
+		if (quad[f]) return true;
+		const u64 *r0 = F(f);
+		bool lin = (r0[0] & ~1ull) != 0;
+		for (i64 w = 1; w < W && !lin; w++) lin = r0[w] != 0;
+		if (!lin) { live[f] = 0; return (r0[0] & 1) == 0; }
+		return true;
+	};
+	for (i64 f = 0; f < P.m0; f++) if (!classify(f)) { P.inconsistent = true; break; }
+	std::vector<char> var_alive((size_t)(r + 1), 1);
+	std::vector<u64> u((size_t)W), sig((size_t)W), su((size_t)W);
+	for (i64 f = 0; !P.inconsistent && f < P.m0; f++) {
+		if (!live[f] || quad[f]) continue;
+		u64 *r0 = F(f);
+		i64 a = -1;
+		for (i64 w = W - 1; w >= 0 && a < 0; w--) if (r0[w] & (w ? ~0ull : ~1ull)) a = w * 64 + 63 - __builtin_clzll(r0[w] & (w ? ~0ull : ~1ull));
+		std::copy(r0, r0 + W, sig.begin());
+		qflip(sig.data(), a);                      // c_a = sigma(c): constant bit 0, variables above
+		live[f] = 0;
+		var_alive[a] = 0;
+		P.sub_var.push_back((int)a);
+		P.sub_sigma.insert(P.sub_sigma.end(), sig.begin(), sig.end());
+		const bool s0 = sig[0] & 1;
+		for (i64 g = 0; g < P.m0; g++) {
+			if (!live[g]) continue;
+			u64 *G = F(g);
+			std::fill(u.begin(), u.end(), 0);
+			bool any_u = false;
+			if (quad[g]) {
+				for (i64 w = 0; w < W; w++) { u[w] = G[a * W + w]; G[a * W + w] = 0; }
+				for (i64 b = 1; b < a; b++) if (qbit(&G[b * W], a)) { qflip(&G[b * W], a); qflip(u.data(), b); }
+				any_u = !qzero(u.data(), W);
+			}
+			const bool la = qbit(G, a);
+			if (la) { qflip(G, a); qxor(G, sig.data(), W); }
+			if (any_u) {
+				if (s0) qxor(G, u.data(), W);
+				for (i64 w = 0; w < W; w++) { su[w] = sig[w] & u[w]; G[w] ^= su[w]; }
+				for (i64 e = 1; e <= r; e++) {
+					if (qbit(sig.data(), e)) qxor_above(&G[e * W], u.data(), e, W);
+					if (qbit(u.data(), e)) qxor_above(&G[e * W], sig.data(), e, W);
+				}
+			}
+			if (!la && !any_u) continue;
+			if (!classify(g)) { P.inconsistent = true; break; }
+		}
+		f = -1;                                    // rescan: a substitution may have made earlier forms affine
+	}
+	if (P.inconsistent) {
+		P.reff = 0; P.fw = 1; P.m = 1; P.forms.assign(1, 1);
+		return;
+	}
+	P.alive.clear();
+	for (i64 a = 1; a <= r; a++) if (var_alive[a]) P.alive.push_back((int)a);
+	const i64 re = (i64)P.alive.size();
+	P.reff = re;
+	P.fw = (1 + re + re * (re - 1) / 2 + 63) / 64;
+	P.m = 0;
+	for (i64 f = 0; f < P.m0; f++) if (live[f]) P.m++;
+	P.forms.assign((size_t)(std::max<i64>(P.m, 1) * P.fw), 0);
+	i64 k = 0;
+	for (i64 f = 0; f < P.m0; f++) {
+		if (!live[f]) continue;
+		const u64 *G = F(f);
+		u64 *o = &P.forms[k++ * P.fw];
+		if (G[0] & 1) o[0] |= 1;
+		for (i64 v = 0; v < re; v++) {
+			if (qbit(G, P.alive[v])) qflip(o, 1 + v);
+			const u64 *row = &G[(i64)P.alive[v] * W];
+			for (i64 v2 = v + 1; v2 < re; v2++)
+				if (qbit(row, P.alive[v2])) qflip(o, 1 + re + v2 * (v2 - 1) / 2 + v);
+		}
+	}
+}
+
+// the point of the space that effective assignment y (reff bits) extends to; c_orig: its coefficients (dw words)
+bool quad_point(const QuadPlan &P, const u64 *y, u64 *x, u64 *c_orig)
+{
+	const i64 r = P.r, W = P.W, words = P.words;
+	std::vector<u64> c((size_t)W, 0);
+	c[0] = 1;
+	for (i64 v = 0; v < P.reff; v++) if (qbit(y, v)) qflip(c.data(), P.alive[v]);
+	for (i64 k = (i64)P.sub_var.size() - 1; k >= 0; k--) {
+		const u64 *sg = &P.sub_sigma[k * W];
+		u64 par = 0;
+		for (i64 w = 0; w < W; w++) par ^= sg[w] & c[w];
+		if (__builtin_popcountll(par) & 1) qflip(c.data(), P.sub_var[k]);
+	}
+	std::copy(P.origin.begin(), P.origin.end(), x);
+	std::fill(c_orig, c_orig + P.dw, 0);
+	for (i64 a = 0; a < r; a++)
+		if (qbit(c.data(), a + 1)) { qxor(x, &P.V[a * words], words); qxor(c_orig, &P.T[a * P.dw], P.dw); }
+	for (size_t k = 0; k < P.kpiv.size(); k++) {
+		const i64 s = P.kpiv[k];
+		const bool v = (qbit(x, P.pair_i[s]) & qbit(x, P.pair_j[s])) ^ qbit(x, P.n + s);
+		if (v) { qxor(x, &P.V[(r + (i64)k) * words], words); qxor(c_orig, &P.T[(r + (i64)k) * P.dw], P.dw); }
+	}
+	for (i64 s = 0; s < P.S; s++)                  // every product coordinate must now be the product of its linear bits
+		if ((qbit(x, P.pair_i[s]) & qbit(x, P.pair_j[s])) != qbit(x, P.n + s)) return false;
+	return true;
+}
+
+struct QDev {                                      // a pool buffer, released at scope end
+	void *p = nullptr;
+	~QDev() { pool().release(p); }
+	hipError_t get(size_t bytes, int device) { pool().release(p); p = nullptr; return pool().alloc(&p, bytes, device); }
+	template <class X> X *as() const { return static_cast<X *>(p); }
+};
+
+int quad_forms_device(QuadPlan &P, int device, hipStream_t st)
+{
+	const i64 r = P.r, W = P.W, cells = (r + 1) * W;
+	P.M.assign((size_t)(std::max<i64>(P.m0, 1) * cells), 0);
+	if (P.m0 == 0) return GF2BV_OK;
+	QDev dl, dq, dpi, dpj, dso, dsi, dout;
+	HIPCHK(dl.get(P.lin.size() * 8, device)); HIPCHK(dq.get(P.qaff.size() * 8, device));
+	HIPCHK(dpi.get(P.pair_i.size() * 4, device)); HIPCHK(dpj.get(P.pair_j.size() * 4, device));
+	HIPCHK(dso.get(P.sup_off.size() * 8, device)); HIPCHK(dsi.get(P.sup_idx.size() * 4, device));
+	HIPCHK(dout.get(P.M.size() * 8, device));
+	HIPCHK(hipMemcpyAsync(dl.p, P.lin.data(), P.lin.size() * 8, hipMemcpyHostToDevice, st));
+	HIPCHK(hipMemcpyAsync(dq.p, P.qaff.data(), P.qaff.size() * 8, hipMemcpyHostToDevice, st));
+	HIPCHK(hipMemcpyAsync(dpi.p, P.pair_i.data(), P.pair_i.size() * 4, hipMemcpyHostToDevice, st));
+	HIPCHK(hipMemcpyAsync(dpj.p, P.pair_j.data(), P.pair_j.size() * 4, hipMemcpyHostToDevice, st));
+	HIPCHK(hipMemcpyAsync(dso.p, P.sup_off.data(), P.sup_off.size() * 8, hipMemcpyHostToDevice, st));
+	HIPCHK(hipMemcpyAsync(dsi.p, P.sup_idx.data(), P.sup_idx.size() * 4, hipMemcpyHostToDevice, st));
+	k_quad_forms<<<dim3((unsigned)P.m0), dim3(256), (size_t)cells * 8, st>>>(dl.as<u64>(), dq.as<u64>(), dpi.as<int>(), dpj.as<int>(),
+	                                                                         dso.as<i64>(), dsi.as<int>(), (int)r, (int)W, dout.as<u64>());
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(P.M.data(), dout.p, P.M.size() * 8, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipStreamSynchronize(st));
+	return GF2BV_OK;
+}
+
+// every common zero of m forms (equation-int layout, fw words) in R <= kQuadMaxEnum variables; `total` counts them all,
+// `ys` holds them when there are at most kQuadMaxPoints (in no particular order)
+int quad_search_device(const u64 *forms, i64 m, i64 fw, int R, int device, hipStream_t st, std::vector<u64> &ys, u64 *total)
+{
+	ys.clear();
+	if (m == 0) {                                  // no form: the whole cube
+		*total = 1ull << R;
+		if ((i64)*total <= kQuadMaxPoints) for (u64 y = 0; y < *total; y++) ys.push_back(y);
+		return GF2BV_OK;
+	}
+	auto coef = [&](i64 f, i64 bit) { return qbit(forms + f * fw, bit); };
+	auto pair_bit = [&](i64 j, i64 k) { return 1 + R + (k > j ? k * (k - 1) / 2 + j : j * (j - 1) / 2 + k); };
+	// the 64 forms of the first pass: the first that are linearly independent (a form in the span of those already chosen
+	// removes no candidate, and leading forms of low rank are common -- pair coordinates over few variables come first)
+	std::vector<i64> chosen;
+	{
+		std::vector<u64> red;                      // reduced chosen forms, each with its pivot bit
+		std::vector<i64> piv;
+		std::vector<u64> v((size_t)fw);
+		for (i64 f = 0; f < m && (i64)chosen.size() < 64; f++) {
+			std::copy(forms + f * fw, forms + (f + 1) * fw, v.begin());
+			for (size_t k = 0; k < piv.size(); k++) if (qbit(v.data(), piv[k])) qxor(v.data(), &red[k * fw], fw);
+			i64 p = -1;
+			for (i64 w = 0; w < fw && p < 0; w++) if (v[w]) p = w * 64 + __builtin_ctzll(v[w]);
+			if (p < 0) continue;
+			for (size_t k = 0; k < piv.size(); k++) if (qbit(&red[k * fw], p)) qxor(&red[k * fw], v.data(), fw);
+			red.insert(red.end(), v.begin(), v.end());
+			piv.push_back(p);
+			chosen.push_back(f);
+		}
+	}
+	std::vector<u64> tab((size_t)(1 + R + R * R), 0), E((size_t)(m * (R + 2)), 0);
+	for (i64 f = 0; f < m; f++) {                  // every form in k_quad_check's layout
+		u64 *e = &E[f * (R + 2)];
+		if (coef(f, 0)) e[0] = 1;
+		for (i64 k = 0; k < R; k++) {
+			if (coef(f, 1 + k)) e[1] |= 1ull << k;
+			for (i64 j = 0; j < k; j++) if (coef(f, pair_bit(j, k))) e[2 + j] |= 1ull << k;
+		}
+	}
+	for (size_t c = 0; c < chosen.size(); c++) {   // the chosen ones bit-sliced: bit c of every word
+		const i64 f = chosen[c];
+		const u64 fb = 1ull << c;
+		if (coef(f, 0)) tab[0] |= fb;
+		for (i64 k = 0; k < R; k++) {
+			if (coef(f, 1 + k)) tab[1 + k] |= fb;
+			for (i64 j = 0; j < k; j++)
+				if (coef(f, pair_bit(j, k))) { tab[1 + R + j * R + k] |= fb; tab[1 + R + k * R + j] |= fb; }
+		}
+	}
+	const int H = std::max(0, std::min(R - 10, 18)), L = R - H;
+	const u64 nlanes = 1ull << H;
+	const int bd = (int)std::min<u64>(256, (nlanes + 63) / 64 * 64);
+	const dim3 grid((unsigned)((nlanes + bd - 1) / bd));
+	const size_t lds = (size_t)bd * L * 8;
+	const u64 ocap = (u64)kQuadMaxPoints;
+	QDev dtab, dE, dcand, dcnt, dout;
+	HIPCHK(dtab.get(tab.size() * 8, device)); HIPCHK(dE.get(E.size() * 8, device)); HIPCHK(dcnt.get(16, device));
+	HIPCHK(hipMemcpyAsync(dtab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, st));
+	HIPCHK(hipMemcpyAsync(dE.p, E.data(), E.size() * 8, hipMemcpyHostToDevice, st));
+	HIPCHK(hipMemsetAsync(dcnt.p, 0, 16, st));
+	const u64 cap = (u64)kQuadMaxCand;
+	HIPCHK(dcand.get(cap * 8, device));
+	HIPCHK(dout.get(ocap * 8, device));
+	k_quad_search<<<grid, dim3(bd), lds, st>>>(dtab.as<u64>(), R, L, nlanes, dcand.as<u64>(), cap, dcnt.as<unsigned long long>(), nullptr, 0);
+	HIPCHK(hipGetLastError());
+	u64 cnt[2] = {0, 0};
+	HIPCHK(hipMemcpyAsync(cnt, dcnt.p, 8, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipStreamSynchronize(st));
+	g_quad_times.candidates += (i64)cnt[0];
+	if (cnt[0] > cap) {
+		// more candidates than can be kept: search again, each lane testing its candidates against every form itself
+		k_quad_search<<<grid, dim3(bd), lds, st>>>(dtab.as<u64>(), R, L, nlanes, dout.as<u64>(), ocap, dcnt.as<unsigned long long>() + 1,
+		                                           dE.as<u64>(), m);
+		HIPCHK(hipGetLastError());
+	} else if (cnt[0]) {
+		const u64 waves = std::min<u64>(cnt[0], 8192);
+		k_quad_check<<<dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st>>>(dE.as<u64>(), m, R, dcand.as<u64>(), cnt[0], dout.as<u64>(),
+		                                                                     ocap, dcnt.as<unsigned long long>() + 1);
+		HIPCHK(hipGetLastError());
+	}
+	HIPCHK(hipMemcpyAsync(cnt + 1, dcnt.as<u64>() + 1, 8, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipStreamSynchronize(st));
+	*total = cnt[1];
+	if ((i64)cnt[1] <= kQuadMaxPoints) {
+		ys.resize((size_t)cnt[1]);
+		if (cnt[1]) HIPCHK(hipMemcpyAsync(ys.data(), dout.p, cnt[1] * 8, hipMemcpyDeviceToHost, st));
+		HIPCHK(hipStreamSynchronize(st));
+	}
+	return GF2BV_OK;
+}
+
+int quad_plan_build(QuadPlan &P, const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n, int device, hipStream_t st)
+{
+	auto t0 = std::chrono::steady_clock::now();
+	quad_reduce(P, origin, basis, d, words, n);
+	if (P.r > kQuadMaxRank) { P.reff = -1; g_quad_times.reduce += ms_since(t0); return GF2BV_OK; }
+	quad_inputs(P);
+	g_quad_times.reduce += ms_since(t0);
+	t0 = std::chrono::steady_clock::now();
+	if (device < 0) quad_forms_host(P);
+	else { int rc = quad_forms_device(P, device, st); if (rc) return rc; }
+	g_quad_times.forms += ms_since(t0);
+	t0 = std::chrono::steady_clock::now();
+	quad_affine(P);
+	g_quad_times.affine += ms_since(t0);
+	return GF2BV_OK;
+}
+
+// every consistent point of one space (words each, in no particular order) and its coefficients in the space's basis
+// (coef: dw = ceil(d / 64) words each).  *total: their number (exact, also when
+// `pts` could not hold them: more than kQuadMaxPoints); *gave_up: the search found no way down (step 3).
+int quad_collect(const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n, int max_enum, int device, hipStream_t st,
+                 i64 parent_reff, int depth, std::vector<u64> &pts, std::vector<u64> &coef, u64 *total, i64 *lin_rank,
+                 bool *gave_up)
+{
+	pts.clear(); coef.clear(); *total = 0;
+	g_quad_times.levels = std::max<i64>(g_quad_times.levels, depth + 1);
+	QuadPlan P;
+	int rc = quad_plan_build(P, origin, basis, d, words, n, device, st);
+	if (rc) return rc;
+	if (depth == 0) *lin_rank = P.r;
+	if (P.reff < 0) { *gave_up = true; return GF2BV_OK; }
+	if (P.inconsistent) return GF2BV_OK;
+	std::vector<u64> ys;                           // effective assignments, yw words each
+	const i64 yw = std::max<i64>(1, (P.reff + 63) / 64);
+	if (P.reff <= max_enum) {
+		auto t0 = std::chrono::steady_clock::now();
+		rc = quad_search_device(P.forms.data(), P.m, P.fw, (int)P.reff, device, st, ys, total);
+		g_quad_times.search += ms_since(t0);
+		if (rc) return rc;
+	} else {
+		if ((depth > 0 && P.reff >= parent_reff) || depth >= kQuadMaxDepth) { *gave_up = true; return GF2BV_OK; }
+		// relinearise: the forms are the equations of a QuadraticSystem of reff unknowns; in augmented words the constant
+		// (bit 0 of an equation int) is column `cols` and unknown k is column k
+		auto t0 = std::chrono::steady_clock::now();
+		const i64 cols = P.reff + P.reff * (P.reff - 1) / 2, rows = std::max(cols, P.m), stride = P.fw;
+		std::vector<u64> aug((size_t)(rows * stride), 0);
+		for (i64 f = 0; f < P.m; f++) {
+			const u64 *e = &P.forms[f * P.fw];
+			u64 *a = &aug[f * stride];
+			for (i64 w = 0; w < stride; w++) a[w] = (e[w] >> 1) | (w + 1 < P.fw ? e[w + 1] << 63 : 0);
+			if (e[0] & 1) qflip(a, cols);
+		}
+		gf2bv_result *res = nullptr;
+		rc = gf2bv_solve_words(reinterpret_cast<const uint64_t *>(aug.data()), rows, cols, stride, GF2BV_MODE_AFFINE_SPACE, device, &res);
+		if (rc) return rc;
+		std::unique_ptr<gf2bv_result, void (*)(gf2bv_result *)> keep(res, gf2bv_result_free);
+		g_quad_times.relin += ms_since(t0);
+		if (gf2bv_result_status(res) != GF2BV_STATUS_SOLVED) return GF2BV_OK;
+		const i64 d2 = gf2bv_result_dimension(res), w2 = gf2bv_result_words(res);
+		std::vector<u64> o2((size_t)w2), b2((size_t)std::max<i64>(1, d2 * w2));
+		gf2bv_result_origin(res, reinterpret_cast<uint64_t *>(o2.data()));
+		if (d2) gf2bv_result_basis(res, reinterpret_cast<uint64_t *>(b2.data()));
+		std::vector<u64> sub, sub_coef;
+		i64 lr;
+		rc = quad_collect(o2.data(), b2.data(), d2, w2, P.reff, max_enum, device, st, P.reff, depth + 1, sub, sub_coef, total, &lr, gave_up);
+		if (rc || *gave_up) return rc;
+		const i64 np = (i64)sub.size() / std::max<i64>(1, w2);
+		ys.assign((size_t)(np * yw), 0);
+		for (i64 k = 0; k < np; k++)
+			for (i64 v = 0; v < P.reff; v++) if (qbit(&sub[k * w2], v)) qflip(&ys[k * yw], v);
+	}
+	if ((i64)*total > kQuadMaxPoints) return GF2BV_OK;
+	const i64 np = (i64)ys.size() / yw;
+	pts.assign((size_t)(np * words), 0);
+	coef.assign((size_t)(np * P.dw), 0);
+	for (i64 k = 0; k < np; k++)
+		if (!quad_point(P, &ys[k * yw], &pts[k * words], &coef[k * P.dw]))
+			return fail(GF2BV_ERR_HIP, "quad search: a point that passed the forms is not consistent (internal error)");
+	return GF2BV_OK;
+}
+
+int check_quad_space(const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n_lin)
+{
+	if (!origin || (d > 0 && !basis)) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (d < 0 || words <= 0) return fail(GF2BV_ERR_ARG, "dimension must be >= 0 and words > 0");
+	if (n_lin < 1 || n_lin > 46340) return fail(GF2BV_ERR_ARG, "n_lin must be 1..46340");
+	if (words < (n_lin + n_lin * (n_lin - 1) / 2 + 63) / 64)
+		return fail(GF2BV_ERR_ARG, "words does not cover n_lin + n_lin(n_lin-1)/2 columns");
+	return GF2BV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gf2bv_quad_plan(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin,
+                    int64_t *r, int64_t *r_eff, int64_t *m, int64_t *form_words, uint64_t *forms_, int64_t forms_cap)
+{
+	const u64 *origin = reinterpret_cast<const u64 *>(origin_), *basis = reinterpret_cast<const u64 *>(basis_);
+	return catching([&]() -> int {
+	int rc = check_quad_space(origin, basis, dimension, words, n_lin);
+	if (rc) return rc;
+	if (!r || !r_eff || !m || !form_words) return fail(GF2BV_ERR_ARG, "null pointer");
+	QuadPlan P;
+	rc = quad_plan_build(P, origin, basis, dimension, words, n_lin, -1, nullptr);
+	if (rc) return rc;
+	*r = P.r; *r_eff = P.reff;
+	*m = P.reff < 0 ? 0 : P.m;
+	*form_words = P.reff < 0 ? 0 : P.fw;
+	if (forms_ && P.reff >= 0 && P.m <= forms_cap) std::copy(P.forms.begin(), P.forms.begin() + P.m * P.fw, reinterpret_cast<u64 *>(forms_));
+	return GF2BV_OK;
+	});
+}
+
+int gf2bv_quad_points(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin,
+                      const uint64_t *ys_, int64_t nys, int64_t y_words, uint64_t *out_words_)
+{
+	const u64 *origin = reinterpret_cast<const u64 *>(origin_), *basis = reinterpret_cast<const u64 *>(basis_);
+	const u64 *ys = reinterpret_cast<const u64 *>(ys_);
+	u64 *out_words = reinterpret_cast<u64 *>(out_words_);
+	return catching([&]() -> int {
+	int rc = check_quad_space(origin, basis, dimension, words, n_lin);
+	if (rc) return rc;
+	if (nys < 0 || (nys > 0 && (!ys || !out_words))) return fail(GF2BV_ERR_ARG, "null pointer");
+	QuadPlan P;
+	rc = quad_plan_build(P, origin, basis, dimension, words, n_lin, -1, nullptr);
+	if (rc) return rc;
+	if (P.reff < 0 || P.inconsistent) return fail(GF2BV_ERR_ARG, "the space has no forms to map from");
+	if (y_words < std::max<i64>(1, (P.reff + 63) / 64)) return fail(GF2BV_ERR_ARG, "y_words does not cover r_eff bits");
+	std::vector<u64> c((size_t)P.dw);
+	for (i64 k = 0; k < nys; k++)
+		if (!quad_point(P, ys + k * y_words, out_words + k * words, c.data()))
+			return fail(GF2BV_ERR_ARG, "an assignment that is not a common zero of the forms");
+	return GF2BV_OK;
+	});
+}
+
+int gf2bv_quad_forms_search(const uint64_t *forms_, int64_t m, int64_t r_eff, int device, int64_t max_out, int64_t *count,
+                            uint64_t *out_)
+{
+	const u64 *forms = reinterpret_cast<const u64 *>(forms_);
+	u64 *out = reinterpret_cast<u64 *>(out_);
+	return guarded([&]() -> int {
+	if (!count || (m > 0 && !forms) || (max_out > 0 && !out) || m < 0 || max_out < 0) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (r_eff < 0 || r_eff > kQuadMaxEnum) return fail(GF2BV_ERR_ARG, "r_eff must be 0..40");
+	*count = 0;
+	int rc = check_device(device);
+	if (rc) return rc;
+	hipStream_t st = nullptr;
+	HIPCHK(pool().stream(&st, device, 0));
+	std::unique_ptr<void, std::function<void(void *)>> keep(st, [&](void *) { pool().release_stream(st, device, 0); });
+	std::vector<u64> ys;
+	u64 total = 0;
+	rc = quad_search_device(forms, m, (r_eff + r_eff * (r_eff - 1) / 2 + 64) / 64, (int)r_eff, device, st, ys, &total);
+	if (rc) return rc;
+	*count = (int64_t)total;
+	if ((i64)total > kQuadMaxPoints && max_out > 0) return fail(GF2BV_ERR_NOMEM, "more common zeros than can be collected");
+	std::sort(ys.begin(), ys.end());
+	std::copy(ys.begin(), ys.begin() + std::min<i64>((i64)ys.size(), max_out), out);
+	return GF2BV_OK;
+	});
+}
+
+int gf2bv_quad_search(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin,
+                      int max_enum, int64_t max_solutions, int device, int64_t *count, int64_t *lin_rank, uint64_t *out_words_)
+{
+	if (max_solutions > 0 && !out_words_) return fail(GF2BV_ERR_ARG, "null pointer");
+	uint64_t *pts = nullptr;
+	const int rc = gf2bv_quad_search_alloc(origin_, basis_, dimension, words, n_lin, max_enum, max_solutions, device, count, lin_rank,
+	                                       &pts);
+	if (rc == GF2BV_OK && pts) memcpy(out_words_, pts, sizeof(uint64_t) * (size_t)(std::min<int64_t>(*count, max_solutions) * words));
+	gf2bv_quad_free(pts);
+	return rc;
+}
+
+int gf2bv_quad_search_alloc(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin,
+                            int max_enum, int64_t max_solutions, int device, int64_t *count, int64_t *lin_rank, uint64_t **out_words)
+{
+	const u64 *origin = reinterpret_cast<const u64 *>(origin_), *basis = reinterpret_cast<const u64 *>(basis_);
+	return guarded([&]() -> int {
+	int rc = check_quad_space(origin, basis, dimension, words, n_lin);
+	if (rc) return rc;
+	if (!count || !lin_rank || !out_words) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (max_enum < 0 || max_enum > kQuadMaxEnum) return fail(GF2BV_ERR_ARG, "max_enum must be 0..40");
+	if (max_solutions < 0) return fail(GF2BV_ERR_ARG, "max_solutions must be >= 0");
+	*count = 0; *lin_rank = 0; *out_words = nullptr;
+	rc = check_device(device);
+	if (rc) return rc;
+	g_quad_times = QuadTimes();
+	const auto t0 = std::chrono::steady_clock::now();
+	hipStream_t st = nullptr;
+	HIPCHK(pool().stream(&st, device, 0));
+	std::unique_ptr<void, std::function<void(void *)>> keep(st, [&](void *) { pool().release_stream(st, device, 0); });
+	std::vector<u64> pts, coef;
+	u64 total = 0;
+	bool gave_up = false;
+	rc = quad_collect(origin, basis, dimension, words, n_lin, max_enum, device, st, 0, 0, pts, coef, &total,
+	                  reinterpret_cast<i64 *>(lin_rank), &gave_up);
+	g_quad_times.total = ms_since(t0);
+	if (rc) return rc;
+	if (gave_up) { *count = -1; return GF2BV_OK; }
+	*count = (int64_t)total;
+	if ((i64)total > kQuadMaxPoints) {
+		if (max_solutions > 0) return fail(GF2BV_ERR_NOMEM, "more than 2^22 consistent points: too many to collect and order");
+		return GF2BV_OK;
+	}
+	// iteration order of AffineSpace: the Gray walk for dimension <= 64 (inverse-Gray index of the coefficients), the
+	// binary walk above (the coefficients as an integer, basis[0] the least significant bit)
+	const i64 np = (i64)total, dw = std::max<i64>(1, (dimension + 63) / 64);
+	std::vector<i64> order((size_t)np);
+	for (i64 k = 0; k < np; k++) order[k] = k;
+	if (dimension <= 64) {
+		std::vector<u64> key((size_t)np);
+		for (i64 k = 0; k < np; k++) {
+			u64 g = coef[k * dw];
+			for (int sh = 1; sh < 64; sh <<= 1) g ^= g >> sh;
+			key[k] = g;
+		}
+		std::sort(order.begin(), order.end(), [&](i64 a, i64 b) { return key[a] < key[b]; });
+	} else {
+		std::sort(order.begin(), order.end(), [&](i64 a, i64 b) {
+			for (i64 w = dw - 1; w >= 0; w--)
+				if (coef[a * dw + w] != coef[b * dw + w]) return coef[a * dw + w] < coef[b * dw + w];
+			return false;
+		});
+	}
+	const i64 nout = std::min<i64>(np, max_solutions);
+	if (nout == 0) return GF2BV_OK;
+	uint64_t *out = static_cast<uint64_t *>(malloc(sizeof(uint64_t) * (size_t)(nout * words)));
+	if (!out) return fail(GF2BV_ERR_NOMEM, "out of host memory");
+	for (i64 k = 0; k < nout; k++) memcpy(out + k * words, &pts[order[k] * words], sizeof(uint64_t) * (size_t)words);
+	*out_words = out;
+	return GF2BV_OK;
+	});
+}
+
+void gf2bv_quad_free(uint64_t *words) { free(words); }
+
+void gf2bv_quad_last_times(double *out8)
+{
+	if (!out8) return;
+	const QuadTimes &t = g_quad_times;
+	const double v[8] = {t.reduce, t.forms, t.affine, t.search, t.relin, t.total, (double)t.levels, (double)t.candidates};
+	std::copy(v, v + 8, out8);
+}
 
 }  // extern "C"

@@ -249,3 +249,30 @@ class FactoredSystem:
             sol = self._system.convert_sol(raw)
             if sol is not None:
                 yield sol
+
+    # -- QuadraticSystem.search_*, per instance (quadratic systems only) ------------------------------------------------------
+    def _searchable(self) -> None:
+        if not self._quadratic:
+            raise TypeError("search_* needs a QuadraticSystem's factorization")
+
+    def search_one_rhs(self, values_list: Sequence[Sequence[int]], *, max_enum: int = 32) -> list:
+        """QuadraticSystem.search_one for every instance, the spaces from one factorization"""
+        self._searchable()
+        out = []
+        for space in self._solve(values_list, 1):
+            if space is None:
+                out.append(None)
+            else:
+                sols = self._system._search_space(space, max_enum, 1, first=True)
+                out.append(sols[0] if sols else None)
+        return out
+
+    def search_one(self, values: Sequence[int], *, max_enum: int = 32):
+        return self.search_one_rhs([values], max_enum=max_enum)[0]
+
+    def search_all(self, values: Sequence[int], *, max_enum: int = 32, max_solutions: int = 65536) -> list:
+        self._searchable()
+        space = self._solve([values], 1)[0]
+        if space is None:
+            return []
+        return self._system._search_space(space, max_enum, max_solutions)

@@ -35,6 +35,7 @@ EXPORTS = [
     "gf2bv_result_status", "gf2bv_result_rank", "gf2bv_result_dimension", "gf2bv_result_words",
     "gf2bv_result_origin", "gf2bv_result_basis", "gf2bv_result_pivots", "gf2bv_result_stats",
     "gf2bv_result_free", "gf2bv_space_combine", "gf2bv_space_open", "gf2bv_space_enumerate", "gf2bv_space_buffer", "gf2bv_space_close",
+    "gf2bv_quad_search", "gf2bv_quad_search_alloc", "gf2bv_quad_free", "gf2bv_quad_plan", "gf2bv_quad_points", "gf2bv_quad_forms_search", "gf2bv_quad_last_times",
     "gf2bv_slab_work_words", "gf2bv_slab_tiles", "gf2bv_slab_open", "gf2bv_slab_blocks", "gf2bv_slab_owner",
     "gf2bv_slab_payload_bytes", "gf2bv_slab_factor", "gf2bv_slab_apply", "gf2bv_slab_factor_on", "gf2bv_slab_apply_on",
     "gf2bv_slab_finish_local", "gf2bv_slab_solve",
@@ -124,6 +125,15 @@ def lib():
         L.gf2bv_space_enumerate.argtypes = [vp, ctypes.c_uint64, i64, i32, vp]
         L.gf2bv_space_close.argtypes = [vp]
         L.gf2bv_space_close.restype = None
+        L.gf2bv_quad_search.argtypes = [vp, vp, i64, i64, i64, i32, i64, i32, vp, vp, vp]
+        L.gf2bv_quad_search_alloc.argtypes = [vp, vp, i64, i64, i64, i32, i64, i32, vp, vp, pp]
+        L.gf2bv_quad_free.argtypes = [vp]
+        L.gf2bv_quad_free.restype = None
+        L.gf2bv_quad_plan.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, i64]
+        L.gf2bv_quad_points.argtypes = [vp, vp, i64, i64, i64, vp, i64, i64, vp]
+        L.gf2bv_quad_forms_search.argtypes = [vp, i64, i64, i32, i64, vp, vp]
+        L.gf2bv_quad_last_times.argtypes = [vp]
+        L.gf2bv_quad_last_times.restype = None
         L.gf2bv_slab_work_words.argtypes = [i64, i64]
         L.gf2bv_slab_work_words.restype = i64
         L.gf2bv_slab_tiles.argtypes = [i64]
@@ -491,6 +501,65 @@ def space_enumerate(origin: np.ndarray, basis: np.ndarray, first: int, count: in
         return out
     finally:
         lib().gf2bv_space_close(h)
+
+
+def _ints_to_words(vals, words: int) -> np.ndarray:
+    out = np.zeros((max(len(vals), 1), words), dtype=np.uint64)
+    for k, v in enumerate(vals):
+        out[k] = np.frombuffer(int(v).to_bytes(words * 8, "little"), dtype=np.uint64)
+    return out
+
+
+def _words_to_ints(arr: np.ndarray, n: int) -> list:
+    return [int.from_bytes(arr[k].tobytes(), "little") for k in range(n)]
+
+
+def quad_words(n_lin: int) -> int:
+    """words of a QuadraticSystem point with n_lin linear unknowns (n_lin + n_lin(n_lin-1)/2 columns)"""
+    return (n_lin + n_lin * (n_lin - 1) // 2 + 63) // 64
+
+
+def quad_plan(origin: int, basis, n_lin: int) -> dict:
+    """gf2bv_quad_plan (host only): r, r_eff (-1: not reduced), and the forms as equation ints over r_eff unknowns."""
+    words = quad_words(n_lin)
+    o, b = _ints_to_words([origin], words), _ints_to_words(list(basis), words)
+    r, re, m, fw = (ctypes.c_int64() for _ in range(4))
+    _check(lib().gf2bv_quad_plan(o.ctypes.data, b.ctypes.data, len(basis), words, n_lin, ctypes.byref(r), ctypes.byref(re),
+                                 ctypes.byref(m), ctypes.byref(fw), None, 0))
+    forms = np.zeros((max(m.value, 1), max(fw.value, 1)), dtype=np.uint64)
+    _check(lib().gf2bv_quad_plan(o.ctypes.data, b.ctypes.data, len(basis), words, n_lin, ctypes.byref(r), ctypes.byref(re),
+                                 ctypes.byref(m), ctypes.byref(fw), forms.ctypes.data, m.value))
+    return {"r": r.value, "r_eff": re.value, "forms": _words_to_ints(forms, m.value)}
+
+
+def quad_points(origin: int, basis, n_lin: int, ys) -> list:
+    """gf2bv_quad_points (host only): the points of the space that common zeros `ys` of quad_plan's forms stand for."""
+    words = quad_words(n_lin)
+    o, b = _ints_to_words([origin], words), _ints_to_words(list(basis), words)
+    yw = max(1, max((int(y).bit_length() for y in ys), default=0) // 64 + 1)
+    y = _ints_to_words(list(ys), yw)
+    out = np.zeros((max(len(ys), 1), words), dtype=np.uint64)
+    _check(lib().gf2bv_quad_points(o.ctypes.data, b.ctypes.data, len(basis), words, n_lin, y.ctypes.data, len(ys), yw,
+                                   out.ctypes.data))
+    return _words_to_ints(out, len(ys))
+
+
+def quad_forms_search(forms, r_eff: int, device: int = 0, max_out: int = 1 << 22) -> tuple:
+    """gf2bv_quad_forms_search: (count, ascending common zeros) of forms given as equation ints over r_eff unknowns."""
+    fw = (r_eff + r_eff * (r_eff - 1) // 2 + 64) // 64
+    f = _ints_to_words(list(forms), fw)
+    cnt = ctypes.c_int64()
+    out = np.zeros(max(max_out, 1), dtype=np.uint64)
+    _check(lib().gf2bv_quad_forms_search(f.ctypes.data, len(forms), r_eff, device, max_out, ctypes.byref(cnt), out.ctypes.data))
+    return cnt.value, [int(v) for v in out[:min(cnt.value, max_out)]]
+
+
+def quad_last_times() -> dict:
+    """this thread's last gf2bv_quad_search: phase times in ms, levels, first-pass candidates"""
+    v = (ctypes.c_double * 8)()
+    lib().gf2bv_quad_last_times(v)
+    keys = ("ms_reduce", "ms_forms", "ms_affine", "ms_search", "ms_relin", "ms_total", "levels", "candidates")
+    return dict(zip(keys, list(v)))
 
 
 def synth_device(d_ptr: int, rows: int, cols: int, stride: int, seed: int, device: int = 0, stream: int = 0):

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 from typing import Iterable, Optional, Sequence, Union
 
-from ._internal import AffineSpace, eqs_to_sage_mat_helper, m4ri_solve, m4ri_solve_many, m4ri_solve_rhs, mul_bit_quad
+from ._internal import AffineSpace, QuadSearchGaveUp, eqs_to_sage_mat_helper, m4ri_solve, m4ri_solve_many, m4ri_solve_rhs, mul_bit_quad
 from .bitvec import BitVec
 
 Zeros = Sequence[Union[BitVec, int]]
@@ -336,6 +336,40 @@ class QuadraticSystem(LinearSystem):
                         break
             out.append(sol)
         return out
+
+    # -- the consistent points on the GPU (no counterpart in the reference) -------------------------------------------------
+    # solve_all walks all 2^d points of the linearised space on the host; search_all reduces the space to quadratic forms in
+    # r_eff <= r variables (r: the rank of its projection onto the linear unknowns) and finds their common zeros on the device
+    # (AffineSpace.quad_search -> gf2bv_quad_search).  Same elements in the same order as solve_all,
+    # at any dimension.
+    def _search_space(self, space, max_enum: int, max_solutions: int, first: bool = False) -> list:
+        try:
+            raws = space.quad_search(self._lin_size, max_enum, max_solutions, first)
+        except QuadSearchGaveUp as e:
+            raise DimensionTooLargeError(f"Solution space (dim {space.dimension}): {e.args[0]}", space=space) from None
+        out = []
+        for raw in raws:
+            sol = self.convert_sol(raw)
+            if sol is None:
+                raise RuntimeError("quad_search returned an inconsistent point")
+            out.append(sol)
+        return out
+
+    def search_all(self, zeros: Zeros, *, max_enum: int = 32, max_solutions: int = 65536) -> list:
+        """list(solve_all(zeros, max_dimension=d)) without the 2^d walk; DimensionTooLargeError (with .space) when the search
+        gives up, ValueError when there are more than max_solutions consistent points."""
+        space = self.solve_raw_space(zeros)
+        if space is None:
+            return []
+        return self._search_space(space, max_enum, max_solutions)
+
+    def search_one(self, zeros: Zeros, *, max_enum: int = 32):
+        """solve_one(zeros) at any dimension: the first consistent point in iteration order, None if there is none."""
+        space = self.solve_raw_space(zeros)
+        if space is None:
+            return None
+        sols = self._search_space(space, max_enum, 1, first=True)
+        return sols[0] if sols else None
 
     def evaluate(self, bv: BitVec, sol: tuple) -> int:
         raw, shift = 0, 0

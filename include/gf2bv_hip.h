@@ -302,6 +302,41 @@ int  gf2bv_space_enumerate(gf2bv_space *space, uint64_t first, int64_t count, in
 const uint64_t *gf2bv_space_buffer(const gf2bv_space *space);
 void gf2bv_space_close(gf2bv_space *space);
 
+/* ---- quadratic search: the consistent points of a linearised quadratic system's solution space ----------------------------
+ * A space of QuadraticSystem unknowns: coordinates 0..n_lin-1 are linear, pair (i, j), j < i, is at n_lin + i(i-1)/2 + j;
+ * `words` must cover those n_lin + n_lin(n_lin-1)/2 columns.  A point is consistent when every pair coordinate equals the
+ * product of its two linear bits (QuadraticSystem.convert_sol).  The space is reduced to quadratic forms in r_eff variables
+ * whose common zeros are exactly the consistent points (r: the rank of the space's projection onto the linear coordinates,
+ * at most 256 is reduced).
+ * gf2bv_quad_search: *count = the number of consistent points; the first min(count, max_solutions) of them, in the order in
+ * which AffineSpace iteration meets them, are written to out_words (count x words).  *count = -1: the search gave up (r above
+ * 256, or r_eff above max_enum and relinearisation makes no progress); *lin_rank = r in every case.  max_enum: 0..40.
+ * More than 2^22 consistent points are counted, not collected: GF2BV_ERR_NOMEM when max_solutions > 0.  Argument errors
+ * return GF2BV_ERR_ARG before any device is touched.
+ * gf2bv_quad_search_alloc: the same search, the points in a buffer the library allocates for exactly min(count, max_solutions)
+ * points (*out_words = NULL when that is 0), released with gf2bv_quad_free.
+ * gf2bv_quad_plan (host only, touches no device): r, r_eff (-1: r above 256, no forms), m forms of form_words words each in
+ * the equation-int layout of a QuadraticSystem of r_eff unknowns (bit 0 = constant, bit 1 + v = variable v, bit
+ * 1 + r_eff + i(i-1)/2 + j = the product of variables i and j, j < i), written when forms != NULL and m <= forms_cap.  No
+ * consistent point at all: r_eff = 0 and the single form 1.
+ * gf2bv_quad_points (host only): the points (words each) that nys common zeros ys (y_words each) of those forms stand for.
+ * gf2bv_quad_forms_search: every common zero of m forms (that layout, r_eff <= 40) by the device search, ascending;
+ * *count = their number, the first max_out written.
+ * gf2bv_quad_last_times: this thread's last gf2bv_quad_search in ms -- reduction, forms build, affine elimination, device
+ * search, relinearised solves, total -- then the number of levels and of first-pass candidates. */
+int  gf2bv_quad_search(const uint64_t *origin, const uint64_t *basis, int64_t dimension, int64_t words, int64_t n_lin,
+                       int max_enum, int64_t max_solutions, int device, int64_t *count, int64_t *lin_rank, uint64_t *out_words);
+int  gf2bv_quad_search_alloc(const uint64_t *origin, const uint64_t *basis, int64_t dimension, int64_t words, int64_t n_lin,
+                             int max_enum, int64_t max_solutions, int device, int64_t *count, int64_t *lin_rank, uint64_t **out_words);
+void gf2bv_quad_free(uint64_t *words);
+int  gf2bv_quad_plan(const uint64_t *origin, const uint64_t *basis, int64_t dimension, int64_t words, int64_t n_lin,
+                     int64_t *r, int64_t *r_eff, int64_t *m, int64_t *form_words, uint64_t *forms, int64_t forms_cap);
+int  gf2bv_quad_points(const uint64_t *origin, const uint64_t *basis, int64_t dimension, int64_t words, int64_t n_lin,
+                       const uint64_t *ys, int64_t nys, int64_t y_words, uint64_t *out_words);
+int  gf2bv_quad_forms_search(const uint64_t *forms, int64_t m, int64_t r_eff, int device, int64_t max_out, int64_t *count,
+                             uint64_t *out);
+void gf2bv_quad_last_times(double *out8);
+
 /* ---- synthetic systems + independent residual check (bench / tests) ----------------------- */
 /* word w of row r = mix64(mix64(seed) ^ ((r<<20)|w)); planted solution = pseudo-row 0xFFFFF;
  * RHS = <row, planted>.  Writes rows x stride_words words at d_aug. */
