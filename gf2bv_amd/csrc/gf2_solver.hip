@@ -76,12 +76,85 @@ inline i64 round_up(i64 v, i64 m) { return (v + m - 1) / m * m; }
 // (never stored); the working matrix and the multiplier sets get this much slack behind them
 constexpr size_t kOuterSlackBytes = (size_t)GF2_WSEG * 1024 * 32;   // (the largest item of the outer pass's workgroup shapes: 12288 rows)
 
-struct Trace {
-	bool on = getenv("GF2BV_TRACE") != nullptr;
-	std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-	void mark(const char *what)
+// ---- environment switches -----------------------------------------------------------------------
+// Every GF2BV_* variable this library reads, described where read() -- the only function of this file that reads the environment --
+// parses it (the members' initialisers are the defaults; DESIGN.md section 8 adds lifetimes, users and history).  Members hold what was
+// ASKED for: what a solve makes of it is Solver state.  flag: on iff set, whatever the text; value: set, "" included (atoi("") is 0);
+// non-empty: "" counts as unset; tri-state: a value, -1 while unset.  Read at every entry that needs it; slab_pad and keep_big are latched.
+struct Knobs {
+	bool plain = false, outer_chain = false, serial = false, ysweep = false, small_probe = false, trace = false, two_level_min_set = false;
+	bool outer_side = true, fast = true, fused_narrow = true, sparse_fast = true, pc = true, gang_nt = true, gang_bs = true, small = true, keep_big = true;
+	int stream_pairs = -1, two_level = -1, optimistic = -1, xcd_pin = -1, bs_inv = -1, small_zc = -1;          // tri-states (two_level: -1 by size, 0 off, else K)
+	int update = 0, flag_sync = 1, xcd_wgs = 32, self_wait_us = 50, gang = 0, batch_threads = 2, debug_sync = 0;
+	i64 slab_pad = 64, host_pool_mb = 4608;
+	double two_level_min_mib = 512;
+	static constexpr int kNumUpdates = 6;
+	enum Part { kAll, kSmall, kHostPool };      // what an entry reads: the small path and gf2bv_host_free only their own (the lookups they always made)
+	static Knobs read(Part what = kAll)
 	{
-		if (!on) return;
+		Knobs k;
+		if (const char *e = getenv("GF2BV_HOST_POOL_MB")) { const long v = atol(e); if (v >= 0) k.host_pool_mb = v; }      // value, >= 0 (else 4608): MiB of idle page-locked staging gf2bv_host_free keeps
+		if (what == kHostPool) return k;
+		if (const char *e = getenv("GF2BV_SMALL")) k.small = atoi(e) != 0;      // value, on: 0 sends small systems down the blocked path
+		if (const char *e = getenv("GF2BV_SMALL_ZC")) k.small_zc = atoi(e) != 0;      // tri-state (unset: up to 32 KiB): the small path reads its input over the link, never / always
+		k.small_probe = getenv("GF2BV_SMALL_PROBE") != nullptr;      // flag: the small path's phase times on stderr
+		if (what == kSmall) return k;
+		if (const char *e = getenv("GF2BV_PLAIN")) k.plain = atoi(e) != 0;      // value: != 0 turns stream pairing, XCD pinning, flag hand-overs and the optimistic enqueue off by default
+		if (const char *e = getenv("GF2BV_STREAM_PAIRS")) k.stream_pairs = atoi(e) != 0;      // tri-state (unset: !plain): 0 gives a single solve any idle bulk stream, not a probed one
+		if (const char *e = getenv("GF2BV_UPDATE")) { const int v = atoi(e); if (v >= 0 && v < kNumUpdates) k.update = v; }      // value: index into kUpdates, anything outside it is 0
+		if (const char *e = getenv("GF2BV_TWO_LEVEL"); e && *e) { const int v = atoi(e); k.two_level = v <= 0 ? 0 : std::min(GF2_KMAX, std::max(2, v)); }      // non-empty: <= 0 is 0, no outer panels; else K = clamp(v, 2, GF2_KMAX) forced; unset: by size
+		if (const char *e = getenv("GF2BV_TWO_LEVEL_MIN_MIB"); e && *e) { k.two_level_min_set = true; k.two_level_min_mib = atof(e); }      // non-empty (unset: 512, or 0 under a forced K): outer panels while more than this many MiB remain right of them
+		if (const char *e = getenv("GF2BV_OUTER_CHAIN"); e && *e) k.outer_chain = atoi(e) != 0;      // non-empty, off: != 0 runs the chain of panel steps on every word group instead of P = T x S
+		if (const char *e = getenv("GF2BV_OUTER_SIDE"); e && *e) k.outer_side = atoi(e) != 0;      // non-empty, on: 0 puts the outer step on the next panel's tiles in front of the pass, not beside it
+		if (const char *e = getenv("GF2BV_FAST")) k.fast = atoi(e) != 0;      // value, on: 0 never tries the one-launch block search
+		if (const char *e = getenv("GF2BV_OPTIMISTIC")) k.optimistic = atoi(e) != 0;      // tri-state (unset: !plain): 0 enqueues the general panel steps behind every search
+		if (const char *e = getenv("GF2BV_FUSED_NARROW")) k.fused_narrow = atoi(e) != 0;      // value, on: 0 runs search and narrow step of an optimistic block as two launches
+		if (const char *e = getenv("GF2BV_SPARSE_FAST")) k.sparse_fast = atoi(e) != 0;      // value, on: 0 sends sparse systems through the general panel steps
+		if (const char *e = getenv("GF2BV_PC")) k.pc = atoi(e) != 0;      // value, on: 0 lets the bulk update fetch the pivot rows through the panel records
+		if (const char *e = getenv("GF2BV_FLAG_SYNC")) k.flag_sync = atoi(e);      // value, 1: 0 hands over through events; 2 skips the concurrency probe (the expired-gate path)
+		k.serial = getenv("GF2BV_SERIAL") != nullptr;      // flag: panel and bulk path on ONE stream
+		if (const char *e = getenv("GF2BV_XCD_PIN")) k.xcd_pin = atoi(e) != 0;      // tri-state (unset: off under plain, else the dispatch probe): a gang's systems each on one XCD
+		if (const char *e = getenv("GF2BV_XCD_WGS")) k.xcd_wgs = std::min(256, std::max(1, atoi(e)));      // value, clamp(v, 1, 256): bulk-update workgroups per system of a pinned gang
+		if (const char *e = getenv("GF2BV_GANG_NT")) k.gang_nt = atoi(e) != 0;      // value, on: 0 gives pinned gangs plain instead of streaming row accesses
+		if (const char *e = getenv("GF2BV_GANG_BS")) k.gang_bs = atoi(e) != 0;      // value, on: 0 runs one back-substitution chain per system of a gang
+		if (const char *e = getenv("GF2BV_BS_INV")) k.bs_inv = atoi(e) != 0;      // tri-state (unset: from 16 panel groups up): diagonal blocks inverted up front, never / always
+		k.ysweep = getenv("GF2BV_YSWEEP") != nullptr;      // flag: every back-substitution through the table sweeps over Y
+		if (const char *e = getenv("GF2BV_SELF_WAIT_US")) { const int v = atoi(e); if (v >= 0 && v <= 1000000) k.self_wait_us = v; }      // value, 0 .. 1000000 (else 50): a search's unit 0 hands publishing over after this long; 0 never waits
+		if (const char *e = getenv("GF2BV_GANG")) { const int v = atoi(e); if (v >= 1) k.gang = v; }      // value: >= 1 overrides the planned gang size, else 0
+		if (const char *e = getenv("GF2BV_BATCH_THREADS")) { const int v = atoi(e); if (v >= 1) k.batch_threads = std::min(v, 16); }      // value: min(v, 16) host threads of a batch call when v >= 1
+		if (const char *e = getenv("GF2BV_SLAB_PAD")) k.slab_pad = std::max<i64>(1, atol(e));      // value, max(1, v), latched: rows behind a tile slab
+		if (const char *e = getenv("GF2BV_KEEP_BIG")) k.keep_big = atoi(e) != 0;      // value, on, latched: 0 keeps no large idle buffer in the pool
+		k.trace = getenv("GF2BV_TRACE") != nullptr;      // flag: host-side times on stderr
+		if (const char *e = getenv("GF2BV_DEBUG_SYNC")) k.debug_sync = atoi(e);      // value, bit mask: hipDeviceSynchronize after every block's panel path (1) / bulk path (2)
+		return k;
+	}
+	void refresh() { const Knobs now = read(); bs_inv = now.bs_inv; ysweep = now.ysweep; trace = now.trace; }      // a later call on a kept handle
+	std::string dump() const          // one NAME=value line per variable, as parsed (gf2bv_knob_dump)
+	{
+		auto n = [](i64 v) { return std::to_string(v); };
+		auto tri = [](int v) { return v < 0 ? std::string("unset") : std::to_string(v); };
+		char mib[32]; snprintf(mib, sizeof mib, "%g", two_level_min_mib);
+		const std::pair<const char *, std::string> rows[] = {
+			{ "GF2BV_PLAIN", n(plain) }, { "GF2BV_STREAM_PAIRS", tri(stream_pairs) }, { "GF2BV_UPDATE", n(update) }, { "GF2BV_TWO_LEVEL", tri(two_level) },
+			{ "GF2BV_TWO_LEVEL_MIN_MIB", two_level_min_set ? mib : "unset" }, { "GF2BV_OUTER_CHAIN", n(outer_chain) }, { "GF2BV_OUTER_SIDE", n(outer_side) },
+			{ "GF2BV_FAST", n(fast) }, { "GF2BV_OPTIMISTIC", tri(optimistic) }, { "GF2BV_FUSED_NARROW", n(fused_narrow) }, { "GF2BV_SPARSE_FAST", n(sparse_fast) },
+			{ "GF2BV_PC", n(pc) }, { "GF2BV_FLAG_SYNC", n(flag_sync) }, { "GF2BV_SERIAL", n(serial) }, { "GF2BV_XCD_PIN", tri(xcd_pin) }, { "GF2BV_XCD_WGS", n(xcd_wgs) },
+			{ "GF2BV_GANG_NT", n(gang_nt) }, { "GF2BV_GANG_BS", n(gang_bs) }, { "GF2BV_BS_INV", tri(bs_inv) }, { "GF2BV_YSWEEP", n(ysweep) }, { "GF2BV_SMALL", n(small) },
+			{ "GF2BV_SMALL_ZC", tri(small_zc) }, { "GF2BV_SMALL_PROBE", n(small_probe) }, { "GF2BV_SELF_WAIT_US", n(self_wait_us) }, { "GF2BV_GANG", n(gang) },
+			{ "GF2BV_BATCH_THREADS", n(batch_threads) }, { "GF2BV_SLAB_PAD", n(slab_pad) }, { "GF2BV_KEEP_BIG", n(keep_big) }, { "GF2BV_HOST_POOL_MB", n(host_pool_mb) },
+			{ "GF2BV_TRACE", n(trace) }, { "GF2BV_DEBUG_SYNC", n(debug_sync) },
+		};
+		std::string s;
+		for (const auto &r : rows) s += std::string(r.first) + "=" + r.second + "\n";
+		return s;
+	}
+};
+
+struct Trace {
+	std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+	void mark(const Knobs &kn, const char *what)
+	{
+		if (!kn.trace) return;
 		auto t = std::chrono::steady_clock::now();
 		fprintf(stderr, "[gf2bv trace] %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t0).count());
 		t0 = t;
@@ -93,7 +166,7 @@ struct Trace {
 // tile with 16-byte tiles): every batch of every tile but the first then straddled NINE lines.  65536^2: 33.7 -> 32.5 ms with
 // any multiple of 64 (64 ... 1024 alike: the channel hash does not care about the stride); other sizes 0-1 %
 // (profiles/r03_slab_pad.txt; GF2BV_SLAB_PAD=2 restores the old layout).
-inline i64 slab_pad() { static const i64 pad = getenv("GF2BV_SLAB_PAD") ? std::max<i64>(1, atol(getenv("GF2BV_SLAB_PAD"))) : 64; return pad; }
+inline i64 slab_pad() { static const i64 pad = Knobs::read().slab_pad; return pad; }
 inline i64 slab_rows(i64 rows) { return round_up(std::max<i64>(rows, 1), 64) + slab_pad(); }
 // column tiles of a row of wt words: whole ownership units of 8 words (one 64-byte tile / four 16-byte tiles)
 inline i64 tiles_for(i64 wt) { return round_up(std::max<i64>(wt, 1), (i64)1 << GF2_OWN_LOG) / GF2_TW; }
@@ -104,15 +177,6 @@ inline i64 tiles_for(i64 wt) { return round_up(std::max<i64>(wt, 1), (i64)1 << G
 // microseconds of GPU time) would spend 5+ ms in them.  Buffers up to 64 MiB (512 MiB in total per
 // process), streams and events are therefore recycled across calls.  Thread-safe; everything handed
 // out is idle (a solve releases its resources only after synchronising its streams).
-// GF2BV_PLAIN=1 (round 6): the floor without heuristics on undocumented hardware behaviour -- no stream-pair probing (any idle
-// low-priority stream), no XCD pinning of gangs (the plain (spans, systems) grid), hand-overs between the streams through events instead
-// of counters in memory + k_gate, every block enqueued with both panel paths (no optimistic enqueue).  Same answers (the parity file runs
-// under it), the speed it costs is reported by bench.py as `plain_ms_per_step`.  An explicit knob still wins over it.
-bool plain_mode()
-{
-	const char *e = getenv("GF2BV_PLAIN");
-	return e && atoi(e) != 0;
-}
 
 struct Pool {
 	std::mutex mu;
@@ -133,11 +197,7 @@ struct Pool {
 	std::map<int, std::vector<Big>> big_free;                         // device -> idle large buffers
 	std::unordered_map<void *, std::pair<int, size_t>> big_live;      // handed-out large buffers
 	std::map<int, size_t> big_cap;                                    // device -> bytes of idle large buffers kept there
-	static bool keep_big()
-	{
-		static const bool keep = !(getenv("GF2BV_KEEP_BIG") && atoi(getenv("GF2BV_KEEP_BIG")) == 0);
-		return keep;
-	}
+	static bool keep_big() { static const bool keep = Knobs::read().keep_big; return keep; }
 	// (mu held) idle large buffers of `device` may hold this many bytes: a sixth of the device's memory, 48 GiB at most
 	size_t big_cap_locked(int device)
 	{
@@ -321,7 +381,7 @@ struct Pool {
 	// does: on a good pair it ends after NB x ~24 us (measured 187-192 us for 8 blocks), on a bad one after NB x ~55 us (439-446): each
 	// block's panel kernels wait for the hold before them.  (A first probe -- when does the last of 80 panel-shaped workgroups begin
 	// beside two holds: 3 us or 36 -- saw only some of the bad pairs; this one agreed with the solve on 38 of 38 pairs.)
-	hipError_t probe_pair(hipStream_t a, hipStream_t b, int device, int *ok, int depth = 0)
+	hipError_t probe_pair(hipStream_t a, hipStream_t b, int device, int *ok, const Knobs &kn, int depth = 0)
 	{
 		*ok = 1;
 		constexpr int NB = 6;
@@ -357,19 +417,18 @@ struct Pool {
 		// neighbour can only slow a probe down
 		if (depth < 2 && chain_us > 0.75 * 37.0 * NB && chain_us < 1.5 * 37.0 * NB) {
 			int again = 1;
-			if (probe_pair(a, b, device, &again, depth + 1) == hipSuccess) *ok = *ok || again;
+			if (probe_pair(a, b, device, &again, kn, depth + 1) == hipSuccess) *ok = *ok || again;
 		}
-		if (getenv("GF2BV_TRACE"))
+		if (kn.trace)
 			fprintf(stderr, "[gf2bv trace] stream pair %p / %p: the panel chain of %d probe blocks took %.1f us (%s)\n", (void *)a, (void *)b, NB, chain_us,
 			        *ok ? "good" : "waits for the bulk stream");
 		return hipSuccess;
 	}
 	// cls: the class the stream comes from and goes back to (1, or 3 for a batch call's gangs); also: the panel streams of the solves that
 	// will run beside this one (all idle now) -- the stream has to get on with them as well.
-	hipError_t low_stream_for(hipStream_t a, int device, hipStream_t *out, int cls = 1, const std::vector<hipStream_t> &also = {})
+	hipError_t low_stream_for(const Knobs &kn, hipStream_t a, int device, hipStream_t *out, int cls = 1, const std::vector<hipStream_t> &also = {})
 	{
-		const bool pairing = !(getenv("GF2BV_STREAM_PAIRS") ? atoi(getenv("GF2BV_STREAM_PAIRS")) == 0 : plain_mode());
-		if (!pairing || !a) return stream(out, device, cls);
+		if (!(kn.stream_pairs >= 0 ? kn.stream_pairs != 0 : !kn.plain) || !a) return stream(out, device, cls);
 		std::lock_guard<std::mutex> pl(probe_mu);
 		std::vector<hipStream_t> rejected, with;
 		with.push_back(a);
@@ -416,7 +475,7 @@ struct Pool {
 				}
 				if (ok < 0) {
 					ok = 1;
-					if (probe_pair(x, c, device, &ok) != hipSuccess) { (void)hipGetLastError(); ok = 1; }      // (a probe that cannot run decides nothing -- and leaves no verdict: the pair is asked again)
+					if (probe_pair(x, c, device, &ok, kn) != hipSuccess) { (void)hipGetLastError(); ok = 1; }      // (a probe that cannot run decides nothing -- and leaves no verdict: the pair is asked again)
 					else {
 						std::lock_guard<std::mutex> lk(mu);
 						pair_ok[{x, c}] = ok;
@@ -441,7 +500,7 @@ Pool &pool()
 
 // ---- kernel configurations -----------------------------------------------------------------
 // Bulk update: G panels fused per HBM pass, T grease tables per panel (balanced bit-fields).
-int streams_run_concurrently(int device, hipStream_t a, hipStream_t b, int *ok);
+int streams_run_concurrently(const Knobs &kn, int device, hipStream_t a, hipStream_t b, int *ok);
 int xcd_dispatch_is_round_robin(int device, hipStream_t st, int *ok);
 void forget_concurrency(int device);
 
@@ -496,15 +555,7 @@ const UpdateImpl kUpdates[] = {
 	UPDATE16_IMPL(640, 2, true, 640),
 };
 
-const UpdateImpl *pick_update()
-{
-	const UpdateImpl *chosen = &kUpdates[0];
-	if (const char *e = getenv("GF2BV_UPDATE")) {      // index into the table above (tests run every instance)
-		const int idx = atoi(e);
-		if (idx >= 0 && idx < (int)(sizeof kUpdates / sizeof kUpdates[0])) chosen = &kUpdates[idx];
-	}
-	return chosen;
-}
+static_assert(sizeof kUpdates / sizeof kUpdates[0] == Knobs::kNumUpdates, "GF2BV_UPDATE indexes this table");
 
 // Back-substitution sweeps over Y use the single-panel kernel (5-bit tables, 128-byte segments).
 constexpr int YK = 5, YTW = 16, YNT = 1024;
@@ -539,7 +590,6 @@ struct Solver {
 	u64 *M = nullptr;             // tile-major working copy (always owned)
 	const u64 *src = nullptr;     // caller's row-major matrix on the device (stride words per row)
 	u64 *tmp_src = nullptr;       // row-major staging buffer when the input came from the host
-	u64 *Ybuf = nullptr;
 	u64 *Minv = nullptr;          // inverted diagonal blocks of the back-substitution (k_bs_inv -> k_bs_near2)
 	i64 rows = 0, cols = 0, stride = 0;
 	i64 ntiles = 0, srows = 0;    // tiles, rows per tile slab (padded)
@@ -563,7 +613,7 @@ struct Solver {
 	int nrhs = 1;
 	u64 *rhs_bad = nullptr;
 	bool time_kernels = false;
-	int dbg_sync = 0;
+	Knobs kn;                     // the environment switches as solver_alloc found them (see Knobs: a kept handle refreshes three per call)
 	const UpdateImpl *impl = nullptr;
 
 	void *arena = nullptr;        // st, panels, aux, fu, alive, pivcol, urow, blk_first, mult, Wb live in here
@@ -581,10 +631,9 @@ struct Solver {
 	i64 tile_hi = 0;              // bulk kernels touch tiles < tile_hi (= ntiles; the outer panel's end while it is eliminated)
 	static constexpr int nlist = 2;      // row lists / T matrices kept: by panel parity (the previous panel's outer pass may still be reading its own)
 	hipStream_t sC = nullptr;     // outer passes: panel p's runs BESIDE the inner elimination of panel p + 1 (sA + sB)
-	bool outer_side = true;       // GF2BV_OUTER_SIDE=0: the outer step on the next panel's tiles in front of the pass on the outer stream (rounds 3-5)
-	                              // (late round 5 also split the pass itself over two streams -- GF2BV_OUTER_SPLIT: 131072^2 162 -> 155 ms, 262144^2
-	                              // -0.8 %, but a fourth stream that cost later batch calls of the process their overlap; removed in round 6,
-	                              // profiles/r05_outer_shapes.txt)
+	                              // (late round 5 also split the pass itself over two streams, behind a switch of its own: 131072^2 162 -> 155 ms,
+	                              // 262144^2 -0.8 %, but a fourth stream that cost later batch calls of the process their overlap; removed in
+	                              // round 6, profiles/r05_outer_shapes.txt)
 	hipEvent_t evOuter = nullptr, evPri = nullptr, evPanelDone = nullptr, evBig = nullptr;
 	bool bulk_waits_outer = false;     // the next bulk launch of the one-level schedule has to wait for the last outer pass
 	bool ends_outer_panel(int b) const { return tl_K > 0 && b < tl_bend && (b + 1) % tl_K == 0; }
@@ -592,37 +641,23 @@ struct Solver {
 	u64 *Uwin = nullptr;          // rank x GMAX: pivot rows' words of the following window (k_prio_window -> k_unwind)
 	int *oprow = nullptr;         // k_outer_prow -> k_outer_apply / k_update16k: row lists of the outer panel being applied
 	u64 *Tm = nullptr;            // k_outer_trsm<IDENT> -> k_outer_apply: the panel's pivot rows as combinations of its source rows
-	bool outer_chain = false;     // GF2BV_OUTER_CHAIN=1: the chain itself on every word group instead (the first form; tests)
 	u64 *Pc = nullptr;            // final pivot rows of the current block, compact: [tile][panel][pivot bit] x 16 B (k_block_trsm -> k_update16)
 	u64 *Pfast = nullptr;         // scratch of k_block_fast: the pivot rows' window words of a block, [panel][word][column]
 	SyncFlags *sf = nullptr;      // progress counters of the two streams (k_gate)
-	bool flag_sync = true;        // per-block hand-overs between the streams through sf + k_gate instead of events (GF2BV_FLAG_SYNC=0)
+	// what a solve decides from the switches and the device (set in one block of solver_alloc)
+	bool flag_sync = true;        // per-block hand-overs between the streams through sf + k_gate instead of events (kn.flag_sync; the device has a say)
+	bool optimistic = true;       // the general panel steps are dropped behind the one-launch search once block 0 has taken it (kn.optimistic)
+	bool xcd_pin = true;          // gangs of a multiple of 8 systems: every system's bulk-update workgroups on ONE XCD, one system after the other, with
+	                              // streaming row accesses (single systems keep plain ones: measured <= 1 % either way in round 4); false: the plain grid
 	int sync_base = 0;            // the counters only grow: a pass that re-enqueues blocks (resume after a poisoned one) counts from here
-	bool fast_blocks = true;      // try the one-launch block search on dense blocks (GF2BV_FAST=0 disables)
-	bool optimistic = true;       // ... and drop the general panel steps behind it once block 0 has taken it (GF2BV_OPTIMISTIC=0)
 	int units = 0;
-	bool ext_events = true;       // hand-off and timing events ride on kernel start / completion signals (hipExtLaunchKernel)
-	                              // instead of marker packets: ~1 % at every size; GF2BV_EXT_EVENTS=0 restores hipEventRecord
-	int sparse_mode = 2;          // search skips absent columns: 0 never, 1 always, 2 per chunk by density (GF2BV_SPARSE)
-	int fused_rpt = 0;            // row blocks of 256 per narrowing workgroup of k_block_fast_narrow (0 = by size)
-	bool use_pc = true;           // GF2BV_PC=0: the bulk update fetches the pivot rows through the panel records, as before round 3
-	bool xcd_pin = true;          // gangs of a multiple of 8 systems: every system's bulk-update workgroups on ONE XCD, one system after the
-	                              // other there, xcd_wgs workgroups each (GF2BV_XCD_WGS); GF2BV_XCD_PIN=0: the plain (spans, systems) grid
-	int xcd_wgs = 32;
-	bool nt_gang = true;          // streaming (non-temporal) row accesses of the bulk update of pinned gangs (GF2BV_GANG_NT=0: plain); single systems
-	                              // keep plain accesses (measured <= 1 % either way in round 4)
-	bool gang_bs = true;          // GF2BV_GANG_BS=0: one back-substitution chain per system of a gang, as rounds 1-3
 	// sparse systems (round 5): blocks the dense one-launch search cannot take go through k_block_sparse -- candidates = the alive rows
-	// with a non-zero window, from the bit masks the look-ahead leaves in wmask (GF2BV_SPARSE_FAST=0: the general panel steps)
-	bool sparse_fast = true;      // allowed at all
+	// with a non-zero window, from the bit masks the look-ahead leaves in wmask (allowed at all: kn.sparse_fast)
 	bool sparse_on = false;       // this solve has switched to it (after block 0 went the general way)
 	int sparse_giveups = 0;
 	int sparse_tier = 0;          // pool size of k_block_sparse: 0 = 1024 rows (beside the bulk update), 1 = 4096, 2 = 6144
 	u64 *wmask = nullptr;         // 2 x ceil(rows / 64) words: alive / alive with a non-zero window, per 64 rows
-	bool fused_narrow = true;     // optimistic blocks: search and narrow step in ONE launch (k_block_fast_narrow); GF2BV_FUSED_NARROW=0: two
-	int narrow_rpt = 1;           // row blocks of 256 per narrow workgroup of a panel step (set in solver_alloc; GF2BV_NARROW_RPT)
-	int self_wait = 5000;         // ticks (100 MHz) unit 0 of a panel search waits for the other units before it leaves
-	                              // publishing to the last arriver: 50 us (GF2BV_SELF_WAIT_US; 0 = never wait)
+	int narrow_rpt = 1;           // row blocks of 256 per narrow workgroup of a panel step (set in solver_alloc)
 	u64 *Y = nullptr;
 	int *ycols = nullptr;
 	u64 *out = nullptr;
@@ -742,9 +777,8 @@ int check_device(int device)
 // 100 ms, 65536^2 34 -> 47 ms; with a threshold on what remains right of the panel (profiles/r03_two_level.txt): 131072^2 best at
 // 384-512 MiB (182 ms), 98304^2 at 512 MiB (87.3 against 92.8), 65536^2 never.  So: K = 8 while more than 512 MiB remain
 // (262144^2: the first 75 % of the pivots; 131072^2: the first half; 98304^2: the first third; nothing below ~70000^2).
-// GF2BV_TWO_LEVEL=0 turns it off, =K (2..12)
-// forces K from the first block on for every full panel whatever the size (tests).  Single systems on one GPU only: gangs
-// and column-slab solves keep the one-level schedule.
+// GF2BV_TWO_LEVEL=0 turns it off, =K (2..12) forces K from the first block on for every full panel whatever the size (tests).
+// Single systems on one GPU only: gangs and column-slab solves keep the one-level schedule.
 void plan_two_level(Solver &S)
 {
 	S.tl_K = 0; S.tl_bend = 0; S.nsets = 2;
@@ -755,21 +789,17 @@ void plan_two_level(Solver &S)
 	// opt-in, bit-exact and slower: 4.4 against 3.9 ms per system; round 5 measured it again on the final gang layout (a system per
 	// XCD, streaming row accesses, gangs of 32 and of 8): 3.50-3.60 against 3.20-3.29 ms per system of 32768^2, K = 4 / 8 / 12 and
 	// thresholds alike (profiles/r05_batch_scans.txt) -- a gang's inner elimination is a chain of all-rows launches of thousands of
-	// workgroups that do not fit beside k_update16k, so chain and pass wait for each other instead of overlapping.  The knob
-	// (GF2BV_GANG_TWO_LEVEL) and its test are gone with round 5.
+	// workgroups that do not fit beside k_update16k, so chain and pass wait for each other instead of overlapping.  The opt-in
+	// and its test are gone with round 5.
 	if (S.nsys != 1) return;
 	// outer panels of 12 blocks from 3 GiB up, of 8 below: the outer pass gains with K (isolated 5.20 / 5.30 / 5.38 TB/s of
 	// sweep-words for K = 8 / 10 / 12), the inner elimination and the T chain grow with it -- 262144^2 1.303 -> 1.269 s,
 	// 196608^2 566 -> 557 ms, 393216^2 4.26 -> 4.13 s, but 131072^2 184.0 -> 185.3 ms (profiles/r03_two_level.txt)
 	int K = (double)S.rows * (double)S.wt * 8.0 >= 3.0 * 1073741824.0 ? GF2_KMAX : 8;       // (per system: a gang's panels stay at 8 blocks)
 	double min_bytes = 0.5 * 1073741824.0;
-	if (const char *e = getenv("GF2BV_TWO_LEVEL"); e && *e) {
-		const int v = atoi(e);
-		if (v <= 0) return;
-		K = std::min(GF2_KMAX, std::max(2, v));
-		min_bytes = 0;
-	}
-	if (const char *e = getenv("GF2BV_TWO_LEVEL_MIN_MIB"); e && *e) min_bytes = 1048576.0 * atof(e);      // (threshold scans)
+	if (S.kn.two_level == 0) return;
+	if (S.kn.two_level > 0) { K = S.kn.two_level; min_bytes = 0; }
+	if (S.kn.two_level_min_set) min_bytes = 1048576.0 * S.kn.two_level_min_mib;      // (threshold scans)
 	const int G = S.impl->G;
 	int bend = 0;
 	for (int b0 = 0; b0 + K < S.nblocks; b0 += K) {            // (the last block never ends an outer panel: it may be short)
@@ -780,17 +810,17 @@ void plan_two_level(Solver &S)
 	}
 	if (!bend) return;
 	S.tl_K = K; S.tl_bend = bend;
-	if (const char *e = getenv("GF2BV_OUTER_CHAIN"); e && *e) S.outer_chain = atoi(e) != 0;
 	S.nsets = 2 * K;              // the outer pass of panel p reads its K sets while the blocks of panel p + 1 write theirs
 }
 
 int solver_alloc(Solver &S)
 {
+	const Knobs &kn = S.kn = Knobs::read();
 	S.wt = (S.cols + S.nrhs + 63) / 64;
 	S.cw = (S.cols + 63) / 64;
 	S.npanels = (int)((S.cols + 63) / 64);
 	S.maxr = std::min(S.rows, S.cols);
-	S.impl = pick_update();
+	S.impl = &kUpdates[S.kn.update];
 	S.ntiles = tiles_for(S.wt);
 	S.srows = slab_rows(S.rows);
 	S.m_stride = S.ntiles * TW * S.srows;
@@ -804,47 +834,34 @@ int solver_alloc(Solver &S)
 	S.tile_hi = S.ntiles;
 	plan_two_level(S);
 	S.units = (int)std::min<i64>(256, std::max<i64>(1, (S.rows + 255) / 256));
-	if (const char *e = getenv("GF2BV_DEBUG_SYNC")) S.dbg_sync = atoi(e);
-	if (const char *e = getenv("GF2BV_FAST")) S.fast_blocks = atoi(e) != 0;
-	const bool plain = plain_mode();
-	S.flag_sync = S.world == 1 && !plain; // (a column-slab solve hands over through the host between the pieces: events)
-	S.optimistic = !plain;
-	if (const char *e = getenv("GF2BV_FLAG_SYNC")) S.flag_sync = S.flag_sync && atoi(e) != 0;
-	if (getenv("GF2BV_SERIAL")) S.flag_sync = false;      // (one stream: the panel gate would wait for a gate queued behind it)
-	if (const char *e = getenv("GF2BV_OPTIMISTIC")) S.optimistic = atoi(e) != 0;
-	if (const char *e = getenv("GF2BV_FUSED_NARROW")) S.fused_narrow = atoi(e) != 0;
-	if (const char *e = getenv("GF2BV_SPARSE_FAST")) S.sparse_fast = atoi(e) != 0;
-	if (const char *e = getenv("GF2BV_PC")) S.use_pc = atoi(e) != 0;
-	if (const char *e = getenv("GF2BV_XCD_PIN")) S.xcd_pin = atoi(e) != 0;
-	else if (plain) S.xcd_pin = false;
-	else if (S.nsys >= 8 && S.nsys % 8 == 0) {           // a gang that would be pinned: is the dispatch order what the pinning assumes?
+	// (a column-slab solve hands over through the host between the pieces: events; on one stream the panel gate would wait for a gate queued behind it)
+	S.flag_sync = S.world == 1 && !kn.plain && kn.flag_sync != 0 && !kn.serial;
+	S.optimistic = kn.optimistic >= 0 ? kn.optimistic != 0 : !kn.plain;
+	S.xcd_pin = kn.xcd_pin >= 0 ? kn.xcd_pin != 0 : !kn.plain;
+	if (kn.xcd_pin < 0 && !kn.plain && S.nsys >= 8 && S.nsys % 8 == 0) {           // a gang that would be pinned: is the dispatch order what the pinning assumes?
 		int ok = 0;
 		int rc = xcd_dispatch_is_round_robin(S.device, S.sA, &ok);
 		if (rc) return rc;
 		S.xcd_pin = ok != 0;
 	}
-	if (const char *e = getenv("GF2BV_XCD_WGS")) S.xcd_wgs = std::min(256, std::max(1, atoi(e)));
-	if (const char *e = getenv("GF2BV_GANG_NT")) S.nt_gang = atoi(e) != 0;
-	if (const char *e = getenv("GF2BV_GANG_BS")) S.gang_bs = atoi(e) != 0;
 	// narrow workgroups: as many rows each as keeps ~256 of them (all systems of a gang together) busy, at most 8 blocks
 	{
 		const i64 blocks = (S.rows + 255) / 256 * std::max(1, S.nsys);
 		S.narrow_rpt = (int)std::min<i64>(8, std::max<i64>(1, blocks / 256));
 	}
-	if (const char *e = getenv("GF2BV_SELF_WAIT_US")) { int v = atoi(e); if (v >= 0 && v <= 1000000) S.self_wait = v * 100; }
-	if (getenv("GF2BV_SERIAL")) { S.sB = S.sA; S.own_sB = false; }     // ablation: no look-ahead overlap
+	if (kn.serial) { S.sB = S.sA; S.own_sB = false; }     // ablation: no look-ahead overlap
 	else {
 		// the bulk path yields to the (latency-critical) panel path wherever both have work queued: lowest priority
 		// (round 5: single systems take a stream that is KNOWN to run beside sA, see Pool::low_stream_for.  Gangs take any: two
 		// lock-step gangs side by side ran 16 MT19937 systems in 33 ms on whatever the pool handed out and in 36-41 ms on pairs
 		// chosen this way -- with four busy queues other relations than panel / bulk of ONE solve decide, profiles/r05_stream_pairs.txt)
-		if (S.nsys == 1) HIPCHK(pool().low_stream_for(S.sA, S.device, &S.sB));
+		if (S.nsys == 1) HIPCHK(pool().low_stream_for(kn, S.sA, S.device, &S.sB));
 		else HIPCHK(pool().stream(&S.sB, S.device, 3));
 		S.own_sB = true;
 	}
 	if (S.flag_sync && S.sB != S.sA) {
 		int ok = 0;
-		int rc = streams_run_concurrently(S.device, S.sA, S.sB, &ok);
+		int rc = streams_run_concurrently(kn, S.device, S.sA, S.sB, &ok);
 		if (rc) return rc;
 		S.flag_sync = ok != 0;
 	}
@@ -860,7 +877,7 @@ int solver_alloc(Solver &S)
 		             o_wb = carve(sizeof(u64) * 2 * GF2_GMAX * R), o_uw = carve(sizeof(u64) * GF2_GMAX * (S.maxr + 64)),
 		             o_pf = carve(sizeof(u64) * GF2_GMAX * GF2_GMAX * 64), o_opr = carve(sizeof(int) * GF2_OUTER_LISTS * S.nlist),
 		             o_tm = carve(S.tl_K ? S.nlist * sizeof(u64) * GF2_KMAX * GF2_KMAX * GF2_GMAX * 64 * GF2_GMAX : 0),
-		             o_pc = carve(S.use_pc ? sizeof(u64) * 2 * GF2_GMAX * 64 * (size_t)S.ntiles : 0),
+		             o_pc = carve(kn.pc ? sizeof(u64) * 2 * GF2_GMAX * 64 * (size_t)S.ntiles : 0),
 		             o_wm = carve(sizeof(u64) * 2 * (size_t)((R + 63) / 64 + 1));
 		S.arena_stride = off;
 		S.sync_base = 0;
@@ -870,7 +887,7 @@ int solver_alloc(Solver &S)
 		S.fu = (FindUnit *)(base + o_fu); S.died = (int *)(base + o_alive); S.pivcol = (int *)(base + o_piv);
 		S.urow = (int *)(base + o_urow); S.blk_first = (int *)(base + o_blk); S.mult = (u64 *)(base + o_mult);
 		S.Wb = (u64 *)(base + o_wb); S.Uwin = (u64 *)(base + o_uw); S.Pfast = (u64 *)(base + o_pf); S.oprow = (int *)(base + o_opr); S.Tm = (u64 *)(base + o_tm);
-		S.Pc = S.use_pc ? (u64 *)(base + o_pc) : nullptr;
+		S.Pc = kn.pc ? (u64 *)(base + o_pc) : nullptr;
 		S.wmask = (u64 *)(base + o_wm);
 		// zero everything that is read before it is written: state, panel records, unit scratch, block bounds, multipliers
 		for (int s = 0; s < S.nsys; s++) {
@@ -886,9 +903,8 @@ int solver_alloc(Solver &S)
 	HIPCHK(pool().event(&S.ev3, true));
 	if (S.tl_K) {
 		for (hipEvent_t *e : { &S.evOuter, &S.evPri, &S.evPanelDone }) HIPCHK(pool().event(e, false));
-		if (S.sB != S.sA) { if (S.nsys == 1) HIPCHK(pool().low_stream_for(S.sA, S.device, &S.sC)); else HIPCHK(pool().stream(&S.sC, S.device, 3)); }       // (GF2BV_SERIAL: everything on one stream)
+		if (S.sB != S.sA) { if (S.nsys == 1) HIPCHK(pool().low_stream_for(kn, S.sA, S.device, &S.sC)); else HIPCHK(pool().stream(&S.sC, S.device, 3)); }       // (GF2BV_SERIAL: everything on one stream)
 		HIPCHK(pool().event(&S.evBig, false));
-		if (const char *e = getenv("GF2BV_OUTER_SIDE"); e && *e) S.outer_side = atoi(e) != 0;
 	}
 	S.evA.resize(S.nblocks); S.evPrio.resize(S.nblocks); S.waitPrio.assign(S.nblocks, nullptr);
 	for (int b = 0; b < S.nblocks; b++) {
@@ -908,15 +924,14 @@ void forget_concurrency(int device)       // a gate timed out although the probe
 	std::lock_guard<std::mutex> lk(c.mu);
 	c.known[device] = 0;
 }
-int streams_run_concurrently(int device, hipStream_t a, hipStream_t b, int *ok)
+int streams_run_concurrently(const Knobs &kn, int device, hipStream_t a, hipStream_t b, int *ok)
 {
 	std::mutex &mu = concurrency_cache().mu;
 	std::map<int, int> &known = concurrency_cache().known;
 	std::lock_guard<std::mutex> lk(mu);
 	auto it = known.find(device);
 	if (it != known.end()) { *ok = it->second; return GF2BV_OK; }
-	// (GF2BV_FLAG_SYNC=2: take concurrency for granted until a gate times out -- exercises the time-out / retry path)
-	if (getenv("GF2BV_FLAG_SYNC") && atoi(getenv("GF2BV_FLAG_SYNC")) == 2) { *ok = 1; return GF2BV_OK; }
+	if (kn.flag_sync == 2) { *ok = 1; return GF2BV_OK; }      // (taken for granted until a gate times out: exercises the time-out / retry path)
 	int *d = nullptr;
 	HIPCHK(pool().alloc((void **)&d, 2 * sizeof(int), device));
 	struct Free { int *p; ~Free() { pool().release(p); } } guard{d};
@@ -1012,20 +1027,16 @@ int launch_update_timed(Solver &S, hipStream_t st, int b, int j0, int gb, int wl
 	if (S.time_kernels) {
 		HIPCHK(pool().event(&ka, true)); HIPCHK(pool().event(&kb, true));
 		S.kev.push_back(ka); S.kev.push_back(kb);
-		if (!S.ext_events) HIPCHK(hipEventRecord(ka, st));
 	}
 	const i64 est_rows = std::max<i64>(256, S.rows - (i64)j0 * 64);      // alive rows of a dense system (the kernel uses the true bound)
 	const bool pin = S.xcd_pin && S.nsys >= 8 && S.nsys % 8 == 0;
-	const int wgs = pick_update_wgs(est_rows, ntiles, S.nsys, pin ? S.xcd_wgs : 0);
-	hipEvent_t begun = nullptr, done = nullptr;
-	if (S.ext_events) { begun = ka; done = S.time_kernels ? kb : (last && !S.flag_sync ? S.evPrio[b] : nullptr); }
+	const int wgs = pick_update_wgs(est_rows, ntiles, S.nsys, pin ? S.kn.xcd_wgs : 0);
+	// the launch's own start / completion signals (hipExtLaunchKernel) carry the timing events or the hand-off: no marker packets, ~1 % at every size
+	const hipEvent_t begun = ka, done = S.time_kernels ? kb : (last && !S.flag_sync ? S.evPrio[b] : nullptr);
 	HIPCHK(S.impl->update(dim3((unsigned)wgs, S.nsys), st, S.M, S.rows, S.srows, j0, gb, wlo, S.panels, S.aux, mset,
-	                      S.blk_first + b, tile_begin, ntiles, S.world, S.wrank, nw_lo, pin && S.nt_gang,
+	                      S.blk_first + b, tile_begin, ntiles, S.world, S.wrank, nw_lo, pin && S.kn.gang_nt,
 	                      (const uint4 *)S.Pc, S.ss(), begun, done, pin ? S.nsys : 0));
-	if (S.time_kernels && !S.ext_events) HIPCHK(hipEventRecord(kb, st));
-	if (!last || S.flag_sync) return GF2BV_OK;
-	if (S.ext_events) *handoff = done;
-	else { HIPCHK(hipEventRecord(S.evPrio[b], st)); *handoff = S.evPrio[b]; }
+	if (last && !S.flag_sync) *handoff = done;
 	return GF2BV_OK;
 }
 
@@ -1061,7 +1072,7 @@ BlockGeom block_geom(const Solver &S, int b)
 // fast_only: the block gets the one-launch search and the one-pass narrow step only (see enqueue_forward)
 bool fast_block_possible(const Solver &S, const BlockGeom &g)
 {
-	return S.fast_blocks && g.gb == GF2_GMAX && (i64)(g.j0 + g.gb) * 64 <= S.cols && S.rows >= GF2_FAST_NC;
+	return S.kn.fast && g.gb == GF2_GMAX && (i64)(g.j0 + g.gb) * 64 <= S.cols && S.rows >= GF2_FAST_NC;
 }
 
 // flag hand-over, panel stream: "block b factorised" (its multipliers are complete) -- and, where the look-ahead of block b
@@ -1073,14 +1084,36 @@ int panel_handover(Solver &S, int b)      // general panel steps: a launch for t
 	return GF2BV_OK;
 }
 
+constexpr int kSparseByDensity = 2;      // k_panel_step's search mode: it skips absent columns per chunk, by density (0 never, 1 always)
 int enqueue_block_panel(Solver &S, int b, bool fast_only = false, bool sparse = false)
 {
 	const BlockGeom g = block_geom(S, b);
 	const unsigned row_blocks = (unsigned)((S.rows + 255) / 256);
 	u64 *const half[2] = { S.Wb, S.Wb + (i64)GF2_GMAX * S.rows };
-	if (fast_only && sparse) {
+	// a one-launch block's last launch announces narrow_done itself (flag_sync) or carries evA[b] as its completion signal
+	const hipEvent_t done = S.flag_sync ? nullptr : S.evA[b];
+	const DoneSignal sig = S.flag_sync ? DoneSignal{ &S.sf->cnt_narrow, &S.sf->narrow_done, S.sync_base + b + 1 } : DoneSignal{};
+	if (fast_only && !sparse && S.kn.fused_narrow && S.nsys == 1) {
+		// search + narrow step in one launch: workgroup 0 searches, the others narrow each panel as soon as it is formed
+		// (single systems: a gang is throughput-bound, and its ~130 x nsys narrowing workgroups would hold their LDS for the whole
+		// search -- measured equal either way, 243 against 242 systems/s of 32768^2: gangs keep the two launches)
+		// at most ~128 narrowing workgroups: they stay resident for the whole search, and a CU that holds TWO of them (2 x 26 KiB
+		// of LDS) cannot take a bulk-update workgroup (133 of 160 KiB) until they end -- with 257 workgroups on 256 CUs there is
+		// always such a CU, and the pass whose launch lands just behind the search waits ~20 us for its last workgroup
+		// (tools/pass_rates.py: every fourth pass of the mid-range of a 65536^2 solve)
+		const int rpt = (int)std::min<i64>(8, std::max<i64>(S.narrow_rpt, (row_blocks + 127) / 128));
+		hipExtLaunchKernelGGL(k_block_fast_narrow, dim3(1 + (row_blocks + rpt - 1) / rpt, S.nsys), dim3(256), 0, S.sA, nullptr, done, 0,
+		                      S.M, S.rows, S.srows, g.j0, g.gb, b, (const u64 *)half[0], S.st, S.died, S.panels, S.aux, S.pivcol, S.urow,
+		                      S.blk_first + b, S.Pfast, g.mset, S.impl->T, rpt, sig, S.ss());
+		HIPCHK(hipGetLastError());
+		return GF2BV_OK;
+	}
+	if (fast_only) {
+		if (!sparse)
+			k_block_fast<<<dim3(1, S.nsys), dim3(256), 0, S.sA>>>(S.M, S.rows, S.srows, g.j0, g.gb, 1, b, (const u64 *)half[0], S.st, S.died,
+			                                                      S.panels, S.aux, S.pivcol, S.urow, S.blk_first + b, S.Pfast, S.ss());
 		// sparse systems: the pool of the search = alive rows with a non-zero window (wmask, left by the look-ahead of the block before)
-		if (S.sparse_tier == 0)
+		else if (S.sparse_tier == 0)
 			k_block_sparse<256, 4><<<dim3(1, S.nsys), dim3(256), 0, S.sA>>>(S.M, S.rows, S.srows, g.j0, g.gb, 1, b, (const u64 *)half[0], S.st, S.died,
 			                                                                 S.panels, S.aux, S.pivcol, S.urow, S.blk_first + b, (const u64 *)S.wmask, S.ss());
 		else if (S.sparse_tier == 1)             // (after a give-up, or when the first block counted more rows than the small pool holds: 4096 rows)
@@ -1089,43 +1122,10 @@ int enqueue_block_panel(Solver &S, int b, bool fast_only = false, bool sparse = 
 		else          // (after two: 6144 rows -- 1024 threads at 128 registers, the candidates' words partly in scratch: slow, but still ahead of five general steps)
 			k_block_sparse<1024, 6><<<dim3(1, S.nsys), dim3(1024), 0, S.sA>>>(S.M, S.rows, S.srows, g.j0, g.gb, 1, b, (const u64 *)half[0], S.st, S.died,
 			                                                                  S.panels, S.aux, S.pivcol, S.urow, S.blk_first + b, (const u64 *)S.wmask, S.ss());
-		hipExtLaunchKernelGGL(k_narrow_all, dim3((row_blocks + S.narrow_rpt - 1) / S.narrow_rpt, S.nsys), dim3(256), 0, S.sA, nullptr,
-		                      S.ext_events && !S.flag_sync ? S.evA[b] : nullptr, 0, (const u64 *)S.M, S.rows, S.srows, g.j0, b, (const u64 *)half[0],
-		                      (const SolveState *)S.st, (const int *)S.died, (const PanelAux *)S.aux, g.mset, S.impl->T, S.narrow_rpt,
-		                      S.flag_sync ? DoneSignal{ &S.sf->cnt_narrow, &S.sf->narrow_done, S.sync_base + b + 1 } : DoneSignal{}, S.ss());
+		hipExtLaunchKernelGGL(k_narrow_all, dim3((row_blocks + S.narrow_rpt - 1) / S.narrow_rpt, S.nsys), dim3(256), 0, S.sA, nullptr, done, 0,
+		                      (const u64 *)S.M, S.rows, S.srows, g.j0, b, (const u64 *)half[0], (const SolveState *)S.st, (const int *)S.died,
+		                      (const PanelAux *)S.aux, g.mset, S.impl->T, S.narrow_rpt, sig, S.ss());
 		HIPCHK(hipGetLastError());
-		if (S.flag_sync) return GF2BV_OK;
-		if (!S.ext_events) HIPCHK(hipEventRecord(S.evA[b], S.sA));
-		return GF2BV_OK;
-	}
-	if (fast_only && S.fused_narrow && S.nsys == 1) {
-		// search + narrow step in one launch: workgroup 0 searches, the others narrow each panel as soon as it is formed
-		// (single systems: a gang is throughput-bound, and its ~130 x nsys narrowing workgroups would hold their LDS for the whole
-		// search -- measured equal either way, 243 against 242 systems/s of 32768^2: gangs keep the two launches)
-		// at most ~128 narrowing workgroups: they stay resident for the whole search, and a CU that holds TWO of them (2 x 26 KiB
-		// of LDS) cannot take a bulk-update workgroup (133 of 160 KiB) until they end -- with 257 workgroups on 256 CUs there is
-		// always such a CU, and the pass whose launch lands just behind the search waits ~20 us for its last workgroup
-		// (tools/pass_rates.py: every fourth pass of the mid-range of a 65536^2 solve)
-		const int rpt = S.fused_rpt > 0 ? S.fused_rpt : (int)std::min<i64>(8, std::max<i64>(S.narrow_rpt, (row_blocks + 127) / 128));
-		hipExtLaunchKernelGGL(k_block_fast_narrow, dim3(1 + (row_blocks + rpt - 1) / rpt, S.nsys), dim3(256), 0, S.sA, nullptr,
-		                      S.ext_events && !S.flag_sync ? S.evA[b] : nullptr, 0, S.M, S.rows, S.srows, g.j0, g.gb, b, (const u64 *)half[0],
-		                      S.st, S.died, S.panels, S.aux, S.pivcol, S.urow, S.blk_first + b, S.Pfast, g.mset, S.impl->T, rpt,
-		                      S.flag_sync ? DoneSignal{ &S.sf->cnt_narrow, &S.sf->narrow_done, S.sync_base + b + 1 } : DoneSignal{}, S.ss());
-		HIPCHK(hipGetLastError());
-		if (S.flag_sync) return GF2BV_OK;       // (the launch announces narrow_done itself)
-		if (!S.ext_events) HIPCHK(hipEventRecord(S.evA[b], S.sA));
-		return GF2BV_OK;
-	}
-	if (fast_only) {
-		k_block_fast<<<dim3(1, S.nsys), dim3(256), 0, S.sA>>>(S.M, S.rows, S.srows, g.j0, g.gb, 1, b, (const u64 *)half[0], S.st, S.died,
-		                                                      S.panels, S.aux, S.pivcol, S.urow, S.blk_first + b, S.Pfast, S.ss());
-		hipExtLaunchKernelGGL(k_narrow_all, dim3((row_blocks + S.narrow_rpt - 1) / S.narrow_rpt, S.nsys), dim3(256), 0, S.sA, nullptr,
-		                      S.ext_events && !S.flag_sync ? S.evA[b] : nullptr, 0, (const u64 *)S.M, S.rows, S.srows, g.j0, b, (const u64 *)half[0],
-		                      (const SolveState *)S.st, (const int *)S.died, (const PanelAux *)S.aux, g.mset, S.impl->T, S.narrow_rpt,
-		                      S.flag_sync ? DoneSignal{ &S.sf->cnt_narrow, &S.sf->narrow_done, S.sync_base + b + 1 } : DoneSignal{}, S.ss());
-		HIPCHK(hipGetLastError());
-		if (S.flag_sync) return GF2BV_OK;       // (the narrow launch announces narrow_done itself)
-		if (!S.ext_events) HIPCHK(hipEventRecord(S.evA[b], S.sA));
 		return GF2BV_OK;
 	}
 	// dense blocks: all G panels from a few hundred candidate rows in one launch; the general steps behind it find the
@@ -1140,19 +1140,19 @@ int enqueue_block_panel(Solver &S, int b, bool fast_only = false, bool sparse = 
 		const int find_wgs = gf >= 0 ? (S.units + 3) / 4 : 0;
 		const unsigned wgs = (unsigned)find_wgs + (gp >= 0 ? (row_blocks + S.narrow_rpt - 1) / S.narrow_rpt : 0u);
 		// the block's last step carries the hand-off event as its own completion signal (no marker packet)
-		const bool ext = S.ext_events && !S.flag_sync && s == g.gb && b != S.nblocks - 1;
+		const bool ext = !S.flag_sync && s == g.gb && b != S.nblocks - 1;
 		hipExtLaunchKernelGGL(k_panel_step, dim3(wgs, S.nsys), dim3(256), 0, S.sA, nullptr, ext ? S.evA[b] : nullptr, 0,
 		                      S.M, S.rows, S.srows, g.j0, gp, gf, g.gb, colmask,
 		                      (const u64 *)half[s ? (s - 1) & 1 : 0], half[s & 1], S.st, S.died, S.fu, S.units, find_wgs,
 		                      S.panels, S.aux, S.pivcol, S.urow, g.mset,
-		                      gf == g.gb - 1 ? S.blk_first + b : (int *)nullptr, S.impl->T, S.sparse_mode, S.self_wait, S.narrow_rpt, b, S.ss());
+		                      gf == g.gb - 1 ? S.blk_first + b : (int *)nullptr, S.impl->T, kSparseByDensity, S.kn.self_wait_us * 100, S.narrow_rpt, b, S.ss());
 	}
 	if (b == S.nblocks - 1)
 		k_win_scatter<<<dim3((unsigned)((S.rows * g.gb + 255) / 256), S.nsys), dim3(256), 0, S.sA>>>(S.M, S.rows, S.srows, g.j0, g.gb, half[g.gb & 1], S.died, S.st, S.ss());
 	HIPCHK(hipGetLastError());
 	if (S.flag_sync) { int rc = panel_handover(S, b); if (rc) return rc; }
-	else if (!(S.ext_events && b != S.nblocks - 1)) HIPCHK(hipEventRecord(S.evA[b], S.sA));
-	if (S.dbg_sync & 1) HIPCHK(hipDeviceSynchronize());
+	else if (b == S.nblocks - 1) HIPCHK(hipEventRecord(S.evA[b], S.sA));
+	if (S.kn.debug_sync & 1) HIPCHK(hipDeviceSynchronize());
 	return GF2BV_OK;
 }
 
@@ -1195,7 +1195,7 @@ int enqueue_block_bulk(Solver &S, int b)
 		HIPCHK(hipEventRecord(S.evPrio[b], S.sB));      // "bulk of block b complete" (no update launch of this rank carries it)
 		S.waitPrio[b] = S.evPrio[b];
 	}
-	if (S.dbg_sync & 2) HIPCHK(hipDeviceSynchronize());
+	if (S.kn.debug_sync & 2) HIPCHK(hipDeviceSynchronize());
 	return GF2BV_OK;
 }
 
@@ -1276,7 +1276,7 @@ int enqueue_outer_prepare(Solver &S, hipStream_t st, int b0, int b1)
 	int *gprow = S.oprow + (size_t)((b0 / S.tl_K) % S.nlist) * GF2_OUTER_LISTS;
 	u64 *Tm = S.Tm + (size_t)((b0 / S.tl_K) % S.nlist) * ((size_t)GF2_KMAX * GF2_KMAX * GF2_GMAX * 64 * GF2_GMAX);
 	k_outer_prow<<<dim3(1, S.nsys), dim3(256), 0, st>>>(b0 * G, b1 - b0, S.panels, S.aux, gprow, S.ss());
-	if (!S.outer_chain)
+	if (!S.kn.outer_chain)
 		k_outer_trsm<4, true><<<dim3((unsigned)(npan / 4), S.nsys), dim3(256), 0, st>>>(S.M, S.rows, S.srows, b0 * G, npan, 0, S.panels, S.aux, S.mult,
 		                                                                               set_words, b0 % S.nsets, S.nsets, S.impl->T, Tm, S.ss());
 	HIPCHK(hipGetLastError());
@@ -1293,7 +1293,7 @@ int enqueue_outer_apply(Solver &S, hipStream_t st, int b0, int b1, i64 t_begin, 
 	const i64 set_words = (i64)G * mult_rows(S.rows);
 	int *gprow = S.oprow + (size_t)((b0 / S.tl_K) % S.nlist) * GF2_OUTER_LISTS;
 	const int npan = (b1 - b0) * G;
-	if (S.outer_chain) {
+	if (S.kn.outer_chain) {
 		const i64 g_begin = t_begin * TW / 4, ng = t_end * TW / 4 - g_begin;
 		k_outer_trsm<4, false><<<dim3((unsigned)ng, S.nsys), dim3(256), 0, st>>>(S.M, S.rows, S.srows, b0 * G, npan, (int)g_begin, S.panels, S.aux,
 		                                                                          S.mult, set_words, b0 % S.nsets, S.nsets, S.impl->T, (u64 *)nullptr, S.ss());
@@ -1305,7 +1305,6 @@ int enqueue_outer_apply(Solver &S, hipStream_t st, int b0, int b1, i64 t_begin, 
 	if (S.time_kernels) {
 		HIPCHK(pool().event(&ka, true)); HIPCHK(pool().event(&kb, true));
 		S.kev.push_back(ka); S.kev.push_back(kb);
-		if (!S.ext_events) HIPCHK(hipEventRecord(ka, st));
 	}
 	// items of a dense system: the kernel derives the true count from the alive bound and loops if there are more
 	const i64 est_lo = std::min<i64>(S.rows, (i64)b0 * 64 * G) & ~(i64)63, R64 = round_up(S.rows, 64);
@@ -1313,12 +1312,11 @@ int enqueue_outer_apply(Solver &S, hipStream_t st, int b0, int b1, i64 t_begin, 
 	static_assert((size_t)item_rows * 32 <= kOuterSlackBytes, "the slack behind the matrix covers an item");
 	const i64 nch = std::max<i64>(1, (R64 - est_lo + item_rows - 1) / item_rows);
 	const i64 wgs = std::min<i64>(nch * nt, (i64)1 << 30);
-	hipExtLaunchKernelGGL(k_update16k_wide, dim3((unsigned)wgs, S.nsys), dim3(1024), 0, st, S.ext_events ? ka : nullptr, S.ext_events ? kb : nullptr, 0,
+	hipExtLaunchKernelGGL(k_update16k_wide, dim3((unsigned)wgs, S.nsys), dim3(1024), 0, st, ka, kb, 0,
 	                      S.M, S.rows, S.srows, b1 - b0, (const int *)gprow, (const u64 *)S.mult,
 	                      set_words, b0 % S.nsets, S.nsets, (const int *)(S.blk_first + b0), (const int *)S.died, b1 * G, (int)t_begin, (int)nt, S.ss(), 1);
 	HIPCHK(hipGetLastError());
-	if (S.time_kernels && !S.ext_events) HIPCHK(hipEventRecord(kb, st));
-	if (S.dbg_sync & 2) HIPCHK(hipDeviceSynchronize());
+	if (S.kn.debug_sync & 2) HIPCHK(hipDeviceSynchronize());
 	return GF2BV_OK;
 }
 
@@ -1346,7 +1344,7 @@ int enqueue_forward(Solver &S)
 	// one-level schedule -- the matrix and the window buffer are exactly as that block needs.
 	bool optimistic = false;
 	SolveState hst{};
-	const bool may_probe = S.fast_blocks && S.optimistic && S.nsys == 1 && S.world == 1 && S.nblocks >= 8 && fast_block_possible(S, block_geom(S, 0));
+	const bool may_probe = S.kn.fast && S.optimistic && S.nsys == 1 && S.world == 1 && S.nblocks >= 8 && fast_block_possible(S, block_geom(S, 0));
 	auto fast_only_ok = [&](int blk) {
 		// rows left when the block starts: at most 64 leftover candidates sit below the bound besides the pivots found
 		return fast_block_possible(S, block_geom(S, blk)) && S.rows - (i64)blk * 64 * S.impl->G >= GF2_FAST_NC + 128;
@@ -1355,7 +1353,7 @@ int enqueue_forward(Solver &S)
 	// instead of the G + 1 general panel steps (one-level schedules only; the look-ahead of every block leaves the masks the next
 	// block's pool is taken from).  A block it cannot take poisons the panel path like a failed optimistic block: the host resumes
 	// there with the general steps for THAT block and goes on sparse behind it (three times at most, then general to the end).
-	const bool may_sparse = may_probe && S.sparse_fast && S.tl_K == 0;
+	const bool may_sparse = may_probe && S.kn.sparse_fast && S.tl_K == 0;
 	int general_only = -1;                      // (resume) this one block takes the general steps whatever the mode
 	auto sparse_ok = [&](int blk) { return S.sparse_on && blk != general_only && fast_block_possible(S, block_geom(S, blk)); };
 	// after a poisoned block pb: everything in flight drained, the plan cut back to what has run, the counters rebased
@@ -1445,7 +1443,7 @@ int enqueue_forward(Solver &S)
 			// inner elimination's bulk stream, idle at this point, and runs BESIDE the start of the pass proper instead of before it:
 			// it needs the previous pass complete (evBig; it used to follow it in stream order) and this panel's T; the pass proper
 			// needs T alone (disjoint tiles).  No new stream.
-			const bool side = S.outer_side && S.sB != so && S.sB != S.sA;
+			const bool side = S.kn.outer_side && S.sB != so && S.sB != S.sA;
 			if (side) {
 				HIPCHK(hipStreamWaitEvent(S.sB, S.evPanelDone, 0));
 				if (big_recorded) HIPCHK(hipStreamWaitEvent(S.sB, S.evBig, 0));
@@ -1471,7 +1469,7 @@ int enqueue_forward(Solver &S)
 	for (; b < S.nblocks; b++)
 		if ((rc = one_block(b))) return rc;
 	if ((rc = enqueue_forward_join(S))) return rc;
-	tr.mark("forward: all blocks submitted");          // (host side only: the device is still working; what follows waits for it)
+	tr.mark(S.kn, "forward: all blocks submitted");          // (host side only: the device is still working; what follows waits for it)
 	while (optimistic || S.sparse_on) {
 		HIPCHK(hipMemcpyAsync(&hst, S.st, sizeof hst, hipMemcpyDeviceToHost, S.sA));
 		HIPCHK(hipStreamSynchronize(S.sA));
@@ -1553,8 +1551,7 @@ int enqueue_backward_parity(Solver &S, const std::vector<int> &ycols_host)
 	// Round 4: from sixteen groups (16384 columns) up the diagonal blocks are inverted up front (k_bs_inv, all groups in one launch, ~90 us) and the
 	// serial walk of a link (k_bs_near, 12 us) becomes a matrix-vector product (k_bs_near2, ~4 us).  GF2BV_BS_INV=0 / 1: never / always.
 	const int ngroups = (S.npanels + GF2_BSG - 1) / GF2_BSG;
-	bool inv = ngroups >= 16;
-	if (const char *e = getenv("GF2BV_BS_INV")) inv = atoi(e) != 0 && ngroups >= 1;
+	const bool inv = S.kn.bs_inv >= 0 ? S.kn.bs_inv != 0 && ngroups >= 1 : ngroups >= 16;
 	if (inv) {
 		HIPCHK(pool().alloc((void **)&S.Minv, sizeof(u64) * (size_t)ngroups * 16 * 64 * 16, S.device));
 		static std::mutex mu;
@@ -1625,7 +1622,7 @@ int enqueue_backward_gang(Solver &S)
 // per panel whatever the dimension).  GF2BV_YSWEEP sends every count to the sweeps (the general path, for cross-checking).
 int enqueue_backsub(Solver &S, const std::vector<int> &ycols)
 {
-	if ((i64)ycols.size() <= GF2_BS_MAXRHS && !getenv("GF2BV_YSWEEP")) return enqueue_backward_parity(S, ycols);
+	if ((i64)ycols.size() <= GF2_BS_MAXRHS && !S.kn.ysweep) return enqueue_backward_parity(S, ycols);
 	return enqueue_backward(S, ycols);
 }
 
@@ -1633,10 +1630,10 @@ int solver_enqueue(Solver &S)
 {
 	Trace tr;
 	int rc = solver_alloc(S);
-	tr.mark("solver_alloc");
+	tr.mark(S.kn, "solver_alloc");
 	if (rc) return rc;
 	rc = enqueue_forward(S);
-	tr.mark("enqueue_forward");
+	tr.mark(S.kn, "enqueue_forward");
 	if (rc) return rc;
 	if (S.mode == GF2BV_MODE_SINGLE) return enqueue_backsub(S, { (int)S.cols });
 	return GF2BV_OK;
@@ -1744,7 +1741,7 @@ int finish_end(Solver &S, gf2bv_result **out)
 	Trace tr;
 	HIPCHK(hipStreamSynchronize(S.sA));
 	HIPCHK(hipStreamSynchronize(S.sB));
-	tr.mark("finish: sync");
+	tr.mark(S.kn, "finish: sync");
 	int rc = handover_verdict(S);
 	if (rc) return rc;
 	const SolveState &hst = S.hst;
@@ -1753,7 +1750,7 @@ int finish_end(Solver &S, gf2bv_result **out)
 	std::unique_ptr<gf2bv_result> R = new_result(!hst.inconsistent, S.cols, S.hpiv.data(), hst.rank, S.hout.data() + (size_t)((S.ny - 1) * cwx));
 	if (!hst.inconsistent && S.mode == GF2BV_MODE_AFFINE_SPACE) R->basis = basis_rows(S.hout.data(), S.cw, S.free_order, R->dim);
 	fill_stats(S, R.get());
-	tr.mark("finish: result");
+	tr.mark(S.kn, "finish: result");
 	*out = R.release();
 	return GF2BV_OK;
 }
@@ -1869,8 +1866,7 @@ int solve_gang(Solver &S, gf2bv_result **out)
 		if (rc) return rc;
 	}
 	if (S.mode == GF2BV_MODE_SINGLE) {
-		const bool per_system = !S.gang_bs;      // (GF2BV_GANG_BS=0, A/B: one chain per system, as rounds 1-3)
-		if (per_system)
+		if (!S.kn.gang_bs)      // (A/B: one chain per system, as rounds 1-3)
 			for (int s = 0; s < S.nsys; s++) {
 				rc = enqueue_backward_parity(V[s], { (int)S.cols });
 				if (rc) return rc;
@@ -1905,7 +1901,7 @@ int solve_gang(Solver &S, gf2bv_result **out)
 }
 
 // Gang size for nsys same-shape systems (free_b: free device memory, < 0 = ask the current device).
-i64 pick_gang(i64 nsys, i64 rows, i64 cols, i64 free_bytes = -1)
+i64 pick_gang(const Knobs &kn, i64 nsys, i64 rows, i64 cols, i64 free_bytes = -1)
 {
 	// gang size: ~4.5 GiB of working matrices per gang (32768^2: 32 systems -- round 4: 192 x 32768^2 run 3.22 ms per system in gangs
 	// of 32 against 3.22-3.32 in gangs of 24, and 512 systems are 16 equal gangs instead of 21 + a part gang; 4096^2: 64), at
@@ -1927,7 +1923,7 @@ i64 pick_gang(i64 nsys, i64 rows, i64 cols, i64 free_bytes = -1)
 	}
 	// whole multiples of 8 systems: the bulk update of such a gang keeps every system on ONE XCD (k_update16: xcd_nsys)
 	if (gang >= 8) gang = gang / 8 * 8;
-	if (const char *e = getenv("GF2BV_GANG")) { int v = atoi(e); if (v >= 1) gang = v; }
+	if (kn.gang >= 1) gang = kn.gang;
 	gang = std::max<i64>(1, std::min<i64>(gang, nsys));
 	{
 		size_t free_b = 0, total_b = 0;
@@ -1976,11 +1972,9 @@ int run_on_threads(int n, F &&fn)
 // bulk update runs throughout a gang's elimination (its launches are in flight 89 % of the wall time), there is no idle tail
 // to fill, and part gangs only make smaller launches.
 template <class Stage>
-int run_gangs(int device, i64 nsys, i64 gang, hipEvent_t ready, size_t worker_bytes, gf2bv_result **out, Stage &&stage)
+int run_gangs(const Knobs &kn, int device, i64 nsys, i64 gang, hipEvent_t ready, size_t worker_bytes, gf2bv_result **out, Stage &&stage)
 {
 	const i64 ngangs = (nsys + gang - 1) / gang;
-	int nthreads = 2;
-	if (const char *e = getenv("GF2BV_BATCH_THREADS")) { int v = atoi(e); if (v >= 1) nthreads = std::min(v, 16); }
 	std::atomic<i64> next_gang{0};
 	auto work = [&]() -> int {
 		struct Mine {
@@ -2016,7 +2010,7 @@ int run_gangs(int device, i64 nsys, i64 gang, hipEvent_t ready, size_t worker_by
 		}
 		return GF2BV_OK;
 	};
-	const int rc = run_on_threads((int)std::min<i64>(ngangs, nthreads), [&](int) {
+	const int rc = run_on_threads((int)std::min<i64>(ngangs, kn.batch_threads), [&](int) {
 		const int r = work();
 		if (r) next_gang.store(ngangs);
 		return r;
@@ -2127,11 +2121,10 @@ struct StagePool {
 };
 StagePool &stage_pool() { static StagePool *p = new StagePool(); return *p; }
 
-bool small_eligible(i64 rows, i64 cols)
+bool small_eligible(const Knobs &kn, i64 rows, i64 cols)
 {
-	if (const char *e = getenv("GF2BV_SMALL")) if (atoi(e) == 0) return false;
 	const i64 wt = (cols + 1 + 63) / 64;
-	return cols <= GF2_SMALL_MAXCOLS && rows <= GF2_SMALL_MAXROWS && (rows + 512) * small_pitch(wt) <= GF2_SMALL_LDS_WORDS;
+	return kn.small && cols <= GF2_SMALL_MAXCOLS && rows <= GF2_SMALL_MAXROWS && (rows + 512) * small_pitch(wt) <= GF2_SMALL_LDS_WORDS;
 }
 
 int small_stage(SmallStage &G, size_t in_bytes, size_t out_bytes)
@@ -2153,7 +2146,7 @@ int small_stage(SmallStage &G, size_t in_bytes, size_t out_bytes)
 	return GF2BV_OK;
 }
 
-int small_solve(const MatrixInput &in, i64 rows, i64 cols, int mode, int device, hipStream_t stream, gf2bv_result **out)
+int small_solve(const Knobs &kn, const MatrixInput &in, i64 rows, i64 cols, int mode, int device, hipStream_t stream, gf2bv_result **out)
 {
 	const auto t_begin = std::chrono::steady_clock::now();
 	const i64 wt = (cols + 1 + 63) / 64, cw = (cols + 63) / 64;
@@ -2161,7 +2154,6 @@ int small_solve(const MatrixInput &in, i64 rows, i64 cols, int mode, int device,
 	const size_t head = 16 + 4 * (size_t)((cols + 1) & ~(i64)1);
 	const size_t res_bytes = head + 8 * (size_t)cw * (1 + (want_basis ? (size_t)cols : 0));
 	const size_t out_bytes = res_bytes + 64;                 // (+ 8 phase counters of the probe, GF2BV_SMALL_PROBE=1)
-	const bool probe = getenv("GF2BV_SMALL_PROBE") != nullptr;
 	size_t in_bytes = 0;
 	i64 ndig = 0;
 	if (in.h_off) { ndig = in.h_off[rows]; in_bytes = sizeof(i64) * (size_t)(rows + 1) + sizeof(uint32_t) * (size_t)std::max<i64>(ndig, 1); }
@@ -2182,8 +2174,7 @@ int small_solve(const MatrixInput &in, i64 rows, i64 cols, int mode, int device,
 	const i64 *d_off = nullptr;
 	// inputs up to 32 KiB: no copy at all -- the kernel reads the pinned staging buffer over the link (two batched round trips;
 	// 2-6 us less than a host-to-device copy in front of the launch: profiles/r04_small.txt).  GF2BV_SMALL_ZC=0 / 1 forces either.
-	bool zero_copy = in_bytes <= ((size_t)32 << 10);
-	if (const char *e = getenv("GF2BV_SMALL_ZC")) zero_copy = atoi(e) != 0;
+	const bool zero_copy = kn.small_zc >= 0 ? kn.small_zc != 0 : in_bytes <= ((size_t)32 << 10);
 	if (in_bytes) {
 		if (!zero_copy) HIPCHK(pool().alloc(&back.d_in, in_bytes, device));
 		char *d_base = zero_copy ? G.h_in : (char *)back.d_in;
@@ -2213,11 +2204,11 @@ int small_solve(const MatrixInput &in, i64 rows, i64 cols, int mode, int device,
 	}
 	memset(G.h_out, 0, 16);
 	k_small_solve<NT><<<dim3(1), dim3(NT), lds, st>>>(d_src, d_stride, d_dig, d_off, in.bpd, (int)rows, (int)cols, want_basis ? 1 : 0, (unsigned *)G.h_out,
-	                                                   probe ? (unsigned long long *)(G.h_out + res_bytes) : nullptr);
+	                                                   kn.small_probe ? (unsigned long long *)(G.h_out + res_bytes) : nullptr);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipStreamSynchronize(st));
 	const unsigned *ho = (const unsigned *)G.h_out;
-	if (probe) {
+	if (kn.small_probe) {
 		const unsigned long long *p = (const unsigned long long *)(G.h_out + res_bytes);
 		fprintf(stderr, "[gf2bv small %lld x %lld] us: load %.1f candidates %.1f wavefront0 %.1f candidate rows %.1f tables %.1f all rows %.1f read-out %.1f; passes %llu\n",
 		        (long long)rows, (long long)cols, p[0] / 100.0, p[1] / 100.0, p[2] / 100.0, p[3] / 100.0, p[4] / 100.0, p[5] / 100.0, p[6] / 100.0, p[7]);
@@ -2575,6 +2566,7 @@ int factor_solve(gf2bv_factor *h, const u64 *rhs, bool on_device, i64 nrhs, i64 
 	std::lock_guard<std::mutex> lk(h->mu);
 	const auto t0 = std::chrono::steady_clock::now();
 	Solver &S = h->S;
+	S.kn.refresh();
 	HIPCHK(hipSetDevice(h->device));
 	const i64 rw = h->rw, C = kFactorSlots;
 	Scratch scratch;
@@ -2775,18 +2767,11 @@ int append_chunk(gf2bv_factor *h, i64 r0, i64 k, const AppendBufs &B, double ms[
 	return GF2BV_OK;
 }
 
-// times of the phases of the last append (GF2BV_TRACE prints them): grow, reduce, new pivots, merge, basis
-void append_trace(const double ms[5], i64 k)
-{
-	if (!getenv("GF2BV_TRACE")) return;
-	fprintf(stderr, "[gf2bv trace] append %lld rows: grow %.3f reduce %.3f new %.3f merge %.3f basis %.3f ms\n", (long long)k, ms[0], ms[1],
-	        ms[2], ms[3], ms[4]);
-}
-
 int factor_append(gf2bv_factor *h, const MatrixInput &in, i64 k, hipStream_t stream)
 {
 	std::lock_guard<std::mutex> lk(h->mu);
 	Solver &S = h->S;
+	S.kn.refresh();
 	HIPCHK(hipSetDevice(h->device));
 	const i64 rows = h->rows, cols = h->cols, rows2 = rows + k, rw2 = (rows2 + 63) / 64;
 	const bool grow = rows2 > h->cap_rows;
@@ -2903,7 +2888,8 @@ int factor_append(gf2bv_factor *h, const MatrixInput &in, i64 k, hipStream_t str
 		const std::string why = g_err;
 		return fail(GF2BV_ERR_HIP, (std::string(kFailedHandle) + ": " + why).c_str());
 	}
-	append_trace(ms, k);
+	if (S.kn.trace)       // times of the append's phases
+		fprintf(stderr, "[gf2bv trace] append %lld rows: grow %.3f reduce %.3f new %.3f merge %.3f basis %.3f ms\n", (long long)k, ms[0], ms[1], ms[2], ms[3], ms[4]);
 	return GF2BV_OK;
 }
 
@@ -2920,7 +2906,7 @@ int factor_copy(gf2bv_factor *h, gf2bv_factor **out)
 	c->cap_rows = h->cap_rows; c->hp = h->hp; c->urow = h->urow;
 	Solver &D = c->S;
 	D = S;                            // the scalars and host vectors; every resource below is the copy's own
-	D.M = nullptr; D.tmp_src = nullptr; D.Ybuf = nullptr; D.Minv = nullptr; D.arena = nullptr; D.Y = nullptr; D.ycols = nullptr;
+	D.M = nullptr; D.tmp_src = nullptr; D.Minv = nullptr; D.arena = nullptr; D.Y = nullptr; D.ycols = nullptr;
 	D.out = nullptr; D.rhs_bad = nullptr; D.src = nullptr;
 	D.sA = D.sB = D.sC = nullptr; D.own_sA = D.own_sB = false;
 	D.ev0 = D.ev1 = D.ev2 = D.ev3 = D.evx = nullptr;
@@ -2997,7 +2983,7 @@ int gf2bv_solve_device(void *d_aug, int64_t rows, int64_t cols, int64_t stride_w
 	int rc = check_matrix_input(in, rows, cols, mode);
 	if (!rc) rc = check_device(device);
 	if (rc) return rc;
-	if (small_eligible(rows, cols) && !time_kernels) return small_solve(in, rows, cols, mode, device, (hipStream_t)stream, out);
+	if (const Knobs kn = Knobs::read(Knobs::kSmall); small_eligible(kn, rows, cols) && !time_kernels) return small_solve(kn, in, rows, cols, mode, device, (hipStream_t)stream, out);
 	Solver S;
 	S.t_begin = std::chrono::steady_clock::now();
 	S.device = device;
@@ -3027,7 +3013,8 @@ int gf2bv_solve_batch_device(void *d_aug, int64_t nsys, int64_t sys_stride_words
 	// Independent systems of one shape run as GANGS: the forward elimination of `gang` systems is one set
 	// of launches (blockIdx.y = system), so the latency-bound panel path and the host's ~3500 launches
 	// per elimination are shared by the whole gang and the bulk updates of all its systems fill the chip.
-	const i64 gang = pick_gang(nsys, rows, cols);
+	const Knobs kn = Knobs::read();
+	const i64 gang = pick_gang(kn, nsys, rows, cols);
 	// Ordering contract: the matrices are whatever `stream` (the caller's stream, NULL = the null stream) has
 	// produced when this call is made.  The gangs run on the library's own non-blocking streams, which are not
 	// ordered against any other stream by themselves: each waits for an event recorded on `stream` here.
@@ -3037,7 +3024,7 @@ int gf2bv_solve_batch_device(void *d_aug, int64_t nsys, int64_t sys_stride_words
 	} ready;
 	HIPCHK(pool().event(&ready.ev, false));
 	HIPCHK(hipEventRecord(ready.ev, (hipStream_t)stream));
-	return run_gangs(device, nsys, gang, ready.ev, 0, out, [&](Solver &S, i64 s0, int, void *) -> int {
+	return run_gangs(kn, device, nsys, gang, ready.ev, 0, out, [&](Solver &S, i64 s0, int, void *) -> int {
 		S.src = (const u64 *)d_aug + s0 * sys_stride_words;
 		S.src_sys_words = sys_stride_words;
 		S.rows = rows; S.cols = cols; S.stride = stride_words; S.mode = mode;
@@ -3057,7 +3044,7 @@ int gf2bv_solve_words(const uint64_t *aug, int64_t rows, int64_t cols, int64_t s
 	int rc = check_matrix_input(in, rows, cols, mode);
 	if (!rc) rc = check_device(device);
 	if (rc) return rc;
-	if (small_eligible(rows, cols)) return small_solve(in, rows, cols, mode, device, nullptr, out);
+	if (const Knobs kn = Knobs::read(Knobs::kSmall); small_eligible(kn, rows, cols)) return small_solve(kn, in, rows, cols, mode, device, nullptr, out);
 	const i64 wt = (cols + 1 + 63) / 64;
 	Solver S;
 	S.t_begin = std::chrono::steady_clock::now();
@@ -3122,12 +3109,13 @@ int gf2bv_solve_batch_digits(const uint32_t *digits, const int64_t *digit_off, i
 	HIPCHK(hipMemcpyAsync(G.off, digit_off, sizeof(i64) * (nrows_all + 1), hipMemcpyHostToDevice, G.st));
 	HIPCHK(pool().event(&G.ready, false));
 	HIPCHK(hipEventRecord(G.ready, G.st));
-	const i64 gang = pick_gang(nsys, rows, cols);
+	const Knobs kn = Knobs::read();
+	const i64 gang = pick_gang(kn, nsys, rows, cols);
 	const i64 ngangs = (nsys + gang - 1) / gang;
 	i64 max_dig = 1;
 	for (i64 q = 0; q < ngangs; q++)
 		max_dig = std::max<i64>(max_dig, digit_off[std::min<i64>(nsys, (q + 1) * gang) * rows] - digit_off[q * gang * rows]);
-	return run_gangs(device, nsys, gang, G.ready, sizeof(uint32_t) * max_dig, out, [&](Solver &S, i64 s0, int ns, void *buf) -> int {
+	return run_gangs(kn, device, nsys, gang, G.ready, sizeof(uint32_t) * max_dig, out, [&](Solver &S, i64 s0, int ns, void *buf) -> int {
 		uint32_t *dig = (uint32_t *)buf;
 		const i64 d0 = digit_off[s0 * rows], nd = digit_off[(s0 + ns) * rows] - d0;
 		if (nd) HIPCHK(hipMemcpyAsync(dig, digits + d0, sizeof(uint32_t) * nd, hipMemcpyHostToDevice, S.sA));
@@ -3177,7 +3165,7 @@ int gf2bv_solve_digits(const uint32_t *digits, const int64_t *digit_off, int bit
 	int rc = check_matrix_input(in, rows, cols, mode);
 	if (!rc) rc = check_device(device);
 	if (rc) return rc;
-	if (small_eligible(rows, cols)) return small_solve(in, rows, cols, mode, device, nullptr, out);
+	if (const Knobs kn = Knobs::read(Knobs::kSmall); small_eligible(kn, rows, cols)) return small_solve(kn, in, rows, cols, mode, device, nullptr, out);
 	Solver S;
 	S.t_begin = std::chrono::steady_clock::now();
 	S.device = device;
@@ -3631,6 +3619,7 @@ int gf2bv_slab_solve(gf2bv_slab *h, gf2bv_result **out)
 	if (!h || !out) return fail(GF2BV_ERR_ARG, "null pointer");
 	*out = nullptr;
 	Solver &S = h->S;
+	S.kn.refresh();
 	HIPCHK(hipSetDevice(S.device));
 	int rc = enqueue_check_rhs(S);
 	if (rc == GF2BV_OK) rc = enqueue_backward_parity(S, { (int)S.cols });
@@ -3923,8 +3912,7 @@ void gf2bv_host_free(void *h_ptr)
 		P.live.erase(it);
 		size_t kept = 0;
 		for (const auto &b : P.idle) kept += b.bytes;
-		size_t cap_mb = 4608;
-		if (const char *e = getenv("GF2BV_HOST_POOL_MB")) { long v = atol(e); if (v >= 0) cap_mb = (size_t)v; }
+		const size_t cap_mb = (size_t)Knobs::read(Knobs::kHostPool).host_pool_mb;
 		if (P.idle.size() < 4 && kept + bytes <= (cap_mb << 20)) P.idle.push_back({ h_ptr, bytes });
 		else drop = h_ptr;
 	}
@@ -3949,7 +3937,18 @@ int64_t gf2bv_host_pool_trim(void)
 int64_t gf2bv_plan_gang(int64_t nsys, int64_t rows, int64_t cols, int64_t free_bytes)
 {
 	if (nsys <= 0 || rows <= 0 || cols <= 0 || free_bytes < 0) return 0;
-	return pick_gang(nsys, rows, cols, free_bytes);
+	return pick_gang(Knobs::read(), nsys, rows, cols, free_bytes);
+}
+
+// The environment switches as a per-call entry would parse them now, one NAME=value line each (see Knobs); no device is touched.
+int gf2bv_knob_dump(char *buf, int64_t n)
+{
+	return catching([&]() -> int {
+	const std::string s = Knobs::read().dump();
+	if (!buf || (int64_t)s.size() >= n) return fail(GF2BV_ERR_ARG, "null pointer, or a buffer too small for the knob dump");
+	memcpy(buf, s.c_str(), s.size() + 1);
+	return GF2BV_OK;
+	});
 }
 
 int64_t gf2bv_pool_trim(int device)

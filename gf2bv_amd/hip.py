@@ -44,6 +44,7 @@ EXPORTS = [
     "gf2bv_stream_ceiling_device", "gf2bv_lds_clock_device", "gf2bv_kernel_resources",
     "gf2bv_device_alloc", "gf2bv_device_free", "gf2bv_device_upload", "gf2bv_device_download",
     "gf2bv_pool_trim", "gf2bv_pool_idle_bytes", "gf2bv_host_alloc", "gf2bv_host_free", "gf2bv_host_pool_trim", "gf2bv_plan_gang",
+    "gf2bv_knob_dump",
 ]
 
 
@@ -168,6 +169,7 @@ def lib():
         L.gf2bv_host_pool_trim.restype = i64
         L.gf2bv_plan_gang.argtypes = [i64, i64, i64, i64]
         L.gf2bv_plan_gang.restype = i64
+        L.gf2bv_knob_dump.argtypes = [ctypes.c_char_p, i64]
         L.gf2bv_pool_trim.argtypes = [i32]
         L.gf2bv_pool_trim.restype = i64
         L.gf2bv_pool_idle_bytes.argtypes = [i32]
@@ -624,6 +626,14 @@ def kernel_resources(device: int = 0) -> dict:
 def pool_trim(device: int = 0) -> int:
     """Return every idle buffer of the library's pool on `device` to the device; bytes freed (gf2bv_pool_trim)."""
     return int(lib().gf2bv_pool_trim(device))
+
+
+def knobs() -> dict:
+    """The GF2BV_* environment switches as the library parses them now (gf2bv_knob_dump; DESIGN.md, "Environment switches"):
+    name -> value as text, after defaults and clamps; "unset" where an unset variable leaves the choice to the solve.  No GPU needed."""
+    buf = ctypes.create_string_buffer(4096)
+    _check(lib().gf2bv_knob_dump(buf, len(buf)))
+    return dict(line.split("=", 1) for line in buf.value.decode().splitlines())
 
 
 def host_pool_trim() -> int:

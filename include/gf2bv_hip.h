@@ -17,7 +17,8 @@
  * the last-error string, which is thread-local, and a thread-safe pool that recycles idle
  * device buffers, streams and events between calls (small buffers up to 512 MiB in total,
  * plus up to six large working buffers per device, at most a sixth of the device's memory and
- * never more than 48 GiB; GF2BV_KEEP_BIG=0 in the environment keeps none; gf2bv_pool_trim()
+ * never more than 48 GiB; GF2BV_KEEP_BIG=0 in the environment keeps none (every GF2BV_* variable the
+ * library reads is listed in DESIGN.md, "Environment switches"); gf2bv_pool_trim()
  * returns all of them to the device, and an allocation the device refuses -- the library's own or
  * gf2bv_device_alloc -- frees them and is repeated once).  Matches the reference releasing the GIL around the
  * whole factor/solve/kernel section (_internal.c:429-492).
@@ -381,7 +382,7 @@ int gf2bv_device_download(int device, void *h_dst, const void *d_src, int64_t by
 /* Page-locked host staging for bindings that assemble their input on the host (the CPython shim gathers every equation's digit
  * array -- gf2bv/_internal.c:403-426 walks them bit by bit instead -- into ONE buffer before gf2bv_solve_digits): the
  * host-to-device copy out of such a buffer is a single DMA, and the buffers are recycled between calls (up to four idle ones,
- * GF2BV_HOST_POOL_MB MiB in all, default 4608; gf2bv_host_pool_trim frees the idle ones and returns their bytes).  Any host
+ * GF2BV_HOST_POOL_MB MiB in all, default 4608 -- DESIGN.md, "Environment switches"; gf2bv_host_pool_trim frees the idle ones and returns their bytes).  Any host
  * pointer remains valid input for every entry point; this is an optimisation, not a requirement. */
 int  gf2bv_host_alloc(int64_t bytes, void **h_ptr);
 void gf2bv_host_free(void *h_ptr);
@@ -397,6 +398,10 @@ int64_t gf2bv_pool_idle_bytes(int device);
 /* The gang size gf2bv_solve_batch_* would choose for `nsys` systems of rows x cols with `free_bytes` of device memory free: a pure
  * function, no device is touched (bench.py --dry-run-ranks: every rank's plan of the multi-GPU batch job, testable without GPUs). */
 int64_t gf2bv_plan_gang(int64_t nsys, int64_t rows, int64_t cols, int64_t free_bytes);
+/* The GF2BV_* environment switches as a solve entered now would parse them ("Environment switches"): one "NAME=value\n"
+ * line per variable into buf (n bytes, NUL-terminated), the value after defaults and clamps, "unset" where a variable that is not
+ * set leaves the choice to the solve.  No device is touched.  GF2BV_ERR_ARG when buf is null or too small (2048 bytes suffice). */
+int gf2bv_knob_dump(char *buf, int64_t n);
 
 #ifdef __cplusplus
 }
