@@ -900,6 +900,54 @@ PyObject *py_m4ri_solve_packed(PyObject *, PyObject *const *args, Py_ssize_t nar
 	return result_to_py(res, mode, device);
 }
 
+// m4ri_solve_quad_packed(lin, term_off, ta, tb, n_lin, rows, mode[, device]) -> None | int | AffineSpace.
+// New entry (no counterpart in the reference): a quadratic system kept FACTORED -- per equation a linear form and products of two
+// linear forms over the n_lin + 1 bits of the unlinearised unknowns (gf2bv_hip.h, "quadratic expansion") -- is expanded into the
+// linearised matrix on the device and solved there; no equation int over the n_lin(n_lin-1)/2 product unknowns exists on the host.
+// lin: rows_live x Wl 64-bit words, term_off: rows_live + 1 int64, ta / tb: term_off[-1] x Wl words each (C-contiguous buffers,
+// Wl = ceil((n_lin + 1) / 64)); rows >= rows_live: the row count the solver sees (zero rows are added on the device).  Same result
+// types as m4ri_solve over n_lin + n_lin(n_lin-1)/2 columns.
+PyObject *py_m4ri_solve_quad_packed(PyObject *, PyObject *const *args, Py_ssize_t nargs)
+{
+	if (nargs != 7 && nargs != 8) { PyErr_SetString(PyExc_TypeError, "m4ri_solve_quad_packed requires 7 arguments"); return nullptr; }
+	int device = default_device();
+	if (nargs == 8 && !parse_device(args[7], &device)) return nullptr;
+	const Py_ssize_t n = PyLong_AsSsize_t(args[4]), rows = PyLong_AsSsize_t(args[5]);
+	if ((n == -1 || rows == -1) && PyErr_Occurred()) return nullptr;
+	if (n < 1 || n > 65535) { PyErr_SetString(PyExc_ValueError, "n_lin must be 1..65535"); return nullptr; }
+	const Py_ssize_t wl = (n + 1 + 63) / 64;
+	const long mode = PyLong_AsLong(args[6]);
+	if (mode == -1 && PyErr_Occurred()) return nullptr;
+	Py_buffer view[4];
+	int got = 0;
+	for (; got < 4; got++)
+		if (PyObject_GetBuffer(args[got], &view[got], PyBUF_C_CONTIGUOUS) != 0) break;
+	const char *bad = nullptr;
+	if (got == 4) {
+		const Py_ssize_t live = view[0].len / (wl * 8), nterms = view[2].len / (wl * 8);
+		const int64_t *off = static_cast<const int64_t *>(view[1].buf);
+		if (view[0].len != live * wl * 8) bad = "lin must hold whole rows of ceil((n_lin + 1) / 64) 64-bit words";
+		else if (view[1].len != (live + 1) * 8) bad = "term_off must hold one int64 per row of lin and one more";
+		else if (view[2].len != nterms * wl * 8 || view[3].len != view[2].len) bad = "ta and tb must hold the same number of whole operands";
+		else if (off[live] != nterms) bad = "term_off must end at the number of operands in ta";
+		else if (rows < live) bad = "rows must be at least the rows of lin";
+		if (bad) PyErr_SetString(PyExc_ValueError, bad);
+		else {
+			gf2bv_result *res = nullptr;
+			int rc;
+			Py_BEGIN_ALLOW_THREADS
+			rc = gf2bv_solve_quad_terms(static_cast<const uint64_t *>(view[0].buf), off, static_cast<const uint64_t *>(view[2].buf),
+			                            static_cast<const uint64_t *>(view[3].buf), live, rows, n, (int)mode, device, &res);
+			Py_END_ALLOW_THREADS
+			for (int k = 0; k < 4; k++) PyBuffer_Release(&view[k]);
+			if (rc != GF2BV_OK) return raise_rc(rc, "solve");
+			return result_to_py(res, mode, device);
+		}
+	}
+	for (int k = 0; k < got; k++) PyBuffer_Release(&view[k]);
+	return nullptr;
+}
+
 // m4ri_solve_many(list_of_equation_lists, cols, mode[, devices]) -> list of (None | int | AffineSpace).
 // New entry (no counterpart in the reference): independent systems of one shape -- one per output
 // bit / per instance in the recovery examples -- are solved as lock-step gangs by one call; every
@@ -1394,6 +1442,8 @@ PyMethodDef module_methods[] = {
 	 "m4ri_solve(equations, cols, mode, device=None)\n--\n\nSolve the linear system on the MI355X; None when inconsistent."},
 	{"m4ri_solve_packed", FAST(py_m4ri_solve_packed), METH_FASTCALL,
 	 "m4ri_solve_packed(buffer, rows, words, cols, mode, device=None)\n--\n\nm4ri_solve on equations already packed as rows x words 64-bit words (equation-int bit order)."},
+	{"m4ri_solve_quad_packed", FAST(py_m4ri_solve_quad_packed), METH_FASTCALL,
+	 "m4ri_solve_quad_packed(lin, term_off, ta, tb, n_lin, rows, mode, device=None)\n--\n\nm4ri_solve on a quadratic system kept factored (linear forms and products of two linear forms, packed 64-bit words): expanded into the linearised matrix on the GPU."},
 	{"m4ri_solve_rhs", FAST(py_m4ri_solve_rhs), METH_FASTCALL,
 	 "m4ri_solve_rhs(equations, cols, mode, rhs, device=None)\n--\n\nSolve one coefficient matrix against every right-hand side in rhs (bit r = affine term of equation r) with one elimination; list of m4ri_solve results."},
 	{"m4ri_factor", FAST(py_m4ri_factor), METH_FASTCALL,

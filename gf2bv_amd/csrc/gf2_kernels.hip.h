@@ -4755,3 +4755,99 @@ k_quad_check(const u64 *__restrict__ E, i64 m, int R, const u64 *__restrict__ ca
 		}
 	}
 }
+
+
+// ==========================================================================================
+// QUADRATIC EXPANSION: factored quadratic equations -> the linearised rows the solver takes
+// ==========================================================================================
+// (host side: gf2bv_quad_expand_device in gf2_solver.hip; the front-end that keeps equations factored: gf2bv_amd/packed.py,
+// DESIGN.md section 7)
+//
+// Row r is e = lin[r] ^ XOR_t mul(ta[t], tb[t]), t in term_off[r] .. term_off[r + 1], every operand a linear form of Wl words in the
+// equation-int order (bit 0 constant, bit 1 + g unknown g < n), and mul is QuadraticSystem._mul_bit: constant and linear bits
+// a & b, pair (i, j), j < i, present iff a_i b_j ^ a_j b_i.  The output is the C-ABI row: column c < n unknown c, column
+// n + i(i-1)/2 + j pair (i, j), column cols = n + n(n-1)/2 the constant, everything behind it zero.
+// For a fixed i the pairs (i, 0 .. i-1) are one run of i consecutive columns equal to (a_i ? b[0..i) : 0) ^ (b_i ? a[0..i) : 0),
+// so a 64-bit output word is put together from whole runs: 64-bit windows of the operands (two LDS words and a funnel shift
+// each), two runs per word once i >= 64 and up to eleven in the first words of the pair block.
+// Work split: one workgroup per row at a time (grid-stride over the rows), the row's operands in LDS once, every lane forming
+// two consecutive output words per step and storing them as 16 bytes, consecutive lanes consecutive 16 bytes: each output word
+// has one writer, no atomics.  A row with more than `tch` products takes several passes (the later ones XOR into what the
+// same lane stored before).  Rows >= rows_live are written as zeros (the padding up to rows >= cols).
+// LDS: (1 + 2 tch) x Wl words (dynamic).
+__device__ __forceinline__ u64 qx_window(const u64 *x, int Wl, i64 q)      // bits q .. q + 63 of an operand (zero past its end)
+{
+	const int w = (int)(q >> 6), s = (int)(q & 63);
+	const u64 lo = w < Wl ? x[w] : 0, hi = w + 1 < Wl ? x[w + 1] : 0;
+	return s ? (lo >> s) | (hi << (64 - s)) : lo;
+}
+__device__ __forceinline__ u64 qx_low(i64 len) { return len >= 64 ? ~0ull : (1ull << len) - 1; }
+
+// columns c0 .. c0 + 63 of a row: what nt products (operands A[t], B[t]) contribute, and with `first` the linear part too
+__device__ __forceinline__ u64 qx_word(const u64 *lin, const u64 *A, const u64 *B, int nt, int Wl, i64 n, i64 cols, i64 c0, bool first)
+{
+	u64 acc = 0;
+	if (c0 < n) {                                                  // the linear unknowns: column c = bit c + 1
+		u64 v = first ? qx_window(lin, Wl, c0 + 1) : 0;
+		for (int t = 0; t < nt; t++) v ^= qx_window(A + t * Wl, Wl, c0 + 1) & qx_window(B + t * Wl, Wl, c0 + 1);
+		acc = v & qx_low(n - c0);
+	}
+	const i64 p_lo = (c0 > n ? c0 : n) - n, p_hi = (c0 + 64 < cols ? c0 + 64 : cols) - n;      // the word's pair indices
+	if (nt > 0 && p_lo < p_hi) {
+		i64 i = (i64)((1.0f + sqrtf(1.0f + 8.0f * (float)p_lo)) * 0.5f);      // the triangular root of p_lo: i(i-1)/2 <= p_lo < i(i+1)/2 ...
+		if (i < 1) i = 1;
+		while (i * (i - 1) / 2 > p_lo) i--;                                     // ... made exact in integers
+		while (i * (i + 1) / 2 <= p_lo) i++;
+		for (i64 s = i * (i - 1) / 2; s < p_hi; s += i, i++) {                  // run i: pairs s .. s + i - 1
+			const i64 j0 = (p_lo > s ? p_lo : s) - s, j1 = (p_hi < s + i ? p_hi : s + i) - s;
+			u64 run = 0;
+			for (int t = 0; t < nt; t++) {
+				const u64 *a = A + t * Wl, *b = B + t * Wl;
+				const u64 ai = 0 - ((a[(1 + i) >> 6] >> ((1 + i) & 63)) & 1), bi = 0 - ((b[(1 + i) >> 6] >> ((1 + i) & 63)) & 1);
+				run ^= (ai & qx_window(b, Wl, 1 + j0)) ^ (bi & qx_window(a, Wl, 1 + j0));
+			}
+			acc |= (run & qx_low(j1 - j0)) << (n + s + j0 - c0);
+		}
+	}
+	if (cols >= c0 && cols < c0 + 64) {                            // the constant: column cols = bit 0
+		u64 k = first ? lin[0] : 0;
+		for (int t = 0; t < nt; t++) k ^= A[t * Wl] & B[t * Wl];
+		acc |= (k & 1) << (cols - c0);
+	}
+	return acc;
+}
+
+__global__ void __launch_bounds__(256)
+k_quad_expand(const u64 *__restrict__ lin, const i64 *__restrict__ term_off, const u64 *__restrict__ ta, const u64 *__restrict__ tb,
+              i64 rows_live, i64 rows, int n, int Wl, int tch, u64 *__restrict__ out, i64 stride)
+{
+	extern __shared__ u64 qx_lds[];                    // [lin: Wl | A: tch x Wl | B: tch x Wl]
+	u64 *sl = qx_lds, *sa = sl + Wl, *sb = sa + (i64)tch * Wl;
+	const i64 cols = (i64)n + (i64)n * (n - 1) / 2;
+	const i64 npair = stride >> 1;                     // 16-byte pieces of a row (stride is even)
+	for (i64 r = blockIdx.x; r < rows; r += gridDim.x) {
+		ulonglong2 *o = reinterpret_cast<ulonglong2 *>(out + r * stride);
+		if (r >= rows_live) {
+			for (i64 k = threadIdx.x; k < npair; k += blockDim.x) o[k] = make_ulonglong2(0, 0);
+			continue;
+		}
+		i64 t0 = term_off[r], t1 = term_off[r + 1];
+		if (t0 < 0 || t1 < t0) t0 = t1 = 0;            // (offsets the entry could not check: such a row is its linear part)
+		bool first = true;
+		do {
+			const int nt = (int)(t1 - t0 < tch ? t1 - t0 : tch);
+			__syncthreads();                           // the pass before has read its operands
+			if (first) for (int e = threadIdx.x; e < Wl; e += blockDim.x) sl[e] = lin[r * Wl + e];
+			for (int e = threadIdx.x; e < nt * Wl; e += blockDim.x) { sa[e] = ta[t0 * Wl + e]; sb[e] = tb[t0 * Wl + e]; }
+			__syncthreads();
+			for (i64 k = threadIdx.x; k < npair; k += blockDim.x) {
+				u64 w0 = qx_word(sl, sa, sb, nt, Wl, n, cols, 128 * k, first);
+				u64 w1 = qx_word(sl, sa, sb, nt, Wl, n, cols, 128 * k + 64, first);
+				if (!first) { const ulonglong2 old = o[k]; w0 ^= old.x; w1 ^= old.y; }
+				o[k] = make_ulonglong2(w0, w1);
+			}
+			t0 += nt;
+			first = false;
+		} while (t0 < t1);
+	}
+}

@@ -4675,3 +4675,165 @@ void gf2bv_quad_last_times(double *out8)
 }
 
 }  // extern "C"
+
+// =================================================================================================
+// Quadratic expansion: equations kept factored (a linear form plus products of two linear forms) become the linearised rows of
+// the C-ABI layout on the device (k_quad_expand), where gf2bv_solve_device and the factor entries read them.
+namespace {
+
+struct QuadTerms {                     // the factored form, in host or in device memory
+	const u64 *lin = nullptr;          // rows_live x wl
+	const i64 *off = nullptr;          // rows_live + 1
+	const u64 *ta = nullptr, *tb = nullptr;
+	i64 rows_live = 0, rows = 0, n = 0;
+	i64 wl() const { return (n + 1 + 63) / 64; }
+	i64 cols() const { return n + n * (n - 1) / 2; }
+	i64 wt() const { return (cols() + 1 + 63) / 64; }
+};
+
+// The shape of a factored system; `host`: the offsets can be read (they start at 0 and never decrease; operands wherever they say
+// there are products)
+int check_quad_terms(const QuadTerms &q, bool host)
+{
+	if (!q.lin && q.rows_live > 0) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (!q.off) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (q.n < 1 || q.n > 65535 || q.cols() >= (1ll << 31) - 64) return fail(GF2BV_ERR_ARG, "n_lin must be at least 1 and n_lin + n_lin(n_lin-1)/2 below 2^31 - 64");
+	if (q.rows < 0 || q.rows >= (1ll << 31) - 64 || q.rows_live < 0 || q.rows_live > q.rows)
+		return fail(GF2BV_ERR_ARG, "rows_live must be 0..rows");
+	if (!host) {
+		if (!q.ta || !q.tb || !q.lin) return fail(GF2BV_ERR_ARG, "null pointer");
+		return GF2BV_OK;
+	}
+	if (q.off[0] != 0) return fail(GF2BV_ERR_ARG, "term offsets must start at 0");
+	for (i64 r = 0; r < q.rows_live; r++)
+		if (q.off[r + 1] < q.off[r]) return fail(GF2BV_ERR_ARG, "term offsets must not decrease");
+	if ((!q.ta || !q.tb) && q.off[q.rows_live] > 0) return fail(GF2BV_ERR_ARG, "null pointer");
+	return GF2BV_OK;
+}
+
+// (device pointers, already checked) the kernel on `st`
+int enqueue_quad_expand(const QuadTerms &q, u64 *d_aug, i64 stride, hipStream_t st)
+{
+	if (q.rows == 0) return GF2BV_OK;
+	const i64 wl = q.wl();
+	const int tch = (int)std::max<i64>(1, std::min<i64>(8, (65536 / 8 / wl - 1) / 2));      // products of a row in LDS at a time: 64 KiB at most
+	const i64 pieces = stride / 2;
+	const unsigned block = (unsigned)std::min<i64>(256, round_up(std::max<i64>(pieces, 1), 64));
+	const unsigned grid = (unsigned)std::min<i64>(q.rows, 256 * 8);
+	hipLaunchKernelGGL(k_quad_expand, dim3(grid), dim3(block), sizeof(u64) * (size_t)((1 + 2 * tch) * wl), st, q.lin, q.off, q.ta, q.tb,
+	                   q.rows_live, q.rows, (int)q.n, (int)wl, tch, d_aug, stride);
+	HIPCHK(hipGetLastError());
+	return GF2BV_OK;
+}
+
+// the factored form of host memory uploaded on `st` into buffers of `scratch`: `d` = q with device pointers
+int upload_quad_terms(const QuadTerms &q, QuadTerms &d, Scratch &scratch, int device, hipStream_t st)
+{
+	d = q;
+	const i64 wl = q.wl(), T = q.off[q.rows_live];
+	u64 *lin = nullptr, *ta = nullptr, *tb = nullptr;
+	i64 *off = nullptr;
+	HIPCHK(scratch.alloc((void **)&lin, sizeof(u64) * (size_t)std::max<i64>(1, q.rows_live * wl), device));
+	HIPCHK(scratch.alloc((void **)&off, sizeof(i64) * (size_t)(q.rows_live + 1), device));
+	HIPCHK(scratch.alloc((void **)&ta, sizeof(u64) * (size_t)std::max<i64>(1, T * wl), device));
+	HIPCHK(scratch.alloc((void **)&tb, sizeof(u64) * (size_t)std::max<i64>(1, T * wl), device));
+	if (q.rows_live > 0) HIPCHK(hipMemcpyAsync(lin, q.lin, sizeof(u64) * (size_t)(q.rows_live * wl), hipMemcpyHostToDevice, st));
+	HIPCHK(hipMemcpyAsync(off, q.off, sizeof(i64) * (size_t)(q.rows_live + 1), hipMemcpyHostToDevice, st));
+	if (T > 0) {
+		HIPCHK(hipMemcpyAsync(ta, q.ta, sizeof(u64) * (size_t)(T * wl), hipMemcpyHostToDevice, st));
+		HIPCHK(hipMemcpyAsync(tb, q.tb, sizeof(u64) * (size_t)(T * wl), hipMemcpyHostToDevice, st));
+	}
+	d.lin = lin; d.off = off; d.ta = ta; d.tb = tb;
+	return GF2BV_OK;
+}
+
+struct PoolStream {                    // a stream of the pool for the length of an entry
+	hipStream_t st = nullptr;
+	int device = 0;
+	~PoolStream() { pool().release_stream(st, device, 0); }
+};
+
+}  // namespace
+
+extern "C" {
+
+int gf2bv_quad_expand_device(const void *d_lin, const void *d_term_off, const void *d_ta, const void *d_tb, int64_t rows_live,
+                             int64_t rows, int64_t n_lin, void *d_aug, int64_t stride_words, int device, void *stream)
+{
+	return catching([&]() -> int {
+	QuadTerms q;
+	q.lin = (const u64 *)d_lin; q.off = (const i64 *)d_term_off; q.ta = (const u64 *)d_ta; q.tb = (const u64 *)d_tb;
+	q.rows_live = rows_live; q.rows = rows; q.n = n_lin;
+	int rc = check_quad_terms(q, false);
+	if (rc) return rc;
+	if (!d_aug) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (stride_words % 2 != 0 || stride_words < q.wt() || ((uintptr_t)d_aug & 15))
+		return fail(GF2BV_ERR_ARG, "device matrix needs 16-byte alignment and an even stride_words covering cols+1 bits");
+	rc = check_device(device);
+	if (rc) return rc;
+	return enqueue_quad_expand(q, (u64 *)d_aug, stride_words, (hipStream_t)stream);
+	});
+}
+
+int gf2bv_quad_expand_words(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t rows_live,
+                            int64_t rows, int64_t n_lin, uint64_t *out_aug, int64_t stride_words, int device)
+{
+	return catching([&]() -> int {
+	QuadTerms q, d;
+	q.lin = reinterpret_cast<const u64 *>(lin); q.off = reinterpret_cast<const i64 *>(term_off);
+	q.ta = reinterpret_cast<const u64 *>(ta); q.tb = reinterpret_cast<const u64 *>(tb);
+	q.rows_live = rows_live; q.rows = rows; q.n = n_lin;
+	int rc = check_quad_terms(q, true);
+	if (rc) return rc;
+	if (!out_aug && rows > 0) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (stride_words < q.wt()) return fail(GF2BV_ERR_ARG, "stride_words does not cover cols+1 bits");
+	rc = check_device(device);
+	if (rc) return rc;
+	if (rows == 0) return GF2BV_OK;
+	PoolStream ps; ps.device = device;
+	HIPCHK(pool().stream(&ps.st, device, 0));
+	Scratch scratch;                   // (declared after ps: released first, after synchronising the stream)
+	scratch.sync_first = ps.st;
+	rc = upload_quad_terms(q, d, scratch, device, ps.st);
+	if (rc) return rc;
+	const i64 ds = round_up(stride_words, 2);
+	u64 *d_aug = nullptr;
+	HIPCHK(scratch.alloc((void **)&d_aug, sizeof(u64) * (size_t)(rows * ds), device));
+	rc = enqueue_quad_expand(d, d_aug, ds, ps.st);
+	if (rc) return rc;
+	HIPCHK(hipMemcpy2DAsync(out_aug, stride_words * 8, d_aug, ds * 8, stride_words * 8, rows, hipMemcpyDeviceToHost, ps.st));
+	HIPCHK(hipStreamSynchronize(ps.st));
+	return GF2BV_OK;
+	});
+}
+
+int gf2bv_solve_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t rows_live,
+                           int64_t rows, int64_t n_lin, int mode, int device, gf2bv_result **out)
+{
+	return catching([&]() -> int {
+	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
+	*out = nullptr;
+	QuadTerms q, d;
+	q.lin = reinterpret_cast<const u64 *>(lin); q.off = reinterpret_cast<const i64 *>(term_off);
+	q.ta = reinterpret_cast<const u64 *>(ta); q.tb = reinterpret_cast<const u64 *>(tb);
+	q.rows_live = rows_live; q.rows = rows; q.n = n_lin;
+	int rc = check_quad_terms(q, true);
+	if (!rc) rc = check_shape(rows, q.cols(), mode);
+	if (!rc) rc = check_device(device);
+	if (rc) return rc;
+	PoolStream ps; ps.device = device;
+	HIPCHK(pool().stream(&ps.st, device, 0));
+	Scratch scratch;
+	scratch.sync_first = ps.st;
+	rc = upload_quad_terms(q, d, scratch, device, ps.st);
+	if (rc) return rc;
+	const i64 ds = round_up(q.wt(), 2);
+	u64 *d_aug = nullptr;
+	HIPCHK(scratch.alloc((void **)&d_aug, sizeof(u64) * (size_t)(rows * ds), device));
+	rc = enqueue_quad_expand(d, d_aug, ds, ps.st);
+	if (rc) return rc;
+	return gf2bv_solve_device(d_aug, rows, q.cols(), ds, mode, device, ps.st, 0, out);      // same stream: ordered behind the expansion
+	});
+}
+
+}  // extern "C"

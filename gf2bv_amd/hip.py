@@ -35,6 +35,7 @@ EXPORTS = [
     "gf2bv_result_status", "gf2bv_result_rank", "gf2bv_result_dimension", "gf2bv_result_words",
     "gf2bv_result_origin", "gf2bv_result_basis", "gf2bv_result_pivots", "gf2bv_result_stats",
     "gf2bv_result_free", "gf2bv_space_combine", "gf2bv_space_open", "gf2bv_space_enumerate", "gf2bv_space_buffer", "gf2bv_space_close",
+    "gf2bv_quad_expand_device", "gf2bv_quad_expand_words", "gf2bv_solve_quad_terms",
     "gf2bv_quad_search", "gf2bv_quad_search_alloc", "gf2bv_quad_free", "gf2bv_quad_plan", "gf2bv_quad_points", "gf2bv_quad_forms_search", "gf2bv_quad_last_times",
     "gf2bv_slab_work_words", "gf2bv_slab_tiles", "gf2bv_slab_open", "gf2bv_slab_blocks", "gf2bv_slab_owner",
     "gf2bv_slab_payload_bytes", "gf2bv_slab_factor", "gf2bv_slab_apply", "gf2bv_slab_factor_on", "gf2bv_slab_apply_on",
@@ -135,6 +136,9 @@ def lib():
         L.gf2bv_quad_forms_search.argtypes = [vp, i64, i64, i32, i64, vp, vp]
         L.gf2bv_quad_last_times.argtypes = [vp]
         L.gf2bv_quad_last_times.restype = None
+        L.gf2bv_quad_expand_device.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, i64, i32, vp]
+        L.gf2bv_quad_expand_words.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, i64, i32]
+        L.gf2bv_solve_quad_terms.argtypes = [vp, vp, vp, vp, i64, i64, i64, i32, i32, pp]
         L.gf2bv_slab_work_words.argtypes = [i64, i64]
         L.gf2bv_slab_work_words.restype = i64
         L.gf2bv_slab_tiles.argtypes = [i64]
@@ -562,6 +566,55 @@ def quad_last_times() -> dict:
     lib().gf2bv_quad_last_times(v)
     keys = ("ms_reduce", "ms_forms", "ms_affine", "ms_search", "ms_relin", "ms_total", "levels", "candidates")
     return dict(zip(keys, list(v)))
+
+
+def quad_cols(n_lin: int) -> int:
+    """columns of a linearised quadratic system in n_lin unknowns: the unknowns and their n_lin(n_lin-1)/2 products"""
+    return n_lin + n_lin * (n_lin - 1) // 2
+
+
+def _quad_terms(lin, term_off, ta, tb, n_lin: int):
+    """the factored form of gf2bv_quad_expand_* as contiguous arrays, shapes checked against each other"""
+    wl = (n_lin + 1 + 63) // 64
+    lin = np.ascontiguousarray(lin, dtype=np.uint64).reshape(-1, wl)
+    term_off = np.ascontiguousarray(term_off, dtype=np.int64).reshape(-1)
+    ta = np.ascontiguousarray(ta, dtype=np.uint64).reshape(-1, wl)
+    tb = np.ascontiguousarray(tb, dtype=np.uint64).reshape(-1, wl)
+    if len(term_off) != len(lin) + 1 or len(ta) != len(tb) or (len(term_off) and term_off[-1] != len(ta)):
+        raise ValueError("term_off needs one entry per row of lin and one more, ending at the number of operands in ta and tb")
+    return lin, term_off, ta, tb
+
+
+def quad_expand_words(lin, term_off, ta, tb, n_lin: int, rows: int | None = None, stride_words: int | None = None,
+                      device: int = 0) -> np.ndarray:
+    """Factored quadratic equations (lin[r] ^ XOR of the products ta[t] * tb[t], t in term_off[r] .. term_off[r + 1]; linear forms of
+    ceil((n_lin + 1) / 64) words, bit 0 constant, bit 1 + g unknown g) expanded on the device into the linearised rows of the
+    augmented-words layout: [rows, stride_words] uint64, rows beyond len(lin) zero (gf2bv_quad_expand_words)."""
+    lin, term_off, ta, tb = _quad_terms(lin, term_off, ta, tb, n_lin)
+    rows = len(lin) if rows is None else rows
+    stride = (quad_cols(n_lin) + 1 + 63) // 64 if stride_words is None else stride_words
+    out = np.empty((max(rows, 0), max(stride, 0)), dtype=np.uint64)
+    _check(lib().gf2bv_quad_expand_words(lin.ctypes.data, term_off.ctypes.data, ta.ctypes.data, tb.ctypes.data, len(lin), rows, n_lin,
+                                         out.ctypes.data, stride, device))
+    return out
+
+
+def quad_expand_device(d_lin: int, d_term_off: int, d_ta: int, d_tb: int, rows_live: int, rows: int, n_lin: int, d_aug: int,
+                       stride: int, device: int = 0, stream: int = 0) -> None:
+    """quad_expand_words with everything resident in device memory: the kernel is enqueued on `stream` and the call returns; a
+    solve_device / factor_device on the same stream reads the finished rows."""
+    _check(lib().gf2bv_quad_expand_device(d_lin, d_term_off, d_ta, d_tb, rows_live, rows, n_lin, d_aug, stride, device, stream or None))
+
+
+def solve_quad_terms(lin, term_off, ta, tb, n_lin: int, rows: int | None = None, mode: int = MODE_SINGLE, device: int = 0) -> Solution:
+    """The factored system uploaded, expanded on the device and solved there (gf2bv_solve_quad_terms): what solve_words returns for
+    quad_expand_words of the same arrays.  rows (default: max(len(lin), columns)) >= the columns."""
+    lin, term_off, ta, tb = _quad_terms(lin, term_off, ta, tb, n_lin)
+    rows = max(len(lin), quad_cols(n_lin)) if rows is None else rows
+    h = ctypes.c_void_p()
+    _check(lib().gf2bv_solve_quad_terms(lin.ctypes.data, term_off.ctypes.data, ta.ctypes.data, tb.ctypes.data, len(lin), rows, n_lin,
+                                        mode, device, ctypes.byref(h)))
+    return _take(h, mode)
 
 
 def synth_device(d_ptr: int, rows: int, cols: int, stride: int, seed: int, device: int = 0, stream: int = 0):

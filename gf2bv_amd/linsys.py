@@ -227,7 +227,82 @@ class LinearSystem:
         return bv.evaluate(raw)
 
 
-class QuadraticSystem(LinearSystem):
+class _QuadraticPoints:
+    """What a linearised quadratic system does with the solutions of its linear solve, shared by ``QuadraticSystem`` and the packed
+    front-end's ``PackedQuadraticSystem``: the points whose product unknowns equal the products of their linear part.  Needs
+    ``_lin_size`` / ``_quad_size`` / ``_quad_sizes``, ``_convert_sol`` and ``solve_raw_space`` / ``solve_all`` of the class it is mixed into."""
+
+    def _products_match(self, lin: int, quad: int) -> bool:
+        n = self._lin_size
+        for i in range(n):
+            if (lin >> i) & 1:
+                # products with x_i = 1: pairs (i, j) for j < i must repeat the low i bits of lin
+                want = lin & ((1 << i) - 1)
+            else:
+                want = 0
+            if quad & ((1 << i) - 1) != want:
+                return False
+            quad >>= i
+        assert quad == 0, "Invalid quadratic part"
+        return True
+
+    def convert_sol(self, s: int) -> Optional[tuple]:
+        lin = s & ((1 << self._lin_size) - 1)
+        quad = s >> self._lin_size
+        assert quad >> self._quad_size == 0, "Invalid solution"
+        if not self._products_match(lin, quad):
+            return None
+        return self._convert_sol(lin)[:-1]
+
+    def solve_one(self, zeros: Zeros):
+        # the particular solution of the linearised system need not be consistent: take the first one that is
+        for sol in self.solve_all(zeros):
+            return sol
+        return None
+
+    # -- the consistent points on the GPU (no counterpart in the reference) -------------------------------------------------
+    # solve_all walks all 2^d points of the linearised space on the host; search_all reduces the space to quadratic forms in
+    # r_eff <= r variables (r: the rank of its projection onto the linear unknowns) and finds their common zeros on the device
+    # (AffineSpace.quad_search -> gf2bv_quad_search, DESIGN.md section 7).  Same elements in the same order as solve_all,
+    # at any dimension.
+    def _search_space(self, space, max_enum: int, max_solutions: int, first: bool = False) -> list:
+        try:
+            raws = space.quad_search(self._lin_size, max_enum, max_solutions, first)
+        except QuadSearchGaveUp as e:
+            raise DimensionTooLargeError(f"Solution space (dim {space.dimension}): {e.args[0]}", space=space) from None
+        out = []
+        for raw in raws:
+            sol = self.convert_sol(raw)
+            if sol is None:
+                raise RuntimeError("quad_search returned an inconsistent point")
+            out.append(sol)
+        return out
+
+    def search_all(self, zeros: Zeros, *, max_enum: int = 32, max_solutions: int = 65536) -> list:
+        """list(solve_all(zeros, max_dimension=d)) without the 2^d walk; DimensionTooLargeError (with .space) when the search
+        gives up, ValueError when there are more than max_solutions consistent points."""
+        space = self.solve_raw_space(zeros)
+        if space is None:
+            return []
+        return self._search_space(space, max_enum, max_solutions)
+
+    def search_one(self, zeros: Zeros, *, max_enum: int = 32):
+        """solve_one(zeros) at any dimension: the first consistent point in iteration order, None if there is none."""
+        space = self.solve_raw_space(zeros)
+        if space is None:
+            return None
+        sols = self._search_space(space, max_enum, 1, first=True)
+        return sols[0] if sols else None
+
+    def evaluate(self, bv: BitVec, sol: tuple) -> int:
+        raw, shift = 0, 0
+        for value, width in zip(sol, self._quad_sizes):
+            raw |= value << shift
+            shift += width
+        return bv.evaluate(raw)
+
+
+class QuadraticSystem(_QuadraticPoints, LinearSystem):
     """Quadratic equations over GF(2) by linearisation: on top of the n unknowns of ``sizes`` every product
     x_i x_j (j < i) is an unknown of its own, n(n-1)/2 of them after the linear ones, and the linearised system
     goes through the same solve path (e.g. 128 unknowns -> 8256 columns, the NLFSR example).  Solutions whose
@@ -289,34 +364,6 @@ class QuadraticSystem(LinearSystem):
             raise ValueError("The input should be a single bit")
         return self._bit_assert(a._bits[0], v)
 
-    def _products_match(self, lin: int, quad: int) -> bool:
-        n = self._lin_size
-        for i in range(n):
-            if (lin >> i) & 1:
-                # products with x_i = 1: pairs (i, j) for j < i must repeat the low i bits of lin
-                want = lin & ((1 << i) - 1)
-            else:
-                want = 0
-            if quad & ((1 << i) - 1) != want:
-                return False
-            quad >>= i
-        assert quad == 0, "Invalid quadratic part"
-        return True
-
-    def convert_sol(self, s: int) -> Optional[tuple]:
-        lin = s & ((1 << self._lin_size) - 1)
-        quad = s >> self._lin_size
-        assert quad >> self._quad_size == 0, "Invalid solution"
-        if not self._products_match(lin, quad):
-            return None
-        return self._convert_sol(lin)[:-1]
-
-    def solve_one(self, zeros: Zeros):
-        # the particular solution of the linearised system need not be consistent: take the first one that is
-        for sol in self.solve_all(zeros):
-            return sol
-        return None
-
     def solve_one_rhs(self, exprs: Zeros, values_list: Sequence[Sequence[int]], *, max_dimension: int = 16) -> list:
         """solve_one for every instance (the first element of its solve_all that passes convert_sol, None if there is none),
         from ONE elimination (solve_raw_space_rhs); DimensionTooLargeError as solve_all raises it."""
@@ -336,44 +383,3 @@ class QuadraticSystem(LinearSystem):
                         break
             out.append(sol)
         return out
-
-    # -- the consistent points on the GPU (no counterpart in the reference) -------------------------------------------------
-    # solve_all walks all 2^d points of the linearised space on the host; search_all reduces the space to quadratic forms in
-    # r_eff <= r variables (r: the rank of its projection onto the linear unknowns) and finds their common zeros on the device
-    # (AffineSpace.quad_search -> gf2bv_quad_search).  Same elements in the same order as solve_all,
-    # at any dimension.
-    def _search_space(self, space, max_enum: int, max_solutions: int, first: bool = False) -> list:
-        try:
-            raws = space.quad_search(self._lin_size, max_enum, max_solutions, first)
-        except QuadSearchGaveUp as e:
-            raise DimensionTooLargeError(f"Solution space (dim {space.dimension}): {e.args[0]}", space=space) from None
-        out = []
-        for raw in raws:
-            sol = self.convert_sol(raw)
-            if sol is None:
-                raise RuntimeError("quad_search returned an inconsistent point")
-            out.append(sol)
-        return out
-
-    def search_all(self, zeros: Zeros, *, max_enum: int = 32, max_solutions: int = 65536) -> list:
-        """list(solve_all(zeros, max_dimension=d)) without the 2^d walk; DimensionTooLargeError (with .space) when the search
-        gives up, ValueError when there are more than max_solutions consistent points."""
-        space = self.solve_raw_space(zeros)
-        if space is None:
-            return []
-        return self._search_space(space, max_enum, max_solutions)
-
-    def search_one(self, zeros: Zeros, *, max_enum: int = 32):
-        """solve_one(zeros) at any dimension: the first consistent point in iteration order, None if there is none."""
-        space = self.solve_raw_space(zeros)
-        if space is None:
-            return None
-        sols = self._search_space(space, max_enum, 1, first=True)
-        return sols[0] if sols else None
-
-    def evaluate(self, bv: BitVec, sol: tuple) -> int:
-        raw, shift = 0, 0
-        for value, width in zip(sol, self._quad_sizes):
-            raw |= value << shift
-            shift += width
-        return bv.evaluate(raw)

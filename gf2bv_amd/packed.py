@@ -21,9 +21,9 @@ from typing import Iterable, Optional, Sequence
 
 import numpy as np
 
-from ._internal import m4ri_solve_packed
+from ._internal import m4ri_solve_packed, m4ri_solve_quad_packed
 from .bitvec import BitVec
-from .linsys import DimensionTooLargeError
+from .linsys import DimensionTooLargeError, _QuadraticPoints
 
 
 def _const_bits(n: int, value: int) -> np.ndarray:
@@ -84,6 +84,8 @@ class PackedBitVec(BitVec):
 
     # -- xor (reference :39-49) ----------------------------------------------------------------
     def __xor__(self, other):
+        if isinstance(other, PackedQuadBitVec):
+            return NotImplemented                      # (its __rxor__ takes over: the sum is quadratic)
         return PackedBitVec(self._rows ^ self._coerce(other))
 
     __rxor__ = __xor__
@@ -170,6 +172,8 @@ class PackedBitVec(BitVec):
         return PackedBitVec(np.tile(self._rows, (n, 1)))
 
     def concat(self, other: "PackedBitVec"):
+        if isinstance(other, PackedQuadBitVec):        # (linear bits in front of bits that carry products)
+            return other._like(self._rows, np.zeros(len(self) + 1, dtype=np.int64), other._ta[:0], other._tb[:0]).concat(other)
         return PackedBitVec(np.concatenate([self._rows, other._rows]))
 
     # -- evaluation (reference :128-134) -----------------------------------------------------------
@@ -287,3 +291,215 @@ class PackedLinearSystem:
             raw |= value << shift
             shift += width
         return bv.evaluate(raw)
+
+
+# ---- quadratic systems kept factored ---------------------------------------------------------------------------------------------
+# QuadraticSystem.mul_bit writes the linearised row of a product on the host, n(n-1)/2 bits beyond the n + 1 of its operands: at
+# n = 256 that is 10 ms per product and a 32896-column system cannot be written down in an hour.  Here a symbolic bit stays what the
+# caller wrote: a linear form over the n + 1 bits plus a list of products of two such forms.  The rows of the linearised matrix
+# come into being on the device (k_quad_expand, through m4ri_solve_quad_packed / hip.quad_expand_words), where the solver reads them.
+def _refuse(name: str):
+    def method(self, *args, **kwargs):
+        raise TypeError(f"{name} is not supported on a PackedQuadBitVec (bits that carry products): only ^, indexing and concat are")
+    method.__name__ = name
+    return method
+
+
+class PackedQuadBitVec:
+    """k symbolic bits, each a linear form (a row of ``_lin``, Wl = ceil((n + 1) / 64) words in the order of ``PackedBitVec``)
+    plus products of two linear forms: bit i owns the operand rows ``_off[i] .. _off[i + 1]`` of ``_ta`` / ``_tb``.  The value of
+    a product is ``QuadraticSystem._mul_bit`` of its operands; equal products are not cancelled here, they cancel when the rows
+    are expanded."""
+    __slots__ = ("_lin", "_off", "_ta", "_tb", "_n")
+
+    def __init__(self, lin: np.ndarray, off: np.ndarray, ta: np.ndarray, tb: np.ndarray, n: int):
+        self._lin, self._off, self._ta, self._tb = lin, off, ta, tb      # [k, Wl] uint64, [k + 1] int64, [T, Wl], [T, Wl]: immutable
+        self._n = n                                    # unknowns of the system (Wl alone leaves 64 candidates)
+
+    def _like(self, lin, off, ta, tb) -> "PackedQuadBitVec":
+        return PackedQuadBitVec(lin, off, ta, tb, self._n)
+
+    def __len__(self):
+        return self._lin.shape[0]
+
+    def _take(self, idx: np.ndarray) -> "PackedQuadBitVec":
+        """the bits idx[0], idx[1], ... as a new vector"""
+        cnt = self._off[idx + 1] - self._off[idx]
+        off = np.zeros(len(idx) + 1, dtype=np.int64)
+        np.cumsum(cnt, out=off[1:])
+        src = np.repeat(self._off[idx] - off[:-1], cnt) + np.arange(off[-1])       # operand row of every kept product
+        return self._like(self._lin[idx], off, self._ta[src], self._tb[src])
+
+    def __getitem__(self, key):
+        n = len(self)
+        if isinstance(key, slice):
+            return self._take(np.arange(n)[key])
+        i = operator.index(key)
+        if not -n <= i < n:
+            raise IndexError("PackedQuadBitVec index out of range")
+        return self._take(np.array([i % n]))
+
+    def __xor__(self, other):
+        if isinstance(other, PackedQuadBitVec):
+            if other._lin.shape != self._lin.shape:
+                raise ValueError("Cannot mix bitvecs of different lengths")
+            # bit i of the sum owns the products of self[i], then those of other[i]
+            owner = np.concatenate([np.repeat(np.arange(len(self)), np.diff(self._off)), np.repeat(np.arange(len(self)), np.diff(other._off))])
+            order = np.argsort(owner, kind="stable")
+            return self._like(self._lin ^ other._lin, self._off + other._off, np.concatenate([self._ta, other._ta])[order],
+                              np.concatenate([self._tb, other._tb])[order])
+        if isinstance(other, PackedBitVec):
+            if other._rows.shape != self._lin.shape:
+                raise ValueError("Cannot mix bitvecs of different lengths")
+            return self._like(self._lin ^ other._rows, self._off, self._ta, self._tb)
+        if isinstance(other, BitVec):
+            raise TypeError("cannot mix packed and tuple-of-int BitVecs")
+        lin = self._lin.copy()
+        lin[:, 0] ^= _const_bits(len(self), other)      # a constant only has the affine bit
+        return self._like(lin, self._off, self._ta, self._tb)
+
+    __rxor__ = __xor__
+    __pow__ = __xor__
+
+    def concat(self, other):
+        if isinstance(other, PackedBitVec):
+            other = self._like(other._rows, np.zeros(len(other) + 1, dtype=np.int64), self._ta[:0], self._tb[:0])
+        if not isinstance(other, PackedQuadBitVec):
+            raise TypeError("concat needs a PackedQuadBitVec or a PackedBitVec")
+        if other._lin.shape[1] != self._lin.shape[1]:
+            raise ValueError("Cannot mix bitvecs over different numbers of unknowns")
+        return self._like(np.concatenate([self._lin, other._lin]), np.concatenate([self._off, other._off[1:] + self._off[-1]]),
+                          np.concatenate([self._ta, other._ta]), np.concatenate([self._tb, other._tb]))
+
+    def evaluate(self, s: int) -> int:
+        """Value under the raw point ``s`` of the LINEARISED unknowns (bit j = unknown j, the products behind the n linear ones),
+        as BitVec.evaluate gives it for the expanded bits; on the host, a product at a time."""
+        n = self._n
+        low = ((s << 1) | 1) & ((1 << (n + 1)) - 1)
+        runs = [(s >> (n + i * (i - 1) // 2)) & ((1 << i) - 1) for i in range(n)]          # the products (i, 0 .. i-1) at s
+        ints = lambda rows: [int.from_bytes(r.tobytes(), "little") for r in rows]            # noqa: E731
+        lin, ta, tb = ints(self._lin), ints(self._ta), ints(self._tb)
+        par = lambda v: bin(v).count("1") & 1                                                 # noqa: E731
+        value = 0
+        for k in range(len(self)):
+            bit = par(lin[k] & low)
+            for t in range(self._off[k], self._off[k + 1]):
+                a, b = ta[t], tb[t]
+                bit ^= par(a & b & low)
+                for i in range(n):
+                    if (a >> (1 + i)) & 1:
+                        bit ^= par((b >> 1) & runs[i])
+                    if (b >> (1 + i)) & 1:
+                        bit ^= par((a >> 1) & runs[i])
+            value |= bit << k
+        return value
+
+
+for _name in ("__and__", "__rand__", "__or__", "__ror__", "__lshift__", "__rshift__", "__mod__", "__invert__", "lshift_ext", "rotl", "rotr",
+              "sum", "zeroext", "signext", "broadcast", "dup"):
+    setattr(PackedQuadBitVec, _name, _refuse(_name))
+del _name
+
+
+class PackedQuadraticSystem(_QuadraticPoints, PackedLinearSystem):
+    """QuadraticSystem (gf2bv/__init__.py:290-408) with the equations kept factored: same methods, same results, and no row of the
+    linearised matrix -- n + n(n-1)/2 columns -- on the host.  ``gens()`` are PackedBitVecs over the n + 1 bits of the unknowns
+    themselves, so everything linear (the LFSR / PRNG models of tests.harness_models) runs on them as on a PackedLinearSystem's;
+    ``mul_bit`` / ``bit_assert`` give PackedQuadBitVecs; the solve methods hand the factored arrays to the device, which expands
+    and solves them.  ``convert_sol``, ``solve_one`` and the searches are QuadraticSystem's own (_QuadraticPoints)."""
+
+    def __init__(self, sizes: Iterable[int]):
+        sizes = list(sizes)
+        n = sum(sizes)
+        self._quad_sizes = sizes
+        self._lin_size = n
+        self._quad_size = n * (n - 1) // 2
+        self._sizes = sizes + [self._quad_size]        # (what _convert_sol splits a raw solution into)
+        self._cols = n + self._quad_size
+        self._words = (n + 1 + 63) // 64               # words of a linear form: the generators have no product coordinates
+        self._vars = PackedLinearSystem(sizes).gens()
+
+    def __reduce__(self):
+        return (self.__class__, (self._quad_sizes,))
+
+    def _single(self, a, what: str) -> np.ndarray:
+        if isinstance(a, PackedQuadBitVec):
+            raise TypeError(f"{what} of a bit that carries products is of degree above 2")
+        if not isinstance(a, PackedBitVec):
+            raise TypeError(f"{what} needs PackedBitVecs of this system")
+        if len(a) != 1:
+            raise ValueError("The inputs should be single bits" if what == "mul_bit" else "The input should be a single bit")
+        if a._rows.shape[1] != self._words:
+            raise ValueError("Cannot mix bitvecs over different numbers of unknowns")
+        return a._rows
+
+    def mul_bit(self, a: PackedBitVec, b: PackedBitVec) -> PackedQuadBitVec:
+        ra, rb = self._single(a, "mul_bit"), self._single(b, "mul_bit")
+        return PackedQuadBitVec(np.zeros((1, self._words), dtype=np.uint64), np.array([0, 1], dtype=np.int64), ra, rb, self._lin_size)
+
+    def bit_assert(self, a: PackedBitVec, v: int) -> list:
+        """QuadraticSystem.bit_assert: "bit a equals v" and its product with every unknown x other than a itself, a * x = v * x --
+        the same rows in the same order, as [a ^ v, one PackedQuadBitVec of the products]"""
+        ra = self._single(a, "bit_assert")
+        assert v in (0, 1), "Invalid bit"
+        assert ra[0, 1:].any() or ra[0, 0] > 1, "a should not be a constant"
+        assert not (a._bits[0] >> (self._lin_size + 1)), "Not a linear term"
+        x = np.concatenate([g._rows for g in self._vars])                  # unknown i: bit 1 + i alone
+        x = x[(x != ra).any(axis=1)]                                       # (the reference skips x == a)
+        lin = x if v else np.zeros_like(x)
+        return [a ^ v, PackedQuadBitVec(lin, np.arange(len(x) + 1, dtype=np.int64), np.repeat(ra, len(x), axis=0), x, self._lin_size)]
+
+    # -- zeros -> the factored arrays the device expands --------------------------------------------------------------------------
+    def _terms(self, zeros: Sequence):
+        """(lin [R, Wl], term_off [R + 1], ta, tb) of all the bits of ``zeros``, in order.  No row is dropped: whether a factored
+        row is the literal 0 or the equation "1 = 0" is only known once it is expanded, and the solver needs neither decided -- an
+        all-zero row changes no pivot, origin or basis, and a row that is exactly the constant 1 makes it report the system
+        inconsistent (LinearSystem._rhs_eqs relies on the same two facts)."""
+        none = np.zeros((0, self._words), dtype=np.uint64)
+        lins, cnts, tas, tbs = [none], [], [none], [none]
+        for z in zeros:
+            if isinstance(z, PackedQuadBitVec):
+                lin = z._lin
+                cnts.append(np.diff(z._off))
+                tas.append(z._ta)
+                tbs.append(z._tb)
+            elif isinstance(z, PackedBitVec):
+                lin = z._rows
+                cnts.append(np.zeros(len(lin), dtype=np.int64))
+            elif isinstance(z, BitVec):
+                raise TypeError("cannot mix packed and tuple-of-int BitVecs")
+            elif isinstance(z, int) and z in (0, 1):                       # the literal 0, or the equation "1 = 0"
+                lin = np.zeros((1, self._words), dtype=np.uint64)
+                lin[0, 0] = z
+                cnts.append(np.zeros(1, dtype=np.int64))
+            else:
+                raise TypeError("a bare equation of a packed quadratic system is 0 or 1: build the others from gens() and mul_bit")
+            if lin.shape[1] != self._words:
+                raise ValueError("Cannot mix bitvecs over different numbers of unknowns")
+            lins.append(lin)
+        lin = np.concatenate(lins)
+        off = np.zeros(len(lin) + 1, dtype=np.int64)
+        if cnts:
+            np.cumsum(np.concatenate(cnts), out=off[1:])
+        return lin, off, np.concatenate(tas), np.concatenate(tbs)
+
+    def _stack_rows(self, zeros: Sequence):
+        raise TypeError("a packed quadratic system has no rows on the host: use get_eqs, or hip.quad_expand_words on the factored arrays")
+
+    def get_eqs(self, zeros: Sequence) -> list:
+        """the reference's list of equation ints over the linearised unknowns, expanded on the device (needs the GPU)"""
+        from . import hip                              # noqa: PLC0415  (ctypes binding, first use only)
+        lin, off, ta, tb = self._terms(zeros)
+        if not len(lin):
+            return []
+        mask = (1 << self._cols) - 1
+        eqs = []
+        for r in hip.quad_expand_words(lin, off, ta, tb, self._lin_size):
+            v = int.from_bytes(r.tobytes(), "little")
+            eqs.append(((v & mask) << 1) | (v >> self._cols))              # column c is bit c + 1, column cols the constant
+        return [e for e in eqs if e]                   # literal zeros carry no information
+
+    # -- boundary call ---------------------------------------------------------------------------------------------------------------
+    def _solve_internal(self, zeros: Sequence, mode: int):
+        lin, off, ta, tb = self._terms(zeros)
+        return m4ri_solve_quad_packed(lin, off, ta, tb, self._lin_size, max(len(lin), self._cols), mode)      # (the boundary wants rows >= cols)

@@ -338,6 +338,33 @@ int  gf2bv_quad_forms_search(const uint64_t *forms, int64_t m, int64_t r_eff, in
                              uint64_t *out);
 void gf2bv_quad_last_times(double *out8);
 
+/* ---- quadratic expansion: factored quadratic equations -> linearised rows, on the device ---------------------------------
+ * A quadratic equation in n_lin unknowns kept FACTORED: a linear form plus products of two linear forms, every form
+ * Wl = ceil((n_lin + 1) / 64) words in the equation-int order (bit 0 = constant, bit 1 + g = unknown g; bits above n_lin ignored).
+ *   lin[rows_live][Wl]        the linear part of each row,
+ *   term_off[rows_live + 1]   int64, starts at 0, never decreases: row r owns the products ta[t] * tb[t], t in term_off[r] .. term_off[r+1],
+ *   ta[T][Wl], tb[T][Wl]      the operands, T = term_off[rows_live] (may be null when T is 0, host forms only).
+ * (Arrays with entries for all `rows` rows are fine: what lies behind rows_live is not read.)
+ * Row r of the output is e = lin[r] ^ XOR_t mul(ta[t], tb[t]) in the augmented-words layout for cols = n_lin + n_lin(n_lin-1)/2:
+ * column c = bit c + 1 of e, column `cols` = bit 0 of e, every bit from cols + 1 to the end of the stride zero.  mul(a, b) is
+ * QuadraticSystem._mul_bit (gf2bv/__init__.py:334-338): constant and linear bits a & b (x^2 = x; no constant x linear cross terms),
+ * pair (i, j), j < i, at bit 1 + n_lin + i(i-1)/2 + j iff a_i b_j ^ a_j b_i with a_i = bit 1 + i of a.  Rows rows_live .. rows - 1
+ * are written as zeros (the padding up to rows >= cols).
+ * gf2bv_quad_expand_device: everything in device memory; the kernel is enqueued on `stream` (a HIP stream handle or NULL) and
+ * the call returns, as gf2bv_synth_device does: gf2bv_solve_device / gf2bv_factor_device / gf2bv_factor_append_device on the same
+ * stream consume d_aug with no synchronisation in between.  d_aug 16-byte aligned, stride_words even and >= ceil((cols + 1) / 64).
+ * The offsets cannot be checked there: a row whose offsets decrease or are negative is expanded as its linear part.
+ * gf2bv_quad_expand_words: host pointers in, rows x stride_words words back in host memory (upload, kernel, download).
+ * gf2bv_solve_quad_terms: upload, expansion into a buffer of the pool, gf2bv_solve_device on the same stream; needs rows >= cols.
+ * Argument errors (null pointers, n_lin < 1 or cols >= 2^31 - 64, rows_live outside 0..rows, offsets that do not start at 0 or
+ * decrease, rows < cols for the solve entry, a bad stride or mode) return GF2BV_ERR_ARG before any device is touched. */
+int gf2bv_quad_expand_device(const void *d_lin, const void *d_term_off, const void *d_ta, const void *d_tb, int64_t rows_live,
+                             int64_t rows, int64_t n_lin, void *d_aug, int64_t stride_words, int device, void *stream);
+int gf2bv_quad_expand_words(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t rows_live,
+                            int64_t rows, int64_t n_lin, uint64_t *out_aug, int64_t stride_words, int device);
+int gf2bv_solve_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t rows_live,
+                           int64_t rows, int64_t n_lin, int mode, int device, gf2bv_result **out);
+
 /* ---- synthetic systems + independent residual check (bench / tests) ----------------------- */
 /* word w of row r = mix64(mix64(seed) ^ ((r<<20)|w)); planted solution = pseudo-row 0xFFFFF;
  * RHS = <row, planted>.  Writes rows x stride_words words at d_aug. */
