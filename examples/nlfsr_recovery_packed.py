@@ -31,8 +31,30 @@ def recover(kind, seed, count=2 ** 14 + 1000):
     assert sols == [(secret,)], (kind.__name__, len(sols))
     assert qsys.solve_one(zeros) == (secret,)
     print(f"{kind.__name__:14s} {len(zeros)} equations x {qsys._cols} unknowns: generate {t1 - t0:.2f}s  solve_all {t2 - t1:.3f}s  ok")
+    guess_loop(qsys, x, zeros, secret)
     return secret
 
+
+def guess_loop(qsys, x, base, secret, bits=(0, 1, 2)):
+    """Guesses against a kept factorization: the system is factored ONCE (the first search on `fs` makes the factorization), then
+    each state bit is tried both ways on a copy of it.  bit_assert(a, v) is `a = v` and its n - 1 products with the other
+    unknowns, kept factored on the host; add expands them on the device and appends them to the copy's factorization.  The base
+    system has the secret as its only consistent point, so the right guess finds it again and the wrong one finds none."""
+    t0 = time.perf_counter()
+    with qsys.factor(base) as fs:
+        nothing = [0] * len(base)
+        assert fs.search_one(nothing) == (secret,)         # factors the base: what copy() copies from here on
+        t1 = time.perf_counter()
+        for i in bits:
+            found = {}
+            for v in (0, 1):
+                with fs.copy() as g:                       # a device-to-device copy, no factorization
+                    g.add(qsys.bit_assert(x[i], v))        # appended to the copy's factorization
+                    found[v] = g.search_one(nothing + [0, 0])
+            want = (secret >> i) & 1
+            assert found[want] == (secret,) and found[1 - want] is None, (i, found)
+    t2 = time.perf_counter()
+    print(f"{'':14s} {len(base)} equations factored once in {t1 - t0:.3f}s, {2 * len(bits)} bit_assert guesses on copies in {t2 - t1:.3f}s  ok")
 
 if __name__ == "__main__":
     recover(GaloisLFSR, 1)

@@ -677,56 +677,8 @@ PyObject *factor_pivots(FactorObject *self, void *)
 	return t;
 }
 
-PyObject *factor_solve(FactorObject *self, PyObject *rhs)
-{
-	if (!factor_open(self)) return nullptr;
-	const int64_t rw = (self->rows + 63) / 64;
-	std::vector<uint64_t> words;
-	const uint64_t *src = nullptr;
-	int64_t nrhs = 0, stride = rw;
-	Py_buffer view{};
-	bool have_view = false;
-	if (PyList_Check(rhs)) {
-		nrhs = PyList_GET_SIZE(rhs);
-		if (nrhs == 0) return PyList_New(0);
-		if (!rhs_list_words(rhs, self->rows, words)) return nullptr;
-		src = words.data();
-	} else if (PyObject_CheckBuffer(rhs)) {
-		if (PyObject_GetBuffer(rhs, &view, PyBUF_C_CONTIGUOUS | PyBUF_FORMAT) < 0) return nullptr;
-		have_view = true;
-		const char *f = view.format ? view.format : "B";
-		if (*f == '<' || *f == '=' || *f == '@') f++;
-		if (view.ndim != 2 || view.itemsize != 8 || !(strcmp(f, "Q") == 0 || strcmp(f, "L") == 0)) {
-			PyBuffer_Release(&view);
-			PyErr_SetString(PyExc_TypeError, "right-hand sides as a buffer: a C-contiguous 2-D uint64 array");
-			return nullptr;
-		}
-		nrhs = view.shape[0];
-		stride = view.shape[1];
-		if (stride < rw) {
-			PyBuffer_Release(&view);
-			PyErr_SetString(PyExc_ValueError, "the right-hand-side array needs ceil(rows / 64) words per row");
-			return nullptr;
-		}
-		if (nrhs == 0) { PyBuffer_Release(&view); return PyList_New(0); }
-		src = static_cast<const uint64_t *>(view.buf);
-	} else {
-		PyErr_SetString(PyExc_TypeError, "The right-hand sides must be a list of integers or a 2-D uint64 array");
-		return nullptr;
-	}
-	std::vector<gf2bv_result *> res((size_t)nrhs, nullptr);
-	int rc;
-	gf2bv_factor *h = self->h;
-	Py_BEGIN_ALLOW_THREADS
-	rc = gf2bv_factor_solve(h, src, nrhs, stride, res.data());
-	Py_END_ALLOW_THREADS
-	if (have_view) PyBuffer_Release(&view);
-	if (rc != GF2BV_OK) {
-		for (gf2bv_result *r : res) if (r) gf2bv_result_free(r);
-		return raise_rc(rc, "solve");
-	}
-	return results_to_list(res, self->mode, self->device);
-}
+// (the body follows RhsInput, which every entry that takes right-hand sides shares)
+PyObject *factor_solve(FactorObject *self, PyObject *rhs);
 
 // append(equations): equations added below the factored ones -- a list of equation ints (bit 0 ignored) or a C-contiguous 2-D
 // uint64 array of n x words words in the same bit order (m4ri_solve_packed's layout); the handle then stands for the stacked matrix
@@ -775,6 +727,19 @@ PyObject *factor_append(FactorObject *self, PyObject *eqs)
 	}
 	if (rc != GF2BV_OK) return raise_rc(rc, "append");
 	self->rows = gf2bv_factor_rows(h);
+	Py_RETURN_NONE;
+}
+
+struct QuadBuffers;
+bool factor_append_quad_impl(FactorObject *self, PyObject *const *args);
+
+// append_quad(lin, term_off, ta, tb, n_lin): factored quadratic equations (m4ri_factor_quad_packed's arrays) added below the factored
+// ones, expanded on the device (gf2bv_factor_append_quad_terms); n_lin must be the one the factorization was made with
+PyObject *factor_append_quad(FactorObject *self, PyObject *const *args, Py_ssize_t nargs)
+{
+	if (nargs != 5) { PyErr_SetString(PyExc_TypeError, "append_quad requires 5 arguments"); return nullptr; }
+	if (!factor_open(self)) return nullptr;
+	if (!factor_append_quad_impl(self, args)) return nullptr;
 	Py_RETURN_NONE;
 }
 
@@ -830,6 +795,8 @@ PyMethodDef factor_methods[] = {
 	 "solve(rhs)\n--\n\nOne m4ri_solve result per right-hand side (a list of ints, bit r = affine term of equation r, or an nrhs x words uint64 array)."},
 	{"append", (PyCFunction)factor_append, METH_O,
 	 "append(equations)\n--\n\nAdd equations (a list of ints, bit 0 ignored, or an n x words uint64 array in the same bit order) below the factored ones; later solves take ceil(rows / 64)-word right-hand sides of the stacked system."},
+	{"append_quad", (PyCFunction)(void (*)(void))factor_append_quad, METH_FASTCALL,
+	 "append_quad(lin, term_off, ta, tb, n_lin)\n--\n\nAdd factored quadratic equations (m4ri_factor_quad_packed's arrays) below the factored ones; they are expanded on the device."},
 	{"copy", (PyCFunction)factor_copy, METH_NOARGS, "copy()\n--\n\nAn independent Factorization with the same state (a device-to-device copy, no factorization)."},
 	{"close", (PyCFunction)factor_close, METH_NOARGS, "close()\n--\n\nRelease the device memory; later use raises ValueError."},
 	{"__enter__", (PyCFunction)factor_enter, METH_NOARGS, nullptr},
@@ -946,6 +913,321 @@ PyObject *py_m4ri_solve_quad_packed(PyObject *, PyObject *const *args, Py_ssize_
 	}
 	for (int k = 0; k < got; k++) PyBuffer_Release(&view[k]);
 	return nullptr;
+}
+
+// ---- the packed front-ends in front of the kept factorization, the shared elimination and the batch --------------------------
+// The factored form of a quadratic system as four C-contiguous buffers (m4ri_solve_quad_packed's arguments), checked against each
+// other and against n_lin before the library sees them: whole rows of Wl = ceil((n_lin + 1) / 64) words, one offset per row and one
+// more, offsets that start at 0, never decrease and end at the number of operands.  TypeError for what is no buffer, ValueError for
+// a shape.
+struct QuadBuffers {
+	Py_buffer view[4];
+	int got = 0;
+	Py_ssize_t n = 0, live = 0, nterms = 0;
+	const uint64_t *lin = nullptr, *ta = nullptr, *tb = nullptr;
+	const int64_t *off = nullptr;
+	QuadBuffers() = default;
+	QuadBuffers(const QuadBuffers &) = delete;
+	QuadBuffers &operator=(const QuadBuffers &) = delete;
+	~QuadBuffers() { for (int k = 0; k < got; k++) PyBuffer_Release(&view[k]); }
+	bool parse(PyObject *const *args, PyObject *n_obj)
+	{
+		n = PyLong_AsSsize_t(n_obj);
+		if (n == -1 && PyErr_Occurred()) return false;
+		if (n < 1 || n > 65535) { PyErr_SetString(PyExc_ValueError, "n_lin must be 1..65535"); return false; }
+		const Py_ssize_t wl = (n + 1 + 63) / 64;
+		for (; got < 4; got++)
+			if (PyObject_GetBuffer(args[got], &view[got], PyBUF_C_CONTIGUOUS) != 0) return false;
+		live = view[0].len / (wl * 8);
+		nterms = view[2].len / (wl * 8);
+		off = static_cast<const int64_t *>(view[1].buf);
+		const char *bad = nullptr;
+		if (view[0].len != live * wl * 8) bad = "lin must hold whole rows of ceil((n_lin + 1) / 64) 64-bit words";
+		else if (view[1].len != (live + 1) * 8) bad = "term_off must hold one int64 per row of lin and one more";
+		else if (view[2].len != nterms * wl * 8 || view[3].len != view[2].len) bad = "ta and tb must hold the same number of whole operands";
+		else if (off[0] != 0) bad = "term_off must start at 0";
+		else if (off[live] != nterms) bad = "term_off must end at the number of operands in ta";
+		else
+			for (Py_ssize_t r = 0; r < live; r++)
+				if (off[r + 1] < off[r]) { bad = "term_off must not decrease"; break; }
+		if (bad) { PyErr_SetString(PyExc_ValueError, bad); return false; }
+		lin = static_cast<const uint64_t *>(view[0].buf);
+		ta = static_cast<const uint64_t *>(view[2].buf);
+		tb = static_cast<const uint64_t *>(view[3].buf);
+		return true;
+	}
+	Py_ssize_t cols() const { return n + n * (n - 1) / 2; }
+};
+
+// rows x words packed equations (m4ri_solve_packed's buffer) as 32-bit digits: two per word
+struct PackedRows {
+	Py_buffer view{};
+	bool have = false;
+	std::vector<int64_t> off;
+	PackedRows() = default;
+	PackedRows(const PackedRows &) = delete;
+	PackedRows &operator=(const PackedRows &) = delete;
+	~PackedRows() { if (have) PyBuffer_Release(&view); }
+	bool parse(PyObject *buf, Py_ssize_t rows, Py_ssize_t words, Py_ssize_t cols)
+	{
+		if (PyObject_GetBuffer(buf, &view, PyBUF_C_CONTIGUOUS) != 0) return false;
+		have = true;
+		if (rows < 0 || words <= 0 || view.len != rows * words * 8 || words * 64 < cols + 1) {
+			PyErr_SetString(PyExc_ValueError, "buffer must hold rows x words 64-bit words covering cols + 1 bits");
+			return false;
+		}
+		try { off.resize((size_t)rows + 1); } catch (const std::bad_alloc &) { PyErr_NoMemory(); return false; }
+		for (Py_ssize_t r = 0; r <= rows; r++) off[(size_t)r] = (int64_t)r * words * 2;
+		return true;
+	}
+	const uint32_t *digits() const { return static_cast<const uint32_t *>(view.buf); }
+};
+
+// right-hand sides, for Factorization.solve and every m4ri_solve_rhs_*packed: a list of non-negative ints or a C-contiguous 2-D
+// uint64 array of nrhs x >= ceil(rows / 64) words
+struct RhsInput {
+	std::vector<uint64_t> words;
+	Py_buffer view{};
+	bool have = false;
+	const uint64_t *src = nullptr;
+	int64_t nrhs = 0, stride = 0;
+	RhsInput() = default;
+	RhsInput(const RhsInput &) = delete;
+	RhsInput &operator=(const RhsInput &) = delete;
+	~RhsInput() { if (have) PyBuffer_Release(&view); }
+	bool parse(PyObject *rhs, int64_t rows)
+	{
+		const int64_t rw = (rows + 63) / 64;
+		stride = rw;
+		if (PyList_Check(rhs)) {
+			nrhs = PyList_GET_SIZE(rhs);
+			if (nrhs && !rhs_list_words(rhs, rows, words)) return false;
+			src = words.data();
+			return true;
+		}
+		if (!PyObject_CheckBuffer(rhs)) {
+			PyErr_SetString(PyExc_TypeError, "The right-hand sides must be a list of integers or a 2-D uint64 array");
+			return false;
+		}
+		if (PyObject_GetBuffer(rhs, &view, PyBUF_C_CONTIGUOUS | PyBUF_FORMAT) < 0) return false;
+		have = true;
+		const char *f = view.format ? view.format : "B";
+		if (*f == '<' || *f == '=' || *f == '@') f++;
+		if (view.ndim != 2 || view.itemsize != 8 || !(strcmp(f, "Q") == 0 || strcmp(f, "L") == 0)) {
+			PyErr_SetString(PyExc_TypeError, "right-hand sides as a buffer: a C-contiguous 2-D uint64 array");
+			return false;
+		}
+		nrhs = view.shape[0];
+		stride = view.shape[1];
+		if (stride < rw) {
+			PyErr_SetString(PyExc_ValueError, "the right-hand-side array needs ceil(rows / 64) words per row");
+			return false;
+		}
+		src = static_cast<const uint64_t *>(view.buf);
+		return true;
+	}
+};
+
+PyObject *factor_solve(FactorObject *self, PyObject *rhs)
+{
+	if (!factor_open(self)) return nullptr;
+	RhsInput ri;
+	if (!ri.parse(rhs, self->rows)) return nullptr;
+	if (ri.nrhs == 0) return PyList_New(0);
+	std::vector<gf2bv_result *> res((size_t)ri.nrhs, nullptr);
+	int rc;
+	gf2bv_factor *h = self->h;
+	Py_BEGIN_ALLOW_THREADS
+	rc = gf2bv_factor_solve(h, ri.src, ri.nrhs, ri.stride, res.data());
+	Py_END_ALLOW_THREADS
+	if (rc != GF2BV_OK) {
+		for (gf2bv_result *r : res) if (r) gf2bv_result_free(r);
+		return raise_rc(rc, "solve");
+	}
+	return results_to_list(res, self->mode, self->device);
+}
+
+PyObject *new_factorization(gf2bv_factor *h, int64_t rows, int64_t cols, long mode, int device)
+{
+	FactorObject *f = PyObject_New(FactorObject, Factorization_Type);
+	if (!f) { gf2bv_factor_free(h); return nullptr; }
+	f->h = h; f->rows = rows; f->cols = cols; f->mode = mode; f->device = device;
+	return (PyObject *)f;
+}
+
+bool parse_mode(PyObject *obj, long *mode)
+{
+	*mode = PyLong_AsLong(obj);
+	if (*mode == -1 && PyErr_Occurred()) return false;
+	if (*mode != GF2BV_MODE_SINGLE && *mode != GF2BV_MODE_AFFINE_SPACE) { PyErr_SetString(PyExc_ValueError, "Invalid mode"); return false; }
+	return true;
+}
+
+bool factor_append_quad_impl(FactorObject *self, PyObject *const *args)
+{
+	QuadBuffers qb;
+	if (!qb.parse(args, args[4])) return false;
+	if (qb.cols() != self->cols) { PyErr_SetString(PyExc_ValueError, "n_lin does not match the factorization's columns"); return false; }
+	if (qb.live == 0) return true;
+	gf2bv_factor *h = self->h;
+	int rc;
+	Py_BEGIN_ALLOW_THREADS
+	rc = gf2bv_factor_append_quad_terms(h, qb.lin, qb.off, qb.ta, qb.tb, qb.live, qb.n);
+	Py_END_ALLOW_THREADS
+	if (rc != GF2BV_OK) { raise_rc(rc, "append"); return false; }
+	self->rows = gf2bv_factor_rows(h);
+	return true;
+}
+
+// m4ri_factor_packed(buffer, rows, words, cols, mode[, device]) -> Factorization: m4ri_factor on m4ri_solve_packed's buffer
+// (gf2bv_factor_digits, 32 payload bits per digit)
+PyObject *py_m4ri_factor_packed(PyObject *, PyObject *const *args, Py_ssize_t nargs)
+{
+	if (nargs != 5 && nargs != 6) { PyErr_SetString(PyExc_TypeError, "m4ri_factor_packed requires 5 arguments"); return nullptr; }
+	int device = default_device();
+	if (nargs == 6 && !parse_device(args[5], &device)) return nullptr;
+	const Py_ssize_t rows = PyLong_AsSsize_t(args[1]), words = PyLong_AsSsize_t(args[2]);
+	if ((rows == -1 || words == -1) && PyErr_Occurred()) return nullptr;
+	Py_ssize_t cols;
+	long mode;
+	if (!parse_cols_mode(args[3], args[4], &cols, &mode) || !rows_cover_cols(rows, cols)) return nullptr;
+	PackedRows pr;
+	if (!pr.parse(args[0], rows, words, cols)) return nullptr;
+	gf2bv_factor *h = nullptr;
+	int rc;
+	Py_BEGIN_ALLOW_THREADS
+	rc = gf2bv_factor_digits(pr.digits(), pr.off.data(), 32, rows, cols, (int)mode, device, &h);
+	Py_END_ALLOW_THREADS
+	if (rc != GF2BV_OK) return raise_rc(rc, "factorization");
+	return new_factorization(h, rows, cols, mode, device);
+}
+
+// The prologue of the entries that take the factored form and a row count: arguments `first` .. `first + 3` are the four buffers,
+// then n_lin, rows, mode at the given positions; rows must cover the rows of lin (`live_rows`: the batch entry's systems are checked
+// by its own offsets instead) and the columns
+bool parse_quad_call(PyObject *const *args, int n_at, int rows_at, int mode_at, bool live_rows, QuadBuffers &qb, Py_ssize_t *rows, long *mode)
+{
+	*rows = PyLong_AsSsize_t(args[rows_at]);
+	if (*rows == -1 && PyErr_Occurred()) return false;
+	if (!parse_mode(args[mode_at], mode) || !qb.parse(args, args[n_at])) return false;
+	if (live_rows && *rows < qb.live) { PyErr_SetString(PyExc_ValueError, "rows must be at least the rows of lin"); return false; }
+	return rows_cover_cols(*rows, qb.cols());
+}
+
+// m4ri_factor_quad_packed(lin, term_off, ta, tb, n_lin, rows, mode[, device]) -> Factorization over n_lin + n_lin(n_lin-1)/2
+// columns: m4ri_solve_quad_packed's arguments, expanded on the device and factored there (gf2bv_factor_quad_terms)
+PyObject *py_m4ri_factor_quad_packed(PyObject *, PyObject *const *args, Py_ssize_t nargs)
+{
+	if (nargs != 7 && nargs != 8) { PyErr_SetString(PyExc_TypeError, "m4ri_factor_quad_packed requires 7 arguments"); return nullptr; }
+	int device = default_device();
+	if (nargs == 8 && !parse_device(args[7], &device)) return nullptr;
+	Py_ssize_t rows;
+	long mode;
+	QuadBuffers qb;
+	if (!parse_quad_call(args, 4, 5, 6, true, qb, &rows, &mode)) return nullptr;
+	gf2bv_factor *h = nullptr;
+	int rc;
+	Py_BEGIN_ALLOW_THREADS
+	rc = gf2bv_factor_quad_terms(qb.lin, qb.off, qb.ta, qb.tb, qb.live, rows, qb.n, (int)mode, device, &h);
+	Py_END_ALLOW_THREADS
+	if (rc != GF2BV_OK) return raise_rc(rc, "factorization");
+	return new_factorization(h, rows, qb.cols(), mode, device);
+}
+
+// m4ri_solve_rhs_packed(buffer, rows, words, cols, mode, rhs[, device]) -> list: m4ri_solve_rhs on m4ri_solve_packed's buffer;
+// rhs as Factorization.solve takes it
+PyObject *py_m4ri_solve_rhs_packed(PyObject *, PyObject *const *args, Py_ssize_t nargs)
+{
+	if (nargs != 6 && nargs != 7) { PyErr_SetString(PyExc_TypeError, "m4ri_solve_rhs_packed requires 6 arguments"); return nullptr; }
+	int device = default_device();
+	if (nargs == 7 && !parse_device(args[6], &device)) return nullptr;
+	const Py_ssize_t rows = PyLong_AsSsize_t(args[1]), words = PyLong_AsSsize_t(args[2]);
+	if ((rows == -1 || words == -1) && PyErr_Occurred()) return nullptr;
+	Py_ssize_t cols;
+	long mode;
+	if (!parse_cols_mode(args[3], args[4], &cols, &mode) || !rows_cover_cols(rows, cols)) return nullptr;
+	PackedRows pr;
+	if (!pr.parse(args[0], rows, words, cols)) return nullptr;
+	RhsInput ri;
+	if (!ri.parse(args[5], rows)) return nullptr;
+	if (ri.nrhs == 0) return PyList_New(0);
+	std::vector<gf2bv_result *> res((size_t)ri.nrhs, nullptr);
+	int rc;
+	Py_BEGIN_ALLOW_THREADS
+	rc = gf2bv_solve_rhs_digits(pr.digits(), pr.off.data(), 32, rows, cols, ri.src, ri.nrhs, ri.stride, (int)mode, device, res.data());
+	Py_END_ALLOW_THREADS
+	if (rc != GF2BV_OK) {
+		for (gf2bv_result *r : res) if (r) gf2bv_result_free(r);
+		return raise_rc(rc, "solve");
+	}
+	return results_to_list(res, mode, device);
+}
+
+// m4ri_solve_rhs_quad_packed(lin, term_off, ta, tb, n_lin, rows, mode, rhs[, device]) -> list: one elimination of the expanded
+// system for every right-hand side (gf2bv_solve_rhs_quad_terms); the constants of the factored rows are NOT read, rhs holds them
+PyObject *py_m4ri_solve_rhs_quad_packed(PyObject *, PyObject *const *args, Py_ssize_t nargs)
+{
+	if (nargs != 8 && nargs != 9) { PyErr_SetString(PyExc_TypeError, "m4ri_solve_rhs_quad_packed requires 8 arguments"); return nullptr; }
+	int device = default_device();
+	if (nargs == 9 && !parse_device(args[8], &device)) return nullptr;
+	Py_ssize_t rows;
+	long mode;
+	QuadBuffers qb;
+	if (!parse_quad_call(args, 4, 5, 6, true, qb, &rows, &mode)) return nullptr;
+	RhsInput ri;
+	if (!ri.parse(args[7], rows)) return nullptr;
+	if (ri.nrhs == 0) return PyList_New(0);
+	std::vector<gf2bv_result *> res((size_t)ri.nrhs, nullptr);
+	int rc;
+	Py_BEGIN_ALLOW_THREADS
+	rc = gf2bv_solve_rhs_quad_terms(qb.lin, qb.off, qb.ta, qb.tb, qb.live, rows, qb.n, ri.src, ri.nrhs, ri.stride, (int)mode, device, res.data());
+	Py_END_ALLOW_THREADS
+	if (rc != GF2BV_OK) {
+		for (gf2bv_result *r : res) if (r) gf2bv_result_free(r);
+		return raise_rc(rc, "solve");
+	}
+	return results_to_list(res, mode, device);
+}
+
+// m4ri_solve_many_quad_packed(lin, term_off, ta, tb, sys_row_off, n_lin, rows, mode[, device]) -> list, one element per system:
+// independent quadratic systems over the same n_lin as one concatenated term set, system s the rows sys_row_off[s] ..
+// sys_row_off[s + 1] (a C-contiguous int64 buffer of nsys + 1 offsets from 0), each padded to `rows` rows on the device and all
+// solved as lock-step gangs (gf2bv_solve_batch_quad_terms); element s is what m4ri_solve_quad_packed returns for system s
+PyObject *py_m4ri_solve_many_quad_packed(PyObject *, PyObject *const *args, Py_ssize_t nargs)
+{
+	if (nargs != 8 && nargs != 9) { PyErr_SetString(PyExc_TypeError, "m4ri_solve_many_quad_packed requires 8 arguments"); return nullptr; }
+	int device = default_device();
+	if (nargs == 9 && !parse_device(args[8], &device)) return nullptr;
+	Py_ssize_t rows;
+	long mode;
+	QuadBuffers qb;
+	if (!parse_quad_call(args, 5, 6, 7, false, qb, &rows, &mode)) return nullptr;
+	Py_buffer sv;
+	if (PyObject_GetBuffer(args[4], &sv, PyBUF_C_CONTIGUOUS) != 0) return nullptr;
+	const int64_t *sys = static_cast<const int64_t *>(sv.buf);
+	const Py_ssize_t nsys = sv.len / 8 - 1;
+	const char *bad = nullptr;
+	if (sv.len % 8 || nsys < 0) bad = "sys_row_off must hold one int64 per system and one more";
+	else if (sys[0] != 0) bad = "sys_row_off must start at 0";
+	else if (sys[nsys] != qb.live) bad = "sys_row_off must end at the rows of lin";
+	else
+		for (Py_ssize_t k = 0; k < nsys; k++) {
+			if (sys[k + 1] < sys[k]) { bad = "sys_row_off must not decrease"; break; }
+			if (sys[k + 1] - sys[k] > rows) { bad = "rows must be at least the rows of every system"; break; }
+		}
+	if (bad) { PyBuffer_Release(&sv); PyErr_SetString(PyExc_ValueError, bad); return nullptr; }
+	if (nsys == 0) { PyBuffer_Release(&sv); return PyList_New(0); }
+	std::vector<gf2bv_result *> res((size_t)nsys, nullptr);
+	int rc;
+	Py_BEGIN_ALLOW_THREADS
+	rc = gf2bv_solve_batch_quad_terms(qb.lin, qb.off, qb.ta, qb.tb, sys, nsys, rows, qb.n, (int)mode, device, res.data());
+	Py_END_ALLOW_THREADS
+	PyBuffer_Release(&sv);
+	if (rc != GF2BV_OK) {
+		for (gf2bv_result *r : res) if (r) gf2bv_result_free(r);
+		return raise_rc(rc, "solve");
+	}
+	return results_to_list(res, mode, device);
 }
 
 // m4ri_solve_many(list_of_equation_lists, cols, mode[, devices]) -> list of (None | int | AffineSpace).
@@ -1448,6 +1730,16 @@ PyMethodDef module_methods[] = {
 	 "m4ri_solve_rhs(equations, cols, mode, rhs, device=None)\n--\n\nSolve one coefficient matrix against every right-hand side in rhs (bit r = affine term of equation r) with one elimination; list of m4ri_solve results."},
 	{"m4ri_factor", FAST(py_m4ri_factor), METH_FASTCALL,
 	 "m4ri_factor(equations, cols, mode, device=None)\n--\n\nFactor the coefficient matrix once (bit 0 of every equation ignored); Factorization.solve(rhs) equals m4ri_solve_rhs(equations, cols, mode, rhs)."},
+	{"m4ri_factor_packed", FAST(py_m4ri_factor_packed), METH_FASTCALL,
+	 "m4ri_factor_packed(buffer, rows, words, cols, mode, device=None)\n--\n\nm4ri_factor on m4ri_solve_packed's buffer."},
+	{"m4ri_factor_quad_packed", FAST(py_m4ri_factor_quad_packed), METH_FASTCALL,
+	 "m4ri_factor_quad_packed(lin, term_off, ta, tb, n_lin, rows, mode, device=None)\n--\n\nA Factorization of the linearised matrix of factored quadratic equations, expanded on the device."},
+	{"m4ri_solve_rhs_packed", FAST(py_m4ri_solve_rhs_packed), METH_FASTCALL,
+	 "m4ri_solve_rhs_packed(buffer, rows, words, cols, mode, rhs, device=None)\n--\n\nm4ri_solve_rhs on m4ri_solve_packed's buffer; rhs a list of ints or an nrhs x words uint64 array."},
+	{"m4ri_solve_rhs_quad_packed", FAST(py_m4ri_solve_rhs_quad_packed), METH_FASTCALL,
+	 "m4ri_solve_rhs_quad_packed(lin, term_off, ta, tb, n_lin, rows, mode, rhs, device=None)\n--\n\nm4ri_solve_rhs on factored quadratic equations, expanded on the device."},
+	{"m4ri_solve_many_quad_packed", FAST(py_m4ri_solve_many_quad_packed), METH_FASTCALL,
+	 "m4ri_solve_many_quad_packed(lin, term_off, ta, tb, sys_row_off, n_lin, rows, mode, device=None)\n--\n\nIndependent factored quadratic systems of one concatenated term set, expanded by one launch and solved as lock-step gangs."},
 	{"m4ri_solve_many", FAST(py_m4ri_solve_many), METH_FASTCALL,
 	 "m4ri_solve_many(systems, cols, mode, devices=None)\n--\n\nSolve a list of same-shape systems in one batched call, sharded over the given GPUs (None: the default device, \"all\": every visible one); list of m4ri_solve results."},
 	{"to_bits", FAST(py_to_bits), METH_FASTCALL, "to_bits(n, a)\n--\n\nLow n bits of a, LSB first."},

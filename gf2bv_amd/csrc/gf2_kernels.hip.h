@@ -4817,9 +4817,10 @@ __device__ __forceinline__ u64 qx_word(const u64 *lin, const u64 *A, const u64 *
 	return acc;
 }
 
-__global__ void __launch_bounds__(256)
-k_quad_expand(const u64 *__restrict__ lin, const i64 *__restrict__ term_off, const u64 *__restrict__ ta, const u64 *__restrict__ tb,
-              i64 rows_live, i64 rows, int n, int Wl, int tch, u64 *__restrict__ out, i64 stride)
+// rows blockIdx.x, blockIdx.x + gridDim.x, ... of ONE system (lin / term_off from its first row, out its first output row)
+__device__ __forceinline__ void
+qx_expand_rows(const u64 *__restrict__ lin, const i64 *__restrict__ term_off, const u64 *__restrict__ ta, const u64 *__restrict__ tb,
+               i64 rows_live, i64 rows, int n, int Wl, int tch, u64 *__restrict__ out, i64 stride)
 {
 	extern __shared__ u64 qx_lds[];                    // [lin: Wl | A: tch x Wl | B: tch x Wl]
 	u64 *sl = qx_lds, *sa = sl + Wl, *sb = sa + (i64)tch * Wl;
@@ -4850,4 +4851,24 @@ k_quad_expand(const u64 *__restrict__ lin, const i64 *__restrict__ term_off, con
 			first = false;
 		} while (t0 < t1);
 	}
+}
+
+__global__ void __launch_bounds__(256)
+k_quad_expand(const u64 *__restrict__ lin, const i64 *__restrict__ term_off, const u64 *__restrict__ ta, const u64 *__restrict__ tb,
+              i64 rows_live, i64 rows, int n, int Wl, int tch, u64 *__restrict__ out, i64 stride)
+{
+	qx_expand_rows(lin, term_off, ta, tb, rows_live, rows, n, Wl, tch, out, stride);
+}
+
+// The batched instance (gf2bv_solve_batch_quad_terms): blockIdx.y = system.  The systems' factored rows are ONE concatenated term
+// set -- system s owns rows sys_row_off[s] .. sys_row_off[s + 1] of lin / term_off (the offsets into ta / tb stay absolute) -- and
+// system s is written to out + s x sys_stride as `rows` rows: its live rows expanded, the rest zeros, so the host pads nothing.
+// Same split per system as k_quad_expand (a workgroup per row, one writer per word, 16-byte stores from consecutive lanes).  The
+// row offsets are checked by the host entry (0 <= live <= rows): every store lands inside the system's rows x stride words.
+__global__ void __launch_bounds__(256)
+k_quad_expand_batch(const u64 *__restrict__ lin, const i64 *__restrict__ term_off, const u64 *__restrict__ ta, const u64 *__restrict__ tb,
+                    const i64 *__restrict__ sys_row_off, i64 rows, int n, int Wl, int tch, u64 *__restrict__ out, i64 stride, i64 sys_stride)
+{
+	const i64 r0 = sys_row_off[blockIdx.y], live = sys_row_off[blockIdx.y + 1] - r0;
+	qx_expand_rows(lin + r0 * Wl, term_off + r0, ta, tb, live < rows ? live : rows, rows, n, Wl, tch, out + (i64)blockIdx.y * sys_stride, stride);
 }

@@ -4726,17 +4726,70 @@ int enqueue_quad_expand(const QuadTerms &q, u64 *d_aug, i64 stride, hipStream_t 
 	return GF2BV_OK;
 }
 
-// the factored form of host memory uploaded on `st` into buffers of `scratch`: `d` = q with device pointers
-int upload_quad_terms(const QuadTerms &q, QuadTerms &d, Scratch &scratch, int device, hipStream_t st)
+// A pool buffer of a quadratic entry: a refusal is GF2BV_ERR_NOMEM (the expanded rows of a large system or batch may not fit; an
+// append tells a refusal, which leaves the handle as it was, from a failure that does not)
+int quad_alloc(Scratch &scratch, void **out, size_t bytes, int device)
+{
+	const hipError_t e = scratch.alloc(out, std::max<size_t>(bytes, 16), device);
+	if (e == hipErrorOutOfMemory) {
+		(void)hipGetLastError();
+		return fail(GF2BV_ERR_NOMEM, "the factored rows or their expansion do not fit on the device");
+	}
+	if (e != hipSuccess) return fail(GF2BV_ERR_HIP, "expansion buffers", e);
+	return GF2BV_OK;
+}
+
+// The batched form: nsys systems over one concatenated term set, system s owning the rows sys_off[s] .. sys_off[s + 1], at most
+// q.rows of them; q.rows_live becomes sys_off[nsys], the rows of the whole set
+int check_quad_batch(QuadTerms &q, const i64 *sys_off, i64 nsys)
+{
+	if (!sys_off) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (sys_off[0] != 0) return fail(GF2BV_ERR_ARG, "system row offsets must start at 0");
+	for (i64 s = 0; s < nsys; s++) {
+		if (sys_off[s + 1] < sys_off[s]) return fail(GF2BV_ERR_ARG, "system row offsets must not decrease");
+		if (sys_off[s + 1] - sys_off[s] > q.rows) return fail(GF2BV_ERR_ARG, "a system's live rows must be 0..rows");
+	}
+	if (sys_off[nsys] >= (1ll << 31) - 64) return fail(GF2BV_ERR_ARG, "the rows of all systems together must stay below 2^31 - 64");
+	const i64 rows = q.rows;
+	q.rows_live = q.rows = sys_off[nsys];          // (check_quad_terms: the concatenated set as one system of all its rows)
+	const int rc = check_quad_terms(q, true);
+	q.rows = rows;
+	return rc;
+}
+
+// (device pointers, already checked) the batched kernel on `st`: system s at d_aug + s x sys_stride, q.rows x stride words
+int enqueue_quad_expand_batch(const QuadTerms &q, const i64 *d_sys_off, i64 nsys, u64 *d_aug, i64 stride, i64 sys_stride, hipStream_t st)
+{
+	if (q.rows == 0 || nsys == 0) return GF2BV_OK;
+	const i64 wl = q.wl();
+	const int tch = (int)std::max<i64>(1, std::min<i64>(8, (65536 / 8 / wl - 1) / 2));
+	const unsigned block = (unsigned)std::min<i64>(256, round_up(std::max<i64>(stride / 2, 1), 64));
+	// a workgroup per row at a time; a few thousand workgroups in all, however many systems share the launch
+	const unsigned gx = (unsigned)std::min<i64>(q.rows, std::max<i64>(256, 256 * 8 / nsys));
+	for (i64 s0 = 0; s0 < nsys; s0 += 65535) {      // (grid y holds 65535 systems)
+		const unsigned ns = (unsigned)std::min<i64>(65535, nsys - s0);
+		hipLaunchKernelGGL(k_quad_expand_batch, dim3(gx, ns), dim3(block), sizeof(u64) * (size_t)((1 + 2 * tch) * wl), st, q.lin, q.off, q.ta, q.tb,
+		                   d_sys_off + s0, q.rows, (int)q.n, (int)wl, tch, d_aug + s0 * sys_stride, stride, sys_stride);
+	}
+	HIPCHK(hipGetLastError());
+	return GF2BV_OK;
+}
+
+// the factored form of host memory uploaded on `st` into buffers of `scratch`: `d` = q with device pointers; `nomem`: a refused
+// buffer is GF2BV_ERR_NOMEM (quad_alloc) instead of GF2BV_ERR_HIP
+int upload_quad_terms(const QuadTerms &q, QuadTerms &d, Scratch &scratch, int device, hipStream_t st, bool nomem = false)
 {
 	d = q;
 	const i64 wl = q.wl(), T = q.off[q.rows_live];
 	u64 *lin = nullptr, *ta = nullptr, *tb = nullptr;
 	i64 *off = nullptr;
-	HIPCHK(scratch.alloc((void **)&lin, sizeof(u64) * (size_t)std::max<i64>(1, q.rows_live * wl), device));
-	HIPCHK(scratch.alloc((void **)&off, sizeof(i64) * (size_t)(q.rows_live + 1), device));
-	HIPCHK(scratch.alloc((void **)&ta, sizeof(u64) * (size_t)std::max<i64>(1, T * wl), device));
-	HIPCHK(scratch.alloc((void **)&tb, sizeof(u64) * (size_t)std::max<i64>(1, T * wl), device));
+	const size_t bytes[4] = { sizeof(u64) * (size_t)std::max<i64>(1, q.rows_live * wl), sizeof(i64) * (size_t)(q.rows_live + 1),
+	                          sizeof(u64) * (size_t)std::max<i64>(1, T * wl), sizeof(u64) * (size_t)std::max<i64>(1, T * wl) };
+	void **const bufs[4] = { (void **)&lin, (void **)&off, (void **)&ta, (void **)&tb };
+	for (int k = 0; k < 4; k++) {
+		if (!nomem) HIPCHK(scratch.alloc(bufs[k], bytes[k], device));      // (gf2bv_quad_expand_words, gf2bv_solve_quad_terms: as they always did)
+		else if (int rc = quad_alloc(scratch, bufs[k], bytes[k], device)) return rc;
+	}
 	if (q.rows_live > 0) HIPCHK(hipMemcpyAsync(lin, q.lin, sizeof(u64) * (size_t)(q.rows_live * wl), hipMemcpyHostToDevice, st));
 	HIPCHK(hipMemcpyAsync(off, q.off, sizeof(i64) * (size_t)(q.rows_live + 1), hipMemcpyHostToDevice, st));
 	if (T > 0) {
@@ -4835,5 +4888,168 @@ int gf2bv_solve_quad_terms(const uint64_t *lin, const int64_t *term_off, const u
 	return gf2bv_solve_device(d_aug, rows, q.cols(), ds, mode, device, ps.st, 0, out);      // same stream: ordered behind the expansion
 	});
 }
+
+// ---- the entries that keep, append to, share and batch an expansion: each is upload, expansion into a pool buffer and the device
+// entry underneath on ONE pool stream (ordered behind the expansion; the host waits only where that entry waits).  The buffers go
+// back to the pool when the entry returns: a handle has its own copy by then, a result is on the host.
+#define QUAD_TERMS(q)                                                                                       \
+	QuadTerms q, d;                                                                                         \
+	q.lin = reinterpret_cast<const u64 *>(lin); q.off = reinterpret_cast<const i64 *>(term_off);            \
+	q.ta = reinterpret_cast<const u64 *>(ta); q.tb = reinterpret_cast<const u64 *>(tb);                     \
+	q.n = n_lin
+
+int gf2bv_factor_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t rows_live,
+                            int64_t rows, int64_t n_lin, int mode, int device, gf2bv_factor **out)
+{
+	return catching([&]() -> int {
+	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
+	*out = nullptr;
+	QUAD_TERMS(q);
+	q.rows_live = rows_live; q.rows = rows;
+	int rc = check_quad_terms(q, true);
+	if (!rc) rc = check_shape(rows, q.cols(), mode);
+	if (!rc) rc = check_device(device);
+	if (rc) return rc;
+	PoolStream ps; ps.device = device;
+	HIPCHK(pool().stream(&ps.st, device, 0));
+	Scratch scratch;
+	scratch.sync_first = ps.st;
+	if ((rc = upload_quad_terms(q, d, scratch, device, ps.st, true))) return rc;
+	const i64 ds = round_up(q.wt(), 2);
+	u64 *d_aug = nullptr;
+	if ((rc = quad_alloc(scratch, (void **)&d_aug, sizeof(u64) * (size_t)(rows * ds), device))) return rc;
+	if ((rc = enqueue_quad_expand(d, d_aug, ds, ps.st))) return rc;
+	return gf2bv_factor_device(d_aug, rows, q.cols(), ds, mode, device, ps.st, out);
+	});
+}
+
+int gf2bv_factor_append_quad_terms(gf2bv_factor *h, const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb,
+                                   int64_t rows, int64_t n_lin)
+{
+	return catching([&]() -> int {
+	if (!h) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (h->failed) return fail(GF2BV_ERR_ARG, kFailedHandle);
+	if (rows < 1) return fail(GF2BV_ERR_ARG, "rows must be at least 1");
+	QUAD_TERMS(q);
+	q.rows_live = q.rows = rows;
+	int rc = check_quad_terms(q, true);
+	if (rc) return rc;
+	if (q.cols() != h->cols) return fail(GF2BV_ERR_ARG, "n_lin does not match the handle's columns");
+	if (h->rows + rows >= (1ll << 31) - 64) return fail(GF2BV_ERR_ARG, "system too large");
+	const int device = h->device;
+	if ((rc = check_device(device))) return rc;
+	PoolStream ps; ps.device = device;
+	HIPCHK(pool().stream(&ps.st, device, 0));
+	Scratch scratch;
+	scratch.sync_first = ps.st;
+	// (the uploaded terms and the expansion are taken before gf2bv_factor_append_device takes its own buffers: a refusal of any
+	// of them leaves the handle as it was)
+	if ((rc = upload_quad_terms(q, d, scratch, device, ps.st, true))) return rc;
+	const i64 ds = round_up(q.wt(), 2);
+	u64 *d_aug = nullptr;
+	if ((rc = quad_alloc(scratch, (void **)&d_aug, sizeof(u64) * (size_t)(rows * ds), device))) return rc;
+	if ((rc = enqueue_quad_expand(d, d_aug, ds, ps.st))) return rc;
+	return gf2bv_factor_append_device(h, d_aug, rows, ds, ps.st);
+	});
+}
+
+int gf2bv_solve_rhs_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t rows_live,
+                               int64_t rows, int64_t n_lin, const uint64_t *rhs, int64_t nrhs, int64_t rhs_words, int mode, int device,
+                               gf2bv_result **out)
+{
+	return catching([&]() -> int {
+	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
+	for (i64 j = 0; j < nrhs; j++) out[j] = nullptr;
+	QUAD_TERMS(q);
+	q.rows_live = rows_live; q.rows = rows;
+	int rc = check_quad_terms(q, true);
+	if (!rc) rc = check_shape(rows, q.cols(), mode);
+	if (!rc) rc = check_rhs_args(rows, q.cols(), rhs, false, nrhs, rhs_words);
+	if (!rc) rc = check_device(device);
+	if (rc) return rc;
+	PoolStream ps; ps.device = device;
+	HIPCHK(pool().stream(&ps.st, device, 0));
+	Scratch scratch;
+	scratch.sync_first = ps.st;
+	if ((rc = upload_quad_terms(q, d, scratch, device, ps.st, true))) return rc;
+	const i64 ds = round_up(q.wt(), 2);
+	u64 *d_aug = nullptr, *d_rhs = nullptr;
+	if ((rc = quad_alloc(scratch, (void **)&d_aug, sizeof(u64) * (size_t)(rows * ds), device))) return rc;
+	if ((rc = quad_alloc(scratch, (void **)&d_rhs, sizeof(u64) * (size_t)(nrhs * rhs_words), device))) return rc;
+	HIPCHK(hipMemcpyAsync(d_rhs, rhs, sizeof(u64) * (size_t)(nrhs * rhs_words), hipMemcpyHostToDevice, ps.st));
+	if ((rc = enqueue_quad_expand(d, d_aug, ds, ps.st))) return rc;
+	// (the constant the expansion leaves in column `cols` is ignored there: the caller's rhs holds the constants)
+	return gf2bv_solve_rhs_device(d_aug, rows, q.cols(), ds, d_rhs, nrhs, rhs_words, mode, device, ps.st, 0, out);
+	});
+}
+
+int gf2bv_quad_expand_batch_words(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb,
+                                  const int64_t *sys_row_off, int64_t nsys, int64_t rows, int64_t n_lin, uint64_t *out_aug,
+                                  int64_t stride_words, int device)
+{
+	return catching([&]() -> int {
+	if (nsys < 0) return fail(GF2BV_ERR_ARG, "nsys must not be negative");
+	QUAD_TERMS(q);
+	q.rows = rows;
+	if (q.n < 1 || q.n > 65535) return fail(GF2BV_ERR_ARG, "n_lin must be at least 1 and n_lin + n_lin(n_lin-1)/2 below 2^31 - 64");
+	if (rows < 0 || rows >= (1ll << 31) - 64) return fail(GF2BV_ERR_ARG, "rows must be 0 .. 2^31 - 65");
+	int rc = check_quad_batch(q, reinterpret_cast<const i64 *>(sys_row_off), nsys);
+	if (rc) return rc;
+	if (!out_aug && rows > 0 && nsys > 0) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (stride_words < q.wt()) return fail(GF2BV_ERR_ARG, "stride_words does not cover cols+1 bits");
+	if ((rc = check_device(device))) return rc;
+	if (rows == 0 || nsys == 0) return GF2BV_OK;
+	PoolStream ps; ps.device = device;
+	HIPCHK(pool().stream(&ps.st, device, 0));
+	Scratch scratch;
+	scratch.sync_first = ps.st;
+	if ((rc = upload_quad_terms(q, d, scratch, device, ps.st, true))) return rc;
+	i64 *d_sys = nullptr;
+	if ((rc = quad_alloc(scratch, (void **)&d_sys, sizeof(i64) * (size_t)(nsys + 1), device))) return rc;
+	HIPCHK(hipMemcpyAsync(d_sys, sys_row_off, sizeof(i64) * (size_t)(nsys + 1), hipMemcpyHostToDevice, ps.st));
+	const i64 ds = round_up(stride_words, 2);
+	u64 *d_aug = nullptr;
+	if ((rc = quad_alloc(scratch, (void **)&d_aug, sizeof(u64) * (size_t)(nsys * rows * ds), device))) return rc;
+	d.rows = rows;
+	if ((rc = enqueue_quad_expand_batch(d, d_sys, nsys, d_aug, ds, rows * ds, ps.st))) return rc;
+	HIPCHK(hipMemcpy2DAsync(out_aug, stride_words * 8, d_aug, ds * 8, stride_words * 8, nsys * rows, hipMemcpyDeviceToHost, ps.st));
+	HIPCHK(hipStreamSynchronize(ps.st));
+	return GF2BV_OK;
+	});
+}
+
+int gf2bv_solve_batch_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb,
+                                 const int64_t *sys_row_off, int64_t nsys, int64_t rows, int64_t n_lin, int mode, int device,
+                                 gf2bv_result **out)
+{
+	return catching([&]() -> int {
+	if (!out || nsys < 0) return fail(GF2BV_ERR_ARG, "null pointer");
+	for (i64 s = 0; s < nsys; s++) out[s] = nullptr;
+	QUAD_TERMS(q);
+	q.rows = rows;
+	if (q.n < 1 || q.n > 65535) return fail(GF2BV_ERR_ARG, "n_lin must be at least 1 and n_lin + n_lin(n_lin-1)/2 below 2^31 - 64");
+	int rc = check_shape(rows, q.cols(), mode);
+	if (!rc) rc = check_quad_batch(q, reinterpret_cast<const i64 *>(sys_row_off), nsys);
+	if (!rc) rc = check_device(device);
+	if (rc) return rc;
+	if (nsys == 0) return GF2BV_OK;
+	PoolStream ps; ps.device = device;
+	HIPCHK(pool().stream(&ps.st, device, 0));
+	Scratch scratch;
+	scratch.sync_first = ps.st;
+	if ((rc = upload_quad_terms(q, d, scratch, device, ps.st, true))) return rc;
+	i64 *d_sys = nullptr;
+	if ((rc = quad_alloc(scratch, (void **)&d_sys, sizeof(i64) * (size_t)(nsys + 1), device))) return rc;
+	HIPCHK(hipMemcpyAsync(d_sys, sys_row_off, sizeof(i64) * (size_t)(nsys + 1), hipMemcpyHostToDevice, ps.st));
+	const i64 ds = round_up(q.wt(), 2);
+	u64 *d_aug = nullptr;
+	if ((rc = quad_alloc(scratch, (void **)&d_aug, sizeof(u64) * (size_t)(nsys * rows * ds), device))) return rc;
+	d.rows = rows;
+	if ((rc = enqueue_quad_expand_batch(d, d_sys, nsys, d_aug, ds, rows * ds, ps.st))) return rc;
+	// (the gangs run on streams of their own, behind an event gf2bv_solve_batch_device records on this one)
+	return gf2bv_solve_batch_device(d_aug, nsys, rows * ds, rows, q.cols(), ds, mode, device, ps.st, 0, out);
+	});
+}
+#undef QUAD_TERMS
 
 }  // extern "C"

@@ -36,6 +36,8 @@ EXPORTS = [
     "gf2bv_result_origin", "gf2bv_result_basis", "gf2bv_result_pivots", "gf2bv_result_stats",
     "gf2bv_result_free", "gf2bv_space_combine", "gf2bv_space_open", "gf2bv_space_enumerate", "gf2bv_space_buffer", "gf2bv_space_close",
     "gf2bv_quad_expand_device", "gf2bv_quad_expand_words", "gf2bv_solve_quad_terms",
+    "gf2bv_factor_quad_terms", "gf2bv_factor_append_quad_terms", "gf2bv_solve_rhs_quad_terms", "gf2bv_solve_batch_quad_terms",
+    "gf2bv_quad_expand_batch_words",
     "gf2bv_quad_search", "gf2bv_quad_search_alloc", "gf2bv_quad_free", "gf2bv_quad_plan", "gf2bv_quad_points", "gf2bv_quad_forms_search", "gf2bv_quad_last_times",
     "gf2bv_slab_work_words", "gf2bv_slab_tiles", "gf2bv_slab_open", "gf2bv_slab_blocks", "gf2bv_slab_owner",
     "gf2bv_slab_payload_bytes", "gf2bv_slab_factor", "gf2bv_slab_apply", "gf2bv_slab_factor_on", "gf2bv_slab_apply_on",
@@ -139,6 +141,11 @@ def lib():
         L.gf2bv_quad_expand_device.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, i64, i32, vp]
         L.gf2bv_quad_expand_words.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, i64, i32]
         L.gf2bv_solve_quad_terms.argtypes = [vp, vp, vp, vp, i64, i64, i64, i32, i32, pp]
+        L.gf2bv_factor_quad_terms.argtypes = [vp, vp, vp, vp, i64, i64, i64, i32, i32, pp]
+        L.gf2bv_factor_append_quad_terms.argtypes = [vp, vp, vp, vp, vp, i64, i64]
+        L.gf2bv_solve_rhs_quad_terms.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, i64, i64, i32, i32, pp]
+        L.gf2bv_solve_batch_quad_terms.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i32, i32, pp]
+        L.gf2bv_quad_expand_batch_words.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, vp, i64, i32]
         L.gf2bv_slab_work_words.argtypes = [i64, i64]
         L.gf2bv_slab_work_words.restype = i64
         L.gf2bv_slab_tiles.argtypes = [i64]
@@ -406,6 +413,13 @@ class Factor:
         """append_words with the equations resident in device memory (16-byte aligned, even stride; left untouched)"""
         _check(lib().gf2bv_factor_append_device(self._handle(), d_ptr, rows, stride, stream or None))
 
+    def append_quad_terms(self, lin, term_off, ta, tb, n_lin: int) -> None:
+        """Append factored quadratic equations (the arrays of quad_expand_words, every row live): expanded on the device and
+        appended there (gf2bv_factor_append_quad_terms); n_lin must be the one the factorization was made with"""
+        lin, term_off, ta, tb = _quad_terms(lin, term_off, ta, tb, n_lin)
+        _check(lib().gf2bv_factor_append_quad_terms(self._handle(), lin.ctypes.data, term_off.ctypes.data, ta.ctypes.data, tb.ctypes.data,
+                                                    len(lin), n_lin))
+
     def copy(self) -> "Factor":
         """An independent handle with the same state (a device-to-device copy, no factorization)"""
         h = ctypes.c_void_p()
@@ -615,6 +629,67 @@ def solve_quad_terms(lin, term_off, ta, tb, n_lin: int, rows: int | None = None,
     _check(lib().gf2bv_solve_quad_terms(lin.ctypes.data, term_off.ctypes.data, ta.ctypes.data, tb.ctypes.data, len(lin), rows, n_lin,
                                         mode, device, ctypes.byref(h)))
     return _take(h, mode)
+
+
+def factor_quad_terms(lin, term_off, ta, tb, n_lin: int, rows: int | None = None, mode: int = MODE_SINGLE, device: int = 0) -> Factor:
+    """The factored system uploaded, expanded on the device and factored there (gf2bv_factor_quad_terms): what factor_words returns
+    for quad_expand_words of the same arrays.  rows (default: max(len(lin), columns)) >= the columns."""
+    lin, term_off, ta, tb = _quad_terms(lin, term_off, ta, tb, n_lin)
+    rows = max(len(lin), quad_cols(n_lin)) if rows is None else rows
+    h = ctypes.c_void_p()
+    rc = lib().gf2bv_factor_quad_terms(lin.ctypes.data, term_off.ctypes.data, ta.ctypes.data, tb.ctypes.data, len(lin), rows, n_lin,
+                                       mode, device, ctypes.byref(h))
+    return _factor(rc, h, rows, quad_cols(n_lin), mode)
+
+
+def solve_rhs_quad_terms(lin, term_off, ta, tb, n_lin: int, rhs: np.ndarray, rows: int | None = None, mode: int = MODE_SINGLE,
+                         device: int = 0) -> list:
+    """Many right-hand sides of one factored system, one elimination (gf2bv_solve_rhs_quad_terms): what solve_rhs_words returns for
+    quad_expand_words of the same arrays (the constants of the factored rows are ignored: rhs holds them)."""
+    lin, term_off, ta, tb = _quad_terms(lin, term_off, ta, tb, n_lin)
+    rows = max(len(lin), quad_cols(n_lin)) if rows is None else rows
+    rhs = _rhs_array(rhs)
+    nrhs = rhs.shape[0]
+    hs = (ctypes.c_void_p * max(nrhs, 1))()
+    rc = lib().gf2bv_solve_rhs_quad_terms(lin.ctypes.data, term_off.ctypes.data, ta.ctypes.data, tb.ctypes.data, len(lin), rows, n_lin,
+                                          rhs.ctypes.data, nrhs, rhs.shape[1], mode, device, hs)
+    return _take_all(hs, nrhs, rc, mode)
+
+
+def _sys_row_off(sys_row_off, nrows: int) -> np.ndarray:
+    sys_row_off = np.ascontiguousarray(sys_row_off, dtype=np.int64).reshape(-1)
+    if len(sys_row_off) < 1 or sys_row_off[-1] != nrows:
+        raise ValueError("sys_row_off needs one entry per system and one more, ending at the rows of lin")
+    return sys_row_off
+
+
+def solve_batch_quad_terms(lin, term_off, ta, tb, sys_row_off, n_lin: int, rows: int | None = None, mode: int = MODE_SINGLE,
+                           device: int = 0) -> list:
+    """Independent factored systems over the same n_lin as one concatenated term set (system s: rows sys_row_off[s] ..
+    sys_row_off[s + 1]), expanded by one launch -- each padded to `rows` rows on the device -- and solved as lock-step gangs
+    (gf2bv_solve_batch_quad_terms).  Element s is what solve_quad_terms returns for system s with the same `rows`."""
+    lin, term_off, ta, tb = _quad_terms(lin, term_off, ta, tb, n_lin)
+    sys_row_off = _sys_row_off(sys_row_off, len(lin))
+    nsys = len(sys_row_off) - 1
+    rows = max(int(np.diff(sys_row_off).max(initial=0)), quad_cols(n_lin)) if rows is None else rows
+    hs = (ctypes.c_void_p * max(nsys, 1))()
+    rc = lib().gf2bv_solve_batch_quad_terms(lin.ctypes.data, term_off.ctypes.data, ta.ctypes.data, tb.ctypes.data, sys_row_off.ctypes.data,
+                                            nsys, rows, n_lin, mode, device, hs)
+    return _take_all(hs, nsys, rc, mode)
+
+
+def quad_expand_batch_words(lin, term_off, ta, tb, sys_row_off, n_lin: int, rows: int, stride_words: int | None = None,
+                            device: int = 0) -> np.ndarray:
+    """The batched expansion alone (gf2bv_quad_expand_batch_words): [nsys, rows, stride_words] uint64, system s the rows
+    sys_row_off[s] .. sys_row_off[s + 1] of the term set expanded and the rows behind them zero."""
+    lin, term_off, ta, tb = _quad_terms(lin, term_off, ta, tb, n_lin)
+    sys_row_off = _sys_row_off(sys_row_off, len(lin))
+    nsys = len(sys_row_off) - 1
+    stride = (quad_cols(n_lin) + 1 + 63) // 64 if stride_words is None else stride_words
+    out = np.empty((nsys, max(rows, 0), max(stride, 0)), dtype=np.uint64)
+    _check(lib().gf2bv_quad_expand_batch_words(lin.ctypes.data, term_off.ctypes.data, ta.ctypes.data, tb.ctypes.data,
+                                               sys_row_off.ctypes.data, nsys, rows, n_lin, out.ctypes.data, stride, device))
+    return out
 
 
 def synth_device(d_ptr: int, rows: int, cols: int, stride: int, seed: int, device: int = 0, stream: int = 0):

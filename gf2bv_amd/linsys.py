@@ -230,7 +230,8 @@ class LinearSystem:
 class _QuadraticPoints:
     """What a linearised quadratic system does with the solutions of its linear solve, shared by ``QuadraticSystem`` and the packed
     front-end's ``PackedQuadraticSystem``: the points whose product unknowns equal the products of their linear part.  Needs
-    ``_lin_size`` / ``_quad_size`` / ``_quad_sizes``, ``_convert_sol`` and ``solve_raw_space`` / ``solve_all`` of the class it is mixed into."""
+    ``_lin_size`` / ``_quad_size`` / ``_quad_sizes``, ``_convert_sol`` and ``solve_raw_space`` / ``solve_raw_space_rhs`` / ``solve_all`` of the
+    class it is mixed into."""
 
     def _products_match(self, lin: int, quad: int) -> bool:
         n = self._lin_size
@@ -293,6 +294,26 @@ class _QuadraticPoints:
             return None
         sols = self._search_space(space, max_enum, 1, first=True)
         return sols[0] if sols else None
+
+    def solve_one_rhs(self, exprs: Zeros, values_list: Sequence[Sequence[int]], *, max_dimension: int = 16) -> list:
+        """solve_one for every instance (the first element of its solve_all that passes convert_sol, None if there is none),
+        from ONE elimination (solve_raw_space_rhs); DimensionTooLargeError as solve_all raises it."""
+        out = []
+        for space in self.solve_raw_space_rhs(exprs, values_list):
+            sol = None
+            if space is not None:
+                if space.dimension > max_dimension:
+                    raise DimensionTooLargeError(
+                        f"Solution space (dim {space.dimension}) is too large, try increase max_dimension "
+                        f"({max_dimension}) if you want (there will be 2**dim solutions)",
+                        space=space,
+                    )
+                for raw in space:
+                    sol = self.convert_sol(raw)
+                    if sol is not None:
+                        break
+            out.append(sol)
+        return out
 
     def evaluate(self, bv: BitVec, sol: tuple) -> int:
         raw, shift = 0, 0
@@ -363,23 +384,3 @@ class QuadraticSystem(_QuadraticPoints, LinearSystem):
         if len(a) != 1:
             raise ValueError("The input should be a single bit")
         return self._bit_assert(a._bits[0], v)
-
-    def solve_one_rhs(self, exprs: Zeros, values_list: Sequence[Sequence[int]], *, max_dimension: int = 16) -> list:
-        """solve_one for every instance (the first element of its solve_all that passes convert_sol, None if there is none),
-        from ONE elimination (solve_raw_space_rhs); DimensionTooLargeError as solve_all raises it."""
-        out = []
-        for space in self.solve_raw_space_rhs(exprs, values_list):
-            sol = None
-            if space is not None:
-                if space.dimension > max_dimension:
-                    raise DimensionTooLargeError(
-                        f"Solution space (dim {space.dimension}) is too large, try increase max_dimension "
-                        f"({max_dimension}) if you want (there will be 2**dim solutions)",
-                        space=space,
-                    )
-                for raw in space:
-                    sol = self.convert_sol(raw)
-                    if sol is not None:
-                        break
-            out.append(sol)
-        return out

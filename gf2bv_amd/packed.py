@@ -21,7 +21,7 @@ from typing import Iterable, Optional, Sequence
 
 import numpy as np
 
-from ._internal import m4ri_solve_packed, m4ri_solve_quad_packed
+from ._internal import m4ri_solve_many_quad_packed, m4ri_solve_packed, m4ri_solve_quad_packed
 from .bitvec import BitVec
 from .linsys import DimensionTooLargeError, _QuadraticPoints
 
@@ -285,6 +285,47 @@ class PackedLinearSystem:
             if sol is not None:
                 yield sol
 
+    # -- many right-hand sides of one matrix, and the matrix factored once (LinearSystem's, no counterpart in the reference) ------
+    def _flat_rows(self, exprs: Sequence):
+        """(widths, rows) of `exprs` for a factored system: per expression its width (0: an equation int), and every row in
+        order as one [n, W] array.  Unlike ``_stack_rows`` no row is dropped: a right-hand side has a bit for each."""
+        parts, widths = [np.zeros((0, self._words), dtype=np.uint64)], []
+        for e in exprs:
+            if isinstance(e, PackedBitVec):
+                if e._rows.shape[1] != self._words:
+                    raise ValueError("Cannot mix bitvecs over different numbers of unknowns")
+                parts.append(e._rows)
+                widths.append(len(e))
+            elif isinstance(e, (BitVec, PackedQuadBitVec)):
+                raise TypeError("a packed linear system takes PackedBitVecs and equation ints")
+            else:                                      # a bare equation int
+                r = np.frombuffer((int(e) & ((1 << (64 * self._words)) - 1)).to_bytes(8 * self._words, "little"), dtype=np.uint64)
+                parts.append(r[None, :])
+                widths.append(0)
+        return widths, np.concatenate(parts)
+
+    def factor(self, exprs: Sequence, device=None):
+        """``LinearSystem.factor`` on packed expressions (PackedBitVec or equation int): the same FactoredSystem surface and the
+        same answers, the rows handed over as one array."""
+        from .factored import PackedFactoredSystem     # noqa: PLC0415
+        return PackedFactoredSystem(self, exprs, device)
+
+    def _solve_internal_rhs(self, exprs: Sequence, values_list: Sequence[Sequence[int]], mode: int) -> list:
+        fs = self.factor(exprs)                        # (the bookkeeping of the right-hand sides only: nothing is factored or kept)
+        rhs = fs.rhs_words(values_list)
+        if not len(rhs):
+            return []
+        return fs._solve_once(rhs, mode)
+
+    def solve_raw_one_rhs(self, exprs: Sequence, values_list: Sequence[Sequence[int]]) -> list:
+        return self._solve_internal_rhs(exprs, values_list, 0)
+
+    def solve_raw_space_rhs(self, exprs: Sequence, values_list: Sequence[Sequence[int]]) -> list:
+        return self._solve_internal_rhs(exprs, values_list, 1)
+
+    def solve_one_rhs(self, exprs: Sequence, values_list: Sequence[Sequence[int]]) -> list:
+        return [None if raw is None else self.convert_sol(raw) for raw in self._solve_internal_rhs(exprs, values_list, 0)]
+
     def evaluate(self, bv: BitVec, sol: tuple) -> int:
         raw, shift = 0, 0
         for value, width in zip(sol, self._sizes):
@@ -406,7 +447,8 @@ class PackedQuadraticSystem(_QuadraticPoints, PackedLinearSystem):
     linearised matrix -- n + n(n-1)/2 columns -- on the host.  ``gens()`` are PackedBitVecs over the n + 1 bits of the unknowns
     themselves, so everything linear (the LFSR / PRNG models of tests.harness_models) runs on them as on a PackedLinearSystem's;
     ``mul_bit`` / ``bit_assert`` give PackedQuadBitVecs; the solve methods hand the factored arrays to the device, which expands
-    and solves them.  ``convert_sol``, ``solve_one`` and the searches are QuadraticSystem's own (_QuadraticPoints)."""
+    and solves them.  ``convert_sol``, ``solve_one``, ``solve_one_rhs`` and the searches are QuadraticSystem's own (_QuadraticPoints); ``factor``,
+    ``solve_*_rhs`` and ``solve_*_many`` hand over the factored arrays as well."""
 
     def __init__(self, sizes: Iterable[int]):
         sizes = list(sizes)
@@ -503,3 +545,37 @@ class PackedQuadraticSystem(_QuadraticPoints, PackedLinearSystem):
     def _solve_internal(self, zeros: Sequence, mode: int):
         lin, off, ta, tb = self._terms(zeros)
         return m4ri_solve_quad_packed(lin, off, ta, tb, self._lin_size, max(len(lin), self._cols), mode)      # (the boundary wants rows >= cols)
+
+    # -- a kept factorization, many right-hand sides, batches: QuadraticSystem's methods on the factored arrays --------------------
+    # (solve_*_rhs are PackedLinearSystem's through ``factor``; solve_one_rhs is QuadraticSystem's own, _QuadraticPoints)
+    def _flat_rows(self, exprs: Sequence):
+        raise TypeError("a packed quadratic system has no rows on the host")
+
+    def factor(self, exprs: Sequence, device=None):
+        """``QuadraticSystem.factor`` on packed expressions (PackedBitVec, PackedQuadBitVec, the literals 0 / 1): the same
+        FactoredSystem surface -- ``add(q.bit_assert(a, v))`` on a ``copy()`` included -- with every row expanded on the device."""
+        from .factored import PackedQuadFactoredSystem     # noqa: PLC0415
+        return PackedQuadFactoredSystem(self, exprs, device)
+
+    def _solve_internal_many(self, zeros_list: Sequence[Sequence], mode: int) -> list:
+        """independent systems as ONE concatenated term set: one upload, one expansion launch, lock-step gangs"""
+        terms = [self._terms(z) for z in zeros_list]
+        if not terms:
+            return []
+        sys_off = np.zeros(len(terms) + 1, dtype=np.int64)
+        np.cumsum([len(t[0]) for t in terms], out=sys_off[1:])
+        lin = np.concatenate([t[0] for t in terms])
+        off = np.zeros(len(lin) + 1, dtype=np.int64)
+        np.cumsum(np.concatenate([np.diff(t[1]) for t in terms]), out=off[1:])
+        ta, tb = np.concatenate([t[2] for t in terms]), np.concatenate([t[3] for t in terms])
+        rows = max(self._cols, int(np.diff(sys_off).max()))               # (the boundary wants rows >= cols; zero rows come from the device)
+        return m4ri_solve_many_quad_packed(lin, off, ta, tb, sys_off, self._lin_size, rows, mode)
+
+    def solve_raw_one_many(self, zeros_list: Sequence[Sequence]) -> list:
+        return self._solve_internal_many(zeros_list, 0)
+
+    def solve_raw_space_many(self, zeros_list: Sequence[Sequence]) -> list:
+        return self._solve_internal_many(zeros_list, 1)
+
+    def solve_one_many(self, zeros_list: Sequence[Sequence]) -> list:
+        return [None if raw is None else self.convert_sol(raw) for raw in self._solve_internal_many(zeros_list, 0)]

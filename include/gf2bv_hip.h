@@ -365,6 +365,39 @@ int gf2bv_quad_expand_words(const uint64_t *lin, const int64_t *term_off, const 
 int gf2bv_solve_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t rows_live,
                            int64_t rows, int64_t n_lin, int mode, int device, gf2bv_result **out);
 
+/* The factored form in front of the entries that keep a factorization, share one elimination or batch: each uploads the term
+ * arrays (host pointers, as gf2bv_solve_quad_terms takes them), expands them into a buffer of the pool and runs the device entry
+ * named on the same pool stream; the host waits only where that entry waits, and the buffers are back in the pool on return.
+ * Results are those of that entry on gf2bv_quad_expand_words of the same arrays.  Argument errors -- the rules of
+ * gf2bv_solve_quad_terms and of the entry underneath -- return GF2BV_ERR_ARG before any device is touched; an expansion that does
+ * not fit on the device returns GF2BV_ERR_NOMEM.
+ * gf2bv_factor_quad_terms: gf2bv_factor_device on the expansion (rows >= cols; the handle keeps its own copy).
+ * gf2bv_factor_append_quad_terms: gf2bv_factor_append_device on the handle's device; all `rows` >= 1 rows are live; n_lin must be
+ *   the one the handle was made with (n_lin + n_lin(n_lin-1)/2 = its cols).  The failure contract of gf2bv_factor_append_* holds:
+ *   the uploaded terms and the expansion are taken before the kept state changes, GF2BV_ERR_ARG and GF2BV_ERR_NOMEM leave the
+ *   handle as it was.
+ * gf2bv_solve_rhs_quad_terms: gf2bv_solve_rhs_device; rhs in host memory, in the format of gf2bv_solve_rhs_words.  As in every rhs
+ *   entry the constant of the matrix input -- what the expansion leaves in column `cols` -- is ignored: rhs holds the constants.
+ * gf2bv_solve_batch_quad_terms: nsys independent systems over the same n_lin as ONE concatenated term set; system s owns the
+ *   factored rows sys_row_off[s] .. sys_row_off[s + 1] (nsys + 1 int64, from 0, never decreasing; term_off has one entry per row of
+ *   the whole set and one more, its offsets absolute).  A system's live rows may not exceed `rows`, and rows >= cols: one launch
+ *   expands every system (grid y = system) into rows x stride words each, the rows behind its live ones as zeros -- the host pads
+ *   nothing --, and gf2bv_solve_batch_device solves them as lock-step gangs.  On any non-zero return every out[s] is null.
+ * gf2bv_quad_expand_batch_words: that expansion alone, brought back to the host: out_aug holds nsys x rows x stride_words words. */
+int gf2bv_factor_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t rows_live,
+                            int64_t rows, int64_t n_lin, int mode, int device, gf2bv_factor **out);
+int gf2bv_factor_append_quad_terms(gf2bv_factor *h, const uint64_t *lin, const int64_t *term_off, const uint64_t *ta,
+                                   const uint64_t *tb, int64_t rows, int64_t n_lin);
+int gf2bv_solve_rhs_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t rows_live,
+                               int64_t rows, int64_t n_lin, const uint64_t *rhs, int64_t nrhs, int64_t rhs_words, int mode, int device,
+                               gf2bv_result **out);
+int gf2bv_solve_batch_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb,
+                                 const int64_t *sys_row_off, int64_t nsys, int64_t rows, int64_t n_lin, int mode, int device,
+                                 gf2bv_result **out);
+int gf2bv_quad_expand_batch_words(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb,
+                                  const int64_t *sys_row_off, int64_t nsys, int64_t rows, int64_t n_lin, uint64_t *out_aug,
+                                  int64_t stride_words, int device);
+
 /* ---- synthetic systems + independent residual check (bench / tests) ----------------------- */
 /* word w of row r = mix64(mix64(seed) ^ ((r<<20)|w)); planted solution = pseudo-row 0xFFFFF;
  * RHS = <row, planted>.  Writes rows x stride_words words at d_aug. */
