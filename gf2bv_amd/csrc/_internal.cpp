@@ -368,6 +368,13 @@ bool parse_devices(PyObject *obj, std::vector<int> *devs)
 }
 
 // cols / mode checks of every solve entry (_internal.c:372-395)
+bool parse_mode(PyObject *obj, long *mode)
+{
+	*mode = PyLong_AsLong(obj);
+	if (*mode == -1 && PyErr_Occurred()) return false;
+	if (*mode != GF2BV_MODE_SINGLE && *mode != GF2BV_MODE_AFFINE_SPACE) { PyErr_SetString(PyExc_ValueError, "Invalid mode"); return false; }
+	return true;
+}
 bool parse_cols_mode(PyObject *cols_obj, PyObject *mode_obj, Py_ssize_t *cols, long *mode)
 {
 	*cols = PyLong_AsSsize_t(cols_obj);
@@ -376,13 +383,7 @@ bool parse_cols_mode(PyObject *cols_obj, PyObject *mode_obj, Py_ssize_t *cols, l
 		PyErr_SetString(PyExc_ValueError, "Number of columns must be positive");
 		return false;
 	}
-	*mode = PyLong_AsLong(mode_obj);
-	if (*mode == -1 && PyErr_Occurred()) return false;
-	if (*mode != GF2BV_MODE_SINGLE && *mode != GF2BV_MODE_AFFINE_SPACE) {
-		PyErr_SetString(PyExc_ValueError, "Invalid mode");
-		return false;
-	}
-	return true;
+	return parse_mode(mode_obj, mode);
 }
 
 // ... and the rows they need (after parse_cols_mode)
@@ -391,6 +392,14 @@ bool rows_cover_cols(Py_ssize_t rows, Py_ssize_t cols)
 	if (rows >= cols) return true;
 	PyErr_SetString(PyExc_ValueError, "Number of rows must be greater than or equal to number of columns, try pad with zeros.");
 	return false;
+}
+
+// The prologue of the solve entries: `k` arguments, and after them the optional device
+bool entry_device(const char *name, Py_ssize_t k, PyObject *const *args, Py_ssize_t nargs, int *device)
+{
+	if (nargs != k && nargs != k + 1) { PyErr_Format(PyExc_TypeError, "%s requires %zd arguments", name, k); return false; }
+	*device = default_device();
+	return nargs == k || parse_device(args[k], device);
 }
 
 // A failed library call as a Python exception: ValueError for bad arguments, RuntimeError otherwise.  `msg`: the library's
@@ -510,9 +519,8 @@ bool parse_equations(PyObject *list, PyObject *cols_obj, PyObject *mode_obj, Py_
 // m4ri_solve(equations, cols, mode) -- gf2bv/_internal.c:359-502
 PyObject *py_m4ri_solve(PyObject *, PyObject *const *args, Py_ssize_t nargs)
 {
-	if (nargs != 3 && nargs != 4) { PyErr_SetString(PyExc_TypeError, "m4ri_solve requires 3 arguments"); return nullptr; }
-	int device = default_device();
-	if (nargs == 4 && !parse_device(args[3], &device)) return nullptr;
+	int device;
+	if (!entry_device("m4ri_solve", 3, args, nargs, &device)) return nullptr;
 	PyObject *list = args[0];
 	Py_ssize_t rows, cols;
 	long mode;
@@ -580,6 +588,168 @@ PyObject *results_to_list(std::vector<gf2bv_result *> &res, long mode, int devic
 	return out;
 }
 
+// The epilogue of the list-returning entries: `fill(out)`, run with the GIL released, makes the n result handles of a library call;
+// a failure frees whichever exist and raises
+template <class F>
+PyObject *collect_results(int64_t n, long mode, int device, F &&fill)
+{
+	std::vector<gf2bv_result *> res((size_t)n, nullptr);
+	int rc;
+	Py_BEGIN_ALLOW_THREADS
+	rc = fill(res.data());
+	Py_END_ALLOW_THREADS
+	if (rc != GF2BV_OK) {
+		for (gf2bv_result *r : res) if (r) gf2bv_result_free(r);
+		return raise_rc(rc, "solve");
+	}
+	return results_to_list(res, mode, device);
+}
+
+// ---- what the packed front-ends pass in, one parser per kind of input ---------------------------------------------------------
+// The factored form of a quadratic system as four C-contiguous buffers (m4ri_solve_quad_packed's arguments), checked against each
+// other and against n_lin before the library sees them: whole rows of Wl = ceil((n_lin + 1) / 64) words, one offset per row and one
+// more, offsets that start at 0, never decrease and end at the number of operands.  TypeError for what is no buffer, ValueError for
+// a shape.
+struct QuadBuffers {
+	Py_buffer view[4];
+	int got = 0;
+	Py_ssize_t n = 0, live = 0, nterms = 0;
+	const uint64_t *lin = nullptr, *ta = nullptr, *tb = nullptr;
+	const int64_t *off = nullptr;
+	QuadBuffers() = default;
+	QuadBuffers(const QuadBuffers &) = delete;
+	QuadBuffers &operator=(const QuadBuffers &) = delete;
+	~QuadBuffers() { for (int k = 0; k < got; k++) PyBuffer_Release(&view[k]); }
+	bool parse(PyObject *const *args, PyObject *n_obj)
+	{
+		n = PyLong_AsSsize_t(n_obj);
+		if (n == -1 && PyErr_Occurred()) return false;
+		if (n < 1 || n > 65535) { PyErr_SetString(PyExc_ValueError, "n_lin must be 1..65535"); return false; }
+		const Py_ssize_t wl = (n + 1 + 63) / 64;
+		for (; got < 4; got++)
+			if (PyObject_GetBuffer(args[got], &view[got], PyBUF_C_CONTIGUOUS) != 0) return false;
+		live = view[0].len / (wl * 8);
+		nterms = view[2].len / (wl * 8);
+		off = static_cast<const int64_t *>(view[1].buf);
+		const char *bad = nullptr;
+		if (view[0].len != live * wl * 8) bad = "lin must hold whole rows of ceil((n_lin + 1) / 64) 64-bit words";
+		else if (view[1].len != (live + 1) * 8) bad = "term_off must hold one int64 per row of lin and one more";
+		else if (view[2].len != nterms * wl * 8 || view[3].len != view[2].len) bad = "ta and tb must hold the same number of whole operands";
+		else if (off[0] != 0) bad = "term_off must start at 0";
+		else if (off[live] != nterms) bad = "term_off must end at the number of operands in ta";
+		else
+			for (Py_ssize_t r = 0; r < live; r++)
+				if (off[r + 1] < off[r]) { bad = "term_off must not decrease"; break; }
+		if (bad) { PyErr_SetString(PyExc_ValueError, bad); return false; }
+		lin = static_cast<const uint64_t *>(view[0].buf);
+		ta = static_cast<const uint64_t *>(view[2].buf);
+		tb = static_cast<const uint64_t *>(view[3].buf);
+		return true;
+	}
+	Py_ssize_t cols() const { return n + n * (n - 1) / 2; }
+};
+
+// (a buffer taken with PyBUF_C_CONTIGUOUS | PyBUF_FORMAT) a 2-D uint64 array?
+bool is_u64_matrix(const Py_buffer &view)
+{
+	const char *f = view.format ? view.format : "B";
+	if (*f == '<' || *f == '=' || *f == '@') f++;
+	return view.ndim == 2 && view.itemsize == 8 && (strcmp(f, "Q") == 0 || strcmp(f, "L") == 0);
+}
+
+// a buffer of the caller's, held until the entry returns
+struct HeldBuffer {
+	Py_buffer view{};
+	bool have = false;
+	HeldBuffer() = default;
+	HeldBuffer(const HeldBuffer &) = delete;
+	HeldBuffer &operator=(const HeldBuffer &) = delete;
+	~HeldBuffer() { if (have) PyBuffer_Release(&view); }
+	bool take(PyObject *buf, int flags)
+	{
+		if (PyObject_GetBuffer(buf, &view, flags) != 0) return false;
+		return have = true;
+	}
+};
+
+// rows x words packed equations (m4ri_solve_packed's buffer) as 32-bit digits: two per word
+struct PackedRows : HeldBuffer {
+	std::vector<int64_t> off;
+	bool offsets(Py_ssize_t rows, Py_ssize_t words)
+	{
+		try { off.resize((size_t)rows + 1); } catch (const std::bad_alloc &) { PyErr_NoMemory(); return false; }
+		for (Py_ssize_t r = 0; r <= rows; r++) off[(size_t)r] = (int64_t)r * words * 2;
+		return true;
+	}
+	bool parse(PyObject *buf, Py_ssize_t rows, Py_ssize_t words, Py_ssize_t cols)
+	{
+		if (!take(buf, PyBUF_C_CONTIGUOUS)) return false;
+		if (rows < 0 || words <= 0 || view.len != rows * words * 8 || words * 64 < cols + 1) {
+			PyErr_SetString(PyExc_ValueError, "buffer must hold rows x words 64-bit words covering cols + 1 bits");
+			return false;
+		}
+		return offsets(rows, words);
+	}
+	const uint32_t *digits() const { return static_cast<const uint32_t *>(view.buf); }
+};
+
+// right-hand sides, for Factorization.solve and every m4ri_solve_rhs_*packed: a list of non-negative ints or a C-contiguous 2-D
+// uint64 array of nrhs x >= ceil(rows / 64) words
+struct RhsInput : HeldBuffer {
+	std::vector<uint64_t> words;
+	const uint64_t *src = nullptr;
+	int64_t nrhs = 0, stride = 0;
+	bool parse(PyObject *rhs, int64_t rows)
+	{
+		const int64_t rw = (rows + 63) / 64;
+		stride = rw;
+		if (PyList_Check(rhs)) {
+			nrhs = PyList_GET_SIZE(rhs);
+			if (nrhs && !rhs_list_words(rhs, rows, words)) return false;
+			src = words.data();
+			return true;
+		}
+		if (!PyObject_CheckBuffer(rhs)) {
+			PyErr_SetString(PyExc_TypeError, "The right-hand sides must be a list of integers or a 2-D uint64 array");
+			return false;
+		}
+		if (!take(rhs, PyBUF_C_CONTIGUOUS | PyBUF_FORMAT)) return false;
+		if (!is_u64_matrix(view)) {
+			PyErr_SetString(PyExc_TypeError, "right-hand sides as a buffer: a C-contiguous 2-D uint64 array");
+			return false;
+		}
+		nrhs = view.shape[0];
+		stride = view.shape[1];
+		if (stride < rw) {
+			PyErr_SetString(PyExc_ValueError, "the right-hand-side array needs ceil(rows / 64) words per row");
+			return false;
+		}
+		src = static_cast<const uint64_t *>(view.buf);
+		return true;
+	}
+};
+
+// The prologue of the entries on m4ri_solve_packed's buffer: arguments 0 .. 4 are the buffer, rows, words, cols and mode
+bool parse_packed_call(PyObject *const *args, PackedRows &pr, Py_ssize_t *rows, Py_ssize_t *cols, long *mode)
+{
+	*rows = PyLong_AsSsize_t(args[1]);
+	const Py_ssize_t words = PyLong_AsSsize_t(args[2]);
+	if ((*rows == -1 || words == -1) && PyErr_Occurred()) return false;
+	return parse_cols_mode(args[3], args[4], cols, mode) && rows_cover_cols(*rows, *cols) && pr.parse(args[0], *rows, words, *cols);
+}
+
+// The prologue of the entries that take the factored form and a row count: arguments 0 .. 3 are the four buffers, then n_lin, rows,
+// mode at the given positions; rows must cover the rows of lin (`live_rows`: the batch entry's systems are checked by its own
+// offsets instead) and the columns
+bool parse_quad_call(PyObject *const *args, int n_at, int rows_at, int mode_at, bool live_rows, QuadBuffers &qb, Py_ssize_t *rows, long *mode)
+{
+	*rows = PyLong_AsSsize_t(args[rows_at]);
+	if (*rows == -1 && PyErr_Occurred()) return false;
+	if (!parse_mode(args[mode_at], mode) || !qb.parse(args, args[n_at])) return false;
+	if (live_rows && *rows < qb.live) { PyErr_SetString(PyExc_ValueError, "rows must be at least the rows of lin"); return false; }
+	return rows_cover_cols(*rows, qb.cols());
+}
+
 // m4ri_solve_rhs(equations, cols, mode, rhs, device=None) -> list of (None | int | AffineSpace), one per element of `rhs`.
 // New entry (no counterpart in the reference): many systems that share their coefficient matrix -- the reference factors A alone
 // (gf2bv/_internal.c:398-433) and only then solves against B (:438-455) -- eliminated ONCE (gf2bv_solve_rhs_digits).  `equations`
@@ -587,9 +757,8 @@ PyObject *results_to_list(std::vector<gf2bv_result *> &res, long mode, int devic
 // system j (bits >= rows ignored).  Element j is what m4ri_solve returns for `equations` with their affine terms taken from rhs[j].
 PyObject *py_m4ri_solve_rhs(PyObject *, PyObject *const *args, Py_ssize_t nargs)
 {
-	if (nargs != 4 && nargs != 5) { PyErr_SetString(PyExc_TypeError, "m4ri_solve_rhs requires 4 arguments"); return nullptr; }
-	int device = default_device();
-	if (nargs == 5 && !parse_device(args[4], &device)) return nullptr;
+	int device;
+	if (!entry_device("m4ri_solve_rhs", 4, args, nargs, &device)) return nullptr;
 	PyObject *list = args[0], *rhs = args[3];
 	if (!PyList_Check(rhs)) {
 		PyErr_SetString(PyExc_TypeError, "The right-hand sides must be a list of integers");
@@ -605,16 +774,9 @@ PyObject *py_m4ri_solve_rhs(PyObject *, PyObject *const *args, Py_ssize_t nargs)
 	if (!rhs_list_words(rhs, rows, words)) return nullptr;
 	DigitGather dg;
 	if (!dg.gather_list(list, cols)) return nullptr;
-	std::vector<gf2bv_result *> res((size_t)nrhs, nullptr);
-	int rc;
-	Py_BEGIN_ALLOW_THREADS
-	rc = gf2bv_solve_rhs_digits(dg.digits, dg.off.data(), PyLong_SHIFT, rows, cols, words.data(), nrhs, rw, (int)mode, device, res.data());
-	Py_END_ALLOW_THREADS
-	if (rc != GF2BV_OK) {
-		for (gf2bv_result *r : res) if (r) gf2bv_result_free(r);
-		return raise_rc(rc, "solve");
-	}
-	return results_to_list(res, mode, device);
+	return collect_results(nrhs, mode, device, [&](gf2bv_result **out) {
+		return gf2bv_solve_rhs_digits(dg.digits, dg.off.data(), PyLong_SHIFT, rows, cols, words.data(), nrhs, rw, (int)mode, device, out);
+	});
 }
 
 // ---- Factorization: a kept factorization of one matrix (gf2bv_factor_*; no counterpart in the reference) --------------------
@@ -677,8 +839,23 @@ PyObject *factor_pivots(FactorObject *self, void *)
 	return t;
 }
 
-// (the body follows RhsInput, which every entry that takes right-hand sides shares)
-PyObject *factor_solve(FactorObject *self, PyObject *rhs);
+PyObject *new_factorization(gf2bv_factor *h, int64_t rows, int64_t cols, long mode, int device)
+{
+	FactorObject *f = PyObject_New(FactorObject, Factorization_Type);
+	if (!f) { gf2bv_factor_free(h); return nullptr; }
+	f->h = h; f->rows = rows; f->cols = cols; f->mode = mode; f->device = device;
+	return (PyObject *)f;
+}
+
+PyObject *factor_solve(FactorObject *self, PyObject *rhs)
+{
+	if (!factor_open(self)) return nullptr;
+	RhsInput ri;
+	if (!ri.parse(rhs, self->rows)) return nullptr;
+	if (ri.nrhs == 0) return PyList_New(0);
+	gf2bv_factor *h = self->h;
+	return collect_results(ri.nrhs, self->mode, self->device, [&](gf2bv_result **out) { return gf2bv_factor_solve(h, ri.src, ri.nrhs, ri.stride, out); });
+}
 
 // append(equations): equations added below the factored ones -- a list of equation ints (bit 0 ignored) or a C-contiguous 2-D
 // uint64 array of n x words words in the same bit order (m4ri_solve_packed's layout); the handle then stands for the stacked matrix
@@ -686,10 +863,9 @@ PyObject *factor_append(FactorObject *self, PyObject *eqs)
 {
 	if (!factor_open(self)) return nullptr;
 	int rc;
-	int64_t n = 0;
 	gf2bv_factor *h = self->h;
 	if (PyList_Check(eqs)) {
-		n = PyList_GET_SIZE(eqs);
+		const int64_t n = PyList_GET_SIZE(eqs);
 		if (n == 0) Py_RETURN_NONE;
 		DigitGather dg;
 		if (!dg.gather_list(eqs, self->cols)) return nullptr;
@@ -697,30 +873,22 @@ PyObject *factor_append(FactorObject *self, PyObject *eqs)
 		rc = gf2bv_factor_append_digits(h, dg.digits, dg.off.data(), PyLong_SHIFT, n);
 		Py_END_ALLOW_THREADS
 	} else if (PyObject_CheckBuffer(eqs)) {
-		Py_buffer view{};
-		if (PyObject_GetBuffer(eqs, &view, PyBUF_C_CONTIGUOUS | PyBUF_FORMAT) < 0) return nullptr;
-		const char *f = view.format ? view.format : "B";
-		if (*f == '<' || *f == '=' || *f == '@') f++;
-		if (view.ndim != 2 || view.itemsize != 8 || !(strcmp(f, "Q") == 0 || strcmp(f, "L") == 0)) {
-			PyBuffer_Release(&view);
+		PackedRows pr;
+		if (!pr.take(eqs, PyBUF_C_CONTIGUOUS | PyBUF_FORMAT)) return nullptr;
+		if (!is_u64_matrix(pr.view)) {
 			PyErr_SetString(PyExc_TypeError, "equations as a buffer: a C-contiguous 2-D uint64 array");
 			return nullptr;
 		}
-		n = view.shape[0];
-		const int64_t words = view.shape[1];
+		const int64_t n = pr.view.shape[0], words = pr.view.shape[1];
 		if (words * 64 < self->cols + 1) {
-			PyBuffer_Release(&view);
 			PyErr_SetString(PyExc_ValueError, "the equation array needs words covering cols + 1 bits");
 			return nullptr;
 		}
-		if (n == 0) { PyBuffer_Release(&view); Py_RETURN_NONE; }
-		std::vector<int64_t> off;
-		try { off.resize((size_t)n + 1); } catch (const std::bad_alloc &) { PyBuffer_Release(&view); return PyErr_NoMemory(); }
-		for (int64_t r = 0; r <= n; r++) off[(size_t)r] = r * words * 2;
+		if (n == 0) Py_RETURN_NONE;
+		if (!pr.offsets(n, words)) return nullptr;
 		Py_BEGIN_ALLOW_THREADS
-		rc = gf2bv_factor_append_digits(h, static_cast<const uint32_t *>(view.buf), off.data(), 32, n);
+		rc = gf2bv_factor_append_digits(h, pr.digits(), pr.off.data(), 32, n);
 		Py_END_ALLOW_THREADS
-		PyBuffer_Release(&view);
 	} else {
 		PyErr_SetString(PyExc_TypeError, "The equations must be a list of integers or a 2-D uint64 array");
 		return nullptr;
@@ -730,16 +898,23 @@ PyObject *factor_append(FactorObject *self, PyObject *eqs)
 	Py_RETURN_NONE;
 }
 
-struct QuadBuffers;
-bool factor_append_quad_impl(FactorObject *self, PyObject *const *args);
-
 // append_quad(lin, term_off, ta, tb, n_lin): factored quadratic equations (m4ri_factor_quad_packed's arrays) added below the factored
 // ones, expanded on the device (gf2bv_factor_append_quad_terms); n_lin must be the one the factorization was made with
 PyObject *factor_append_quad(FactorObject *self, PyObject *const *args, Py_ssize_t nargs)
 {
 	if (nargs != 5) { PyErr_SetString(PyExc_TypeError, "append_quad requires 5 arguments"); return nullptr; }
 	if (!factor_open(self)) return nullptr;
-	if (!factor_append_quad_impl(self, args)) return nullptr;
+	QuadBuffers qb;
+	if (!qb.parse(args, args[4])) return nullptr;
+	if (qb.cols() != self->cols) { PyErr_SetString(PyExc_ValueError, "n_lin does not match the factorization's columns"); return nullptr; }
+	if (qb.live == 0) Py_RETURN_NONE;
+	gf2bv_factor *h = self->h;
+	int rc;
+	Py_BEGIN_ALLOW_THREADS
+	rc = gf2bv_factor_append_quad_terms(h, qb.lin, qb.off, qb.ta, qb.tb, qb.live, qb.n);
+	Py_END_ALLOW_THREADS
+	if (rc != GF2BV_OK) return raise_rc(rc, "append");
+	self->rows = gf2bv_factor_rows(h);
 	Py_RETURN_NONE;
 }
 
@@ -753,10 +928,7 @@ PyObject *factor_copy(FactorObject *self, PyObject *)
 	rc = gf2bv_factor_copy(h, &c);
 	Py_END_ALLOW_THREADS
 	if (rc != GF2BV_OK) return raise_rc(rc, "copy");
-	FactorObject *f = PyObject_New(FactorObject, Factorization_Type);
-	if (!f) { gf2bv_factor_free(c); return nullptr; }
-	f->h = c; f->rows = self->rows; f->cols = self->cols; f->mode = self->mode; f->device = self->device;
-	return (PyObject *)f;
+	return new_factorization(c, self->rows, self->cols, self->mode, self->device);
 }
 
 PyObject *factor_close(FactorObject *self, PyObject *)
@@ -810,9 +982,8 @@ PyType_Spec factor_spec = {"_internal.Factorization", sizeof(FactorObject), 0,
 
 PyObject *py_m4ri_factor(PyObject *, PyObject *const *args, Py_ssize_t nargs)
 {
-	if (nargs != 3 && nargs != 4) { PyErr_SetString(PyExc_TypeError, "m4ri_factor requires 3 arguments"); return nullptr; }
-	int device = default_device();
-	if (nargs == 4 && !parse_device(args[3], &device)) return nullptr;
+	int device;
+	if (!entry_device("m4ri_factor", 3, args, nargs, &device)) return nullptr;
 	PyObject *list = args[0];
 	Py_ssize_t rows, cols;
 	long mode;
@@ -825,10 +996,7 @@ PyObject *py_m4ri_factor(PyObject *, PyObject *const *args, Py_ssize_t nargs)
 	rc = gf2bv_factor_digits(dg.digits, dg.off.data(), PyLong_SHIFT, rows, cols, (int)mode, device, &h);
 	Py_END_ALLOW_THREADS
 	if (rc != GF2BV_OK) return raise_rc(rc, "factorization");
-	FactorObject *f = PyObject_New(FactorObject, Factorization_Type);
-	if (!f) { gf2bv_factor_free(h); return nullptr; }
-	f->h = h; f->rows = rows; f->cols = cols; f->mode = mode; f->device = device;
-	return (PyObject *)f;
+	return new_factorization(h, rows, cols, mode, device);
 }
 
 // m4ri_solve_packed(buffer, rows, words, cols, mode) -> None | int | AffineSpace.
@@ -839,30 +1007,17 @@ PyObject *py_m4ri_factor(PyObject *, PyObject *const *args, Py_ssize_t nargs)
 // gf2bv/_internal.c:403-426 does bit by bit.  Same checks, same result types as m4ri_solve.
 PyObject *py_m4ri_solve_packed(PyObject *, PyObject *const *args, Py_ssize_t nargs)
 {
-	if (nargs != 5 && nargs != 6) { PyErr_SetString(PyExc_TypeError, "m4ri_solve_packed requires 5 arguments"); return nullptr; }
-	int device = default_device();
-	if (nargs == 6 && !parse_device(args[5], &device)) return nullptr;
-	const Py_ssize_t rows = PyLong_AsSsize_t(args[1]), words = PyLong_AsSsize_t(args[2]);
-	if ((rows == -1 || words == -1) && PyErr_Occurred()) return nullptr;
-	Py_ssize_t cols;
+	int device;
+	if (!entry_device("m4ri_solve_packed", 5, args, nargs, &device)) return nullptr;
+	Py_ssize_t rows, cols;
 	long mode;
-	if (!parse_cols_mode(args[3], args[4], &cols, &mode) || !rows_cover_cols(rows, cols)) return nullptr;
-	Py_buffer view;
-	if (PyObject_GetBuffer(args[0], &view, PyBUF_C_CONTIGUOUS) != 0) return nullptr;
-	if (words <= 0 || view.len != rows * words * 8 || words * 64 < cols + 1) {
-		PyBuffer_Release(&view);
-		PyErr_SetString(PyExc_ValueError, "buffer must hold rows x words 64-bit words covering cols + 1 bits");
-		return nullptr;
-	}
-	std::vector<int64_t> off;
-	try { off.resize((size_t)rows + 1); } catch (const std::bad_alloc &) { PyBuffer_Release(&view); return PyErr_NoMemory(); }
-	for (Py_ssize_t r = 0; r <= rows; r++) off[(size_t)r] = (int64_t)r * words * 2;
+	PackedRows pr;
+	if (!parse_packed_call(args, pr, &rows, &cols, &mode)) return nullptr;
 	gf2bv_result *res = nullptr;
 	int rc;
 	Py_BEGIN_ALLOW_THREADS
-	rc = gf2bv_solve_digits(static_cast<const uint32_t *>(view.buf), off.data(), 32, rows, cols, (int)mode, device, &res);
+	rc = gf2bv_solve_digits(pr.digits(), pr.off.data(), 32, rows, cols, (int)mode, device, &res);
 	Py_END_ALLOW_THREADS
-	PyBuffer_Release(&view);
 	if (rc != GF2BV_OK) return raise_rc(rc, "solve");
 	return result_to_py(res, mode, device);
 }
@@ -876,223 +1031,32 @@ PyObject *py_m4ri_solve_packed(PyObject *, PyObject *const *args, Py_ssize_t nar
 // types as m4ri_solve over n_lin + n_lin(n_lin-1)/2 columns.
 PyObject *py_m4ri_solve_quad_packed(PyObject *, PyObject *const *args, Py_ssize_t nargs)
 {
-	if (nargs != 7 && nargs != 8) { PyErr_SetString(PyExc_TypeError, "m4ri_solve_quad_packed requires 7 arguments"); return nullptr; }
-	int device = default_device();
-	if (nargs == 8 && !parse_device(args[7], &device)) return nullptr;
-	const Py_ssize_t n = PyLong_AsSsize_t(args[4]), rows = PyLong_AsSsize_t(args[5]);
-	if ((n == -1 || rows == -1) && PyErr_Occurred()) return nullptr;
-	if (n < 1 || n > 65535) { PyErr_SetString(PyExc_ValueError, "n_lin must be 1..65535"); return nullptr; }
-	const Py_ssize_t wl = (n + 1 + 63) / 64;
-	const long mode = PyLong_AsLong(args[6]);
-	if (mode == -1 && PyErr_Occurred()) return nullptr;
-	Py_buffer view[4];
-	int got = 0;
-	for (; got < 4; got++)
-		if (PyObject_GetBuffer(args[got], &view[got], PyBUF_C_CONTIGUOUS) != 0) break;
-	const char *bad = nullptr;
-	if (got == 4) {
-		const Py_ssize_t live = view[0].len / (wl * 8), nterms = view[2].len / (wl * 8);
-		const int64_t *off = static_cast<const int64_t *>(view[1].buf);
-		if (view[0].len != live * wl * 8) bad = "lin must hold whole rows of ceil((n_lin + 1) / 64) 64-bit words";
-		else if (view[1].len != (live + 1) * 8) bad = "term_off must hold one int64 per row of lin and one more";
-		else if (view[2].len != nterms * wl * 8 || view[3].len != view[2].len) bad = "ta and tb must hold the same number of whole operands";
-		else if (off[live] != nterms) bad = "term_off must end at the number of operands in ta";
-		else if (rows < live) bad = "rows must be at least the rows of lin";
-		if (bad) PyErr_SetString(PyExc_ValueError, bad);
-		else {
-			gf2bv_result *res = nullptr;
-			int rc;
-			Py_BEGIN_ALLOW_THREADS
-			rc = gf2bv_solve_quad_terms(static_cast<const uint64_t *>(view[0].buf), off, static_cast<const uint64_t *>(view[2].buf),
-			                            static_cast<const uint64_t *>(view[3].buf), live, rows, n, (int)mode, device, &res);
-			Py_END_ALLOW_THREADS
-			for (int k = 0; k < 4; k++) PyBuffer_Release(&view[k]);
-			if (rc != GF2BV_OK) return raise_rc(rc, "solve");
-			return result_to_py(res, mode, device);
-		}
-	}
-	for (int k = 0; k < got; k++) PyBuffer_Release(&view[k]);
-	return nullptr;
+	int device;
+	if (!entry_device("m4ri_solve_quad_packed", 7, args, nargs, &device)) return nullptr;
+	Py_ssize_t rows;
+	long mode;
+	QuadBuffers qb;
+	if (!parse_quad_call(args, 4, 5, 6, true, qb, &rows, &mode)) return nullptr;
+	gf2bv_result *res = nullptr;
+	int rc;
+	Py_BEGIN_ALLOW_THREADS
+	rc = gf2bv_solve_quad_terms(qb.lin, qb.off, qb.ta, qb.tb, qb.live, rows, qb.n, (int)mode, device, &res);
+	Py_END_ALLOW_THREADS
+	if (rc != GF2BV_OK) return raise_rc(rc, "solve");
+	return result_to_py(res, mode, device);
 }
 
 // ---- the packed front-ends in front of the kept factorization, the shared elimination and the batch --------------------------
-// The factored form of a quadratic system as four C-contiguous buffers (m4ri_solve_quad_packed's arguments), checked against each
-// other and against n_lin before the library sees them: whole rows of Wl = ceil((n_lin + 1) / 64) words, one offset per row and one
-// more, offsets that start at 0, never decrease and end at the number of operands.  TypeError for what is no buffer, ValueError for
-// a shape.
-struct QuadBuffers {
-	Py_buffer view[4];
-	int got = 0;
-	Py_ssize_t n = 0, live = 0, nterms = 0;
-	const uint64_t *lin = nullptr, *ta = nullptr, *tb = nullptr;
-	const int64_t *off = nullptr;
-	QuadBuffers() = default;
-	QuadBuffers(const QuadBuffers &) = delete;
-	QuadBuffers &operator=(const QuadBuffers &) = delete;
-	~QuadBuffers() { for (int k = 0; k < got; k++) PyBuffer_Release(&view[k]); }
-	bool parse(PyObject *const *args, PyObject *n_obj)
-	{
-		n = PyLong_AsSsize_t(n_obj);
-		if (n == -1 && PyErr_Occurred()) return false;
-		if (n < 1 || n > 65535) { PyErr_SetString(PyExc_ValueError, "n_lin must be 1..65535"); return false; }
-		const Py_ssize_t wl = (n + 1 + 63) / 64;
-		for (; got < 4; got++)
-			if (PyObject_GetBuffer(args[got], &view[got], PyBUF_C_CONTIGUOUS) != 0) return false;
-		live = view[0].len / (wl * 8);
-		nterms = view[2].len / (wl * 8);
-		off = static_cast<const int64_t *>(view[1].buf);
-		const char *bad = nullptr;
-		if (view[0].len != live * wl * 8) bad = "lin must hold whole rows of ceil((n_lin + 1) / 64) 64-bit words";
-		else if (view[1].len != (live + 1) * 8) bad = "term_off must hold one int64 per row of lin and one more";
-		else if (view[2].len != nterms * wl * 8 || view[3].len != view[2].len) bad = "ta and tb must hold the same number of whole operands";
-		else if (off[0] != 0) bad = "term_off must start at 0";
-		else if (off[live] != nterms) bad = "term_off must end at the number of operands in ta";
-		else
-			for (Py_ssize_t r = 0; r < live; r++)
-				if (off[r + 1] < off[r]) { bad = "term_off must not decrease"; break; }
-		if (bad) { PyErr_SetString(PyExc_ValueError, bad); return false; }
-		lin = static_cast<const uint64_t *>(view[0].buf);
-		ta = static_cast<const uint64_t *>(view[2].buf);
-		tb = static_cast<const uint64_t *>(view[3].buf);
-		return true;
-	}
-	Py_ssize_t cols() const { return n + n * (n - 1) / 2; }
-};
-
-// rows x words packed equations (m4ri_solve_packed's buffer) as 32-bit digits: two per word
-struct PackedRows {
-	Py_buffer view{};
-	bool have = false;
-	std::vector<int64_t> off;
-	PackedRows() = default;
-	PackedRows(const PackedRows &) = delete;
-	PackedRows &operator=(const PackedRows &) = delete;
-	~PackedRows() { if (have) PyBuffer_Release(&view); }
-	bool parse(PyObject *buf, Py_ssize_t rows, Py_ssize_t words, Py_ssize_t cols)
-	{
-		if (PyObject_GetBuffer(buf, &view, PyBUF_C_CONTIGUOUS) != 0) return false;
-		have = true;
-		if (rows < 0 || words <= 0 || view.len != rows * words * 8 || words * 64 < cols + 1) {
-			PyErr_SetString(PyExc_ValueError, "buffer must hold rows x words 64-bit words covering cols + 1 bits");
-			return false;
-		}
-		try { off.resize((size_t)rows + 1); } catch (const std::bad_alloc &) { PyErr_NoMemory(); return false; }
-		for (Py_ssize_t r = 0; r <= rows; r++) off[(size_t)r] = (int64_t)r * words * 2;
-		return true;
-	}
-	const uint32_t *digits() const { return static_cast<const uint32_t *>(view.buf); }
-};
-
-// right-hand sides, for Factorization.solve and every m4ri_solve_rhs_*packed: a list of non-negative ints or a C-contiguous 2-D
-// uint64 array of nrhs x >= ceil(rows / 64) words
-struct RhsInput {
-	std::vector<uint64_t> words;
-	Py_buffer view{};
-	bool have = false;
-	const uint64_t *src = nullptr;
-	int64_t nrhs = 0, stride = 0;
-	RhsInput() = default;
-	RhsInput(const RhsInput &) = delete;
-	RhsInput &operator=(const RhsInput &) = delete;
-	~RhsInput() { if (have) PyBuffer_Release(&view); }
-	bool parse(PyObject *rhs, int64_t rows)
-	{
-		const int64_t rw = (rows + 63) / 64;
-		stride = rw;
-		if (PyList_Check(rhs)) {
-			nrhs = PyList_GET_SIZE(rhs);
-			if (nrhs && !rhs_list_words(rhs, rows, words)) return false;
-			src = words.data();
-			return true;
-		}
-		if (!PyObject_CheckBuffer(rhs)) {
-			PyErr_SetString(PyExc_TypeError, "The right-hand sides must be a list of integers or a 2-D uint64 array");
-			return false;
-		}
-		if (PyObject_GetBuffer(rhs, &view, PyBUF_C_CONTIGUOUS | PyBUF_FORMAT) < 0) return false;
-		have = true;
-		const char *f = view.format ? view.format : "B";
-		if (*f == '<' || *f == '=' || *f == '@') f++;
-		if (view.ndim != 2 || view.itemsize != 8 || !(strcmp(f, "Q") == 0 || strcmp(f, "L") == 0)) {
-			PyErr_SetString(PyExc_TypeError, "right-hand sides as a buffer: a C-contiguous 2-D uint64 array");
-			return false;
-		}
-		nrhs = view.shape[0];
-		stride = view.shape[1];
-		if (stride < rw) {
-			PyErr_SetString(PyExc_ValueError, "the right-hand-side array needs ceil(rows / 64) words per row");
-			return false;
-		}
-		src = static_cast<const uint64_t *>(view.buf);
-		return true;
-	}
-};
-
-PyObject *factor_solve(FactorObject *self, PyObject *rhs)
-{
-	if (!factor_open(self)) return nullptr;
-	RhsInput ri;
-	if (!ri.parse(rhs, self->rows)) return nullptr;
-	if (ri.nrhs == 0) return PyList_New(0);
-	std::vector<gf2bv_result *> res((size_t)ri.nrhs, nullptr);
-	int rc;
-	gf2bv_factor *h = self->h;
-	Py_BEGIN_ALLOW_THREADS
-	rc = gf2bv_factor_solve(h, ri.src, ri.nrhs, ri.stride, res.data());
-	Py_END_ALLOW_THREADS
-	if (rc != GF2BV_OK) {
-		for (gf2bv_result *r : res) if (r) gf2bv_result_free(r);
-		return raise_rc(rc, "solve");
-	}
-	return results_to_list(res, self->mode, self->device);
-}
-
-PyObject *new_factorization(gf2bv_factor *h, int64_t rows, int64_t cols, long mode, int device)
-{
-	FactorObject *f = PyObject_New(FactorObject, Factorization_Type);
-	if (!f) { gf2bv_factor_free(h); return nullptr; }
-	f->h = h; f->rows = rows; f->cols = cols; f->mode = mode; f->device = device;
-	return (PyObject *)f;
-}
-
-bool parse_mode(PyObject *obj, long *mode)
-{
-	*mode = PyLong_AsLong(obj);
-	if (*mode == -1 && PyErr_Occurred()) return false;
-	if (*mode != GF2BV_MODE_SINGLE && *mode != GF2BV_MODE_AFFINE_SPACE) { PyErr_SetString(PyExc_ValueError, "Invalid mode"); return false; }
-	return true;
-}
-
-bool factor_append_quad_impl(FactorObject *self, PyObject *const *args)
-{
-	QuadBuffers qb;
-	if (!qb.parse(args, args[4])) return false;
-	if (qb.cols() != self->cols) { PyErr_SetString(PyExc_ValueError, "n_lin does not match the factorization's columns"); return false; }
-	if (qb.live == 0) return true;
-	gf2bv_factor *h = self->h;
-	int rc;
-	Py_BEGIN_ALLOW_THREADS
-	rc = gf2bv_factor_append_quad_terms(h, qb.lin, qb.off, qb.ta, qb.tb, qb.live, qb.n);
-	Py_END_ALLOW_THREADS
-	if (rc != GF2BV_OK) { raise_rc(rc, "append"); return false; }
-	self->rows = gf2bv_factor_rows(h);
-	return true;
-}
-
 // m4ri_factor_packed(buffer, rows, words, cols, mode[, device]) -> Factorization: m4ri_factor on m4ri_solve_packed's buffer
 // (gf2bv_factor_digits, 32 payload bits per digit)
 PyObject *py_m4ri_factor_packed(PyObject *, PyObject *const *args, Py_ssize_t nargs)
 {
-	if (nargs != 5 && nargs != 6) { PyErr_SetString(PyExc_TypeError, "m4ri_factor_packed requires 5 arguments"); return nullptr; }
-	int device = default_device();
-	if (nargs == 6 && !parse_device(args[5], &device)) return nullptr;
-	const Py_ssize_t rows = PyLong_AsSsize_t(args[1]), words = PyLong_AsSsize_t(args[2]);
-	if ((rows == -1 || words == -1) && PyErr_Occurred()) return nullptr;
-	Py_ssize_t cols;
+	int device;
+	if (!entry_device("m4ri_factor_packed", 5, args, nargs, &device)) return nullptr;
+	Py_ssize_t rows, cols;
 	long mode;
-	if (!parse_cols_mode(args[3], args[4], &cols, &mode) || !rows_cover_cols(rows, cols)) return nullptr;
 	PackedRows pr;
-	if (!pr.parse(args[0], rows, words, cols)) return nullptr;
+	if (!parse_packed_call(args, pr, &rows, &cols, &mode)) return nullptr;
 	gf2bv_factor *h = nullptr;
 	int rc;
 	Py_BEGIN_ALLOW_THREADS
@@ -1102,25 +1066,12 @@ PyObject *py_m4ri_factor_packed(PyObject *, PyObject *const *args, Py_ssize_t na
 	return new_factorization(h, rows, cols, mode, device);
 }
 
-// The prologue of the entries that take the factored form and a row count: arguments `first` .. `first + 3` are the four buffers,
-// then n_lin, rows, mode at the given positions; rows must cover the rows of lin (`live_rows`: the batch entry's systems are checked
-// by its own offsets instead) and the columns
-bool parse_quad_call(PyObject *const *args, int n_at, int rows_at, int mode_at, bool live_rows, QuadBuffers &qb, Py_ssize_t *rows, long *mode)
-{
-	*rows = PyLong_AsSsize_t(args[rows_at]);
-	if (*rows == -1 && PyErr_Occurred()) return false;
-	if (!parse_mode(args[mode_at], mode) || !qb.parse(args, args[n_at])) return false;
-	if (live_rows && *rows < qb.live) { PyErr_SetString(PyExc_ValueError, "rows must be at least the rows of lin"); return false; }
-	return rows_cover_cols(*rows, qb.cols());
-}
-
 // m4ri_factor_quad_packed(lin, term_off, ta, tb, n_lin, rows, mode[, device]) -> Factorization over n_lin + n_lin(n_lin-1)/2
 // columns: m4ri_solve_quad_packed's arguments, expanded on the device and factored there (gf2bv_factor_quad_terms)
 PyObject *py_m4ri_factor_quad_packed(PyObject *, PyObject *const *args, Py_ssize_t nargs)
 {
-	if (nargs != 7 && nargs != 8) { PyErr_SetString(PyExc_TypeError, "m4ri_factor_quad_packed requires 7 arguments"); return nullptr; }
-	int device = default_device();
-	if (nargs == 8 && !parse_device(args[7], &device)) return nullptr;
+	int device;
+	if (!entry_device("m4ri_factor_quad_packed", 7, args, nargs, &device)) return nullptr;
 	Py_ssize_t rows;
 	long mode;
 	QuadBuffers qb;
@@ -1138,38 +1089,26 @@ PyObject *py_m4ri_factor_quad_packed(PyObject *, PyObject *const *args, Py_ssize
 // rhs as Factorization.solve takes it
 PyObject *py_m4ri_solve_rhs_packed(PyObject *, PyObject *const *args, Py_ssize_t nargs)
 {
-	if (nargs != 6 && nargs != 7) { PyErr_SetString(PyExc_TypeError, "m4ri_solve_rhs_packed requires 6 arguments"); return nullptr; }
-	int device = default_device();
-	if (nargs == 7 && !parse_device(args[6], &device)) return nullptr;
-	const Py_ssize_t rows = PyLong_AsSsize_t(args[1]), words = PyLong_AsSsize_t(args[2]);
-	if ((rows == -1 || words == -1) && PyErr_Occurred()) return nullptr;
-	Py_ssize_t cols;
+	int device;
+	if (!entry_device("m4ri_solve_rhs_packed", 6, args, nargs, &device)) return nullptr;
+	Py_ssize_t rows, cols;
 	long mode;
-	if (!parse_cols_mode(args[3], args[4], &cols, &mode) || !rows_cover_cols(rows, cols)) return nullptr;
 	PackedRows pr;
-	if (!pr.parse(args[0], rows, words, cols)) return nullptr;
+	if (!parse_packed_call(args, pr, &rows, &cols, &mode)) return nullptr;
 	RhsInput ri;
 	if (!ri.parse(args[5], rows)) return nullptr;
 	if (ri.nrhs == 0) return PyList_New(0);
-	std::vector<gf2bv_result *> res((size_t)ri.nrhs, nullptr);
-	int rc;
-	Py_BEGIN_ALLOW_THREADS
-	rc = gf2bv_solve_rhs_digits(pr.digits(), pr.off.data(), 32, rows, cols, ri.src, ri.nrhs, ri.stride, (int)mode, device, res.data());
-	Py_END_ALLOW_THREADS
-	if (rc != GF2BV_OK) {
-		for (gf2bv_result *r : res) if (r) gf2bv_result_free(r);
-		return raise_rc(rc, "solve");
-	}
-	return results_to_list(res, mode, device);
+	return collect_results(ri.nrhs, mode, device, [&](gf2bv_result **out) {
+		return gf2bv_solve_rhs_digits(pr.digits(), pr.off.data(), 32, rows, cols, ri.src, ri.nrhs, ri.stride, (int)mode, device, out);
+	});
 }
 
 // m4ri_solve_rhs_quad_packed(lin, term_off, ta, tb, n_lin, rows, mode, rhs[, device]) -> list: one elimination of the expanded
 // system for every right-hand side (gf2bv_solve_rhs_quad_terms); the constants of the factored rows are NOT read, rhs holds them
 PyObject *py_m4ri_solve_rhs_quad_packed(PyObject *, PyObject *const *args, Py_ssize_t nargs)
 {
-	if (nargs != 8 && nargs != 9) { PyErr_SetString(PyExc_TypeError, "m4ri_solve_rhs_quad_packed requires 8 arguments"); return nullptr; }
-	int device = default_device();
-	if (nargs == 9 && !parse_device(args[8], &device)) return nullptr;
+	int device;
+	if (!entry_device("m4ri_solve_rhs_quad_packed", 8, args, nargs, &device)) return nullptr;
 	Py_ssize_t rows;
 	long mode;
 	QuadBuffers qb;
@@ -1177,16 +1116,9 @@ PyObject *py_m4ri_solve_rhs_quad_packed(PyObject *, PyObject *const *args, Py_ss
 	RhsInput ri;
 	if (!ri.parse(args[7], rows)) return nullptr;
 	if (ri.nrhs == 0) return PyList_New(0);
-	std::vector<gf2bv_result *> res((size_t)ri.nrhs, nullptr);
-	int rc;
-	Py_BEGIN_ALLOW_THREADS
-	rc = gf2bv_solve_rhs_quad_terms(qb.lin, qb.off, qb.ta, qb.tb, qb.live, rows, qb.n, ri.src, ri.nrhs, ri.stride, (int)mode, device, res.data());
-	Py_END_ALLOW_THREADS
-	if (rc != GF2BV_OK) {
-		for (gf2bv_result *r : res) if (r) gf2bv_result_free(r);
-		return raise_rc(rc, "solve");
-	}
-	return results_to_list(res, mode, device);
+	return collect_results(ri.nrhs, mode, device, [&](gf2bv_result **out) {
+		return gf2bv_solve_rhs_quad_terms(qb.lin, qb.off, qb.ta, qb.tb, qb.live, rows, qb.n, ri.src, ri.nrhs, ri.stride, (int)mode, device, out);
+	});
 }
 
 // m4ri_solve_many_quad_packed(lin, term_off, ta, tb, sys_row_off, n_lin, rows, mode[, device]) -> list, one element per system:
@@ -1195,19 +1127,18 @@ PyObject *py_m4ri_solve_rhs_quad_packed(PyObject *, PyObject *const *args, Py_ss
 // solved as lock-step gangs (gf2bv_solve_batch_quad_terms); element s is what m4ri_solve_quad_packed returns for system s
 PyObject *py_m4ri_solve_many_quad_packed(PyObject *, PyObject *const *args, Py_ssize_t nargs)
 {
-	if (nargs != 8 && nargs != 9) { PyErr_SetString(PyExc_TypeError, "m4ri_solve_many_quad_packed requires 8 arguments"); return nullptr; }
-	int device = default_device();
-	if (nargs == 9 && !parse_device(args[8], &device)) return nullptr;
+	int device;
+	if (!entry_device("m4ri_solve_many_quad_packed", 8, args, nargs, &device)) return nullptr;
 	Py_ssize_t rows;
 	long mode;
 	QuadBuffers qb;
 	if (!parse_quad_call(args, 5, 6, 7, false, qb, &rows, &mode)) return nullptr;
-	Py_buffer sv;
-	if (PyObject_GetBuffer(args[4], &sv, PyBUF_C_CONTIGUOUS) != 0) return nullptr;
-	const int64_t *sys = static_cast<const int64_t *>(sv.buf);
-	const Py_ssize_t nsys = sv.len / 8 - 1;
+	HeldBuffer sv;
+	if (!sv.take(args[4], PyBUF_C_CONTIGUOUS)) return nullptr;
+	const int64_t *sys = static_cast<const int64_t *>(sv.view.buf);
+	const Py_ssize_t nsys = sv.view.len / 8 - 1;
 	const char *bad = nullptr;
-	if (sv.len % 8 || nsys < 0) bad = "sys_row_off must hold one int64 per system and one more";
+	if (sv.view.len % 8 || nsys < 0) bad = "sys_row_off must hold one int64 per system and one more";
 	else if (sys[0] != 0) bad = "sys_row_off must start at 0";
 	else if (sys[nsys] != qb.live) bad = "sys_row_off must end at the rows of lin";
 	else
@@ -1215,19 +1146,11 @@ PyObject *py_m4ri_solve_many_quad_packed(PyObject *, PyObject *const *args, Py_s
 			if (sys[k + 1] < sys[k]) { bad = "sys_row_off must not decrease"; break; }
 			if (sys[k + 1] - sys[k] > rows) { bad = "rows must be at least the rows of every system"; break; }
 		}
-	if (bad) { PyBuffer_Release(&sv); PyErr_SetString(PyExc_ValueError, bad); return nullptr; }
-	if (nsys == 0) { PyBuffer_Release(&sv); return PyList_New(0); }
-	std::vector<gf2bv_result *> res((size_t)nsys, nullptr);
-	int rc;
-	Py_BEGIN_ALLOW_THREADS
-	rc = gf2bv_solve_batch_quad_terms(qb.lin, qb.off, qb.ta, qb.tb, sys, nsys, rows, qb.n, (int)mode, device, res.data());
-	Py_END_ALLOW_THREADS
-	PyBuffer_Release(&sv);
-	if (rc != GF2BV_OK) {
-		for (gf2bv_result *r : res) if (r) gf2bv_result_free(r);
-		return raise_rc(rc, "solve");
-	}
-	return results_to_list(res, mode, device);
+	if (bad) { PyErr_SetString(PyExc_ValueError, bad); return nullptr; }
+	if (nsys == 0) return PyList_New(0);
+	return collect_results(nsys, mode, device, [&](gf2bv_result **out) {
+		return gf2bv_solve_batch_quad_terms(qb.lin, qb.off, qb.ta, qb.tb, sys, nsys, rows, qb.n, (int)mode, device, out);
+	});
 }
 
 // m4ri_solve_many(list_of_equation_lists, cols, mode[, devices]) -> list of (None | int | AffineSpace).

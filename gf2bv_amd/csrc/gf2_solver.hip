@@ -4711,39 +4711,42 @@ int check_quad_terms(const QuadTerms &q, bool host)
 	return GF2BV_OK;
 }
 
+QuadTerms quad_terms(const void *lin, const void *term_off, const void *ta, const void *tb, i64 rows_live, i64 rows, i64 n_lin)
+{
+	QuadTerms q;
+	q.lin = (const u64 *)lin; q.off = (const i64 *)term_off; q.ta = (const u64 *)ta; q.tb = (const u64 *)tb;
+	q.rows_live = rows_live; q.rows = rows; q.n = n_lin;
+	return q;
+}
+
+// What both expansion kernels are launched with: `tch` products of a row in LDS at a time (64 KiB at most), a thread per two words
+// of an output row
+struct QuadLaunch { int tch; unsigned block; size_t lds; };
+QuadLaunch quad_launch(const QuadTerms &q, i64 stride)
+{
+	const i64 wl = q.wl();
+	const int tch = (int)std::max<i64>(1, std::min<i64>(8, (65536 / 8 / wl - 1) / 2));
+	return { tch, (unsigned)std::min<i64>(256, round_up(std::max<i64>(stride / 2, 1), 64)), sizeof(u64) * (size_t)((1 + 2 * tch) * wl) };
+}
+
 // (device pointers, already checked) the kernel on `st`
 int enqueue_quad_expand(const QuadTerms &q, u64 *d_aug, i64 stride, hipStream_t st)
 {
 	if (q.rows == 0) return GF2BV_OK;
-	const i64 wl = q.wl();
-	const int tch = (int)std::max<i64>(1, std::min<i64>(8, (65536 / 8 / wl - 1) / 2));      // products of a row in LDS at a time: 64 KiB at most
-	const i64 pieces = stride / 2;
-	const unsigned block = (unsigned)std::min<i64>(256, round_up(std::max<i64>(pieces, 1), 64));
+	const QuadLaunch l = quad_launch(q, stride);
 	const unsigned grid = (unsigned)std::min<i64>(q.rows, 256 * 8);
-	hipLaunchKernelGGL(k_quad_expand, dim3(grid), dim3(block), sizeof(u64) * (size_t)((1 + 2 * tch) * wl), st, q.lin, q.off, q.ta, q.tb,
-	                   q.rows_live, q.rows, (int)q.n, (int)wl, tch, d_aug, stride);
+	hipLaunchKernelGGL(k_quad_expand, dim3(grid), dim3(l.block), l.lds, st, q.lin, q.off, q.ta, q.tb, q.rows_live, q.rows, (int)q.n,
+	                   (int)q.wl(), l.tch, d_aug, stride);
 	HIPCHK(hipGetLastError());
 	return GF2BV_OK;
 }
 
-// A pool buffer of a quadratic entry: a refusal is GF2BV_ERR_NOMEM (the expanded rows of a large system or batch may not fit; an
-// append tells a refusal, which leaves the handle as it was, from a failure that does not)
-int quad_alloc(Scratch &scratch, void **out, size_t bytes, int device)
-{
-	const hipError_t e = scratch.alloc(out, std::max<size_t>(bytes, 16), device);
-	if (e == hipErrorOutOfMemory) {
-		(void)hipGetLastError();
-		return fail(GF2BV_ERR_NOMEM, "the factored rows or their expansion do not fit on the device");
-	}
-	if (e != hipSuccess) return fail(GF2BV_ERR_HIP, "expansion buffers", e);
-	return GF2BV_OK;
-}
-
-// The batched form: nsys systems over one concatenated term set, system s owning the rows sys_off[s] .. sys_off[s + 1], at most
-// q.rows of them; q.rows_live becomes sys_off[nsys], the rows of the whole set
+// The batched form: nsys (not negative) systems over one concatenated term set, system s owning the rows sys_off[s] .. sys_off[s + 1],
+// at most q.rows of them; q.rows_live becomes sys_off[nsys], the rows of the whole set
 int check_quad_batch(QuadTerms &q, const i64 *sys_off, i64 nsys)
 {
 	if (!sys_off) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (q.rows < 0 || q.rows >= (1ll << 31) - 64) return fail(GF2BV_ERR_ARG, "rows must be 0 .. 2^31 - 65");
 	if (sys_off[0] != 0) return fail(GF2BV_ERR_ARG, "system row offsets must start at 0");
 	for (i64 s = 0; s < nsys; s++) {
 		if (sys_off[s + 1] < sys_off[s]) return fail(GF2BV_ERR_ARG, "system row offsets must not decrease");
@@ -4761,42 +4764,15 @@ int check_quad_batch(QuadTerms &q, const i64 *sys_off, i64 nsys)
 int enqueue_quad_expand_batch(const QuadTerms &q, const i64 *d_sys_off, i64 nsys, u64 *d_aug, i64 stride, i64 sys_stride, hipStream_t st)
 {
 	if (q.rows == 0 || nsys == 0) return GF2BV_OK;
-	const i64 wl = q.wl();
-	const int tch = (int)std::max<i64>(1, std::min<i64>(8, (65536 / 8 / wl - 1) / 2));
-	const unsigned block = (unsigned)std::min<i64>(256, round_up(std::max<i64>(stride / 2, 1), 64));
+	const QuadLaunch l = quad_launch(q, stride);
 	// a workgroup per row at a time; a few thousand workgroups in all, however many systems share the launch
 	const unsigned gx = (unsigned)std::min<i64>(q.rows, std::max<i64>(256, 256 * 8 / nsys));
 	for (i64 s0 = 0; s0 < nsys; s0 += 65535) {      // (grid y holds 65535 systems)
 		const unsigned ns = (unsigned)std::min<i64>(65535, nsys - s0);
-		hipLaunchKernelGGL(k_quad_expand_batch, dim3(gx, ns), dim3(block), sizeof(u64) * (size_t)((1 + 2 * tch) * wl), st, q.lin, q.off, q.ta, q.tb,
-		                   d_sys_off + s0, q.rows, (int)q.n, (int)wl, tch, d_aug + s0 * sys_stride, stride, sys_stride);
+		hipLaunchKernelGGL(k_quad_expand_batch, dim3(gx, ns), dim3(l.block), l.lds, st, q.lin, q.off, q.ta, q.tb, d_sys_off + s0, q.rows,
+		                   (int)q.n, (int)q.wl(), l.tch, d_aug + s0 * sys_stride, stride, sys_stride);
 	}
 	HIPCHK(hipGetLastError());
-	return GF2BV_OK;
-}
-
-// the factored form of host memory uploaded on `st` into buffers of `scratch`: `d` = q with device pointers; `nomem`: a refused
-// buffer is GF2BV_ERR_NOMEM (quad_alloc) instead of GF2BV_ERR_HIP
-int upload_quad_terms(const QuadTerms &q, QuadTerms &d, Scratch &scratch, int device, hipStream_t st, bool nomem = false)
-{
-	d = q;
-	const i64 wl = q.wl(), T = q.off[q.rows_live];
-	u64 *lin = nullptr, *ta = nullptr, *tb = nullptr;
-	i64 *off = nullptr;
-	const size_t bytes[4] = { sizeof(u64) * (size_t)std::max<i64>(1, q.rows_live * wl), sizeof(i64) * (size_t)(q.rows_live + 1),
-	                          sizeof(u64) * (size_t)std::max<i64>(1, T * wl), sizeof(u64) * (size_t)std::max<i64>(1, T * wl) };
-	void **const bufs[4] = { (void **)&lin, (void **)&off, (void **)&ta, (void **)&tb };
-	for (int k = 0; k < 4; k++) {
-		if (!nomem) HIPCHK(scratch.alloc(bufs[k], bytes[k], device));      // (gf2bv_quad_expand_words, gf2bv_solve_quad_terms: as they always did)
-		else if (int rc = quad_alloc(scratch, bufs[k], bytes[k], device)) return rc;
-	}
-	if (q.rows_live > 0) HIPCHK(hipMemcpyAsync(lin, q.lin, sizeof(u64) * (size_t)(q.rows_live * wl), hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpyAsync(off, q.off, sizeof(i64) * (size_t)(q.rows_live + 1), hipMemcpyHostToDevice, st));
-	if (T > 0) {
-		HIPCHK(hipMemcpyAsync(ta, q.ta, sizeof(u64) * (size_t)(T * wl), hipMemcpyHostToDevice, st));
-		HIPCHK(hipMemcpyAsync(tb, q.tb, sizeof(u64) * (size_t)(T * wl), hipMemcpyHostToDevice, st));
-	}
-	d.lin = lin; d.off = off; d.ta = ta; d.tb = tb;
 	return GF2BV_OK;
 }
 
@@ -4804,6 +4780,67 @@ struct PoolStream {                    // a stream of the pool for the length of
 	hipStream_t st = nullptr;
 	int device = 0;
 	~PoolStream() { pool().release_stream(st, device, 0); }
+};
+
+// A factored system of host memory (checked) staged on the device for the length of an entry: the terms uploaded and expanded into
+// d_aug (q.rows x ds words a system) on ONE pool stream, where the entry underneath is ordered behind the expansion.  On every return
+// path the stream is synchronised before a buffer goes back to the pool (Scratch) and goes back itself after that (PoolStream:
+// declared first, destroyed last): a handle has its own copy by then, a result is on the host.
+struct QuadStage {
+	PoolStream ps;
+	Scratch scratch;
+	const bool nomem;                  // a refused pool buffer is GF2BV_ERR_NOMEM (the expanded rows of a large system or batch may not fit; an
+	                                   // append tells a refusal, which leaves the handle as it was, from a failure that does not); the two
+	                                   // first entries, gf2bv_quad_expand_words and gf2bv_solve_quad_terms, keep their GF2BV_ERR_HIP
+	u64 *d_aug = nullptr, *d_rhs = nullptr;
+	i64 ds = 0;
+	explicit QuadStage(int device, bool nomem = true) : nomem(nomem) { ps.device = device; }
+
+	int alloc(void **out, size_t bytes)
+	{
+		const hipError_t e = scratch.alloc(out, bytes, ps.device);
+		if (e == hipErrorOutOfMemory && nomem) {
+			(void)hipGetLastError();
+			return fail(GF2BV_ERR_NOMEM, "the factored rows or their expansion do not fit on the device");
+		}
+		if (e != hipSuccess) return fail(GF2BV_ERR_HIP, "expansion buffers", e);
+		return GF2BV_OK;
+	}
+	template <class T>
+	int upload(T **d, const T *h, size_t bytes)
+	{
+		if (int rc = alloc((void **)d, bytes)) return rc;
+		if (bytes) HIPCHK(hipMemcpyAsync(*d, h, bytes, hipMemcpyHostToDevice, ps.st));
+		return GF2BV_OK;
+	}
+	// Upload and expansion, with rows `stride` words apart rounded up to an even `ds`; sys_off: the batched form, nsys systems (q as
+	// check_quad_batch left it); rhs: right-hand sides that go up into d_rhs in front of the expansion
+	int expand(QuadTerms q, i64 stride, const i64 *sys_off = nullptr, i64 nsys = 1, const u64 *rhs = nullptr, size_t rhs_bytes = 0)
+	{
+		HIPCHK(pool().stream(&ps.st, ps.device, 0));
+		scratch.sync_first = ps.st;
+		const i64 wl = q.wl(), T = q.off[q.rows_live];
+		u64 *lin = nullptr, *ta = nullptr, *tb = nullptr;
+		i64 *off = nullptr, *d_sys = nullptr;
+		int rc = upload(&lin, q.lin, sizeof(u64) * (size_t)(q.rows_live * wl));
+		if (!rc) rc = upload(&off, q.off, sizeof(i64) * (size_t)(q.rows_live + 1));
+		if (!rc) rc = upload(&ta, q.ta, sizeof(u64) * (size_t)(T * wl));
+		if (!rc) rc = upload(&tb, q.tb, sizeof(u64) * (size_t)(T * wl));
+		if (!rc && sys_off) rc = upload(&d_sys, sys_off, sizeof(i64) * (size_t)(nsys + 1));
+		ds = round_up(stride, 2);
+		if (!rc) rc = alloc((void **)&d_aug, sizeof(u64) * (size_t)(nsys * q.rows * ds));
+		if (!rc && rhs) rc = upload(&d_rhs, rhs, rhs_bytes);
+		if (rc) return rc;
+		q.lin = lin; q.off = off; q.ta = ta; q.tb = tb;
+		return sys_off ? enqueue_quad_expand_batch(q, d_sys, nsys, d_aug, ds, q.rows * ds, ps.st) : enqueue_quad_expand(q, d_aug, ds, ps.st);
+	}
+	// the expansion's `nrows` rows into host memory, `stride` words apart; the host waits
+	int download(void *out, i64 stride, i64 nrows)
+	{
+		HIPCHK(hipMemcpy2DAsync(out, stride * 8, d_aug, ds * 8, stride * 8, nrows, hipMemcpyDeviceToHost, ps.st));
+		HIPCHK(hipStreamSynchronize(ps.st));
+		return GF2BV_OK;
+	}
 };
 
 }  // namespace
@@ -4814,9 +4851,7 @@ int gf2bv_quad_expand_device(const void *d_lin, const void *d_term_off, const vo
                              int64_t rows, int64_t n_lin, void *d_aug, int64_t stride_words, int device, void *stream)
 {
 	return catching([&]() -> int {
-	QuadTerms q;
-	q.lin = (const u64 *)d_lin; q.off = (const i64 *)d_term_off; q.ta = (const u64 *)d_ta; q.tb = (const u64 *)d_tb;
-	q.rows_live = rows_live; q.rows = rows; q.n = n_lin;
+	const QuadTerms q = quad_terms(d_lin, d_term_off, d_ta, d_tb, rows_live, rows, n_lin);
 	int rc = check_quad_terms(q, false);
 	if (rc) return rc;
 	if (!d_aug) return fail(GF2BV_ERR_ARG, "null pointer");
@@ -4828,35 +4863,22 @@ int gf2bv_quad_expand_device(const void *d_lin, const void *d_term_off, const vo
 	});
 }
 
+// ---- the entries on a factored system of host memory: each nulls its outputs, checks, stages (QuadStage) and calls the device entry
+// underneath on the stage's stream (the host waits only where that entry waits), or copies the expansion back
 int gf2bv_quad_expand_words(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t rows_live,
                             int64_t rows, int64_t n_lin, uint64_t *out_aug, int64_t stride_words, int device)
 {
 	return catching([&]() -> int {
-	QuadTerms q, d;
-	q.lin = reinterpret_cast<const u64 *>(lin); q.off = reinterpret_cast<const i64 *>(term_off);
-	q.ta = reinterpret_cast<const u64 *>(ta); q.tb = reinterpret_cast<const u64 *>(tb);
-	q.rows_live = rows_live; q.rows = rows; q.n = n_lin;
+	const QuadTerms q = quad_terms(lin, term_off, ta, tb, rows_live, rows, n_lin);
 	int rc = check_quad_terms(q, true);
 	if (rc) return rc;
 	if (!out_aug && rows > 0) return fail(GF2BV_ERR_ARG, "null pointer");
 	if (stride_words < q.wt()) return fail(GF2BV_ERR_ARG, "stride_words does not cover cols+1 bits");
-	rc = check_device(device);
-	if (rc) return rc;
+	if ((rc = check_device(device))) return rc;
 	if (rows == 0) return GF2BV_OK;
-	PoolStream ps; ps.device = device;
-	HIPCHK(pool().stream(&ps.st, device, 0));
-	Scratch scratch;                   // (declared after ps: released first, after synchronising the stream)
-	scratch.sync_first = ps.st;
-	rc = upload_quad_terms(q, d, scratch, device, ps.st);
-	if (rc) return rc;
-	const i64 ds = round_up(stride_words, 2);
-	u64 *d_aug = nullptr;
-	HIPCHK(scratch.alloc((void **)&d_aug, sizeof(u64) * (size_t)(rows * ds), device));
-	rc = enqueue_quad_expand(d, d_aug, ds, ps.st);
-	if (rc) return rc;
-	HIPCHK(hipMemcpy2DAsync(out_aug, stride_words * 8, d_aug, ds * 8, stride_words * 8, rows, hipMemcpyDeviceToHost, ps.st));
-	HIPCHK(hipStreamSynchronize(ps.st));
-	return GF2BV_OK;
+	QuadStage stage(device, false);
+	if ((rc = stage.expand(q, stride_words))) return rc;
+	return stage.download(out_aug, stride_words, rows);
 	});
 }
 
@@ -4866,37 +4888,16 @@ int gf2bv_solve_quad_terms(const uint64_t *lin, const int64_t *term_off, const u
 	return catching([&]() -> int {
 	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
 	*out = nullptr;
-	QuadTerms q, d;
-	q.lin = reinterpret_cast<const u64 *>(lin); q.off = reinterpret_cast<const i64 *>(term_off);
-	q.ta = reinterpret_cast<const u64 *>(ta); q.tb = reinterpret_cast<const u64 *>(tb);
-	q.rows_live = rows_live; q.rows = rows; q.n = n_lin;
+	const QuadTerms q = quad_terms(lin, term_off, ta, tb, rows_live, rows, n_lin);
 	int rc = check_quad_terms(q, true);
 	if (!rc) rc = check_shape(rows, q.cols(), mode);
 	if (!rc) rc = check_device(device);
 	if (rc) return rc;
-	PoolStream ps; ps.device = device;
-	HIPCHK(pool().stream(&ps.st, device, 0));
-	Scratch scratch;
-	scratch.sync_first = ps.st;
-	rc = upload_quad_terms(q, d, scratch, device, ps.st);
-	if (rc) return rc;
-	const i64 ds = round_up(q.wt(), 2);
-	u64 *d_aug = nullptr;
-	HIPCHK(scratch.alloc((void **)&d_aug, sizeof(u64) * (size_t)(rows * ds), device));
-	rc = enqueue_quad_expand(d, d_aug, ds, ps.st);
-	if (rc) return rc;
-	return gf2bv_solve_device(d_aug, rows, q.cols(), ds, mode, device, ps.st, 0, out);      // same stream: ordered behind the expansion
+	QuadStage stage(device, false);
+	if ((rc = stage.expand(q, q.wt()))) return rc;
+	return gf2bv_solve_device(stage.d_aug, rows, q.cols(), stage.ds, mode, device, stage.ps.st, 0, out);
 	});
 }
-
-// ---- the entries that keep, append to, share and batch an expansion: each is upload, expansion into a pool buffer and the device
-// entry underneath on ONE pool stream (ordered behind the expansion; the host waits only where that entry waits).  The buffers go
-// back to the pool when the entry returns: a handle has its own copy by then, a result is on the host.
-#define QUAD_TERMS(q)                                                                                       \
-	QuadTerms q, d;                                                                                         \
-	q.lin = reinterpret_cast<const u64 *>(lin); q.off = reinterpret_cast<const i64 *>(term_off);            \
-	q.ta = reinterpret_cast<const u64 *>(ta); q.tb = reinterpret_cast<const u64 *>(tb);                     \
-	q.n = n_lin
 
 int gf2bv_factor_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t rows_live,
                             int64_t rows, int64_t n_lin, int mode, int device, gf2bv_factor **out)
@@ -4904,22 +4905,14 @@ int gf2bv_factor_quad_terms(const uint64_t *lin, const int64_t *term_off, const 
 	return catching([&]() -> int {
 	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
 	*out = nullptr;
-	QUAD_TERMS(q);
-	q.rows_live = rows_live; q.rows = rows;
+	const QuadTerms q = quad_terms(lin, term_off, ta, tb, rows_live, rows, n_lin);
 	int rc = check_quad_terms(q, true);
 	if (!rc) rc = check_shape(rows, q.cols(), mode);
 	if (!rc) rc = check_device(device);
 	if (rc) return rc;
-	PoolStream ps; ps.device = device;
-	HIPCHK(pool().stream(&ps.st, device, 0));
-	Scratch scratch;
-	scratch.sync_first = ps.st;
-	if ((rc = upload_quad_terms(q, d, scratch, device, ps.st, true))) return rc;
-	const i64 ds = round_up(q.wt(), 2);
-	u64 *d_aug = nullptr;
-	if ((rc = quad_alloc(scratch, (void **)&d_aug, sizeof(u64) * (size_t)(rows * ds), device))) return rc;
-	if ((rc = enqueue_quad_expand(d, d_aug, ds, ps.st))) return rc;
-	return gf2bv_factor_device(d_aug, rows, q.cols(), ds, mode, device, ps.st, out);
+	QuadStage stage(device);
+	if ((rc = stage.expand(q, q.wt()))) return rc;
+	return gf2bv_factor_device(stage.d_aug, rows, q.cols(), stage.ds, mode, device, stage.ps.st, out);
 	});
 }
 
@@ -4930,26 +4923,17 @@ int gf2bv_factor_append_quad_terms(gf2bv_factor *h, const uint64_t *lin, const i
 	if (!h) return fail(GF2BV_ERR_ARG, "null pointer");
 	if (h->failed) return fail(GF2BV_ERR_ARG, kFailedHandle);
 	if (rows < 1) return fail(GF2BV_ERR_ARG, "rows must be at least 1");
-	QUAD_TERMS(q);
-	q.rows_live = q.rows = rows;
+	const QuadTerms q = quad_terms(lin, term_off, ta, tb, rows, rows, n_lin);
 	int rc = check_quad_terms(q, true);
 	if (rc) return rc;
 	if (q.cols() != h->cols) return fail(GF2BV_ERR_ARG, "n_lin does not match the handle's columns");
 	if (h->rows + rows >= (1ll << 31) - 64) return fail(GF2BV_ERR_ARG, "system too large");
-	const int device = h->device;
-	if ((rc = check_device(device))) return rc;
-	PoolStream ps; ps.device = device;
-	HIPCHK(pool().stream(&ps.st, device, 0));
-	Scratch scratch;
-	scratch.sync_first = ps.st;
+	if ((rc = check_device(h->device))) return rc;
 	// (the uploaded terms and the expansion are taken before gf2bv_factor_append_device takes its own buffers: a refusal of any
 	// of them leaves the handle as it was)
-	if ((rc = upload_quad_terms(q, d, scratch, device, ps.st, true))) return rc;
-	const i64 ds = round_up(q.wt(), 2);
-	u64 *d_aug = nullptr;
-	if ((rc = quad_alloc(scratch, (void **)&d_aug, sizeof(u64) * (size_t)(rows * ds), device))) return rc;
-	if ((rc = enqueue_quad_expand(d, d_aug, ds, ps.st))) return rc;
-	return gf2bv_factor_append_device(h, d_aug, rows, ds, ps.st);
+	QuadStage stage(h->device);
+	if ((rc = stage.expand(q, q.wt()))) return rc;
+	return gf2bv_factor_append_device(h, stage.d_aug, rows, stage.ds, stage.ps.st);
 	});
 }
 
@@ -4960,26 +4944,16 @@ int gf2bv_solve_rhs_quad_terms(const uint64_t *lin, const int64_t *term_off, con
 	return catching([&]() -> int {
 	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
 	for (i64 j = 0; j < nrhs; j++) out[j] = nullptr;
-	QUAD_TERMS(q);
-	q.rows_live = rows_live; q.rows = rows;
+	const QuadTerms q = quad_terms(lin, term_off, ta, tb, rows_live, rows, n_lin);
 	int rc = check_quad_terms(q, true);
 	if (!rc) rc = check_shape(rows, q.cols(), mode);
 	if (!rc) rc = check_rhs_args(rows, q.cols(), rhs, false, nrhs, rhs_words);
 	if (!rc) rc = check_device(device);
 	if (rc) return rc;
-	PoolStream ps; ps.device = device;
-	HIPCHK(pool().stream(&ps.st, device, 0));
-	Scratch scratch;
-	scratch.sync_first = ps.st;
-	if ((rc = upload_quad_terms(q, d, scratch, device, ps.st, true))) return rc;
-	const i64 ds = round_up(q.wt(), 2);
-	u64 *d_aug = nullptr, *d_rhs = nullptr;
-	if ((rc = quad_alloc(scratch, (void **)&d_aug, sizeof(u64) * (size_t)(rows * ds), device))) return rc;
-	if ((rc = quad_alloc(scratch, (void **)&d_rhs, sizeof(u64) * (size_t)(nrhs * rhs_words), device))) return rc;
-	HIPCHK(hipMemcpyAsync(d_rhs, rhs, sizeof(u64) * (size_t)(nrhs * rhs_words), hipMemcpyHostToDevice, ps.st));
-	if ((rc = enqueue_quad_expand(d, d_aug, ds, ps.st))) return rc;
+	QuadStage stage(device);
+	if ((rc = stage.expand(q, q.wt(), nullptr, 1, reinterpret_cast<const u64 *>(rhs), sizeof(u64) * (size_t)(nrhs * rhs_words)))) return rc;
 	// (the constant the expansion leaves in column `cols` is ignored there: the caller's rhs holds the constants)
-	return gf2bv_solve_rhs_device(d_aug, rows, q.cols(), ds, d_rhs, nrhs, rhs_words, mode, device, ps.st, 0, out);
+	return gf2bv_solve_rhs_device(stage.d_aug, rows, q.cols(), stage.ds, stage.d_rhs, nrhs, rhs_words, mode, device, stage.ps.st, 0, out);
 	});
 }
 
@@ -4989,32 +4963,17 @@ int gf2bv_quad_expand_batch_words(const uint64_t *lin, const int64_t *term_off, 
 {
 	return catching([&]() -> int {
 	if (nsys < 0) return fail(GF2BV_ERR_ARG, "nsys must not be negative");
-	QUAD_TERMS(q);
-	q.rows = rows;
-	if (q.n < 1 || q.n > 65535) return fail(GF2BV_ERR_ARG, "n_lin must be at least 1 and n_lin + n_lin(n_lin-1)/2 below 2^31 - 64");
-	if (rows < 0 || rows >= (1ll << 31) - 64) return fail(GF2BV_ERR_ARG, "rows must be 0 .. 2^31 - 65");
-	int rc = check_quad_batch(q, reinterpret_cast<const i64 *>(sys_row_off), nsys);
+	const i64 *sys_off = reinterpret_cast<const i64 *>(sys_row_off);
+	QuadTerms q = quad_terms(lin, term_off, ta, tb, 0, rows, n_lin);
+	int rc = check_quad_batch(q, sys_off, nsys);
 	if (rc) return rc;
 	if (!out_aug && rows > 0 && nsys > 0) return fail(GF2BV_ERR_ARG, "null pointer");
 	if (stride_words < q.wt()) return fail(GF2BV_ERR_ARG, "stride_words does not cover cols+1 bits");
 	if ((rc = check_device(device))) return rc;
 	if (rows == 0 || nsys == 0) return GF2BV_OK;
-	PoolStream ps; ps.device = device;
-	HIPCHK(pool().stream(&ps.st, device, 0));
-	Scratch scratch;
-	scratch.sync_first = ps.st;
-	if ((rc = upload_quad_terms(q, d, scratch, device, ps.st, true))) return rc;
-	i64 *d_sys = nullptr;
-	if ((rc = quad_alloc(scratch, (void **)&d_sys, sizeof(i64) * (size_t)(nsys + 1), device))) return rc;
-	HIPCHK(hipMemcpyAsync(d_sys, sys_row_off, sizeof(i64) * (size_t)(nsys + 1), hipMemcpyHostToDevice, ps.st));
-	const i64 ds = round_up(stride_words, 2);
-	u64 *d_aug = nullptr;
-	if ((rc = quad_alloc(scratch, (void **)&d_aug, sizeof(u64) * (size_t)(nsys * rows * ds), device))) return rc;
-	d.rows = rows;
-	if ((rc = enqueue_quad_expand_batch(d, d_sys, nsys, d_aug, ds, rows * ds, ps.st))) return rc;
-	HIPCHK(hipMemcpy2DAsync(out_aug, stride_words * 8, d_aug, ds * 8, stride_words * 8, nsys * rows, hipMemcpyDeviceToHost, ps.st));
-	HIPCHK(hipStreamSynchronize(ps.st));
-	return GF2BV_OK;
+	QuadStage stage(device);
+	if ((rc = stage.expand(q, stride_words, sys_off, nsys))) return rc;
+	return stage.download(out_aug, stride_words, nsys * rows);
 	});
 }
 
@@ -5025,31 +4984,18 @@ int gf2bv_solve_batch_quad_terms(const uint64_t *lin, const int64_t *term_off, c
 	return catching([&]() -> int {
 	if (!out || nsys < 0) return fail(GF2BV_ERR_ARG, "null pointer");
 	for (i64 s = 0; s < nsys; s++) out[s] = nullptr;
-	QUAD_TERMS(q);
-	q.rows = rows;
-	if (q.n < 1 || q.n > 65535) return fail(GF2BV_ERR_ARG, "n_lin must be at least 1 and n_lin + n_lin(n_lin-1)/2 below 2^31 - 64");
-	int rc = check_shape(rows, q.cols(), mode);
-	if (!rc) rc = check_quad_batch(q, reinterpret_cast<const i64 *>(sys_row_off), nsys);
+	const i64 *sys_off = reinterpret_cast<const i64 *>(sys_row_off);
+	QuadTerms q = quad_terms(lin, term_off, ta, tb, 0, rows, n_lin);
+	int rc = check_quad_batch(q, sys_off, nsys);
+	if (!rc) rc = check_shape(rows, q.cols(), mode);
 	if (!rc) rc = check_device(device);
 	if (rc) return rc;
 	if (nsys == 0) return GF2BV_OK;
-	PoolStream ps; ps.device = device;
-	HIPCHK(pool().stream(&ps.st, device, 0));
-	Scratch scratch;
-	scratch.sync_first = ps.st;
-	if ((rc = upload_quad_terms(q, d, scratch, device, ps.st, true))) return rc;
-	i64 *d_sys = nullptr;
-	if ((rc = quad_alloc(scratch, (void **)&d_sys, sizeof(i64) * (size_t)(nsys + 1), device))) return rc;
-	HIPCHK(hipMemcpyAsync(d_sys, sys_row_off, sizeof(i64) * (size_t)(nsys + 1), hipMemcpyHostToDevice, ps.st));
-	const i64 ds = round_up(q.wt(), 2);
-	u64 *d_aug = nullptr;
-	if ((rc = quad_alloc(scratch, (void **)&d_aug, sizeof(u64) * (size_t)(nsys * rows * ds), device))) return rc;
-	d.rows = rows;
-	if ((rc = enqueue_quad_expand_batch(d, d_sys, nsys, d_aug, ds, rows * ds, ps.st))) return rc;
+	QuadStage stage(device);
+	if ((rc = stage.expand(q, q.wt(), sys_off, nsys))) return rc;
 	// (the gangs run on streams of their own, behind an event gf2bv_solve_batch_device records on this one)
-	return gf2bv_solve_batch_device(d_aug, nsys, rows * ds, rows, q.cols(), ds, mode, device, ps.st, 0, out);
+	return gf2bv_solve_batch_device(stage.d_aug, nsys, rows * stage.ds, rows, q.cols(), stage.ds, mode, device, stage.ps.st, 0, out);
 	});
 }
-#undef QUAD_TERMS
 
 }  // extern "C"

@@ -282,10 +282,15 @@ def solve_batch_device(d_ptr: int, nsys: int, sys_stride: int, rows: int, cols: 
                        mode: int = MODE_SINGLE, device: int = 0, stream: int = 0, time_kernels: bool = False) -> list:
     """nsys equal-shape systems resident in device memory, solved as lock-step gangs.  `stream` = the stream that
     produced the matrices (0 = the null stream): the gangs are ordered after it."""
-    hs = (ctypes.c_void_p * max(nsys, 1))()
+    hs = _handles(nsys)
     rc = lib().gf2bv_solve_batch_device(d_ptr, nsys, sys_stride, rows, cols, stride, mode, device, stream or None,
                                         1 if time_kernels else 0, hs)
     return _take_all(hs, nsys, rc, mode)
+
+
+def _handles(n: int):
+    """the out[] of an entry that makes n results (never of length 0)"""
+    return (ctypes.c_void_p * max(n, 1))()
 
 
 def _take_all(hs, nsys: int, rc: int, mode: int) -> list:
@@ -304,7 +309,7 @@ def solve_batch_digits(digits: np.ndarray, offsets: np.ndarray, bits_per_digit: 
     host thread per entry (gf2bv_solve_batch_digits_multi); default: everything on `device`."""
     digits = np.ascontiguousarray(digits, dtype=np.uint32)
     offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-    hs = (ctypes.c_void_p * max(nsys, 1))()
+    hs = _handles(nsys)
     if devices is None:
         rc = lib().gf2bv_solve_batch_digits(digits.ctypes.data, offsets.ctypes.data, bits_per_digit, nsys, rows, cols,
                                             mode, device, hs)
@@ -346,7 +351,7 @@ def solve_rhs_words(aug: np.ndarray, rows: int, cols: int, rhs: np.ndarray, mode
     stride = aug.shape[1] if aug.ndim == 2 else (cols + 1 + 63) // 64
     rhs = _rhs_array(rhs)
     nrhs = rhs.shape[0]
-    hs = (ctypes.c_void_p * max(nrhs, 1))()
+    hs = _handles(nrhs)
     rc = lib().gf2bv_solve_rhs_words(aug.ctypes.data, rows, cols, stride, rhs.ctypes.data, nrhs, rhs.shape[1], mode, device, hs)
     return _take_all(hs, nrhs, rc, mode)
 
@@ -358,7 +363,7 @@ def solve_rhs_digits(digits: np.ndarray, offsets: np.ndarray, bits_per_digit: in
     offsets = np.ascontiguousarray(offsets, dtype=np.int64)
     rhs = _rhs_array(rhs)
     nrhs = rhs.shape[0]
-    hs = (ctypes.c_void_p * max(nrhs, 1))()
+    hs = _handles(nrhs)
     rc = lib().gf2bv_solve_rhs_digits(digits.ctypes.data, offsets.ctypes.data, bits_per_digit, rows, cols, rhs.ctypes.data, nrhs,
                                       rhs.shape[1], mode, device, hs)
     return _take_all(hs, nrhs, rc, mode)
@@ -367,7 +372,7 @@ def solve_rhs_digits(digits: np.ndarray, offsets: np.ndarray, bits_per_digit: in
 def solve_rhs_device(d_ptr: int, rows: int, cols: int, stride: int, d_rhs: int, nrhs: int, rhs_words: int,
                      mode: int = MODE_SINGLE, device: int = 0, stream: int = 0, time_kernels: bool = False) -> list:
     """solve_rhs_words with matrix and right-hand sides resident in device memory (both left untouched)."""
-    hs = (ctypes.c_void_p * max(nrhs, 1))()
+    hs = _handles(nrhs)
     rc = lib().gf2bv_solve_rhs_device(d_ptr, rows, cols, stride, d_rhs, nrhs, rhs_words, mode, device, stream or None,
                                       1 if time_kernels else 0, hs)
     return _take_all(hs, max(nrhs, 0), rc, mode)
@@ -417,7 +422,7 @@ class Factor:
         """Append factored quadratic equations (the arrays of quad_expand_words, every row live): expanded on the device and
         appended there (gf2bv_factor_append_quad_terms); n_lin must be the one the factorization was made with"""
         lin, term_off, ta, tb = _quad_terms(lin, term_off, ta, tb, n_lin)
-        _check(lib().gf2bv_factor_append_quad_terms(self._handle(), lin.ctypes.data, term_off.ctypes.data, ta.ctypes.data, tb.ctypes.data,
+        _check(lib().gf2bv_factor_append_quad_terms(self._handle(), *_ptrs(lin, term_off, ta, tb),
                                                     len(lin), n_lin))
 
     def copy(self) -> "Factor":
@@ -444,13 +449,13 @@ class Factor:
         """rhs: [nrhs, >= ceil(rows / 64)] uint64 (see solve_rhs_words); one Solution per right-hand side"""
         rhs = _rhs_array(rhs)
         nrhs = rhs.shape[0]
-        hs = (ctypes.c_void_p * max(nrhs, 1))()
+        hs = _handles(nrhs)
         rc = lib().gf2bv_factor_solve(self._handle(), rhs.ctypes.data, nrhs, rhs.shape[1], hs)
         return _take_all(hs, nrhs, rc, self.mode)
 
     def solve_device(self, d_rhs: int, nrhs: int, rhs_words: int, stream: int = 0) -> list:
         """solve() with the right-hand sides resident in device memory"""
-        hs = (ctypes.c_void_p * max(nrhs, 1))()
+        hs = _handles(nrhs)
         rc = lib().gf2bv_factor_solve_device(self._handle(), d_rhs, nrhs, rhs_words, stream or None, 0, hs)
         return _take_all(hs, max(nrhs, 0), rc, self.mode)
 
@@ -599,6 +604,10 @@ def _quad_terms(lin, term_off, ta, tb, n_lin: int):
     return lin, term_off, ta, tb
 
 
+def _ptrs(*arrays):
+    return [a.ctypes.data for a in arrays]
+
+
 def quad_expand_words(lin, term_off, ta, tb, n_lin: int, rows: int | None = None, stride_words: int | None = None,
                       device: int = 0) -> np.ndarray:
     """Factored quadratic equations (lin[r] ^ XOR of the products ta[t] * tb[t], t in term_off[r] .. term_off[r + 1]; linear forms of
@@ -608,7 +617,7 @@ def quad_expand_words(lin, term_off, ta, tb, n_lin: int, rows: int | None = None
     rows = len(lin) if rows is None else rows
     stride = (quad_cols(n_lin) + 1 + 63) // 64 if stride_words is None else stride_words
     out = np.empty((max(rows, 0), max(stride, 0)), dtype=np.uint64)
-    _check(lib().gf2bv_quad_expand_words(lin.ctypes.data, term_off.ctypes.data, ta.ctypes.data, tb.ctypes.data, len(lin), rows, n_lin,
+    _check(lib().gf2bv_quad_expand_words(*_ptrs(lin, term_off, ta, tb), len(lin), rows, n_lin,
                                          out.ctypes.data, stride, device))
     return out
 
@@ -626,7 +635,7 @@ def solve_quad_terms(lin, term_off, ta, tb, n_lin: int, rows: int | None = None,
     lin, term_off, ta, tb = _quad_terms(lin, term_off, ta, tb, n_lin)
     rows = max(len(lin), quad_cols(n_lin)) if rows is None else rows
     h = ctypes.c_void_p()
-    _check(lib().gf2bv_solve_quad_terms(lin.ctypes.data, term_off.ctypes.data, ta.ctypes.data, tb.ctypes.data, len(lin), rows, n_lin,
+    _check(lib().gf2bv_solve_quad_terms(*_ptrs(lin, term_off, ta, tb), len(lin), rows, n_lin,
                                         mode, device, ctypes.byref(h)))
     return _take(h, mode)
 
@@ -637,7 +646,7 @@ def factor_quad_terms(lin, term_off, ta, tb, n_lin: int, rows: int | None = None
     lin, term_off, ta, tb = _quad_terms(lin, term_off, ta, tb, n_lin)
     rows = max(len(lin), quad_cols(n_lin)) if rows is None else rows
     h = ctypes.c_void_p()
-    rc = lib().gf2bv_factor_quad_terms(lin.ctypes.data, term_off.ctypes.data, ta.ctypes.data, tb.ctypes.data, len(lin), rows, n_lin,
+    rc = lib().gf2bv_factor_quad_terms(*_ptrs(lin, term_off, ta, tb), len(lin), rows, n_lin,
                                        mode, device, ctypes.byref(h))
     return _factor(rc, h, rows, quad_cols(n_lin), mode)
 
@@ -650,8 +659,8 @@ def solve_rhs_quad_terms(lin, term_off, ta, tb, n_lin: int, rhs: np.ndarray, row
     rows = max(len(lin), quad_cols(n_lin)) if rows is None else rows
     rhs = _rhs_array(rhs)
     nrhs = rhs.shape[0]
-    hs = (ctypes.c_void_p * max(nrhs, 1))()
-    rc = lib().gf2bv_solve_rhs_quad_terms(lin.ctypes.data, term_off.ctypes.data, ta.ctypes.data, tb.ctypes.data, len(lin), rows, n_lin,
+    hs = _handles(nrhs)
+    rc = lib().gf2bv_solve_rhs_quad_terms(*_ptrs(lin, term_off, ta, tb), len(lin), rows, n_lin,
                                           rhs.ctypes.data, nrhs, rhs.shape[1], mode, device, hs)
     return _take_all(hs, nrhs, rc, mode)
 
@@ -672,8 +681,8 @@ def solve_batch_quad_terms(lin, term_off, ta, tb, sys_row_off, n_lin: int, rows:
     sys_row_off = _sys_row_off(sys_row_off, len(lin))
     nsys = len(sys_row_off) - 1
     rows = max(int(np.diff(sys_row_off).max(initial=0)), quad_cols(n_lin)) if rows is None else rows
-    hs = (ctypes.c_void_p * max(nsys, 1))()
-    rc = lib().gf2bv_solve_batch_quad_terms(lin.ctypes.data, term_off.ctypes.data, ta.ctypes.data, tb.ctypes.data, sys_row_off.ctypes.data,
+    hs = _handles(nsys)
+    rc = lib().gf2bv_solve_batch_quad_terms(*_ptrs(lin, term_off, ta, tb), sys_row_off.ctypes.data,
                                             nsys, rows, n_lin, mode, device, hs)
     return _take_all(hs, nsys, rc, mode)
 
@@ -687,7 +696,7 @@ def quad_expand_batch_words(lin, term_off, ta, tb, sys_row_off, n_lin: int, rows
     nsys = len(sys_row_off) - 1
     stride = (quad_cols(n_lin) + 1 + 63) // 64 if stride_words is None else stride_words
     out = np.empty((nsys, max(rows, 0), max(stride, 0)), dtype=np.uint64)
-    _check(lib().gf2bv_quad_expand_batch_words(lin.ctypes.data, term_off.ctypes.data, ta.ctypes.data, tb.ctypes.data,
+    _check(lib().gf2bv_quad_expand_batch_words(*_ptrs(lin, term_off, ta, tb),
                                                sys_row_off.ctypes.data, nsys, rows, n_lin, out.ctypes.data, stride, device))
     return out
 

@@ -189,6 +189,10 @@ def test_entries_check_arguments_before_device_use():
         m4ri_solve_quad_packed(lin, off, ta, tb[:-1].copy(), n, rows, 0)
     with pytest.raises(ValueError, match="end at the number"):
         m4ri_solve_quad_packed(lin, off, ta[:-1].copy(), tb[:-1].copy(), n, rows, 0)
+    with pytest.raises(ValueError, match="term_off must start at 0"):         # (the extension's own check, not the library's)
+        m4ri_solve_quad_packed(lin, bad0, ta, tb, n, rows, 0)
+    with pytest.raises(ValueError, match="term_off must not decrease"):
+        m4ri_solve_quad_packed(lin, dec, ta, tb, n, rows, 0)
     with pytest.raises(ValueError, match="at least the rows of lin"):
         m4ri_solve_quad_packed(lin, off, ta, tb, n, 69, 0)
     with pytest.raises(ValueError, match="n_lin"):

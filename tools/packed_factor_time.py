@@ -25,6 +25,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
+import torch  # noqa: E402  (before the library: one HIP runtime per process, as in the tests)
 
 from gf2bv_amd import LinearSystem, PackedLinearSystem, PackedQuadBitVec, PackedQuadraticSystem, QuadraticSystem, hip  # noqa: E402
 from gf2bv_amd.packed import _popcount64  # noqa: E402
@@ -223,7 +224,6 @@ def case_many(n: int, counts, reps: int):
 
 if __name__ == "__main__":
     small = "--small" in sys.argv
-    import torch  # noqa: E402  (the device's name)
     say(f"tools/packed_factor_time.py{' --small' if small else ''} on one {torch.cuda.get_device_name(0)} (build {hip.build_id()}).")
     reps = 1 if small else 5
     for n, with_int in ((24, True), (40, False)) if small else ((128, True), (256, False)):
