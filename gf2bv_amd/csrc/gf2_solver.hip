@@ -497,6 +497,15 @@ Pool &pool()
 	static Pool *p = new Pool();      // intentionally leaked: the HIP runtime may be gone at static destruction
 	return *p;
 }
+// A pool buffer for an entry that tells "does not fit" from a failure: out of device memory is GF2BV_ERR_NOMEM with the message
+// `nomem` (and the runtime's sticky error cleared), any other error GF2BV_ERR_HIP with `what`.
+int alloc_or_nomem(void **out, size_t bytes, int device, const char *nomem, const char *what)
+{
+	const hipError_t e = pool().alloc(out, bytes, device);
+	if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(GF2BV_ERR_NOMEM, nomem); }
+	if (e != hipSuccess) return fail(GF2BV_ERR_HIP, what, e);
+	return GF2BV_OK;
+}
 
 // ---- kernel configurations -----------------------------------------------------------------
 // Bulk update: G panels fused per HBM pass, T grease tables per panel (balanced bit-fields).
@@ -583,67 +592,50 @@ hipError_t launch_ysweep(dim3 grid, hipStream_t s, u64 *Y, i64 ys, i64 rows, con
 constexpr int TW = GF2_TW;        // words per column tile
 
 // ---- one solve ---------------------------------------------------------------------------------
-struct Solver {
+inline size_t round256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
+// Where the side arrays of ONE system lie in its arena: byte offsets, each rounded up to 256, in this order (solver_alloc clears
+// st .. died and blk_first .. Wb with one memset each), and the bytes from one system of a gang to the next.  arena_layout()
+// computes it, ArenaPtrs::bind() turns it into pointers; nothing else lists the members.
+struct ArenaLayout {
+	size_t st = 0, sf = 0, panels = 0, aux = 0, fu = 0, died = 0, pivcol = 0, urow = 0, blk_first = 0, mult = 0, Wb = 0, Uwin = 0, Pfast = 0,
+	       oprow = 0, Tm = 0, Pc = 0, wmask = 0, stride = 0;
+};
+
+// What a solve IS apart from the device and pool resources it holds: the shape, the plan, the counters and the host copies.  Plain
+// values, free to copy -- a gang's views and the copy of a kept factorization start from their original's (make_view, factor_copy).
+struct SolverPlan {
 	int device = 0;
-	hipStream_t sA = nullptr, sB = nullptr;      // panel path / bulk path
-	bool own_sA = false, own_sB = false;
-	u64 *M = nullptr;             // tile-major working copy (always owned)
-	const u64 *src = nullptr;     // caller's row-major matrix on the device (stride words per row)
-	u64 *tmp_src = nullptr;       // row-major staging buffer when the input came from the host
-	u64 *Minv = nullptr;          // inverted diagonal blocks of the back-substitution (k_bs_inv -> k_bs_near2)
 	i64 rows = 0, cols = 0, stride = 0;
 	i64 ntiles = 0, srows = 0;    // tiles, rows per tile slab (padded)
 	// gang: nsys same-shape systems eliminated in lock-step by the same launches (blockIdx.y = system);
-	// system s lives at M + s * m_stride words / arena + s * arena_stride bytes, its input at src + s * src_sys_words
+	// system s lives at M + s * m_stride words / arena + s * lay.stride bytes, its input at src + s * src_sys_words
 	int nsys = 1;
 	int gang_nsys = 1;            // (a view: the size of the gang it belongs to)
 	// column-slab solve of ONE system over `world` GPUs: this rank owns the column tiles t with t % world == wrank
 	// (cyclic, so that the shrinking trailing matrix stays balanced) and runs the bulk path on those only; the panel
 	// path of a block runs on the owner of its window's tile (see gf2bv_slab_* below)
 	int world = 1, wrank = 0;
-	bool ext_M = false;           // the working matrix belongs to the caller (slab solves: a tensor the ranks exchange tiles of)
 	i64 m_stride = 0, src_sys_words = 0;
-	size_t arena_stride = 0;
+	ArenaLayout lay;              // (a view: of its one system, stride 0)
 	bool view = false;            // a non-owning window on one system of a gang (back-substitution, export)
 	bool own_bs = true;           // (a view) Y / ycols / out are its own; false: `out` points into the gang's (enqueue_backward_gang)
-	SysStride ss() const { return SysStride{ m_stride, (i64)arena_stride }; }
+	SysStride ss() const { return SysStride{ m_stride, (i64)lay.stride }; }
 	int mode = 0;
 	// many right-hand sides of one matrix (gf2bv_solve_rhs_*): right-hand side j is column cols + j, k_check_rhs_many leaves
 	// the per-RHS inconsistency bits in rhs_bad (ceil(nrhs / 64) words); nrhs == 1 with rhs_bad == nullptr: every other entry
 	int nrhs = 1;
-	u64 *rhs_bad = nullptr;
 	bool time_kernels = false;
 	Knobs kn;                     // the environment switches as solver_alloc found them (see Knobs: a kept handle refreshes three per call)
 	const UpdateImpl *impl = nullptr;
 
-	void *arena = nullptr;        // st, panels, aux, fu, alive, pivcol, urow, blk_first, mult, Wb live in here
-	SolveState *st = nullptr;
-	PanelRec *panels = nullptr;
-	PanelAux *aux = nullptr;
-	FindUnit *fu = nullptr;
-	int *died = nullptr;          // per row: panel that made it a pivot source, GF2_NEVER while alive
-	int *pivcol = nullptr, *urow = nullptr, *blk_first = nullptr;
-	u64 *mult = nullptr;          // nsets sets x G x rows: block b writes / reads set b % nsets (2 = ping-pong; an outer panel of the
-	                              // two-level elimination keeps all its K blocks' multipliers until its outer pass: nsets = K)
-	int nsets = 2;
+	int nsets = 2;                // multiplier sets (ArenaPtrs::mult)
 	// two-level elimination (large systems; see k_update16k): blocks [0, tl_bend) go in outer panels of tl_K blocks
 	int tl_K = 0, tl_bend = 0;
 	i64 tile_hi = 0;              // bulk kernels touch tiles < tile_hi (= ntiles; the outer panel's end while it is eliminated)
 	static constexpr int nlist = 2;      // row lists / T matrices kept: by panel parity (the previous panel's outer pass may still be reading its own)
-	hipStream_t sC = nullptr;     // outer passes: panel p's runs BESIDE the inner elimination of panel p + 1 (sA + sB)
-	                              // (late round 5 also split the pass itself over two streams, behind a switch of its own: 131072^2 162 -> 155 ms,
-	                              // 262144^2 -0.8 %, but a fourth stream that cost later batch calls of the process their overlap; removed in
-	                              // round 6, profiles/r05_outer_shapes.txt)
-	hipEvent_t evOuter = nullptr, evPri = nullptr, evPanelDone = nullptr, evBig = nullptr;
 	bool bulk_waits_outer = false;     // the next bulk launch of the one-level schedule has to wait for the last outer pass
 	bool ends_outer_panel(int b) const { return tl_K > 0 && b < tl_bend && (b + 1) % tl_K == 0; }
-	u64 *Wb = nullptr;            // 2 x rows x GMAX window words (the panel steps ping-pong between the halves)
-	u64 *Uwin = nullptr;          // rank x GMAX: pivot rows' words of the following window (k_prio_window -> k_unwind)
-	int *oprow = nullptr;         // k_outer_prow -> k_outer_apply / k_update16k: row lists of the outer panel being applied
-	u64 *Tm = nullptr;            // k_outer_trsm<IDENT> -> k_outer_apply: the panel's pivot rows as combinations of its source rows
-	u64 *Pc = nullptr;            // final pivot rows of the current block, compact: [tile][panel][pivot bit] x 16 B (k_block_trsm -> k_update16)
-	u64 *Pfast = nullptr;         // scratch of k_block_fast: the pivot rows' window words of a block, [panel][word][column]
-	SyncFlags *sf = nullptr;      // progress counters of the two streams (k_gate)
 	// what a solve decides from the switches and the device (set in one block of solver_alloc)
 	bool flag_sync = true;        // per-block hand-overs between the streams through sf + k_gate instead of events (kn.flag_sync; the device has a say)
 	bool optimistic = true;       // the general panel steps are dropped behind the one-launch search once block 0 has taken it (kn.optimistic)
@@ -656,11 +648,7 @@ struct Solver {
 	bool sparse_on = false;       // this solve has switched to it (after block 0 went the general way)
 	int sparse_giveups = 0;
 	int sparse_tier = 0;          // pool size of k_block_sparse: 0 = 1024 rows (beside the bulk update), 1 = 4096, 2 = 6144
-	u64 *wmask = nullptr;         // 2 x ceil(rows / 64) words: alive / alive with a non-zero window, per 64 rows
 	int narrow_rpt = 1;           // row blocks of 256 per narrow workgroup of a panel step (set in solver_alloc)
-	u64 *Y = nullptr;
-	int *ycols = nullptr;
-	u64 *out = nullptr;
 	i64 ys = 0;
 	int ny = 0;
 	int h_ycol = 0;               // (host copy of the gang's one right-hand-side column: lives as long as the copy may)
@@ -668,56 +656,131 @@ struct Solver {
 	int npanels = 0, nblocks = 0;
 	i64 wt = 0, cw = 0;
 
-	hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
-	std::vector<hipEvent_t> evA, evPrio, kev, waitPrio;     // waitPrio[b]: the event that means "bulk of block b complete"
 	std::vector<int> free_order;     // free columns in M4RI kernel order (mode 1)
 	// host staging of the export (filled by asynchronous copies between finish_begin and finish_end)
 	SolveState hst{};
 	std::vector<u64> hout;
 	std::vector<PanelRec> hp;
 	std::vector<int32_t> hpiv;
-	hipEvent_t evx = nullptr;
 	std::chrono::steady_clock::time_point t_begin;
 	float ms_pack = 0;
+};
 
+ArenaLayout arena_layout(const SolverPlan &P)
+{
+	const i64 R = std::max<i64>(1, P.rows), NP = std::max(1, P.npanels);
+	const int G = P.impl->G;
+	ArenaLayout L;
+	size_t off = 0;
+	auto carve = [&](size_t bytes) { size_t at = off; off += round256(bytes); return at; };
+	L.st = carve(sizeof(SolveState)); L.sf = carve(sizeof(SyncFlags)); L.panels = carve(sizeof(PanelRec) * NP); L.aux = carve(sizeof(PanelAux) * NP);
+	L.fu = carve(sizeof(FindUnit) * (P.units + 1 + GF2_MAXGROUPS)); L.died = carve(sizeof(int) * (size_t)R);
+	L.pivcol = carve(sizeof(int) * (P.maxr + 64)); L.urow = carve(sizeof(int) * (P.maxr + 64));
+	L.blk_first = carve(sizeof(int) * std::max(1, P.nblocks)); L.mult = carve(sizeof(u64) * P.nsets * G * mult_rows(R) + (P.tl_K ? kOuterSlackBytes : 0));
+	L.Wb = carve(sizeof(u64) * 2 * GF2_GMAX * R); L.Uwin = carve(sizeof(u64) * GF2_GMAX * (P.maxr + 64));
+	L.Pfast = carve(sizeof(u64) * GF2_GMAX * GF2_GMAX * 64); L.oprow = carve(sizeof(int) * GF2_OUTER_LISTS * P.nlist);
+	L.Tm = carve(P.tl_K ? P.nlist * sizeof(u64) * GF2_KMAX * GF2_KMAX * GF2_GMAX * 64 * GF2_GMAX : 0);
+	L.Pc = carve(P.kn.pc ? sizeof(u64) * 2 * GF2_GMAX * 64 * (size_t)P.ntiles : 0);
+	L.wmask = carve(sizeof(u64) * 2 * (size_t)((R + 63) / 64 + 1));
+	L.stride = off;
+	return L;
+}
+
+// The side arrays of one system: pointers into its arena, set by bind() alone -- to a solve's fresh arena, to a view's part of its
+// gang's, to the arena of a kept factorization's copy (whose `died` then moves to the handle's own died_buf where it has one).
+struct ArenaPtrs {
+	SolveState *st = nullptr;
+	SyncFlags *sf = nullptr;      // progress counters of the two streams (k_gate)
+	PanelRec *panels = nullptr;
+	PanelAux *aux = nullptr;
+	FindUnit *fu = nullptr;
+	int *died = nullptr;          // per row: panel that made it a pivot source, GF2_NEVER while alive
+	int *pivcol = nullptr, *urow = nullptr, *blk_first = nullptr;
+	u64 *mult = nullptr;          // nsets sets x G x rows: block b writes / reads set b % nsets (2 = ping-pong; an outer panel of the
+	                              // two-level elimination keeps all its K blocks' multipliers until its outer pass: nsets = K)
+	u64 *Wb = nullptr;            // 2 x rows x GMAX window words (the panel steps ping-pong between the halves)
+	u64 *Uwin = nullptr;          // rank x GMAX: pivot rows' words of the following window (k_prio_window -> k_unwind)
+	u64 *Pfast = nullptr;         // scratch of k_block_fast: the pivot rows' window words of a block, [panel][word][column]
+	int *oprow = nullptr;         // k_outer_prow -> k_outer_apply / k_update16k: row lists of the outer panel being applied
+	u64 *Tm = nullptr;            // k_outer_trsm<IDENT> -> k_outer_apply: the panel's pivot rows as combinations of its source rows
+	u64 *Pc = nullptr;            // final pivot rows of the current block, compact: [tile][panel][pivot bit] x 16 B (k_block_trsm -> k_update16); null: kn.pc is off
+	u64 *wmask = nullptr;         // 2 x ceil(rows / 64) words: alive / alive with a non-zero window, per 64 rows
+
+	void bind(const ArenaLayout &L, void *arena, bool pc)
+	{
+		char *base = (char *)arena;
+		st = (SolveState *)(base + L.st); sf = (SyncFlags *)(base + L.sf); panels = (PanelRec *)(base + L.panels); aux = (PanelAux *)(base + L.aux);
+		fu = (FindUnit *)(base + L.fu); died = (int *)(base + L.died); pivcol = (int *)(base + L.pivcol); urow = (int *)(base + L.urow);
+		blk_first = (int *)(base + L.blk_first); mult = (u64 *)(base + L.mult); Wb = (u64 *)(base + L.Wb); Uwin = (u64 *)(base + L.Uwin);
+		Pfast = (u64 *)(base + L.Pfast); oprow = (int *)(base + L.oprow); Tm = (u64 *)(base + L.Tm);
+		Pc = pc ? (u64 *)(base + L.Pc) : nullptr;
+		wmask = (u64 *)(base + L.wmask);
+	}
+};
+
+// The device and pool resources a solve holds (or, a view, borrows), the flags that say whose they are and the caller's own src and
+// rhs_bad: never copied with the plan; Solver::release() alone gives back what is owned and resets the rest.
+struct SolverHandles {
+	hipStream_t sA = nullptr, sB = nullptr;      // panel path / bulk path
+	bool own_sA = false, own_sB = false;
+	u64 *M = nullptr;             // tile-major working copy (owned, unless ext_M)
+	bool ext_M = false;           // the working matrix belongs to the caller (slab solves: a tensor the ranks exchange tiles of)
+	const u64 *src = nullptr;     // caller's row-major matrix on the device (stride words per row)
+	u64 *tmp_src = nullptr;       // row-major staging buffer when the input came from the host
+	u64 *Minv = nullptr;          // inverted diagonal blocks of the back-substitution (k_bs_inv -> k_bs_near2)
+	u64 *rhs_bad = nullptr;       // (the caller's: see nrhs)
+	void *arena = nullptr;        // the side arrays of all nsys systems (ArenaPtrs: those of system 0)
+	hipStream_t sC = nullptr;     // outer passes: panel p's runs BESIDE the inner elimination of panel p + 1 (sA + sB)
+	                              // (late round 5 also split the pass itself over two streams, behind a switch of its own: 131072^2 162 -> 155 ms,
+	                              // 262144^2 -0.8 %, but a fourth stream that cost later batch calls of the process their overlap; removed in
+	                              // round 6, profiles/r05_outer_shapes.txt)
+	hipEvent_t evOuter = nullptr, evPri = nullptr, evPanelDone = nullptr, evBig = nullptr;
+	u64 *Y = nullptr;
+	int *ycols = nullptr;
+	u64 *out = nullptr;
+	hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
+	std::vector<hipEvent_t> evA, evPrio, kev, waitPrio;     // waitPrio[b]: the event that means "bulk of block b complete"
+	hipEvent_t evx = nullptr;
+};
+
+// One solve: its plan, its side arrays and its resources.  Every resource has one owner, so a Solver is not copied: what starts
+// from another one copies the SolverPlan, binds the ArenaPtrs and says what it borrows or acquires (make_view, factor_copy).
+struct Solver : SolverPlan, ArenaPtrs, SolverHandles {
+	SolverPlan &plan() { return *this; }
+	const SolverPlan &plan() const { return *this; }
+	Solver() = default;
+	Solver(const Solver &) = delete;
+	Solver &operator=(const Solver &) = delete;          // (another solve's plan: plan() = other.plan())
 	~Solver() { release(); }
+	// An owner gives everything back once its streams are idle; a view (make_view) what it acquired, and lets go of what it borrowed.
 	void release()
 	{
 		if (!arena && !M && !tmp_src && !Y && !ycols && !out && !sA && !sB && !ev0) return;     // nothing held
 		(void)hipSetDevice(device);
-		if (view) {               // owns only what its own back-substitution allocated
+		Pool &P = pool();
+		if (view) {
 			if (sA && (Y || ycols || out)) (void)hipStreamSynchronize(sA);
-			Pool &P = pool();
 			if (own_bs) for (void *p : { (void *)Y, (void *)ycols, (void *)out, (void *)Minv }) P.release(p);
 			P.release_event(ev2, true);
-			P.release_event(evx, true); evx = nullptr;
-			Y = nullptr; ycols = nullptr; out = nullptr; Minv = nullptr; ev2 = nullptr;
-			arena = nullptr; M = nullptr; tmp_src = nullptr; sA = sB = nullptr;
-			ev0 = ev1 = ev3 = nullptr;
-			kev.clear(); evA.clear(); evPrio.clear();
-			return;
+			P.release_event(evx, true);
+			arena = nullptr; M = nullptr; sA = sB = nullptr; ev0 = ev1 = ev3 = nullptr;          // (borrowed)
+		} else {
+			// nothing goes back to the pool while work may still be in flight (error paths return early)
+			if (sC) (void)hipStreamSynchronize(sC);
+			if (sB) (void)hipStreamSynchronize(sB);
+			if (arena || M) (void)hipStreamSynchronize(sA);
+			for (void *p : { arena, (void *)Y, (void *)ycols, (void *)out, (void *)Minv, (void *)(ext_M ? nullptr : M), (void *)tmp_src }) P.release(p);
+			for (hipEvent_t e : { ev0, ev1, ev2, ev3, evx }) P.release_event(e, true);
+			for (hipEvent_t e : { evOuter, evPri, evPanelDone, evBig }) P.release_event(e, false);
+			if (sC) P.release_stream(sC, device, nsys > 1 ? 3 : 1);
+			for (hipEvent_t e : kev) P.release_event(e, true);
+			for (hipEvent_t e : evA) P.release_event(e, false);
+			for (hipEvent_t e : evPrio) P.release_event(e, false);
+			if (own_sB && sB) P.release_stream(sB, device, nsys > 1 ? 3 : 1);
+			if (own_sA && sA) P.release_stream(sA, device, false);
 		}
-		// nothing goes back to the pool while work may still be in flight (error paths return early)
-		if (sC) (void)hipStreamSynchronize(sC);
-		if (sB) (void)hipStreamSynchronize(sB);
-		if (arena || M) (void)hipStreamSynchronize(sA);
-		Pool &P = pool();
-		for (void *p : { arena, (void *)Y, (void *)ycols, (void *)out, (void *)Minv, (void *)(ext_M ? nullptr : M), (void *)tmp_src }) P.release(p);
-		arena = nullptr; Y = nullptr; ycols = nullptr; out = nullptr; Minv = nullptr; M = nullptr; tmp_src = nullptr;
-		st = nullptr; panels = nullptr; aux = nullptr; fu = nullptr; died = nullptr; pivcol = nullptr;
-		urow = nullptr; blk_first = nullptr; mult = nullptr; Wb = nullptr;
-		for (hipEvent_t *e : { &ev0, &ev1, &ev2, &ev3, &evx }) { P.release_event(*e, true); *e = nullptr; }
-		for (hipEvent_t *e : { &evOuter, &evPri, &evPanelDone, &evBig }) { P.release_event(*e, false); *e = nullptr; }
-		if (sC) P.release_stream(sC, device, nsys > 1 ? 3 : 1);
-		sC = nullptr;
-		for (hipEvent_t e : kev) P.release_event(e, true);
-		for (hipEvent_t e : evA) P.release_event(e, false);
-		for (hipEvent_t e : evPrio) P.release_event(e, false);
-		kev.clear(); evA.clear(); evPrio.clear();
-		if (own_sB && sB) P.release_stream(sB, device, nsys > 1 ? 3 : 1);
-		sB = nullptr;
-		if (own_sA && sA) P.release_stream(sA, device, false);
-		sA = nullptr;
+		static_cast<ArenaPtrs &>(*this) = ArenaPtrs();
+		static_cast<SolverHandles &>(*this) = SolverHandles();
 	}
 };
 
@@ -867,34 +930,16 @@ int solver_alloc(Solver &S)
 	}
 	// one arena for all side arrays (a dozen hipMalloc/hipFree pairs cost more than a small solve)
 	{
-		const i64 R = std::max<i64>(1, S.rows), NP = std::max(1, S.npanels);
-		size_t off = 0;
-		auto carve = [&](size_t bytes) { size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
-		const size_t o_st = carve(sizeof(SolveState)), o_sf = carve(sizeof(SyncFlags)), o_pan = carve(sizeof(PanelRec) * NP), o_aux = carve(sizeof(PanelAux) * NP),
-		             o_fu = carve(sizeof(FindUnit) * (S.units + 1 + GF2_MAXGROUPS)), o_alive = carve(sizeof(int) * (size_t)R),
-		             o_piv = carve(sizeof(int) * (S.maxr + 64)), o_urow = carve(sizeof(int) * (S.maxr + 64)),
-		             o_blk = carve(sizeof(int) * std::max(1, S.nblocks)), o_mult = carve(sizeof(u64) * S.nsets * G * mult_rows(R) + (S.tl_K ? kOuterSlackBytes : 0)),
-		             o_wb = carve(sizeof(u64) * 2 * GF2_GMAX * R), o_uw = carve(sizeof(u64) * GF2_GMAX * (S.maxr + 64)),
-		             o_pf = carve(sizeof(u64) * GF2_GMAX * GF2_GMAX * 64), o_opr = carve(sizeof(int) * GF2_OUTER_LISTS * S.nlist),
-		             o_tm = carve(S.tl_K ? S.nlist * sizeof(u64) * GF2_KMAX * GF2_KMAX * GF2_GMAX * 64 * GF2_GMAX : 0),
-		             o_pc = carve(kn.pc ? sizeof(u64) * 2 * GF2_GMAX * 64 * (size_t)S.ntiles : 0),
-		             o_wm = carve(sizeof(u64) * 2 * (size_t)((R + 63) / 64 + 1));
-		S.arena_stride = off;
+		const ArenaLayout &L = S.lay = arena_layout(S);
 		S.sync_base = 0;
-		HIPCHK(pool().alloc(&S.arena, off * S.nsys, S.device));
-		char *base = (char *)S.arena;
-		S.st = (SolveState *)(base + o_st); S.sf = (SyncFlags *)(base + o_sf); S.panels = (PanelRec *)(base + o_pan); S.aux = (PanelAux *)(base + o_aux);
-		S.fu = (FindUnit *)(base + o_fu); S.died = (int *)(base + o_alive); S.pivcol = (int *)(base + o_piv);
-		S.urow = (int *)(base + o_urow); S.blk_first = (int *)(base + o_blk); S.mult = (u64 *)(base + o_mult);
-		S.Wb = (u64 *)(base + o_wb); S.Uwin = (u64 *)(base + o_uw); S.Pfast = (u64 *)(base + o_pf); S.oprow = (int *)(base + o_opr); S.Tm = (u64 *)(base + o_tm);
-		S.Pc = kn.pc ? (u64 *)(base + o_pc) : nullptr;
-		S.wmask = (u64 *)(base + o_wm);
+		HIPCHK(pool().alloc(&S.arena, L.stride * S.nsys, S.device));
+		S.bind(L, S.arena, kn.pc);
 		// zero everything that is read before it is written: state, panel records, unit scratch, block bounds, multipliers
 		for (int s = 0; s < S.nsys; s++) {
-			char *b = base + (size_t)s * off;
-			HIPCHK(hipMemsetAsync(b + o_st, 0, o_alive - o_st, S.sA));
-			HIPCHK(hipMemsetAsync(b + o_alive, GF2_NEVER & 0xff, sizeof(int) * (size_t)R, S.sA));
-			HIPCHK(hipMemsetAsync(b + o_blk, 0, o_wb - o_blk, S.sA));
+			char *b = (char *)S.arena + (size_t)s * L.stride;
+			HIPCHK(hipMemsetAsync(b + L.st, 0, L.died - L.st, S.sA));
+			HIPCHK(hipMemsetAsync(b + L.died, GF2_NEVER & 0xff, sizeof(int) * (size_t)std::max<i64>(1, S.rows), S.sA));
+			HIPCHK(hipMemsetAsync(b + L.blk_first, 0, L.Wb - L.blk_first, S.sA));
 		}
 	}
 	HIPCHK(pool().event(&S.ev0, true));
@@ -1829,24 +1874,21 @@ int solver_finish(Solver &S, gf2bv_result **out)
 	return finish_end(S, out);
 }
 
-// A non-owning window on system s of a gang: same streams and events, pointers moved to that
-// system's matrix and arena.  Back-substitution and export then run per system, unchanged.
+// A non-owning window on system s of a gang: the gang's plan for one system, that system's matrix and side arrays.
+// Back-substitution and export then run per system, unchanged.  Borrowed: the streams sA and sB and the timing events ev0, ev1,
+// ev3.  Its own: ev2, evx and whatever its back-substitution allocates (unless own_bs is cleared: enqueue_backward_gang).
 int make_view(const Solver &S, int s, Solver &V)
 {
-	V = S;
+	V.plan() = S.plan();
 	V.view = true;
 	V.gang_nsys = S.nsys;
-	V.nsys = 1; V.m_stride = 0; V.arena_stride = 0; V.src_sys_words = 0;
-	V.own_sA = V.own_sB = false;
-	V.src = nullptr; V.tmp_src = nullptr;
-	V.kev.clear(); V.evA.clear(); V.evPrio.clear();
-	const i64 ao = (i64)S.arena_stride * s;
-	auto mv = [ao](auto *&p) { p = reinterpret_cast<decltype(+p)>(reinterpret_cast<char *>(p) + ao); };
+	V.nsys = 1; V.m_stride = 0; V.src_sys_words = 0;
 	V.M = S.M + S.m_stride * s;
-	V.arena = (char *)S.arena + ao;
-	mv(V.st); mv(V.panels); mv(V.aux); mv(V.fu); mv(V.died); mv(V.pivcol); mv(V.urow); mv(V.blk_first); mv(V.mult); mv(V.Wb); mv(V.Uwin); mv(V.Pfast); if (V.Pc) mv(V.Pc);
-	V.Y = nullptr; V.ycols = nullptr; V.out = nullptr; V.Minv = nullptr;
-	V.ev2 = nullptr;
+	V.arena = (char *)S.arena + S.lay.stride * s;
+	V.bind(S.lay, V.arena, S.kn.pc);
+	V.lay.stride = 0;
+	V.sA = S.sA; V.sB = S.sB;
+	V.ev0 = S.ev0; V.ev1 = S.ev1; V.ev3 = S.ev3;
 	HIPCHK(pool().event(&V.ev2, true));
 	return GF2BV_OK;
 }
@@ -2266,14 +2308,12 @@ int check_rhs_args(i64 rows, i64 cols, const void *rhs, bool on_device, i64 nrhs
 	return GF2BV_OK;
 }
 
-// The coefficients into the tile-major working matrix S.M (ntiles tiles, srows rows per slab) on S.sA: the digits packed straight into
+// The coefficients into the tile-major working matrix (ntiles tiles, srows rows per slab) on stream `st`: the digits packed straight into
 // tiles (k_pack_digits puts the affine term at column `cols`; the callers overwrite it), or the words that hold coefficients -- and
 // only those -- copied into tiles (the words right of them are zero-filled)
-// (M: where row 0 goes, S.M when null -- an append packs its rows below the kept ones by passing S.M + row0 x TW)
-int pack_coefficients(const MatrixInput &in, i64 rows, i64 cols, i64 ntiles, i64 srows, Solver &S, Scratch &scratch, u64 *M = nullptr)
+// (M: where row 0 goes -- an append packs its rows below the kept ones by passing S.M + row0 x TW)
+int pack_coefficients(const MatrixInput &in, i64 rows, i64 cols, i64 ntiles, i64 srows, int device, hipStream_t st, Scratch &scratch, u64 *M)
 {
-	const int device = S.device;
-	if (!M) M = S.M;
 	const i64 cw = (cols + 63) / 64, rw = (rows + 63) / 64;
 	if (in.h_off) {
 		const i64 ndig = in.h_off[rows];
@@ -2281,9 +2321,9 @@ int pack_coefficients(const MatrixInput &in, i64 rows, i64 cols, i64 ntiles, i64
 		i64 *d_off = nullptr;
 		HIPCHK(scratch.alloc((void **)&d_dig, sizeof(uint32_t) * std::max<i64>(1, ndig), device));
 		HIPCHK(scratch.alloc((void **)&d_off, sizeof(i64) * (rows + 1), device));
-		if (ndig) HIPCHK(hipMemcpyAsync(d_dig, in.h_digits, sizeof(uint32_t) * ndig, hipMemcpyHostToDevice, S.sA));
-		HIPCHK(hipMemcpyAsync(d_off, in.h_off, sizeof(i64) * (rows + 1), hipMemcpyHostToDevice, S.sA));
-		k_pack_digits<<<dim3((unsigned)((ntiles * TW + 255) / 256), (unsigned)std::min<i64>(rows, 65535)), dim3(256), 0, S.sA>>>(
+		if (ndig) HIPCHK(hipMemcpyAsync(d_dig, in.h_digits, sizeof(uint32_t) * ndig, hipMemcpyHostToDevice, st));
+		HIPCHK(hipMemcpyAsync(d_off, in.h_off, sizeof(i64) * (rows + 1), hipMemcpyHostToDevice, st));
+		k_pack_digits<<<dim3((unsigned)((ntiles * TW + 255) / 256), (unsigned)std::min<i64>(rows, 65535)), dim3(256), 0, st>>>(
 			d_dig, d_off, in.bpd, rows, cols, ntiles * TW, srows, M, SysStride{0, 0}, (i64)0);
 	} else {
 		const u64 *src = in.d_words;
@@ -2292,10 +2332,10 @@ int pack_coefficients(const MatrixInput &in, i64 rows, i64 cols, i64 ntiles, i64
 			sstride = round_up(cw, 2);
 			u64 *tmp = nullptr;
 			HIPCHK(scratch.alloc((void **)&tmp, sizeof(u64) * rows * sstride, device));
-			HIPCHK(hipMemcpy2DAsync(tmp, sstride * 8, in.h_words, in.stride * 8, cw * 8, rows, hipMemcpyHostToDevice, S.sA));
+			HIPCHK(hipMemcpy2DAsync(tmp, sstride * 8, in.h_words, in.stride * 8, cw * 8, rows, hipMemcpyHostToDevice, st));
 			src = tmp;
 		}
-		k_to_tiled<<<dim3((unsigned)rw, (unsigned)((ntiles + 15) / 16)), dim3(256), 0, S.sA>>>(src, sstride, rows, ntiles, cw, srows, M,
+		k_to_tiled<<<dim3((unsigned)rw, (unsigned)((ntiles + 15) / 16)), dim3(256), 0, st>>>(src, sstride, rows, ntiles, cw, srows, M,
 		                                                                                      (i64)0, SysStride{0, 0});
 	}
 	HIPCHK(hipGetLastError());
@@ -2316,14 +2356,8 @@ int solve_rhs(const MatrixInput &in, const u64 *rhs, bool rhs_on_device, i64 nrh
 	S.rows = rows; S.cols = cols; S.mode = mode; S.nrhs = (int)nrhs;
 	S.time_kernels = time_kernels;
 	S.stride = in.h_off ? ntiles * TW : in.stride;
-	{
-		const hipError_t e = pool().alloc((void **)&S.M, sizeof(u64) * ntiles * TW * srows + kOuterSlackBytes, device);
-		if (e == hipErrorOutOfMemory) {
-			(void)hipGetLastError();
-			return fail(GF2BV_ERR_NOMEM, "the matrix widened by the right-hand sides does not fit on the device");
-		}
-		if (e != hipSuccess) return fail(GF2BV_ERR_HIP, "working matrix", e);
-	}
+	if (int rc = alloc_or_nomem((void **)&S.M, sizeof(u64) * ntiles * TW * srows + kOuterSlackBytes, device,
+	                            "the matrix widened by the right-hand sides does not fit on the device", "working matrix")) return rc;
 	Scratch scratch;                  // (declared after S: released first, after synchronising the solve's stream)
 	scratch.sync_first = S.sA;
 	HIPCHK(scratch.alloc((void **)&S.rhs_bad, sizeof(u64) * nmw, device));
@@ -2332,7 +2366,7 @@ int solve_rhs(const MatrixInput &in, const u64 *rhs, bool rhs_on_device, i64 nrh
 	HIPCHK(hipEventRecord(p0, S.sA));
 	HIPCHK(hipMemsetAsync(S.rhs_bad, 0, sizeof(u64) * nmw, S.sA));
 	int rc;
-	if ((rc = pack_coefficients(in, rows, cols, ntiles, srows, S, scratch))) return rc;
+	if ((rc = pack_coefficients(in, rows, cols, ntiles, srows, S.device, S.sA, scratch, S.M))) return rc;
 	const u64 *d_rhs = rhs;
 	i64 rhs_stride = rhs_words;
 	if (!rhs_on_device) {             // (only the words that hold rows go up)
@@ -2434,9 +2468,34 @@ void release_backsub(Solver &S)
 	S.Y = nullptr; S.ycols = nullptr; S.out = nullptr; S.Minv = nullptr;
 }
 
+// The kernel basis of a kept factorization (mode 1) from its pivots: the free columns in M4RI's order, one back-substitution over
+// them.  The caller gives back what the back-substitution took (release_backsub).
+int factor_basis(gf2bv_factor *h, std::vector<u64> &basis)
+{
+	Solver &S = h->S;
+	basis.clear();
+	int rc = load_free_order(S);
+	if (rc) return rc;
+	const i64 dim = h->cols - h->rank;
+	if (!dim) return GF2BV_OK;
+	if ((rc = enqueue_backsub(S, S.free_order))) return rc;
+	std::vector<u64> hout((size_t)(dim * std::max<i64>(1, h->cw)));
+	HIPCHK(hipMemcpyAsync(hout.data(), S.out, sizeof(u64) * hout.size(), hipMemcpyDeviceToHost, S.sA));
+	HIPCHK(hipStreamSynchronize(S.sA));
+	basis = basis_rows(hout.data(), h->cw, S.free_order, dim);
+	return GF2BV_OK;
+}
+
+// device memory a kept factorization holds: the working matrix, the arena and, once the rows have outgrown the arena's, its own row records
+i64 factor_device_bytes(const gf2bv_factor *h)
+{
+	const Solver &S = h->S;
+	return (i64)(sizeof(u64) * S.ntiles * TW * S.srows + kOuterSlackBytes + S.lay.stride) + (h->died_buf ? (i64)sizeof(int) * h->cap_rows : 0);
+}
+
 int factor_matrix(const MatrixInput &in, i64 rows, i64 cols, int mode, int device, hipStream_t stream, gf2bv_factor **out)
 {
-	const i64 rw = (rows + 63) / 64, cw = (cols + 63) / 64, cwx = std::max<i64>(1, cw);
+	const i64 rw = (rows + 63) / 64, cw = (cols + 63) / 64;
 	const i64 tw0 = round_up(cols + kFactorSlots, 128) / 64;          // (the identity starts on a whole 16-byte tile)
 	const i64 wt = tw0 + rw, ntiles = tiles_for(wt), srows = slab_rows(rows);
 	std::unique_ptr<gf2bv_factor> h(new gf2bv_factor());
@@ -2459,17 +2518,11 @@ int factor_matrix(const MatrixInput &in, i64 rows, i64 cols, int mode, int devic
 		HIPCHK(hipStreamWaitEvent(S.sA, e, 0));
 		pool().release_event(e, false);
 	}
-	{
-		const hipError_t e = pool().alloc((void **)&S.M, sizeof(u64) * ntiles * TW * srows + kOuterSlackBytes, device);
-		if (e == hipErrorOutOfMemory) {
-			(void)hipGetLastError();
-			return fail(GF2BV_ERR_NOMEM, "the factorization (the matrix and its row transform, about twice the matrix) does not fit on the device");
-		}
-		if (e != hipSuccess) return fail(GF2BV_ERR_HIP, "working matrix", e);
-	}
+	if (int rc = alloc_or_nomem((void **)&S.M, sizeof(u64) * ntiles * TW * srows + kOuterSlackBytes, device,
+	                            "the factorization (the matrix and its row transform, about twice the matrix) does not fit on the device", "working matrix")) return rc;
 	Scratch scratch;
 	scratch.sync_first = S.sA;
-	int rc = pack_coefficients(in, rows, cols, ntiles, srows, S, scratch);
+	int rc = pack_coefficients(in, rows, cols, ntiles, srows, S.device, S.sA, scratch, S.M);
 	if (rc) return rc;
 	k_factor_init<<<dim3((unsigned)((rows + 255) / 256), (unsigned)std::min<i64>(wt - (cols >> 6), 64)), dim3(256), 0, S.sA>>>(
 		rows, cols, srows, tw0, rw, S.M);
@@ -2491,17 +2544,7 @@ int factor_matrix(const MatrixInput &in, i64 rows, i64 cols, int mode, int devic
 	if (h->rank) HIPCHK(hipMemcpy(h->urow.data(), S.urow, sizeof(int) * h->rank, hipMemcpyDeviceToHost));
 	h->hp.assign(S.hp.begin(), S.hp.begin() + S.npanels);
 	h->cap_rows = rows;
-	if (mode == GF2BV_MODE_AFFINE_SPACE) {
-		if ((rc = load_free_order(S))) return rc;
-		const i64 dim = cols - h->rank;
-		if (dim) {
-			if ((rc = enqueue_backsub(S, S.free_order))) return rc;
-			std::vector<u64> hout((size_t)(dim * cwx));
-			HIPCHK(hipMemcpyAsync(hout.data(), S.out, sizeof(u64) * hout.size(), hipMemcpyDeviceToHost, S.sA));
-			HIPCHK(hipStreamSynchronize(S.sA));
-			h->basis = basis_rows(hout.data(), cw, S.free_order, dim);
-		}
-	}
+	if (mode == GF2BV_MODE_AFFINE_SPACE && (rc = factor_basis(h.get(), h->basis))) return rc;
 	{
 		gf2bv_result R;
 		R.rank = h->rank; R.dim = cols - h->rank;
@@ -2510,7 +2553,7 @@ int factor_matrix(const MatrixInput &in, i64 rows, i64 cols, int mode, int devic
 		h->fst = R.stats;
 	}
 	release_backsub(S);
-	h->device_bytes = (i64)(sizeof(u64) * ntiles * TW * srows + kOuterSlackBytes + S.arena_stride);
+	h->device_bytes = factor_device_bytes(h.get());
 	*out = h.release();
 	return GF2BV_OK;
 }
@@ -2785,18 +2828,9 @@ int factor_append(gf2bv_factor *h, const MatrixInput &in, i64 k, hipStream_t str
 	int *died2 = S.died;
 	if (grow) {
 		M2 = nullptr; died2 = nullptr;
-		const hipError_t e = pool().alloc((void **)&M2, sizeof(u64) * ntiles2 * TW * srows2 + kOuterSlackBytes, h->device);
-		if (e == hipErrorOutOfMemory) {
-			(void)hipGetLastError();
-			return fail(GF2BV_ERR_NOMEM, "the grown factorization does not fit on the device");
-		}
-		if (e != hipSuccess) return fail(GF2BV_ERR_HIP, "grown working matrix", e);
-		const hipError_t e2 = pool().alloc((void **)&died2, sizeof(int) * cap, h->device);
-		if (e2 != hipSuccess) {
-			pool().release(M2);
-			if (e2 == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(GF2BV_ERR_NOMEM, "the grown factorization does not fit on the device"); }
-			return fail(GF2BV_ERR_HIP, "grown row records", e2);
-		}
+		const char *nomem = "the grown factorization does not fit on the device";
+		if (int rc = alloc_or_nomem((void **)&M2, sizeof(u64) * ntiles2 * TW * srows2 + kOuterSlackBytes, h->device, nomem, "grown working matrix")) return rc;
+		if (int rc = alloc_or_nomem((void **)&died2, sizeof(int) * cap, h->device, nomem, "grown row records")) { pool().release(M2); return rc; }
 	}
 	// (on an error past this point the grown buffers go back to the pool; the kept state is only replaced at the end)
 	struct Grown {
@@ -2830,13 +2864,7 @@ int factor_append(gf2bv_factor *h, const MatrixInput &in, i64 k, hipStream_t str
 		HIPCHK(hipGetLastError());
 	}
 	HIPCHK(hipMemsetAsync(died2 + rows, GF2_NEVER & 0xff, sizeof(int) * k, S.sA));
-	{
-		Solver P;                         // (pack_coefficients' stream and device)
-		P.device = h->device; P.sA = S.sA;
-		int rc = pack_coefficients(in, k, cols, ntiles2, srows2, P, scratch, M2 + rows * TW);
-		P.sA = nullptr;
-		if (rc) return rc;
-	}
+	if (int rc = pack_coefficients(in, k, cols, ntiles2, srows2, h->device, S.sA, scratch, M2 + rows * TW)) return rc;
 	k_append_init<<<dim3((unsigned)((k + 255) / 256), (unsigned)std::min<i64>(h->tw0 + rw2 - (cols >> 6), 64)), dim3(256), 0, S.sA>>>(
 		rows, k, cols, srows2, h->tw0, h->tw0 + rw2, M2);
 	HIPCHK(hipGetLastError());
@@ -2862,24 +2890,15 @@ int factor_append(gf2bv_factor *h, const MatrixInput &in, i64 k, hipStream_t str
 		std::vector<u64> basis;
 		if (h->mode == GF2BV_MODE_AFFINE_SPACE) {
 			const auto tb = std::chrono::steady_clock::now();
-			int rc = load_free_order(S);
-			if (rc) return rc;
-			const i64 dim = cols - h->rank;
-			if (dim) {
-				if ((rc = enqueue_backsub(S, S.free_order))) return rc;
-				std::vector<u64> hout((size_t)(dim * std::max<i64>(1, h->cw)));
-				HIPCHK(hipMemcpyAsync(hout.data(), S.out, sizeof(u64) * hout.size(), hipMemcpyDeviceToHost, S.sA));
-				HIPCHK(hipStreamSynchronize(S.sA));
-				basis = basis_rows(hout.data(), h->cw, S.free_order, dim);
-				release_backsub(S);
-			}
+			if (int rc = factor_basis(h, basis)) return rc;
+			if (cols - h->rank) release_backsub(S);      // (a back-substitution ran)
 			ms[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb).count();
 		}
 		h->basis = std::move(basis);
 		h->rows = rows2; h->rw = rw2;
 		S.rows = rows2; S.wt = h->tw0 + rw2; S.nrhs = (int)(S.wt * 64 - cols);
 		h->fst.rows = rows2; h->fst.stride_words = S.wt; h->fst.rank = h->rank; h->fst.dimension = cols - h->rank;
-		h->device_bytes = (i64)(sizeof(u64) * S.ntiles * TW * S.srows + kOuterSlackBytes + S.arena_stride) + (i64)sizeof(int) * h->cap_rows;
+		h->device_bytes = factor_device_bytes(h);
 		return GF2BV_OK;
 	};
 	if (int rc = rest()) {
@@ -2893,7 +2912,8 @@ int factor_append(gf2bv_factor *h, const MatrixInput &in, i64 k, hipStream_t str
 	return GF2BV_OK;
 }
 
-// An independent handle: the kept state copied device to device, the host fields as they are
+// An independent handle: the host fields and the solver's plan as they are, the kept state copied device to device into resources of
+// the copy's own: a stream, four timing events, the matrix, an arena and, where the original has one, a died_buf.  Nothing is borrowed.
 int factor_copy(gf2bv_factor *h, gf2bv_factor **out)
 {
 	std::lock_guard<std::mutex> lk(h->mu);
@@ -2905,45 +2925,22 @@ int factor_copy(gf2bv_factor *h, gf2bv_factor **out)
 	c->piv = h->piv; c->basis = h->basis; c->fst = h->fst; c->device_bytes = h->device_bytes;
 	c->cap_rows = h->cap_rows; c->hp = h->hp; c->urow = h->urow;
 	Solver &D = c->S;
-	D = S;                            // the scalars and host vectors; every resource below is the copy's own
-	D.M = nullptr; D.tmp_src = nullptr; D.Minv = nullptr; D.arena = nullptr; D.Y = nullptr; D.ycols = nullptr;
-	D.out = nullptr; D.rhs_bad = nullptr; D.src = nullptr;
-	D.sA = D.sB = D.sC = nullptr; D.own_sA = D.own_sB = false;
-	D.ev0 = D.ev1 = D.ev2 = D.ev3 = D.evx = nullptr;
-	D.evOuter = D.evPri = D.evPanelDone = D.evBig = nullptr;
-	D.kev.clear(); D.evA.clear(); D.evPrio.clear(); D.waitPrio.clear();
-	D.st = nullptr; D.sf = nullptr; D.panels = nullptr; D.aux = nullptr; D.fu = nullptr; D.died = nullptr; D.pivcol = nullptr;
-	D.urow = nullptr; D.blk_first = nullptr; D.mult = nullptr; D.Wb = nullptr; D.Uwin = nullptr; D.Pfast = nullptr; D.oprow = nullptr;
-	D.Tm = nullptr; D.Pc = nullptr; D.wmask = nullptr; D.sf = nullptr;
+	D.plan() = S.plan();
 	HIPCHK(pool().stream(&D.sA, h->device, false));
 	D.own_sA = true;
 	for (hipEvent_t *e : { &D.ev0, &D.ev1, &D.ev2, &D.ev3 }) HIPCHK(pool().event(e, true));
-	const size_t mbytes = sizeof(u64) * S.ntiles * TW * S.srows + kOuterSlackBytes;
-	{
-		const hipError_t e = pool().alloc((void **)&D.M, mbytes, h->device);
-		if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(GF2BV_ERR_NOMEM, "the copy of the factorization does not fit on the device"); }
-		if (e != hipSuccess) return fail(GF2BV_ERR_HIP, "working matrix", e);
-		const hipError_t e2 = pool().alloc(&D.arena, S.arena_stride, h->device);
-		if (e2 == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(GF2BV_ERR_NOMEM, "the copy of the factorization does not fit on the device"); }
-		if (e2 != hipSuccess) return fail(GF2BV_ERR_HIP, "arena", e2);
-		if (h->died_buf) {
-			const hipError_t e3 = pool().alloc((void **)&c->died_buf, sizeof(int) * h->cap_rows, h->device);
-			if (e3 == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(GF2BV_ERR_NOMEM, "the copy of the factorization does not fit on the device"); }
-			if (e3 != hipSuccess) return fail(GF2BV_ERR_HIP, "row records", e3);
-		}
-	}
+	const char *nomem = "the copy of the factorization does not fit on the device";
+	int rc = alloc_or_nomem((void **)&D.M, sizeof(u64) * S.ntiles * TW * S.srows + kOuterSlackBytes, h->device, nomem, "working matrix");
+	if (!rc) rc = alloc_or_nomem(&D.arena, S.lay.stride, h->device, nomem, "arena");
+	if (!rc && h->died_buf) rc = alloc_or_nomem((void **)&c->died_buf, sizeof(int) * h->cap_rows, h->device, nomem, "row records");
+	if (rc) return rc;
+	D.bind(D.lay, D.arena, D.kn.pc);
+	if (c->died_buf) D.died = c->died_buf;
 	// the copy starts after what the original's stream has queued
 	HIPCHK(hipStreamSynchronize(S.sA));
 	HIPCHK(hipMemcpyAsync(D.M, S.M, sizeof(u64) * S.ntiles * TW * S.srows, hipMemcpyDeviceToDevice, D.sA));
-	HIPCHK(hipMemcpyAsync(D.arena, S.arena, S.arena_stride, hipMemcpyDeviceToDevice, D.sA));
+	HIPCHK(hipMemcpyAsync(D.arena, S.arena, S.lay.stride, hipMemcpyDeviceToDevice, D.sA));
 	if (h->died_buf) HIPCHK(hipMemcpyAsync(c->died_buf, h->died_buf, sizeof(int) * h->cap_rows, hipMemcpyDeviceToDevice, D.sA));
-	char *ob = (char *)S.arena, *nb = (char *)D.arena;
-	auto rebase = [&](auto *p) { return p ? (decltype(p))(nb + ((const char *)p - ob)) : p; };
-	D.st = rebase(S.st); D.sf = rebase(S.sf); D.panels = rebase(S.panels); D.aux = rebase(S.aux); D.fu = rebase(S.fu);
-	D.pivcol = rebase(S.pivcol); D.urow = rebase(S.urow); D.blk_first = rebase(S.blk_first); D.mult = rebase(S.mult);
-	D.Wb = rebase(S.Wb); D.Uwin = rebase(S.Uwin); D.Pfast = rebase(S.Pfast); D.oprow = rebase(S.oprow); D.Tm = rebase(S.Tm);
-	D.Pc = rebase(S.Pc); D.wmask = rebase(S.wmask);
-	D.died = h->died_buf ? c->died_buf : rebase(S.died);
 	HIPCHK(hipStreamSynchronize(D.sA));
 	*out = c.release();
 	return GF2BV_OK;
@@ -3180,7 +3177,7 @@ int gf2bv_solve_digits(const uint32_t *digits, const int64_t *digit_off, int bit
 	hipEvent_t p0, p1;
 	HIPCHK(scratch.event(&p0)); HIPCHK(scratch.event(&p1));
 	HIPCHK(hipEventRecord(p0, S.sA));
-	if ((rc = pack_coefficients(in, rows, cols, ntiles, srows, S, scratch))) return rc;
+	if ((rc = pack_coefficients(in, rows, cols, ntiles, srows, S.device, S.sA, scratch, S.M))) return rc;
 	HIPCHK(hipEventRecord(p1, S.sA));
 	rc = solver_enqueue(S);
 	if (rc == GF2BV_OK) {
@@ -3471,7 +3468,7 @@ int gf2bv_slab_open(void *d_aug, int64_t rows, int64_t cols, int64_t stride_word
 	const i64 R = std::max<i64>(1, S.rows);
 	const int G = S.impl->G;
 	size_t off = 0;
-	auto carve = [&](size_t bytes) { size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
+	auto carve = [&](size_t bytes) { size_t at = off; off += round256(bytes); return at; };
 	(void)carve(sizeof(SolveState)); h->o_blk = carve(sizeof(int)); h->o_pan = carve(sizeof(PanelRec) * G);
 	h->o_aux = carve(sizeof(PanelAux) * G); h->o_mult = carve(sizeof(u64) * G * mult_rows(R));
 	h->payload_bytes = off;

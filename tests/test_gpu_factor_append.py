@@ -289,6 +289,35 @@ def test_copy_is_independent():
             c.close()
 
 
+@pytest.mark.parametrize("two_level", [None, "2"])
+@pytest.mark.parametrize("mode", [0, 1])
+def test_copy_outlives_its_original(mode, two_level, monkeypatch):
+    """A copy owns everything it works on: the original (grown by an append: it has row records of its own) is closed first and a
+    second factorization of the same shape takes its buffers from the pool and overwrites them; the copy still answers, and still
+    appends.  GF2BV_TWO_LEVEL=2: the first two of the four blocks form an outer panel (T matrices, row lists, 2K multiplier sets)."""
+    if two_level:
+        monkeypatch.setenv("GF2BV_TWO_LEVEL", two_level)
+    rng = random.Random(77 + mode)
+    rows, cols = 1050, 1000
+    aug = _base(rng, rows, cols, 800, [2, 900])
+    other = _base(rng, rows, cols, 900, [7])
+    b1 = _batch(rng, "rand", 120, aug, cols, aug.shape[1])
+    b2 = _batch(rng, "sparse", 500, aug, cols, aug.shape[1])
+    f = hip.factor_words(aug, rows, cols, mode)
+    f.append_words(b1)
+    c = f.copy()
+    f.close()
+    g = hip.factor_words(other, rows, cols, mode)
+    try:
+        _check_stacked(c, np.vstack([aug, b1]), cols, mode, rng)
+        c.append_words(b2)
+        _check_stacked(c, np.vstack([aug, b1, b2]), cols, mode, rng)
+        _check_stacked(g, other, cols, mode, rng)
+    finally:
+        c.close()
+        g.close()
+
+
 @pytest.mark.parametrize("bs", [32, 1])
 def test_mt19937_outputs_arrive(bs):
     """Too few outputs factored, the rest appended in batches (FactoredSystem.add); the known answer of examples/mt.py."""
