@@ -1046,6 +1046,70 @@ PyObject *py_m4ri_solve_quad_packed(PyObject *, PyObject *const *args, Py_ssize_
 	return result_to_py(res, mode, device);
 }
 
+// ---- degree-3 XL: quadratic equations multiplied by 1 and by every unknown on the device (gf2bv_hip.h, "degree-3 XL") --------------
+// m4ri_solve_xl3(equations, n_lin, mode[, device]) -> None | int | AffineSpace over n_lin + C(n_lin,2) + C(n_lin,3) columns.
+// New entry (no counterpart in the reference): `equations` are QuadraticSystem's equation ints (bit 0 the constant, bit 1 + c column
+// c of the n_lin + C(n_lin,2) linearised unknowns; higher bits and the sign ignored).  They are written as augmented words on the
+// host -- one pass over the digits, no PyLong is made -- and gf2bv_solve_xl3_words multiplies, pads and solves them on the device.
+PyObject *py_m4ri_solve_xl3(PyObject *, PyObject *const *args, Py_ssize_t nargs)
+{
+	int device;
+	if (!entry_device("m4ri_solve_xl3", 3, args, nargs, &device)) return nullptr;
+	PyObject *list = args[0];
+	if (!PyList_Check(list)) { PyErr_SetString(PyExc_TypeError, "The first argument equations must be a list"); return nullptr; }
+	const Py_ssize_t n = PyLong_AsSsize_t(args[1]);
+	if (n == -1 && PyErr_Occurred()) return nullptr;
+	if (n < 1 || n > 65535) { PyErr_SetString(PyExc_ValueError, "n_lin must be 1..65535"); return nullptr; }
+	long mode;
+	if (!parse_mode(args[2], &mode)) return nullptr;
+	const int64_t m = PyList_GET_SIZE(list), cols2 = n + n * (n - 1) / 2, w2 = (cols2 + 1 + 63) / 64;
+	std::vector<uint64_t> quad;
+	try { quad.assign((size_t)(m * w2), 0); } catch (const std::bad_alloc &) { PyErr_NoMemory(); return nullptr; }
+	for (int64_t r = 0; r < m; r++) {
+		PyObject *item = PyList_GET_ITEM(list, r);
+		if (!PyLong_Check(item)) { PyErr_SetString(PyExc_TypeError, "List items must be integers"); return nullptr; }
+		PyLongObject *v = (PyLongObject *)item;
+		uint64_t *w = quad.data() + (size_t)(r * w2);
+		const Py_ssize_t nd = GF2_DIGIT_COUNT(v);
+		for (Py_ssize_t d = 0; d < nd; d++) {                      // bit b of the int is column b - 1
+			uint64_t x = (uint64_t)GF2_DIGITS(v)[d];
+			int64_t at = (int64_t)d * PyLong_SHIFT - 1;
+			if (d == 0) { x >>= 1; at = 0; }
+			if (at >= cols2) break;
+			w[at >> 6] |= x << (at & 63);
+			if ((at & 63) + PyLong_SHIFT > 64 && (at >> 6) + 1 < w2) w[(at >> 6) + 1] |= x >> (64 - (at & 63));
+		}
+		for (int64_t k = (cols2 >> 6) + 1; k < w2; k++) w[k] = 0;  // (nothing above the columns)
+		w[cols2 >> 6] &= ((uint64_t)1 << (cols2 & 63)) - 1;
+		if (nd > 0 && (GF2_DIGITS(v)[0] & 1)) w[cols2 >> 6] |= (uint64_t)1 << (cols2 & 63);      // the constant: column cols2
+	}
+	gf2bv_result *res = nullptr;
+	int rc;
+	Py_BEGIN_ALLOW_THREADS
+	rc = gf2bv_solve_xl3_words(quad.data(), m, w2, n, (int)mode, device, &res);
+	Py_END_ALLOW_THREADS
+	if (rc != GF2BV_OK) return raise_rc(rc, "solve");
+	return result_to_py(res, mode, device);
+}
+
+// m4ri_solve_xl3_quad_packed(lin, term_off, ta, tb, n_lin, mode[, device]) -> None | int | AffineSpace: m4ri_solve_quad_packed's
+// arrays (every row live), expanded, multiplied, padded and solved on the device (gf2bv_solve_xl3_quad_terms)
+PyObject *py_m4ri_solve_xl3_quad_packed(PyObject *, PyObject *const *args, Py_ssize_t nargs)
+{
+	int device;
+	if (!entry_device("m4ri_solve_xl3_quad_packed", 6, args, nargs, &device)) return nullptr;
+	long mode;
+	QuadBuffers qb;
+	if (!parse_mode(args[5], &mode) || !qb.parse(args, args[4])) return nullptr;
+	gf2bv_result *res = nullptr;
+	int rc;
+	Py_BEGIN_ALLOW_THREADS
+	rc = gf2bv_solve_xl3_quad_terms(qb.lin, qb.off, qb.ta, qb.tb, qb.live, qb.n, (int)mode, device, &res);
+	Py_END_ALLOW_THREADS
+	if (rc != GF2BV_OK) return raise_rc(rc, "solve");
+	return result_to_py(res, mode, device);
+}
+
 // ---- the packed front-ends in front of the kept factorization, the shared elimination and the batch --------------------------
 // m4ri_factor_packed(buffer, rows, words, cols, mode[, device]) -> Factorization: m4ri_factor on m4ri_solve_packed's buffer
 // (gf2bv_factor_digits, 32 payload bits per digit)
@@ -1649,6 +1713,10 @@ PyMethodDef module_methods[] = {
 	 "m4ri_solve_packed(buffer, rows, words, cols, mode, device=None)\n--\n\nm4ri_solve on equations already packed as rows x words 64-bit words (equation-int bit order)."},
 	{"m4ri_solve_quad_packed", FAST(py_m4ri_solve_quad_packed), METH_FASTCALL,
 	 "m4ri_solve_quad_packed(lin, term_off, ta, tb, n_lin, rows, mode, device=None)\n--\n\nm4ri_solve on a quadratic system kept factored (linear forms and products of two linear forms, packed 64-bit words): expanded into the linearised matrix on the GPU."},
+	{"m4ri_solve_xl3", FAST(py_m4ri_solve_xl3), METH_FASTCALL,
+	 "m4ri_solve_xl3(equations, n_lin, mode, device=None)\n--\n\nDegree-3 XL: QuadraticSystem equation ints multiplied by 1 and by every unknown on the GPU and solved over the monomials of degree <= 3."},
+	{"m4ri_solve_xl3_quad_packed", FAST(py_m4ri_solve_xl3_quad_packed), METH_FASTCALL,
+	 "m4ri_solve_xl3_quad_packed(lin, term_off, ta, tb, n_lin, mode, device=None)\n--\n\nm4ri_solve_xl3 on a quadratic system kept factored: expanded, multiplied and solved on the GPU."},
 	{"m4ri_solve_rhs", FAST(py_m4ri_solve_rhs), METH_FASTCALL,
 	 "m4ri_solve_rhs(equations, cols, mode, rhs, device=None)\n--\n\nSolve one coefficient matrix against every right-hand side in rhs (bit r = affine term of equation r) with one elimination; list of m4ri_solve results."},
 	{"m4ri_factor", FAST(py_m4ri_factor), METH_FASTCALL,

@@ -4872,3 +4872,113 @@ k_quad_expand_batch(const u64 *__restrict__ lin, const i64 *__restrict__ term_of
 	const i64 r0 = sys_row_off[blockIdx.y], live = sys_row_off[blockIdx.y + 1] - r0;
 	qx_expand_rows(lin + r0 * Wl, term_off + r0, ta, tb, live < rows ? live : rows, rows, n, Wl, tch, out + (i64)blockIdx.y * sys_stride, stride);
 }
+
+
+// ==========================================================================================
+// DEGREE-3 XL: every quadratic row, and its product with every unknown, over the monomials of degree <= 3
+// ==========================================================================================
+// (host side: gf2bv_xl3_expand_device in gf2_solver.hip)
+//
+// Source: m rows as k_quad_expand writes them -- column c < n unknown c (l_c), column n + i(i-1)/2 + j pair (i, j), j < i (q_ij),
+// column cols2 = n + C(n,2) the constant c.  Output: cols3 = cols2 + C(n,3) columns, the first cols2 as in the source, triple
+// (i, j, l), l < j < i, at cols2 + C(i,3) + C(j,2) + l, the constant at cols3.  Equation e owns the rows e(n+1) .. e(n+1) + n:
+// first f_e itself, then x_k f_e for k = 0 .. n-1 with x^2 = x:
+//   unknown k = c ^ l_k, pair {k, i} = l_i ^ q_ki, triple T containing k = q of the other two; constant 0.
+// Runs of consecutive columns of x_k f:
+//   pairs (i, 0..i-1):       i = k: l[0..k) ^ q(k, 0..k-1);  i > k: the one bit l_i ^ q(i, k) at position k;  i < k: nothing.
+//   triples (i, j, 0..j-1):  k = i: q(j, 0..j-1);  k = j: q(i, 0..j-1);  k < j: the one bit q(i, j) at position k;  else nothing.
+// So pairs below C(k,2) and triples below C(k,3) are zero (the word leaves at once), and inside a block i > k the runs j < k are
+// skipped in one step.  Whole runs are 64-bit windows of the source row in LDS, as in k_quad_expand.
+// Work split: the rows are dealt to the workgroups in contiguous spans, so a workgroup reads a source row into LDS once for all the
+// products of it that fall into its span; every lane forms two consecutive output words per step and stores them as 16 bytes,
+// consecutive lanes consecutive 16 bytes: each output word has one writer, no atomics.  Rows >= m(n+1) are written as zeros.
+// LDS: W2 = ceil((cols2 + 1) / 64) words (dynamic).
+__device__ __forceinline__ u64 xl_bit(const u64 *s, i64 q) { return (s[q >> 6] >> (q & 63)) & 1; }
+__device__ __forceinline__ i64 xl_c2(i64 i) { return i * (i - 1) / 2; }
+__device__ __forceinline__ i64 xl_c3(i64 i) { return i * (i - 1) * (i - 2) / 6; }
+__device__ __forceinline__ i64 xl_tri_root(i64 p)                          // the largest i >= 1 with C(i,2) <= p
+{
+	i64 i = (i64)((1.0f + sqrtf(1.0f + 8.0f * (float)p)) * 0.5f);          // (float: exact to a few units below 2^31) ...
+	if (i < 1) i = 1;
+	while (xl_c2(i) > p) i--;                                              // ... made exact in integers
+	while (xl_c2(i + 1) <= p) i++;
+	return i;
+}
+__device__ __forceinline__ i64 xl_tet_root(i64 t)                          // the largest i >= 2 with C(i,3) <= t
+{
+	i64 i = (i64)cbrtf(6.0f * (float)t) + 1;
+	if (i < 2) i = 2;
+	while (xl_c3(i) > t) i--;
+	while (xl_c3(i + 1) <= t) i++;
+	return i;
+}
+
+// columns c0 .. c0 + 63 of the row x_k f (k < 0: f itself) of the source row `src`
+__device__ __forceinline__ u64 xl3_word(const u64 *src, int W2, i64 n, i64 cols2, i64 cols3, i64 c0, int k)
+{
+	if (k < 0) {                                                           // f: its own columns, no triple, the constant behind them
+		u64 acc = c0 < cols2 ? qx_window(src, W2, c0) & qx_low(cols2 - c0) : 0;
+		if (cols3 >= c0 && cols3 < c0 + 64) acc |= xl_bit(src, cols2) << (cols3 - c0);
+		return acc;
+	}
+	u64 acc = 0;
+	if (k >= c0 && k < c0 + 64) acc = (xl_bit(src, cols2) ^ xl_bit(src, k)) << (k - c0);
+	const i64 p_lo = (c0 > n ? c0 : n) - n, p_hi = (c0 + 64 < cols2 ? c0 + 64 : cols2) - n;        // the word's pair indices
+	if (p_lo < p_hi && p_hi > xl_c2(k)) {
+		i64 i = xl_tri_root(p_lo);
+		if (i < k) i = k;
+		for (i64 s = xl_c2(i); s < p_hi; s += i, i++) {                    // run i: pairs s .. s + i - 1
+			const i64 j0 = (p_lo > s ? p_lo : s) - s, j1 = (p_hi < s + i ? p_hi : s + i) - s;
+			if (i == k) {
+				if (j0 < j1) acc |= ((qx_window(src, W2, j0) ^ qx_window(src, W2, n + s + j0)) & qx_low(j1 - j0)) << (n + s + j0 - c0);
+			} else if (k >= j0 && k < j1)
+				acc |= (xl_bit(src, i) ^ xl_bit(src, n + s + k)) << (n + s + k - c0);
+		}
+	}
+	const i64 t_lo = (c0 > cols2 ? c0 : cols2) - cols2, t_hi = (c0 + 64 < cols3 ? c0 + 64 : cols3) - cols2;      // its triple indices
+	if (t_lo < t_hi && t_hi > xl_c3(k)) {
+		i64 i = xl_tet_root(t_lo), j = xl_tri_root(t_lo - xl_c3(i));       // the run t_lo lies in: 1 <= j < i
+		i64 s = xl_c3(i) + xl_c2(j);
+		while (s < t_hi) {                                                 // run (i, j): triples s .. s + j - 1
+			if (i < k) { i = k; j = 1; s = xl_c3(i); continue; }           // (k >= 3 here: nothing below block k)
+			if (i > k && j < k) { j = k; s = xl_c3(i) + xl_c2(j); continue; }      // (nothing in the runs below j = k)
+			const i64 j0 = (t_lo > s ? t_lo : s) - s, j1 = (t_hi < s + j ? t_hi : s + j) - s;
+			if (j0 < j1) {
+				if (i == k) acc |= (qx_window(src, W2, n + xl_c2(j) + j0) & qx_low(j1 - j0)) << (cols2 + s + j0 - c0);
+				else if (j == k) acc |= (qx_window(src, W2, n + xl_c2(i) + j0) & qx_low(j1 - j0)) << (cols2 + s + j0 - c0);
+				else if (k >= j0 && k < j1) acc |= xl_bit(src, n + xl_c2(i) + j) << (cols2 + s + k - c0);      // (k < j)
+			}
+			s += j;
+			if (++j == i) { i++; j = 1; }
+		}
+	}
+	return acc;
+}
+
+__global__ void __launch_bounds__(256)
+k_xl3_expand(const u64 *__restrict__ quad, i64 m, i64 quad_stride, int n, int W2, i64 rows, u64 *__restrict__ out, i64 stride)
+{
+	extern __shared__ u64 xl_lds[];                    // the source row: W2 words
+	const i64 cols2 = (i64)n + xl_c2(n), cols3 = cols2 + xl_c3(n);
+	const i64 npair = stride >> 1;                     // 16-byte pieces of a row (stride is even)
+	const i64 span = (rows + gridDim.x - 1) / gridDim.x;
+	const i64 r0 = (i64)blockIdx.x * span, r1 = r0 + span < rows ? r0 + span : rows;
+	i64 have = -1;                                     // the equation whose row is in LDS
+	for (i64 r = r0; r < r1; r++) {
+		ulonglong2 *o = reinterpret_cast<ulonglong2 *>(out + r * stride);
+		const i64 e = r / (n + 1);
+		if (e >= m) {
+			for (i64 p = threadIdx.x; p < npair; p += blockDim.x) o[p] = make_ulonglong2(0, 0);
+			continue;
+		}
+		if (e != have) {
+			__syncthreads();                           // the rows before have read theirs
+			for (int w = threadIdx.x; w < W2; w += blockDim.x) xl_lds[w] = quad[e * quad_stride + w];
+			__syncthreads();
+			have = e;
+		}
+		const int k = (int)(r - e * (n + 1)) - 1;
+		for (i64 p = threadIdx.x; p < npair; p += blockDim.x)
+			o[p] = make_ulonglong2(xl3_word(xl_lds, W2, n, cols2, cols3, 128 * p, k), xl3_word(xl_lds, W2, n, cols2, cols3, 128 * p + 64, k));
+	}
+}

@@ -4773,6 +4773,44 @@ int enqueue_quad_expand_batch(const QuadTerms &q, const i64 *d_sys_off, i64 nsys
 	return GF2BV_OK;
 }
 
+// Degree-3 XL (k_xl3_expand): m quadratic rows over n unknowns -- the rows k_quad_expand writes -- become `rows` rows over the
+// monomials of degree <= 3: each equation and its product with every unknown, then zeros
+struct Xl3Shape {
+	i64 m = 0, n = 0, rows = 0;
+	i64 cols2() const { return n + n * (n - 1) / 2; }
+	i64 cols3() const { return cols2() + n * (n - 1) * (n - 2) / 6; }
+	i64 w2() const { return (cols2() + 1 + 63) / 64; }         // words of a source row, which the kernel holds in LDS
+	i64 wt() const { return (cols3() + 1 + 63) / 64; }
+	i64 live() const { return m * (n + 1); }
+};
+constexpr i64 kXl3LdsBytes = 65536;
+
+// The shape, and the source stride against it; no pointer is looked at.  `pad`: a solve entry, whose rows are the live ones padded up
+// to the columns
+int check_xl3(Xl3Shape &x, i64 quad_stride, bool pad = false)
+{
+	if (x.n < 1 || x.n > 65535 || x.cols3() >= (1ll << 31) - 64)
+		return fail(GF2BV_ERR_ARG, "n_lin must be at least 1 and n_lin + C(n_lin,2) + C(n_lin,3) below 2^31 - 64");
+	if (x.m < 0 || x.m >= (1ll << 31) - 64 || x.live() >= (1ll << 31) - 64) return fail(GF2BV_ERR_ARG, "m(n_lin + 1) must stay below 2^31 - 64");
+	if (pad) x.rows = std::max(x.live(), x.cols3());
+	if (x.rows >= (1ll << 31) - 64 || x.rows < x.live()) return fail(GF2BV_ERR_ARG, "rows must be at least m(n_lin + 1) and below 2^31 - 64");
+	if (x.w2() * 8 > kXl3LdsBytes) return fail(GF2BV_ERR_ARG, "a quadratic row of this n_lin does not fit the expansion kernel's LDS (64 KiB)");
+	if (quad_stride < x.w2()) return fail(GF2BV_ERR_ARG, "quad_stride_words does not cover the quadratic columns and the constant");
+	return GF2BV_OK;
+}
+
+// (device pointers, already checked) the kernel on `st`: a few thousand workgroups, each a contiguous span of the rows
+int enqueue_xl3_expand(const Xl3Shape &x, const u64 *d_quad, i64 quad_stride, u64 *d_aug, i64 stride, hipStream_t st)
+{
+	if (x.rows == 0) return GF2BV_OK;
+	const unsigned block = (unsigned)std::min<i64>(256, round_up(std::max<i64>(stride / 2, 1), 64));
+	const unsigned grid = (unsigned)std::min<i64>(x.rows, 256 * 16);
+	hipLaunchKernelGGL(k_xl3_expand, dim3(grid), dim3(block), sizeof(u64) * (size_t)x.w2(), st, d_quad, x.m, quad_stride, (int)x.n,
+	                   (int)x.w2(), x.rows, d_aug, stride);
+	HIPCHK(hipGetLastError());
+	return GF2BV_OK;
+}
+
 struct PoolStream {                    // a stream of the pool for the length of an entry
 	hipStream_t st = nullptr;
 	int device = 0;
@@ -4791,7 +4829,17 @@ struct QuadStage {
 	                                   // first entries, gf2bv_quad_expand_words and gf2bv_solve_quad_terms, keep their GF2BV_ERR_HIP
 	u64 *d_aug = nullptr, *d_rhs = nullptr;
 	i64 ds = 0;
+	u64 *d_xl = nullptr;               // the degree-3 XL expansion of the rows in d_aug (expand_xl3), xs words a row: both are held at once
+	i64 xs = 0;
 	explicit QuadStage(int device, bool nomem = true) : nomem(nomem) { ps.device = device; }
+
+	int open()                         // the stream, once
+	{
+		if (ps.st) return GF2BV_OK;
+		HIPCHK(pool().stream(&ps.st, ps.device, 0));
+		scratch.sync_first = ps.st;
+		return GF2BV_OK;
+	}
 
 	int alloc(void **out, size_t bytes)
 	{
@@ -4814,8 +4862,7 @@ struct QuadStage {
 	// check_quad_batch left it); rhs: right-hand sides that go up into d_rhs in front of the expansion
 	int expand(QuadTerms q, i64 stride, const i64 *sys_off = nullptr, i64 nsys = 1, const u64 *rhs = nullptr, size_t rhs_bytes = 0)
 	{
-		HIPCHK(pool().stream(&ps.st, ps.device, 0));
-		scratch.sync_first = ps.st;
+		if (int rc = open()) return rc;
 		const i64 wl = q.wl(), T = q.off[q.rows_live];
 		u64 *lin = nullptr, *ta = nullptr, *tb = nullptr;
 		i64 *off = nullptr, *d_sys = nullptr;
@@ -4831,10 +4878,25 @@ struct QuadStage {
 		q.lin = lin; q.off = off; q.ta = ta; q.tb = tb;
 		return sys_off ? enqueue_quad_expand_batch(q, d_sys, nsys, d_aug, ds, q.rows * ds, ps.st) : enqueue_quad_expand(q, d_aug, ds, ps.st);
 	}
-	// the expansion's `nrows` rows into host memory, `stride` words apart; the host waits
-	int download(void *out, i64 stride, i64 nrows)
+	// Quadratic rows that are expanded already (host memory, `stride` words apart) into d_aug as they are
+	int upload_rows(const u64 *quad, i64 m, i64 stride)
 	{
-		HIPCHK(hipMemcpy2DAsync(out, stride * 8, d_aug, ds * 8, stride * 8, nrows, hipMemcpyDeviceToHost, ps.st));
+		if (int rc = open()) return rc;
+		ds = stride;
+		return upload(&d_aug, quad, sizeof(u64) * (size_t)(m * stride));
+	}
+	// The degree-3 XL expansion of the x.m quadratic rows in d_aug into d_xl, x.rows rows `stride` words apart rounded up to an even xs,
+	// behind whatever wrote d_aug on the stream
+	int expand_xl3(const Xl3Shape &x, i64 stride)
+	{
+		xs = round_up(stride, 2);
+		if (int rc = alloc((void **)&d_xl, sizeof(u64) * (size_t)(x.rows * xs))) return rc;
+		return enqueue_xl3_expand(x, d_aug, ds, d_xl, xs, ps.st);
+	}
+	// `nrows` rows of the expansion (`xl`: of the XL expansion) into host memory, `stride` words apart; the host waits
+	int download(void *out, i64 stride, i64 nrows, bool xl = false)
+	{
+		HIPCHK(hipMemcpy2DAsync(out, stride * 8, xl ? d_xl : d_aug, (xl ? xs : ds) * 8, stride * 8, nrows, hipMemcpyDeviceToHost, ps.st));
 		HIPCHK(hipStreamSynchronize(ps.st));
 		return GF2BV_OK;
 	}
@@ -4992,6 +5054,84 @@ int gf2bv_solve_batch_quad_terms(const uint64_t *lin, const int64_t *term_off, c
 	if ((rc = stage.expand(q, q.wt(), sys_off, nsys))) return rc;
 	// (the gangs run on streams of their own, behind an event gf2bv_solve_batch_device records on this one)
 	return gf2bv_solve_batch_device(stage.d_aug, nsys, rows * stage.ds, rows, q.cols(), stage.ds, mode, device, stage.ps.st, 0, out);
+	});
+}
+
+// ---- degree-3 XL: the quadratic rows (expanded already, or factored) multiplied by 1 and by every unknown on the device
+int gf2bv_xl3_expand_device(const void *d_quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int64_t rows, void *d_aug,
+                            int64_t stride_words, int device, void *stream)
+{
+	return catching([&]() -> int {
+	Xl3Shape x;
+	x.m = m; x.n = n_lin; x.rows = rows;
+	if (!d_aug || (!d_quad && m > 0)) return fail(GF2BV_ERR_ARG, "null pointer");
+	int rc = check_xl3(x, quad_stride_words);
+	if (rc) return rc;
+	if (stride_words % 2 != 0 || stride_words < x.wt() || ((uintptr_t)d_aug & 15))
+		return fail(GF2BV_ERR_ARG, "device matrix needs 16-byte alignment and an even stride_words covering cols+1 bits");
+	if ((rc = check_device(device))) return rc;
+	return enqueue_xl3_expand(x, (const u64 *)d_quad, quad_stride_words, (u64 *)d_aug, stride_words, (hipStream_t)stream);
+	});
+}
+
+int gf2bv_xl3_expand_words(const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int64_t rows, uint64_t *out_aug,
+                           int64_t stride_words, int device)
+{
+	return catching([&]() -> int {
+	Xl3Shape x;
+	x.m = m; x.n = n_lin; x.rows = rows;
+	if ((!out_aug && rows > 0) || (!quad && m > 0)) return fail(GF2BV_ERR_ARG, "null pointer");
+	int rc = check_xl3(x, quad_stride_words);
+	if (rc) return rc;
+	if (stride_words < x.wt()) return fail(GF2BV_ERR_ARG, "stride_words does not cover cols+1 bits");
+	if ((rc = check_device(device))) return rc;
+	if (rows == 0) return GF2BV_OK;
+	QuadStage stage(device);
+	if ((rc = stage.upload_rows(reinterpret_cast<const u64 *>(quad), m, quad_stride_words))) return rc;
+	if ((rc = stage.expand_xl3(x, stride_words))) return rc;
+	return stage.download(out_aug, stride_words, rows, true);
+	});
+}
+
+int gf2bv_solve_xl3_words(const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int mode, int device,
+                          gf2bv_result **out)
+{
+	return catching([&]() -> int {
+	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
+	*out = nullptr;
+	if (!quad && m > 0) return fail(GF2BV_ERR_ARG, "null pointer");
+	Xl3Shape x;
+	x.m = m; x.n = n_lin;
+	int rc = check_xl3(x, quad_stride_words, true);
+	if (!rc) rc = check_shape(x.rows, x.cols3(), mode);
+	if (!rc) rc = check_device(device);
+	if (rc) return rc;
+	QuadStage stage(device);
+	if ((rc = stage.upload_rows(reinterpret_cast<const u64 *>(quad), m, quad_stride_words))) return rc;
+	if ((rc = stage.expand_xl3(x, x.wt()))) return rc;
+	return gf2bv_solve_device(stage.d_xl, x.rows, x.cols3(), stage.xs, mode, device, stage.ps.st, 0, out);
+	});
+}
+
+int gf2bv_solve_xl3_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t m,
+                               int64_t n_lin, int mode, int device, gf2bv_result **out)
+{
+	return catching([&]() -> int {
+	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
+	*out = nullptr;
+	const QuadTerms q = quad_terms(lin, term_off, ta, tb, m, m, n_lin);      // the m quadratic rows, no padding
+	int rc = check_quad_terms(q, true);
+	if (rc) return rc;
+	Xl3Shape x;
+	x.m = m; x.n = n_lin;
+	rc = check_xl3(x, q.wt(), true);
+	if (!rc) rc = check_shape(x.rows, x.cols3(), mode);
+	if (!rc) rc = check_device(device);
+	if (rc) return rc;
+	QuadStage stage(device);
+	if ((rc = stage.expand(q, q.wt()))) return rc;
+	if ((rc = stage.expand_xl3(x, x.wt()))) return rc;
+	return gf2bv_solve_device(stage.d_xl, x.rows, x.cols3(), stage.xs, mode, device, stage.ps.st, 0, out);
 	});
 }
 

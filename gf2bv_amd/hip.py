@@ -38,6 +38,7 @@ EXPORTS = [
     "gf2bv_quad_expand_device", "gf2bv_quad_expand_words", "gf2bv_solve_quad_terms",
     "gf2bv_factor_quad_terms", "gf2bv_factor_append_quad_terms", "gf2bv_solve_rhs_quad_terms", "gf2bv_solve_batch_quad_terms",
     "gf2bv_quad_expand_batch_words",
+    "gf2bv_xl3_expand_device", "gf2bv_xl3_expand_words", "gf2bv_solve_xl3_words", "gf2bv_solve_xl3_quad_terms",
     "gf2bv_quad_search", "gf2bv_quad_search_alloc", "gf2bv_quad_free", "gf2bv_quad_plan", "gf2bv_quad_points", "gf2bv_quad_forms_search", "gf2bv_quad_last_times",
     "gf2bv_slab_work_words", "gf2bv_slab_tiles", "gf2bv_slab_open", "gf2bv_slab_blocks", "gf2bv_slab_owner",
     "gf2bv_slab_payload_bytes", "gf2bv_slab_factor", "gf2bv_slab_apply", "gf2bv_slab_factor_on", "gf2bv_slab_apply_on",
@@ -146,6 +147,10 @@ def lib():
         L.gf2bv_solve_rhs_quad_terms.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, i64, i64, i32, i32, pp]
         L.gf2bv_solve_batch_quad_terms.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i32, i32, pp]
         L.gf2bv_quad_expand_batch_words.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, vp, i64, i32]
+        L.gf2bv_xl3_expand_device.argtypes = [vp, i64, i64, i64, i64, vp, i64, i32, vp]
+        L.gf2bv_xl3_expand_words.argtypes = [vp, i64, i64, i64, i64, vp, i64, i32]
+        L.gf2bv_solve_xl3_words.argtypes = [vp, i64, i64, i64, i32, i32, pp]
+        L.gf2bv_solve_xl3_quad_terms.argtypes = [vp, vp, vp, vp, i64, i64, i32, i32, pp]
         L.gf2bv_slab_work_words.argtypes = [i64, i64]
         L.gf2bv_slab_work_words.restype = i64
         L.gf2bv_slab_tiles.argtypes = [i64]
@@ -699,6 +704,57 @@ def quad_expand_batch_words(lin, term_off, ta, tb, sys_row_off, n_lin: int, rows
     _check(lib().gf2bv_quad_expand_batch_words(*_ptrs(lin, term_off, ta, tb),
                                                sys_row_off.ctypes.data, nsys, rows, n_lin, out.ctypes.data, stride, device))
     return out
+
+
+def xl3_cols(n_lin: int) -> int:
+    """columns of the degree-3 XL system in n_lin unknowns: the unknowns, their pairs and their triples"""
+    return quad_cols(n_lin) + n_lin * (n_lin - 1) * (n_lin - 2) // 6
+
+
+def _quad_rows(quad) -> np.ndarray:
+    """quadratic rows of the augmented-words layout (what quad_expand_words returns) as a contiguous [m, stride] array"""
+    quad = np.ascontiguousarray(quad, dtype=np.uint64)
+    if quad.ndim != 2:
+        raise ValueError("the quadratic rows must be a 2-D uint64 array, one row per equation")
+    return quad
+
+
+def xl3_expand_words(quad, n_lin: int, rows: int | None = None, stride_words: int | None = None, device: int = 0) -> np.ndarray:
+    """Degree-3 XL on the device (gf2bv_xl3_expand_words): `quad` holds m quadratic rows as quad_expand_words returns them; the
+    result is [rows, stride_words] uint64 over xl3_cols(n_lin) columns -- rows e(n+1) .. e(n+1) + n equation e and its product
+    with every unknown, rows beyond m(n+1) zero."""
+    quad = _quad_rows(quad)
+    m = len(quad)
+    rows = m * (n_lin + 1) if rows is None else rows
+    stride = (xl3_cols(n_lin) + 1 + 63) // 64 if stride_words is None else stride_words
+    out = np.empty((max(rows, 0), max(stride, 0)), dtype=np.uint64)
+    _check(lib().gf2bv_xl3_expand_words(quad.ctypes.data, m, quad.shape[1], n_lin, rows, out.ctypes.data, stride, device))
+    return out
+
+
+def xl3_expand_device(d_quad: int, m: int, quad_stride: int, n_lin: int, rows: int, d_aug: int, stride: int, device: int = 0,
+                      stream: int = 0) -> None:
+    """xl3_expand_words with everything resident in device memory: the kernel is enqueued on `stream` and the call returns; a
+    solve_device / factor_device on the same stream reads the finished rows."""
+    _check(lib().gf2bv_xl3_expand_device(d_quad, m, quad_stride, n_lin, rows, d_aug, stride, device, stream or None))
+
+
+def solve_xl3_words(quad, n_lin: int, mode: int = MODE_SINGLE, device: int = 0) -> Solution:
+    """Quadratic rows uploaded, multiplied on the device and solved there (gf2bv_solve_xl3_words): what solve_words returns for
+    xl3_expand_words of the same rows padded to max(m(n+1), xl3_cols(n_lin)) rows."""
+    quad = _quad_rows(quad)
+    h = ctypes.c_void_p()
+    _check(lib().gf2bv_solve_xl3_words(quad.ctypes.data, len(quad), quad.shape[1], n_lin, mode, device, ctypes.byref(h)))
+    return _take(h, mode)
+
+
+def solve_xl3_quad_terms(lin, term_off, ta, tb, n_lin: int, mode: int = MODE_SINGLE, device: int = 0) -> Solution:
+    """The factored system uploaded, expanded, multiplied and solved on the device (gf2bv_solve_xl3_quad_terms): what
+    solve_xl3_words returns for quad_expand_words of the same arrays."""
+    lin, term_off, ta, tb = _quad_terms(lin, term_off, ta, tb, n_lin)
+    h = ctypes.c_void_p()
+    _check(lib().gf2bv_solve_xl3_quad_terms(*_ptrs(lin, term_off, ta, tb), len(lin), n_lin, mode, device, ctypes.byref(h)))
+    return _take(h, mode)
 
 
 def synth_device(d_ptr: int, rows: int, cols: int, stride: int, seed: int, device: int = 0, stream: int = 0):

@@ -9,7 +9,8 @@ from __future__ import annotations
 
 from typing import Iterable, Optional, Sequence, Union
 
-from ._internal import AffineSpace, QuadSearchGaveUp, eqs_to_sage_mat_helper, m4ri_solve, m4ri_solve_many, m4ri_solve_rhs, mul_bit_quad
+from ._internal import (AffineSpace, QuadSearchGaveUp, eqs_to_sage_mat_helper, m4ri_solve, m4ri_solve_many, m4ri_solve_rhs, m4ri_solve_xl3,
+                        mul_bit_quad)
 from .bitvec import BitVec
 
 Zeros = Sequence[Union[BitVec, int]]
@@ -227,6 +228,23 @@ class LinearSystem:
         return bv.evaluate(raw)
 
 
+# -- the columns of degree-3 XL: the n unknowns, their pairs, their triples -----------------------------------------
+def xl3_cols(n: int) -> int:
+    return n + n * (n - 1) // 2 + n * (n - 1) * (n - 2) // 6
+
+
+def xl3_pair_col(n: int, i: int, j: int) -> int:
+    """column of x_i x_j, j < i: QuadraticSystem's"""
+    assert 0 <= j < i < n
+    return n + i * (i - 1) // 2 + j
+
+
+def xl3_triple_col(n: int, i: int, j: int, l: int) -> int:
+    """column of x_i x_j x_l, l < j < i"""
+    assert 0 <= l < j < i < n
+    return n + n * (n - 1) // 2 + i * (i - 1) * (i - 2) // 6 + j * (j - 1) // 2 + l
+
+
 class _QuadraticPoints:
     """What a linearised quadratic system does with the solutions of its linear solve, shared by ``QuadraticSystem`` and the packed
     front-end's ``PackedQuadraticSystem``: the points whose product unknowns equal the products of their linear part.  Needs
@@ -315,6 +333,84 @@ class _QuadraticPoints:
             out.append(sol)
         return out
 
+    # -- degree-3 XL (no counterpart in the reference) ----------------------------------------------------------
+    # Every equation is multiplied by 1 and by each unknown on the device and the system is linearised over the n + C(n,2) + C(n,3)
+    # monomials of degree <= 3 (xl3_cols): about n^2 / 6 independent quadratic equations pin the solution down where plain
+    # linearisation needs n^2 / 2.  The class mixed into supplies _solve_internal_xl(zeros, mode) and get_eqs_xl(zeros).
+    @staticmethod
+    def _check_degree(degree: int):
+        if degree != 3:
+            raise ValueError(f"XL is built for degree 3 only (multipliers 1 and x_k), not degree {degree!r}")
+
+    def solve_raw_one_xl(self, zeros: Zeros):
+        return self._solve_internal_xl(zeros, 0)
+
+    def solve_raw_space_xl(self, zeros: Zeros):
+        return self._solve_internal_xl(zeros, 1)
+
+    def _xl_index(self):
+        """(bit position of every coordinate's members) index arrays of the pair and the triple columns, built once per system"""
+        idx = getattr(self, "_xl_index_cache", None)
+        if idx is None:
+            import numpy as np                         # noqa: PLC0415  (first use only: the package imports without numpy)
+            n = self._lin_size
+            pi, pj = np.tril_indices(n, -1)            # (1,0) (2,0) (2,1) ...: pair (i, j) at i(i-1)/2 + j
+            a = np.arange(n)
+            ti, tj, tl = np.nonzero((a[:, None, None] > a[None, :, None]) & (a[None, :, None] > a[None, None, :]))      # i, then j, then l
+            idx = self._xl_index_cache = (pi, pj, ti, tj, tl)
+        return idx
+
+    def convert_sol_xl(self, s: int) -> Optional[tuple]:
+        """the linear parts of a raw point over the cubic columns when every pair and triple coordinate is the product of its linear
+        bits, None otherwise"""
+        import numpy as np                             # noqa: PLC0415
+        n = self._lin_size
+        cols3 = xl3_cols(n)
+        assert s >> cols3 == 0, "Invalid solution"
+        bits = np.unpackbits(np.frombuffer(s.to_bytes((cols3 + 7) // 8, "little"), dtype=np.uint8), bitorder="little")[:cols3]
+        pi, pj, ti, tj, tl = self._xl_index()
+        lin, pairs, triples = bits[:n], bits[n:n + len(pi)], bits[n + len(pi):]
+        if not (np.array_equal(pairs, lin[pi] & lin[pj]) and np.array_equal(triples, lin[ti] & lin[tj] & lin[tl])):
+            return None
+        return self._convert_sol(s & ((1 << n) - 1))[:-1]
+
+    def solve_all_xl(self, zeros: Zeros, *, degree: int = 3, max_dimension: int = 16):
+        """solve_all through degree-3 XL: the consistent points of the cubic system's solution space, in AffineSpace order"""
+        self._check_degree(degree)
+        space = self.solve_raw_space_xl(zeros)
+        if space is None:
+            return
+        if space.dimension > max_dimension:
+            raise DimensionTooLargeError(
+                f"Solution space (dim {space.dimension}) is too large, try increase max_dimension "
+                f"({max_dimension}) if you want (there will be 2**dim solutions)",
+                space=space,
+            )
+        for raw in space:
+            sol = self.convert_sol_xl(raw)
+            if sol is not None:
+                yield sol
+
+    def solve_one_xl(self, zeros: Zeros, *, degree: int = 3):
+        self._check_degree(degree)
+        for sol in self.solve_all_xl(zeros):
+            return sol
+        return None
+
+    def _xl_eqs(self, quad) -> list:
+        """quadratic rows of the augmented-words layout -> the equation ints of their degree-3 XL rows (bit 0 the constant, bit 1 + c
+        column c), multiplied on the device, zeros dropped"""
+        from . import hip                              # noqa: PLC0415  (ctypes binding, first use only)
+        if not len(quad):
+            return []
+        cols3 = xl3_cols(self._lin_size)
+        mask = (1 << cols3) - 1
+        eqs = []
+        for r in hip.xl3_expand_words(quad, self._lin_size):
+            v = int.from_bytes(r.tobytes(), "little")
+            eqs.append(((v & mask) << 1) | (v >> cols3))
+        return [e for e in eqs if e]
+
     def evaluate(self, bv: BitVec, sol: tuple) -> int:
         raw, shift = 0, 0
         for value, width in zip(sol, self._quad_sizes):
@@ -384,3 +480,21 @@ class QuadraticSystem(_QuadraticPoints, LinearSystem):
         if len(a) != 1:
             raise ValueError("The input should be a single bit")
         return self._bit_assert(a._bits[0], v)
+
+    # -- degree-3 XL: the equation ints go down as they are, the device multiplies and pads them ------------------------------------------
+    def _solve_internal_xl(self, zeros: Zeros, mode: int):
+        eqs = self.get_eqs(zeros)
+        if 1 in eqs:                            # the equation "1 = 0"
+            return None
+        return m4ri_solve_xl3(eqs, self._lin_size, mode)
+
+    def get_eqs_xl(self, zeros: Zeros) -> list:
+        """the equations and their products with every unknown as equation ints over the cubic columns (needs the GPU and numpy)"""
+        import numpy as np                             # noqa: PLC0415
+        eqs = self.get_eqs(zeros)
+        words = (self._cols + 1 + 63) // 64
+        mask = (1 << self._cols) - 1
+        quad = np.zeros((len(eqs), words), dtype=np.uint64)
+        for r, e in enumerate(eqs):
+            quad[r] = np.frombuffer((((e >> 1) & mask) | ((e & 1) << self._cols)).to_bytes(8 * words, "little"), dtype=np.uint64)
+        return self._xl_eqs(quad)

@@ -21,7 +21,7 @@ from typing import Iterable, Optional, Sequence
 
 import numpy as np
 
-from ._internal import m4ri_solve_many_quad_packed, m4ri_solve_packed, m4ri_solve_quad_packed
+from ._internal import m4ri_solve_many_quad_packed, m4ri_solve_packed, m4ri_solve_quad_packed, m4ri_solve_xl3_quad_packed
 from .bitvec import BitVec
 from .linsys import DimensionTooLargeError, _QuadraticPoints
 
@@ -545,6 +545,19 @@ class PackedQuadraticSystem(_QuadraticPoints, PackedLinearSystem):
     def _solve_internal(self, zeros: Sequence, mode: int):
         lin, off, ta, tb = self._terms(zeros)
         return m4ri_solve_quad_packed(lin, off, ta, tb, self._lin_size, max(len(lin), self._cols), mode)      # (the boundary wants rows >= cols)
+
+    # -- degree-3 XL: the factored arrays go down, the device expands, multiplies and pads them (nothing is decided on the host) ----
+    def _solve_internal_xl(self, zeros: Sequence, mode: int):
+        lin, off, ta, tb = self._terms(zeros)
+        return m4ri_solve_xl3_quad_packed(lin, off, ta, tb, self._lin_size, mode)
+
+    def get_eqs_xl(self, zeros: Sequence) -> list:
+        """the equations and their products with every unknown as equation ints over the cubic columns (needs the GPU)"""
+        from . import hip                              # noqa: PLC0415
+        lin, off, ta, tb = self._terms(zeros)
+        if not len(lin):
+            return []
+        return self._xl_eqs(hip.quad_expand_words(lin, off, ta, tb, self._lin_size))
 
     # -- a kept factorization, many right-hand sides, batches: QuadraticSystem's methods on the factored arrays --------------------
     # (solve_*_rhs are PackedLinearSystem's through ``factor``; solve_one_rhs is QuadraticSystem's own, _QuadraticPoints)

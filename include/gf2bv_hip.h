@@ -398,6 +398,38 @@ int gf2bv_quad_expand_batch_words(const uint64_t *lin, const int64_t *term_off, 
                                   const int64_t *sys_row_off, int64_t nsys, int64_t rows, int64_t n_lin, uint64_t *out_aug,
                                   int64_t stride_words, int device);
 
+/* ---- degree-3 XL: quadratic equations multiplied by 1 and by every unknown, on the device --------------------------------------
+ * Input: m quadratic rows in n_lin unknowns in the augmented-words layout for cols2 = n_lin + n_lin(n_lin-1)/2 -- what
+ * gf2bv_quad_expand_* writes: column c < n_lin unknown c, column n_lin + i(i-1)/2 + j the pair (i, j), j < i, column cols2 the
+ * constant --, quad_stride_words >= ceil((cols2 + 1) / 64) words apart.
+ * Output: `rows` >= m(n_lin + 1) rows over cols3 = cols2 + n_lin(n_lin-1)(n_lin-2)/6 columns: the first cols2 as in the input, the
+ * triple (i, j, l), l < j < i, at column cols2 + i(i-1)(i-2)/6 + j(j-1)/2 + l, the constant at column cols3, every bit from cols3 + 1
+ * to the end of the stride zero.  Equation e gives the rows e(n_lin+1) .. e(n_lin+1) + n_lin: row e(n_lin+1) is f_e itself, row
+ * e(n_lin+1) + 1 + k is x_k f_e with x^2 = x.  For f = c + sum l_i x_i + sum q_ij x_i x_j that product has the constant 0, unknown k
+ * = c ^ l_k, pair {k, i} = l_i ^ q_ki, the triple T containing k = q of the other two members of T, everything else 0.  Rows
+ * m(n_lin+1) .. rows - 1 are written as zeros (the padding up to rows >= cols3).
+ * gf2bv_xl3_expand_device: everything in device memory; the kernel is enqueued on `stream` (a HIP stream handle or NULL) and the
+ * call returns, as gf2bv_quad_expand_device does: gf2bv_solve_device / gf2bv_factor_device on the same stream consume d_aug with no
+ * synchronisation in between, and d_quad may be what gf2bv_quad_expand_device wrote on that stream.  d_aug 16-byte aligned,
+ * stride_words even and >= ceil((cols3 + 1) / 64).
+ * gf2bv_xl3_expand_words: host pointers in, rows x stride_words words back in host memory (upload, kernel, download).
+ * gf2bv_solve_xl3_words: upload, expansion into a buffer of the pool with rows = max(m(n_lin+1), cols3), gf2bv_solve_device on the
+ * same pool stream: a result over cols3 columns.
+ * gf2bv_solve_xl3_quad_terms: the factored form of gf2bv_solve_quad_terms (all m rows live): the quadratic rows are expanded on the
+ * device with no padding, multiplied there on the same stream and solved; quadratic rows and expansion are held at once.
+ * Argument errors (null pointers, n_lin < 1, cols3 or m(n_lin+1) or rows >= 2^31 - 64, rows < m(n_lin+1), a short stride, for the
+ * device entry an odd stride_words or a misaligned d_aug, a quadratic row above the kernel's LDS budget of 64 KiB -- n_lin > 1023 --,
+ * a bad mode, the offset rules of gf2bv_solve_quad_terms) return GF2BV_ERR_ARG before any device is touched; an expansion that does
+ * not fit on the device returns GF2BV_ERR_NOMEM. */
+int gf2bv_xl3_expand_device(const void *d_quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int64_t rows, void *d_aug,
+                            int64_t stride_words, int device, void *stream);
+int gf2bv_xl3_expand_words(const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int64_t rows, uint64_t *out_aug,
+                           int64_t stride_words, int device);
+int gf2bv_solve_xl3_words(const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int mode, int device,
+                          gf2bv_result **out);
+int gf2bv_solve_xl3_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t m,
+                               int64_t n_lin, int mode, int device, gf2bv_result **out);
+
 /* ---- synthetic systems + independent residual check (bench / tests) ----------------------- */
 /* word w of row r = mix64(mix64(seed) ^ ((r<<20)|w)); planted solution = pseudo-row 0xFFFFF;
  * RHS = <row, planted>.  Writes rows x stride_words words at d_aug. */
