@@ -1047,27 +1047,19 @@ PyObject *py_m4ri_solve_quad_packed(PyObject *, PyObject *const *args, Py_ssize_
 }
 
 // ---- degree-3 XL: quadratic equations multiplied by 1 and by every unknown on the device (gf2bv_hip.h, "degree-3 XL") --------------
-// m4ri_solve_xl3(equations, n_lin, mode[, device]) -> None | int | AffineSpace over n_lin + C(n_lin,2) + C(n_lin,3) columns.
-// New entry (no counterpart in the reference): `equations` are QuadraticSystem's equation ints (bit 0 the constant, bit 1 + c column
-// c of the n_lin + C(n_lin,2) linearised unknowns; higher bits and the sign ignored).  They are written as augmented words on the
-// host -- one pass over the digits, no PyLong is made -- and gf2bv_solve_xl3_words multiplies, pads and solves them on the device.
-PyObject *py_m4ri_solve_xl3(PyObject *, PyObject *const *args, Py_ssize_t nargs)
+// QuadraticSystem's equation ints of `list` as augmented words over the n_lin = `n_obj` unknowns and their pairs (column c = bit 1 + c,
+// the constant at column cols2), w2 words a row: one pass over the digits
+bool quad_rows_from_ints(PyObject *list, PyObject *n_obj, std::vector<uint64_t> &quad, int64_t *m_out, int64_t *n_out, int64_t *w2_out)
 {
-	int device;
-	if (!entry_device("m4ri_solve_xl3", 3, args, nargs, &device)) return nullptr;
-	PyObject *list = args[0];
-	if (!PyList_Check(list)) { PyErr_SetString(PyExc_TypeError, "The first argument equations must be a list"); return nullptr; }
-	const Py_ssize_t n = PyLong_AsSsize_t(args[1]);
-	if (n == -1 && PyErr_Occurred()) return nullptr;
-	if (n < 1 || n > 65535) { PyErr_SetString(PyExc_ValueError, "n_lin must be 1..65535"); return nullptr; }
-	long mode;
-	if (!parse_mode(args[2], &mode)) return nullptr;
+	if (!PyList_Check(list)) { PyErr_SetString(PyExc_TypeError, "The first argument equations must be a list"); return false; }
+	const Py_ssize_t n = PyLong_AsSsize_t(n_obj);
+	if (n == -1 && PyErr_Occurred()) return false;
+	if (n < 1 || n > 65535) { PyErr_SetString(PyExc_ValueError, "n_lin must be 1..65535"); return false; }
 	const int64_t m = PyList_GET_SIZE(list), cols2 = n + n * (n - 1) / 2, w2 = (cols2 + 1 + 63) / 64;
-	std::vector<uint64_t> quad;
-	try { quad.assign((size_t)(m * w2), 0); } catch (const std::bad_alloc &) { PyErr_NoMemory(); return nullptr; }
+	try { quad.assign((size_t)(m * w2), 0); } catch (const std::bad_alloc &) { PyErr_NoMemory(); return false; }
 	for (int64_t r = 0; r < m; r++) {
 		PyObject *item = PyList_GET_ITEM(list, r);
-		if (!PyLong_Check(item)) { PyErr_SetString(PyExc_TypeError, "List items must be integers"); return nullptr; }
+		if (!PyLong_Check(item)) { PyErr_SetString(PyExc_TypeError, "List items must be integers"); return false; }
 		PyLongObject *v = (PyLongObject *)item;
 		uint64_t *w = quad.data() + (size_t)(r * w2);
 		const Py_ssize_t nd = GF2_DIGIT_COUNT(v);
@@ -1083,6 +1075,23 @@ PyObject *py_m4ri_solve_xl3(PyObject *, PyObject *const *args, Py_ssize_t nargs)
 		w[cols2 >> 6] &= ((uint64_t)1 << (cols2 & 63)) - 1;
 		if (nd > 0 && (GF2_DIGITS(v)[0] & 1)) w[cols2 >> 6] |= (uint64_t)1 << (cols2 & 63);      // the constant: column cols2
 	}
+	*m_out = m; *n_out = n; *w2_out = w2;
+	return true;
+}
+
+// m4ri_solve_xl3(equations, n_lin, mode[, device]) -> None | int | AffineSpace over n_lin + C(n_lin,2) + C(n_lin,3) columns.
+// New entry (no counterpart in the reference): `equations` are QuadraticSystem's equation ints (bit 0 the constant, bit 1 + c column
+// c of the n_lin + C(n_lin,2) linearised unknowns; higher bits and the sign ignored).  They are written as augmented words on the
+// host -- one pass over the digits, no PyLong is made -- and gf2bv_solve_xl3_words multiplies, pads and solves them on the device.
+PyObject *py_m4ri_solve_xl3(PyObject *, PyObject *const *args, Py_ssize_t nargs)
+{
+	int device;
+	if (!entry_device("m4ri_solve_xl3", 3, args, nargs, &device)) return nullptr;
+	long mode;
+	if (!parse_mode(args[2], &mode)) return nullptr;
+	std::vector<uint64_t> quad;
+	int64_t m, n, w2;
+	if (!quad_rows_from_ints(args[0], args[1], quad, &m, &n, &w2)) return nullptr;
 	gf2bv_result *res = nullptr;
 	int rc;
 	Py_BEGIN_ALLOW_THREADS
@@ -1108,6 +1117,71 @@ PyObject *py_m4ri_solve_xl3_quad_packed(PyObject *, PyObject *const *args, Py_ss
 	Py_END_ALLOW_THREADS
 	if (rc != GF2BV_OK) return raise_rc(rc, "solve");
 	return result_to_py(res, mode, device);
+}
+
+// ---- hybrid XL: guessed unknowns, every assignment's system in one batch (gf2bv_hip.h, "hybrid XL") ---------------------------------
+// (guess, a0, na) of the two entries below: a sequence of unknown indices and the range of assignments; the library checks the values
+struct GuessArgs {
+	std::vector<int32_t> g;
+	int64_t a0 = 0, na = 0;
+	bool parse(PyObject *guess, PyObject *a0_obj, PyObject *na_obj)
+	{
+		PyObject *seq = PySequence_Fast(guess, "guess must be a sequence of unknown indices");
+		if (!seq) return false;
+		const Py_ssize_t f = PySequence_Fast_GET_SIZE(seq);
+		bool ok = true;
+		for (Py_ssize_t t = 0; t < f && ok; t++) {
+			const long v = PyLong_AsLong(PySequence_Fast_GET_ITEM(seq, t));
+			if (v == -1 && PyErr_Occurred()) ok = false;
+			else if (v < 0 || v > 65535) { PyErr_SetString(PyExc_ValueError, "a guessed unknown must be 0 .. n_lin - 1"); ok = false; }
+			else g.push_back((int32_t)v);
+		}
+		Py_DECREF(seq);
+		if (!ok) return false;
+		a0 = PyLong_AsLongLong(a0_obj);
+		if (a0 == -1 && PyErr_Occurred()) return false;
+		na = PyLong_AsLongLong(na_obj);
+		if (na == -1 && PyErr_Occurred()) return false;
+		if (a0 < 0 || na < 0 || na >= ((int64_t)1 << 31)) { PyErr_SetString(PyExc_ValueError, "the assignments must be a range of 0 .. 2^nguess - 1"); return false; }
+		return true;
+	}
+};
+
+// m4ri_solve_xl3_guess(equations, n_lin, guess, a0, na, mode[, device]) -> list of None | int | AffineSpace over the cubic columns of
+// the n_lin - len(guess) remaining unknowns, element s for assignment a0 + s (bit t of it the value of unknown guess[t]).
+// New entry (no counterpart in the reference): the equation ints are written as augmented words in one pass, as m4ri_solve_xl3 does,
+// and gf2bv_solve_xl3_guess_words substitutes, multiplies, pads and solves every assignment's system on the device as one batch.
+PyObject *py_m4ri_solve_xl3_guess(PyObject *, PyObject *const *args, Py_ssize_t nargs)
+{
+	int device;
+	if (!entry_device("m4ri_solve_xl3_guess", 6, args, nargs, &device)) return nullptr;
+	long mode;
+	GuessArgs ga;
+	if (!parse_mode(args[5], &mode) || !ga.parse(args[2], args[3], args[4])) return nullptr;
+	std::vector<uint64_t> quad;
+	int64_t m, n, w2;
+	if (!quad_rows_from_ints(args[0], args[1], quad, &m, &n, &w2)) return nullptr;
+	if (ga.na == 0) return PyList_New(0);
+	return collect_results(ga.na, mode, device, [&](gf2bv_result **out) {
+		return gf2bv_solve_xl3_guess_words(quad.data(), m, w2, n, ga.g.data(), (int64_t)ga.g.size(), ga.a0, ga.na, (int)mode, device, out);
+	});
+}
+
+// m4ri_solve_xl3_guess_quad_packed(lin, term_off, ta, tb, n_lin, guess, a0, na, mode[, device]) -> list: m4ri_solve_xl3_guess on
+// m4ri_solve_quad_packed's arrays (every row live), expanded on the device first (gf2bv_solve_xl3_guess_quad_terms)
+PyObject *py_m4ri_solve_xl3_guess_quad_packed(PyObject *, PyObject *const *args, Py_ssize_t nargs)
+{
+	int device;
+	if (!entry_device("m4ri_solve_xl3_guess_quad_packed", 9, args, nargs, &device)) return nullptr;
+	long mode;
+	GuessArgs ga;
+	QuadBuffers qb;
+	if (!parse_mode(args[8], &mode) || !ga.parse(args[5], args[6], args[7]) || !qb.parse(args, args[4])) return nullptr;
+	if (ga.na == 0) return PyList_New(0);
+	return collect_results(ga.na, mode, device, [&](gf2bv_result **out) {
+		return gf2bv_solve_xl3_guess_quad_terms(qb.lin, qb.off, qb.ta, qb.tb, qb.live, qb.n, ga.g.data(), (int64_t)ga.g.size(), ga.a0, ga.na,
+		                                        (int)mode, device, out);
+	});
 }
 
 // ---- the packed front-ends in front of the kept factorization, the shared elimination and the batch --------------------------
@@ -1717,6 +1791,10 @@ PyMethodDef module_methods[] = {
 	 "m4ri_solve_xl3(equations, n_lin, mode, device=None)\n--\n\nDegree-3 XL: QuadraticSystem equation ints multiplied by 1 and by every unknown on the GPU and solved over the monomials of degree <= 3."},
 	{"m4ri_solve_xl3_quad_packed", FAST(py_m4ri_solve_xl3_quad_packed), METH_FASTCALL,
 	 "m4ri_solve_xl3_quad_packed(lin, term_off, ta, tb, n_lin, mode, device=None)\n--\n\nm4ri_solve_xl3 on a quadratic system kept factored: expanded, multiplied and solved on the GPU."},
+	{"m4ri_solve_xl3_guess", FAST(py_m4ri_solve_xl3_guess), METH_FASTCALL,
+	 "m4ri_solve_xl3_guess(equations, n_lin, guess, a0, na, mode, device=None)\n--\n\nHybrid XL: the guessed unknowns substituted for the assignments a0 .. a0 + na - 1 and every assignment's degree-3 XL system solved on the GPU as one batch."},
+	{"m4ri_solve_xl3_guess_quad_packed", FAST(py_m4ri_solve_xl3_guess_quad_packed), METH_FASTCALL,
+	 "m4ri_solve_xl3_guess_quad_packed(lin, term_off, ta, tb, n_lin, guess, a0, na, mode, device=None)\n--\n\nm4ri_solve_xl3_guess on a quadratic system kept factored."},
 	{"m4ri_solve_rhs", FAST(py_m4ri_solve_rhs), METH_FASTCALL,
 	 "m4ri_solve_rhs(equations, cols, mode, rhs, device=None)\n--\n\nSolve one coefficient matrix against every right-hand side in rhs (bit r = affine term of equation r) with one elimination; list of m4ri_solve results."},
 	{"m4ri_factor", FAST(py_m4ri_factor), METH_FASTCALL,

@@ -4955,8 +4955,9 @@ __device__ __forceinline__ u64 xl3_word(const u64 *src, int W2, i64 n, i64 cols2
 	return acc;
 }
 
-__global__ void __launch_bounds__(256)
-k_xl3_expand(const u64 *__restrict__ quad, i64 m, i64 quad_stride, int n, int W2, i64 rows, u64 *__restrict__ out, i64 stride)
+// the rows of ONE system (quad its first source row, out its first output row), dealt to the workgroups of grid x
+__device__ __forceinline__ void
+xl3_expand_rows(const u64 *__restrict__ quad, i64 m, i64 quad_stride, int n, int W2, i64 rows, u64 *__restrict__ out, i64 stride)
 {
 	extern __shared__ u64 xl_lds[];                    // the source row: W2 words
 	const i64 cols2 = (i64)n + xl_c2(n), cols3 = cols2 + xl_c3(n);
@@ -4980,5 +4981,126 @@ k_xl3_expand(const u64 *__restrict__ quad, i64 m, i64 quad_stride, int n, int W2
 		const int k = (int)(r - e * (n + 1)) - 1;
 		for (i64 p = threadIdx.x; p < npair; p += blockDim.x)
 			o[p] = make_ulonglong2(xl3_word(xl_lds, W2, n, cols2, cols3, 128 * p, k), xl3_word(xl_lds, W2, n, cols2, cols3, 128 * p + 64, k));
+	}
+}
+
+__global__ void __launch_bounds__(256)
+k_xl3_expand(const u64 *__restrict__ quad, i64 m, i64 quad_stride, int n, int W2, i64 rows, u64 *__restrict__ out, i64 stride)
+{
+	xl3_expand_rows(quad, m, quad_stride, n, W2, rows, out, stride);
+}
+
+// The batched instance (gf2bv_xl3_expand_batch_device): blockIdx.y = system.  System s reads its m quadratic rows at
+// quad + s x quad_sys_stride and writes its `rows` rows at out + s x sys_stride; same split per system as k_xl3_expand.  The host
+// entry checks sys_stride >= rows x stride and quad_sys_stride >= m x quad_stride: every access lands inside the system's own words.
+__global__ void __launch_bounds__(256)
+k_xl3_expand_batch(const u64 *__restrict__ quad, i64 quad_sys_stride, i64 m, i64 quad_stride, int n, int W2, i64 rows,
+                   u64 *__restrict__ out, i64 stride, i64 sys_stride)
+{
+	xl3_expand_rows(quad + (i64)blockIdx.y * quad_sys_stride, m, quad_stride, n, W2, rows, out + (i64)blockIdx.y * sys_stride, stride);
+}
+
+
+// ==========================================================================================
+// HYBRID XL: guessed unknowns substituted into the quadratic rows, one specialised system per assignment
+// ==========================================================================================
+// (host side: gf2bv_quad_specialise_device in gf2_solver.hip)
+//
+// Source: m quadratic rows over n unknowns as k_quad_expand writes them.  The guess is f distinct unknowns g_0 .. g_{f-1}; assignment
+// a sets x_{g_t} to bit t of a.  R is the other n' = n - f unknowns in increasing index.  Assignment a's row over n' unknowns:
+//   pair (i', j')   q'  = q(R[i'], R[j'])                                  -- the same for every assignment
+//   unknown i'      l'  = l(R[i']) ^ XOR_{t in a} q(R[i'], g_t)
+//   constant        c'  = c ^ XOR_{t in a} l(g_t) ^ XOR_{t < u in a} q(g_t, g_u)
+// with q(x, y) the source column n + C(max,2) + min.  System s = a - a0 gets its m rows `out_stride` words apart at
+// out + s x sys_stride.
+// Work split: a workgroup takes one source row at a time (grid x strides over the rows) and a contiguous share of the assignments
+// (grid y).  It holds in LDS the source row, the row of assignment 0 (`base`: every column renumbered, formed once, a lane per
+// column and a ballot per word), and per guess t the vector V_t = (q(R[i'], g_t))_i' with two words of constants: bit 0 of the
+// first l(g_t), bit u < t of the second q(g_t, g_u).  An assignment's row is then base ^ XOR_{t in a} V_t in the words of the
+// linear columns, its constant bit, and base alone everywhere else: every output word has one writer, there are no atomics, two
+// consecutive words go out as 16 bytes from consecutive lanes where the strides are even and the output is 16-byte aligned (one
+// word at a time otherwise), and everything behind column cols2' up to the stride is written as zero.
+// LDS (dynamic): W2 + W2' + f (Wv + 2) words and n' ints, Wv = ceil(n' / 64); the host entry keeps it within 64 KiB.
+struct SpecGuess { int g[30]; };                       // the guessed unknowns, by value (f <= 30)
+
+__global__ void __launch_bounds__(256)
+k_quad_specialise(const u64 *__restrict__ quad, i64 m, i64 quad_stride, int n, int W2, SpecGuess guess, int f, i64 a0, i64 na,
+                  u64 *__restrict__ out, i64 out_stride, i64 sys_stride, int vec)
+{
+	extern __shared__ u64 sp_lds[];                    // [src: W2 | base: W2s | V: f x (Wv + 2) | R: n' ints]
+	const int ns = n - f, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+	const i64 cols2 = (i64)n + xl_c2(n), cols2s = (i64)ns + xl_c2(ns);
+	const int W2s = (int)((cols2s + 1 + 63) >> 6), Wv = (ns + 63) >> 6, Vs = Wv + 2;
+	u64 *src = sp_lds, *base = src + W2, *V = base + W2s;
+	int *R = reinterpret_cast<int *>(V + (i64)f * Vs);
+	for (int u = threadIdx.x; u < n; u += blockDim.x) {            // R: unknown u is remaining number u - #(guesses below it)
+		int below = 0;
+		bool guessed = false;
+		for (int t = 0; t < f; t++) { below += guess.g[t] < u; guessed |= guess.g[t] == u; }
+		if (!guessed) R[u - below] = u;
+	}
+	const i64 span = (na + gridDim.y - 1) / gridDim.y;             // this workgroup's assignments: systems s0 .. s1 - 1
+	const i64 s0 = (i64)blockIdx.y * span, s1 = s0 + span < na ? s0 + span : na;
+	const u64 cmask = 1ull << (cols2s & 63);
+	const int cword = (int)(cols2s >> 6);
+	for (i64 r = blockIdx.x; r < m; r += gridDim.x) {
+		__syncthreads();                               // R is there; the row before has been read
+		for (int w = threadIdx.x; w < W2; w += blockDim.x) src[w] = quad[r * quad_stride + w];
+		__syncthreads();
+		for (int w = wave; w < W2s; w += nwaves) {     // base: column c of the specialised row from its source column
+			const i64 c = 64 * (i64)w + lane;
+			i64 sc = -1;
+			if (c < ns) sc = R[c];
+			else if (c < cols2s) {
+				const i64 p = c - ns, i = xl_tri_root(p), j = p - xl_c2(i);
+				sc = n + xl_c2(R[i]) + R[j];
+			} else if (c == cols2s) sc = cols2;
+			const u64 word = __ballot(sc >= 0 && xl_bit(src, sc));
+			if (lane == 0) base[w] = word;
+		}
+		for (int e = wave; e < f * Vs; e += nwaves) {  // V_t and its constants
+			const int t = e / Vs, w = e - t * Vs, g = guess.g[t];
+			i64 sc = -1;
+			if (w < Wv) {
+				const int i = 64 * w + lane;
+				if (i < ns) { const int x = R[i]; sc = x > g ? n + xl_c2(x) + g : n + xl_c2(g) + x; }
+			} else if (w == Wv) {
+				if (lane == 0) sc = g;
+			} else if (lane < t) {
+				const int h = guess.g[lane];
+				sc = h > g ? n + xl_c2(h) + g : n + xl_c2(g) + h;
+			}
+			const u64 word = __ballot(sc >= 0 && xl_bit(src, sc));
+			if (lane == 0) V[e] = word;
+		}
+		__syncthreads();
+		// word w of assignment a
+		auto word_of = [&](i64 a, i64 w) -> u64 {
+			if (w >= W2s) return 0;
+			u64 acc = base[w];
+			if (w < Wv || w == cword) {
+				unsigned par = 0;
+				for (unsigned rest = (unsigned)a; rest; rest &= rest - 1) {
+					const int t = __ffs(rest) - 1;
+					const u64 *v = V + (i64)t * Vs;
+					if (w < Wv) acc ^= v[w];
+					par ^= (unsigned)v[Wv] ^ (unsigned)__popc((unsigned)v[Wv + 1] & (unsigned)a);
+				}
+				if (w == cword && (par & 1)) acc ^= cmask;
+			}
+			return acc;
+		};
+		if (vec) {
+			const i64 np = out_stride >> 1;
+			for (i64 idx = threadIdx.x; idx < (s1 - s0) * np; idx += blockDim.x) {
+				const i64 s = s0 + idx / np, p = idx % np;
+				reinterpret_cast<ulonglong2 *>(out + s * sys_stride + r * out_stride)[p] = make_ulonglong2(word_of(a0 + s, 2 * p), word_of(a0 + s, 2 * p + 1));
+			}
+		} else {
+			for (i64 idx = threadIdx.x; idx < (s1 - s0) * out_stride; idx += blockDim.x) {
+				const i64 s = s0 + idx / out_stride, w = idx % out_stride;
+				out[s * sys_stride + r * out_stride + w] = word_of(a0 + s, w);
+			}
+		}
 	}
 }

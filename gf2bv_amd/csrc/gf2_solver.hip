@@ -4811,6 +4811,83 @@ int enqueue_xl3_expand(const Xl3Shape &x, const u64 *d_quad, i64 quad_stride, u6
 	return GF2BV_OK;
 }
 
+// (device pointers, already checked) the batched kernel on `st`: system s reads its x.m rows at d_quad + s x quad_sys_stride and writes
+// x.rows rows at d_aug + s x sys_stride
+int enqueue_xl3_expand_batch(const Xl3Shape &x, const u64 *d_quad, i64 quad_sys_stride, i64 quad_stride, i64 nsys, u64 *d_aug, i64 stride,
+                             i64 sys_stride, hipStream_t st)
+{
+	if (x.rows == 0 || nsys == 0) return GF2BV_OK;
+	const unsigned block = (unsigned)std::min<i64>(256, round_up(std::max<i64>(stride / 2, 1), 64));
+	// contiguous spans of rows per workgroup, a few thousand workgroups in all where the systems are many
+	const unsigned gx = (unsigned)std::min<i64>(x.rows, std::max<i64>(256, 256 * 16 / nsys));
+	for (i64 s0 = 0; s0 < nsys; s0 += 65535) {         // (grid y holds 65535 systems)
+		const unsigned ns = (unsigned)std::min<i64>(65535, nsys - s0);
+		hipLaunchKernelGGL(k_xl3_expand_batch, dim3(gx, ns), dim3(block), sizeof(u64) * (size_t)x.w2(), st, d_quad + s0 * quad_sys_stride,
+		                   quad_sys_stride, x.m, quad_stride, (int)x.n, (int)x.w2(), x.rows, d_aug + s0 * sys_stride, stride, sys_stride);
+	}
+	HIPCHK(hipGetLastError());
+	return GF2BV_OK;
+}
+
+// Hybrid XL (k_quad_specialise): f guessed unknowns substituted into m quadratic rows over n unknowns, for the assignments
+// a0 .. a0 + na - 1; every assignment leaves the system `x` of m rows over n - f unknowns
+struct GuessShape {
+	i64 m = 0, n = 0, f = 0, a0 = 0, na = 0;
+	SpecGuess g{};
+	Xl3Shape x;
+	i64 w2() const { return (n + n * (n - 1) / 2 + 1 + 63) / 64; }
+	i64 lds_bytes() const { return 8 * (w2() + x.w2() + f * ((x.n + 63) / 64 + 2)) + 4 * x.n; }
+};
+
+// The guess, the range of assignments and the source stride; no device pointer is looked at
+int check_guess(GuessShape &s, const int32_t *guess, i64 quad_stride)
+{
+	if (s.n < 1 || s.n > 65535 || s.n + s.n * (s.n - 1) / 2 >= (1ll << 31) - 64)
+		return fail(GF2BV_ERR_ARG, "n_lin must be at least 1 and n_lin + C(n_lin,2) below 2^31 - 64");
+	if (s.f < 0 || s.f > std::min<i64>(s.n - 1, 30)) return fail(GF2BV_ERR_ARG, "nguess must be 0 .. min(n_lin - 1, 30)");
+	if (!guess && s.f > 0) return fail(GF2BV_ERR_ARG, "null pointer");
+	for (i64 t = 0; t < s.f; t++) {
+		if (guess[t] < 0 || guess[t] >= s.n) return fail(GF2BV_ERR_ARG, "a guessed unknown must be 0 .. n_lin - 1");
+		for (i64 u = 0; u < t; u++)
+			if (guess[u] == guess[t]) return fail(GF2BV_ERR_ARG, "a guessed unknown is repeated");
+		s.g.g[t] = guess[t];
+	}
+	if (s.a0 < 0 || s.na < 0 || s.a0 > (1ll << s.f) || s.na > (1ll << s.f) - s.a0)
+		return fail(GF2BV_ERR_ARG, "the assignments a0 .. a0 + na - 1 must lie in 0 .. 2^nguess - 1");
+	if (s.m < 0 || s.m >= (1ll << 31) - 64 || s.na * std::max<i64>(s.m, 1) >= (1ll << 31) - 64)
+		return fail(GF2BV_ERR_ARG, "m and na x m must stay below 2^31 - 64");
+	s.x.m = s.m; s.x.n = s.n - s.f;
+	if (quad_stride < s.w2()) return fail(GF2BV_ERR_ARG, "quad_stride_words does not cover the quadratic columns and the constant");
+	if (s.lds_bytes() > kXl3LdsBytes)
+		return fail(GF2BV_ERR_ARG, "the quadratic row, its specialised form and the guess vectors do not fit the specialisation kernel's LDS (64 KiB)");
+	return GF2BV_OK;
+}
+
+// The systems behind a solve entry: each assignment's expansion padded up to its columns, all of them one batch
+int check_guess_solve(GuessShape &s, int mode)
+{
+	int rc = check_xl3(s.x, s.x.w2(), true);
+	if (rc) return rc;
+	if (s.na * s.x.rows >= (1ll << 31) - 64) return fail(GF2BV_ERR_ARG, "the rows of all assignments' systems together must stay below 2^31 - 64");
+	return check_shape(s.x.rows, s.x.cols3(), mode);
+}
+
+// (device pointers, already checked) the kernel on `st`: system a - a0 at d_out + (a - a0) x sys_stride, m rows out_stride words apart
+int enqueue_quad_specialise(const GuessShape &s, const u64 *d_quad, i64 quad_stride, u64 *d_out, i64 out_stride, i64 sys_stride, hipStream_t st)
+{
+	if (s.m == 0 || s.na == 0) return GF2BV_OK;
+	const unsigned gx = (unsigned)std::min<i64>(s.m, 1024);
+	const unsigned gy = (unsigned)std::max<i64>(1, std::min<i64>({ s.na, 65535, 2048 / gx }));      // a couple of thousand workgroups
+	const int vec = !(out_stride & 1) && !(sys_stride & 1) && !((uintptr_t)d_out & 15);
+	hipLaunchKernelGGL(k_quad_specialise, dim3(gx, gy), dim3(256), (size_t)s.lds_bytes(), st, d_quad, s.m, quad_stride, (int)s.n, (int)s.w2(),
+	                   s.g, (int)s.f, s.a0, s.na, d_out, out_stride, sys_stride, vec);
+	HIPCHK(hipGetLastError());
+	return GF2BV_OK;
+}
+
+// What one assignment's system holds on the device while a solve entry runs: its specialised rows and its padded expansion
+i64 guess_system_bytes(const Xl3Shape &x) { return 8 * (x.m * round_up(x.w2(), 2) + x.rows * round_up(x.wt(), 2)); }
+
 struct PoolStream {                    // a stream of the pool for the length of an entry
 	hipStream_t st = nullptr;
 	int device = 0;
@@ -4831,6 +4908,8 @@ struct QuadStage {
 	i64 ds = 0;
 	u64 *d_xl = nullptr;               // the degree-3 XL expansion of the rows in d_aug (expand_xl3), xs words a row: both are held at once
 	i64 xs = 0;
+	u64 *d_spec = nullptr;             // hybrid XL: the rows in d_aug specialised for na assignments (specialise), ss words a row, m x ss a system
+	i64 ss = 0;
 	explicit QuadStage(int device, bool nomem = true) : nomem(nomem) { ps.device = device; }
 
 	int open()                         // the stream, once
@@ -4893,6 +4972,21 @@ struct QuadStage {
 		if (int rc = alloc((void **)&d_xl, sizeof(u64) * (size_t)(x.rows * xs))) return rc;
 		return enqueue_xl3_expand(x, d_aug, ds, d_xl, xs, ps.st);
 	}
+	// The rows in d_aug specialised for every assignment of `g` into d_spec, rows `stride` words apart
+	int specialise(const GuessShape &g, i64 stride)
+	{
+		ss = stride;
+		if (int rc = alloc((void **)&d_spec, sizeof(u64) * (size_t)(g.na * g.m * ss))) return rc;
+		return enqueue_quad_specialise(g, d_aug, ds, d_spec, ss, g.m * ss, ps.st);
+	}
+	// The degree-3 XL expansions of nsys systems of x.m quadratic rows in d_spec (system s at s x spec_sys words) into d_xl, system s at
+	// s x x.rows x xs
+	int expand_xl3_batch(const Xl3Shape &x, i64 nsys, i64 spec_sys, i64 stride)
+	{
+		xs = round_up(stride, 2);
+		if (int rc = alloc((void **)&d_xl, sizeof(u64) * (size_t)(nsys * x.rows * xs))) return rc;
+		return enqueue_xl3_expand_batch(x, d_spec, spec_sys, ss, nsys, d_xl, xs, x.rows * xs, ps.st);
+	}
 	// `nrows` rows of the expansion (`xl`: of the XL expansion) into host memory, `stride` words apart; the host waits
 	int download(void *out, i64 stride, i64 nrows, bool xl = false)
 	{
@@ -4901,6 +4995,31 @@ struct QuadStage {
 		return GF2BV_OK;
 	}
 };
+
+// the shape rules the two batched expansion entries share; no pointer is looked at
+int check_xl3_batch(Xl3Shape &x, i64 nsys, i64 quad_sys_stride, i64 quad_stride, i64 stride, i64 sys_stride)
+{
+	if (nsys < 0) return fail(GF2BV_ERR_ARG, "nsys must not be negative");
+	int rc = check_xl3(x, quad_stride);
+	if (rc) return rc;
+	if (nsys * std::max<i64>(x.rows, 1) >= (1ll << 31) - 64) return fail(GF2BV_ERR_ARG, "the rows of all systems together must stay below 2^31 - 64");
+	if (quad_sys_stride < x.m * quad_stride) return fail(GF2BV_ERR_ARG, "quad_sys_stride_words must be at least m * quad_stride_words");
+	if (stride < x.wt() || stride >= (1ll << 31)) return fail(GF2BV_ERR_ARG, "stride_words does not cover cols+1 bits");
+	if (sys_stride < x.rows * stride) return fail(GF2BV_ERR_ARG, "sys_stride_words must be at least rows * stride_words");
+	return GF2BV_OK;
+}
+
+// behind the rows in stage.d_aug: specialisation, batched expansion and the gang solve, all ordered on the stage's stream
+int solve_guess_staged(QuadStage &stage, const GuessShape &g, int mode, int device, gf2bv_result **out)
+{
+	int rc = stage.specialise(g, round_up(g.x.w2(), 2));
+	if (!rc) rc = stage.expand_xl3_batch(g.x, g.na, g.m * stage.ss, g.x.wt());
+	if (rc) return rc;
+	rc = gf2bv_solve_batch_device(stage.d_xl, g.na, g.x.rows * stage.xs, g.x.rows, g.x.cols3(), stage.xs, mode, device, stage.ps.st, 0, out);
+	if (rc)
+		for (i64 s = 0; s < g.na; s++) { gf2bv_result_free(out[s]); out[s] = nullptr; }
+	return rc;
+}
 
 }  // namespace
 
@@ -5132,6 +5251,165 @@ int gf2bv_solve_xl3_quad_terms(const uint64_t *lin, const int64_t *term_off, con
 	if ((rc = stage.expand(q, q.wt()))) return rc;
 	if ((rc = stage.expand_xl3(x, x.wt()))) return rc;
 	return gf2bv_solve_device(stage.d_xl, x.rows, x.cols3(), stage.xs, mode, device, stage.ps.st, 0, out);
+	});
+}
+
+// ---- hybrid XL: guessed unknowns substituted for many assignments at once, every assignment's system expanded and solved as one batch
+int gf2bv_quad_specialise_device(const void *d_quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, const int32_t *guess,
+                                 int64_t nguess, int64_t a0, int64_t na, void *d_out, int64_t out_stride_words, int64_t sys_stride_words,
+                                 int device, void *stream)
+{
+	return catching([&]() -> int {
+	GuessShape g;
+	g.m = m; g.n = n_lin; g.f = nguess; g.a0 = a0; g.na = na;
+	if (!d_out || (!d_quad && m > 0)) return fail(GF2BV_ERR_ARG, "null pointer");
+	int rc = check_guess(g, guess, quad_stride_words);
+	if (rc) return rc;
+	if (out_stride_words < g.x.w2() || out_stride_words >= (1ll << 31) || sys_stride_words < m * out_stride_words || ((uintptr_t)d_out & 7))
+		return fail(GF2BV_ERR_ARG, "out_stride_words must cover the specialised columns and the constant, sys_stride_words m rows of it");
+	if ((rc = check_device(device))) return rc;
+	return enqueue_quad_specialise(g, (const u64 *)d_quad, quad_stride_words, (u64 *)d_out, out_stride_words, sys_stride_words, (hipStream_t)stream);
+	});
+}
+
+int gf2bv_quad_specialise_words(const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, const int32_t *guess,
+                                int64_t nguess, int64_t a0, int64_t na, uint64_t *out, int64_t out_stride_words, int device)
+{
+	return catching([&]() -> int {
+	GuessShape g;
+	g.m = m; g.n = n_lin; g.f = nguess; g.a0 = a0; g.na = na;
+	if ((!out && m > 0 && na > 0) || (!quad && m > 0)) return fail(GF2BV_ERR_ARG, "null pointer");
+	int rc = check_guess(g, guess, quad_stride_words);
+	if (rc) return rc;
+	if (out_stride_words < g.x.w2() || out_stride_words >= (1ll << 31))
+		return fail(GF2BV_ERR_ARG, "out_stride_words does not cover the specialised columns and the constant");
+	if ((rc = check_device(device))) return rc;
+	if (m == 0 || na == 0) return GF2BV_OK;
+	QuadStage stage(device);
+	if ((rc = stage.upload_rows(reinterpret_cast<const u64 *>(quad), m, quad_stride_words))) return rc;
+	if ((rc = stage.specialise(g, out_stride_words))) return rc;          // (the caller's stride, odd or even: the rows come back as they are)
+	HIPCHK(hipMemcpyAsync(out, stage.d_spec, sizeof(u64) * (size_t)(na * m * out_stride_words), hipMemcpyDeviceToHost, stage.ps.st));
+	HIPCHK(hipStreamSynchronize(stage.ps.st));
+	return GF2BV_OK;
+	});
+}
+
+int gf2bv_xl3_expand_batch_device(const void *d_quad, int64_t nsys, int64_t quad_sys_stride_words, int64_t m, int64_t quad_stride_words,
+                                  int64_t n_lin, int64_t rows, void *d_aug, int64_t stride_words, int64_t sys_stride_words, int device,
+                                  void *stream)
+{
+	return catching([&]() -> int {
+	Xl3Shape x;
+	x.m = m; x.n = n_lin; x.rows = rows;
+	if (!d_aug || (!d_quad && m > 0)) return fail(GF2BV_ERR_ARG, "null pointer");
+	int rc = check_xl3_batch(x, nsys, quad_sys_stride_words, quad_stride_words, stride_words, sys_stride_words);
+	if (rc) return rc;
+	if (stride_words % 2 != 0 || sys_stride_words % 2 != 0 || ((uintptr_t)d_aug & 15))
+		return fail(GF2BV_ERR_ARG, "device matrices need 16-byte alignment and even stride_words and sys_stride_words");
+	if ((rc = check_device(device))) return rc;
+	return enqueue_xl3_expand_batch(x, (const u64 *)d_quad, quad_sys_stride_words, quad_stride_words, nsys, (u64 *)d_aug, stride_words,
+	                                sys_stride_words, (hipStream_t)stream);
+	});
+}
+
+int gf2bv_xl3_expand_batch_words(const uint64_t *quad, int64_t nsys, int64_t quad_sys_stride_words, int64_t m, int64_t quad_stride_words,
+                                 int64_t n_lin, int64_t rows, uint64_t *out_aug, int64_t stride_words, int64_t sys_stride_words, int device)
+{
+	return catching([&]() -> int {
+	Xl3Shape x;
+	x.m = m; x.n = n_lin; x.rows = rows;
+	if ((!out_aug && rows > 0 && nsys > 0) || (!quad && m > 0 && nsys > 0)) return fail(GF2BV_ERR_ARG, "null pointer");
+	int rc = check_xl3_batch(x, nsys, quad_sys_stride_words, quad_stride_words, stride_words, sys_stride_words);
+	if (rc) return rc;
+	if ((rc = check_device(device))) return rc;
+	if (rows == 0 || nsys == 0) return GF2BV_OK;
+	QuadStage stage(device);
+	if ((rc = stage.open())) return rc;
+	stage.ss = quad_stride_words;                      // (the last system's rows end the source: nothing behind them is read)
+	if ((rc = stage.upload(&stage.d_spec, reinterpret_cast<const u64 *>(quad),
+	                       m ? sizeof(u64) * (size_t)((nsys - 1) * quad_sys_stride_words + m * quad_stride_words) : 0))) return rc;
+	if ((rc = stage.expand_xl3_batch(x, nsys, quad_sys_stride_words, stride_words))) return rc;
+	if (sys_stride_words == rows * stride_words)
+		HIPCHK(hipMemcpy2DAsync(out_aug, stride_words * 8, stage.d_xl, stage.xs * 8, stride_words * 8, nsys * rows, hipMemcpyDeviceToHost, stage.ps.st));
+	else
+		for (i64 s = 0; s < nsys; s++)
+			HIPCHK(hipMemcpy2DAsync(out_aug + s * sys_stride_words, stride_words * 8, stage.d_xl + s * rows * stage.xs, stage.xs * 8,
+			                        stride_words * 8, rows, hipMemcpyDeviceToHost, stage.ps.st));
+	HIPCHK(hipStreamSynchronize(stage.ps.st));
+	return GF2BV_OK;
+	});
+}
+
+int gf2bv_solve_xl3_guess_words(const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, const int32_t *guess,
+                                int64_t nguess, int64_t a0, int64_t na, int mode, int device, gf2bv_result **out)
+{
+	return catching([&]() -> int {
+	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
+	for (i64 s = 0; s < na; s++) out[s] = nullptr;
+	if (!quad && m > 0) return fail(GF2BV_ERR_ARG, "null pointer");
+	GuessShape g;
+	g.m = m; g.n = n_lin; g.f = nguess; g.a0 = a0; g.na = na;
+	int rc = check_guess(g, guess, quad_stride_words);
+	if (!rc) rc = check_guess_solve(g, mode);
+	if (!rc) rc = check_device(device);
+	if (rc) return rc;
+	if (na == 0) return GF2BV_OK;
+	QuadStage stage(device);
+	if ((rc = stage.upload_rows(reinterpret_cast<const u64 *>(quad), m, quad_stride_words))) return rc;
+	return solve_guess_staged(stage, g, mode, device, out);
+	});
+}
+
+int gf2bv_solve_xl3_guess_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t m,
+                                     int64_t n_lin, const int32_t *guess, int64_t nguess, int64_t a0, int64_t na, int mode, int device,
+                                     gf2bv_result **out)
+{
+	return catching([&]() -> int {
+	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
+	for (i64 s = 0; s < na; s++) out[s] = nullptr;
+	const QuadTerms q = quad_terms(lin, term_off, ta, tb, m, m, n_lin);      // the m quadratic rows, no padding
+	int rc = check_quad_terms(q, true);
+	if (rc) return rc;
+	GuessShape g;
+	g.m = m; g.n = n_lin; g.f = nguess; g.a0 = a0; g.na = na;
+	rc = check_guess(g, guess, q.wt());
+	if (!rc) rc = check_guess_solve(g, mode);
+	if (!rc) rc = check_device(device);
+	if (rc) return rc;
+	if (na == 0) return GF2BV_OK;
+	QuadStage stage(device);
+	if ((rc = stage.expand(q, q.wt()))) return rc;
+	return solve_guess_staged(stage, g, mode, device, out);
+	});
+}
+
+// The largest number of assignments (at most 2^nguess) whose specialised rows and padded expansions take at most a quarter of
+// free_bytes -- the solver keeps a tile-major copy of about the size of every system of a gang, so expansion and copy stay below half of
+// what was free -- and whose rows together stay below 2^31 - 64; 0 when one system does not fit, -1 for a bad shape.  No device is touched.
+int64_t gf2bv_xl3_guess_chunk(int64_t m, int64_t n_lin, int64_t nguess, int64_t free_bytes)
+{
+	if (n_lin < 1 || n_lin > 65535 || nguess < 0 || nguess > std::min<i64>(n_lin - 1, 30) || m < 0 || free_bytes < 0) return -1;
+	Xl3Shape x;
+	x.m = m; x.n = n_lin - nguess;
+	if (check_xl3(x, x.w2(), true)) return -1;
+	const i64 fit = free_bytes / 4 / guess_system_bytes(x);
+	return std::min<i64>({ 1ll << nguess, fit, ((1ll << 31) - 65) / x.rows });
+}
+
+int gf2bv_xl3_guess_chunk_device(int64_t m, int64_t n_lin, int64_t nguess, int device, int64_t *chunk)
+{
+	return catching([&]() -> int {
+	if (!chunk) return fail(GF2BV_ERR_ARG, "null pointer");
+	*chunk = 0;
+	if (gf2bv_xl3_guess_chunk(m, n_lin, nguess, 0) < 0) return fail(GF2BV_ERR_ARG, "m, n_lin or nguess out of range");
+	int rc = check_device(device);
+	if (rc) return rc;
+	HIPCHK(hipSetDevice(device));
+	size_t free_b = 0, total_b = 0;
+	HIPCHK(hipMemGetInfo(&free_b, &total_b));
+	// (what the pool holds idle is handed out again before the device is asked for more)
+	*chunk = gf2bv_xl3_guess_chunk(m, n_lin, nguess, (i64)free_b + std::max<i64>(0, gf2bv_pool_idle_bytes(device)));
+	return GF2BV_OK;
 	});
 }
 

@@ -39,6 +39,8 @@ EXPORTS = [
     "gf2bv_factor_quad_terms", "gf2bv_factor_append_quad_terms", "gf2bv_solve_rhs_quad_terms", "gf2bv_solve_batch_quad_terms",
     "gf2bv_quad_expand_batch_words",
     "gf2bv_xl3_expand_device", "gf2bv_xl3_expand_words", "gf2bv_solve_xl3_words", "gf2bv_solve_xl3_quad_terms",
+    "gf2bv_quad_specialise_device", "gf2bv_quad_specialise_words", "gf2bv_xl3_expand_batch_device", "gf2bv_xl3_expand_batch_words",
+    "gf2bv_solve_xl3_guess_words", "gf2bv_solve_xl3_guess_quad_terms", "gf2bv_xl3_guess_chunk", "gf2bv_xl3_guess_chunk_device",
     "gf2bv_quad_search", "gf2bv_quad_search_alloc", "gf2bv_quad_free", "gf2bv_quad_plan", "gf2bv_quad_points", "gf2bv_quad_forms_search", "gf2bv_quad_last_times",
     "gf2bv_slab_work_words", "gf2bv_slab_tiles", "gf2bv_slab_open", "gf2bv_slab_blocks", "gf2bv_slab_owner",
     "gf2bv_slab_payload_bytes", "gf2bv_slab_factor", "gf2bv_slab_apply", "gf2bv_slab_factor_on", "gf2bv_slab_apply_on",
@@ -151,6 +153,15 @@ def lib():
         L.gf2bv_xl3_expand_words.argtypes = [vp, i64, i64, i64, i64, vp, i64, i32]
         L.gf2bv_solve_xl3_words.argtypes = [vp, i64, i64, i64, i32, i32, pp]
         L.gf2bv_solve_xl3_quad_terms.argtypes = [vp, vp, vp, vp, i64, i64, i32, i32, pp]
+        L.gf2bv_quad_specialise_device.argtypes = [vp, i64, i64, i64, vp, i64, i64, i64, vp, i64, i64, i32, vp]
+        L.gf2bv_quad_specialise_words.argtypes = [vp, i64, i64, i64, vp, i64, i64, i64, vp, i64, i32]
+        L.gf2bv_xl3_expand_batch_device.argtypes = [vp, i64, i64, i64, i64, i64, i64, vp, i64, i64, i32, vp]
+        L.gf2bv_xl3_expand_batch_words.argtypes = [vp, i64, i64, i64, i64, i64, i64, vp, i64, i64, i32]
+        L.gf2bv_solve_xl3_guess_words.argtypes = [vp, i64, i64, i64, vp, i64, i64, i64, i32, i32, pp]
+        L.gf2bv_solve_xl3_guess_quad_terms.argtypes = [vp, vp, vp, vp, i64, i64, vp, i64, i64, i64, i32, i32, pp]
+        L.gf2bv_xl3_guess_chunk.argtypes = [i64, i64, i64, i64]
+        L.gf2bv_xl3_guess_chunk.restype = i64
+        L.gf2bv_xl3_guess_chunk_device.argtypes = [i64, i64, i64, i32, ctypes.POINTER(i64)]
         L.gf2bv_slab_work_words.argtypes = [i64, i64]
         L.gf2bv_slab_work_words.restype = i64
         L.gf2bv_slab_tiles.argtypes = [i64]
@@ -755,6 +766,102 @@ def solve_xl3_quad_terms(lin, term_off, ta, tb, n_lin: int, mode: int = MODE_SIN
     h = ctypes.c_void_p()
     _check(lib().gf2bv_solve_xl3_quad_terms(*_ptrs(lin, term_off, ta, tb), len(lin), n_lin, mode, device, ctypes.byref(h)))
     return _take(h, mode)
+
+
+# -- hybrid XL: guessed unknowns, every assignment's system in one batch (gf2bv_hip.h, "hybrid XL") ---------------------------------------
+def _guess(guess) -> np.ndarray:
+    return np.ascontiguousarray(guess, dtype=np.int32).reshape(-1)
+
+
+def _assignments(guess: np.ndarray, a0: int, na: int | None) -> int:
+    return max((1 << len(guess)) - a0, 0) if na is None else na
+
+
+def quad_specialise_words(quad, n_lin: int, guess, a0: int = 0, na: int | None = None, stride_words: int | None = None,
+                          device: int = 0) -> np.ndarray:
+    """The guessed unknowns substituted into m quadratic rows on the device (gf2bv_quad_specialise_words): [na, m, stride_words]
+    uint64, element s the rows of assignment a0 + s (bit t of it is the value of unknown guess[t]) over the n_lin - len(guess)
+    remaining unknowns.  na defaults to every assignment from a0 on."""
+    quad, guess = _quad_rows(quad), _guess(guess)
+    na = _assignments(guess, a0, na)
+    stride = (quad_cols(n_lin - len(guess)) + 1 + 63) // 64 if stride_words is None else stride_words
+    out = np.empty((max(na, 0), len(quad), max(stride, 0)), dtype=np.uint64)
+    _check(lib().gf2bv_quad_specialise_words(quad.ctypes.data, len(quad), quad.shape[1], n_lin, guess.ctypes.data, len(guess), a0, na,
+                                             out.ctypes.data, stride, device))
+    return out
+
+
+def quad_specialise_device(d_quad: int, m: int, quad_stride: int, n_lin: int, guess, a0: int, na: int, d_out: int, out_stride: int,
+                           sys_stride: int, device: int = 0, stream: int = 0) -> None:
+    """quad_specialise_words with the rows resident in device memory (the guess stays a host array): system s at
+    d_out + s * sys_stride words; the kernel is enqueued on `stream` and the call returns."""
+    guess = _guess(guess)
+    _check(lib().gf2bv_quad_specialise_device(d_quad, m, quad_stride, n_lin, guess.ctypes.data, len(guess), a0, na, d_out, out_stride,
+                                              sys_stride, device, stream or None))
+
+
+def xl3_expand_batch_words(quads, n_lin: int, rows: int | None = None, stride_words: int | None = None, sys_stride_words: int | None = None,
+                           device: int = 0) -> np.ndarray:
+    """The degree-3 XL expansion of nsys systems in one launch (gf2bv_xl3_expand_batch_words): `quads` is [nsys, m, quad_stride]
+    uint64; the result is [nsys, sys_stride_words] uint64, system s its `rows` rows stride_words apart from word 0 of element s
+    (what xl3_expand_words gives for quads[s]) and the words behind them as numpy left them."""
+    quads = np.ascontiguousarray(quads, dtype=np.uint64)
+    if quads.ndim != 3:
+        raise ValueError("the systems must be a 3-D uint64 array: system, equation, word")
+    nsys, m, qs = quads.shape
+    rows = m * (n_lin + 1) if rows is None else rows
+    stride = (xl3_cols(n_lin) + 1 + 63) // 64 if stride_words is None else stride_words
+    sys_stride = rows * stride if sys_stride_words is None else sys_stride_words
+    out = np.zeros((nsys, max(sys_stride, 0)), dtype=np.uint64)
+    _check(lib().gf2bv_xl3_expand_batch_words(quads.ctypes.data, nsys, m * qs, m, qs, n_lin, rows, out.ctypes.data, stride, sys_stride,
+                                              device))
+    return out
+
+
+def xl3_expand_batch_device(d_quad: int, nsys: int, quad_sys_stride: int, m: int, quad_stride: int, n_lin: int, rows: int, d_aug: int,
+                            stride: int, sys_stride: int, device: int = 0, stream: int = 0) -> None:
+    """xl3_expand_batch_words with everything resident in device memory: enqueued on `stream`, the call returns; a
+    solve_batch_device with the same stream reads the finished systems."""
+    _check(lib().gf2bv_xl3_expand_batch_device(d_quad, nsys, quad_sys_stride, m, quad_stride, n_lin, rows, d_aug, stride, sys_stride,
+                                               device, stream or None))
+
+
+def solve_xl3_guess_words(quad, n_lin: int, guess, a0: int = 0, na: int | None = None, mode: int = MODE_SINGLE, device: int = 0) -> list:
+    """Hybrid XL (gf2bv_solve_xl3_guess_words): the quadratic rows uploaded, specialised for the assignments a0 .. a0 + na - 1 of the
+    guessed unknowns, every assignment's rows multiplied and all systems solved as lock-step gangs.  Element s is what
+    solve_xl3_words returns for quad_specialise_words(...)[s] over n_lin - len(guess) unknowns."""
+    quad, guess = _quad_rows(quad), _guess(guess)
+    na = _assignments(guess, a0, na)
+    hs = _handles(na)
+    rc = lib().gf2bv_solve_xl3_guess_words(quad.ctypes.data, len(quad), quad.shape[1], n_lin, guess.ctypes.data, len(guess), a0, na,
+                                           mode, device, hs)
+    return _take_all(hs, max(na, 0), rc, mode)
+
+
+def solve_xl3_guess_quad_terms(lin, term_off, ta, tb, n_lin: int, guess, a0: int = 0, na: int | None = None, mode: int = MODE_SINGLE,
+                               device: int = 0) -> list:
+    """solve_xl3_guess_words on a factored system: expanded on the device first (gf2bv_solve_xl3_guess_quad_terms)."""
+    lin, term_off, ta, tb = _quad_terms(lin, term_off, ta, tb, n_lin)
+    guess = _guess(guess)
+    na = _assignments(guess, a0, na)
+    hs = _handles(na)
+    rc = lib().gf2bv_solve_xl3_guess_quad_terms(*_ptrs(lin, term_off, ta, tb), len(lin), n_lin, guess.ctypes.data, len(guess), a0, na,
+                                                mode, device, hs)
+    return _take_all(hs, max(na, 0), rc, mode)
+
+
+def xl3_guess_chunk(m: int, n_lin: int, nguess: int, free_bytes: int | None = None, device: int = 0) -> int:
+    """How many assignments one solve_xl3_guess_* call should take: the largest count (at most 2^nguess) whose specialised rows and
+    expansions fit a quarter of free_bytes; 0 when one system does not fit.  free_bytes None: the free memory of `device`
+    (gf2bv_xl3_guess_chunk_device); given: a pure function, no device is touched (gf2bv_xl3_guess_chunk)."""
+    if free_bytes is None:
+        chunk = ctypes.c_int64()
+        _check(lib().gf2bv_xl3_guess_chunk_device(m, n_lin, nguess, device, ctypes.byref(chunk)))
+        return int(chunk.value)
+    chunk = int(lib().gf2bv_xl3_guess_chunk(m, n_lin, nguess, free_bytes))
+    if chunk < 0:
+        raise ValueError("m, n_lin, nguess or free_bytes out of range")
+    return chunk
 
 
 def synth_device(d_ptr: int, rows: int, cols: int, stride: int, seed: int, device: int = 0, stream: int = 0):

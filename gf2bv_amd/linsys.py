@@ -9,7 +9,7 @@ from __future__ import annotations
 
 from typing import Iterable, Optional, Sequence, Union
 
-from ._internal import (AffineSpace, QuadSearchGaveUp, eqs_to_sage_mat_helper, m4ri_solve, m4ri_solve_many, m4ri_solve_rhs, m4ri_solve_xl3,
+from ._internal import (AffineSpace, QuadSearchGaveUp, eqs_to_sage_mat_helper, m4ri_solve, m4ri_solve_many, m4ri_solve_rhs, m4ri_solve_xl3, m4ri_solve_xl3_guess,
                         mul_bit_quad)
 from .bitvec import BitVec
 
@@ -348,29 +348,35 @@ class _QuadraticPoints:
     def solve_raw_space_xl(self, zeros: Zeros):
         return self._solve_internal_xl(zeros, 1)
 
-    def _xl_index(self):
-        """(bit position of every coordinate's members) index arrays of the pair and the triple columns, built once per system"""
-        idx = getattr(self, "_xl_index_cache", None)
+    def _xl_index(self, n: Optional[int] = None):
+        """(bit position of every coordinate's members) index arrays of the pair and the triple columns over n unknowns (default: the
+        system's), built once per n"""
+        n = self._lin_size if n is None else n
+        cache = self.__dict__.setdefault("_xl_index_cache", {})
+        idx = cache.get(n)
         if idx is None:
             import numpy as np                         # noqa: PLC0415  (first use only: the package imports without numpy)
-            n = self._lin_size
             pi, pj = np.tril_indices(n, -1)            # (1,0) (2,0) (2,1) ...: pair (i, j) at i(i-1)/2 + j
             a = np.arange(n)
             ti, tj, tl = np.nonzero((a[:, None, None] > a[None, :, None]) & (a[None, :, None] > a[None, None, :]))      # i, then j, then l
-            idx = self._xl_index_cache = (pi, pj, ti, tj, tl)
+            idx = cache[n] = (pi, pj, ti, tj, tl)
         return idx
+
+    def _xl_products_match(self, s: int, n: int) -> bool:
+        """every pair and triple coordinate of a raw point over the cubic columns of n unknowns is the product of its linear bits"""
+        import numpy as np                             # noqa: PLC0415
+        cols3 = xl3_cols(n)
+        assert s >> cols3 == 0, "Invalid solution"
+        bits = np.unpackbits(np.frombuffer(s.to_bytes((cols3 + 7) // 8, "little"), dtype=np.uint8), bitorder="little")[:cols3]
+        pi, pj, ti, tj, tl = self._xl_index(n)
+        lin, pairs, triples = bits[:n], bits[n:n + len(pi)], bits[n + len(pi):]
+        return bool(np.array_equal(pairs, lin[pi] & lin[pj]) and np.array_equal(triples, lin[ti] & lin[tj] & lin[tl]))
 
     def convert_sol_xl(self, s: int) -> Optional[tuple]:
         """the linear parts of a raw point over the cubic columns when every pair and triple coordinate is the product of its linear
         bits, None otherwise"""
-        import numpy as np                             # noqa: PLC0415
         n = self._lin_size
-        cols3 = xl3_cols(n)
-        assert s >> cols3 == 0, "Invalid solution"
-        bits = np.unpackbits(np.frombuffer(s.to_bytes((cols3 + 7) // 8, "little"), dtype=np.uint8), bitorder="little")[:cols3]
-        pi, pj, ti, tj, tl = self._xl_index()
-        lin, pairs, triples = bits[:n], bits[n:n + len(pi)], bits[n + len(pi):]
-        if not (np.array_equal(pairs, lin[pi] & lin[pj]) and np.array_equal(triples, lin[ti] & lin[tj] & lin[tl])):
+        if not self._xl_products_match(s, n):
             return None
         return self._convert_sol(s & ((1 << n) - 1))[:-1]
 
@@ -394,6 +400,110 @@ class _QuadraticPoints:
     def solve_one_xl(self, zeros: Zeros, *, degree: int = 3):
         self._check_degree(degree)
         for sol in self.solve_all_xl(zeros):
+            return sol
+        return None
+
+    # -- hybrid XL (no counterpart in the reference) -------------------------------------------------------------
+    # With fewer equations than degree-3 XL needs, f unknowns are fixed in all 2^f ways: assignment a sets unknown guess[t] to bit t of
+    # a and leaves a quadratic system in the other n - f unknowns (renumbered in increasing index), which needs about (n - f)^2 / 6
+    # equations.  The device substitutes, multiplies and solves every assignment's system as one batch.  The class mixed into supplies
+    # _solve_internal_xl_guess(zeros, guess, mode) -> None (every assignment inconsistent) or (number of equations, run) with
+    # run(first, count) the list of raw results of the assignments first .. first + count - 1.
+    def _parse_guess(self, guess) -> list:
+        """the flattened unknown index of every item: an int, or a one-bit BitVec / PackedBitVec that is exactly one unknown"""
+        n = self._lin_size
+        out = []
+        for item in guess:
+            if isinstance(item, BitVec):
+                bits = item._bits
+                v = bits[0] if len(bits) == 1 else 0
+                if v < 2 or v & (v - 1) or v.bit_length() - 2 >= n:
+                    raise ValueError("a guessed bit must be exactly one unknown")
+                idx = v.bit_length() - 2
+            elif isinstance(item, int) and not isinstance(item, bool):
+                idx = item
+            else:
+                raise ValueError("a guess is an unknown index or a one-bit BitVec")
+            if not 0 <= idx < n:
+                raise ValueError(f"guessed unknown {idx} is not in 0..{n - 1}")
+            if idx in out:
+                raise ValueError(f"unknown {idx} is guessed twice")
+            out.append(idx)
+        if len(out) > min(n - 1, 30):
+            raise ValueError(f"at most min(n - 1, 30) = {min(n - 1, 30)} unknowns can be guessed, not {len(out)}")
+        return out
+
+    def _xl_guess_chunks(self, zeros: Zeros, guess, assignments, mode: int):
+        """(first assignment, raw results) chunk by chunk, the next chunk solved only when it is asked for"""
+        g = self._parse_guess(guess)
+        first, count = (0, 1 << len(g)) if assignments is None else assignments
+        if first < 0 or count < 0 or first + count > 1 << len(g):
+            raise ValueError(f"assignments must be a range (first, count) inside 0..{(1 << len(g)) - 1}")
+        staged = self._solve_internal_xl_guess(zeros, g, mode)
+        if staged is None:
+            yield first, [None] * count
+            return
+        m, run = staged
+        from . import hip                              # noqa: PLC0415  (ctypes binding, first use only)
+        chunk = hip.xl3_guess_chunk(m, self._lin_size, len(g))
+        if chunk < 1:
+            raise MemoryError("one assignment's degree-3 XL system does not fit a quarter of the free device memory")
+        end = first + count
+        while first < end:
+            na = min(chunk, end - first)
+            yield first, run(first, na)
+            first += na
+
+    def solve_raw_one_xl_guess(self, zeros: Zeros, guess, assignments=None) -> list:
+        """one particular solution (or None) per assignment, over the cubic columns of the remaining unknowns"""
+        return [raw for _, raws in self._xl_guess_chunks(zeros, guess, assignments, 0) for raw in raws]
+
+    def solve_raw_space_xl_guess(self, zeros: Zeros, guess, assignments=None) -> list:
+        """one AffineSpace (or None) per assignment -- `assignments` = (first, count), default all 2^f -- over the cubic columns of the
+        remaining unknowns"""
+        return [raw for _, raws in self._xl_guess_chunks(zeros, guess, assignments, 1) for raw in raws]
+
+    def convert_sol_xl_guess(self, raw: int, guess, assignment: int) -> Optional[tuple]:
+        """convert_sol_xl of a raw point of assignment `assignment`'s system: the check over the remaining unknowns, then their bits
+        and the guessed ones scattered into the solution; None when a product coordinate disagrees"""
+        g = self._parse_guess(guess)
+        return self._scatter_guess(raw, g, assignment)
+
+    def _scatter_guess(self, raw: int, g: list, assignment: int) -> Optional[tuple]:
+        n = self._lin_size
+        ns = n - len(g)
+        if not self._xl_products_match(raw, ns):
+            return None
+        full = 0
+        for t, idx in enumerate(g):
+            full |= ((assignment >> t) & 1) << idx
+        rest = [u for u in range(n) if u not in g]
+        for k, u in enumerate(rest):
+            full |= ((raw >> k) & 1) << u
+        return self._convert_sol(full)[:-1]
+
+    def solve_all_xl_guess(self, zeros: Zeros, guess, *, degree: int = 3, max_dimension: int = 16, assignments=None):
+        """the consistent points of every assignment's degree-3 XL system, in assignment order and within an assignment in AffineSpace
+        order; the assignments are solved a chunk at a time (hip.xl3_guess_chunk), the next chunk when more is asked for"""
+        self._check_degree(degree)
+        g = self._parse_guess(guess)
+        for first, spaces in self._xl_guess_chunks(zeros, g, assignments, 1):
+            for k, space in enumerate(spaces):
+                if space is None:
+                    continue
+                if space.dimension > max_dimension:
+                    raise DimensionTooLargeError(
+                        f"Solution space of assignment {first + k} (dim {space.dimension}) is too large, try increase max_dimension "
+                        f"({max_dimension}) or guess more unknowns (there will be 2**dim solutions)",
+                        space=space,
+                    )
+                for raw in space:
+                    sol = self._scatter_guess(raw, g, first + k)
+                    if sol is not None:
+                        yield sol
+
+    def solve_one_xl_guess(self, zeros: Zeros, guess, *, degree: int = 3, max_dimension: int = 16):
+        for sol in self.solve_all_xl_guess(zeros, guess, degree=degree, max_dimension=max_dimension):
             return sol
         return None
 
@@ -487,6 +597,12 @@ class QuadraticSystem(_QuadraticPoints, LinearSystem):
         if 1 in eqs:                            # the equation "1 = 0"
             return None
         return m4ri_solve_xl3(eqs, self._lin_size, mode)
+
+    def _solve_internal_xl_guess(self, zeros: Zeros, guess: list, mode: int):
+        eqs = self.get_eqs(zeros)
+        if 1 in eqs:                            # the equation "1 = 0": under every assignment
+            return None
+        return len(eqs), lambda first, count: m4ri_solve_xl3_guess(eqs, self._lin_size, guess, first, count, mode)
 
     def get_eqs_xl(self, zeros: Zeros) -> list:
         """the equations and their products with every unknown as equation ints over the cubic columns (needs the GPU and numpy)"""

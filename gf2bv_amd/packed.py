@@ -21,7 +21,8 @@ from typing import Iterable, Optional, Sequence
 
 import numpy as np
 
-from ._internal import m4ri_solve_many_quad_packed, m4ri_solve_packed, m4ri_solve_quad_packed, m4ri_solve_xl3_quad_packed
+from ._internal import (m4ri_solve_many_quad_packed, m4ri_solve_packed, m4ri_solve_quad_packed, m4ri_solve_xl3_guess_quad_packed,
+                        m4ri_solve_xl3_quad_packed)
 from .bitvec import BitVec
 from .linsys import DimensionTooLargeError, _QuadraticPoints
 
@@ -550,6 +551,10 @@ class PackedQuadraticSystem(_QuadraticPoints, PackedLinearSystem):
     def _solve_internal_xl(self, zeros: Sequence, mode: int):
         lin, off, ta, tb = self._terms(zeros)
         return m4ri_solve_xl3_quad_packed(lin, off, ta, tb, self._lin_size, mode)
+
+    def _solve_internal_xl_guess(self, zeros: Sequence, guess: list, mode: int):
+        lin, off, ta, tb = self._terms(zeros)
+        return len(lin), lambda first, count: m4ri_solve_xl3_guess_quad_packed(lin, off, ta, tb, self._lin_size, guess, first, count, mode)
 
     def get_eqs_xl(self, zeros: Sequence) -> list:
         """the equations and their products with every unknown as equation ints over the cubic columns (needs the GPU)"""

@@ -430,6 +430,62 @@ int gf2bv_solve_xl3_words(const uint64_t *quad, int64_t m, int64_t quad_stride_w
 int gf2bv_solve_xl3_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t m,
                                int64_t n_lin, int mode, int device, gf2bv_result **out);
 
+/* ---- hybrid XL: guess unknowns, solve every assignment's degree-3 XL system as one batch ------------------------------------
+ * With fewer than about n^2/6 independent quadratic equations degree-3 XL leaves a large space.  Fixing f unknowns in all 2^f ways
+ * leaves 2^f quadratic systems in n' = n_lin - f unknowns with the same m equations each, which need about n'^2/6: independent
+ * systems of one shape, solved as lock-step gangs (gf2bv_solve_batch_device).
+ * Source rows: m quadratic rows over n_lin unknowns in the layout gf2bv_quad_expand_* writes (column c < n_lin unknown c, column
+ * n_lin + i(i-1)/2 + j pair (i, j), j < i, the constant at column cols2).
+ * Guess: nguess distinct unknown indices g_0 .. g_{nguess-1} in the caller's order (a host int32 array in every entry),
+ * 0 <= nguess <= min(n_lin - 1, 30).  Assignment index a sets x_{g_t} to bit t of a.  R is the other unknowns in increasing index,
+ * renumbered 0 .. n'-1.
+ * Specialised row of assignment a: the same layout over n' unknowns, W2' = ceil((cols2' + 1) / 64) words:
+ *   q'(i', j') = q(R[i'], R[j'])                                           (the pair block does not depend on a)
+ *   l'(i')     = l(R[i']) ^ XOR_{t: a_t = 1} q(R[i'], g_t)
+ *   c'         = c ^ XOR_{t: a_t = 1} l(g_t) ^ XOR_{t < u: a_t = a_u = 1} q(g_t, g_u)
+ * A row may become 0 or the constant 1; it stays in and the solver reports the inconsistency.
+ * System of assignment a: the degree-3 XL expansion of its m specialised rows exactly as gf2bv_xl3_expand_* defines it for n',
+ * padded with zero rows to rows' = max(m(n'+1), cols3(n')).
+ * gf2bv_quad_specialise_device (k_quad_specialise): the rows of assignments a0 .. a0 + na - 1; system s = a - a0 gets m rows
+ * out_stride_words apart at d_out + s * sys_stride_words, every bit behind column cols2' written as zero.  out_stride_words >= W2',
+ * sys_stride_words >= m * out_stride_words; 16-byte stores where both strides are even and d_out is 16-byte aligned, 8-byte stores
+ * otherwise.  Enqueued on `stream`, the call returns: the ordering contract of gf2bv_xl3_expand_device.
+ * gf2bv_quad_specialise_words: host pointers; out holds na x m x out_stride_words words.
+ * gf2bv_xl3_expand_batch_device (k_xl3_expand_batch): nsys systems of m quadratic rows each, system s at
+ * d_quad + s * quad_sys_stride_words, expanded to `rows` rows each at d_aug + s * sys_stride_words; d_aug 16-byte aligned,
+ * stride_words and sys_stride_words even, sys_stride_words >= rows * stride_words, quad_sys_stride_words >= m * quad_stride_words.
+ * gf2bv_xl3_expand_batch_words: the same with host pointers (no parity or alignment rule; the words of out_aug between a system's
+ * rows and the next system are left as they are).
+ * gf2bv_solve_xl3_guess_words / _quad_terms: on one pool stream the upload (or the quadratic expansion with no padding), the
+ * specialisation, the batched expansion and gf2bv_solve_batch_device over cols3(n') columns; out[a - a0] is assignment a's result.
+ * Held at once: the quadratic rows, na x m specialised rows and na x rows' expanded rows, plus what the gangs take.  On a non-zero
+ * return every out[s] is NULL.
+ * GF2BV_ERR_ARG, before any device is touched: null pointers, n_lin < 1, nguess < 0 or > min(n_lin - 1, 30), a guess out of range or
+ * repeated, a0 < 0, na < 0, a0 + na > 2^nguess, na * m or na * rows' or nsys * rows >= 2^31 - 64, short strides, the rules of the XL
+ * and batch entries underneath, a source row that does not fit the specialisation kernel's LDS together with its specialised form
+ * and the guess vectors (64 KiB), a bad mode.  GF2BV_ERR_NOMEM: the staging does not fit.
+ * gf2bv_xl3_guess_chunk (pure, no device): the largest count c <= 2^nguess whose specialised rows plus expansions take at most a
+ * quarter of free_bytes (the solver keeps a tile-major copy of about the size of every system it has in a gang: expansion plus copy
+ * stay below half of what was free) and whose rows together stay below 2^31 - 64; 0 when one system does not fit, -1 for a bad
+ * shape.  gf2bv_xl3_guess_chunk_device reads the free memory of `device` (and what the library's pool holds idle there). */
+int gf2bv_quad_specialise_device(const void *d_quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, const int32_t *guess,
+                                 int64_t nguess, int64_t a0, int64_t na, void *d_out, int64_t out_stride_words, int64_t sys_stride_words,
+                                 int device, void *stream);
+int gf2bv_quad_specialise_words(const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, const int32_t *guess,
+                                int64_t nguess, int64_t a0, int64_t na, uint64_t *out, int64_t out_stride_words, int device);
+int gf2bv_xl3_expand_batch_device(const void *d_quad, int64_t nsys, int64_t quad_sys_stride_words, int64_t m, int64_t quad_stride_words,
+                                  int64_t n_lin, int64_t rows, void *d_aug, int64_t stride_words, int64_t sys_stride_words, int device,
+                                  void *stream);
+int gf2bv_xl3_expand_batch_words(const uint64_t *quad, int64_t nsys, int64_t quad_sys_stride_words, int64_t m, int64_t quad_stride_words,
+                                 int64_t n_lin, int64_t rows, uint64_t *out_aug, int64_t stride_words, int64_t sys_stride_words, int device);
+int gf2bv_solve_xl3_guess_words(const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, const int32_t *guess,
+                                int64_t nguess, int64_t a0, int64_t na, int mode, int device, gf2bv_result **out);
+int gf2bv_solve_xl3_guess_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t m,
+                                     int64_t n_lin, const int32_t *guess, int64_t nguess, int64_t a0, int64_t na, int mode, int device,
+                                     gf2bv_result **out);
+int64_t gf2bv_xl3_guess_chunk(int64_t m, int64_t n_lin, int64_t nguess, int64_t free_bytes);
+int gf2bv_xl3_guess_chunk_device(int64_t m, int64_t n_lin, int64_t nguess, int device, int64_t *chunk);
+
 /* ---- synthetic systems + independent residual check (bench / tests) ----------------------- */
 /* word w of row r = mix64(mix64(seed) ^ ((r<<20)|w)); planted solution = pseudo-row 0xFFFFF;
  * RHS = <row, planted>.  Writes rows x stride_words words at d_aug. */
