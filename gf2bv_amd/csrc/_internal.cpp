@@ -1047,6 +1047,8 @@ PyObject *py_m4ri_solve_quad_packed(PyObject *, PyObject *const *args, Py_ssize_
 }
 
 // ---- degree-3 XL: quadratic equations multiplied by 1 and by every unknown on the device (gf2bv_hip.h, "degree-3 XL") --------------
+// (every entry of this section and of the hybrid one is a template over the degree D: m4ri_solve_xl4* are the same code on the xl4
+// entries of the library, over the monomials of degree <= 4 -- gf2bv_hip.h, "degree-4 XL")
 // QuadraticSystem's equation ints of `list` as augmented words over the n_lin = `n_obj` unknowns and their pairs (column c = bit 1 + c,
 // the constant at column cols2), w2 words a row: one pass over the digits
 bool quad_rows_from_ints(PyObject *list, PyObject *n_obj, std::vector<uint64_t> &quad, int64_t *m_out, int64_t *n_out, int64_t *w2_out)
@@ -1083,10 +1085,10 @@ bool quad_rows_from_ints(PyObject *list, PyObject *n_obj, std::vector<uint64_t> 
 // New entry (no counterpart in the reference): `equations` are QuadraticSystem's equation ints (bit 0 the constant, bit 1 + c column
 // c of the n_lin + C(n_lin,2) linearised unknowns; higher bits and the sign ignored).  They are written as augmented words on the
 // host -- one pass over the digits, no PyLong is made -- and gf2bv_solve_xl3_words multiplies, pads and solves them on the device.
-PyObject *py_m4ri_solve_xl3(PyObject *, PyObject *const *args, Py_ssize_t nargs)
+template <int D> PyObject *py_m4ri_solve_xl(PyObject *, PyObject *const *args, Py_ssize_t nargs)
 {
 	int device;
-	if (!entry_device("m4ri_solve_xl3", 3, args, nargs, &device)) return nullptr;
+	if (!entry_device(D == 4 ? "m4ri_solve_xl4" : "m4ri_solve_xl3", 3, args, nargs, &device)) return nullptr;
 	long mode;
 	if (!parse_mode(args[2], &mode)) return nullptr;
 	std::vector<uint64_t> quad;
@@ -1095,7 +1097,7 @@ PyObject *py_m4ri_solve_xl3(PyObject *, PyObject *const *args, Py_ssize_t nargs)
 	gf2bv_result *res = nullptr;
 	int rc;
 	Py_BEGIN_ALLOW_THREADS
-	rc = gf2bv_solve_xl3_words(quad.data(), m, w2, n, (int)mode, device, &res);
+	rc = (D == 4 ? gf2bv_solve_xl4_words : gf2bv_solve_xl3_words)(quad.data(), m, w2, n, (int)mode, device, &res);
 	Py_END_ALLOW_THREADS
 	if (rc != GF2BV_OK) return raise_rc(rc, "solve");
 	return result_to_py(res, mode, device);
@@ -1103,17 +1105,17 @@ PyObject *py_m4ri_solve_xl3(PyObject *, PyObject *const *args, Py_ssize_t nargs)
 
 // m4ri_solve_xl3_quad_packed(lin, term_off, ta, tb, n_lin, mode[, device]) -> None | int | AffineSpace: m4ri_solve_quad_packed's
 // arrays (every row live), expanded, multiplied, padded and solved on the device (gf2bv_solve_xl3_quad_terms)
-PyObject *py_m4ri_solve_xl3_quad_packed(PyObject *, PyObject *const *args, Py_ssize_t nargs)
+template <int D> PyObject *py_m4ri_solve_xl_quad_packed(PyObject *, PyObject *const *args, Py_ssize_t nargs)
 {
 	int device;
-	if (!entry_device("m4ri_solve_xl3_quad_packed", 6, args, nargs, &device)) return nullptr;
+	if (!entry_device(D == 4 ? "m4ri_solve_xl4_quad_packed" : "m4ri_solve_xl3_quad_packed", 6, args, nargs, &device)) return nullptr;
 	long mode;
 	QuadBuffers qb;
 	if (!parse_mode(args[5], &mode) || !qb.parse(args, args[4])) return nullptr;
 	gf2bv_result *res = nullptr;
 	int rc;
 	Py_BEGIN_ALLOW_THREADS
-	rc = gf2bv_solve_xl3_quad_terms(qb.lin, qb.off, qb.ta, qb.tb, qb.live, qb.n, (int)mode, device, &res);
+	rc = (D == 4 ? gf2bv_solve_xl4_quad_terms : gf2bv_solve_xl3_quad_terms)(qb.lin, qb.off, qb.ta, qb.tb, qb.live, qb.n, (int)mode, device, &res);
 	Py_END_ALLOW_THREADS
 	if (rc != GF2BV_OK) return raise_rc(rc, "solve");
 	return result_to_py(res, mode, device);
@@ -1151,10 +1153,10 @@ struct GuessArgs {
 // the n_lin - len(guess) remaining unknowns, element s for assignment a0 + s (bit t of it the value of unknown guess[t]).
 // New entry (no counterpart in the reference): the equation ints are written as augmented words in one pass, as m4ri_solve_xl3 does,
 // and gf2bv_solve_xl3_guess_words substitutes, multiplies, pads and solves every assignment's system on the device as one batch.
-PyObject *py_m4ri_solve_xl3_guess(PyObject *, PyObject *const *args, Py_ssize_t nargs)
+template <int D> PyObject *py_m4ri_solve_xl_guess(PyObject *, PyObject *const *args, Py_ssize_t nargs)
 {
 	int device;
-	if (!entry_device("m4ri_solve_xl3_guess", 6, args, nargs, &device)) return nullptr;
+	if (!entry_device(D == 4 ? "m4ri_solve_xl4_guess" : "m4ri_solve_xl3_guess", 6, args, nargs, &device)) return nullptr;
 	long mode;
 	GuessArgs ga;
 	if (!parse_mode(args[5], &mode) || !ga.parse(args[2], args[3], args[4])) return nullptr;
@@ -1163,24 +1165,24 @@ PyObject *py_m4ri_solve_xl3_guess(PyObject *, PyObject *const *args, Py_ssize_t 
 	if (!quad_rows_from_ints(args[0], args[1], quad, &m, &n, &w2)) return nullptr;
 	if (ga.na == 0) return PyList_New(0);
 	return collect_results(ga.na, mode, device, [&](gf2bv_result **out) {
-		return gf2bv_solve_xl3_guess_words(quad.data(), m, w2, n, ga.g.data(), (int64_t)ga.g.size(), ga.a0, ga.na, (int)mode, device, out);
+		return (D == 4 ? gf2bv_solve_xl4_guess_words : gf2bv_solve_xl3_guess_words)(quad.data(), m, w2, n, ga.g.data(), (int64_t)ga.g.size(), ga.a0, ga.na, (int)mode, device, out);
 	});
 }
 
 // m4ri_solve_xl3_guess_quad_packed(lin, term_off, ta, tb, n_lin, guess, a0, na, mode[, device]) -> list: m4ri_solve_xl3_guess on
 // m4ri_solve_quad_packed's arrays (every row live), expanded on the device first (gf2bv_solve_xl3_guess_quad_terms)
-PyObject *py_m4ri_solve_xl3_guess_quad_packed(PyObject *, PyObject *const *args, Py_ssize_t nargs)
+template <int D> PyObject *py_m4ri_solve_xl_guess_quad_packed(PyObject *, PyObject *const *args, Py_ssize_t nargs)
 {
 	int device;
-	if (!entry_device("m4ri_solve_xl3_guess_quad_packed", 9, args, nargs, &device)) return nullptr;
+	if (!entry_device(D == 4 ? "m4ri_solve_xl4_guess_quad_packed" : "m4ri_solve_xl3_guess_quad_packed", 9, args, nargs, &device)) return nullptr;
 	long mode;
 	GuessArgs ga;
 	QuadBuffers qb;
 	if (!parse_mode(args[8], &mode) || !ga.parse(args[5], args[6], args[7]) || !qb.parse(args, args[4])) return nullptr;
 	if (ga.na == 0) return PyList_New(0);
 	return collect_results(ga.na, mode, device, [&](gf2bv_result **out) {
-		return gf2bv_solve_xl3_guess_quad_terms(qb.lin, qb.off, qb.ta, qb.tb, qb.live, qb.n, ga.g.data(), (int64_t)ga.g.size(), ga.a0, ga.na,
-		                                        (int)mode, device, out);
+		return (D == 4 ? gf2bv_solve_xl4_guess_quad_terms : gf2bv_solve_xl3_guess_quad_terms)(qb.lin, qb.off, qb.ta, qb.tb, qb.live, qb.n, ga.g.data(),
+		                                                                                     (int64_t)ga.g.size(), ga.a0, ga.na, (int)mode, device, out);
 	});
 }
 
@@ -1787,14 +1789,22 @@ PyMethodDef module_methods[] = {
 	 "m4ri_solve_packed(buffer, rows, words, cols, mode, device=None)\n--\n\nm4ri_solve on equations already packed as rows x words 64-bit words (equation-int bit order)."},
 	{"m4ri_solve_quad_packed", FAST(py_m4ri_solve_quad_packed), METH_FASTCALL,
 	 "m4ri_solve_quad_packed(lin, term_off, ta, tb, n_lin, rows, mode, device=None)\n--\n\nm4ri_solve on a quadratic system kept factored (linear forms and products of two linear forms, packed 64-bit words): expanded into the linearised matrix on the GPU."},
-	{"m4ri_solve_xl3", FAST(py_m4ri_solve_xl3), METH_FASTCALL,
+	{"m4ri_solve_xl3", FAST(py_m4ri_solve_xl<3>), METH_FASTCALL,
 	 "m4ri_solve_xl3(equations, n_lin, mode, device=None)\n--\n\nDegree-3 XL: QuadraticSystem equation ints multiplied by 1 and by every unknown on the GPU and solved over the monomials of degree <= 3."},
-	{"m4ri_solve_xl3_quad_packed", FAST(py_m4ri_solve_xl3_quad_packed), METH_FASTCALL,
+	{"m4ri_solve_xl3_quad_packed", FAST(py_m4ri_solve_xl_quad_packed<3>), METH_FASTCALL,
 	 "m4ri_solve_xl3_quad_packed(lin, term_off, ta, tb, n_lin, mode, device=None)\n--\n\nm4ri_solve_xl3 on a quadratic system kept factored: expanded, multiplied and solved on the GPU."},
-	{"m4ri_solve_xl3_guess", FAST(py_m4ri_solve_xl3_guess), METH_FASTCALL,
+	{"m4ri_solve_xl3_guess", FAST(py_m4ri_solve_xl_guess<3>), METH_FASTCALL,
 	 "m4ri_solve_xl3_guess(equations, n_lin, guess, a0, na, mode, device=None)\n--\n\nHybrid XL: the guessed unknowns substituted for the assignments a0 .. a0 + na - 1 and every assignment's degree-3 XL system solved on the GPU as one batch."},
-	{"m4ri_solve_xl3_guess_quad_packed", FAST(py_m4ri_solve_xl3_guess_quad_packed), METH_FASTCALL,
+	{"m4ri_solve_xl3_guess_quad_packed", FAST(py_m4ri_solve_xl_guess_quad_packed<3>), METH_FASTCALL,
 	 "m4ri_solve_xl3_guess_quad_packed(lin, term_off, ta, tb, n_lin, guess, a0, na, mode, device=None)\n--\n\nm4ri_solve_xl3_guess on a quadratic system kept factored."},
+	{"m4ri_solve_xl4", FAST(py_m4ri_solve_xl<4>), METH_FASTCALL,
+	 "m4ri_solve_xl4(equations, n_lin, mode, device=None)\n--\n\nDegree-4 XL: m4ri_solve_xl3 with the products by every pair of unknowns too, solved over the monomials of degree <= 4."},
+	{"m4ri_solve_xl4_quad_packed", FAST(py_m4ri_solve_xl_quad_packed<4>), METH_FASTCALL,
+	 "m4ri_solve_xl4_quad_packed(lin, term_off, ta, tb, n_lin, mode, device=None)\n--\n\nm4ri_solve_xl4 on a quadratic system kept factored."},
+	{"m4ri_solve_xl4_guess", FAST(py_m4ri_solve_xl_guess<4>), METH_FASTCALL,
+	 "m4ri_solve_xl4_guess(equations, n_lin, guess, a0, na, mode, device=None)\n--\n\nHybrid XL at degree 4: m4ri_solve_xl3_guess with every assignment's degree-4 XL system."},
+	{"m4ri_solve_xl4_guess_quad_packed", FAST(py_m4ri_solve_xl_guess_quad_packed<4>), METH_FASTCALL,
+	 "m4ri_solve_xl4_guess_quad_packed(lin, term_off, ta, tb, n_lin, guess, a0, na, mode, device=None)\n--\n\nm4ri_solve_xl4_guess on a quadratic system kept factored."},
 	{"m4ri_solve_rhs", FAST(py_m4ri_solve_rhs), METH_FASTCALL,
 	 "m4ri_solve_rhs(equations, cols, mode, rhs, device=None)\n--\n\nSolve one coefficient matrix against every right-hand side in rhs (bit r = affine term of equation r) with one elimination; list of m4ri_solve results."},
 	{"m4ri_factor", FAST(py_m4ri_factor), METH_FASTCALL,

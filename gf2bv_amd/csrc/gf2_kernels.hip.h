@@ -5104,3 +5104,153 @@ k_quad_specialise(const u64 *__restrict__ quad, i64 m, i64 quad_stride, int n, i
 		}
 	}
 }
+
+
+// ==========================================================================================
+// DEGREE-4 XL: every quadratic row, its product with every unknown and with every pair of unknowns, over the monomials of degree <= 4
+// ==========================================================================================
+// (host side: gf2bv_xl4_expand_device in gf2_solver.hip)
+//
+// Source: as for degree 3.  Output: cols4 = cols3 + C(n,4) columns, the first cols3 exactly degree 3's, quadruple (i, j, l, p),
+// p < l < j < i, at cols3 + C(i,4) + C(j,3) + C(l,2) + p, the constant at cols4.  Equation e owns the R4 = 1 + n + C(n,2) rows from
+// e R4: f_e, then x_k f_e for k = 0 .. n-1 (degree 3's words, no quadruple), then x_a x_b f_e, b < a, at offset 1 + n + C(a,2) + b.
+// With S = {a, b}, x_a x_b f has
+//   pair S = c ^ l_a ^ l_b ^ q_ab, triple S + {t} = l_t ^ q_ta ^ q_tb, quadruple S + {t, u} = q_tu, everything else 0.
+// Runs of consecutive columns of x_a x_b f:
+//   triples (i, j, 0..j-1):        (i, j) = (a, b): l[0..b) ^ q(a, 0..b-1) ^ q(b, 0..b-1);  exactly one of i, j is a and b < j: the
+//                                  one bit of the third member t at position b;  else nothing.
+//   quadruples (i, j, l, 0..l-1):  S inside {i, j, l} with third member t: q(t, 0..l-1);  a in {i, j, l} and b < l: the one bit
+//                                  q(other two) at position b;  else nothing.
+// So everything below pair C(a,2) + b, triple C(a,3) and quadruple C(a,4) is zero and the word leaves after a few comparisons; inside
+// a block the runs that hold nothing are skipped in one step each (the jumps below only ever move forward in (i, j, l)).
+// Work split: the rows x_a x_b f with large a are almost all zero, so contiguous spans of rows would give some workgroups nothing
+// but early exits and others every populated word.  A workgroup therefore takes one equation (its row goes to LDS once) and every
+// `parts`-th of that equation's R4 rows: each workgroup sees an even sample of the multipliers.  The zero rows behind m R4 are dealt
+// round-robin.  Stores as in k_xl3_expand: two words a lane, 16 bytes, consecutive lanes consecutive; one writer per word, no atomics.
+// LDS: W2 words (dynamic).
+__host__ __device__ __forceinline__ i64 xl_c4(i64 i) { return i * (i - 1) * (i - 2) * (i - 3) / 24; }
+__host__ __device__ __forceinline__ i64 xl_quart_root(i64 u)                   // the largest i >= 3 with C(i,4) <= u
+{
+	i64 i = (i64)sqrtf(sqrtf(24.0f * (float)u)) + 2;                           // (float: a few units off below 2^31) ...
+	if (i < 3) i = 3;
+	while (xl_c4(i) > u) i--;                                                  // ... made exact in integers
+	while (xl_c4(i + 1) <= u) i++;
+	return i;
+}
+__device__ __forceinline__ i64 xl_q(i64 n, i64 u, i64 v) { return u > v ? n + xl_c2(u) + v : n + xl_c2(v) + u; }      // column of x_u x_v
+
+// columns c0 .. c0 + 63 of the row x_a x_b f, b < a, of the source row `src`
+__device__ __forceinline__ u64 xl4_pair_word(const u64 *src, int W2, i64 n, i64 cols2, i64 cols3, i64 cols4, i64 c0, int a, int b)
+{
+	const i64 pc = n + xl_c2(a) + b;                                           // the pair S: nothing below it
+	if (c0 + 64 <= pc) return 0;
+	u64 acc = 0;
+	if (pc >= c0) acc = (xl_bit(src, cols2) ^ xl_bit(src, a) ^ xl_bit(src, b) ^ xl_bit(src, pc)) << (pc - c0);
+	const i64 t_lo = (c0 > cols2 ? c0 : cols2) - cols2, t_hi = (c0 + 64 < cols3 ? c0 + 64 : cols3) - cols2;      // the word's triple indices
+	if (t_lo < t_hi && t_hi > xl_c3(a)) {
+		i64 i = xl_tet_root(t_lo), j = xl_tri_root(t_lo - xl_c3(i));           // the run t_lo lies in: 1 <= j < i
+		i64 s = xl_c3(i) + xl_c2(j);
+		while (s < t_hi) {                                                     // run (i, j): triples s .. s + j - 1
+			if (i < a) { i = a; j = 1; s = xl_c3(i); continue; }               // (a >= 3 here: nothing below block a)
+			const i64 jn = i == a ? b : a;                                     // the first run of block i that holds anything
+			if (j < jn) { j = jn; s = xl_c3(i) + xl_c2(j); continue; }
+			if (i > a && j > a) { i++; j = 1; s = xl_c3(i); continue; }        // (nothing above the run j = a)
+			const i64 j0 = (t_lo > s ? t_lo : s) - s, j1 = (t_hi < s + j ? t_hi : s + j) - s;
+			if (j0 < j1) {
+				if (i == a && j == b)
+					acc |= ((qx_window(src, W2, j0) ^ qx_window(src, W2, n + xl_c2(a) + j0) ^ qx_window(src, W2, n + xl_c2(b) + j0)) & qx_low(j1 - j0))
+					       << (cols2 + s + j0 - c0);
+				else if (b >= j0 && b < j1) {                                  // (i = a, j > b) or (i > a, j = a): b < j
+					const i64 t = i == a ? j : i;
+					acc |= (xl_bit(src, t) ^ xl_bit(src, xl_q(n, t, a)) ^ xl_bit(src, xl_q(n, t, b))) << (cols2 + s + b - c0);
+				}
+			}
+			s += j;
+			if (++j == i) { i++; j = 1; }
+		}
+	}
+	const i64 u_lo = (c0 > cols3 ? c0 : cols3) - cols3, u_hi = (c0 + 64 < cols4 ? c0 + 64 : cols4) - cols3;      // its quadruple indices
+	if (u_lo < u_hi && u_hi > xl_c4(a)) {
+		i64 i = xl_quart_root(u_lo), j = xl_tet_root(u_lo - xl_c4(i));         // the run u_lo lies in: 1 <= l < j < i
+		i64 l = xl_tri_root(u_lo - xl_c4(i) - xl_c3(j));
+		i64 s = xl_c4(i) + xl_c3(j) + xl_c2(l);
+		while (s < u_hi) {                                                     // run (i, j, l): quadruples s .. s + l - 1
+			bool jump = true;                                                  // to the next run that can hold anything
+			if (i < a) { i = a; j = 2; l = 1; }                                // (a >= 4 here)
+			else if (i == a && j < b) { j = b; l = 1; }                        // i = a: b must be j or l, or lie below l
+			else if (i == a && j > b && l < b) l = b;
+			else if (i > a && j < a) { j = a; l = 1; }                         // i > a: a must be j or l
+			else if (i > a && j == a && l < b) l = b;                          //   j = a: b must be l or lie below it
+			else if (i > a && j > a && l < a) l = a;                           //   j > a: l must be a
+			else if (i > a && j > a && l > a) { l = 1; if (++j == i) { i++; j = 2; } }
+			else jump = false;
+			if (jump) { s = xl_c4(i) + xl_c3(j) + xl_c2(l); continue; }
+			const i64 j0 = (u_lo > s ? u_lo : s) - s, j1 = (u_hi < s + l ? u_hi : s + l) - s;
+			if (j0 < j1) {
+				i64 t = -1;                                                    // S inside {i, j, l}: the third member
+				if (i == a) t = j == b ? l : (l == b ? j : -1);
+				else if (j == a && l == b) t = i;
+				if (t >= 0) acc |= (qx_window(src, W2, n + xl_c2(t) + j0) & qx_low(j1 - j0)) << (cols3 + s + j0 - c0);
+				else if (b >= j0 && b < j1) {                                  // a in {i, j, l}, b < l: q of the other two
+					const i64 hi = i == a ? j : i, lo = l == a ? j : l;
+					acc |= xl_bit(src, n + xl_c2(hi) + lo) << (cols3 + s + b - c0);
+				}
+			}
+			s += l;
+			if (++l == j) { l = 1; if (++j == i) { i++; j = 2; } }
+		}
+	}
+	return acc;
+}
+
+// columns c0 .. c0 + 63 of local row rl of an equation's R4 rows
+__device__ __forceinline__ u64 xl4_word(const u64 *src, int W2, i64 n, i64 cols2, i64 cols3, i64 cols4, i64 c0, int k, int a, int b)
+{
+	if (a >= 0) return xl4_pair_word(src, W2, n, cols2, cols3, cols4, c0, a, b);
+	if (k >= 0) return c0 < cols3 ? xl3_word(src, W2, n, cols2, cols3, c0, k) : 0;      // x_k f: degree 3's word, no quadruple, constant 0
+	u64 acc = c0 < cols2 ? qx_window(src, W2, c0) & qx_low(cols2 - c0) : 0;             // f: its own columns, the constant behind all
+	if (cols4 >= c0 && cols4 < c0 + 64) acc |= xl_bit(src, cols2) << (cols4 - c0);
+	return acc;
+}
+
+// the rows of ONE system (quad its first source row, out its first output row), dealt to the workgroups of grid x
+__device__ __forceinline__ void
+xl4_expand_rows(const u64 *__restrict__ quad, i64 m, i64 quad_stride, int n, int W2, i64 rows, int parts, u64 *__restrict__ out, i64 stride)
+{
+	extern __shared__ u64 xl_lds[];                    // the source row: W2 words
+	const i64 cols2 = (i64)n + xl_c2(n), cols3 = cols2 + xl_c3(n), cols4 = cols3 + xl_c4(n), R4 = 1 + cols2;
+	const i64 npair = stride >> 1;                     // 16-byte pieces of a row (stride is even)
+	for (i64 u = blockIdx.x; u < m * parts; u += gridDim.x) {      // unit u: equation e, its rows part, part + parts, ...
+		const i64 e = u / parts;
+		__syncthreads();                               // the rows before have read theirs
+		for (int w = threadIdx.x; w < W2; w += blockDim.x) xl_lds[w] = quad[e * quad_stride + w];
+		__syncthreads();
+		for (i64 rl = u - e * parts; rl < R4; rl += parts) {
+			int k = -1, a = -1, b = -1;
+			if (rl > n) { a = (int)xl_tri_root(rl - 1 - n); b = (int)(rl - 1 - n - xl_c2(a)); }
+			else k = (int)rl - 1;
+			ulonglong2 *o = reinterpret_cast<ulonglong2 *>(out + (e * R4 + rl) * stride);
+			for (i64 p = threadIdx.x; p < npair; p += blockDim.x)
+				o[p] = make_ulonglong2(xl4_word(xl_lds, W2, n, cols2, cols3, cols4, 128 * p, k, a, b),
+				                       xl4_word(xl_lds, W2, n, cols2, cols3, cols4, 128 * p + 64, k, a, b));
+		}
+	}
+	for (i64 r = m * R4 + blockIdx.x; r < rows; r += gridDim.x) {  // the padding
+		ulonglong2 *o = reinterpret_cast<ulonglong2 *>(out + r * stride);
+		for (i64 p = threadIdx.x; p < npair; p += blockDim.x) o[p] = make_ulonglong2(0, 0);
+	}
+}
+
+__global__ void __launch_bounds__(256)
+k_xl4_expand(const u64 *__restrict__ quad, i64 m, i64 quad_stride, int n, int W2, i64 rows, int parts, u64 *__restrict__ out, i64 stride)
+{
+	xl4_expand_rows(quad, m, quad_stride, n, W2, rows, parts, out, stride);
+}
+
+// The batched instance (gf2bv_xl4_expand_batch_device): blockIdx.y = system, strides and checks as for k_xl3_expand_batch
+__global__ void __launch_bounds__(256)
+k_xl4_expand_batch(const u64 *__restrict__ quad, i64 quad_sys_stride, i64 m, i64 quad_stride, int n, int W2, i64 rows, int parts,
+                   u64 *__restrict__ out, i64 stride, i64 sys_stride)
+{
+	xl4_expand_rows(quad + (i64)blockIdx.y * quad_sys_stride, m, quad_stride, n, W2, rows, parts, out + (i64)blockIdx.y * sys_stride, stride);
+}

@@ -4773,57 +4773,87 @@ int enqueue_quad_expand_batch(const QuadTerms &q, const i64 *d_sys_off, i64 nsys
 	return GF2BV_OK;
 }
 
-// Degree-3 XL (k_xl3_expand): m quadratic rows over n unknowns -- the rows k_quad_expand writes -- become `rows` rows over the
-// monomials of degree <= 3: each equation and its product with every unknown, then zeros
-struct Xl3Shape {
+// XL (k_xl3_expand, k_xl4_expand): m quadratic rows over n unknowns -- the rows k_quad_expand writes -- become `rows` rows over the
+// monomials of degree <= `degree`: each equation, its product with every unknown and (degree 4) with every pair of unknowns, then zeros
+struct XlShape {
 	i64 m = 0, n = 0, rows = 0;
+	int degree = 3;
 	i64 cols2() const { return n + n * (n - 1) / 2; }
 	i64 cols3() const { return cols2() + n * (n - 1) * (n - 2) / 6; }
+	i64 cols4() const { return cols3() + n * (n - 1) * (n - 2) * (n - 3) / 24; }
+	i64 cols() const { return degree == 4 ? cols4() : cols3(); }
+	i64 per_eq() const { return degree == 4 ? 1 + cols2() : n + 1; }      // rows an equation owns
 	i64 w2() const { return (cols2() + 1 + 63) / 64; }         // words of a source row, which the kernel holds in LDS
-	i64 wt() const { return (cols3() + 1 + 63) / 64; }
-	i64 live() const { return m * (n + 1); }
+	i64 wt() const { return (cols() + 1 + 63) / 64; }
+	i64 live() const { return m * per_eq(); }
 };
 constexpr i64 kXl3LdsBytes = 65536;
 
 // The shape, and the source stride against it; no pointer is looked at.  `pad`: a solve entry, whose rows are the live ones padded up
 // to the columns
-int check_xl3(Xl3Shape &x, i64 quad_stride, bool pad = false)
+int check_xl(XlShape &x, i64 quad_stride, bool pad = false)
 {
-	if (x.n < 1 || x.n > 65535 || x.cols3() >= (1ll << 31) - 64)
-		return fail(GF2BV_ERR_ARG, "n_lin must be at least 1 and n_lin + C(n_lin,2) + C(n_lin,3) below 2^31 - 64");
-	if (x.m < 0 || x.m >= (1ll << 31) - 64 || x.live() >= (1ll << 31) - 64) return fail(GF2BV_ERR_ARG, "m(n_lin + 1) must stay below 2^31 - 64");
-	if (pad) x.rows = std::max(x.live(), x.cols3());
-	if (x.rows >= (1ll << 31) - 64 || x.rows < x.live()) return fail(GF2BV_ERR_ARG, "rows must be at least m(n_lin + 1) and below 2^31 - 64");
+	const bool d4 = x.degree == 4;
+	if (x.n < 1 || x.n > 65535 || x.cols() >= (1ll << 31) - 64)
+		return fail(GF2BV_ERR_ARG, d4 ? "n_lin must be at least 1 and n_lin + C(n_lin,2) + C(n_lin,3) + C(n_lin,4) below 2^31 - 64"
+		                              : "n_lin must be at least 1 and n_lin + C(n_lin,2) + C(n_lin,3) below 2^31 - 64");
+	if (x.m < 0 || x.m >= (1ll << 31) - 64 || x.live() >= (1ll << 31) - 64)
+		return fail(GF2BV_ERR_ARG, d4 ? "m(1 + n_lin + C(n_lin,2)) must stay below 2^31 - 64" : "m(n_lin + 1) must stay below 2^31 - 64");
+	if (pad) x.rows = std::max(x.live(), x.cols());
+	if (x.rows >= (1ll << 31) - 64 || x.rows < x.live())
+		return fail(GF2BV_ERR_ARG, d4 ? "rows must be at least m(1 + n_lin + C(n_lin,2)) and below 2^31 - 64"
+		                              : "rows must be at least m(n_lin + 1) and below 2^31 - 64");
 	if (x.w2() * 8 > kXl3LdsBytes) return fail(GF2BV_ERR_ARG, "a quadratic row of this n_lin does not fit the expansion kernel's LDS (64 KiB)");
 	if (quad_stride < x.w2()) return fail(GF2BV_ERR_ARG, "quad_stride_words does not cover the quadratic columns and the constant");
 	return GF2BV_OK;
 }
 
-// (device pointers, already checked) the kernel on `st`: a few thousand workgroups, each a contiguous span of the rows
-int enqueue_xl3_expand(const Xl3Shape &x, const u64 *d_quad, i64 quad_stride, u64 *d_aug, i64 stride, hipStream_t st)
+// Degree 4: the workgroups of one system take (equation, part) units -- every parts-th row of an equation's rows -- a few thousand
+// units over all `nsys` systems where the equations allow it
+int xl4_parts(const XlShape &x, i64 nsys)
+{
+	return (int)std::max<i64>(1, std::min<i64>(x.per_eq(), 4096 / std::max<i64>(x.m * nsys, 1)));
+}
+
+// (device pointers, already checked) the kernel on `st`.  Degree 3: a few thousand workgroups, each a contiguous span of the rows;
+// degree 4: a workgroup per (equation, part) unit
+int enqueue_xl_expand(const XlShape &x, const u64 *d_quad, i64 quad_stride, u64 *d_aug, i64 stride, hipStream_t st)
 {
 	if (x.rows == 0) return GF2BV_OK;
 	const unsigned block = (unsigned)std::min<i64>(256, round_up(std::max<i64>(stride / 2, 1), 64));
-	const unsigned grid = (unsigned)std::min<i64>(x.rows, 256 * 16);
-	hipLaunchKernelGGL(k_xl3_expand, dim3(grid), dim3(block), sizeof(u64) * (size_t)x.w2(), st, d_quad, x.m, quad_stride, (int)x.n,
-	                   (int)x.w2(), x.rows, d_aug, stride);
+	if (x.degree == 4) {
+		const int parts = xl4_parts(x, 1);
+		const unsigned grid = (unsigned)std::min<i64>(std::max<i64>(x.m * parts, std::min<i64>(x.rows - x.live(), 4096)), 1 << 20);
+		hipLaunchKernelGGL(k_xl4_expand, dim3(grid), dim3(block), sizeof(u64) * (size_t)x.w2(), st, d_quad, x.m, quad_stride, (int)x.n,
+		                   (int)x.w2(), x.rows, parts, d_aug, stride);
+	} else {
+		const unsigned grid = (unsigned)std::min<i64>(x.rows, 256 * 16);
+		hipLaunchKernelGGL(k_xl3_expand, dim3(grid), dim3(block), sizeof(u64) * (size_t)x.w2(), st, d_quad, x.m, quad_stride, (int)x.n,
+		                   (int)x.w2(), x.rows, d_aug, stride);
+	}
 	HIPCHK(hipGetLastError());
 	return GF2BV_OK;
 }
 
 // (device pointers, already checked) the batched kernel on `st`: system s reads its x.m rows at d_quad + s x quad_sys_stride and writes
 // x.rows rows at d_aug + s x sys_stride
-int enqueue_xl3_expand_batch(const Xl3Shape &x, const u64 *d_quad, i64 quad_sys_stride, i64 quad_stride, i64 nsys, u64 *d_aug, i64 stride,
-                             i64 sys_stride, hipStream_t st)
+int enqueue_xl_expand_batch(const XlShape &x, const u64 *d_quad, i64 quad_sys_stride, i64 quad_stride, i64 nsys, u64 *d_aug, i64 stride,
+                            i64 sys_stride, hipStream_t st)
 {
 	if (x.rows == 0 || nsys == 0) return GF2BV_OK;
 	const unsigned block = (unsigned)std::min<i64>(256, round_up(std::max<i64>(stride / 2, 1), 64));
-	// contiguous spans of rows per workgroup, a few thousand workgroups in all where the systems are many
-	const unsigned gx = (unsigned)std::min<i64>(x.rows, std::max<i64>(256, 256 * 16 / nsys));
+	// degree 3: contiguous spans of rows per workgroup, a few thousand workgroups in all where the systems are many
+	const int parts = xl4_parts(x, nsys);
+	const unsigned gx = x.degree == 4 ? (unsigned)std::min<i64>(std::max<i64>(x.m * parts, std::min<i64>(x.rows - x.live(), 256)), 1 << 20)
+	                                  : (unsigned)std::min<i64>(x.rows, std::max<i64>(256, 256 * 16 / nsys));
 	for (i64 s0 = 0; s0 < nsys; s0 += 65535) {         // (grid y holds 65535 systems)
 		const unsigned ns = (unsigned)std::min<i64>(65535, nsys - s0);
-		hipLaunchKernelGGL(k_xl3_expand_batch, dim3(gx, ns), dim3(block), sizeof(u64) * (size_t)x.w2(), st, d_quad + s0 * quad_sys_stride,
-		                   quad_sys_stride, x.m, quad_stride, (int)x.n, (int)x.w2(), x.rows, d_aug + s0 * sys_stride, stride, sys_stride);
+		if (x.degree == 4)
+			hipLaunchKernelGGL(k_xl4_expand_batch, dim3(gx, ns), dim3(block), sizeof(u64) * (size_t)x.w2(), st, d_quad + s0 * quad_sys_stride,
+			                   quad_sys_stride, x.m, quad_stride, (int)x.n, (int)x.w2(), x.rows, parts, d_aug + s0 * sys_stride, stride, sys_stride);
+		else
+			hipLaunchKernelGGL(k_xl3_expand_batch, dim3(gx, ns), dim3(block), sizeof(u64) * (size_t)x.w2(), st, d_quad + s0 * quad_sys_stride,
+			                   quad_sys_stride, x.m, quad_stride, (int)x.n, (int)x.w2(), x.rows, d_aug + s0 * sys_stride, stride, sys_stride);
 	}
 	HIPCHK(hipGetLastError());
 	return GF2BV_OK;
@@ -4834,7 +4864,7 @@ int enqueue_xl3_expand_batch(const Xl3Shape &x, const u64 *d_quad, i64 quad_sys_
 struct GuessShape {
 	i64 m = 0, n = 0, f = 0, a0 = 0, na = 0;
 	SpecGuess g{};
-	Xl3Shape x;
+	XlShape x;
 	i64 w2() const { return (n + n * (n - 1) / 2 + 1 + 63) / 64; }
 	i64 lds_bytes() const { return 8 * (w2() + x.w2() + f * ((x.n + 63) / 64 + 2)) + 4 * x.n; }
 };
@@ -4866,10 +4896,10 @@ int check_guess(GuessShape &s, const int32_t *guess, i64 quad_stride)
 // The systems behind a solve entry: each assignment's expansion padded up to its columns, all of them one batch
 int check_guess_solve(GuessShape &s, int mode)
 {
-	int rc = check_xl3(s.x, s.x.w2(), true);
+	int rc = check_xl(s.x, s.x.w2(), true);
 	if (rc) return rc;
 	if (s.na * s.x.rows >= (1ll << 31) - 64) return fail(GF2BV_ERR_ARG, "the rows of all assignments' systems together must stay below 2^31 - 64");
-	return check_shape(s.x.rows, s.x.cols3(), mode);
+	return check_shape(s.x.rows, s.x.cols(), mode);
 }
 
 // (device pointers, already checked) the kernel on `st`: system a - a0 at d_out + (a - a0) x sys_stride, m rows out_stride words apart
@@ -4886,7 +4916,7 @@ int enqueue_quad_specialise(const GuessShape &s, const u64 *d_quad, i64 quad_str
 }
 
 // What one assignment's system holds on the device while a solve entry runs: its specialised rows and its padded expansion
-i64 guess_system_bytes(const Xl3Shape &x) { return 8 * (x.m * round_up(x.w2(), 2) + x.rows * round_up(x.wt(), 2)); }
+i64 guess_system_bytes(const XlShape &x) { return 8 * (x.m * round_up(x.w2(), 2) + x.rows * round_up(x.wt(), 2)); }
 
 struct PoolStream {                    // a stream of the pool for the length of an entry
 	hipStream_t st = nullptr;
@@ -4906,7 +4936,7 @@ struct QuadStage {
 	                                   // first entries, gf2bv_quad_expand_words and gf2bv_solve_quad_terms, keep their GF2BV_ERR_HIP
 	u64 *d_aug = nullptr, *d_rhs = nullptr;
 	i64 ds = 0;
-	u64 *d_xl = nullptr;               // the degree-3 XL expansion of the rows in d_aug (expand_xl3), xs words a row: both are held at once
+	u64 *d_xl = nullptr;               // the XL expansion of the rows in d_aug (expand_xl), xs words a row: both are held at once
 	i64 xs = 0;
 	u64 *d_spec = nullptr;             // hybrid XL: the rows in d_aug specialised for na assignments (specialise), ss words a row, m x ss a system
 	i64 ss = 0;
@@ -4964,13 +4994,13 @@ struct QuadStage {
 		ds = stride;
 		return upload(&d_aug, quad, sizeof(u64) * (size_t)(m * stride));
 	}
-	// The degree-3 XL expansion of the x.m quadratic rows in d_aug into d_xl, x.rows rows `stride` words apart rounded up to an even xs,
+	// The XL expansion (x.degree) of the x.m quadratic rows in d_aug into d_xl, x.rows rows `stride` words apart rounded up to an even xs,
 	// behind whatever wrote d_aug on the stream
-	int expand_xl3(const Xl3Shape &x, i64 stride)
+	int expand_xl(const XlShape &x, i64 stride)
 	{
 		xs = round_up(stride, 2);
 		if (int rc = alloc((void **)&d_xl, sizeof(u64) * (size_t)(x.rows * xs))) return rc;
-		return enqueue_xl3_expand(x, d_aug, ds, d_xl, xs, ps.st);
+		return enqueue_xl_expand(x, d_aug, ds, d_xl, xs, ps.st);
 	}
 	// The rows in d_aug specialised for every assignment of `g` into d_spec, rows `stride` words apart
 	int specialise(const GuessShape &g, i64 stride)
@@ -4979,13 +5009,13 @@ struct QuadStage {
 		if (int rc = alloc((void **)&d_spec, sizeof(u64) * (size_t)(g.na * g.m * ss))) return rc;
 		return enqueue_quad_specialise(g, d_aug, ds, d_spec, ss, g.m * ss, ps.st);
 	}
-	// The degree-3 XL expansions of nsys systems of x.m quadratic rows in d_spec (system s at s x spec_sys words) into d_xl, system s at
+	// The XL expansions (x.degree) of nsys systems of x.m quadratic rows in d_spec (system s at s x spec_sys words) into d_xl, system s at
 	// s x x.rows x xs
-	int expand_xl3_batch(const Xl3Shape &x, i64 nsys, i64 spec_sys, i64 stride)
+	int expand_xl_batch(const XlShape &x, i64 nsys, i64 spec_sys, i64 stride)
 	{
 		xs = round_up(stride, 2);
 		if (int rc = alloc((void **)&d_xl, sizeof(u64) * (size_t)(nsys * x.rows * xs))) return rc;
-		return enqueue_xl3_expand_batch(x, d_spec, spec_sys, ss, nsys, d_xl, xs, x.rows * xs, ps.st);
+		return enqueue_xl_expand_batch(x, d_spec, spec_sys, ss, nsys, d_xl, xs, x.rows * xs, ps.st);
 	}
 	// `nrows` rows of the expansion (`xl`: of the XL expansion) into host memory, `stride` words apart; the host waits
 	int download(void *out, i64 stride, i64 nrows, bool xl = false)
@@ -4997,10 +5027,10 @@ struct QuadStage {
 };
 
 // the shape rules the two batched expansion entries share; no pointer is looked at
-int check_xl3_batch(Xl3Shape &x, i64 nsys, i64 quad_sys_stride, i64 quad_stride, i64 stride, i64 sys_stride)
+int check_xl_batch(XlShape &x, i64 nsys, i64 quad_sys_stride, i64 quad_stride, i64 stride, i64 sys_stride)
 {
 	if (nsys < 0) return fail(GF2BV_ERR_ARG, "nsys must not be negative");
-	int rc = check_xl3(x, quad_stride);
+	int rc = check_xl(x, quad_stride);
 	if (rc) return rc;
 	if (nsys * std::max<i64>(x.rows, 1) >= (1ll << 31) - 64) return fail(GF2BV_ERR_ARG, "the rows of all systems together must stay below 2^31 - 64");
 	if (quad_sys_stride < x.m * quad_stride) return fail(GF2BV_ERR_ARG, "quad_sys_stride_words must be at least m * quad_stride_words");
@@ -5013,9 +5043,9 @@ int check_xl3_batch(Xl3Shape &x, i64 nsys, i64 quad_sys_stride, i64 quad_stride,
 int solve_guess_staged(QuadStage &stage, const GuessShape &g, int mode, int device, gf2bv_result **out)
 {
 	int rc = stage.specialise(g, round_up(g.x.w2(), 2));
-	if (!rc) rc = stage.expand_xl3_batch(g.x, g.na, g.m * stage.ss, g.x.wt());
+	if (!rc) rc = stage.expand_xl_batch(g.x, g.na, g.m * stage.ss, g.x.wt());
 	if (rc) return rc;
-	rc = gf2bv_solve_batch_device(stage.d_xl, g.na, g.x.rows * stage.xs, g.x.rows, g.x.cols3(), stage.xs, mode, device, stage.ps.st, 0, out);
+	rc = gf2bv_solve_batch_device(stage.d_xl, g.na, g.x.rows * stage.xs, g.x.rows, g.x.cols(), stage.xs, mode, device, stage.ps.st, 0, out);
 	if (rc)
 		for (i64 s = 0; s < g.na; s++) { gf2bv_result_free(out[s]); out[s] = nullptr; }
 	return rc;
@@ -5177,62 +5207,62 @@ int gf2bv_solve_batch_quad_terms(const uint64_t *lin, const int64_t *term_off, c
 }
 
 // ---- degree-3 XL: the quadratic rows (expanded already, or factored) multiplied by 1 and by every unknown on the device
-int gf2bv_xl3_expand_device(const void *d_quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int64_t rows, void *d_aug,
+static int xl_expand_device(int degree, const void *d_quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int64_t rows, void *d_aug,
                             int64_t stride_words, int device, void *stream)
 {
 	return catching([&]() -> int {
-	Xl3Shape x;
-	x.m = m; x.n = n_lin; x.rows = rows;
+	XlShape x;
+	x.degree = degree; x.m = m; x.n = n_lin; x.rows = rows;
 	if (!d_aug || (!d_quad && m > 0)) return fail(GF2BV_ERR_ARG, "null pointer");
-	int rc = check_xl3(x, quad_stride_words);
+	int rc = check_xl(x, quad_stride_words);
 	if (rc) return rc;
 	if (stride_words % 2 != 0 || stride_words < x.wt() || ((uintptr_t)d_aug & 15))
 		return fail(GF2BV_ERR_ARG, "device matrix needs 16-byte alignment and an even stride_words covering cols+1 bits");
 	if ((rc = check_device(device))) return rc;
-	return enqueue_xl3_expand(x, (const u64 *)d_quad, quad_stride_words, (u64 *)d_aug, stride_words, (hipStream_t)stream);
+	return enqueue_xl_expand(x, (const u64 *)d_quad, quad_stride_words, (u64 *)d_aug, stride_words, (hipStream_t)stream);
 	});
 }
 
-int gf2bv_xl3_expand_words(const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int64_t rows, uint64_t *out_aug,
+static int xl_expand_words(int degree, const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int64_t rows, uint64_t *out_aug,
                            int64_t stride_words, int device)
 {
 	return catching([&]() -> int {
-	Xl3Shape x;
-	x.m = m; x.n = n_lin; x.rows = rows;
+	XlShape x;
+	x.degree = degree; x.m = m; x.n = n_lin; x.rows = rows;
 	if ((!out_aug && rows > 0) || (!quad && m > 0)) return fail(GF2BV_ERR_ARG, "null pointer");
-	int rc = check_xl3(x, quad_stride_words);
+	int rc = check_xl(x, quad_stride_words);
 	if (rc) return rc;
 	if (stride_words < x.wt()) return fail(GF2BV_ERR_ARG, "stride_words does not cover cols+1 bits");
 	if ((rc = check_device(device))) return rc;
 	if (rows == 0) return GF2BV_OK;
 	QuadStage stage(device);
 	if ((rc = stage.upload_rows(reinterpret_cast<const u64 *>(quad), m, quad_stride_words))) return rc;
-	if ((rc = stage.expand_xl3(x, stride_words))) return rc;
+	if ((rc = stage.expand_xl(x, stride_words))) return rc;
 	return stage.download(out_aug, stride_words, rows, true);
 	});
 }
 
-int gf2bv_solve_xl3_words(const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int mode, int device,
+static int solve_xl_words(int degree, const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int mode, int device,
                           gf2bv_result **out)
 {
 	return catching([&]() -> int {
 	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
 	*out = nullptr;
 	if (!quad && m > 0) return fail(GF2BV_ERR_ARG, "null pointer");
-	Xl3Shape x;
-	x.m = m; x.n = n_lin;
-	int rc = check_xl3(x, quad_stride_words, true);
-	if (!rc) rc = check_shape(x.rows, x.cols3(), mode);
+	XlShape x;
+	x.degree = degree; x.m = m; x.n = n_lin;
+	int rc = check_xl(x, quad_stride_words, true);
+	if (!rc) rc = check_shape(x.rows, x.cols(), mode);
 	if (!rc) rc = check_device(device);
 	if (rc) return rc;
 	QuadStage stage(device);
 	if ((rc = stage.upload_rows(reinterpret_cast<const u64 *>(quad), m, quad_stride_words))) return rc;
-	if ((rc = stage.expand_xl3(x, x.wt()))) return rc;
-	return gf2bv_solve_device(stage.d_xl, x.rows, x.cols3(), stage.xs, mode, device, stage.ps.st, 0, out);
+	if ((rc = stage.expand_xl(x, x.wt()))) return rc;
+	return gf2bv_solve_device(stage.d_xl, x.rows, x.cols(), stage.xs, mode, device, stage.ps.st, 0, out);
 	});
 }
 
-int gf2bv_solve_xl3_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t m,
+static int solve_xl_quad_terms(int degree, const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t m,
                                int64_t n_lin, int mode, int device, gf2bv_result **out)
 {
 	return catching([&]() -> int {
@@ -5241,16 +5271,16 @@ int gf2bv_solve_xl3_quad_terms(const uint64_t *lin, const int64_t *term_off, con
 	const QuadTerms q = quad_terms(lin, term_off, ta, tb, m, m, n_lin);      // the m quadratic rows, no padding
 	int rc = check_quad_terms(q, true);
 	if (rc) return rc;
-	Xl3Shape x;
-	x.m = m; x.n = n_lin;
-	rc = check_xl3(x, q.wt(), true);
-	if (!rc) rc = check_shape(x.rows, x.cols3(), mode);
+	XlShape x;
+	x.degree = degree; x.m = m; x.n = n_lin;
+	rc = check_xl(x, q.wt(), true);
+	if (!rc) rc = check_shape(x.rows, x.cols(), mode);
 	if (!rc) rc = check_device(device);
 	if (rc) return rc;
 	QuadStage stage(device);
 	if ((rc = stage.expand(q, q.wt()))) return rc;
-	if ((rc = stage.expand_xl3(x, x.wt()))) return rc;
-	return gf2bv_solve_device(stage.d_xl, x.rows, x.cols3(), stage.xs, mode, device, stage.ps.st, 0, out);
+	if ((rc = stage.expand_xl(x, x.wt()))) return rc;
+	return gf2bv_solve_device(stage.d_xl, x.rows, x.cols(), stage.xs, mode, device, stage.ps.st, 0, out);
 	});
 }
 
@@ -5294,32 +5324,32 @@ int gf2bv_quad_specialise_words(const uint64_t *quad, int64_t m, int64_t quad_st
 	});
 }
 
-int gf2bv_xl3_expand_batch_device(const void *d_quad, int64_t nsys, int64_t quad_sys_stride_words, int64_t m, int64_t quad_stride_words,
+static int xl_expand_batch_device(int degree, const void *d_quad, int64_t nsys, int64_t quad_sys_stride_words, int64_t m, int64_t quad_stride_words,
                                   int64_t n_lin, int64_t rows, void *d_aug, int64_t stride_words, int64_t sys_stride_words, int device,
                                   void *stream)
 {
 	return catching([&]() -> int {
-	Xl3Shape x;
-	x.m = m; x.n = n_lin; x.rows = rows;
+	XlShape x;
+	x.degree = degree; x.m = m; x.n = n_lin; x.rows = rows;
 	if (!d_aug || (!d_quad && m > 0)) return fail(GF2BV_ERR_ARG, "null pointer");
-	int rc = check_xl3_batch(x, nsys, quad_sys_stride_words, quad_stride_words, stride_words, sys_stride_words);
+	int rc = check_xl_batch(x, nsys, quad_sys_stride_words, quad_stride_words, stride_words, sys_stride_words);
 	if (rc) return rc;
 	if (stride_words % 2 != 0 || sys_stride_words % 2 != 0 || ((uintptr_t)d_aug & 15))
 		return fail(GF2BV_ERR_ARG, "device matrices need 16-byte alignment and even stride_words and sys_stride_words");
 	if ((rc = check_device(device))) return rc;
-	return enqueue_xl3_expand_batch(x, (const u64 *)d_quad, quad_sys_stride_words, quad_stride_words, nsys, (u64 *)d_aug, stride_words,
+	return enqueue_xl_expand_batch(x, (const u64 *)d_quad, quad_sys_stride_words, quad_stride_words, nsys, (u64 *)d_aug, stride_words,
 	                                sys_stride_words, (hipStream_t)stream);
 	});
 }
 
-int gf2bv_xl3_expand_batch_words(const uint64_t *quad, int64_t nsys, int64_t quad_sys_stride_words, int64_t m, int64_t quad_stride_words,
+static int xl_expand_batch_words(int degree, const uint64_t *quad, int64_t nsys, int64_t quad_sys_stride_words, int64_t m, int64_t quad_stride_words,
                                  int64_t n_lin, int64_t rows, uint64_t *out_aug, int64_t stride_words, int64_t sys_stride_words, int device)
 {
 	return catching([&]() -> int {
-	Xl3Shape x;
-	x.m = m; x.n = n_lin; x.rows = rows;
+	XlShape x;
+	x.degree = degree; x.m = m; x.n = n_lin; x.rows = rows;
 	if ((!out_aug && rows > 0 && nsys > 0) || (!quad && m > 0 && nsys > 0)) return fail(GF2BV_ERR_ARG, "null pointer");
-	int rc = check_xl3_batch(x, nsys, quad_sys_stride_words, quad_stride_words, stride_words, sys_stride_words);
+	int rc = check_xl_batch(x, nsys, quad_sys_stride_words, quad_stride_words, stride_words, sys_stride_words);
 	if (rc) return rc;
 	if ((rc = check_device(device))) return rc;
 	if (rows == 0 || nsys == 0) return GF2BV_OK;
@@ -5328,7 +5358,7 @@ int gf2bv_xl3_expand_batch_words(const uint64_t *quad, int64_t nsys, int64_t qua
 	stage.ss = quad_stride_words;                      // (the last system's rows end the source: nothing behind them is read)
 	if ((rc = stage.upload(&stage.d_spec, reinterpret_cast<const u64 *>(quad),
 	                       m ? sizeof(u64) * (size_t)((nsys - 1) * quad_sys_stride_words + m * quad_stride_words) : 0))) return rc;
-	if ((rc = stage.expand_xl3_batch(x, nsys, quad_sys_stride_words, stride_words))) return rc;
+	if ((rc = stage.expand_xl_batch(x, nsys, quad_sys_stride_words, stride_words))) return rc;
 	if (sys_stride_words == rows * stride_words)
 		HIPCHK(hipMemcpy2DAsync(out_aug, stride_words * 8, stage.d_xl, stage.xs * 8, stride_words * 8, nsys * rows, hipMemcpyDeviceToHost, stage.ps.st));
 	else
@@ -5340,7 +5370,7 @@ int gf2bv_xl3_expand_batch_words(const uint64_t *quad, int64_t nsys, int64_t qua
 	});
 }
 
-int gf2bv_solve_xl3_guess_words(const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, const int32_t *guess,
+static int solve_xl_guess_words(int degree, const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, const int32_t *guess,
                                 int64_t nguess, int64_t a0, int64_t na, int mode, int device, gf2bv_result **out)
 {
 	return catching([&]() -> int {
@@ -5348,6 +5378,7 @@ int gf2bv_solve_xl3_guess_words(const uint64_t *quad, int64_t m, int64_t quad_st
 	for (i64 s = 0; s < na; s++) out[s] = nullptr;
 	if (!quad && m > 0) return fail(GF2BV_ERR_ARG, "null pointer");
 	GuessShape g;
+	g.x.degree = degree;
 	g.m = m; g.n = n_lin; g.f = nguess; g.a0 = a0; g.na = na;
 	int rc = check_guess(g, guess, quad_stride_words);
 	if (!rc) rc = check_guess_solve(g, mode);
@@ -5360,7 +5391,7 @@ int gf2bv_solve_xl3_guess_words(const uint64_t *quad, int64_t m, int64_t quad_st
 	});
 }
 
-int gf2bv_solve_xl3_guess_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t m,
+static int solve_xl_guess_quad_terms(int degree, const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t m,
                                      int64_t n_lin, const int32_t *guess, int64_t nguess, int64_t a0, int64_t na, int mode, int device,
                                      gf2bv_result **out)
 {
@@ -5371,6 +5402,7 @@ int gf2bv_solve_xl3_guess_quad_terms(const uint64_t *lin, const int64_t *term_of
 	int rc = check_quad_terms(q, true);
 	if (rc) return rc;
 	GuessShape g;
+	g.x.degree = degree;
 	g.m = m; g.n = n_lin; g.f = nguess; g.a0 = a0; g.na = na;
 	rc = check_guess(g, guess, q.wt());
 	if (!rc) rc = check_guess_solve(g, mode);
@@ -5386,31 +5418,136 @@ int gf2bv_solve_xl3_guess_quad_terms(const uint64_t *lin, const int64_t *term_of
 // The largest number of assignments (at most 2^nguess) whose specialised rows and padded expansions take at most a quarter of
 // free_bytes -- the solver keeps a tile-major copy of about the size of every system of a gang, so expansion and copy stay below half of
 // what was free -- and whose rows together stay below 2^31 - 64; 0 when one system does not fit, -1 for a bad shape.  No device is touched.
-int64_t gf2bv_xl3_guess_chunk(int64_t m, int64_t n_lin, int64_t nguess, int64_t free_bytes)
+static int64_t xl_guess_chunk(int degree, int64_t m, int64_t n_lin, int64_t nguess, int64_t free_bytes)
 {
 	if (n_lin < 1 || n_lin > 65535 || nguess < 0 || nguess > std::min<i64>(n_lin - 1, 30) || m < 0 || free_bytes < 0) return -1;
-	Xl3Shape x;
-	x.m = m; x.n = n_lin - nguess;
-	if (check_xl3(x, x.w2(), true)) return -1;
+	XlShape x;
+	x.degree = degree; x.m = m; x.n = n_lin - nguess;
+	if (check_xl(x, x.w2(), true)) return -1;
 	const i64 fit = free_bytes / 4 / guess_system_bytes(x);
 	return std::min<i64>({ 1ll << nguess, fit, ((1ll << 31) - 65) / x.rows });
 }
 
-int gf2bv_xl3_guess_chunk_device(int64_t m, int64_t n_lin, int64_t nguess, int device, int64_t *chunk)
+static int xl_guess_chunk_device(int degree, int64_t m, int64_t n_lin, int64_t nguess, int device, int64_t *chunk)
 {
 	return catching([&]() -> int {
 	if (!chunk) return fail(GF2BV_ERR_ARG, "null pointer");
 	*chunk = 0;
-	if (gf2bv_xl3_guess_chunk(m, n_lin, nguess, 0) < 0) return fail(GF2BV_ERR_ARG, "m, n_lin or nguess out of range");
+	if (xl_guess_chunk(degree, m, n_lin, nguess, 0) < 0) return fail(GF2BV_ERR_ARG, "m, n_lin or nguess out of range");
 	int rc = check_device(device);
 	if (rc) return rc;
 	HIPCHK(hipSetDevice(device));
 	size_t free_b = 0, total_b = 0;
 	HIPCHK(hipMemGetInfo(&free_b, &total_b));
 	// (what the pool holds idle is handed out again before the device is asked for more)
-	*chunk = gf2bv_xl3_guess_chunk(m, n_lin, nguess, (i64)free_b + std::max<i64>(0, gf2bv_pool_idle_bytes(device)));
+	*chunk = xl_guess_chunk(degree, m, n_lin, nguess, (i64)free_b + std::max<i64>(0, gf2bv_pool_idle_bytes(device)));
 	return GF2BV_OK;
 	});
 }
+
+// the exported names: each body above once, for degree 3 and degree 4
+int gf2bv_xl3_expand_device(const void *d_quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int64_t rows, void *d_aug,
+                            int64_t stride_words, int device, void *stream)
+{
+	return xl_expand_device(3, d_quad, m, quad_stride_words, n_lin, rows, d_aug, stride_words, device, stream);
+}
+int gf2bv_xl4_expand_device(const void *d_quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int64_t rows, void *d_aug,
+                            int64_t stride_words, int device, void *stream)
+{
+	return xl_expand_device(4, d_quad, m, quad_stride_words, n_lin, rows, d_aug, stride_words, device, stream);
+}
+int gf2bv_xl3_expand_words(const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int64_t rows, uint64_t *out_aug,
+                           int64_t stride_words, int device)
+{
+	return xl_expand_words(3, quad, m, quad_stride_words, n_lin, rows, out_aug, stride_words, device);
+}
+int gf2bv_xl4_expand_words(const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int64_t rows, uint64_t *out_aug,
+                           int64_t stride_words, int device)
+{
+	return xl_expand_words(4, quad, m, quad_stride_words, n_lin, rows, out_aug, stride_words, device);
+}
+int gf2bv_solve_xl3_words(const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int mode, int device, gf2bv_result **out)
+{
+	return solve_xl_words(3, quad, m, quad_stride_words, n_lin, mode, device, out);
+}
+int gf2bv_solve_xl4_words(const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int mode, int device, gf2bv_result **out)
+{
+	return solve_xl_words(4, quad, m, quad_stride_words, n_lin, mode, device, out);
+}
+int gf2bv_solve_xl3_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t m, int64_t n_lin,
+                               int mode, int device, gf2bv_result **out)
+{
+	return solve_xl_quad_terms(3, lin, term_off, ta, tb, m, n_lin, mode, device, out);
+}
+int gf2bv_solve_xl4_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t m, int64_t n_lin,
+                               int mode, int device, gf2bv_result **out)
+{
+	return solve_xl_quad_terms(4, lin, term_off, ta, tb, m, n_lin, mode, device, out);
+}
+int gf2bv_xl3_expand_batch_device(const void *d_quad, int64_t nsys, int64_t quad_sys_stride_words, int64_t m, int64_t quad_stride_words,
+                                  int64_t n_lin, int64_t rows, void *d_aug, int64_t stride_words, int64_t sys_stride_words, int device,
+                                  void *stream)
+{
+	return xl_expand_batch_device(3, d_quad, nsys, quad_sys_stride_words, m, quad_stride_words, n_lin, rows, d_aug, stride_words, sys_stride_words,
+	                              device, stream);
+}
+int gf2bv_xl4_expand_batch_device(const void *d_quad, int64_t nsys, int64_t quad_sys_stride_words, int64_t m, int64_t quad_stride_words,
+                                  int64_t n_lin, int64_t rows, void *d_aug, int64_t stride_words, int64_t sys_stride_words, int device,
+                                  void *stream)
+{
+	return xl_expand_batch_device(4, d_quad, nsys, quad_sys_stride_words, m, quad_stride_words, n_lin, rows, d_aug, stride_words, sys_stride_words,
+	                              device, stream);
+}
+int gf2bv_xl3_expand_batch_words(const uint64_t *quad, int64_t nsys, int64_t quad_sys_stride_words, int64_t m, int64_t quad_stride_words,
+                                 int64_t n_lin, int64_t rows, uint64_t *out_aug, int64_t stride_words, int64_t sys_stride_words, int device)
+{
+	return xl_expand_batch_words(3, quad, nsys, quad_sys_stride_words, m, quad_stride_words, n_lin, rows, out_aug, stride_words, sys_stride_words,
+	                             device);
+}
+int gf2bv_xl4_expand_batch_words(const uint64_t *quad, int64_t nsys, int64_t quad_sys_stride_words, int64_t m, int64_t quad_stride_words,
+                                 int64_t n_lin, int64_t rows, uint64_t *out_aug, int64_t stride_words, int64_t sys_stride_words, int device)
+{
+	return xl_expand_batch_words(4, quad, nsys, quad_sys_stride_words, m, quad_stride_words, n_lin, rows, out_aug, stride_words, sys_stride_words,
+	                             device);
+}
+int gf2bv_solve_xl3_guess_words(const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, const int32_t *guess, int64_t nguess,
+                                int64_t a0, int64_t na, int mode, int device, gf2bv_result **out)
+{
+	return solve_xl_guess_words(3, quad, m, quad_stride_words, n_lin, guess, nguess, a0, na, mode, device, out);
+}
+int gf2bv_solve_xl4_guess_words(const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, const int32_t *guess, int64_t nguess,
+                                int64_t a0, int64_t na, int mode, int device, gf2bv_result **out)
+{
+	return solve_xl_guess_words(4, quad, m, quad_stride_words, n_lin, guess, nguess, a0, na, mode, device, out);
+}
+int gf2bv_solve_xl3_guess_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t m, int64_t n_lin,
+                                     const int32_t *guess, int64_t nguess, int64_t a0, int64_t na, int mode, int device, gf2bv_result **out)
+{
+	return solve_xl_guess_quad_terms(3, lin, term_off, ta, tb, m, n_lin, guess, nguess, a0, na, mode, device, out);
+}
+int gf2bv_solve_xl4_guess_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t m, int64_t n_lin,
+                                     const int32_t *guess, int64_t nguess, int64_t a0, int64_t na, int mode, int device, gf2bv_result **out)
+{
+	return solve_xl_guess_quad_terms(4, lin, term_off, ta, tb, m, n_lin, guess, nguess, a0, na, mode, device, out);
+}
+int64_t gf2bv_xl3_guess_chunk(int64_t m, int64_t n_lin, int64_t nguess, int64_t free_bytes)
+{
+	return xl_guess_chunk(3, m, n_lin, nguess, free_bytes);
+}
+int64_t gf2bv_xl4_guess_chunk(int64_t m, int64_t n_lin, int64_t nguess, int64_t free_bytes)
+{
+	return xl_guess_chunk(4, m, n_lin, nguess, free_bytes);
+}
+int gf2bv_xl3_guess_chunk_device(int64_t m, int64_t n_lin, int64_t nguess, int device, int64_t *chunk)
+{
+	return xl_guess_chunk_device(3, m, n_lin, nguess, device, chunk);
+}
+int gf2bv_xl4_guess_chunk_device(int64_t m, int64_t n_lin, int64_t nguess, int device, int64_t *chunk)
+{
+	return xl_guess_chunk_device(4, m, n_lin, nguess, device, chunk);
+}
+
+// k_xl4_expand's quartic root, the same function compiled for the host: the largest i >= 3 with C(i,4) <= u (u >= 0), for checks
+int64_t gf2bv_xl4_quartic_root(int64_t u) { return u < 0 ? -1 : xl_quart_root(u); }
 
 }  // extern "C"

@@ -41,6 +41,9 @@ EXPORTS = [
     "gf2bv_xl3_expand_device", "gf2bv_xl3_expand_words", "gf2bv_solve_xl3_words", "gf2bv_solve_xl3_quad_terms",
     "gf2bv_quad_specialise_device", "gf2bv_quad_specialise_words", "gf2bv_xl3_expand_batch_device", "gf2bv_xl3_expand_batch_words",
     "gf2bv_solve_xl3_guess_words", "gf2bv_solve_xl3_guess_quad_terms", "gf2bv_xl3_guess_chunk", "gf2bv_xl3_guess_chunk_device",
+    "gf2bv_xl4_expand_device", "gf2bv_xl4_expand_words", "gf2bv_solve_xl4_words", "gf2bv_solve_xl4_quad_terms",
+    "gf2bv_xl4_expand_batch_device", "gf2bv_xl4_expand_batch_words", "gf2bv_solve_xl4_guess_words", "gf2bv_solve_xl4_guess_quad_terms",
+    "gf2bv_xl4_guess_chunk", "gf2bv_xl4_guess_chunk_device", "gf2bv_xl4_quartic_root",
     "gf2bv_quad_search", "gf2bv_quad_search_alloc", "gf2bv_quad_free", "gf2bv_quad_plan", "gf2bv_quad_points", "gf2bv_quad_forms_search", "gf2bv_quad_last_times",
     "gf2bv_slab_work_words", "gf2bv_slab_tiles", "gf2bv_slab_open", "gf2bv_slab_blocks", "gf2bv_slab_owner",
     "gf2bv_slab_payload_bytes", "gf2bv_slab_factor", "gf2bv_slab_apply", "gf2bv_slab_factor_on", "gf2bv_slab_apply_on",
@@ -149,19 +152,22 @@ def lib():
         L.gf2bv_solve_rhs_quad_terms.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, i64, i64, i32, i32, pp]
         L.gf2bv_solve_batch_quad_terms.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i32, i32, pp]
         L.gf2bv_quad_expand_batch_words.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, vp, i64, i32]
-        L.gf2bv_xl3_expand_device.argtypes = [vp, i64, i64, i64, i64, vp, i64, i32, vp]
-        L.gf2bv_xl3_expand_words.argtypes = [vp, i64, i64, i64, i64, vp, i64, i32]
-        L.gf2bv_solve_xl3_words.argtypes = [vp, i64, i64, i64, i32, i32, pp]
-        L.gf2bv_solve_xl3_quad_terms.argtypes = [vp, vp, vp, vp, i64, i64, i32, i32, pp]
+        for d in ("xl3", "xl4"):                       # the two degrees: the same signatures
+            getattr(L, f"gf2bv_{d}_expand_device").argtypes = [vp, i64, i64, i64, i64, vp, i64, i32, vp]
+            getattr(L, f"gf2bv_{d}_expand_words").argtypes = [vp, i64, i64, i64, i64, vp, i64, i32]
+            getattr(L, f"gf2bv_solve_{d}_words").argtypes = [vp, i64, i64, i64, i32, i32, pp]
+            getattr(L, f"gf2bv_solve_{d}_quad_terms").argtypes = [vp, vp, vp, vp, i64, i64, i32, i32, pp]
+            getattr(L, f"gf2bv_{d}_expand_batch_device").argtypes = [vp, i64, i64, i64, i64, i64, i64, vp, i64, i64, i32, vp]
+            getattr(L, f"gf2bv_{d}_expand_batch_words").argtypes = [vp, i64, i64, i64, i64, i64, i64, vp, i64, i64, i32]
+            getattr(L, f"gf2bv_solve_{d}_guess_words").argtypes = [vp, i64, i64, i64, vp, i64, i64, i64, i32, i32, pp]
+            getattr(L, f"gf2bv_solve_{d}_guess_quad_terms").argtypes = [vp, vp, vp, vp, i64, i64, vp, i64, i64, i64, i32, i32, pp]
+            getattr(L, f"gf2bv_{d}_guess_chunk").argtypes = [i64, i64, i64, i64]
+            getattr(L, f"gf2bv_{d}_guess_chunk").restype = i64
+            getattr(L, f"gf2bv_{d}_guess_chunk_device").argtypes = [i64, i64, i64, i32, ctypes.POINTER(i64)]
         L.gf2bv_quad_specialise_device.argtypes = [vp, i64, i64, i64, vp, i64, i64, i64, vp, i64, i64, i32, vp]
         L.gf2bv_quad_specialise_words.argtypes = [vp, i64, i64, i64, vp, i64, i64, i64, vp, i64, i32]
-        L.gf2bv_xl3_expand_batch_device.argtypes = [vp, i64, i64, i64, i64, i64, i64, vp, i64, i64, i32, vp]
-        L.gf2bv_xl3_expand_batch_words.argtypes = [vp, i64, i64, i64, i64, i64, i64, vp, i64, i64, i32]
-        L.gf2bv_solve_xl3_guess_words.argtypes = [vp, i64, i64, i64, vp, i64, i64, i64, i32, i32, pp]
-        L.gf2bv_solve_xl3_guess_quad_terms.argtypes = [vp, vp, vp, vp, i64, i64, vp, i64, i64, i64, i32, i32, pp]
-        L.gf2bv_xl3_guess_chunk.argtypes = [i64, i64, i64, i64]
-        L.gf2bv_xl3_guess_chunk.restype = i64
-        L.gf2bv_xl3_guess_chunk_device.argtypes = [i64, i64, i64, i32, ctypes.POINTER(i64)]
+        L.gf2bv_xl4_quartic_root.argtypes = [i64]
+        L.gf2bv_xl4_quartic_root.restype = i64
         L.gf2bv_slab_work_words.argtypes = [i64, i64]
         L.gf2bv_slab_work_words.restype = i64
         L.gf2bv_slab_tiles.argtypes = [i64]
@@ -722,6 +728,25 @@ def xl3_cols(n_lin: int) -> int:
     return quad_cols(n_lin) + n_lin * (n_lin - 1) * (n_lin - 2) // 6
 
 
+def xl4_cols(n_lin: int) -> int:
+    """columns of the degree-4 XL system in n_lin unknowns: degree 3's and the quadruples"""
+    return xl3_cols(n_lin) + n_lin * (n_lin - 1) * (n_lin - 2) * (n_lin - 3) // 24
+
+
+# The xl3_* and xl4_* functions below are one body each, taking the degree (3: multipliers 1 and x_k, n + 1 rows an equation; 4: also
+# x_a x_b, 1 + n + C(n,2) rows an equation -- gf2bv_hip.h, "degree-4 XL")
+def _xl_cols(degree: int, n_lin: int) -> int:
+    return xl4_cols(n_lin) if degree == 4 else xl3_cols(n_lin)
+
+
+def _xl_rows_per_eq(degree: int, n_lin: int) -> int:
+    return 1 + quad_cols(n_lin) if degree == 4 else n_lin + 1
+
+
+def _xl_fn(degree: int, name: str):
+    return getattr(lib(), name.format(degree))
+
+
 def _quad_rows(quad) -> np.ndarray:
     """quadratic rows of the augmented-words layout (what quad_expand_words returns) as a contiguous [m, stride] array"""
     quad = np.ascontiguousarray(quad, dtype=np.uint64)
@@ -730,41 +755,42 @@ def _quad_rows(quad) -> np.ndarray:
     return quad
 
 
-def xl3_expand_words(quad, n_lin: int, rows: int | None = None, stride_words: int | None = None, device: int = 0) -> np.ndarray:
-    """Degree-3 XL on the device (gf2bv_xl3_expand_words): `quad` holds m quadratic rows as quad_expand_words returns them; the
-    result is [rows, stride_words] uint64 over xl3_cols(n_lin) columns -- rows e(n+1) .. e(n+1) + n equation e and its product
-    with every unknown, rows beyond m(n+1) zero."""
+def _xl_expand_words(degree: int, quad, n_lin: int, rows: int | None = None, stride_words: int | None = None, device: int = 0) -> np.ndarray:
+    """XL on the device (gf2bv_xl3_expand_words / gf2bv_xl4_expand_words): `quad` holds m quadratic rows as quad_expand_words returns
+    them; the result is [rows, stride_words] uint64 over xl3_cols(n_lin) / xl4_cols(n_lin) columns.  Degree 3: rows e(n+1) .. e(n+1) + n
+    equation e and its product with every unknown; degree 4: the 1 + n + C(n,2) rows from e(1 + n + C(n,2)), the products with every
+    pair of unknowns behind those.  Rows beyond the live ones zero."""
     quad = _quad_rows(quad)
     m = len(quad)
-    rows = m * (n_lin + 1) if rows is None else rows
-    stride = (xl3_cols(n_lin) + 1 + 63) // 64 if stride_words is None else stride_words
+    rows = m * _xl_rows_per_eq(degree, n_lin) if rows is None else rows
+    stride = (_xl_cols(degree, n_lin) + 1 + 63) // 64 if stride_words is None else stride_words
     out = np.empty((max(rows, 0), max(stride, 0)), dtype=np.uint64)
-    _check(lib().gf2bv_xl3_expand_words(quad.ctypes.data, m, quad.shape[1], n_lin, rows, out.ctypes.data, stride, device))
+    _check(_xl_fn(degree, "gf2bv_xl{}_expand_words")(quad.ctypes.data, m, quad.shape[1], n_lin, rows, out.ctypes.data, stride, device))
     return out
 
 
-def xl3_expand_device(d_quad: int, m: int, quad_stride: int, n_lin: int, rows: int, d_aug: int, stride: int, device: int = 0,
+def _xl_expand_device(degree: int, d_quad: int, m: int, quad_stride: int, n_lin: int, rows: int, d_aug: int, stride: int, device: int = 0,
                       stream: int = 0) -> None:
     """xl3_expand_words with everything resident in device memory: the kernel is enqueued on `stream` and the call returns; a
     solve_device / factor_device on the same stream reads the finished rows."""
-    _check(lib().gf2bv_xl3_expand_device(d_quad, m, quad_stride, n_lin, rows, d_aug, stride, device, stream or None))
+    _check(_xl_fn(degree, "gf2bv_xl{}_expand_device")(d_quad, m, quad_stride, n_lin, rows, d_aug, stride, device, stream or None))
 
 
-def solve_xl3_words(quad, n_lin: int, mode: int = MODE_SINGLE, device: int = 0) -> Solution:
-    """Quadratic rows uploaded, multiplied on the device and solved there (gf2bv_solve_xl3_words): what solve_words returns for
-    xl3_expand_words of the same rows padded to max(m(n+1), xl3_cols(n_lin)) rows."""
+def _solve_xl_words(degree: int, quad, n_lin: int, mode: int = MODE_SINGLE, device: int = 0) -> Solution:
+    """Quadratic rows uploaded, multiplied on the device and solved there (gf2bv_solve_xl3_words / gf2bv_solve_xl4_words): what
+    solve_words returns for the expansion of the same rows padded with zero rows up to the columns of that degree."""
     quad = _quad_rows(quad)
     h = ctypes.c_void_p()
-    _check(lib().gf2bv_solve_xl3_words(quad.ctypes.data, len(quad), quad.shape[1], n_lin, mode, device, ctypes.byref(h)))
+    _check(_xl_fn(degree, "gf2bv_solve_xl{}_words")(quad.ctypes.data, len(quad), quad.shape[1], n_lin, mode, device, ctypes.byref(h)))
     return _take(h, mode)
 
 
-def solve_xl3_quad_terms(lin, term_off, ta, tb, n_lin: int, mode: int = MODE_SINGLE, device: int = 0) -> Solution:
-    """The factored system uploaded, expanded, multiplied and solved on the device (gf2bv_solve_xl3_quad_terms): what
-    solve_xl3_words returns for quad_expand_words of the same arrays."""
+def _solve_xl_quad_terms(degree: int, lin, term_off, ta, tb, n_lin: int, mode: int = MODE_SINGLE, device: int = 0) -> Solution:
+    """The factored system uploaded, expanded, multiplied and solved on the device (gf2bv_solve_xl3_quad_terms / _xl4_): what
+    solve_xl3_words / solve_xl4_words returns for quad_expand_words of the same arrays."""
     lin, term_off, ta, tb = _quad_terms(lin, term_off, ta, tb, n_lin)
     h = ctypes.c_void_p()
-    _check(lib().gf2bv_solve_xl3_quad_terms(*_ptrs(lin, term_off, ta, tb), len(lin), n_lin, mode, device, ctypes.byref(h)))
+    _check(_xl_fn(degree, "gf2bv_solve_xl{}_quad_terms")(*_ptrs(lin, term_off, ta, tb), len(lin), n_lin, mode, device, ctypes.byref(h)))
     return _take(h, mode)
 
 
@@ -800,7 +826,7 @@ def quad_specialise_device(d_quad: int, m: int, quad_stride: int, n_lin: int, gu
                                               sys_stride, device, stream or None))
 
 
-def xl3_expand_batch_words(quads, n_lin: int, rows: int | None = None, stride_words: int | None = None, sys_stride_words: int | None = None,
+def _xl_expand_batch_words(degree: int, quads, n_lin: int, rows: int | None = None, stride_words: int | None = None, sys_stride_words: int | None = None,
                            device: int = 0) -> np.ndarray:
     """The degree-3 XL expansion of nsys systems in one launch (gf2bv_xl3_expand_batch_words): `quads` is [nsys, m, quad_stride]
     uint64; the result is [nsys, sys_stride_words] uint64, system s its `rows` rows stride_words apart from word 0 of element s
@@ -809,59 +835,150 @@ def xl3_expand_batch_words(quads, n_lin: int, rows: int | None = None, stride_wo
     if quads.ndim != 3:
         raise ValueError("the systems must be a 3-D uint64 array: system, equation, word")
     nsys, m, qs = quads.shape
-    rows = m * (n_lin + 1) if rows is None else rows
-    stride = (xl3_cols(n_lin) + 1 + 63) // 64 if stride_words is None else stride_words
+    rows = m * _xl_rows_per_eq(degree, n_lin) if rows is None else rows
+    stride = (_xl_cols(degree, n_lin) + 1 + 63) // 64 if stride_words is None else stride_words
     sys_stride = rows * stride if sys_stride_words is None else sys_stride_words
     out = np.zeros((nsys, max(sys_stride, 0)), dtype=np.uint64)
-    _check(lib().gf2bv_xl3_expand_batch_words(quads.ctypes.data, nsys, m * qs, m, qs, n_lin, rows, out.ctypes.data, stride, sys_stride,
+    _check(_xl_fn(degree, "gf2bv_xl{}_expand_batch_words")(quads.ctypes.data, nsys, m * qs, m, qs, n_lin, rows, out.ctypes.data, stride, sys_stride,
                                               device))
     return out
 
 
-def xl3_expand_batch_device(d_quad: int, nsys: int, quad_sys_stride: int, m: int, quad_stride: int, n_lin: int, rows: int, d_aug: int,
+def _xl_expand_batch_device(degree: int, d_quad: int, nsys: int, quad_sys_stride: int, m: int, quad_stride: int, n_lin: int, rows: int, d_aug: int,
                             stride: int, sys_stride: int, device: int = 0, stream: int = 0) -> None:
     """xl3_expand_batch_words with everything resident in device memory: enqueued on `stream`, the call returns; a
     solve_batch_device with the same stream reads the finished systems."""
-    _check(lib().gf2bv_xl3_expand_batch_device(d_quad, nsys, quad_sys_stride, m, quad_stride, n_lin, rows, d_aug, stride, sys_stride,
+    _check(_xl_fn(degree, "gf2bv_xl{}_expand_batch_device")(d_quad, nsys, quad_sys_stride, m, quad_stride, n_lin, rows, d_aug, stride, sys_stride,
                                                device, stream or None))
 
 
-def solve_xl3_guess_words(quad, n_lin: int, guess, a0: int = 0, na: int | None = None, mode: int = MODE_SINGLE, device: int = 0) -> list:
+def _solve_xl_guess_words(degree: int, quad, n_lin: int, guess, a0: int = 0, na: int | None = None, mode: int = MODE_SINGLE, device: int = 0) -> list:
     """Hybrid XL (gf2bv_solve_xl3_guess_words): the quadratic rows uploaded, specialised for the assignments a0 .. a0 + na - 1 of the
     guessed unknowns, every assignment's rows multiplied and all systems solved as lock-step gangs.  Element s is what
     solve_xl3_words returns for quad_specialise_words(...)[s] over n_lin - len(guess) unknowns."""
     quad, guess = _quad_rows(quad), _guess(guess)
     na = _assignments(guess, a0, na)
     hs = _handles(na)
-    rc = lib().gf2bv_solve_xl3_guess_words(quad.ctypes.data, len(quad), quad.shape[1], n_lin, guess.ctypes.data, len(guess), a0, na,
+    rc = _xl_fn(degree, "gf2bv_solve_xl{}_guess_words")(quad.ctypes.data, len(quad), quad.shape[1], n_lin, guess.ctypes.data, len(guess), a0, na,
                                            mode, device, hs)
     return _take_all(hs, max(na, 0), rc, mode)
 
 
-def solve_xl3_guess_quad_terms(lin, term_off, ta, tb, n_lin: int, guess, a0: int = 0, na: int | None = None, mode: int = MODE_SINGLE,
+def _solve_xl_guess_quad_terms(degree: int, lin, term_off, ta, tb, n_lin: int, guess, a0: int = 0, na: int | None = None, mode: int = MODE_SINGLE,
                                device: int = 0) -> list:
     """solve_xl3_guess_words on a factored system: expanded on the device first (gf2bv_solve_xl3_guess_quad_terms)."""
     lin, term_off, ta, tb = _quad_terms(lin, term_off, ta, tb, n_lin)
     guess = _guess(guess)
     na = _assignments(guess, a0, na)
     hs = _handles(na)
-    rc = lib().gf2bv_solve_xl3_guess_quad_terms(*_ptrs(lin, term_off, ta, tb), len(lin), n_lin, guess.ctypes.data, len(guess), a0, na,
+    rc = _xl_fn(degree, "gf2bv_solve_xl{}_guess_quad_terms")(*_ptrs(lin, term_off, ta, tb), len(lin), n_lin, guess.ctypes.data, len(guess), a0, na,
                                                 mode, device, hs)
     return _take_all(hs, max(na, 0), rc, mode)
 
 
-def xl3_guess_chunk(m: int, n_lin: int, nguess: int, free_bytes: int | None = None, device: int = 0) -> int:
+def _xl_guess_chunk(degree: int, m: int, n_lin: int, nguess: int, free_bytes: int | None = None, device: int = 0) -> int:
     """How many assignments one solve_xl3_guess_* call should take: the largest count (at most 2^nguess) whose specialised rows and
     expansions fit a quarter of free_bytes; 0 when one system does not fit.  free_bytes None: the free memory of `device`
     (gf2bv_xl3_guess_chunk_device); given: a pure function, no device is touched (gf2bv_xl3_guess_chunk)."""
     if free_bytes is None:
         chunk = ctypes.c_int64()
-        _check(lib().gf2bv_xl3_guess_chunk_device(m, n_lin, nguess, device, ctypes.byref(chunk)))
+        _check(_xl_fn(degree, "gf2bv_xl{}_guess_chunk_device")(m, n_lin, nguess, device, ctypes.byref(chunk)))
         return int(chunk.value)
-    chunk = int(lib().gf2bv_xl3_guess_chunk(m, n_lin, nguess, free_bytes))
+    chunk = int(_xl_fn(degree, "gf2bv_xl{}_guess_chunk")(m, n_lin, nguess, free_bytes))
     if chunk < 0:
         raise ValueError("m, n_lin, nguess or free_bytes out of range")
     return chunk
+
+
+# -- the public names: each body above for degree 3 and for degree 4 ---------------------------------------------------------------------
+def xl3_expand_words(quad, n_lin: int, rows: int | None = None, stride_words: int | None = None, device: int = 0) -> np.ndarray:
+    """_xl_expand_words for degree 3"""
+    return _xl_expand_words(3, quad, n_lin, rows, stride_words, device)
+
+
+def xl4_expand_words(quad, n_lin: int, rows: int | None = None, stride_words: int | None = None, device: int = 0) -> np.ndarray:
+    """_xl_expand_words for degree 4"""
+    return _xl_expand_words(4, quad, n_lin, rows, stride_words, device)
+
+
+def xl3_expand_device(d_quad: int, m: int, quad_stride: int, n_lin: int, rows: int, d_aug: int, stride: int, device: int = 0, stream: int = 0) -> None:
+    """_xl_expand_device for degree 3"""
+    return _xl_expand_device(3, d_quad, m, quad_stride, n_lin, rows, d_aug, stride, device, stream)
+
+
+def xl4_expand_device(d_quad: int, m: int, quad_stride: int, n_lin: int, rows: int, d_aug: int, stride: int, device: int = 0, stream: int = 0) -> None:
+    """_xl_expand_device for degree 4"""
+    return _xl_expand_device(4, d_quad, m, quad_stride, n_lin, rows, d_aug, stride, device, stream)
+
+
+def solve_xl3_words(quad, n_lin: int, mode: int = MODE_SINGLE, device: int = 0) -> Solution:
+    """_solve_xl_words for degree 3"""
+    return _solve_xl_words(3, quad, n_lin, mode, device)
+
+
+def solve_xl4_words(quad, n_lin: int, mode: int = MODE_SINGLE, device: int = 0) -> Solution:
+    """_solve_xl_words for degree 4"""
+    return _solve_xl_words(4, quad, n_lin, mode, device)
+
+
+def solve_xl3_quad_terms(lin, term_off, ta, tb, n_lin: int, mode: int = MODE_SINGLE, device: int = 0) -> Solution:
+    """_solve_xl_quad_terms for degree 3"""
+    return _solve_xl_quad_terms(3, lin, term_off, ta, tb, n_lin, mode, device)
+
+
+def solve_xl4_quad_terms(lin, term_off, ta, tb, n_lin: int, mode: int = MODE_SINGLE, device: int = 0) -> Solution:
+    """_solve_xl_quad_terms for degree 4"""
+    return _solve_xl_quad_terms(4, lin, term_off, ta, tb, n_lin, mode, device)
+
+
+def xl3_expand_batch_words(quads, n_lin: int, rows: int | None = None, stride_words: int | None = None, sys_stride_words: int | None = None, device: int = 0) -> np.ndarray:
+    """_xl_expand_batch_words for degree 3"""
+    return _xl_expand_batch_words(3, quads, n_lin, rows, stride_words, sys_stride_words, device)
+
+
+def xl4_expand_batch_words(quads, n_lin: int, rows: int | None = None, stride_words: int | None = None, sys_stride_words: int | None = None, device: int = 0) -> np.ndarray:
+    """_xl_expand_batch_words for degree 4"""
+    return _xl_expand_batch_words(4, quads, n_lin, rows, stride_words, sys_stride_words, device)
+
+
+def xl3_expand_batch_device(d_quad: int, nsys: int, quad_sys_stride: int, m: int, quad_stride: int, n_lin: int, rows: int, d_aug: int, stride: int, sys_stride: int, device: int = 0, stream: int = 0) -> None:
+    """_xl_expand_batch_device for degree 3"""
+    return _xl_expand_batch_device(3, d_quad, nsys, quad_sys_stride, m, quad_stride, n_lin, rows, d_aug, stride, sys_stride, device, stream)
+
+
+def xl4_expand_batch_device(d_quad: int, nsys: int, quad_sys_stride: int, m: int, quad_stride: int, n_lin: int, rows: int, d_aug: int, stride: int, sys_stride: int, device: int = 0, stream: int = 0) -> None:
+    """_xl_expand_batch_device for degree 4"""
+    return _xl_expand_batch_device(4, d_quad, nsys, quad_sys_stride, m, quad_stride, n_lin, rows, d_aug, stride, sys_stride, device, stream)
+
+
+def solve_xl3_guess_words(quad, n_lin: int, guess, a0: int = 0, na: int | None = None, mode: int = MODE_SINGLE, device: int = 0) -> list:
+    """_solve_xl_guess_words for degree 3"""
+    return _solve_xl_guess_words(3, quad, n_lin, guess, a0, na, mode, device)
+
+
+def solve_xl4_guess_words(quad, n_lin: int, guess, a0: int = 0, na: int | None = None, mode: int = MODE_SINGLE, device: int = 0) -> list:
+    """_solve_xl_guess_words for degree 4"""
+    return _solve_xl_guess_words(4, quad, n_lin, guess, a0, na, mode, device)
+
+
+def solve_xl3_guess_quad_terms(lin, term_off, ta, tb, n_lin: int, guess, a0: int = 0, na: int | None = None, mode: int = MODE_SINGLE, device: int = 0) -> list:
+    """_solve_xl_guess_quad_terms for degree 3"""
+    return _solve_xl_guess_quad_terms(3, lin, term_off, ta, tb, n_lin, guess, a0, na, mode, device)
+
+
+def solve_xl4_guess_quad_terms(lin, term_off, ta, tb, n_lin: int, guess, a0: int = 0, na: int | None = None, mode: int = MODE_SINGLE, device: int = 0) -> list:
+    """_solve_xl_guess_quad_terms for degree 4"""
+    return _solve_xl_guess_quad_terms(4, lin, term_off, ta, tb, n_lin, guess, a0, na, mode, device)
+
+
+def xl3_guess_chunk(m: int, n_lin: int, nguess: int, free_bytes: int | None = None, device: int = 0) -> int:
+    """_xl_guess_chunk for degree 3"""
+    return _xl_guess_chunk(3, m, n_lin, nguess, free_bytes, device)
+
+
+def xl4_guess_chunk(m: int, n_lin: int, nguess: int, free_bytes: int | None = None, device: int = 0) -> int:
+    """_xl_guess_chunk for degree 4"""
+    return _xl_guess_chunk(4, m, n_lin, nguess, free_bytes, device)
 
 
 def synth_device(d_ptr: int, rows: int, cols: int, stride: int, seed: int, device: int = 0, stream: int = 0):

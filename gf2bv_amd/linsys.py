@@ -10,7 +10,7 @@ from __future__ import annotations
 from typing import Iterable, Optional, Sequence, Union
 
 from ._internal import (AffineSpace, QuadSearchGaveUp, eqs_to_sage_mat_helper, m4ri_solve, m4ri_solve_many, m4ri_solve_rhs, m4ri_solve_xl3, m4ri_solve_xl3_guess,
-                        mul_bit_quad)
+                        m4ri_solve_xl4, m4ri_solve_xl4_guess, mul_bit_quad)
 from .bitvec import BitVec
 
 Zeros = Sequence[Union[BitVec, int]]
@@ -245,6 +245,17 @@ def xl3_triple_col(n: int, i: int, j: int, l: int) -> int:
     return n + n * (n - 1) // 2 + i * (i - 1) * (i - 2) // 6 + j * (j - 1) // 2 + l
 
 
+# -- degree 4 adds the quadruples behind degree 3's columns ---------------------------------------------------------------------------------
+def xl4_cols(n: int) -> int:
+    return xl3_cols(n) + n * (n - 1) * (n - 2) * (n - 3) // 24
+
+
+def xl4_quad_col(n: int, i: int, j: int, l: int, p: int) -> int:
+    """column of x_i x_j x_l x_p, p < l < j < i"""
+    assert 0 <= p < l < j < i < n
+    return xl3_cols(n) + i * (i - 1) * (i - 2) * (i - 3) // 24 + j * (j - 1) * (j - 2) // 6 + l * (l - 1) // 2 + p
+
+
 class _QuadraticPoints:
     """What a linearised quadratic system does with the solutions of its linear solve, shared by ``QuadraticSystem`` and the packed
     front-end's ``PackedQuadraticSystem``: the points whose product unknowns equal the products of their linear part.  Needs
@@ -336,7 +347,10 @@ class _QuadraticPoints:
     # -- degree-3 XL (no counterpart in the reference) ----------------------------------------------------------
     # Every equation is multiplied by 1 and by each unknown on the device and the system is linearised over the n + C(n,2) + C(n,3)
     # monomials of degree <= 3 (xl3_cols): about n^2 / 6 independent quadratic equations pin the solution down where plain
-    # linearisation needs n^2 / 2.  The class mixed into supplies _solve_internal_xl(zeros, mode) and get_eqs_xl(zeros).
+    # linearisation needs n^2 / 2.  The class mixed into supplies _solve_internal_xl(zeros, mode, degree) and get_eqs_xl(zeros).
+    # Degree-4 XL (the *_xl4 methods) multiplies by every pair x_a x_b too and linearises over the monomials of degree <= 4 (xl4_cols): about
+    # n^2 / 12 equations.  The multipliers reach the equations' own degree, so f_i f_j = f_j f_i and f_i f_i = f_i: the m(1 + n + C(n,2))
+    # rows have rank at most that minus m + C(m,2).  Both degrees run through the same methods underneath, which take the degree.
     @staticmethod
     def _check_degree(degree: int):
         if degree != 3:
@@ -344,6 +358,12 @@ class _QuadraticPoints:
 
     def solve_raw_one_xl(self, zeros: Zeros):
         return self._solve_internal_xl(zeros, 0)
+
+    def solve_raw_one_xl4(self, zeros: Zeros):
+        return self._solve_internal_xl(zeros, 0, 4)
+
+    def solve_raw_space_xl4(self, zeros: Zeros):
+        return self._solve_internal_xl(zeros, 1, 4)
 
     def solve_raw_space_xl(self, zeros: Zeros):
         return self._solve_internal_xl(zeros, 1)
@@ -362,15 +382,33 @@ class _QuadraticPoints:
             idx = cache[n] = (pi, pj, ti, tj, tl)
         return idx
 
-    def _xl_products_match(self, s: int, n: int) -> bool:
-        """every pair and triple coordinate of a raw point over the cubic columns of n unknowns is the product of its linear bits"""
+    def _xl4_index(self, n: int):
+        """the same for the quadruple columns: i, then j, then l, then p"""
+        cache = self.__dict__.setdefault("_xl4_index_cache", {})
+        idx = cache.get(n)
+        if idx is None:
+            import numpy as np                         # noqa: PLC0415
+            a = np.arange(n)
+            idx = cache[n] = np.nonzero((a[:, None, None, None] > a[None, :, None, None]) & (a[None, :, None, None] > a[None, None, :, None])
+                                        & (a[None, None, :, None] > a[None, None, None, :]))
+        return idx
+
+    def _xl_products_match(self, s: int, n: int, degree: int = 3) -> bool:
+        """every pair and triple (degree 4: and quadruple) coordinate of a raw point over the XL columns of n unknowns is the product
+        of its linear bits"""
         import numpy as np                             # noqa: PLC0415
         cols3 = xl3_cols(n)
-        assert s >> cols3 == 0, "Invalid solution"
-        bits = np.unpackbits(np.frombuffer(s.to_bytes((cols3 + 7) // 8, "little"), dtype=np.uint8), bitorder="little")[:cols3]
+        cols = xl4_cols(n) if degree == 4 else cols3
+        assert s >> cols == 0, "Invalid solution"
+        bits = np.unpackbits(np.frombuffer(s.to_bytes((cols + 7) // 8, "little"), dtype=np.uint8), bitorder="little")[:cols]
         pi, pj, ti, tj, tl = self._xl_index(n)
-        lin, pairs, triples = bits[:n], bits[n:n + len(pi)], bits[n + len(pi):]
-        return bool(np.array_equal(pairs, lin[pi] & lin[pj]) and np.array_equal(triples, lin[ti] & lin[tj] & lin[tl]))
+        lin, pairs, triples = bits[:n], bits[n:n + len(pi)], bits[n + len(pi):cols3]
+        if not (np.array_equal(pairs, lin[pi] & lin[pj]) and np.array_equal(triples, lin[ti] & lin[tj] & lin[tl])):
+            return False
+        if degree == 4:
+            qi, qj, ql, qp = self._xl4_index(n)
+            return bool(np.array_equal(bits[cols3:], lin[qi] & lin[qj] & lin[ql] & lin[qp]))
+        return True
 
     def convert_sol_xl(self, s: int) -> Optional[tuple]:
         """the linear parts of a raw point over the cubic columns when every pair and triple coordinate is the product of its linear
@@ -380,10 +418,30 @@ class _QuadraticPoints:
             return None
         return self._convert_sol(s & ((1 << n) - 1))[:-1]
 
+    def convert_sol_xl4(self, s: int) -> Optional[tuple]:
+        """convert_sol_xl over the quartic columns: the quadruple coordinates are checked too"""
+        n = self._lin_size
+        if not self._xl_products_match(s, n, 4):
+            return None
+        return self._convert_sol(s & ((1 << n) - 1))[:-1]
+
     def solve_all_xl(self, zeros: Zeros, *, degree: int = 3, max_dimension: int = 16):
         """solve_all through degree-3 XL: the consistent points of the cubic system's solution space, in AffineSpace order"""
         self._check_degree(degree)
-        space = self.solve_raw_space_xl(zeros)
+        return self._solve_all_xl(zeros, max_dimension, 3)
+
+    def solve_all_xl4(self, zeros: Zeros, *, max_dimension: int = 16):
+        """solve_all through degree-4 XL (multipliers 1, x_k and x_a x_b; about n^2 / 12 equations): the consistent points of the
+        quartic system's solution space, in AffineSpace order"""
+        return self._solve_all_xl(zeros, max_dimension, 4)
+
+    def solve_one_xl4(self, zeros: Zeros):
+        for sol in self.solve_all_xl4(zeros):
+            return sol
+        return None
+
+    def _solve_all_xl(self, zeros: Zeros, max_dimension: int, degree: int):
+        space = self._solve_internal_xl(zeros, 1, degree)
         if space is None:
             return
         if space.dimension > max_dimension:
@@ -393,7 +451,7 @@ class _QuadraticPoints:
                 space=space,
             )
         for raw in space:
-            sol = self.convert_sol_xl(raw)
+            sol = self.convert_sol_xl4(raw) if degree == 4 else self.convert_sol_xl(raw)
             if sol is not None:
                 yield sol
 
@@ -407,7 +465,7 @@ class _QuadraticPoints:
     # With fewer equations than degree-3 XL needs, f unknowns are fixed in all 2^f ways: assignment a sets unknown guess[t] to bit t of
     # a and leaves a quadratic system in the other n - f unknowns (renumbered in increasing index), which needs about (n - f)^2 / 6
     # equations.  The device substitutes, multiplies and solves every assignment's system as one batch.  The class mixed into supplies
-    # _solve_internal_xl_guess(zeros, guess, mode) -> None (every assignment inconsistent) or (number of equations, run) with
+    # _solve_internal_xl_guess(zeros, guess, mode) (degree 4: _solve_internal_xl4_guess) -> None (every assignment inconsistent) or (number of equations, run) with
     # run(first, count) the list of raw results of the assignments first .. first + count - 1.
     def _parse_guess(self, guess) -> list:
         """the flattened unknown index of every item: an int, or a one-bit BitVec / PackedBitVec that is exactly one unknown"""
@@ -433,21 +491,21 @@ class _QuadraticPoints:
             raise ValueError(f"at most min(n - 1, 30) = {min(n - 1, 30)} unknowns can be guessed, not {len(out)}")
         return out
 
-    def _xl_guess_chunks(self, zeros: Zeros, guess, assignments, mode: int):
+    def _xl_guess_chunks(self, zeros: Zeros, guess, assignments, mode: int, degree: int = 3):
         """(first assignment, raw results) chunk by chunk, the next chunk solved only when it is asked for"""
         g = self._parse_guess(guess)
         first, count = (0, 1 << len(g)) if assignments is None else assignments
         if first < 0 or count < 0 or first + count > 1 << len(g):
             raise ValueError(f"assignments must be a range (first, count) inside 0..{(1 << len(g)) - 1}")
-        staged = self._solve_internal_xl_guess(zeros, g, mode)
+        staged = (self._solve_internal_xl4_guess if degree == 4 else self._solve_internal_xl_guess)(zeros, g, mode)
         if staged is None:
             yield first, [None] * count
             return
         m, run = staged
         from . import hip                              # noqa: PLC0415  (ctypes binding, first use only)
-        chunk = hip.xl3_guess_chunk(m, self._lin_size, len(g))
+        chunk = (hip.xl4_guess_chunk if degree == 4 else hip.xl3_guess_chunk)(m, self._lin_size, len(g))
         if chunk < 1:
-            raise MemoryError("one assignment's degree-3 XL system does not fit a quarter of the free device memory")
+            raise MemoryError(f"one assignment's degree-{degree} XL system does not fit a quarter of the free device memory")
         end = first + count
         while first < end:
             na = min(chunk, end - first)
@@ -463,16 +521,28 @@ class _QuadraticPoints:
         remaining unknowns"""
         return [raw for _, raws in self._xl_guess_chunks(zeros, guess, assignments, 1) for raw in raws]
 
+    def solve_raw_one_xl4_guess(self, zeros: Zeros, guess, assignments=None) -> list:
+        """solve_raw_one_xl_guess over the quartic columns of the remaining unknowns"""
+        return [raw for _, raws in self._xl_guess_chunks(zeros, guess, assignments, 0, 4) for raw in raws]
+
+    def solve_raw_space_xl4_guess(self, zeros: Zeros, guess, assignments=None) -> list:
+        """solve_raw_space_xl_guess over the quartic columns of the remaining unknowns"""
+        return [raw for _, raws in self._xl_guess_chunks(zeros, guess, assignments, 1, 4) for raw in raws]
+
+    def convert_sol_xl4_guess(self, raw: int, guess, assignment: int) -> Optional[tuple]:
+        """convert_sol_xl_guess of a raw point over the quartic columns of the remaining unknowns"""
+        return self._scatter_guess(raw, self._parse_guess(guess), assignment, 4)
+
     def convert_sol_xl_guess(self, raw: int, guess, assignment: int) -> Optional[tuple]:
         """convert_sol_xl of a raw point of assignment `assignment`'s system: the check over the remaining unknowns, then their bits
         and the guessed ones scattered into the solution; None when a product coordinate disagrees"""
         g = self._parse_guess(guess)
         return self._scatter_guess(raw, g, assignment)
 
-    def _scatter_guess(self, raw: int, g: list, assignment: int) -> Optional[tuple]:
+    def _scatter_guess(self, raw: int, g: list, assignment: int, degree: int = 3) -> Optional[tuple]:
         n = self._lin_size
         ns = n - len(g)
-        if not self._xl_products_match(raw, ns):
+        if not self._xl_products_match(raw, ns, degree):
             return None
         full = 0
         for t, idx in enumerate(g):
@@ -486,8 +556,20 @@ class _QuadraticPoints:
         """the consistent points of every assignment's degree-3 XL system, in assignment order and within an assignment in AffineSpace
         order; the assignments are solved a chunk at a time (hip.xl3_guess_chunk), the next chunk when more is asked for"""
         self._check_degree(degree)
+        return self._solve_all_xl_guess(zeros, guess, max_dimension, assignments, 3)
+
+    def solve_all_xl4_guess(self, zeros: Zeros, guess, *, max_dimension: int = 16, assignments=None):
+        """solve_all_xl_guess with every assignment's degree-4 XL system (about (n - f)^2 / 12 equations)"""
+        return self._solve_all_xl_guess(zeros, guess, max_dimension, assignments, 4)
+
+    def solve_one_xl4_guess(self, zeros: Zeros, guess, *, max_dimension: int = 16):
+        for sol in self.solve_all_xl4_guess(zeros, guess, max_dimension=max_dimension):
+            return sol
+        return None
+
+    def _solve_all_xl_guess(self, zeros: Zeros, guess, max_dimension: int, assignments, degree: int):
         g = self._parse_guess(guess)
-        for first, spaces in self._xl_guess_chunks(zeros, g, assignments, 1):
+        for first, spaces in self._xl_guess_chunks(zeros, g, assignments, 1, degree):
             for k, space in enumerate(spaces):
                 if space is None:
                     continue
@@ -498,7 +580,7 @@ class _QuadraticPoints:
                         space=space,
                     )
                 for raw in space:
-                    sol = self._scatter_guess(raw, g, first + k)
+                    sol = self._scatter_guess(raw, g, first + k, degree)
                     if sol is not None:
                         yield sol
 
@@ -507,16 +589,16 @@ class _QuadraticPoints:
             return sol
         return None
 
-    def _xl_eqs(self, quad) -> list:
-        """quadratic rows of the augmented-words layout -> the equation ints of their degree-3 XL rows (bit 0 the constant, bit 1 + c
-        column c), multiplied on the device, zeros dropped"""
+    def _xl_eqs(self, quad, degree: int = 3) -> list:
+        """quadratic rows of the augmented-words layout -> the equation ints of their XL rows of that degree (bit 0 the constant,
+        bit 1 + c column c), multiplied on the device, zeros dropped"""
         from . import hip                              # noqa: PLC0415  (ctypes binding, first use only)
         if not len(quad):
             return []
-        cols3 = xl3_cols(self._lin_size)
+        cols3 = xl4_cols(self._lin_size) if degree == 4 else xl3_cols(self._lin_size)
         mask = (1 << cols3) - 1
         eqs = []
-        for r in hip.xl3_expand_words(quad, self._lin_size):
+        for r in (hip.xl4_expand_words if degree == 4 else hip.xl3_expand_words)(quad, self._lin_size):
             v = int.from_bytes(r.tobytes(), "little")
             eqs.append(((v & mask) << 1) | (v >> cols3))
         return [e for e in eqs if e]
@@ -592,20 +674,34 @@ class QuadraticSystem(_QuadraticPoints, LinearSystem):
         return self._bit_assert(a._bits[0], v)
 
     # -- degree-3 XL: the equation ints go down as they are, the device multiplies and pads them ------------------------------------------
-    def _solve_internal_xl(self, zeros: Zeros, mode: int):
+    def _solve_internal_xl(self, zeros: Zeros, mode: int, degree: int = 3):
         eqs = self.get_eqs(zeros)
         if 1 in eqs:                            # the equation "1 = 0"
             return None
-        return m4ri_solve_xl3(eqs, self._lin_size, mode)
+        return (m4ri_solve_xl4 if degree == 4 else m4ri_solve_xl3)(eqs, self._lin_size, mode)
 
     def _solve_internal_xl_guess(self, zeros: Zeros, guess: list, mode: int):
+        return self._stage_xl_guess(zeros, guess, mode, 3)
+
+    def _solve_internal_xl4_guess(self, zeros: Zeros, guess: list, mode: int):
+        return self._stage_xl_guess(zeros, guess, mode, 4)
+
+    def _stage_xl_guess(self, zeros: Zeros, guess: list, mode: int, degree: int):
         eqs = self.get_eqs(zeros)
         if 1 in eqs:                            # the equation "1 = 0": under every assignment
             return None
-        return len(eqs), lambda first, count: m4ri_solve_xl3_guess(eqs, self._lin_size, guess, first, count, mode)
+        solve = m4ri_solve_xl4_guess if degree == 4 else m4ri_solve_xl3_guess
+        return len(eqs), lambda first, count: solve(eqs, self._lin_size, guess, first, count, mode)
 
     def get_eqs_xl(self, zeros: Zeros) -> list:
         """the equations and their products with every unknown as equation ints over the cubic columns (needs the GPU and numpy)"""
+        return self._get_eqs_xl(zeros, 3)
+
+    def get_eqs_xl4(self, zeros: Zeros) -> list:
+        """the equations and their products with every unknown and every pair of unknowns as equation ints over the quartic columns"""
+        return self._get_eqs_xl(zeros, 4)
+
+    def _get_eqs_xl(self, zeros: Zeros, degree: int) -> list:
         import numpy as np                             # noqa: PLC0415
         eqs = self.get_eqs(zeros)
         words = (self._cols + 1 + 63) // 64
@@ -613,4 +709,4 @@ class QuadraticSystem(_QuadraticPoints, LinearSystem):
         quad = np.zeros((len(eqs), words), dtype=np.uint64)
         for r, e in enumerate(eqs):
             quad[r] = np.frombuffer((((e >> 1) & mask) | ((e & 1) << self._cols)).to_bytes(8 * words, "little"), dtype=np.uint64)
-        return self._xl_eqs(quad)
+        return self._xl_eqs(quad, degree)

@@ -22,7 +22,7 @@ from typing import Iterable, Optional, Sequence
 import numpy as np
 
 from ._internal import (m4ri_solve_many_quad_packed, m4ri_solve_packed, m4ri_solve_quad_packed, m4ri_solve_xl3_guess_quad_packed,
-                        m4ri_solve_xl3_quad_packed)
+                        m4ri_solve_xl3_quad_packed, m4ri_solve_xl4_guess_quad_packed, m4ri_solve_xl4_quad_packed)
 from .bitvec import BitVec
 from .linsys import DimensionTooLargeError, _QuadraticPoints
 
@@ -548,21 +548,35 @@ class PackedQuadraticSystem(_QuadraticPoints, PackedLinearSystem):
         return m4ri_solve_quad_packed(lin, off, ta, tb, self._lin_size, max(len(lin), self._cols), mode)      # (the boundary wants rows >= cols)
 
     # -- degree-3 XL: the factored arrays go down, the device expands, multiplies and pads them (nothing is decided on the host) ----
-    def _solve_internal_xl(self, zeros: Sequence, mode: int):
+    def _solve_internal_xl(self, zeros: Sequence, mode: int, degree: int = 3):
         lin, off, ta, tb = self._terms(zeros)
-        return m4ri_solve_xl3_quad_packed(lin, off, ta, tb, self._lin_size, mode)
+        return (m4ri_solve_xl4_quad_packed if degree == 4 else m4ri_solve_xl3_quad_packed)(lin, off, ta, tb, self._lin_size, mode)
 
     def _solve_internal_xl_guess(self, zeros: Sequence, guess: list, mode: int):
+        return self._stage_xl_guess(zeros, guess, mode, 3)
+
+    def _solve_internal_xl4_guess(self, zeros: Sequence, guess: list, mode: int):
+        return self._stage_xl_guess(zeros, guess, mode, 4)
+
+    def _stage_xl_guess(self, zeros: Sequence, guess: list, mode: int, degree: int):
         lin, off, ta, tb = self._terms(zeros)
-        return len(lin), lambda first, count: m4ri_solve_xl3_guess_quad_packed(lin, off, ta, tb, self._lin_size, guess, first, count, mode)
+        solve = m4ri_solve_xl4_guess_quad_packed if degree == 4 else m4ri_solve_xl3_guess_quad_packed
+        return len(lin), lambda first, count: solve(lin, off, ta, tb, self._lin_size, guess, first, count, mode)
 
     def get_eqs_xl(self, zeros: Sequence) -> list:
         """the equations and their products with every unknown as equation ints over the cubic columns (needs the GPU)"""
+        return self._get_eqs_xl(zeros, 3)
+
+    def _get_eqs_xl(self, zeros: Sequence, degree: int) -> list:
         from . import hip                              # noqa: PLC0415
         lin, off, ta, tb = self._terms(zeros)
         if not len(lin):
             return []
-        return self._xl_eqs(hip.quad_expand_words(lin, off, ta, tb, self._lin_size))
+        return self._xl_eqs(hip.quad_expand_words(lin, off, ta, tb, self._lin_size), degree)
+
+    def get_eqs_xl4(self, zeros: Sequence) -> list:
+        """the equations and their products with every unknown and every pair of unknowns as equation ints over the quartic columns"""
+        return self._get_eqs_xl(zeros, 4)
 
     # -- a kept factorization, many right-hand sides, batches: QuadraticSystem's methods on the factored arrays --------------------
     # (solve_*_rhs are PackedLinearSystem's through ``factor``; solve_one_rhs is QuadraticSystem's own, _QuadraticPoints)

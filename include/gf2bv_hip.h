@@ -486,6 +486,47 @@ int gf2bv_solve_xl3_guess_quad_terms(const uint64_t *lin, const int64_t *term_of
 int64_t gf2bv_xl3_guess_chunk(int64_t m, int64_t n_lin, int64_t nguess, int64_t free_bytes);
 int gf2bv_xl3_guess_chunk_device(int64_t m, int64_t n_lin, int64_t nguess, int device, int64_t *chunk);
 
+/* ---- degree-4 XL: quadratic equations multiplied by 1, by every unknown and by every pair of unknowns, on the device ----------------
+ * The xl4 entries are the xl3 entries above with the same arguments, stream-ordering and staging contracts; only the layout differs.
+ * Input: m quadratic rows as for degree 3.
+ * Columns: cols4 = cols3 + C(n_lin,4).  The first cols3 columns are exactly degree 3's; the quadruple (i, j, l, p), p < l < j < i, is at
+ * column cols3 + C(i,4) + C(j,3) + C(l,2) + p; the constant at column cols4; every bit from cols4 + 1 to the end of the stride zero.
+ * Rows: equation e owns R4 = 1 + n_lin + C(n_lin,2) rows from e * R4: f_e itself; x_k f_e at offset 1 + k, k = 0 .. n_lin - 1;
+ * x_a x_b f_e, b < a, at offset 1 + n_lin + C(a,2) + b.  Rows m * R4 .. rows - 1 are written as zeros; the solve entries use
+ * rows = max(m * R4, cols4).
+ * Products, for f = c + sum l_i x_i + sum q_ij x_i x_j and S = {a, b}: x_a x_b f has the constant and every unknown 0, the pair S
+ * = c ^ l_a ^ l_b ^ q_ab and every other pair 0, the triple S + {i} = l_i ^ q_ia ^ q_ib, the quadruple S + {i, j} = q_ij, and every
+ * monomial that does not contain S 0.  The rows f and x_k f are degree 3's with zero quadruple columns.
+ * Rank: the multipliers reach the equations' own degree, so f_i f_j and f_j f_i coincide and f_i f_i = f_i: before saturation the
+ * rank of the m * R4 rows is m * R4 - m - C(m,2).
+ * gf2bv_xl4_expand_device / _words (k_xl4_expand), gf2bv_solve_xl4_words, gf2bv_solve_xl4_quad_terms, gf2bv_xl4_expand_batch_device /
+ * _words (k_xl4_expand_batch), gf2bv_solve_xl4_guess_words / _quad_terms (gf2bv_quad_specialise_device's rows over n' = n_lin - nguess
+ * unknowns, expanded to degree 4 and solved as one batch over cols4(n') columns), gf2bv_xl4_guess_chunk / _chunk_device: as their xl3
+ * twins.  GF2BV_ERR_ARG before any device is touched for the same reasons, with cols4 in place of cols3 and m * R4 in place of
+ * m(n_lin + 1): every store of the kernels lands inside rows x stride_words.
+ * gf2bv_xl4_quartic_root: the kernel's index function on the host -- the largest i >= 3 with C(i,4) <= u, -1 for u < 0 -- for checks. */
+int gf2bv_xl4_expand_device(const void *d_quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int64_t rows, void *d_aug,
+                            int64_t stride_words, int device, void *stream);
+int gf2bv_xl4_expand_words(const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int64_t rows, uint64_t *out_aug,
+                           int64_t stride_words, int device);
+int gf2bv_solve_xl4_words(const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int mode, int device,
+                          gf2bv_result **out);
+int gf2bv_solve_xl4_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t m,
+                               int64_t n_lin, int mode, int device, gf2bv_result **out);
+int gf2bv_xl4_expand_batch_device(const void *d_quad, int64_t nsys, int64_t quad_sys_stride_words, int64_t m, int64_t quad_stride_words,
+                                  int64_t n_lin, int64_t rows, void *d_aug, int64_t stride_words, int64_t sys_stride_words, int device,
+                                  void *stream);
+int gf2bv_xl4_expand_batch_words(const uint64_t *quad, int64_t nsys, int64_t quad_sys_stride_words, int64_t m, int64_t quad_stride_words,
+                                 int64_t n_lin, int64_t rows, uint64_t *out_aug, int64_t stride_words, int64_t sys_stride_words, int device);
+int gf2bv_solve_xl4_guess_words(const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, const int32_t *guess,
+                                int64_t nguess, int64_t a0, int64_t na, int mode, int device, gf2bv_result **out);
+int gf2bv_solve_xl4_guess_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t m,
+                                     int64_t n_lin, const int32_t *guess, int64_t nguess, int64_t a0, int64_t na, int mode, int device,
+                                     gf2bv_result **out);
+int64_t gf2bv_xl4_guess_chunk(int64_t m, int64_t n_lin, int64_t nguess, int64_t free_bytes);
+int gf2bv_xl4_guess_chunk_device(int64_t m, int64_t n_lin, int64_t nguess, int device, int64_t *chunk);
+int64_t gf2bv_xl4_quartic_root(int64_t u);
+
 /* ---- synthetic systems + independent residual check (bench / tests) ----------------------- */
 /* word w of row r = mix64(mix64(seed) ^ ((r<<20)|w)); planted solution = pseudo-row 0xFFFFF;
  * RHS = <row, planted>.  Writes rows x stride_words words at d_aug. */
