@@ -750,6 +750,48 @@ bool parse_quad_call(PyObject *const *args, int n_at, int rows_at, int mode_at, 
 	return rows_cover_cols(*rows, qb.cols());
 }
 
+// The factored form of a cubic system as eight C-contiguous buffers (m4ri_solve_cubic_packed's arguments: lin, off2, ta, tb, off3,
+// ua, ub, uc), checked like QuadBuffers: whole rows of Wl words, two offset arrays with one entry per row and one more, each
+// starting at 0, never decreasing and ending at the number of its operands
+struct CubicBuffers {
+	Py_buffer view[8];
+	int got = 0;
+	Py_ssize_t n = 0, live = 0;
+	CubicBuffers() = default;
+	CubicBuffers(const CubicBuffers &) = delete;
+	CubicBuffers &operator=(const CubicBuffers &) = delete;
+	~CubicBuffers() { for (int k = 0; k < got; k++) PyBuffer_Release(&view[k]); }
+	const uint64_t *words(int k) const { return static_cast<const uint64_t *>(view[k].buf); }
+	const int64_t *offsets(int k) const { return static_cast<const int64_t *>(view[k].buf); }
+	bool parse(PyObject *const *args, PyObject *n_obj)
+	{
+		n = PyLong_AsSsize_t(n_obj);
+		if (n == -1 && PyErr_Occurred()) return false;
+		if (n < 1 || n > 65535) { PyErr_SetString(PyExc_ValueError, "n_lin must be 1..65535"); return false; }
+		const Py_ssize_t wl = (n + 1 + 63) / 64;
+		for (; got < 8; got++)
+			if (PyObject_GetBuffer(args[got], &view[got], PyBUF_C_CONTIGUOUS) != 0) return false;
+		live = view[0].len / (wl * 8);
+		const char *bad = nullptr;
+		if (view[0].len != live * wl * 8) bad = "lin must hold whole rows of ceil((n_lin + 1) / 64) 64-bit words";
+		for (int at = 1; at <= 4 && !bad; at += 3) {       // off2 with ta, tb; off3 with ua, ub, uc
+			const int nop = at == 1 ? 2 : 3;
+			const Py_ssize_t nterms = view[at + 1].len / (wl * 8);
+			const int64_t *off = offsets(at);
+			if (view[at].len != (live + 1) * 8) bad = "off2 and off3 must hold one int64 per row of lin and one more";
+			else if (off[0] != 0) bad = "off2 and off3 must start at 0";
+			else if (off[live] != nterms) bad = "off2 and off3 must end at the number of operands of their products";
+			for (int k = 1; k <= nop && !bad; k++)
+				if (view[at + k].len != nterms * wl * 8) bad = "the operands of a product must hold the same number of whole forms";
+			for (Py_ssize_t r = 0; r < live && !bad; r++)
+				if (off[r + 1] < off[r]) bad = "off2 and off3 must not decrease";
+		}
+		if (bad) { PyErr_SetString(PyExc_ValueError, bad); return false; }
+		return true;
+	}
+	Py_ssize_t cols() const { return n + n * (n - 1) / 2 + n * (n - 1) * (n - 2) / 6; }
+};
+
 // m4ri_solve_rhs(equations, cols, mode, rhs, device=None) -> list of (None | int | AffineSpace), one per element of `rhs`.
 // New entry (no counterpart in the reference): many systems that share their coefficient matrix -- the reference factors A alone
 // (gf2bv/_internal.c:398-433) and only then solves against B (:438-455) -- eliminated ONCE (gf2bv_solve_rhs_digits).  `equations`
@@ -1041,6 +1083,32 @@ PyObject *py_m4ri_solve_quad_packed(PyObject *, PyObject *const *args, Py_ssize_
 	int rc;
 	Py_BEGIN_ALLOW_THREADS
 	rc = gf2bv_solve_quad_terms(qb.lin, qb.off, qb.ta, qb.tb, qb.live, rows, qb.n, (int)mode, device, &res);
+	Py_END_ALLOW_THREADS
+	if (rc != GF2BV_OK) return raise_rc(rc, "solve");
+	return result_to_py(res, mode, device);
+}
+
+// m4ri_solve_cubic_packed(lin, off2, ta, tb, off3, ua, ub, uc, n_lin, rows, mode[, device]) -> None | int | AffineSpace.
+// New entry (no counterpart in the reference): a cubic system kept FACTORED -- per equation a linear form, products of two and
+// products of three affine forms over the n_lin + 1 bits of the unknowns, the products exact (gf2bv_hip.h, "cubic expansion") -- is
+// expanded over the n_lin + C(n_lin,2) + C(n_lin,3) columns on the device and solved there.  Buffers as for m4ri_solve_quad_packed,
+// off3 / ua / ub / uc the cubic twins of off2 / ta / tb; rows >= the rows of lin and >= the columns.
+PyObject *py_m4ri_solve_cubic_packed(PyObject *, PyObject *const *args, Py_ssize_t nargs)
+{
+	int device;
+	if (!entry_device("m4ri_solve_cubic_packed", 11, args, nargs, &device)) return nullptr;
+	const Py_ssize_t rows = PyLong_AsSsize_t(args[9]);
+	if (rows == -1 && PyErr_Occurred()) return nullptr;
+	long mode;
+	CubicBuffers cb;
+	if (!parse_mode(args[10], &mode) || !cb.parse(args, args[8])) return nullptr;
+	if (rows < cb.live) { PyErr_SetString(PyExc_ValueError, "rows must be at least the rows of lin"); return nullptr; }
+	if (!rows_cover_cols(rows, cb.cols())) return nullptr;
+	gf2bv_result *res = nullptr;
+	int rc;
+	Py_BEGIN_ALLOW_THREADS
+	rc = gf2bv_solve_cubic_terms(cb.words(0), cb.offsets(1), cb.words(2), cb.words(3), cb.offsets(4), cb.words(5), cb.words(6), cb.words(7),
+	                             cb.live, rows, cb.n, (int)mode, device, &res);
 	Py_END_ALLOW_THREADS
 	if (rc != GF2BV_OK) return raise_rc(rc, "solve");
 	return result_to_py(res, mode, device);
@@ -1791,6 +1859,8 @@ PyMethodDef module_methods[] = {
 	 "m4ri_solve_quad_packed(lin, term_off, ta, tb, n_lin, rows, mode, device=None)\n--\n\nm4ri_solve on a quadratic system kept factored (linear forms and products of two linear forms, packed 64-bit words): expanded into the linearised matrix on the GPU."},
 	{"m4ri_solve_xl3", FAST(py_m4ri_solve_xl<3>), METH_FASTCALL,
 	 "m4ri_solve_xl3(equations, n_lin, mode, device=None)\n--\n\nDegree-3 XL: QuadraticSystem equation ints multiplied by 1 and by every unknown on the GPU and solved over the monomials of degree <= 3."},
+	{"m4ri_solve_cubic_packed", FAST(py_m4ri_solve_cubic_packed), METH_FASTCALL,
+	 "m4ri_solve_cubic_packed(lin, off2, ta, tb, off3, ua, ub, uc, n_lin, rows, mode, device=None)\n--\n\nm4ri_solve on a cubic system kept factored (a linear form, products of two and of three affine forms, packed 64-bit words; exact products): expanded over the monomials of degree <= 3 on the GPU."},
 	{"m4ri_solve_xl3_quad_packed", FAST(py_m4ri_solve_xl_quad_packed<3>), METH_FASTCALL,
 	 "m4ri_solve_xl3_quad_packed(lin, term_off, ta, tb, n_lin, mode, device=None)\n--\n\nm4ri_solve_xl3 on a quadratic system kept factored: expanded, multiplied and solved on the GPU."},
 	{"m4ri_solve_xl3_guess", FAST(py_m4ri_solve_xl_guess<3>), METH_FASTCALL,

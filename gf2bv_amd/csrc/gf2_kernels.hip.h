@@ -5254,3 +5254,135 @@ k_xl4_expand_batch(const u64 *__restrict__ quad, i64 quad_sys_stride, i64 m, i64
 {
 	xl4_expand_rows(quad + (i64)blockIdx.y * quad_sys_stride, m, quad_stride, n, W2, rows, parts, out + (i64)blockIdx.y * sys_stride, stride);
 }
+
+
+// ==========================================================================================
+// CUBIC EXPANSION: factored cubic equations -> the linearised rows over the monomials of degree <= 3
+// ==========================================================================================
+// (host side: gf2bv_cubic_expand_device in gf2_solver.hip; the front-end: PackedCubicSystem in gf2bv_amd/packed.py)
+//
+// Row r is e = lin[r] ^ XOR_t ta[t] tb[t] ^ XOR_u ua[u] ub[u] uc[u], t in off2[r] .. off2[r + 1], u in off3[r] .. off3[r + 1], every
+// operand an affine form of Wl words in the equation-int order (bit 0 constant, bit 1 + g unknown g < n).  The products are the EXACT
+// ones of GF(2)[x] / (x_i^2 + x_i), constants included -- not QuadraticSystem._mul_bit, which k_quad_expand follows and which drops
+// the constant x linear cross terms.  With l = a b's linear part (l_i = a0 b_i ^ a_i b0 ^ a_i b_i), q its pairs (q_ij = a_i b_j ^ a_j b_i):
+//   a b:    constant a0 b0, unknown i l_i, pair (i, j) q_ij;
+//   a b c:  constant a0 b0 c0, unknown i a0 b0 c_i ^ l_i c0 ^ l_i c_i, pair (i, j) q_ij (c0 ^ c_i ^ c_j) ^ l_i c_j ^ l_j c_i,
+//           triple (i, j, l) q_ij c_l ^ q_il c_j ^ q_jl c_i.
+// The output is the row k_xl3_expand writes: column c < n unknown c, pair (i, j), j < i, at n + C(i,2) + j, triple (i, j, l),
+// l < j < i, at cols2 + C(i,3) + C(j,2) + l, the constant at cols3, everything behind it zero.
+// Runs of consecutive columns, each a few 64-bit windows of the operands in LDS ANDed with lane-uniform masks:
+//   pairs (i, 0..i-1):       a b: (a_i & b[0..i)) ^ (b_i & a[0..i));  a b c: (q_i & (c0 ^ c_i ^ c)) ^ (l_i & c) ^ (c_i & l) over [0..i)
+//   triples (i, j, 0..j-1):  (c[0..j) & m_ab) ^ (b[0..j) & m_ac) ^ (a[0..j) & m_bc), m_ab = a_i b_j ^ a_j b_i and m_ac, m_bc alike.
+// Work split as in k_quad_expand: one workgroup per row at a time (grid-stride over the rows), the row's operands in LDS once, every
+// lane forming two consecutive output words per step and storing them as 16 bytes, consecutive lanes consecutive 16 bytes: each
+// output word has one writer, no atomics.  A pass holds `tch2` quadratic and `tch3` cubic terms; a row with more of either takes
+// several passes (the later ones XOR into what the same lane stored before).  Rows >= rows_live are written as zeros.
+// LDS: (1 + 2 tch2 + 3 tch3) x Wl words (dynamic).
+__device__ __forceinline__ u64 cx_mask(const u64 *x, i64 g) { return 0 - xl_bit(x, 1 + g); }      // unknown g of an operand, as a mask
+
+// columns c0 .. c0 + 63 of a row: what n2 quadratic terms (A, B) and n3 cubic terms (UA, UB, UC) contribute, with `first` the linear
+// part too
+__device__ __forceinline__ u64 cx_word(const u64 *lin, const u64 *A, const u64 *B, int n2, const u64 *UA, const u64 *UB, const u64 *UC, int n3,
+                                       int Wl, i64 n, i64 cols2, i64 cols3, i64 c0, bool first)
+{
+	u64 acc = 0;
+	if (c0 < n) {                                                  // the unknowns: column c = bit c + 1
+		u64 v = first ? qx_window(lin, Wl, c0 + 1) : 0;
+		for (int t = 0; t < n2; t++) {
+			const u64 *a = A + t * Wl, *b = B + t * Wl;
+			const u64 aw = qx_window(a, Wl, c0 + 1), bw = qx_window(b, Wl, c0 + 1);
+			v ^= (aw & bw) ^ ((0 - (a[0] & 1)) & bw) ^ ((0 - (b[0] & 1)) & aw);
+		}
+		for (int t = 0; t < n3; t++) {
+			const u64 *a = UA + t * Wl, *b = UB + t * Wl, *c = UC + t * Wl;
+			const u64 a0 = 0 - (a[0] & 1), b0 = 0 - (b[0] & 1), k0 = 0 - (c[0] & 1);
+			const u64 aw = qx_window(a, Wl, c0 + 1), bw = qx_window(b, Wl, c0 + 1), cw = qx_window(c, Wl, c0 + 1);
+			const u64 l = (aw & bw) ^ (a0 & bw) ^ (b0 & aw);
+			v ^= (a0 & b0 & cw) ^ (k0 & l) ^ (l & cw);
+		}
+		acc = v & qx_low(n - c0);
+	}
+	const i64 p_lo = (c0 > n ? c0 : n) - n, p_hi = (c0 + 64 < cols2 ? c0 + 64 : cols2) - n;        // the word's pair indices
+	if (n2 + n3 > 0 && p_lo < p_hi) {
+		i64 i = xl_tri_root(p_lo);
+		for (i64 s = xl_c2(i); s < p_hi; s += i, i++) {                    // run i: pairs s .. s + i - 1
+			const i64 j0 = (p_lo > s ? p_lo : s) - s, j1 = (p_hi < s + i ? p_hi : s + i) - s;
+			u64 run = 0;
+			for (int t = 0; t < n2; t++) {
+				const u64 *a = A + t * Wl, *b = B + t * Wl;
+				run ^= (cx_mask(a, i) & qx_window(b, Wl, 1 + j0)) ^ (cx_mask(b, i) & qx_window(a, Wl, 1 + j0));
+			}
+			for (int t = 0; t < n3; t++) {
+				const u64 *a = UA + t * Wl, *b = UB + t * Wl, *c = UC + t * Wl;
+				const u64 a0 = 0 - (a[0] & 1), b0 = 0 - (b[0] & 1), k0 = 0 - (c[0] & 1);
+				const u64 ai = cx_mask(a, i), bi = cx_mask(b, i), ci = cx_mask(c, i);
+				const u64 aw = qx_window(a, Wl, 1 + j0), bw = qx_window(b, Wl, 1 + j0), cw = qx_window(c, Wl, 1 + j0);
+				const u64 q = (ai & bw) ^ (bi & aw), l = (aw & bw) ^ (a0 & bw) ^ (b0 & aw), li = (ai & bi) ^ (a0 & bi) ^ (b0 & ai);
+				run ^= (q & (k0 ^ ci ^ cw)) ^ (li & cw) ^ (ci & l);
+			}
+			acc |= (run & qx_low(j1 - j0)) << (n + s + j0 - c0);
+		}
+	}
+	const i64 t_lo = (c0 > cols2 ? c0 : cols2) - cols2, t_hi = (c0 + 64 < cols3 ? c0 + 64 : cols3) - cols2;      // its triple indices
+	if (n3 > 0 && t_lo < t_hi) {
+		i64 i = xl_tet_root(t_lo), j = xl_tri_root(t_lo - xl_c3(i));       // the run t_lo lies in: 1 <= j < i
+		for (i64 s = xl_c3(i) + xl_c2(j); s < t_hi;) {                     // run (i, j): triples s .. s + j - 1
+			const i64 j0 = (t_lo > s ? t_lo : s) - s, j1 = (t_hi < s + j ? t_hi : s + j) - s;
+			u64 run = 0;
+			for (int t = 0; t < n3; t++) {
+				const u64 *a = UA + t * Wl, *b = UB + t * Wl, *c = UC + t * Wl;
+				const u64 ai = cx_mask(a, i), bi = cx_mask(b, i), ci = cx_mask(c, i), aj = cx_mask(a, j), bj = cx_mask(b, j), cj = cx_mask(c, j);
+				run ^= (qx_window(c, Wl, 1 + j0) & ((ai & bj) ^ (aj & bi))) ^ (qx_window(b, Wl, 1 + j0) & ((ai & cj) ^ (aj & ci)))
+				     ^ (qx_window(a, Wl, 1 + j0) & ((bi & cj) ^ (bj & ci)));
+			}
+			acc |= (run & qx_low(j1 - j0)) << (cols2 + s + j0 - c0);
+			s += j;
+			if (++j == i) { i++; j = 1; }
+		}
+	}
+	if (cols3 >= c0 && cols3 < c0 + 64) {                          // the constant: column cols3 = bit 0
+		u64 k = first ? lin[0] : 0;
+		for (int t = 0; t < n2; t++) k ^= A[t * Wl] & B[t * Wl];
+		for (int t = 0; t < n3; t++) k ^= UA[t * Wl] & UB[t * Wl] & UC[t * Wl];
+		acc |= (k & 1) << (cols3 - c0);
+	}
+	return acc;
+}
+
+__global__ void __launch_bounds__(256)
+k_cubic_expand(const u64 *__restrict__ lin, const i64 *__restrict__ off2, const u64 *__restrict__ ta, const u64 *__restrict__ tb,
+               const i64 *__restrict__ off3, const u64 *__restrict__ ua, const u64 *__restrict__ ub, const u64 *__restrict__ uc,
+               i64 rows_live, i64 rows, int n, int Wl, int tch2, int tch3, u64 *__restrict__ out, i64 stride)
+{
+	extern __shared__ u64 cx_lds[];                    // [lin: Wl | A, B: tch2 x Wl each | UA, UB, UC: tch3 x Wl each]
+	u64 *sl = cx_lds, *sa = sl + Wl, *sb = sa + (i64)tch2 * Wl, *sua = sb + (i64)tch2 * Wl, *sub = sua + (i64)tch3 * Wl, *suc = sub + (i64)tch3 * Wl;
+	const i64 cols2 = (i64)n + xl_c2(n), cols3 = cols2 + xl_c3(n);
+	const i64 npair = stride >> 1;                     // 16-byte pieces of a row (stride is even)
+	for (i64 r = blockIdx.x; r < rows; r += gridDim.x) {
+		ulonglong2 *o = reinterpret_cast<ulonglong2 *>(out + r * stride);
+		if (r >= rows_live) {
+			for (i64 k = threadIdx.x; k < npair; k += blockDim.x) o[k] = make_ulonglong2(0, 0);
+			continue;
+		}
+		i64 t0 = off2[r], t1 = off2[r + 1], u0 = off3[r], u1 = off3[r + 1];
+		if (t0 < 0 || t1 < t0 || u0 < 0 || u1 < u0) t0 = t1 = u0 = u1 = 0;      // (offsets the entry could not check: such a row is its linear part)
+		bool first = true;
+		do {
+			const int n2 = (int)(t1 - t0 < tch2 ? t1 - t0 : tch2), n3 = (int)(u1 - u0 < tch3 ? u1 - u0 : tch3);
+			__syncthreads();                           // the pass before has read its operands
+			if (first) for (int e = threadIdx.x; e < Wl; e += blockDim.x) sl[e] = lin[r * Wl + e];
+			for (int e = threadIdx.x; e < n2 * Wl; e += blockDim.x) { sa[e] = ta[t0 * Wl + e]; sb[e] = tb[t0 * Wl + e]; }
+			for (int e = threadIdx.x; e < n3 * Wl; e += blockDim.x) { sua[e] = ua[u0 * Wl + e]; sub[e] = ub[u0 * Wl + e]; suc[e] = uc[u0 * Wl + e]; }
+			__syncthreads();
+			for (i64 k = threadIdx.x; k < npair; k += blockDim.x) {
+				u64 w0 = cx_word(sl, sa, sb, n2, sua, sub, suc, n3, Wl, n, cols2, cols3, 128 * k, first);
+				u64 w1 = cx_word(sl, sa, sb, n2, sua, sub, suc, n3, Wl, n, cols2, cols3, 128 * k + 64, first);
+				if (!first) { const ulonglong2 old = o[k]; w0 ^= old.x; w1 ^= old.y; }
+				o[k] = make_ulonglong2(w0, w1);
+			}
+			t0 += n2;
+			u0 += n3;
+			first = false;
+		} while (t0 < t1 || u0 < u1);
+	}
+}

@@ -4773,6 +4773,78 @@ int enqueue_quad_expand_batch(const QuadTerms &q, const i64 *d_sys_off, i64 nsys
 	return GF2BV_OK;
 }
 
+// Cubic expansion (k_cubic_expand): a linear form plus products of two and of three affine forms, the products exact in
+// GF(2)[x] / (x_i^2 + x_i), become rows over the n + C(n,2) + C(n,3) columns of degree-3 XL
+struct CubicTerms {                    // the factored form, in host or in device memory
+	const u64 *lin = nullptr;          // rows_live x wl
+	const i64 *off2 = nullptr;         // rows_live + 1
+	const u64 *ta = nullptr, *tb = nullptr;
+	const i64 *off3 = nullptr;         // rows_live + 1
+	const u64 *ua = nullptr, *ub = nullptr, *uc = nullptr;
+	i64 rows_live = 0, rows = 0, n = 0;
+	i64 wl() const { return (n + 1 + 63) / 64; }
+	i64 cols() const { return n + n * (n - 1) / 2 + n * (n - 1) * (n - 2) / 6; }
+	i64 wt() const { return (cols() + 1 + 63) / 64; }
+};
+
+// What the kernel is launched with: `tch2` quadratic and `tch3` cubic terms of a row in LDS at a time (64 KiB in all, the cubic
+// operands served first where a form is long), a thread per two words of an output row
+struct CubicLaunch { int tch2, tch3; unsigned block; size_t lds; };
+constexpr i64 kCubicLdsBytes = 65536;
+CubicLaunch cubic_launch(i64 n, i64 stride)
+{
+	const i64 wl = (n + 1 + 63) / 64, avail = kCubicLdsBytes / 8 / wl - 1;      // operands beside the linear part
+	const int tch3 = (int)std::max<i64>(1, std::min<i64>(8, avail / 5));
+	const int tch2 = (int)std::max<i64>(1, std::min<i64>(8, (avail - 3 * tch3) / 2));
+	return { tch2, tch3, (unsigned)std::min<i64>(256, round_up(std::max<i64>(stride / 2, 1), 64)), sizeof(u64) * (size_t)((1 + 2 * tch2 + 3 * tch3) * wl) };
+}
+
+// The shape of a factored cubic system; `host`: the offsets can be read (each array starts at 0 and never decreases; operands
+// wherever they say there are terms)
+int check_cubic_terms(const CubicTerms &c, bool host)
+{
+	if (!c.lin && c.rows_live > 0) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (!c.off2 || !c.off3) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (c.n < 1 || c.n > 65535 || c.cols() >= (1ll << 31) - 64)
+		return fail(GF2BV_ERR_ARG, "n_lin must be at least 1 and n_lin + C(n_lin,2) + C(n_lin,3) below 2^31 - 64");
+	if (c.rows < 0 || c.rows >= (1ll << 31) - 64 || c.rows_live < 0 || c.rows_live > c.rows)
+		return fail(GF2BV_ERR_ARG, "rows_live must be 0..rows");
+	if ((i64)cubic_launch(c.n, 2).lds > kCubicLdsBytes)
+		return fail(GF2BV_ERR_ARG, "the operands of this n_lin do not fit the expansion kernel's LDS (64 KiB)");
+	if (!host) {
+		if (!c.lin || !c.ta || !c.tb || !c.ua || !c.ub || !c.uc) return fail(GF2BV_ERR_ARG, "null pointer");
+		return GF2BV_OK;
+	}
+	if (c.off2[0] != 0 || c.off3[0] != 0) return fail(GF2BV_ERR_ARG, "term offsets must start at 0");
+	for (i64 r = 0; r < c.rows_live; r++)
+		if (c.off2[r + 1] < c.off2[r] || c.off3[r + 1] < c.off3[r]) return fail(GF2BV_ERR_ARG, "term offsets must not decrease");
+	if ((!c.ta || !c.tb) && c.off2[c.rows_live] > 0) return fail(GF2BV_ERR_ARG, "null pointer");
+	if ((!c.ua || !c.ub || !c.uc) && c.off3[c.rows_live] > 0) return fail(GF2BV_ERR_ARG, "null pointer");
+	return GF2BV_OK;
+}
+
+CubicTerms cubic_terms(const void *lin, const void *off2, const void *ta, const void *tb, const void *off3, const void *ua, const void *ub,
+                       const void *uc, i64 rows_live, i64 rows, i64 n_lin)
+{
+	CubicTerms c;
+	c.lin = (const u64 *)lin; c.off2 = (const i64 *)off2; c.ta = (const u64 *)ta; c.tb = (const u64 *)tb;
+	c.off3 = (const i64 *)off3; c.ua = (const u64 *)ua; c.ub = (const u64 *)ub; c.uc = (const u64 *)uc;
+	c.rows_live = rows_live; c.rows = rows; c.n = n_lin;
+	return c;
+}
+
+// (device pointers, already checked) the kernel on `st`
+int enqueue_cubic_expand(const CubicTerms &c, u64 *d_aug, i64 stride, hipStream_t st)
+{
+	if (c.rows == 0) return GF2BV_OK;
+	const CubicLaunch l = cubic_launch(c.n, stride);
+	const unsigned grid = (unsigned)std::min<i64>(c.rows, 256 * 16);
+	hipLaunchKernelGGL(k_cubic_expand, dim3(grid), dim3(l.block), l.lds, st, c.lin, c.off2, c.ta, c.tb, c.off3, c.ua, c.ub, c.uc, c.rows_live,
+	                   c.rows, (int)c.n, (int)c.wl(), l.tch2, l.tch3, d_aug, stride);
+	HIPCHK(hipGetLastError());
+	return GF2BV_OK;
+}
+
 // XL (k_xl3_expand, k_xl4_expand): m quadratic rows over n unknowns -- the rows k_quad_expand writes -- become `rows` rows over the
 // monomials of degree <= `degree`: each equation, its product with every unknown and (degree 4) with every pair of unknowns, then zeros
 struct XlShape {
@@ -4987,6 +5059,27 @@ struct QuadStage {
 		q.lin = lin; q.off = off; q.ta = ta; q.tb = tb;
 		return sys_off ? enqueue_quad_expand_batch(q, d_sys, nsys, d_aug, ds, q.rows * ds, ps.st) : enqueue_quad_expand(q, d_aug, ds, ps.st);
 	}
+	// The cubic form: upload and expansion (k_cubic_expand) into d_aug, rows `stride` words apart rounded up to an even `ds`
+	int expand(CubicTerms c, i64 stride)
+	{
+		if (int rc = open()) return rc;
+		const i64 wl = c.wl(), T2 = c.off2[c.rows_live], T3 = c.off3[c.rows_live];
+		u64 *lin = nullptr, *ta = nullptr, *tb = nullptr, *ua = nullptr, *ub = nullptr, *uc = nullptr;
+		i64 *off2 = nullptr, *off3 = nullptr;
+		int rc = upload(&lin, c.lin, sizeof(u64) * (size_t)(c.rows_live * wl));
+		if (!rc) rc = upload(&off2, c.off2, sizeof(i64) * (size_t)(c.rows_live + 1));
+		if (!rc) rc = upload(&ta, c.ta, sizeof(u64) * (size_t)(T2 * wl));
+		if (!rc) rc = upload(&tb, c.tb, sizeof(u64) * (size_t)(T2 * wl));
+		if (!rc) rc = upload(&off3, c.off3, sizeof(i64) * (size_t)(c.rows_live + 1));
+		if (!rc) rc = upload(&ua, c.ua, sizeof(u64) * (size_t)(T3 * wl));
+		if (!rc) rc = upload(&ub, c.ub, sizeof(u64) * (size_t)(T3 * wl));
+		if (!rc) rc = upload(&uc, c.uc, sizeof(u64) * (size_t)(T3 * wl));
+		ds = round_up(stride, 2);
+		if (!rc) rc = alloc((void **)&d_aug, sizeof(u64) * (size_t)(c.rows * ds));
+		if (rc) return rc;
+		c.lin = lin; c.off2 = off2; c.ta = ta; c.tb = tb; c.off3 = off3; c.ua = ua; c.ub = ub; c.uc = uc;
+		return enqueue_cubic_expand(c, d_aug, ds, ps.st);
+	}
 	// Quadratic rows that are expanded already (host memory, `stride` words apart) into d_aug as they are
 	int upload_rows(const u64 *quad, i64 m, i64 stride)
 	{
@@ -5104,6 +5197,72 @@ int gf2bv_solve_quad_terms(const uint64_t *lin, const int64_t *term_off, const u
 	QuadStage stage(device, false);
 	if ((rc = stage.expand(q, q.wt()))) return rc;
 	return gf2bv_solve_device(stage.d_aug, rows, q.cols(), stage.ds, mode, device, stage.ps.st, 0, out);
+	});
+}
+
+// ---- the cubic form: the same three entries over n_lin + C(n_lin,2) + C(n_lin,3) columns (k_cubic_expand)
+int gf2bv_cubic_expand_device(const void *d_lin, const void *d_off2, const void *d_ta, const void *d_tb, const void *d_off3, const void *d_ua,
+                              const void *d_ub, const void *d_uc, int64_t rows_live, int64_t rows, int64_t n_lin, void *d_aug,
+                              int64_t stride_words, int device, void *stream)
+{
+	return catching([&]() -> int {
+	const CubicTerms c = cubic_terms(d_lin, d_off2, d_ta, d_tb, d_off3, d_ua, d_ub, d_uc, rows_live, rows, n_lin);
+	int rc = check_cubic_terms(c, false);
+	if (rc) return rc;
+	if (!d_aug) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (stride_words % 2 != 0 || stride_words < c.wt() || ((uintptr_t)d_aug & 15))
+		return fail(GF2BV_ERR_ARG, "device matrix needs 16-byte alignment and an even stride_words covering cols+1 bits");
+	rc = check_device(device);
+	if (rc) return rc;
+	return enqueue_cubic_expand(c, (u64 *)d_aug, stride_words, (hipStream_t)stream);
+	});
+}
+
+int gf2bv_cubic_expand_words(const uint64_t *lin, const int64_t *off2, const uint64_t *ta, const uint64_t *tb, const int64_t *off3,
+                             const uint64_t *ua, const uint64_t *ub, const uint64_t *uc, int64_t rows_live, int64_t rows, int64_t n_lin,
+                             uint64_t *out_aug, int64_t stride_words, int device)
+{
+	return catching([&]() -> int {
+	const CubicTerms c = cubic_terms(lin, off2, ta, tb, off3, ua, ub, uc, rows_live, rows, n_lin);
+	int rc = check_cubic_terms(c, true);
+	if (rc) return rc;
+	if (!out_aug && rows > 0) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (stride_words < c.wt()) return fail(GF2BV_ERR_ARG, "stride_words does not cover cols+1 bits");
+	if ((rc = check_device(device))) return rc;
+	if (rows == 0) return GF2BV_OK;
+	QuadStage stage(device);
+	if ((rc = stage.expand(c, stride_words))) return rc;
+	return stage.download(out_aug, stride_words, rows);
+	});
+}
+
+int gf2bv_solve_cubic_terms(const uint64_t *lin, const int64_t *off2, const uint64_t *ta, const uint64_t *tb, const int64_t *off3,
+                            const uint64_t *ua, const uint64_t *ub, const uint64_t *uc, int64_t rows_live, int64_t rows, int64_t n_lin,
+                            int mode, int device, gf2bv_result **out)
+{
+	return catching([&]() -> int {
+	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
+	*out = nullptr;
+	const CubicTerms c = cubic_terms(lin, off2, ta, tb, off3, ua, ub, uc, rows_live, rows, n_lin);
+	int rc = check_cubic_terms(c, true);
+	if (!rc) rc = check_shape(rows, c.cols(), mode);
+	if (!rc) rc = check_device(device);
+	if (rc) return rc;
+	QuadStage stage(device);
+	if ((rc = stage.expand(c, c.wt()))) return rc;
+	return gf2bv_solve_device(stage.d_aug, rows, c.cols(), stage.ds, mode, device, stage.ps.st, 0, out);
+	});
+}
+
+int gf2bv_cubic_chunks(int64_t n_lin, int32_t *quad_chunk, int32_t *cubic_chunk)
+{
+	return catching([&]() -> int {
+	if (!quad_chunk || !cubic_chunk) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (n_lin < 1 || n_lin > 65535) return fail(GF2BV_ERR_ARG, "n_lin must be 1..65535");
+	const CubicLaunch l = cubic_launch(n_lin, 2);
+	*quad_chunk = l.tch2;
+	*cubic_chunk = l.tch3;
+	return GF2BV_OK;
 	});
 }
 

@@ -38,6 +38,7 @@ EXPORTS = [
     "gf2bv_quad_expand_device", "gf2bv_quad_expand_words", "gf2bv_solve_quad_terms",
     "gf2bv_factor_quad_terms", "gf2bv_factor_append_quad_terms", "gf2bv_solve_rhs_quad_terms", "gf2bv_solve_batch_quad_terms",
     "gf2bv_quad_expand_batch_words",
+    "gf2bv_cubic_expand_device", "gf2bv_cubic_expand_words", "gf2bv_solve_cubic_terms", "gf2bv_cubic_chunks",
     "gf2bv_xl3_expand_device", "gf2bv_xl3_expand_words", "gf2bv_solve_xl3_words", "gf2bv_solve_xl3_quad_terms",
     "gf2bv_quad_specialise_device", "gf2bv_quad_specialise_words", "gf2bv_xl3_expand_batch_device", "gf2bv_xl3_expand_batch_words",
     "gf2bv_solve_xl3_guess_words", "gf2bv_solve_xl3_guess_quad_terms", "gf2bv_xl3_guess_chunk", "gf2bv_xl3_guess_chunk_device",
@@ -152,6 +153,10 @@ def lib():
         L.gf2bv_solve_rhs_quad_terms.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, i64, i64, i32, i32, pp]
         L.gf2bv_solve_batch_quad_terms.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i32, i32, pp]
         L.gf2bv_quad_expand_batch_words.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, vp, i64, i32]
+        L.gf2bv_cubic_expand_device.argtypes = [vp] * 8 + [i64, i64, i64, vp, i64, i32, vp]
+        L.gf2bv_cubic_expand_words.argtypes = [vp] * 8 + [i64, i64, i64, vp, i64, i32]
+        L.gf2bv_solve_cubic_terms.argtypes = [vp] * 8 + [i64, i64, i64, i32, i32, pp]
+        L.gf2bv_cubic_chunks.argtypes = [i64, vp, vp]
         for d in ("xl3", "xl4"):                       # the two degrees: the same signatures
             getattr(L, f"gf2bv_{d}_expand_device").argtypes = [vp, i64, i64, i64, i64, vp, i64, i32, vp]
             getattr(L, f"gf2bv_{d}_expand_words").argtypes = [vp, i64, i64, i64, i64, vp, i64, i32]
@@ -726,6 +731,57 @@ def quad_expand_batch_words(lin, term_off, ta, tb, sys_row_off, n_lin: int, rows
 def xl3_cols(n_lin: int) -> int:
     """columns of the degree-3 XL system in n_lin unknowns: the unknowns, their pairs and their triples"""
     return quad_cols(n_lin) + n_lin * (n_lin - 1) * (n_lin - 2) // 6
+
+
+def _cubic_terms(lin, off2, ta, tb, off3, ua, ub, uc, n_lin: int):
+    """the factored form of gf2bv_cubic_expand_* as contiguous arrays, shapes checked against each other"""
+    lin, off2, ta, tb = _quad_terms(lin, off2, ta, tb, n_lin)
+    wl = lin.shape[1]
+    off3 = np.ascontiguousarray(off3, dtype=np.int64).reshape(-1)
+    ua, ub, uc = (np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, wl) for x in (ua, ub, uc))
+    if len(off3) != len(lin) + 1 or len(ua) != len(ub) or len(ua) != len(uc) or (len(off3) and off3[-1] != len(ua)):
+        raise ValueError("off3 needs one entry per row of lin and one more, ending at the number of operands in ua, ub and uc")
+    return lin, off2, ta, tb, off3, ua, ub, uc
+
+
+def cubic_chunks(n_lin: int) -> tuple:
+    """(quadratic, cubic) terms of a row that one pass of the cubic expansion kernel holds in LDS (gf2bv_cubic_chunks, host only)"""
+    q, c = ctypes.c_int32(), ctypes.c_int32()
+    _check(lib().gf2bv_cubic_chunks(n_lin, ctypes.byref(q), ctypes.byref(c)))
+    return q.value, c.value
+
+
+def cubic_expand_words(lin, off2, ta, tb, off3, ua, ub, uc, n_lin: int, rows: int | None = None, stride_words: int | None = None,
+                       device: int = 0) -> np.ndarray:
+    """Factored cubic equations (lin[r] ^ XOR of ta[t] * tb[t], t in off2[r] .. off2[r + 1] ^ XOR of ua[u] * ub[u] * uc[u], u in
+    off3[r] .. off3[r + 1]; affine forms of ceil((n_lin + 1) / 64) words, bit 0 constant, bit 1 + g unknown g; the products exact in
+    GF(2)[x] / (x_i^2 + x_i)) expanded on the device into rows over the xl3_cols(n_lin) columns of the augmented-words layout:
+    [rows, stride_words] uint64, rows beyond len(lin) zero (gf2bv_cubic_expand_words)."""
+    terms = _cubic_terms(lin, off2, ta, tb, off3, ua, ub, uc, n_lin)
+    rows = len(terms[0]) if rows is None else rows
+    stride = (xl3_cols(n_lin) + 1 + 63) // 64 if stride_words is None else stride_words
+    out = np.empty((max(rows, 0), max(stride, 0)), dtype=np.uint64)
+    _check(lib().gf2bv_cubic_expand_words(*_ptrs(*terms), len(terms[0]), rows, n_lin, out.ctypes.data, stride, device))
+    return out
+
+
+def cubic_expand_device(d_lin: int, d_off2: int, d_ta: int, d_tb: int, d_off3: int, d_ua: int, d_ub: int, d_uc: int, rows_live: int,
+                        rows: int, n_lin: int, d_aug: int, stride: int, device: int = 0, stream: int = 0) -> None:
+    """cubic_expand_words with everything resident in device memory: the kernel is enqueued on `stream` and the call returns; a
+    solve_device on the same stream reads the finished rows."""
+    _check(lib().gf2bv_cubic_expand_device(d_lin, d_off2, d_ta, d_tb, d_off3, d_ua, d_ub, d_uc, rows_live, rows, n_lin, d_aug, stride,
+                                           device, stream or None))
+
+
+def solve_cubic_terms(lin, off2, ta, tb, off3, ua, ub, uc, n_lin: int, rows: int | None = None, mode: int = MODE_SINGLE,
+                      device: int = 0) -> Solution:
+    """The factored cubic system uploaded, expanded on the device and solved there (gf2bv_solve_cubic_terms): what solve_words
+    returns for cubic_expand_words of the same arrays.  rows (default: max(len(lin), columns)) >= the columns."""
+    terms = _cubic_terms(lin, off2, ta, tb, off3, ua, ub, uc, n_lin)
+    rows = max(len(terms[0]), xl3_cols(n_lin)) if rows is None else rows
+    h = ctypes.c_void_p()
+    _check(lib().gf2bv_solve_cubic_terms(*_ptrs(*terms), len(terms[0]), rows, n_lin, mode, device, ctypes.byref(h)))
+    return _take(h, mode)
 
 
 def xl4_cols(n_lin: int) -> int:

@@ -21,10 +21,11 @@ from typing import Iterable, Optional, Sequence
 
 import numpy as np
 
-from ._internal import (m4ri_solve_many_quad_packed, m4ri_solve_packed, m4ri_solve_quad_packed, m4ri_solve_xl3_guess_quad_packed,
-                        m4ri_solve_xl3_quad_packed, m4ri_solve_xl4_guess_quad_packed, m4ri_solve_xl4_quad_packed)
+from ._internal import (m4ri_solve_cubic_packed, m4ri_solve_many_quad_packed, m4ri_solve_packed, m4ri_solve_quad_packed,
+                        m4ri_solve_xl3_guess_quad_packed, m4ri_solve_xl3_quad_packed, m4ri_solve_xl4_guess_quad_packed,
+                        m4ri_solve_xl4_quad_packed)
 from .bitvec import BitVec
-from .linsys import DimensionTooLargeError, _QuadraticPoints
+from .linsys import DimensionTooLargeError, _QuadraticPoints, xl3_cols
 
 
 def _const_bits(n: int, value: int) -> np.ndarray:
@@ -85,8 +86,8 @@ class PackedBitVec(BitVec):
 
     # -- xor (reference :39-49) ----------------------------------------------------------------
     def __xor__(self, other):
-        if isinstance(other, PackedQuadBitVec):
-            return NotImplemented                      # (its __rxor__ takes over: the sum is quadratic)
+        if isinstance(other, (PackedQuadBitVec, PackedCubicBitVec)):
+            return NotImplemented                      # (its __rxor__ takes over: the sum is quadratic or cubic)
         return PackedBitVec(self._rows ^ self._coerce(other))
 
     __rxor__ = __xor__
@@ -175,6 +176,8 @@ class PackedBitVec(BitVec):
     def concat(self, other: "PackedBitVec"):
         if isinstance(other, PackedQuadBitVec):        # (linear bits in front of bits that carry products)
             return other._like(self._rows, np.zeros(len(self) + 1, dtype=np.int64), other._ta[:0], other._tb[:0]).concat(other)
+        if isinstance(other, PackedCubicBitVec):
+            return other._linear(self._rows).concat(other)
         return PackedBitVec(np.concatenate([self._rows, other._rows]))
 
     # -- evaluation (reference :128-134) -----------------------------------------------------------
@@ -396,6 +399,8 @@ class PackedQuadBitVec:
             return self._like(self._lin ^ other._rows, self._off, self._ta, self._tb)
         if isinstance(other, BitVec):
             raise TypeError("cannot mix packed and tuple-of-int BitVecs")
+        if isinstance(other, PackedCubicBitVec):
+            return NotImplemented                      # (its __rxor__ says why the two do not mix)
         lin = self._lin.copy()
         lin[:, 0] ^= _const_bits(len(self), other)      # a constant only has the affine bit
         return self._like(lin, self._off, self._ta, self._tb)
@@ -611,3 +616,304 @@ class PackedQuadraticSystem(_QuadraticPoints, PackedLinearSystem):
 
     def solve_one_many(self, zeros_list: Sequence[Sequence]) -> list:
         return [None if raw is None else self.convert_sol(raw) for raw in self._solve_internal_many(zeros_list, 0)]
+
+
+# ---- cubic systems kept factored ---------------------------------------------------------------------------------------------------
+# One degree up: a symbolic bit is a linear form plus products of two affine forms plus products of three, and the rows over the
+# n + C(n,2) + C(n,3) columns of degree-3 XL come into being on the device (k_cubic_expand, through m4ri_solve_cubic_packed /
+# hip.cubic_expand_words).  The products here are the EXACT products of GF(2)[x] / (x_i^2 + x_i), constants included;
+# QuadraticSystem._mul_bit, which the quadratic classes above follow, drops the constant x linear cross terms.  That is why the two
+# kinds of vector do not mix.
+_QUAD_MIX = ("a PackedQuadBitVec cannot be mixed with a PackedCubicBitVec: the quadratic class's products follow the reference's "
+             "_mul_bit (no constant x linear cross terms), this class's are the exact products")
+
+
+def _refuse_cubic(name: str):
+    def method(self, *args, **kwargs):
+        raise TypeError(f"{name} is not supported on a PackedCubicBitVec (bits that carry products): only ^, indexing and concat are")
+    method.__name__ = name
+    return method
+
+
+def _take_terms(off: np.ndarray, ops: tuple, idx: np.ndarray):
+    """the products (offsets, operand arrays) of the bits idx[0], idx[1], ..."""
+    cnt = off[idx + 1] - off[idx]
+    new = np.zeros(len(idx) + 1, dtype=np.int64)
+    np.cumsum(cnt, out=new[1:])
+    src = np.repeat(off[idx] - new[:-1], cnt) + np.arange(new[-1])         # operand row of every kept product
+    return new, tuple(x[src] for x in ops)
+
+
+def _xor_terms(off_a: np.ndarray, ops_a: tuple, off_b: np.ndarray, ops_b: tuple):
+    """bit i of the sum owns the products of a[i], then those of b[i]"""
+    k = len(off_a) - 1
+    owner = np.concatenate([np.repeat(np.arange(k), np.diff(off_a)), np.repeat(np.arange(k), np.diff(off_b))])
+    order = np.argsort(owner, kind="stable")
+    return off_a + off_b, tuple(np.concatenate([x, y])[order] for x, y in zip(ops_a, ops_b))
+
+
+def _exact_product_int(forms: tuple, n: int) -> int:
+    """the exact product of two or three affine forms (equation ints over n unknowns) as an equation int over the cubic columns:
+    bit 0 the constant, bit 1 + c column c of xl3_cols(n), put together from runs of consecutive columns"""
+    low = (1 << n) - 1
+    a, b = forms[0], forms[1]
+    a0, b0, A, B = a & 1, b & 1, (a >> 1) & low, (b >> 1) & low
+    l = (A & B) ^ (B if a0 else 0) ^ (A if b0 else 0)                      # the linear part of a b
+    k0 = a0 & b0
+    pair0, tri0 = 1 + n, 1 + n + n * (n - 1) // 2
+    if len(forms) == 2:
+        e = k0 | (l << 1)
+        for i in range(1, n):
+            run = ((B if (A >> i) & 1 else 0) ^ (A if (B >> i) & 1 else 0)) & ((1 << i) - 1)
+            e |= run << (pair0 + i * (i - 1) // 2)
+        return e
+    c = forms[2]
+    c0, C = c & 1, (c >> 1) & low
+    e = (k0 & c0) | (((C if k0 else 0) ^ (l if c0 else 0) ^ (l & C)) << 1)
+    for i in range(1, n):
+        ai, bi, ci, li = (A >> i) & 1, (B >> i) & 1, (C >> i) & 1, (l >> i) & 1
+        q = (B if ai else 0) ^ (A if bi else 0)                            # pairs (i, .) of a b
+        run = (q & (C ^ (low if c0 ^ ci else 0))) ^ (C if li else 0) ^ (l if ci else 0)
+        e |= (run & ((1 << i) - 1)) << (pair0 + i * (i - 1) // 2)
+        if not (ai | bi | ci):
+            continue                                   # (every mask below has a factor from i)
+        for j in range(1, i):
+            aj, bj, cj = (A >> j) & 1, (B >> j) & 1, (C >> j) & 1
+            run = (C if (ai & bj) ^ (aj & bi) else 0) ^ (B if (ai & cj) ^ (aj & ci) else 0) ^ (A if (bi & cj) ^ (bj & ci) else 0)
+            e |= (run & ((1 << j) - 1)) << (tri0 + i * (i - 1) * (i - 2) // 6 + j * (j - 1) // 2)
+    return e
+
+
+class PackedCubicBitVec:
+    """k symbolic bits, each a linear form (a row of ``_lin``, Wl = ceil((n + 1) / 64) words in the order of ``PackedBitVec``) plus
+    products of two affine forms (bit i owns the operand rows ``_off2[i] .. _off2[i + 1]`` of ``_ta`` / ``_tb``) plus products of
+    three (``_off3``, ``_ua`` / ``_ub`` / ``_uc``).  A product is the exact product in GF(2)[x] / (x_i^2 + x_i); equal products are
+    not cancelled here, they cancel when the rows are expanded."""
+    __slots__ = ("_lin", "_off2", "_ta", "_tb", "_off3", "_ua", "_ub", "_uc", "_n")
+
+    def __init__(self, lin, off2, ta, tb, off3, ua, ub, uc, n: int):
+        self._lin, self._off2, self._ta, self._tb = lin, off2, ta, tb      # [k, Wl] uint64, [k + 1] int64, [T2, Wl] x 2: immutable
+        self._off3, self._ua, self._ub, self._uc = off3, ua, ub, uc        # [k + 1] int64, [T3, Wl] x 3
+        self._n = n                                    # unknowns of the system
+
+    def _linear(self, rows: np.ndarray) -> "PackedCubicBitVec":
+        """linear bits (the rows of a PackedBitVec) as a vector of this kind"""
+        none, off = self._lin[:0], np.zeros(len(rows) + 1, dtype=np.int64)
+        return PackedCubicBitVec(rows, off, none, none, off, none, none, none, self._n)
+
+    def _groups(self):
+        return (self._off2, (self._ta, self._tb)), (self._off3, (self._ua, self._ub, self._uc))
+
+    def _with(self, lin, quad, cubic) -> "PackedCubicBitVec":
+        return PackedCubicBitVec(lin, quad[0], *quad[1], cubic[0], *cubic[1], self._n)
+
+    def _degree(self) -> int:
+        return 3 if len(self._ua) else 2 if len(self._ta) else 1
+
+    def __len__(self):
+        return self._lin.shape[0]
+
+    def _take(self, idx: np.ndarray) -> "PackedCubicBitVec":
+        quad, cubic = self._groups()
+        return self._with(self._lin[idx], _take_terms(*quad, idx), _take_terms(*cubic, idx))
+
+    def __getitem__(self, key):
+        n = len(self)
+        if isinstance(key, slice):
+            return self._take(np.arange(n)[key])
+        i = operator.index(key)
+        if not -n <= i < n:
+            raise IndexError("PackedCubicBitVec index out of range")
+        return self._take(np.array([i % n]))
+
+    def _coerce(self, other, what: str) -> "PackedCubicBitVec":
+        if isinstance(other, PackedQuadBitVec):
+            raise TypeError(_QUAD_MIX)
+        if isinstance(other, PackedBitVec):
+            other = self._linear(other._rows)
+        if not isinstance(other, PackedCubicBitVec):
+            if isinstance(other, BitVec):
+                raise TypeError("cannot mix packed and tuple-of-int BitVecs")
+            raise TypeError(f"{what} needs a PackedCubicBitVec or a PackedBitVec")
+        if other._lin.shape[1] != self._lin.shape[1] or other._n != self._n:
+            raise ValueError("Cannot mix bitvecs over different numbers of unknowns")
+        return other
+
+    def __xor__(self, other):
+        if isinstance(other, (PackedCubicBitVec, BitVec, PackedQuadBitVec)):
+            other = self._coerce(other, "^")
+            if len(other) != len(self):
+                raise ValueError("Cannot mix bitvecs of different lengths")
+            (q1, c1), (q2, c2) = self._groups(), other._groups()
+            return self._with(self._lin ^ other._lin, _xor_terms(*q1, *q2), _xor_terms(*c1, *c2))
+        lin = self._lin.copy()
+        lin[:, 0] ^= _const_bits(len(self), other)      # a constant only has the affine bit
+        return self._with(lin, *self._groups())
+
+    __rxor__ = __xor__
+    __pow__ = __xor__
+
+    def concat(self, other):
+        other = self._coerce(other, "concat")
+        cat = lambda g, h: (np.concatenate([g[0], h[0][1:] + g[0][-1]]), tuple(np.concatenate([x, y]) for x, y in zip(g[1], h[1])))  # noqa: E731
+        (q1, c1), (q2, c2) = self._groups(), other._groups()
+        return self._with(np.concatenate([self._lin, other._lin]), cat(q1, q2), cat(c1, c2))
+
+    def _eq_ints(self) -> list:
+        """every bit as an equation int over the cubic columns, expanded on the host a product at a time"""
+        n = self._n
+        ints = lambda rows: [int.from_bytes(r.tobytes(), "little") & ((1 << (n + 1)) - 1) for r in rows]      # noqa: E731
+        lin, ops2, ops3 = ints(self._lin), [ints(x) for x in (self._ta, self._tb)], [ints(x) for x in (self._ua, self._ub, self._uc)]
+        out = []
+        for k, e in enumerate(lin):
+            for t in range(self._off2[k], self._off2[k + 1]):
+                e ^= _exact_product_int((ops2[0][t], ops2[1][t]), n)
+            for u in range(self._off3[k], self._off3[k + 1]):
+                e ^= _exact_product_int((ops3[0][u], ops3[1][u], ops3[2][u]), n)
+            out.append(e)
+        return out
+
+    def evaluate(self, s: int) -> int:
+        """Value under the raw point ``s`` over the cubic columns (bit c = column c: the n unknowns, their pairs, their triples),
+        as BitVec.evaluate gives it for the expanded bits; on the host."""
+        point = ((s << 1) | 1) & ((1 << (xl3_cols(self._n) + 1)) - 1)
+        return sum((bin(e & point).count("1") & 1) << k for k, e in enumerate(self._eq_ints()))
+
+
+for _name in ("__and__", "__rand__", "__or__", "__ror__", "__lshift__", "__rshift__", "__mod__", "__invert__", "lshift_ext", "rotl", "rotr",
+              "sum", "zeroext", "signext", "broadcast", "dup"):
+    setattr(PackedCubicBitVec, _name, _refuse_cubic(_name))
+del _name
+
+
+def _refuse_system(name: str):
+    def method(self, *args, **kwargs):
+        raise TypeError(f"{name} is not built for a PackedCubicSystem")
+    method.__name__ = name
+    return method
+
+
+class PackedCubicSystem(PackedLinearSystem):
+    """Equations of degree <= 3 written directly and kept factored: ``gens()`` are PackedLinearSystem's PackedBitVecs, ``mul_bit``
+    multiplies single bits up to degree 3 (exact products), and the solve methods hand the factored arrays to the device, which
+    expands them over the n + C(n,2) + C(n,3) columns of degree-3 XL and solves.  ``solve_all`` keeps the points of the linearised
+    space whose pair and triple coordinates are the products of their linear bits."""
+
+    def __init__(self, sizes: Iterable[int]):
+        super().__init__(sizes)
+        self._lin_size = sum(self._sizes)
+        self._cols = xl3_cols(self._lin_size)          # (``_words`` stays the words of a linear form: the generators have no product coordinates)
+
+    _xl_index = _QuadraticPoints._xl_index
+    _xl_products_match = _QuadraticPoints._xl_products_match
+
+    def _single(self, a) -> PackedCubicBitVec:
+        if isinstance(a, PackedQuadBitVec):
+            raise TypeError(_QUAD_MIX)
+        if not isinstance(a, (PackedBitVec, PackedCubicBitVec)):
+            raise TypeError("mul_bit needs PackedBitVecs or PackedCubicBitVecs of this system")
+        if len(a) != 1:
+            raise ValueError("The inputs should be single bits")
+        rows = a._rows if isinstance(a, PackedBitVec) else a._lin
+        if rows.shape[1] != self._words:
+            raise ValueError("Cannot mix bitvecs over different numbers of unknowns")
+        if isinstance(a, PackedBitVec):
+            none, off = rows[:0], np.zeros(2, dtype=np.int64)
+            return PackedCubicBitVec(rows, off, none, none, off, none, none, none, self._lin_size)
+        return a
+
+    def mul_bit(self, a, b) -> PackedCubicBitVec:
+        """the exact product of two single bits whose degrees (structural: a bit has cubic terms, or quadratic ones, or neither) add up
+        to 3 at most.  By distributivity lin_a lin_b is one quadratic term and (ta tb) lin_b one cubic term per product of a."""
+        a, b = self._single(a), self._single(b)
+        if a._degree() + b._degree() > 3:
+            raise TypeError(f"mul_bit of bits of degree {a._degree()} and {b._degree()} is of degree {a._degree() + b._degree()}, above 3")
+        if a._degree() < b._degree():
+            a, b = b, a                                # (b is linear now)
+        k = len(a._ta)
+        return PackedCubicBitVec(np.zeros((1, self._words), dtype=np.uint64), np.array([0, 1], dtype=np.int64), a._lin, b._lin,
+                                 np.array([0, k], dtype=np.int64), a._ta, a._tb, np.repeat(b._lin, k, axis=0), self._lin_size)
+
+    # -- zeros -> the factored arrays the device expands ----------------------------------------------------------------------------
+    def _terms(self, zeros: Sequence):
+        """(lin, off2, ta, tb, off3, ua, ub, uc) of all the bits of ``zeros``, in order; no row is dropped (PackedQuadraticSystem._terms)"""
+        none = np.zeros((0, self._words), dtype=np.uint64)
+        acc = none[:0]
+        vec = PackedCubicBitVec(acc, np.zeros(1, dtype=np.int64), none, none, np.zeros(1, dtype=np.int64), none, none, none, self._lin_size)
+        parts = []
+        for z in zeros:
+            if isinstance(z, PackedQuadBitVec):
+                raise TypeError(_QUAD_MIX)
+            if isinstance(z, PackedBitVec):
+                z = vec._linear(z._rows)
+            elif isinstance(z, BitVec):
+                raise TypeError("cannot mix packed and tuple-of-int BitVecs")
+            elif isinstance(z, int) and z in (0, 1):                       # the literal 0, or the equation "1 = 0"
+                lin = np.zeros((1, self._words), dtype=np.uint64)
+                lin[0, 0] = z
+                z = vec._linear(lin)
+            elif not isinstance(z, PackedCubicBitVec):
+                raise TypeError("a bare equation of a packed cubic system is 0 or 1: build the others from gens() and mul_bit")
+            if z._lin.shape[1] != self._words:
+                raise ValueError("Cannot mix bitvecs over different numbers of unknowns")
+            parts.append(z)
+        cnt = lambda name: np.concatenate([np.zeros(0, dtype=np.int64)] + [np.diff(getattr(z, name)) for z in parts])      # noqa: E731
+        cat = lambda name: np.concatenate([none] + [getattr(z, name) for z in parts])                                       # noqa: E731
+        lin = cat("_lin")
+        off2, off3 = np.zeros(len(lin) + 1, dtype=np.int64), np.zeros(len(lin) + 1, dtype=np.int64)
+        np.cumsum(cnt("_off2"), out=off2[1:])
+        np.cumsum(cnt("_off3"), out=off3[1:])
+        return lin, off2, cat("_ta"), cat("_tb"), off3, cat("_ua"), cat("_ub"), cat("_uc")
+
+    def get_eqs(self, zeros: Sequence) -> list:
+        """equation ints over the cubic columns, expanded on the device (needs the GPU); zero rows are dropped"""
+        from . import hip                              # noqa: PLC0415  (ctypes binding, first use only)
+        terms = self._terms(zeros)
+        if not len(terms[0]):
+            return []
+        mask = (1 << self._cols) - 1
+        eqs = []
+        for r in hip.cubic_expand_words(*terms, self._lin_size):
+            v = int.from_bytes(r.tobytes(), "little")
+            eqs.append(((v & mask) << 1) | (v >> self._cols))              # column c is bit c + 1, column cols the constant
+        return [e for e in eqs if e]
+
+    # -- boundary call ---------------------------------------------------------------------------------------------------------------
+    def _solve_internal(self, zeros: Sequence, mode: int):
+        terms = self._terms(zeros)
+        return m4ri_solve_cubic_packed(*terms, self._lin_size, max(len(terms[0]), self._cols), mode)      # (the boundary wants rows >= cols)
+
+    def convert_sol(self, s: int) -> Optional[tuple]:
+        """the values of the generators at a raw point over the cubic columns whose pair and triple coordinates are the products of
+        its linear bits, None for any other point"""
+        n = self._lin_size
+        if not self._xl_products_match(s, n, 3):
+            return None
+        return self._convert_sol(s & ((1 << n) - 1))
+
+    def solve_one(self, zeros: Sequence):
+        # the particular solution of the linearised system need not be consistent: take the first one that is
+        for sol in self.solve_all(zeros):
+            return sol
+        return None
+
+    def _raw_point(self, lin: int) -> int:
+        """the raw point over the cubic columns whose linear part is ``lin``"""
+        n = self._lin_size
+        pi, pj, ti, tj, tl = self._xl_index(n)
+        x = np.array([(lin >> i) & 1 for i in range(n)], dtype=np.uint8)
+        bits = np.concatenate([x, x[pi] & x[pj], x[ti] & x[tj] & x[tl]])
+        return int.from_bytes(np.packbits(bits, bitorder="little").tobytes(), "little")
+
+    def evaluate(self, bv, sol: tuple) -> int:
+        raw, shift = 0, 0
+        for value, width in zip(sol, self._sizes):
+            raw |= value << shift
+            shift += width
+        return bv.evaluate(self._raw_point(raw) if isinstance(bv, PackedCubicBitVec) else raw)
+
+
+for _name in ("get_rows", "_stack_rows", "_flat_rows", "factor", "bit_assert", "_solve_internal_rhs", "solve_raw_one_rhs", "solve_raw_space_rhs",
+              "solve_one_rhs"):
+    setattr(PackedCubicSystem, _name, _refuse_system(_name))
+del _name

@@ -365,6 +365,42 @@ int gf2bv_quad_expand_words(const uint64_t *lin, const int64_t *term_off, const 
 int gf2bv_solve_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t rows_live,
                            int64_t rows, int64_t n_lin, int mode, int device, gf2bv_result **out);
 
+/* ---- cubic expansion: factored cubic equations -> linearised rows over the monomials of degree <= 3, on the device ----------
+ * A cubic equation in n_lin unknowns kept FACTORED: a linear form plus products of two and products of three affine forms, every
+ * form Wl = ceil((n_lin + 1) / 64) words in the equation-int order (bit 0 = constant, bit 1 + g = unknown g; bits above n_lin ignored).
+ *   lin[rows_live][Wl]           the linear part of each row,
+ *   off2[rows_live + 1]          int64, starts at 0, never decreases: row r owns the products ta[t] * tb[t], t in off2[r] .. off2[r+1],
+ *   ta[T2][Wl], tb[T2][Wl]       their operands, T2 = off2[rows_live] (may be null when T2 is 0, host forms only),
+ *   off3[rows_live + 1]          the same for the products ua[u] * ub[u] * uc[u], u in off3[r] .. off3[r+1],
+ *   ua[T3][Wl], ub, uc           their operands, T3 = off3[rows_live] (may be null when T3 is 0, host forms only).
+ * Row r of the output is e = lin[r] ^ XOR_t ta[t] tb[t] ^ XOR_u ua[u] ub[u] uc[u], the products being the EXACT products of
+ * GF(2)[x] / (x_i^2 + x_i): constants multiply like anything else.  (This is NOT the mul of the quadratic expansion above, which
+ * follows QuadraticSystem._mul_bit and has no constant x linear cross terms.)  The layout is degree-3 XL's augmented-words row over
+ * cols3 = n_lin + C(n_lin,2) + C(n_lin,3): column c < n_lin unknown c, pair (i, j), j < i, at n_lin + C(i,2) + j, triple (i, j, l),
+ * l < j < i, at cols2 + C(i,3) + C(j,2) + l, the constant at column cols3, every bit behind it up to the end of the stride zero.
+ * Rows rows_live .. rows - 1 are written as zeros.
+ * gf2bv_cubic_expand_device: everything in device memory; the kernel is enqueued on `stream` (a HIP stream handle or NULL) and the
+ * call returns: gf2bv_solve_device on the same stream consumes d_aug with no synchronisation in between.  d_aug 16-byte aligned,
+ * stride_words even and >= ceil((cols3 + 1) / 64).  The offsets cannot be checked there: a row whose offsets (of either kind)
+ * decrease or are negative is expanded as its linear part.
+ * gf2bv_cubic_expand_words: host pointers in, rows x stride_words words back in host memory (upload, kernel, download).
+ * gf2bv_solve_cubic_terms: upload, expansion into a buffer of the pool, gf2bv_solve_device on the same pool stream; rows >= cols3.
+ * Argument errors (null pointers, n_lin < 1 or cols3 >= 2^31 - 64, rows_live outside 0..rows, either offset array not starting at 0
+ * or decreasing, rows < cols3 for the solve entry, a bad stride or mode, operands that do not fit the kernel's 64 KiB of LDS) return
+ * GF2BV_ERR_ARG before any device is touched; an expansion that does not fit on the device returns GF2BV_ERR_NOMEM.
+ * gf2bv_cubic_chunks (pure, no device): how many quadratic and how many cubic terms of a row one pass of the kernel holds in LDS at
+ * this n_lin; a row with more of either takes several passes. */
+int gf2bv_cubic_expand_device(const void *d_lin, const void *d_off2, const void *d_ta, const void *d_tb, const void *d_off3,
+                              const void *d_ua, const void *d_ub, const void *d_uc, int64_t rows_live, int64_t rows, int64_t n_lin,
+                              void *d_aug, int64_t stride_words, int device, void *stream);
+int gf2bv_cubic_expand_words(const uint64_t *lin, const int64_t *off2, const uint64_t *ta, const uint64_t *tb, const int64_t *off3,
+                             const uint64_t *ua, const uint64_t *ub, const uint64_t *uc, int64_t rows_live, int64_t rows,
+                             int64_t n_lin, uint64_t *out_aug, int64_t stride_words, int device);
+int gf2bv_solve_cubic_terms(const uint64_t *lin, const int64_t *off2, const uint64_t *ta, const uint64_t *tb, const int64_t *off3,
+                            const uint64_t *ua, const uint64_t *ub, const uint64_t *uc, int64_t rows_live, int64_t rows,
+                            int64_t n_lin, int mode, int device, gf2bv_result **out);
+int gf2bv_cubic_chunks(int64_t n_lin, int32_t *quad_chunk, int32_t *cubic_chunk);
+
 /* The factored form in front of the entries that keep a factorization, share one elimination or batch: each uploads the term
  * arrays (host pointers, as gf2bv_solve_quad_terms takes them), expands them into a buffer of the pool and runs the device entry
  * named on the same pool stream; the host waits only where that entry waits, and the buffers are back in the pool on return.
