@@ -1114,6 +1114,27 @@ PyObject *py_m4ri_solve_cubic_packed(PyObject *, PyObject *const *args, Py_ssize
 	return result_to_py(res, mode, device);
 }
 
+// m4ri_solve_xl4_cubic_packed(lin, off2, ta, tb, off3, ua, ub, uc, n_lin, mode[, device]) -> None | int | AffineSpace over the
+// n_lin + C(n_lin,2) + C(n_lin,3) + C(n_lin,4) columns of degree-4 XL.  New entry (no counterpart in the reference):
+// m4ri_solve_cubic_packed's arrays (every row live), expanded, multiplied by 1 and by every unknown, padded and solved on the device
+// (gf2bv_solve_xl4_cubic_terms; gf2bv_hip.h, "degree-4 XL on cubic equations")
+PyObject *py_m4ri_solve_xl4_cubic_packed(PyObject *, PyObject *const *args, Py_ssize_t nargs)
+{
+	int device;
+	if (!entry_device("m4ri_solve_xl4_cubic_packed", 10, args, nargs, &device)) return nullptr;
+	long mode;
+	CubicBuffers cb;
+	if (!parse_mode(args[9], &mode) || !cb.parse(args, args[8])) return nullptr;
+	gf2bv_result *res = nullptr;
+	int rc;
+	Py_BEGIN_ALLOW_THREADS
+	rc = gf2bv_solve_xl4_cubic_terms(cb.words(0), cb.offsets(1), cb.words(2), cb.words(3), cb.offsets(4), cb.words(5), cb.words(6), cb.words(7),
+	                                 cb.live, cb.n, (int)mode, device, &res);
+	Py_END_ALLOW_THREADS
+	if (rc != GF2BV_OK) return raise_rc(rc, "solve");
+	return result_to_py(res, mode, device);
+}
+
 // ---- degree-3 XL: quadratic equations multiplied by 1 and by every unknown on the device (gf2bv_hip.h, "degree-3 XL") --------------
 // (every entry of this section and of the hybrid one is a template over the degree D: m4ri_solve_xl4* are the same code on the xl4
 // entries of the library, over the monomials of degree <= 4 -- gf2bv_hip.h, "degree-4 XL")
@@ -1867,6 +1888,8 @@ PyMethodDef module_methods[] = {
 	 "m4ri_solve_xl3_guess(equations, n_lin, guess, a0, na, mode, device=None)\n--\n\nHybrid XL: the guessed unknowns substituted for the assignments a0 .. a0 + na - 1 and every assignment's degree-3 XL system solved on the GPU as one batch."},
 	{"m4ri_solve_xl3_guess_quad_packed", FAST(py_m4ri_solve_xl_guess_quad_packed<3>), METH_FASTCALL,
 	 "m4ri_solve_xl3_guess_quad_packed(lin, term_off, ta, tb, n_lin, guess, a0, na, mode, device=None)\n--\n\nm4ri_solve_xl3_guess on a quadratic system kept factored."},
+	{"m4ri_solve_xl4_cubic_packed", FAST(py_m4ri_solve_xl4_cubic_packed), METH_FASTCALL,
+	 "m4ri_solve_xl4_cubic_packed(lin, off2, ta, tb, off3, ua, ub, uc, n_lin, mode, device=None)\n--\n\nDegree-4 XL on a cubic system kept factored: every equation multiplied by 1 and by each unknown on the GPU, solved over the monomials of degree <= 4."},
 	{"m4ri_solve_xl4", FAST(py_m4ri_solve_xl<4>), METH_FASTCALL,
 	 "m4ri_solve_xl4(equations, n_lin, mode, device=None)\n--\n\nDegree-4 XL: m4ri_solve_xl3 with the products by every pair of unknowns too, solved over the monomials of degree <= 4."},
 	{"m4ri_solve_xl4_quad_packed", FAST(py_m4ri_solve_xl_quad_packed<4>), METH_FASTCALL,

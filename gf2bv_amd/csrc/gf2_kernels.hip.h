@@ -5386,3 +5386,127 @@ k_cubic_expand(const u64 *__restrict__ lin, const i64 *__restrict__ off2, const 
 		} while (t0 < t1 || u0 < u1);
 	}
 }
+
+
+// ==========================================================================================
+// DEGREE-4 XL ON CUBIC ROWS: every cubic row, and its product with every unknown, over the monomials of degree <= 4
+// ==========================================================================================
+// (host side: gf2bv_xl4_cubic_expand_device in gf2_solver.hip; the front-end: PackedCubicSystem.solve_all_xl4)
+//
+// Source: m rows as k_cubic_expand writes them -- column c < n unknown c (l_c), pair (i, j), j < i, at n + C(i,2) + j (q_ij), triple
+// (i, j, l), l < j < i, at cols2 + C(i,3) + C(j,2) + l (t_ijl), the constant c at cols3; W3 = ceil((cols3 + 1) / 64) words are read.
+// Output: k_xl4_expand's columns -- the first cols3 as in the source, quadruple (i, j, l, p), p < l < j < i, at
+// cols3 + C(i,4) + C(j,3) + C(l,2) + p, the constant at cols4.  Equation e owns the rows e(n+1) .. e(n+1) + n: first f_e itself (its
+// own cols3 columns, no quadruple, the constant moved to cols4), then x_k f_e for k = 0 .. n-1 with x^2 = x.  A monomial M of x_k f is
+// f[M] ^ f[M - k] where M contains k and 0 elsewhere:
+//   unknown k = c ^ l_k, pair {k, i} = l_i ^ q_ki, triple {k, a, b} = q_ab ^ t_kab, quadruple containing k = t of the other three;
+//   constant 0.
+// Runs of consecutive columns of x_k f:
+//   pairs (i, 0..i-1):            i = k: l[0..k) ^ q(k, 0..k-1);  i > k: the one bit l_i ^ q(i, k) at position k;  i < k: nothing.
+//   triples (i, j, 0..j-1):       i = k: q(j, 0..j-1) ^ t(k, j, 0..j-1);  j = k: q(i, 0..k-1) ^ t(i, k, 0..k-1);  k < j: the one bit
+//                                 q(i, j) ^ t(i, j, k) at position k;  else nothing.
+//   quadruples (i, j, l, 0..l-1): k = i: t(j, l, 0..l-1);  k = j: t(i, l, 0..l-1);  k = l: t(i, j, 0..l-1);  k < l: the one bit
+//                                 t(i, j, l) at position k;  else nothing.
+// So pairs below C(k,2), triples below C(k,3) and quadruples below C(k,4) are zero (the word leaves at once), and inside a block i > k
+// the runs that cannot contain k are skipped in one step (the jumps only ever move forward in (i, j, l)).  Whole runs are 64-bit
+// windows of the source row in LDS, each masked to its run: no bit behind the source's constant column reaches the output.
+// Work split as in k_xl3_expand: contiguous spans of rows per workgroup, so a source row goes to LDS once for the products of it in
+// the span; every lane forms two consecutive output words per step and stores them as 16 bytes, consecutive lanes consecutive
+// 16 bytes: each output word has one writer, no atomics.  Rows >= m(n+1) are written as zeros.
+// LDS: W3 words (dynamic).
+
+// columns c0 .. c0 + 63 of the row x_k f (k < 0: f itself) of the cubic source row `src`
+__device__ __forceinline__ u64 xl4c_word(const u64 *src, int W3, i64 n, i64 cols2, i64 cols3, i64 cols4, i64 c0, int k)
+{
+	if (k < 0) {                                                           // f: its own columns, no quadruple, the constant behind all
+		u64 acc = c0 < cols3 ? qx_window(src, W3, c0) & qx_low(cols3 - c0) : 0;
+		if (cols4 >= c0 && cols4 < c0 + 64) acc |= xl_bit(src, cols3) << (cols4 - c0);
+		return acc;
+	}
+	u64 acc = 0;
+	if (k >= c0 && k < c0 + 64) acc = (xl_bit(src, cols3) ^ xl_bit(src, k)) << (k - c0);
+	const i64 p_lo = (c0 > n ? c0 : n) - n, p_hi = (c0 + 64 < cols2 ? c0 + 64 : cols2) - n;        // the word's pair indices
+	if (p_lo < p_hi && p_hi > xl_c2(k)) {
+		i64 i = xl_tri_root(p_lo);
+		if (i < k) i = k;
+		for (i64 s = xl_c2(i); s < p_hi; s += i, i++) {                    // run i: pairs s .. s + i - 1
+			const i64 j0 = (p_lo > s ? p_lo : s) - s, j1 = (p_hi < s + i ? p_hi : s + i) - s;
+			if (i == k) {
+				if (j0 < j1) acc |= ((qx_window(src, W3, j0) ^ qx_window(src, W3, n + s + j0)) & qx_low(j1 - j0)) << (n + s + j0 - c0);
+			} else if (k >= j0 && k < j1)
+				acc |= (xl_bit(src, i) ^ xl_bit(src, n + s + k)) << (n + s + k - c0);
+		}
+	}
+	const i64 t_lo = (c0 > cols2 ? c0 : cols2) - cols2, t_hi = (c0 + 64 < cols3 ? c0 + 64 : cols3) - cols2;      // its triple indices
+	if (t_lo < t_hi && t_hi > xl_c3(k)) {
+		i64 i = xl_tet_root(t_lo), j = xl_tri_root(t_lo - xl_c3(i));       // the run t_lo lies in: 1 <= j < i
+		i64 s = xl_c3(i) + xl_c2(j);
+		while (s < t_hi) {                                                 // run (i, j): triples s .. s + j - 1
+			if (i < k) { i = k; j = 1; s = xl_c3(i); continue; }           // (k >= 3 here: nothing below block k)
+			if (i > k && j < k) { j = k; s = xl_c3(i) + xl_c2(j); continue; }      // (nothing in the runs below j = k)
+			const i64 j0 = (t_lo > s ? t_lo : s) - s, j1 = (t_hi < s + j ? t_hi : s + j) - s;
+			if (j0 < j1) {
+				if (i == k || j == k)                                      // q of the other member with 0..j-1, and the triples themselves
+					acc |= ((qx_window(src, W3, n + xl_c2(i == k ? j : i) + j0) ^ qx_window(src, W3, cols2 + s + j0)) & qx_low(j1 - j0))
+					       << (cols2 + s + j0 - c0);
+				else if (k >= j0 && k < j1)                                // (k < j)
+					acc |= (xl_bit(src, n + xl_c2(i) + j) ^ xl_bit(src, cols2 + s + k)) << (cols2 + s + k - c0);
+			}
+			s += j;
+			if (++j == i) { i++; j = 1; }
+		}
+	}
+	const i64 u_lo = (c0 > cols3 ? c0 : cols3) - cols3, u_hi = (c0 + 64 < cols4 ? c0 + 64 : cols4) - cols3;      // its quadruple indices
+	if (u_lo < u_hi && u_hi > xl_c4(k)) {
+		i64 i = xl_quart_root(u_lo), j = xl_tet_root(u_lo - xl_c4(i));     // the run u_lo lies in: 1 <= l < j < i
+		i64 l = xl_tri_root(u_lo - xl_c4(i) - xl_c3(j));
+		i64 s = xl_c4(i) + xl_c3(j) + xl_c2(l);
+		while (s < u_hi) {                                                 // run (i, j, l): quadruples s .. s + l - 1
+			bool jump = true;                                              // to the next run that can hold anything
+			if (i < k) { i = k; j = 2; l = 1; }                            // (k >= 4 here: nothing below block k)
+			else if (i > k && j < k) { j = k; l = 1; }                     // i > k: k is j or l, or lies below l
+			else if (i > k && j > k && l < k) l = k;
+			else jump = false;
+			if (jump) { s = xl_c4(i) + xl_c3(j) + xl_c2(l); continue; }
+			const i64 j0 = (u_lo > s ? u_lo : s) - s, j1 = (u_hi < s + l ? u_hi : s + l) - s;
+			if (j0 < j1) {
+				if (i == k || j == k || l == k) {                          // t of the other two with 0..l-1
+					const i64 hi = i == k ? j : i, lo = l == k ? j : l;
+					acc |= (qx_window(src, W3, cols2 + xl_c3(hi) + xl_c2(lo) + j0) & qx_low(j1 - j0)) << (cols3 + s + j0 - c0);
+				} else if (k >= j0 && k < j1)                              // (k < l)
+					acc |= xl_bit(src, cols2 + xl_c3(i) + xl_c2(j) + l) << (cols3 + s + k - c0);
+			}
+			s += l;
+			if (++l == j) { l = 1; if (++j == i) { i++; j = 2; } }
+		}
+	}
+	return acc;
+}
+
+__global__ void __launch_bounds__(256)
+k_xl4_cubic_expand(const u64 *__restrict__ cubic, i64 m, i64 cubic_stride, int n, int W3, i64 rows, u64 *__restrict__ out, i64 stride)
+{
+	extern __shared__ u64 xl_lds[];                    // the source row: W3 words
+	const i64 cols2 = (i64)n + xl_c2(n), cols3 = cols2 + xl_c3(n), cols4 = cols3 + xl_c4(n);
+	const i64 npair = stride >> 1;                     // 16-byte pieces of a row (stride is even)
+	const i64 span = (rows + gridDim.x - 1) / gridDim.x;
+	const i64 r0 = (i64)blockIdx.x * span, r1 = r0 + span < rows ? r0 + span : rows;
+	i64 have = -1;                                     // the equation whose row is in LDS
+	for (i64 r = r0; r < r1; r++) {
+		ulonglong2 *o = reinterpret_cast<ulonglong2 *>(out + r * stride);
+		const i64 e = r / (n + 1);
+		if (e >= m) {
+			for (i64 p = threadIdx.x; p < npair; p += blockDim.x) o[p] = make_ulonglong2(0, 0);
+			continue;
+		}
+		if (e != have) {
+			__syncthreads();                           // the rows before have read theirs
+			for (int w = threadIdx.x; w < W3; w += blockDim.x) xl_lds[w] = cubic[e * cubic_stride + w];
+			__syncthreads();
+			have = e;
+		}
+		const int k = (int)(r - e * (n + 1)) - 1;
+		for (i64 p = threadIdx.x; p < npair; p += blockDim.x)
+			o[p] = make_ulonglong2(xl4c_word(xl_lds, W3, n, cols2, cols3, cols4, 128 * p, k), xl4c_word(xl_lds, W3, n, cols2, cols3, cols4, 128 * p + 64, k));
+	}
+}

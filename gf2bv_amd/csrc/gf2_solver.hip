@@ -4846,16 +4846,20 @@ int enqueue_cubic_expand(const CubicTerms &c, u64 *d_aug, i64 stride, hipStream_
 }
 
 // XL (k_xl3_expand, k_xl4_expand): m quadratic rows over n unknowns -- the rows k_quad_expand writes -- become `rows` rows over the
-// monomials of degree <= `degree`: each equation, its product with every unknown and (degree 4) with every pair of unknowns, then zeros
+// monomials of degree <= `degree`: each equation, its product with every unknown and (degree 4) with every pair of unknowns, then zeros.
+// src = 3 (k_xl4_cubic_expand, degree 4 only): the m rows are cubic -- the rows k_cubic_expand writes -- and the multipliers stop at
+// the unknowns
 struct XlShape {
 	i64 m = 0, n = 0, rows = 0;
 	int degree = 3;
+	int src = 2;                       // the degree of the source rows
 	i64 cols2() const { return n + n * (n - 1) / 2; }
 	i64 cols3() const { return cols2() + n * (n - 1) * (n - 2) / 6; }
 	i64 cols4() const { return cols3() + n * (n - 1) * (n - 2) * (n - 3) / 24; }
 	i64 cols() const { return degree == 4 ? cols4() : cols3(); }
-	i64 per_eq() const { return degree == 4 ? 1 + cols2() : n + 1; }      // rows an equation owns
-	i64 w2() const { return (cols2() + 1 + 63) / 64; }         // words of a source row, which the kernel holds in LDS
+	i64 per_eq() const { return degree == 4 && src == 2 ? 1 + cols2() : n + 1; }      // rows an equation owns
+	i64 w2() const { return (cols2() + 1 + 63) / 64; }         // words of a quadratic row
+	i64 wsrc() const { return src == 3 ? (cols3() + 1 + 63) / 64 : w2(); }      // words of a source row, which the kernel holds in LDS
 	i64 wt() const { return (cols() + 1 + 63) / 64; }
 	i64 live() const { return m * per_eq(); }
 };
@@ -4865,18 +4869,23 @@ constexpr i64 kXl3LdsBytes = 65536;
 // to the columns
 int check_xl(XlShape &x, i64 quad_stride, bool pad = false)
 {
-	const bool d4 = x.degree == 4;
+	const bool d4 = x.degree == 4 && x.src == 2, cubic = x.src == 3;
+	if (cubic && x.degree != 4) return fail(GF2BV_ERR_ARG, "cubic rows take degree 4");
 	if (x.n < 1 || x.n > 65535 || x.cols() >= (1ll << 31) - 64)
-		return fail(GF2BV_ERR_ARG, d4 ? "n_lin must be at least 1 and n_lin + C(n_lin,2) + C(n_lin,3) + C(n_lin,4) below 2^31 - 64"
-		                              : "n_lin must be at least 1 and n_lin + C(n_lin,2) + C(n_lin,3) below 2^31 - 64");
+		return fail(GF2BV_ERR_ARG, d4 || cubic ? "n_lin must be at least 1 and n_lin + C(n_lin,2) + C(n_lin,3) + C(n_lin,4) below 2^31 - 64"
+		                                       : "n_lin must be at least 1 and n_lin + C(n_lin,2) + C(n_lin,3) below 2^31 - 64");
 	if (x.m < 0 || x.m >= (1ll << 31) - 64 || x.live() >= (1ll << 31) - 64)
 		return fail(GF2BV_ERR_ARG, d4 ? "m(1 + n_lin + C(n_lin,2)) must stay below 2^31 - 64" : "m(n_lin + 1) must stay below 2^31 - 64");
 	if (pad) x.rows = std::max(x.live(), x.cols());
 	if (x.rows >= (1ll << 31) - 64 || x.rows < x.live())
 		return fail(GF2BV_ERR_ARG, d4 ? "rows must be at least m(1 + n_lin + C(n_lin,2)) and below 2^31 - 64"
 		                              : "rows must be at least m(n_lin + 1) and below 2^31 - 64");
-	if (x.w2() * 8 > kXl3LdsBytes) return fail(GF2BV_ERR_ARG, "a quadratic row of this n_lin does not fit the expansion kernel's LDS (64 KiB)");
-	if (quad_stride < x.w2()) return fail(GF2BV_ERR_ARG, "quad_stride_words does not cover the quadratic columns and the constant");
+	if (x.wsrc() * 8 > kXl3LdsBytes)
+		return fail(GF2BV_ERR_ARG, cubic ? "a cubic row of this n_lin does not fit the expansion kernel's LDS (64 KiB)"
+		                                 : "a quadratic row of this n_lin does not fit the expansion kernel's LDS (64 KiB)");
+	if (quad_stride < x.wsrc())
+		return fail(GF2BV_ERR_ARG, cubic ? "cubic_stride_words does not cover the cubic columns and the constant"
+		                                 : "quad_stride_words does not cover the quadratic columns and the constant");
 	return GF2BV_OK;
 }
 
@@ -4888,12 +4897,16 @@ int xl4_parts(const XlShape &x, i64 nsys)
 }
 
 // (device pointers, already checked) the kernel on `st`.  Degree 3: a few thousand workgroups, each a contiguous span of the rows;
-// degree 4: a workgroup per (equation, part) unit
+// degree 4: a workgroup per (equation, part) unit; cubic rows: degree 3's spans
 int enqueue_xl_expand(const XlShape &x, const u64 *d_quad, i64 quad_stride, u64 *d_aug, i64 stride, hipStream_t st)
 {
 	if (x.rows == 0) return GF2BV_OK;
 	const unsigned block = (unsigned)std::min<i64>(256, round_up(std::max<i64>(stride / 2, 1), 64));
-	if (x.degree == 4) {
+	if (x.src == 3) {
+		const unsigned grid = (unsigned)std::min<i64>(x.rows, 256 * 16);
+		hipLaunchKernelGGL(k_xl4_cubic_expand, dim3(grid), dim3(block), sizeof(u64) * (size_t)x.wsrc(), st, d_quad, x.m, quad_stride, (int)x.n,
+		                   (int)x.wsrc(), x.rows, d_aug, stride);
+	} else if (x.degree == 4) {
 		const int parts = xl4_parts(x, 1);
 		const unsigned grid = (unsigned)std::min<i64>(std::max<i64>(x.m * parts, std::min<i64>(x.rows - x.live(), 4096)), 1 << 20);
 		hipLaunchKernelGGL(k_xl4_expand, dim3(grid), dim3(block), sizeof(u64) * (size_t)x.w2(), st, d_quad, x.m, quad_stride, (int)x.n,
@@ -5087,7 +5100,7 @@ struct QuadStage {
 		ds = stride;
 		return upload(&d_aug, quad, sizeof(u64) * (size_t)(m * stride));
 	}
-	// The XL expansion (x.degree) of the x.m quadratic rows in d_aug into d_xl, x.rows rows `stride` words apart rounded up to an even xs,
+	// The XL expansion (x.degree, x.src) of the x.m quadratic or cubic rows in d_aug into d_xl, x.rows rows `stride` words apart rounded up to an even xs,
 	// behind whatever wrote d_aug on the stream
 	int expand_xl(const XlShape &x, i64 stride)
 	{
@@ -5366,12 +5379,13 @@ int gf2bv_solve_batch_quad_terms(const uint64_t *lin, const int64_t *term_off, c
 }
 
 // ---- degree-3 XL: the quadratic rows (expanded already, or factored) multiplied by 1 and by every unknown on the device
-static int xl_expand_device(int degree, const void *d_quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int64_t rows, void *d_aug,
+// (src: the degree of the source rows -- 2 everywhere but in the gf2bv_*_xl4_cubic_* entries at the end, whose rows are cubic)
+static int xl_expand_device(int degree, int src, const void *d_quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int64_t rows, void *d_aug,
                             int64_t stride_words, int device, void *stream)
 {
 	return catching([&]() -> int {
 	XlShape x;
-	x.degree = degree; x.m = m; x.n = n_lin; x.rows = rows;
+	x.degree = degree; x.src = src; x.m = m; x.n = n_lin; x.rows = rows;
 	if (!d_aug || (!d_quad && m > 0)) return fail(GF2BV_ERR_ARG, "null pointer");
 	int rc = check_xl(x, quad_stride_words);
 	if (rc) return rc;
@@ -5382,12 +5396,12 @@ static int xl_expand_device(int degree, const void *d_quad, int64_t m, int64_t q
 	});
 }
 
-static int xl_expand_words(int degree, const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int64_t rows, uint64_t *out_aug,
+static int xl_expand_words(int degree, int src, const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int64_t rows, uint64_t *out_aug,
                            int64_t stride_words, int device)
 {
 	return catching([&]() -> int {
 	XlShape x;
-	x.degree = degree; x.m = m; x.n = n_lin; x.rows = rows;
+	x.degree = degree; x.src = src; x.m = m; x.n = n_lin; x.rows = rows;
 	if ((!out_aug && rows > 0) || (!quad && m > 0)) return fail(GF2BV_ERR_ARG, "null pointer");
 	int rc = check_xl(x, quad_stride_words);
 	if (rc) return rc;
@@ -5401,7 +5415,7 @@ static int xl_expand_words(int degree, const uint64_t *quad, int64_t m, int64_t 
 	});
 }
 
-static int solve_xl_words(int degree, const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int mode, int device,
+static int solve_xl_words(int degree, int src, const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int mode, int device,
                           gf2bv_result **out)
 {
 	return catching([&]() -> int {
@@ -5409,7 +5423,7 @@ static int solve_xl_words(int degree, const uint64_t *quad, int64_t m, int64_t q
 	*out = nullptr;
 	if (!quad && m > 0) return fail(GF2BV_ERR_ARG, "null pointer");
 	XlShape x;
-	x.degree = degree; x.m = m; x.n = n_lin;
+	x.degree = degree; x.src = src; x.m = m; x.n = n_lin;
 	int rc = check_xl(x, quad_stride_words, true);
 	if (!rc) rc = check_shape(x.rows, x.cols(), mode);
 	if (!rc) rc = check_device(device);
@@ -5608,30 +5622,30 @@ static int xl_guess_chunk_device(int degree, int64_t m, int64_t n_lin, int64_t n
 int gf2bv_xl3_expand_device(const void *d_quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int64_t rows, void *d_aug,
                             int64_t stride_words, int device, void *stream)
 {
-	return xl_expand_device(3, d_quad, m, quad_stride_words, n_lin, rows, d_aug, stride_words, device, stream);
+	return xl_expand_device(3, 2, d_quad, m, quad_stride_words, n_lin, rows, d_aug, stride_words, device, stream);
 }
 int gf2bv_xl4_expand_device(const void *d_quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int64_t rows, void *d_aug,
                             int64_t stride_words, int device, void *stream)
 {
-	return xl_expand_device(4, d_quad, m, quad_stride_words, n_lin, rows, d_aug, stride_words, device, stream);
+	return xl_expand_device(4, 2, d_quad, m, quad_stride_words, n_lin, rows, d_aug, stride_words, device, stream);
 }
 int gf2bv_xl3_expand_words(const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int64_t rows, uint64_t *out_aug,
                            int64_t stride_words, int device)
 {
-	return xl_expand_words(3, quad, m, quad_stride_words, n_lin, rows, out_aug, stride_words, device);
+	return xl_expand_words(3, 2, quad, m, quad_stride_words, n_lin, rows, out_aug, stride_words, device);
 }
 int gf2bv_xl4_expand_words(const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int64_t rows, uint64_t *out_aug,
                            int64_t stride_words, int device)
 {
-	return xl_expand_words(4, quad, m, quad_stride_words, n_lin, rows, out_aug, stride_words, device);
+	return xl_expand_words(4, 2, quad, m, quad_stride_words, n_lin, rows, out_aug, stride_words, device);
 }
 int gf2bv_solve_xl3_words(const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int mode, int device, gf2bv_result **out)
 {
-	return solve_xl_words(3, quad, m, quad_stride_words, n_lin, mode, device, out);
+	return solve_xl_words(3, 2, quad, m, quad_stride_words, n_lin, mode, device, out);
 }
 int gf2bv_solve_xl4_words(const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int mode, int device, gf2bv_result **out)
 {
-	return solve_xl_words(4, quad, m, quad_stride_words, n_lin, mode, device, out);
+	return solve_xl_words(4, 2, quad, m, quad_stride_words, n_lin, mode, device, out);
 }
 int gf2bv_solve_xl3_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t m, int64_t n_lin,
                                int mode, int device, gf2bv_result **out)
@@ -5704,6 +5718,45 @@ int gf2bv_xl3_guess_chunk_device(int64_t m, int64_t n_lin, int64_t nguess, int d
 int gf2bv_xl4_guess_chunk_device(int64_t m, int64_t n_lin, int64_t nguess, int device, int64_t *chunk)
 {
 	return xl_guess_chunk_device(4, m, n_lin, nguess, device, chunk);
+}
+
+// ---- degree-4 XL on cubic rows (k_xl4_cubic_expand): the bodies above with src = 3, and the factored form staged through both kernels
+int gf2bv_xl4_cubic_expand_device(const void *d_cubic, int64_t m, int64_t cubic_stride_words, int64_t n_lin, int64_t rows, void *d_aug,
+                                  int64_t stride_words, int device, void *stream)
+{
+	return xl_expand_device(4, 3, d_cubic, m, cubic_stride_words, n_lin, rows, d_aug, stride_words, device, stream);
+}
+int gf2bv_xl4_cubic_expand_words(const uint64_t *cubic, int64_t m, int64_t cubic_stride_words, int64_t n_lin, int64_t rows, uint64_t *out_aug,
+                                 int64_t stride_words, int device)
+{
+	return xl_expand_words(4, 3, cubic, m, cubic_stride_words, n_lin, rows, out_aug, stride_words, device);
+}
+int gf2bv_solve_xl4_cubic_words(const uint64_t *cubic, int64_t m, int64_t cubic_stride_words, int64_t n_lin, int mode, int device,
+                                gf2bv_result **out)
+{
+	return solve_xl_words(4, 3, cubic, m, cubic_stride_words, n_lin, mode, device, out);
+}
+int gf2bv_solve_xl4_cubic_terms(const uint64_t *lin, const int64_t *off2, const uint64_t *ta, const uint64_t *tb, const int64_t *off3,
+                                const uint64_t *ua, const uint64_t *ub, const uint64_t *uc, int64_t m, int64_t n_lin, int mode, int device,
+                                gf2bv_result **out)
+{
+	return catching([&]() -> int {
+	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
+	*out = nullptr;
+	const CubicTerms c = cubic_terms(lin, off2, ta, tb, off3, ua, ub, uc, m, m, n_lin);      // the m cubic rows, no padding
+	int rc = check_cubic_terms(c, true);
+	if (rc) return rc;
+	XlShape x;
+	x.degree = 4; x.src = 3; x.m = m; x.n = n_lin;
+	rc = check_xl(x, c.wt(), true);
+	if (!rc) rc = check_shape(x.rows, x.cols(), mode);
+	if (!rc) rc = check_device(device);
+	if (rc) return rc;
+	QuadStage stage(device);
+	if ((rc = stage.expand(c, c.wt()))) return rc;
+	if ((rc = stage.expand_xl(x, x.wt()))) return rc;
+	return gf2bv_solve_device(stage.d_xl, x.rows, x.cols(), stage.xs, mode, device, stage.ps.st, 0, out);
+	});
 }
 
 // k_xl4_expand's quartic root, the same function compiled for the host: the largest i >= 3 with C(i,4) <= u (u >= 0), for checks

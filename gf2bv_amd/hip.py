@@ -45,6 +45,7 @@ EXPORTS = [
     "gf2bv_xl4_expand_device", "gf2bv_xl4_expand_words", "gf2bv_solve_xl4_words", "gf2bv_solve_xl4_quad_terms",
     "gf2bv_xl4_expand_batch_device", "gf2bv_xl4_expand_batch_words", "gf2bv_solve_xl4_guess_words", "gf2bv_solve_xl4_guess_quad_terms",
     "gf2bv_xl4_guess_chunk", "gf2bv_xl4_guess_chunk_device", "gf2bv_xl4_quartic_root",
+    "gf2bv_xl4_cubic_expand_device", "gf2bv_xl4_cubic_expand_words", "gf2bv_solve_xl4_cubic_words", "gf2bv_solve_xl4_cubic_terms",
     "gf2bv_quad_search", "gf2bv_quad_search_alloc", "gf2bv_quad_free", "gf2bv_quad_plan", "gf2bv_quad_points", "gf2bv_quad_forms_search", "gf2bv_quad_last_times",
     "gf2bv_slab_work_words", "gf2bv_slab_tiles", "gf2bv_slab_open", "gf2bv_slab_blocks", "gf2bv_slab_owner",
     "gf2bv_slab_payload_bytes", "gf2bv_slab_factor", "gf2bv_slab_apply", "gf2bv_slab_factor_on", "gf2bv_slab_apply_on",
@@ -173,6 +174,10 @@ def lib():
         L.gf2bv_quad_specialise_words.argtypes = [vp, i64, i64, i64, vp, i64, i64, i64, vp, i64, i32]
         L.gf2bv_xl4_quartic_root.argtypes = [i64]
         L.gf2bv_xl4_quartic_root.restype = i64
+        L.gf2bv_xl4_cubic_expand_device.argtypes = [vp, i64, i64, i64, i64, vp, i64, i32, vp]
+        L.gf2bv_xl4_cubic_expand_words.argtypes = [vp, i64, i64, i64, i64, vp, i64, i32]
+        L.gf2bv_solve_xl4_cubic_words.argtypes = [vp, i64, i64, i64, i32, i32, pp]
+        L.gf2bv_solve_xl4_cubic_terms.argtypes = [vp] * 8 + [i64, i64, i32, i32, pp]
         L.gf2bv_slab_work_words.argtypes = [i64, i64]
         L.gf2bv_slab_work_words.restype = i64
         L.gf2bv_slab_tiles.argtypes = [i64]
@@ -1035,6 +1040,53 @@ def xl3_guess_chunk(m: int, n_lin: int, nguess: int, free_bytes: int | None = No
 def xl4_guess_chunk(m: int, n_lin: int, nguess: int, free_bytes: int | None = None, device: int = 0) -> int:
     """_xl_guess_chunk for degree 4"""
     return _xl_guess_chunk(4, m, n_lin, nguess, free_bytes, device)
+
+
+# -- degree-4 XL on cubic rows: multipliers 1 and x_k, n + 1 rows an equation (gf2bv_hip.h, "degree-4 XL on cubic equations") ------------
+def _cubic_rows(cubic) -> np.ndarray:
+    """cubic rows of the augmented-words layout (what cubic_expand_words returns) as a contiguous [m, stride] array"""
+    cubic = np.ascontiguousarray(cubic, dtype=np.uint64)
+    if cubic.ndim != 2:
+        raise ValueError("the cubic rows must be a 2-D uint64 array, one row per equation")
+    return cubic
+
+
+def xl4_cubic_expand_words(cubic, n_lin: int, rows: int | None = None, stride_words: int | None = None, device: int = 0) -> np.ndarray:
+    """Degree-4 XL of cubic rows on the device (gf2bv_xl4_cubic_expand_words): `cubic` holds m rows as cubic_expand_words returns
+    them; the result is [rows, stride_words] uint64 over xl4_cols(n_lin) columns, rows e(n+1) .. e(n+1) + n equation e and its product
+    with every unknown, rows beyond m(n+1) zero."""
+    cubic = _cubic_rows(cubic)
+    m = len(cubic)
+    rows = m * (n_lin + 1) if rows is None else rows
+    stride = (xl4_cols(n_lin) + 1 + 63) // 64 if stride_words is None else stride_words
+    out = np.empty((max(rows, 0), max(stride, 0)), dtype=np.uint64)
+    _check(lib().gf2bv_xl4_cubic_expand_words(cubic.ctypes.data, m, cubic.shape[1], n_lin, rows, out.ctypes.data, stride, device))
+    return out
+
+
+def xl4_cubic_expand_device(d_cubic: int, m: int, cubic_stride: int, n_lin: int, rows: int, d_aug: int, stride: int, device: int = 0,
+                            stream: int = 0) -> None:
+    """xl4_cubic_expand_words with everything resident in device memory: the kernel is enqueued on `stream` and the call returns; a
+    solve_device on the same stream reads the finished rows."""
+    _check(lib().gf2bv_xl4_cubic_expand_device(d_cubic, m, cubic_stride, n_lin, rows, d_aug, stride, device, stream or None))
+
+
+def solve_xl4_cubic_words(cubic, n_lin: int, mode: int = MODE_SINGLE, device: int = 0) -> Solution:
+    """Cubic rows uploaded, multiplied on the device and solved there (gf2bv_solve_xl4_cubic_words): what solve_words returns for
+    xl4_cubic_expand_words of the same rows padded with zero rows up to xl4_cols(n_lin)."""
+    cubic = _cubic_rows(cubic)
+    h = ctypes.c_void_p()
+    _check(lib().gf2bv_solve_xl4_cubic_words(cubic.ctypes.data, len(cubic), cubic.shape[1], n_lin, mode, device, ctypes.byref(h)))
+    return _take(h, mode)
+
+
+def solve_xl4_cubic_terms(lin, off2, ta, tb, off3, ua, ub, uc, n_lin: int, mode: int = MODE_SINGLE, device: int = 0) -> Solution:
+    """The factored cubic system uploaded, expanded, multiplied and solved on the device (gf2bv_solve_xl4_cubic_terms): what
+    solve_xl4_cubic_words returns for cubic_expand_words of the same arrays."""
+    terms = _cubic_terms(lin, off2, ta, tb, off3, ua, ub, uc, n_lin)
+    h = ctypes.c_void_p()
+    _check(lib().gf2bv_solve_xl4_cubic_terms(*_ptrs(*terms), len(terms[0]), n_lin, mode, device, ctypes.byref(h)))
+    return _take(h, mode)
 
 
 def synth_device(d_ptr: int, rows: int, cols: int, stride: int, seed: int, device: int = 0, stream: int = 0):

@@ -563,6 +563,38 @@ int64_t gf2bv_xl4_guess_chunk(int64_t m, int64_t n_lin, int64_t nguess, int64_t 
 int gf2bv_xl4_guess_chunk_device(int64_t m, int64_t n_lin, int64_t nguess, int device, int64_t *chunk);
 int64_t gf2bv_xl4_quartic_root(int64_t u);
 
+/* ---- degree-4 XL on cubic equations: cubic rows multiplied by 1 and by every unknown, on the device (k_xl4_cubic_expand) ------------
+ * Input: m cubic rows over n_lin unknowns as gf2bv_cubic_expand_* writes them, cubic_stride_words apart: column c < n_lin the unknown
+ * l_c, pair (i, j), j < i, at n_lin + C(i,2) + j (q_ij), triple (i, j, l), l < j < i, at cols2 + C(i,3) + C(j,2) + l (t_ijl), the
+ * constant c at cols3.  W3 = ceil((cols3 + 1) / 64) words of a row are read; bits behind the constant column are ignored.
+ * Output: degree-4 XL's columns (cols4 of them, the constant at cols4, every bit behind it up to the stride zero).
+ * Rows: equation e owns the n_lin + 1 rows from e(n_lin + 1): f_e itself (its cols3 columns, no quadruple), then x_k f_e,
+ * k = 0 .. n_lin - 1, with x^2 = x.  Rows m(n_lin + 1) .. rows - 1 are written as zeros; the solve entries use
+ * rows = max(m(n_lin + 1), cols4).
+ * Products: a monomial M of x_k f is f[M] ^ f[M - {k}] where M contains k and 0 elsewhere -- the unknown k = c ^ l_k, the pair {k, i}
+ * = l_i ^ q_ki, the triple {k, a, b} = q_ab ^ t_kab, a quadruple containing k = t of its other three; the constant 0.
+ * Rank: the multipliers (degree 1) stay below the equations' degree, so there is no forced relation among the rows as at degree 4 on
+ * quadratic rows: about cols4 / (n_lin + 1) equations give full rank.
+ * gf2bv_xl4_cubic_expand_device: everything in device memory; the kernel is enqueued on `stream` and the call returns.  d_aug needs
+ * 16-byte alignment and an even stride_words covering cols4 + 1 bits.
+ * gf2bv_xl4_cubic_expand_words: host pointers in, rows x stride_words words back (upload, kernel, download).
+ * gf2bv_solve_xl4_cubic_words: expanded cubic rows in, multiplied and solved on the device.
+ * gf2bv_solve_xl4_cubic_terms: the factored form of gf2bv_solve_cubic_terms (m live rows, no padding) uploaded, expanded by
+ * k_cubic_expand, multiplied by k_xl4_cubic_expand and handed to gf2bv_solve_device, all on one pool stream: no row of either
+ * expansion exists on the host.
+ * GF2BV_ERR_ARG before any device is touched: null pointers, n_lin < 1 or cols4 >= 2^31 - 64, m(n_lin + 1) >= 2^31 - 64,
+ * rows < m(n_lin + 1), a cubic row beyond the kernel's LDS (W3 * 8 > 64 KiB: n_lin above 146), cubic_stride_words < W3, a stride
+ * that does not cover cols4 + 1 bits, a bad mode, and for the factored form what gf2bv_solve_cubic_terms refuses. */
+int gf2bv_xl4_cubic_expand_device(const void *d_cubic, int64_t m, int64_t cubic_stride_words, int64_t n_lin, int64_t rows, void *d_aug,
+                                  int64_t stride_words, int device, void *stream);
+int gf2bv_xl4_cubic_expand_words(const uint64_t *cubic, int64_t m, int64_t cubic_stride_words, int64_t n_lin, int64_t rows,
+                                 uint64_t *out_aug, int64_t stride_words, int device);
+int gf2bv_solve_xl4_cubic_words(const uint64_t *cubic, int64_t m, int64_t cubic_stride_words, int64_t n_lin, int mode, int device,
+                                gf2bv_result **out);
+int gf2bv_solve_xl4_cubic_terms(const uint64_t *lin, const int64_t *off2, const uint64_t *ta, const uint64_t *tb, const int64_t *off3,
+                                const uint64_t *ua, const uint64_t *ub, const uint64_t *uc, int64_t m, int64_t n_lin, int mode,
+                                int device, gf2bv_result **out);
+
 /* ---- synthetic systems + independent residual check (bench / tests) ----------------------- */
 /* word w of row r = mix64(mix64(seed) ^ ((r<<20)|w)); planted solution = pseudo-row 0xFFFFF;
  * RHS = <row, planted>.  Writes rows x stride_words words at d_aug. */
