@@ -4757,6 +4757,38 @@ k_quad_check(const u64 *__restrict__ E, i64 m, int R, const u64 *__restrict__ ca
 }
 
 
+// Index arithmetic of the expansion kernels below: bit q of a row, the binomials C(i,2..4) that place a pair, triple or quadruple with
+// largest member i, and their inverses (float first guess, made exact in integers)
+__device__ __forceinline__ u64 xl_bit(const u64 *s, i64 q) { return (s[q >> 6] >> (q & 63)) & 1; }
+__device__ __forceinline__ i64 xl_c2(i64 i) { return i * (i - 1) / 2; }
+__device__ __forceinline__ i64 xl_c3(i64 i) { return i * (i - 1) * (i - 2) / 6; }
+__host__ __device__ __forceinline__ i64 xl_c4(i64 i) { return i * (i - 1) * (i - 2) * (i - 3) / 24; }
+__device__ __forceinline__ i64 xl_tri_root(i64 p)                          // the largest i >= 1 with C(i,2) <= p
+{
+	i64 i = (i64)((1.0f + sqrtf(1.0f + 8.0f * (float)p)) * 0.5f);          // (float: exact to a few units below 2^31) ...
+	if (i < 1) i = 1;
+	while (xl_c2(i) > p) i--;                                              // ... made exact in integers
+	while (xl_c2(i + 1) <= p) i++;
+	return i;
+}
+__device__ __forceinline__ i64 xl_tet_root(i64 t)                          // the largest i >= 2 with C(i,3) <= t
+{
+	i64 i = (i64)cbrtf(6.0f * (float)t) + 1;
+	if (i < 2) i = 2;
+	while (xl_c3(i) > t) i--;
+	while (xl_c3(i + 1) <= t) i++;
+	return i;
+}
+__host__ __device__ __forceinline__ i64 xl_quart_root(i64 u)                   // the largest i >= 3 with C(i,4) <= u
+{
+	i64 i = (i64)sqrtf(sqrtf(24.0f * (float)u)) + 2;                           // (float: a few units off below 2^31) ...
+	if (i < 3) i = 3;
+	while (xl_c4(i) > u) i--;                                                  // ... made exact in integers
+	while (xl_c4(i + 1) <= u) i++;
+	return i;
+}
+
+
 // ==========================================================================================
 // QUADRATIC EXPANSION: factored quadratic equations -> the linearised rows the solver takes
 // ==========================================================================================
@@ -4794,11 +4826,8 @@ __device__ __forceinline__ u64 qx_word(const u64 *lin, const u64 *A, const u64 *
 	}
 	const i64 p_lo = (c0 > n ? c0 : n) - n, p_hi = (c0 + 64 < cols ? c0 + 64 : cols) - n;      // the word's pair indices
 	if (nt > 0 && p_lo < p_hi) {
-		i64 i = (i64)((1.0f + sqrtf(1.0f + 8.0f * (float)p_lo)) * 0.5f);      // the triangular root of p_lo: i(i-1)/2 <= p_lo < i(i+1)/2 ...
-		if (i < 1) i = 1;
-		while (i * (i - 1) / 2 > p_lo) i--;                                     // ... made exact in integers
-		while (i * (i + 1) / 2 <= p_lo) i++;
-		for (i64 s = i * (i - 1) / 2; s < p_hi; s += i, i++) {                  // run i: pairs s .. s + i - 1
+		i64 i = xl_tri_root(p_lo);                                             // the run p_lo lies in
+		for (i64 s = xl_c2(i); s < p_hi; s += i, i++) {                        // run i: pairs s .. s + i - 1
 			const i64 j0 = (p_lo > s ? p_lo : s) - s, j1 = (p_hi < s + i ? p_hi : s + i) - s;
 			u64 run = 0;
 			for (int t = 0; t < nt; t++) {
@@ -4875,54 +4904,47 @@ k_quad_expand_batch(const u64 *__restrict__ lin, const i64 *__restrict__ term_of
 
 
 // ==========================================================================================
-// DEGREE-3 XL: every quadratic row, and its product with every unknown, over the monomials of degree <= 3
+// XL BY ONE UNKNOWN: every row, and its product with every unknown, over the monomials one degree up
 // ==========================================================================================
-// (host side: gf2bv_xl3_expand_device in gf2_solver.hip)
+// (host side: gf2bv_xl3_expand_device and gf2bv_xl4_cubic_expand_device in gf2_solver.hip)
 //
-// Source: m rows as k_quad_expand writes them -- column c < n unknown c (l_c), column n + i(i-1)/2 + j pair (i, j), j < i (q_ij),
-// column cols2 = n + C(n,2) the constant c.  Output: cols3 = cols2 + C(n,3) columns, the first cols2 as in the source, triple
-// (i, j, l), l < j < i, at cols2 + C(i,3) + C(j,2) + l, the constant at cols3.  Equation e owns the rows e(n+1) .. e(n+1) + n:
-// first f_e itself, then x_k f_e for k = 0 .. n-1 with x^2 = x:
-//   unknown k = c ^ l_k, pair {k, i} = l_i ^ q_ki, triple T containing k = q of the other two; constant 0.
+// Columns, here and in every kernel below: c < n unknown c (l_c), pair (i, j), j < i, at n + C(i,2) + j (q_ij), triple (i, j, l),
+// l < j < i, at cols2 + C(i,3) + C(j,2) + l (t_ijl), quadruple (i, j, l, p), p < l < j < i, at cols3 + C(i,4) + C(j,3) + C(l,2) + p, with
+// cols2 = n + C(n,2), cols3 = cols2 + C(n,3), cols4 = cols3 + C(n,4); the constant c sits behind the last monomial column of a row.
+// Source: m rows of degree SRC -- SRC = 2 as k_quad_expand writes them (constant at cols2), SRC = 3 as k_cubic_expand writes them
+// (constant at cols3); Ws = ceil((cols_SRC + 1) / 64) words are read.  Output: the monomials of degree <= SRC + 1, the first cols_SRC
+// columns as in the source, the constant at cols_{SRC+1}.  Equation e owns the rows e(n+1) .. e(n+1) + n: first f_e itself (its own
+// columns, nothing of the new degree, the constant moved), then x_k f_e for k = 0 .. n-1 with x^2 = x.
+// The rule: monomial M of x_k f is f[M] ^ f[M - k] where M contains k and 0 elsewhere (f[M] = 0 for a monomial of degree SRC + 1):
+//   unknown k = c ^ l_k, pair {k, i} = l_i ^ q_ki, triple {k, a, b} = q_ab (SRC = 3: ^ t_kab), quadruple containing k (SRC = 3 only) =
+//   t of the other three; constant 0.
 // Runs of consecutive columns of x_k f:
-//   pairs (i, 0..i-1):       i = k: l[0..k) ^ q(k, 0..k-1);  i > k: the one bit l_i ^ q(i, k) at position k;  i < k: nothing.
-//   triples (i, j, 0..j-1):  k = i: q(j, 0..j-1);  k = j: q(i, 0..j-1);  k < j: the one bit q(i, j) at position k;  else nothing.
-// So pairs below C(k,2) and triples below C(k,3) are zero (the word leaves at once), and inside a block i > k the runs j < k are
-// skipped in one step.  Whole runs are 64-bit windows of the source row in LDS, as in k_quad_expand.
+//   pairs (i, 0..i-1):            i = k: l[0..k) ^ q(k, 0..k-1);  i > k: the one bit l_i ^ q(i, k) at position k;  i < k: nothing.
+//   triples (i, j, 0..j-1):       i = k: q(j, 0..j-1);  j = k: q(i, 0..k-1);  k < j: the one bit q(i, j) at position k;  else nothing.
+//                                 SRC = 3 adds the source's own triples to each: t(i, j, 0..j-1), or the bit t(i, j, k).
+//   quadruples (i, j, l, 0..l-1): (SRC = 3 only) k = i: t(j, l, 0..l-1);  k = j: t(i, l, 0..l-1);  k = l: t(i, j, 0..l-1);  k < l: the one
+//                                 bit t(i, j, l) at position k;  else nothing.
+// So pairs below C(k,2), triples below C(k,3) and quadruples below C(k,4) are zero (the word leaves at once), and inside a block i > k
+// the runs that cannot contain k are skipped in one step (the jumps only ever move forward in (i, j, l)).  Whole runs are 64-bit
+// windows of the source row in LDS, as in k_quad_expand, each masked to its run: no bit behind the source's constant column reaches
+// the output.
 // Work split: the rows are dealt to the workgroups in contiguous spans, so a workgroup reads a source row into LDS once for all the
 // products of it that fall into its span; every lane forms two consecutive output words per step and stores them as 16 bytes,
 // consecutive lanes consecutive 16 bytes: each output word has one writer, no atomics.  Rows >= m(n+1) are written as zeros.
-// LDS: W2 = ceil((cols2 + 1) / 64) words (dynamic).
-__device__ __forceinline__ u64 xl_bit(const u64 *s, i64 q) { return (s[q >> 6] >> (q & 63)) & 1; }
-__device__ __forceinline__ i64 xl_c2(i64 i) { return i * (i - 1) / 2; }
-__device__ __forceinline__ i64 xl_c3(i64 i) { return i * (i - 1) * (i - 2) / 6; }
-__device__ __forceinline__ i64 xl_tri_root(i64 p)                          // the largest i >= 1 with C(i,2) <= p
-{
-	i64 i = (i64)((1.0f + sqrtf(1.0f + 8.0f * (float)p)) * 0.5f);          // (float: exact to a few units below 2^31) ...
-	if (i < 1) i = 1;
-	while (xl_c2(i) > p) i--;                                              // ... made exact in integers
-	while (xl_c2(i + 1) <= p) i++;
-	return i;
-}
-__device__ __forceinline__ i64 xl_tet_root(i64 t)                          // the largest i >= 2 with C(i,3) <= t
-{
-	i64 i = (i64)cbrtf(6.0f * (float)t) + 1;
-	if (i < 2) i = 2;
-	while (xl_c3(i) > t) i--;
-	while (xl_c3(i + 1) <= t) i++;
-	return i;
-}
+// LDS: Ws words (dynamic).
 
-// columns c0 .. c0 + 63 of the row x_k f (k < 0: f itself) of the source row `src`
-__device__ __forceinline__ u64 xl3_word(const u64 *src, int W2, i64 n, i64 cols2, i64 cols3, i64 c0, int k)
+// columns c0 .. c0 + 63 of the row x_k f (k < 0: f itself) of the source row `src` of degree SRC (cols4 is read for SRC = 3 only)
+template <int SRC>
+__device__ __forceinline__ u64 xl_mul_word(const u64 *src, int Ws, i64 n, i64 cols2, i64 cols3, i64 cols4, i64 c0, int k)
 {
-	if (k < 0) {                                                           // f: its own columns, no triple, the constant behind them
-		u64 acc = c0 < cols2 ? qx_window(src, W2, c0) & qx_low(cols2 - c0) : 0;
-		if (cols3 >= c0 && cols3 < c0 + 64) acc |= xl_bit(src, cols2) << (cols3 - c0);
+	const i64 cs = SRC == 3 ? cols3 : cols2, co = SRC == 3 ? cols4 : cols3;    // the constant's column in the source and in the output
+	if (k < 0) {                                                           // f: its own columns, the constant behind all
+		u64 acc = c0 < cs ? qx_window(src, Ws, c0) & qx_low(cs - c0) : 0;
+		if (co >= c0 && co < c0 + 64) acc |= xl_bit(src, cs) << (co - c0);
 		return acc;
 	}
 	u64 acc = 0;
-	if (k >= c0 && k < c0 + 64) acc = (xl_bit(src, cols2) ^ xl_bit(src, k)) << (k - c0);
+	if (k >= c0 && k < c0 + 64) acc = (xl_bit(src, cs) ^ xl_bit(src, k)) << (k - c0);
 	const i64 p_lo = (c0 > n ? c0 : n) - n, p_hi = (c0 + 64 < cols2 ? c0 + 64 : cols2) - n;        // the word's pair indices
 	if (p_lo < p_hi && p_hi > xl_c2(k)) {
 		i64 i = xl_tri_root(p_lo);
@@ -4930,7 +4952,7 @@ __device__ __forceinline__ u64 xl3_word(const u64 *src, int W2, i64 n, i64 cols2
 		for (i64 s = xl_c2(i); s < p_hi; s += i, i++) {                    // run i: pairs s .. s + i - 1
 			const i64 j0 = (p_lo > s ? p_lo : s) - s, j1 = (p_hi < s + i ? p_hi : s + i) - s;
 			if (i == k) {
-				if (j0 < j1) acc |= ((qx_window(src, W2, j0) ^ qx_window(src, W2, n + s + j0)) & qx_low(j1 - j0)) << (n + s + j0 - c0);
+				if (j0 < j1) acc |= ((qx_window(src, Ws, j0) ^ qx_window(src, Ws, n + s + j0)) & qx_low(j1 - j0)) << (n + s + j0 - c0);
 			} else if (k >= j0 && k < j1)
 				acc |= (xl_bit(src, i) ^ xl_bit(src, n + s + k)) << (n + s + k - c0);
 		}
@@ -4944,23 +4966,58 @@ __device__ __forceinline__ u64 xl3_word(const u64 *src, int W2, i64 n, i64 cols2
 			if (i > k && j < k) { j = k; s = xl_c3(i) + xl_c2(j); continue; }      // (nothing in the runs below j = k)
 			const i64 j0 = (t_lo > s ? t_lo : s) - s, j1 = (t_hi < s + j ? t_hi : s + j) - s;
 			if (j0 < j1) {
-				if (i == k) acc |= (qx_window(src, W2, n + xl_c2(j) + j0) & qx_low(j1 - j0)) << (cols2 + s + j0 - c0);
-				else if (j == k) acc |= (qx_window(src, W2, n + xl_c2(i) + j0) & qx_low(j1 - j0)) << (cols2 + s + j0 - c0);
-				else if (k >= j0 && k < j1) acc |= xl_bit(src, n + xl_c2(i) + j) << (cols2 + s + k - c0);      // (k < j)
+				// (one form per source: a shared one compiled to a slower k_xl3_expand, profiles/expand_refactor_time.txt)
+				if constexpr (SRC == 3) {
+					if (i == k || j == k)                                  // q of the other member with 0..j-1, and the triples themselves
+						acc |= ((qx_window(src, Ws, n + xl_c2(i == k ? j : i) + j0) ^ qx_window(src, Ws, cols2 + s + j0)) & qx_low(j1 - j0))
+						       << (cols2 + s + j0 - c0);
+					else if (k >= j0 && k < j1)                            // (k < j)
+						acc |= (xl_bit(src, n + xl_c2(i) + j) ^ xl_bit(src, cols2 + s + k)) << (cols2 + s + k - c0);
+				} else {
+					if (i == k) acc |= (qx_window(src, Ws, n + xl_c2(j) + j0) & qx_low(j1 - j0)) << (cols2 + s + j0 - c0);
+					else if (j == k) acc |= (qx_window(src, Ws, n + xl_c2(i) + j0) & qx_low(j1 - j0)) << (cols2 + s + j0 - c0);
+					else if (k >= j0 && k < j1) acc |= xl_bit(src, n + xl_c2(i) + j) << (cols2 + s + k - c0);      // (k < j)
+				}
 			}
 			s += j;
 			if (++j == i) { i++; j = 1; }
 		}
 	}
+	if (SRC == 2) return acc;
+	const i64 u_lo = (c0 > cols3 ? c0 : cols3) - cols3, u_hi = (c0 + 64 < cols4 ? c0 + 64 : cols4) - cols3;      // its quadruple indices
+	if (u_lo < u_hi && u_hi > xl_c4(k)) {
+		i64 i = xl_quart_root(u_lo), j = xl_tet_root(u_lo - xl_c4(i));     // the run u_lo lies in: 1 <= l < j < i
+		i64 l = xl_tri_root(u_lo - xl_c4(i) - xl_c3(j));
+		i64 s = xl_c4(i) + xl_c3(j) + xl_c2(l);
+		while (s < u_hi) {                                                 // run (i, j, l): quadruples s .. s + l - 1
+			bool jump = true;                                              // to the next run that can hold anything
+			if (i < k) { i = k; j = 2; l = 1; }                            // (k >= 4 here: nothing below block k)
+			else if (i > k && j < k) { j = k; l = 1; }                     // i > k: k is j or l, or lies below l
+			else if (i > k && j > k && l < k) l = k;
+			else jump = false;
+			if (jump) { s = xl_c4(i) + xl_c3(j) + xl_c2(l); continue; }
+			const i64 j0 = (u_lo > s ? u_lo : s) - s, j1 = (u_hi < s + l ? u_hi : s + l) - s;
+			if (j0 < j1) {
+				if (i == k || j == k || l == k) {                          // t of the other two with 0..l-1
+					const i64 hi = i == k ? j : i, lo = l == k ? j : l;
+					acc |= (qx_window(src, Ws, cols2 + xl_c3(hi) + xl_c2(lo) + j0) & qx_low(j1 - j0)) << (cols3 + s + j0 - c0);
+				} else if (k >= j0 && k < j1)                              // (k < l)
+					acc |= xl_bit(src, cols2 + xl_c3(i) + xl_c2(j) + l) << (cols3 + s + k - c0);
+			}
+			s += l;
+			if (++l == j) { l = 1; if (++j == i) { i++; j = 2; } }
+		}
+	}
 	return acc;
 }
 
-// the rows of ONE system (quad its first source row, out its first output row), dealt to the workgroups of grid x
+// the rows of ONE system (rows_src its first source row, out its first output row), dealt to the workgroups of grid x
+template <int SRC>
 __device__ __forceinline__ void
-xl3_expand_rows(const u64 *__restrict__ quad, i64 m, i64 quad_stride, int n, int W2, i64 rows, u64 *__restrict__ out, i64 stride)
+xl_span_rows(const u64 *__restrict__ rows_src, i64 m, i64 src_stride, int n, int Ws, i64 rows, u64 *__restrict__ out, i64 stride)
 {
-	extern __shared__ u64 xl_lds[];                    // the source row: W2 words
-	const i64 cols2 = (i64)n + xl_c2(n), cols3 = cols2 + xl_c3(n);
+	extern __shared__ u64 xl_lds[];                    // the source row: Ws words
+	const i64 cols2 = (i64)n + xl_c2(n), cols3 = cols2 + xl_c3(n), cols4 = SRC == 3 ? cols3 + xl_c4(n) : 0;
 	const i64 npair = stride >> 1;                     // 16-byte pieces of a row (stride is even)
 	const i64 span = (rows + gridDim.x - 1) / gridDim.x;
 	const i64 r0 = (i64)blockIdx.x * span, r1 = r0 + span < rows ? r0 + span : rows;
@@ -4974,20 +5031,22 @@ xl3_expand_rows(const u64 *__restrict__ quad, i64 m, i64 quad_stride, int n, int
 		}
 		if (e != have) {
 			__syncthreads();                           // the rows before have read theirs
-			for (int w = threadIdx.x; w < W2; w += blockDim.x) xl_lds[w] = quad[e * quad_stride + w];
+			for (int w = threadIdx.x; w < Ws; w += blockDim.x) xl_lds[w] = rows_src[e * src_stride + w];
 			__syncthreads();
 			have = e;
 		}
 		const int k = (int)(r - e * (n + 1)) - 1;
 		for (i64 p = threadIdx.x; p < npair; p += blockDim.x)
-			o[p] = make_ulonglong2(xl3_word(xl_lds, W2, n, cols2, cols3, 128 * p, k), xl3_word(xl_lds, W2, n, cols2, cols3, 128 * p + 64, k));
+			o[p] = make_ulonglong2(xl_mul_word<SRC>(xl_lds, Ws, n, cols2, cols3, cols4, 128 * p, k),
+			                       xl_mul_word<SRC>(xl_lds, Ws, n, cols2, cols3, cols4, 128 * p + 64, k));
 	}
 }
 
+// Degree-3 XL: quadratic source rows (SRC = 2), W2 = ceil((cols2 + 1) / 64) words each
 __global__ void __launch_bounds__(256)
 k_xl3_expand(const u64 *__restrict__ quad, i64 m, i64 quad_stride, int n, int W2, i64 rows, u64 *__restrict__ out, i64 stride)
 {
-	xl3_expand_rows(quad, m, quad_stride, n, W2, rows, out, stride);
+	xl_span_rows<2>(quad, m, quad_stride, n, W2, rows, out, stride);
 }
 
 // The batched instance (gf2bv_xl3_expand_batch_device): blockIdx.y = system.  System s reads its m quadratic rows at
@@ -4997,7 +5056,7 @@ __global__ void __launch_bounds__(256)
 k_xl3_expand_batch(const u64 *__restrict__ quad, i64 quad_sys_stride, i64 m, i64 quad_stride, int n, int W2, i64 rows,
                    u64 *__restrict__ out, i64 stride, i64 sys_stride)
 {
-	xl3_expand_rows(quad + (i64)blockIdx.y * quad_sys_stride, m, quad_stride, n, W2, rows, out + (i64)blockIdx.y * sys_stride, stride);
+	xl_span_rows<2>(quad + (i64)blockIdx.y * quad_sys_stride, m, quad_stride, n, W2, rows, out + (i64)blockIdx.y * sys_stride, stride);
 }
 
 
@@ -5128,15 +5187,6 @@ k_quad_specialise(const u64 *__restrict__ quad, i64 m, i64 quad_stride, int n, i
 // `parts`-th of that equation's R4 rows: each workgroup sees an even sample of the multipliers.  The zero rows behind m R4 are dealt
 // round-robin.  Stores as in k_xl3_expand: two words a lane, 16 bytes, consecutive lanes consecutive; one writer per word, no atomics.
 // LDS: W2 words (dynamic).
-__host__ __device__ __forceinline__ i64 xl_c4(i64 i) { return i * (i - 1) * (i - 2) * (i - 3) / 24; }
-__host__ __device__ __forceinline__ i64 xl_quart_root(i64 u)                   // the largest i >= 3 with C(i,4) <= u
-{
-	i64 i = (i64)sqrtf(sqrtf(24.0f * (float)u)) + 2;                           // (float: a few units off below 2^31) ...
-	if (i < 3) i = 3;
-	while (xl_c4(i) > u) i--;                                                  // ... made exact in integers
-	while (xl_c4(i + 1) <= u) i++;
-	return i;
-}
 __device__ __forceinline__ i64 xl_q(i64 n, i64 u, i64 v) { return u > v ? n + xl_c2(u) + v : n + xl_c2(v) + u; }      // column of x_u x_v
 
 // columns c0 .. c0 + 63 of the row x_a x_b f, b < a, of the source row `src`
@@ -5207,7 +5257,7 @@ __device__ __forceinline__ u64 xl4_pair_word(const u64 *src, int W2, i64 n, i64 
 __device__ __forceinline__ u64 xl4_word(const u64 *src, int W2, i64 n, i64 cols2, i64 cols3, i64 cols4, i64 c0, int k, int a, int b)
 {
 	if (a >= 0) return xl4_pair_word(src, W2, n, cols2, cols3, cols4, c0, a, b);
-	if (k >= 0) return c0 < cols3 ? xl3_word(src, W2, n, cols2, cols3, c0, k) : 0;      // x_k f: degree 3's word, no quadruple, constant 0
+	if (k >= 0) return c0 < cols3 ? xl_mul_word<2>(src, W2, n, cols2, cols3, 0, c0, k) : 0;      // x_k f: degree 3's word, no quadruple, constant 0
 	u64 acc = c0 < cols2 ? qx_window(src, W2, c0) & qx_low(cols2 - c0) : 0;             // f: its own columns, the constant behind all
 	if (cols4 >= c0 && cols4 < c0 + 64) acc |= xl_bit(src, cols2) << (cols4 - c0);
 	return acc;
@@ -5393,120 +5443,10 @@ k_cubic_expand(const u64 *__restrict__ lin, const i64 *__restrict__ off2, const 
 // ==========================================================================================
 // (host side: gf2bv_xl4_cubic_expand_device in gf2_solver.hip; the front-end: PackedCubicSystem.solve_all_xl4)
 //
-// Source: m rows as k_cubic_expand writes them -- column c < n unknown c (l_c), pair (i, j), j < i, at n + C(i,2) + j (q_ij), triple
-// (i, j, l), l < j < i, at cols2 + C(i,3) + C(j,2) + l (t_ijl), the constant c at cols3; W3 = ceil((cols3 + 1) / 64) words are read.
-// Output: k_xl4_expand's columns -- the first cols3 as in the source, quadruple (i, j, l, p), p < l < j < i, at
-// cols3 + C(i,4) + C(j,3) + C(l,2) + p, the constant at cols4.  Equation e owns the rows e(n+1) .. e(n+1) + n: first f_e itself (its
-// own cols3 columns, no quadruple, the constant moved to cols4), then x_k f_e for k = 0 .. n-1 with x^2 = x.  A monomial M of x_k f is
-// f[M] ^ f[M - k] where M contains k and 0 elsewhere:
-//   unknown k = c ^ l_k, pair {k, i} = l_i ^ q_ki, triple {k, a, b} = q_ab ^ t_kab, quadruple containing k = t of the other three;
-//   constant 0.
-// Runs of consecutive columns of x_k f:
-//   pairs (i, 0..i-1):            i = k: l[0..k) ^ q(k, 0..k-1);  i > k: the one bit l_i ^ q(i, k) at position k;  i < k: nothing.
-//   triples (i, j, 0..j-1):       i = k: q(j, 0..j-1) ^ t(k, j, 0..j-1);  j = k: q(i, 0..k-1) ^ t(i, k, 0..k-1);  k < j: the one bit
-//                                 q(i, j) ^ t(i, j, k) at position k;  else nothing.
-//   quadruples (i, j, l, 0..l-1): k = i: t(j, l, 0..l-1);  k = j: t(i, l, 0..l-1);  k = l: t(i, j, 0..l-1);  k < l: the one bit
-//                                 t(i, j, l) at position k;  else nothing.
-// So pairs below C(k,2), triples below C(k,3) and quadruples below C(k,4) are zero (the word leaves at once), and inside a block i > k
-// the runs that cannot contain k are skipped in one step (the jumps only ever move forward in (i, j, l)).  Whole runs are 64-bit
-// windows of the source row in LDS, each masked to its run: no bit behind the source's constant column reaches the output.
-// Work split as in k_xl3_expand: contiguous spans of rows per workgroup, so a source row goes to LDS once for the products of it in
-// the span; every lane forms two consecutive output words per step and stores them as 16 bytes, consecutive lanes consecutive
-// 16 bytes: each output word has one writer, no atomics.  Rows >= m(n+1) are written as zeros.
-// LDS: W3 words (dynamic).
-
-// columns c0 .. c0 + 63 of the row x_k f (k < 0: f itself) of the cubic source row `src`
-__device__ __forceinline__ u64 xl4c_word(const u64 *src, int W3, i64 n, i64 cols2, i64 cols3, i64 cols4, i64 c0, int k)
-{
-	if (k < 0) {                                                           // f: its own columns, no quadruple, the constant behind all
-		u64 acc = c0 < cols3 ? qx_window(src, W3, c0) & qx_low(cols3 - c0) : 0;
-		if (cols4 >= c0 && cols4 < c0 + 64) acc |= xl_bit(src, cols3) << (cols4 - c0);
-		return acc;
-	}
-	u64 acc = 0;
-	if (k >= c0 && k < c0 + 64) acc = (xl_bit(src, cols3) ^ xl_bit(src, k)) << (k - c0);
-	const i64 p_lo = (c0 > n ? c0 : n) - n, p_hi = (c0 + 64 < cols2 ? c0 + 64 : cols2) - n;        // the word's pair indices
-	if (p_lo < p_hi && p_hi > xl_c2(k)) {
-		i64 i = xl_tri_root(p_lo);
-		if (i < k) i = k;
-		for (i64 s = xl_c2(i); s < p_hi; s += i, i++) {                    // run i: pairs s .. s + i - 1
-			const i64 j0 = (p_lo > s ? p_lo : s) - s, j1 = (p_hi < s + i ? p_hi : s + i) - s;
-			if (i == k) {
-				if (j0 < j1) acc |= ((qx_window(src, W3, j0) ^ qx_window(src, W3, n + s + j0)) & qx_low(j1 - j0)) << (n + s + j0 - c0);
-			} else if (k >= j0 && k < j1)
-				acc |= (xl_bit(src, i) ^ xl_bit(src, n + s + k)) << (n + s + k - c0);
-		}
-	}
-	const i64 t_lo = (c0 > cols2 ? c0 : cols2) - cols2, t_hi = (c0 + 64 < cols3 ? c0 + 64 : cols3) - cols2;      // its triple indices
-	if (t_lo < t_hi && t_hi > xl_c3(k)) {
-		i64 i = xl_tet_root(t_lo), j = xl_tri_root(t_lo - xl_c3(i));       // the run t_lo lies in: 1 <= j < i
-		i64 s = xl_c3(i) + xl_c2(j);
-		while (s < t_hi) {                                                 // run (i, j): triples s .. s + j - 1
-			if (i < k) { i = k; j = 1; s = xl_c3(i); continue; }           // (k >= 3 here: nothing below block k)
-			if (i > k && j < k) { j = k; s = xl_c3(i) + xl_c2(j); continue; }      // (nothing in the runs below j = k)
-			const i64 j0 = (t_lo > s ? t_lo : s) - s, j1 = (t_hi < s + j ? t_hi : s + j) - s;
-			if (j0 < j1) {
-				if (i == k || j == k)                                      // q of the other member with 0..j-1, and the triples themselves
-					acc |= ((qx_window(src, W3, n + xl_c2(i == k ? j : i) + j0) ^ qx_window(src, W3, cols2 + s + j0)) & qx_low(j1 - j0))
-					       << (cols2 + s + j0 - c0);
-				else if (k >= j0 && k < j1)                                // (k < j)
-					acc |= (xl_bit(src, n + xl_c2(i) + j) ^ xl_bit(src, cols2 + s + k)) << (cols2 + s + k - c0);
-			}
-			s += j;
-			if (++j == i) { i++; j = 1; }
-		}
-	}
-	const i64 u_lo = (c0 > cols3 ? c0 : cols3) - cols3, u_hi = (c0 + 64 < cols4 ? c0 + 64 : cols4) - cols3;      // its quadruple indices
-	if (u_lo < u_hi && u_hi > xl_c4(k)) {
-		i64 i = xl_quart_root(u_lo), j = xl_tet_root(u_lo - xl_c4(i));     // the run u_lo lies in: 1 <= l < j < i
-		i64 l = xl_tri_root(u_lo - xl_c4(i) - xl_c3(j));
-		i64 s = xl_c4(i) + xl_c3(j) + xl_c2(l);
-		while (s < u_hi) {                                                 // run (i, j, l): quadruples s .. s + l - 1
-			bool jump = true;                                              // to the next run that can hold anything
-			if (i < k) { i = k; j = 2; l = 1; }                            // (k >= 4 here: nothing below block k)
-			else if (i > k && j < k) { j = k; l = 1; }                     // i > k: k is j or l, or lies below l
-			else if (i > k && j > k && l < k) l = k;
-			else jump = false;
-			if (jump) { s = xl_c4(i) + xl_c3(j) + xl_c2(l); continue; }
-			const i64 j0 = (u_lo > s ? u_lo : s) - s, j1 = (u_hi < s + l ? u_hi : s + l) - s;
-			if (j0 < j1) {
-				if (i == k || j == k || l == k) {                          // t of the other two with 0..l-1
-					const i64 hi = i == k ? j : i, lo = l == k ? j : l;
-					acc |= (qx_window(src, W3, cols2 + xl_c3(hi) + xl_c2(lo) + j0) & qx_low(j1 - j0)) << (cols3 + s + j0 - c0);
-				} else if (k >= j0 && k < j1)                              // (k < l)
-					acc |= xl_bit(src, cols2 + xl_c3(i) + xl_c2(j) + l) << (cols3 + s + k - c0);
-			}
-			s += l;
-			if (++l == j) { l = 1; if (++j == i) { i++; j = 2; } }
-		}
-	}
-	return acc;
-}
-
+// XL by one unknown (above) with SRC = 3: m rows as k_cubic_expand writes them, W3 = ceil((cols3 + 1) / 64) words each, become
+// k_xl4_expand's columns, m(n+1) live rows.  Rule, runs, work split and LDS as stated there.
 __global__ void __launch_bounds__(256)
 k_xl4_cubic_expand(const u64 *__restrict__ cubic, i64 m, i64 cubic_stride, int n, int W3, i64 rows, u64 *__restrict__ out, i64 stride)
 {
-	extern __shared__ u64 xl_lds[];                    // the source row: W3 words
-	const i64 cols2 = (i64)n + xl_c2(n), cols3 = cols2 + xl_c3(n), cols4 = cols3 + xl_c4(n);
-	const i64 npair = stride >> 1;                     // 16-byte pieces of a row (stride is even)
-	const i64 span = (rows + gridDim.x - 1) / gridDim.x;
-	const i64 r0 = (i64)blockIdx.x * span, r1 = r0 + span < rows ? r0 + span : rows;
-	i64 have = -1;                                     // the equation whose row is in LDS
-	for (i64 r = r0; r < r1; r++) {
-		ulonglong2 *o = reinterpret_cast<ulonglong2 *>(out + r * stride);
-		const i64 e = r / (n + 1);
-		if (e >= m) {
-			for (i64 p = threadIdx.x; p < npair; p += blockDim.x) o[p] = make_ulonglong2(0, 0);
-			continue;
-		}
-		if (e != have) {
-			__syncthreads();                           // the rows before have read theirs
-			for (int w = threadIdx.x; w < W3; w += blockDim.x) xl_lds[w] = cubic[e * cubic_stride + w];
-			__syncthreads();
-			have = e;
-		}
-		const int k = (int)(r - e * (n + 1)) - 1;
-		for (i64 p = threadIdx.x; p < npair; p += blockDim.x)
-			o[p] = make_ulonglong2(xl4c_word(xl_lds, W3, n, cols2, cols3, cols4, 128 * p, k), xl4c_word(xl_lds, W3, n, cols2, cols3, cols4, 128 * p + 64, k));
-	}
+	xl_span_rows<3>(cubic, m, cubic_stride, n, W3, rows, out, stride);
 }

@@ -4674,73 +4674,96 @@ void gf2bv_quad_last_times(double *out8)
 }  // extern "C"
 
 // =================================================================================================
-// Quadratic expansion: equations kept factored (a linear form plus products of two linear forms) become the linearised rows of
-// the C-ABI layout on the device (k_quad_expand), where gf2bv_solve_device and the factor entries read them.
+// Expansion of factored equations: a linear form plus products of two (degree 3: and of three) forms become the linearised rows of
+// the C-ABI layout on the device (k_quad_expand, k_cubic_expand), where gf2bv_solve_device and the factor entries read them.
 namespace {
 
-struct QuadTerms {                     // the factored form, in host or in device memory
-	const u64 *lin = nullptr;          // rows_live x wl
-	const i64 *off = nullptr;          // rows_live + 1
-	const u64 *ta = nullptr, *tb = nullptr;
-	i64 rows_live = 0, rows = 0, n = 0;
+constexpr i64 kExpandLdsBytes = 65536;                 // what every expansion kernel below may take of a workgroup's LDS
+
+// the workgroup of every expansion kernel: a thread per two words of an output row
+unsigned expand_block(i64 stride) { return (unsigned)std::min<i64>(256, round_up(std::max<i64>(stride / 2, 1), 64)); }
+
+// The factored form, in host or in device memory.  degree 2: the products follow QuadraticSystem._mul_bit, over n + C(n,2) columns,
+// and off3, ua, ub, uc are unused; degree 3: products of two and of three affine forms, exact in GF(2)[x] / (x_i^2 + x_i), over the
+// n + C(n,2) + C(n,3) columns of degree-3 XL
+struct Terms {
+	int degree;
+	const u64 *lin;                    // rows_live x wl
+	const i64 *off2;                   // rows_live + 1
+	const u64 *ta, *tb;
+	const i64 *off3;                   // rows_live + 1
+	const u64 *ua, *ub, *uc;
+	i64 rows_live, rows, n;
+	Terms(const void *lin, const void *off2, const void *ta, const void *tb, i64 rows_live, i64 rows, i64 n_lin, const void *off3 = nullptr,
+	      const void *ua = nullptr, const void *ub = nullptr, const void *uc = nullptr, int degree = 2)
+		: degree(degree), lin((const u64 *)lin), off2((const i64 *)off2), ta((const u64 *)ta), tb((const u64 *)tb), off3((const i64 *)off3),
+		  ua((const u64 *)ua), ub((const u64 *)ub), uc((const u64 *)uc), rows_live(rows_live), rows(rows), n(n_lin) {}
 	i64 wl() const { return (n + 1 + 63) / 64; }
-	i64 cols() const { return n + n * (n - 1) / 2; }
+	i64 cols() const { return n + n * (n - 1) / 2 + (degree == 3 ? n * (n - 1) * (n - 2) / 6 : 0); }
 	i64 wt() const { return (cols() + 1 + 63) / 64; }
 };
 
-// The shape of a factored system; `host`: the offsets can be read (they start at 0 and never decrease; operands wherever they say
-// there are products)
-int check_quad_terms(const QuadTerms &q, bool host)
+// What k_quad_expand and its batched form are launched with: `tch` products of a row in LDS at a time
+struct QuadLaunch { int tch; unsigned block; size_t lds; };
+QuadLaunch quad_launch(const Terms &q, i64 stride)
 {
-	if (!q.lin && q.rows_live > 0) return fail(GF2BV_ERR_ARG, "null pointer");
-	if (!q.off) return fail(GF2BV_ERR_ARG, "null pointer");
-	if (q.n < 1 || q.n > 65535 || q.cols() >= (1ll << 31) - 64) return fail(GF2BV_ERR_ARG, "n_lin must be at least 1 and n_lin + n_lin(n_lin-1)/2 below 2^31 - 64");
-	if (q.rows < 0 || q.rows >= (1ll << 31) - 64 || q.rows_live < 0 || q.rows_live > q.rows)
+	const i64 wl = q.wl();
+	const int tch = (int)std::max<i64>(1, std::min<i64>(8, (kExpandLdsBytes / 8 / wl - 1) / 2));
+	return { tch, expand_block(stride), sizeof(u64) * (size_t)((1 + 2 * tch) * wl) };
+}
+
+// What k_cubic_expand is launched with: `tch2` quadratic and `tch3` cubic terms of a row in LDS at a time (the cubic operands served
+// first where a form is long)
+struct CubicLaunch { int tch2, tch3; unsigned block; size_t lds; };
+CubicLaunch cubic_launch(i64 n, i64 stride)
+{
+	const i64 wl = (n + 1 + 63) / 64, avail = kExpandLdsBytes / 8 / wl - 1;      // operands beside the linear part
+	const int tch3 = (int)std::max<i64>(1, std::min<i64>(8, avail / 5));
+	const int tch2 = (int)std::max<i64>(1, std::min<i64>(8, (avail - 3 * tch3) / 2));
+	return { tch2, tch3, expand_block(stride), sizeof(u64) * (size_t)((1 + 2 * tch2 + 3 * tch3) * wl) };
+}
+
+// The shape of a factored system; `host`: the offsets can be read (each array starts at 0 and never decreases; operands wherever
+// they say there are terms)
+int check_terms(const Terms &t, bool host)
+{
+	const bool cubic = t.degree == 3;
+	if (!t.lin && t.rows_live > 0) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (!t.off2 || (cubic && !t.off3)) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (t.n < 1 || t.n > 65535 || t.cols() >= (1ll << 31) - 64)
+		return fail(GF2BV_ERR_ARG, cubic ? "n_lin must be at least 1 and n_lin + C(n_lin,2) + C(n_lin,3) below 2^31 - 64"
+		                                 : "n_lin must be at least 1 and n_lin + n_lin(n_lin-1)/2 below 2^31 - 64");
+	if (t.rows < 0 || t.rows >= (1ll << 31) - 64 || t.rows_live < 0 || t.rows_live > t.rows)
 		return fail(GF2BV_ERR_ARG, "rows_live must be 0..rows");
+	if (cubic && (i64)cubic_launch(t.n, 2).lds > kExpandLdsBytes)
+		return fail(GF2BV_ERR_ARG, "the operands of this n_lin do not fit the expansion kernel's LDS (64 KiB)");
 	if (!host) {
-		if (!q.ta || !q.tb || !q.lin) return fail(GF2BV_ERR_ARG, "null pointer");
+		if (!t.lin || !t.ta || !t.tb || (cubic && (!t.ua || !t.ub || !t.uc))) return fail(GF2BV_ERR_ARG, "null pointer");
 		return GF2BV_OK;
 	}
-	if (q.off[0] != 0) return fail(GF2BV_ERR_ARG, "term offsets must start at 0");
-	for (i64 r = 0; r < q.rows_live; r++)
-		if (q.off[r + 1] < q.off[r]) return fail(GF2BV_ERR_ARG, "term offsets must not decrease");
-	if ((!q.ta || !q.tb) && q.off[q.rows_live] > 0) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (t.off2[0] != 0 || (cubic && t.off3[0] != 0)) return fail(GF2BV_ERR_ARG, "term offsets must start at 0");
+	for (i64 r = 0; r < t.rows_live; r++)
+		if (t.off2[r + 1] < t.off2[r] || (cubic && t.off3[r + 1] < t.off3[r])) return fail(GF2BV_ERR_ARG, "term offsets must not decrease");
+	if ((!t.ta || !t.tb) && t.off2[t.rows_live] > 0) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (cubic && (!t.ua || !t.ub || !t.uc) && t.off3[t.rows_live] > 0) return fail(GF2BV_ERR_ARG, "null pointer");
 	return GF2BV_OK;
 }
 
-QuadTerms quad_terms(const void *lin, const void *term_off, const void *ta, const void *tb, i64 rows_live, i64 rows, i64 n_lin)
-{
-	QuadTerms q;
-	q.lin = (const u64 *)lin; q.off = (const i64 *)term_off; q.ta = (const u64 *)ta; q.tb = (const u64 *)tb;
-	q.rows_live = rows_live; q.rows = rows; q.n = n_lin;
-	return q;
-}
-
-// What both expansion kernels are launched with: `tch` products of a row in LDS at a time (64 KiB at most), a thread per two words
-// of an output row
-struct QuadLaunch { int tch; unsigned block; size_t lds; };
-QuadLaunch quad_launch(const QuadTerms &q, i64 stride)
-{
-	const i64 wl = q.wl();
-	const int tch = (int)std::max<i64>(1, std::min<i64>(8, (65536 / 8 / wl - 1) / 2));
-	return { tch, (unsigned)std::min<i64>(256, round_up(std::max<i64>(stride / 2, 1), 64)), sizeof(u64) * (size_t)((1 + 2 * tch) * wl) };
-}
-
 // (device pointers, already checked) the kernel on `st`
-int enqueue_quad_expand(const QuadTerms &q, u64 *d_aug, i64 stride, hipStream_t st)
+int enqueue_quad_expand(const Terms &q, u64 *d_aug, i64 stride, hipStream_t st)
 {
 	if (q.rows == 0) return GF2BV_OK;
 	const QuadLaunch l = quad_launch(q, stride);
 	const unsigned grid = (unsigned)std::min<i64>(q.rows, 256 * 8);
-	hipLaunchKernelGGL(k_quad_expand, dim3(grid), dim3(l.block), l.lds, st, q.lin, q.off, q.ta, q.tb, q.rows_live, q.rows, (int)q.n,
+	hipLaunchKernelGGL(k_quad_expand, dim3(grid), dim3(l.block), l.lds, st, q.lin, q.off2, q.ta, q.tb, q.rows_live, q.rows, (int)q.n,
 	                   (int)q.wl(), l.tch, d_aug, stride);
 	HIPCHK(hipGetLastError());
 	return GF2BV_OK;
 }
 
 // The batched form: nsys (not negative) systems over one concatenated term set, system s owning the rows sys_off[s] .. sys_off[s + 1],
-// at most q.rows of them; q.rows_live becomes sys_off[nsys], the rows of the whole set
-int check_quad_batch(QuadTerms &q, const i64 *sys_off, i64 nsys)
+// at most q.rows of them; q.rows_live becomes sys_off[nsys], the rows of the whole set.  Quadratic terms only: there is no batched cubic kernel
+int check_quad_batch(Terms &q, const i64 *sys_off, i64 nsys)
 {
 	if (!sys_off) return fail(GF2BV_ERR_ARG, "null pointer");
 	if (q.rows < 0 || q.rows >= (1ll << 31) - 64) return fail(GF2BV_ERR_ARG, "rows must be 0 .. 2^31 - 65");
@@ -4751,14 +4774,14 @@ int check_quad_batch(QuadTerms &q, const i64 *sys_off, i64 nsys)
 	}
 	if (sys_off[nsys] >= (1ll << 31) - 64) return fail(GF2BV_ERR_ARG, "the rows of all systems together must stay below 2^31 - 64");
 	const i64 rows = q.rows;
-	q.rows_live = q.rows = sys_off[nsys];          // (check_quad_terms: the concatenated set as one system of all its rows)
-	const int rc = check_quad_terms(q, true);
+	q.rows_live = q.rows = sys_off[nsys];          // (check_terms: the concatenated set as one system of all its rows)
+	const int rc = check_terms(q, true);
 	q.rows = rows;
 	return rc;
 }
 
 // (device pointers, already checked) the batched kernel on `st`: system s at d_aug + s x sys_stride, q.rows x stride words
-int enqueue_quad_expand_batch(const QuadTerms &q, const i64 *d_sys_off, i64 nsys, u64 *d_aug, i64 stride, i64 sys_stride, hipStream_t st)
+int enqueue_quad_expand_batch(const Terms &q, const i64 *d_sys_off, i64 nsys, u64 *d_aug, i64 stride, i64 sys_stride, hipStream_t st)
 {
 	if (q.rows == 0 || nsys == 0) return GF2BV_OK;
 	const QuadLaunch l = quad_launch(q, stride);
@@ -4766,75 +4789,15 @@ int enqueue_quad_expand_batch(const QuadTerms &q, const i64 *d_sys_off, i64 nsys
 	const unsigned gx = (unsigned)std::min<i64>(q.rows, std::max<i64>(256, 256 * 8 / nsys));
 	for (i64 s0 = 0; s0 < nsys; s0 += 65535) {      // (grid y holds 65535 systems)
 		const unsigned ns = (unsigned)std::min<i64>(65535, nsys - s0);
-		hipLaunchKernelGGL(k_quad_expand_batch, dim3(gx, ns), dim3(l.block), l.lds, st, q.lin, q.off, q.ta, q.tb, d_sys_off + s0, q.rows,
+		hipLaunchKernelGGL(k_quad_expand_batch, dim3(gx, ns), dim3(l.block), l.lds, st, q.lin, q.off2, q.ta, q.tb, d_sys_off + s0, q.rows,
 		                   (int)q.n, (int)q.wl(), l.tch, d_aug + s0 * sys_stride, stride, sys_stride);
 	}
 	HIPCHK(hipGetLastError());
 	return GF2BV_OK;
 }
 
-// Cubic expansion (k_cubic_expand): a linear form plus products of two and of three affine forms, the products exact in
-// GF(2)[x] / (x_i^2 + x_i), become rows over the n + C(n,2) + C(n,3) columns of degree-3 XL
-struct CubicTerms {                    // the factored form, in host or in device memory
-	const u64 *lin = nullptr;          // rows_live x wl
-	const i64 *off2 = nullptr;         // rows_live + 1
-	const u64 *ta = nullptr, *tb = nullptr;
-	const i64 *off3 = nullptr;         // rows_live + 1
-	const u64 *ua = nullptr, *ub = nullptr, *uc = nullptr;
-	i64 rows_live = 0, rows = 0, n = 0;
-	i64 wl() const { return (n + 1 + 63) / 64; }
-	i64 cols() const { return n + n * (n - 1) / 2 + n * (n - 1) * (n - 2) / 6; }
-	i64 wt() const { return (cols() + 1 + 63) / 64; }
-};
-
-// What the kernel is launched with: `tch2` quadratic and `tch3` cubic terms of a row in LDS at a time (64 KiB in all, the cubic
-// operands served first where a form is long), a thread per two words of an output row
-struct CubicLaunch { int tch2, tch3; unsigned block; size_t lds; };
-constexpr i64 kCubicLdsBytes = 65536;
-CubicLaunch cubic_launch(i64 n, i64 stride)
-{
-	const i64 wl = (n + 1 + 63) / 64, avail = kCubicLdsBytes / 8 / wl - 1;      // operands beside the linear part
-	const int tch3 = (int)std::max<i64>(1, std::min<i64>(8, avail / 5));
-	const int tch2 = (int)std::max<i64>(1, std::min<i64>(8, (avail - 3 * tch3) / 2));
-	return { tch2, tch3, (unsigned)std::min<i64>(256, round_up(std::max<i64>(stride / 2, 1), 64)), sizeof(u64) * (size_t)((1 + 2 * tch2 + 3 * tch3) * wl) };
-}
-
-// The shape of a factored cubic system; `host`: the offsets can be read (each array starts at 0 and never decreases; operands
-// wherever they say there are terms)
-int check_cubic_terms(const CubicTerms &c, bool host)
-{
-	if (!c.lin && c.rows_live > 0) return fail(GF2BV_ERR_ARG, "null pointer");
-	if (!c.off2 || !c.off3) return fail(GF2BV_ERR_ARG, "null pointer");
-	if (c.n < 1 || c.n > 65535 || c.cols() >= (1ll << 31) - 64)
-		return fail(GF2BV_ERR_ARG, "n_lin must be at least 1 and n_lin + C(n_lin,2) + C(n_lin,3) below 2^31 - 64");
-	if (c.rows < 0 || c.rows >= (1ll << 31) - 64 || c.rows_live < 0 || c.rows_live > c.rows)
-		return fail(GF2BV_ERR_ARG, "rows_live must be 0..rows");
-	if ((i64)cubic_launch(c.n, 2).lds > kCubicLdsBytes)
-		return fail(GF2BV_ERR_ARG, "the operands of this n_lin do not fit the expansion kernel's LDS (64 KiB)");
-	if (!host) {
-		if (!c.lin || !c.ta || !c.tb || !c.ua || !c.ub || !c.uc) return fail(GF2BV_ERR_ARG, "null pointer");
-		return GF2BV_OK;
-	}
-	if (c.off2[0] != 0 || c.off3[0] != 0) return fail(GF2BV_ERR_ARG, "term offsets must start at 0");
-	for (i64 r = 0; r < c.rows_live; r++)
-		if (c.off2[r + 1] < c.off2[r] || c.off3[r + 1] < c.off3[r]) return fail(GF2BV_ERR_ARG, "term offsets must not decrease");
-	if ((!c.ta || !c.tb) && c.off2[c.rows_live] > 0) return fail(GF2BV_ERR_ARG, "null pointer");
-	if ((!c.ua || !c.ub || !c.uc) && c.off3[c.rows_live] > 0) return fail(GF2BV_ERR_ARG, "null pointer");
-	return GF2BV_OK;
-}
-
-CubicTerms cubic_terms(const void *lin, const void *off2, const void *ta, const void *tb, const void *off3, const void *ua, const void *ub,
-                       const void *uc, i64 rows_live, i64 rows, i64 n_lin)
-{
-	CubicTerms c;
-	c.lin = (const u64 *)lin; c.off2 = (const i64 *)off2; c.ta = (const u64 *)ta; c.tb = (const u64 *)tb;
-	c.off3 = (const i64 *)off3; c.ua = (const u64 *)ua; c.ub = (const u64 *)ub; c.uc = (const u64 *)uc;
-	c.rows_live = rows_live; c.rows = rows; c.n = n_lin;
-	return c;
-}
-
 // (device pointers, already checked) the kernel on `st`
-int enqueue_cubic_expand(const CubicTerms &c, u64 *d_aug, i64 stride, hipStream_t st)
+int enqueue_cubic_expand(const Terms &c, u64 *d_aug, i64 stride, hipStream_t st)
 {
 	if (c.rows == 0) return GF2BV_OK;
 	const CubicLaunch l = cubic_launch(c.n, stride);
@@ -4845,14 +4808,21 @@ int enqueue_cubic_expand(const CubicTerms &c, u64 *d_aug, i64 stride, hipStream_
 	return GF2BV_OK;
 }
 
+// (device pointers, already checked) the kernel of the terms' degree on `st`
+int enqueue_expand(const Terms &t, u64 *d_aug, i64 stride, hipStream_t st)
+{
+	return t.degree == 3 ? enqueue_cubic_expand(t, d_aug, stride, st) : enqueue_quad_expand(t, d_aug, stride, st);
+}
+
 // XL (k_xl3_expand, k_xl4_expand): m quadratic rows over n unknowns -- the rows k_quad_expand writes -- become `rows` rows over the
 // monomials of degree <= `degree`: each equation, its product with every unknown and (degree 4) with every pair of unknowns, then zeros.
 // src = 3 (k_xl4_cubic_expand, degree 4 only): the m rows are cubic -- the rows k_cubic_expand writes -- and the multipliers stop at
 // the unknowns
 struct XlShape {
-	i64 m = 0, n = 0, rows = 0;
-	int degree = 3;
-	int src = 2;                       // the degree of the source rows
+	int degree;
+	int src;                           // the degree of the source rows
+	i64 m, n, rows;
+	XlShape(int degree, int src, i64 m, i64 n, i64 rows = 0) : degree(degree), src(src), m(m), n(n), rows(rows) {}
 	i64 cols2() const { return n + n * (n - 1) / 2; }
 	i64 cols3() const { return cols2() + n * (n - 1) * (n - 2) / 6; }
 	i64 cols4() const { return cols3() + n * (n - 1) * (n - 2) * (n - 3) / 24; }
@@ -4863,7 +4833,6 @@ struct XlShape {
 	i64 wt() const { return (cols() + 1 + 63) / 64; }
 	i64 live() const { return m * per_eq(); }
 };
-constexpr i64 kXl3LdsBytes = 65536;
 
 // The shape, and the source stride against it; no pointer is looked at.  `pad`: a solve entry, whose rows are the live ones padded up
 // to the columns
@@ -4880,7 +4849,7 @@ int check_xl(XlShape &x, i64 quad_stride, bool pad = false)
 	if (x.rows >= (1ll << 31) - 64 || x.rows < x.live())
 		return fail(GF2BV_ERR_ARG, d4 ? "rows must be at least m(1 + n_lin + C(n_lin,2)) and below 2^31 - 64"
 		                              : "rows must be at least m(n_lin + 1) and below 2^31 - 64");
-	if (x.wsrc() * 8 > kXl3LdsBytes)
+	if (x.wsrc() * 8 > kExpandLdsBytes)
 		return fail(GF2BV_ERR_ARG, cubic ? "a cubic row of this n_lin does not fit the expansion kernel's LDS (64 KiB)"
 		                                 : "a quadratic row of this n_lin does not fit the expansion kernel's LDS (64 KiB)");
 	if (quad_stride < x.wsrc())
@@ -4901,7 +4870,7 @@ int xl4_parts(const XlShape &x, i64 nsys)
 int enqueue_xl_expand(const XlShape &x, const u64 *d_quad, i64 quad_stride, u64 *d_aug, i64 stride, hipStream_t st)
 {
 	if (x.rows == 0) return GF2BV_OK;
-	const unsigned block = (unsigned)std::min<i64>(256, round_up(std::max<i64>(stride / 2, 1), 64));
+	const unsigned block = expand_block(stride);
 	if (x.src == 3) {
 		const unsigned grid = (unsigned)std::min<i64>(x.rows, 256 * 16);
 		hipLaunchKernelGGL(k_xl4_cubic_expand, dim3(grid), dim3(block), sizeof(u64) * (size_t)x.wsrc(), st, d_quad, x.m, quad_stride, (int)x.n,
@@ -4926,7 +4895,7 @@ int enqueue_xl_expand_batch(const XlShape &x, const u64 *d_quad, i64 quad_sys_st
                             i64 sys_stride, hipStream_t st)
 {
 	if (x.rows == 0 || nsys == 0) return GF2BV_OK;
-	const unsigned block = (unsigned)std::min<i64>(256, round_up(std::max<i64>(stride / 2, 1), 64));
+	const unsigned block = expand_block(stride);
 	// degree 3: contiguous spans of rows per workgroup, a few thousand workgroups in all where the systems are many
 	const int parts = xl4_parts(x, nsys);
 	const unsigned gx = x.degree == 4 ? (unsigned)std::min<i64>(std::max<i64>(x.m * parts, std::min<i64>(x.rows - x.live(), 256)), 1 << 20)
@@ -4947,9 +4916,10 @@ int enqueue_xl_expand_batch(const XlShape &x, const u64 *d_quad, i64 quad_sys_st
 // Hybrid XL (k_quad_specialise): f guessed unknowns substituted into m quadratic rows over n unknowns, for the assignments
 // a0 .. a0 + na - 1; every assignment leaves the system `x` of m rows over n - f unknowns
 struct GuessShape {
-	i64 m = 0, n = 0, f = 0, a0 = 0, na = 0;
+	i64 m, n, f, a0, na;
 	SpecGuess g{};
-	XlShape x;
+	XlShape x;                         // (check_guess fills m and n; the degree matters to the solve entries only)
+	GuessShape(i64 m, i64 n_lin, i64 nguess, i64 a0, i64 na, int degree = 3) : m(m), n(n_lin), f(nguess), a0(a0), na(na), x(degree, 2, 0, 0) {}
 	i64 w2() const { return (n + n * (n - 1) / 2 + 1 + 63) / 64; }
 	i64 lds_bytes() const { return 8 * (w2() + x.w2() + f * ((x.n + 63) / 64 + 2)) + 4 * x.n; }
 };
@@ -4973,7 +4943,7 @@ int check_guess(GuessShape &s, const int32_t *guess, i64 quad_stride)
 		return fail(GF2BV_ERR_ARG, "m and na x m must stay below 2^31 - 64");
 	s.x.m = s.m; s.x.n = s.n - s.f;
 	if (quad_stride < s.w2()) return fail(GF2BV_ERR_ARG, "quad_stride_words does not cover the quadratic columns and the constant");
-	if (s.lds_bytes() > kXl3LdsBytes)
+	if (s.lds_bytes() > kExpandLdsBytes)
 		return fail(GF2BV_ERR_ARG, "the quadratic row, its specialised form and the guess vectors do not fit the specialisation kernel's LDS (64 KiB)");
 	return GF2BV_OK;
 }
@@ -5052,46 +5022,31 @@ struct QuadStage {
 		if (bytes) HIPCHK(hipMemcpyAsync(*d, h, bytes, hipMemcpyHostToDevice, ps.st));
 		return GF2BV_OK;
 	}
-	// Upload and expansion, with rows `stride` words apart rounded up to an even `ds`; sys_off: the batched form, nsys systems (q as
-	// check_quad_batch left it); rhs: right-hand sides that go up into d_rhs in front of the expansion
-	int expand(QuadTerms q, i64 stride, const i64 *sys_off = nullptr, i64 nsys = 1, const u64 *rhs = nullptr, size_t rhs_bytes = 0)
+	// Upload of the term groups and expansion (t.degree's kernel), with rows `stride` words apart rounded up to an even `ds`; sys_off:
+	// the batched form, nsys systems (t as check_quad_batch left it); rhs: right-hand sides that go up into d_rhs in front of the expansion
+	int expand(Terms t, i64 stride, const i64 *sys_off = nullptr, i64 nsys = 1, const u64 *rhs = nullptr, size_t rhs_bytes = 0)
 	{
+		if (sys_off && t.degree != 2) return fail(GF2BV_ERR_ARG, "the batched expansion takes quadratic terms");
 		if (int rc = open()) return rc;
-		const i64 wl = q.wl(), T = q.off[q.rows_live];
-		u64 *lin = nullptr, *ta = nullptr, *tb = nullptr;
-		i64 *off = nullptr, *d_sys = nullptr;
-		int rc = upload(&lin, q.lin, sizeof(u64) * (size_t)(q.rows_live * wl));
-		if (!rc) rc = upload(&off, q.off, sizeof(i64) * (size_t)(q.rows_live + 1));
-		if (!rc) rc = upload(&ta, q.ta, sizeof(u64) * (size_t)(T * wl));
-		if (!rc) rc = upload(&tb, q.tb, sizeof(u64) * (size_t)(T * wl));
+		const i64 wl = t.wl();
+		i64 *d_sys = nullptr;
+		int rc = upload((u64 **)&t.lin, t.lin, sizeof(u64) * (size_t)(t.rows_live * wl));
+		// a group's offsets, then its operands: each host pointer of `t` becomes the device copy
+		auto group = [&](const i64 *&off, std::initializer_list<const u64 **> ops) {
+			const size_t bytes = sizeof(u64) * (size_t)(off[t.rows_live] * wl);
+			if (!rc) rc = upload((i64 **)&off, off, sizeof(i64) * (size_t)(t.rows_live + 1));
+			for (const u64 **op : ops)
+				if (!rc) rc = upload((u64 **)op, *op, bytes);
+		};
+		group(t.off2, { &t.ta, &t.tb });
+		if (t.degree == 3) group(t.off3, { &t.ua, &t.ub, &t.uc });
 		if (!rc && sys_off) rc = upload(&d_sys, sys_off, sizeof(i64) * (size_t)(nsys + 1));
 		ds = round_up(stride, 2);
-		if (!rc) rc = alloc((void **)&d_aug, sizeof(u64) * (size_t)(nsys * q.rows * ds));
+		if (!rc) rc = alloc((void **)&d_aug, sizeof(u64) * (size_t)(nsys * t.rows * ds));
 		if (!rc && rhs) rc = upload(&d_rhs, rhs, rhs_bytes);
 		if (rc) return rc;
-		q.lin = lin; q.off = off; q.ta = ta; q.tb = tb;
-		return sys_off ? enqueue_quad_expand_batch(q, d_sys, nsys, d_aug, ds, q.rows * ds, ps.st) : enqueue_quad_expand(q, d_aug, ds, ps.st);
-	}
-	// The cubic form: upload and expansion (k_cubic_expand) into d_aug, rows `stride` words apart rounded up to an even `ds`
-	int expand(CubicTerms c, i64 stride)
-	{
-		if (int rc = open()) return rc;
-		const i64 wl = c.wl(), T2 = c.off2[c.rows_live], T3 = c.off3[c.rows_live];
-		u64 *lin = nullptr, *ta = nullptr, *tb = nullptr, *ua = nullptr, *ub = nullptr, *uc = nullptr;
-		i64 *off2 = nullptr, *off3 = nullptr;
-		int rc = upload(&lin, c.lin, sizeof(u64) * (size_t)(c.rows_live * wl));
-		if (!rc) rc = upload(&off2, c.off2, sizeof(i64) * (size_t)(c.rows_live + 1));
-		if (!rc) rc = upload(&ta, c.ta, sizeof(u64) * (size_t)(T2 * wl));
-		if (!rc) rc = upload(&tb, c.tb, sizeof(u64) * (size_t)(T2 * wl));
-		if (!rc) rc = upload(&off3, c.off3, sizeof(i64) * (size_t)(c.rows_live + 1));
-		if (!rc) rc = upload(&ua, c.ua, sizeof(u64) * (size_t)(T3 * wl));
-		if (!rc) rc = upload(&ub, c.ub, sizeof(u64) * (size_t)(T3 * wl));
-		if (!rc) rc = upload(&uc, c.uc, sizeof(u64) * (size_t)(T3 * wl));
-		ds = round_up(stride, 2);
-		if (!rc) rc = alloc((void **)&d_aug, sizeof(u64) * (size_t)(c.rows * ds));
-		if (rc) return rc;
-		c.lin = lin; c.off2 = off2; c.ta = ta; c.tb = tb; c.off3 = off3; c.ua = ua; c.ub = ub; c.uc = uc;
-		return enqueue_cubic_expand(c, d_aug, ds, ps.st);
+		if (sys_off) return enqueue_quad_expand_batch(t, d_sys, nsys, d_aug, ds, t.rows * ds, ps.st);
+		return enqueue_expand(t, d_aug, ds, ps.st);
 	}
 	// Quadratic rows that are expanded already (host memory, `stride` words apart) into d_aug as they are
 	int upload_rows(const u64 *quad, i64 m, i64 stride)
@@ -5161,110 +5116,86 @@ int solve_guess_staged(QuadStage &stage, const GuessShape &g, int mode, int devi
 
 extern "C" {
 
-int gf2bv_quad_expand_device(const void *d_lin, const void *d_term_off, const void *d_ta, const void *d_tb, int64_t rows_live,
-                             int64_t rows, int64_t n_lin, void *d_aug, int64_t stride_words, int device, void *stream)
+// ---- the three entries on one factored system, quadratic or cubic (the terms say which kernel): each body once, the exported names
+// behind them.  The entries on host memory null their outputs, check, stage (QuadStage) and call the device entry underneath on the
+// stage's stream (the host waits only where that entry waits), or copy the expansion back
+static int terms_expand_device(const Terms &t, void *d_aug, int64_t stride_words, int device, void *stream)
 {
 	return catching([&]() -> int {
-	const QuadTerms q = quad_terms(d_lin, d_term_off, d_ta, d_tb, rows_live, rows, n_lin);
-	int rc = check_quad_terms(q, false);
+	int rc = check_terms(t, false);
 	if (rc) return rc;
 	if (!d_aug) return fail(GF2BV_ERR_ARG, "null pointer");
-	if (stride_words % 2 != 0 || stride_words < q.wt() || ((uintptr_t)d_aug & 15))
+	if (stride_words % 2 != 0 || stride_words < t.wt() || ((uintptr_t)d_aug & 15))
 		return fail(GF2BV_ERR_ARG, "device matrix needs 16-byte alignment and an even stride_words covering cols+1 bits");
 	rc = check_device(device);
 	if (rc) return rc;
-	return enqueue_quad_expand(q, (u64 *)d_aug, stride_words, (hipStream_t)stream);
+	return enqueue_expand(t, (u64 *)d_aug, stride_words, (hipStream_t)stream);
 	});
 }
 
-// ---- the entries on a factored system of host memory: each nulls its outputs, checks, stages (QuadStage) and calls the device entry
-// underneath on the stage's stream (the host waits only where that entry waits), or copies the expansion back
-int gf2bv_quad_expand_words(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t rows_live,
-                            int64_t rows, int64_t n_lin, uint64_t *out_aug, int64_t stride_words, int device)
+// (nomem: what a refused pool buffer is reported as, see QuadStage)
+static int terms_expand_words(const Terms &t, uint64_t *out_aug, int64_t stride_words, int device, bool nomem)
 {
 	return catching([&]() -> int {
-	const QuadTerms q = quad_terms(lin, term_off, ta, tb, rows_live, rows, n_lin);
-	int rc = check_quad_terms(q, true);
+	int rc = check_terms(t, true);
 	if (rc) return rc;
-	if (!out_aug && rows > 0) return fail(GF2BV_ERR_ARG, "null pointer");
-	if (stride_words < q.wt()) return fail(GF2BV_ERR_ARG, "stride_words does not cover cols+1 bits");
+	if (!out_aug && t.rows > 0) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (stride_words < t.wt()) return fail(GF2BV_ERR_ARG, "stride_words does not cover cols+1 bits");
 	if ((rc = check_device(device))) return rc;
-	if (rows == 0) return GF2BV_OK;
-	QuadStage stage(device, false);
-	if ((rc = stage.expand(q, stride_words))) return rc;
-	return stage.download(out_aug, stride_words, rows);
+	if (t.rows == 0) return GF2BV_OK;
+	QuadStage stage(device, nomem);
+	if ((rc = stage.expand(t, stride_words))) return rc;
+	return stage.download(out_aug, stride_words, t.rows);
 	});
 }
 
-int gf2bv_solve_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t rows_live,
-                           int64_t rows, int64_t n_lin, int mode, int device, gf2bv_result **out)
+static int solve_terms(const Terms &t, int mode, int device, gf2bv_result **out, bool nomem)
 {
 	return catching([&]() -> int {
 	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
 	*out = nullptr;
-	const QuadTerms q = quad_terms(lin, term_off, ta, tb, rows_live, rows, n_lin);
-	int rc = check_quad_terms(q, true);
-	if (!rc) rc = check_shape(rows, q.cols(), mode);
+	int rc = check_terms(t, true);
+	if (!rc) rc = check_shape(t.rows, t.cols(), mode);
 	if (!rc) rc = check_device(device);
 	if (rc) return rc;
-	QuadStage stage(device, false);
-	if ((rc = stage.expand(q, q.wt()))) return rc;
-	return gf2bv_solve_device(stage.d_aug, rows, q.cols(), stage.ds, mode, device, stage.ps.st, 0, out);
+	QuadStage stage(device, nomem);
+	if ((rc = stage.expand(t, t.wt()))) return rc;
+	return gf2bv_solve_device(stage.d_aug, t.rows, t.cols(), stage.ds, mode, device, stage.ps.st, 0, out);
 	});
 }
 
-// ---- the cubic form: the same three entries over n_lin + C(n_lin,2) + C(n_lin,3) columns (k_cubic_expand)
+int gf2bv_quad_expand_device(const void *d_lin, const void *d_term_off, const void *d_ta, const void *d_tb, int64_t rows_live,
+                             int64_t rows, int64_t n_lin, void *d_aug, int64_t stride_words, int device, void *stream)
+{
+	return terms_expand_device(Terms(d_lin, d_term_off, d_ta, d_tb, rows_live, rows, n_lin), d_aug, stride_words, device, stream);
+}
+int gf2bv_quad_expand_words(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t rows_live,
+                            int64_t rows, int64_t n_lin, uint64_t *out_aug, int64_t stride_words, int device)
+{
+	return terms_expand_words(Terms(lin, term_off, ta, tb, rows_live, rows, n_lin), out_aug, stride_words, device, false);
+}
+int gf2bv_solve_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t rows_live,
+                           int64_t rows, int64_t n_lin, int mode, int device, gf2bv_result **out)
+{
+	return solve_terms(Terms(lin, term_off, ta, tb, rows_live, rows, n_lin), mode, device, out, false);
+}
 int gf2bv_cubic_expand_device(const void *d_lin, const void *d_off2, const void *d_ta, const void *d_tb, const void *d_off3, const void *d_ua,
                               const void *d_ub, const void *d_uc, int64_t rows_live, int64_t rows, int64_t n_lin, void *d_aug,
                               int64_t stride_words, int device, void *stream)
 {
-	return catching([&]() -> int {
-	const CubicTerms c = cubic_terms(d_lin, d_off2, d_ta, d_tb, d_off3, d_ua, d_ub, d_uc, rows_live, rows, n_lin);
-	int rc = check_cubic_terms(c, false);
-	if (rc) return rc;
-	if (!d_aug) return fail(GF2BV_ERR_ARG, "null pointer");
-	if (stride_words % 2 != 0 || stride_words < c.wt() || ((uintptr_t)d_aug & 15))
-		return fail(GF2BV_ERR_ARG, "device matrix needs 16-byte alignment and an even stride_words covering cols+1 bits");
-	rc = check_device(device);
-	if (rc) return rc;
-	return enqueue_cubic_expand(c, (u64 *)d_aug, stride_words, (hipStream_t)stream);
-	});
+	return terms_expand_device(Terms(d_lin, d_off2, d_ta, d_tb, rows_live, rows, n_lin, d_off3, d_ua, d_ub, d_uc, 3), d_aug, stride_words, device, stream);
 }
-
 int gf2bv_cubic_expand_words(const uint64_t *lin, const int64_t *off2, const uint64_t *ta, const uint64_t *tb, const int64_t *off3,
                              const uint64_t *ua, const uint64_t *ub, const uint64_t *uc, int64_t rows_live, int64_t rows, int64_t n_lin,
                              uint64_t *out_aug, int64_t stride_words, int device)
 {
-	return catching([&]() -> int {
-	const CubicTerms c = cubic_terms(lin, off2, ta, tb, off3, ua, ub, uc, rows_live, rows, n_lin);
-	int rc = check_cubic_terms(c, true);
-	if (rc) return rc;
-	if (!out_aug && rows > 0) return fail(GF2BV_ERR_ARG, "null pointer");
-	if (stride_words < c.wt()) return fail(GF2BV_ERR_ARG, "stride_words does not cover cols+1 bits");
-	if ((rc = check_device(device))) return rc;
-	if (rows == 0) return GF2BV_OK;
-	QuadStage stage(device);
-	if ((rc = stage.expand(c, stride_words))) return rc;
-	return stage.download(out_aug, stride_words, rows);
-	});
+	return terms_expand_words(Terms(lin, off2, ta, tb, rows_live, rows, n_lin, off3, ua, ub, uc, 3), out_aug, stride_words, device, true);
 }
-
 int gf2bv_solve_cubic_terms(const uint64_t *lin, const int64_t *off2, const uint64_t *ta, const uint64_t *tb, const int64_t *off3,
                             const uint64_t *ua, const uint64_t *ub, const uint64_t *uc, int64_t rows_live, int64_t rows, int64_t n_lin,
                             int mode, int device, gf2bv_result **out)
 {
-	return catching([&]() -> int {
-	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
-	*out = nullptr;
-	const CubicTerms c = cubic_terms(lin, off2, ta, tb, off3, ua, ub, uc, rows_live, rows, n_lin);
-	int rc = check_cubic_terms(c, true);
-	if (!rc) rc = check_shape(rows, c.cols(), mode);
-	if (!rc) rc = check_device(device);
-	if (rc) return rc;
-	QuadStage stage(device);
-	if ((rc = stage.expand(c, c.wt()))) return rc;
-	return gf2bv_solve_device(stage.d_aug, rows, c.cols(), stage.ds, mode, device, stage.ps.st, 0, out);
-	});
+	return solve_terms(Terms(lin, off2, ta, tb, rows_live, rows, n_lin, off3, ua, ub, uc, 3), mode, device, out, true);
 }
 
 int gf2bv_cubic_chunks(int64_t n_lin, int32_t *quad_chunk, int32_t *cubic_chunk)
@@ -5285,8 +5216,8 @@ int gf2bv_factor_quad_terms(const uint64_t *lin, const int64_t *term_off, const 
 	return catching([&]() -> int {
 	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
 	*out = nullptr;
-	const QuadTerms q = quad_terms(lin, term_off, ta, tb, rows_live, rows, n_lin);
-	int rc = check_quad_terms(q, true);
+	const Terms q(lin, term_off, ta, tb, rows_live, rows, n_lin);
+	int rc = check_terms(q, true);
 	if (!rc) rc = check_shape(rows, q.cols(), mode);
 	if (!rc) rc = check_device(device);
 	if (rc) return rc;
@@ -5303,8 +5234,8 @@ int gf2bv_factor_append_quad_terms(gf2bv_factor *h, const uint64_t *lin, const i
 	if (!h) return fail(GF2BV_ERR_ARG, "null pointer");
 	if (h->failed) return fail(GF2BV_ERR_ARG, kFailedHandle);
 	if (rows < 1) return fail(GF2BV_ERR_ARG, "rows must be at least 1");
-	const QuadTerms q = quad_terms(lin, term_off, ta, tb, rows, rows, n_lin);
-	int rc = check_quad_terms(q, true);
+	const Terms q(lin, term_off, ta, tb, rows, rows, n_lin);
+	int rc = check_terms(q, true);
 	if (rc) return rc;
 	if (q.cols() != h->cols) return fail(GF2BV_ERR_ARG, "n_lin does not match the handle's columns");
 	if (h->rows + rows >= (1ll << 31) - 64) return fail(GF2BV_ERR_ARG, "system too large");
@@ -5324,8 +5255,8 @@ int gf2bv_solve_rhs_quad_terms(const uint64_t *lin, const int64_t *term_off, con
 	return catching([&]() -> int {
 	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
 	for (i64 j = 0; j < nrhs; j++) out[j] = nullptr;
-	const QuadTerms q = quad_terms(lin, term_off, ta, tb, rows_live, rows, n_lin);
-	int rc = check_quad_terms(q, true);
+	const Terms q(lin, term_off, ta, tb, rows_live, rows, n_lin);
+	int rc = check_terms(q, true);
 	if (!rc) rc = check_shape(rows, q.cols(), mode);
 	if (!rc) rc = check_rhs_args(rows, q.cols(), rhs, false, nrhs, rhs_words);
 	if (!rc) rc = check_device(device);
@@ -5344,7 +5275,7 @@ int gf2bv_quad_expand_batch_words(const uint64_t *lin, const int64_t *term_off, 
 	return catching([&]() -> int {
 	if (nsys < 0) return fail(GF2BV_ERR_ARG, "nsys must not be negative");
 	const i64 *sys_off = reinterpret_cast<const i64 *>(sys_row_off);
-	QuadTerms q = quad_terms(lin, term_off, ta, tb, 0, rows, n_lin);
+	Terms q(lin, term_off, ta, tb, 0, rows, n_lin);
 	int rc = check_quad_batch(q, sys_off, nsys);
 	if (rc) return rc;
 	if (!out_aug && rows > 0 && nsys > 0) return fail(GF2BV_ERR_ARG, "null pointer");
@@ -5365,7 +5296,7 @@ int gf2bv_solve_batch_quad_terms(const uint64_t *lin, const int64_t *term_off, c
 	if (!out || nsys < 0) return fail(GF2BV_ERR_ARG, "null pointer");
 	for (i64 s = 0; s < nsys; s++) out[s] = nullptr;
 	const i64 *sys_off = reinterpret_cast<const i64 *>(sys_row_off);
-	QuadTerms q = quad_terms(lin, term_off, ta, tb, 0, rows, n_lin);
+	Terms q(lin, term_off, ta, tb, 0, rows, n_lin);
 	int rc = check_quad_batch(q, sys_off, nsys);
 	if (!rc) rc = check_shape(rows, q.cols(), mode);
 	if (!rc) rc = check_device(device);
@@ -5384,8 +5315,7 @@ static int xl_expand_device(int degree, int src, const void *d_quad, int64_t m, 
                             int64_t stride_words, int device, void *stream)
 {
 	return catching([&]() -> int {
-	XlShape x;
-	x.degree = degree; x.src = src; x.m = m; x.n = n_lin; x.rows = rows;
+	XlShape x(degree, src, m, n_lin, rows);
 	if (!d_aug || (!d_quad && m > 0)) return fail(GF2BV_ERR_ARG, "null pointer");
 	int rc = check_xl(x, quad_stride_words);
 	if (rc) return rc;
@@ -5400,8 +5330,7 @@ static int xl_expand_words(int degree, int src, const uint64_t *quad, int64_t m,
                            int64_t stride_words, int device)
 {
 	return catching([&]() -> int {
-	XlShape x;
-	x.degree = degree; x.src = src; x.m = m; x.n = n_lin; x.rows = rows;
+	XlShape x(degree, src, m, n_lin, rows);
 	if ((!out_aug && rows > 0) || (!quad && m > 0)) return fail(GF2BV_ERR_ARG, "null pointer");
 	int rc = check_xl(x, quad_stride_words);
 	if (rc) return rc;
@@ -5422,8 +5351,7 @@ static int solve_xl_words(int degree, int src, const uint64_t *quad, int64_t m, 
 	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
 	*out = nullptr;
 	if (!quad && m > 0) return fail(GF2BV_ERR_ARG, "null pointer");
-	XlShape x;
-	x.degree = degree; x.src = src; x.m = m; x.n = n_lin;
+	XlShape x(degree, src, m, n_lin);
 	int rc = check_xl(x, quad_stride_words, true);
 	if (!rc) rc = check_shape(x.rows, x.cols(), mode);
 	if (!rc) rc = check_device(device);
@@ -5435,23 +5363,21 @@ static int solve_xl_words(int degree, int src, const uint64_t *quad, int64_t m, 
 	});
 }
 
-static int solve_xl_quad_terms(int degree, const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t m,
-                               int64_t n_lin, int mode, int device, gf2bv_result **out)
+// (the factored form of either degree: t.rows = t.rows_live = m rows, no padding, expanded by its own kernel in front of the XL kernel)
+static int solve_xl_terms(int degree, const Terms &t, int mode, int device, gf2bv_result **out)
 {
 	return catching([&]() -> int {
 	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
 	*out = nullptr;
-	const QuadTerms q = quad_terms(lin, term_off, ta, tb, m, m, n_lin);      // the m quadratic rows, no padding
-	int rc = check_quad_terms(q, true);
+	int rc = check_terms(t, true);
 	if (rc) return rc;
-	XlShape x;
-	x.degree = degree; x.m = m; x.n = n_lin;
-	rc = check_xl(x, q.wt(), true);
+	XlShape x(degree, t.degree, t.rows, t.n);
+	rc = check_xl(x, t.wt(), true);
 	if (!rc) rc = check_shape(x.rows, x.cols(), mode);
 	if (!rc) rc = check_device(device);
 	if (rc) return rc;
 	QuadStage stage(device);
-	if ((rc = stage.expand(q, q.wt()))) return rc;
+	if ((rc = stage.expand(t, t.wt()))) return rc;
 	if ((rc = stage.expand_xl(x, x.wt()))) return rc;
 	return gf2bv_solve_device(stage.d_xl, x.rows, x.cols(), stage.xs, mode, device, stage.ps.st, 0, out);
 	});
@@ -5463,8 +5389,7 @@ int gf2bv_quad_specialise_device(const void *d_quad, int64_t m, int64_t quad_str
                                  int device, void *stream)
 {
 	return catching([&]() -> int {
-	GuessShape g;
-	g.m = m; g.n = n_lin; g.f = nguess; g.a0 = a0; g.na = na;
+	GuessShape g(m, n_lin, nguess, a0, na);
 	if (!d_out || (!d_quad && m > 0)) return fail(GF2BV_ERR_ARG, "null pointer");
 	int rc = check_guess(g, guess, quad_stride_words);
 	if (rc) return rc;
@@ -5479,8 +5404,7 @@ int gf2bv_quad_specialise_words(const uint64_t *quad, int64_t m, int64_t quad_st
                                 int64_t nguess, int64_t a0, int64_t na, uint64_t *out, int64_t out_stride_words, int device)
 {
 	return catching([&]() -> int {
-	GuessShape g;
-	g.m = m; g.n = n_lin; g.f = nguess; g.a0 = a0; g.na = na;
+	GuessShape g(m, n_lin, nguess, a0, na);
 	if ((!out && m > 0 && na > 0) || (!quad && m > 0)) return fail(GF2BV_ERR_ARG, "null pointer");
 	int rc = check_guess(g, guess, quad_stride_words);
 	if (rc) return rc;
@@ -5502,8 +5426,7 @@ static int xl_expand_batch_device(int degree, const void *d_quad, int64_t nsys, 
                                   void *stream)
 {
 	return catching([&]() -> int {
-	XlShape x;
-	x.degree = degree; x.m = m; x.n = n_lin; x.rows = rows;
+	XlShape x(degree, 2, m, n_lin, rows);
 	if (!d_aug || (!d_quad && m > 0)) return fail(GF2BV_ERR_ARG, "null pointer");
 	int rc = check_xl_batch(x, nsys, quad_sys_stride_words, quad_stride_words, stride_words, sys_stride_words);
 	if (rc) return rc;
@@ -5519,8 +5442,7 @@ static int xl_expand_batch_words(int degree, const uint64_t *quad, int64_t nsys,
                                  int64_t n_lin, int64_t rows, uint64_t *out_aug, int64_t stride_words, int64_t sys_stride_words, int device)
 {
 	return catching([&]() -> int {
-	XlShape x;
-	x.degree = degree; x.m = m; x.n = n_lin; x.rows = rows;
+	XlShape x(degree, 2, m, n_lin, rows);
 	if ((!out_aug && rows > 0 && nsys > 0) || (!quad && m > 0 && nsys > 0)) return fail(GF2BV_ERR_ARG, "null pointer");
 	int rc = check_xl_batch(x, nsys, quad_sys_stride_words, quad_stride_words, stride_words, sys_stride_words);
 	if (rc) return rc;
@@ -5550,9 +5472,7 @@ static int solve_xl_guess_words(int degree, const uint64_t *quad, int64_t m, int
 	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
 	for (i64 s = 0; s < na; s++) out[s] = nullptr;
 	if (!quad && m > 0) return fail(GF2BV_ERR_ARG, "null pointer");
-	GuessShape g;
-	g.x.degree = degree;
-	g.m = m; g.n = n_lin; g.f = nguess; g.a0 = a0; g.na = na;
+	GuessShape g(m, n_lin, nguess, a0, na, degree);
 	int rc = check_guess(g, guess, quad_stride_words);
 	if (!rc) rc = check_guess_solve(g, mode);
 	if (!rc) rc = check_device(device);
@@ -5571,12 +5491,10 @@ static int solve_xl_guess_quad_terms(int degree, const uint64_t *lin, const int6
 	return catching([&]() -> int {
 	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
 	for (i64 s = 0; s < na; s++) out[s] = nullptr;
-	const QuadTerms q = quad_terms(lin, term_off, ta, tb, m, m, n_lin);      // the m quadratic rows, no padding
-	int rc = check_quad_terms(q, true);
+	const Terms q(lin, term_off, ta, tb, m, m, n_lin);      // the m quadratic rows, no padding
+	int rc = check_terms(q, true);
 	if (rc) return rc;
-	GuessShape g;
-	g.x.degree = degree;
-	g.m = m; g.n = n_lin; g.f = nguess; g.a0 = a0; g.na = na;
+	GuessShape g(m, n_lin, nguess, a0, na, degree);
 	rc = check_guess(g, guess, q.wt());
 	if (!rc) rc = check_guess_solve(g, mode);
 	if (!rc) rc = check_device(device);
@@ -5594,8 +5512,7 @@ static int solve_xl_guess_quad_terms(int degree, const uint64_t *lin, const int6
 static int64_t xl_guess_chunk(int degree, int64_t m, int64_t n_lin, int64_t nguess, int64_t free_bytes)
 {
 	if (n_lin < 1 || n_lin > 65535 || nguess < 0 || nguess > std::min<i64>(n_lin - 1, 30) || m < 0 || free_bytes < 0) return -1;
-	XlShape x;
-	x.degree = degree; x.m = m; x.n = n_lin - nguess;
+	XlShape x(degree, 2, m, n_lin - nguess);
 	if (check_xl(x, x.w2(), true)) return -1;
 	const i64 fit = free_bytes / 4 / guess_system_bytes(x);
 	return std::min<i64>({ 1ll << nguess, fit, ((1ll << 31) - 65) / x.rows });
@@ -5650,12 +5567,12 @@ int gf2bv_solve_xl4_words(const uint64_t *quad, int64_t m, int64_t quad_stride_w
 int gf2bv_solve_xl3_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t m, int64_t n_lin,
                                int mode, int device, gf2bv_result **out)
 {
-	return solve_xl_quad_terms(3, lin, term_off, ta, tb, m, n_lin, mode, device, out);
+	return solve_xl_terms(3, Terms(lin, term_off, ta, tb, m, m, n_lin), mode, device, out);
 }
 int gf2bv_solve_xl4_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t m, int64_t n_lin,
                                int mode, int device, gf2bv_result **out)
 {
-	return solve_xl_quad_terms(4, lin, term_off, ta, tb, m, n_lin, mode, device, out);
+	return solve_xl_terms(4, Terms(lin, term_off, ta, tb, m, m, n_lin), mode, device, out);
 }
 int gf2bv_xl3_expand_batch_device(const void *d_quad, int64_t nsys, int64_t quad_sys_stride_words, int64_t m, int64_t quad_stride_words,
                                   int64_t n_lin, int64_t rows, void *d_aug, int64_t stride_words, int64_t sys_stride_words, int device,
@@ -5740,23 +5657,7 @@ int gf2bv_solve_xl4_cubic_terms(const uint64_t *lin, const int64_t *off2, const 
                                 const uint64_t *ua, const uint64_t *ub, const uint64_t *uc, int64_t m, int64_t n_lin, int mode, int device,
                                 gf2bv_result **out)
 {
-	return catching([&]() -> int {
-	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
-	*out = nullptr;
-	const CubicTerms c = cubic_terms(lin, off2, ta, tb, off3, ua, ub, uc, m, m, n_lin);      // the m cubic rows, no padding
-	int rc = check_cubic_terms(c, true);
-	if (rc) return rc;
-	XlShape x;
-	x.degree = 4; x.src = 3; x.m = m; x.n = n_lin;
-	rc = check_xl(x, c.wt(), true);
-	if (!rc) rc = check_shape(x.rows, x.cols(), mode);
-	if (!rc) rc = check_device(device);
-	if (rc) return rc;
-	QuadStage stage(device);
-	if ((rc = stage.expand(c, c.wt()))) return rc;
-	if ((rc = stage.expand_xl(x, x.wt()))) return rc;
-	return gf2bv_solve_device(stage.d_xl, x.rows, x.cols(), stage.xs, mode, device, stage.ps.st, 0, out);
-	});
+	return solve_xl_terms(4, Terms(lin, off2, ta, tb, m, m, n_lin, off3, ua, ub, uc, 3), mode, device, out);
 }
 
 // k_xl4_expand's quartic root, the same function compiled for the host: the largest i >= 3 with C(i,4) <= u (u >= 0), for checks
