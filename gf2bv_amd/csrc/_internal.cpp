@@ -515,6 +515,20 @@ bool parse_equations(PyObject *list, PyObject *cols_obj, PyObject *mode_obj, Py_
 	return parse_cols_mode(cols_obj, mode_obj, cols, mode) && rows_cover_cols(*rows, *cols);
 }
 
+// The epilogue of the entries that return one result: `call(&res)`, run with the GIL released, is the library call that makes it
+// (collect_results below: the entries that return a list)
+template <class F>
+PyObject *single_result(long mode, int device, F &&call)
+{
+	gf2bv_result *res = nullptr;
+	int rc;
+	Py_BEGIN_ALLOW_THREADS          // same place the reference drops the GIL (_internal.c:429)
+	rc = call(&res);
+	Py_END_ALLOW_THREADS
+	if (rc != GF2BV_OK) return raise_rc(rc, "solve");
+	return result_to_py(res, mode, device);
+}
+
 // ------------------------------------------------------------------------------------------------
 // m4ri_solve(equations, cols, mode) -- gf2bv/_internal.c:359-502
 PyObject *py_m4ri_solve(PyObject *, PyObject *const *args, Py_ssize_t nargs)
@@ -528,13 +542,9 @@ PyObject *py_m4ri_solve(PyObject *, PyObject *const *args, Py_ssize_t nargs)
 	DigitGather dg;
 	if (!dg.gather_list(list, cols)) return nullptr;
 
-	gf2bv_result *res = nullptr;
-	int rc;
-	Py_BEGIN_ALLOW_THREADS          // same place the reference drops the GIL (_internal.c:429)
-	rc = gf2bv_solve_digits(dg.digits, dg.off.data(), PyLong_SHIFT, rows, cols, (int)mode, device, &res);
-	Py_END_ALLOW_THREADS
-	if (rc != GF2BV_OK) return raise_rc(rc, "solve");
-	return result_to_py(res, mode, device);
+	return single_result(mode, device, [&](gf2bv_result **res) {
+		return gf2bv_solve_digits(dg.digits, dg.off.data(), PyLong_SHIFT, rows, cols, (int)mode, device, res);
+	});
 }
 
 // right-hand sides (a list of non-negative ints, bit r = affine term of equation r) -> len(rhs) x ceil(rows / 64) words, bits >= rows
@@ -606,47 +616,69 @@ PyObject *collect_results(int64_t n, long mode, int device, F &&fill)
 }
 
 // ---- what the packed front-ends pass in, one parser per kind of input ---------------------------------------------------------
-// The factored form of a quadratic system as four C-contiguous buffers (m4ri_solve_quad_packed's arguments), checked against each
-// other and against n_lin before the library sees them: whole rows of Wl = ceil((n_lin + 1) / 64) words, one offset per row and one
-// more, offsets that start at 0, never decrease and end at the number of operands.  TypeError for what is no buffer, ValueError for
-// a shape.
-struct QuadBuffers {
-	Py_buffer view[4];
+// The factored form of a system as C-contiguous buffers: lin, then per group of products its offsets and its operands -- four
+// buffers for a quadratic system (m4ri_solve_quad_packed's arguments: lin, term_off, ta, tb), eight for a cubic one
+// (m4ri_solve_cubic_packed's: lin, off2, ta, tb, off3, ua, ub, uc).  A layout names the groups and words the refusals.
+struct TermGroup { int off_at, op_at, arity; };               // argument of the offsets, of the first operand; operands per product
+struct TermLayout {
+	int nbuf, ngroups;
+	TermGroup group[2];
+	// The order of the checks, and so which refusal a caller sees for buffers with two faults, is each entry's own from before
+	// the parsers were one: the quadratic entries look at the operands' sizes before the offsets' values, the cubic ones behind
+	// the offsets' end.  Callers and tests match these texts.
+	bool ops_first;
+	const char *bad_len, *bad_ops, *bad_start, *bad_end, *bad_order;
+};
+const TermLayout QUAD_TERMS = {4, 1, {{1, 2, 2}, {0, 0, 0}}, true,
+	"term_off must hold one int64 per row of lin and one more", "ta and tb must hold the same number of whole operands",
+	"term_off must start at 0", "term_off must end at the number of operands in ta", "term_off must not decrease"};
+const TermLayout CUBIC_TERMS = {8, 2, {{1, 2, 2}, {4, 5, 3}}, false,
+	"off2 and off3 must hold one int64 per row of lin and one more", "the operands of a product must hold the same number of whole forms",
+	"off2 and off3 must start at 0", "off2 and off3 must end at the number of operands of their products", "off2 and off3 must not decrease"};
+
+// The buffers of a layout, checked against each other and against n_lin before the library sees them: whole rows of
+// Wl = ceil((n_lin + 1) / 64) words, per group one offset per row and one more, offsets that start at 0, never decrease and end at
+// the number of operands, operands of equal size.  TypeError for what is no buffer, ValueError for a shape.
+struct TermBuffers {
+	const TermLayout &lay;
+	Py_buffer view[8];
 	int got = 0;
-	Py_ssize_t n = 0, live = 0, nterms = 0;
-	const uint64_t *lin = nullptr, *ta = nullptr, *tb = nullptr;
-	const int64_t *off = nullptr;
-	QuadBuffers() = default;
-	QuadBuffers(const QuadBuffers &) = delete;
-	QuadBuffers &operator=(const QuadBuffers &) = delete;
-	~QuadBuffers() { for (int k = 0; k < got; k++) PyBuffer_Release(&view[k]); }
+	Py_ssize_t n = 0, live = 0;
+	explicit TermBuffers(const TermLayout &layout) : lay(layout) {}
+	TermBuffers(const TermBuffers &) = delete;
+	TermBuffers &operator=(const TermBuffers &) = delete;
+	~TermBuffers() { for (int k = 0; k < got; k++) PyBuffer_Release(&view[k]); }
+	const uint64_t *words(int k) const { return static_cast<const uint64_t *>(view[k].buf); }
+	const int64_t *offsets(int k) const { return static_cast<const int64_t *>(view[k].buf); }
 	bool parse(PyObject *const *args, PyObject *n_obj)
 	{
 		n = PyLong_AsSsize_t(n_obj);
 		if (n == -1 && PyErr_Occurred()) return false;
 		if (n < 1 || n > 65535) { PyErr_SetString(PyExc_ValueError, "n_lin must be 1..65535"); return false; }
 		const Py_ssize_t wl = (n + 1 + 63) / 64;
-		for (; got < 4; got++)
+		for (; got < lay.nbuf; got++)
 			if (PyObject_GetBuffer(args[got], &view[got], PyBUF_C_CONTIGUOUS) != 0) return false;
 		live = view[0].len / (wl * 8);
-		nterms = view[2].len / (wl * 8);
-		off = static_cast<const int64_t *>(view[1].buf);
 		const char *bad = nullptr;
 		if (view[0].len != live * wl * 8) bad = "lin must hold whole rows of ceil((n_lin + 1) / 64) 64-bit words";
-		else if (view[1].len != (live + 1) * 8) bad = "term_off must hold one int64 per row of lin and one more";
-		else if (view[2].len != nterms * wl * 8 || view[3].len != view[2].len) bad = "ta and tb must hold the same number of whole operands";
-		else if (off[0] != 0) bad = "term_off must start at 0";
-		else if (off[live] != nterms) bad = "term_off must end at the number of operands in ta";
-		else
-			for (Py_ssize_t r = 0; r < live; r++)
-				if (off[r + 1] < off[r]) { bad = "term_off must not decrease"; break; }
+		for (int g = 0; g < lay.ngroups && !bad; g++) {
+			const TermGroup &tg = lay.group[g];
+			const Py_ssize_t nterms = view[tg.op_at].len / (wl * 8);
+			const int64_t *off = offsets(tg.off_at);
+			bool ops_ok = true;
+			for (int k = 0; k < tg.arity; k++) ops_ok = ops_ok && view[tg.op_at + k].len == nterms * wl * 8;
+			if (view[tg.off_at].len != (live + 1) * 8) bad = lay.bad_len;
+			else if (lay.ops_first && !ops_ok) bad = lay.bad_ops;
+			else if (off[0] != 0) bad = lay.bad_start;
+			else if (off[live] != nterms) bad = lay.bad_end;
+			else if (!ops_ok) bad = lay.bad_ops;
+			for (Py_ssize_t r = 0; r < live && !bad; r++)
+				if (off[r + 1] < off[r]) bad = lay.bad_order;
+		}
 		if (bad) { PyErr_SetString(PyExc_ValueError, bad); return false; }
-		lin = static_cast<const uint64_t *>(view[0].buf);
-		ta = static_cast<const uint64_t *>(view[2].buf);
-		tb = static_cast<const uint64_t *>(view[3].buf);
 		return true;
 	}
-	Py_ssize_t cols() const { return n + n * (n - 1) / 2; }
+	Py_ssize_t cols() const { return n + n * (n - 1) / 2 + (lay.ngroups == 2 ? n * (n - 1) * (n - 2) / 6 : 0); }
 };
 
 // (a buffer taken with PyBUF_C_CONTIGUOUS | PyBUF_FORMAT) a 2-D uint64 array?
@@ -738,59 +770,17 @@ bool parse_packed_call(PyObject *const *args, PackedRows &pr, Py_ssize_t *rows, 
 	return parse_cols_mode(args[3], args[4], cols, mode) && rows_cover_cols(*rows, *cols) && pr.parse(args[0], *rows, words, *cols);
 }
 
-// The prologue of the entries that take the factored form and a row count: arguments 0 .. 3 are the four buffers, then n_lin, rows,
-// mode at the given positions; rows must cover the rows of lin (`live_rows`: the batch entry's systems are checked by its own
+// The prologue of the entries that take the factored form and a row count: the first arguments are the layout's buffers, then n_lin,
+// rows, mode at the given positions; rows must cover the rows of lin (`live_rows`: the batch entry's systems are checked by its own
 // offsets instead) and the columns
-bool parse_quad_call(PyObject *const *args, int n_at, int rows_at, int mode_at, bool live_rows, QuadBuffers &qb, Py_ssize_t *rows, long *mode)
+bool parse_quad_call(PyObject *const *args, int n_at, int rows_at, int mode_at, bool live_rows, TermBuffers &tb, Py_ssize_t *rows, long *mode)
 {
 	*rows = PyLong_AsSsize_t(args[rows_at]);
 	if (*rows == -1 && PyErr_Occurred()) return false;
-	if (!parse_mode(args[mode_at], mode) || !qb.parse(args, args[n_at])) return false;
-	if (live_rows && *rows < qb.live) { PyErr_SetString(PyExc_ValueError, "rows must be at least the rows of lin"); return false; }
-	return rows_cover_cols(*rows, qb.cols());
+	if (!parse_mode(args[mode_at], mode) || !tb.parse(args, args[n_at])) return false;
+	if (live_rows && *rows < tb.live) { PyErr_SetString(PyExc_ValueError, "rows must be at least the rows of lin"); return false; }
+	return rows_cover_cols(*rows, tb.cols());
 }
-
-// The factored form of a cubic system as eight C-contiguous buffers (m4ri_solve_cubic_packed's arguments: lin, off2, ta, tb, off3,
-// ua, ub, uc), checked like QuadBuffers: whole rows of Wl words, two offset arrays with one entry per row and one more, each
-// starting at 0, never decreasing and ending at the number of its operands
-struct CubicBuffers {
-	Py_buffer view[8];
-	int got = 0;
-	Py_ssize_t n = 0, live = 0;
-	CubicBuffers() = default;
-	CubicBuffers(const CubicBuffers &) = delete;
-	CubicBuffers &operator=(const CubicBuffers &) = delete;
-	~CubicBuffers() { for (int k = 0; k < got; k++) PyBuffer_Release(&view[k]); }
-	const uint64_t *words(int k) const { return static_cast<const uint64_t *>(view[k].buf); }
-	const int64_t *offsets(int k) const { return static_cast<const int64_t *>(view[k].buf); }
-	bool parse(PyObject *const *args, PyObject *n_obj)
-	{
-		n = PyLong_AsSsize_t(n_obj);
-		if (n == -1 && PyErr_Occurred()) return false;
-		if (n < 1 || n > 65535) { PyErr_SetString(PyExc_ValueError, "n_lin must be 1..65535"); return false; }
-		const Py_ssize_t wl = (n + 1 + 63) / 64;
-		for (; got < 8; got++)
-			if (PyObject_GetBuffer(args[got], &view[got], PyBUF_C_CONTIGUOUS) != 0) return false;
-		live = view[0].len / (wl * 8);
-		const char *bad = nullptr;
-		if (view[0].len != live * wl * 8) bad = "lin must hold whole rows of ceil((n_lin + 1) / 64) 64-bit words";
-		for (int at = 1; at <= 4 && !bad; at += 3) {       // off2 with ta, tb; off3 with ua, ub, uc
-			const int nop = at == 1 ? 2 : 3;
-			const Py_ssize_t nterms = view[at + 1].len / (wl * 8);
-			const int64_t *off = offsets(at);
-			if (view[at].len != (live + 1) * 8) bad = "off2 and off3 must hold one int64 per row of lin and one more";
-			else if (off[0] != 0) bad = "off2 and off3 must start at 0";
-			else if (off[live] != nterms) bad = "off2 and off3 must end at the number of operands of their products";
-			for (int k = 1; k <= nop && !bad; k++)
-				if (view[at + k].len != nterms * wl * 8) bad = "the operands of a product must hold the same number of whole forms";
-			for (Py_ssize_t r = 0; r < live && !bad; r++)
-				if (off[r + 1] < off[r]) bad = "off2 and off3 must not decrease";
-		}
-		if (bad) { PyErr_SetString(PyExc_ValueError, bad); return false; }
-		return true;
-	}
-	Py_ssize_t cols() const { return n + n * (n - 1) / 2 + n * (n - 1) * (n - 2) / 6; }
-};
 
 // m4ri_solve_rhs(equations, cols, mode, rhs, device=None) -> list of (None | int | AffineSpace), one per element of `rhs`.
 // New entry (no counterpart in the reference): many systems that share their coefficient matrix -- the reference factors A alone
@@ -889,6 +879,19 @@ PyObject *new_factorization(gf2bv_factor *h, int64_t rows, int64_t cols, long mo
 	return (PyObject *)f;
 }
 
+// The epilogue of the entries that return a Factorization, the twin of single_result: `call(&h)` factors a matrix of rows x cols
+template <class F>
+PyObject *factor_result(int64_t rows, int64_t cols, long mode, int device, F &&call)
+{
+	gf2bv_factor *h = nullptr;
+	int rc;
+	Py_BEGIN_ALLOW_THREADS
+	rc = call(&h);
+	Py_END_ALLOW_THREADS
+	if (rc != GF2BV_OK) return raise_rc(rc, "factorization");
+	return new_factorization(h, rows, cols, mode, device);
+}
+
 PyObject *factor_solve(FactorObject *self, PyObject *rhs)
 {
 	if (!factor_open(self)) return nullptr;
@@ -946,14 +949,14 @@ PyObject *factor_append_quad(FactorObject *self, PyObject *const *args, Py_ssize
 {
 	if (nargs != 5) { PyErr_SetString(PyExc_TypeError, "append_quad requires 5 arguments"); return nullptr; }
 	if (!factor_open(self)) return nullptr;
-	QuadBuffers qb;
+	TermBuffers qb(QUAD_TERMS);
 	if (!qb.parse(args, args[4])) return nullptr;
 	if (qb.cols() != self->cols) { PyErr_SetString(PyExc_ValueError, "n_lin does not match the factorization's columns"); return nullptr; }
 	if (qb.live == 0) Py_RETURN_NONE;
 	gf2bv_factor *h = self->h;
 	int rc;
 	Py_BEGIN_ALLOW_THREADS
-	rc = gf2bv_factor_append_quad_terms(h, qb.lin, qb.off, qb.ta, qb.tb, qb.live, qb.n);
+	rc = gf2bv_factor_append_quad_terms(h, qb.words(0), qb.offsets(1), qb.words(2), qb.words(3), qb.live, qb.n);
 	Py_END_ALLOW_THREADS
 	if (rc != GF2BV_OK) return raise_rc(rc, "append");
 	self->rows = gf2bv_factor_rows(h);
@@ -1032,13 +1035,9 @@ PyObject *py_m4ri_factor(PyObject *, PyObject *const *args, Py_ssize_t nargs)
 	if (!parse_equations(list, args[1], args[2], &rows, &cols, &mode)) return nullptr;
 	DigitGather dg;
 	if (!dg.gather_list(list, cols)) return nullptr;
-	gf2bv_factor *h = nullptr;
-	int rc;
-	Py_BEGIN_ALLOW_THREADS
-	rc = gf2bv_factor_digits(dg.digits, dg.off.data(), PyLong_SHIFT, rows, cols, (int)mode, device, &h);
-	Py_END_ALLOW_THREADS
-	if (rc != GF2BV_OK) return raise_rc(rc, "factorization");
-	return new_factorization(h, rows, cols, mode, device);
+	return factor_result(rows, cols, mode, device, [&](gf2bv_factor **h) {
+		return gf2bv_factor_digits(dg.digits, dg.off.data(), PyLong_SHIFT, rows, cols, (int)mode, device, h);
+	});
 }
 
 // m4ri_solve_packed(buffer, rows, words, cols, mode) -> None | int | AffineSpace.
@@ -1055,13 +1054,9 @@ PyObject *py_m4ri_solve_packed(PyObject *, PyObject *const *args, Py_ssize_t nar
 	long mode;
 	PackedRows pr;
 	if (!parse_packed_call(args, pr, &rows, &cols, &mode)) return nullptr;
-	gf2bv_result *res = nullptr;
-	int rc;
-	Py_BEGIN_ALLOW_THREADS
-	rc = gf2bv_solve_digits(pr.digits(), pr.off.data(), 32, rows, cols, (int)mode, device, &res);
-	Py_END_ALLOW_THREADS
-	if (rc != GF2BV_OK) return raise_rc(rc, "solve");
-	return result_to_py(res, mode, device);
+	return single_result(mode, device, [&](gf2bv_result **res) {
+		return gf2bv_solve_digits(pr.digits(), pr.off.data(), 32, rows, cols, (int)mode, device, res);
+	});
 }
 
 // m4ri_solve_quad_packed(lin, term_off, ta, tb, n_lin, rows, mode[, device]) -> None | int | AffineSpace.
@@ -1077,15 +1072,11 @@ PyObject *py_m4ri_solve_quad_packed(PyObject *, PyObject *const *args, Py_ssize_
 	if (!entry_device("m4ri_solve_quad_packed", 7, args, nargs, &device)) return nullptr;
 	Py_ssize_t rows;
 	long mode;
-	QuadBuffers qb;
+	TermBuffers qb(QUAD_TERMS);
 	if (!parse_quad_call(args, 4, 5, 6, true, qb, &rows, &mode)) return nullptr;
-	gf2bv_result *res = nullptr;
-	int rc;
-	Py_BEGIN_ALLOW_THREADS
-	rc = gf2bv_solve_quad_terms(qb.lin, qb.off, qb.ta, qb.tb, qb.live, rows, qb.n, (int)mode, device, &res);
-	Py_END_ALLOW_THREADS
-	if (rc != GF2BV_OK) return raise_rc(rc, "solve");
-	return result_to_py(res, mode, device);
+	return single_result(mode, device, [&](gf2bv_result **res) {
+		return gf2bv_solve_quad_terms(qb.words(0), qb.offsets(1), qb.words(2), qb.words(3), qb.live, rows, qb.n, (int)mode, device, res);
+	});
 }
 
 // m4ri_solve_cubic_packed(lin, off2, ta, tb, off3, ua, ub, uc, n_lin, rows, mode[, device]) -> None | int | AffineSpace.
@@ -1097,21 +1088,14 @@ PyObject *py_m4ri_solve_cubic_packed(PyObject *, PyObject *const *args, Py_ssize
 {
 	int device;
 	if (!entry_device("m4ri_solve_cubic_packed", 11, args, nargs, &device)) return nullptr;
-	const Py_ssize_t rows = PyLong_AsSsize_t(args[9]);
-	if (rows == -1 && PyErr_Occurred()) return nullptr;
+	Py_ssize_t rows;
 	long mode;
-	CubicBuffers cb;
-	if (!parse_mode(args[10], &mode) || !cb.parse(args, args[8])) return nullptr;
-	if (rows < cb.live) { PyErr_SetString(PyExc_ValueError, "rows must be at least the rows of lin"); return nullptr; }
-	if (!rows_cover_cols(rows, cb.cols())) return nullptr;
-	gf2bv_result *res = nullptr;
-	int rc;
-	Py_BEGIN_ALLOW_THREADS
-	rc = gf2bv_solve_cubic_terms(cb.words(0), cb.offsets(1), cb.words(2), cb.words(3), cb.offsets(4), cb.words(5), cb.words(6), cb.words(7),
-	                             cb.live, rows, cb.n, (int)mode, device, &res);
-	Py_END_ALLOW_THREADS
-	if (rc != GF2BV_OK) return raise_rc(rc, "solve");
-	return result_to_py(res, mode, device);
+	TermBuffers cb(CUBIC_TERMS);
+	if (!parse_quad_call(args, 8, 9, 10, true, cb, &rows, &mode)) return nullptr;
+	return single_result(mode, device, [&](gf2bv_result **res) {
+		return gf2bv_solve_cubic_terms(cb.words(0), cb.offsets(1), cb.words(2), cb.words(3), cb.offsets(4), cb.words(5), cb.words(6), cb.words(7),
+		                               cb.live, rows, cb.n, (int)mode, device, res);
+	});
 }
 
 // m4ri_solve_xl4_cubic_packed(lin, off2, ta, tb, off3, ua, ub, uc, n_lin, mode[, device]) -> None | int | AffineSpace over the
@@ -1123,16 +1107,12 @@ PyObject *py_m4ri_solve_xl4_cubic_packed(PyObject *, PyObject *const *args, Py_s
 	int device;
 	if (!entry_device("m4ri_solve_xl4_cubic_packed", 10, args, nargs, &device)) return nullptr;
 	long mode;
-	CubicBuffers cb;
+	TermBuffers cb(CUBIC_TERMS);
 	if (!parse_mode(args[9], &mode) || !cb.parse(args, args[8])) return nullptr;
-	gf2bv_result *res = nullptr;
-	int rc;
-	Py_BEGIN_ALLOW_THREADS
-	rc = gf2bv_solve_xl4_cubic_terms(cb.words(0), cb.offsets(1), cb.words(2), cb.words(3), cb.offsets(4), cb.words(5), cb.words(6), cb.words(7),
-	                                 cb.live, cb.n, (int)mode, device, &res);
-	Py_END_ALLOW_THREADS
-	if (rc != GF2BV_OK) return raise_rc(rc, "solve");
-	return result_to_py(res, mode, device);
+	return single_result(mode, device, [&](gf2bv_result **res) {
+		return gf2bv_solve_xl4_cubic_terms(cb.words(0), cb.offsets(1), cb.words(2), cb.words(3), cb.offsets(4), cb.words(5), cb.words(6), cb.words(7),
+		                                   cb.live, cb.n, (int)mode, device, res);
+	});
 }
 
 // ---- degree-3 XL: quadratic equations multiplied by 1 and by every unknown on the device (gf2bv_hip.h, "degree-3 XL") --------------
@@ -1183,13 +1163,9 @@ template <int D> PyObject *py_m4ri_solve_xl(PyObject *, PyObject *const *args, P
 	std::vector<uint64_t> quad;
 	int64_t m, n, w2;
 	if (!quad_rows_from_ints(args[0], args[1], quad, &m, &n, &w2)) return nullptr;
-	gf2bv_result *res = nullptr;
-	int rc;
-	Py_BEGIN_ALLOW_THREADS
-	rc = (D == 4 ? gf2bv_solve_xl4_words : gf2bv_solve_xl3_words)(quad.data(), m, w2, n, (int)mode, device, &res);
-	Py_END_ALLOW_THREADS
-	if (rc != GF2BV_OK) return raise_rc(rc, "solve");
-	return result_to_py(res, mode, device);
+	return single_result(mode, device, [&](gf2bv_result **res) {
+		return (D == 4 ? gf2bv_solve_xl4_words : gf2bv_solve_xl3_words)(quad.data(), m, w2, n, (int)mode, device, res);
+	});
 }
 
 // m4ri_solve_xl3_quad_packed(lin, term_off, ta, tb, n_lin, mode[, device]) -> None | int | AffineSpace: m4ri_solve_quad_packed's
@@ -1199,15 +1175,11 @@ template <int D> PyObject *py_m4ri_solve_xl_quad_packed(PyObject *, PyObject *co
 	int device;
 	if (!entry_device(D == 4 ? "m4ri_solve_xl4_quad_packed" : "m4ri_solve_xl3_quad_packed", 6, args, nargs, &device)) return nullptr;
 	long mode;
-	QuadBuffers qb;
+	TermBuffers qb(QUAD_TERMS);
 	if (!parse_mode(args[5], &mode) || !qb.parse(args, args[4])) return nullptr;
-	gf2bv_result *res = nullptr;
-	int rc;
-	Py_BEGIN_ALLOW_THREADS
-	rc = (D == 4 ? gf2bv_solve_xl4_quad_terms : gf2bv_solve_xl3_quad_terms)(qb.lin, qb.off, qb.ta, qb.tb, qb.live, qb.n, (int)mode, device, &res);
-	Py_END_ALLOW_THREADS
-	if (rc != GF2BV_OK) return raise_rc(rc, "solve");
-	return result_to_py(res, mode, device);
+	return single_result(mode, device, [&](gf2bv_result **res) {
+		return (D == 4 ? gf2bv_solve_xl4_quad_terms : gf2bv_solve_xl3_quad_terms)(qb.words(0), qb.offsets(1), qb.words(2), qb.words(3), qb.live, qb.n, (int)mode, device, res);
+	});
 }
 
 // ---- hybrid XL: guessed unknowns, every assignment's system in one batch (gf2bv_hip.h, "hybrid XL") ---------------------------------
@@ -1266,11 +1238,11 @@ template <int D> PyObject *py_m4ri_solve_xl_guess_quad_packed(PyObject *, PyObje
 	if (!entry_device(D == 4 ? "m4ri_solve_xl4_guess_quad_packed" : "m4ri_solve_xl3_guess_quad_packed", 9, args, nargs, &device)) return nullptr;
 	long mode;
 	GuessArgs ga;
-	QuadBuffers qb;
+	TermBuffers qb(QUAD_TERMS);
 	if (!parse_mode(args[8], &mode) || !ga.parse(args[5], args[6], args[7]) || !qb.parse(args, args[4])) return nullptr;
 	if (ga.na == 0) return PyList_New(0);
 	return collect_results(ga.na, mode, device, [&](gf2bv_result **out) {
-		return (D == 4 ? gf2bv_solve_xl4_guess_quad_terms : gf2bv_solve_xl3_guess_quad_terms)(qb.lin, qb.off, qb.ta, qb.tb, qb.live, qb.n, ga.g.data(),
+		return (D == 4 ? gf2bv_solve_xl4_guess_quad_terms : gf2bv_solve_xl3_guess_quad_terms)(qb.words(0), qb.offsets(1), qb.words(2), qb.words(3), qb.live, qb.n, ga.g.data(),
 		                                                                                     (int64_t)ga.g.size(), ga.a0, ga.na, (int)mode, device, out);
 	});
 }
@@ -1286,13 +1258,9 @@ PyObject *py_m4ri_factor_packed(PyObject *, PyObject *const *args, Py_ssize_t na
 	long mode;
 	PackedRows pr;
 	if (!parse_packed_call(args, pr, &rows, &cols, &mode)) return nullptr;
-	gf2bv_factor *h = nullptr;
-	int rc;
-	Py_BEGIN_ALLOW_THREADS
-	rc = gf2bv_factor_digits(pr.digits(), pr.off.data(), 32, rows, cols, (int)mode, device, &h);
-	Py_END_ALLOW_THREADS
-	if (rc != GF2BV_OK) return raise_rc(rc, "factorization");
-	return new_factorization(h, rows, cols, mode, device);
+	return factor_result(rows, cols, mode, device, [&](gf2bv_factor **h) {
+		return gf2bv_factor_digits(pr.digits(), pr.off.data(), 32, rows, cols, (int)mode, device, h);
+	});
 }
 
 // m4ri_factor_quad_packed(lin, term_off, ta, tb, n_lin, rows, mode[, device]) -> Factorization over n_lin + n_lin(n_lin-1)/2
@@ -1303,15 +1271,11 @@ PyObject *py_m4ri_factor_quad_packed(PyObject *, PyObject *const *args, Py_ssize
 	if (!entry_device("m4ri_factor_quad_packed", 7, args, nargs, &device)) return nullptr;
 	Py_ssize_t rows;
 	long mode;
-	QuadBuffers qb;
+	TermBuffers qb(QUAD_TERMS);
 	if (!parse_quad_call(args, 4, 5, 6, true, qb, &rows, &mode)) return nullptr;
-	gf2bv_factor *h = nullptr;
-	int rc;
-	Py_BEGIN_ALLOW_THREADS
-	rc = gf2bv_factor_quad_terms(qb.lin, qb.off, qb.ta, qb.tb, qb.live, rows, qb.n, (int)mode, device, &h);
-	Py_END_ALLOW_THREADS
-	if (rc != GF2BV_OK) return raise_rc(rc, "factorization");
-	return new_factorization(h, rows, qb.cols(), mode, device);
+	return factor_result(rows, qb.cols(), mode, device, [&](gf2bv_factor **h) {
+		return gf2bv_factor_quad_terms(qb.words(0), qb.offsets(1), qb.words(2), qb.words(3), qb.live, rows, qb.n, (int)mode, device, h);
+	});
 }
 
 // m4ri_solve_rhs_packed(buffer, rows, words, cols, mode, rhs[, device]) -> list: m4ri_solve_rhs on m4ri_solve_packed's buffer;
@@ -1340,13 +1304,13 @@ PyObject *py_m4ri_solve_rhs_quad_packed(PyObject *, PyObject *const *args, Py_ss
 	if (!entry_device("m4ri_solve_rhs_quad_packed", 8, args, nargs, &device)) return nullptr;
 	Py_ssize_t rows;
 	long mode;
-	QuadBuffers qb;
+	TermBuffers qb(QUAD_TERMS);
 	if (!parse_quad_call(args, 4, 5, 6, true, qb, &rows, &mode)) return nullptr;
 	RhsInput ri;
 	if (!ri.parse(args[7], rows)) return nullptr;
 	if (ri.nrhs == 0) return PyList_New(0);
 	return collect_results(ri.nrhs, mode, device, [&](gf2bv_result **out) {
-		return gf2bv_solve_rhs_quad_terms(qb.lin, qb.off, qb.ta, qb.tb, qb.live, rows, qb.n, ri.src, ri.nrhs, ri.stride, (int)mode, device, out);
+		return gf2bv_solve_rhs_quad_terms(qb.words(0), qb.offsets(1), qb.words(2), qb.words(3), qb.live, rows, qb.n, ri.src, ri.nrhs, ri.stride, (int)mode, device, out);
 	});
 }
 
@@ -1360,7 +1324,7 @@ PyObject *py_m4ri_solve_many_quad_packed(PyObject *, PyObject *const *args, Py_s
 	if (!entry_device("m4ri_solve_many_quad_packed", 8, args, nargs, &device)) return nullptr;
 	Py_ssize_t rows;
 	long mode;
-	QuadBuffers qb;
+	TermBuffers qb(QUAD_TERMS);
 	if (!parse_quad_call(args, 5, 6, 7, false, qb, &rows, &mode)) return nullptr;
 	HeldBuffer sv;
 	if (!sv.take(args[4], PyBUF_C_CONTIGUOUS)) return nullptr;
@@ -1378,7 +1342,7 @@ PyObject *py_m4ri_solve_many_quad_packed(PyObject *, PyObject *const *args, Py_s
 	if (bad) { PyErr_SetString(PyExc_ValueError, bad); return nullptr; }
 	if (nsys == 0) return PyList_New(0);
 	return collect_results(nsys, mode, device, [&](gf2bv_result **out) {
-		return gf2bv_solve_batch_quad_terms(qb.lin, qb.off, qb.ta, qb.tb, sys, nsys, rows, qb.n, (int)mode, device, out);
+		return gf2bv_solve_batch_quad_terms(qb.words(0), qb.offsets(1), qb.words(2), qb.words(3), sys, nsys, rows, qb.n, (int)mode, device, out);
 	});
 }
 

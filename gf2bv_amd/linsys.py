@@ -24,7 +24,80 @@ class DimensionTooLargeError(Exception):
         self.space = space
 
 
-class LinearSystem:
+def _refuse_large(space: AffineSpace, max_dimension: int) -> None:
+    if space.dimension > max_dimension:
+        raise DimensionTooLargeError(
+            f"Solution space (dim {space.dimension}) is too large, try increase max_dimension "
+            f"({max_dimension}) if you want (there will be 2**dim solutions)",
+            space=space,
+        )
+
+
+def _space_points(space: Optional[AffineSpace], max_dimension: int, convert):
+    """the points of a solution space (None: no solution) that `convert` keeps, in AffineSpace order"""
+    if space is None:
+        return
+    _refuse_large(space, max_dimension)
+    for raw in space:
+        sol = convert(raw)
+        if sol is not None:
+            yield sol
+
+
+def _raw_value(sol: tuple, sizes: Sequence[int]) -> int:
+    """per-variable ints -> the raw int they are the parts of"""
+    raw, shift = 0, 0
+    for value, width in zip(sol, sizes):
+        raw |= value << shift
+        shift += width
+    return raw
+
+
+def _eqs_from_words(rows, cols: int) -> list:
+    """device rows of the augmented-words layout (column c at bit c, the constant at column `cols`) -> equation ints (bit 0 the
+    constant, bit 1 + c column c), zeros dropped"""
+    mask = (1 << cols) - 1
+    eqs = []
+    for r in rows:
+        v = int.from_bytes(r.tobytes(), "little")
+        eqs.append(((v & mask) << 1) | (v >> cols))
+    return [e for e in eqs if e]                       # literal zeros carry no information
+
+
+class _SolveSurface:
+    """What follows the boundary call, shared by ``LinearSystem`` and the packed front-end's ``PackedLinearSystem``: raw solutions
+    to per-variable ints and back.  Needs ``_sizes`` and ``_solve_internal(zeros, mode)`` of the class it is mixed into."""
+
+    # -- raw int -> per-variable ints (reference :242-251) ----------------------------------------------
+    def _convert_sol(self, s: int) -> tuple:
+        parts = []
+        for width in self._sizes:
+            parts.append(s & ((1 << width) - 1))
+            s >>= width
+        assert s == 0, "Invalid solution"
+        return tuple(parts)
+
+    def convert_sol(self, s: int) -> Optional[tuple]:
+        return self._convert_sol(s)
+
+    def solve_raw_one(self, zeros: Zeros):
+        return self._solve_internal(zeros, 0)
+
+    def solve_raw_space(self, zeros: Zeros):
+        return self._solve_internal(zeros, 1)
+
+    def solve_all(self, zeros: Zeros, *, max_dimension: int = 16):
+        yield from _space_points(self.solve_raw_space(zeros), max_dimension, self.convert_sol)
+
+    def solve_one(self, zeros: Zeros):
+        raw = self._solve_internal(zeros, 0)
+        return None if raw is None else self.convert_sol(raw)
+
+    def evaluate(self, bv: BitVec, sol: tuple) -> int:
+        return bv.evaluate(_raw_value(sol, self._sizes))
+
+
+class LinearSystem(_SolveSurface):
     def __init__(self, sizes: Iterable[int]):
         self._sizes = list(sizes)
         self._cols = sum(self._sizes)
@@ -91,43 +164,6 @@ class LinearSystem:
         if len(eqs) < self._cols:               # the boundary wants rows >= cols
             eqs.extend([0] * (self._cols - len(eqs)))
         return m4ri_solve(eqs, self._cols, mode)
-
-    # -- raw int -> per-variable ints (reference :242-251) ----------------------------------------------
-    def _convert_sol(self, s: int) -> tuple:
-        parts = []
-        for width in self._sizes:
-            parts.append(s & ((1 << width) - 1))
-            s >>= width
-        assert s == 0, "Invalid solution"
-        return tuple(parts)
-
-    def convert_sol(self, s: int) -> Optional[tuple]:
-        return self._convert_sol(s)
-
-    def solve_raw_one(self, zeros: Zeros):
-        return self._solve_internal(zeros, 0)
-
-    def solve_raw_space(self, zeros: Zeros):
-        return self._solve_internal(zeros, 1)
-
-    def solve_all(self, zeros: Zeros, *, max_dimension: int = 16):
-        space = self.solve_raw_space(zeros)
-        if space is None:
-            return
-        if space.dimension > max_dimension:
-            raise DimensionTooLargeError(
-                f"Solution space (dim {space.dimension}) is too large, try increase max_dimension "
-                f"({max_dimension}) if you want (there will be 2**dim solutions)",
-                space=space,
-            )
-        for raw in space:
-            sol = self.convert_sol(raw)
-            if sol is not None:
-                yield sol
-
-    def solve_one(self, zeros: Zeros):
-        raw = self._solve_internal(zeros, 0)
-        return None if raw is None else self.convert_sol(raw)
 
     # -- batches (no counterpart in the reference) ----------------------------------------------------------
     # Independent instances of the same LinearSystem (one zeros list per instance / per output bit) go to
@@ -219,13 +255,6 @@ class LinearSystem:
         (one per expression) and equal this system's methods on [e ^ v for e, v in zip(exprs, values)].  Needs numpy."""
         from .factored import FactoredSystem     # noqa: PLC0415  (numpy on first use only)
         return FactoredSystem(self, exprs, device)
-
-    def evaluate(self, bv: BitVec, sol: tuple) -> int:
-        raw, shift = 0, 0
-        for value, width in zip(sol, self._sizes):
-            raw |= value << shift
-            shift += width
-        return bv.evaluate(raw)
 
 
 # -- the columns of degree-3 XL: the n unknowns, their pairs, their triples (DESIGN.md section 7) -----------------------------------------
@@ -331,12 +360,7 @@ class _QuadraticPoints:
         for space in self.solve_raw_space_rhs(exprs, values_list):
             sol = None
             if space is not None:
-                if space.dimension > max_dimension:
-                    raise DimensionTooLargeError(
-                        f"Solution space (dim {space.dimension}) is too large, try increase max_dimension "
-                        f"({max_dimension}) if you want (there will be 2**dim solutions)",
-                        space=space,
-                    )
+                _refuse_large(space, max_dimension)
                 for raw in space:
                     sol = self.convert_sol(raw)
                     if sol is not None:
@@ -441,19 +465,8 @@ class _QuadraticPoints:
         return None
 
     def _solve_all_xl(self, zeros: Zeros, max_dimension: int, degree: int):
-        space = self._solve_internal_xl(zeros, 1, degree)
-        if space is None:
-            return
-        if space.dimension > max_dimension:
-            raise DimensionTooLargeError(
-                f"Solution space (dim {space.dimension}) is too large, try increase max_dimension "
-                f"({max_dimension}) if you want (there will be 2**dim solutions)",
-                space=space,
-            )
-        for raw in space:
-            sol = self.convert_sol_xl4(raw) if degree == 4 else self.convert_sol_xl(raw)
-            if sol is not None:
-                yield sol
+        convert = self.convert_sol_xl4 if degree == 4 else self.convert_sol_xl
+        yield from _space_points(self._solve_internal_xl(zeros, 1, degree), max_dimension, convert)
 
     def solve_one_xl(self, zeros: Zeros, *, degree: int = 3):
         self._check_degree(degree)
@@ -595,20 +608,12 @@ class _QuadraticPoints:
         from . import hip                              # noqa: PLC0415  (ctypes binding, first use only)
         if not len(quad):
             return []
-        cols3 = xl4_cols(self._lin_size) if degree == 4 else xl3_cols(self._lin_size)
-        mask = (1 << cols3) - 1
-        eqs = []
-        for r in (hip.xl4_expand_words if degree == 4 else hip.xl3_expand_words)(quad, self._lin_size):
-            v = int.from_bytes(r.tobytes(), "little")
-            eqs.append(((v & mask) << 1) | (v >> cols3))
-        return [e for e in eqs if e]
+        if degree == 4:
+            return _eqs_from_words(hip.xl4_expand_words(quad, self._lin_size), xl4_cols(self._lin_size))
+        return _eqs_from_words(hip.xl3_expand_words(quad, self._lin_size), xl3_cols(self._lin_size))
 
     def evaluate(self, bv: BitVec, sol: tuple) -> int:
-        raw, shift = 0, 0
-        for value, width in zip(sol, self._quad_sizes):
-            raw |= value << shift
-            shift += width
-        return bv.evaluate(raw)
+        return bv.evaluate(_raw_value(sol, self._quad_sizes))
 
 
 class QuadraticSystem(_QuadraticPoints, LinearSystem):

@@ -25,7 +25,7 @@ from ._internal import (m4ri_solve_cubic_packed, m4ri_solve_many_quad_packed, m4
                         m4ri_solve_xl3_guess_quad_packed, m4ri_solve_xl3_quad_packed, m4ri_solve_xl4_guess_quad_packed,
                         m4ri_solve_xl4_cubic_packed, m4ri_solve_xl4_quad_packed)
 from .bitvec import BitVec
-from .linsys import DimensionTooLargeError, _QuadraticPoints, xl3_cols, xl4_cols
+from .linsys import _QuadraticPoints, _SolveSurface, _eqs_from_words, _raw_value, _space_points, xl3_cols, xl4_cols
 
 
 def _const_bits(n: int, value: int) -> np.ndarray:
@@ -86,7 +86,7 @@ class PackedBitVec(BitVec):
 
     # -- xor (reference :39-49) ----------------------------------------------------------------
     def __xor__(self, other):
-        if isinstance(other, (PackedQuadBitVec, PackedCubicBitVec)):
+        if isinstance(other, _TermsBitVec):
             return NotImplemented                      # (its __rxor__ takes over: the sum is quadratic or cubic)
         return PackedBitVec(self._rows ^ self._coerce(other))
 
@@ -174,10 +174,8 @@ class PackedBitVec(BitVec):
         return PackedBitVec(np.tile(self._rows, (n, 1)))
 
     def concat(self, other: "PackedBitVec"):
-        if isinstance(other, PackedQuadBitVec):        # (linear bits in front of bits that carry products)
-            return other._like(self._rows, np.zeros(len(self) + 1, dtype=np.int64), other._ta[:0], other._tb[:0]).concat(other)
-        if isinstance(other, PackedCubicBitVec):
-            return other._linear(self._rows).concat(other)
+        if isinstance(other, _TermsBitVec):            # (linear bits in front of bits that carry products)
+            return other._from_rows(self._rows, other._n).concat(other)
         return PackedBitVec(np.concatenate([self._rows, other._rows]))
 
     # -- evaluation (reference :128-134) -----------------------------------------------------------
@@ -188,9 +186,9 @@ class PackedBitVec(BitVec):
         return int(sum(int(b) << i for i, b in enumerate(par)))
 
 
-class PackedLinearSystem:
+class PackedLinearSystem(_SolveSurface):
     """LinearSystem (gf2bv/__init__.py:137-287) on PackedBitVecs: same methods, same results, no list of ints on the
-    way to the solver."""
+    way to the solver (what follows the boundary call is LinearSystem's own code, _SolveSurface)."""
 
     def __init__(self, sizes: Iterable[int]):
         self._sizes = list(sizes)
@@ -253,42 +251,6 @@ class PackedLinearSystem:
         rows = np.ascontiguousarray(rows)
         return m4ri_solve_packed(rows, rows.shape[0], self._words, self._cols, mode)
 
-    def _convert_sol(self, s: int) -> tuple:
-        parts = []
-        for width in self._sizes:
-            parts.append(s & ((1 << width) - 1))
-            s >>= width
-        assert s == 0, "Invalid solution"
-        return tuple(parts)
-
-    def convert_sol(self, s: int) -> Optional[tuple]:
-        return self._convert_sol(s)
-
-    def solve_raw_one(self, zeros: Sequence):
-        return self._solve_internal(zeros, 0)
-
-    def solve_raw_space(self, zeros: Sequence):
-        return self._solve_internal(zeros, 1)
-
-    def solve_one(self, zeros: Sequence):
-        raw = self._solve_internal(zeros, 0)
-        return None if raw is None else self.convert_sol(raw)
-
-    def solve_all(self, zeros: Sequence, *, max_dimension: int = 16):
-        space = self.solve_raw_space(zeros)
-        if space is None:
-            return
-        if space.dimension > max_dimension:
-            raise DimensionTooLargeError(
-                f"Solution space (dim {space.dimension}) is too large, try increase max_dimension "
-                f"({max_dimension}) if you want (there will be 2**dim solutions)",
-                space=space,
-            )
-        for raw in space:
-            sol = self.convert_sol(raw)
-            if sol is not None:
-                yield sol
-
     # -- many right-hand sides of one matrix, and the matrix factored once (LinearSystem's, no counterpart in the reference) ------
     def _flat_rows(self, exprs: Sequence):
         """(widths, rows) of `exprs` for a factored system: per expression its width (0: an equation int), and every row in
@@ -330,50 +292,80 @@ class PackedLinearSystem:
     def solve_one_rhs(self, exprs: Sequence, values_list: Sequence[Sequence[int]]) -> list:
         return [None if raw is None else self.convert_sol(raw) for raw in self._solve_internal_rhs(exprs, values_list, 0)]
 
-    def evaluate(self, bv: BitVec, sol: tuple) -> int:
-        raw, shift = 0, 0
-        for value, width in zip(sol, self._sizes):
-            raw |= value << shift
-            shift += width
-        return bv.evaluate(raw)
 
-
-# ---- quadratic systems kept factored ---------------------------------------------------------------------------------------------
+# ---- systems kept factored: one vector of bits that carry products --------------------------------------------------------------
 # QuadraticSystem.mul_bit writes the linearised row of a product on the host, n(n-1)/2 bits beyond the n + 1 of its operands: at
 # n = 256 that is 10 ms per product and a 32896-column system cannot be written down in an hour.  Here a symbolic bit stays what the
-# caller wrote: a linear form over the n + 1 bits plus a list of products of two such forms.  The rows of the linearised matrix
-# come into being on the device (k_quad_expand, through m4ri_solve_quad_packed / hip.quad_expand_words), where the solver reads them.
+# caller wrote: a linear form over the n + 1 bits plus lists of products of such forms.  The rows of the linearised matrix come into
+# being on the device (k_quad_expand / k_cubic_expand, through m4ri_solve_quad_packed / m4ri_solve_cubic_packed / hip.*_expand_words),
+# where the solver reads them.  PackedQuadBitVec (products of two forms) and PackedCubicBitVec (of two and of three) are one
+# vector over groups of products, _TermsBitVec.
+def _take_terms(group: tuple, idx: np.ndarray):
+    """the products (offsets, operand arrays) of the bits idx[0], idx[1], ... of a group"""
+    off, ops = group
+    cnt = off[idx + 1] - off[idx]
+    new = np.zeros(len(idx) + 1, dtype=np.int64)
+    np.cumsum(cnt, out=new[1:])
+    src = np.repeat(off[idx] - new[:-1], cnt) + np.arange(new[-1])         # operand row of every kept product
+    return new, tuple([x[src] for x in ops])
+
+
+def _xor_terms(a: tuple, b: tuple):
+    """bit i of the sum owns the products of a[i], then those of b[i]"""
+    (off_a, ops_a), (off_b, ops_b) = a, b
+    bits = np.arange(len(off_a) - 1)
+    owner = np.concatenate([np.repeat(bits, np.diff(off_a)), np.repeat(bits, np.diff(off_b))])
+    order = np.argsort(owner, kind="stable")
+    return off_a + off_b, tuple([np.concatenate(xy)[order] for xy in zip(ops_a, ops_b)])
+
+
+def _cat_terms(a: tuple, b: tuple):
+    """the bits of b behind those of a"""
+    (off_a, ops_a), (off_b, ops_b) = a, b
+    return np.concatenate([off_a, off_b[1:] + off_a[-1]]), tuple([np.concatenate(xy) for xy in zip(ops_a, ops_b)])
+
+
 def _refuse(name: str):
     def method(self, *args, **kwargs):
-        raise TypeError(f"{name} is not supported on a PackedQuadBitVec (bits that carry products): only ^, indexing and concat are")
+        raise TypeError(f"{name} is not supported on a {type(self).__name__} (bits that carry products): only ^, indexing and concat are")
     method.__name__ = name
     return method
 
 
-class PackedQuadBitVec:
-    """k symbolic bits, each a linear form (a row of ``_lin``, Wl = ceil((n + 1) / 64) words in the order of ``PackedBitVec``)
-    plus products of two linear forms: bit i owns the operand rows ``_off[i] .. _off[i + 1]`` of ``_ta`` / ``_tb``.  The value of
-    a product is ``QuadraticSystem._mul_bit`` of its operands; equal products are not cancelled here, they cancel when the rows
-    are expanded."""
-    __slots__ = ("_lin", "_off", "_ta", "_tb", "_n")
+def _part(group: int, operand: Optional[int] = None) -> property:
+    """a group's offsets, or one of its operand arrays, under the name the class documents"""
+    if operand is None:
+        return property(lambda self: self._groups[group][0])
+    return property(lambda self: self._groups[group][1][operand])
 
-    def __init__(self, lin: np.ndarray, off: np.ndarray, ta: np.ndarray, tb: np.ndarray, n: int):
-        self._lin, self._off, self._ta, self._tb = lin, off, ta, tb      # [k, Wl] uint64, [k + 1] int64, [T, Wl], [T, Wl]: immutable
-        self._n = n                                    # unknowns of the system (Wl alone leaves 64 candidates)
 
-    def _like(self, lin, off, ta, tb) -> "PackedQuadBitVec":
-        return PackedQuadBitVec(lin, off, ta, tb, self._n)
+class _TermsBitVec:
+    """k symbolic bits, each a linear form (a row of ``_lin``, Wl = ceil((n + 1) / 64) words in the order of ``PackedBitVec``) plus
+    products of linear forms, kept as one group ``(off, ops)`` per arity of ``_ARITIES``: bit i owns the rows ``off[i] .. off[i + 1]``
+    of every operand array of ``ops``.  Equal products are not cancelled here, they cancel when the rows are expanded.  What a
+    product's value is, and what may be mixed with what (``_coerce``), is the subclass's."""
+    __slots__ = ("_lin", "_groups", "_n")
+    _ARITIES: tuple = ()
+
+    def _new(self, lin: np.ndarray, groups: tuple):
+        v = object.__new__(type(self))
+        v._lin, v._groups, v._n = lin, groups, self._n                     # [k, Wl] uint64, ([k + 1] int64, [T, Wl] x arity) per group: immutable
+        return v
+
+    @classmethod
+    def _from_rows(cls, rows: np.ndarray, n: int):
+        """linear bits (the rows of a PackedBitVec) over n unknowns as a vector of this kind"""
+        v = object.__new__(cls)
+        none, off = rows[:0], np.zeros(len(rows) + 1, dtype=np.int64)
+        v._lin, v._groups, v._n = rows, tuple([(off, (none,) * arity) for arity in cls._ARITIES]), n
+        return v
 
     def __len__(self):
         return self._lin.shape[0]
 
-    def _take(self, idx: np.ndarray) -> "PackedQuadBitVec":
+    def _take(self, idx: np.ndarray):
         """the bits idx[0], idx[1], ... as a new vector"""
-        cnt = self._off[idx + 1] - self._off[idx]
-        off = np.zeros(len(idx) + 1, dtype=np.int64)
-        np.cumsum(cnt, out=off[1:])
-        src = np.repeat(self._off[idx] - off[:-1], cnt) + np.arange(off[-1])       # operand row of every kept product
-        return self._like(self._lin[idx], off, self._ta[src], self._tb[src])
+        return self._new(self._lin[idx], tuple([_take_terms(g, idx) for g in self._groups]))
 
     def __getitem__(self, key):
         n = len(self)
@@ -381,42 +373,66 @@ class PackedQuadBitVec:
             return self._take(np.arange(n)[key])
         i = operator.index(key)
         if not -n <= i < n:
-            raise IndexError("PackedQuadBitVec index out of range")
+            raise IndexError(f"{type(self).__name__} index out of range")
         return self._take(np.array([i % n]))
 
     def __xor__(self, other):
-        if isinstance(other, PackedQuadBitVec):
-            if other._lin.shape != self._lin.shape:
+        if isinstance(other, PackedBitVec) and other._rows.shape == self._lin.shape:
+            return self._new(self._lin ^ other._rows, self._groups)      # (no products to merge, no vector to make of the rows)
+        if isinstance(other, (_TermsBitVec, BitVec)):
+            other = self._coerce(other, "^")
+            if other is NotImplemented:
+                return other
+            if other._lin.shape[0] != self._lin.shape[0]:
                 raise ValueError("Cannot mix bitvecs of different lengths")
-            # bit i of the sum owns the products of self[i], then those of other[i]
-            owner = np.concatenate([np.repeat(np.arange(len(self)), np.diff(self._off)), np.repeat(np.arange(len(self)), np.diff(other._off))])
-            order = np.argsort(owner, kind="stable")
-            return self._like(self._lin ^ other._lin, self._off + other._off, np.concatenate([self._ta, other._ta])[order],
-                              np.concatenate([self._tb, other._tb])[order])
-        if isinstance(other, PackedBitVec):
-            if other._rows.shape != self._lin.shape:
-                raise ValueError("Cannot mix bitvecs of different lengths")
-            return self._like(self._lin ^ other._rows, self._off, self._ta, self._tb)
-        if isinstance(other, BitVec):
-            raise TypeError("cannot mix packed and tuple-of-int BitVecs")
-        if isinstance(other, PackedCubicBitVec):
-            return NotImplemented                      # (its __rxor__ says why the two do not mix)
+            return self._new(self._lin ^ other._lin, tuple(map(_xor_terms, self._groups, other._groups)))
         lin = self._lin.copy()
         lin[:, 0] ^= _const_bits(len(self), other)      # a constant only has the affine bit
-        return self._like(lin, self._off, self._ta, self._tb)
+        return self._new(lin, self._groups)
 
     __rxor__ = __xor__
     __pow__ = __xor__
 
     def concat(self, other):
-        if isinstance(other, PackedBitVec):
-            other = self._like(other._rows, np.zeros(len(other) + 1, dtype=np.int64), self._ta[:0], self._tb[:0])
+        other = self._coerce(other, "concat")
+        return self._new(np.concatenate([self._lin, other._lin]), tuple(map(_cat_terms, self._groups, other._groups)))
+
+
+for _name in ("__and__", "__rand__", "__or__", "__ror__", "__lshift__", "__rshift__", "__mod__", "__invert__", "lshift_ext", "rotl", "rotr",
+              "sum", "zeroext", "signext", "broadcast", "dup"):
+    setattr(_TermsBitVec, _name, _refuse(_name))
+del _name
+
+
+# The quadratic class's products are QuadraticSystem._mul_bit's, which drops the constant x linear cross terms; the cubic class's are
+# the EXACT products of GF(2)[x] / (x_i^2 + x_i), constants included.  That is why the two kinds of vector do not mix.
+_QUAD_MIX = ("a PackedQuadBitVec cannot be mixed with a PackedCubicBitVec: the quadratic class's products follow the reference's "
+             "_mul_bit (no constant x linear cross terms), this class's are the exact products")
+
+
+class PackedQuadBitVec(_TermsBitVec):
+    """``_TermsBitVec`` with products of two linear forms: bit i owns the operand rows ``_off[i] .. _off[i + 1]`` of ``_ta`` /
+    ``_tb``.  The value of a product is ``QuadraticSystem._mul_bit`` of its operands."""
+    __slots__ = ()
+    _ARITIES = (2,)
+    _off, _ta, _tb = _part(0), _part(0, 0), _part(0, 1)
+
+    def __init__(self, lin: np.ndarray, off: np.ndarray, ta: np.ndarray, tb: np.ndarray, n: int):
+        self._lin, self._groups = lin, ((off, (ta, tb)),)                  # [k, Wl] uint64, [k + 1] int64, [T, Wl], [T, Wl]: immutable
+        self._n = n                                    # unknowns of the system (Wl alone leaves 64 candidates)
+
+    def _coerce(self, other, what: str):
+        # (the texts are the ones each operator has always had: under ^ a form of another width is "of different lengths", and concat
+        # names the kinds it takes where ^ names the one it does not)
         if not isinstance(other, PackedQuadBitVec):
-            raise TypeError("concat needs a PackedQuadBitVec or a PackedBitVec")
+            if what == "^" and isinstance(other, PackedCubicBitVec):
+                return NotImplemented                  # (its __rxor__ says why the two do not mix)
+            if not isinstance(other, PackedBitVec):
+                raise TypeError("cannot mix packed and tuple-of-int BitVecs" if what == "^" else "concat needs a PackedQuadBitVec or a PackedBitVec")
+            other = self._from_rows(other._rows, self._n)
         if other._lin.shape[1] != self._lin.shape[1]:
-            raise ValueError("Cannot mix bitvecs over different numbers of unknowns")
-        return self._like(np.concatenate([self._lin, other._lin]), np.concatenate([self._off, other._off[1:] + self._off[-1]]),
-                          np.concatenate([self._ta, other._ta]), np.concatenate([self._tb, other._tb]))
+            raise ValueError("Cannot mix bitvecs of different lengths" if what == "^" else "Cannot mix bitvecs over different numbers of unknowns")
+        return other
 
     def evaluate(self, s: int) -> int:
         """Value under the raw point ``s`` of the LINEARISED unknowns (bit j = unknown j, the products behind the n linear ones),
@@ -442,10 +458,50 @@ class PackedQuadBitVec:
         return value
 
 
-for _name in ("__and__", "__rand__", "__or__", "__ror__", "__lshift__", "__rshift__", "__mod__", "__invert__", "lshift_ext", "rotl", "rotr",
-              "sum", "zeroext", "signext", "broadcast", "dup"):
-    setattr(PackedQuadBitVec, _name, _refuse(_name))
-del _name
+def _zeros_terms(zeros: Sequence, cls, kind: str, words: int) -> tuple:
+    """(lin [R, Wl], then per group of ``cls`` its offsets [R + 1] and its operand arrays) of all the bits of ``zeros``, in order, for a
+    system of that kind.  No row is dropped: whether a factored row is the literal 0 or the equation "1 = 0" is only known once it is
+    expanded, and the solver needs neither decided -- an all-zero row changes no pivot, origin or basis, and a row that is exactly
+    the constant 1 makes it report the system inconsistent (LinearSystem._rhs_eqs relies on the same two facts)."""
+    none = np.zeros((0, words), dtype=np.uint64)
+    one_row = np.zeros(1, dtype=np.int64)
+    lins, vecs, terms = [none], [], []                 # per entry its rows; its groups, or (linear rows) a count of no products per row
+    for z in zeros:
+        if isinstance(z, cls):
+            lin = z._lin
+            vecs.append(z._groups)
+            terms.append(z._groups)
+        elif isinstance(z, PackedBitVec):              # (no vector is made of linear rows)
+            lin = z._rows
+            terms.append(np.zeros(len(lin), dtype=np.int64))
+        elif isinstance(z, BitVec):
+            raise TypeError("cannot mix packed and tuple-of-int BitVecs")
+        elif isinstance(z, int) and z in (0, 1):       # the literal 0, or the equation "1 = 0"
+            lin = np.zeros((1, words), dtype=np.uint64)
+            lin[0, 0] = z
+            terms.append(one_row)
+        elif isinstance(z, PackedQuadBitVec):          # (given to a cubic system)
+            raise TypeError(_QUAD_MIX)
+        else:
+            raise TypeError(f"a bare equation of a packed {kind} system is 0 or 1: build the others from gens() and mul_bit")
+        if lin.shape[1] != words:
+            raise ValueError("Cannot mix bitvecs over different numbers of unknowns")
+        lins.append(lin)
+    lin = np.concatenate(lins)
+    out = [lin]
+    for g, arity in enumerate(cls._ARITIES):
+        off = np.zeros(len(lin) + 1, dtype=np.int64)
+        if not vecs:
+            cnt = terms
+        elif len(vecs) == len(terms):                  # (the usual cases, all linear and all products, without a test per entry)
+            cnt = [np.diff(v[g][0]) for v in vecs]
+        else:
+            cnt = [np.diff(t[g][0]) if type(t) is tuple else t for t in terms]
+        if cnt:
+            np.cumsum(np.concatenate(cnt), out=off[1:])
+        out.append(off)
+        out.extend(np.concatenate([none] + [v[g][1][k] for v in vecs]) for k in range(arity))
+    return tuple(out)
 
 
 class PackedQuadraticSystem(_QuadraticPoints, PackedLinearSystem):
@@ -499,37 +555,8 @@ class PackedQuadraticSystem(_QuadraticPoints, PackedLinearSystem):
 
     # -- zeros -> the factored arrays the device expands --------------------------------------------------------------------------
     def _terms(self, zeros: Sequence):
-        """(lin [R, Wl], term_off [R + 1], ta, tb) of all the bits of ``zeros``, in order.  No row is dropped: whether a factored
-        row is the literal 0 or the equation "1 = 0" is only known once it is expanded, and the solver needs neither decided -- an
-        all-zero row changes no pivot, origin or basis, and a row that is exactly the constant 1 makes it report the system
-        inconsistent (LinearSystem._rhs_eqs relies on the same two facts)."""
-        none = np.zeros((0, self._words), dtype=np.uint64)
-        lins, cnts, tas, tbs = [none], [], [none], [none]
-        for z in zeros:
-            if isinstance(z, PackedQuadBitVec):
-                lin = z._lin
-                cnts.append(np.diff(z._off))
-                tas.append(z._ta)
-                tbs.append(z._tb)
-            elif isinstance(z, PackedBitVec):
-                lin = z._rows
-                cnts.append(np.zeros(len(lin), dtype=np.int64))
-            elif isinstance(z, BitVec):
-                raise TypeError("cannot mix packed and tuple-of-int BitVecs")
-            elif isinstance(z, int) and z in (0, 1):                       # the literal 0, or the equation "1 = 0"
-                lin = np.zeros((1, self._words), dtype=np.uint64)
-                lin[0, 0] = z
-                cnts.append(np.zeros(1, dtype=np.int64))
-            else:
-                raise TypeError("a bare equation of a packed quadratic system is 0 or 1: build the others from gens() and mul_bit")
-            if lin.shape[1] != self._words:
-                raise ValueError("Cannot mix bitvecs over different numbers of unknowns")
-            lins.append(lin)
-        lin = np.concatenate(lins)
-        off = np.zeros(len(lin) + 1, dtype=np.int64)
-        if cnts:
-            np.cumsum(np.concatenate(cnts), out=off[1:])
-        return lin, off, np.concatenate(tas), np.concatenate(tbs)
+        """(lin [R, Wl], term_off [R + 1], ta, tb) of all the bits of ``zeros``, in order; no row is dropped (_zeros_terms)"""
+        return _zeros_terms(zeros, PackedQuadBitVec, "quadratic", self._words)
 
     def _stack_rows(self, zeros: Sequence):
         raise TypeError("a packed quadratic system has no rows on the host: use get_eqs, or hip.quad_expand_words on the factored arrays")
@@ -540,12 +567,7 @@ class PackedQuadraticSystem(_QuadraticPoints, PackedLinearSystem):
         lin, off, ta, tb = self._terms(zeros)
         if not len(lin):
             return []
-        mask = (1 << self._cols) - 1
-        eqs = []
-        for r in hip.quad_expand_words(lin, off, ta, tb, self._lin_size):
-            v = int.from_bytes(r.tobytes(), "little")
-            eqs.append(((v & mask) << 1) | (v >> self._cols))              # column c is bit c + 1, column cols the constant
-        return [e for e in eqs if e]                   # literal zeros carry no information
+        return _eqs_from_words(hip.quad_expand_words(lin, off, ta, tb, self._lin_size), self._cols)
 
     # -- boundary call ---------------------------------------------------------------------------------------------------------------
     def _solve_internal(self, zeros: Sequence, mode: int):
@@ -621,37 +643,7 @@ class PackedQuadraticSystem(_QuadraticPoints, PackedLinearSystem):
 # ---- cubic systems kept factored ---------------------------------------------------------------------------------------------------
 # One degree up: a symbolic bit is a linear form plus products of two affine forms plus products of three, and the rows over the
 # n + C(n,2) + C(n,3) columns of degree-3 XL come into being on the device (k_cubic_expand, through m4ri_solve_cubic_packed /
-# hip.cubic_expand_words).  The products here are the EXACT products of GF(2)[x] / (x_i^2 + x_i), constants included;
-# QuadraticSystem._mul_bit, which the quadratic classes above follow, drops the constant x linear cross terms.  That is why the two
-# kinds of vector do not mix.
-_QUAD_MIX = ("a PackedQuadBitVec cannot be mixed with a PackedCubicBitVec: the quadratic class's products follow the reference's "
-             "_mul_bit (no constant x linear cross terms), this class's are the exact products")
-
-
-def _refuse_cubic(name: str):
-    def method(self, *args, **kwargs):
-        raise TypeError(f"{name} is not supported on a PackedCubicBitVec (bits that carry products): only ^, indexing and concat are")
-    method.__name__ = name
-    return method
-
-
-def _take_terms(off: np.ndarray, ops: tuple, idx: np.ndarray):
-    """the products (offsets, operand arrays) of the bits idx[0], idx[1], ..."""
-    cnt = off[idx + 1] - off[idx]
-    new = np.zeros(len(idx) + 1, dtype=np.int64)
-    np.cumsum(cnt, out=new[1:])
-    src = np.repeat(off[idx] - new[:-1], cnt) + np.arange(new[-1])         # operand row of every kept product
-    return new, tuple(x[src] for x in ops)
-
-
-def _xor_terms(off_a: np.ndarray, ops_a: tuple, off_b: np.ndarray, ops_b: tuple):
-    """bit i of the sum owns the products of a[i], then those of b[i]"""
-    k = len(off_a) - 1
-    owner = np.concatenate([np.repeat(np.arange(k), np.diff(off_a)), np.repeat(np.arange(k), np.diff(off_b))])
-    order = np.argsort(owner, kind="stable")
-    return off_a + off_b, tuple(np.concatenate([x, y])[order] for x, y in zip(ops_a, ops_b))
-
-
+# hip.cubic_expand_words).
 def _exact_product_int(forms: tuple, n: int) -> int:
     """the exact product of two or three affine forms (equation ints over n unknowns) as an equation int over the cubic columns:
     bit 0 the constant, bit 1 + c column c of xl3_cols(n), put together from runs of consecutive columns"""
@@ -684,80 +676,36 @@ def _exact_product_int(forms: tuple, n: int) -> int:
     return e
 
 
-class PackedCubicBitVec:
-    """k symbolic bits, each a linear form (a row of ``_lin``, Wl = ceil((n + 1) / 64) words in the order of ``PackedBitVec``) plus
-    products of two affine forms (bit i owns the operand rows ``_off2[i] .. _off2[i + 1]`` of ``_ta`` / ``_tb``) plus products of
-    three (``_off3``, ``_ua`` / ``_ub`` / ``_uc``).  A product is the exact product in GF(2)[x] / (x_i^2 + x_i); equal products are
-    not cancelled here, they cancel when the rows are expanded."""
-    __slots__ = ("_lin", "_off2", "_ta", "_tb", "_off3", "_ua", "_ub", "_uc", "_n")
+class PackedCubicBitVec(_TermsBitVec):
+    """``_TermsBitVec`` with products of two affine forms (bit i owns the operand rows ``_off2[i] .. _off2[i + 1]`` of ``_ta`` /
+    ``_tb``) and products of three (``_off3``, ``_ua`` / ``_ub`` / ``_uc``).  A product is the exact product in
+    GF(2)[x] / (x_i^2 + x_i)."""
+    __slots__ = ()
+    _ARITIES = (2, 3)
+    _off2, _ta, _tb = _part(0), _part(0, 0), _part(0, 1)
+    _off3, _ua, _ub, _uc = _part(1), _part(1, 0), _part(1, 1), _part(1, 2)
 
     def __init__(self, lin, off2, ta, tb, off3, ua, ub, uc, n: int):
-        self._lin, self._off2, self._ta, self._tb = lin, off2, ta, tb      # [k, Wl] uint64, [k + 1] int64, [T2, Wl] x 2: immutable
-        self._off3, self._ua, self._ub, self._uc = off3, ua, ub, uc        # [k + 1] int64, [T3, Wl] x 3
+        # [k, Wl] uint64, then [k + 1] int64, [T2, Wl] x 2 and [k + 1] int64, [T3, Wl] x 3: immutable
+        self._lin, self._groups = lin, ((off2, (ta, tb)), (off3, (ua, ub, uc)))
         self._n = n                                    # unknowns of the system
 
-    def _linear(self, rows: np.ndarray) -> "PackedCubicBitVec":
-        """linear bits (the rows of a PackedBitVec) as a vector of this kind"""
-        none, off = self._lin[:0], np.zeros(len(rows) + 1, dtype=np.int64)
-        return PackedCubicBitVec(rows, off, none, none, off, none, none, none, self._n)
-
-    def _groups(self):
-        return (self._off2, (self._ta, self._tb)), (self._off3, (self._ua, self._ub, self._uc))
-
-    def _with(self, lin, quad, cubic) -> "PackedCubicBitVec":
-        return PackedCubicBitVec(lin, quad[0], *quad[1], cubic[0], *cubic[1], self._n)
-
     def _degree(self) -> int:
-        return 3 if len(self._ua) else 2 if len(self._ta) else 1
-
-    def __len__(self):
-        return self._lin.shape[0]
-
-    def _take(self, idx: np.ndarray) -> "PackedCubicBitVec":
-        quad, cubic = self._groups()
-        return self._with(self._lin[idx], _take_terms(*quad, idx), _take_terms(*cubic, idx))
-
-    def __getitem__(self, key):
-        n = len(self)
-        if isinstance(key, slice):
-            return self._take(np.arange(n)[key])
-        i = operator.index(key)
-        if not -n <= i < n:
-            raise IndexError("PackedCubicBitVec index out of range")
-        return self._take(np.array([i % n]))
+        (_, quad), (_, cubic) = self._groups
+        return 3 if len(cubic[0]) else 2 if len(quad[0]) else 1
 
     def _coerce(self, other, what: str) -> "PackedCubicBitVec":
-        if isinstance(other, PackedQuadBitVec):
-            raise TypeError(_QUAD_MIX)
-        if isinstance(other, PackedBitVec):
-            other = self._linear(other._rows)
         if not isinstance(other, PackedCubicBitVec):
-            if isinstance(other, BitVec):
-                raise TypeError("cannot mix packed and tuple-of-int BitVecs")
-            raise TypeError(f"{what} needs a PackedCubicBitVec or a PackedBitVec")
+            if isinstance(other, PackedQuadBitVec):
+                raise TypeError(_QUAD_MIX)
+            if not isinstance(other, PackedBitVec):
+                if isinstance(other, BitVec):
+                    raise TypeError("cannot mix packed and tuple-of-int BitVecs")
+                raise TypeError(f"{what} needs a PackedCubicBitVec or a PackedBitVec")
+            other = self._from_rows(other._rows, self._n)
         if other._lin.shape[1] != self._lin.shape[1] or other._n != self._n:
             raise ValueError("Cannot mix bitvecs over different numbers of unknowns")
         return other
-
-    def __xor__(self, other):
-        if isinstance(other, (PackedCubicBitVec, BitVec, PackedQuadBitVec)):
-            other = self._coerce(other, "^")
-            if len(other) != len(self):
-                raise ValueError("Cannot mix bitvecs of different lengths")
-            (q1, c1), (q2, c2) = self._groups(), other._groups()
-            return self._with(self._lin ^ other._lin, _xor_terms(*q1, *q2), _xor_terms(*c1, *c2))
-        lin = self._lin.copy()
-        lin[:, 0] ^= _const_bits(len(self), other)      # a constant only has the affine bit
-        return self._with(lin, *self._groups())
-
-    __rxor__ = __xor__
-    __pow__ = __xor__
-
-    def concat(self, other):
-        other = self._coerce(other, "concat")
-        cat = lambda g, h: (np.concatenate([g[0], h[0][1:] + g[0][-1]]), tuple(np.concatenate([x, y]) for x, y in zip(g[1], h[1])))  # noqa: E731
-        (q1, c1), (q2, c2) = self._groups(), other._groups()
-        return self._with(np.concatenate([self._lin, other._lin]), cat(q1, q2), cat(c1, c2))
 
     def _eq_ints(self) -> list:
         """every bit as an equation int over the cubic columns, expanded on the host a product at a time"""
@@ -778,12 +726,6 @@ class PackedCubicBitVec:
         as BitVec.evaluate gives it for the expanded bits; on the host."""
         point = ((s << 1) | 1) & ((1 << (xl3_cols(self._n) + 1)) - 1)
         return sum((bin(e & point).count("1") & 1) << k for k, e in enumerate(self._eq_ints()))
-
-
-for _name in ("__and__", "__rand__", "__or__", "__ror__", "__lshift__", "__rshift__", "__mod__", "__invert__", "lshift_ext", "rotl", "rotr",
-              "sum", "zeroext", "signext", "broadcast", "dup"):
-    setattr(PackedCubicBitVec, _name, _refuse_cubic(_name))
-del _name
 
 
 def _refuse_system(name: str):
@@ -820,53 +762,26 @@ class PackedCubicSystem(PackedLinearSystem):
         rows = a._rows if isinstance(a, PackedBitVec) else a._lin
         if rows.shape[1] != self._words:
             raise ValueError("Cannot mix bitvecs over different numbers of unknowns")
-        if isinstance(a, PackedBitVec):
-            none, off = rows[:0], np.zeros(2, dtype=np.int64)
-            return PackedCubicBitVec(rows, off, none, none, off, none, none, none, self._lin_size)
-        return a
+        return PackedCubicBitVec._from_rows(rows, self._lin_size) if isinstance(a, PackedBitVec) else a
 
     def mul_bit(self, a, b) -> PackedCubicBitVec:
         """the exact product of two single bits whose degrees (structural: a bit has cubic terms, or quadratic ones, or neither) add up
         to 3 at most.  By distributivity lin_a lin_b is one quadratic term and (ta tb) lin_b one cubic term per product of a."""
         a, b = self._single(a), self._single(b)
-        if a._degree() + b._degree() > 3:
-            raise TypeError(f"mul_bit of bits of degree {a._degree()} and {b._degree()} is of degree {a._degree() + b._degree()}, above 3")
-        if a._degree() < b._degree():
+        da, db = a._degree(), b._degree()
+        if da + db > 3:
+            raise TypeError(f"mul_bit of bits of degree {da} and {db} is of degree {da + db}, above 3")
+        if da < db:
             a, b = b, a                                # (b is linear now)
-        k = len(a._ta)
+        ta, tb = a._groups[0][1]
+        k = len(ta)
         return PackedCubicBitVec(np.zeros((1, self._words), dtype=np.uint64), np.array([0, 1], dtype=np.int64), a._lin, b._lin,
-                                 np.array([0, k], dtype=np.int64), a._ta, a._tb, np.repeat(b._lin, k, axis=0), self._lin_size)
+                                 np.array([0, k], dtype=np.int64), ta, tb, np.repeat(b._lin, k, axis=0), self._lin_size)
 
     # -- zeros -> the factored arrays the device expands ----------------------------------------------------------------------------
     def _terms(self, zeros: Sequence):
-        """(lin, off2, ta, tb, off3, ua, ub, uc) of all the bits of ``zeros``, in order; no row is dropped (PackedQuadraticSystem._terms)"""
-        none = np.zeros((0, self._words), dtype=np.uint64)
-        acc = none[:0]
-        vec = PackedCubicBitVec(acc, np.zeros(1, dtype=np.int64), none, none, np.zeros(1, dtype=np.int64), none, none, none, self._lin_size)
-        parts = []
-        for z in zeros:
-            if isinstance(z, PackedQuadBitVec):
-                raise TypeError(_QUAD_MIX)
-            if isinstance(z, PackedBitVec):
-                z = vec._linear(z._rows)
-            elif isinstance(z, BitVec):
-                raise TypeError("cannot mix packed and tuple-of-int BitVecs")
-            elif isinstance(z, int) and z in (0, 1):                       # the literal 0, or the equation "1 = 0"
-                lin = np.zeros((1, self._words), dtype=np.uint64)
-                lin[0, 0] = z
-                z = vec._linear(lin)
-            elif not isinstance(z, PackedCubicBitVec):
-                raise TypeError("a bare equation of a packed cubic system is 0 or 1: build the others from gens() and mul_bit")
-            if z._lin.shape[1] != self._words:
-                raise ValueError("Cannot mix bitvecs over different numbers of unknowns")
-            parts.append(z)
-        cnt = lambda name: np.concatenate([np.zeros(0, dtype=np.int64)] + [np.diff(getattr(z, name)) for z in parts])      # noqa: E731
-        cat = lambda name: np.concatenate([none] + [getattr(z, name) for z in parts])                                       # noqa: E731
-        lin = cat("_lin")
-        off2, off3 = np.zeros(len(lin) + 1, dtype=np.int64), np.zeros(len(lin) + 1, dtype=np.int64)
-        np.cumsum(cnt("_off2"), out=off2[1:])
-        np.cumsum(cnt("_off3"), out=off3[1:])
-        return lin, off2, cat("_ta"), cat("_tb"), off3, cat("_ua"), cat("_ub"), cat("_uc")
+        """(lin, off2, ta, tb, off3, ua, ub, uc) of all the bits of ``zeros``, in order; no row is dropped (_zeros_terms)"""
+        return _zeros_terms(zeros, PackedCubicBitVec, "cubic", self._words)
 
     def get_eqs(self, zeros: Sequence) -> list:
         """equation ints over the cubic columns, expanded on the device (needs the GPU); zero rows are dropped"""
@@ -874,12 +789,7 @@ class PackedCubicSystem(PackedLinearSystem):
         terms = self._terms(zeros)
         if not len(terms[0]):
             return []
-        mask = (1 << self._cols) - 1
-        eqs = []
-        for r in hip.cubic_expand_words(*terms, self._lin_size):
-            v = int.from_bytes(r.tobytes(), "little")
-            eqs.append(((v & mask) << 1) | (v >> self._cols))              # column c is bit c + 1, column cols the constant
-        return [e for e in eqs if e]
+        return _eqs_from_words(hip.cubic_expand_words(*terms, self._lin_size), self._cols)
 
     # -- boundary call ---------------------------------------------------------------------------------------------------------------
     def _solve_internal(self, zeros: Sequence, mode: int):
@@ -919,19 +829,7 @@ class PackedCubicSystem(PackedLinearSystem):
 
     def solve_all_xl4(self, zeros: Sequence, *, max_dimension: int = 16):
         """solve_all through degree-4 XL: the consistent points of the quartic system's solution space, in AffineSpace order"""
-        space = self.solve_raw_space_xl4(zeros)
-        if space is None:
-            return
-        if space.dimension > max_dimension:
-            raise DimensionTooLargeError(
-                f"Solution space (dim {space.dimension}) is too large, try increase max_dimension "
-                f"({max_dimension}) if you want (there will be 2**dim solutions)",
-                space=space,
-            )
-        for raw in space:
-            sol = self.convert_sol_xl4(raw)
-            if sol is not None:
-                yield sol
+        yield from _space_points(self.solve_raw_space_xl4(zeros), max_dimension, self.convert_sol_xl4)
 
     def solve_one_xl4(self, zeros: Sequence):
         for sol in self.solve_all_xl4(zeros):
@@ -945,13 +843,7 @@ class PackedCubicSystem(PackedLinearSystem):
         terms = self._terms(zeros)
         if not len(terms[0]):
             return []
-        cols4 = xl4_cols(self._lin_size)
-        mask = (1 << cols4) - 1
-        eqs = []
-        for r in hip.xl4_cubic_expand_words(hip.cubic_expand_words(*terms, self._lin_size), self._lin_size):
-            v = int.from_bytes(r.tobytes(), "little")
-            eqs.append(((v & mask) << 1) | (v >> cols4))                   # column c is bit c + 1, column cols4 the constant
-        return [e for e in eqs if e]
+        return _eqs_from_words(hip.xl4_cubic_expand_words(hip.cubic_expand_words(*terms, self._lin_size), self._lin_size), xl4_cols(self._lin_size))
 
     def _raw_point(self, lin: int) -> int:
         """the raw point over the cubic columns whose linear part is ``lin``"""
@@ -962,10 +854,7 @@ class PackedCubicSystem(PackedLinearSystem):
         return int.from_bytes(np.packbits(bits, bitorder="little").tobytes(), "little")
 
     def evaluate(self, bv, sol: tuple) -> int:
-        raw, shift = 0, 0
-        for value, width in zip(sol, self._sizes):
-            raw |= value << shift
-            shift += width
+        raw = _raw_value(sol, self._sizes)
         return bv.evaluate(self._raw_point(raw) if isinstance(bv, PackedCubicBitVec) else raw)
 
 

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from gf2bv_amd import BitVec, DimensionTooLargeError, PackedCubicBitVec, PackedCubicSystem, PackedQuadraticSystem, hip
+from gf2bv_amd import _internal
 from gf2bv_amd._internal import m4ri_solve_cubic_packed
 from gf2bv_amd.linsys import xl3_cols
 from oracle import gf2_oracle as O
@@ -259,6 +260,79 @@ def test_entries_check_arguments_before_device_use():
         M(lin, off2, ta, tb, off3, ua, ub, uc, n, 128, 1)
     with pytest.raises(TypeError):
         M(lin, off2, ta, tb, off3, ua, ub, uc, n, rows)
+
+
+# The factored-form parser of the extension, per entry and per group of products: (name, number of buffers, arguments behind them).
+# n_lin = 3 (one word a form), two rows, one product per group; rows = the columns, so nothing but the buffers is wrong.
+_TERM_ENTRIES = [("m4ri_solve_quad_packed", 4, (3, 6, 0)), ("m4ri_factor_quad_packed", 4, (3, 6, 0)), ("m4ri_solve_rhs_quad_packed", 4, (3, 6, 0, [0])),
+                 ("m4ri_solve_many_quad_packed", 4, (np.array([0, 2], dtype=np.int64), 3, 6, 0)),
+                 ("m4ri_solve_xl3_quad_packed", 4, (3, 0)), ("m4ri_solve_xl4_quad_packed", 4, (3, 0)),
+                 ("m4ri_solve_xl3_guess_quad_packed", 4, (3, [0], 0, 2, 0)), ("m4ri_solve_xl4_guess_quad_packed", 4, (3, [0], 0, 2, 0)),
+                 ("m4ri_solve_cubic_packed", 8, (3, 7, 0)), ("m4ri_solve_xl4_cubic_packed", 8, (3, 0))]
+_QUAD_WORDS = {"len": "term_off must hold one int64 per row of lin and one more", "start": "term_off must start at 0",
+               "order": "term_off must not decrease", "end": "term_off must end at the number of operands in ta",
+               "ops": "ta and tb must hold the same number of whole operands",
+               "ops and start": "ta and tb must hold the same number of whole operands"}       # (the operands are looked at first)
+_CUBIC_WORDS = {"len": "off2 and off3 must hold one int64 per row of lin and one more", "start": "off2 and off3 must start at 0",
+                "order": "off2 and off3 must not decrease", "end": "off2 and off3 must end at the number of operands of their products",
+                "ops": "the operands of a product must hold the same number of whole forms",
+                "ops and start": "off2 and off3 must start at 0"}                               # (the offsets are looked at first)
+
+
+@pytest.mark.parametrize("entry, nbuf, tail, group", [(e, k, t, g) for e, k, t in _TERM_ENTRIES for g in range(k // 4)])
+def test_term_parser_messages_per_entry_and_group(entry, nbuf, tail, group):
+    """every refusal of the factored-form parser, word for word, before any device use"""
+    f = getattr(_internal, entry)
+    one = np.ones((1, 1), dtype=np.uint64)
+    off = np.array([0, 1, 1], dtype=np.int64)
+    good = [np.zeros((2, 1), dtype=np.uint64), off, one, one] + ([off, one, one, one] if nbuf == 8 else [])
+    off_at, last_op = (1, 3) if group == 0 else (4, 7)
+    words = _QUAD_WORDS if nbuf == 4 else _CUBIC_WORDS
+
+    def refused(text, **swap):
+        bufs = list(good)
+        for k, v in swap.items():
+            bufs[int(k[1:])] = v
+        with pytest.raises(ValueError) as e:
+            f(*bufs, *tail)
+        assert str(e.value) == text
+
+    two = np.ones((2, 1), dtype=np.uint64)
+    refused("lin must hold whole rows of ceil((n_lin + 1) / 64) 64-bit words", b0=good[0].tobytes()[:-4])
+    refused(words["len"], **{f"b{off_at}": off[:-1].copy()})
+    refused(words["start"], **{f"b{off_at}": np.array([1, 1, 1], dtype=np.int64)})
+    refused(words["order"], **{f"b{off_at}": np.array([0, 2, 1], dtype=np.int64)})
+    refused(words["end"], **{f"b{off_at}": np.array([0, 1, 2], dtype=np.int64)})
+    refused(words["ops"], **{f"b{last_op}": two})
+    refused(words["ops and start"], **{f"b{last_op}": two, f"b{off_at}": np.array([1, 1, 1], dtype=np.int64)})
+
+
+def _same_arrays(got, want):
+    assert len(got) == len(want)
+    for g, (dtype, values) in zip(got, want):
+        w = np.array(values, dtype=dtype).reshape((len(values), 1) if dtype is np.uint64 else (len(values),))
+        assert g.dtype == w.dtype and g.shape == w.shape and g.flags.c_contiguous and np.array_equal(g, w), (g, w)
+
+
+def test_terms_layout_is_the_recorded_one():
+    """``_terms`` of both systems on a literal 0, a literal 1, a sliced PackedBitVec, a vector with products and a concat of linear
+    and product bits, n = 5: unknown i is bit 1 + i of the one word of a form, the expected arrays written down by hand"""
+    U, I = np.uint64, np.int64
+    p = PackedQuadraticSystem([5])
+    (x,) = p.gens()
+    q = p.mul_bit(x[0], x[1]) ^ x[2] ^ 1                                  # 1 + x2 + x0 x1
+    w = p.mul_bit(x[3], x[4]) ^ p.mul_bit(x[0], x[2])                      # x3 x4 + x0 x2
+    _same_arrays(p._terms([0, 1, x[1:3], q, x[4:5].concat(w)]),
+                 [(U, [0, 1, 4, 8, 9, 32, 0]), (I, [0, 0, 0, 0, 0, 1, 1, 3]), (U, [2, 16, 2]), (U, [4, 32, 8])])
+    _same_arrays(p._terms([]), [(U, []), (I, [0]), (U, []), (U, [])])
+    c = PackedCubicSystem([5])
+    (y,) = c.gens()
+    q = c.mul_bit(y[0], y[1]) ^ y[2] ^ 1                                  # 1 + x2 + x0 x1
+    t = c.mul_bit(c.mul_bit(y[0], y[1]), y[3])                             # (0 + x0 x1) x3 = 0 * x3 + x0 x1 x3
+    _same_arrays(c._terms([0, 1, y[1:3], q, y[4:5].concat(t ^ q)]),
+                 [(U, [0, 1, 4, 8, 9, 32, 9]), (I, [0, 0, 0, 0, 0, 1, 1, 3]), (U, [2, 0, 2]), (U, [4, 16, 4]),
+                  (I, [0, 0, 0, 0, 0, 0, 0, 1]), (U, [2]), (U, [4]), (U, [16])])
+    _same_arrays(c._terms([]), [(U, []), (I, [0]), (U, []), (U, []), (I, [0]), (U, []), (U, []), (U, [])])
 
 
 def test_pickle_round_trip():

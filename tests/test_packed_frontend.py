@@ -133,3 +133,30 @@ def test_get_rows_returns_an_array_of_its_own():
     keep = r1.copy()
     r2 = pk.get_rows([x ^ 0xFFFF])
     assert (r1 == keep).all() and not (r1 == r2).all()
+
+
+# The public surface of the five system classes: every name must stay, and none may appear.
+_BOTH = """convert_sol evaluate factor gens get_eqs solve_all solve_one solve_one_rhs solve_raw_one solve_raw_one_rhs solve_raw_space
+    solve_raw_space_rhs"""
+_MANY = "solve_one_many solve_raw_one_many solve_raw_space_many"
+_QUADRATIC = """bit_assert convert_sol_xl convert_sol_xl4 convert_sol_xl4_guess convert_sol_xl_guess get_eqs_xl get_eqs_xl4 mul_bit search_all
+    search_one solve_all_xl solve_all_xl4 solve_all_xl4_guess solve_all_xl_guess solve_one_xl solve_one_xl4 solve_one_xl4_guess solve_one_xl_guess
+    solve_raw_one_xl solve_raw_one_xl4 solve_raw_one_xl4_guess solve_raw_one_xl_guess solve_raw_space_xl solve_raw_space_xl4
+    solve_raw_space_xl4_guess solve_raw_space_xl_guess"""
+_PUBLIC = {
+    "LinearSystem": f"{_BOTH} {_MANY} get_sage_mat get_sage_mat_slow",
+    "QuadraticSystem": f"{_BOTH} {_MANY} get_sage_mat get_sage_mat_slow {_QUADRATIC}",
+    "PackedLinearSystem": f"{_BOTH} get_rows",
+    "PackedQuadraticSystem": f"{_BOTH} {_MANY} get_rows {_QUADRATIC}",
+    "PackedCubicSystem": f"""{_BOTH} get_rows bit_assert mul_bit convert_sol_xl4 get_eqs_xl4 solve_all_xl4 solve_one_xl4 solve_raw_one_xl4
+        solve_raw_space_xl4""",
+}
+
+
+@pytest.mark.parametrize("name", sorted(_PUBLIC))
+def test_public_names_of_the_system_classes(name):
+    import gf2bv_amd
+    cls = getattr(gf2bv_amd, name)
+    assert sorted(n for n in dir(cls) if not n.startswith("_")) == sorted(_PUBLIC[name].split())
+    # a packed system is no LinearSystem: its batch, right-hand-side and Sage methods read equation ints
+    assert issubclass(cls, LinearSystem) == (name in ("LinearSystem", "QuadraticSystem"))
