@@ -1247,6 +1247,25 @@ template <int D> PyObject *py_m4ri_solve_xl_guess_quad_packed(PyObject *, PyObje
 	});
 }
 
+// m4ri_solve_xl4_guess_cubic_packed(lin, off2, ta, tb, off3, ua, ub, uc, n_lin, guess, a0, na, mode[, device]) -> list of None | int |
+// AffineSpace over the quartic columns of the n_lin - len(guess) remaining unknowns, element s for assignment a0 + s: hybrid degree-4
+// XL on m4ri_solve_cubic_packed's arrays (every row live), expanded, specialised, multiplied and solved on the device as one batch
+// (gf2bv_solve_xl4_cubic_guess_terms; gf2bv_hip.h, "hybrid degree-4 XL on cubic equations")
+PyObject *py_m4ri_solve_xl4_guess_cubic_packed(PyObject *, PyObject *const *args, Py_ssize_t nargs)
+{
+	int device;
+	if (!entry_device("m4ri_solve_xl4_guess_cubic_packed", 13, args, nargs, &device)) return nullptr;
+	long mode;
+	GuessArgs ga;
+	TermBuffers cb(CUBIC_TERMS);
+	if (!parse_mode(args[12], &mode) || !ga.parse(args[9], args[10], args[11]) || !cb.parse(args, args[8])) return nullptr;
+	if (ga.na == 0) return PyList_New(0);
+	return collect_results(ga.na, mode, device, [&](gf2bv_result **out) {
+		return gf2bv_solve_xl4_cubic_guess_terms(cb.words(0), cb.offsets(1), cb.words(2), cb.words(3), cb.offsets(4), cb.words(5), cb.words(6),
+		                                         cb.words(7), cb.live, cb.n, ga.g.data(), (int64_t)ga.g.size(), ga.a0, ga.na, (int)mode, device, out);
+	});
+}
+
 // ---- the packed front-ends in front of the kept factorization, the shared elimination and the batch --------------------------
 // m4ri_factor_packed(buffer, rows, words, cols, mode[, device]) -> Factorization: m4ri_factor on m4ri_solve_packed's buffer
 // (gf2bv_factor_digits, 32 payload bits per digit)
@@ -1858,6 +1877,8 @@ PyMethodDef module_methods[] = {
 	 "m4ri_solve_xl4(equations, n_lin, mode, device=None)\n--\n\nDegree-4 XL: m4ri_solve_xl3 with the products by every pair of unknowns too, solved over the monomials of degree <= 4."},
 	{"m4ri_solve_xl4_quad_packed", FAST(py_m4ri_solve_xl_quad_packed<4>), METH_FASTCALL,
 	 "m4ri_solve_xl4_quad_packed(lin, term_off, ta, tb, n_lin, mode, device=None)\n--\n\nm4ri_solve_xl4 on a quadratic system kept factored."},
+	{"m4ri_solve_xl4_guess_cubic_packed", FAST(py_m4ri_solve_xl4_guess_cubic_packed), METH_FASTCALL,
+	 "m4ri_solve_xl4_guess_cubic_packed(lin, off2, ta, tb, off3, ua, ub, uc, n_lin, guess, a0, na, mode, device=None)\n--\n\nHybrid degree-4 XL on a cubic system kept factored: the guessed unknowns substituted for the assignments a0 .. a0 + na - 1 and every assignment's system solved on the GPU as one batch."},
 	{"m4ri_solve_xl4_guess", FAST(py_m4ri_solve_xl_guess<4>), METH_FASTCALL,
 	 "m4ri_solve_xl4_guess(equations, n_lin, guess, a0, na, mode, device=None)\n--\n\nHybrid XL at degree 4: m4ri_solve_xl3_guess with every assignment's degree-4 XL system."},
 	{"m4ri_solve_xl4_guess_quad_packed", FAST(py_m4ri_solve_xl_guess_quad_packed<4>), METH_FASTCALL,

@@ -5450,3 +5450,150 @@ k_xl4_cubic_expand(const u64 *__restrict__ cubic, i64 m, i64 cubic_stride, int n
 {
 	xl_span_rows<3>(cubic, m, cubic_stride, n, W3, rows, out, stride);
 }
+
+// The batched instance (gf2bv_xl4_cubic_expand_batch_device): blockIdx.y = system, strides and checks as for k_xl3_expand_batch
+__global__ void __launch_bounds__(256)
+k_xl4_cubic_expand_batch(const u64 *__restrict__ cubic, i64 cubic_sys_stride, i64 m, i64 cubic_stride, int n, int W3, i64 rows,
+                         u64 *__restrict__ out, i64 stride, i64 sys_stride)
+{
+	xl_span_rows<3>(cubic + (i64)blockIdx.y * cubic_sys_stride, m, cubic_stride, n, W3, rows, out + (i64)blockIdx.y * sys_stride, stride);
+}
+
+
+// ==========================================================================================
+// HYBRID XL ON CUBIC ROWS: guessed unknowns substituted into the cubic rows, one specialised system per assignment
+// ==========================================================================================
+// (host side: gf2bv_cubic_specialise_device in gf2_solver.hip)
+//
+// k_quad_specialise one degree up.  Source: m cubic rows over n unknowns as k_cubic_expand writes them (constant at cols3).  Guess,
+// assignments and R as there.  With l, q, t the source's linear, pair and triple coefficients taken over unordered sets, assignment
+// a's row over n' unknowns:
+//   triple (i', j', k')   t' = t(R[i'], R[j'], R[k'])                                                -- the same for every assignment
+//   pair (i', j')         q' = q(R[i'], R[j']) ^ XOR_{u in a} t(R[i'], R[j'], g_u)
+//   unknown i'            l' = l(R[i']) ^ XOR_{u in a} q(R[i'], g_u) ^ XOR_{u < v in a} t(R[i'], g_u, g_v)
+//   constant              c' = c ^ XOR_{u in a} l(g_u) ^ XOR_{u < v in a} q(g_u, g_v) ^ XOR_{u < v < w in a} t(g_u, g_v, g_w)
+// in the degree-3 column layout of n' unknowns.  System s = a - a0 gets its m rows `out_stride` words apart at out + s x sys_stride.
+// Work split as in k_quad_specialise: a workgroup takes one source row at a time (grid x strides over the rows) and a contiguous
+// share of the assignments (grid y).  It holds in LDS the source row, the row of assignment 0 (`base`: every column renumbered, formed
+// once, a lane per column and a ballot per word), per guess u the vector V_u over the first cols2' columns (linear column i':
+// q(R[i'], g_u); pair column (i', j'): t(R[i'], R[j'], g_u)), per pair of guesses v < u the vector P_uv over the n' linear columns
+// (t(R[i'], g_u, g_v)), and the constants' bits: K1 (bit u: l(g_u)), K2_u (bit v < u: q(g_u, g_v)), K3_uv (bit w < v: t(g_u, g_v, g_w)).
+// An assignment's word is base ^ the vectors a selects: only the words below cols2' and the constant's word differ from base.  Every
+// output word has one writer, there are no atomics, two consecutive words go out as 16 bytes from consecutive lanes where the strides
+// are even and the output is 16-byte aligned (one word at a time otherwise), and everything behind column cols3' up to the stride is
+// written as zero.  No bit behind the source's constant column is read.
+// LDS (dynamic): W3 + W3' + f Wp + C(f,2) (Wv + 1) + 1 + f words and n' ints, Wp = ceil(cols2' / 64), Wv = ceil(n' / 64); the host
+// entry keeps it within 64 KiB.
+__device__ __forceinline__ i64 xl_t3(i64 cols2, i64 x, i64 y, i64 z)       // column of x_x x_y x_z (distinct)
+{
+	i64 s;
+	if (x < y) { s = x; x = y; y = s; }
+	if (y < z) { s = y; y = z; z = s; }
+	if (x < y) { s = x; x = y; y = s; }
+	return cols2 + xl_c3(x) + xl_c2(y) + z;
+}
+
+__global__ void __launch_bounds__(256)
+k_cubic_specialise(const u64 *__restrict__ cubic, i64 m, i64 cubic_stride, int n, int W3, SpecGuess guess, int f, i64 a0, i64 na,
+                   u64 *__restrict__ out, i64 out_stride, i64 sys_stride, int vec)
+{
+	extern __shared__ u64 sp_lds[];                    // [src: W3 | base: W3s | V: f x Wp | P: C(f,2) x Wv | K1 | K2: f | K3: C(f,2) | R: n' ints]
+	const int ns = n - f, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+	const i64 cols2 = (i64)n + xl_c2(n), cols3 = cols2 + xl_c3(n), cols2s = (i64)ns + xl_c2(ns), cols3s = cols2s + xl_c3(ns);
+	const int W3s = (int)((cols3s + 1 + 63) >> 6), Wp = (int)((cols2s + 63) >> 6), Wv = (ns + 63) >> 6, npair = f * (f - 1) / 2;
+	u64 *src = sp_lds, *base = src + W3, *V = base + W3s, *P = V + (i64)f * Wp, *K1 = P + (i64)npair * Wv, *K2 = K1 + 1, *K3 = K2 + f;
+	int *R = reinterpret_cast<int *>(K3 + npair);
+	for (int u = threadIdx.x; u < n; u += blockDim.x) {            // R: unknown u is remaining number u - #(guesses below it)
+		int below = 0;
+		bool guessed = false;
+		for (int t = 0; t < f; t++) { below += guess.g[t] < u; guessed |= guess.g[t] == u; }
+		if (!guessed) R[u - below] = u;
+	}
+	const i64 span = (na + gridDim.y - 1) / gridDim.y;             // this workgroup's assignments: systems s0 .. s1 - 1
+	const i64 s0 = (i64)blockIdx.y * span, s1 = s0 + span < na ? s0 + span : na;
+	const u64 cmask = 1ull << (cols3s & 63);
+	const int cword = (int)(cols3s >> 6);
+	const int nV = f * Wp, nP = npair * Wv, nK = 1 + f + npair;
+	for (i64 r = blockIdx.x; r < m; r += gridDim.x) {
+		__syncthreads();                               // R is there; the row before has been read
+		for (int w = threadIdx.x; w < W3; w += blockDim.x) src[w] = cubic[r * cubic_stride + w];
+		__syncthreads();
+		for (int w = wave; w < W3s; w += nwaves) {     // base: column c of the specialised row from its source column
+			const i64 c = 64 * (i64)w + lane;
+			i64 sc = -1;
+			if (c < ns) sc = R[c];
+			else if (c < cols2s) {
+				const i64 p = c - ns, i = xl_tri_root(p), j = p - xl_c2(i);
+				sc = n + xl_c2(R[i]) + R[j];
+			} else if (c < cols3s) {
+				const i64 p = c - cols2s, i = xl_tet_root(p), q = p - xl_c3(i), j = xl_tri_root(q), l = q - xl_c2(j);
+				sc = cols2 + xl_c3(R[i]) + xl_c2(R[j]) + R[l];
+			} else if (c == cols3s) sc = cols3;
+			const u64 word = __ballot(sc >= 0 && xl_bit(src, sc));
+			if (lane == 0) base[w] = word;
+		}
+		for (int e = wave; e < nV + nP + nK; e += nwaves) {            // the vectors and the constants' bits (V onwards is one array)
+			i64 sc = -1;
+			if (e < nV) {                                  // V_u, word w
+				const int u = e / Wp, w = e - u * Wp, g = guess.g[u];
+				const i64 c = 64 * (i64)w + lane;
+				if (c < ns) sc = xl_q(n, R[c], g);
+				else if (c < cols2s) {
+					const i64 p = c - ns, i = xl_tri_root(p), j = p - xl_c2(i);
+					sc = xl_t3(cols2, R[i], R[j], g);
+				}
+			} else if (e < nV + nP) {                      // P_uv, v < u, word w
+				const int pi = (e - nV) / Wv, w = (e - nV) - pi * Wv, u = (int)xl_tri_root(pi), v = pi - (int)xl_c2(u);
+				const int i = 64 * w + lane;
+				if (i < ns) sc = xl_t3(cols2, R[i], guess.g[u], guess.g[v]);
+			} else if (e == nV + nP) {                     // K1
+				if (lane < f) sc = guess.g[lane];
+			} else if (e <= nV + nP + f) {                 // K2_u
+				const int u = e - nV - nP - 1;
+				if (lane < u) sc = xl_q(n, guess.g[u], guess.g[lane]);
+			} else {                                       // K3_uv
+				const int pi = e - nV - nP - 1 - f, u = (int)xl_tri_root(pi), v = pi - (int)xl_c2(u);
+				if (lane < v) sc = xl_t3(cols2, guess.g[u], guess.g[v], guess.g[lane]);
+			}
+			const u64 word = __ballot(sc >= 0 && xl_bit(src, sc));
+			if (lane == 0) V[e] = word;
+		}
+		__syncthreads();
+		// word w of assignment a
+		auto word_of = [&](i64 a, i64 w) -> u64 {
+			if (w >= W3s) return 0;
+			u64 acc = base[w];
+			const bool kw = w == cword;
+			if (w < Wp || kw) {
+				const unsigned bits = (unsigned)a;
+				unsigned par = kw ? (unsigned)__popc((unsigned)K1[0] & bits) : 0;
+				for (unsigned rest = bits; rest; rest &= rest - 1) {
+					const int u = __ffs(rest) - 1;
+					if (w < Wp) acc ^= V[(i64)u * Wp + w];
+					if (w < Wv || kw) {
+						if (kw) par ^= (unsigned)__popc((unsigned)K2[u] & bits);
+						for (unsigned lower = bits & ((1u << u) - 1); lower; lower &= lower - 1) {
+							const int pi = u * (u - 1) / 2 + __ffs(lower) - 1;
+							if (w < Wv) acc ^= P[(i64)pi * Wv + w];
+							if (kw) par ^= (unsigned)__popc((unsigned)K3[pi] & bits);
+						}
+					}
+				}
+				if (par & 1) acc ^= cmask;
+			}
+			return acc;
+		};
+		if (vec) {
+			const i64 np = out_stride >> 1;
+			for (i64 idx = threadIdx.x; idx < (s1 - s0) * np; idx += blockDim.x) {
+				const i64 s = s0 + idx / np, p = idx % np;
+				reinterpret_cast<ulonglong2 *>(out + s * sys_stride + r * out_stride)[p] = make_ulonglong2(word_of(a0 + s, 2 * p), word_of(a0 + s, 2 * p + 1));
+			}
+		} else {
+			for (i64 idx = threadIdx.x; idx < (s1 - s0) * out_stride; idx += blockDim.x) {
+				const i64 s = s0 + idx / out_stride, w = idx % out_stride;
+				out[s * sys_stride + r * out_stride + w] = word_of(a0 + s, w);
+			}
+		}
+	}
+}

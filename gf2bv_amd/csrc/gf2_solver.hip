@@ -4896,13 +4896,17 @@ int enqueue_xl_expand_batch(const XlShape &x, const u64 *d_quad, i64 quad_sys_st
 {
 	if (x.rows == 0 || nsys == 0) return GF2BV_OK;
 	const unsigned block = expand_block(stride);
-	// degree 3: contiguous spans of rows per workgroup, a few thousand workgroups in all where the systems are many
+	// degree 3 and cubic rows: contiguous spans of rows per workgroup, a few thousand workgroups in all where the systems are many
 	const int parts = xl4_parts(x, nsys);
-	const unsigned gx = x.degree == 4 ? (unsigned)std::min<i64>(std::max<i64>(x.m * parts, std::min<i64>(x.rows - x.live(), 256)), 1 << 20)
-	                                  : (unsigned)std::min<i64>(x.rows, std::max<i64>(256, 256 * 16 / nsys));
+	const bool units = x.degree == 4 && x.src == 2;
+	const unsigned gx = units ? (unsigned)std::min<i64>(std::max<i64>(x.m * parts, std::min<i64>(x.rows - x.live(), 256)), 1 << 20)
+	                          : (unsigned)std::min<i64>(x.rows, std::max<i64>(256, 256 * 16 / nsys));
 	for (i64 s0 = 0; s0 < nsys; s0 += 65535) {         // (grid y holds 65535 systems)
 		const unsigned ns = (unsigned)std::min<i64>(65535, nsys - s0);
-		if (x.degree == 4)
+		if (x.src == 3)
+			hipLaunchKernelGGL(k_xl4_cubic_expand_batch, dim3(gx, ns), dim3(block), sizeof(u64) * (size_t)x.wsrc(), st, d_quad + s0 * quad_sys_stride,
+			                   quad_sys_stride, x.m, quad_stride, (int)x.n, (int)x.wsrc(), x.rows, d_aug + s0 * sys_stride, stride, sys_stride);
+		else if (x.degree == 4)
 			hipLaunchKernelGGL(k_xl4_expand_batch, dim3(gx, ns), dim3(block), sizeof(u64) * (size_t)x.w2(), st, d_quad + s0 * quad_sys_stride,
 			                   quad_sys_stride, x.m, quad_stride, (int)x.n, (int)x.w2(), x.rows, parts, d_aug + s0 * sys_stride, stride, sys_stride);
 		else
@@ -4913,22 +4917,32 @@ int enqueue_xl_expand_batch(const XlShape &x, const u64 *d_quad, i64 quad_sys_st
 	return GF2BV_OK;
 }
 
-// Hybrid XL (k_quad_specialise): f guessed unknowns substituted into m quadratic rows over n unknowns, for the assignments
-// a0 .. a0 + na - 1; every assignment leaves the system `x` of m rows over n - f unknowns
+// Hybrid XL (k_quad_specialise, k_cubic_specialise): f guessed unknowns substituted into m rows of degree `src` over n unknowns, for
+// the assignments a0 .. a0 + na - 1; every assignment leaves the system `x` of m rows of that degree over n - f unknowns
 struct GuessShape {
 	i64 m, n, f, a0, na;
+	int src;                           // the degree of the source rows
 	SpecGuess g{};
 	XlShape x;                         // (check_guess fills m and n; the degree matters to the solve entries only)
-	GuessShape(i64 m, i64 n_lin, i64 nguess, i64 a0, i64 na, int degree = 3) : m(m), n(n_lin), f(nguess), a0(a0), na(na), x(degree, 2, 0, 0) {}
-	i64 w2() const { return (n + n * (n - 1) / 2 + 1 + 63) / 64; }
-	i64 lds_bytes() const { return 8 * (w2() + x.w2() + f * ((x.n + 63) / 64 + 2)) + 4 * x.n; }
+	GuessShape(i64 m, i64 n_lin, i64 nguess, i64 a0, i64 na, int degree = 3, int src = 2)
+		: m(m), n(n_lin), f(nguess), a0(a0), na(na), src(src), x(degree, src, 0, 0) {}
+	i64 cols() const { return n + n * (n - 1) / 2 + (src == 3 ? n * (n - 1) * (n - 2) / 6 : 0); }      // the source's columns
+	i64 wsrc() const { return (cols() + 1 + 63) / 64; }                // words of a source row
+	i64 lds_bytes() const                                              // what the source's kernel holds (see there)
+	{
+		const i64 wv = (x.n + 63) / 64;
+		if (src == 3) return 8 * (wsrc() + x.wsrc() + f * ((x.cols2() + 63) / 64) + f * (f - 1) / 2 * (wv + 1) + 1 + f) + 4 * x.n;
+		return 8 * (wsrc() + x.w2() + f * (wv + 2)) + 4 * x.n;
+	}
 };
 
 // The guess, the range of assignments and the source stride; no device pointer is looked at
 int check_guess(GuessShape &s, const int32_t *guess, i64 quad_stride)
 {
-	if (s.n < 1 || s.n > 65535 || s.n + s.n * (s.n - 1) / 2 >= (1ll << 31) - 64)
-		return fail(GF2BV_ERR_ARG, "n_lin must be at least 1 and n_lin + C(n_lin,2) below 2^31 - 64");
+	const bool cubic = s.src == 3;
+	if (s.n < 1 || s.n > 65535 || s.cols() >= (1ll << 31) - 64)
+		return fail(GF2BV_ERR_ARG, cubic ? "n_lin must be at least 1 and n_lin + C(n_lin,2) + C(n_lin,3) below 2^31 - 64"
+		                                 : "n_lin must be at least 1 and n_lin + C(n_lin,2) below 2^31 - 64");
 	if (s.f < 0 || s.f > std::min<i64>(s.n - 1, 30)) return fail(GF2BV_ERR_ARG, "nguess must be 0 .. min(n_lin - 1, 30)");
 	if (!guess && s.f > 0) return fail(GF2BV_ERR_ARG, "null pointer");
 	for (i64 t = 0; t < s.f; t++) {
@@ -4942,36 +4956,40 @@ int check_guess(GuessShape &s, const int32_t *guess, i64 quad_stride)
 	if (s.m < 0 || s.m >= (1ll << 31) - 64 || s.na * std::max<i64>(s.m, 1) >= (1ll << 31) - 64)
 		return fail(GF2BV_ERR_ARG, "m and na x m must stay below 2^31 - 64");
 	s.x.m = s.m; s.x.n = s.n - s.f;
-	if (quad_stride < s.w2()) return fail(GF2BV_ERR_ARG, "quad_stride_words does not cover the quadratic columns and the constant");
+	if (quad_stride < s.wsrc())
+		return fail(GF2BV_ERR_ARG, cubic ? "cubic_stride_words does not cover the cubic columns and the constant"
+		                                 : "quad_stride_words does not cover the quadratic columns and the constant");
 	if (s.lds_bytes() > kExpandLdsBytes)
-		return fail(GF2BV_ERR_ARG, "the quadratic row, its specialised form and the guess vectors do not fit the specialisation kernel's LDS (64 KiB)");
+		return fail(GF2BV_ERR_ARG, cubic ? "the cubic row, its specialised form and the guess vectors do not fit the specialisation kernel's LDS (64 KiB)"
+		                                 : "the quadratic row, its specialised form and the guess vectors do not fit the specialisation kernel's LDS (64 KiB)");
 	return GF2BV_OK;
 }
 
 // The systems behind a solve entry: each assignment's expansion padded up to its columns, all of them one batch
 int check_guess_solve(GuessShape &s, int mode)
 {
-	int rc = check_xl(s.x, s.x.w2(), true);
+	int rc = check_xl(s.x, s.x.wsrc(), true);
 	if (rc) return rc;
 	if (s.na * s.x.rows >= (1ll << 31) - 64) return fail(GF2BV_ERR_ARG, "the rows of all assignments' systems together must stay below 2^31 - 64");
 	return check_shape(s.x.rows, s.x.cols(), mode);
 }
 
-// (device pointers, already checked) the kernel on `st`: system a - a0 at d_out + (a - a0) x sys_stride, m rows out_stride words apart
-int enqueue_quad_specialise(const GuessShape &s, const u64 *d_quad, i64 quad_stride, u64 *d_out, i64 out_stride, i64 sys_stride, hipStream_t st)
+// (device pointers, already checked) the source's kernel on `st`: system a - a0 at d_out + (a - a0) x sys_stride, m rows out_stride
+// words apart
+int enqueue_specialise(const GuessShape &s, const u64 *d_quad, i64 quad_stride, u64 *d_out, i64 out_stride, i64 sys_stride, hipStream_t st)
 {
 	if (s.m == 0 || s.na == 0) return GF2BV_OK;
 	const unsigned gx = (unsigned)std::min<i64>(s.m, 1024);
 	const unsigned gy = (unsigned)std::max<i64>(1, std::min<i64>({ s.na, 65535, 2048 / gx }));      // a couple of thousand workgroups
 	const int vec = !(out_stride & 1) && !(sys_stride & 1) && !((uintptr_t)d_out & 15);
-	hipLaunchKernelGGL(k_quad_specialise, dim3(gx, gy), dim3(256), (size_t)s.lds_bytes(), st, d_quad, s.m, quad_stride, (int)s.n, (int)s.w2(),
-	                   s.g, (int)s.f, s.a0, s.na, d_out, out_stride, sys_stride, vec);
+	hipLaunchKernelGGL(s.src == 3 ? k_cubic_specialise : k_quad_specialise, dim3(gx, gy), dim3(256), (size_t)s.lds_bytes(), st, d_quad, s.m,
+	                   quad_stride, (int)s.n, (int)s.wsrc(), s.g, (int)s.f, s.a0, s.na, d_out, out_stride, sys_stride, vec);
 	HIPCHK(hipGetLastError());
 	return GF2BV_OK;
 }
 
 // What one assignment's system holds on the device while a solve entry runs: its specialised rows and its padded expansion
-i64 guess_system_bytes(const XlShape &x) { return 8 * (x.m * round_up(x.w2(), 2) + x.rows * round_up(x.wt(), 2)); }
+i64 guess_system_bytes(const XlShape &x) { return 8 * (x.m * round_up(x.wsrc(), 2) + x.rows * round_up(x.wt(), 2)); }
 
 struct PoolStream {                    // a stream of the pool for the length of an entry
 	hipStream_t st = nullptr;
@@ -5068,9 +5086,9 @@ struct QuadStage {
 	{
 		ss = stride;
 		if (int rc = alloc((void **)&d_spec, sizeof(u64) * (size_t)(g.na * g.m * ss))) return rc;
-		return enqueue_quad_specialise(g, d_aug, ds, d_spec, ss, g.m * ss, ps.st);
+		return enqueue_specialise(g, d_aug, ds, d_spec, ss, g.m * ss, ps.st);
 	}
-	// The XL expansions (x.degree) of nsys systems of x.m quadratic rows in d_spec (system s at s x spec_sys words) into d_xl, system s at
+	// The XL expansions (x.degree, x.src) of nsys systems of x.m quadratic or cubic rows in d_spec (system s at s x spec_sys words) into d_xl, system s at
 	// s x x.rows x xs
 	int expand_xl_batch(const XlShape &x, i64 nsys, i64 spec_sys, i64 stride)
 	{
@@ -5094,7 +5112,9 @@ int check_xl_batch(XlShape &x, i64 nsys, i64 quad_sys_stride, i64 quad_stride, i
 	int rc = check_xl(x, quad_stride);
 	if (rc) return rc;
 	if (nsys * std::max<i64>(x.rows, 1) >= (1ll << 31) - 64) return fail(GF2BV_ERR_ARG, "the rows of all systems together must stay below 2^31 - 64");
-	if (quad_sys_stride < x.m * quad_stride) return fail(GF2BV_ERR_ARG, "quad_sys_stride_words must be at least m * quad_stride_words");
+	if (quad_sys_stride < x.m * quad_stride)
+		return fail(GF2BV_ERR_ARG, x.src == 3 ? "cubic_sys_stride_words must be at least m * cubic_stride_words"
+		                                      : "quad_sys_stride_words must be at least m * quad_stride_words");
 	if (stride < x.wt() || stride >= (1ll << 31)) return fail(GF2BV_ERR_ARG, "stride_words does not cover cols+1 bits");
 	if (sys_stride < x.rows * stride) return fail(GF2BV_ERR_ARG, "sys_stride_words must be at least rows * stride_words");
 	return GF2BV_OK;
@@ -5103,7 +5123,7 @@ int check_xl_batch(XlShape &x, i64 nsys, i64 quad_sys_stride, i64 quad_stride, i
 // behind the rows in stage.d_aug: specialisation, batched expansion and the gang solve, all ordered on the stage's stream
 int solve_guess_staged(QuadStage &stage, const GuessShape &g, int mode, int device, gf2bv_result **out)
 {
-	int rc = stage.specialise(g, round_up(g.x.w2(), 2));
+	int rc = stage.specialise(g, round_up(g.x.wsrc(), 2));
 	if (!rc) rc = stage.expand_xl_batch(g.x, g.na, g.m * stage.ss, g.x.wt());
 	if (rc) return rc;
 	rc = gf2bv_solve_batch_device(stage.d_xl, g.na, g.x.rows * stage.xs, g.x.rows, g.x.cols(), stage.xs, mode, device, stage.ps.st, 0, out);
@@ -5384,31 +5404,32 @@ static int solve_xl_terms(int degree, const Terms &t, int mode, int device, gf2b
 }
 
 // ---- hybrid XL: guessed unknowns substituted for many assignments at once, every assignment's system expanded and solved as one batch
-int gf2bv_quad_specialise_device(const void *d_quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, const int32_t *guess,
-                                 int64_t nguess, int64_t a0, int64_t na, void *d_out, int64_t out_stride_words, int64_t sys_stride_words,
-                                 int device, void *stream)
+// (src: the degree of the source rows -- 2 everywhere but in the gf2bv_*_cubic_* entries at the end, whose rows are cubic)
+static int specialise_device(int src, const void *d_quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, const int32_t *guess,
+                             int64_t nguess, int64_t a0, int64_t na, void *d_out, int64_t out_stride_words, int64_t sys_stride_words,
+                             int device, void *stream)
 {
 	return catching([&]() -> int {
-	GuessShape g(m, n_lin, nguess, a0, na);
+	GuessShape g(m, n_lin, nguess, a0, na, src + 1, src);
 	if (!d_out || (!d_quad && m > 0)) return fail(GF2BV_ERR_ARG, "null pointer");
 	int rc = check_guess(g, guess, quad_stride_words);
 	if (rc) return rc;
-	if (out_stride_words < g.x.w2() || out_stride_words >= (1ll << 31) || sys_stride_words < m * out_stride_words || ((uintptr_t)d_out & 7))
+	if (out_stride_words < g.x.wsrc() || out_stride_words >= (1ll << 31) || sys_stride_words < m * out_stride_words || ((uintptr_t)d_out & 7))
 		return fail(GF2BV_ERR_ARG, "out_stride_words must cover the specialised columns and the constant, sys_stride_words m rows of it");
 	if ((rc = check_device(device))) return rc;
-	return enqueue_quad_specialise(g, (const u64 *)d_quad, quad_stride_words, (u64 *)d_out, out_stride_words, sys_stride_words, (hipStream_t)stream);
+	return enqueue_specialise(g, (const u64 *)d_quad, quad_stride_words, (u64 *)d_out, out_stride_words, sys_stride_words, (hipStream_t)stream);
 	});
 }
 
-int gf2bv_quad_specialise_words(const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, const int32_t *guess,
-                                int64_t nguess, int64_t a0, int64_t na, uint64_t *out, int64_t out_stride_words, int device)
+static int specialise_words(int src, const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, const int32_t *guess,
+                            int64_t nguess, int64_t a0, int64_t na, uint64_t *out, int64_t out_stride_words, int device)
 {
 	return catching([&]() -> int {
-	GuessShape g(m, n_lin, nguess, a0, na);
+	GuessShape g(m, n_lin, nguess, a0, na, src + 1, src);
 	if ((!out && m > 0 && na > 0) || (!quad && m > 0)) return fail(GF2BV_ERR_ARG, "null pointer");
 	int rc = check_guess(g, guess, quad_stride_words);
 	if (rc) return rc;
-	if (out_stride_words < g.x.w2() || out_stride_words >= (1ll << 31))
+	if (out_stride_words < g.x.wsrc() || out_stride_words >= (1ll << 31))
 		return fail(GF2BV_ERR_ARG, "out_stride_words does not cover the specialised columns and the constant");
 	if ((rc = check_device(device))) return rc;
 	if (m == 0 || na == 0) return GF2BV_OK;
@@ -5421,12 +5442,12 @@ int gf2bv_quad_specialise_words(const uint64_t *quad, int64_t m, int64_t quad_st
 	});
 }
 
-static int xl_expand_batch_device(int degree, const void *d_quad, int64_t nsys, int64_t quad_sys_stride_words, int64_t m, int64_t quad_stride_words,
+static int xl_expand_batch_device(int degree, int src, const void *d_quad, int64_t nsys, int64_t quad_sys_stride_words, int64_t m, int64_t quad_stride_words,
                                   int64_t n_lin, int64_t rows, void *d_aug, int64_t stride_words, int64_t sys_stride_words, int device,
                                   void *stream)
 {
 	return catching([&]() -> int {
-	XlShape x(degree, 2, m, n_lin, rows);
+	XlShape x(degree, src, m, n_lin, rows);
 	if (!d_aug || (!d_quad && m > 0)) return fail(GF2BV_ERR_ARG, "null pointer");
 	int rc = check_xl_batch(x, nsys, quad_sys_stride_words, quad_stride_words, stride_words, sys_stride_words);
 	if (rc) return rc;
@@ -5438,11 +5459,11 @@ static int xl_expand_batch_device(int degree, const void *d_quad, int64_t nsys, 
 	});
 }
 
-static int xl_expand_batch_words(int degree, const uint64_t *quad, int64_t nsys, int64_t quad_sys_stride_words, int64_t m, int64_t quad_stride_words,
+static int xl_expand_batch_words(int degree, int src, const uint64_t *quad, int64_t nsys, int64_t quad_sys_stride_words, int64_t m, int64_t quad_stride_words,
                                  int64_t n_lin, int64_t rows, uint64_t *out_aug, int64_t stride_words, int64_t sys_stride_words, int device)
 {
 	return catching([&]() -> int {
-	XlShape x(degree, 2, m, n_lin, rows);
+	XlShape x(degree, src, m, n_lin, rows);
 	if ((!out_aug && rows > 0 && nsys > 0) || (!quad && m > 0 && nsys > 0)) return fail(GF2BV_ERR_ARG, "null pointer");
 	int rc = check_xl_batch(x, nsys, quad_sys_stride_words, quad_stride_words, stride_words, sys_stride_words);
 	if (rc) return rc;
@@ -5465,14 +5486,14 @@ static int xl_expand_batch_words(int degree, const uint64_t *quad, int64_t nsys,
 	});
 }
 
-static int solve_xl_guess_words(int degree, const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, const int32_t *guess,
+static int solve_xl_guess_words(int degree, int src, const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, const int32_t *guess,
                                 int64_t nguess, int64_t a0, int64_t na, int mode, int device, gf2bv_result **out)
 {
 	return catching([&]() -> int {
 	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
 	for (i64 s = 0; s < na; s++) out[s] = nullptr;
 	if (!quad && m > 0) return fail(GF2BV_ERR_ARG, "null pointer");
-	GuessShape g(m, n_lin, nguess, a0, na, degree);
+	GuessShape g(m, n_lin, nguess, a0, na, degree, src);
 	int rc = check_guess(g, guess, quad_stride_words);
 	if (!rc) rc = check_guess_solve(g, mode);
 	if (!rc) rc = check_device(device);
@@ -5484,17 +5505,16 @@ static int solve_xl_guess_words(int degree, const uint64_t *quad, int64_t m, int
 	});
 }
 
-static int solve_xl_guess_quad_terms(int degree, const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t m,
-                                     int64_t n_lin, const int32_t *guess, int64_t nguess, int64_t a0, int64_t na, int mode, int device,
-                                     gf2bv_result **out)
+// (the factored form of either degree: q.rows = q.rows_live = m rows, no padding)
+static int solve_xl_guess_terms(int degree, const Terms &q, const int32_t *guess, int64_t nguess, int64_t a0, int64_t na, int mode, int device,
+                                gf2bv_result **out)
 {
 	return catching([&]() -> int {
 	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
 	for (i64 s = 0; s < na; s++) out[s] = nullptr;
-	const Terms q(lin, term_off, ta, tb, m, m, n_lin);      // the m quadratic rows, no padding
 	int rc = check_terms(q, true);
 	if (rc) return rc;
-	GuessShape g(m, n_lin, nguess, a0, na, degree);
+	GuessShape g(q.rows, q.n, nguess, a0, na, degree, q.degree);
 	rc = check_guess(g, guess, q.wt());
 	if (!rc) rc = check_guess_solve(g, mode);
 	if (!rc) rc = check_device(device);
@@ -5509,33 +5529,44 @@ static int solve_xl_guess_quad_terms(int degree, const uint64_t *lin, const int6
 // The largest number of assignments (at most 2^nguess) whose specialised rows and padded expansions take at most a quarter of
 // free_bytes -- the solver keeps a tile-major copy of about the size of every system of a gang, so expansion and copy stay below half of
 // what was free -- and whose rows together stay below 2^31 - 64; 0 when one system does not fit, -1 for a bad shape.  No device is touched.
-static int64_t xl_guess_chunk(int degree, int64_t m, int64_t n_lin, int64_t nguess, int64_t free_bytes)
+static int64_t xl_guess_chunk(int degree, int src, int64_t m, int64_t n_lin, int64_t nguess, int64_t free_bytes)
 {
 	if (n_lin < 1 || n_lin > 65535 || nguess < 0 || nguess > std::min<i64>(n_lin - 1, 30) || m < 0 || free_bytes < 0) return -1;
-	XlShape x(degree, 2, m, n_lin - nguess);
-	if (check_xl(x, x.w2(), true)) return -1;
+	XlShape x(degree, src, m, n_lin - nguess);
+	if (check_xl(x, x.wsrc(), true)) return -1;
 	const i64 fit = free_bytes / 4 / guess_system_bytes(x);
 	return std::min<i64>({ 1ll << nguess, fit, ((1ll << 31) - 65) / x.rows });
 }
 
-static int xl_guess_chunk_device(int degree, int64_t m, int64_t n_lin, int64_t nguess, int device, int64_t *chunk)
+static int xl_guess_chunk_device(int degree, int src, int64_t m, int64_t n_lin, int64_t nguess, int device, int64_t *chunk)
 {
 	return catching([&]() -> int {
 	if (!chunk) return fail(GF2BV_ERR_ARG, "null pointer");
 	*chunk = 0;
-	if (xl_guess_chunk(degree, m, n_lin, nguess, 0) < 0) return fail(GF2BV_ERR_ARG, "m, n_lin or nguess out of range");
+	if (xl_guess_chunk(degree, src, m, n_lin, nguess, 0) < 0) return fail(GF2BV_ERR_ARG, "m, n_lin or nguess out of range");
 	int rc = check_device(device);
 	if (rc) return rc;
 	HIPCHK(hipSetDevice(device));
 	size_t free_b = 0, total_b = 0;
 	HIPCHK(hipMemGetInfo(&free_b, &total_b));
 	// (what the pool holds idle is handed out again before the device is asked for more)
-	*chunk = xl_guess_chunk(degree, m, n_lin, nguess, (i64)free_b + std::max<i64>(0, gf2bv_pool_idle_bytes(device)));
+	*chunk = xl_guess_chunk(degree, src, m, n_lin, nguess, (i64)free_b + std::max<i64>(0, gf2bv_pool_idle_bytes(device)));
 	return GF2BV_OK;
 	});
 }
 
 // the exported names: each body above once, for degree 3 and degree 4
+int gf2bv_quad_specialise_device(const void *d_quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, const int32_t *guess,
+                                 int64_t nguess, int64_t a0, int64_t na, void *d_out, int64_t out_stride_words, int64_t sys_stride_words,
+                                 int device, void *stream)
+{
+	return specialise_device(2, d_quad, m, quad_stride_words, n_lin, guess, nguess, a0, na, d_out, out_stride_words, sys_stride_words, device, stream);
+}
+int gf2bv_quad_specialise_words(const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, const int32_t *guess,
+                                int64_t nguess, int64_t a0, int64_t na, uint64_t *out, int64_t out_stride_words, int device)
+{
+	return specialise_words(2, quad, m, quad_stride_words, n_lin, guess, nguess, a0, na, out, out_stride_words, device);
+}
 int gf2bv_xl3_expand_device(const void *d_quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, int64_t rows, void *d_aug,
                             int64_t stride_words, int device, void *stream)
 {
@@ -5578,63 +5609,63 @@ int gf2bv_xl3_expand_batch_device(const void *d_quad, int64_t nsys, int64_t quad
                                   int64_t n_lin, int64_t rows, void *d_aug, int64_t stride_words, int64_t sys_stride_words, int device,
                                   void *stream)
 {
-	return xl_expand_batch_device(3, d_quad, nsys, quad_sys_stride_words, m, quad_stride_words, n_lin, rows, d_aug, stride_words, sys_stride_words,
+	return xl_expand_batch_device(3, 2, d_quad, nsys, quad_sys_stride_words, m, quad_stride_words, n_lin, rows, d_aug, stride_words, sys_stride_words,
 	                              device, stream);
 }
 int gf2bv_xl4_expand_batch_device(const void *d_quad, int64_t nsys, int64_t quad_sys_stride_words, int64_t m, int64_t quad_stride_words,
                                   int64_t n_lin, int64_t rows, void *d_aug, int64_t stride_words, int64_t sys_stride_words, int device,
                                   void *stream)
 {
-	return xl_expand_batch_device(4, d_quad, nsys, quad_sys_stride_words, m, quad_stride_words, n_lin, rows, d_aug, stride_words, sys_stride_words,
+	return xl_expand_batch_device(4, 2, d_quad, nsys, quad_sys_stride_words, m, quad_stride_words, n_lin, rows, d_aug, stride_words, sys_stride_words,
 	                              device, stream);
 }
 int gf2bv_xl3_expand_batch_words(const uint64_t *quad, int64_t nsys, int64_t quad_sys_stride_words, int64_t m, int64_t quad_stride_words,
                                  int64_t n_lin, int64_t rows, uint64_t *out_aug, int64_t stride_words, int64_t sys_stride_words, int device)
 {
-	return xl_expand_batch_words(3, quad, nsys, quad_sys_stride_words, m, quad_stride_words, n_lin, rows, out_aug, stride_words, sys_stride_words,
+	return xl_expand_batch_words(3, 2, quad, nsys, quad_sys_stride_words, m, quad_stride_words, n_lin, rows, out_aug, stride_words, sys_stride_words,
 	                             device);
 }
 int gf2bv_xl4_expand_batch_words(const uint64_t *quad, int64_t nsys, int64_t quad_sys_stride_words, int64_t m, int64_t quad_stride_words,
                                  int64_t n_lin, int64_t rows, uint64_t *out_aug, int64_t stride_words, int64_t sys_stride_words, int device)
 {
-	return xl_expand_batch_words(4, quad, nsys, quad_sys_stride_words, m, quad_stride_words, n_lin, rows, out_aug, stride_words, sys_stride_words,
+	return xl_expand_batch_words(4, 2, quad, nsys, quad_sys_stride_words, m, quad_stride_words, n_lin, rows, out_aug, stride_words, sys_stride_words,
 	                             device);
 }
 int gf2bv_solve_xl3_guess_words(const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, const int32_t *guess, int64_t nguess,
                                 int64_t a0, int64_t na, int mode, int device, gf2bv_result **out)
 {
-	return solve_xl_guess_words(3, quad, m, quad_stride_words, n_lin, guess, nguess, a0, na, mode, device, out);
+	return solve_xl_guess_words(3, 2, quad, m, quad_stride_words, n_lin, guess, nguess, a0, na, mode, device, out);
 }
 int gf2bv_solve_xl4_guess_words(const uint64_t *quad, int64_t m, int64_t quad_stride_words, int64_t n_lin, const int32_t *guess, int64_t nguess,
                                 int64_t a0, int64_t na, int mode, int device, gf2bv_result **out)
 {
-	return solve_xl_guess_words(4, quad, m, quad_stride_words, n_lin, guess, nguess, a0, na, mode, device, out);
+	return solve_xl_guess_words(4, 2, quad, m, quad_stride_words, n_lin, guess, nguess, a0, na, mode, device, out);
 }
 int gf2bv_solve_xl3_guess_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t m, int64_t n_lin,
                                      const int32_t *guess, int64_t nguess, int64_t a0, int64_t na, int mode, int device, gf2bv_result **out)
 {
-	return solve_xl_guess_quad_terms(3, lin, term_off, ta, tb, m, n_lin, guess, nguess, a0, na, mode, device, out);
+	return solve_xl_guess_terms(3, Terms(lin, term_off, ta, tb, m, m, n_lin), guess, nguess, a0, na, mode, device, out);
 }
 int gf2bv_solve_xl4_guess_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t m, int64_t n_lin,
                                      const int32_t *guess, int64_t nguess, int64_t a0, int64_t na, int mode, int device, gf2bv_result **out)
 {
-	return solve_xl_guess_quad_terms(4, lin, term_off, ta, tb, m, n_lin, guess, nguess, a0, na, mode, device, out);
+	return solve_xl_guess_terms(4, Terms(lin, term_off, ta, tb, m, m, n_lin), guess, nguess, a0, na, mode, device, out);
 }
 int64_t gf2bv_xl3_guess_chunk(int64_t m, int64_t n_lin, int64_t nguess, int64_t free_bytes)
 {
-	return xl_guess_chunk(3, m, n_lin, nguess, free_bytes);
+	return xl_guess_chunk(3, 2, m, n_lin, nguess, free_bytes);
 }
 int64_t gf2bv_xl4_guess_chunk(int64_t m, int64_t n_lin, int64_t nguess, int64_t free_bytes)
 {
-	return xl_guess_chunk(4, m, n_lin, nguess, free_bytes);
+	return xl_guess_chunk(4, 2, m, n_lin, nguess, free_bytes);
 }
 int gf2bv_xl3_guess_chunk_device(int64_t m, int64_t n_lin, int64_t nguess, int device, int64_t *chunk)
 {
-	return xl_guess_chunk_device(3, m, n_lin, nguess, device, chunk);
+	return xl_guess_chunk_device(3, 2, m, n_lin, nguess, device, chunk);
 }
 int gf2bv_xl4_guess_chunk_device(int64_t m, int64_t n_lin, int64_t nguess, int device, int64_t *chunk)
 {
-	return xl_guess_chunk_device(4, m, n_lin, nguess, device, chunk);
+	return xl_guess_chunk_device(4, 2, m, n_lin, nguess, device, chunk);
 }
 
 // ---- degree-4 XL on cubic rows (k_xl4_cubic_expand): the bodies above with src = 3, and the factored form staged through both kernels
@@ -5658,6 +5689,51 @@ int gf2bv_solve_xl4_cubic_terms(const uint64_t *lin, const int64_t *off2, const 
                                 gf2bv_result **out)
 {
 	return solve_xl_terms(4, Terms(lin, off2, ta, tb, m, m, n_lin, off3, ua, ub, uc, 3), mode, device, out);
+}
+
+// ---- hybrid degree-4 XL on cubic rows (k_cubic_specialise, k_xl4_cubic_expand_batch): the hybrid bodies above with src = 3
+int gf2bv_cubic_specialise_device(const void *d_cubic, int64_t m, int64_t cubic_stride_words, int64_t n_lin, const int32_t *guess,
+                                  int64_t nguess, int64_t a0, int64_t na, void *d_out, int64_t out_stride_words, int64_t sys_stride_words,
+                                  int device, void *stream)
+{
+	return specialise_device(3, d_cubic, m, cubic_stride_words, n_lin, guess, nguess, a0, na, d_out, out_stride_words, sys_stride_words, device, stream);
+}
+int gf2bv_cubic_specialise_words(const uint64_t *cubic, int64_t m, int64_t cubic_stride_words, int64_t n_lin, const int32_t *guess,
+                                 int64_t nguess, int64_t a0, int64_t na, uint64_t *out, int64_t out_stride_words, int device)
+{
+	return specialise_words(3, cubic, m, cubic_stride_words, n_lin, guess, nguess, a0, na, out, out_stride_words, device);
+}
+int gf2bv_xl4_cubic_expand_batch_device(const void *d_cubic, int64_t nsys, int64_t cubic_sys_stride_words, int64_t m, int64_t cubic_stride_words,
+                                        int64_t n_lin, int64_t rows, void *d_aug, int64_t stride_words, int64_t sys_stride_words, int device,
+                                        void *stream)
+{
+	return xl_expand_batch_device(4, 3, d_cubic, nsys, cubic_sys_stride_words, m, cubic_stride_words, n_lin, rows, d_aug, stride_words,
+	                              sys_stride_words, device, stream);
+}
+int gf2bv_xl4_cubic_expand_batch_words(const uint64_t *cubic, int64_t nsys, int64_t cubic_sys_stride_words, int64_t m, int64_t cubic_stride_words,
+                                       int64_t n_lin, int64_t rows, uint64_t *out_aug, int64_t stride_words, int64_t sys_stride_words, int device)
+{
+	return xl_expand_batch_words(4, 3, cubic, nsys, cubic_sys_stride_words, m, cubic_stride_words, n_lin, rows, out_aug, stride_words,
+	                             sys_stride_words, device);
+}
+int gf2bv_solve_xl4_cubic_guess_words(const uint64_t *cubic, int64_t m, int64_t cubic_stride_words, int64_t n_lin, const int32_t *guess,
+                                      int64_t nguess, int64_t a0, int64_t na, int mode, int device, gf2bv_result **out)
+{
+	return solve_xl_guess_words(4, 3, cubic, m, cubic_stride_words, n_lin, guess, nguess, a0, na, mode, device, out);
+}
+int gf2bv_solve_xl4_cubic_guess_terms(const uint64_t *lin, const int64_t *off2, const uint64_t *ta, const uint64_t *tb, const int64_t *off3,
+                                      const uint64_t *ua, const uint64_t *ub, const uint64_t *uc, int64_t m, int64_t n_lin,
+                                      const int32_t *guess, int64_t nguess, int64_t a0, int64_t na, int mode, int device, gf2bv_result **out)
+{
+	return solve_xl_guess_terms(4, Terms(lin, off2, ta, tb, m, m, n_lin, off3, ua, ub, uc, 3), guess, nguess, a0, na, mode, device, out);
+}
+int64_t gf2bv_xl4_cubic_guess_chunk(int64_t m, int64_t n_lin, int64_t nguess, int64_t free_bytes)
+{
+	return xl_guess_chunk(4, 3, m, n_lin, nguess, free_bytes);
+}
+int gf2bv_xl4_cubic_guess_chunk_device(int64_t m, int64_t n_lin, int64_t nguess, int device, int64_t *chunk)
+{
+	return xl_guess_chunk_device(4, 3, m, n_lin, nguess, device, chunk);
 }
 
 // k_xl4_expand's quartic root, the same function compiled for the host: the largest i >= 3 with C(i,4) <= u (u >= 0), for checks

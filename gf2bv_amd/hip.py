@@ -46,6 +46,8 @@ EXPORTS = [
     "gf2bv_xl4_expand_batch_device", "gf2bv_xl4_expand_batch_words", "gf2bv_solve_xl4_guess_words", "gf2bv_solve_xl4_guess_quad_terms",
     "gf2bv_xl4_guess_chunk", "gf2bv_xl4_guess_chunk_device", "gf2bv_xl4_quartic_root",
     "gf2bv_xl4_cubic_expand_device", "gf2bv_xl4_cubic_expand_words", "gf2bv_solve_xl4_cubic_words", "gf2bv_solve_xl4_cubic_terms",
+    "gf2bv_cubic_specialise_device", "gf2bv_cubic_specialise_words", "gf2bv_xl4_cubic_expand_batch_device", "gf2bv_xl4_cubic_expand_batch_words",
+    "gf2bv_solve_xl4_cubic_guess_words", "gf2bv_solve_xl4_cubic_guess_terms", "gf2bv_xl4_cubic_guess_chunk", "gf2bv_xl4_cubic_guess_chunk_device",
     "gf2bv_quad_search", "gf2bv_quad_search_alloc", "gf2bv_quad_free", "gf2bv_quad_plan", "gf2bv_quad_points", "gf2bv_quad_forms_search", "gf2bv_quad_last_times",
     "gf2bv_slab_work_words", "gf2bv_slab_tiles", "gf2bv_slab_open", "gf2bv_slab_blocks", "gf2bv_slab_owner",
     "gf2bv_slab_payload_bytes", "gf2bv_slab_factor", "gf2bv_slab_apply", "gf2bv_slab_factor_on", "gf2bv_slab_apply_on",
@@ -178,6 +180,15 @@ def lib():
         L.gf2bv_xl4_cubic_expand_words.argtypes = [vp, i64, i64, i64, i64, vp, i64, i32]
         L.gf2bv_solve_xl4_cubic_words.argtypes = [vp, i64, i64, i64, i32, i32, pp]
         L.gf2bv_solve_xl4_cubic_terms.argtypes = [vp] * 8 + [i64, i64, i32, i32, pp]
+        L.gf2bv_cubic_specialise_device.argtypes = L.gf2bv_quad_specialise_device.argtypes
+        L.gf2bv_cubic_specialise_words.argtypes = L.gf2bv_quad_specialise_words.argtypes
+        L.gf2bv_xl4_cubic_expand_batch_device.argtypes = L.gf2bv_xl4_expand_batch_device.argtypes
+        L.gf2bv_xl4_cubic_expand_batch_words.argtypes = L.gf2bv_xl4_expand_batch_words.argtypes
+        L.gf2bv_solve_xl4_cubic_guess_words.argtypes = L.gf2bv_solve_xl4_guess_words.argtypes
+        L.gf2bv_solve_xl4_cubic_guess_terms.argtypes = [vp] * 8 + [i64, i64, vp, i64, i64, i64, i32, i32, pp]
+        L.gf2bv_xl4_cubic_guess_chunk.argtypes = [i64, i64, i64, i64]
+        L.gf2bv_xl4_cubic_guess_chunk.restype = i64
+        L.gf2bv_xl4_cubic_guess_chunk_device.argtypes = [i64, i64, i64, i32, ctypes.POINTER(i64)]
         L.gf2bv_slab_work_words.argtypes = [i64, i64]
         L.gf2bv_slab_work_words.restype = i64
         L.gf2bv_slab_tiles.argtypes = [i64]
@@ -1087,6 +1098,91 @@ def solve_xl4_cubic_terms(lin, off2, ta, tb, off3, ua, ub, uc, n_lin: int, mode:
     h = ctypes.c_void_p()
     _check(lib().gf2bv_solve_xl4_cubic_terms(*_ptrs(*terms), len(terms[0]), n_lin, mode, device, ctypes.byref(h)))
     return _take(h, mode)
+
+
+# -- hybrid degree-4 XL on cubic rows: the hybrid functions above one degree up (gf2bv_hip.h, "hybrid degree-4 XL on cubic equations") ----
+def cubic_specialise_words(cubic, n_lin: int, guess, a0: int = 0, na: int | None = None, stride_words: int | None = None,
+                           device: int = 0) -> np.ndarray:
+    """The guessed unknowns substituted into m cubic rows on the device (gf2bv_cubic_specialise_words): [na, m, stride_words] uint64,
+    element s the rows of assignment a0 + s (bit t of it is the value of unknown guess[t]) over the xl3_cols of the
+    n_lin - len(guess) remaining unknowns.  na defaults to every assignment from a0 on."""
+    cubic, guess = _cubic_rows(cubic), _guess(guess)
+    na = _assignments(guess, a0, na)
+    stride = (xl3_cols(n_lin - len(guess)) + 1 + 63) // 64 if stride_words is None else stride_words
+    out = np.empty((max(na, 0), len(cubic), max(stride, 0)), dtype=np.uint64)
+    _check(lib().gf2bv_cubic_specialise_words(cubic.ctypes.data, len(cubic), cubic.shape[1], n_lin, guess.ctypes.data, len(guess), a0, na,
+                                              out.ctypes.data, stride, device))
+    return out
+
+
+def cubic_specialise_device(d_cubic: int, m: int, cubic_stride: int, n_lin: int, guess, a0: int, na: int, d_out: int, out_stride: int,
+                            sys_stride: int, device: int = 0, stream: int = 0) -> None:
+    """cubic_specialise_words with the rows resident in device memory (the guess stays a host array): system s at
+    d_out + s * sys_stride words; the kernel is enqueued on `stream` and the call returns."""
+    guess = _guess(guess)
+    _check(lib().gf2bv_cubic_specialise_device(d_cubic, m, cubic_stride, n_lin, guess.ctypes.data, len(guess), a0, na, d_out, out_stride,
+                                               sys_stride, device, stream or None))
+
+
+def xl4_cubic_expand_batch_words(cubics, n_lin: int, rows: int | None = None, stride_words: int | None = None,
+                                 sys_stride_words: int | None = None, device: int = 0) -> np.ndarray:
+    """xl4_cubic_expand_words of nsys systems in one launch (gf2bv_xl4_cubic_expand_batch_words): `cubics` is [nsys, m, cubic_stride]
+    uint64; the result is [nsys, sys_stride_words] uint64, system s its `rows` rows stride_words apart from word 0 of element s and
+    the words behind them as numpy left them."""
+    cubics = np.ascontiguousarray(cubics, dtype=np.uint64)
+    if cubics.ndim != 3:
+        raise ValueError("the systems must be a 3-D uint64 array: system, equation, word")
+    nsys, m, cs = cubics.shape
+    rows = m * (n_lin + 1) if rows is None else rows
+    stride = (xl4_cols(n_lin) + 1 + 63) // 64 if stride_words is None else stride_words
+    sys_stride = rows * stride if sys_stride_words is None else sys_stride_words
+    out = np.zeros((nsys, max(sys_stride, 0)), dtype=np.uint64)
+    _check(lib().gf2bv_xl4_cubic_expand_batch_words(cubics.ctypes.data, nsys, m * cs, m, cs, n_lin, rows, out.ctypes.data, stride, sys_stride,
+                                                    device))
+    return out
+
+
+def xl4_cubic_expand_batch_device(d_cubic: int, nsys: int, cubic_sys_stride: int, m: int, cubic_stride: int, n_lin: int, rows: int, d_aug: int,
+                                  stride: int, sys_stride: int, device: int = 0, stream: int = 0) -> None:
+    """xl4_cubic_expand_batch_words with everything resident in device memory: enqueued on `stream`, the call returns; a
+    solve_batch_device with the same stream reads the finished systems."""
+    _check(lib().gf2bv_xl4_cubic_expand_batch_device(d_cubic, nsys, cubic_sys_stride, m, cubic_stride, n_lin, rows, d_aug, stride, sys_stride,
+                                                     device, stream or None))
+
+
+def solve_xl4_cubic_guess_words(cubic, n_lin: int, guess, a0: int = 0, na: int | None = None, mode: int = MODE_SINGLE, device: int = 0) -> list:
+    """Hybrid degree-4 XL on cubic rows (gf2bv_solve_xl4_cubic_guess_words): the rows uploaded, specialised for the assignments
+    a0 .. a0 + na - 1 of the guessed unknowns, every assignment's rows multiplied and all systems solved as lock-step gangs.  Element s
+    is what solve_xl4_cubic_words returns for cubic_specialise_words(...)[s] over n_lin - len(guess) unknowns."""
+    cubic, guess = _cubic_rows(cubic), _guess(guess)
+    na = _assignments(guess, a0, na)
+    hs = _handles(na)
+    rc = lib().gf2bv_solve_xl4_cubic_guess_words(cubic.ctypes.data, len(cubic), cubic.shape[1], n_lin, guess.ctypes.data, len(guess), a0, na,
+                                                 mode, device, hs)
+    return _take_all(hs, max(na, 0), rc, mode)
+
+
+def solve_xl4_cubic_guess_terms(lin, off2, ta, tb, off3, ua, ub, uc, n_lin: int, guess, a0: int = 0, na: int | None = None,
+                                mode: int = MODE_SINGLE, device: int = 0) -> list:
+    """solve_xl4_cubic_guess_words on a factored cubic system: expanded on the device first (gf2bv_solve_xl4_cubic_guess_terms)."""
+    terms = _cubic_terms(lin, off2, ta, tb, off3, ua, ub, uc, n_lin)
+    guess = _guess(guess)
+    na = _assignments(guess, a0, na)
+    hs = _handles(na)
+    rc = lib().gf2bv_solve_xl4_cubic_guess_terms(*_ptrs(*terms), len(terms[0]), n_lin, guess.ctypes.data, len(guess), a0, na, mode, device, hs)
+    return _take_all(hs, max(na, 0), rc, mode)
+
+
+def xl4_cubic_guess_chunk(m: int, n_lin: int, nguess: int, free_bytes: int | None = None, device: int = 0) -> int:
+    """xl4_guess_chunk for the systems of solve_xl4_cubic_guess_* (gf2bv_xl4_cubic_guess_chunk / _chunk_device)"""
+    if free_bytes is None:
+        chunk = ctypes.c_int64()
+        _check(lib().gf2bv_xl4_cubic_guess_chunk_device(m, n_lin, nguess, device, ctypes.byref(chunk)))
+        return int(chunk.value)
+    chunk = int(lib().gf2bv_xl4_cubic_guess_chunk(m, n_lin, nguess, free_bytes))
+    if chunk < 0:
+        raise ValueError("m, n_lin, nguess or free_bytes out of range")
+    return chunk
 
 
 def synth_device(d_ptr: int, rows: int, cols: int, stride: int, seed: int, device: int = 0, stream: int = 0):

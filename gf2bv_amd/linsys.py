@@ -515,8 +515,7 @@ class _QuadraticPoints:
             yield first, [None] * count
             return
         m, run = staged
-        from . import hip                              # noqa: PLC0415  (ctypes binding, first use only)
-        chunk = (hip.xl4_guess_chunk if degree == 4 else hip.xl3_guess_chunk)(m, self._lin_size, len(g))
+        chunk = self._xl_guess_chunk(degree)(m, self._lin_size, len(g))
         if chunk < 1:
             raise MemoryError(f"one assignment's degree-{degree} XL system does not fit a quarter of the free device memory")
         end = first + count
@@ -524,6 +523,11 @@ class _QuadraticPoints:
             na = min(chunk, end - first)
             yield first, run(first, na)
             first += na
+
+    def _xl_guess_chunk(self, degree: int):
+        """the library's chunk function for this class's systems of that degree"""
+        from . import hip                              # noqa: PLC0415  (ctypes binding, first use only)
+        return hip.xl4_guess_chunk if degree == 4 else hip.xl3_guess_chunk
 
     def solve_raw_one_xl_guess(self, zeros: Zeros, guess, assignments=None) -> list:
         """one particular solution (or None) per assignment, over the cubic columns of the remaining unknowns"""
@@ -563,7 +567,10 @@ class _QuadraticPoints:
         rest = [u for u in range(n) if u not in g]
         for k, u in enumerate(rest):
             full |= ((raw >> k) & 1) << u
-        return self._convert_sol(full)[:-1]
+        return self._guess_sol(full)
+
+    def _guess_sol(self, full: int) -> tuple:
+        return self._convert_sol(full)[:-1]            # (without the trailing block of the product unknowns)
 
     def solve_all_xl_guess(self, zeros: Zeros, guess, *, degree: int = 3, max_dimension: int = 16, assignments=None):
         """the consistent points of every assignment's degree-3 XL system, in assignment order and within an assignment in AffineSpace

@@ -22,8 +22,8 @@ from typing import Iterable, Optional, Sequence
 import numpy as np
 
 from ._internal import (m4ri_solve_cubic_packed, m4ri_solve_many_quad_packed, m4ri_solve_packed, m4ri_solve_quad_packed,
-                        m4ri_solve_xl3_guess_quad_packed, m4ri_solve_xl3_quad_packed, m4ri_solve_xl4_guess_quad_packed,
-                        m4ri_solve_xl4_cubic_packed, m4ri_solve_xl4_quad_packed)
+                        m4ri_solve_xl3_guess_quad_packed, m4ri_solve_xl3_quad_packed, m4ri_solve_xl4_guess_cubic_packed,
+                        m4ri_solve_xl4_guess_quad_packed, m4ri_solve_xl4_cubic_packed, m4ri_solve_xl4_quad_packed)
 from .bitvec import BitVec
 from .linsys import _QuadraticPoints, _SolveSurface, _eqs_from_words, _raw_value, _space_points, xl3_cols, xl4_cols
 
@@ -741,7 +741,8 @@ class PackedCubicSystem(PackedLinearSystem):
     expands them over the n + C(n,2) + C(n,3) columns of degree-3 XL and solves.  ``solve_all`` keeps the points of the linearised
     space whose pair and triple coordinates are the products of their linear bits.  The ``*_xl4`` methods are degree-4 XL: the device
     multiplies every expanded equation by 1 and by each unknown too and solves over the n + C(n,2) + C(n,3) + C(n,4) monomials of
-    degree <= 4, which takes about C(n,3) / 4 equations where plain linearisation takes about C(n,3)."""
+    degree <= 4, which takes about C(n,3) / 4 equations where plain linearisation takes about C(n,3).  Its hybrid form, which
+    guesses unknowns, is PackedCubicGuessSystem's."""
 
     def __init__(self, sizes: Iterable[int]):
         super().__init__(sizes)
@@ -862,3 +863,37 @@ for _name in ("get_rows", "_stack_rows", "_flat_rows", "factor", "bit_assert", "
               "solve_one_rhs"):
     setattr(PackedCubicSystem, _name, _refuse_system(_name))
 del _name
+
+
+class PackedCubicGuessSystem(PackedCubicSystem):
+    """A PackedCubicSystem with the hybrid form of degree-4 XL.  The ``*_xl4_guess`` methods have the meaning and the guess parsing of
+    the quadratic classes': f unknowns are fixed in all 2^f ways, the device substitutes them into the expanded cubic rows and solves
+    every assignment's degree-4 XL system in the other n - f unknowns as one batch.  Everything else is PackedCubicSystem's, whose set
+    of public names is fixed; the bits of either class work with the other."""
+
+    # -- _QuadraticPoints' methods over this class's staging, chunk function and solution tuple --------------------------------------
+    _parse_guess = _QuadraticPoints._parse_guess
+    _xl_guess_chunks = _QuadraticPoints._xl_guess_chunks
+    _scatter_guess = _QuadraticPoints._scatter_guess
+    _solve_all_xl_guess = _QuadraticPoints._solve_all_xl_guess
+    solve_raw_one_xl4_guess = _QuadraticPoints.solve_raw_one_xl4_guess
+    solve_raw_space_xl4_guess = _QuadraticPoints.solve_raw_space_xl4_guess
+    convert_sol_xl4_guess = _QuadraticPoints.convert_sol_xl4_guess
+    solve_one_xl4_guess = _QuadraticPoints.solve_one_xl4_guess
+
+    def solve_all_xl4_guess(self, zeros: Sequence, guess, *, max_dimension: int = 16, assignments=None):
+        """the consistent points of every assignment's degree-4 XL system (about cols4(n - f) / (n - f + 1) equations), in assignment
+        order and within an assignment in AffineSpace order; the assignments are solved a chunk at a time (hip.xl4_cubic_guess_chunk),
+        the next chunk when more is asked for"""
+        return self._solve_all_xl_guess(zeros, guess, max_dimension, assignments, 4)
+
+    def _solve_internal_xl4_guess(self, zeros: Sequence, guess: list, mode: int):
+        terms = self._terms(zeros)
+        return len(terms[0]), lambda first, count: m4ri_solve_xl4_guess_cubic_packed(*terms, self._lin_size, guess, first, count, mode)
+
+    def _xl_guess_chunk(self, degree: int):
+        from . import hip                              # noqa: PLC0415  (ctypes binding, first use only)
+        return hip.xl4_cubic_guess_chunk
+
+    def _guess_sol(self, full: int) -> tuple:
+        return self._convert_sol(full)                 # (this class has no block of product unknowns behind the generators')

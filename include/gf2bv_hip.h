@@ -595,6 +595,52 @@ int gf2bv_solve_xl4_cubic_terms(const uint64_t *lin, const int64_t *off2, const 
                                 const uint64_t *ua, const uint64_t *ub, const uint64_t *uc, int64_t m, int64_t n_lin, int mode,
                                 int device, gf2bv_result **out);
 
+/* ---- hybrid degree-4 XL on cubic equations: guess unknowns, solve every assignment's system as one batch ---------------------------
+ * The hybrid entries above one degree up: with fewer than about cols4 / (n_lin + 1) cubic equations, f unknowns are fixed in all 2^f
+ * ways, which leaves 2^f cubic systems in n' = n_lin - f unknowns with the same m equations each; they need about cols4(n') / (n' + 1).
+ * Source rows: m cubic rows over n_lin unknowns as gf2bv_cubic_expand_* writes them (the layout of the section above), W3 words read.
+ * Guess, assignment index and R: as for gf2bv_quad_specialise_device.
+ * Specialised row of assignment a, in the same layout over n' unknowns, W3' = ceil((cols3' + 1) / 64) words, with l, q, t taken over
+ * unordered sets:
+ *   t'(i', j', k') = t(R[i'], R[j'], R[k'])                                 (the triple block does not depend on a)
+ *   q'(i', j')     = q(R[i'], R[j']) ^ XOR_{u: a_u = 1} t(R[i'], R[j'], g_u)
+ *   l'(i')         = l(R[i']) ^ XOR_{u: a_u = 1} q(R[i'], g_u) ^ XOR_{u < v: a_u = a_v = 1} t(R[i'], g_u, g_v)
+ *   c'             = c ^ XOR_{u} l(g_u) ^ XOR_{u < v} q(g_u, g_v) ^ XOR_{u < v < w} t(g_u, g_v, g_w)      (over the set bits of a)
+ * A row may become 0 or the constant 1; it stays in and the solver reports the inconsistency.
+ * gf2bv_cubic_specialise_device / _words (k_cubic_specialise): arguments, strides, store widths and the ordering contract of
+ * gf2bv_quad_specialise_device / _words, with out_stride_words >= W3' and every bit behind column cols3' written as zero; bits
+ * behind the source's constant column are ignored.
+ * gf2bv_xl4_cubic_expand_batch_device / _words (k_xl4_cubic_expand_batch): gf2bv_xl3_expand_batch_device / _words on nsys systems of
+ * m cubic rows each, every system expanded exactly as gf2bv_xl4_cubic_expand_* defines it.
+ * gf2bv_solve_xl4_cubic_guess_words: expanded cubic rows in; upload, specialisation, batched multiply and gf2bv_solve_batch_device
+ * over cols4(n') columns on one pool stream, rows' = max(m(n' + 1), cols4(n')) a system; out[a - a0] is assignment a's result.
+ * gf2bv_solve_xl4_cubic_guess_terms: the factored form of gf2bv_solve_cubic_terms (m live rows, no padding) uploaded and expanded
+ * by k_cubic_expand in front of the same chain: no row of any expansion exists on the host.  On a non-zero return every out[s] is NULL.
+ * gf2bv_xl4_cubic_guess_chunk / _chunk_device: gf2bv_xl3_guess_chunk / _chunk_device for these systems (m W3' + rows' W4' words each).
+ * GF2BV_ERR_ARG before any device is touched: what the quadratic hybrid entries refuse, with cols3 for cols2 in the source and cols4(n')
+ * for cols3(n') in the systems; the cubic row, its specialised form and the guess vectors beyond the specialisation kernel's LDS
+ * (8 (W3 + W3' + f ceil(cols2' / 64) + C(f,2) (ceil(n' / 64) + 1) + 1 + f) + 4 n' bytes > 64 KiB); what gf2bv_xl4_cubic_expand_* and,
+ * for the factored form, gf2bv_solve_cubic_terms refuse. */
+int gf2bv_cubic_specialise_device(const void *d_cubic, int64_t m, int64_t cubic_stride_words, int64_t n_lin, const int32_t *guess,
+                                  int64_t nguess, int64_t a0, int64_t na, void *d_out, int64_t out_stride_words, int64_t sys_stride_words,
+                                  int device, void *stream);
+int gf2bv_cubic_specialise_words(const uint64_t *cubic, int64_t m, int64_t cubic_stride_words, int64_t n_lin, const int32_t *guess,
+                                 int64_t nguess, int64_t a0, int64_t na, uint64_t *out, int64_t out_stride_words, int device);
+int gf2bv_xl4_cubic_expand_batch_device(const void *d_cubic, int64_t nsys, int64_t cubic_sys_stride_words, int64_t m,
+                                        int64_t cubic_stride_words, int64_t n_lin, int64_t rows, void *d_aug, int64_t stride_words,
+                                        int64_t sys_stride_words, int device, void *stream);
+int gf2bv_xl4_cubic_expand_batch_words(const uint64_t *cubic, int64_t nsys, int64_t cubic_sys_stride_words, int64_t m,
+                                       int64_t cubic_stride_words, int64_t n_lin, int64_t rows, uint64_t *out_aug, int64_t stride_words,
+                                       int64_t sys_stride_words, int device);
+int gf2bv_solve_xl4_cubic_guess_words(const uint64_t *cubic, int64_t m, int64_t cubic_stride_words, int64_t n_lin, const int32_t *guess,
+                                      int64_t nguess, int64_t a0, int64_t na, int mode, int device, gf2bv_result **out);
+int gf2bv_solve_xl4_cubic_guess_terms(const uint64_t *lin, const int64_t *off2, const uint64_t *ta, const uint64_t *tb, const int64_t *off3,
+                                      const uint64_t *ua, const uint64_t *ub, const uint64_t *uc, int64_t m, int64_t n_lin,
+                                      const int32_t *guess, int64_t nguess, int64_t a0, int64_t na, int mode, int device,
+                                      gf2bv_result **out);
+int64_t gf2bv_xl4_cubic_guess_chunk(int64_t m, int64_t n_lin, int64_t nguess, int64_t free_bytes);
+int gf2bv_xl4_cubic_guess_chunk_device(int64_t m, int64_t n_lin, int64_t nguess, int device, int64_t *chunk);
+
 /* ---- synthetic systems + independent residual check (bench / tests) ----------------------- */
 /* word w of row r = mix64(mix64(seed) ^ ((r<<20)|w)); planted solution = pseudo-row 0xFFFFF;
  * RHS = <row, planted>.  Writes rows x stride_words words at d_aug. */
