@@ -4516,6 +4516,15 @@ int check_quad_space(const u64 *origin, const u64 *basis, i64 d, i64 words, i64 
 	return GF2BV_OK;
 }
 
+// what gf2bv_quad_plan and gf2bv_quad_plan_device hand out of a built plan
+void quad_plan_export(const QuadPlan &P, int64_t *r, int64_t *r_eff, int64_t *m, int64_t *form_words, uint64_t *forms, int64_t forms_cap)
+{
+	*r = P.r; *r_eff = P.reff;
+	*m = P.reff < 0 ? 0 : P.m;
+	*form_words = P.reff < 0 ? 0 : P.fw;
+	if (forms && P.reff >= 0 && P.m <= forms_cap) std::copy(P.forms.begin(), P.forms.begin() + P.m * P.fw, reinterpret_cast<u64 *>(forms));
+}
+
 }  // namespace
 
 extern "C" {
@@ -4531,10 +4540,28 @@ int gf2bv_quad_plan(const uint64_t *origin_, const uint64_t *basis_, int64_t dim
 	QuadPlan P;
 	rc = quad_plan_build(P, origin, basis, dimension, words, n_lin, -1, nullptr);
 	if (rc) return rc;
-	*r = P.r; *r_eff = P.reff;
-	*m = P.reff < 0 ? 0 : P.m;
-	*form_words = P.reff < 0 ? 0 : P.fw;
-	if (forms_ && P.reff >= 0 && P.m <= forms_cap) std::copy(P.forms.begin(), P.forms.begin() + P.m * P.fw, reinterpret_cast<u64 *>(forms_));
+	quad_plan_export(P, r, r_eff, m, form_words, forms_, forms_cap);
+	return GF2BV_OK;
+	});
+}
+
+int gf2bv_quad_plan_device(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin, int device,
+                           int64_t *r, int64_t *r_eff, int64_t *m, int64_t *form_words, uint64_t *forms_, int64_t forms_cap)
+{
+	const u64 *origin = reinterpret_cast<const u64 *>(origin_), *basis = reinterpret_cast<const u64 *>(basis_);
+	return guarded([&]() -> int {
+	int rc = check_quad_space(origin, basis, dimension, words, n_lin);
+	if (rc) return rc;
+	if (!r || !r_eff || !m || !form_words) return fail(GF2BV_ERR_ARG, "null pointer");
+	rc = check_device(device);
+	if (rc) return rc;
+	hipStream_t st = nullptr;
+	HIPCHK(pool().stream(&st, device, 0));
+	std::unique_ptr<void, std::function<void(void *)>> keep(st, [&](void *) { pool().release_stream(st, device, 0); });
+	QuadPlan P;
+	rc = quad_plan_build(P, origin, basis, dimension, words, n_lin, device, st);
+	if (rc) return rc;
+	quad_plan_export(P, r, r_eff, m, form_words, forms_, forms_cap);
 	return GF2BV_OK;
 	});
 }

@@ -48,7 +48,7 @@ EXPORTS = [
     "gf2bv_xl4_cubic_expand_device", "gf2bv_xl4_cubic_expand_words", "gf2bv_solve_xl4_cubic_words", "gf2bv_solve_xl4_cubic_terms",
     "gf2bv_cubic_specialise_device", "gf2bv_cubic_specialise_words", "gf2bv_xl4_cubic_expand_batch_device", "gf2bv_xl4_cubic_expand_batch_words",
     "gf2bv_solve_xl4_cubic_guess_words", "gf2bv_solve_xl4_cubic_guess_terms", "gf2bv_xl4_cubic_guess_chunk", "gf2bv_xl4_cubic_guess_chunk_device",
-    "gf2bv_quad_search", "gf2bv_quad_search_alloc", "gf2bv_quad_free", "gf2bv_quad_plan", "gf2bv_quad_points", "gf2bv_quad_forms_search", "gf2bv_quad_last_times",
+    "gf2bv_quad_search", "gf2bv_quad_search_alloc", "gf2bv_quad_free", "gf2bv_quad_plan", "gf2bv_quad_plan_device", "gf2bv_quad_points", "gf2bv_quad_forms_search", "gf2bv_quad_last_times",
     "gf2bv_slab_work_words", "gf2bv_slab_tiles", "gf2bv_slab_open", "gf2bv_slab_blocks", "gf2bv_slab_owner",
     "gf2bv_slab_payload_bytes", "gf2bv_slab_factor", "gf2bv_slab_apply", "gf2bv_slab_factor_on", "gf2bv_slab_apply_on",
     "gf2bv_slab_finish_local", "gf2bv_slab_solve",
@@ -144,6 +144,7 @@ def lib():
         L.gf2bv_quad_free.argtypes = [vp]
         L.gf2bv_quad_free.restype = None
         L.gf2bv_quad_plan.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, i64]
+        L.gf2bv_quad_plan_device.argtypes = [vp, vp, i64, i64, i64, i32, vp, vp, vp, vp, vp, i64]
         L.gf2bv_quad_points.argtypes = [vp, vp, i64, i64, i64, vp, i64, i64, vp]
         L.gf2bv_quad_forms_search.argtypes = [vp, i64, i64, i32, i64, vp, vp]
         L.gf2bv_quad_last_times.argtypes = [vp]
@@ -587,16 +588,21 @@ def quad_words(n_lin: int) -> int:
     return (n_lin + n_lin * (n_lin - 1) // 2 + 63) // 64
 
 
-def quad_plan(origin: int, basis, n_lin: int) -> dict:
-    """gf2bv_quad_plan (host only): r, r_eff (-1: not reduced), and the forms as equation ints over r_eff unknowns."""
+def quad_plan(origin: int, basis, n_lin: int, device: int | None = None) -> dict:
+    """gf2bv_quad_plan (host only): r, r_eff (-1: not reduced), and the forms as equation ints over r_eff unknowns.  With a
+    device: gf2bv_quad_plan_device, the same plan with the forms built by k_quad_forms on that device."""
     words = quad_words(n_lin)
     o, b = _ints_to_words([origin], words), _ints_to_words(list(basis), words)
     r, re, m, fw = (ctypes.c_int64() for _ in range(4))
-    _check(lib().gf2bv_quad_plan(o.ctypes.data, b.ctypes.data, len(basis), words, n_lin, ctypes.byref(r), ctypes.byref(re),
-                                 ctypes.byref(m), ctypes.byref(fw), None, 0))
+
+    def plan(forms, cap):
+        head = (o.ctypes.data, b.ctypes.data, len(basis), words, n_lin)
+        tail = (ctypes.byref(r), ctypes.byref(re), ctypes.byref(m), ctypes.byref(fw), forms, cap)
+        _check(lib().gf2bv_quad_plan(*head, *tail) if device is None else lib().gf2bv_quad_plan_device(*head, device, *tail))
+
+    plan(None, 0)
     forms = np.zeros((max(m.value, 1), max(fw.value, 1)), dtype=np.uint64)
-    _check(lib().gf2bv_quad_plan(o.ctypes.data, b.ctypes.data, len(basis), words, n_lin, ctypes.byref(r), ctypes.byref(re),
-                                 ctypes.byref(m), ctypes.byref(fw), forms.ctypes.data, m.value))
+    plan(forms.ctypes.data, m.value)
     return {"r": r.value, "r_eff": re.value, "forms": _words_to_ints(forms, m.value)}
 
 

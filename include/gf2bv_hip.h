@@ -320,6 +320,8 @@ void gf2bv_space_close(gf2bv_space *space);
  * the equation-int layout of a QuadraticSystem of r_eff unknowns (bit 0 = constant, bit 1 + v = variable v, bit
  * 1 + r_eff + i(i-1)/2 + j = the product of variables i and j, j < i), written when forms != NULL and m <= forms_cap.  No
  * consistent point at all: r_eff = 0 and the single form 1.
+ * gf2bv_quad_plan_device: the same plan with the forms built by the device kernel of gf2bv_quad_search (k_quad_forms) instead of
+ * its host twin, so that the two can be compared; argument errors return GF2BV_ERR_ARG before any device is touched.
  * gf2bv_quad_points (host only): the points (words each) that nys common zeros ys (y_words each) of those forms stand for.
  * gf2bv_quad_forms_search: every common zero of m forms (that layout, r_eff <= 40) by the device search, ascending;
  * *count = their number, the first max_out written.
@@ -332,6 +334,8 @@ int  gf2bv_quad_search_alloc(const uint64_t *origin, const uint64_t *basis, int6
 void gf2bv_quad_free(uint64_t *words);
 int  gf2bv_quad_plan(const uint64_t *origin, const uint64_t *basis, int64_t dimension, int64_t words, int64_t n_lin,
                      int64_t *r, int64_t *r_eff, int64_t *m, int64_t *form_words, uint64_t *forms, int64_t forms_cap);
+int  gf2bv_quad_plan_device(const uint64_t *origin, const uint64_t *basis, int64_t dimension, int64_t words, int64_t n_lin, int device,
+                            int64_t *r, int64_t *r_eff, int64_t *m, int64_t *form_words, uint64_t *forms, int64_t forms_cap);
 int  gf2bv_quad_points(const uint64_t *origin, const uint64_t *basis, int64_t dimension, int64_t words, int64_t n_lin,
                        const uint64_t *ys, int64_t nys, int64_t y_words, uint64_t *out_words);
 int  gf2bv_quad_forms_search(const uint64_t *forms, int64_t m, int64_t r_eff, int device, int64_t max_out, int64_t *count,

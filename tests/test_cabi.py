@@ -108,6 +108,16 @@ def test_single_entries_check_arguments_before_device_use():
     err(L.gf2bv_slab_open(A, 99, cols, 2, W, WW, 1, 0, 0, H), "greater than or equal")
     err(L.gf2bv_slab_open(A, rows, cols, 2, W, WW - 1, 1, 0, 0, H), "too small")
     assert not h.value
+    # gf2bv_quad_plan_device: the space and the outputs are checked like gf2bv_quad_plan's, in front of the device
+    r, re, m, fw = (ctypes.c_int64() for _ in range(4))
+    outs = (ctypes.byref(r), ctypes.byref(re), ctypes.byref(m), ctypes.byref(fw), None, 0)
+    err(L.gf2bv_quad_plan_device(None, A, 0, 2, 10, 0, *outs), "null")
+    err(L.gf2bv_quad_plan_device(A, None, 3, 2, 10, 0, *outs), "null")
+    err(L.gf2bv_quad_plan_device(A, A, -1, 2, 10, 0, *outs), "dimension")
+    err(L.gf2bv_quad_plan_device(A, A, 0, 2, 0, 0, *outs), "n_lin")
+    err(L.gf2bv_quad_plan_device(A, A, 0, 1, 12, 0, *outs), "words does not cover")
+    err(L.gf2bv_quad_plan_device(A, A, 0, 2, 10, 0, None, *outs[1:]), "null")
+    err(L.gf2bv_quad_plan_device(A, A, 0, 2, 10, 0, *outs[:3], None, None, 0), "null")
 
 
 def test_batch_entries_check_arguments_before_device_use():
