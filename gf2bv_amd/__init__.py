@@ -9,6 +9,7 @@ There is no CPU fallback: importing works anywhere, solving needs the GPU.
 from ._internal import AffineSpace, eqs_to_sage_mat_helper, m4ri_solve, mul_bit_quad, to_bits, tuple_where, xor_tuple
 from .bitvec import BitVec
 from .linsys import DimensionTooLargeError, LinearSystem, QuadraticSystem, Zeros
+from .search import search_all_cubic, search_all_xl, search_one_cubic, search_one_xl
 
 
 def __getattr__(name):
@@ -26,5 +27,6 @@ __all__ = [
     "AffineSpace", "BitVec", "DimensionTooLargeError", "LinearSystem", "PackedBitVec", "PackedCubicBitVec", "PackedCubicGuessSystem",
     "PackedCubicSystem", "PackedLinearSystem",
     "PackedQuadBitVec", "PackedQuadraticSystem", "QuadraticSystem", "Zeros",
-    "eqs_to_sage_mat_helper", "m4ri_solve", "mul_bit_quad", "to_bits", "tuple_where", "xor_tuple",
+    "eqs_to_sage_mat_helper", "m4ri_solve", "mul_bit_quad", "search_all_cubic", "search_all_xl", "search_one_cubic", "search_one_xl",
+    "to_bits", "tuple_where", "xor_tuple",
 ]

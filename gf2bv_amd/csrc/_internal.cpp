@@ -241,7 +241,9 @@ PyObject *iter_next_slow(SpaceIterObject *self)
 }
 
 PyObject *QuadGaveUp;      // _internal.QuadSearchGaveUp(message, lin_rank)
+PyObject *CubicGaveUp;     // _internal.CubicSearchGaveUp(message, lin_rank)
 PyObject *space_quad_search(AffineSpaceObject *self, PyObject *const *args, Py_ssize_t nargs);
+PyObject *space_cubic_search(AffineSpaceObject *self, PyObject *const *args, Py_ssize_t nargs);
 
 PyGetSetDef space_getset[] = {
 	{"dimension", (getter)space_dimension, nullptr, "Dimension of the affine space", nullptr},
@@ -257,6 +259,9 @@ PyMethodDef space_methods[] = {
 	 "quad_search(n_lin, max_enum=32, max_solutions=65536, first=False)\n--\n\nThe consistent points of a QuadraticSystem space (product "
 	 "coordinates = products of the n_lin linear bits), in iteration order, searched on the GPU (first=True: the first max_solutions of "
 	 "them, however many there are); not in the reference."},
+	{"cubic_search", (PyCFunction)(void (*)(void))space_cubic_search, METH_FASTCALL,
+	 "cubic_search(n_lin, max_enum=32, max_solutions=65536, first=False)\n--\n\nquad_search for a space over the degree-3 columns (pair "
+	 "and triple coordinates = products of the n_lin linear bits): degree-3 XL's and PackedCubicSystem's; not in the reference."},
 	{nullptr, nullptr, 0, nullptr}};
 
 PyType_Slot space_slots[] = {
@@ -1749,10 +1754,12 @@ PyObject *py_sage_helper(PyObject *, PyObject *const *args, Py_ssize_t nargs)
 // AffineSpace.quad_search(n_lin, max_enum=32, max_solutions=65536, first=False): the consistent points of the space (every
 // product coordinate the product of its linear bits), in iteration order, found on the device (gf2bv_quad_search_alloc).
 // More than max_solutions points: ValueError -- or, with first=True, the first max_solutions of them.  Not in the reference.
-PyObject *space_quad_search(AffineSpaceObject *self, PyObject *const *args, Py_ssize_t nargs)
+// AffineSpace.cubic_search: the same over the degree-3 columns (gf2bv_cubic_search_alloc), CubicSearchGaveUp when it gives up.
+PyObject *space_search(AffineSpaceObject *self, PyObject *const *args, Py_ssize_t nargs, bool cubic)
 {
 	if (nargs < 1 || nargs > 4) {
-		PyErr_SetString(PyExc_TypeError, "quad_search(n_lin, max_enum=32, max_solutions=65536, first=False)");
+		PyErr_SetString(PyExc_TypeError, cubic ? "cubic_search(n_lin, max_enum=32, max_solutions=65536, first=False)"
+		                                       : "quad_search(n_lin, max_enum=32, max_solutions=65536, first=False)");
 		return nullptr;
 	}
 	const long long n_lin = PyLong_AsLongLong(args[0]);
@@ -1768,8 +1775,8 @@ PyObject *space_quad_search(AffineSpaceObject *self, PyObject *const *args, Py_s
 	uint64_t *pts = nullptr;                  // exactly min(count, max_solutions) points, owned by the library
 	int rc;
 	Py_BEGIN_ALLOW_THREADS
-	rc = gf2bv_quad_search_alloc(self->origin, self->basis, self->dim, self->words, n_lin, (int)max_enum, max_sol, device, &count,
-	                             &lin_rank, &pts);
+	rc = (cubic ? gf2bv_cubic_search_alloc : gf2bv_quad_search_alloc)(self->origin, self->basis, self->dim, self->words, n_lin,
+	                                                                  (int)max_enum, max_sol, device, &count, &lin_rank, &pts);
 	Py_END_ALLOW_THREADS
 	if (rc == GF2BV_ERR_NOMEM && count > max_sol) {     // more than 2^22 points: too many to order
 		gf2bv_quad_free(pts);
@@ -1780,13 +1787,18 @@ PyObject *space_quad_search(AffineSpaceObject *self, PyObject *const *args, Py_s
 			PyErr_Format(PyExc_ValueError, "%lld consistent points, more than max_solutions (%lld)", (long long)count, max_sol);
 		return nullptr;
 	}
-	if (rc != GF2BV_OK) { gf2bv_quad_free(pts); return raise_rc(rc, "quad_search"); }
+	if (rc != GF2BV_OK) { gf2bv_quad_free(pts); return raise_rc(rc, cubic ? "cubic_search" : "quad_search"); }
 	if (count < 0) {
 		gf2bv_quad_free(pts);
-		PyObject *msg = PyUnicode_FromFormat("the search gave up: the space's projection onto the %lld linear coordinates has rank %lld, "
-		                                     "and neither a search (max_enum %lld) nor relinearisation gets below it",
+		PyObject *msg = PyUnicode_FromFormat(cubic ? "the search gave up: the space's projection onto the %lld linear coordinates has rank %lld, "
+		                                             "and the affine elimination does not get it down to max_enum (%lld) or it is above 64"
+		                                           : "the search gave up: the space's projection onto the %lld linear coordinates has rank %lld, "
+		                                             "and neither a search (max_enum %lld) nor relinearisation gets below it",
 		                                     n_lin, (long long)lin_rank, max_enum);
-		if (msg) { PyObject *e = Py_BuildValue("(NL)", msg, (long long)lin_rank); if (e) { PyErr_SetObject(QuadGaveUp, e); Py_DECREF(e); } }
+		if (msg) {
+			PyObject *e = Py_BuildValue("(NL)", msg, (long long)lin_rank);
+			if (e) { PyErr_SetObject(cubic ? CubicGaveUp : QuadGaveUp, e); Py_DECREF(e); }
+		}
 		return nullptr;
 	}
 	if (count > max_sol && !first) {
@@ -1804,6 +1816,9 @@ PyObject *space_quad_search(AffineSpaceObject *self, PyObject *const *args, Py_s
 	gf2bv_quad_free(pts);
 	return t;
 }
+
+PyObject *space_quad_search(AffineSpaceObject *self, PyObject *const *args, Py_ssize_t nargs) { return space_search(self, args, nargs, false); }
+PyObject *space_cubic_search(AffineSpaceObject *self, PyObject *const *args, Py_ssize_t nargs) { return space_search(self, args, nargs, true); }
 
 // _space_from_ints(cols, origin, basis): build an AffineSpace from host integers.  Not part of the
 // reference surface; lets the CPU test-suite exercise get()/iteration order without a GPU.
@@ -1929,8 +1944,10 @@ PyMODINIT_FUNC PyInit__internal(void)
 	Py_INCREF(AffineSpace_Type); Py_INCREF(SpaceIterGray_Type); Py_INCREF(SpaceIterSlow_Type); Py_INCREF(Factorization_Type);
 	QuadGaveUp = PyErr_NewException("_internal.QuadSearchGaveUp", PyExc_RuntimeError, nullptr);
 	if (!QuadGaveUp) { Py_DECREF(m); return nullptr; }
-	Py_INCREF(QuadGaveUp);
-	if (PyModule_AddObject(m, "QuadSearchGaveUp", QuadGaveUp) < 0 ||
+	CubicGaveUp = PyErr_NewException("_internal.CubicSearchGaveUp", PyExc_RuntimeError, nullptr);
+	if (!CubicGaveUp) { Py_DECREF(m); return nullptr; }
+	Py_INCREF(QuadGaveUp); Py_INCREF(CubicGaveUp);
+	if (PyModule_AddObject(m, "QuadSearchGaveUp", QuadGaveUp) < 0 || PyModule_AddObject(m, "CubicSearchGaveUp", CubicGaveUp) < 0 ||
 	    PyModule_AddObject(m, "AffineSpace", (PyObject *)AffineSpace_Type) < 0 ||
 	    PyModule_AddObject(m, "Factorization", (PyObject *)Factorization_Type) < 0 ||
 	    PyModule_AddObject(m, "AffineSpaceIterator", (PyObject *)SpaceIterGray_Type) < 0 ||

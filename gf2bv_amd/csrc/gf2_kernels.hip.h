@@ -5597,3 +5597,221 @@ k_cubic_specialise(const u64 *__restrict__ cubic, i64 m, i64 cubic_stride, int n
 		}
 	}
 }
+
+
+// ==========================================================================================
+// CUBIC SEARCH: the consistent points of a solution space over the degree-3 columns
+// ==========================================================================================
+// (host side and the mathematics: gf2bv_cubic_search in gf2_solver.hip)
+//
+// A cubic form over R <= 64 unknowns is an equation int of fw = ceil((1 + R + C(R,2) + C(R,3)) / 64) words: bit 0 the constant,
+// bit 1 + k unknown k, bit 1 + R + C(i,2) + j the product of unknowns j < i, bit 1 + R + C(R,2) + C(i,3) + C(j,2) + l the product
+// of unknowns l < j < i -- the layout of a PackedCubicSystem of R unknowns.
+//
+// k_cubic_products: one workgroup per product coordinate s of the space (members mem[3 s ..], the third -1 for a pair): the form
+// v_s = l_a l_b (l_c) ^ q_s, every l and q an affine form of W <= 2 words (bit 0 = constant, bit 1 + k = unknown k).  A thread forms
+// whole output words, stepping the monomial along the layout.  The coefficient of a monomial x_M in a product of affine forms in
+// GF(2)[x] / (x^2 + x) is the Moebius sum XOR_{T subset of M} prod_F F(1_T), F(1_T) = F_0 ^ XOR_{v in T} F_v: at most 8 subsets of 3
+// parities each, and x^2 = x is folded in by construction (the sum sees the product only as a function on the cube).
+// k_cubic_forms: one workgroup per form t: F_t = XOR of v_s over the support of t (sup_idx[sup_off[t] .. sup_off[t + 1]): t's own
+// coordinate and the pivots whose K row has a bit at t) -- the second pass, a sparse GF(2) product with coalesced rows.
+__device__ __forceinline__ u64 cf_bit(const u64 *f, int v) { return (f[(v + 1) >> 6] >> ((v + 1) & 63)) & 1; }
+__global__ void __launch_bounds__(256)
+k_cubic_products(const u64 *__restrict__ lin, const u64 *__restrict__ qaff, const int *__restrict__ mem, int R, int W, int fw,
+                 u64 *__restrict__ V)
+{
+	__shared__ u64 ops[3][2];
+	const i64 s = blockIdx.x;
+	const int nf = mem[3 * s + 2] >= 0 ? 3 : 2;
+	if (threadIdx.x < 6) {
+		const int f = threadIdx.x >> 1, w = threadIdx.x & 1;
+		ops[f][w] = (f < nf && w < W) ? lin[(i64)mem[3 * s + f] * W + w] : 0;
+	}
+	__syncthreads();
+	const int nbits = 1 + R + R * (R - 1) / 2 + R * (R - 1) * (R - 2) / 6;
+	for (int w = threadIdx.x; w < fw; w += blockDim.x) {
+		int q = w * 64, kind, a = 0, b = 0, c = 0;            // the monomial of bit q: kind members, a > b > c
+		if (q == 0) kind = 0;
+		else if (q <= R) { kind = 1; a = q - 1; }
+		else if (q < 1 + R + R * (R - 1) / 2) { kind = 2; const int p = q - 1 - R; a = (int)xl_tri_root(p); b = p - (int)xl_c2(a); }
+		else {
+			kind = 3;
+			const int t = q - 1 - R - R * (R - 1) / 2;
+			a = (int)xl_tet_root(t);
+			const int rem = t - (int)xl_c3(a);
+			b = (int)xl_tri_root(rem); c = rem - (int)xl_c2(b);
+		}
+		u64 word = 0;
+		for (int k = 0; k < 64 && q < nbits; k++, q++) {
+			// bit 0 of fm: the form's constant; bits 1..kind: its coefficients at the monomial's members
+			unsigned fm[3];
+			for (int f = 0; f < 3; f++) {
+				unsigned x = (unsigned)(ops[f][0] & 1);
+				if (kind >= 1) x |= (unsigned)cf_bit(ops[f], a) << 1;
+				if (kind >= 2) x |= (unsigned)cf_bit(ops[f], b) << 2;
+				if (kind >= 3) x |= (unsigned)cf_bit(ops[f], c) << 3;
+				fm[f] = x;
+			}
+			unsigned coef = 0;
+			for (unsigned T = 0; T < (1u << kind); T++) {
+				const unsigned mask = 1u | (T << 1);
+				unsigned p = __popc(fm[0] & mask) & __popc(fm[1] & mask);
+				if (nf == 3) p &= __popc(fm[2] & mask);
+				coef ^= p;
+			}
+			word |= (u64)(coef & 1) << k;
+			if (kind == 0) { kind = 1; a = 0; }
+			else if (kind == 1) { if (++a == R) { kind = 2; a = 1; b = 0; } }
+			else if (kind == 2) { if (++b == a) { b = 0; if (++a == R) { kind = 3; a = 2; b = 1; c = 0; } } }
+			else if (++c == b) { c = 0; if (++b == a) { a++; b = 1; } }
+		}
+		if (w < W) word ^= qaff[s * W + w];
+		V[s * (i64)fw + w] = word;
+	}
+}
+
+__global__ void __launch_bounds__(256)
+k_cubic_forms(const u64 *__restrict__ V, const i64 *__restrict__ sup_off, const int *__restrict__ sup_idx, int fw, u64 *__restrict__ out)
+{
+	const i64 t = blockIdx.x, k0 = sup_off[t], k1 = sup_off[t + 1];
+	for (int w = threadIdx.x; w < fw; w += blockDim.x) {
+		u64 acc = 0;
+		for (i64 k = k0; k < k1; k++) acc ^= V[(i64)sup_idx[k] * fw + w];
+		out[t * (i64)fw + w] = acc;
+	}
+}
+
+// k_cubic_check and the fused mode of k_cubic_search: E holds every form outside the first pass as ew = 2 + R + C(R,2) words
+// [constant, linear mask, U_0 .. U_{R-1}, T_{01}, T_{02}, T_{12}, T_{03}, ...]: U_j has bit k > j set when the form has x_j x_k,
+// T_{jk} (j < k, at 2 + R + C(k,2) + j) has bit l > k set when it has x_j x_k x_l.  Then
+// F(y) = c ^ par(lin & y) ^ XOR_{j in y} par(U_j & y) ^ XOR_{j < k in y} par(T_jk & y): one popcount per set bit and per set
+// bit pair of y.
+__device__ __forceinline__ u64 cubic_form_value(const u64 *__restrict__ e, int R, u64 y)
+{
+	u64 acc = e[0] + (u64)__popcll(e[1] & y);
+	const u64 *U = e + 2, *T = e + 2 + R;
+	for (u64 bj = y; bj; bj &= bj - 1) {
+		const int j = ctz64(bj);
+		acc += (u64)__popcll(U[j] & y);
+		for (u64 bk = bj & (bj - 1); bk; bk &= bk - 1) {
+			const int k = ctz64(bk);
+			acc += (u64)__popcll(T[k * (k - 1) / 2 + j] & y);
+		}
+	}
+	return acc & 1;
+}
+__device__ __forceinline__ bool cubic_all_vanish(const u64 *__restrict__ E, i64 m, int R, u64 y)
+{
+	const i64 ew = 2 + R + R * (R - 1) / 2;
+	for (i64 f = 0; f < m; f++)
+		if (cubic_form_value(E + f * ew, R, y)) return false;
+	return true;
+}
+
+// k_cubic_search: every common zero of 64 cubic forms in R <= 64 variables, bit-sliced (bit f of a word = form f).
+// tab: [K | Lw[R] | Sw[C(R,2)] | Tw[C(R,3)]]: the constants, the linear coefficients, the pair coefficients (a < b at C(b,2) + a)
+// and the triple coefficients (a < b < c at C(c,3) + C(b,2) + a).  Lane g fixes the high H = R - L variables to the bits of g and walks
+// the low L in Gray order, so the three lowest set bits k1 < k2 < k3 of the step index i are the same in every lane:
+//   d2[k1][k2] ^= Tw[k1][k2][k3] (k3 exists; a scalar load), d1[k1] ^= d2[k1][k2] (k2 exists), v ^= d1[k1], zero test.
+// Before step i the low point is g(i - 1) = e_{k1-1} ^ e_{k2-1} ^ (Gray code of i >> (k2 + 1), above k2): d1[k] starts as the first
+// derivative of the lane's restricted form at e_{k-1}; d2[k1][k2] as its second derivative at e_{k1-1} ^ e_{k2-1} (its value is
+// independent of x_k1 and x_k2); between two uses of d2[k1][k2] exactly x_k3 flips.
+// State: L + L(L-1)/2 words a lane in LDS, one column per thread (slot * blockDim + tid); one wavefront per workgroup, L <= 12:
+// 78 words a lane, 39 KiB a workgroup, four workgroups a CU.  Appends and `cap`: as k_quad_search.  With E != nullptr (the first
+// pass left more candidates than the list holds) the lane tests its candidate against the m forms of E itself -- the forms that are
+// not among the 64 of the table -- and appends only the common zeros of all.
+__device__ __forceinline__ int cs_pr(int a, int b) { return b * (b - 1) / 2 + a; }
+__device__ __forceinline__ int cs_tr(int a, int b, int c) { return c * (c - 1) * (c - 2) / 6 + b * (b - 1) / 2 + a; }
+__global__ void __launch_bounds__(64)
+k_cubic_search(const u64 *__restrict__ tab, int R, int L, u64 nlanes, u64 *__restrict__ list, u64 cap,
+               unsigned long long *__restrict__ count, const u64 *__restrict__ E, i64 m)
+{
+	extern __shared__ u64 cds[];
+	const u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+	if (g >= nlanes) return;                          // (no barrier below)
+	const u64 *Lw = tab + 1, *Sw = Lw + R, *Tw = Sw + R * (R - 1) / 2;
+	const int H = R - L, bd = blockDim.x, tid = threadIdx.x;
+	u64 v = tab[0];
+	for (int j = 0; j < H; j++) {
+		if (!((g >> j) & 1)) continue;
+		v ^= Lw[L + j];
+		for (int j2 = j + 1; j2 < H; j2++) {
+			if (!((g >> j2) & 1)) continue;
+			v ^= Sw[cs_pr(L + j, L + j2)];
+			for (int j3 = j2 + 1; j3 < H; j3++)
+				if ((g >> j3) & 1) v ^= Tw[cs_tr(L + j, L + j2, L + j3)];
+		}
+	}
+	for (int k = 0; k < L; k++) {
+		u64 lam = Lw[k];
+		for (int j = 0; j < H; j++) {
+			if (!((g >> j) & 1)) continue;
+			lam ^= Sw[cs_pr(k, L + j)];
+			for (int j2 = j + 1; j2 < H; j2++)
+				if ((g >> j2) & 1) lam ^= Tw[cs_tr(k, L + j, L + j2)];
+		}
+		if (k) {                                      // the derivative at e_{k-1}, where k is first flipped
+			lam ^= Sw[cs_pr(k - 1, k)];
+			for (int j = 0; j < H; j++)
+				if ((g >> j) & 1) lam ^= Tw[cs_tr(k - 1, k, L + j)];
+		}
+		cds[k * bd + tid] = lam;
+	}
+	for (int k2 = 1; k2 < L; k2++)
+		for (int k1 = 0; k1 < k2; k1++) {
+			u64 s = Sw[cs_pr(k1, k2)];
+			for (int j = 0; j < H; j++)
+				if ((g >> j) & 1) s ^= Tw[cs_tr(k1, k2, L + j)];
+			if (k1 >= 1) s ^= Tw[cs_tr(k1 - 1, k1, k2)];
+			if (k2 - 1 > k1) s ^= Tw[cs_tr(k1, k2 - 1, k2)];
+			cds[(L + cs_pr(k1, k2)) * bd + tid] = s;
+		}
+	const u64 base = L < 64 ? g << L : 0;
+	if (v == 0 && (!E || cubic_all_vanish(E, m, R, base))) {
+		const unsigned long long at = atomicAdd(count, 1ull);
+		if (at < cap) list[at] = base;
+	}
+	const u64 steps = 1ull << L;
+	for (u64 i = 1; i < steps; i++) {
+		const int k1 = ctz64(i);
+		const u64 rest = i & (i - 1);
+		u64 d = cds[k1 * bd + tid];
+		if (rest) {
+			const int k2 = ctz64(rest);
+			const u64 rest2 = rest & (rest - 1);
+			const int slot = (L + cs_pr(k1, k2)) * bd + tid;
+			u64 e = cds[slot];
+			if (rest2) {
+				e ^= Tw[cs_tr(k1, k2, ctz64(rest2))];
+				cds[slot] = e;
+			}
+			d ^= e;
+			cds[k1 * bd + tid] = d;
+		}
+		v ^= d;
+		if (v == 0 && (!E || cubic_all_vanish(E, m, R, base | (i ^ (i >> 1))))) {
+			const unsigned long long at = atomicAdd(count, 1ull);
+			if (at < cap) list[at] = base | (i ^ (i >> 1));
+		}
+	}
+}
+
+// k_cubic_check: the second pass.  One wavefront per candidate point y, lanes over the forms (layout E above); a candidate at which
+// every form vanishes is appended to out.
+__global__ void __launch_bounds__(256)
+k_cubic_check(const u64 *__restrict__ E, i64 m, int R, const u64 *__restrict__ cand, u64 ncand, u64 *__restrict__ out,
+              u64 cap, unsigned long long *__restrict__ count)
+{
+	const int lane = threadIdx.x & 63;
+	const i64 ew = 2 + R + R * (R - 1) / 2;
+	const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((u64)gridDim.x * blockDim.x) >> 6;
+	for (u64 c = wave; c < ncand; c += nwaves) {
+		const u64 y = cand[c];
+		u64 bad = 0;
+		for (i64 f = lane; f < m; f += 64) bad |= cubic_form_value(E + f * ew, R, y);
+		if (!wave_or(bad) && lane == 0) {
+			const unsigned long long at = atomicAdd(count, 1ull);
+			if (at < cap) out[at] = y;
+		}
+	}
+}

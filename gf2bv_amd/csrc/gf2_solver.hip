@@ -12,6 +12,7 @@
 #include "../../include/gf2bv_hip.h"
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -4096,9 +4097,10 @@ struct QuadPlan {
 };
 
 // step 1 and the inputs of step 2
-void quad_reduce(QuadPlan &P, const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n)
+// (S product coordinates behind the n linear ones: C(n,2) here, C(n,2) + C(n,3) for the cubic search)
+void quad_reduce(QuadPlan &P, const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n, i64 S)
 {
-	P.n = n; P.S = n * (n - 1) / 2; P.N = n + P.S; P.words = words; P.d = d; P.dw = std::max<i64>(1, (d + 63) / 64);
+	P.n = n; P.S = S; P.N = n + P.S; P.words = words; P.d = d; P.dw = std::max<i64>(1, (d + 63) / 64);
 	P.origin.assign(origin, origin + words);
 	P.V.assign(basis, basis + d * words);
 	P.T.assign((size_t)(d * P.dw), 0);
@@ -4333,6 +4335,27 @@ int quad_forms_device(QuadPlan &P, int device, hipStream_t st)
 	return GF2BV_OK;
 }
 
+// the first 64 forms (fw words each) that are linearly independent, in their order
+std::vector<i64> first_independent_forms(const u64 *forms, i64 m, i64 fw)
+{
+	std::vector<i64> chosen;
+	std::vector<u64> red;                          // reduced chosen forms, each with its pivot bit
+	std::vector<i64> piv;
+	std::vector<u64> v((size_t)fw);
+	for (i64 f = 0; f < m && (i64)chosen.size() < 64; f++) {
+		std::copy(forms + f * fw, forms + (f + 1) * fw, v.begin());
+		for (size_t k = 0; k < piv.size(); k++) if (qbit(v.data(), piv[k])) qxor(v.data(), &red[k * fw], fw);
+		i64 p = -1;
+		for (i64 w = 0; w < fw && p < 0; w++) if (v[w]) p = w * 64 + __builtin_ctzll(v[w]);
+		if (p < 0) continue;
+		for (size_t k = 0; k < piv.size(); k++) if (qbit(&red[k * fw], p)) qxor(&red[k * fw], v.data(), fw);
+		red.insert(red.end(), v.begin(), v.end());
+		piv.push_back(p);
+		chosen.push_back(f);
+	}
+	return chosen;
+}
+
 // every common zero of m forms (equation-int layout, fw words) in R <= kQuadMaxEnum variables; `total` counts them all,
 // `ys` holds them when there are at most kQuadMaxPoints (in no particular order)
 int quad_search_device(const u64 *forms, i64 m, i64 fw, int R, int device, hipStream_t st, std::vector<u64> &ys, u64 *total)
@@ -4347,23 +4370,7 @@ int quad_search_device(const u64 *forms, i64 m, i64 fw, int R, int device, hipSt
 	auto pair_bit = [&](i64 j, i64 k) { return 1 + R + (k > j ? k * (k - 1) / 2 + j : j * (j - 1) / 2 + k); };
 	// the 64 forms of the first pass: the first that are linearly independent (a form in the span of those already chosen
 	// removes no candidate, and leading forms of low rank are common -- pair coordinates over few variables come first)
-	std::vector<i64> chosen;
-	{
-		std::vector<u64> red;                      // reduced chosen forms, each with its pivot bit
-		std::vector<i64> piv;
-		std::vector<u64> v((size_t)fw);
-		for (i64 f = 0; f < m && (i64)chosen.size() < 64; f++) {
-			std::copy(forms + f * fw, forms + (f + 1) * fw, v.begin());
-			for (size_t k = 0; k < piv.size(); k++) if (qbit(v.data(), piv[k])) qxor(v.data(), &red[k * fw], fw);
-			i64 p = -1;
-			for (i64 w = 0; w < fw && p < 0; w++) if (v[w]) p = w * 64 + __builtin_ctzll(v[w]);
-			if (p < 0) continue;
-			for (size_t k = 0; k < piv.size(); k++) if (qbit(&red[k * fw], p)) qxor(&red[k * fw], v.data(), fw);
-			red.insert(red.end(), v.begin(), v.end());
-			piv.push_back(p);
-			chosen.push_back(f);
-		}
-	}
+	const std::vector<i64> chosen = first_independent_forms(forms, m, fw);
 	std::vector<u64> tab((size_t)(1 + R + R * R), 0), E((size_t)(m * (R + 2)), 0);
 	for (i64 f = 0; f < m; f++) {                  // every form in k_quad_check's layout
 		u64 *e = &E[f * (R + 2)];
@@ -4428,7 +4435,7 @@ int quad_search_device(const u64 *forms, i64 m, i64 fw, int R, int device, hipSt
 int quad_plan_build(QuadPlan &P, const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n, int device, hipStream_t st)
 {
 	auto t0 = std::chrono::steady_clock::now();
-	quad_reduce(P, origin, basis, d, words, n);
+	quad_reduce(P, origin, basis, d, words, n, n * (n - 1) / 2);
 	if (P.r > kQuadMaxRank) { P.reff = -1; g_quad_times.reduce += ms_since(t0); return GF2BV_OK; }
 	quad_inputs(P);
 	g_quad_times.reduce += ms_since(t0);
@@ -4523,6 +4530,61 @@ void quad_plan_export(const QuadPlan &P, int64_t *r, int64_t *r_eff, int64_t *m,
 	*m = P.reff < 0 ? 0 : P.m;
 	*form_words = P.reff < 0 ? 0 : P.fw;
 	if (forms && P.reff >= 0 && P.m <= forms_cap) std::copy(P.forms.begin(), P.forms.begin() + P.m * P.fw, reinterpret_cast<u64 *>(forms));
+}
+
+// What gf2bv_quad_search_alloc and gf2bv_cubic_search_alloc do once their arguments are checked: the pool stream, `collect` (every
+// consistent point with its coefficients in the space's basis), AffineSpace order, the first max_solutions points in a malloc'ed buffer
+using CollectFn = std::function<int(hipStream_t, std::vector<u64> &, std::vector<u64> &, u64 *, bool *)>;
+int search_alloc(QuadTimes &times, int64_t dimension, int64_t words, int64_t max_solutions, int device, int64_t *count, int64_t *lin_rank,
+                 uint64_t **out_words, const CollectFn &collect)
+{
+	*count = 0; *lin_rank = 0; *out_words = nullptr;
+	int rc = check_device(device);
+	if (rc) return rc;
+	times = QuadTimes();
+	const auto t0 = std::chrono::steady_clock::now();
+	hipStream_t st = nullptr;
+	HIPCHK(pool().stream(&st, device, 0));
+	std::unique_ptr<void, std::function<void(void *)>> keep(st, [&](void *) { pool().release_stream(st, device, 0); });
+	std::vector<u64> pts, coef;
+	u64 total = 0;
+	bool gave_up = false;
+	rc = collect(st, pts, coef, &total, &gave_up);
+	times.total = ms_since(t0);
+	if (rc) return rc;
+	if (gave_up) { *count = -1; return GF2BV_OK; }
+	*count = (int64_t)total;
+	if ((i64)total > kQuadMaxPoints) {
+		if (max_solutions > 0) return fail(GF2BV_ERR_NOMEM, "more than 2^22 consistent points: too many to collect and order");
+		return GF2BV_OK;
+	}
+	// iteration order of AffineSpace: the Gray walk for dimension <= 64 (inverse-Gray index of the coefficients), the
+	// binary walk above (the coefficients as an integer, basis[0] the least significant bit)
+	const i64 np = (i64)total, dw = std::max<i64>(1, (dimension + 63) / 64);
+	std::vector<i64> order((size_t)np);
+	for (i64 k = 0; k < np; k++) order[k] = k;
+	if (dimension <= 64) {
+		std::vector<u64> key((size_t)np);
+		for (i64 k = 0; k < np; k++) {
+			u64 g = coef[k * dw];
+			for (int sh = 1; sh < 64; sh <<= 1) g ^= g >> sh;
+			key[k] = g;
+		}
+		std::sort(order.begin(), order.end(), [&](i64 a, i64 b) { return key[a] < key[b]; });
+	} else {
+		std::sort(order.begin(), order.end(), [&](i64 a, i64 b) {
+			for (i64 w = dw - 1; w >= 0; w--)
+				if (coef[a * dw + w] != coef[b * dw + w]) return coef[a * dw + w] < coef[b * dw + w];
+			return false;
+		});
+	}
+	const i64 nout = std::min<i64>(np, max_solutions);
+	if (nout == 0) return GF2BV_OK;
+	uint64_t *out = static_cast<uint64_t *>(malloc(sizeof(uint64_t) * (size_t)(nout * words)));
+	if (!out) return fail(GF2BV_ERR_NOMEM, "out of host memory");
+	for (i64 k = 0; k < nout; k++) memcpy(out + k * words, &pts[order[k] * words], sizeof(uint64_t) * (size_t)words);
+	*out_words = out;
+	return GF2BV_OK;
 }
 
 }  // namespace
@@ -4637,54 +4699,11 @@ int gf2bv_quad_search_alloc(const uint64_t *origin_, const uint64_t *basis_, int
 	if (!count || !lin_rank || !out_words) return fail(GF2BV_ERR_ARG, "null pointer");
 	if (max_enum < 0 || max_enum > kQuadMaxEnum) return fail(GF2BV_ERR_ARG, "max_enum must be 0..40");
 	if (max_solutions < 0) return fail(GF2BV_ERR_ARG, "max_solutions must be >= 0");
-	*count = 0; *lin_rank = 0; *out_words = nullptr;
-	rc = check_device(device);
-	if (rc) return rc;
-	g_quad_times = QuadTimes();
-	const auto t0 = std::chrono::steady_clock::now();
-	hipStream_t st = nullptr;
-	HIPCHK(pool().stream(&st, device, 0));
-	std::unique_ptr<void, std::function<void(void *)>> keep(st, [&](void *) { pool().release_stream(st, device, 0); });
-	std::vector<u64> pts, coef;
-	u64 total = 0;
-	bool gave_up = false;
-	rc = quad_collect(origin, basis, dimension, words, n_lin, max_enum, device, st, 0, 0, pts, coef, &total,
-	                  reinterpret_cast<i64 *>(lin_rank), &gave_up);
-	g_quad_times.total = ms_since(t0);
-	if (rc) return rc;
-	if (gave_up) { *count = -1; return GF2BV_OK; }
-	*count = (int64_t)total;
-	if ((i64)total > kQuadMaxPoints) {
-		if (max_solutions > 0) return fail(GF2BV_ERR_NOMEM, "more than 2^22 consistent points: too many to collect and order");
-		return GF2BV_OK;
-	}
-	// iteration order of AffineSpace: the Gray walk for dimension <= 64 (inverse-Gray index of the coefficients), the
-	// binary walk above (the coefficients as an integer, basis[0] the least significant bit)
-	const i64 np = (i64)total, dw = std::max<i64>(1, (dimension + 63) / 64);
-	std::vector<i64> order((size_t)np);
-	for (i64 k = 0; k < np; k++) order[k] = k;
-	if (dimension <= 64) {
-		std::vector<u64> key((size_t)np);
-		for (i64 k = 0; k < np; k++) {
-			u64 g = coef[k * dw];
-			for (int sh = 1; sh < 64; sh <<= 1) g ^= g >> sh;
-			key[k] = g;
-		}
-		std::sort(order.begin(), order.end(), [&](i64 a, i64 b) { return key[a] < key[b]; });
-	} else {
-		std::sort(order.begin(), order.end(), [&](i64 a, i64 b) {
-			for (i64 w = dw - 1; w >= 0; w--)
-				if (coef[a * dw + w] != coef[b * dw + w]) return coef[a * dw + w] < coef[b * dw + w];
-			return false;
-		});
-	}
-	const i64 nout = std::min<i64>(np, max_solutions);
-	if (nout == 0) return GF2BV_OK;
-	uint64_t *out = static_cast<uint64_t *>(malloc(sizeof(uint64_t) * (size_t)(nout * words)));
-	if (!out) return fail(GF2BV_ERR_NOMEM, "out of host memory");
-	for (i64 k = 0; k < nout; k++) memcpy(out + k * words, &pts[order[k] * words], sizeof(uint64_t) * (size_t)words);
-	*out_words = out;
-	return GF2BV_OK;
+	return search_alloc(g_quad_times, dimension, words, max_solutions, device, count, lin_rank, out_words,
+	                    [&](hipStream_t st, std::vector<u64> &pts, std::vector<u64> &coef, u64 *total, bool *gave_up) {
+		return quad_collect(origin, basis, dimension, words, n_lin, max_enum, device, st, 0, 0, pts, coef, total,
+		                    reinterpret_cast<i64 *>(lin_rank), gave_up);
+	});
 	});
 }
 
@@ -4694,6 +4713,480 @@ void gf2bv_quad_last_times(double *out8)
 {
 	if (!out8) return;
 	const QuadTimes &t = g_quad_times;
+	const double v[8] = {t.reduce, t.forms, t.affine, t.search, t.relin, t.total, (double)t.levels, (double)t.candidates};
+	std::copy(v, v + 8, out8);
+}
+
+}  // extern "C"
+
+// ---- cubic search: the consistent points of a solution space over the degree-3 columns -----------------------------------
+//   A space x(c) = o ^ B c over n linear coordinates followed by the C(n,2) pair and the C(n,3) triple
+// coordinates (the columns of degree-3 XL and of PackedCubicSystem).  Step 1 is the quadratic search's with N = cols3 (quad_reduce,
+// quad_inputs).  Step 2: one CUBIC form in r variables per product coordinate outside P (k_cubic_products, k_cubic_forms).  Affine
+// forms are eliminated by re-parametrising: they are solved as a linear system, c_a = c_0 ^ G y over the free variables y, the affine
+// inputs are composed with that map and the forms rebuilt in fewer variables, until no affine form appears.  Step 3:
+// r_eff <= max_enum: k_cubic_search + k_cubic_check; above: the search gives up (there is no relinearisation level).
+namespace {
+
+constexpr i64 kCubicMaxRank = 64;               // larger projection ranks are not reduced (a point of the forms is one word)
+constexpr i64 kCubicFormsBytes = 1ll << 30;     // what the forms of one build (products and forms) or of one search may take
+constexpr int kCubicMaxEnum = 40;
+constexpr int kCubicWalk = 12;                  // low variables a lane of k_cubic_search walks (78 words of LDS a lane)
+
+thread_local QuadTimes g_cubic_times;
+
+inline i64 cubic_width(i64 R) { return 1 + R + R * (R - 1) / 2 + R * (R - 1) * (R - 2) / 6; }
+
+struct CubicPlan : QuadPlan {                    // (lin, qaff: the affine inputs in the R variables left; M unused)
+	std::vector<int> mem;                        // S x 3: the members of a product coordinate, the third -1 for a pair
+	std::vector<u64> lin0, qaff0;                // the affine inputs in the r coefficients c_a
+	std::vector<u64> amap;                       // r x W: c_a as an affine form in the R variables left (bit 0 constant, bit 1 + v)
+	i64 R = 0, rounds = 0;
+};
+
+void cubic_reduce(CubicPlan &P, const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n)
+{
+	const i64 S2 = n * (n - 1) / 2, S3 = n * (n - 1) * (n - 2) / 6;
+	quad_reduce(P, origin, basis, d, words, n, S2 + S3);
+	if (P.r > kCubicMaxRank) return;
+	quad_inputs(P);
+	P.lin0.swap(P.lin); P.qaff0.swap(P.qaff);
+	P.lin.assign(P.lin0.size(), 0); P.qaff.assign(P.qaff0.size(), 0);
+	P.mem.assign((size_t)(3 * std::max<i64>(P.S, 1)), -1);
+	for (i64 s = 0; s < S2; s++) { P.mem[3 * s] = P.pair_i[s]; P.mem[3 * s + 1] = P.pair_j[s]; }
+	i64 s = S2;
+	for (i64 i = 2; i < n; i++) for (i64 j = 1; j < i; j++) for (i64 l = 0; l < j; l++, s++) {
+		P.mem[3 * s] = (int)i; P.mem[3 * s + 1] = (int)j; P.mem[3 * s + 2] = (int)l;
+	}
+	P.R = P.r;
+	P.amap.assign((size_t)(std::max<i64>(P.r, 1) * P.W), 0);
+	for (i64 a = 0; a < P.r; a++) qflip(&P.amap[a * P.W], a + 1);
+}
+
+// an affine form in the c_a composed with amap
+void cubic_compose_form(const CubicPlan &P, const u64 *f, u64 *o)
+{
+	std::fill(o, o + P.W, 0);
+	if (f[0] & 1) o[0] = 1;
+	for (i64 a = 1; a <= P.r; a++) if (qbit(f, a)) qxor(o, &P.amap[(a - 1) * P.W], P.W);
+}
+void cubic_compose(CubicPlan &P)
+{
+	for (i64 i = 0; i < P.n; i++) cubic_compose_form(P, &P.lin0[i * P.W], &P.lin[i * P.W]);
+	for (i64 s = 0; s < P.S; s++) cubic_compose_form(P, &P.qaff0[s * P.W], &P.qaff[s * P.W]);
+}
+
+// the host twin of k_cubic_products + k_cubic_forms (gf2bv_cubic_plan never touches a device): polynomial multiplication, monomial by
+// monomial, through a decode table of the layout
+void cubic_forms_host(const CubicPlan &P, i64 fw, std::vector<u64> &F)
+{
+	const i64 R = P.R, W = P.W, nb = cubic_width(R), o2 = 1 + R, o3 = o2 + R * (R - 1) / 2;
+	std::vector<std::array<int, 3>> dec((size_t)nb, std::array<int, 3>{-1, -1, -1});
+	for (i64 k = 0; k < R; k++) dec[1 + k] = {(int)k, -1, -1};
+	for (i64 i = 1, q = o2; i < R; i++) for (i64 j = 0; j < i; j++, q++) dec[q] = {(int)i, (int)j, -1};
+	for (i64 i = 2, q = o3; i < R; i++) for (i64 j = 1; j < i; j++) for (i64 l = 0; l < j; l++, q++) dec[q] = {(int)i, (int)j, (int)l};
+	auto with = [&](std::array<int, 3> mm, int v) -> i64 {      // the bit of the monomial mm (at most two members) times x_v
+		if (mm[0] != v && mm[1] != v) { mm[2] = v; std::sort(mm.begin(), mm.end(), std::greater<int>()); }
+		if (mm[0] < 0) return 0;
+		if (mm[1] < 0) return 1 + mm[0];
+		if (mm[2] < 0) return o2 + (i64)mm[0] * (mm[0] - 1) / 2 + mm[1];
+		return o3 + (i64)mm[0] * (mm[0] - 1) * (mm[0] - 2) / 6 + (i64)mm[1] * (mm[1] - 1) / 2 + mm[2];
+	};
+	auto mul = [&](const std::vector<u64> &f, const u64 *aff, std::vector<u64> &out) {      // f of degree <= 2 times an affine form
+		std::fill(out.begin(), out.end(), 0);
+		for (i64 w = 0; w < fw; w++)
+			for (u64 bits = f[w]; bits; bits &= bits - 1) {
+				const i64 q = w * 64 + __builtin_ctzll(bits);
+				if (aff[0] & 1) qflip(out.data(), q);
+				for (i64 v = 0; v < R; v++) if (qbit(aff, v + 1)) qflip(out.data(), with(dec[q], (int)v));
+			}
+	};
+	std::vector<u64> V((size_t)(std::max<i64>(P.S, 1) * fw), 0), a((size_t)fw), b((size_t)fw);
+	for (i64 s = 0; s < P.S; s++) {
+		std::fill(a.begin(), a.end(), 0);
+		std::copy(&P.lin[(i64)P.mem[3 * s] * W], &P.lin[(i64)P.mem[3 * s] * W] + std::min(W, fw), a.begin());
+		mul(a, &P.lin[(i64)P.mem[3 * s + 1] * W], b);
+		if (P.mem[3 * s + 2] >= 0) { mul(b, &P.lin[(i64)P.mem[3 * s + 2] * W], a); a.swap(b); }
+		qxor(b.data(), &P.qaff[s * W], std::min(W, fw));
+		std::copy(b.begin(), b.end(), &V[s * fw]);
+	}
+	F.assign((size_t)(std::max<i64>(P.m0, 1) * fw), 0);
+	for (i64 t = 0; t < P.m0; t++)
+		for (i64 k = P.sup_off[t]; k < P.sup_off[t + 1]; k++) qxor(&F[t * fw], &V[(i64)P.sup_idx[k] * fw], fw);
+}
+
+int cubic_forms_device(const CubicPlan &P, i64 fw, std::vector<u64> &F, int device, hipStream_t st)
+{
+	F.assign((size_t)(std::max<i64>(P.m0, 1) * fw), 0);
+	if (P.m0 == 0) return GF2BV_OK;
+	QDev dl, dq, dm, dso, dsi, dv, dout;
+	HIPCHK(dl.get(P.lin.size() * 8, device)); HIPCHK(dq.get(P.qaff.size() * 8, device)); HIPCHK(dm.get(P.mem.size() * 4, device));
+	HIPCHK(dso.get(P.sup_off.size() * 8, device)); HIPCHK(dsi.get(P.sup_idx.size() * 4, device));
+	HIPCHK(dv.get((size_t)(P.S * fw) * 8, device)); HIPCHK(dout.get((size_t)(P.m0 * fw) * 8, device));
+	HIPCHK(hipMemcpyAsync(dl.p, P.lin.data(), P.lin.size() * 8, hipMemcpyHostToDevice, st));
+	HIPCHK(hipMemcpyAsync(dq.p, P.qaff.data(), P.qaff.size() * 8, hipMemcpyHostToDevice, st));
+	HIPCHK(hipMemcpyAsync(dm.p, P.mem.data(), P.mem.size() * 4, hipMemcpyHostToDevice, st));
+	HIPCHK(hipMemcpyAsync(dso.p, P.sup_off.data(), P.sup_off.size() * 8, hipMemcpyHostToDevice, st));
+	HIPCHK(hipMemcpyAsync(dsi.p, P.sup_idx.data(), P.sup_idx.size() * 4, hipMemcpyHostToDevice, st));
+	k_cubic_products<<<dim3((unsigned)P.S), dim3(256), 0, st>>>(dl.as<u64>(), dq.as<u64>(), dm.as<int>(), (int)P.R, (int)P.W, (int)fw, dv.as<u64>());
+	HIPCHK(hipGetLastError());
+	k_cubic_forms<<<dim3((unsigned)P.m0), dim3(256), 0, st>>>(dv.as<u64>(), dso.as<i64>(), dsi.as<int>(), (int)fw, dout.as<u64>());
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(F.data(), dout.p, (size_t)(P.m0 * fw) * 8, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipStreamSynchronize(st));
+	return GF2BV_OK;
+}
+
+// One round of the affine elimination: the affine forms among F (m0 x fw, R variables) solved as a linear system and amap composed with
+// its solution.  false: no affine form but zeros (nothing changed).  P.inconsistent: the system has no solution.
+bool cubic_affine_round(CubicPlan &P, i64 fw, const std::vector<u64> &F)
+{
+	const i64 R = P.R, W = P.W, aw = std::min(W, fw), w0 = (R + 1) >> 6;
+	std::vector<u64> rows, v((size_t)W);                   // reduced affine forms, each with its pivot variable's bit
+	std::vector<i64> piv;
+	for (i64 f = 0; f < P.m0; f++) {
+		const u64 *e = &F[f * fw];
+		bool affine = true;
+		if (w0 < fw) {
+			affine = (e[w0] >> ((R + 1) & 63)) == 0;
+			for (i64 w = w0 + 1; w < fw && affine; w++) affine = e[w] == 0;
+		}
+		if (!affine) continue;
+		std::fill(v.begin(), v.end(), 0);
+		std::copy(e, e + aw, v.begin());
+		for (size_t k = 0; k < piv.size(); k++) if (qbit(v.data(), piv[k])) qxor(v.data(), &rows[k * W], W);
+		i64 p = -1;
+		for (i64 w = 0; w < W && p < 0; w++) { const u64 x = v[w] & (w ? ~0ull : ~1ull); if (x) p = w * 64 + __builtin_ctzll(x); }
+		if (p < 0) {
+			if (v[0] & 1) { P.inconsistent = true; return true; }
+			continue;
+		}
+		for (size_t k = 0; k < piv.size(); k++) if (qbit(&rows[k * W], p)) qxor(&rows[k * W], v.data(), W);
+		rows.insert(rows.end(), v.begin(), v.end());
+		piv.push_back(p);
+	}
+	if (piv.empty()) return false;
+	std::vector<i64> row_of((size_t)(R + 1), -1), fresh((size_t)(R + 1), -1);
+	for (size_t k = 0; k < piv.size(); k++) row_of[piv[k]] = (i64)k;
+	i64 nr = 0;
+	for (i64 b = 1; b <= R; b++) if (row_of[b] < 0) fresh[b] = ++nr;              // bit of the free variable in the new forms
+	std::vector<u64> sub((size_t)((R + 1) * W), 0);        // variable bit b as an affine form in the variables left
+	for (i64 b = 1; b <= R; b++) {
+		u64 *o = &sub[b * W];
+		if (row_of[b] < 0) { qflip(o, fresh[b]); continue; }
+		const u64 *e = &rows[row_of[b] * W];
+		if (e[0] & 1) o[0] = 1;
+		for (i64 c = 1; c <= R; c++) if (c != b && qbit(e, c)) qflip(o, fresh[c]);
+	}
+	std::vector<u64> next((size_t)(std::max<i64>(P.r, 1) * W), 0);
+	for (i64 a = 0; a < P.r; a++) {
+		const u64 *e = &P.amap[a * W];
+		u64 *o = &next[a * W];
+		if (e[0] & 1) o[0] = 1;
+		for (i64 b = 1; b <= R; b++) if (qbit(e, b)) qxor(o, &sub[b * W], W);
+	}
+	P.amap.swap(next);
+	P.R = nr;
+	return true;
+}
+
+int cubic_plan_build(CubicPlan &P, const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n, int device, hipStream_t st)
+{
+	auto t0 = std::chrono::steady_clock::now();
+	cubic_reduce(P, origin, basis, d, words, n);
+	g_cubic_times.reduce += ms_since(t0);
+	if (P.r > kCubicMaxRank) { P.reff = -1; return GF2BV_OK; }
+	std::vector<u64> F;
+	i64 fw = 1;
+	for (;;) {
+		t0 = std::chrono::steady_clock::now();
+		cubic_compose(P);
+		fw = (cubic_width(P.R) + 63) / 64;
+		if ((P.S + P.m0) * fw * 8 > kCubicFormsBytes)
+			return fail(GF2BV_ERR_NOMEM, "the cubic forms of this space take more than 1 GiB");
+		if (device < 0) cubic_forms_host(P, fw, F);
+		else { int rc = cubic_forms_device(P, fw, F, device, st); if (rc) return rc; }
+		g_cubic_times.forms += ms_since(t0);
+		t0 = std::chrono::steady_clock::now();
+		P.rounds++;
+		const bool changed = cubic_affine_round(P, fw, F);
+		g_cubic_times.affine += ms_since(t0);
+		if (P.inconsistent) { P.reff = 0; P.fw = 1; P.m = 1; P.forms.assign(1, 1); return GF2BV_OK; }
+		if (!changed) break;
+	}
+	P.reff = P.R; P.fw = fw; P.m = 0;
+	P.forms.clear();
+	for (i64 f = 0; f < P.m0; f++)
+		if (!qzero(&F[f * fw], fw)) { P.forms.insert(P.forms.end(), &F[f * fw], &F[f * fw] + fw); P.m++; }
+	if (P.forms.empty()) P.forms.assign((size_t)fw, 0);
+	return GF2BV_OK;
+}
+
+// the point of the space that effective assignment y (reff <= 64 bits) extends to; c_orig: its coefficients (dw words)
+bool cubic_point(const CubicPlan &P, u64 y, u64 *x, u64 *c_orig)
+{
+	const i64 r = P.r, W = P.W, words = P.words;
+	const u64 ye[2] = {1ull | (y << 1), y >> 63};
+	std::copy(P.origin.begin(), P.origin.end(), x);
+	std::fill(c_orig, c_orig + P.dw, 0);
+	for (i64 a = 0; a < r; a++) {
+		u64 par = 0;
+		for (i64 w = 0; w < W; w++) par ^= P.amap[a * W + w] & ye[w];
+		if (__builtin_popcountll(par) & 1) { qxor(x, &P.V[a * words], words); qxor(c_orig, &P.T[a * P.dw], P.dw); }
+	}
+	auto prod = [&](i64 s) {
+		bool v = qbit(x, P.mem[3 * s]) & qbit(x, P.mem[3 * s + 1]);
+		if (P.mem[3 * s + 2] >= 0) v &= qbit(x, P.mem[3 * s + 2]);
+		return v;
+	};
+	for (size_t k = 0; k < P.kpiv.size(); k++) {
+		const i64 s = P.kpiv[k];
+		if (prod(s) != qbit(x, P.n + s)) { qxor(x, &P.V[(r + (i64)k) * words], words); qxor(c_orig, &P.T[(r + (i64)k) * P.dw], P.dw); }
+	}
+	for (i64 s = 0; s < P.S; s++) if (prod(s) != qbit(x, P.n + s)) return false;
+	return true;
+}
+
+// every common zero of m cubic forms (equation-int layout, fw words) in R <= kCubicMaxEnum variables; total, ys: as quad_search_device
+int cubic_search_device(const u64 *forms, i64 m, i64 fw, int R, int device, hipStream_t st, std::vector<u64> &ys, u64 *total)
+{
+	ys.clear();
+	if (m == 0) {                                  // no form: the whole cube
+		*total = 1ull << R;
+		if ((i64)*total <= kQuadMaxPoints) for (u64 y = 0; y < *total; y++) ys.push_back(y);
+		return GF2BV_OK;
+	}
+	const i64 nb = cubic_width(R), ew = 2 + R + (i64)R * (R - 1) / 2, o2 = 1 + R, o3 = o2 + (i64)R * (R - 1) / 2;
+	if (m * ew * 8 > kCubicFormsBytes) return fail(GF2BV_ERR_NOMEM, "the cubic forms of this search take more than 1 GiB");
+	static_assert(kQuadMaxCand == kQuadMaxPoints, "the candidate list doubles as the list of zeros");
+	const std::vector<i64> chosen = first_independent_forms(forms, m, fw);
+	// the second pass tests the forms the first did not hold (a chosen form vanishes at every candidate; a zero form everywhere)
+	std::vector<char> in_first((size_t)m, 0);
+	for (i64 f : chosen) in_first[f] = 1;
+	std::vector<i64> rest;
+	for (i64 f = 0; f < m; f++) if (!in_first[f] && !qzero(forms + f * fw, fw)) rest.push_back(f);
+	const i64 mr = (i64)rest.size();
+	std::vector<u64> tab((size_t)nb, 0), E((size_t)(std::max<i64>(mr, 1) * ew), 0);
+	for (i64 g = 0; g < mr; g++) {                 // in k_cubic_check's layout
+		const u64 *src = forms + rest[g] * fw;
+		u64 *e = &E[g * ew];
+		e[0] = src[0] & 1;
+		for (i64 k = 0; k < R; k++) if (qbit(src, 1 + k)) e[1] |= 1ull << k;
+		for (i64 k = 1, q = o2; k < R; k++) for (i64 j = 0; j < k; j++, q++) if (qbit(src, q)) e[2 + j] |= 1ull << k;
+		for (i64 l = 2, q = o3; l < R; l++) for (i64 k = 1; k < l; k++) for (i64 j = 0; j < k; j++, q++)
+			if (qbit(src, q)) e[2 + R + k * (k - 1) / 2 + j] |= 1ull << l;
+	}
+	for (size_t c = 0; c < chosen.size(); c++) {   // the chosen ones bit-sliced: bit c of every word; tab is indexed like a form's bits
+		const u64 *src = forms + chosen[c] * fw;
+		for (i64 q = 0; q < nb; q++) if (qbit(src, q)) tab[q] |= 1ull << c;
+	}
+	const int L = std::min(R, kCubicWalk), H = R - L;
+	const u64 nlanes = 1ull << H;
+	const dim3 grid((unsigned)((nlanes + 63) / 64));
+	const size_t lds = (size_t)64 * (L + L * (L - 1) / 2) * 8;
+	const u64 ocap = (u64)kQuadMaxPoints, cap = (u64)kQuadMaxCand;
+	QDev dtab, dE, dcand, dcnt, dout;
+	HIPCHK(dtab.get(tab.size() * 8, device)); HIPCHK(dE.get(E.size() * 8, device)); HIPCHK(dcnt.get(16, device));
+	HIPCHK(hipMemcpyAsync(dtab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, st));
+	HIPCHK(hipMemcpyAsync(dE.p, E.data(), E.size() * 8, hipMemcpyHostToDevice, st));
+	HIPCHK(hipMemsetAsync(dcnt.p, 0, 16, st));
+	HIPCHK(dcand.get(cap * 8, device));
+	HIPCHK(dout.get(ocap * 8, device));
+	k_cubic_search<<<grid, dim3(64), lds, st>>>(dtab.as<u64>(), R, L, nlanes, dcand.as<u64>(), cap, dcnt.as<unsigned long long>(), nullptr, 0);
+	HIPCHK(hipGetLastError());
+	u64 cnt[2] = {0, 0};
+	HIPCHK(hipMemcpyAsync(cnt, dcnt.p, 8, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipStreamSynchronize(st));
+	g_cubic_times.candidates += (i64)cnt[0];
+	const void *found = dout.p;
+	if (mr == 0) {
+		cnt[1] = cnt[0];                           // every form was in the first pass: its candidates are the zeros (cap == ocap)
+		found = dcand.p;
+	} else if (cnt[0] > cap) {
+		// more candidates than can be kept: search again, each lane testing its candidates against the other forms itself
+		k_cubic_search<<<grid, dim3(64), lds, st>>>(dtab.as<u64>(), R, L, nlanes, dout.as<u64>(), ocap, dcnt.as<unsigned long long>() + 1,
+		                                            dE.as<u64>(), mr);
+		HIPCHK(hipGetLastError());
+	} else if (cnt[0]) {
+		const u64 waves = std::min<u64>(cnt[0], 8192);
+		k_cubic_check<<<dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st>>>(dE.as<u64>(), mr, R, dcand.as<u64>(), cnt[0], dout.as<u64>(),
+		                                                                      ocap, dcnt.as<unsigned long long>() + 1);
+		HIPCHK(hipGetLastError());
+	}
+	if (mr) {
+		HIPCHK(hipMemcpyAsync(cnt + 1, dcnt.as<u64>() + 1, 8, hipMemcpyDeviceToHost, st));
+		HIPCHK(hipStreamSynchronize(st));
+	}
+	*total = cnt[1];
+	if ((i64)cnt[1] <= kQuadMaxPoints) {
+		ys.resize((size_t)cnt[1]);
+		if (cnt[1]) HIPCHK(hipMemcpyAsync(ys.data(), found, cnt[1] * 8, hipMemcpyDeviceToHost, st));
+		HIPCHK(hipStreamSynchronize(st));
+	}
+	return GF2BV_OK;
+}
+
+// every consistent point of the space and its coefficients: quad_collect without the relinearisation level
+int cubic_collect(const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n, int max_enum, int device, hipStream_t st,
+                  std::vector<u64> &pts, std::vector<u64> &coef, u64 *total, i64 *lin_rank, bool *gave_up)
+{
+	pts.clear(); coef.clear(); *total = 0;
+	CubicPlan P;
+	int rc = cubic_plan_build(P, origin, basis, d, words, n, device, st);
+	g_cubic_times.levels = P.rounds;
+	*lin_rank = P.r;
+	if (rc) return rc;
+	if (P.reff < 0 || (!P.inconsistent && P.reff > max_enum)) { *gave_up = true; return GF2BV_OK; }
+	if (P.inconsistent) return GF2BV_OK;
+	std::vector<u64> ys;
+	auto t0 = std::chrono::steady_clock::now();
+	rc = cubic_search_device(P.forms.data(), P.m, P.fw, (int)P.reff, device, st, ys, total);
+	g_cubic_times.search += ms_since(t0);
+	if (rc) return rc;
+	if ((i64)*total > kQuadMaxPoints) return GF2BV_OK;
+	const i64 np = (i64)ys.size();
+	pts.assign((size_t)(np * words), 0);
+	coef.assign((size_t)(np * P.dw), 0);
+	for (i64 k = 0; k < np; k++)
+		if (!cubic_point(P, ys[k], &pts[k * words], &coef[k * P.dw]))
+			return fail(GF2BV_ERR_HIP, "cubic search: a point that passed the forms is not consistent (internal error)");
+	return GF2BV_OK;
+}
+
+int check_cubic_space(const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n_lin)
+{
+	if (!origin || (d > 0 && !basis)) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (d < 0 || words <= 0) return fail(GF2BV_ERR_ARG, "dimension must be >= 0 and words > 0");
+	if (n_lin < 1 || n_lin > 2000) return fail(GF2BV_ERR_ARG, "n_lin must be 1..2000");
+	if (words < (n_lin + n_lin * (n_lin - 1) / 2 + n_lin * (n_lin - 1) * (n_lin - 2) / 6 + 63) / 64)
+		return fail(GF2BV_ERR_ARG, "words does not cover n_lin + C(n_lin,2) + C(n_lin,3) columns");
+	return GF2BV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gf2bv_cubic_plan(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin,
+                     int64_t *r, int64_t *r_eff, int64_t *m, int64_t *form_words, uint64_t *forms_, int64_t forms_cap)
+{
+	const u64 *origin = reinterpret_cast<const u64 *>(origin_), *basis = reinterpret_cast<const u64 *>(basis_);
+	return catching([&]() -> int {
+	int rc = check_cubic_space(origin, basis, dimension, words, n_lin);
+	if (rc) return rc;
+	if (!r || !r_eff || !m || !form_words) return fail(GF2BV_ERR_ARG, "null pointer");
+	CubicPlan P;
+	rc = cubic_plan_build(P, origin, basis, dimension, words, n_lin, -1, nullptr);
+	if (rc) return rc;
+	quad_plan_export(P, r, r_eff, m, form_words, forms_, forms_cap);
+	return GF2BV_OK;
+	});
+}
+
+int gf2bv_cubic_plan_device(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin, int device,
+                            int64_t *r, int64_t *r_eff, int64_t *m, int64_t *form_words, uint64_t *forms_, int64_t forms_cap)
+{
+	const u64 *origin = reinterpret_cast<const u64 *>(origin_), *basis = reinterpret_cast<const u64 *>(basis_);
+	return guarded([&]() -> int {
+	int rc = check_cubic_space(origin, basis, dimension, words, n_lin);
+	if (rc) return rc;
+	if (!r || !r_eff || !m || !form_words) return fail(GF2BV_ERR_ARG, "null pointer");
+	rc = check_device(device);
+	if (rc) return rc;
+	hipStream_t st = nullptr;
+	HIPCHK(pool().stream(&st, device, 0));
+	std::unique_ptr<void, std::function<void(void *)>> keep(st, [&](void *) { pool().release_stream(st, device, 0); });
+	CubicPlan P;
+	rc = cubic_plan_build(P, origin, basis, dimension, words, n_lin, device, st);
+	if (rc) return rc;
+	quad_plan_export(P, r, r_eff, m, form_words, forms_, forms_cap);
+	return GF2BV_OK;
+	});
+}
+
+int gf2bv_cubic_points(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin,
+                       const uint64_t *ys_, int64_t nys, int64_t y_words, uint64_t *out_words_)
+{
+	const u64 *origin = reinterpret_cast<const u64 *>(origin_), *basis = reinterpret_cast<const u64 *>(basis_);
+	const u64 *ys = reinterpret_cast<const u64 *>(ys_);
+	u64 *out_words = reinterpret_cast<u64 *>(out_words_);
+	return catching([&]() -> int {
+	int rc = check_cubic_space(origin, basis, dimension, words, n_lin);
+	if (rc) return rc;
+	if (nys < 0 || (nys > 0 && (!ys || !out_words))) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (y_words < 1) return fail(GF2BV_ERR_ARG, "y_words does not cover r_eff bits");
+	CubicPlan P;
+	rc = cubic_plan_build(P, origin, basis, dimension, words, n_lin, -1, nullptr);
+	if (rc) return rc;
+	if (P.reff < 0 || P.inconsistent) return fail(GF2BV_ERR_ARG, "the space has no forms to map from");
+	std::vector<u64> c((size_t)P.dw);
+	for (i64 k = 0; k < nys; k++)
+		if (!cubic_point(P, ys[k * y_words], out_words + k * words, c.data()))
+			return fail(GF2BV_ERR_ARG, "an assignment that is not a common zero of the forms");
+	return GF2BV_OK;
+	});
+}
+
+int gf2bv_cubic_forms_search(const uint64_t *forms_, int64_t m, int64_t r_eff, int device, int64_t max_out, int64_t *count,
+                             uint64_t *out_)
+{
+	const u64 *forms = reinterpret_cast<const u64 *>(forms_);
+	u64 *out = reinterpret_cast<u64 *>(out_);
+	return guarded([&]() -> int {
+	if (!count || (m > 0 && !forms) || (max_out > 0 && !out) || m < 0 || max_out < 0) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (r_eff < 0 || r_eff > kCubicMaxEnum) return fail(GF2BV_ERR_ARG, "r_eff must be 0..40");
+	*count = 0;
+	int rc = check_device(device);
+	if (rc) return rc;
+	hipStream_t st = nullptr;
+	HIPCHK(pool().stream(&st, device, 0));
+	std::unique_ptr<void, std::function<void(void *)>> keep(st, [&](void *) { pool().release_stream(st, device, 0); });
+	std::vector<u64> ys;
+	u64 total = 0;
+	rc = cubic_search_device(forms, m, (cubic_width(r_eff) + 63) / 64, (int)r_eff, device, st, ys, &total);
+	if (rc) return rc;
+	*count = (int64_t)total;
+	if ((i64)total > kQuadMaxPoints && max_out > 0) return fail(GF2BV_ERR_NOMEM, "more common zeros than can be collected");
+	std::sort(ys.begin(), ys.end());
+	std::copy(ys.begin(), ys.begin() + std::min<i64>((i64)ys.size(), max_out), out);
+	return GF2BV_OK;
+	});
+}
+
+int gf2bv_cubic_search(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin,
+                       int max_enum, int64_t max_solutions, int device, int64_t *count, int64_t *lin_rank, uint64_t *out_words_)
+{
+	if (max_solutions > 0 && !out_words_) return fail(GF2BV_ERR_ARG, "null pointer");
+	uint64_t *pts = nullptr;
+	const int rc = gf2bv_cubic_search_alloc(origin_, basis_, dimension, words, n_lin, max_enum, max_solutions, device, count, lin_rank,
+	                                        &pts);
+	if (rc == GF2BV_OK && pts) memcpy(out_words_, pts, sizeof(uint64_t) * (size_t)(std::min<int64_t>(*count, max_solutions) * words));
+	gf2bv_quad_free(pts);
+	return rc;
+}
+
+int gf2bv_cubic_search_alloc(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin,
+                             int max_enum, int64_t max_solutions, int device, int64_t *count, int64_t *lin_rank, uint64_t **out_words)
+{
+	const u64 *origin = reinterpret_cast<const u64 *>(origin_), *basis = reinterpret_cast<const u64 *>(basis_);
+	return guarded([&]() -> int {
+	int rc = check_cubic_space(origin, basis, dimension, words, n_lin);
+	if (rc) return rc;
+	if (!count || !lin_rank || !out_words) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (max_enum < 0 || max_enum > kCubicMaxEnum) return fail(GF2BV_ERR_ARG, "max_enum must be 0..40");
+	if (max_solutions < 0) return fail(GF2BV_ERR_ARG, "max_solutions must be >= 0");
+	return search_alloc(g_cubic_times, dimension, words, max_solutions, device, count, lin_rank, out_words,
+	                    [&](hipStream_t st, std::vector<u64> &pts, std::vector<u64> &coef, u64 *total, bool *gave_up) {
+		return cubic_collect(origin, basis, dimension, words, n_lin, max_enum, device, st, pts, coef, total,
+		                     reinterpret_cast<i64 *>(lin_rank), gave_up);
+	});
+	});
+}
+
+void gf2bv_cubic_last_times(double *out8)
+{
+	if (!out8) return;
+	const QuadTimes &t = g_cubic_times;
 	const double v[8] = {t.reduce, t.forms, t.affine, t.search, t.relin, t.total, (double)t.levels, (double)t.candidates};
 	std::copy(v, v + 8, out8);
 }

@@ -49,6 +49,7 @@ EXPORTS = [
     "gf2bv_cubic_specialise_device", "gf2bv_cubic_specialise_words", "gf2bv_xl4_cubic_expand_batch_device", "gf2bv_xl4_cubic_expand_batch_words",
     "gf2bv_solve_xl4_cubic_guess_words", "gf2bv_solve_xl4_cubic_guess_terms", "gf2bv_xl4_cubic_guess_chunk", "gf2bv_xl4_cubic_guess_chunk_device",
     "gf2bv_quad_search", "gf2bv_quad_search_alloc", "gf2bv_quad_free", "gf2bv_quad_plan", "gf2bv_quad_plan_device", "gf2bv_quad_points", "gf2bv_quad_forms_search", "gf2bv_quad_last_times",
+    "gf2bv_cubic_search", "gf2bv_cubic_search_alloc", "gf2bv_cubic_plan", "gf2bv_cubic_plan_device", "gf2bv_cubic_points", "gf2bv_cubic_forms_search", "gf2bv_cubic_last_times",
     "gf2bv_slab_work_words", "gf2bv_slab_tiles", "gf2bv_slab_open", "gf2bv_slab_blocks", "gf2bv_slab_owner",
     "gf2bv_slab_payload_bytes", "gf2bv_slab_factor", "gf2bv_slab_apply", "gf2bv_slab_factor_on", "gf2bv_slab_apply_on",
     "gf2bv_slab_finish_local", "gf2bv_slab_solve",
@@ -149,6 +150,14 @@ def lib():
         L.gf2bv_quad_forms_search.argtypes = [vp, i64, i64, i32, i64, vp, vp]
         L.gf2bv_quad_last_times.argtypes = [vp]
         L.gf2bv_quad_last_times.restype = None
+        L.gf2bv_cubic_search.argtypes = L.gf2bv_quad_search.argtypes
+        L.gf2bv_cubic_search_alloc.argtypes = L.gf2bv_quad_search_alloc.argtypes
+        L.gf2bv_cubic_plan.argtypes = L.gf2bv_quad_plan.argtypes
+        L.gf2bv_cubic_plan_device.argtypes = L.gf2bv_quad_plan_device.argtypes
+        L.gf2bv_cubic_points.argtypes = L.gf2bv_quad_points.argtypes
+        L.gf2bv_cubic_forms_search.argtypes = L.gf2bv_quad_forms_search.argtypes
+        L.gf2bv_cubic_last_times.argtypes = [vp]
+        L.gf2bv_cubic_last_times.restype = None
         L.gf2bv_quad_expand_device.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, i64, i32, vp]
         L.gf2bv_quad_expand_words.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, i64, i32]
         L.gf2bv_solve_quad_terms.argtypes = [vp, vp, vp, vp, i64, i64, i64, i32, i32, pp]
@@ -632,6 +641,57 @@ def quad_last_times() -> dict:
     """this thread's last gf2bv_quad_search: phase times in ms, levels, first-pass candidates"""
     v = (ctypes.c_double * 8)()
     lib().gf2bv_quad_last_times(v)
+    keys = ("ms_reduce", "ms_forms", "ms_affine", "ms_search", "ms_relin", "ms_total", "levels", "candidates")
+    return dict(zip(keys, list(v)))
+
+
+# -- the same over the degree-3 columns (gf2bv_cubic_*): n_lin + C(n_lin,2) + C(n_lin,3) coordinates, cubic forms ----------------------------
+def cubic_cols(n_lin: int) -> int:
+    return n_lin + n_lin * (n_lin - 1) // 2 + n_lin * (n_lin - 1) * (n_lin - 2) // 6
+
+
+def cubic_plan(origin: int, basis, n_lin: int, device: int | None = None) -> dict:
+    """gf2bv_cubic_plan (host only): r, r_eff (-1: r above 64, not reduced), and the forms as equation ints of a PackedCubicSystem of
+    r_eff unknowns.  With a device: gf2bv_cubic_plan_device, the forms built by k_cubic_products / k_cubic_forms on that device."""
+    words = (cubic_cols(n_lin) + 63) // 64
+    o, b = _ints_to_words([origin], words), _ints_to_words(list(basis), words)
+    r, re, m, fw = (ctypes.c_int64() for _ in range(4))
+
+    def plan(forms, cap):
+        head = (o.ctypes.data, b.ctypes.data, len(basis), words, n_lin)
+        tail = (ctypes.byref(r), ctypes.byref(re), ctypes.byref(m), ctypes.byref(fw), forms, cap)
+        _check(lib().gf2bv_cubic_plan(*head, *tail) if device is None else lib().gf2bv_cubic_plan_device(*head, device, *tail))
+
+    plan(None, 0)
+    forms = np.zeros((max(m.value, 1), max(fw.value, 1)), dtype=np.uint64)
+    plan(forms.ctypes.data, m.value)
+    return {"r": r.value, "r_eff": re.value, "forms": _words_to_ints(forms, m.value)}
+
+
+def cubic_points(origin: int, basis, n_lin: int, ys) -> list:
+    """gf2bv_cubic_points (host only): the points of the space that common zeros `ys` (ints below 2^64) of cubic_plan's forms stand for."""
+    words = (cubic_cols(n_lin) + 63) // 64
+    o, b = _ints_to_words([origin], words), _ints_to_words(list(basis), words)
+    y = _ints_to_words(list(ys), 1)
+    out = np.zeros((max(len(ys), 1), words), dtype=np.uint64)
+    _check(lib().gf2bv_cubic_points(o.ctypes.data, b.ctypes.data, len(basis), words, n_lin, y.ctypes.data, len(ys), 1, out.ctypes.data))
+    return _words_to_ints(out, len(ys))
+
+
+def cubic_forms_search(forms, r_eff: int, device: int = 0, max_out: int = 1 << 22) -> tuple:
+    """gf2bv_cubic_forms_search: (count, ascending common zeros) of cubic forms given as equation ints over r_eff unknowns."""
+    fw = (cubic_cols(r_eff) + 64) // 64
+    f = _ints_to_words(list(forms), fw)
+    cnt = ctypes.c_int64()
+    out = np.zeros(max(max_out, 1), dtype=np.uint64)
+    _check(lib().gf2bv_cubic_forms_search(f.ctypes.data, len(forms), r_eff, device, max_out, ctypes.byref(cnt), out.ctypes.data))
+    return cnt.value, [int(v) for v in out[:min(cnt.value, max_out)]]
+
+
+def cubic_last_times() -> dict:
+    """this thread's last gf2bv_cubic_search: phase times in ms, rounds of the affine elimination, first-pass candidates"""
+    v = (ctypes.c_double * 8)()
+    lib().gf2bv_cubic_last_times(v)
     keys = ("ms_reduce", "ms_forms", "ms_affine", "ms_search", "ms_relin", "ms_total", "levels", "candidates")
     return dict(zip(keys, list(v)))
 

@@ -342,6 +342,38 @@ int  gf2bv_quad_forms_search(const uint64_t *forms, int64_t m, int64_t r_eff, in
                              uint64_t *out);
 void gf2bv_quad_last_times(double *out8);
 
+/* ---- cubic search: the consistent points of a solution space over the degree-3 columns ----------------------------------------
+ * A space over the columns of degree-3 XL and of PackedCubicSystem: coordinates 0..n_lin-1 are linear, pair (i, j), j < i, is at
+ * n_lin + C(i,2) + j, triple (i, j, l), l < j < i, at n_lin + C(n_lin,2) + C(i,3) + C(j,2) + l; n_lin 1..2000 and `words` must
+ * cover those columns.  A point is consistent when every pair and triple coordinate equals the product of its linear bits.  The
+ * space is reduced to CUBIC forms in r_eff variables whose common zeros are exactly the consistent points.
+ * The entries mirror the quadratic ones above one for one -- same arguments, same results, same order of the points, the same
+ * 2^22 cap on collected points, max_enum 0..40, points released with gf2bv_quad_free -- with these differences:
+ *  - r (the rank of the projection onto the linear coordinates) is reduced up to kCubicMaxRank = 64: a point of the forms is one word.
+ *    Above it gf2bv_cubic_search gives up (*count = -1) and gf2bv_cubic_plan says r_eff = -1.
+ *  - There is no relinearisation level: r_eff > max_enum gives up.  (r_eff <= r <= n_lin: with n_lin <= max_enum it never does.)
+ *  - The forms are the equation ints of a PackedCubicSystem of r_eff unknowns: bit 0 the constant, bit 1 + k unknown k, bit
+ *    1 + r_eff + C(i,2) + j the product of unknowns j < i, bit 1 + r_eff + C(r_eff,2) + C(i,3) + C(j,2) + l that of l < j < i;
+ *    form_words = ceil((1 + r_eff + C(r_eff,2) + C(r_eff,3)) / 64).  Zero forms are dropped; none of those left is affine.
+ *  - Memory: one build holds C(n_lin,2) + C(n_lin,3) product forms and up to as many forms of form_words(r) words each, on the
+ *    host (gf2bv_cubic_plan) or on the device; a search holds m forms of 2 + r_eff + C(r_eff,2) words.  Above 1 GiB either returns
+ *    GF2BV_ERR_NOMEM without attempting the allocation.
+ *  - gf2bv_cubic_points: y_words >= 1; an assignment is the first word of each.
+ *  - gf2bv_cubic_last_times: the relinearisation entry is 0 and `levels` counts the rounds of the affine elimination. */
+int  gf2bv_cubic_search(const uint64_t *origin, const uint64_t *basis, int64_t dimension, int64_t words, int64_t n_lin,
+                        int max_enum, int64_t max_solutions, int device, int64_t *count, int64_t *lin_rank, uint64_t *out_words);
+int  gf2bv_cubic_search_alloc(const uint64_t *origin, const uint64_t *basis, int64_t dimension, int64_t words, int64_t n_lin,
+                              int max_enum, int64_t max_solutions, int device, int64_t *count, int64_t *lin_rank, uint64_t **out_words);
+int  gf2bv_cubic_plan(const uint64_t *origin, const uint64_t *basis, int64_t dimension, int64_t words, int64_t n_lin,
+                      int64_t *r, int64_t *r_eff, int64_t *m, int64_t *form_words, uint64_t *forms, int64_t forms_cap);
+int  gf2bv_cubic_plan_device(const uint64_t *origin, const uint64_t *basis, int64_t dimension, int64_t words, int64_t n_lin, int device,
+                             int64_t *r, int64_t *r_eff, int64_t *m, int64_t *form_words, uint64_t *forms, int64_t forms_cap);
+int  gf2bv_cubic_points(const uint64_t *origin, const uint64_t *basis, int64_t dimension, int64_t words, int64_t n_lin,
+                        const uint64_t *ys, int64_t nys, int64_t y_words, uint64_t *out_words);
+int  gf2bv_cubic_forms_search(const uint64_t *forms, int64_t m, int64_t r_eff, int device, int64_t max_out, int64_t *count,
+                              uint64_t *out);
+void gf2bv_cubic_last_times(double *out8);
+
 /* ---- quadratic expansion: factored quadratic equations -> linearised rows, on the device ---------------------------------
  * A quadratic equation in n_lin unknowns kept FACTORED: a linear form plus products of two linear forms, every form
  * Wl = ceil((n_lin + 1) / 64) words in the equation-int order (bit 0 = constant, bit 1 + g = unknown g; bits above n_lin ignored).
