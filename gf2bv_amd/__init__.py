@@ -16,7 +16,7 @@ def __getattr__(name):
     # the packed front-end needs numpy (>= 1.20; np.bitwise_count of 2.x is used when present): imported on first use so
     # that the package itself has no import-time dependency beyond the standard library
     if name in ("PackedBitVec", "PackedLinearSystem", "PackedQuadBitVec", "PackedQuadraticSystem", "PackedCubicBitVec",
-                "PackedCubicSystem", "PackedCubicGuessSystem", "packed"):
+                "PackedCubicSystem", "PackedCubicGuessSystem", "PackedQuarticBitVec", "PackedQuarticSystem", "packed"):
         import importlib
         mod = importlib.import_module(".packed", __name__)
         return mod if name == "packed" else getattr(mod, name)
@@ -26,7 +26,7 @@ def __getattr__(name):
 __all__ = [
     "AffineSpace", "BitVec", "DimensionTooLargeError", "LinearSystem", "PackedBitVec", "PackedCubicBitVec", "PackedCubicGuessSystem",
     "PackedCubicSystem", "PackedLinearSystem",
-    "PackedQuadBitVec", "PackedQuadraticSystem", "QuadraticSystem", "Zeros",
+    "PackedQuadBitVec", "PackedQuadraticSystem", "PackedQuarticBitVec", "PackedQuarticSystem", "QuadraticSystem", "Zeros",
     "eqs_to_sage_mat_helper", "m4ri_solve", "mul_bit_quad", "search_all_cubic", "search_all_xl", "search_one_cubic", "search_one_xl",
     "to_bits", "tuple_where", "xor_tuple",
 ]

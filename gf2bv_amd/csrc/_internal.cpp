@@ -623,30 +623,35 @@ PyObject *collect_results(int64_t n, long mode, int device, F &&fill)
 // ---- what the packed front-ends pass in, one parser per kind of input ---------------------------------------------------------
 // The factored form of a system as C-contiguous buffers: lin, then per group of products its offsets and its operands -- four
 // buffers for a quadratic system (m4ri_solve_quad_packed's arguments: lin, term_off, ta, tb), eight for a cubic one
-// (m4ri_solve_cubic_packed's: lin, off2, ta, tb, off3, ua, ub, uc).  A layout names the groups and words the refusals.
+// (m4ri_solve_cubic_packed's: lin, off2, ta, tb, off3, ua, ub, uc), thirteen for a quartic one (m4ri_solve_quartic_packed's: the
+// cubic eight, then off4, va, vb, vc, vd).  A layout names the groups and words the refusals.
 struct TermGroup { int off_at, op_at, arity; };               // argument of the offsets, of the first operand; operands per product
 struct TermLayout {
 	int nbuf, ngroups;
-	TermGroup group[2];
+	TermGroup group[3];
 	// The order of the checks, and so which refusal a caller sees for buffers with two faults, is each entry's own from before
 	// the parsers were one: the quadratic entries look at the operands' sizes before the offsets' values, the cubic ones behind
 	// the offsets' end.  Callers and tests match these texts.
 	bool ops_first;
 	const char *bad_len, *bad_ops, *bad_start, *bad_end, *bad_order;
 };
-const TermLayout QUAD_TERMS = {4, 1, {{1, 2, 2}, {0, 0, 0}}, true,
+const TermLayout QUAD_TERMS = {4, 1, {{1, 2, 2}, {0, 0, 0}, {0, 0, 0}}, true,
 	"term_off must hold one int64 per row of lin and one more", "ta and tb must hold the same number of whole operands",
 	"term_off must start at 0", "term_off must end at the number of operands in ta", "term_off must not decrease"};
-const TermLayout CUBIC_TERMS = {8, 2, {{1, 2, 2}, {4, 5, 3}}, false,
+const TermLayout CUBIC_TERMS = {8, 2, {{1, 2, 2}, {4, 5, 3}, {0, 0, 0}}, false,
 	"off2 and off3 must hold one int64 per row of lin and one more", "the operands of a product must hold the same number of whole forms",
 	"off2 and off3 must start at 0", "off2 and off3 must end at the number of operands of their products", "off2 and off3 must not decrease"};
+const TermLayout QUARTIC_TERMS = {13, 3, {{1, 2, 2}, {4, 5, 3}, {8, 9, 4}}, false,
+	"off2, off3 and off4 must hold one int64 per row of lin and one more", "the operands of a product must hold the same number of whole forms",
+	"off2, off3 and off4 must start at 0", "off2, off3 and off4 must end at the number of operands of their products",
+	"off2, off3 and off4 must not decrease"};
 
 // The buffers of a layout, checked against each other and against n_lin before the library sees them: whole rows of
 // Wl = ceil((n_lin + 1) / 64) words, per group one offset per row and one more, offsets that start at 0, never decrease and end at
 // the number of operands, operands of equal size.  TypeError for what is no buffer, ValueError for a shape.
 struct TermBuffers {
 	const TermLayout &lay;
-	Py_buffer view[8];
+	Py_buffer view[13];
 	int got = 0;
 	Py_ssize_t n = 0, live = 0;
 	explicit TermBuffers(const TermLayout &layout) : lay(layout) {}
@@ -683,7 +688,11 @@ struct TermBuffers {
 		if (bad) { PyErr_SetString(PyExc_ValueError, bad); return false; }
 		return true;
 	}
-	Py_ssize_t cols() const { return n + n * (n - 1) / 2 + (lay.ngroups == 2 ? n * (n - 1) * (n - 2) / 6 : 0); }
+	Py_ssize_t cols() const
+	{
+		const Py_ssize_t c3 = n * (n - 1) * (n - 2) / 6;
+		return n + n * (n - 1) / 2 + (lay.ngroups >= 2 ? c3 : 0) + (lay.ngroups == 3 ? (n > 1024 ? (Py_ssize_t)1 << 40 : c3 * (n - 3) / 4) : 0);
+	}
 };
 
 // (a buffer taken with PyBUF_C_CONTIGUOUS | PyBUF_FORMAT) a 2-D uint64 array?
@@ -1100,6 +1109,25 @@ PyObject *py_m4ri_solve_cubic_packed(PyObject *, PyObject *const *args, Py_ssize
 	return single_result(mode, device, [&](gf2bv_result **res) {
 		return gf2bv_solve_cubic_terms(cb.words(0), cb.offsets(1), cb.words(2), cb.words(3), cb.offsets(4), cb.words(5), cb.words(6), cb.words(7),
 		                               cb.live, rows, cb.n, (int)mode, device, res);
+	});
+}
+
+// m4ri_solve_quartic_packed(lin, off2, ta, tb, off3, ua, ub, uc, off4, va, vb, vc, vd, n_lin, rows, mode[, device]) -> None | int |
+// AffineSpace.  New entry (no counterpart in the reference): m4ri_solve_cubic_packed one arity up -- products of four affine forms too
+// (off4 / va / vb / vc / vd), expanded over the n_lin + C(n_lin,2) + C(n_lin,3) + C(n_lin,4) columns on the device
+// (gf2bv_hip.h, "quartic expansion") and solved there; rows >= the rows of lin and >= the columns.
+PyObject *py_m4ri_solve_quartic_packed(PyObject *, PyObject *const *args, Py_ssize_t nargs)
+{
+	int device;
+	if (!entry_device("m4ri_solve_quartic_packed", 16, args, nargs, &device)) return nullptr;
+	Py_ssize_t rows;
+	long mode;
+	TermBuffers qb(QUARTIC_TERMS);
+	if (!parse_quad_call(args, 13, 14, 15, true, qb, &rows, &mode)) return nullptr;
+	return single_result(mode, device, [&](gf2bv_result **res) {
+		return gf2bv_solve_quartic_terms(qb.words(0), qb.offsets(1), qb.words(2), qb.words(3), qb.offsets(4), qb.words(5), qb.words(6), qb.words(7),
+		                                 qb.offsets(8), qb.words(9), qb.words(10), qb.words(11), qb.words(12), qb.live, rows, qb.n, (int)mode,
+		                                 device, res);
 	});
 }
 
@@ -1878,6 +1906,8 @@ PyMethodDef module_methods[] = {
 	 "m4ri_solve_quad_packed(lin, term_off, ta, tb, n_lin, rows, mode, device=None)\n--\n\nm4ri_solve on a quadratic system kept factored (linear forms and products of two linear forms, packed 64-bit words): expanded into the linearised matrix on the GPU."},
 	{"m4ri_solve_xl3", FAST(py_m4ri_solve_xl<3>), METH_FASTCALL,
 	 "m4ri_solve_xl3(equations, n_lin, mode, device=None)\n--\n\nDegree-3 XL: QuadraticSystem equation ints multiplied by 1 and by every unknown on the GPU and solved over the monomials of degree <= 3."},
+	{"m4ri_solve_quartic_packed", FAST(py_m4ri_solve_quartic_packed), METH_FASTCALL,
+	 "m4ri_solve_quartic_packed(lin, off2, ta, tb, off3, ua, ub, uc, off4, va, vb, vc, vd, n_lin, rows, mode, device=None)\n--\n\nm4ri_solve on a quartic system kept factored (a linear form, products of two, of three and of four affine forms, packed 64-bit words; exact products): expanded over the monomials of degree <= 4 on the GPU."},
 	{"m4ri_solve_cubic_packed", FAST(py_m4ri_solve_cubic_packed), METH_FASTCALL,
 	 "m4ri_solve_cubic_packed(lin, off2, ta, tb, off3, ua, ub, uc, n_lin, rows, mode, device=None)\n--\n\nm4ri_solve on a cubic system kept factored (a linear form, products of two and of three affine forms, packed 64-bit words; exact products): expanded over the monomials of degree <= 3 on the GPU."},
 	{"m4ri_solve_xl3_quad_packed", FAST(py_m4ri_solve_xl_quad_packed<3>), METH_FASTCALL,

@@ -5439,6 +5439,167 @@ k_cubic_expand(const u64 *__restrict__ lin, const i64 *__restrict__ off2, const 
 
 
 // ==========================================================================================
+// QUARTIC EXPANSION: factored quartic equations -> the linearised rows over the monomials of degree <= 4
+// ==========================================================================================
+// (host side: gf2bv_quartic_expand_device in gf2_solver.hip; the front-end: PackedQuarticSystem in gf2bv_amd/packed.py)
+//
+// Row r is e = lin[r] ^ XOR_t ta[t] tb[t] ^ XOR_u ua[u] ub[u] uc[u] ^ XOR_v va[v] vb[v] vc[v] vd[v], t in off2[r] .. off2[r + 1], u in
+// off3[r] .. off3[r + 1], v in off4[r] .. off4[r + 1]: k_cubic_expand's row with products of four affine forms too, every product exact
+// in GF(2)[x] / (x_i^2 + x_i).  The output is the row k_xl4_cubic_expand writes (XL by one unknown, above): degree 3's columns, quadruple
+// (i, j, l, p), p < l < j < i, at cols3 + C(i,4) + C(j,3) + C(l,2) + p, the constant at cols4, everything behind it zero.
+// The rule is distributivity for the columns of degree <= 3, over the two word functions above, and a determinant for the quadruples.
+// A pass first STAGES cubic rows in LDS with cx_word, W3 = ceil((cols3 + 1) / 64) words each and the constant at cols3 (the source
+// layout of xl_mul_word<3>): C, the part of degree <= 3 of the row (the linear part with the first pass, the pass's quadratic and cubic
+// terms), and P_v = a b c for each quartic term of the pass.  It then FOLDS into C what the quartic terms put on the columns of
+// degree <= 3 and on the constant: with d the term's fourth operand, P_v itself where d has the constant, and the columns below
+// cols3 of xl_mul_word<3>(P_v, k) for every unknown k of d -- (a b c) d with x^2 = x, collisions and constants included.  That is
+// W3 x weight(d) word functions per term, dealt one each to the lanes of the workgroup, which XOR them into C with LDS atomics; the
+// lightest of a term's four operands is moved into d's place first (one lane per term; the product commutes).  At last it EMITS
+// output word w as xl_mul_word<3>(C, k = -1) -- C's own columns, the constant moved to cols4 -- XORed with the quartic terms'
+// quadruples: four distinct unknowns can only come one from each form, so the coefficient of x_i x_j x_l x_p is the permanent --
+// over GF(2) the determinant -- of the operands' bits at i, j, l, p.  Expanded along p, run (i, j, l, 0..l-1) is
+// d[0..l) & det(a b c) ^ c[0..l) & det(a b d) ^ b[0..l) & det(a c d) ^ a[0..l) & det(b c d), the 3 x 3 determinants taken at (i, j, l)
+// from the 2 x 2 minors of (a, b) and of (c, d): four LDS windows and twelve mask bits per term and run (qz_quad_word).
+// Work split as in k_cubic_expand: one workgroup per row at a time, every lane two consecutive output words stored as 16 bytes, one
+// writer per output word, no atomics on the output; a row with more than `tch2` / `tch3` / `tch4` terms of a kind takes several passes that XOR into
+// what the same lane stored before.  Rows >= rows_live are written as zeros.
+// LDS: (1 + 2 tch2 + 3 tch3 + 4 tch4) x Wl + (1 + tch4) x W3 words (dynamic).
+__device__ __forceinline__ int qz_weight(const u64 *x, int Wl, int n)      // constant and unknowns of an operand (bits above n do not count)
+{
+	int s = 0;
+	for (int w = 0; w < Wl; w++) s += __popcll(w == Wl - 1 ? x[w] & qx_low(n + 1 - 64 * w) : x[w]);
+	return s;
+}
+
+// the quadruple columns among c0 .. c0 + 63 of what n4 quartic terms contribute
+__device__ __forceinline__ u64 qz_quad_word(const u64 *VA, const u64 *VB, const u64 *VC, const u64 *VD, int n4, int Wl, i64 cols3, i64 cols4, i64 c0)
+{
+	u64 acc = 0;
+	const i64 u_lo = (c0 > cols3 ? c0 : cols3) - cols3, u_hi = (c0 + 64 < cols4 ? c0 + 64 : cols4) - cols3;      // the word's quadruple indices
+	if (u_lo >= u_hi) return 0;
+	i64 i = xl_quart_root(u_lo), j = xl_tet_root(u_lo - xl_c4(i));         // the run u_lo lies in: 1 <= l < j < i
+	i64 l = xl_tri_root(u_lo - xl_c4(i) - xl_c3(j));
+	for (i64 s = xl_c4(i) + xl_c3(j) + xl_c2(l); s < u_hi;) {              // run (i, j, l): quadruples s .. s + l - 1
+		const i64 j0 = (u_lo > s ? u_lo : s) - s, j1 = (u_hi < s + l ? u_hi : s + l) - s;
+		u64 run = 0;
+		for (int t = 0; t < n4; t++) {
+			const u64 *a = VA + t * Wl, *b = VB + t * Wl, *c = VC + t * Wl, *d = VD + t * Wl;
+			const u64 ai = cx_mask(a, i), aj = cx_mask(a, j), al = cx_mask(a, l), bi = cx_mask(b, i), bj = cx_mask(b, j), bl = cx_mask(b, l);
+			const u64 ci = cx_mask(c, i), cj = cx_mask(c, j), cl = cx_mask(c, l), di = cx_mask(d, i), dj = cx_mask(d, j), dl = cx_mask(d, l);
+			const u64 ab_ij = (ai & bj) ^ (aj & bi), ab_il = (ai & bl) ^ (al & bi), ab_jl = (aj & bl) ^ (al & bj);
+			const u64 cd_ij = (ci & dj) ^ (cj & di), cd_il = (ci & dl) ^ (cl & di), cd_jl = (cj & dl) ^ (cl & dj);
+			run ^= (qx_window(d, Wl, 1 + j0) & ((ci & ab_jl) ^ (cj & ab_il) ^ (cl & ab_ij)))
+			     ^ (qx_window(c, Wl, 1 + j0) & ((di & ab_jl) ^ (dj & ab_il) ^ (dl & ab_ij)))
+			     ^ (qx_window(b, Wl, 1 + j0) & ((ai & cd_jl) ^ (aj & cd_il) ^ (al & cd_ij)))
+			     ^ (qx_window(a, Wl, 1 + j0) & ((bi & cd_jl) ^ (bj & cd_il) ^ (bl & cd_ij)));
+		}
+		acc |= (run & qx_low(j1 - j0)) << (cols3 + s + j0 - c0);
+		s += l;
+		if (++l == j) { l = 1; if (++j == i) { i++; j = 2; } }
+	}
+	return acc;
+}
+
+// unit u of the pass's quartic terms -- the set bits of their multipliers d in term order, bit 0 of a form its constant -- as
+// (term v, unknown g or -1); false past the last unit
+__device__ __forceinline__ bool qz_unit(const u64 *VD, int n4, int Wl, int n, int u, int &v, int &g)
+{
+	for (v = 0; v < n4; v++)
+		for (int w = 0; w < Wl; w++) {
+			u64 bits = VD[v * Wl + w];
+			if (w == Wl - 1) bits &= qx_low(n + 1 - 64 * w);
+			const int pc = __popcll(bits);
+			if (u >= pc) { u -= pc; continue; }
+			while (u-- > 0) bits &= bits - 1;
+			g = 64 * w + __ffsll((long long)bits) - 2;
+			return true;
+		}
+	return false;
+}
+
+__global__ void __launch_bounds__(256)
+k_quartic_expand(const u64 *__restrict__ lin, const i64 *__restrict__ off2, const u64 *__restrict__ ta, const u64 *__restrict__ tb,
+                 const i64 *__restrict__ off3, const u64 *__restrict__ ua, const u64 *__restrict__ ub, const u64 *__restrict__ uc,
+                 const i64 *__restrict__ off4, const u64 *__restrict__ va, const u64 *__restrict__ vb, const u64 *__restrict__ vc,
+                 const u64 *__restrict__ vd, i64 rows_live, i64 rows, int n, int Wl, int W3, int tch2, int tch3, int tch4,
+                 u64 *__restrict__ out, i64 stride)
+{
+	extern __shared__ u64 qz_lds[];    // [lin: Wl | A, B: tch2 x Wl each | UA, UB, UC: tch3 x Wl each | VA .. VD: tch4 x Wl each | C: W3 | P: tch4 x W3]
+	u64 *sl = qz_lds, *sa = sl + Wl, *sb = sa + (i64)tch2 * Wl, *sua = sb + (i64)tch2 * Wl, *sub = sua + (i64)tch3 * Wl, *suc = sub + (i64)tch3 * Wl;
+	u64 *sva = suc + (i64)tch3 * Wl, *svb = sva + (i64)tch4 * Wl, *svc = svb + (i64)tch4 * Wl, *svd = svc + (i64)tch4 * Wl;
+	u64 *sc = svd + (i64)tch4 * Wl, *sp = sc + W3;
+	const i64 cols2 = (i64)n + xl_c2(n), cols3 = cols2 + xl_c3(n), cols4 = cols3 + xl_c4(n);
+	const i64 npair = stride >> 1;                     // 16-byte pieces of a row (stride is even)
+	for (i64 r = blockIdx.x; r < rows; r += gridDim.x) {
+		ulonglong2 *o = reinterpret_cast<ulonglong2 *>(out + r * stride);
+		if (r >= rows_live) {
+			for (i64 k = threadIdx.x; k < npair; k += blockDim.x) o[k] = make_ulonglong2(0, 0);
+			continue;
+		}
+		i64 t0 = off2[r], t1 = off2[r + 1], u0 = off3[r], u1 = off3[r + 1], v0 = off4[r], v1 = off4[r + 1];
+		if (t0 < 0 || t1 < t0 || u0 < 0 || u1 < u0 || v0 < 0 || v1 < v0) t0 = t1 = u0 = u1 = v0 = v1 = 0;      // (offsets the entry could not check: such a row is its linear part)
+		bool first = true;
+		do {
+			const int n2 = (int)(t1 - t0 < tch2 ? t1 - t0 : tch2), n3 = (int)(u1 - u0 < tch3 ? u1 - u0 : tch3), n4 = (int)(v1 - v0 < tch4 ? v1 - v0 : tch4);
+			__syncthreads();                           // the pass before has read its operands and its staged rows
+			if (first) for (int e = threadIdx.x; e < Wl; e += blockDim.x) sl[e] = lin[r * Wl + e];
+			for (int e = threadIdx.x; e < n2 * Wl; e += blockDim.x) { sa[e] = ta[t0 * Wl + e]; sb[e] = tb[t0 * Wl + e]; }
+			for (int e = threadIdx.x; e < n3 * Wl; e += blockDim.x) { sua[e] = ua[u0 * Wl + e]; sub[e] = ub[u0 * Wl + e]; suc[e] = uc[u0 * Wl + e]; }
+			for (int e = threadIdx.x; e < n4 * Wl; e += blockDim.x) {
+				sva[e] = va[v0 * Wl + e]; svb[e] = vb[v0 * Wl + e]; svc[e] = vc[v0 * Wl + e]; svd[e] = vd[v0 * Wl + e];
+			}
+			__syncthreads();
+			if ((int)threadIdx.x < n4) {               // the lightest operand of term v becomes its multiplier d
+				u64 *d = svd + threadIdx.x * Wl, *best = d;
+				u64 *const others[3] = { sva + threadIdx.x * Wl, svb + threadIdx.x * Wl, svc + threadIdx.x * Wl };
+				int wb = qz_weight(d, Wl, n);
+				for (u64 *x : others) {
+					const int wx = qz_weight(x, Wl, n);
+					if (wx < wb) { wb = wx; best = x; }
+				}
+				if (best != d)
+					for (int w = 0; w < Wl; w++) { const u64 v = d[w]; d[w] = best[w]; best[w] = v; }
+			}
+			__syncthreads();
+			for (int e = threadIdx.x; e < (1 + n4) * W3; e += blockDim.x) {      // stage C and every P_v: cubic rows, the constant at cols3
+				const int v = e / W3 - 1, w = e - (v + 1) * W3;
+				sc[e] = v < 0 ? cx_word(sl, sa, sb, n2, sua, sub, suc, n3, Wl, n, cols2, cols3, 64 * (i64)w, first)
+				              : cx_word(sl, sa, sb, 0, sva + v * Wl, svb + v * Wl, svc + v * Wl, 1, Wl, n, cols2, cols3, 64 * (i64)w, false);
+			}
+			__syncthreads();
+			if (n4 > 0) {                              // fold the quartic terms' columns of degree <= 3 and their constants into C
+				int units = 0;
+				for (int e = 0; e < n4 * Wl; e++) units += __popcll((e + 1) % Wl == 0 ? svd[e] & qx_low(n + 1 - 64 * (Wl - 1)) : svd[e]);
+				for (int e = threadIdx.x; e < units * W3; e += blockDim.x) {
+					const int u = e / W3, w = e - u * W3;
+					int v, g;
+					if (!qz_unit(svd, n4, Wl, n, u, v, g)) continue;
+					const u64 *p = sp + (i64)v * W3;
+					const u64 x = g < 0 ? p[w] : xl_mul_word<3>(p, W3, n, cols2, cols3, cols4, 64 * (i64)w, g) & qx_low(cols3 - 64 * (i64)w);
+					if (x) atomicXor(reinterpret_cast<unsigned long long *>(sc + w), (unsigned long long)x);
+				}
+				__syncthreads();
+			}
+			for (i64 k = threadIdx.x; k < npair; k += blockDim.x) {
+				u64 w0 = xl_mul_word<3>(sc, W3, n, cols2, cols3, cols4, 128 * k, -1);
+				u64 w1 = xl_mul_word<3>(sc, W3, n, cols2, cols3, cols4, 128 * k + 64, -1);
+				if (n4 > 0) {
+					w0 ^= qz_quad_word(sva, svb, svc, svd, n4, Wl, cols3, cols4, 128 * k);
+					w1 ^= qz_quad_word(sva, svb, svc, svd, n4, Wl, cols3, cols4, 128 * k + 64);
+				}
+				if (!first) { const ulonglong2 old = o[k]; w0 ^= old.x; w1 ^= old.y; }
+				o[k] = make_ulonglong2(w0, w1);
+			}
+			t0 += n2;
+			u0 += n3;
+			v0 += n4;
+			first = false;
+		} while (t0 < t1 || u0 < u1 || v0 < v1);
+	}
+}
+
+
+// ==========================================================================================
 // DEGREE-4 XL ON CUBIC ROWS: every cubic row, and its product with every unknown, over the monomials of degree <= 4
 // ==========================================================================================
 // (host side: gf2bv_xl4_cubic_expand_device in gf2_solver.hip; the front-end: PackedCubicSystem.solve_all_xl4)

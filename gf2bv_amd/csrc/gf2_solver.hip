@@ -5194,18 +5194,20 @@ void gf2bv_cubic_last_times(double *out8)
 }  // extern "C"
 
 // =================================================================================================
-// Expansion of factored equations: a linear form plus products of two (degree 3: and of three) forms become the linearised rows of
-// the C-ABI layout on the device (k_quad_expand, k_cubic_expand), where gf2bv_solve_device and the factor entries read them.
+// Expansion of factored equations: a linear form plus products of two (degree 3: and of three, degree 4: and of four) forms become the
+// linearised rows of the C-ABI layout on the device (k_quad_expand, k_cubic_expand, k_quartic_expand), where gf2bv_solve_device and
+// the factor entries read them.
 namespace {
 
-constexpr i64 kExpandLdsBytes = 65536;                 // what every expansion kernel below may take of a workgroup's LDS
+constexpr i64 kExpandLdsBytes = 65536;                 // what every expansion kernel below may take of a workgroup's LDS ...
+constexpr i64 kQuarticLdsBytes = 160 * 1024 - 256;     // ... but k_quartic_expand, which stages cubic rows there (the attribute is raised above 64 KiB)
 
 // the workgroup of every expansion kernel: a thread per two words of an output row
 unsigned expand_block(i64 stride) { return (unsigned)std::min<i64>(256, round_up(std::max<i64>(stride / 2, 1), 64)); }
 
 // The factored form, in host or in device memory.  degree 2: the products follow QuadraticSystem._mul_bit, over n + C(n,2) columns,
 // and off3, ua, ub, uc are unused; degree 3: products of two and of three affine forms, exact in GF(2)[x] / (x_i^2 + x_i), over the
-// n + C(n,2) + C(n,3) columns of degree-3 XL
+// n + C(n,2) + C(n,3) columns of degree-3 XL; degree 4: and of four (off4, va .. vd), over degree-4 XL's columns
 struct Terms {
 	int degree;
 	const u64 *lin;                    // rows_live x wl
@@ -5213,13 +5215,25 @@ struct Terms {
 	const u64 *ta, *tb;
 	const i64 *off3;                   // rows_live + 1
 	const u64 *ua, *ub, *uc;
+	const i64 *off4 = nullptr;         // rows_live + 1
+	const u64 *va = nullptr, *vb = nullptr, *vc = nullptr, *vd = nullptr;
 	i64 rows_live, rows, n;
 	Terms(const void *lin, const void *off2, const void *ta, const void *tb, i64 rows_live, i64 rows, i64 n_lin, const void *off3 = nullptr,
 	      const void *ua = nullptr, const void *ub = nullptr, const void *uc = nullptr, int degree = 2)
 		: degree(degree), lin((const u64 *)lin), off2((const i64 *)off2), ta((const u64 *)ta), tb((const u64 *)tb), off3((const i64 *)off3),
 		  ua((const u64 *)ua), ub((const u64 *)ub), uc((const u64 *)uc), rows_live(rows_live), rows(rows), n(n_lin) {}
+	Terms &quartic(const void *o4, const void *a, const void *b, const void *c, const void *d)
+	{
+		degree = 4, off4 = (const i64 *)o4, va = (const u64 *)a, vb = (const u64 *)b, vc = (const u64 *)c, vd = (const u64 *)d;
+		return *this;
+	}
 	i64 wl() const { return (n + 1 + 63) / 64; }
-	i64 cols() const { return n + n * (n - 1) / 2 + (degree == 3 ? n * (n - 1) * (n - 2) / 6 : 0); }
+	i64 cols3() const { return n + n * (n - 1) / 2 + n * (n - 1) * (n - 2) / 6; }
+	i64 cols() const
+	{
+		if (degree == 4) return n > 1024 ? (1ll << 40) : cols3() + n * (n - 1) * (n - 2) / 6 * (n - 3) / 4;      // (C(1025,4) is far above any row)
+		return degree == 3 ? cols3() : n + n * (n - 1) / 2;
+	}
 	i64 wt() const { return (cols() + 1 + 63) / 64; }
 };
 
@@ -5243,29 +5257,51 @@ CubicLaunch cubic_launch(i64 n, i64 stride)
 	return { tch2, tch3, expand_block(stride), sizeof(u64) * (size_t)((1 + 2 * tch2 + 3 * tch3) * wl) };
 }
 
+// What k_quartic_expand is launched with: `tch2` / `tch3` / `tch4` terms of a row in LDS at a time beside the linear part and the
+// 1 + tch4 staged cubic rows of w3 words.  The staged rows come first: with every chunk at 1 a pass needs 10 wl + 2 w3 words, which
+// is what bounds n_lin (about 157); lds above kQuarticLdsBytes: this n_lin does not fit
+struct QuarticLaunch { int tch2, tch3, tch4; unsigned block; size_t lds; };
+QuarticLaunch quartic_launch(i64 n, i64 stride)
+{
+	const i64 wl = (n + 1 + 63) / 64, w3 = n > 1024 ? (1ll << 30) : (n + n * (n - 1) / 2 + n * (n - 1) * (n - 2) / 6 + 1 + 63) / 64;
+	i64 rest = kQuarticLdsBytes / 8 - wl - w3;
+	const int tch4 = (int)std::max<i64>(1, std::min<i64>(4, rest / 3 / (4 * wl + w3)));
+	rest -= tch4 * (4 * wl + w3);
+	const int tch3 = (int)std::max<i64>(1, std::min<i64>(8, rest / 2 / (3 * wl)));
+	rest -= tch3 * 3 * wl;
+	const int tch2 = (int)std::max<i64>(1, std::min<i64>(8, rest / (2 * wl)));
+	return { tch2, tch3, tch4, expand_block(stride), sizeof(u64) * (size_t)((1 + 2 * tch2 + 3 * tch3 + 4 * tch4) * wl + (1 + tch4) * w3) };
+}
+
 // The shape of a factored system; `host`: the offsets can be read (each array starts at 0 and never decreases; operands wherever
 // they say there are terms)
 int check_terms(const Terms &t, bool host)
 {
-	const bool cubic = t.degree == 3;
+	const bool cubic = t.degree >= 3, quartic = t.degree == 4;
 	if (!t.lin && t.rows_live > 0) return fail(GF2BV_ERR_ARG, "null pointer");
-	if (!t.off2 || (cubic && !t.off3)) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (!t.off2 || (cubic && !t.off3) || (quartic && !t.off4)) return fail(GF2BV_ERR_ARG, "null pointer");
 	if (t.n < 1 || t.n > 65535 || t.cols() >= (1ll << 31) - 64)
-		return fail(GF2BV_ERR_ARG, cubic ? "n_lin must be at least 1 and n_lin + C(n_lin,2) + C(n_lin,3) below 2^31 - 64"
-		                                 : "n_lin must be at least 1 and n_lin + n_lin(n_lin-1)/2 below 2^31 - 64");
+		return fail(GF2BV_ERR_ARG, quartic ? "n_lin must be at least 1 and n_lin + C(n_lin,2) + C(n_lin,3) + C(n_lin,4) below 2^31 - 64"
+		                           : cubic ? "n_lin must be at least 1 and n_lin + C(n_lin,2) + C(n_lin,3) below 2^31 - 64"
+		                                   : "n_lin must be at least 1 and n_lin + n_lin(n_lin-1)/2 below 2^31 - 64");
 	if (t.rows < 0 || t.rows >= (1ll << 31) - 64 || t.rows_live < 0 || t.rows_live > t.rows)
 		return fail(GF2BV_ERR_ARG, "rows_live must be 0..rows");
-	if (cubic && (i64)cubic_launch(t.n, 2).lds > kExpandLdsBytes)
+	if (quartic && (i64)quartic_launch(t.n, 2).lds > kQuarticLdsBytes)
+		return fail(GF2BV_ERR_ARG, "the operands and the staged cubic rows of this n_lin do not fit the expansion kernel's LDS (160 KiB)");
+	if (t.degree == 3 && (i64)cubic_launch(t.n, 2).lds > kExpandLdsBytes)
 		return fail(GF2BV_ERR_ARG, "the operands of this n_lin do not fit the expansion kernel's LDS (64 KiB)");
 	if (!host) {
-		if (!t.lin || !t.ta || !t.tb || (cubic && (!t.ua || !t.ub || !t.uc))) return fail(GF2BV_ERR_ARG, "null pointer");
+		if (!t.lin || !t.ta || !t.tb || (cubic && (!t.ua || !t.ub || !t.uc)) || (quartic && (!t.va || !t.vb || !t.vc || !t.vd)))
+			return fail(GF2BV_ERR_ARG, "null pointer");
 		return GF2BV_OK;
 	}
-	if (t.off2[0] != 0 || (cubic && t.off3[0] != 0)) return fail(GF2BV_ERR_ARG, "term offsets must start at 0");
+	if (t.off2[0] != 0 || (cubic && t.off3[0] != 0) || (quartic && t.off4[0] != 0)) return fail(GF2BV_ERR_ARG, "term offsets must start at 0");
 	for (i64 r = 0; r < t.rows_live; r++)
-		if (t.off2[r + 1] < t.off2[r] || (cubic && t.off3[r + 1] < t.off3[r])) return fail(GF2BV_ERR_ARG, "term offsets must not decrease");
+		if (t.off2[r + 1] < t.off2[r] || (cubic && t.off3[r + 1] < t.off3[r]) || (quartic && t.off4[r + 1] < t.off4[r]))
+			return fail(GF2BV_ERR_ARG, "term offsets must not decrease");
 	if ((!t.ta || !t.tb) && t.off2[t.rows_live] > 0) return fail(GF2BV_ERR_ARG, "null pointer");
 	if (cubic && (!t.ua || !t.ub || !t.uc) && t.off3[t.rows_live] > 0) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (quartic && (!t.va || !t.vb || !t.vc || !t.vd) && t.off4[t.rows_live] > 0) return fail(GF2BV_ERR_ARG, "null pointer");
 	return GF2BV_OK;
 }
 
@@ -5328,9 +5364,34 @@ int enqueue_cubic_expand(const Terms &c, u64 *d_aug, i64 stride, hipStream_t st)
 	return GF2BV_OK;
 }
 
+// (device pointers, already checked; the device is current) the kernel on `st`
+int enqueue_quartic_expand(const Terms &c, u64 *d_aug, i64 stride, hipStream_t st)
+{
+	if (c.rows == 0) return GF2BV_OK;
+	const QuarticLaunch l = quartic_launch(c.n, stride);
+	if ((i64)l.lds > kExpandLdsBytes) {                // (a function attribute holds per device: raised once on each that needs it)
+		static std::mutex mu;
+		static std::map<int, bool> raised;
+		int device = 0;
+		HIPCHK(hipGetDevice(&device));
+		std::lock_guard<std::mutex> lk(mu);
+		if (!raised[device]) {
+			HIPCHK(hipFuncSetAttribute((const void *)k_quartic_expand, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kQuarticLdsBytes));
+			raised[device] = true;
+		}
+	}
+	const unsigned grid = (unsigned)std::min<i64>(c.rows, 256 * 16);
+	hipLaunchKernelGGL(k_quartic_expand, dim3(grid), dim3(l.block), l.lds, st, c.lin, c.off2, c.ta, c.tb, c.off3, c.ua, c.ub, c.uc, c.off4, c.va,
+	                   c.vb, c.vc, c.vd, c.rows_live, c.rows, (int)c.n, (int)c.wl(), (int)((c.cols3() + 1 + 63) / 64), l.tch2, l.tch3, l.tch4, d_aug,
+	                   stride);
+	HIPCHK(hipGetLastError());
+	return GF2BV_OK;
+}
+
 // (device pointers, already checked) the kernel of the terms' degree on `st`
 int enqueue_expand(const Terms &t, u64 *d_aug, i64 stride, hipStream_t st)
 {
+	if (t.degree == 4) return enqueue_quartic_expand(t, d_aug, stride, st);
 	return t.degree == 3 ? enqueue_cubic_expand(t, d_aug, stride, st) : enqueue_quad_expand(t, d_aug, stride, st);
 }
 
@@ -5577,7 +5638,8 @@ struct QuadStage {
 				if (!rc) rc = upload((u64 **)op, *op, bytes);
 		};
 		group(t.off2, { &t.ta, &t.tb });
-		if (t.degree == 3) group(t.off3, { &t.ua, &t.ub, &t.uc });
+		if (t.degree >= 3) group(t.off3, { &t.ua, &t.ub, &t.uc });
+		if (t.degree == 4) group(t.off4, { &t.va, &t.vb, &t.vc, &t.vd });
 		if (!rc && sys_off) rc = upload(&d_sys, sys_off, sizeof(i64) * (size_t)(nsys + 1));
 		ds = round_up(stride, 2);
 		if (!rc) rc = alloc((void **)&d_aug, sizeof(u64) * (size_t)(nsys * t.rows * ds));
@@ -5736,6 +5798,45 @@ int gf2bv_solve_cubic_terms(const uint64_t *lin, const int64_t *off2, const uint
                             int mode, int device, gf2bv_result **out)
 {
 	return solve_terms(Terms(lin, off2, ta, tb, rows_live, rows, n_lin, off3, ua, ub, uc, 3), mode, device, out, true);
+}
+
+int gf2bv_quartic_expand_device(const void *d_lin, const void *d_off2, const void *d_ta, const void *d_tb, const void *d_off3, const void *d_ua,
+                                const void *d_ub, const void *d_uc, const void *d_off4, const void *d_va, const void *d_vb, const void *d_vc,
+                                const void *d_vd, int64_t rows_live, int64_t rows, int64_t n_lin, void *d_aug, int64_t stride_words, int device,
+                                void *stream)
+{
+	return terms_expand_device(Terms(d_lin, d_off2, d_ta, d_tb, rows_live, rows, n_lin, d_off3, d_ua, d_ub, d_uc).quartic(d_off4, d_va, d_vb, d_vc, d_vd),
+	                           d_aug, stride_words, device, stream);
+}
+int gf2bv_quartic_expand_words(const uint64_t *lin, const int64_t *off2, const uint64_t *ta, const uint64_t *tb, const int64_t *off3,
+                               const uint64_t *ua, const uint64_t *ub, const uint64_t *uc, const int64_t *off4, const uint64_t *va,
+                               const uint64_t *vb, const uint64_t *vc, const uint64_t *vd, int64_t rows_live, int64_t rows, int64_t n_lin,
+                               uint64_t *out_aug, int64_t stride_words, int device)
+{
+	return terms_expand_words(Terms(lin, off2, ta, tb, rows_live, rows, n_lin, off3, ua, ub, uc).quartic(off4, va, vb, vc, vd), out_aug, stride_words,
+	                          device, true);
+}
+int gf2bv_solve_quartic_terms(const uint64_t *lin, const int64_t *off2, const uint64_t *ta, const uint64_t *tb, const int64_t *off3,
+                              const uint64_t *ua, const uint64_t *ub, const uint64_t *uc, const int64_t *off4, const uint64_t *va,
+                              const uint64_t *vb, const uint64_t *vc, const uint64_t *vd, int64_t rows_live, int64_t rows, int64_t n_lin,
+                              int mode, int device, gf2bv_result **out)
+{
+	return solve_terms(Terms(lin, off2, ta, tb, rows_live, rows, n_lin, off3, ua, ub, uc).quartic(off4, va, vb, vc, vd), mode, device, out, true);
+}
+
+int gf2bv_quartic_chunks(int64_t n_lin, int32_t *quad_chunk, int32_t *cubic_chunk, int32_t *quartic_chunk)
+{
+	return catching([&]() -> int {
+	if (!quad_chunk || !cubic_chunk || !quartic_chunk) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (n_lin < 1 || n_lin > 65535) return fail(GF2BV_ERR_ARG, "n_lin must be 1..65535");
+	const QuarticLaunch l = quartic_launch(n_lin, 2);
+	if ((i64)l.lds > kQuarticLdsBytes)
+		return fail(GF2BV_ERR_ARG, "the operands and the staged cubic rows of this n_lin do not fit the expansion kernel's LDS (160 KiB)");
+	*quad_chunk = l.tch2;
+	*cubic_chunk = l.tch3;
+	*quartic_chunk = l.tch4;
+	return GF2BV_OK;
+	});
 }
 
 int gf2bv_cubic_chunks(int64_t n_lin, int32_t *quad_chunk, int32_t *cubic_chunk)

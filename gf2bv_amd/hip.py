@@ -39,6 +39,7 @@ EXPORTS = [
     "gf2bv_factor_quad_terms", "gf2bv_factor_append_quad_terms", "gf2bv_solve_rhs_quad_terms", "gf2bv_solve_batch_quad_terms",
     "gf2bv_quad_expand_batch_words",
     "gf2bv_cubic_expand_device", "gf2bv_cubic_expand_words", "gf2bv_solve_cubic_terms", "gf2bv_cubic_chunks",
+    "gf2bv_quartic_expand_device", "gf2bv_quartic_expand_words", "gf2bv_solve_quartic_terms", "gf2bv_quartic_chunks",
     "gf2bv_xl3_expand_device", "gf2bv_xl3_expand_words", "gf2bv_solve_xl3_words", "gf2bv_solve_xl3_quad_terms",
     "gf2bv_quad_specialise_device", "gf2bv_quad_specialise_words", "gf2bv_xl3_expand_batch_device", "gf2bv_xl3_expand_batch_words",
     "gf2bv_solve_xl3_guess_words", "gf2bv_solve_xl3_guess_quad_terms", "gf2bv_xl3_guess_chunk", "gf2bv_xl3_guess_chunk_device",
@@ -170,6 +171,10 @@ def lib():
         L.gf2bv_cubic_expand_words.argtypes = [vp] * 8 + [i64, i64, i64, vp, i64, i32]
         L.gf2bv_solve_cubic_terms.argtypes = [vp] * 8 + [i64, i64, i64, i32, i32, pp]
         L.gf2bv_cubic_chunks.argtypes = [i64, vp, vp]
+        L.gf2bv_quartic_expand_device.argtypes = [vp] * 13 + [i64, i64, i64, vp, i64, i32, vp]
+        L.gf2bv_quartic_expand_words.argtypes = [vp] * 13 + [i64, i64, i64, vp, i64, i32]
+        L.gf2bv_solve_quartic_terms.argtypes = [vp] * 13 + [i64, i64, i64, i32, i32, pp]
+        L.gf2bv_quartic_chunks.argtypes = [i64, vp, vp, vp]
         for d in ("xl3", "xl4"):                       # the two degrees: the same signatures
             getattr(L, f"gf2bv_{d}_expand_device").argtypes = [vp, i64, i64, i64, i64, vp, i64, i32, vp]
             getattr(L, f"gf2bv_{d}_expand_words").argtypes = [vp, i64, i64, i64, i64, vp, i64, i32]
@@ -869,6 +874,59 @@ def solve_cubic_terms(lin, off2, ta, tb, off3, ua, ub, uc, n_lin: int, rows: int
 def xl4_cols(n_lin: int) -> int:
     """columns of the degree-4 XL system in n_lin unknowns: degree 3's and the quadruples"""
     return xl3_cols(n_lin) + n_lin * (n_lin - 1) * (n_lin - 2) * (n_lin - 3) // 24
+
+
+# -- quartic systems kept factored: the cubic functions above one arity up (gf2bv_hip.h, "quartic expansion") ------------------------------
+def _quartic_terms(lin, off2, ta, tb, off3, ua, ub, uc, off4, va, vb, vc, vd, n_lin: int):
+    """the factored form of gf2bv_quartic_expand_* as contiguous arrays, shapes checked against each other"""
+    cubic = _cubic_terms(lin, off2, ta, tb, off3, ua, ub, uc, n_lin)
+    wl = cubic[0].shape[1]
+    off4 = np.ascontiguousarray(off4, dtype=np.int64).reshape(-1)
+    ops = tuple(np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, wl) for x in (va, vb, vc, vd))
+    if len(off4) != len(cubic[0]) + 1 or len({len(x) for x in ops}) != 1 or (len(off4) and off4[-1] != len(ops[0])):
+        raise ValueError("off4 needs one entry per row of lin and one more, ending at the number of operands in va, vb, vc and vd")
+    return cubic + (off4,) + ops
+
+
+def quartic_chunks(n_lin: int) -> tuple:
+    """(quadratic, cubic, quartic) terms of a row that one pass of the quartic expansion kernel holds in LDS (gf2bv_quartic_chunks,
+    host only); ValueError for an n_lin whose staged cubic rows do not fit the LDS"""
+    q, c, v = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    _check(lib().gf2bv_quartic_chunks(n_lin, ctypes.byref(q), ctypes.byref(c), ctypes.byref(v)))
+    return q.value, c.value, v.value
+
+
+def quartic_expand_words(lin, off2, ta, tb, off3, ua, ub, uc, off4, va, vb, vc, vd, n_lin: int, rows: int | None = None,
+                         stride_words: int | None = None, device: int = 0) -> np.ndarray:
+    """Factored quartic equations (cubic_expand_words' rows ^ XOR of va[v] * vb[v] * vc[v] * vd[v], v in off4[r] .. off4[r + 1]; the
+    products exact in GF(2)[x] / (x_i^2 + x_i)) expanded on the device into rows over the xl4_cols(n_lin) columns of the
+    augmented-words layout: [rows, stride_words] uint64, rows beyond len(lin) zero (gf2bv_quartic_expand_words)."""
+    terms = _quartic_terms(lin, off2, ta, tb, off3, ua, ub, uc, off4, va, vb, vc, vd, n_lin)
+    rows = len(terms[0]) if rows is None else rows
+    stride = (xl4_cols(n_lin) + 1 + 63) // 64 if stride_words is None else stride_words
+    out = np.empty((max(rows, 0), max(stride, 0)), dtype=np.uint64)
+    _check(lib().gf2bv_quartic_expand_words(*_ptrs(*terms), len(terms[0]), rows, n_lin, out.ctypes.data, stride, device))
+    return out
+
+
+def quartic_expand_device(d_lin: int, d_off2: int, d_ta: int, d_tb: int, d_off3: int, d_ua: int, d_ub: int, d_uc: int, d_off4: int, d_va: int,
+                          d_vb: int, d_vc: int, d_vd: int, rows_live: int, rows: int, n_lin: int, d_aug: int, stride: int, device: int = 0,
+                          stream: int = 0) -> None:
+    """quartic_expand_words with everything resident in device memory: the kernel is enqueued on `stream` and the call returns; a
+    solve_device on the same stream reads the finished rows."""
+    _check(lib().gf2bv_quartic_expand_device(d_lin, d_off2, d_ta, d_tb, d_off3, d_ua, d_ub, d_uc, d_off4, d_va, d_vb, d_vc, d_vd, rows_live, rows,
+                                             n_lin, d_aug, stride, device, stream or None))
+
+
+def solve_quartic_terms(lin, off2, ta, tb, off3, ua, ub, uc, off4, va, vb, vc, vd, n_lin: int, rows: int | None = None,
+                        mode: int = MODE_SINGLE, device: int = 0) -> Solution:
+    """The factored quartic system uploaded, expanded on the device and solved there (gf2bv_solve_quartic_terms): what solve_words
+    returns for quartic_expand_words of the same arrays.  rows (default: max(len(lin), columns)) >= the columns."""
+    terms = _quartic_terms(lin, off2, ta, tb, off3, ua, ub, uc, off4, va, vb, vc, vd, n_lin)
+    rows = max(len(terms[0]), xl4_cols(n_lin)) if rows is None else rows
+    h = ctypes.c_void_p()
+    _check(lib().gf2bv_solve_quartic_terms(*_ptrs(*terms), len(terms[0]), rows, n_lin, mode, device, ctypes.byref(h)))
+    return _take(h, mode)
 
 
 # The xl3_* and xl4_* functions below are one body each, taking the degree (3: multipliers 1 and x_k, n + 1 rows an equation; 4: also

@@ -17,12 +17,13 @@ tests.harness_models run on it unchanged); ``get_eqs`` still returns the referen
 from __future__ import annotations
 
 import operator
+from math import comb
 from typing import Iterable, Optional, Sequence
 
 import numpy as np
 
 from ._internal import (m4ri_solve_cubic_packed, m4ri_solve_many_quad_packed, m4ri_solve_packed, m4ri_solve_quad_packed,
-                        m4ri_solve_xl3_guess_quad_packed, m4ri_solve_xl3_quad_packed, m4ri_solve_xl4_guess_cubic_packed,
+                        m4ri_solve_quartic_packed, m4ri_solve_xl3_guess_quad_packed, m4ri_solve_xl3_quad_packed, m4ri_solve_xl4_guess_cubic_packed,
                         m4ri_solve_xl4_guess_quad_packed, m4ri_solve_xl4_cubic_packed, m4ri_solve_xl4_quad_packed)
 from .bitvec import BitVec
 from .linsys import _QuadraticPoints, _SolveSurface, _eqs_from_words, _raw_value, _space_points, xl3_cols, xl4_cols
@@ -728,9 +729,9 @@ class PackedCubicBitVec(_TermsBitVec):
         return sum((bin(e & point).count("1") & 1) << k for k, e in enumerate(self._eq_ints()))
 
 
-def _refuse_system(name: str):
+def _refuse_system(name: str, system: str = "PackedCubicSystem"):
     def method(self, *args, **kwargs):
-        raise TypeError(f"{name} is not built for a PackedCubicSystem")
+        raise TypeError(f"{name} is not built for a {system}")
     method.__name__ = name
     return method
 
@@ -897,3 +898,213 @@ class PackedCubicGuessSystem(PackedCubicSystem):
 
     def _guess_sol(self, full: int) -> tuple:
         return self._convert_sol(full)                 # (this class has no block of product unknowns behind the generators')
+
+
+# ---- quartic systems kept factored -------------------------------------------------------------------------------------------------
+# One degree up again: a symbolic bit is a linear form plus products of two, of three and of four affine forms, and the rows over the
+# n + C(n,2) + C(n,3) + C(n,4) columns of degree-4 XL come into being on the device (k_quartic_expand, through
+# m4ri_solve_quartic_packed / hip.quartic_expand_words).  The columns of degree <= 3 are the cubic class's, so a product of two or of
+# three forms is the same equation int in both layouts.
+def _monomial_bit(members: tuple, n: int) -> int:
+    """the bit, in an equation int over the quartic columns, of the monomial of these unknowns (descending, four at most): the
+    unknowns, then per degree the combinatorial number C(i,k) + C(j,k-1) + ... of its members"""
+    k = len(members)
+    if k < 2:
+        return 1 + members[0] if k else 0
+    return 1 + n + sum(comb(n, d) for d in range(2, k)) + sum(comb(g, k - t) for t, g in enumerate(members))
+
+
+def _monomial_of_bit(bit: int, n: int) -> tuple:
+    """the inverse of ``_monomial_bit``"""
+    c = bit - 1
+    if c < n:
+        return (c,) if c >= 0 else ()
+    c -= n
+    k = 2
+    while c >= comb(n, k):
+        c -= comb(n, k)
+        k += 1
+    members = []
+    for d in range(k, 0, -1):
+        g = d - 1
+        while comb(g + 1, d) <= c:
+            g += 1
+        members.append(g)
+        c -= comb(g, d)
+    return tuple(members)
+
+
+def _exact_product4_int(forms: tuple, n: int) -> int:
+    """the exact product of four affine forms as an equation int over the quartic columns: ``_exact_product_int`` of three of them,
+    multiplied a monomial at a time by the constant and by every unknown of the fourth (x^2 = x: the union of the members)"""
+    forms = sorted(forms, key=lambda v: bin(v).count("1"))                 # (the lightest one multiplies, as on the device)
+    d, cubic = forms[0], _exact_product_int(tuple(forms[1:]), n)
+    factors = ([()] if d & 1 else []) + [(g,) for g in range(n) if (d >> (1 + g)) & 1]
+    e = 0
+    while cubic:
+        low = cubic & -cubic
+        cubic ^= low
+        m = _monomial_of_bit(low.bit_length() - 1, n)
+        for x in factors:
+            e ^= 1 << _monomial_bit(tuple(sorted(set(m + x), reverse=True)), n)
+    return e
+
+
+_CUBIC_MIX = ("a PackedQuarticBitVec cannot be mixed with a PackedCubicBitVec: the two kinds carry different groups of products and are "
+              "not promoted; write the bits of one system with that system's mul_bit")
+
+
+class PackedQuarticBitVec(_TermsBitVec):
+    """``_TermsBitVec`` with products of two affine forms (``_off2``, ``_ta`` / ``_tb``), of three (``_off3``, ``_ua`` / ``_ub`` /
+    ``_uc``) and of four (``_off4``, ``_va`` / ``_vb`` / ``_vc`` / ``_vd``).  A product is the exact product in
+    GF(2)[x] / (x_i^2 + x_i)."""
+    __slots__ = ()
+    _ARITIES = (2, 3, 4)
+    _off2, _ta, _tb = _part(0), _part(0, 0), _part(0, 1)
+    _off3, _ua, _ub, _uc = _part(1), _part(1, 0), _part(1, 1), _part(1, 2)
+    _off4, _va, _vb, _vc, _vd = _part(2), _part(2, 0), _part(2, 1), _part(2, 2), _part(2, 3)
+
+    def __init__(self, lin, off2, ta, tb, off3, ua, ub, uc, off4, va, vb, vc, vd, n: int):
+        # [k, Wl] uint64, then per arity [k + 1] int64 and [T, Wl] per operand: immutable
+        self._lin, self._groups = lin, ((off2, (ta, tb)), (off3, (ua, ub, uc)), (off4, (va, vb, vc, vd)))
+        self._n = n                                    # unknowns of the system
+
+    def _degree(self) -> int:
+        return next((arity for arity, (_, ops) in zip((4, 3, 2), self._groups[::-1]) if len(ops[0])), 1)
+
+    def _coerce(self, other, what: str) -> "PackedQuarticBitVec":
+        if not isinstance(other, PackedQuarticBitVec):
+            if isinstance(other, PackedQuadBitVec):
+                raise TypeError(_QUAD_MIX)
+            if isinstance(other, PackedCubicBitVec):
+                raise TypeError(_CUBIC_MIX)
+            if not isinstance(other, PackedBitVec):
+                if isinstance(other, BitVec):
+                    raise TypeError("cannot mix packed and tuple-of-int BitVecs")
+                raise TypeError(f"{what} needs a PackedQuarticBitVec or a PackedBitVec")
+            other = self._from_rows(other._rows, self._n)
+        if other._lin.shape[1] != self._lin.shape[1] or other._n != self._n:
+            raise ValueError("Cannot mix bitvecs over different numbers of unknowns")
+        return other
+
+    def _eq_ints(self) -> list:
+        """every bit as an equation int over the quartic columns, expanded on the host a product at a time"""
+        n = self._n
+        ints = lambda rows: [int.from_bytes(r.tobytes(), "little") & ((1 << (n + 1)) - 1) for r in rows]      # noqa: E731
+        out = ints(self._lin)
+        for (off, ops), product in zip(self._groups, (_exact_product_int, _exact_product_int, _exact_product4_int)):
+            forms = list(zip(*[ints(x) for x in ops]))
+            for k in range(len(out)):
+                for t in range(off[k], off[k + 1]):
+                    out[k] ^= product(forms[t], n)
+        return out
+
+    def evaluate(self, s: int) -> int:
+        """Value under the raw point ``s`` over the quartic columns (bit c = column c: the n unknowns, their pairs, triples and
+        quadruples), as BitVec.evaluate gives it for the expanded bits; on the host."""
+        point = ((s << 1) | 1) & ((1 << (xl4_cols(self._n) + 1)) - 1)
+        return sum((bin(e & point).count("1") & 1) << k for k, e in enumerate(self._eq_ints()))
+
+
+class PackedQuarticSystem(PackedLinearSystem):
+    """Equations of degree <= 4 written directly and kept factored: ``gens()`` are PackedLinearSystem's PackedBitVecs, ``mul_bit``
+    multiplies single bits up to degree 4 (exact products), and the solve methods hand the factored arrays to the device, which
+    expands them over the n + C(n,2) + C(n,3) + C(n,4) columns of degree-4 XL and solves.  ``solve_all`` keeps the points of the
+    linearised space whose pair, triple and quadruple coordinates are the products of their linear bits.  Not a PackedCubicSystem:
+    its columns differ, and the searches over cubic spaces take anything that is one."""
+
+    def __init__(self, sizes: Iterable[int]):
+        super().__init__(sizes)
+        self._lin_size = sum(self._sizes)
+        self._cols = xl4_cols(self._lin_size)          # (``_words`` stays the words of a linear form: the generators have no product coordinates)
+
+    _xl_index = _QuadraticPoints._xl_index
+    _xl4_index = _QuadraticPoints._xl4_index
+    _xl_products_match = _QuadraticPoints._xl_products_match
+
+    def _single(self, a) -> PackedQuarticBitVec:
+        if isinstance(a, PackedQuadBitVec):
+            raise TypeError(_QUAD_MIX)
+        if isinstance(a, PackedCubicBitVec):
+            raise TypeError(_CUBIC_MIX)
+        if not isinstance(a, (PackedBitVec, PackedQuarticBitVec)):
+            raise TypeError("mul_bit needs PackedBitVecs or PackedQuarticBitVecs of this system")
+        if len(a) != 1:
+            raise ValueError("The inputs should be single bits")
+        rows = a._rows if isinstance(a, PackedBitVec) else a._lin
+        if rows.shape[1] != self._words:
+            raise ValueError("Cannot mix bitvecs over different numbers of unknowns")
+        return PackedQuarticBitVec._from_rows(rows, self._lin_size) if isinstance(a, PackedBitVec) else a
+
+    def mul_bit(self, a, b) -> PackedQuarticBitVec:
+        """the exact product of two single bits whose degrees (structural: the highest arity a bit has terms of) add up to 4 at most.
+        By distributivity lin_a lin_b is one quadratic term, a product of either bit times the other's linear form one term of the
+        next arity (the form appended as one more operand), and two products of two forms one quartic term."""
+        a, b = self._single(a), self._single(b)
+        da, db = a._degree(), b._degree()
+        if da + db > 4:
+            raise TypeError(f"mul_bit of bits of degree {da} and {db} is of degree {da + db}, above 4")
+        (_, a2), (_, a3), _ = a._groups                # (a term of a's and one of b's whose arities add up to more than 4 cannot both exist)
+        (_, b2), (_, b3), _ = b._groups
+        by = lambda ops, form: ops + (np.repeat(form, len(ops[0]), axis=0),)                      # noqa: E731
+        cat = lambda *groups: [np.concatenate(xs) for xs in zip(*groups)]                          # noqa: E731
+        ia, ib = np.repeat(np.arange(len(a2[0])), len(b2[0])), np.tile(np.arange(len(b2[0])), len(a2[0]))      # every pair of quadratic terms
+        cubic = cat(by(a2, b._lin), by(b2, a._lin))
+        quartic = cat(by(a3, b._lin), by(b3, a._lin), (a2[0][ia], a2[1][ia], b2[0][ib], b2[1][ib]))
+        one = lambda k: np.array([0, k], dtype=np.int64)                                            # noqa: E731
+        return PackedQuarticBitVec(np.zeros((1, self._words), dtype=np.uint64), one(1), a._lin, b._lin, one(len(cubic[0])), *cubic,
+                                   one(len(quartic[0])), *quartic, self._lin_size)
+
+    # -- zeros -> the factored arrays the device expands ----------------------------------------------------------------------------
+    def _terms(self, zeros: Sequence):
+        """(lin, off2, ta, tb, off3, ua, ub, uc, off4, va, vb, vc, vd) of all the bits of ``zeros``, in order; no row is dropped
+        (_zeros_terms)"""
+        if any(isinstance(z, PackedCubicBitVec) for z in zeros):
+            raise TypeError(_CUBIC_MIX)
+        return _zeros_terms(zeros, PackedQuarticBitVec, "quartic", self._words)
+
+    def get_eqs(self, zeros: Sequence) -> list:
+        """equation ints over the quartic columns, expanded on the device (needs the GPU); zero rows are dropped"""
+        from . import hip                              # noqa: PLC0415  (ctypes binding, first use only)
+        terms = self._terms(zeros)
+        if not len(terms[0]):
+            return []
+        return _eqs_from_words(hip.quartic_expand_words(*terms, self._lin_size), self._cols)
+
+    # -- boundary call ---------------------------------------------------------------------------------------------------------------
+    def _solve_internal(self, zeros: Sequence, mode: int):
+        terms = self._terms(zeros)
+        return m4ri_solve_quartic_packed(*terms, self._lin_size, max(len(terms[0]), self._cols), mode)      # (the boundary wants rows >= cols)
+
+    def convert_sol(self, s: int) -> Optional[tuple]:
+        """the values of the generators at a raw point over the quartic columns whose pair, triple and quadruple coordinates are the
+        products of its linear bits, None for any other point"""
+        n = self._lin_size
+        if not self._xl_products_match(s, n, 4):
+            return None
+        return self._convert_sol(s & ((1 << n) - 1))
+
+    def solve_one(self, zeros: Sequence):
+        # the particular solution of the linearised system need not be consistent: take the first one that is
+        for sol in self.solve_all(zeros):
+            return sol
+        return None
+
+    def _raw_point(self, lin: int) -> int:
+        """the raw point over the quartic columns whose linear part is ``lin``"""
+        n = self._lin_size
+        pi, pj, ti, tj, tl = self._xl_index(n)
+        qi, qj, ql, qp = self._xl4_index(n)
+        x = np.array([(lin >> i) & 1 for i in range(n)], dtype=np.uint8)
+        bits = np.concatenate([x, x[pi] & x[pj], x[ti] & x[tj] & x[tl], x[qi] & x[qj] & x[ql] & x[qp]])
+        return int.from_bytes(np.packbits(bits, bitorder="little").tobytes(), "little")
+
+    def evaluate(self, bv, sol: tuple) -> int:
+        raw = _raw_value(sol, self._sizes)
+        return bv.evaluate(self._raw_point(raw) if isinstance(bv, PackedQuarticBitVec) else raw)
+
+
+for _name in ("get_rows", "_stack_rows", "_flat_rows", "factor", "bit_assert", "_solve_internal_rhs", "solve_raw_one_rhs", "solve_raw_space_rhs",
+              "solve_one_rhs"):
+    setattr(PackedQuarticSystem, _name, _refuse_system(_name, "PackedQuarticSystem"))
+del _name

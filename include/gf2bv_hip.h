@@ -437,6 +437,44 @@ int gf2bv_solve_cubic_terms(const uint64_t *lin, const int64_t *off2, const uint
                             int64_t n_lin, int mode, int device, gf2bv_result **out);
 int gf2bv_cubic_chunks(int64_t n_lin, int32_t *quad_chunk, int32_t *cubic_chunk);
 
+/* ---- quartic expansion: factored quartic equations -> linearised rows over the monomials of degree <= 4, on the device --------
+ * A quartic equation in n_lin unknowns kept FACTORED: the cubic expansion's form with products of four affine forms too, every form
+ * Wl = ceil((n_lin + 1) / 64) words in the equation-int order (bit 0 = constant, bit 1 + g = unknown g; bits above n_lin ignored).
+ *   lin, off2, ta, tb, off3, ua, ub, uc   as for the cubic expansion,
+ *   off4[rows_live + 1]                   int64, starts at 0, never decreases: row r owns the products va[v] * vb[v] * vc[v] * vd[v],
+ *                                         v in off4[r] .. off4[r+1],
+ *   va[T4][Wl], vb, vc, vd                their operands, T4 = off4[rows_live] (may be null when T4 is 0, host forms only).
+ * Row r of the output is e = lin[r] ^ XOR_t ta[t] tb[t] ^ XOR_u ua[u] ub[u] uc[u] ^ XOR_v va[v] vb[v] vc[v] vd[v], the products being
+ * the EXACT products of GF(2)[x] / (x_i^2 + x_i), constants included.  The layout is degree-4 XL's augmented-words row over
+ * cols4 = n_lin + C(n_lin,2) + C(n_lin,3) + C(n_lin,4): column c < n_lin unknown c, pairs and triples where the cubic expansion puts
+ * them, quadruple (i, j, l, p), p < l < j < i, at cols3 + C(i,4) + C(j,3) + C(l,2) + p, the constant at column cols4, every bit behind
+ * it up to the end of the stride zero.  Rows rows_live .. rows - 1 are written as zeros.
+ * gf2bv_quartic_expand_device: everything in device memory; the kernel (k_quartic_expand) is enqueued on `stream` (a HIP stream
+ * handle or NULL) and the call returns: gf2bv_solve_device on the same stream consumes d_aug with no synchronisation in between.
+ * d_aug 16-byte aligned, stride_words even and >= ceil((cols4 + 1) / 64).  The offsets cannot be checked there: a row whose offsets
+ * (of any kind) decrease or are negative is expanded as its linear part.
+ * gf2bv_quartic_expand_words: host pointers in, rows x stride_words words back in host memory (upload, kernel, download).
+ * gf2bv_solve_quartic_terms: upload, expansion into a buffer of the pool, gf2bv_solve_device on the same pool stream; rows >= cols4.
+ * Argument errors (null pointers, n_lin < 1 or cols4 >= 2^31 - 64, rows_live outside 0..rows, any of the three offset arrays not
+ * starting at 0 or decreasing, rows < cols4 for the solve entry, a bad stride or mode, operands and staged rows that do not fit the
+ * kernel's LDS -- it stages cubic rows of ceil((cols3 + 1) / 64) words there, which 160 KiB hold up to n_lin of about 157) return
+ * GF2BV_ERR_ARG before any device is touched; an expansion that does not fit on the device returns GF2BV_ERR_NOMEM.
+ * gf2bv_quartic_chunks (pure, no device): how many quadratic, cubic and quartic terms of a row one pass of the kernel holds in LDS
+ * at this n_lin; a row with more of any takes several passes. */
+int gf2bv_quartic_expand_device(const void *d_lin, const void *d_off2, const void *d_ta, const void *d_tb, const void *d_off3,
+                                const void *d_ua, const void *d_ub, const void *d_uc, const void *d_off4, const void *d_va,
+                                const void *d_vb, const void *d_vc, const void *d_vd, int64_t rows_live, int64_t rows, int64_t n_lin,
+                                void *d_aug, int64_t stride_words, int device, void *stream);
+int gf2bv_quartic_expand_words(const uint64_t *lin, const int64_t *off2, const uint64_t *ta, const uint64_t *tb, const int64_t *off3,
+                               const uint64_t *ua, const uint64_t *ub, const uint64_t *uc, const int64_t *off4, const uint64_t *va,
+                               const uint64_t *vb, const uint64_t *vc, const uint64_t *vd, int64_t rows_live, int64_t rows,
+                               int64_t n_lin, uint64_t *out_aug, int64_t stride_words, int device);
+int gf2bv_solve_quartic_terms(const uint64_t *lin, const int64_t *off2, const uint64_t *ta, const uint64_t *tb, const int64_t *off3,
+                              const uint64_t *ua, const uint64_t *ub, const uint64_t *uc, const int64_t *off4, const uint64_t *va,
+                              const uint64_t *vb, const uint64_t *vc, const uint64_t *vd, int64_t rows_live, int64_t rows,
+                              int64_t n_lin, int mode, int device, gf2bv_result **out);
+int gf2bv_quartic_chunks(int64_t n_lin, int32_t *quad_chunk, int32_t *cubic_chunk, int32_t *quartic_chunk);
+
 /* The factored form in front of the entries that keep a factorization, share one elimination or batch: each uploads the term
  * arrays (host pointers, as gf2bv_solve_quad_terms takes them), expands them into a buffer of the pool and runs the device entry
  * named on the same pool stream; the host waits only where that entry waits, and the buffers are back in the pool on return.
