@@ -4356,16 +4356,83 @@ std::vector<i64> first_independent_forms(const u64 *forms, i64 m, i64 fw)
 	return chosen;
 }
 
-// every common zero of m forms (equation-int layout, fw words) in R <= kQuadMaxEnum variables; `total` counts them all,
-// `ys` holds them when there are at most kQuadMaxPoints (in no particular order)
+// The two-pass search of a degree, which supplies what really differs (SearchPasses): `tab`, the forms of the first pass bit-sliced
+// for its search kernel; `E`, the mE forms the second pass tests, in its check kernel's layout; the two kernels and the search
+// kernel's launch shape.  `total` counts every common zero, `ys` holds them when there are at most kQuadMaxPoints (in no particular order)
+using SearchKernel = void (*)(const u64 *, int, int, u64, u64 *, u64, unsigned long long *, const u64 *, i64);
+using CheckKernel = void (*)(const u64 *, i64, int, const u64 *, u64, u64 *, u64, unsigned long long *);
+struct SearchPasses {
+	const std::vector<u64> &tab, &E;
+	i64 mE;
+	SearchKernel search;
+	CheckKernel check;
+	int R, L;                                      // variables, and how many of them a lane walks
+	unsigned block;
+	size_t lds;
+	QuadTimes &times;
+};
+
+// no form: the whole cube
+void search_whole_cube(int R, std::vector<u64> &ys, u64 *total)
+{
+	*total = 1ull << R;
+	if ((i64)*total <= kQuadMaxPoints) for (u64 y = 0; y < *total; y++) ys.push_back(y);
+}
+
+int search_two_pass(const SearchPasses &s, int device, hipStream_t st, std::vector<u64> &ys, u64 *total)
+{
+	static_assert(kQuadMaxCand == kQuadMaxPoints, "the candidate list doubles as the list of zeros");
+	const int R = s.R, L = s.L;
+	const u64 nlanes = 1ull << (R - L);
+	const dim3 grid((unsigned)((nlanes + s.block - 1) / s.block)), block(s.block);
+	const u64 ocap = (u64)kQuadMaxPoints, cap = (u64)kQuadMaxCand;
+	QDev dtab, dE, dcand, dcnt, dout;
+	HIPCHK(dtab.get(s.tab.size() * 8, device)); HIPCHK(dE.get(s.E.size() * 8, device)); HIPCHK(dcnt.get(16, device));
+	HIPCHK(hipMemcpyAsync(dtab.p, s.tab.data(), s.tab.size() * 8, hipMemcpyHostToDevice, st));
+	HIPCHK(hipMemcpyAsync(dE.p, s.E.data(), s.E.size() * 8, hipMemcpyHostToDevice, st));
+	HIPCHK(hipMemsetAsync(dcnt.p, 0, 16, st));
+	HIPCHK(dcand.get(cap * 8, device));
+	HIPCHK(dout.get(ocap * 8, device));
+	s.search<<<grid, block, s.lds, st>>>(dtab.as<u64>(), R, L, nlanes, dcand.as<u64>(), cap, dcnt.as<unsigned long long>(), nullptr, 0);
+	HIPCHK(hipGetLastError());
+	u64 cnt[2] = {0, 0};
+	HIPCHK(hipMemcpyAsync(cnt, dcnt.p, 8, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipStreamSynchronize(st));
+	s.times.candidates += (i64)cnt[0];
+	const void *found = dout.p;
+	if (s.mE == 0) {
+		cnt[1] = cnt[0];                           // every form was in the first pass: its candidates are the zeros (cap == ocap)
+		found = dcand.p;
+	} else if (cnt[0] > cap) {
+		// more candidates than can be kept: search again, each lane testing its candidates against the forms of E itself
+		s.search<<<grid, block, s.lds, st>>>(dtab.as<u64>(), R, L, nlanes, dout.as<u64>(), ocap, dcnt.as<unsigned long long>() + 1,
+		                                     dE.as<u64>(), s.mE);
+		HIPCHK(hipGetLastError());
+	} else if (cnt[0]) {
+		const u64 waves = std::min<u64>(cnt[0], 8192);
+		s.check<<<dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st>>>(dE.as<u64>(), s.mE, R, dcand.as<u64>(), cnt[0], dout.as<u64>(),
+		                                                               ocap, dcnt.as<unsigned long long>() + 1);
+		HIPCHK(hipGetLastError());
+	}
+	if (s.mE) {
+		HIPCHK(hipMemcpyAsync(cnt + 1, dcnt.as<u64>() + 1, 8, hipMemcpyDeviceToHost, st));
+		HIPCHK(hipStreamSynchronize(st));
+	}
+	*total = cnt[1];
+	if ((i64)cnt[1] <= kQuadMaxPoints) {
+		ys.resize((size_t)cnt[1]);
+		if (cnt[1]) HIPCHK(hipMemcpyAsync(ys.data(), found, cnt[1] * 8, hipMemcpyDeviceToHost, st));
+		HIPCHK(hipStreamSynchronize(st));
+	}
+	return GF2BV_OK;
+}
+
+// every common zero of m forms (equation-int layout, fw words) in R <= kQuadMaxEnum variables (total, ys: search_two_pass).  Every
+// form goes into E, so the driver's branch for an empty E is never taken here
 int quad_search_device(const u64 *forms, i64 m, i64 fw, int R, int device, hipStream_t st, std::vector<u64> &ys, u64 *total)
 {
 	ys.clear();
-	if (m == 0) {                                  // no form: the whole cube
-		*total = 1ull << R;
-		if ((i64)*total <= kQuadMaxPoints) for (u64 y = 0; y < *total; y++) ys.push_back(y);
-		return GF2BV_OK;
-	}
+	if (m == 0) { search_whole_cube(R, ys, total); return GF2BV_OK; }
 	auto coef = [&](i64 f, i64 bit) { return qbit(forms + f * fw, bit); };
 	auto pair_bit = [&](i64 j, i64 k) { return 1 + R + (k > j ? k * (k - 1) / 2 + j : j * (j - 1) / 2 + k); };
 	// the 64 forms of the first pass: the first that are linearly independent (a form in the span of those already chosen
@@ -4391,45 +4458,8 @@ int quad_search_device(const u64 *forms, i64 m, i64 fw, int R, int device, hipSt
 		}
 	}
 	const int H = std::max(0, std::min(R - 10, 18)), L = R - H;
-	const u64 nlanes = 1ull << H;
-	const int bd = (int)std::min<u64>(256, (nlanes + 63) / 64 * 64);
-	const dim3 grid((unsigned)((nlanes + bd - 1) / bd));
-	const size_t lds = (size_t)bd * L * 8;
-	const u64 ocap = (u64)kQuadMaxPoints;
-	QDev dtab, dE, dcand, dcnt, dout;
-	HIPCHK(dtab.get(tab.size() * 8, device)); HIPCHK(dE.get(E.size() * 8, device)); HIPCHK(dcnt.get(16, device));
-	HIPCHK(hipMemcpyAsync(dtab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpyAsync(dE.p, E.data(), E.size() * 8, hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemsetAsync(dcnt.p, 0, 16, st));
-	const u64 cap = (u64)kQuadMaxCand;
-	HIPCHK(dcand.get(cap * 8, device));
-	HIPCHK(dout.get(ocap * 8, device));
-	k_quad_search<<<grid, dim3(bd), lds, st>>>(dtab.as<u64>(), R, L, nlanes, dcand.as<u64>(), cap, dcnt.as<unsigned long long>(), nullptr, 0);
-	HIPCHK(hipGetLastError());
-	u64 cnt[2] = {0, 0};
-	HIPCHK(hipMemcpyAsync(cnt, dcnt.p, 8, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipStreamSynchronize(st));
-	g_quad_times.candidates += (i64)cnt[0];
-	if (cnt[0] > cap) {
-		// more candidates than can be kept: search again, each lane testing its candidates against every form itself
-		k_quad_search<<<grid, dim3(bd), lds, st>>>(dtab.as<u64>(), R, L, nlanes, dout.as<u64>(), ocap, dcnt.as<unsigned long long>() + 1,
-		                                           dE.as<u64>(), m);
-		HIPCHK(hipGetLastError());
-	} else if (cnt[0]) {
-		const u64 waves = std::min<u64>(cnt[0], 8192);
-		k_quad_check<<<dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st>>>(dE.as<u64>(), m, R, dcand.as<u64>(), cnt[0], dout.as<u64>(),
-		                                                                     ocap, dcnt.as<unsigned long long>() + 1);
-		HIPCHK(hipGetLastError());
-	}
-	HIPCHK(hipMemcpyAsync(cnt + 1, dcnt.as<u64>() + 1, 8, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipStreamSynchronize(st));
-	*total = cnt[1];
-	if ((i64)cnt[1] <= kQuadMaxPoints) {
-		ys.resize((size_t)cnt[1]);
-		if (cnt[1]) HIPCHK(hipMemcpyAsync(ys.data(), dout.p, cnt[1] * 8, hipMemcpyDeviceToHost, st));
-		HIPCHK(hipStreamSynchronize(st));
-	}
-	return GF2BV_OK;
+	const unsigned bd = (unsigned)std::min<u64>(256, ((1ull << H) + 63) / 64 * 64);
+	return search_two_pass({ tab, E, m, k_quad_search, k_quad_check, R, L, bd, (size_t)bd * L * 8, g_quad_times }, device, st, ys, total);
 }
 
 int quad_plan_build(QuadPlan &P, const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n, int device, hipStream_t st)
@@ -4513,16 +4543,6 @@ int quad_collect(const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n, i
 	return GF2BV_OK;
 }
 
-int check_quad_space(const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n_lin)
-{
-	if (!origin || (d > 0 && !basis)) return fail(GF2BV_ERR_ARG, "null pointer");
-	if (d < 0 || words <= 0) return fail(GF2BV_ERR_ARG, "dimension must be >= 0 and words > 0");
-	if (n_lin < 1 || n_lin > 46340) return fail(GF2BV_ERR_ARG, "n_lin must be 1..46340");
-	if (words < (n_lin + n_lin * (n_lin - 1) / 2 + 63) / 64)
-		return fail(GF2BV_ERR_ARG, "words does not cover n_lin + n_lin(n_lin-1)/2 columns");
-	return GF2BV_OK;
-}
-
 // what gf2bv_quad_plan and gf2bv_quad_plan_device hand out of a built plan
 void quad_plan_export(const QuadPlan &P, int64_t *r, int64_t *r_eff, int64_t *m, int64_t *form_words, uint64_t *forms, int64_t forms_cap)
 {
@@ -4588,136 +4608,6 @@ int search_alloc(QuadTimes &times, int64_t dimension, int64_t words, int64_t max
 }
 
 }  // namespace
-
-extern "C" {
-
-int gf2bv_quad_plan(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin,
-                    int64_t *r, int64_t *r_eff, int64_t *m, int64_t *form_words, uint64_t *forms_, int64_t forms_cap)
-{
-	const u64 *origin = reinterpret_cast<const u64 *>(origin_), *basis = reinterpret_cast<const u64 *>(basis_);
-	return catching([&]() -> int {
-	int rc = check_quad_space(origin, basis, dimension, words, n_lin);
-	if (rc) return rc;
-	if (!r || !r_eff || !m || !form_words) return fail(GF2BV_ERR_ARG, "null pointer");
-	QuadPlan P;
-	rc = quad_plan_build(P, origin, basis, dimension, words, n_lin, -1, nullptr);
-	if (rc) return rc;
-	quad_plan_export(P, r, r_eff, m, form_words, forms_, forms_cap);
-	return GF2BV_OK;
-	});
-}
-
-int gf2bv_quad_plan_device(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin, int device,
-                           int64_t *r, int64_t *r_eff, int64_t *m, int64_t *form_words, uint64_t *forms_, int64_t forms_cap)
-{
-	const u64 *origin = reinterpret_cast<const u64 *>(origin_), *basis = reinterpret_cast<const u64 *>(basis_);
-	return guarded([&]() -> int {
-	int rc = check_quad_space(origin, basis, dimension, words, n_lin);
-	if (rc) return rc;
-	if (!r || !r_eff || !m || !form_words) return fail(GF2BV_ERR_ARG, "null pointer");
-	rc = check_device(device);
-	if (rc) return rc;
-	hipStream_t st = nullptr;
-	HIPCHK(pool().stream(&st, device, 0));
-	std::unique_ptr<void, std::function<void(void *)>> keep(st, [&](void *) { pool().release_stream(st, device, 0); });
-	QuadPlan P;
-	rc = quad_plan_build(P, origin, basis, dimension, words, n_lin, device, st);
-	if (rc) return rc;
-	quad_plan_export(P, r, r_eff, m, form_words, forms_, forms_cap);
-	return GF2BV_OK;
-	});
-}
-
-int gf2bv_quad_points(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin,
-                      const uint64_t *ys_, int64_t nys, int64_t y_words, uint64_t *out_words_)
-{
-	const u64 *origin = reinterpret_cast<const u64 *>(origin_), *basis = reinterpret_cast<const u64 *>(basis_);
-	const u64 *ys = reinterpret_cast<const u64 *>(ys_);
-	u64 *out_words = reinterpret_cast<u64 *>(out_words_);
-	return catching([&]() -> int {
-	int rc = check_quad_space(origin, basis, dimension, words, n_lin);
-	if (rc) return rc;
-	if (nys < 0 || (nys > 0 && (!ys || !out_words))) return fail(GF2BV_ERR_ARG, "null pointer");
-	QuadPlan P;
-	rc = quad_plan_build(P, origin, basis, dimension, words, n_lin, -1, nullptr);
-	if (rc) return rc;
-	if (P.reff < 0 || P.inconsistent) return fail(GF2BV_ERR_ARG, "the space has no forms to map from");
-	if (y_words < std::max<i64>(1, (P.reff + 63) / 64)) return fail(GF2BV_ERR_ARG, "y_words does not cover r_eff bits");
-	std::vector<u64> c((size_t)P.dw);
-	for (i64 k = 0; k < nys; k++)
-		if (!quad_point(P, ys + k * y_words, out_words + k * words, c.data()))
-			return fail(GF2BV_ERR_ARG, "an assignment that is not a common zero of the forms");
-	return GF2BV_OK;
-	});
-}
-
-int gf2bv_quad_forms_search(const uint64_t *forms_, int64_t m, int64_t r_eff, int device, int64_t max_out, int64_t *count,
-                            uint64_t *out_)
-{
-	const u64 *forms = reinterpret_cast<const u64 *>(forms_);
-	u64 *out = reinterpret_cast<u64 *>(out_);
-	return guarded([&]() -> int {
-	if (!count || (m > 0 && !forms) || (max_out > 0 && !out) || m < 0 || max_out < 0) return fail(GF2BV_ERR_ARG, "null pointer");
-	if (r_eff < 0 || r_eff > kQuadMaxEnum) return fail(GF2BV_ERR_ARG, "r_eff must be 0..40");
-	*count = 0;
-	int rc = check_device(device);
-	if (rc) return rc;
-	hipStream_t st = nullptr;
-	HIPCHK(pool().stream(&st, device, 0));
-	std::unique_ptr<void, std::function<void(void *)>> keep(st, [&](void *) { pool().release_stream(st, device, 0); });
-	std::vector<u64> ys;
-	u64 total = 0;
-	rc = quad_search_device(forms, m, (r_eff + r_eff * (r_eff - 1) / 2 + 64) / 64, (int)r_eff, device, st, ys, &total);
-	if (rc) return rc;
-	*count = (int64_t)total;
-	if ((i64)total > kQuadMaxPoints && max_out > 0) return fail(GF2BV_ERR_NOMEM, "more common zeros than can be collected");
-	std::sort(ys.begin(), ys.end());
-	std::copy(ys.begin(), ys.begin() + std::min<i64>((i64)ys.size(), max_out), out);
-	return GF2BV_OK;
-	});
-}
-
-int gf2bv_quad_search(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin,
-                      int max_enum, int64_t max_solutions, int device, int64_t *count, int64_t *lin_rank, uint64_t *out_words_)
-{
-	if (max_solutions > 0 && !out_words_) return fail(GF2BV_ERR_ARG, "null pointer");
-	uint64_t *pts = nullptr;
-	const int rc = gf2bv_quad_search_alloc(origin_, basis_, dimension, words, n_lin, max_enum, max_solutions, device, count, lin_rank,
-	                                       &pts);
-	if (rc == GF2BV_OK && pts) memcpy(out_words_, pts, sizeof(uint64_t) * (size_t)(std::min<int64_t>(*count, max_solutions) * words));
-	gf2bv_quad_free(pts);
-	return rc;
-}
-
-int gf2bv_quad_search_alloc(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin,
-                            int max_enum, int64_t max_solutions, int device, int64_t *count, int64_t *lin_rank, uint64_t **out_words)
-{
-	const u64 *origin = reinterpret_cast<const u64 *>(origin_), *basis = reinterpret_cast<const u64 *>(basis_);
-	return guarded([&]() -> int {
-	int rc = check_quad_space(origin, basis, dimension, words, n_lin);
-	if (rc) return rc;
-	if (!count || !lin_rank || !out_words) return fail(GF2BV_ERR_ARG, "null pointer");
-	if (max_enum < 0 || max_enum > kQuadMaxEnum) return fail(GF2BV_ERR_ARG, "max_enum must be 0..40");
-	if (max_solutions < 0) return fail(GF2BV_ERR_ARG, "max_solutions must be >= 0");
-	return search_alloc(g_quad_times, dimension, words, max_solutions, device, count, lin_rank, out_words,
-	                    [&](hipStream_t st, std::vector<u64> &pts, std::vector<u64> &coef, u64 *total, bool *gave_up) {
-		return quad_collect(origin, basis, dimension, words, n_lin, max_enum, device, st, 0, 0, pts, coef, total,
-		                    reinterpret_cast<i64 *>(lin_rank), gave_up);
-	});
-	});
-}
-
-void gf2bv_quad_free(uint64_t *words) { free(words); }
-
-void gf2bv_quad_last_times(double *out8)
-{
-	if (!out8) return;
-	const QuadTimes &t = g_quad_times;
-	const double v[8] = {t.reduce, t.forms, t.affine, t.search, t.relin, t.total, (double)t.levels, (double)t.candidates};
-	std::copy(v, v + 8, out8);
-}
-
-}  // extern "C"
 
 // ---- cubic search: the consistent points of a solution space over the degree-3 columns -----------------------------------
 //   A space x(c) = o ^ B c over n linear coordinates followed by the C(n,2) pair and the C(n,3) triple
@@ -4947,18 +4837,14 @@ bool cubic_point(const CubicPlan &P, u64 y, u64 *x, u64 *c_orig)
 	return true;
 }
 
-// every common zero of m cubic forms (equation-int layout, fw words) in R <= kCubicMaxEnum variables; total, ys: as quad_search_device
+// every common zero of m cubic forms (equation-int layout, fw words) in R <= kCubicMaxEnum variables (total, ys: search_two_pass).  Only
+// the forms outside the first pass go into E: with none left the driver reads the candidates as the zeros
 int cubic_search_device(const u64 *forms, i64 m, i64 fw, int R, int device, hipStream_t st, std::vector<u64> &ys, u64 *total)
 {
 	ys.clear();
-	if (m == 0) {                                  // no form: the whole cube
-		*total = 1ull << R;
-		if ((i64)*total <= kQuadMaxPoints) for (u64 y = 0; y < *total; y++) ys.push_back(y);
-		return GF2BV_OK;
-	}
+	if (m == 0) { search_whole_cube(R, ys, total); return GF2BV_OK; }
 	const i64 nb = cubic_width(R), ew = 2 + R + (i64)R * (R - 1) / 2, o2 = 1 + R, o3 = o2 + (i64)R * (R - 1) / 2;
 	if (m * ew * 8 > kCubicFormsBytes) return fail(GF2BV_ERR_NOMEM, "the cubic forms of this search take more than 1 GiB");
-	static_assert(kQuadMaxCand == kQuadMaxPoints, "the candidate list doubles as the list of zeros");
 	const std::vector<i64> chosen = first_independent_forms(forms, m, fw);
 	// the second pass tests the forms the first did not hold (a chosen form vanishes at every candidate; a zero form everywhere)
 	std::vector<char> in_first((size_t)m, 0);
@@ -4980,50 +4866,9 @@ int cubic_search_device(const u64 *forms, i64 m, i64 fw, int R, int device, hipS
 		const u64 *src = forms + chosen[c] * fw;
 		for (i64 q = 0; q < nb; q++) if (qbit(src, q)) tab[q] |= 1ull << c;
 	}
-	const int L = std::min(R, kCubicWalk), H = R - L;
-	const u64 nlanes = 1ull << H;
-	const dim3 grid((unsigned)((nlanes + 63) / 64));
-	const size_t lds = (size_t)64 * (L + L * (L - 1) / 2) * 8;
-	const u64 ocap = (u64)kQuadMaxPoints, cap = (u64)kQuadMaxCand;
-	QDev dtab, dE, dcand, dcnt, dout;
-	HIPCHK(dtab.get(tab.size() * 8, device)); HIPCHK(dE.get(E.size() * 8, device)); HIPCHK(dcnt.get(16, device));
-	HIPCHK(hipMemcpyAsync(dtab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpyAsync(dE.p, E.data(), E.size() * 8, hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemsetAsync(dcnt.p, 0, 16, st));
-	HIPCHK(dcand.get(cap * 8, device));
-	HIPCHK(dout.get(ocap * 8, device));
-	k_cubic_search<<<grid, dim3(64), lds, st>>>(dtab.as<u64>(), R, L, nlanes, dcand.as<u64>(), cap, dcnt.as<unsigned long long>(), nullptr, 0);
-	HIPCHK(hipGetLastError());
-	u64 cnt[2] = {0, 0};
-	HIPCHK(hipMemcpyAsync(cnt, dcnt.p, 8, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipStreamSynchronize(st));
-	g_cubic_times.candidates += (i64)cnt[0];
-	const void *found = dout.p;
-	if (mr == 0) {
-		cnt[1] = cnt[0];                           // every form was in the first pass: its candidates are the zeros (cap == ocap)
-		found = dcand.p;
-	} else if (cnt[0] > cap) {
-		// more candidates than can be kept: search again, each lane testing its candidates against the other forms itself
-		k_cubic_search<<<grid, dim3(64), lds, st>>>(dtab.as<u64>(), R, L, nlanes, dout.as<u64>(), ocap, dcnt.as<unsigned long long>() + 1,
-		                                            dE.as<u64>(), mr);
-		HIPCHK(hipGetLastError());
-	} else if (cnt[0]) {
-		const u64 waves = std::min<u64>(cnt[0], 8192);
-		k_cubic_check<<<dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st>>>(dE.as<u64>(), mr, R, dcand.as<u64>(), cnt[0], dout.as<u64>(),
-		                                                                      ocap, dcnt.as<unsigned long long>() + 1);
-		HIPCHK(hipGetLastError());
-	}
-	if (mr) {
-		HIPCHK(hipMemcpyAsync(cnt + 1, dcnt.as<u64>() + 1, 8, hipMemcpyDeviceToHost, st));
-		HIPCHK(hipStreamSynchronize(st));
-	}
-	*total = cnt[1];
-	if ((i64)cnt[1] <= kQuadMaxPoints) {
-		ys.resize((size_t)cnt[1]);
-		if (cnt[1]) HIPCHK(hipMemcpyAsync(ys.data(), found, cnt[1] * 8, hipMemcpyDeviceToHost, st));
-		HIPCHK(hipStreamSynchronize(st));
-	}
-	return GF2BV_OK;
+	const int L = std::min(R, kCubicWalk);
+	return search_two_pass({ tab, E, mr, k_cubic_search, k_cubic_check, R, L, 64, (size_t)64 * (L + L * (L - 1) / 2) * 8, g_cubic_times },
+	                       device, st, ys, total);
 }
 
 // every consistent point of the space and its coefficients: quad_collect without the relinearisation level
@@ -5053,88 +4898,105 @@ int cubic_collect(const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n, 
 	return GF2BV_OK;
 }
 
-int check_cubic_space(const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n_lin)
+// ---- the entries of both searches: each body once, over what a degree is --------------------------------------------------------
+// Plan: the plan type.  kMaxLin, kLinText, cols, kWordsText: the space check.  kPointWords: the words of an assignment a point is
+// read from, 0 for as many as cover r_eff bits.  width: the bits of a form over R variables.  build, point, search, collect: the plan
+// build, the point function, the device search and the collection of every consistent point.  times: the QuadTimes it writes
+struct QuadDegree {
+	using Plan = QuadPlan;
+	static constexpr i64 kMaxLin = 46340, kPointWords = 0;
+	static constexpr int kMaxEnum = kQuadMaxEnum;
+	static constexpr const char *kLinText = "n_lin must be 1..46340", *kWordsText = "words does not cover n_lin + n_lin(n_lin-1)/2 columns";
+	static i64 cols(i64 n) { return n + n * (n - 1) / 2; }
+	static i64 width(i64 R) { return 1 + R + R * (R - 1) / 2; }
+	static QuadTimes &times() { return g_quad_times; }
+	static constexpr auto build = quad_plan_build;
+	static bool point(const Plan &P, const u64 *y, u64 *x, u64 *c) { return quad_point(P, y, x, c); }
+	static constexpr auto search = quad_search_device;
+	static int collect(const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n, int max_enum, int device, hipStream_t st,
+	                   std::vector<u64> &pts, std::vector<u64> &coef, u64 *total, i64 *lin_rank, bool *gave_up)
+	{
+		return quad_collect(origin, basis, d, words, n, max_enum, device, st, 0, 0, pts, coef, total, lin_rank, gave_up);
+	}
+};
+struct CubicDegree {
+	using Plan = CubicPlan;
+	static constexpr i64 kMaxLin = 2000, kPointWords = 1;
+	static constexpr int kMaxEnum = kCubicMaxEnum;
+	static constexpr const char *kLinText = "n_lin must be 1..2000", *kWordsText = "words does not cover n_lin + C(n_lin,2) + C(n_lin,3) columns";
+	static i64 cols(i64 n) { return n + n * (n - 1) / 2 + n * (n - 1) * (n - 2) / 6; }
+	static i64 width(i64 R) { return cubic_width(R); }
+	static QuadTimes &times() { return g_cubic_times; }
+	static constexpr auto build = cubic_plan_build;
+	static bool point(const Plan &P, const u64 *y, u64 *x, u64 *c) { return cubic_point(P, y[0], x, c); }
+	static constexpr auto search = cubic_search_device;
+	static constexpr auto collect = cubic_collect;
+};
+static_assert(QuadDegree::kMaxEnum == 40 && CubicDegree::kMaxEnum == 40, "the entries' messages name 40");
+
+template <class D>
+int check_space(const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n_lin)
 {
 	if (!origin || (d > 0 && !basis)) return fail(GF2BV_ERR_ARG, "null pointer");
 	if (d < 0 || words <= 0) return fail(GF2BV_ERR_ARG, "dimension must be >= 0 and words > 0");
-	if (n_lin < 1 || n_lin > 2000) return fail(GF2BV_ERR_ARG, "n_lin must be 1..2000");
-	if (words < (n_lin + n_lin * (n_lin - 1) / 2 + n_lin * (n_lin - 1) * (n_lin - 2) / 6 + 63) / 64)
-		return fail(GF2BV_ERR_ARG, "words does not cover n_lin + C(n_lin,2) + C(n_lin,3) columns");
+	if (n_lin < 1 || n_lin > D::kMaxLin) return fail(GF2BV_ERR_ARG, D::kLinText);
+	if (words < (D::cols(n_lin) + 63) / 64) return fail(GF2BV_ERR_ARG, D::kWordsText);
 	return GF2BV_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int gf2bv_cubic_plan(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin,
-                     int64_t *r, int64_t *r_eff, int64_t *m, int64_t *form_words, uint64_t *forms_, int64_t forms_cap)
+// gf2bv_*_plan (device -1: the forms are built on the host) and gf2bv_*_plan_device
+template <class D>
+int search_plan(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin, bool on_device, int device,
+                int64_t *r, int64_t *r_eff, int64_t *m, int64_t *form_words, uint64_t *forms_, int64_t forms_cap)
 {
 	const u64 *origin = reinterpret_cast<const u64 *>(origin_), *basis = reinterpret_cast<const u64 *>(basis_);
-	return catching([&]() -> int {
-	int rc = check_cubic_space(origin, basis, dimension, words, n_lin);
+	int rc = check_space<D>(origin, basis, dimension, words, n_lin);
 	if (rc) return rc;
 	if (!r || !r_eff || !m || !form_words) return fail(GF2BV_ERR_ARG, "null pointer");
-	CubicPlan P;
-	rc = cubic_plan_build(P, origin, basis, dimension, words, n_lin, -1, nullptr);
-	if (rc) return rc;
-	quad_plan_export(P, r, r_eff, m, form_words, forms_, forms_cap);
-	return GF2BV_OK;
-	});
-}
-
-int gf2bv_cubic_plan_device(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin, int device,
-                            int64_t *r, int64_t *r_eff, int64_t *m, int64_t *form_words, uint64_t *forms_, int64_t forms_cap)
-{
-	const u64 *origin = reinterpret_cast<const u64 *>(origin_), *basis = reinterpret_cast<const u64 *>(basis_);
-	return guarded([&]() -> int {
-	int rc = check_cubic_space(origin, basis, dimension, words, n_lin);
-	if (rc) return rc;
-	if (!r || !r_eff || !m || !form_words) return fail(GF2BV_ERR_ARG, "null pointer");
-	rc = check_device(device);
-	if (rc) return rc;
 	hipStream_t st = nullptr;
-	HIPCHK(pool().stream(&st, device, 0));
-	std::unique_ptr<void, std::function<void(void *)>> keep(st, [&](void *) { pool().release_stream(st, device, 0); });
-	CubicPlan P;
-	rc = cubic_plan_build(P, origin, basis, dimension, words, n_lin, device, st);
+	std::unique_ptr<void, std::function<void(void *)>> keep(nullptr, [&](void *) { pool().release_stream(st, device, 0); });
+	if (on_device) {
+		if ((rc = check_device(device))) return rc;
+		HIPCHK(pool().stream(&st, device, 0));
+		keep.reset(st);
+	}
+	typename D::Plan P;
+	rc = D::build(P, origin, basis, dimension, words, n_lin, device, st);
 	if (rc) return rc;
 	quad_plan_export(P, r, r_eff, m, form_words, forms_, forms_cap);
 	return GF2BV_OK;
-	});
 }
 
-int gf2bv_cubic_points(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin,
-                       const uint64_t *ys_, int64_t nys, int64_t y_words, uint64_t *out_words_)
+template <class D>
+int search_points(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin, const uint64_t *ys_,
+                  int64_t nys, int64_t y_words, uint64_t *out_words_)
 {
 	const u64 *origin = reinterpret_cast<const u64 *>(origin_), *basis = reinterpret_cast<const u64 *>(basis_);
 	const u64 *ys = reinterpret_cast<const u64 *>(ys_);
 	u64 *out_words = reinterpret_cast<u64 *>(out_words_);
-	return catching([&]() -> int {
-	int rc = check_cubic_space(origin, basis, dimension, words, n_lin);
+	int rc = check_space<D>(origin, basis, dimension, words, n_lin);
 	if (rc) return rc;
 	if (nys < 0 || (nys > 0 && (!ys || !out_words))) return fail(GF2BV_ERR_ARG, "null pointer");
-	if (y_words < 1) return fail(GF2BV_ERR_ARG, "y_words does not cover r_eff bits");
-	CubicPlan P;
-	rc = cubic_plan_build(P, origin, basis, dimension, words, n_lin, -1, nullptr);
+	if (D::kPointWords && y_words < D::kPointWords) return fail(GF2BV_ERR_ARG, "y_words does not cover r_eff bits");
+	typename D::Plan P;
+	rc = D::build(P, origin, basis, dimension, words, n_lin, -1, nullptr);
 	if (rc) return rc;
 	if (P.reff < 0 || P.inconsistent) return fail(GF2BV_ERR_ARG, "the space has no forms to map from");
+	if (!D::kPointWords && y_words < std::max<i64>(1, (P.reff + 63) / 64)) return fail(GF2BV_ERR_ARG, "y_words does not cover r_eff bits");
 	std::vector<u64> c((size_t)P.dw);
 	for (i64 k = 0; k < nys; k++)
-		if (!cubic_point(P, ys[k * y_words], out_words + k * words, c.data()))
+		if (!D::point(P, ys + k * y_words, out_words + k * words, c.data()))
 			return fail(GF2BV_ERR_ARG, "an assignment that is not a common zero of the forms");
 	return GF2BV_OK;
-	});
 }
 
-int gf2bv_cubic_forms_search(const uint64_t *forms_, int64_t m, int64_t r_eff, int device, int64_t max_out, int64_t *count,
-                             uint64_t *out_)
+template <class D>
+int search_forms(const uint64_t *forms_, int64_t m, int64_t r_eff, int device, int64_t max_out, int64_t *count, uint64_t *out_)
 {
 	const u64 *forms = reinterpret_cast<const u64 *>(forms_);
 	u64 *out = reinterpret_cast<u64 *>(out_);
-	return guarded([&]() -> int {
 	if (!count || (m > 0 && !forms) || (max_out > 0 && !out) || m < 0 || max_out < 0) return fail(GF2BV_ERR_ARG, "null pointer");
-	if (r_eff < 0 || r_eff > kCubicMaxEnum) return fail(GF2BV_ERR_ARG, "r_eff must be 0..40");
+	if (r_eff < 0 || r_eff > D::kMaxEnum) return fail(GF2BV_ERR_ARG, "r_eff must be 0..40");
 	*count = 0;
 	int rc = check_device(device);
 	if (rc) return rc;
@@ -5143,53 +5005,128 @@ int gf2bv_cubic_forms_search(const uint64_t *forms_, int64_t m, int64_t r_eff, i
 	std::unique_ptr<void, std::function<void(void *)>> keep(st, [&](void *) { pool().release_stream(st, device, 0); });
 	std::vector<u64> ys;
 	u64 total = 0;
-	rc = cubic_search_device(forms, m, (cubic_width(r_eff) + 63) / 64, (int)r_eff, device, st, ys, &total);
+	rc = D::search(forms, m, (D::width(r_eff) + 63) / 64, (int)r_eff, device, st, ys, &total);
 	if (rc) return rc;
 	*count = (int64_t)total;
 	if ((i64)total > kQuadMaxPoints && max_out > 0) return fail(GF2BV_ERR_NOMEM, "more common zeros than can be collected");
 	std::sort(ys.begin(), ys.end());
 	std::copy(ys.begin(), ys.begin() + std::min<i64>((i64)ys.size(), max_out), out);
 	return GF2BV_OK;
+}
+
+template <class D>
+int search_space_alloc(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin, int max_enum,
+                       int64_t max_solutions, int device, int64_t *count, int64_t *lin_rank, uint64_t **out_words)
+{
+	const u64 *origin = reinterpret_cast<const u64 *>(origin_), *basis = reinterpret_cast<const u64 *>(basis_);
+	int rc = check_space<D>(origin, basis, dimension, words, n_lin);
+	if (rc) return rc;
+	if (!count || !lin_rank || !out_words) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (max_enum < 0 || max_enum > D::kMaxEnum) return fail(GF2BV_ERR_ARG, "max_enum must be 0..40");
+	if (max_solutions < 0) return fail(GF2BV_ERR_ARG, "max_solutions must be >= 0");
+	return search_alloc(D::times(), dimension, words, max_solutions, device, count, lin_rank, out_words,
+	                    [&](hipStream_t st, std::vector<u64> &pts, std::vector<u64> &coef, u64 *total, bool *gave_up) {
+		return D::collect(origin, basis, dimension, words, n_lin, max_enum, device, st, pts, coef, total, reinterpret_cast<i64 *>(lin_rank),
+		                  gave_up);
 	});
 }
 
-int gf2bv_cubic_search(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin,
-                       int max_enum, int64_t max_solutions, int device, int64_t *count, int64_t *lin_rank, uint64_t *out_words_)
+// gf2bv_*_search: the points of `alloc` (gf2bv_*_search_alloc) copied into the caller's buffer
+template <class Alloc>
+int search_space_copy(Alloc alloc, int64_t words, int64_t max_solutions, int64_t *count, uint64_t *out_words_)
 {
 	if (max_solutions > 0 && !out_words_) return fail(GF2BV_ERR_ARG, "null pointer");
 	uint64_t *pts = nullptr;
-	const int rc = gf2bv_cubic_search_alloc(origin_, basis_, dimension, words, n_lin, max_enum, max_solutions, device, count, lin_rank,
-	                                        &pts);
+	const int rc = alloc(&pts);
 	if (rc == GF2BV_OK && pts) memcpy(out_words_, pts, sizeof(uint64_t) * (size_t)(std::min<int64_t>(*count, max_solutions) * words));
 	gf2bv_quad_free(pts);
 	return rc;
 }
 
-int gf2bv_cubic_search_alloc(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin,
-                             int max_enum, int64_t max_solutions, int device, int64_t *count, int64_t *lin_rank, uint64_t **out_words)
-{
-	const u64 *origin = reinterpret_cast<const u64 *>(origin_), *basis = reinterpret_cast<const u64 *>(basis_);
-	return guarded([&]() -> int {
-	int rc = check_cubic_space(origin, basis, dimension, words, n_lin);
-	if (rc) return rc;
-	if (!count || !lin_rank || !out_words) return fail(GF2BV_ERR_ARG, "null pointer");
-	if (max_enum < 0 || max_enum > kCubicMaxEnum) return fail(GF2BV_ERR_ARG, "max_enum must be 0..40");
-	if (max_solutions < 0) return fail(GF2BV_ERR_ARG, "max_solutions must be >= 0");
-	return search_alloc(g_cubic_times, dimension, words, max_solutions, device, count, lin_rank, out_words,
-	                    [&](hipStream_t st, std::vector<u64> &pts, std::vector<u64> &coef, u64 *total, bool *gave_up) {
-		return cubic_collect(origin, basis, dimension, words, n_lin, max_enum, device, st, pts, coef, total,
-		                     reinterpret_cast<i64 *>(lin_rank), gave_up);
-	});
-	});
-}
-
-void gf2bv_cubic_last_times(double *out8)
+void search_last_times(const QuadTimes &t, double *out8)
 {
 	if (!out8) return;
-	const QuadTimes &t = g_cubic_times;
 	const double v[8] = {t.reduce, t.forms, t.affine, t.search, t.relin, t.total, (double)t.levels, (double)t.candidates};
 	std::copy(v, v + 8, out8);
 }
+
+}  // namespace
+
+extern "C" {
+
+int gf2bv_quad_plan(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin,
+                    int64_t *r, int64_t *r_eff, int64_t *m, int64_t *form_words, uint64_t *forms_, int64_t forms_cap)
+{
+	return catching([&] { return search_plan<QuadDegree>(origin_, basis_, dimension, words, n_lin, false, -1, r, r_eff, m, form_words, forms_, forms_cap); });
+}
+int gf2bv_quad_plan_device(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin, int device,
+                           int64_t *r, int64_t *r_eff, int64_t *m, int64_t *form_words, uint64_t *forms_, int64_t forms_cap)
+{
+	return guarded([&] { return search_plan<QuadDegree>(origin_, basis_, dimension, words, n_lin, true, device, r, r_eff, m, form_words, forms_, forms_cap); });
+}
+int gf2bv_quad_points(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin,
+                      const uint64_t *ys_, int64_t nys, int64_t y_words, uint64_t *out_words_)
+{
+	return catching([&] { return search_points<QuadDegree>(origin_, basis_, dimension, words, n_lin, ys_, nys, y_words, out_words_); });
+}
+int gf2bv_quad_forms_search(const uint64_t *forms_, int64_t m, int64_t r_eff, int device, int64_t max_out, int64_t *count,
+                            uint64_t *out_)
+{
+	return guarded([&] { return search_forms<QuadDegree>(forms_, m, r_eff, device, max_out, count, out_); });
+}
+int gf2bv_quad_search(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin,
+                      int max_enum, int64_t max_solutions, int device, int64_t *count, int64_t *lin_rank, uint64_t *out_words_)
+{
+	return search_space_copy([&](uint64_t **pts) {
+		return gf2bv_quad_search_alloc(origin_, basis_, dimension, words, n_lin, max_enum, max_solutions, device, count, lin_rank, pts);
+	}, words, max_solutions, count, out_words_);
+}
+int gf2bv_quad_search_alloc(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin,
+                            int max_enum, int64_t max_solutions, int device, int64_t *count, int64_t *lin_rank, uint64_t **out_words)
+{
+	return guarded([&] {
+		return search_space_alloc<QuadDegree>(origin_, basis_, dimension, words, n_lin, max_enum, max_solutions, device, count, lin_rank, out_words);
+	});
+}
+void gf2bv_quad_last_times(double *out8) { search_last_times(QuadDegree::times(), out8); }
+
+int gf2bv_cubic_plan(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin,
+                    int64_t *r, int64_t *r_eff, int64_t *m, int64_t *form_words, uint64_t *forms_, int64_t forms_cap)
+{
+	return catching([&] { return search_plan<CubicDegree>(origin_, basis_, dimension, words, n_lin, false, -1, r, r_eff, m, form_words, forms_, forms_cap); });
+}
+int gf2bv_cubic_plan_device(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin, int device,
+                           int64_t *r, int64_t *r_eff, int64_t *m, int64_t *form_words, uint64_t *forms_, int64_t forms_cap)
+{
+	return guarded([&] { return search_plan<CubicDegree>(origin_, basis_, dimension, words, n_lin, true, device, r, r_eff, m, form_words, forms_, forms_cap); });
+}
+int gf2bv_cubic_points(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin,
+                      const uint64_t *ys_, int64_t nys, int64_t y_words, uint64_t *out_words_)
+{
+	return catching([&] { return search_points<CubicDegree>(origin_, basis_, dimension, words, n_lin, ys_, nys, y_words, out_words_); });
+}
+int gf2bv_cubic_forms_search(const uint64_t *forms_, int64_t m, int64_t r_eff, int device, int64_t max_out, int64_t *count,
+                            uint64_t *out_)
+{
+	return guarded([&] { return search_forms<CubicDegree>(forms_, m, r_eff, device, max_out, count, out_); });
+}
+int gf2bv_cubic_search(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin,
+                      int max_enum, int64_t max_solutions, int device, int64_t *count, int64_t *lin_rank, uint64_t *out_words_)
+{
+	return search_space_copy([&](uint64_t **pts) {
+		return gf2bv_cubic_search_alloc(origin_, basis_, dimension, words, n_lin, max_enum, max_solutions, device, count, lin_rank, pts);
+	}, words, max_solutions, count, out_words_);
+}
+int gf2bv_cubic_search_alloc(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin,
+                            int max_enum, int64_t max_solutions, int device, int64_t *count, int64_t *lin_rank, uint64_t **out_words)
+{
+	return guarded([&] {
+		return search_space_alloc<CubicDegree>(origin_, basis_, dimension, words, n_lin, max_enum, max_solutions, device, count, lin_rank, out_words);
+	});
+}
+void gf2bv_cubic_last_times(double *out8) { search_last_times(CubicDegree::times(), out8); }
+
+void gf2bv_quad_free(uint64_t *words) { free(words); }
 
 }  // extern "C"
 
@@ -5205,103 +5142,96 @@ constexpr i64 kQuarticLdsBytes = 160 * 1024 - 256;     // ... but k_quartic_expa
 // the workgroup of every expansion kernel: a thread per two words of an output row
 unsigned expand_block(i64 stride) { return (unsigned)std::min<i64>(256, round_up(std::max<i64>(stride / 2, 1), 64)); }
 
-// The factored form, in host or in device memory.  degree 2: the products follow QuadraticSystem._mul_bit, over n + C(n,2) columns,
-// and off3, ua, ub, uc are unused; degree 3: products of two and of three affine forms, exact in GF(2)[x] / (x_i^2 + x_i), over the
-// n + C(n,2) + C(n,3) columns of degree-3 XL; degree 4: and of four (off4, va .. vd), over degree-4 XL's columns
+// The factored form, in host or in device memory: a linear form a row plus, per group, products of `arity` forms -- rows off[r] ..
+// off[r + 1] of each of the group's operand arrays.  One group (degree 2): the products follow QuadraticSystem._mul_bit, over
+// n + C(n,2) columns; two and three groups (degree 3, 4): affine forms and products exact in GF(2)[x] / (x_i^2 + x_i), over the
+// columns of degree-3 and of degree-4 XL
+struct TermGroup {
+	int arity;                         // 2, 3, 4 in this order
+	const i64 *off;                    // rows_live + 1
+	const u64 *ops[4];                 // the first `arity`
+	bool lacks_operand() const { return std::any_of(ops, ops + arity, [](const u64 *p) { return !p; }); }
+};
 struct Terms {
-	int degree;
 	const u64 *lin;                    // rows_live x wl
-	const i64 *off2;                   // rows_live + 1
-	const u64 *ta, *tb;
-	const i64 *off3;                   // rows_live + 1
-	const u64 *ua, *ub, *uc;
-	const i64 *off4 = nullptr;         // rows_live + 1
-	const u64 *va = nullptr, *vb = nullptr, *vc = nullptr, *vd = nullptr;
 	i64 rows_live, rows, n;
-	Terms(const void *lin, const void *off2, const void *ta, const void *tb, i64 rows_live, i64 rows, i64 n_lin, const void *off3 = nullptr,
-	      const void *ua = nullptr, const void *ub = nullptr, const void *uc = nullptr, int degree = 2)
-		: degree(degree), lin((const u64 *)lin), off2((const i64 *)off2), ta((const u64 *)ta), tb((const u64 *)tb), off3((const i64 *)off3),
-		  ua((const u64 *)ua), ub((const u64 *)ub), uc((const u64 *)uc), rows_live(rows_live), rows(rows), n(n_lin) {}
-	Terms &quartic(const void *o4, const void *a, const void *b, const void *c, const void *d)
+	int ngroups = 0;
+	TermGroup group[3] = {};
+	// every group as { off, operand, operand, ... }, in the order of the exported entries' argument lists
+	Terms(const void *lin, i64 rows_live, i64 rows, i64 n_lin, std::initializer_list<std::initializer_list<const void *>> groups)
+		: lin((const u64 *)lin), rows_live(rows_live), rows(rows), n(n_lin)
 	{
-		degree = 4, off4 = (const i64 *)o4, va = (const u64 *)a, vb = (const u64 *)b, vc = (const u64 *)c, vd = (const u64 *)d;
-		return *this;
+		for (const auto &g : groups) {
+			TermGroup &t = group[ngroups];
+			t.arity = 2 + ngroups++;
+			t.off = (const i64 *)*g.begin();
+			std::transform(g.begin() + 1, g.end(), t.ops, [](const void *p) { return (const u64 *)p; });
+		}
 	}
+	int degree() const { return ngroups + 1; }
 	i64 wl() const { return (n + 1 + 63) / 64; }
 	i64 cols3() const { return n + n * (n - 1) / 2 + n * (n - 1) * (n - 2) / 6; }
 	i64 cols() const
 	{
-		if (degree == 4) return n > 1024 ? (1ll << 40) : cols3() + n * (n - 1) * (n - 2) / 6 * (n - 3) / 4;      // (C(1025,4) is far above any row)
-		return degree == 3 ? cols3() : n + n * (n - 1) / 2;
+		if (ngroups == 3) return n > 1024 ? (1ll << 40) : cols3() + n * (n - 1) * (n - 2) / 6 * (n - 3) / 4;      // (C(1025,4) is far above any row)
+		return ngroups == 2 ? cols3() : n + n * (n - 1) / 2;
 	}
 	i64 wt() const { return (cols() + 1 + 63) / 64; }
 };
 
-// What k_quad_expand and its batched form are launched with: `tch` products of a row in LDS at a time
-struct QuadLaunch { int tch; unsigned block; size_t lds; };
-QuadLaunch quad_launch(const Terms &q, i64 stride)
+// What the expansion kernel of a degree is launched with: tch[g] terms of group g of a row in LDS at a time
+struct ExpandLaunch { int tch[3]; unsigned block; size_t lds; };
+ExpandLaunch expand_launch(int degree, i64 n, i64 stride)
 {
-	const i64 wl = q.wl();
-	const int tch = (int)std::max<i64>(1, std::min<i64>(8, (kExpandLdsBytes / 8 / wl - 1) / 2));
-	return { tch, expand_block(stride), sizeof(u64) * (size_t)((1 + 2 * tch) * wl) };
-}
-
-// What k_cubic_expand is launched with: `tch2` quadratic and `tch3` cubic terms of a row in LDS at a time (the cubic operands served
-// first where a form is long)
-struct CubicLaunch { int tch2, tch3; unsigned block; size_t lds; };
-CubicLaunch cubic_launch(i64 n, i64 stride)
-{
-	const i64 wl = (n + 1 + 63) / 64, avail = kExpandLdsBytes / 8 / wl - 1;      // operands beside the linear part
-	const int tch3 = (int)std::max<i64>(1, std::min<i64>(8, avail / 5));
-	const int tch2 = (int)std::max<i64>(1, std::min<i64>(8, (avail - 3 * tch3) / 2));
-	return { tch2, tch3, expand_block(stride), sizeof(u64) * (size_t)((1 + 2 * tch2 + 3 * tch3) * wl) };
-}
-
-// What k_quartic_expand is launched with: `tch2` / `tch3` / `tch4` terms of a row in LDS at a time beside the linear part and the
-// 1 + tch4 staged cubic rows of w3 words.  The staged rows come first: with every chunk at 1 a pass needs 10 wl + 2 w3 words, which
-// is what bounds n_lin (about 157); lds above kQuarticLdsBytes: this n_lin does not fit
-struct QuarticLaunch { int tch2, tch3, tch4; unsigned block; size_t lds; };
-QuarticLaunch quartic_launch(i64 n, i64 stride)
-{
-	const i64 wl = (n + 1 + 63) / 64, w3 = n > 1024 ? (1ll << 30) : (n + n * (n - 1) / 2 + n * (n - 1) * (n - 2) / 6 + 1 + 63) / 64;
+	const i64 wl = (n + 1 + 63) / 64;
+	auto chunk = [](i64 most, i64 fit) { return (int)std::max<i64>(1, std::min(most, fit)); };
+	if (degree == 2) {                 // k_quad_expand and its batched form
+		const int tch = chunk(8, (kExpandLdsBytes / 8 / wl - 1) / 2);
+		return { { tch, 0, 0 }, expand_block(stride), sizeof(u64) * (size_t)((1 + 2 * tch) * wl) };
+	}
+	if (degree == 3) {                 // k_cubic_expand: the cubic operands served first where a form is long
+		const i64 avail = kExpandLdsBytes / 8 / wl - 1;            // operands beside the linear part
+		const int tch3 = chunk(8, avail / 5), tch2 = chunk(8, (avail - 3 * tch3) / 2);
+		return { { tch2, tch3, 0 }, expand_block(stride), sizeof(u64) * (size_t)((1 + 2 * tch2 + 3 * tch3) * wl) };
+	}
+	// k_quartic_expand: beside the linear part and the terms, 1 + tch4 staged cubic rows of w3 words.  The staged rows come first:
+	// with every chunk at 1 a pass needs 10 wl + 2 w3 words, which is what bounds n_lin (about 157); lds above kQuarticLdsBytes:
+	// this n_lin does not fit
+	const i64 w3 = n > 1024 ? (1ll << 30) : (n + n * (n - 1) / 2 + n * (n - 1) * (n - 2) / 6 + 1 + 63) / 64;
 	i64 rest = kQuarticLdsBytes / 8 - wl - w3;
-	const int tch4 = (int)std::max<i64>(1, std::min<i64>(4, rest / 3 / (4 * wl + w3)));
+	const int tch4 = chunk(4, rest / 3 / (4 * wl + w3));
 	rest -= tch4 * (4 * wl + w3);
-	const int tch3 = (int)std::max<i64>(1, std::min<i64>(8, rest / 2 / (3 * wl)));
+	const int tch3 = chunk(8, rest / 2 / (3 * wl));
 	rest -= tch3 * 3 * wl;
-	const int tch2 = (int)std::max<i64>(1, std::min<i64>(8, rest / (2 * wl)));
-	return { tch2, tch3, tch4, expand_block(stride), sizeof(u64) * (size_t)((1 + 2 * tch2 + 3 * tch3 + 4 * tch4) * wl + (1 + tch4) * w3) };
+	const int tch2 = chunk(8, rest / (2 * wl));
+	return { { tch2, tch3, tch4 }, expand_block(stride), sizeof(u64) * (size_t)((1 + 2 * tch2 + 3 * tch3 + 4 * tch4) * wl + (1 + tch4) * w3) };
 }
 
 // The shape of a factored system; `host`: the offsets can be read (each array starts at 0 and never decreases; operands wherever
 // they say there are terms)
 int check_terms(const Terms &t, bool host)
 {
-	const bool cubic = t.degree >= 3, quartic = t.degree == 4;
+	static const char *const kColsText[3] = { "n_lin must be at least 1 and n_lin + n_lin(n_lin-1)/2 below 2^31 - 64",
+	                                          "n_lin must be at least 1 and n_lin + C(n_lin,2) + C(n_lin,3) below 2^31 - 64",
+	                                          "n_lin must be at least 1 and n_lin + C(n_lin,2) + C(n_lin,3) + C(n_lin,4) below 2^31 - 64" };
+	auto any_group = [&](auto &&pred) { return std::any_of(t.group, t.group + t.ngroups, pred); };
 	if (!t.lin && t.rows_live > 0) return fail(GF2BV_ERR_ARG, "null pointer");
-	if (!t.off2 || (cubic && !t.off3) || (quartic && !t.off4)) return fail(GF2BV_ERR_ARG, "null pointer");
-	if (t.n < 1 || t.n > 65535 || t.cols() >= (1ll << 31) - 64)
-		return fail(GF2BV_ERR_ARG, quartic ? "n_lin must be at least 1 and n_lin + C(n_lin,2) + C(n_lin,3) + C(n_lin,4) below 2^31 - 64"
-		                           : cubic ? "n_lin must be at least 1 and n_lin + C(n_lin,2) + C(n_lin,3) below 2^31 - 64"
-		                                   : "n_lin must be at least 1 and n_lin + n_lin(n_lin-1)/2 below 2^31 - 64");
+	if (any_group([](const TermGroup &g) { return !g.off; })) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (t.n < 1 || t.n > 65535 || t.cols() >= (1ll << 31) - 64) return fail(GF2BV_ERR_ARG, kColsText[t.ngroups - 1]);
 	if (t.rows < 0 || t.rows >= (1ll << 31) - 64 || t.rows_live < 0 || t.rows_live > t.rows)
 		return fail(GF2BV_ERR_ARG, "rows_live must be 0..rows");
-	if (quartic && (i64)quartic_launch(t.n, 2).lds > kQuarticLdsBytes)
+	if (t.degree() == 4 && (i64)expand_launch(4, t.n, 2).lds > kQuarticLdsBytes)
 		return fail(GF2BV_ERR_ARG, "the operands and the staged cubic rows of this n_lin do not fit the expansion kernel's LDS (160 KiB)");
-	if (t.degree == 3 && (i64)cubic_launch(t.n, 2).lds > kExpandLdsBytes)
+	if (t.degree() == 3 && (i64)expand_launch(3, t.n, 2).lds > kExpandLdsBytes)
 		return fail(GF2BV_ERR_ARG, "the operands of this n_lin do not fit the expansion kernel's LDS (64 KiB)");
 	if (!host) {
-		if (!t.lin || !t.ta || !t.tb || (cubic && (!t.ua || !t.ub || !t.uc)) || (quartic && (!t.va || !t.vb || !t.vc || !t.vd)))
-			return fail(GF2BV_ERR_ARG, "null pointer");
+		if (!t.lin || any_group([](const TermGroup &g) { return g.lacks_operand(); })) return fail(GF2BV_ERR_ARG, "null pointer");
 		return GF2BV_OK;
 	}
-	if (t.off2[0] != 0 || (cubic && t.off3[0] != 0) || (quartic && t.off4[0] != 0)) return fail(GF2BV_ERR_ARG, "term offsets must start at 0");
+	if (any_group([](const TermGroup &g) { return g.off[0] != 0; })) return fail(GF2BV_ERR_ARG, "term offsets must start at 0");
 	for (i64 r = 0; r < t.rows_live; r++)
-		if (t.off2[r + 1] < t.off2[r] || (cubic && t.off3[r + 1] < t.off3[r]) || (quartic && t.off4[r + 1] < t.off4[r]))
-			return fail(GF2BV_ERR_ARG, "term offsets must not decrease");
-	if ((!t.ta || !t.tb) && t.off2[t.rows_live] > 0) return fail(GF2BV_ERR_ARG, "null pointer");
-	if (cubic && (!t.ua || !t.ub || !t.uc) && t.off3[t.rows_live] > 0) return fail(GF2BV_ERR_ARG, "null pointer");
-	if (quartic && (!t.va || !t.vb || !t.vc || !t.vd) && t.off4[t.rows_live] > 0) return fail(GF2BV_ERR_ARG, "null pointer");
+		if (any_group([r](const TermGroup &g) { return g.off[r + 1] < g.off[r]; })) return fail(GF2BV_ERR_ARG, "term offsets must not decrease");
+	if (any_group([&](const TermGroup &g) { return g.lacks_operand() && g.off[t.rows_live] > 0; })) return fail(GF2BV_ERR_ARG, "null pointer");
 	return GF2BV_OK;
 }
 
@@ -5309,10 +5239,11 @@ int check_terms(const Terms &t, bool host)
 int enqueue_quad_expand(const Terms &q, u64 *d_aug, i64 stride, hipStream_t st)
 {
 	if (q.rows == 0) return GF2BV_OK;
-	const QuadLaunch l = quad_launch(q, stride);
+	const ExpandLaunch l = expand_launch(2, q.n, stride);
+	const TermGroup &g = q.group[0];
 	const unsigned grid = (unsigned)std::min<i64>(q.rows, 256 * 8);
-	hipLaunchKernelGGL(k_quad_expand, dim3(grid), dim3(l.block), l.lds, st, q.lin, q.off2, q.ta, q.tb, q.rows_live, q.rows, (int)q.n,
-	                   (int)q.wl(), l.tch, d_aug, stride);
+	hipLaunchKernelGGL(k_quad_expand, dim3(grid), dim3(l.block), l.lds, st, q.lin, g.off, g.ops[0], g.ops[1], q.rows_live, q.rows, (int)q.n,
+	                   (int)q.wl(), l.tch[0], d_aug, stride);
 	HIPCHK(hipGetLastError());
 	return GF2BV_OK;
 }
@@ -5340,13 +5271,14 @@ int check_quad_batch(Terms &q, const i64 *sys_off, i64 nsys)
 int enqueue_quad_expand_batch(const Terms &q, const i64 *d_sys_off, i64 nsys, u64 *d_aug, i64 stride, i64 sys_stride, hipStream_t st)
 {
 	if (q.rows == 0 || nsys == 0) return GF2BV_OK;
-	const QuadLaunch l = quad_launch(q, stride);
+	const ExpandLaunch l = expand_launch(2, q.n, stride);
+	const TermGroup &g = q.group[0];
 	// a workgroup per row at a time; a few thousand workgroups in all, however many systems share the launch
 	const unsigned gx = (unsigned)std::min<i64>(q.rows, std::max<i64>(256, 256 * 8 / nsys));
 	for (i64 s0 = 0; s0 < nsys; s0 += 65535) {      // (grid y holds 65535 systems)
 		const unsigned ns = (unsigned)std::min<i64>(65535, nsys - s0);
-		hipLaunchKernelGGL(k_quad_expand_batch, dim3(gx, ns), dim3(l.block), l.lds, st, q.lin, q.off2, q.ta, q.tb, d_sys_off + s0, q.rows,
-		                   (int)q.n, (int)q.wl(), l.tch, d_aug + s0 * sys_stride, stride, sys_stride);
+		hipLaunchKernelGGL(k_quad_expand_batch, dim3(gx, ns), dim3(l.block), l.lds, st, q.lin, g.off, g.ops[0], g.ops[1], d_sys_off + s0, q.rows,
+		                   (int)q.n, (int)q.wl(), l.tch[0], d_aug + s0 * sys_stride, stride, sys_stride);
 	}
 	HIPCHK(hipGetLastError());
 	return GF2BV_OK;
@@ -5356,10 +5288,11 @@ int enqueue_quad_expand_batch(const Terms &q, const i64 *d_sys_off, i64 nsys, u6
 int enqueue_cubic_expand(const Terms &c, u64 *d_aug, i64 stride, hipStream_t st)
 {
 	if (c.rows == 0) return GF2BV_OK;
-	const CubicLaunch l = cubic_launch(c.n, stride);
+	const ExpandLaunch l = expand_launch(3, c.n, stride);
+	const TermGroup &q = c.group[0], &u = c.group[1];
 	const unsigned grid = (unsigned)std::min<i64>(c.rows, 256 * 16);
-	hipLaunchKernelGGL(k_cubic_expand, dim3(grid), dim3(l.block), l.lds, st, c.lin, c.off2, c.ta, c.tb, c.off3, c.ua, c.ub, c.uc, c.rows_live,
-	                   c.rows, (int)c.n, (int)c.wl(), l.tch2, l.tch3, d_aug, stride);
+	hipLaunchKernelGGL(k_cubic_expand, dim3(grid), dim3(l.block), l.lds, st, c.lin, q.off, q.ops[0], q.ops[1], u.off, u.ops[0], u.ops[1], u.ops[2],
+	                   c.rows_live, c.rows, (int)c.n, (int)c.wl(), l.tch[0], l.tch[1], d_aug, stride);
 	HIPCHK(hipGetLastError());
 	return GF2BV_OK;
 }
@@ -5368,7 +5301,8 @@ int enqueue_cubic_expand(const Terms &c, u64 *d_aug, i64 stride, hipStream_t st)
 int enqueue_quartic_expand(const Terms &c, u64 *d_aug, i64 stride, hipStream_t st)
 {
 	if (c.rows == 0) return GF2BV_OK;
-	const QuarticLaunch l = quartic_launch(c.n, stride);
+	const ExpandLaunch l = expand_launch(4, c.n, stride);
+	const TermGroup &q = c.group[0], &u = c.group[1], &v = c.group[2];
 	if ((i64)l.lds > kExpandLdsBytes) {                // (a function attribute holds per device: raised once on each that needs it)
 		static std::mutex mu;
 		static std::map<int, bool> raised;
@@ -5381,9 +5315,9 @@ int enqueue_quartic_expand(const Terms &c, u64 *d_aug, i64 stride, hipStream_t s
 		}
 	}
 	const unsigned grid = (unsigned)std::min<i64>(c.rows, 256 * 16);
-	hipLaunchKernelGGL(k_quartic_expand, dim3(grid), dim3(l.block), l.lds, st, c.lin, c.off2, c.ta, c.tb, c.off3, c.ua, c.ub, c.uc, c.off4, c.va,
-	                   c.vb, c.vc, c.vd, c.rows_live, c.rows, (int)c.n, (int)c.wl(), (int)((c.cols3() + 1 + 63) / 64), l.tch2, l.tch3, l.tch4, d_aug,
-	                   stride);
+	hipLaunchKernelGGL(k_quartic_expand, dim3(grid), dim3(l.block), l.lds, st, c.lin, q.off, q.ops[0], q.ops[1], u.off, u.ops[0], u.ops[1], u.ops[2],
+	                   v.off, v.ops[0], v.ops[1], v.ops[2], v.ops[3], c.rows_live, c.rows, (int)c.n, (int)c.wl(), (int)((c.cols3() + 1 + 63) / 64),
+	                   l.tch[0], l.tch[1], l.tch[2], d_aug, stride);
 	HIPCHK(hipGetLastError());
 	return GF2BV_OK;
 }
@@ -5391,8 +5325,8 @@ int enqueue_quartic_expand(const Terms &c, u64 *d_aug, i64 stride, hipStream_t s
 // (device pointers, already checked) the kernel of the terms' degree on `st`
 int enqueue_expand(const Terms &t, u64 *d_aug, i64 stride, hipStream_t st)
 {
-	if (t.degree == 4) return enqueue_quartic_expand(t, d_aug, stride, st);
-	return t.degree == 3 ? enqueue_cubic_expand(t, d_aug, stride, st) : enqueue_quad_expand(t, d_aug, stride, st);
+	if (t.degree() == 4) return enqueue_quartic_expand(t, d_aug, stride, st);
+	return t.degree() == 3 ? enqueue_cubic_expand(t, d_aug, stride, st) : enqueue_quad_expand(t, d_aug, stride, st);
 }
 
 // XL (k_xl3_expand, k_xl4_expand): m quadratic rows over n unknowns -- the rows k_quad_expand writes -- become `rows` rows over the
@@ -5621,25 +5555,22 @@ struct QuadStage {
 		if (bytes) HIPCHK(hipMemcpyAsync(*d, h, bytes, hipMemcpyHostToDevice, ps.st));
 		return GF2BV_OK;
 	}
-	// Upload of the term groups and expansion (t.degree's kernel), with rows `stride` words apart rounded up to an even `ds`; sys_off:
+	// Upload of the term groups and expansion (the kernel of t.degree()), with rows `stride` words apart rounded up to an even `ds`; sys_off:
 	// the batched form, nsys systems (t as check_quad_batch left it); rhs: right-hand sides that go up into d_rhs in front of the expansion
 	int expand(Terms t, i64 stride, const i64 *sys_off = nullptr, i64 nsys = 1, const u64 *rhs = nullptr, size_t rhs_bytes = 0)
 	{
-		if (sys_off && t.degree != 2) return fail(GF2BV_ERR_ARG, "the batched expansion takes quadratic terms");
+		if (sys_off && t.degree() != 2) return fail(GF2BV_ERR_ARG, "the batched expansion takes quadratic terms");
 		if (int rc = open()) return rc;
 		const i64 wl = t.wl();
 		i64 *d_sys = nullptr;
 		int rc = upload((u64 **)&t.lin, t.lin, sizeof(u64) * (size_t)(t.rows_live * wl));
 		// a group's offsets, then its operands: each host pointer of `t` becomes the device copy
-		auto group = [&](const i64 *&off, std::initializer_list<const u64 **> ops) {
-			const size_t bytes = sizeof(u64) * (size_t)(off[t.rows_live] * wl);
-			if (!rc) rc = upload((i64 **)&off, off, sizeof(i64) * (size_t)(t.rows_live + 1));
-			for (const u64 **op : ops)
-				if (!rc) rc = upload((u64 **)op, *op, bytes);
-		};
-		group(t.off2, { &t.ta, &t.tb });
-		if (t.degree >= 3) group(t.off3, { &t.ua, &t.ub, &t.uc });
-		if (t.degree == 4) group(t.off4, { &t.va, &t.vb, &t.vc, &t.vd });
+		for (TermGroup *g = t.group; g < t.group + t.ngroups; g++) {
+			const size_t bytes = sizeof(u64) * (size_t)(g->off[t.rows_live] * wl);
+			if (!rc) rc = upload((i64 **)&g->off, g->off, sizeof(i64) * (size_t)(t.rows_live + 1));
+			for (int k = 0; k < g->arity; k++)
+				if (!rc) rc = upload((u64 **)&g->ops[k], g->ops[k], bytes);
+		}
 		if (!rc && sys_off) rc = upload(&d_sys, sys_off, sizeof(i64) * (size_t)(nsys + 1));
 		ds = round_up(stride, 2);
 		if (!rc) rc = alloc((void **)&d_aug, sizeof(u64) * (size_t)(nsys * t.rows * ds));
@@ -5769,35 +5700,35 @@ static int solve_terms(const Terms &t, int mode, int device, gf2bv_result **out,
 int gf2bv_quad_expand_device(const void *d_lin, const void *d_term_off, const void *d_ta, const void *d_tb, int64_t rows_live,
                              int64_t rows, int64_t n_lin, void *d_aug, int64_t stride_words, int device, void *stream)
 {
-	return terms_expand_device(Terms(d_lin, d_term_off, d_ta, d_tb, rows_live, rows, n_lin), d_aug, stride_words, device, stream);
+	return terms_expand_device(Terms(d_lin, rows_live, rows, n_lin, { { d_term_off, d_ta, d_tb } }), d_aug, stride_words, device, stream);
 }
 int gf2bv_quad_expand_words(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t rows_live,
                             int64_t rows, int64_t n_lin, uint64_t *out_aug, int64_t stride_words, int device)
 {
-	return terms_expand_words(Terms(lin, term_off, ta, tb, rows_live, rows, n_lin), out_aug, stride_words, device, false);
+	return terms_expand_words(Terms(lin, rows_live, rows, n_lin, { { term_off, ta, tb } }), out_aug, stride_words, device, false);
 }
 int gf2bv_solve_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t rows_live,
                            int64_t rows, int64_t n_lin, int mode, int device, gf2bv_result **out)
 {
-	return solve_terms(Terms(lin, term_off, ta, tb, rows_live, rows, n_lin), mode, device, out, false);
+	return solve_terms(Terms(lin, rows_live, rows, n_lin, { { term_off, ta, tb } }), mode, device, out, false);
 }
 int gf2bv_cubic_expand_device(const void *d_lin, const void *d_off2, const void *d_ta, const void *d_tb, const void *d_off3, const void *d_ua,
                               const void *d_ub, const void *d_uc, int64_t rows_live, int64_t rows, int64_t n_lin, void *d_aug,
                               int64_t stride_words, int device, void *stream)
 {
-	return terms_expand_device(Terms(d_lin, d_off2, d_ta, d_tb, rows_live, rows, n_lin, d_off3, d_ua, d_ub, d_uc, 3), d_aug, stride_words, device, stream);
+	return terms_expand_device(Terms(d_lin, rows_live, rows, n_lin, { { d_off2, d_ta, d_tb }, { d_off3, d_ua, d_ub, d_uc } }), d_aug, stride_words, device, stream);
 }
 int gf2bv_cubic_expand_words(const uint64_t *lin, const int64_t *off2, const uint64_t *ta, const uint64_t *tb, const int64_t *off3,
                              const uint64_t *ua, const uint64_t *ub, const uint64_t *uc, int64_t rows_live, int64_t rows, int64_t n_lin,
                              uint64_t *out_aug, int64_t stride_words, int device)
 {
-	return terms_expand_words(Terms(lin, off2, ta, tb, rows_live, rows, n_lin, off3, ua, ub, uc, 3), out_aug, stride_words, device, true);
+	return terms_expand_words(Terms(lin, rows_live, rows, n_lin, { { off2, ta, tb }, { off3, ua, ub, uc } }), out_aug, stride_words, device, true);
 }
 int gf2bv_solve_cubic_terms(const uint64_t *lin, const int64_t *off2, const uint64_t *ta, const uint64_t *tb, const int64_t *off3,
                             const uint64_t *ua, const uint64_t *ub, const uint64_t *uc, int64_t rows_live, int64_t rows, int64_t n_lin,
                             int mode, int device, gf2bv_result **out)
 {
-	return solve_terms(Terms(lin, off2, ta, tb, rows_live, rows, n_lin, off3, ua, ub, uc, 3), mode, device, out, true);
+	return solve_terms(Terms(lin, rows_live, rows, n_lin, { { off2, ta, tb }, { off3, ua, ub, uc } }), mode, device, out, true);
 }
 
 int gf2bv_quartic_expand_device(const void *d_lin, const void *d_off2, const void *d_ta, const void *d_tb, const void *d_off3, const void *d_ua,
@@ -5805,7 +5736,7 @@ int gf2bv_quartic_expand_device(const void *d_lin, const void *d_off2, const voi
                                 const void *d_vd, int64_t rows_live, int64_t rows, int64_t n_lin, void *d_aug, int64_t stride_words, int device,
                                 void *stream)
 {
-	return terms_expand_device(Terms(d_lin, d_off2, d_ta, d_tb, rows_live, rows, n_lin, d_off3, d_ua, d_ub, d_uc).quartic(d_off4, d_va, d_vb, d_vc, d_vd),
+	return terms_expand_device(Terms(d_lin, rows_live, rows, n_lin, { { d_off2, d_ta, d_tb }, { d_off3, d_ua, d_ub, d_uc }, { d_off4, d_va, d_vb, d_vc, d_vd } }),
 	                           d_aug, stride_words, device, stream);
 }
 int gf2bv_quartic_expand_words(const uint64_t *lin, const int64_t *off2, const uint64_t *ta, const uint64_t *tb, const int64_t *off3,
@@ -5813,7 +5744,7 @@ int gf2bv_quartic_expand_words(const uint64_t *lin, const int64_t *off2, const u
                                const uint64_t *vb, const uint64_t *vc, const uint64_t *vd, int64_t rows_live, int64_t rows, int64_t n_lin,
                                uint64_t *out_aug, int64_t stride_words, int device)
 {
-	return terms_expand_words(Terms(lin, off2, ta, tb, rows_live, rows, n_lin, off3, ua, ub, uc).quartic(off4, va, vb, vc, vd), out_aug, stride_words,
+	return terms_expand_words(Terms(lin, rows_live, rows, n_lin, { { off2, ta, tb }, { off3, ua, ub, uc }, { off4, va, vb, vc, vd } }), out_aug, stride_words,
 	                          device, true);
 }
 int gf2bv_solve_quartic_terms(const uint64_t *lin, const int64_t *off2, const uint64_t *ta, const uint64_t *tb, const int64_t *off3,
@@ -5821,7 +5752,7 @@ int gf2bv_solve_quartic_terms(const uint64_t *lin, const int64_t *off2, const ui
                               const uint64_t *vb, const uint64_t *vc, const uint64_t *vd, int64_t rows_live, int64_t rows, int64_t n_lin,
                               int mode, int device, gf2bv_result **out)
 {
-	return solve_terms(Terms(lin, off2, ta, tb, rows_live, rows, n_lin, off3, ua, ub, uc).quartic(off4, va, vb, vc, vd), mode, device, out, true);
+	return solve_terms(Terms(lin, rows_live, rows, n_lin, { { off2, ta, tb }, { off3, ua, ub, uc }, { off4, va, vb, vc, vd } }), mode, device, out, true);
 }
 
 int gf2bv_quartic_chunks(int64_t n_lin, int32_t *quad_chunk, int32_t *cubic_chunk, int32_t *quartic_chunk)
@@ -5829,12 +5760,12 @@ int gf2bv_quartic_chunks(int64_t n_lin, int32_t *quad_chunk, int32_t *cubic_chun
 	return catching([&]() -> int {
 	if (!quad_chunk || !cubic_chunk || !quartic_chunk) return fail(GF2BV_ERR_ARG, "null pointer");
 	if (n_lin < 1 || n_lin > 65535) return fail(GF2BV_ERR_ARG, "n_lin must be 1..65535");
-	const QuarticLaunch l = quartic_launch(n_lin, 2);
+	const ExpandLaunch l = expand_launch(4, n_lin, 2);
 	if ((i64)l.lds > kQuarticLdsBytes)
 		return fail(GF2BV_ERR_ARG, "the operands and the staged cubic rows of this n_lin do not fit the expansion kernel's LDS (160 KiB)");
-	*quad_chunk = l.tch2;
-	*cubic_chunk = l.tch3;
-	*quartic_chunk = l.tch4;
+	*quad_chunk = l.tch[0];
+	*cubic_chunk = l.tch[1];
+	*quartic_chunk = l.tch[2];
 	return GF2BV_OK;
 	});
 }
@@ -5844,9 +5775,9 @@ int gf2bv_cubic_chunks(int64_t n_lin, int32_t *quad_chunk, int32_t *cubic_chunk)
 	return catching([&]() -> int {
 	if (!quad_chunk || !cubic_chunk) return fail(GF2BV_ERR_ARG, "null pointer");
 	if (n_lin < 1 || n_lin > 65535) return fail(GF2BV_ERR_ARG, "n_lin must be 1..65535");
-	const CubicLaunch l = cubic_launch(n_lin, 2);
-	*quad_chunk = l.tch2;
-	*cubic_chunk = l.tch3;
+	const ExpandLaunch l = expand_launch(3, n_lin, 2);
+	*quad_chunk = l.tch[0];
+	*cubic_chunk = l.tch[1];
 	return GF2BV_OK;
 	});
 }
@@ -5857,7 +5788,7 @@ int gf2bv_factor_quad_terms(const uint64_t *lin, const int64_t *term_off, const 
 	return catching([&]() -> int {
 	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
 	*out = nullptr;
-	const Terms q(lin, term_off, ta, tb, rows_live, rows, n_lin);
+	const Terms q(lin, rows_live, rows, n_lin, { { term_off, ta, tb } });
 	int rc = check_terms(q, true);
 	if (!rc) rc = check_shape(rows, q.cols(), mode);
 	if (!rc) rc = check_device(device);
@@ -5875,7 +5806,7 @@ int gf2bv_factor_append_quad_terms(gf2bv_factor *h, const uint64_t *lin, const i
 	if (!h) return fail(GF2BV_ERR_ARG, "null pointer");
 	if (h->failed) return fail(GF2BV_ERR_ARG, kFailedHandle);
 	if (rows < 1) return fail(GF2BV_ERR_ARG, "rows must be at least 1");
-	const Terms q(lin, term_off, ta, tb, rows, rows, n_lin);
+	const Terms q(lin, rows, rows, n_lin, { { term_off, ta, tb } });
 	int rc = check_terms(q, true);
 	if (rc) return rc;
 	if (q.cols() != h->cols) return fail(GF2BV_ERR_ARG, "n_lin does not match the handle's columns");
@@ -5896,7 +5827,7 @@ int gf2bv_solve_rhs_quad_terms(const uint64_t *lin, const int64_t *term_off, con
 	return catching([&]() -> int {
 	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
 	for (i64 j = 0; j < nrhs; j++) out[j] = nullptr;
-	const Terms q(lin, term_off, ta, tb, rows_live, rows, n_lin);
+	const Terms q(lin, rows_live, rows, n_lin, { { term_off, ta, tb } });
 	int rc = check_terms(q, true);
 	if (!rc) rc = check_shape(rows, q.cols(), mode);
 	if (!rc) rc = check_rhs_args(rows, q.cols(), rhs, false, nrhs, rhs_words);
@@ -5916,7 +5847,7 @@ int gf2bv_quad_expand_batch_words(const uint64_t *lin, const int64_t *term_off, 
 	return catching([&]() -> int {
 	if (nsys < 0) return fail(GF2BV_ERR_ARG, "nsys must not be negative");
 	const i64 *sys_off = reinterpret_cast<const i64 *>(sys_row_off);
-	Terms q(lin, term_off, ta, tb, 0, rows, n_lin);
+	Terms q(lin, 0, rows, n_lin, { { term_off, ta, tb } });
 	int rc = check_quad_batch(q, sys_off, nsys);
 	if (rc) return rc;
 	if (!out_aug && rows > 0 && nsys > 0) return fail(GF2BV_ERR_ARG, "null pointer");
@@ -5937,7 +5868,7 @@ int gf2bv_solve_batch_quad_terms(const uint64_t *lin, const int64_t *term_off, c
 	if (!out || nsys < 0) return fail(GF2BV_ERR_ARG, "null pointer");
 	for (i64 s = 0; s < nsys; s++) out[s] = nullptr;
 	const i64 *sys_off = reinterpret_cast<const i64 *>(sys_row_off);
-	Terms q(lin, term_off, ta, tb, 0, rows, n_lin);
+	Terms q(lin, 0, rows, n_lin, { { term_off, ta, tb } });
 	int rc = check_quad_batch(q, sys_off, nsys);
 	if (!rc) rc = check_shape(rows, q.cols(), mode);
 	if (!rc) rc = check_device(device);
@@ -6012,7 +5943,7 @@ static int solve_xl_terms(int degree, const Terms &t, int mode, int device, gf2b
 	*out = nullptr;
 	int rc = check_terms(t, true);
 	if (rc) return rc;
-	XlShape x(degree, t.degree, t.rows, t.n);
+	XlShape x(degree, t.degree(), t.rows, t.n);
 	rc = check_xl(x, t.wt(), true);
 	if (!rc) rc = check_shape(x.rows, x.cols(), mode);
 	if (!rc) rc = check_device(device);
@@ -6135,7 +6066,7 @@ static int solve_xl_guess_terms(int degree, const Terms &q, const int32_t *guess
 	for (i64 s = 0; s < na; s++) out[s] = nullptr;
 	int rc = check_terms(q, true);
 	if (rc) return rc;
-	GuessShape g(q.rows, q.n, nguess, a0, na, degree, q.degree);
+	GuessShape g(q.rows, q.n, nguess, a0, na, degree, q.degree());
 	rc = check_guess(g, guess, q.wt());
 	if (!rc) rc = check_guess_solve(g, mode);
 	if (!rc) rc = check_device(device);
@@ -6219,12 +6150,12 @@ int gf2bv_solve_xl4_words(const uint64_t *quad, int64_t m, int64_t quad_stride_w
 int gf2bv_solve_xl3_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t m, int64_t n_lin,
                                int mode, int device, gf2bv_result **out)
 {
-	return solve_xl_terms(3, Terms(lin, term_off, ta, tb, m, m, n_lin), mode, device, out);
+	return solve_xl_terms(3, Terms(lin, m, m, n_lin, { { term_off, ta, tb } }), mode, device, out);
 }
 int gf2bv_solve_xl4_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t m, int64_t n_lin,
                                int mode, int device, gf2bv_result **out)
 {
-	return solve_xl_terms(4, Terms(lin, term_off, ta, tb, m, m, n_lin), mode, device, out);
+	return solve_xl_terms(4, Terms(lin, m, m, n_lin, { { term_off, ta, tb } }), mode, device, out);
 }
 int gf2bv_xl3_expand_batch_device(const void *d_quad, int64_t nsys, int64_t quad_sys_stride_words, int64_t m, int64_t quad_stride_words,
                                   int64_t n_lin, int64_t rows, void *d_aug, int64_t stride_words, int64_t sys_stride_words, int device,
@@ -6265,12 +6196,12 @@ int gf2bv_solve_xl4_guess_words(const uint64_t *quad, int64_t m, int64_t quad_st
 int gf2bv_solve_xl3_guess_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t m, int64_t n_lin,
                                      const int32_t *guess, int64_t nguess, int64_t a0, int64_t na, int mode, int device, gf2bv_result **out)
 {
-	return solve_xl_guess_terms(3, Terms(lin, term_off, ta, tb, m, m, n_lin), guess, nguess, a0, na, mode, device, out);
+	return solve_xl_guess_terms(3, Terms(lin, m, m, n_lin, { { term_off, ta, tb } }), guess, nguess, a0, na, mode, device, out);
 }
 int gf2bv_solve_xl4_guess_quad_terms(const uint64_t *lin, const int64_t *term_off, const uint64_t *ta, const uint64_t *tb, int64_t m, int64_t n_lin,
                                      const int32_t *guess, int64_t nguess, int64_t a0, int64_t na, int mode, int device, gf2bv_result **out)
 {
-	return solve_xl_guess_terms(4, Terms(lin, term_off, ta, tb, m, m, n_lin), guess, nguess, a0, na, mode, device, out);
+	return solve_xl_guess_terms(4, Terms(lin, m, m, n_lin, { { term_off, ta, tb } }), guess, nguess, a0, na, mode, device, out);
 }
 int64_t gf2bv_xl3_guess_chunk(int64_t m, int64_t n_lin, int64_t nguess, int64_t free_bytes)
 {
@@ -6309,7 +6240,7 @@ int gf2bv_solve_xl4_cubic_terms(const uint64_t *lin, const int64_t *off2, const 
                                 const uint64_t *ua, const uint64_t *ub, const uint64_t *uc, int64_t m, int64_t n_lin, int mode, int device,
                                 gf2bv_result **out)
 {
-	return solve_xl_terms(4, Terms(lin, off2, ta, tb, m, m, n_lin, off3, ua, ub, uc, 3), mode, device, out);
+	return solve_xl_terms(4, Terms(lin, m, m, n_lin, { { off2, ta, tb }, { off3, ua, ub, uc } }), mode, device, out);
 }
 
 // ---- hybrid degree-4 XL on cubic rows (k_cubic_specialise, k_xl4_cubic_expand_batch): the hybrid bodies above with src = 3
@@ -6346,7 +6277,7 @@ int gf2bv_solve_xl4_cubic_guess_terms(const uint64_t *lin, const int64_t *off2, 
                                       const uint64_t *ua, const uint64_t *ub, const uint64_t *uc, int64_t m, int64_t n_lin,
                                       const int32_t *guess, int64_t nguess, int64_t a0, int64_t na, int mode, int device, gf2bv_result **out)
 {
-	return solve_xl_guess_terms(4, Terms(lin, off2, ta, tb, m, m, n_lin, off3, ua, ub, uc, 3), guess, nguess, a0, na, mode, device, out);
+	return solve_xl_guess_terms(4, Terms(lin, m, m, n_lin, { { off2, ta, tb }, { off3, ua, ub, uc } }), guess, nguess, a0, na, mode, device, out);
 }
 int64_t gf2bv_xl4_cubic_guess_chunk(int64_t m, int64_t n_lin, int64_t nguess, int64_t free_bytes)
 {

@@ -479,7 +479,7 @@ class Factor:
     def append_quad_terms(self, lin, term_off, ta, tb, n_lin: int) -> None:
         """Append factored quadratic equations (the arrays of quad_expand_words, every row live): expanded on the device and
         appended there (gf2bv_factor_append_quad_terms); n_lin must be the one the factorization was made with"""
-        lin, term_off, ta, tb = _quad_terms(lin, term_off, ta, tb, n_lin)
+        lin, term_off, ta, tb = _terms(n_lin, lin, term_off, ta, tb)
         _check(lib().gf2bv_factor_append_quad_terms(self._handle(), *_ptrs(lin, term_off, ta, tb),
                                                     len(lin), n_lin))
 
@@ -602,17 +602,26 @@ def quad_words(n_lin: int) -> int:
     return (n_lin + n_lin * (n_lin - 1) // 2 + 63) // 64
 
 
-def quad_plan(origin: int, basis, n_lin: int, device: int | None = None) -> dict:
-    """gf2bv_quad_plan (host only): r, r_eff (-1: not reduced), and the forms as equation ints over r_eff unknowns.  With a
-    device: gf2bv_quad_plan_device, the same plan with the forms built by k_quad_forms on that device."""
-    words = quad_words(n_lin)
+def cubic_cols(n_lin: int) -> int:
+    return n_lin + n_lin * (n_lin - 1) // 2 + n_lin * (n_lin - 1) * (n_lin - 2) // 6
+
+
+# The quad_* and cubic_* search functions below are one body each, taking the kind: "quad" (gf2bv_quad_*, points over the
+# n_lin + n_lin(n_lin-1)/2 columns of a QuadraticSystem) or "cubic" (gf2bv_cubic_*, over cubic_cols(n_lin) columns, cubic forms)
+def _space_words(kind: str, n_lin: int) -> int:
+    return quad_words(n_lin) if kind == "quad" else (cubic_cols(n_lin) + 63) // 64
+
+
+def _search_plan(kind: str, origin: int, basis, n_lin: int, device: int | None) -> dict:
+    words = _space_words(kind, n_lin)
     o, b = _ints_to_words([origin], words), _ints_to_words(list(basis), words)
     r, re, m, fw = (ctypes.c_int64() for _ in range(4))
+    host, on_device = getattr(lib(), f"gf2bv_{kind}_plan"), getattr(lib(), f"gf2bv_{kind}_plan_device")
 
     def plan(forms, cap):
         head = (o.ctypes.data, b.ctypes.data, len(basis), words, n_lin)
         tail = (ctypes.byref(r), ctypes.byref(re), ctypes.byref(m), ctypes.byref(fw), forms, cap)
-        _check(lib().gf2bv_quad_plan(*head, *tail) if device is None else lib().gf2bv_quad_plan_device(*head, device, *tail))
+        _check(host(*head, *tail) if device is None else on_device(*head, device, *tail))
 
     plan(None, 0)
     forms = np.zeros((max(m.value, 1), max(fw.value, 1)), dtype=np.uint64)
@@ -620,85 +629,71 @@ def quad_plan(origin: int, basis, n_lin: int, device: int | None = None) -> dict
     return {"r": r.value, "r_eff": re.value, "forms": _words_to_ints(forms, m.value)}
 
 
-def quad_points(origin: int, basis, n_lin: int, ys) -> list:
-    """gf2bv_quad_points (host only): the points of the space that common zeros `ys` of quad_plan's forms stand for."""
-    words = quad_words(n_lin)
+def _search_points(kind: str, origin: int, basis, n_lin: int, ys, yw: int) -> list:
+    words = _space_words(kind, n_lin)
     o, b = _ints_to_words([origin], words), _ints_to_words(list(basis), words)
-    yw = max(1, max((int(y).bit_length() for y in ys), default=0) // 64 + 1)
     y = _ints_to_words(list(ys), yw)
     out = np.zeros((max(len(ys), 1), words), dtype=np.uint64)
-    _check(lib().gf2bv_quad_points(o.ctypes.data, b.ctypes.data, len(basis), words, n_lin, y.ctypes.data, len(ys), yw,
-                                   out.ctypes.data))
+    _check(getattr(lib(), f"gf2bv_{kind}_points")(o.ctypes.data, b.ctypes.data, len(basis), words, n_lin, y.ctypes.data, len(ys), yw,
+                                                  out.ctypes.data))
     return _words_to_ints(out, len(ys))
 
 
-def quad_forms_search(forms, r_eff: int, device: int = 0, max_out: int = 1 << 22) -> tuple:
-    """gf2bv_quad_forms_search: (count, ascending common zeros) of forms given as equation ints over r_eff unknowns."""
-    fw = (r_eff + r_eff * (r_eff - 1) // 2 + 64) // 64
+def _forms_search(kind: str, forms, fw: int, r_eff: int, device: int, max_out: int) -> tuple:
     f = _ints_to_words(list(forms), fw)
     cnt = ctypes.c_int64()
     out = np.zeros(max(max_out, 1), dtype=np.uint64)
-    _check(lib().gf2bv_quad_forms_search(f.ctypes.data, len(forms), r_eff, device, max_out, ctypes.byref(cnt), out.ctypes.data))
+    _check(getattr(lib(), f"gf2bv_{kind}_forms_search")(f.ctypes.data, len(forms), r_eff, device, max_out, ctypes.byref(cnt), out.ctypes.data))
     return cnt.value, [int(v) for v in out[:min(cnt.value, max_out)]]
 
 
-def quad_last_times() -> dict:
-    """this thread's last gf2bv_quad_search: phase times in ms, levels, first-pass candidates"""
+def _last_times(kind: str) -> dict:
     v = (ctypes.c_double * 8)()
-    lib().gf2bv_quad_last_times(v)
+    getattr(lib(), f"gf2bv_{kind}_last_times")(v)
     keys = ("ms_reduce", "ms_forms", "ms_affine", "ms_search", "ms_relin", "ms_total", "levels", "candidates")
     return dict(zip(keys, list(v)))
 
 
-# -- the same over the degree-3 columns (gf2bv_cubic_*): n_lin + C(n_lin,2) + C(n_lin,3) coordinates, cubic forms ----------------------------
-def cubic_cols(n_lin: int) -> int:
-    return n_lin + n_lin * (n_lin - 1) // 2 + n_lin * (n_lin - 1) * (n_lin - 2) // 6
+def quad_plan(origin: int, basis, n_lin: int, device: int | None = None) -> dict:
+    """gf2bv_quad_plan (host only): r, r_eff (-1: not reduced), and the forms as equation ints over r_eff unknowns.  With a
+    device: gf2bv_quad_plan_device, the same plan with the forms built by k_quad_forms on that device."""
+    return _search_plan("quad", origin, basis, n_lin, device)
+
+
+def quad_points(origin: int, basis, n_lin: int, ys) -> list:
+    """gf2bv_quad_points (host only): the points of the space that common zeros `ys` of quad_plan's forms stand for."""
+    return _search_points("quad", origin, basis, n_lin, ys, max(1, max((int(y).bit_length() for y in ys), default=0) // 64 + 1))
+
+
+def quad_forms_search(forms, r_eff: int, device: int = 0, max_out: int = 1 << 22) -> tuple:
+    """gf2bv_quad_forms_search: (count, ascending common zeros) of forms given as equation ints over r_eff unknowns."""
+    return _forms_search("quad", forms, (r_eff + r_eff * (r_eff - 1) // 2 + 64) // 64, r_eff, device, max_out)
+
+
+def quad_last_times() -> dict:
+    """this thread's last gf2bv_quad_search: phase times in ms, levels, first-pass candidates"""
+    return _last_times("quad")
 
 
 def cubic_plan(origin: int, basis, n_lin: int, device: int | None = None) -> dict:
     """gf2bv_cubic_plan (host only): r, r_eff (-1: r above 64, not reduced), and the forms as equation ints of a PackedCubicSystem of
     r_eff unknowns.  With a device: gf2bv_cubic_plan_device, the forms built by k_cubic_products / k_cubic_forms on that device."""
-    words = (cubic_cols(n_lin) + 63) // 64
-    o, b = _ints_to_words([origin], words), _ints_to_words(list(basis), words)
-    r, re, m, fw = (ctypes.c_int64() for _ in range(4))
-
-    def plan(forms, cap):
-        head = (o.ctypes.data, b.ctypes.data, len(basis), words, n_lin)
-        tail = (ctypes.byref(r), ctypes.byref(re), ctypes.byref(m), ctypes.byref(fw), forms, cap)
-        _check(lib().gf2bv_cubic_plan(*head, *tail) if device is None else lib().gf2bv_cubic_plan_device(*head, device, *tail))
-
-    plan(None, 0)
-    forms = np.zeros((max(m.value, 1), max(fw.value, 1)), dtype=np.uint64)
-    plan(forms.ctypes.data, m.value)
-    return {"r": r.value, "r_eff": re.value, "forms": _words_to_ints(forms, m.value)}
+    return _search_plan("cubic", origin, basis, n_lin, device)
 
 
 def cubic_points(origin: int, basis, n_lin: int, ys) -> list:
     """gf2bv_cubic_points (host only): the points of the space that common zeros `ys` (ints below 2^64) of cubic_plan's forms stand for."""
-    words = (cubic_cols(n_lin) + 63) // 64
-    o, b = _ints_to_words([origin], words), _ints_to_words(list(basis), words)
-    y = _ints_to_words(list(ys), 1)
-    out = np.zeros((max(len(ys), 1), words), dtype=np.uint64)
-    _check(lib().gf2bv_cubic_points(o.ctypes.data, b.ctypes.data, len(basis), words, n_lin, y.ctypes.data, len(ys), 1, out.ctypes.data))
-    return _words_to_ints(out, len(ys))
+    return _search_points("cubic", origin, basis, n_lin, ys, 1)
 
 
 def cubic_forms_search(forms, r_eff: int, device: int = 0, max_out: int = 1 << 22) -> tuple:
     """gf2bv_cubic_forms_search: (count, ascending common zeros) of cubic forms given as equation ints over r_eff unknowns."""
-    fw = (cubic_cols(r_eff) + 64) // 64
-    f = _ints_to_words(list(forms), fw)
-    cnt = ctypes.c_int64()
-    out = np.zeros(max(max_out, 1), dtype=np.uint64)
-    _check(lib().gf2bv_cubic_forms_search(f.ctypes.data, len(forms), r_eff, device, max_out, ctypes.byref(cnt), out.ctypes.data))
-    return cnt.value, [int(v) for v in out[:min(cnt.value, max_out)]]
+    return _forms_search("cubic", forms, (cubic_cols(r_eff) + 64) // 64, r_eff, device, max_out)
 
 
 def cubic_last_times() -> dict:
     """this thread's last gf2bv_cubic_search: phase times in ms, rounds of the affine elimination, first-pass candidates"""
-    v = (ctypes.c_double * 8)()
-    lib().gf2bv_cubic_last_times(v)
-    keys = ("ms_reduce", "ms_forms", "ms_affine", "ms_search", "ms_relin", "ms_total", "levels", "candidates")
-    return dict(zip(keys, list(v)))
+    return _last_times("cubic")
 
 
 def quad_cols(n_lin: int) -> int:
@@ -706,20 +701,66 @@ def quad_cols(n_lin: int) -> int:
     return n_lin + n_lin * (n_lin - 1) // 2
 
 
-def _quad_terms(lin, term_off, ta, tb, n_lin: int):
-    """the factored form of gf2bv_quad_expand_* as contiguous arrays, shapes checked against each other"""
+def xl3_cols(n_lin: int) -> int:
+    """columns of the degree-3 XL system in n_lin unknowns: the unknowns, their pairs and their triples"""
+    return quad_cols(n_lin) + n_lin * (n_lin - 1) * (n_lin - 2) // 6
+
+
+def xl4_cols(n_lin: int) -> int:
+    """columns of the degree-4 XL system in n_lin unknowns: degree 3's and the quadruples"""
+    return xl3_cols(n_lin) + n_lin * (n_lin - 1) * (n_lin - 2) * (n_lin - 3) // 24
+
+
+# how the messages name a group's offsets and its operands
+_GROUP_NAMES = (("term_off", "ta and tb"), ("off3", "ua, ub and uc"), ("off4", "va, vb, vc and vd"))
+
+
+def _terms(n_lin: int, lin, *groups) -> tuple:
+    """the factored form of gf2bv_*_expand_* -- lin, then per group of products (of 2, 3, 4 forms) its offsets and its operand arrays,
+    flat -- as contiguous arrays, shapes checked against each other"""
     wl = (n_lin + 1 + 63) // 64
-    lin = np.ascontiguousarray(lin, dtype=np.uint64).reshape(-1, wl)
-    term_off = np.ascontiguousarray(term_off, dtype=np.int64).reshape(-1)
-    ta = np.ascontiguousarray(ta, dtype=np.uint64).reshape(-1, wl)
-    tb = np.ascontiguousarray(tb, dtype=np.uint64).reshape(-1, wl)
-    if len(term_off) != len(lin) + 1 or len(ta) != len(tb) or (len(term_off) and term_off[-1] != len(ta)):
-        raise ValueError("term_off needs one entry per row of lin and one more, ending at the number of operands in ta and tb")
-    return lin, term_off, ta, tb
+    out, at = [np.ascontiguousarray(lin, dtype=np.uint64).reshape(-1, wl)], 0
+    for arity, (off_name, op_names) in zip((2, 3, 4), _GROUP_NAMES):
+        if at == len(groups):
+            break
+        off = np.ascontiguousarray(groups[at], dtype=np.int64).reshape(-1)
+        ops = [np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, wl) for x in groups[at + 1:at + 1 + arity]]
+        if len(off) != len(out[0]) + 1 or len({len(x) for x in ops}) != 1 or (len(off) and off[-1] != len(ops[0])):
+            raise ValueError(f"{off_name} needs one entry per row of lin and one more, ending at the number of operands in {op_names}")
+        out += [off] + ops
+        at += 1 + arity
+    return tuple(out)
 
 
 def _ptrs(*arrays):
     return [a.ctypes.data for a in arrays]
+
+
+# The quad_*, cubic_* and quartic_* functions below are one body each, taking the degree (2, 3, 4: one, two, three groups of products)
+_DEGREE = {2: ("quad", quad_cols), 3: ("cubic", xl3_cols), 4: ("quartic", xl4_cols)}
+
+
+def _expand_words(degree: int, terms, n_lin: int, rows: int | None, stride_words: int | None, device: int) -> np.ndarray:
+    name, cols = _DEGREE[degree]
+    terms = _terms(n_lin, *terms)
+    rows = len(terms[0]) if rows is None else rows
+    stride = (cols(n_lin) + 1 + 63) // 64 if stride_words is None else stride_words
+    out = np.empty((max(rows, 0), max(stride, 0)), dtype=np.uint64)
+    _check(getattr(lib(), f"gf2bv_{name}_expand_words")(*_ptrs(*terms), len(terms[0]), rows, n_lin, out.ctypes.data, stride, device))
+    return out
+
+
+def _expand_device(degree: int, d_terms, rows_live: int, rows: int, n_lin: int, d_aug: int, stride: int, device: int, stream: int) -> None:
+    _check(getattr(lib(), f"gf2bv_{_DEGREE[degree][0]}_expand_device")(*d_terms, rows_live, rows, n_lin, d_aug, stride, device, stream or None))
+
+
+def _solve_terms(degree: int, terms, n_lin: int, rows: int | None, mode: int, device: int) -> Solution:
+    name, cols = _DEGREE[degree]
+    terms = _terms(n_lin, *terms)
+    rows = max(len(terms[0]), cols(n_lin)) if rows is None else rows
+    h = ctypes.c_void_p()
+    _check(getattr(lib(), f"gf2bv_solve_{name}_terms")(*_ptrs(*terms), len(terms[0]), rows, n_lin, mode, device, ctypes.byref(h)))
+    return _take(h, mode)
 
 
 def quad_expand_words(lin, term_off, ta, tb, n_lin: int, rows: int | None = None, stride_words: int | None = None,
@@ -727,37 +768,26 @@ def quad_expand_words(lin, term_off, ta, tb, n_lin: int, rows: int | None = None
     """Factored quadratic equations (lin[r] ^ XOR of the products ta[t] * tb[t], t in term_off[r] .. term_off[r + 1]; linear forms of
     ceil((n_lin + 1) / 64) words, bit 0 constant, bit 1 + g unknown g) expanded on the device into the linearised rows of the
     augmented-words layout: [rows, stride_words] uint64, rows beyond len(lin) zero (gf2bv_quad_expand_words)."""
-    lin, term_off, ta, tb = _quad_terms(lin, term_off, ta, tb, n_lin)
-    rows = len(lin) if rows is None else rows
-    stride = (quad_cols(n_lin) + 1 + 63) // 64 if stride_words is None else stride_words
-    out = np.empty((max(rows, 0), max(stride, 0)), dtype=np.uint64)
-    _check(lib().gf2bv_quad_expand_words(*_ptrs(lin, term_off, ta, tb), len(lin), rows, n_lin,
-                                         out.ctypes.data, stride, device))
-    return out
+    return _expand_words(2, (lin, term_off, ta, tb), n_lin, rows, stride_words, device)
 
 
 def quad_expand_device(d_lin: int, d_term_off: int, d_ta: int, d_tb: int, rows_live: int, rows: int, n_lin: int, d_aug: int,
                        stride: int, device: int = 0, stream: int = 0) -> None:
     """quad_expand_words with everything resident in device memory: the kernel is enqueued on `stream` and the call returns; a
     solve_device / factor_device on the same stream reads the finished rows."""
-    _check(lib().gf2bv_quad_expand_device(d_lin, d_term_off, d_ta, d_tb, rows_live, rows, n_lin, d_aug, stride, device, stream or None))
+    _expand_device(2, (d_lin, d_term_off, d_ta, d_tb), rows_live, rows, n_lin, d_aug, stride, device, stream)
 
 
 def solve_quad_terms(lin, term_off, ta, tb, n_lin: int, rows: int | None = None, mode: int = MODE_SINGLE, device: int = 0) -> Solution:
     """The factored system uploaded, expanded on the device and solved there (gf2bv_solve_quad_terms): what solve_words returns for
     quad_expand_words of the same arrays.  rows (default: max(len(lin), columns)) >= the columns."""
-    lin, term_off, ta, tb = _quad_terms(lin, term_off, ta, tb, n_lin)
-    rows = max(len(lin), quad_cols(n_lin)) if rows is None else rows
-    h = ctypes.c_void_p()
-    _check(lib().gf2bv_solve_quad_terms(*_ptrs(lin, term_off, ta, tb), len(lin), rows, n_lin,
-                                        mode, device, ctypes.byref(h)))
-    return _take(h, mode)
+    return _solve_terms(2, (lin, term_off, ta, tb), n_lin, rows, mode, device)
 
 
 def factor_quad_terms(lin, term_off, ta, tb, n_lin: int, rows: int | None = None, mode: int = MODE_SINGLE, device: int = 0) -> Factor:
     """The factored system uploaded, expanded on the device and factored there (gf2bv_factor_quad_terms): what factor_words returns
     for quad_expand_words of the same arrays.  rows (default: max(len(lin), columns)) >= the columns."""
-    lin, term_off, ta, tb = _quad_terms(lin, term_off, ta, tb, n_lin)
+    lin, term_off, ta, tb = _terms(n_lin, lin, term_off, ta, tb)
     rows = max(len(lin), quad_cols(n_lin)) if rows is None else rows
     h = ctypes.c_void_p()
     rc = lib().gf2bv_factor_quad_terms(*_ptrs(lin, term_off, ta, tb), len(lin), rows, n_lin,
@@ -769,7 +799,7 @@ def solve_rhs_quad_terms(lin, term_off, ta, tb, n_lin: int, rhs: np.ndarray, row
                          device: int = 0) -> list:
     """Many right-hand sides of one factored system, one elimination (gf2bv_solve_rhs_quad_terms): what solve_rhs_words returns for
     quad_expand_words of the same arrays (the constants of the factored rows are ignored: rhs holds them)."""
-    lin, term_off, ta, tb = _quad_terms(lin, term_off, ta, tb, n_lin)
+    lin, term_off, ta, tb = _terms(n_lin, lin, term_off, ta, tb)
     rows = max(len(lin), quad_cols(n_lin)) if rows is None else rows
     rhs = _rhs_array(rhs)
     nrhs = rhs.shape[0]
@@ -791,7 +821,7 @@ def solve_batch_quad_terms(lin, term_off, ta, tb, sys_row_off, n_lin: int, rows:
     """Independent factored systems over the same n_lin as one concatenated term set (system s: rows sys_row_off[s] ..
     sys_row_off[s + 1]), expanded by one launch -- each padded to `rows` rows on the device -- and solved as lock-step gangs
     (gf2bv_solve_batch_quad_terms).  Element s is what solve_quad_terms returns for system s with the same `rows`."""
-    lin, term_off, ta, tb = _quad_terms(lin, term_off, ta, tb, n_lin)
+    lin, term_off, ta, tb = _terms(n_lin, lin, term_off, ta, tb)
     sys_row_off = _sys_row_off(sys_row_off, len(lin))
     nsys = len(sys_row_off) - 1
     rows = max(int(np.diff(sys_row_off).max(initial=0)), quad_cols(n_lin)) if rows is None else rows
@@ -805,7 +835,7 @@ def quad_expand_batch_words(lin, term_off, ta, tb, sys_row_off, n_lin: int, rows
                             device: int = 0) -> np.ndarray:
     """The batched expansion alone (gf2bv_quad_expand_batch_words): [nsys, rows, stride_words] uint64, system s the rows
     sys_row_off[s] .. sys_row_off[s + 1] of the term set expanded and the rows behind them zero."""
-    lin, term_off, ta, tb = _quad_terms(lin, term_off, ta, tb, n_lin)
+    lin, term_off, ta, tb = _terms(n_lin, lin, term_off, ta, tb)
     sys_row_off = _sys_row_off(sys_row_off, len(lin))
     nsys = len(sys_row_off) - 1
     stride = (quad_cols(n_lin) + 1 + 63) // 64 if stride_words is None else stride_words
@@ -813,22 +843,6 @@ def quad_expand_batch_words(lin, term_off, ta, tb, sys_row_off, n_lin: int, rows
     _check(lib().gf2bv_quad_expand_batch_words(*_ptrs(lin, term_off, ta, tb),
                                                sys_row_off.ctypes.data, nsys, rows, n_lin, out.ctypes.data, stride, device))
     return out
-
-
-def xl3_cols(n_lin: int) -> int:
-    """columns of the degree-3 XL system in n_lin unknowns: the unknowns, their pairs and their triples"""
-    return quad_cols(n_lin) + n_lin * (n_lin - 1) * (n_lin - 2) // 6
-
-
-def _cubic_terms(lin, off2, ta, tb, off3, ua, ub, uc, n_lin: int):
-    """the factored form of gf2bv_cubic_expand_* as contiguous arrays, shapes checked against each other"""
-    lin, off2, ta, tb = _quad_terms(lin, off2, ta, tb, n_lin)
-    wl = lin.shape[1]
-    off3 = np.ascontiguousarray(off3, dtype=np.int64).reshape(-1)
-    ua, ub, uc = (np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, wl) for x in (ua, ub, uc))
-    if len(off3) != len(lin) + 1 or len(ua) != len(ub) or len(ua) != len(uc) or (len(off3) and off3[-1] != len(ua)):
-        raise ValueError("off3 needs one entry per row of lin and one more, ending at the number of operands in ua, ub and uc")
-    return lin, off2, ta, tb, off3, ua, ub, uc
 
 
 def cubic_chunks(n_lin: int) -> tuple:
@@ -844,50 +858,24 @@ def cubic_expand_words(lin, off2, ta, tb, off3, ua, ub, uc, n_lin: int, rows: in
     off3[r] .. off3[r + 1]; affine forms of ceil((n_lin + 1) / 64) words, bit 0 constant, bit 1 + g unknown g; the products exact in
     GF(2)[x] / (x_i^2 + x_i)) expanded on the device into rows over the xl3_cols(n_lin) columns of the augmented-words layout:
     [rows, stride_words] uint64, rows beyond len(lin) zero (gf2bv_cubic_expand_words)."""
-    terms = _cubic_terms(lin, off2, ta, tb, off3, ua, ub, uc, n_lin)
-    rows = len(terms[0]) if rows is None else rows
-    stride = (xl3_cols(n_lin) + 1 + 63) // 64 if stride_words is None else stride_words
-    out = np.empty((max(rows, 0), max(stride, 0)), dtype=np.uint64)
-    _check(lib().gf2bv_cubic_expand_words(*_ptrs(*terms), len(terms[0]), rows, n_lin, out.ctypes.data, stride, device))
-    return out
+    return _expand_words(3, (lin, off2, ta, tb, off3, ua, ub, uc), n_lin, rows, stride_words, device)
 
 
 def cubic_expand_device(d_lin: int, d_off2: int, d_ta: int, d_tb: int, d_off3: int, d_ua: int, d_ub: int, d_uc: int, rows_live: int,
                         rows: int, n_lin: int, d_aug: int, stride: int, device: int = 0, stream: int = 0) -> None:
     """cubic_expand_words with everything resident in device memory: the kernel is enqueued on `stream` and the call returns; a
     solve_device on the same stream reads the finished rows."""
-    _check(lib().gf2bv_cubic_expand_device(d_lin, d_off2, d_ta, d_tb, d_off3, d_ua, d_ub, d_uc, rows_live, rows, n_lin, d_aug, stride,
-                                           device, stream or None))
+    _expand_device(3, (d_lin, d_off2, d_ta, d_tb, d_off3, d_ua, d_ub, d_uc), rows_live, rows, n_lin, d_aug, stride, device, stream)
 
 
 def solve_cubic_terms(lin, off2, ta, tb, off3, ua, ub, uc, n_lin: int, rows: int | None = None, mode: int = MODE_SINGLE,
                       device: int = 0) -> Solution:
     """The factored cubic system uploaded, expanded on the device and solved there (gf2bv_solve_cubic_terms): what solve_words
     returns for cubic_expand_words of the same arrays.  rows (default: max(len(lin), columns)) >= the columns."""
-    terms = _cubic_terms(lin, off2, ta, tb, off3, ua, ub, uc, n_lin)
-    rows = max(len(terms[0]), xl3_cols(n_lin)) if rows is None else rows
-    h = ctypes.c_void_p()
-    _check(lib().gf2bv_solve_cubic_terms(*_ptrs(*terms), len(terms[0]), rows, n_lin, mode, device, ctypes.byref(h)))
-    return _take(h, mode)
-
-
-def xl4_cols(n_lin: int) -> int:
-    """columns of the degree-4 XL system in n_lin unknowns: degree 3's and the quadruples"""
-    return xl3_cols(n_lin) + n_lin * (n_lin - 1) * (n_lin - 2) * (n_lin - 3) // 24
+    return _solve_terms(3, (lin, off2, ta, tb, off3, ua, ub, uc), n_lin, rows, mode, device)
 
 
 # -- quartic systems kept factored: the cubic functions above one arity up (gf2bv_hip.h, "quartic expansion") ------------------------------
-def _quartic_terms(lin, off2, ta, tb, off3, ua, ub, uc, off4, va, vb, vc, vd, n_lin: int):
-    """the factored form of gf2bv_quartic_expand_* as contiguous arrays, shapes checked against each other"""
-    cubic = _cubic_terms(lin, off2, ta, tb, off3, ua, ub, uc, n_lin)
-    wl = cubic[0].shape[1]
-    off4 = np.ascontiguousarray(off4, dtype=np.int64).reshape(-1)
-    ops = tuple(np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, wl) for x in (va, vb, vc, vd))
-    if len(off4) != len(cubic[0]) + 1 or len({len(x) for x in ops}) != 1 or (len(off4) and off4[-1] != len(ops[0])):
-        raise ValueError("off4 needs one entry per row of lin and one more, ending at the number of operands in va, vb, vc and vd")
-    return cubic + (off4,) + ops
-
-
 def quartic_chunks(n_lin: int) -> tuple:
     """(quadratic, cubic, quartic) terms of a row that one pass of the quartic expansion kernel holds in LDS (gf2bv_quartic_chunks,
     host only); ValueError for an n_lin whose staged cubic rows do not fit the LDS"""
@@ -901,12 +889,7 @@ def quartic_expand_words(lin, off2, ta, tb, off3, ua, ub, uc, off4, va, vb, vc, 
     """Factored quartic equations (cubic_expand_words' rows ^ XOR of va[v] * vb[v] * vc[v] * vd[v], v in off4[r] .. off4[r + 1]; the
     products exact in GF(2)[x] / (x_i^2 + x_i)) expanded on the device into rows over the xl4_cols(n_lin) columns of the
     augmented-words layout: [rows, stride_words] uint64, rows beyond len(lin) zero (gf2bv_quartic_expand_words)."""
-    terms = _quartic_terms(lin, off2, ta, tb, off3, ua, ub, uc, off4, va, vb, vc, vd, n_lin)
-    rows = len(terms[0]) if rows is None else rows
-    stride = (xl4_cols(n_lin) + 1 + 63) // 64 if stride_words is None else stride_words
-    out = np.empty((max(rows, 0), max(stride, 0)), dtype=np.uint64)
-    _check(lib().gf2bv_quartic_expand_words(*_ptrs(*terms), len(terms[0]), rows, n_lin, out.ctypes.data, stride, device))
-    return out
+    return _expand_words(4, (lin, off2, ta, tb, off3, ua, ub, uc, off4, va, vb, vc, vd), n_lin, rows, stride_words, device)
 
 
 def quartic_expand_device(d_lin: int, d_off2: int, d_ta: int, d_tb: int, d_off3: int, d_ua: int, d_ub: int, d_uc: int, d_off4: int, d_va: int,
@@ -914,19 +897,15 @@ def quartic_expand_device(d_lin: int, d_off2: int, d_ta: int, d_tb: int, d_off3:
                           stream: int = 0) -> None:
     """quartic_expand_words with everything resident in device memory: the kernel is enqueued on `stream` and the call returns; a
     solve_device on the same stream reads the finished rows."""
-    _check(lib().gf2bv_quartic_expand_device(d_lin, d_off2, d_ta, d_tb, d_off3, d_ua, d_ub, d_uc, d_off4, d_va, d_vb, d_vc, d_vd, rows_live, rows,
-                                             n_lin, d_aug, stride, device, stream or None))
+    _expand_device(4, (d_lin, d_off2, d_ta, d_tb, d_off3, d_ua, d_ub, d_uc, d_off4, d_va, d_vb, d_vc, d_vd), rows_live, rows, n_lin, d_aug,
+                   stride, device, stream)
 
 
 def solve_quartic_terms(lin, off2, ta, tb, off3, ua, ub, uc, off4, va, vb, vc, vd, n_lin: int, rows: int | None = None,
                         mode: int = MODE_SINGLE, device: int = 0) -> Solution:
     """The factored quartic system uploaded, expanded on the device and solved there (gf2bv_solve_quartic_terms): what solve_words
     returns for quartic_expand_words of the same arrays.  rows (default: max(len(lin), columns)) >= the columns."""
-    terms = _quartic_terms(lin, off2, ta, tb, off3, ua, ub, uc, off4, va, vb, vc, vd, n_lin)
-    rows = max(len(terms[0]), xl4_cols(n_lin)) if rows is None else rows
-    h = ctypes.c_void_p()
-    _check(lib().gf2bv_solve_quartic_terms(*_ptrs(*terms), len(terms[0]), rows, n_lin, mode, device, ctypes.byref(h)))
-    return _take(h, mode)
+    return _solve_terms(4, (lin, off2, ta, tb, off3, ua, ub, uc, off4, va, vb, vc, vd), n_lin, rows, mode, device)
 
 
 # The xl3_* and xl4_* functions below are one body each, taking the degree (3: multipliers 1 and x_k, n + 1 rows an equation; 4: also
@@ -984,7 +963,7 @@ def _solve_xl_words(degree: int, quad, n_lin: int, mode: int = MODE_SINGLE, devi
 def _solve_xl_quad_terms(degree: int, lin, term_off, ta, tb, n_lin: int, mode: int = MODE_SINGLE, device: int = 0) -> Solution:
     """The factored system uploaded, expanded, multiplied and solved on the device (gf2bv_solve_xl3_quad_terms / _xl4_): what
     solve_xl3_words / solve_xl4_words returns for quad_expand_words of the same arrays."""
-    lin, term_off, ta, tb = _quad_terms(lin, term_off, ta, tb, n_lin)
+    lin, term_off, ta, tb = _terms(n_lin, lin, term_off, ta, tb)
     h = ctypes.c_void_p()
     _check(_xl_fn(degree, "gf2bv_solve_xl{}_quad_terms")(*_ptrs(lin, term_off, ta, tb), len(lin), n_lin, mode, device, ctypes.byref(h)))
     return _take(h, mode)
@@ -1063,7 +1042,7 @@ def _solve_xl_guess_words(degree: int, quad, n_lin: int, guess, a0: int = 0, na:
 def _solve_xl_guess_quad_terms(degree: int, lin, term_off, ta, tb, n_lin: int, guess, a0: int = 0, na: int | None = None, mode: int = MODE_SINGLE,
                                device: int = 0) -> list:
     """solve_xl3_guess_words on a factored system: expanded on the device first (gf2bv_solve_xl3_guess_quad_terms)."""
-    lin, term_off, ta, tb = _quad_terms(lin, term_off, ta, tb, n_lin)
+    lin, term_off, ta, tb = _terms(n_lin, lin, term_off, ta, tb)
     guess = _guess(guess)
     na = _assignments(guess, a0, na)
     hs = _handles(na)
@@ -1218,7 +1197,7 @@ def solve_xl4_cubic_words(cubic, n_lin: int, mode: int = MODE_SINGLE, device: in
 def solve_xl4_cubic_terms(lin, off2, ta, tb, off3, ua, ub, uc, n_lin: int, mode: int = MODE_SINGLE, device: int = 0) -> Solution:
     """The factored cubic system uploaded, expanded, multiplied and solved on the device (gf2bv_solve_xl4_cubic_terms): what
     solve_xl4_cubic_words returns for cubic_expand_words of the same arrays."""
-    terms = _cubic_terms(lin, off2, ta, tb, off3, ua, ub, uc, n_lin)
+    terms = _terms(n_lin, lin, off2, ta, tb, off3, ua, ub, uc)
     h = ctypes.c_void_p()
     _check(lib().gf2bv_solve_xl4_cubic_terms(*_ptrs(*terms), len(terms[0]), n_lin, mode, device, ctypes.byref(h)))
     return _take(h, mode)
@@ -1289,7 +1268,7 @@ def solve_xl4_cubic_guess_words(cubic, n_lin: int, guess, a0: int = 0, na: int |
 def solve_xl4_cubic_guess_terms(lin, off2, ta, tb, off3, ua, ub, uc, n_lin: int, guess, a0: int = 0, na: int | None = None,
                                 mode: int = MODE_SINGLE, device: int = 0) -> list:
     """solve_xl4_cubic_guess_words on a factored cubic system: expanded on the device first (gf2bv_solve_xl4_cubic_guess_terms)."""
-    terms = _cubic_terms(lin, off2, ta, tb, off3, ua, ub, uc, n_lin)
+    terms = _terms(n_lin, lin, off2, ta, tb, off3, ua, ub, uc)
     guess = _guess(guess)
     na = _assignments(guess, a0, na)
     hs = _handles(na)

@@ -285,7 +285,159 @@ def xl4_quad_col(n: int, i: int, j: int, l: int, p: int) -> int:
     return xl3_cols(n) + i * (i - 1) * (i - 2) * (i - 3) // 24 + j * (j - 1) * (j - 2) // 6 + l * (l - 1) // 2 + p
 
 
-class _QuadraticPoints:
+class _ProductColumns:
+    """The product columns behind the n unknowns -- pairs, triples and (degree 4) quadruples, in the order of xl3_cols / xl4_cols -- as
+    index arrays, and the test that a raw point's product coordinates are the products of its linear bits.  For every system whose
+    columns are those: the XL methods of the quadratic classes, the packed cubic and quartic systems."""
+
+    def _xl_index(self, n: Optional[int] = None):
+        """(bit position of every coordinate's members) index arrays of the pair and the triple columns over n unknowns (default: the
+        system's), built once per n"""
+        n = self._lin_size if n is None else n
+        cache = self.__dict__.setdefault("_xl_index_cache", {})
+        idx = cache.get(n)
+        if idx is None:
+            import numpy as np                         # noqa: PLC0415  (first use only: the package imports without numpy)
+            pi, pj = np.tril_indices(n, -1)            # (1,0) (2,0) (2,1) ...: pair (i, j) at i(i-1)/2 + j
+            a = np.arange(n)
+            ti, tj, tl = np.nonzero((a[:, None, None] > a[None, :, None]) & (a[None, :, None] > a[None, None, :]))      # i, then j, then l
+            idx = cache[n] = (pi, pj, ti, tj, tl)
+        return idx
+
+    def _xl4_index(self, n: int):
+        """the same for the quadruple columns: i, then j, then l, then p"""
+        cache = self.__dict__.setdefault("_xl4_index_cache", {})
+        idx = cache.get(n)
+        if idx is None:
+            import numpy as np                         # noqa: PLC0415
+            a = np.arange(n)
+            idx = cache[n] = np.nonzero((a[:, None, None, None] > a[None, :, None, None]) & (a[None, :, None, None] > a[None, None, :, None])
+                                        & (a[None, None, :, None] > a[None, None, None, :]))
+        return idx
+
+    def _xl_products_match(self, s: int, n: int, degree: int = 3) -> bool:
+        """every pair and triple (degree 4: and quadruple) coordinate of a raw point over the XL columns of n unknowns is the product
+        of its linear bits"""
+        import numpy as np                             # noqa: PLC0415
+        cols3 = xl3_cols(n)
+        cols = xl4_cols(n) if degree == 4 else cols3
+        assert s >> cols == 0, "Invalid solution"
+        bits = np.unpackbits(np.frombuffer(s.to_bytes((cols + 7) // 8, "little"), dtype=np.uint8), bitorder="little")[:cols]
+        pi, pj, ti, tj, tl = self._xl_index(n)
+        lin, pairs, triples = bits[:n], bits[n:n + len(pi)], bits[n + len(pi):cols3]
+        if not (np.array_equal(pairs, lin[pi] & lin[pj]) and np.array_equal(triples, lin[ti] & lin[tj] & lin[tl])):
+            return False
+        if degree == 4:
+            qi, qj, ql, qp = self._xl4_index(n)
+            return bool(np.array_equal(bits[cols3:], lin[qi] & lin[qj] & lin[ql] & lin[qp]))
+        return True
+
+
+class _XlGuess:
+    """The driver of hybrid XL: the guess parsed, every assignment's system solved a chunk at a time, the raw points scattered back over
+    all unknowns; and the ``*_xl4_guess`` methods on top of it.  The class mixed into supplies ``_lin_size``, ``_xl_products_match``
+    (_ProductColumns), ``_solve_internal_xl4_guess(zeros, guess, mode)`` (degree 3: ``_solve_internal_xl_guess``) -> None (every
+    assignment inconsistent) or (number of equations, run) with run(first, count) the list of raw results of the assignments
+    first .. first + count - 1, ``_xl_guess_chunk(degree)`` (the library's chunk function for its systems) and ``_guess_sol(full)`` (its
+    solution tuple of a point over all unknowns)."""
+
+    def _parse_guess(self, guess) -> list:
+        """the flattened unknown index of every item: an int, or a one-bit BitVec / PackedBitVec that is exactly one unknown"""
+        n = self._lin_size
+        out = []
+        for item in guess:
+            if isinstance(item, BitVec):
+                bits = item._bits
+                v = bits[0] if len(bits) == 1 else 0
+                if v < 2 or v & (v - 1) or v.bit_length() - 2 >= n:
+                    raise ValueError("a guessed bit must be exactly one unknown")
+                idx = v.bit_length() - 2
+            elif isinstance(item, int) and not isinstance(item, bool):
+                idx = item
+            else:
+                raise ValueError("a guess is an unknown index or a one-bit BitVec")
+            if not 0 <= idx < n:
+                raise ValueError(f"guessed unknown {idx} is not in 0..{n - 1}")
+            if idx in out:
+                raise ValueError(f"unknown {idx} is guessed twice")
+            out.append(idx)
+        if len(out) > min(n - 1, 30):
+            raise ValueError(f"at most min(n - 1, 30) = {min(n - 1, 30)} unknowns can be guessed, not {len(out)}")
+        return out
+
+    def _xl_guess_chunks(self, zeros: Zeros, guess, assignments, mode: int, degree: int = 3):
+        """(first assignment, raw results) chunk by chunk, the next chunk solved only when it is asked for"""
+        g = self._parse_guess(guess)
+        first, count = (0, 1 << len(g)) if assignments is None else assignments
+        if first < 0 or count < 0 or first + count > 1 << len(g):
+            raise ValueError(f"assignments must be a range (first, count) inside 0..{(1 << len(g)) - 1}")
+        staged = (self._solve_internal_xl4_guess if degree == 4 else self._solve_internal_xl_guess)(zeros, g, mode)
+        if staged is None:
+            yield first, [None] * count
+            return
+        m, run = staged
+        chunk = self._xl_guess_chunk(degree)(m, self._lin_size, len(g))
+        if chunk < 1:
+            raise MemoryError(f"one assignment's degree-{degree} XL system does not fit a quarter of the free device memory")
+        end = first + count
+        while first < end:
+            na = min(chunk, end - first)
+            yield first, run(first, na)
+            first += na
+
+    def _scatter_guess(self, raw: int, g: list, assignment: int, degree: int = 3) -> Optional[tuple]:
+        n = self._lin_size
+        ns = n - len(g)
+        if not self._xl_products_match(raw, ns, degree):
+            return None
+        full = 0
+        for t, idx in enumerate(g):
+            full |= ((assignment >> t) & 1) << idx
+        rest = [u for u in range(n) if u not in g]
+        for k, u in enumerate(rest):
+            full |= ((raw >> k) & 1) << u
+        return self._guess_sol(full)
+
+    def _solve_all_xl_guess(self, zeros: Zeros, guess, max_dimension: int, assignments, degree: int):
+        g = self._parse_guess(guess)
+        for first, spaces in self._xl_guess_chunks(zeros, g, assignments, 1, degree):
+            for k, space in enumerate(spaces):
+                if space is None:
+                    continue
+                if space.dimension > max_dimension:
+                    raise DimensionTooLargeError(
+                        f"Solution space of assignment {first + k} (dim {space.dimension}) is too large, try increase max_dimension "
+                        f"({max_dimension}) or guess more unknowns (there will be 2**dim solutions)",
+                        space=space,
+                    )
+                for raw in space:
+                    sol = self._scatter_guess(raw, g, first + k, degree)
+                    if sol is not None:
+                        yield sol
+
+    def solve_raw_one_xl4_guess(self, zeros: Zeros, guess, assignments=None) -> list:
+        """solve_raw_one_xl_guess over the quartic columns of the remaining unknowns"""
+        return [raw for _, raws in self._xl_guess_chunks(zeros, guess, assignments, 0, 4) for raw in raws]
+
+    def solve_raw_space_xl4_guess(self, zeros: Zeros, guess, assignments=None) -> list:
+        """solve_raw_space_xl_guess over the quartic columns of the remaining unknowns"""
+        return [raw for _, raws in self._xl_guess_chunks(zeros, guess, assignments, 1, 4) for raw in raws]
+
+    def convert_sol_xl4_guess(self, raw: int, guess, assignment: int) -> Optional[tuple]:
+        """convert_sol_xl_guess of a raw point over the quartic columns of the remaining unknowns"""
+        return self._scatter_guess(raw, self._parse_guess(guess), assignment, 4)
+
+    def solve_all_xl4_guess(self, zeros: Zeros, guess, *, max_dimension: int = 16, assignments=None):
+        """solve_all_xl_guess with every assignment's degree-4 XL system (about (n - f)^2 / 12 equations)"""
+        return self._solve_all_xl_guess(zeros, guess, max_dimension, assignments, 4)
+
+    def solve_one_xl4_guess(self, zeros: Zeros, guess, *, max_dimension: int = 16):
+        for sol in self.solve_all_xl4_guess(zeros, guess, max_dimension=max_dimension):
+            return sol
+        return None
+
+
+class _QuadraticPoints(_ProductColumns, _XlGuess):
     """What a linearised quadratic system does with the solutions of its linear solve, shared by ``QuadraticSystem`` and the packed
     front-end's ``PackedQuadraticSystem``: the points whose product unknowns equal the products of their linear part.  Needs
     ``_lin_size`` / ``_quad_size`` / ``_quad_sizes``, ``_convert_sol`` and ``solve_raw_space`` / ``solve_raw_space_rhs`` / ``solve_all`` of the
@@ -392,48 +544,6 @@ class _QuadraticPoints:
     def solve_raw_space_xl(self, zeros: Zeros):
         return self._solve_internal_xl(zeros, 1)
 
-    def _xl_index(self, n: Optional[int] = None):
-        """(bit position of every coordinate's members) index arrays of the pair and the triple columns over n unknowns (default: the
-        system's), built once per n"""
-        n = self._lin_size if n is None else n
-        cache = self.__dict__.setdefault("_xl_index_cache", {})
-        idx = cache.get(n)
-        if idx is None:
-            import numpy as np                         # noqa: PLC0415  (first use only: the package imports without numpy)
-            pi, pj = np.tril_indices(n, -1)            # (1,0) (2,0) (2,1) ...: pair (i, j) at i(i-1)/2 + j
-            a = np.arange(n)
-            ti, tj, tl = np.nonzero((a[:, None, None] > a[None, :, None]) & (a[None, :, None] > a[None, None, :]))      # i, then j, then l
-            idx = cache[n] = (pi, pj, ti, tj, tl)
-        return idx
-
-    def _xl4_index(self, n: int):
-        """the same for the quadruple columns: i, then j, then l, then p"""
-        cache = self.__dict__.setdefault("_xl4_index_cache", {})
-        idx = cache.get(n)
-        if idx is None:
-            import numpy as np                         # noqa: PLC0415
-            a = np.arange(n)
-            idx = cache[n] = np.nonzero((a[:, None, None, None] > a[None, :, None, None]) & (a[None, :, None, None] > a[None, None, :, None])
-                                        & (a[None, None, :, None] > a[None, None, None, :]))
-        return idx
-
-    def _xl_products_match(self, s: int, n: int, degree: int = 3) -> bool:
-        """every pair and triple (degree 4: and quadruple) coordinate of a raw point over the XL columns of n unknowns is the product
-        of its linear bits"""
-        import numpy as np                             # noqa: PLC0415
-        cols3 = xl3_cols(n)
-        cols = xl4_cols(n) if degree == 4 else cols3
-        assert s >> cols == 0, "Invalid solution"
-        bits = np.unpackbits(np.frombuffer(s.to_bytes((cols + 7) // 8, "little"), dtype=np.uint8), bitorder="little")[:cols]
-        pi, pj, ti, tj, tl = self._xl_index(n)
-        lin, pairs, triples = bits[:n], bits[n:n + len(pi)], bits[n + len(pi):cols3]
-        if not (np.array_equal(pairs, lin[pi] & lin[pj]) and np.array_equal(triples, lin[ti] & lin[tj] & lin[tl])):
-            return False
-        if degree == 4:
-            qi, qj, ql, qp = self._xl4_index(n)
-            return bool(np.array_equal(bits[cols3:], lin[qi] & lin[qj] & lin[ql] & lin[qp]))
-        return True
-
     def convert_sol_xl(self, s: int) -> Optional[tuple]:
         """the linear parts of a raw point over the cubic columns when every pair and triple coordinate is the product of its linear
         bits, None otherwise"""
@@ -477,53 +587,8 @@ class _QuadraticPoints:
     # -- hybrid XL (no counterpart in the reference) -------------------------------------------------------------
     # With fewer equations than degree-3 XL needs, f unknowns are fixed in all 2^f ways: assignment a sets unknown guess[t] to bit t of
     # a and leaves a quadratic system in the other n - f unknowns (renumbered in increasing index), which needs about (n - f)^2 / 6
-    # equations.  The device substitutes, multiplies and solves every assignment's system as one batch.  The class mixed into supplies
-    # _solve_internal_xl_guess(zeros, guess, mode) (degree 4: _solve_internal_xl4_guess) -> None (every assignment inconsistent) or (number of equations, run) with
-    # run(first, count) the list of raw results of the assignments first .. first + count - 1.
-    def _parse_guess(self, guess) -> list:
-        """the flattened unknown index of every item: an int, or a one-bit BitVec / PackedBitVec that is exactly one unknown"""
-        n = self._lin_size
-        out = []
-        for item in guess:
-            if isinstance(item, BitVec):
-                bits = item._bits
-                v = bits[0] if len(bits) == 1 else 0
-                if v < 2 or v & (v - 1) or v.bit_length() - 2 >= n:
-                    raise ValueError("a guessed bit must be exactly one unknown")
-                idx = v.bit_length() - 2
-            elif isinstance(item, int) and not isinstance(item, bool):
-                idx = item
-            else:
-                raise ValueError("a guess is an unknown index or a one-bit BitVec")
-            if not 0 <= idx < n:
-                raise ValueError(f"guessed unknown {idx} is not in 0..{n - 1}")
-            if idx in out:
-                raise ValueError(f"unknown {idx} is guessed twice")
-            out.append(idx)
-        if len(out) > min(n - 1, 30):
-            raise ValueError(f"at most min(n - 1, 30) = {min(n - 1, 30)} unknowns can be guessed, not {len(out)}")
-        return out
-
-    def _xl_guess_chunks(self, zeros: Zeros, guess, assignments, mode: int, degree: int = 3):
-        """(first assignment, raw results) chunk by chunk, the next chunk solved only when it is asked for"""
-        g = self._parse_guess(guess)
-        first, count = (0, 1 << len(g)) if assignments is None else assignments
-        if first < 0 or count < 0 or first + count > 1 << len(g):
-            raise ValueError(f"assignments must be a range (first, count) inside 0..{(1 << len(g)) - 1}")
-        staged = (self._solve_internal_xl4_guess if degree == 4 else self._solve_internal_xl_guess)(zeros, g, mode)
-        if staged is None:
-            yield first, [None] * count
-            return
-        m, run = staged
-        chunk = self._xl_guess_chunk(degree)(m, self._lin_size, len(g))
-        if chunk < 1:
-            raise MemoryError(f"one assignment's degree-{degree} XL system does not fit a quarter of the free device memory")
-        end = first + count
-        while first < end:
-            na = min(chunk, end - first)
-            yield first, run(first, na)
-            first += na
-
+    # equations.  The device substitutes, multiplies and solves every assignment's system as one batch.  The driver and the degree-4
+    # methods are _XlGuess's, which says what the class mixed into supplies.
     def _xl_guess_chunk(self, degree: int):
         """the library's chunk function for this class's systems of that degree"""
         from . import hip                              # noqa: PLC0415  (ctypes binding, first use only)
@@ -538,36 +603,11 @@ class _QuadraticPoints:
         remaining unknowns"""
         return [raw for _, raws in self._xl_guess_chunks(zeros, guess, assignments, 1) for raw in raws]
 
-    def solve_raw_one_xl4_guess(self, zeros: Zeros, guess, assignments=None) -> list:
-        """solve_raw_one_xl_guess over the quartic columns of the remaining unknowns"""
-        return [raw for _, raws in self._xl_guess_chunks(zeros, guess, assignments, 0, 4) for raw in raws]
-
-    def solve_raw_space_xl4_guess(self, zeros: Zeros, guess, assignments=None) -> list:
-        """solve_raw_space_xl_guess over the quartic columns of the remaining unknowns"""
-        return [raw for _, raws in self._xl_guess_chunks(zeros, guess, assignments, 1, 4) for raw in raws]
-
-    def convert_sol_xl4_guess(self, raw: int, guess, assignment: int) -> Optional[tuple]:
-        """convert_sol_xl_guess of a raw point over the quartic columns of the remaining unknowns"""
-        return self._scatter_guess(raw, self._parse_guess(guess), assignment, 4)
-
     def convert_sol_xl_guess(self, raw: int, guess, assignment: int) -> Optional[tuple]:
         """convert_sol_xl of a raw point of assignment `assignment`'s system: the check over the remaining unknowns, then their bits
         and the guessed ones scattered into the solution; None when a product coordinate disagrees"""
         g = self._parse_guess(guess)
         return self._scatter_guess(raw, g, assignment)
-
-    def _scatter_guess(self, raw: int, g: list, assignment: int, degree: int = 3) -> Optional[tuple]:
-        n = self._lin_size
-        ns = n - len(g)
-        if not self._xl_products_match(raw, ns, degree):
-            return None
-        full = 0
-        for t, idx in enumerate(g):
-            full |= ((assignment >> t) & 1) << idx
-        rest = [u for u in range(n) if u not in g]
-        for k, u in enumerate(rest):
-            full |= ((raw >> k) & 1) << u
-        return self._guess_sol(full)
 
     def _guess_sol(self, full: int) -> tuple:
         return self._convert_sol(full)[:-1]            # (without the trailing block of the product unknowns)
@@ -577,32 +617,6 @@ class _QuadraticPoints:
         order; the assignments are solved a chunk at a time (hip.xl3_guess_chunk), the next chunk when more is asked for"""
         self._check_degree(degree)
         return self._solve_all_xl_guess(zeros, guess, max_dimension, assignments, 3)
-
-    def solve_all_xl4_guess(self, zeros: Zeros, guess, *, max_dimension: int = 16, assignments=None):
-        """solve_all_xl_guess with every assignment's degree-4 XL system (about (n - f)^2 / 12 equations)"""
-        return self._solve_all_xl_guess(zeros, guess, max_dimension, assignments, 4)
-
-    def solve_one_xl4_guess(self, zeros: Zeros, guess, *, max_dimension: int = 16):
-        for sol in self.solve_all_xl4_guess(zeros, guess, max_dimension=max_dimension):
-            return sol
-        return None
-
-    def _solve_all_xl_guess(self, zeros: Zeros, guess, max_dimension: int, assignments, degree: int):
-        g = self._parse_guess(guess)
-        for first, spaces in self._xl_guess_chunks(zeros, g, assignments, 1, degree):
-            for k, space in enumerate(spaces):
-                if space is None:
-                    continue
-                if space.dimension > max_dimension:
-                    raise DimensionTooLargeError(
-                        f"Solution space of assignment {first + k} (dim {space.dimension}) is too large, try increase max_dimension "
-                        f"({max_dimension}) or guess more unknowns (there will be 2**dim solutions)",
-                        space=space,
-                    )
-                for raw in space:
-                    sol = self._scatter_guess(raw, g, first + k, degree)
-                    if sol is not None:
-                        yield sol
 
     def solve_one_xl_guess(self, zeros: Zeros, guess, *, degree: int = 3, max_dimension: int = 16):
         for sol in self.solve_all_xl_guess(zeros, guess, degree=degree, max_dimension=max_dimension):

@@ -26,7 +26,7 @@ from ._internal import (m4ri_solve_cubic_packed, m4ri_solve_many_quad_packed, m4
                         m4ri_solve_quartic_packed, m4ri_solve_xl3_guess_quad_packed, m4ri_solve_xl3_quad_packed, m4ri_solve_xl4_guess_cubic_packed,
                         m4ri_solve_xl4_guess_quad_packed, m4ri_solve_xl4_cubic_packed, m4ri_solve_xl4_quad_packed)
 from .bitvec import BitVec
-from .linsys import _QuadraticPoints, _SolveSurface, _eqs_from_words, _raw_value, _space_points, xl3_cols, xl4_cols
+from .linsys import _ProductColumns, _QuadraticPoints, _SolveSurface, _XlGuess, _eqs_from_words, _raw_value, _space_points, xl3_cols, xl4_cols
 
 
 def _const_bits(n: int, value: int) -> np.ndarray:
@@ -641,10 +641,12 @@ class PackedQuadraticSystem(_QuadraticPoints, PackedLinearSystem):
         return [None if raw is None else self.convert_sol(raw) for raw in self._solve_internal_many(zeros_list, 0)]
 
 
-# ---- cubic systems kept factored ---------------------------------------------------------------------------------------------------
-# One degree up: a symbolic bit is a linear form plus products of two affine forms plus products of three, and the rows over the
-# n + C(n,2) + C(n,3) columns of degree-3 XL come into being on the device (k_cubic_expand, through m4ri_solve_cubic_packed /
-# hip.cubic_expand_words).
+# ---- cubic and quartic systems kept factored ------------------------------------------------------------------------------------------
+# One and two degrees up: a symbolic bit is a linear form plus products of two, of three and (quartic) of four affine forms, and the rows
+# over the n + C(n,2) + C(n,3) columns of degree-3 XL, or those and the C(n,4) of degree-4 XL, come into being on the device
+# (k_cubic_expand / k_quartic_expand, through m4ri_solve_cubic_packed / m4ri_solve_quartic_packed / hip.*_expand_words).  The columns
+# of degree <= 3 are the same in both layouts, so a product of two or of three forms is the same equation int in both.  Each kind is
+# one vector class and one system class over a shared base (_ExactBitVec, _ExactSystem); the two kinds are siblings and do not mix.
 def _exact_product_int(forms: tuple, n: int) -> int:
     """the exact product of two or three affine forms (equation ints over n unknowns) as an equation int over the cubic columns:
     bit 0 the constant, bit 1 + c column c of xl3_cols(n), put together from runs of consecutive columns"""
@@ -677,234 +679,6 @@ def _exact_product_int(forms: tuple, n: int) -> int:
     return e
 
 
-class PackedCubicBitVec(_TermsBitVec):
-    """``_TermsBitVec`` with products of two affine forms (bit i owns the operand rows ``_off2[i] .. _off2[i + 1]`` of ``_ta`` /
-    ``_tb``) and products of three (``_off3``, ``_ua`` / ``_ub`` / ``_uc``).  A product is the exact product in
-    GF(2)[x] / (x_i^2 + x_i)."""
-    __slots__ = ()
-    _ARITIES = (2, 3)
-    _off2, _ta, _tb = _part(0), _part(0, 0), _part(0, 1)
-    _off3, _ua, _ub, _uc = _part(1), _part(1, 0), _part(1, 1), _part(1, 2)
-
-    def __init__(self, lin, off2, ta, tb, off3, ua, ub, uc, n: int):
-        # [k, Wl] uint64, then [k + 1] int64, [T2, Wl] x 2 and [k + 1] int64, [T3, Wl] x 3: immutable
-        self._lin, self._groups = lin, ((off2, (ta, tb)), (off3, (ua, ub, uc)))
-        self._n = n                                    # unknowns of the system
-
-    def _degree(self) -> int:
-        (_, quad), (_, cubic) = self._groups
-        return 3 if len(cubic[0]) else 2 if len(quad[0]) else 1
-
-    def _coerce(self, other, what: str) -> "PackedCubicBitVec":
-        if not isinstance(other, PackedCubicBitVec):
-            if isinstance(other, PackedQuadBitVec):
-                raise TypeError(_QUAD_MIX)
-            if not isinstance(other, PackedBitVec):
-                if isinstance(other, BitVec):
-                    raise TypeError("cannot mix packed and tuple-of-int BitVecs")
-                raise TypeError(f"{what} needs a PackedCubicBitVec or a PackedBitVec")
-            other = self._from_rows(other._rows, self._n)
-        if other._lin.shape[1] != self._lin.shape[1] or other._n != self._n:
-            raise ValueError("Cannot mix bitvecs over different numbers of unknowns")
-        return other
-
-    def _eq_ints(self) -> list:
-        """every bit as an equation int over the cubic columns, expanded on the host a product at a time"""
-        n = self._n
-        ints = lambda rows: [int.from_bytes(r.tobytes(), "little") & ((1 << (n + 1)) - 1) for r in rows]      # noqa: E731
-        lin, ops2, ops3 = ints(self._lin), [ints(x) for x in (self._ta, self._tb)], [ints(x) for x in (self._ua, self._ub, self._uc)]
-        out = []
-        for k, e in enumerate(lin):
-            for t in range(self._off2[k], self._off2[k + 1]):
-                e ^= _exact_product_int((ops2[0][t], ops2[1][t]), n)
-            for u in range(self._off3[k], self._off3[k + 1]):
-                e ^= _exact_product_int((ops3[0][u], ops3[1][u], ops3[2][u]), n)
-            out.append(e)
-        return out
-
-    def evaluate(self, s: int) -> int:
-        """Value under the raw point ``s`` over the cubic columns (bit c = column c: the n unknowns, their pairs, their triples),
-        as BitVec.evaluate gives it for the expanded bits; on the host."""
-        point = ((s << 1) | 1) & ((1 << (xl3_cols(self._n) + 1)) - 1)
-        return sum((bin(e & point).count("1") & 1) << k for k, e in enumerate(self._eq_ints()))
-
-
-def _refuse_system(name: str, system: str = "PackedCubicSystem"):
-    def method(self, *args, **kwargs):
-        raise TypeError(f"{name} is not built for a {system}")
-    method.__name__ = name
-    return method
-
-
-class PackedCubicSystem(PackedLinearSystem):
-    """Equations of degree <= 3 written directly and kept factored: ``gens()`` are PackedLinearSystem's PackedBitVecs, ``mul_bit``
-    multiplies single bits up to degree 3 (exact products), and the solve methods hand the factored arrays to the device, which
-    expands them over the n + C(n,2) + C(n,3) columns of degree-3 XL and solves.  ``solve_all`` keeps the points of the linearised
-    space whose pair and triple coordinates are the products of their linear bits.  The ``*_xl4`` methods are degree-4 XL: the device
-    multiplies every expanded equation by 1 and by each unknown too and solves over the n + C(n,2) + C(n,3) + C(n,4) monomials of
-    degree <= 4, which takes about C(n,3) / 4 equations where plain linearisation takes about C(n,3).  Its hybrid form, which
-    guesses unknowns, is PackedCubicGuessSystem's."""
-
-    def __init__(self, sizes: Iterable[int]):
-        super().__init__(sizes)
-        self._lin_size = sum(self._sizes)
-        self._cols = xl3_cols(self._lin_size)          # (``_words`` stays the words of a linear form: the generators have no product coordinates)
-
-    _xl_index = _QuadraticPoints._xl_index
-    _xl4_index = _QuadraticPoints._xl4_index
-    _xl_products_match = _QuadraticPoints._xl_products_match
-
-    def _single(self, a) -> PackedCubicBitVec:
-        if isinstance(a, PackedQuadBitVec):
-            raise TypeError(_QUAD_MIX)
-        if not isinstance(a, (PackedBitVec, PackedCubicBitVec)):
-            raise TypeError("mul_bit needs PackedBitVecs or PackedCubicBitVecs of this system")
-        if len(a) != 1:
-            raise ValueError("The inputs should be single bits")
-        rows = a._rows if isinstance(a, PackedBitVec) else a._lin
-        if rows.shape[1] != self._words:
-            raise ValueError("Cannot mix bitvecs over different numbers of unknowns")
-        return PackedCubicBitVec._from_rows(rows, self._lin_size) if isinstance(a, PackedBitVec) else a
-
-    def mul_bit(self, a, b) -> PackedCubicBitVec:
-        """the exact product of two single bits whose degrees (structural: a bit has cubic terms, or quadratic ones, or neither) add up
-        to 3 at most.  By distributivity lin_a lin_b is one quadratic term and (ta tb) lin_b one cubic term per product of a."""
-        a, b = self._single(a), self._single(b)
-        da, db = a._degree(), b._degree()
-        if da + db > 3:
-            raise TypeError(f"mul_bit of bits of degree {da} and {db} is of degree {da + db}, above 3")
-        if da < db:
-            a, b = b, a                                # (b is linear now)
-        ta, tb = a._groups[0][1]
-        k = len(ta)
-        return PackedCubicBitVec(np.zeros((1, self._words), dtype=np.uint64), np.array([0, 1], dtype=np.int64), a._lin, b._lin,
-                                 np.array([0, k], dtype=np.int64), ta, tb, np.repeat(b._lin, k, axis=0), self._lin_size)
-
-    # -- zeros -> the factored arrays the device expands ----------------------------------------------------------------------------
-    def _terms(self, zeros: Sequence):
-        """(lin, off2, ta, tb, off3, ua, ub, uc) of all the bits of ``zeros``, in order; no row is dropped (_zeros_terms)"""
-        return _zeros_terms(zeros, PackedCubicBitVec, "cubic", self._words)
-
-    def get_eqs(self, zeros: Sequence) -> list:
-        """equation ints over the cubic columns, expanded on the device (needs the GPU); zero rows are dropped"""
-        from . import hip                              # noqa: PLC0415  (ctypes binding, first use only)
-        terms = self._terms(zeros)
-        if not len(terms[0]):
-            return []
-        return _eqs_from_words(hip.cubic_expand_words(*terms, self._lin_size), self._cols)
-
-    # -- boundary call ---------------------------------------------------------------------------------------------------------------
-    def _solve_internal(self, zeros: Sequence, mode: int):
-        terms = self._terms(zeros)
-        return m4ri_solve_cubic_packed(*terms, self._lin_size, max(len(terms[0]), self._cols), mode)      # (the boundary wants rows >= cols)
-
-    def convert_sol(self, s: int) -> Optional[tuple]:
-        """the values of the generators at a raw point over the cubic columns whose pair and triple coordinates are the products of
-        its linear bits, None for any other point"""
-        n = self._lin_size
-        if not self._xl_products_match(s, n, 3):
-            return None
-        return self._convert_sol(s & ((1 << n) - 1))
-
-    def solve_one(self, zeros: Sequence):
-        # the particular solution of the linearised system need not be consistent: take the first one that is
-        for sol in self.solve_all(zeros):
-            return sol
-        return None
-
-    # -- degree-4 XL: the factored arrays go down, the device expands, multiplies by 1 and by every unknown, pads and solves ----------
-    def _solve_internal_xl4(self, zeros: Sequence, mode: int):
-        return m4ri_solve_xl4_cubic_packed(*self._terms(zeros), self._lin_size, mode)
-
-    def solve_raw_one_xl4(self, zeros: Sequence):
-        return self._solve_internal_xl4(zeros, 0)
-
-    def solve_raw_space_xl4(self, zeros: Sequence):
-        return self._solve_internal_xl4(zeros, 1)
-
-    def convert_sol_xl4(self, s: int) -> Optional[tuple]:
-        """convert_sol over the quartic columns: the quadruple coordinates are checked too"""
-        n = self._lin_size
-        if not self._xl_products_match(s, n, 4):
-            return None
-        return self._convert_sol(s & ((1 << n) - 1))
-
-    def solve_all_xl4(self, zeros: Sequence, *, max_dimension: int = 16):
-        """solve_all through degree-4 XL: the consistent points of the quartic system's solution space, in AffineSpace order"""
-        yield from _space_points(self.solve_raw_space_xl4(zeros), max_dimension, self.convert_sol_xl4)
-
-    def solve_one_xl4(self, zeros: Sequence):
-        for sol in self.solve_all_xl4(zeros):
-            return sol
-        return None
-
-    def get_eqs_xl4(self, zeros: Sequence) -> list:
-        """the equations and their products with every unknown as equation ints over the quartic columns, expanded and multiplied on
-        the device (needs the GPU); zero rows are dropped"""
-        from . import hip                              # noqa: PLC0415
-        terms = self._terms(zeros)
-        if not len(terms[0]):
-            return []
-        return _eqs_from_words(hip.xl4_cubic_expand_words(hip.cubic_expand_words(*terms, self._lin_size), self._lin_size), xl4_cols(self._lin_size))
-
-    def _raw_point(self, lin: int) -> int:
-        """the raw point over the cubic columns whose linear part is ``lin``"""
-        n = self._lin_size
-        pi, pj, ti, tj, tl = self._xl_index(n)
-        x = np.array([(lin >> i) & 1 for i in range(n)], dtype=np.uint8)
-        bits = np.concatenate([x, x[pi] & x[pj], x[ti] & x[tj] & x[tl]])
-        return int.from_bytes(np.packbits(bits, bitorder="little").tobytes(), "little")
-
-    def evaluate(self, bv, sol: tuple) -> int:
-        raw = _raw_value(sol, self._sizes)
-        return bv.evaluate(self._raw_point(raw) if isinstance(bv, PackedCubicBitVec) else raw)
-
-
-for _name in ("get_rows", "_stack_rows", "_flat_rows", "factor", "bit_assert", "_solve_internal_rhs", "solve_raw_one_rhs", "solve_raw_space_rhs",
-              "solve_one_rhs"):
-    setattr(PackedCubicSystem, _name, _refuse_system(_name))
-del _name
-
-
-class PackedCubicGuessSystem(PackedCubicSystem):
-    """A PackedCubicSystem with the hybrid form of degree-4 XL.  The ``*_xl4_guess`` methods have the meaning and the guess parsing of
-    the quadratic classes': f unknowns are fixed in all 2^f ways, the device substitutes them into the expanded cubic rows and solves
-    every assignment's degree-4 XL system in the other n - f unknowns as one batch.  Everything else is PackedCubicSystem's, whose set
-    of public names is fixed; the bits of either class work with the other."""
-
-    # -- _QuadraticPoints' methods over this class's staging, chunk function and solution tuple --------------------------------------
-    _parse_guess = _QuadraticPoints._parse_guess
-    _xl_guess_chunks = _QuadraticPoints._xl_guess_chunks
-    _scatter_guess = _QuadraticPoints._scatter_guess
-    _solve_all_xl_guess = _QuadraticPoints._solve_all_xl_guess
-    solve_raw_one_xl4_guess = _QuadraticPoints.solve_raw_one_xl4_guess
-    solve_raw_space_xl4_guess = _QuadraticPoints.solve_raw_space_xl4_guess
-    convert_sol_xl4_guess = _QuadraticPoints.convert_sol_xl4_guess
-    solve_one_xl4_guess = _QuadraticPoints.solve_one_xl4_guess
-
-    def solve_all_xl4_guess(self, zeros: Sequence, guess, *, max_dimension: int = 16, assignments=None):
-        """the consistent points of every assignment's degree-4 XL system (about cols4(n - f) / (n - f + 1) equations), in assignment
-        order and within an assignment in AffineSpace order; the assignments are solved a chunk at a time (hip.xl4_cubic_guess_chunk),
-        the next chunk when more is asked for"""
-        return self._solve_all_xl_guess(zeros, guess, max_dimension, assignments, 4)
-
-    def _solve_internal_xl4_guess(self, zeros: Sequence, guess: list, mode: int):
-        terms = self._terms(zeros)
-        return len(terms[0]), lambda first, count: m4ri_solve_xl4_guess_cubic_packed(*terms, self._lin_size, guess, first, count, mode)
-
-    def _xl_guess_chunk(self, degree: int):
-        from . import hip                              # noqa: PLC0415  (ctypes binding, first use only)
-        return hip.xl4_cubic_guess_chunk
-
-    def _guess_sol(self, full: int) -> tuple:
-        return self._convert_sol(full)                 # (this class has no block of product unknowns behind the generators')
-
-
-# ---- quartic systems kept factored -------------------------------------------------------------------------------------------------
-# One degree up again: a symbolic bit is a linear form plus products of two, of three and of four affine forms, and the rows over the
-# n + C(n,2) + C(n,3) + C(n,4) columns of degree-4 XL come into being on the device (k_quartic_expand, through
-# m4ri_solve_quartic_packed / hip.quartic_expand_words).  The columns of degree <= 3 are the cubic class's, so a product of two or of
-# three forms is the same equation int in both layouts.
 def _monomial_bit(members: tuple, n: int) -> int:
     """the bit, in an equation int over the quartic columns, of the monomial of these unknowns (descending, four at most): the
     unknowns, then per degree the combinatorial number C(i,k) + C(j,k-1) + ... of its members"""
@@ -954,12 +728,73 @@ _CUBIC_MIX = ("a PackedQuarticBitVec cannot be mixed with a PackedCubicBitVec: t
               "not promoted; write the bits of one system with that system's mul_bit")
 
 
-class PackedQuarticBitVec(_TermsBitVec):
-    """``_TermsBitVec`` with products of two affine forms (``_off2``, ``_ta`` / ``_tb``), of three (``_off3``, ``_ua`` / ``_ub`` /
-    ``_uc``) and of four (``_off4``, ``_va`` / ``_vb`` / ``_vc`` / ``_vd``).  A product is the exact product in
-    GF(2)[x] / (x_i^2 + x_i)."""
+class _ExactBitVec(_TermsBitVec):
+    """``_TermsBitVec`` whose products are the exact products in GF(2)[x] / (x_i^2 + x_i), of as many affine forms as ``_ARITIES`` says;
+    ``_cols(n)``: the columns its bits expand over; ``_REFUSED``: the other kinds of vector, each with the text it is refused with."""
+    __slots__ = ()
+    _REFUSED: tuple = ()
+    _PRODUCT = {2: _exact_product_int, 3: _exact_product_int, 4: _exact_product4_int}
+
+    def _degree(self) -> int:
+        """structural: the highest arity the bits have terms of, 1 with none"""
+        return next((arity for arity, (_, ops) in zip(self._ARITIES[::-1], self._groups[::-1]) if len(ops[0])), 1)
+
+    def _coerce(self, other, what: str):
+        if not isinstance(other, type(self)):
+            for cls, text in self._REFUSED:
+                if isinstance(other, cls):
+                    raise TypeError(text)
+            if not isinstance(other, PackedBitVec):
+                if isinstance(other, BitVec):
+                    raise TypeError("cannot mix packed and tuple-of-int BitVecs")
+                raise TypeError(f"{what} needs a {type(self).__name__} or a PackedBitVec")
+            other = self._from_rows(other._rows, self._n)
+        if other._lin.shape[1] != self._lin.shape[1] or other._n != self._n:
+            raise ValueError("Cannot mix bitvecs over different numbers of unknowns")
+        return other
+
+    def _eq_ints(self) -> list:
+        """every bit as an equation int over the columns of its kind, expanded on the host a product at a time"""
+        n = self._n
+        ints = lambda rows: [int.from_bytes(r.tobytes(), "little") & ((1 << (n + 1)) - 1) for r in rows]      # noqa: E731
+        out = ints(self._lin)
+        for arity, (off, ops) in zip(self._ARITIES, self._groups):
+            forms = list(zip(*[ints(x) for x in ops]))
+            for k in range(len(out)):
+                for t in range(off[k], off[k + 1]):
+                    out[k] ^= self._PRODUCT[arity](forms[t], n)
+        return out
+
+    def evaluate(self, s: int) -> int:
+        """Value under the raw point ``s`` over the columns of its kind (bit c = column c: the n unknowns, their pairs, their triples
+        and, quartic, their quadruples), as BitVec.evaluate gives it for the expanded bits; on the host."""
+        point = ((s << 1) | 1) & ((1 << (self._cols(self._n) + 1)) - 1)
+        return sum((bin(e & point).count("1") & 1) << k for k, e in enumerate(self._eq_ints()))
+
+
+class PackedCubicBitVec(_ExactBitVec):
+    """``_ExactBitVec`` with products of two affine forms (bit i owns the operand rows ``_off2[i] .. _off2[i + 1]`` of ``_ta`` /
+    ``_tb``) and products of three (``_off3``, ``_ua`` / ``_ub`` / ``_uc``)."""
+    __slots__ = ()
+    _ARITIES = (2, 3)
+    _cols = staticmethod(xl3_cols)
+    _REFUSED = ((PackedQuadBitVec, _QUAD_MIX),)
+    _off2, _ta, _tb = _part(0), _part(0, 0), _part(0, 1)
+    _off3, _ua, _ub, _uc = _part(1), _part(1, 0), _part(1, 1), _part(1, 2)
+
+    def __init__(self, lin, off2, ta, tb, off3, ua, ub, uc, n: int):
+        # [k, Wl] uint64, then [k + 1] int64, [T2, Wl] x 2 and [k + 1] int64, [T3, Wl] x 3: immutable
+        self._lin, self._groups = lin, ((off2, (ta, tb)), (off3, (ua, ub, uc)))
+        self._n = n                                    # unknowns of the system
+
+
+class PackedQuarticBitVec(_ExactBitVec):
+    """``_ExactBitVec`` with products of two affine forms (``_off2``, ``_ta`` / ``_tb``), of three (``_off3``, ``_ua`` / ``_ub`` /
+    ``_uc``) and of four (``_off4``, ``_va`` / ``_vb`` / ``_vc`` / ``_vd``)."""
     __slots__ = ()
     _ARITIES = (2, 3, 4)
+    _cols = staticmethod(xl4_cols)
+    _REFUSED = ((PackedQuadBitVec, _QUAD_MIX), (PackedCubicBitVec, _CUBIC_MIX))
     _off2, _ta, _tb = _part(0), _part(0, 0), _part(0, 1)
     _off3, _ua, _ub, _uc = _part(1), _part(1, 0), _part(1, 1), _part(1, 2)
     _off4, _va, _vb, _vc, _vd = _part(2), _part(2, 0), _part(2, 1), _part(2, 2), _part(2, 3)
@@ -969,118 +804,81 @@ class PackedQuarticBitVec(_TermsBitVec):
         self._lin, self._groups = lin, ((off2, (ta, tb)), (off3, (ua, ub, uc)), (off4, (va, vb, vc, vd)))
         self._n = n                                    # unknowns of the system
 
-    def _degree(self) -> int:
-        return next((arity for arity, (_, ops) in zip((4, 3, 2), self._groups[::-1]) if len(ops[0])), 1)
 
-    def _coerce(self, other, what: str) -> "PackedQuarticBitVec":
-        if not isinstance(other, PackedQuarticBitVec):
-            if isinstance(other, PackedQuadBitVec):
-                raise TypeError(_QUAD_MIX)
-            if isinstance(other, PackedCubicBitVec):
-                raise TypeError(_CUBIC_MIX)
-            if not isinstance(other, PackedBitVec):
-                if isinstance(other, BitVec):
-                    raise TypeError("cannot mix packed and tuple-of-int BitVecs")
-                raise TypeError(f"{what} needs a PackedQuarticBitVec or a PackedBitVec")
-            other = self._from_rows(other._rows, self._n)
-        if other._lin.shape[1] != self._lin.shape[1] or other._n != self._n:
-            raise ValueError("Cannot mix bitvecs over different numbers of unknowns")
-        return other
-
-    def _eq_ints(self) -> list:
-        """every bit as an equation int over the quartic columns, expanded on the host a product at a time"""
-        n = self._n
-        ints = lambda rows: [int.from_bytes(r.tobytes(), "little") & ((1 << (n + 1)) - 1) for r in rows]      # noqa: E731
-        out = ints(self._lin)
-        for (off, ops), product in zip(self._groups, (_exact_product_int, _exact_product_int, _exact_product4_int)):
-            forms = list(zip(*[ints(x) for x in ops]))
-            for k in range(len(out)):
-                for t in range(off[k], off[k + 1]):
-                    out[k] ^= product(forms[t], n)
-        return out
-
-    def evaluate(self, s: int) -> int:
-        """Value under the raw point ``s`` over the quartic columns (bit c = column c: the n unknowns, their pairs, triples and
-        quadruples), as BitVec.evaluate gives it for the expanded bits; on the host."""
-        point = ((s << 1) | 1) & ((1 << (xl4_cols(self._n) + 1)) - 1)
-        return sum((bin(e & point).count("1") & 1) << k for k, e in enumerate(self._eq_ints()))
+def _refuse_system(name: str):
+    def method(self, *args, **kwargs):
+        raise TypeError(f"{name} is not built for a Packed{self._KIND.capitalize()}System")
+    method.__name__ = name
+    return method
 
 
-class PackedQuarticSystem(PackedLinearSystem):
-    """Equations of degree <= 4 written directly and kept factored: ``gens()`` are PackedLinearSystem's PackedBitVecs, ``mul_bit``
-    multiplies single bits up to degree 4 (exact products), and the solve methods hand the factored arrays to the device, which
-    expands them over the n + C(n,2) + C(n,3) + C(n,4) columns of degree-4 XL and solves.  ``solve_all`` keeps the points of the
-    linearised space whose pair, triple and quadruple coordinates are the products of their linear bits.  Not a PackedCubicSystem:
-    its columns differ, and the searches over cubic spaces take anything that is one."""
+class _ExactSystem(_ProductColumns, PackedLinearSystem):
+    """Equations up to the degree of ``_VEC`` (its highest arity) written directly and kept factored: ``gens()`` are PackedLinearSystem's
+    PackedBitVecs, ``mul_bit`` multiplies single bits up to that degree (exact products), and the solve methods hand the factored
+    arrays to the device (``_SOLVE``), which expands them over ``_VEC._cols`` columns and solves.  ``solve_all`` keeps the points of the
+    linearised space whose product coordinates are the products of their linear bits.  ``_KIND``: "cubic" / "quartic"."""
 
     def __init__(self, sizes: Iterable[int]):
         super().__init__(sizes)
         self._lin_size = sum(self._sizes)
-        self._cols = xl4_cols(self._lin_size)          # (``_words`` stays the words of a linear form: the generators have no product coordinates)
+        self._cols = self._VEC._cols(self._lin_size)   # (``_words`` stays the words of a linear form: the generators have no product coordinates)
 
-    _xl_index = _QuadraticPoints._xl_index
-    _xl4_index = _QuadraticPoints._xl4_index
-    _xl_products_match = _QuadraticPoints._xl_products_match
-
-    def _single(self, a) -> PackedQuarticBitVec:
-        if isinstance(a, PackedQuadBitVec):
-            raise TypeError(_QUAD_MIX)
-        if isinstance(a, PackedCubicBitVec):
-            raise TypeError(_CUBIC_MIX)
-        if not isinstance(a, (PackedBitVec, PackedQuarticBitVec)):
-            raise TypeError("mul_bit needs PackedBitVecs or PackedQuarticBitVecs of this system")
+    def _single(self, a):
+        for cls, text in self._VEC._REFUSED:
+            if isinstance(a, cls):
+                raise TypeError(text)
+        if not isinstance(a, (PackedBitVec, self._VEC)):
+            raise TypeError(f"mul_bit needs PackedBitVecs or {self._VEC.__name__}s of this system")
         if len(a) != 1:
             raise ValueError("The inputs should be single bits")
         rows = a._rows if isinstance(a, PackedBitVec) else a._lin
         if rows.shape[1] != self._words:
             raise ValueError("Cannot mix bitvecs over different numbers of unknowns")
-        return PackedQuarticBitVec._from_rows(rows, self._lin_size) if isinstance(a, PackedBitVec) else a
+        return self._VEC._from_rows(rows, self._lin_size) if isinstance(a, PackedBitVec) else a
 
-    def mul_bit(self, a, b) -> PackedQuarticBitVec:
-        """the exact product of two single bits whose degrees (structural: the highest arity a bit has terms of) add up to 4 at most.
-        By distributivity lin_a lin_b is one quadratic term, a product of either bit times the other's linear form one term of the
-        next arity (the form appended as one more operand), and two products of two forms one quartic term."""
+    def mul_bit(self, a, b):
+        """the exact product of two single bits whose degrees (structural: the highest arity a bit has terms of) add up to the
+        system's at most.  By distributivity lin_a lin_b is one quadratic term, a product of either bit times the other's linear form
+        one term of the next arity (the form appended as one more operand), and two products of two forms one quartic term."""
         a, b = self._single(a), self._single(b)
-        da, db = a._degree(), b._degree()
-        if da + db > 4:
-            raise TypeError(f"mul_bit of bits of degree {da} and {db} is of degree {da + db}, above 4")
-        (_, a2), (_, a3), _ = a._groups                # (a term of a's and one of b's whose arities add up to more than 4 cannot both exist)
-        (_, b2), (_, b3), _ = b._groups
+        da, db, degree = a._degree(), b._degree(), self._VEC._ARITIES[-1]
+        if da + db > degree:
+            raise TypeError(f"mul_bit of bits of degree {da} and {db} is of degree {da + db}, above {degree}")
+        a2, b2 = a._groups[0][1], b._groups[0][1]      # (a term of a's and one of b's whose arities add up to more than the degree cannot both exist)
         by = lambda ops, form: ops + (np.repeat(form, len(ops[0]), axis=0),)                      # noqa: E731
         cat = lambda *groups: [np.concatenate(xs) for xs in zip(*groups)]                          # noqa: E731
-        ia, ib = np.repeat(np.arange(len(a2[0])), len(b2[0])), np.tile(np.arange(len(b2[0])), len(a2[0]))      # every pair of quadratic terms
-        cubic = cat(by(a2, b._lin), by(b2, a._lin))
-        quartic = cat(by(a3, b._lin), by(b3, a._lin), (a2[0][ia], a2[1][ia], b2[0][ib], b2[1][ib]))
-        one = lambda k: np.array([0, k], dtype=np.int64)                                            # noqa: E731
-        return PackedQuarticBitVec(np.zeros((1, self._words), dtype=np.uint64), one(1), a._lin, b._lin, one(len(cubic[0])), *cubic,
-                                   one(len(quartic[0])), *quartic, self._lin_size)
+        groups = [[a._lin, b._lin], cat(by(a2, b._lin), by(b2, a._lin))]
+        if degree == 4:
+            a3, b3 = a._groups[1][1], b._groups[1][1]
+            ia, ib = np.repeat(np.arange(len(a2[0])), len(b2[0])), np.tile(np.arange(len(b2[0])), len(a2[0]))      # every pair of quadratic terms
+            groups.append(cat(by(a3, b._lin), by(b3, a._lin), (a2[0][ia], a2[1][ia], b2[0][ib], b2[1][ib])))
+        parts = [x for ops in groups for x in (np.array([0, len(ops[0])], dtype=np.int64), *ops)]
+        return self._VEC(np.zeros((1, self._words), dtype=np.uint64), *parts, self._lin_size)
 
     # -- zeros -> the factored arrays the device expands ----------------------------------------------------------------------------
     def _terms(self, zeros: Sequence):
-        """(lin, off2, ta, tb, off3, ua, ub, uc, off4, va, vb, vc, vd) of all the bits of ``zeros``, in order; no row is dropped
-        (_zeros_terms)"""
-        if any(isinstance(z, PackedCubicBitVec) for z in zeros):
-            raise TypeError(_CUBIC_MIX)
-        return _zeros_terms(zeros, PackedQuarticBitVec, "quartic", self._words)
+        """(lin, then per arity its offsets and its operand arrays: off2, ta, tb, off3, ua, ub, uc ...) of all the bits of ``zeros``, in
+        order; no row is dropped (_zeros_terms)"""
+        return _zeros_terms(zeros, self._VEC, self._KIND, self._words)
 
     def get_eqs(self, zeros: Sequence) -> list:
-        """equation ints over the quartic columns, expanded on the device (needs the GPU); zero rows are dropped"""
+        """equation ints over the system's columns, expanded on the device (needs the GPU); zero rows are dropped"""
         from . import hip                              # noqa: PLC0415  (ctypes binding, first use only)
         terms = self._terms(zeros)
         if not len(terms[0]):
             return []
-        return _eqs_from_words(hip.quartic_expand_words(*terms, self._lin_size), self._cols)
+        return _eqs_from_words(getattr(hip, f"{self._KIND}_expand_words")(*terms, self._lin_size), self._cols)
 
     # -- boundary call ---------------------------------------------------------------------------------------------------------------
     def _solve_internal(self, zeros: Sequence, mode: int):
         terms = self._terms(zeros)
-        return m4ri_solve_quartic_packed(*terms, self._lin_size, max(len(terms[0]), self._cols), mode)      # (the boundary wants rows >= cols)
+        return self._SOLVE(*terms, self._lin_size, max(len(terms[0]), self._cols), mode)      # (the boundary wants rows >= cols)
 
     def convert_sol(self, s: int) -> Optional[tuple]:
-        """the values of the generators at a raw point over the quartic columns whose pair, triple and quadruple coordinates are the
-        products of its linear bits, None for any other point"""
+        """the values of the generators at a raw point over the system's columns whose product coordinates are the products of its
+        linear bits, None for any other point"""
         n = self._lin_size
-        if not self._xl_products_match(s, n, 4):
+        if not self._xl_products_match(s, n, self._VEC._ARITIES[-1]):
             return None
         return self._convert_sol(s & ((1 << n) - 1))
 
@@ -1091,20 +889,95 @@ class PackedQuarticSystem(PackedLinearSystem):
         return None
 
     def _raw_point(self, lin: int) -> int:
-        """the raw point over the quartic columns whose linear part is ``lin``"""
+        """the raw point over the system's columns whose linear part is ``lin``"""
         n = self._lin_size
         pi, pj, ti, tj, tl = self._xl_index(n)
-        qi, qj, ql, qp = self._xl4_index(n)
         x = np.array([(lin >> i) & 1 for i in range(n)], dtype=np.uint8)
-        bits = np.concatenate([x, x[pi] & x[pj], x[ti] & x[tj] & x[tl], x[qi] & x[qj] & x[ql] & x[qp]])
-        return int.from_bytes(np.packbits(bits, bitorder="little").tobytes(), "little")
+        bits = [x, x[pi] & x[pj], x[ti] & x[tj] & x[tl]]
+        if self._VEC._ARITIES[-1] == 4:
+            qi, qj, ql, qp = self._xl4_index(n)
+            bits.append(x[qi] & x[qj] & x[ql] & x[qp])
+        return int.from_bytes(np.packbits(np.concatenate(bits), bitorder="little").tobytes(), "little")
 
     def evaluate(self, bv, sol: tuple) -> int:
         raw = _raw_value(sol, self._sizes)
-        return bv.evaluate(self._raw_point(raw) if isinstance(bv, PackedQuarticBitVec) else raw)
+        return bv.evaluate(self._raw_point(raw) if isinstance(bv, self._VEC) else raw)
 
 
 for _name in ("get_rows", "_stack_rows", "_flat_rows", "factor", "bit_assert", "_solve_internal_rhs", "solve_raw_one_rhs", "solve_raw_space_rhs",
               "solve_one_rhs"):
-    setattr(PackedQuarticSystem, _name, _refuse_system(_name, "PackedQuarticSystem"))
+    setattr(_ExactSystem, _name, _refuse_system(_name))
 del _name
+
+
+class PackedCubicSystem(_ExactSystem):
+    """``_ExactSystem`` of degree 3, over the n + C(n,2) + C(n,3) columns of degree-3 XL.  The ``*_xl4`` methods are degree-4 XL: the
+    device multiplies every expanded equation by 1 and by each unknown too and solves over the n + C(n,2) + C(n,3) + C(n,4) monomials
+    of degree <= 4, which takes about C(n,3) / 4 equations where plain linearisation takes about C(n,3).  Its hybrid form, which
+    guesses unknowns, is PackedCubicGuessSystem's."""
+    _VEC, _KIND, _SOLVE = PackedCubicBitVec, "cubic", staticmethod(m4ri_solve_cubic_packed)
+
+    # -- degree-4 XL: the factored arrays go down, the device expands, multiplies by 1 and by every unknown, pads and solves ----------
+    def _solve_internal_xl4(self, zeros: Sequence, mode: int):
+        return m4ri_solve_xl4_cubic_packed(*self._terms(zeros), self._lin_size, mode)
+
+    def solve_raw_one_xl4(self, zeros: Sequence):
+        return self._solve_internal_xl4(zeros, 0)
+
+    def solve_raw_space_xl4(self, zeros: Sequence):
+        return self._solve_internal_xl4(zeros, 1)
+
+    def convert_sol_xl4(self, s: int) -> Optional[tuple]:
+        """convert_sol over the quartic columns: the quadruple coordinates are checked too"""
+        n = self._lin_size
+        if not self._xl_products_match(s, n, 4):
+            return None
+        return self._convert_sol(s & ((1 << n) - 1))
+
+    def solve_all_xl4(self, zeros: Sequence, *, max_dimension: int = 16):
+        """solve_all through degree-4 XL: the consistent points of the quartic system's solution space, in AffineSpace order"""
+        yield from _space_points(self.solve_raw_space_xl4(zeros), max_dimension, self.convert_sol_xl4)
+
+    def solve_one_xl4(self, zeros: Sequence):
+        for sol in self.solve_all_xl4(zeros):
+            return sol
+        return None
+
+    def get_eqs_xl4(self, zeros: Sequence) -> list:
+        """the equations and their products with every unknown as equation ints over the quartic columns, expanded and multiplied on
+        the device (needs the GPU); zero rows are dropped"""
+        from . import hip                              # noqa: PLC0415
+        terms = self._terms(zeros)
+        if not len(terms[0]):
+            return []
+        return _eqs_from_words(hip.xl4_cubic_expand_words(hip.cubic_expand_words(*terms, self._lin_size), self._lin_size), xl4_cols(self._lin_size))
+
+
+class PackedCubicGuessSystem(_XlGuess, PackedCubicSystem):
+    """A PackedCubicSystem with the hybrid form of degree-4 XL.  The ``*_xl4_guess`` methods have the meaning and the guess parsing of
+    the quadratic classes' (_XlGuess): f unknowns are fixed in all 2^f ways, the device substitutes them into the expanded cubic rows
+    and solves every assignment's degree-4 XL system in the other n - f unknowns (about cols4(n - f) / (n - f + 1) equations) as one
+    batch, a chunk of assignments at a time (hip.xl4_cubic_guess_chunk).  Everything else is PackedCubicSystem's, whose set of public
+    names is fixed; the bits of either class work with the other."""
+
+    def _solve_internal_xl4_guess(self, zeros: Sequence, guess: list, mode: int):
+        terms = self._terms(zeros)
+        return len(terms[0]), lambda first, count: m4ri_solve_xl4_guess_cubic_packed(*terms, self._lin_size, guess, first, count, mode)
+
+    def _xl_guess_chunk(self, degree: int):
+        from . import hip                              # noqa: PLC0415  (ctypes binding, first use only)
+        return hip.xl4_cubic_guess_chunk
+
+    def _guess_sol(self, full: int) -> tuple:
+        return self._convert_sol(full)                 # (this class has no block of product unknowns behind the generators')
+
+
+class PackedQuarticSystem(_ExactSystem):
+    """``_ExactSystem`` of degree 4, over the n + C(n,2) + C(n,3) + C(n,4) columns of degree-4 XL.  Not a PackedCubicSystem: its columns
+    differ, and the searches over cubic spaces take anything that is one."""
+    _VEC, _KIND, _SOLVE = PackedQuarticBitVec, "quartic", staticmethod(m4ri_solve_quartic_packed)
+
+    def _terms(self, zeros: Sequence):
+        if any(isinstance(z, PackedCubicBitVec) for z in zeros):
+            raise TypeError(_CUBIC_MIX)
+        return super()._terms(zeros)
