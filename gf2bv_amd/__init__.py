@@ -10,6 +10,7 @@ from ._internal import AffineSpace, eqs_to_sage_mat_helper, m4ri_solve, mul_bit_
 from .bitvec import BitVec
 from .linsys import DimensionTooLargeError, LinearSystem, QuadraticSystem, Zeros
 from .search import search_all_cubic, search_all_xl, search_one_cubic, search_one_xl
+from .search4 import search_all_quartic, search_all_xl4, search_one_quartic, search_one_xl4
 
 
 def __getattr__(name):
@@ -27,6 +28,7 @@ __all__ = [
     "AffineSpace", "BitVec", "DimensionTooLargeError", "LinearSystem", "PackedBitVec", "PackedCubicBitVec", "PackedCubicGuessSystem",
     "PackedCubicSystem", "PackedLinearSystem",
     "PackedQuadBitVec", "PackedQuadraticSystem", "PackedQuarticBitVec", "PackedQuarticSystem", "QuadraticSystem", "Zeros",
-    "eqs_to_sage_mat_helper", "m4ri_solve", "mul_bit_quad", "search_all_cubic", "search_all_xl", "search_one_cubic", "search_one_xl",
+    "eqs_to_sage_mat_helper", "m4ri_solve", "mul_bit_quad", "search_all_cubic", "search_all_quartic", "search_all_xl",
+    "search_all_xl4", "search_one_cubic", "search_one_quartic", "search_one_xl", "search_one_xl4",
     "to_bits", "tuple_where", "xor_tuple",
 ]

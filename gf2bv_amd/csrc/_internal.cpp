@@ -242,8 +242,10 @@ PyObject *iter_next_slow(SpaceIterObject *self)
 
 PyObject *QuadGaveUp;      // _internal.QuadSearchGaveUp(message, lin_rank)
 PyObject *CubicGaveUp;     // _internal.CubicSearchGaveUp(message, lin_rank)
+PyObject *QuarticGaveUp;   // _internal.QuarticSearchGaveUp(message, lin_rank)
 PyObject *space_quad_search(AffineSpaceObject *self, PyObject *const *args, Py_ssize_t nargs);
 PyObject *space_cubic_search(AffineSpaceObject *self, PyObject *const *args, Py_ssize_t nargs);
+PyObject *space_quartic_search(AffineSpaceObject *self, PyObject *const *args, Py_ssize_t nargs);
 
 PyGetSetDef space_getset[] = {
 	{"dimension", (getter)space_dimension, nullptr, "Dimension of the affine space", nullptr},
@@ -262,6 +264,9 @@ PyMethodDef space_methods[] = {
 	{"cubic_search", (PyCFunction)(void (*)(void))space_cubic_search, METH_FASTCALL,
 	 "cubic_search(n_lin, max_enum=32, max_solutions=65536, first=False)\n--\n\nquad_search for a space over the degree-3 columns (pair "
 	 "and triple coordinates = products of the n_lin linear bits): degree-3 XL's and PackedCubicSystem's; not in the reference."},
+	{"quartic_search", (PyCFunction)(void (*)(void))space_quartic_search, METH_FASTCALL,
+	 "quartic_search(n_lin, max_enum=32, max_solutions=65536, first=False)\n--\n\nquad_search for a space over the degree-4 columns (pair, "
+	 "triple and quadruple coordinates = products of the n_lin linear bits): degree-4 XL's and PackedQuarticSystem's; not in the reference."},
 	{nullptr, nullptr, 0, nullptr}};
 
 PyType_Slot space_slots[] = {
@@ -1782,12 +1787,15 @@ PyObject *py_sage_helper(PyObject *, PyObject *const *args, Py_ssize_t nargs)
 // AffineSpace.quad_search(n_lin, max_enum=32, max_solutions=65536, first=False): the consistent points of the space (every
 // product coordinate the product of its linear bits), in iteration order, found on the device (gf2bv_quad_search_alloc).
 // More than max_solutions points: ValueError -- or, with first=True, the first max_solutions of them.  Not in the reference.
-// AffineSpace.cubic_search: the same over the degree-3 columns (gf2bv_cubic_search_alloc), CubicSearchGaveUp when it gives up.
-PyObject *space_search(AffineSpaceObject *self, PyObject *const *args, Py_ssize_t nargs, bool cubic)
+// AffineSpace.cubic_search, AffineSpace.quartic_search: the same over the degree-3 and the degree-4 columns (gf2bv_cubic_search_alloc,
+// gf2bv_quartic_search_alloc), CubicSearchGaveUp / QuarticSearchGaveUp when it gives up.
+PyObject *space_search(AffineSpaceObject *self, PyObject *const *args, Py_ssize_t nargs, int degree)
 {
+	const bool cubic = degree >= 3;               // (the texts the degrees above 2 share)
+	const auto entry = degree == 4 ? gf2bv_quartic_search_alloc : degree == 3 ? gf2bv_cubic_search_alloc : gf2bv_quad_search_alloc;
+	const char *name = degree == 4 ? "quartic_search" : degree == 3 ? "cubic_search" : "quad_search";
 	if (nargs < 1 || nargs > 4) {
-		PyErr_SetString(PyExc_TypeError, cubic ? "cubic_search(n_lin, max_enum=32, max_solutions=65536, first=False)"
-		                                       : "quad_search(n_lin, max_enum=32, max_solutions=65536, first=False)");
+		PyErr_Format(PyExc_TypeError, "%s(n_lin, max_enum=32, max_solutions=65536, first=False)", name);
 		return nullptr;
 	}
 	const long long n_lin = PyLong_AsLongLong(args[0]);
@@ -1803,8 +1811,7 @@ PyObject *space_search(AffineSpaceObject *self, PyObject *const *args, Py_ssize_
 	uint64_t *pts = nullptr;                  // exactly min(count, max_solutions) points, owned by the library
 	int rc;
 	Py_BEGIN_ALLOW_THREADS
-	rc = (cubic ? gf2bv_cubic_search_alloc : gf2bv_quad_search_alloc)(self->origin, self->basis, self->dim, self->words, n_lin,
-	                                                                  (int)max_enum, max_sol, device, &count, &lin_rank, &pts);
+	rc = entry(self->origin, self->basis, self->dim, self->words, n_lin, (int)max_enum, max_sol, device, &count, &lin_rank, &pts);
 	Py_END_ALLOW_THREADS
 	if (rc == GF2BV_ERR_NOMEM && count > max_sol) {     // more than 2^22 points: too many to order
 		gf2bv_quad_free(pts);
@@ -1815,7 +1822,7 @@ PyObject *space_search(AffineSpaceObject *self, PyObject *const *args, Py_ssize_
 			PyErr_Format(PyExc_ValueError, "%lld consistent points, more than max_solutions (%lld)", (long long)count, max_sol);
 		return nullptr;
 	}
-	if (rc != GF2BV_OK) { gf2bv_quad_free(pts); return raise_rc(rc, cubic ? "cubic_search" : "quad_search"); }
+	if (rc != GF2BV_OK) { gf2bv_quad_free(pts); return raise_rc(rc, name); }
 	if (count < 0) {
 		gf2bv_quad_free(pts);
 		PyObject *msg = PyUnicode_FromFormat(cubic ? "the search gave up: the space's projection onto the %lld linear coordinates has rank %lld, "
@@ -1825,7 +1832,7 @@ PyObject *space_search(AffineSpaceObject *self, PyObject *const *args, Py_ssize_
 		                                     n_lin, (long long)lin_rank, max_enum);
 		if (msg) {
 			PyObject *e = Py_BuildValue("(NL)", msg, (long long)lin_rank);
-			if (e) { PyErr_SetObject(cubic ? CubicGaveUp : QuadGaveUp, e); Py_DECREF(e); }
+			if (e) { PyErr_SetObject(degree == 4 ? QuarticGaveUp : degree == 3 ? CubicGaveUp : QuadGaveUp, e); Py_DECREF(e); }
 		}
 		return nullptr;
 	}
@@ -1845,8 +1852,9 @@ PyObject *space_search(AffineSpaceObject *self, PyObject *const *args, Py_ssize_
 	return t;
 }
 
-PyObject *space_quad_search(AffineSpaceObject *self, PyObject *const *args, Py_ssize_t nargs) { return space_search(self, args, nargs, false); }
-PyObject *space_cubic_search(AffineSpaceObject *self, PyObject *const *args, Py_ssize_t nargs) { return space_search(self, args, nargs, true); }
+PyObject *space_quad_search(AffineSpaceObject *self, PyObject *const *args, Py_ssize_t nargs) { return space_search(self, args, nargs, 2); }
+PyObject *space_cubic_search(AffineSpaceObject *self, PyObject *const *args, Py_ssize_t nargs) { return space_search(self, args, nargs, 3); }
+PyObject *space_quartic_search(AffineSpaceObject *self, PyObject *const *args, Py_ssize_t nargs) { return space_search(self, args, nargs, 4); }
 
 // _space_from_ints(cols, origin, basis): build an AffineSpace from host integers.  Not part of the
 // reference surface; lets the CPU test-suite exercise get()/iteration order without a GPU.
@@ -1976,8 +1984,11 @@ PyMODINIT_FUNC PyInit__internal(void)
 	if (!QuadGaveUp) { Py_DECREF(m); return nullptr; }
 	CubicGaveUp = PyErr_NewException("_internal.CubicSearchGaveUp", PyExc_RuntimeError, nullptr);
 	if (!CubicGaveUp) { Py_DECREF(m); return nullptr; }
-	Py_INCREF(QuadGaveUp); Py_INCREF(CubicGaveUp);
+	QuarticGaveUp = PyErr_NewException("_internal.QuarticSearchGaveUp", PyExc_RuntimeError, nullptr);
+	if (!QuarticGaveUp) { Py_DECREF(m); return nullptr; }
+	Py_INCREF(QuadGaveUp); Py_INCREF(CubicGaveUp); Py_INCREF(QuarticGaveUp);
 	if (PyModule_AddObject(m, "QuadSearchGaveUp", QuadGaveUp) < 0 || PyModule_AddObject(m, "CubicSearchGaveUp", CubicGaveUp) < 0 ||
+	    PyModule_AddObject(m, "QuarticSearchGaveUp", QuarticGaveUp) < 0 ||
 	    PyModule_AddObject(m, "AffineSpace", (PyObject *)AffineSpace_Type) < 0 ||
 	    PyModule_AddObject(m, "Factorization", (PyObject *)Factorization_Type) < 0 ||
 	    PyModule_AddObject(m, "AffineSpaceIterator", (PyObject *)SpaceIterGray_Type) < 0 ||

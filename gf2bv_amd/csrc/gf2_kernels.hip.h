@@ -5976,3 +5976,259 @@ k_cubic_check(const u64 *__restrict__ E, i64 m, int R, const u64 *__restrict__ c
 		}
 	}
 }
+
+
+// ==========================================================================================
+// QUARTIC SEARCH: the consistent points of a solution space over the degree-4 columns
+// ==========================================================================================
+// (host side and the mathematics: gf2bv_quartic_search in gf2_solver.hip)
+//
+// A quartic form over R <= 64 unknowns is the cubic layout followed by the quadruple block: the product of unknowns p < l < j < i is
+// bit 1 + R + C(R,2) + C(R,3) + C(i,4) + C(j,3) + C(l,2) + p -- the equation int of a PackedQuarticSystem of R unknowns.  In every
+// block a monomial with members m_0 < m_1 < ... lies at the block's start + SUM_t C(m_t, t + 1) (qs_c, qs_off).
+//
+// k_quartic_products: k_cubic_products with up to four operands (members mem[4 s ..], -1 where a coordinate has fewer) and the
+// fourth block: at most 16 subsets of 4 parities each in the Moebius sum.  F_t = XOR of v_s over a support is k_cubic_forms itself.
+__device__ __forceinline__ i64 qs_c(int h, int t)        // C(h, t), t = 1..4
+{
+	i64 c = h;
+	if (t >= 2) c = c * (h - 1) / 2;
+	if (t >= 3) c = c * (h - 2) / 3;
+	if (t >= 4) c = c * (h - 3) / 4;
+	return c;
+}
+__device__ __forceinline__ i64 qs_off(int R, int size)   // where the monomials of `size` members start in a form (or in the search table)
+{
+	i64 o = size ? 1 : 0;
+	if (size >= 2) o += R;
+	if (size >= 3) o += qs_c(R, 2);
+	if (size >= 4) o += qs_c(R, 3);
+	return o;
+}
+__global__ void __launch_bounds__(256)
+k_quartic_products(const u64 *__restrict__ lin, const u64 *__restrict__ qaff, const int *__restrict__ mem, int R, int W, int fw,
+                   u64 *__restrict__ V)
+{
+	__shared__ u64 ops[4][2];
+	const i64 s = blockIdx.x;
+	const int nf = mem[4 * s + 3] >= 0 ? 4 : mem[4 * s + 2] >= 0 ? 3 : 2;
+	if (threadIdx.x < 8) {
+		const int f = threadIdx.x >> 1, w = threadIdx.x & 1;
+		ops[f][w] = (f < nf && w < W) ? lin[(i64)mem[4 * s + f] * W + w] : 0;
+	}
+	__syncthreads();
+	const int o2 = (int)qs_off(R, 2), o3 = (int)qs_off(R, 3), o4 = (int)qs_off(R, 4), nbits = o4 + (int)qs_c(R, 4);
+	for (int w = threadIdx.x; w < fw; w += blockDim.x) {
+		int q = w * 64, kind, a = 0, b = 0, c = 0, d = 0;     // the monomial of bit q: kind members, a > b > c > d
+		if (q == 0) kind = 0;
+		else if (q < o2) { kind = 1; a = q - 1; }
+		else if (q < o3) { kind = 2; const int p = q - o2; a = (int)xl_tri_root(p); b = p - (int)xl_c2(a); }
+		else if (q < o4) {
+			kind = 3;
+			const int t = q - o3;
+			a = (int)xl_tet_root(t);
+			const int rem = t - (int)xl_c3(a);
+			b = (int)xl_tri_root(rem); c = rem - (int)xl_c2(b);
+		} else {
+			kind = 4;
+			const int u = q - o4;
+			a = (int)xl_quart_root(u);
+			const int rem = u - (int)xl_c4(a);
+			b = (int)xl_tet_root(rem);
+			const int rem2 = rem - (int)xl_c3(b);
+			c = (int)xl_tri_root(rem2); d = rem2 - (int)xl_c2(c);
+		}
+		u64 word = 0;
+		for (int k = 0; k < 64 && q < nbits; k++, q++) {
+			// bit 0 of fm: the form's constant; bits 1..kind: its coefficients at the monomial's members
+			unsigned fm[4];
+			for (int f = 0; f < 4; f++) {
+				unsigned x = (unsigned)(ops[f][0] & 1);
+				if (kind >= 1) x |= (unsigned)cf_bit(ops[f], a) << 1;
+				if (kind >= 2) x |= (unsigned)cf_bit(ops[f], b) << 2;
+				if (kind >= 3) x |= (unsigned)cf_bit(ops[f], c) << 3;
+				if (kind >= 4) x |= (unsigned)cf_bit(ops[f], d) << 4;
+				fm[f] = x;
+			}
+			unsigned coef = 0;
+			for (unsigned T = 0; T < (1u << kind); T++) {
+				const unsigned mask = 1u | (T << 1);
+				unsigned p = __popc(fm[0] & mask) & __popc(fm[1] & mask);
+				if (nf >= 3) p &= __popc(fm[2] & mask);
+				if (nf == 4) p &= __popc(fm[3] & mask);
+				coef ^= p;
+			}
+			word |= (u64)(coef & 1) << k;
+			if (kind == 0) { kind = 1; a = 0; }
+			else if (kind == 1) { if (++a == R) { kind = 2; a = 1; b = 0; } }
+			else if (kind == 2) { if (++b == a) { b = 0; if (++a == R) { kind = 3; a = 2; b = 1; c = 0; } } }
+			else if (kind == 3) { if (++c == b) { c = 0; if (++b == a) { b = 1; if (++a == R) { kind = 4; a = 3; b = 2; c = 1; d = 0; } } } }
+			else if (++d == c) { d = 0; if (++c == b) { c = 1; if (++b == a) { a++; b = 2; } } }
+		}
+		if (w < W) word ^= qaff[s * W + w];
+		V[s * (i64)fw + w] = word;
+	}
+}
+
+// k_quartic_check and the fused mode of k_quartic_search: E holds every form outside the first pass as
+// ew = 2 + R + C(R,2) + C(R,3) words: the layout of k_cubic_check followed by Q_{jkl} (j < k < l, at 2 + R + C(R,2) + C(l,3) + C(k,2) + j),
+// which has bit p > l set when the form has x_j x_k x_l x_p.  The value adds XOR_{j < k < l in y} par(Q_jkl & y) to the cubic one: one
+// popcount per set bit, pair and triple of y.
+__device__ __forceinline__ u64 quartic_form_value(const u64 *__restrict__ e, int R, u64 y)
+{
+	u64 acc = e[0] + (u64)__popcll(e[1] & y);
+	const u64 *U = e + 2, *T = U + R, *Q = T + R * (R - 1) / 2;
+	for (u64 bj = y; bj; bj &= bj - 1) {
+		const int j = ctz64(bj);
+		acc += (u64)__popcll(U[j] & y);
+		for (u64 bk = bj & (bj - 1); bk; bk &= bk - 1) {
+			const int k = ctz64(bk);
+			acc += (u64)__popcll(T[k * (k - 1) / 2 + j] & y);
+			for (u64 bl = bk & (bk - 1); bl; bl &= bl - 1) {
+				const int l = ctz64(bl);
+				acc += (u64)__popcll(Q[l * (l - 1) * (l - 2) / 6 + k * (k - 1) / 2 + j] & y);
+			}
+		}
+	}
+	return acc & 1;
+}
+// The fused test, by the whole wavefront (a form costs a popcount per triple of the candidate's set bits, far too much for one lane
+// while 63 wait): the lanes at a candidate (`hit`) take turns, the turn's point is read from its lane and the live lanes share the
+// m forms of E among them.  Returns whether this lane's own candidate is a common zero of all of them.  Called in uniform control
+// flow by every lane that has not left the kernel.
+__device__ __forceinline__ bool quartic_wave_vanish(const u64 *__restrict__ E, i64 m, int R, bool hit, u64 y)
+{
+	const i64 ew = 2 + R + R * (R - 1) / 2 + (i64)R * (R - 1) * (R - 2) / 6;
+	const int lane = threadIdx.x & 63;
+	const u64 live = __ballot(1);
+	const int rank = __popcll(live & ((1ull << lane) - 1)), nlive = __popcll(live);
+	bool ok = false;
+	for (u64 todo = __ballot(hit); todo; todo &= todo - 1) {
+		const int src = ctz64(todo);
+		const u64 p = ((u64)(unsigned)__builtin_amdgcn_readlane((int)(y >> 32), src) << 32) | (unsigned)__builtin_amdgcn_readlane((int)y, src);
+		u64 bad = 0;
+		for (i64 f = rank; f < m && !bad; f += nlive) bad = quartic_form_value(E + f * ew, R, p);
+		const bool none = __ballot(bad != 0) == 0;
+		if (lane == src) ok = none;
+	}
+	return ok;
+}
+
+// k_quartic_search: every common zero of 64 quartic forms in R <= 64 variables, bit-sliced (bit f of a word = form f).
+// tab: [K | Lw[R] | Sw[C(R,2)] | Tw[C(R,3)] | Qw[C(R,4)]], indexed like a form's bits.  Lane g fixes the high H = R - L variables to the
+// bits of g and walks the low L in Gray order; with k1 < k2 < k3 < k4 the four lowest set bits of the step index i, the same in every lane:
+//   d3[k1][k2][k3] ^= Qw[k1][k2][k3][k4] (k4 exists; a uniform load), d2[k1][k2] ^= d3[k1][k2][k3] (k3 exists),
+//   d1[k1] ^= d2[k1][k2] (k2 exists), v ^= d1[k1], zero test.
+// A table entry for the set K of ranks is the derivative of the lane's restricted form in the directions K, which does not depend on
+// the variables of K; between two uses exactly the next variable up flips.  It starts at its value at the point of its first use,
+// e_{k-1} summed over k in K (k >= 1, k - 1 not in K): the XOR of the coefficients of the monomials K + T over the sets T of at
+// most 4 - |K| of that point's variables and of the lane's high variables (qs_high runs over the high ones).
+// State: L + C(L,2) + C(L,3) words a lane in LDS, one column per thread (slot * blockDim + tid); one wavefront per workgroup.
+// Appends, `cap` and the fused mode with E != nullptr: as k_cubic_search, but the wavefront tests a candidate together
+// (quartic_wave_vanish).
+//
+// qs_high<NL, BUDGET>: XOR of the coefficients of the monomials (NL low members with layout sum `lowsum`) + T over the subsets T of at
+// most BUDGET of the variables L + j, j a set bit of g.  The high members are the larger ones, so they continue the layout sum.
+template <int NL, int BUDGET>
+__device__ __forceinline__ u64 qs_high(const u64 *__restrict__ tab, int R, i64 lowsum, u64 g, int L)
+{
+	u64 acc = tab[qs_off(R, NL) + lowsum];
+	if constexpr (BUDGET >= 1)
+		for (u64 b = g; b; b &= b - 1)
+			acc ^= qs_high<NL + 1, BUDGET - 1>(tab, R, lowsum + qs_c(L + ctz64(b), NL + 1), b & (b - 1), L);
+	return acc;
+}
+__global__ void __launch_bounds__(64)
+k_quartic_search(const u64 *__restrict__ tab, int R, int L, u64 nlanes, u64 *__restrict__ list, u64 cap,
+                 unsigned long long *__restrict__ count, const u64 *__restrict__ E, i64 m)
+{
+	extern __shared__ u64 qds[];
+	const u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+	if (g >= nlanes) return;                          // (no barrier below)
+	const int bd = blockDim.x, tid = threadIdx.x, s2 = L, s3 = L + L * (L - 1) / 2;      // where d2 and d3 start among the slots
+	const u64 *Qw = tab + qs_off(R, 4);
+	u64 v = qs_high<0, 4>(tab, R, 0, g, L);
+	for (int k = 0; k < L; k++) {
+		u64 lam = qs_high<1, 3>(tab, R, k, g, L);
+		if (k) lam ^= qs_high<2, 2>(tab, R, (k - 1) + qs_c(k, 2), g, L);                 // at e_{k-1}
+		qds[k * bd + tid] = lam;
+	}
+	for (int k2 = 1; k2 < L; k2++)
+		for (int k1 = 0; k1 < k2; k1++) {                 // at e_{k1-1} ^ e_{k2-1}: the cubic and the quartic terms over that point
+			const bool p1 = k1 >= 1, p2 = k2 - 1 > k1;
+			u64 s = qs_high<2, 2>(tab, R, k1 + qs_c(k2, 2), g, L);
+			if (p1) s ^= qs_high<3, 1>(tab, R, (k1 - 1) + qs_c(k1, 2) + qs_c(k2, 3), g, L);
+			if (p2) s ^= qs_high<3, 1>(tab, R, k1 + qs_c(k2 - 1, 2) + qs_c(k2, 3), g, L);
+			if (p1 && p2) s ^= Qw[(k1 - 1) + qs_c(k1, 2) + qs_c(k2 - 1, 3) + qs_c(k2, 4)];
+			qds[(s2 + cs_pr(k1, k2)) * bd + tid] = s;
+		}
+	for (int k3 = 2; k3 < L; k3++)
+		for (int k2 = 1; k2 < k3; k2++)
+			for (int k1 = 0; k1 < k2; k1++) {             // at e_{k1-1} ^ e_{k2-1} ^ e_{k3-1}
+				u64 s = qs_high<3, 1>(tab, R, k1 + qs_c(k2, 2) + qs_c(k3, 3), g, L);
+				if (k1 >= 1) s ^= Qw[(k1 - 1) + qs_c(k1, 2) + qs_c(k2, 3) + qs_c(k3, 4)];
+				if (k2 - 1 > k1) s ^= Qw[k1 + qs_c(k2 - 1, 2) + qs_c(k2, 3) + qs_c(k3, 4)];
+				if (k3 - 1 > k2) s ^= Qw[k1 + qs_c(k2, 2) + qs_c(k3 - 1, 3) + qs_c(k3, 4)];
+				qds[(s3 + cs_tr(k1, k2, k3)) * bd + tid] = s;
+			}
+	const u64 base = L < 64 ? g << L : 0;
+	bool zero = v == 0;
+	if (E) zero = quartic_wave_vanish(E, m, R, zero, base);
+	if (zero) {
+		const unsigned long long at = atomicAdd(count, 1ull);
+		if (at < cap) list[at] = base;
+	}
+	const u64 steps = 1ull << L;
+	for (u64 i = 1; i < steps; i++) {
+		const int k1 = ctz64(i);
+		const u64 rest = i & (i - 1);
+		u64 d = qds[k1 * bd + tid];
+		if (rest) {
+			const int k2 = ctz64(rest);
+			const u64 rest2 = rest & (rest - 1);
+			const int slot2 = (s2 + cs_pr(k1, k2)) * bd + tid;
+			u64 e = qds[slot2];
+			if (rest2) {
+				const int k3 = ctz64(rest2);
+				const u64 rest3 = rest2 & (rest2 - 1);
+				const int slot3 = (s3 + cs_tr(k1, k2, k3)) * bd + tid;
+				u64 f = qds[slot3];
+				if (rest3) {
+					f ^= Qw[k1 + qs_c(k2, 2) + qs_c(k3, 3) + qs_c(ctz64(rest3), 4)];
+					qds[slot3] = f;
+				}
+				e ^= f;
+				qds[slot2] = e;
+			}
+			d ^= e;
+			qds[k1 * bd + tid] = d;
+		}
+		v ^= d;
+		zero = v == 0;
+		if (E) zero = quartic_wave_vanish(E, m, R, zero, base | (i ^ (i >> 1)));
+		if (zero) {
+			const unsigned long long at = atomicAdd(count, 1ull);
+			if (at < cap) list[at] = base | (i ^ (i >> 1));
+		}
+	}
+}
+
+// k_quartic_check: the second pass.  One wavefront per candidate point y, lanes over the forms (layout E above); a candidate at which
+// every form vanishes is appended to out.
+__global__ void __launch_bounds__(256)
+k_quartic_check(const u64 *__restrict__ E, i64 m, int R, const u64 *__restrict__ cand, u64 ncand, u64 *__restrict__ out,
+                u64 cap, unsigned long long *__restrict__ count)
+{
+	const int lane = threadIdx.x & 63;
+	const i64 ew = 2 + R + R * (R - 1) / 2 + (i64)R * (R - 1) * (R - 2) / 6;
+	const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((u64)gridDim.x * blockDim.x) >> 6;
+	for (u64 c = wave; c < ncand; c += nwaves) {
+		const u64 y = cand[c];
+		u64 bad = 0;
+		for (i64 f = lane; f < m; f += 64) bad |= quartic_form_value(E + f * ew, R, y);
+		if (!wave_or(bad) && lane == 0) {
+			const unsigned long long at = atomicAdd(count, 1ull);
+			if (at < cap) out[at] = y;
+		}
+	}
+}

@@ -4616,38 +4616,91 @@ int search_alloc(QuadTimes &times, int64_t dimension, int64_t words, int64_t max
 // forms are eliminated by re-parametrising: they are solved as a linear system, c_a = c_0 ^ G y over the free variables y, the affine
 // inputs are composed with that map and the forms rebuilt in fewer variables, until no affine form appears.  Step 3:
 // r_eff <= max_enum: k_cubic_search + k_cubic_check; above: the search gives up (there is no relinearisation level).
+//
+// The quartic search (gf2bv_quartic_search: the C(n,4) quadruple coordinates behind the triples, the columns of degree-4 XL and of
+// PackedQuarticSystem) is the same three steps at arity 4: the bodies below take the degree (FormsDegree, CubicPlan::arity), the
+// kernels under them are k_quartic_products (with k_cubic_forms), k_quartic_search and k_quartic_check.
 namespace {
 
 constexpr i64 kCubicMaxRank = 64;               // larger projection ranks are not reduced (a point of the forms is one word)
 constexpr i64 kCubicFormsBytes = 1ll << 30;     // what the forms of one build (products and forms) or of one search may take
 constexpr int kCubicMaxEnum = 40;
 constexpr int kCubicWalk = 12;                  // low variables a lane of k_cubic_search walks (78 words of LDS a lane)
+constexpr i64 kQuarticMaxRank = kCubicMaxRank;
+constexpr int kQuarticMaxEnum = kCubicMaxEnum;
+constexpr int kQuarticWalk = 12;                // ... and of k_quartic_search (298 words of LDS a lane, 149 KiB a workgroup)
 
-thread_local QuadTimes g_cubic_times;
+thread_local QuadTimes g_cubic_times, g_quartic_times;
 
 inline i64 cubic_width(i64 R) { return 1 + R + R * (R - 1) / 2 + R * (R - 1) * (R - 2) / 6; }
+inline i64 quartic_width(i64 R) { return cubic_width(R) + R * (R - 1) * (R - 2) * (R - 3) / 24; }
 
 struct CubicPlan : QuadPlan {                    // (lin, qaff: the affine inputs in the R variables left; M unused)
-	std::vector<int> mem;                        // S x 3: the members of a product coordinate, the third -1 for a pair
+	std::vector<int> mem;                        // S x arity: the members of a product coordinate, -1 where it has fewer
 	std::vector<u64> lin0, qaff0;                // the affine inputs in the r coefficients c_a
 	std::vector<u64> amap;                       // r x W: c_a as an affine form in the R variables left (bit 0 constant, bit 1 + v)
 	i64 R = 0, rounds = 0;
+	int arity = 3;                               // the degree: members of a product coordinate at most
 };
+struct QuarticPlan : CubicPlan { QuarticPlan() { arity = 4; } };
+
+// What differs between the degree-3 and the degree-4 search below the entries: the plan's arity, the layout's width, the kernels with
+// the lane split and the second pass's words per form, the times and the messages
+using ProductsKernel = void (*)(const u64 *, const u64 *, const int *, int, int, int, u64 *);
+struct FormsDegree {
+	int arity;
+	i64 (*width)(i64);                           // bits of a form over R variables
+	i64 (*state_words)(i64);                     // words of LDS a lane of the search kernel keeps at a walk of L variables
+	i64 (*check_words)(i64);                     // words of a form in the check kernel's layout
+	ProductsKernel products;
+	SearchKernel search;
+	CheckKernel check;
+	int walk;
+	QuadTimes &(*times)();                       // (the calling thread's: the times are thread_local)
+	const char *nomem_build, *nomem_search, *bad_point;
+};
+constexpr i64 cubic_state_words(i64 L) { return L + L * (L - 1) / 2; }
+constexpr i64 quartic_state_words(i64 L) { return cubic_state_words(L) + L * (L - 1) * (L - 2) / 6; }
+inline i64 cubic_check_words(i64 R) { return 2 + R + R * (R - 1) / 2; }
+inline i64 quartic_check_words(i64 R) { return cubic_check_words(R) + R * (R - 1) * (R - 2) / 6; }
+QuadTimes &cubic_times() { return g_cubic_times; }
+QuadTimes &quartic_times() { return g_quartic_times; }
+const FormsDegree &cubic_degree()
+{
+	static const FormsDegree d = { 3, cubic_width, cubic_state_words, cubic_check_words, k_cubic_products, k_cubic_search, k_cubic_check,
+	                               kCubicWalk, cubic_times,
+	                               "the cubic forms of this space take more than 1 GiB", "the cubic forms of this search take more than 1 GiB",
+	                               "cubic search: a point that passed the forms is not consistent (internal error)" };
+	return d;
+}
+const FormsDegree &quartic_degree()
+{
+	static const FormsDegree d = { 4, quartic_width, quartic_state_words, quartic_check_words, k_quartic_products, k_quartic_search,
+	                               k_quartic_check, kQuarticWalk, quartic_times,
+	                               "the quartic forms of this space take more than 1 GiB", "the quartic forms of this search take more than 1 GiB",
+	                               "quartic search: a point that passed the forms is not consistent (internal error)" };
+	return d;
+}
 
 void cubic_reduce(CubicPlan &P, const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n)
 {
-	const i64 S2 = n * (n - 1) / 2, S3 = n * (n - 1) * (n - 2) / 6;
-	quad_reduce(P, origin, basis, d, words, n, S2 + S3);
+	const i64 S2 = n * (n - 1) / 2, S3 = n * (n - 1) * (n - 2) / 6, S4 = P.arity == 4 ? n * (n - 1) * (n - 2) * (n - 3) / 24 : 0;
+	const int ar = P.arity;
+	quad_reduce(P, origin, basis, d, words, n, S2 + S3 + S4);
 	if (P.r > kCubicMaxRank) return;
 	quad_inputs(P);
 	P.lin0.swap(P.lin); P.qaff0.swap(P.qaff);
 	P.lin.assign(P.lin0.size(), 0); P.qaff.assign(P.qaff0.size(), 0);
-	P.mem.assign((size_t)(3 * std::max<i64>(P.S, 1)), -1);
-	for (i64 s = 0; s < S2; s++) { P.mem[3 * s] = P.pair_i[s]; P.mem[3 * s + 1] = P.pair_j[s]; }
+	P.mem.assign((size_t)(ar * std::max<i64>(P.S, 1)), -1);
+	for (i64 s = 0; s < S2; s++) { P.mem[ar * s] = P.pair_i[s]; P.mem[ar * s + 1] = P.pair_j[s]; }
 	i64 s = S2;
 	for (i64 i = 2; i < n; i++) for (i64 j = 1; j < i; j++) for (i64 l = 0; l < j; l++, s++) {
-		P.mem[3 * s] = (int)i; P.mem[3 * s + 1] = (int)j; P.mem[3 * s + 2] = (int)l;
+		P.mem[ar * s] = (int)i; P.mem[ar * s + 1] = (int)j; P.mem[ar * s + 2] = (int)l;
 	}
+	if (S4)
+		for (i64 i = 3; i < n; i++) for (i64 j = 2; j < i; j++) for (i64 l = 1; l < j; l++) for (i64 p = 0; p < l; p++, s++) {
+			P.mem[ar * s] = (int)i; P.mem[ar * s + 1] = (int)j; P.mem[ar * s + 2] = (int)l; P.mem[ar * s + 3] = (int)p;
+		}
 	P.R = P.r;
 	P.amap.assign((size_t)(std::max<i64>(P.r, 1) * P.W), 0);
 	for (i64 a = 0; a < P.r; a++) qflip(&P.amap[a * P.W], a + 1);
@@ -4668,19 +4721,27 @@ void cubic_compose(CubicPlan &P)
 
 // the host twin of k_cubic_products + k_cubic_forms (gf2bv_cubic_plan never touches a device): polynomial multiplication, monomial by
 // monomial, through a decode table of the layout
+// (quartic_forms_host: the same body at arity 4, the twin of k_quartic_products + k_cubic_forms)
 void cubic_forms_host(const CubicPlan &P, i64 fw, std::vector<u64> &F)
 {
-	const i64 R = P.R, W = P.W, nb = cubic_width(R), o2 = 1 + R, o3 = o2 + R * (R - 1) / 2;
-	std::vector<std::array<int, 3>> dec((size_t)nb, std::array<int, 3>{-1, -1, -1});
-	for (i64 k = 0; k < R; k++) dec[1 + k] = {(int)k, -1, -1};
-	for (i64 i = 1, q = o2; i < R; i++) for (i64 j = 0; j < i; j++, q++) dec[q] = {(int)i, (int)j, -1};
-	for (i64 i = 2, q = o3; i < R; i++) for (i64 j = 1; j < i; j++) for (i64 l = 0; l < j; l++, q++) dec[q] = {(int)i, (int)j, (int)l};
-	auto with = [&](std::array<int, 3> mm, int v) -> i64 {      // the bit of the monomial mm (at most two members) times x_v
-		if (mm[0] != v && mm[1] != v) { mm[2] = v; std::sort(mm.begin(), mm.end(), std::greater<int>()); }
+	const int ar = P.arity;
+	const i64 R = P.R, W = P.W, nb = ar == 4 ? quartic_width(R) : cubic_width(R), o2 = 1 + R, o3 = o2 + R * (R - 1) / 2, o4 = cubic_width(R);
+	std::vector<std::array<int, 4>> dec((size_t)nb, std::array<int, 4>{-1, -1, -1, -1});
+	for (i64 k = 0; k < R; k++) dec[1 + k] = {(int)k, -1, -1, -1};
+	for (i64 i = 1, q = o2; i < R; i++) for (i64 j = 0; j < i; j++, q++) dec[q] = {(int)i, (int)j, -1, -1};
+	for (i64 i = 2, q = o3; i < R; i++) for (i64 j = 1; j < i; j++) for (i64 l = 0; l < j; l++, q++) dec[q] = {(int)i, (int)j, (int)l, -1};
+	if (ar == 4)
+		for (i64 i = 3, q = o4; i < R; i++) for (i64 j = 2; j < i; j++) for (i64 l = 1; l < j; l++) for (i64 p = 0; p < l; p++, q++)
+			dec[q] = {(int)i, (int)j, (int)l, (int)p};
+	auto with = [&](std::array<int, 4> mm, int v) -> i64 {      // the bit of the monomial mm (at most arity - 1 members) times x_v
+		if (mm[0] != v && mm[1] != v && mm[2] != v) { mm[3] = v; std::sort(mm.begin(), mm.end(), std::greater<int>()); }
 		if (mm[0] < 0) return 0;
 		if (mm[1] < 0) return 1 + mm[0];
 		if (mm[2] < 0) return o2 + (i64)mm[0] * (mm[0] - 1) / 2 + mm[1];
-		return o3 + (i64)mm[0] * (mm[0] - 1) * (mm[0] - 2) / 6 + (i64)mm[1] * (mm[1] - 1) / 2 + mm[2];
+		const i64 t3 = (i64)mm[0] * (mm[0] - 1) * (mm[0] - 2) / 6 + (i64)mm[1] * (mm[1] - 1) / 2 + mm[2];
+		if (mm[3] < 0) return o3 + t3;
+		return o4 + (i64)mm[0] * (mm[0] - 1) * (mm[0] - 2) * (mm[0] - 3) / 24 + (i64)mm[1] * (mm[1] - 1) * (mm[1] - 2) / 6
+		       + (i64)mm[2] * (mm[2] - 1) / 2 + mm[3];
 	};
 	auto mul = [&](const std::vector<u64> &f, const u64 *aff, std::vector<u64> &out) {      // f of degree <= 2 times an affine form
 		std::fill(out.begin(), out.end(), 0);
@@ -4694,9 +4755,9 @@ void cubic_forms_host(const CubicPlan &P, i64 fw, std::vector<u64> &F)
 	std::vector<u64> V((size_t)(std::max<i64>(P.S, 1) * fw), 0), a((size_t)fw), b((size_t)fw);
 	for (i64 s = 0; s < P.S; s++) {
 		std::fill(a.begin(), a.end(), 0);
-		std::copy(&P.lin[(i64)P.mem[3 * s] * W], &P.lin[(i64)P.mem[3 * s] * W] + std::min(W, fw), a.begin());
-		mul(a, &P.lin[(i64)P.mem[3 * s + 1] * W], b);
-		if (P.mem[3 * s + 2] >= 0) { mul(b, &P.lin[(i64)P.mem[3 * s + 2] * W], a); a.swap(b); }
+		std::copy(&P.lin[(i64)P.mem[ar * s] * W], &P.lin[(i64)P.mem[ar * s] * W] + std::min(W, fw), a.begin());
+		mul(a, &P.lin[(i64)P.mem[ar * s + 1] * W], b);
+		for (int f = 2; f < ar && P.mem[ar * s + f] >= 0; f++) { mul(b, &P.lin[(i64)P.mem[ar * s + f] * W], a); a.swap(b); }
 		qxor(b.data(), &P.qaff[s * W], std::min(W, fw));
 		std::copy(b.begin(), b.end(), &V[s * fw]);
 	}
@@ -4705,7 +4766,7 @@ void cubic_forms_host(const CubicPlan &P, i64 fw, std::vector<u64> &F)
 		for (i64 k = P.sup_off[t]; k < P.sup_off[t + 1]; k++) qxor(&F[t * fw], &V[(i64)P.sup_idx[k] * fw], fw);
 }
 
-int cubic_forms_device(const CubicPlan &P, i64 fw, std::vector<u64> &F, int device, hipStream_t st)
+int cubic_forms_device(const CubicPlan &P, ProductsKernel products, i64 fw, std::vector<u64> &F, int device, hipStream_t st)
 {
 	F.assign((size_t)(std::max<i64>(P.m0, 1) * fw), 0);
 	if (P.m0 == 0) return GF2BV_OK;
@@ -4718,7 +4779,7 @@ int cubic_forms_device(const CubicPlan &P, i64 fw, std::vector<u64> &F, int devi
 	HIPCHK(hipMemcpyAsync(dm.p, P.mem.data(), P.mem.size() * 4, hipMemcpyHostToDevice, st));
 	HIPCHK(hipMemcpyAsync(dso.p, P.sup_off.data(), P.sup_off.size() * 8, hipMemcpyHostToDevice, st));
 	HIPCHK(hipMemcpyAsync(dsi.p, P.sup_idx.data(), P.sup_idx.size() * 4, hipMemcpyHostToDevice, st));
-	k_cubic_products<<<dim3((unsigned)P.S), dim3(256), 0, st>>>(dl.as<u64>(), dq.as<u64>(), dm.as<int>(), (int)P.R, (int)P.W, (int)fw, dv.as<u64>());
+	products<<<dim3((unsigned)P.S), dim3(256), 0, st>>>(dl.as<u64>(), dq.as<u64>(), dm.as<int>(), (int)P.R, (int)P.W, (int)fw, dv.as<u64>());
 	HIPCHK(hipGetLastError());
 	k_cubic_forms<<<dim3((unsigned)P.m0), dim3(256), 0, st>>>(dv.as<u64>(), dso.as<i64>(), dsi.as<int>(), (int)fw, dout.as<u64>());
 	HIPCHK(hipGetLastError());
@@ -4780,27 +4841,27 @@ bool cubic_affine_round(CubicPlan &P, i64 fw, const std::vector<u64> &F)
 	return true;
 }
 
-int cubic_plan_build(CubicPlan &P, const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n, int device, hipStream_t st)
+int forms_plan_build(const FormsDegree &D, CubicPlan &P, const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n, int device,
+                     hipStream_t st)
 {
 	auto t0 = std::chrono::steady_clock::now();
 	cubic_reduce(P, origin, basis, d, words, n);
-	g_cubic_times.reduce += ms_since(t0);
+	D.times().reduce += ms_since(t0);
 	if (P.r > kCubicMaxRank) { P.reff = -1; return GF2BV_OK; }
 	std::vector<u64> F;
 	i64 fw = 1;
 	for (;;) {
 		t0 = std::chrono::steady_clock::now();
 		cubic_compose(P);
-		fw = (cubic_width(P.R) + 63) / 64;
-		if ((P.S + P.m0) * fw * 8 > kCubicFormsBytes)
-			return fail(GF2BV_ERR_NOMEM, "the cubic forms of this space take more than 1 GiB");
+		fw = (D.width(P.R) + 63) / 64;
+		if ((P.S + P.m0) * fw * 8 > kCubicFormsBytes) return fail(GF2BV_ERR_NOMEM, D.nomem_build);
 		if (device < 0) cubic_forms_host(P, fw, F);
-		else { int rc = cubic_forms_device(P, fw, F, device, st); if (rc) return rc; }
-		g_cubic_times.forms += ms_since(t0);
+		else { int rc = cubic_forms_device(P, D.products, fw, F, device, st); if (rc) return rc; }
+		D.times().forms += ms_since(t0);
 		t0 = std::chrono::steady_clock::now();
 		P.rounds++;
 		const bool changed = cubic_affine_round(P, fw, F);
-		g_cubic_times.affine += ms_since(t0);
+		D.times().affine += ms_since(t0);
 		if (P.inconsistent) { P.reff = 0; P.fw = 1; P.m = 1; P.forms.assign(1, 1); return GF2BV_OK; }
 		if (!changed) break;
 	}
@@ -4811,8 +4872,17 @@ int cubic_plan_build(CubicPlan &P, const u64 *origin, const u64 *basis, i64 d, i
 	if (P.forms.empty()) P.forms.assign((size_t)fw, 0);
 	return GF2BV_OK;
 }
+int cubic_plan_build(CubicPlan &P, const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n, int device, hipStream_t st)
+{
+	return forms_plan_build(cubic_degree(), P, origin, basis, d, words, n, device, st);
+}
+int quartic_plan_build(QuarticPlan &P, const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n, int device, hipStream_t st)
+{
+	return forms_plan_build(quartic_degree(), P, origin, basis, d, words, n, device, st);
+}
 
 // the point of the space that effective assignment y (reff <= 64 bits) extends to; c_orig: its coefficients (dw words)
+// (quartic_point: the same body, the products of a QuarticPlan having up to four members)
 bool cubic_point(const CubicPlan &P, u64 y, u64 *x, u64 *c_orig)
 {
 	const i64 r = P.r, W = P.W, words = P.words;
@@ -4824,9 +4894,10 @@ bool cubic_point(const CubicPlan &P, u64 y, u64 *x, u64 *c_orig)
 		for (i64 w = 0; w < W; w++) par ^= P.amap[a * W + w] & ye[w];
 		if (__builtin_popcountll(par) & 1) { qxor(x, &P.V[a * words], words); qxor(c_orig, &P.T[a * P.dw], P.dw); }
 	}
+	const int ar = P.arity;
 	auto prod = [&](i64 s) {
-		bool v = qbit(x, P.mem[3 * s]) & qbit(x, P.mem[3 * s + 1]);
-		if (P.mem[3 * s + 2] >= 0) v &= qbit(x, P.mem[3 * s + 2]);
+		bool v = qbit(x, P.mem[ar * s]) & qbit(x, P.mem[ar * s + 1]);
+		for (int f = 2; f < ar && P.mem[ar * s + f] >= 0; f++) v &= qbit(x, P.mem[ar * s + f]);
 		return v;
 	};
 	for (size_t k = 0; k < P.kpiv.size(); k++) {
@@ -4839,12 +4910,14 @@ bool cubic_point(const CubicPlan &P, u64 y, u64 *x, u64 *c_orig)
 
 // every common zero of m cubic forms (equation-int layout, fw words) in R <= kCubicMaxEnum variables (total, ys: search_two_pass).  Only
 // the forms outside the first pass go into E: with none left the driver reads the candidates as the zeros
-int cubic_search_device(const u64 *forms, i64 m, i64 fw, int R, int device, hipStream_t st, std::vector<u64> &ys, u64 *total)
+int forms_search_device(const FormsDegree &D, const u64 *forms, i64 m, i64 fw, int R, int device, hipStream_t st, std::vector<u64> &ys,
+                        u64 *total)
 {
 	ys.clear();
 	if (m == 0) { search_whole_cube(R, ys, total); return GF2BV_OK; }
-	const i64 nb = cubic_width(R), ew = 2 + R + (i64)R * (R - 1) / 2, o2 = 1 + R, o3 = o2 + (i64)R * (R - 1) / 2;
-	if (m * ew * 8 > kCubicFormsBytes) return fail(GF2BV_ERR_NOMEM, "the cubic forms of this search take more than 1 GiB");
+	const i64 nb = D.width(R), o2 = 1 + R, o3 = o2 + (i64)R * (R - 1) / 2, o4 = cubic_width(R);
+	const i64 ew = D.check_words(R);
+	if (m * ew * 8 > kCubicFormsBytes) return fail(GF2BV_ERR_NOMEM, D.nomem_search);
 	const std::vector<i64> chosen = first_independent_forms(forms, m, fw);
 	// the second pass tests the forms the first did not hold (a chosen form vanishes at every candidate; a zero form everywhere)
 	std::vector<char> in_first((size_t)m, 0);
@@ -4861,41 +4934,71 @@ int cubic_search_device(const u64 *forms, i64 m, i64 fw, int R, int device, hipS
 		for (i64 k = 1, q = o2; k < R; k++) for (i64 j = 0; j < k; j++, q++) if (qbit(src, q)) e[2 + j] |= 1ull << k;
 		for (i64 l = 2, q = o3; l < R; l++) for (i64 k = 1; k < l; k++) for (i64 j = 0; j < k; j++, q++)
 			if (qbit(src, q)) e[2 + R + k * (k - 1) / 2 + j] |= 1ull << l;
+		if (D.arity == 4)
+			for (i64 p = 3, q = o4; p < R; p++) for (i64 l = 2; l < p; l++) for (i64 k = 1; k < l; k++) for (i64 j = 0; j < k; j++, q++)
+				if (qbit(src, q)) e[o3 + 1 + l * (l - 1) * (l - 2) / 6 + k * (k - 1) / 2 + j] |= 1ull << p;
 	}
 	for (size_t c = 0; c < chosen.size(); c++) {   // the chosen ones bit-sliced: bit c of every word; tab is indexed like a form's bits
 		const u64 *src = forms + chosen[c] * fw;
 		for (i64 q = 0; q < nb; q++) if (qbit(src, q)) tab[q] |= 1ull << c;
 	}
-	const int L = std::min(R, kCubicWalk);
-	return search_two_pass({ tab, E, mr, k_cubic_search, k_cubic_check, R, L, 64, (size_t)64 * (L + L * (L - 1) / 2) * 8, g_cubic_times },
-	                       device, st, ys, total);
+	const int L = std::min(R, D.walk);
+	const size_t lds = (size_t)64 * 8 * D.state_words(L), lds_max = (size_t)64 * 8 * D.state_words(D.walk);
+	if (lds_max > 65536) {                         // (k_quartic_search only: 149 KiB at its full walk; raised once, to the kernel's maximum)
+		static std::mutex mu;
+		static std::map<int, bool> raised;         // device -> the > 64 KiB dynamic-LDS attribute has been raised there
+		std::lock_guard<std::mutex> lk(mu);
+		if (!raised[device]) {
+			HIPCHK(hipFuncSetAttribute((const void *)D.search, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+			raised[device] = true;
+		}
+	}
+	return search_two_pass({ tab, E, mr, D.search, D.check, R, L, 64, lds, D.times() }, device, st, ys, total);
+}
+int cubic_search_device(const u64 *forms, i64 m, i64 fw, int R, int device, hipStream_t st, std::vector<u64> &ys, u64 *total)
+{
+	return forms_search_device(cubic_degree(), forms, m, fw, R, device, st, ys, total);
+}
+int quartic_search_device(const u64 *forms, i64 m, i64 fw, int R, int device, hipStream_t st, std::vector<u64> &ys, u64 *total)
+{
+	return forms_search_device(quartic_degree(), forms, m, fw, R, device, st, ys, total);
 }
 
 // every consistent point of the space and its coefficients: quad_collect without the relinearisation level
-int cubic_collect(const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n, int max_enum, int device, hipStream_t st,
-                  std::vector<u64> &pts, std::vector<u64> &coef, u64 *total, i64 *lin_rank, bool *gave_up)
+int forms_collect(const FormsDegree &D, CubicPlan &P, const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n, int max_enum, int device,
+                  hipStream_t st, std::vector<u64> &pts, std::vector<u64> &coef, u64 *total, i64 *lin_rank, bool *gave_up)
 {
 	pts.clear(); coef.clear(); *total = 0;
-	CubicPlan P;
-	int rc = cubic_plan_build(P, origin, basis, d, words, n, device, st);
-	g_cubic_times.levels = P.rounds;
+	int rc = forms_plan_build(D, P, origin, basis, d, words, n, device, st);
+	D.times().levels = P.rounds;
 	*lin_rank = P.r;
 	if (rc) return rc;
 	if (P.reff < 0 || (!P.inconsistent && P.reff > max_enum)) { *gave_up = true; return GF2BV_OK; }
 	if (P.inconsistent) return GF2BV_OK;
 	std::vector<u64> ys;
 	auto t0 = std::chrono::steady_clock::now();
-	rc = cubic_search_device(P.forms.data(), P.m, P.fw, (int)P.reff, device, st, ys, total);
-	g_cubic_times.search += ms_since(t0);
+	rc = forms_search_device(D, P.forms.data(), P.m, P.fw, (int)P.reff, device, st, ys, total);
+	D.times().search += ms_since(t0);
 	if (rc) return rc;
 	if ((i64)*total > kQuadMaxPoints) return GF2BV_OK;
 	const i64 np = (i64)ys.size();
 	pts.assign((size_t)(np * words), 0);
 	coef.assign((size_t)(np * P.dw), 0);
 	for (i64 k = 0; k < np; k++)
-		if (!cubic_point(P, ys[k], &pts[k * words], &coef[k * P.dw]))
-			return fail(GF2BV_ERR_HIP, "cubic search: a point that passed the forms is not consistent (internal error)");
+		if (!cubic_point(P, ys[k], &pts[k * words], &coef[k * P.dw])) return fail(GF2BV_ERR_HIP, D.bad_point);
 	return GF2BV_OK;
+}
+int cubic_collect(const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n, int max_enum, int device, hipStream_t st,
+                  std::vector<u64> &pts, std::vector<u64> &coef, u64 *total, i64 *lin_rank, bool *gave_up)
+{
+	CubicPlan P;
+	return forms_collect(cubic_degree(), P, origin, basis, d, words, n, max_enum, device, st, pts, coef, total, lin_rank, gave_up);
+}
+int quartic_collect(const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n, int max_enum, int device, hipStream_t st,
+                    std::vector<u64> &pts, std::vector<u64> &coef, u64 *total, i64 *lin_rank, bool *gave_up)
+{
+	QuarticPlan P;
+	return forms_collect(quartic_degree(), P, origin, basis, d, words, n, max_enum, device, st, pts, coef, total, lin_rank, gave_up);
 }
 
 // ---- the entries of both searches: each body once, over what a degree is --------------------------------------------------------
@@ -4932,7 +5035,22 @@ struct CubicDegree {
 	static constexpr auto search = cubic_search_device;
 	static constexpr auto collect = cubic_collect;
 };
-static_assert(QuadDegree::kMaxEnum == 40 && CubicDegree::kMaxEnum == 40, "the entries' messages name 40");
+struct QuarticDegree {
+	using Plan = QuarticPlan;
+	static constexpr i64 kMaxLin = 450, kPointWords = 1;
+	static constexpr int kMaxEnum = kQuarticMaxEnum;
+	static constexpr const char *kLinText = "n_lin must be 1..450",
+	                            *kWordsText = "words does not cover n_lin + C(n_lin,2) + C(n_lin,3) + C(n_lin,4) columns";
+	static i64 cols(i64 n) { return CubicDegree::cols(n) + n * (n - 1) * (n - 2) * (n - 3) / 24; }
+	static i64 width(i64 R) { return quartic_width(R); }
+	static QuadTimes &times() { return g_quartic_times; }
+	static constexpr auto build = quartic_plan_build;
+	static bool point(const Plan &P, const u64 *y, u64 *x, u64 *c) { return cubic_point(P, y[0], x, c); }
+	static constexpr auto search = quartic_search_device;
+	static constexpr auto collect = quartic_collect;
+};
+static_assert((size_t)64 * 8 * quartic_state_words(kQuarticWalk) <= 160 * 1024, "the walk's state fits a CU's LDS");
+static_assert(QuadDegree::kMaxEnum == 40 && CubicDegree::kMaxEnum == 40 && QuarticDegree::kMaxEnum == 40, "the entries' messages name 40");
 
 template <class D>
 int check_space(const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n_lin)
@@ -5125,6 +5243,42 @@ int gf2bv_cubic_search_alloc(const uint64_t *origin_, const uint64_t *basis_, in
 	});
 }
 void gf2bv_cubic_last_times(double *out8) { search_last_times(CubicDegree::times(), out8); }
+
+int gf2bv_quartic_plan(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin,
+                    int64_t *r, int64_t *r_eff, int64_t *m, int64_t *form_words, uint64_t *forms_, int64_t forms_cap)
+{
+	return catching([&] { return search_plan<QuarticDegree>(origin_, basis_, dimension, words, n_lin, false, -1, r, r_eff, m, form_words, forms_, forms_cap); });
+}
+int gf2bv_quartic_plan_device(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin, int device,
+                           int64_t *r, int64_t *r_eff, int64_t *m, int64_t *form_words, uint64_t *forms_, int64_t forms_cap)
+{
+	return guarded([&] { return search_plan<QuarticDegree>(origin_, basis_, dimension, words, n_lin, true, device, r, r_eff, m, form_words, forms_, forms_cap); });
+}
+int gf2bv_quartic_points(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin,
+                      const uint64_t *ys_, int64_t nys, int64_t y_words, uint64_t *out_words_)
+{
+	return catching([&] { return search_points<QuarticDegree>(origin_, basis_, dimension, words, n_lin, ys_, nys, y_words, out_words_); });
+}
+int gf2bv_quartic_forms_search(const uint64_t *forms_, int64_t m, int64_t r_eff, int device, int64_t max_out, int64_t *count,
+                            uint64_t *out_)
+{
+	return guarded([&] { return search_forms<QuarticDegree>(forms_, m, r_eff, device, max_out, count, out_); });
+}
+int gf2bv_quartic_search(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin,
+                      int max_enum, int64_t max_solutions, int device, int64_t *count, int64_t *lin_rank, uint64_t *out_words_)
+{
+	return search_space_copy([&](uint64_t **pts) {
+		return gf2bv_quartic_search_alloc(origin_, basis_, dimension, words, n_lin, max_enum, max_solutions, device, count, lin_rank, pts);
+	}, words, max_solutions, count, out_words_);
+}
+int gf2bv_quartic_search_alloc(const uint64_t *origin_, const uint64_t *basis_, int64_t dimension, int64_t words, int64_t n_lin,
+                            int max_enum, int64_t max_solutions, int device, int64_t *count, int64_t *lin_rank, uint64_t **out_words)
+{
+	return guarded([&] {
+		return search_space_alloc<QuarticDegree>(origin_, basis_, dimension, words, n_lin, max_enum, max_solutions, device, count, lin_rank, out_words);
+	});
+}
+void gf2bv_quartic_last_times(double *out8) { search_last_times(QuarticDegree::times(), out8); }
 
 void gf2bv_quad_free(uint64_t *words) { free(words); }
 

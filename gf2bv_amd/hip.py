@@ -51,6 +51,7 @@ EXPORTS = [
     "gf2bv_solve_xl4_cubic_guess_words", "gf2bv_solve_xl4_cubic_guess_terms", "gf2bv_xl4_cubic_guess_chunk", "gf2bv_xl4_cubic_guess_chunk_device",
     "gf2bv_quad_search", "gf2bv_quad_search_alloc", "gf2bv_quad_free", "gf2bv_quad_plan", "gf2bv_quad_plan_device", "gf2bv_quad_points", "gf2bv_quad_forms_search", "gf2bv_quad_last_times",
     "gf2bv_cubic_search", "gf2bv_cubic_search_alloc", "gf2bv_cubic_plan", "gf2bv_cubic_plan_device", "gf2bv_cubic_points", "gf2bv_cubic_forms_search", "gf2bv_cubic_last_times",
+    "gf2bv_quartic_search", "gf2bv_quartic_search_alloc", "gf2bv_quartic_plan", "gf2bv_quartic_plan_device", "gf2bv_quartic_points", "gf2bv_quartic_forms_search", "gf2bv_quartic_last_times",
     "gf2bv_slab_work_words", "gf2bv_slab_tiles", "gf2bv_slab_open", "gf2bv_slab_blocks", "gf2bv_slab_owner",
     "gf2bv_slab_payload_bytes", "gf2bv_slab_factor", "gf2bv_slab_apply", "gf2bv_slab_factor_on", "gf2bv_slab_apply_on",
     "gf2bv_slab_finish_local", "gf2bv_slab_solve",
@@ -159,6 +160,14 @@ def lib():
         L.gf2bv_cubic_forms_search.argtypes = L.gf2bv_quad_forms_search.argtypes
         L.gf2bv_cubic_last_times.argtypes = [vp]
         L.gf2bv_cubic_last_times.restype = None
+        L.gf2bv_quartic_search.argtypes = L.gf2bv_quad_search.argtypes
+        L.gf2bv_quartic_search_alloc.argtypes = L.gf2bv_quad_search_alloc.argtypes
+        L.gf2bv_quartic_plan.argtypes = L.gf2bv_quad_plan.argtypes
+        L.gf2bv_quartic_plan_device.argtypes = L.gf2bv_quad_plan_device.argtypes
+        L.gf2bv_quartic_points.argtypes = L.gf2bv_quad_points.argtypes
+        L.gf2bv_quartic_forms_search.argtypes = L.gf2bv_quad_forms_search.argtypes
+        L.gf2bv_quartic_last_times.argtypes = [vp]
+        L.gf2bv_quartic_last_times.restype = None
         L.gf2bv_quad_expand_device.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, i64, i32, vp]
         L.gf2bv_quad_expand_words.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, i64, i32]
         L.gf2bv_solve_quad_terms.argtypes = [vp, vp, vp, vp, i64, i64, i64, i32, i32, pp]
@@ -606,10 +615,15 @@ def cubic_cols(n_lin: int) -> int:
     return n_lin + n_lin * (n_lin - 1) // 2 + n_lin * (n_lin - 1) * (n_lin - 2) // 6
 
 
-# The quad_* and cubic_* search functions below are one body each, taking the kind: "quad" (gf2bv_quad_*, points over the
-# n_lin + n_lin(n_lin-1)/2 columns of a QuadraticSystem) or "cubic" (gf2bv_cubic_*, over cubic_cols(n_lin) columns, cubic forms)
+def quartic_cols(n_lin: int) -> int:
+    return cubic_cols(n_lin) + n_lin * (n_lin - 1) * (n_lin - 2) * (n_lin - 3) // 24
+
+
+# The quad_*, cubic_* and quartic_* search functions below are one body each, taking the kind: "quad" (gf2bv_quad_*, points over the
+# n_lin + n_lin(n_lin-1)/2 columns of a QuadraticSystem), "cubic" (gf2bv_cubic_*, over cubic_cols(n_lin) columns, cubic forms) or
+# "quartic" (gf2bv_quartic_*, over quartic_cols(n_lin) columns, quartic forms)
 def _space_words(kind: str, n_lin: int) -> int:
-    return quad_words(n_lin) if kind == "quad" else (cubic_cols(n_lin) + 63) // 64
+    return quad_words(n_lin) if kind == "quad" else ((cubic_cols if kind == "cubic" else quartic_cols)(n_lin) + 63) // 64
 
 
 def _search_plan(kind: str, origin: int, basis, n_lin: int, device: int | None) -> dict:
@@ -694,6 +708,27 @@ def cubic_forms_search(forms, r_eff: int, device: int = 0, max_out: int = 1 << 2
 def cubic_last_times() -> dict:
     """this thread's last gf2bv_cubic_search: phase times in ms, rounds of the affine elimination, first-pass candidates"""
     return _last_times("cubic")
+
+
+def quartic_plan(origin: int, basis, n_lin: int, device: int | None = None) -> dict:
+    """gf2bv_quartic_plan (host only): r, r_eff (-1: r above 64, not reduced), and the forms as equation ints of a PackedQuarticSystem
+    of r_eff unknowns.  With a device: gf2bv_quartic_plan_device, the forms built by k_quartic_products / k_cubic_forms on that device."""
+    return _search_plan("quartic", origin, basis, n_lin, device)
+
+
+def quartic_points(origin: int, basis, n_lin: int, ys) -> list:
+    """gf2bv_quartic_points (host only): the points of the space that common zeros `ys` (ints below 2^64) of quartic_plan's forms stand for."""
+    return _search_points("quartic", origin, basis, n_lin, ys, 1)
+
+
+def quartic_forms_search(forms, r_eff: int, device: int = 0, max_out: int = 1 << 22) -> tuple:
+    """gf2bv_quartic_forms_search: (count, ascending common zeros) of quartic forms given as equation ints over r_eff unknowns."""
+    return _forms_search("quartic", forms, (quartic_cols(r_eff) + 64) // 64, r_eff, device, max_out)
+
+
+def quartic_last_times() -> dict:
+    """this thread's last gf2bv_quartic_search: phase times in ms, rounds of the affine elimination, first-pass candidates"""
+    return _last_times("quartic")
 
 
 def quad_cols(n_lin: int) -> int:

@@ -11,7 +11,7 @@ from __future__ import annotations
 import sys
 from typing import Sequence
 
-from ._internal import CubicSearchGaveUp
+from ._internal import CubicSearchGaveUp, QuarticSearchGaveUp
 from .linsys import DimensionTooLargeError, _QuadraticPoints
 
 __all__ = ["search_all_cubic", "search_all_xl", "search_one_cubic", "search_one_xl"]
@@ -30,20 +30,24 @@ def _cubic_parts(c):
     return c.solve_raw_space, c.convert_sol
 
 
-def _search(parts, system, zeros: Sequence, max_enum: int, max_solutions: int, first: bool) -> list:
+_GAVE_UP = {"cubic": CubicSearchGaveUp, "quartic": QuarticSearchGaveUp}
+
+
+def _search(parts, system, zeros: Sequence, max_enum: int, max_solutions: int, first: bool, kind: str = "cubic") -> list:
+    """the body of every search_* function here and in search4.py; kind: the AffineSpace method, cubic_search or quartic_search"""
     solve, convert = parts(system)
     space = solve(zeros)
     if space is None:
         return []
     try:
-        raws = space.cubic_search(system._lin_size, max_enum, max_solutions, first)
-    except CubicSearchGaveUp as e:
+        raws = getattr(space, kind + "_search")(system._lin_size, max_enum, max_solutions, first)
+    except _GAVE_UP[kind] as e:
         raise DimensionTooLargeError(f"Solution space (dim {space.dimension}): {e.args[0]}", space=space) from None
     out = []
     for raw in raws:
         sol = convert(raw)
         if sol is None:
-            raise RuntimeError("cubic_search returned an inconsistent point")
+            raise RuntimeError(f"{kind}_search returned an inconsistent point")
         out.append(sol)
     return out
 

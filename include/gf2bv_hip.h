@@ -374,6 +374,34 @@ int  gf2bv_cubic_forms_search(const uint64_t *forms, int64_t m, int64_t r_eff, i
                               uint64_t *out);
 void gf2bv_cubic_last_times(double *out8);
 
+/* ---- quartic search: the consistent points of a solution space over the degree-4 columns --------------------------------------
+ * A space over the columns of degree-4 XL and of PackedQuarticSystem: the cubic layout above followed by the quadruples, (i, j, l, p),
+ * p < l < j < i, at n_lin + C(n_lin,2) + C(n_lin,3) + C(i,4) + C(j,3) + C(l,2) + p; n_lin 1..450 and `words` must cover those
+ * columns.  A point is consistent when every pair, triple and quadruple coordinate equals the product of its linear bits.  The space
+ * is reduced to QUARTIC forms in r_eff variables whose common zeros are exactly the consistent points.  The
+ * entries mirror the cubic ones above one for one -- r reduced up to 64, no relinearisation level (r_eff > max_enum gives up),
+ * max_enum 0..40, y_words >= 1, the same order and cap of the points, gf2bv_quad_free -- with these differences:
+ *  - The forms are the equation ints of a PackedQuarticSystem of r_eff unknowns: the cubic form layout followed by the product of
+ *    unknowns p < l < j < i at bit 1 + r_eff + C(r_eff,2) + C(r_eff,3) + C(i,4) + C(j,3) + C(l,2) + p;
+ *    form_words = ceil((1 + r_eff + C(r_eff,2) + C(r_eff,3) + C(r_eff,4)) / 64): 648 at r_eff = 32, 1297 at 38.
+ *  - Memory: one build holds S = C(n_lin,2) + C(n_lin,3) + C(n_lin,4) product forms and up to as many forms of form_words(r) words
+ *    each; a search holds m forms of 2 + r_eff + C(r_eff,2) + C(r_eff,3) words.  Above 1 GiB either returns GF2BV_ERR_NOMEM without
+ *    attempting the allocation.  A space of full rank r = n_lin always fits up to n_lin = 35 (at most 0.83 GiB) and never from 40 on
+ *    (the product forms alone take 1.21 GiB); at 36..39 it fits when few enough product coordinates are left as forms. */
+int  gf2bv_quartic_search(const uint64_t *origin, const uint64_t *basis, int64_t dimension, int64_t words, int64_t n_lin,
+                          int max_enum, int64_t max_solutions, int device, int64_t *count, int64_t *lin_rank, uint64_t *out_words);
+int  gf2bv_quartic_search_alloc(const uint64_t *origin, const uint64_t *basis, int64_t dimension, int64_t words, int64_t n_lin,
+                                int max_enum, int64_t max_solutions, int device, int64_t *count, int64_t *lin_rank, uint64_t **out_words);
+int  gf2bv_quartic_plan(const uint64_t *origin, const uint64_t *basis, int64_t dimension, int64_t words, int64_t n_lin,
+                        int64_t *r, int64_t *r_eff, int64_t *m, int64_t *form_words, uint64_t *forms, int64_t forms_cap);
+int  gf2bv_quartic_plan_device(const uint64_t *origin, const uint64_t *basis, int64_t dimension, int64_t words, int64_t n_lin, int device,
+                               int64_t *r, int64_t *r_eff, int64_t *m, int64_t *form_words, uint64_t *forms, int64_t forms_cap);
+int  gf2bv_quartic_points(const uint64_t *origin, const uint64_t *basis, int64_t dimension, int64_t words, int64_t n_lin,
+                          const uint64_t *ys, int64_t nys, int64_t y_words, uint64_t *out_words);
+int  gf2bv_quartic_forms_search(const uint64_t *forms, int64_t m, int64_t r_eff, int device, int64_t max_out, int64_t *count,
+                                uint64_t *out);
+void gf2bv_quartic_last_times(double *out8);
+
 /* ---- quadratic expansion: factored quadratic equations -> linearised rows, on the device ---------------------------------
  * A quadratic equation in n_lin unknowns kept FACTORED: a linear form plus products of two linear forms, every form
  * Wl = ceil((n_lin + 1) / 64) words in the equation-int order (bit 0 = constant, bit 1 + g = unknown g; bits above n_lin ignored).
