@@ -4663,6 +4663,75 @@ k_quad_forms(const u64 *__restrict__ lin, const u64 *__restrict__ qaff, const in
 	}
 }
 
+// The second pass of every degree A = 2, 3, 4 (k_forms_check<A>) and the fused mode of its search kernel read the forms from E, each as
+// ew = 1 + SUM_{t < A} C(R, t) words [constant, linear mask, U_0 .. U_{R-1}, T_{01}, T_{02}, T_{12}, T_{03}, ..., Q_{012}, ...]: U_j has
+// bit k > j set when the form has x_j x_k; T_{jk} (j < k, at C(k,2) + j of its block) has bit l > k set when it has x_j x_k x_l; Q_{jkl}
+// (j < k < l, at C(l,3) + C(k,2) + j of its block) has bit p > l set when it has x_j x_k x_l x_p.  The blocks past degree A are absent.
+// F(y) = c ^ par(lin & y) ^ XOR_{j in y} par(U_j & y) ^ XOR_{j < k in y} par(T_jk & y) ^ XOR_{j < k < l in y} par(Q_jkl & y): one
+// popcount per set bit, set pair and set triple of y, a level of the nest per degree.
+template <int A>
+__device__ __forceinline__ i64 form_words(int R)
+{
+	int ew = 2 + R;
+	if constexpr (A >= 3) ew += R * (R - 1) / 2;
+	if constexpr (A >= 4) return ew + (i64)R * (R - 1) * (R - 2) / 6;
+	return ew;
+}
+template <int A>
+__device__ __forceinline__ u64 form_value(const u64 *__restrict__ e, int R, u64 y)
+{
+	u64 acc = e[0] + (u64)__popcll(e[1] & y);
+	const u64 *U = e + 2;
+	for (u64 bj = y; bj; bj &= bj - 1) {
+		const int j = ctz64(bj);
+		acc += (u64)__popcll(U[j] & y);
+		if constexpr (A >= 3) {
+			const u64 *T = U + R;
+			for (u64 bk = bj & (bj - 1); bk; bk &= bk - 1) {
+				const int k = ctz64(bk);
+				acc += (u64)__popcll(T[k * (k - 1) / 2 + j] & y);
+				if constexpr (A >= 4) {
+					const u64 *Q = T + R * (R - 1) / 2;
+					for (u64 bl = bk & (bk - 1); bl; bl &= bl - 1) {
+						const int l = ctz64(bl);
+						acc += (u64)__popcll(Q[l * (l - 1) * (l - 2) / 6 + k * (k - 1) / 2 + j] & y);
+					}
+				}
+			}
+		}
+	}
+	return acc & 1;
+}
+template <int A>
+__device__ __forceinline__ bool all_vanish(const u64 *__restrict__ E, i64 m, int R, u64 y)
+{
+	const i64 ew = form_words<A>(R);
+	for (i64 f = 0; f < m; f++)
+		if (form_value<A>(E + f * ew, R, y)) return false;
+	return true;
+}
+
+// k_forms_check<A>: the second pass.  One wavefront per candidate point y (R <= 64 variables), lanes over the forms (layout E above);
+// a candidate at which every form vanishes is appended to out.
+template <int A>
+__global__ void __launch_bounds__(256)
+k_forms_check(const u64 *__restrict__ E, i64 m, int R, const u64 *__restrict__ cand, u64 ncand, u64 *__restrict__ out,
+              u64 cap, unsigned long long *__restrict__ count)
+{
+	const int lane = threadIdx.x & 63;
+	const i64 ew = form_words<A>(R);
+	const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((u64)gridDim.x * blockDim.x) >> 6;
+	for (u64 c = wave; c < ncand; c += nwaves) {
+		const u64 y = cand[c];
+		u64 bad = 0;
+		for (i64 f = lane; f < m; f += 64) bad |= form_value<A>(E + f * ew, R, y);
+		if (!wave_or(bad) && lane == 0) {
+			const unsigned long long at = atomicAdd(count, 1ull);
+			if (at < cap) out[at] = y;
+		}
+	}
+}
+
 // k_quad_search: every common zero of 64 quadratic forms in R <= 64 variables, bit-sliced (bit f of a word = form f).
 // tab: [K | Lw[0..R) | Sw[R x R]]: constants, linear coefficients, and the symmetric pair coefficients (Sw[j][k] = Sw[k][j],
 // zero diagonal).  Lane g fixes the high variables L..R-1 to the bits of g and walks the low L variables in Gray order
@@ -4672,7 +4741,9 @@ k_quad_forms(const u64 *__restrict__ lin, const u64 *__restrict__ qaff, const in
 // column per thread (d1[k * blockDim + tid]); every lane starts from its own point (no lane depends on another).
 // A lane at a zero appends its point to `list` (atomic counter `count`; the points beyond `cap` are counted, not stored).
 // With E != nullptr (the fallback when the 64 forms leave too many candidates to store) the lane first tests the point
-// against all m forms of E (layout of k_quad_check) and appends only the common zeros of every form.
+// against all m forms of E and appends only the common zeros of every form.  quad_all_vanish is all_vanish<2> written out with XOR for
+// the sum: inlined into this walk the shared form measured 1.3 % slower at R = 32 (XOR) or took two more VGPRs (sum), see
+// profiles/forms_degree_refactor_time.txt; k_cubic_search and k_quartic_search compile to the same instructions with either.
 __device__ __forceinline__ bool quad_all_vanish(const u64 *__restrict__ E, i64 m, int R, u64 y)
 {
 	for (i64 f = 0; f < m; f++) {
@@ -4723,35 +4794,6 @@ k_quad_search(const u64 *__restrict__ tab, int R, int L, u64 nlanes, u64 *__rest
 		if (v == 0 && (!E || quad_all_vanish(E, m, R, base | (i ^ (i >> 1))))) {
 			const unsigned long long at = atomicAdd(count, 1ull);
 			if (at < cap) list[at] = base | (i ^ (i >> 1));
-		}
-	}
-}
-
-// k_quad_check: the second pass.  One wavefront per candidate point y (R <= 64 variables), lanes over the forms:
-// E holds every form as R + 2 words [constant, linear mask, U row 0 .. U row R-1] (row j: bits k > j), and
-// Q(y) = c ^ parity(lin & y) ^ XOR_{j in y} parity(row_j & y).  A candidate at which every form vanishes is appended to out.
-__global__ void __launch_bounds__(256)
-k_quad_check(const u64 *__restrict__ E, i64 m, int R, const u64 *__restrict__ cand, u64 ncand, u64 *__restrict__ out,
-             u64 cap, unsigned long long *__restrict__ count)
-{
-	const int lane = threadIdx.x & 63;
-	const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((u64)gridDim.x * blockDim.x) >> 6;
-	for (u64 c = wave; c < ncand; c += nwaves) {
-		const u64 y = cand[c];
-		u64 bad = 0;
-		for (i64 f = lane; f < m; f += 64) {
-			const u64 *e = E + f * (i64)(R + 2);
-			u64 acc = e[0] ^ (u64)__popcll(e[1] & y);
-			u64 bits = y;
-			while (bits) {
-				const int j = ctz64(bits); bits &= bits - 1;
-				acc ^= (u64)__popcll(e[2 + j] & y);
-			}
-			bad |= acc & 1;
-		}
-		if (!wave_or(bad) && lane == 0) {
-			const unsigned long long at = atomicAdd(count, 1ull);
-			if (at < cap) out[at] = y;
 		}
 	}
 }
@@ -5765,66 +5807,102 @@ k_cubic_specialise(const u64 *__restrict__ cubic, i64 m, i64 cubic_stride, int n
 // ==========================================================================================
 // (host side and the mathematics: gf2bv_cubic_search in gf2_solver.hip)
 //
-// A cubic form over R <= 64 unknowns is an equation int of fw = ceil((1 + R + C(R,2) + C(R,3)) / 64) words: bit 0 the constant,
-// bit 1 + k unknown k, bit 1 + R + C(i,2) + j the product of unknowns j < i, bit 1 + R + C(R,2) + C(i,3) + C(j,2) + l the product
-// of unknowns l < j < i -- the layout of a PackedCubicSystem of R unknowns.
-//
-// k_cubic_products: one workgroup per product coordinate s of the space (members mem[3 s ..], the third -1 for a pair): the form
-// v_s = l_a l_b (l_c) ^ q_s, every l and q an affine form of W <= 2 words (bit 0 = constant, bit 1 + k = unknown k).  A thread forms
-// whole output words, stepping the monomial along the layout.  The coefficient of a monomial x_M in a product of affine forms in
-// GF(2)[x] / (x^2 + x) is the Moebius sum XOR_{T subset of M} prod_F F(1_T), F(1_T) = F_0 ^ XOR_{v in T} F_v: at most 8 subsets of 3
-// parities each, and x^2 = x is folded in by construction (the sum sees the product only as a function on the cube).
-// k_cubic_forms: one workgroup per form t: F_t = XOR of v_s over the support of t (sup_idx[sup_off[t] .. sup_off[t + 1]): t's own
+// A form of degree A over R <= 64 unknowns is an equation int of fw = ceil(SUM_{t <= A} C(R, t) / 64) words, a block per monomial size:
+// bit 0 the constant, bit 1 + k unknown k, bit 1 + R + C(i,2) + j the product of unknowns j < i, bit 1 + R + C(R,2) + C(i,3) + C(j,2) + l
+// the product of unknowns l < j < i, and so on -- the layout of a PackedCubicSystem (A = 3) or a PackedQuarticSystem (A = 4) of R
+// unknowns.  In every block a monomial with members m_0 < m_1 < ... lies at the block's start + SUM_t C(m_t, t + 1) (qs_c, qs_off), and
+// qs_root inverts one term of that sum.  The search tables of k_cubic_search and k_quartic_search are indexed the same way.
+__device__ __forceinline__ i64 qs_c(int h, int t)        // C(h, t), t = 1..4
+{
+	i64 c = h;
+	if (t >= 2) c = c * (h - 1) / 2;
+	if (t >= 3) c = c * (h - 2) / 3;
+	if (t >= 4) c = c * (h - 3) / 4;
+	return c;
+}
+__device__ __forceinline__ i64 qs_off(int R, int size)   // where the monomials of `size` members start in a form (or in the search table)
+{
+	i64 o = size ? 1 : 0;
+	if (size >= 2) o += R;
+	if (size >= 3) o += qs_c(R, 2);
+	if (size >= 4) o += qs_c(R, 3);
+	return o;
+}
+__device__ __forceinline__ int qs_root(int p, int t)     // the largest h with C(h, t) <= p, t = 1..4
+{
+	return t == 1 ? p : t == 2 ? (int)xl_tri_root(p) : t == 3 ? (int)xl_tet_root(p) : (int)xl_quart_root(p);
+}
+
+// k_forms_products<A>: one workgroup per product coordinate s of the space (members mem[A s ..], largest first, -1 where it has fewer
+// than A): the form v_s = l_a l_b (l_c (l_d)) ^ q_s, every l and q an affine form of W <= 2 words (bit 0 = constant, bit 1 + k = unknown
+// k).  A thread forms whole output words: it decodes the monomial of its word's first bit (mm[0] > mm[1] > ..., `kind` of them) and
+// steps it along the layout.  The coefficient of a monomial x_M in a product of affine forms in GF(2)[x] / (x^2 + x) is the Moebius sum
+// XOR_{T subset of M} prod_F F(1_T), F(1_T) = F_0 ^ XOR_{v in T} F_v: at most 2^A subsets of A parities each, and x^2 = x is folded in
+// by construction (the sum sees the product only as a function on the cube).  Every index of mm and fm is a constant once the loops
+// over A are unrolled, so both stay in registers.
+// k_forms_sum: one workgroup per form t: F_t = XOR of v_s over the support of t (sup_idx[sup_off[t] .. sup_off[t + 1]): t's own
 // coordinate and the pivots whose K row has a bit at t) -- the second pass, a sparse GF(2) product with coalesced rows.
 __device__ __forceinline__ u64 cf_bit(const u64 *f, int v) { return (f[(v + 1) >> 6] >> ((v + 1) & 63)) & 1; }
+template <int A>
 __global__ void __launch_bounds__(256)
-k_cubic_products(const u64 *__restrict__ lin, const u64 *__restrict__ qaff, const int *__restrict__ mem, int R, int W, int fw,
+k_forms_products(const u64 *__restrict__ lin, const u64 *__restrict__ qaff, const int *__restrict__ mem, int R, int W, int fw,
                  u64 *__restrict__ V)
 {
-	__shared__ u64 ops[3][2];
+	__shared__ u64 ops[A][2];
 	const i64 s = blockIdx.x;
-	const int nf = mem[3 * s + 2] >= 0 ? 3 : 2;
-	if (threadIdx.x < 6) {
+	int nf = 2;
+	while (nf < A && mem[A * s + nf] >= 0) nf++;
+	if (threadIdx.x < 2 * A) {
 		const int f = threadIdx.x >> 1, w = threadIdx.x & 1;
-		ops[f][w] = (f < nf && w < W) ? lin[(i64)mem[3 * s + f] * W + w] : 0;
+		ops[f][w] = (f < nf && w < W) ? lin[(i64)mem[A * s + f] * W + w] : 0;
 	}
 	__syncthreads();
-	const int nbits = 1 + R + R * (R - 1) / 2 + R * (R - 1) * (R - 2) / 6;
+	const int nbits = (int)(qs_off(R, A) + qs_c(R, A));
 	for (int w = threadIdx.x; w < fw; w += blockDim.x) {
-		int q = w * 64, kind, a = 0, b = 0, c = 0;            // the monomial of bit q: kind members, a > b > c
-		if (q == 0) kind = 0;
-		else if (q <= R) { kind = 1; a = q - 1; }
-		else if (q < 1 + R + R * (R - 1) / 2) { kind = 2; const int p = q - 1 - R; a = (int)xl_tri_root(p); b = p - (int)xl_c2(a); }
-		else {
-			kind = 3;
-			const int t = q - 1 - R - R * (R - 1) / 2;
-			a = (int)xl_tet_root(t);
-			const int rem = t - (int)xl_c3(a);
-			b = (int)xl_tri_root(rem); c = rem - (int)xl_c2(b);
+		int q = w * 64, kind = 0, mm[A] = {};
+#pragma unroll
+		for (int t = 1; t <= A; t++) if (q >= (int)qs_off(R, t)) kind = t;
+#pragma unroll
+		for (int K = 1; K <= A; K++) {
+			if (kind != K) continue;
+			int rem = q - (int)qs_off(R, K);
+#pragma unroll
+			for (int i = 0; i < K; i++) { mm[i] = qs_root(rem, K - i); rem -= (int)qs_c(mm[i], K - i); }
 		}
 		u64 word = 0;
 		for (int k = 0; k < 64 && q < nbits; k++, q++) {
 			// bit 0 of fm: the form's constant; bits 1..kind: its coefficients at the monomial's members
-			unsigned fm[3];
-			for (int f = 0; f < 3; f++) {
+			unsigned fm[A];
+#pragma unroll
+			for (int f = 0; f < A; f++) {
 				unsigned x = (unsigned)(ops[f][0] & 1);
-				if (kind >= 1) x |= (unsigned)cf_bit(ops[f], a) << 1;
-				if (kind >= 2) x |= (unsigned)cf_bit(ops[f], b) << 2;
-				if (kind >= 3) x |= (unsigned)cf_bit(ops[f], c) << 3;
+#pragma unroll
+				for (int i = 0; i < A; i++) if (i < kind) x |= (unsigned)cf_bit(ops[f], mm[i]) << (i + 1);
 				fm[f] = x;
 			}
 			unsigned coef = 0;
 			for (unsigned T = 0; T < (1u << kind); T++) {
 				const unsigned mask = 1u | (T << 1);
 				unsigned p = __popc(fm[0] & mask) & __popc(fm[1] & mask);
-				if (nf == 3) p &= __popc(fm[2] & mask);
+#pragma unroll
+				for (int f = 2; f < A; f++) if (f < nf) p &= __popc(fm[f] & mask);
 				coef ^= p;
 			}
 			word |= (u64)(coef & 1) << k;
-			if (kind == 0) { kind = 1; a = 0; }
-			else if (kind == 1) { if (++a == R) { kind = 2; a = 1; b = 0; } }
-			else if (kind == 2) { if (++b == a) { b = 0; if (++a == R) { kind = 3; a = 2; b = 1; c = 0; } } }
-			else if (++c == b) { c = 0; if (++b == a) { a++; b = 1; } }
+			// the next monomial: the smallest member steps; one that reaches the member above it (the largest: R) starts again at its
+			// least value and the member above steps; when the largest starts again the block is over and the next size begins
+			bool carry = true;
+#pragma unroll
+			for (int i = A - 1; i >= 0; i--) {
+				if (i >= kind || !carry) continue;
+				if (++mm[i] == (i ? mm[i - 1] : R)) mm[i] = kind - 1 - i;
+				else carry = false;
+			}
+			if (carry) {
+				kind++;
+#pragma unroll
+				for (int i = 0; i < A; i++) if (i < kind) mm[i] = kind - 1 - i;
+			}
 		}
 		if (w < W) word ^= qaff[s * W + w];
 		V[s * (i64)fw + w] = word;
@@ -5832,7 +5910,7 @@ k_cubic_products(const u64 *__restrict__ lin, const u64 *__restrict__ qaff, cons
 }
 
 __global__ void __launch_bounds__(256)
-k_cubic_forms(const u64 *__restrict__ V, const i64 *__restrict__ sup_off, const int *__restrict__ sup_idx, int fw, u64 *__restrict__ out)
+k_forms_sum(const u64 *__restrict__ V, const i64 *__restrict__ sup_off, const int *__restrict__ sup_idx, int fw, u64 *__restrict__ out)
 {
 	const i64 t = blockIdx.x, k0 = sup_off[t], k1 = sup_off[t + 1];
 	for (int w = threadIdx.x; w < fw; w += blockDim.x) {
@@ -5840,33 +5918,6 @@ k_cubic_forms(const u64 *__restrict__ V, const i64 *__restrict__ sup_off, const 
 		for (i64 k = k0; k < k1; k++) acc ^= V[(i64)sup_idx[k] * fw + w];
 		out[t * (i64)fw + w] = acc;
 	}
-}
-
-// k_cubic_check and the fused mode of k_cubic_search: E holds every form outside the first pass as ew = 2 + R + C(R,2) words
-// [constant, linear mask, U_0 .. U_{R-1}, T_{01}, T_{02}, T_{12}, T_{03}, ...]: U_j has bit k > j set when the form has x_j x_k,
-// T_{jk} (j < k, at 2 + R + C(k,2) + j) has bit l > k set when it has x_j x_k x_l.  Then
-// F(y) = c ^ par(lin & y) ^ XOR_{j in y} par(U_j & y) ^ XOR_{j < k in y} par(T_jk & y): one popcount per set bit and per set
-// bit pair of y.
-__device__ __forceinline__ u64 cubic_form_value(const u64 *__restrict__ e, int R, u64 y)
-{
-	u64 acc = e[0] + (u64)__popcll(e[1] & y);
-	const u64 *U = e + 2, *T = e + 2 + R;
-	for (u64 bj = y; bj; bj &= bj - 1) {
-		const int j = ctz64(bj);
-		acc += (u64)__popcll(U[j] & y);
-		for (u64 bk = bj & (bj - 1); bk; bk &= bk - 1) {
-			const int k = ctz64(bk);
-			acc += (u64)__popcll(T[k * (k - 1) / 2 + j] & y);
-		}
-	}
-	return acc & 1;
-}
-__device__ __forceinline__ bool cubic_all_vanish(const u64 *__restrict__ E, i64 m, int R, u64 y)
-{
-	const i64 ew = 2 + R + R * (R - 1) / 2;
-	for (i64 f = 0; f < m; f++)
-		if (cubic_form_value(E + f * ew, R, y)) return false;
-	return true;
 }
 
 // k_cubic_search: every common zero of 64 cubic forms in R <= 64 variables, bit-sliced (bit f of a word = form f).
@@ -5928,7 +5979,7 @@ k_cubic_search(const u64 *__restrict__ tab, int R, int L, u64 nlanes, u64 *__res
 			cds[(L + cs_pr(k1, k2)) * bd + tid] = s;
 		}
 	const u64 base = L < 64 ? g << L : 0;
-	if (v == 0 && (!E || cubic_all_vanish(E, m, R, base))) {
+	if (v == 0 && (!E || all_vanish<3>(E, m, R, base))) {
 		const unsigned long long at = atomicAdd(count, 1ull);
 		if (at < cap) list[at] = base;
 	}
@@ -5950,29 +6001,9 @@ k_cubic_search(const u64 *__restrict__ tab, int R, int L, u64 nlanes, u64 *__res
 			cds[k1 * bd + tid] = d;
 		}
 		v ^= d;
-		if (v == 0 && (!E || cubic_all_vanish(E, m, R, base | (i ^ (i >> 1))))) {
+		if (v == 0 && (!E || all_vanish<3>(E, m, R, base | (i ^ (i >> 1))))) {
 			const unsigned long long at = atomicAdd(count, 1ull);
 			if (at < cap) list[at] = base | (i ^ (i >> 1));
-		}
-	}
-}
-
-// k_cubic_check: the second pass.  One wavefront per candidate point y, lanes over the forms (layout E above); a candidate at which
-// every form vanishes is appended to out.
-__global__ void __launch_bounds__(256)
-k_cubic_check(const u64 *__restrict__ E, i64 m, int R, const u64 *__restrict__ cand, u64 ncand, u64 *__restrict__ out,
-              u64 cap, unsigned long long *__restrict__ count)
-{
-	const int lane = threadIdx.x & 63;
-	const i64 ew = 2 + R + R * (R - 1) / 2;
-	const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((u64)gridDim.x * blockDim.x) >> 6;
-	for (u64 c = wave; c < ncand; c += nwaves) {
-		const u64 y = cand[c];
-		u64 bad = 0;
-		for (i64 f = lane; f < m; f += 64) bad |= cubic_form_value(E + f * ew, R, y);
-		if (!wave_or(bad) && lane == 0) {
-			const unsigned long long at = atomicAdd(count, 1ull);
-			if (at < cap) out[at] = y;
 		}
 	}
 }
@@ -5983,122 +6014,16 @@ k_cubic_check(const u64 *__restrict__ E, i64 m, int R, const u64 *__restrict__ c
 // ==========================================================================================
 // (host side and the mathematics: gf2bv_quartic_search in gf2_solver.hip)
 //
-// A quartic form over R <= 64 unknowns is the cubic layout followed by the quadruple block: the product of unknowns p < l < j < i is
-// bit 1 + R + C(R,2) + C(R,3) + C(i,4) + C(j,3) + C(l,2) + p -- the equation int of a PackedQuarticSystem of R unknowns.  In every
-// block a monomial with members m_0 < m_1 < ... lies at the block's start + SUM_t C(m_t, t + 1) (qs_c, qs_off).
+// The layout of a quartic form, its products (k_forms_products<4>, k_forms_sum) and its second pass (form_value<4>, k_forms_check<4>) are
+// the templates above at A = 4; what is the degree's own is the walk of k_quartic_search and its fused test.
 //
-// k_quartic_products: k_cubic_products with up to four operands (members mem[4 s ..], -1 where a coordinate has fewer) and the
-// fourth block: at most 16 subsets of 4 parities each in the Moebius sum.  F_t = XOR of v_s over a support is k_cubic_forms itself.
-__device__ __forceinline__ i64 qs_c(int h, int t)        // C(h, t), t = 1..4
-{
-	i64 c = h;
-	if (t >= 2) c = c * (h - 1) / 2;
-	if (t >= 3) c = c * (h - 2) / 3;
-	if (t >= 4) c = c * (h - 3) / 4;
-	return c;
-}
-__device__ __forceinline__ i64 qs_off(int R, int size)   // where the monomials of `size` members start in a form (or in the search table)
-{
-	i64 o = size ? 1 : 0;
-	if (size >= 2) o += R;
-	if (size >= 3) o += qs_c(R, 2);
-	if (size >= 4) o += qs_c(R, 3);
-	return o;
-}
-__global__ void __launch_bounds__(256)
-k_quartic_products(const u64 *__restrict__ lin, const u64 *__restrict__ qaff, const int *__restrict__ mem, int R, int W, int fw,
-                   u64 *__restrict__ V)
-{
-	__shared__ u64 ops[4][2];
-	const i64 s = blockIdx.x;
-	const int nf = mem[4 * s + 3] >= 0 ? 4 : mem[4 * s + 2] >= 0 ? 3 : 2;
-	if (threadIdx.x < 8) {
-		const int f = threadIdx.x >> 1, w = threadIdx.x & 1;
-		ops[f][w] = (f < nf && w < W) ? lin[(i64)mem[4 * s + f] * W + w] : 0;
-	}
-	__syncthreads();
-	const int o2 = (int)qs_off(R, 2), o3 = (int)qs_off(R, 3), o4 = (int)qs_off(R, 4), nbits = o4 + (int)qs_c(R, 4);
-	for (int w = threadIdx.x; w < fw; w += blockDim.x) {
-		int q = w * 64, kind, a = 0, b = 0, c = 0, d = 0;     // the monomial of bit q: kind members, a > b > c > d
-		if (q == 0) kind = 0;
-		else if (q < o2) { kind = 1; a = q - 1; }
-		else if (q < o3) { kind = 2; const int p = q - o2; a = (int)xl_tri_root(p); b = p - (int)xl_c2(a); }
-		else if (q < o4) {
-			kind = 3;
-			const int t = q - o3;
-			a = (int)xl_tet_root(t);
-			const int rem = t - (int)xl_c3(a);
-			b = (int)xl_tri_root(rem); c = rem - (int)xl_c2(b);
-		} else {
-			kind = 4;
-			const int u = q - o4;
-			a = (int)xl_quart_root(u);
-			const int rem = u - (int)xl_c4(a);
-			b = (int)xl_tet_root(rem);
-			const int rem2 = rem - (int)xl_c3(b);
-			c = (int)xl_tri_root(rem2); d = rem2 - (int)xl_c2(c);
-		}
-		u64 word = 0;
-		for (int k = 0; k < 64 && q < nbits; k++, q++) {
-			// bit 0 of fm: the form's constant; bits 1..kind: its coefficients at the monomial's members
-			unsigned fm[4];
-			for (int f = 0; f < 4; f++) {
-				unsigned x = (unsigned)(ops[f][0] & 1);
-				if (kind >= 1) x |= (unsigned)cf_bit(ops[f], a) << 1;
-				if (kind >= 2) x |= (unsigned)cf_bit(ops[f], b) << 2;
-				if (kind >= 3) x |= (unsigned)cf_bit(ops[f], c) << 3;
-				if (kind >= 4) x |= (unsigned)cf_bit(ops[f], d) << 4;
-				fm[f] = x;
-			}
-			unsigned coef = 0;
-			for (unsigned T = 0; T < (1u << kind); T++) {
-				const unsigned mask = 1u | (T << 1);
-				unsigned p = __popc(fm[0] & mask) & __popc(fm[1] & mask);
-				if (nf >= 3) p &= __popc(fm[2] & mask);
-				if (nf == 4) p &= __popc(fm[3] & mask);
-				coef ^= p;
-			}
-			word |= (u64)(coef & 1) << k;
-			if (kind == 0) { kind = 1; a = 0; }
-			else if (kind == 1) { if (++a == R) { kind = 2; a = 1; b = 0; } }
-			else if (kind == 2) { if (++b == a) { b = 0; if (++a == R) { kind = 3; a = 2; b = 1; c = 0; } } }
-			else if (kind == 3) { if (++c == b) { c = 0; if (++b == a) { b = 1; if (++a == R) { kind = 4; a = 3; b = 2; c = 1; d = 0; } } } }
-			else if (++d == c) { d = 0; if (++c == b) { c = 1; if (++b == a) { a++; b = 2; } } }
-		}
-		if (w < W) word ^= qaff[s * W + w];
-		V[s * (i64)fw + w] = word;
-	}
-}
-
-// k_quartic_check and the fused mode of k_quartic_search: E holds every form outside the first pass as
-// ew = 2 + R + C(R,2) + C(R,3) words: the layout of k_cubic_check followed by Q_{jkl} (j < k < l, at 2 + R + C(R,2) + C(l,3) + C(k,2) + j),
-// which has bit p > l set when the form has x_j x_k x_l x_p.  The value adds XOR_{j < k < l in y} par(Q_jkl & y) to the cubic one: one
-// popcount per set bit, pair and triple of y.
-__device__ __forceinline__ u64 quartic_form_value(const u64 *__restrict__ e, int R, u64 y)
-{
-	u64 acc = e[0] + (u64)__popcll(e[1] & y);
-	const u64 *U = e + 2, *T = U + R, *Q = T + R * (R - 1) / 2;
-	for (u64 bj = y; bj; bj &= bj - 1) {
-		const int j = ctz64(bj);
-		acc += (u64)__popcll(U[j] & y);
-		for (u64 bk = bj & (bj - 1); bk; bk &= bk - 1) {
-			const int k = ctz64(bk);
-			acc += (u64)__popcll(T[k * (k - 1) / 2 + j] & y);
-			for (u64 bl = bk & (bk - 1); bl; bl &= bl - 1) {
-				const int l = ctz64(bl);
-				acc += (u64)__popcll(Q[l * (l - 1) * (l - 2) / 6 + k * (k - 1) / 2 + j] & y);
-			}
-		}
-	}
-	return acc & 1;
-}
 // The fused test, by the whole wavefront (a form costs a popcount per triple of the candidate's set bits, far too much for one lane
 // while 63 wait): the lanes at a candidate (`hit`) take turns, the turn's point is read from its lane and the live lanes share the
 // m forms of E among them.  Returns whether this lane's own candidate is a common zero of all of them.  Called in uniform control
 // flow by every lane that has not left the kernel.
 __device__ __forceinline__ bool quartic_wave_vanish(const u64 *__restrict__ E, i64 m, int R, bool hit, u64 y)
 {
-	const i64 ew = 2 + R + R * (R - 1) / 2 + (i64)R * (R - 1) * (R - 2) / 6;
+	const i64 ew = form_words<4>(R);
 	const int lane = threadIdx.x & 63;
 	const u64 live = __ballot(1);
 	const int rank = __popcll(live & ((1ull << lane) - 1)), nlive = __popcll(live);
@@ -6107,7 +6032,7 @@ __device__ __forceinline__ bool quartic_wave_vanish(const u64 *__restrict__ E, i
 		const int src = ctz64(todo);
 		const u64 p = ((u64)(unsigned)__builtin_amdgcn_readlane((int)(y >> 32), src) << 32) | (unsigned)__builtin_amdgcn_readlane((int)y, src);
 		u64 bad = 0;
-		for (i64 f = rank; f < m && !bad; f += nlive) bad = quartic_form_value(E + f * ew, R, p);
+		for (i64 f = rank; f < m && !bad; f += nlive) bad = form_value<4>(E + f * ew, R, p);
 		const bool none = __ballot(bad != 0) == 0;
 		if (lane == src) ok = none;
 	}
@@ -6209,26 +6134,6 @@ k_quartic_search(const u64 *__restrict__ tab, int R, int L, u64 nlanes, u64 *__r
 		if (zero) {
 			const unsigned long long at = atomicAdd(count, 1ull);
 			if (at < cap) list[at] = base | (i ^ (i >> 1));
-		}
-	}
-}
-
-// k_quartic_check: the second pass.  One wavefront per candidate point y, lanes over the forms (layout E above); a candidate at which
-// every form vanishes is appended to out.
-__global__ void __launch_bounds__(256)
-k_quartic_check(const u64 *__restrict__ E, i64 m, int R, const u64 *__restrict__ cand, u64 ncand, u64 *__restrict__ out,
-                u64 cap, unsigned long long *__restrict__ count)
-{
-	const int lane = threadIdx.x & 63;
-	const i64 ew = 2 + R + R * (R - 1) / 2 + (i64)R * (R - 1) * (R - 2) / 6;
-	const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((u64)gridDim.x * blockDim.x) >> 6;
-	for (u64 c = wave; c < ncand; c += nwaves) {
-		const u64 y = cand[c];
-		u64 bad = 0;
-		for (i64 f = lane; f < m; f += 64) bad |= quartic_form_value(E + f * ew, R, y);
-		if (!wave_or(bad) && lane == 0) {
-			const unsigned long long at = atomicAdd(count, 1ull);
-			if (at < cap) out[at] = y;
 		}
 	}
 }

@@ -4048,7 +4048,7 @@ int gf2bv_probe_read(unsigned long long *wg, unsigned long long *un)
 // parts) and K (d - r vectors, zero linear parts, RREF over the product coordinates, pivots P).  Step 2: a choice c_a of the
 // A coefficients extends to a consistent point iff, at every product coordinate t outside P, v_t = XOR_{p in P} v_p K_p[t]
 // where v_s = l_i l_j ^ q_s -- one quadratic form in r variables per such t (k_quad_forms); affine forms are eliminated on
-// the host, one variable each.  Step 3: r_eff <= max_enum: k_quad_search + k_quad_check; above: relinearise (the forms are
+// the host, one variable each.  Step 3: r_eff <= max_enum: k_quad_search + k_forms_check<2>; above: relinearise (the forms are
 // the equations of a QuadraticSystem of r_eff unknowns, solved by this library) and repeat on that space while r_eff falls.
 namespace {
 
@@ -4439,7 +4439,7 @@ int quad_search_device(const u64 *forms, i64 m, i64 fw, int R, int device, hipSt
 	// removes no candidate, and leading forms of low rank are common -- pair coordinates over few variables come first)
 	const std::vector<i64> chosen = first_independent_forms(forms, m, fw);
 	std::vector<u64> tab((size_t)(1 + R + R * R), 0), E((size_t)(m * (R + 2)), 0);
-	for (i64 f = 0; f < m; f++) {                  // every form in k_quad_check's layout
+	for (i64 f = 0; f < m; f++) {                  // every form in k_forms_check<2>'s layout
 		u64 *e = &E[f * (R + 2)];
 		if (coef(f, 0)) e[0] = 1;
 		for (i64 k = 0; k < R; k++) {
@@ -4459,7 +4459,7 @@ int quad_search_device(const u64 *forms, i64 m, i64 fw, int R, int device, hipSt
 	}
 	const int H = std::max(0, std::min(R - 10, 18)), L = R - H;
 	const unsigned bd = (unsigned)std::min<u64>(256, ((1ull << H) + 63) / 64 * 64);
-	return search_two_pass({ tab, E, m, k_quad_search, k_quad_check, R, L, bd, (size_t)bd * L * 8, g_quad_times }, device, st, ys, total);
+	return search_two_pass({ tab, E, m, k_quad_search, k_forms_check<2>, R, L, bd, (size_t)bd * L * 8, g_quad_times }, device, st, ys, total);
 }
 
 int quad_plan_build(QuadPlan &P, const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n, int device, hipStream_t st)
@@ -4609,98 +4609,88 @@ int search_alloc(QuadTimes &times, int64_t dimension, int64_t words, int64_t max
 
 }  // namespace
 
-// ---- cubic search: the consistent points of a solution space over the degree-3 columns -----------------------------------
-//   A space x(c) = o ^ B c over n linear coordinates followed by the C(n,2) pair and the C(n,3) triple
-// coordinates (the columns of degree-3 XL and of PackedCubicSystem).  Step 1 is the quadratic search's with N = cols3 (quad_reduce,
-// quad_inputs).  Step 2: one CUBIC form in r variables per product coordinate outside P (k_cubic_products, k_cubic_forms).  Affine
-// forms are eliminated by re-parametrising: they are solved as a linear system, c_a = c_0 ^ G y over the free variables y, the affine
-// inputs are composed with that map and the forms rebuilt in fewer variables, until no affine form appears.  Step 3:
-// r_eff <= max_enum: k_cubic_search + k_cubic_check; above: the search gives up (there is no relinearisation level).
-//
-// The quartic search (gf2bv_quartic_search: the C(n,4) quadruple coordinates behind the triples, the columns of degree-4 XL and of
-// PackedQuarticSystem) is the same three steps at arity 4: the bodies below take the degree (FormsDegree, CubicPlan::arity), the
-// kernels under them are k_quartic_products (with k_cubic_forms), k_quartic_search and k_quartic_check.
+// ---- cubic and quartic search: the consistent points of a solution space over the columns of degree A = 3, 4 ---------------------
+//   A space x(c) = o ^ B c over n linear coordinates followed by the product coordinates of 2 .. A members:
+// C(n,2) pairs, C(n,3) triples (the columns of degree-3 XL and of PackedCubicSystem) and at A = 4 the C(n,4) quadruples (the columns of
+// degree-4 XL and of PackedQuarticSystem).  Step 1 is the quadratic search's with N = cols (quad_reduce, quad_inputs).  Step 2: one
+// form of degree A in r variables per product coordinate outside P (k_forms_products<A>, k_forms_sum).  Affine forms are eliminated by
+// re-parametrising: they are solved as a linear system, c_a = c_0 ^ G y over the free variables y, the affine inputs are composed with
+// that map and the forms rebuilt in fewer variables, until no affine form appears.  Step 3: r_eff <= max_enum: the degree's search
+// kernel (k_cubic_search, k_quartic_search) + k_forms_check<A>; above: the search gives up (there is no relinearisation level).
+// A degree is described once, by FormsDegree<A> below the bodies, which take it as their template parameter D.
 namespace {
 
-constexpr i64 kCubicMaxRank = 64;               // larger projection ranks are not reduced (a point of the forms is one word)
-constexpr i64 kCubicFormsBytes = 1ll << 30;     // what the forms of one build (products and forms) or of one search may take
-constexpr int kCubicMaxEnum = 40;
+constexpr i64 kFormsMaxRank = 64;               // larger projection ranks are not reduced (a point of the forms is one word)
+constexpr i64 kFormsBytes = 1ll << 30;          // what the forms of one build (products and forms) or of one search may take
+constexpr int kFormsMaxEnum = 40;
 constexpr int kCubicWalk = 12;                  // low variables a lane of k_cubic_search walks (78 words of LDS a lane)
-constexpr i64 kQuarticMaxRank = kCubicMaxRank;
-constexpr int kQuarticMaxEnum = kCubicMaxEnum;
 constexpr int kQuarticWalk = 12;                // ... and of k_quartic_search (298 words of LDS a lane, 149 KiB a workgroup)
+constexpr int kMaxArity = 4;                     // the highest degree: what a Monomial holds
 
 thread_local QuadTimes g_cubic_times, g_quartic_times;
 
-inline i64 cubic_width(i64 R) { return 1 + R + R * (R - 1) / 2 + R * (R - 1) * (R - 2) / 6; }
-inline i64 quartic_width(i64 R) { return cubic_width(R) + R * (R - 1) * (R - 2) * (R - 3) / 24; }
+// The layout of a form, of a space's columns and of the kernels' tables: the monomials in blocks by size, a monomial with members
+// m_0 < m_1 < ... at its block's start + SUM_t C(m_t, t + 1).  Every size below is a sum of binomials over a range of monomial sizes
+constexpr i64 binom(i64 h, int t)
+{
+	i64 c = 1;
+	for (int k = 1; k <= t; k++) c = c * (h - k + 1) / k;
+	return c;
+}
+constexpr i64 binom_sum(i64 h, int lo, int hi)  // SUM_{t = lo .. hi} C(h, t); block `size` of a form over R variables starts at (R, 0, size - 1)
+{
+	i64 s = 0;
+	for (int t = lo; t <= hi; t++) s += binom(h, t);
+	return s;
+}
+using Monomial = std::array<int, kMaxArity>;    // the members, largest first, -1 behind them
+i64 monomial_bit(i64 R, const Monomial &mm)     // its bit in a form over R variables
+{
+	int size = 0;
+	while (size < kMaxArity && mm[size] >= 0) size++;
+	i64 q = binom_sum(R, 0, size - 1);
+	for (int i = 0; i < size; i++) q += binom(mm[i], size - i);
+	return q;
+}
+// the monomials of `size` members over R variables in layout order: fn(the monomial, its place in the block)
+template <class Fn>
+void each_monomial(i64 R, int size, Fn fn)
+{
+	if (size > R) return;
+	Monomial mm;
+	mm.fill(-1);
+	for (int i = 0; i < size; i++) mm[i] = size - 1 - i;
+	for (i64 at = 0;; at++) {
+		fn(mm, at);
+		int i = size - 1;                           // the smallest member steps; one that reaches the member above starts again, and that one steps
+		while (i >= 0 && ++mm[i] == (i ? mm[i - 1] : (int)R)) { mm[i] = size - 1 - i; i--; }
+		if (i < 0) return;
+	}
+}
 
-struct CubicPlan : QuadPlan {                    // (lin, qaff: the affine inputs in the R variables left; M unused)
+struct CubicPlan : QuadPlan {                    // the plan of either degree (lin, qaff: the affine inputs in the R variables left; M unused)
+	explicit CubicPlan(int arity_) : arity(arity_) {}
+	const int arity;                             // members of a product coordinate at most: the degree's (FormsDegree<A>::plan)
 	std::vector<int> mem;                        // S x arity: the members of a product coordinate, -1 where it has fewer
 	std::vector<u64> lin0, qaff0;                // the affine inputs in the r coefficients c_a
 	std::vector<u64> amap;                       // r x W: c_a as an affine form in the R variables left (bit 0 constant, bit 1 + v)
 	i64 R = 0, rounds = 0;
-	int arity = 3;                               // the degree: members of a product coordinate at most
 };
-struct QuarticPlan : CubicPlan { QuarticPlan() { arity = 4; } };
 
-// What differs between the degree-3 and the degree-4 search below the entries: the plan's arity, the layout's width, the kernels with
-// the lane split and the second pass's words per form, the times and the messages
 using ProductsKernel = void (*)(const u64 *, const u64 *, const int *, int, int, int, u64 *);
-struct FormsDegree {
-	int arity;
-	i64 (*width)(i64);                           // bits of a form over R variables
-	i64 (*state_words)(i64);                     // words of LDS a lane of the search kernel keeps at a walk of L variables
-	i64 (*check_words)(i64);                     // words of a form in the check kernel's layout
-	ProductsKernel products;
-	SearchKernel search;
-	CheckKernel check;
-	int walk;
-	QuadTimes &(*times)();                       // (the calling thread's: the times are thread_local)
-	const char *nomem_build, *nomem_search, *bad_point;
-};
-constexpr i64 cubic_state_words(i64 L) { return L + L * (L - 1) / 2; }
-constexpr i64 quartic_state_words(i64 L) { return cubic_state_words(L) + L * (L - 1) * (L - 2) / 6; }
-inline i64 cubic_check_words(i64 R) { return 2 + R + R * (R - 1) / 2; }
-inline i64 quartic_check_words(i64 R) { return cubic_check_words(R) + R * (R - 1) * (R - 2) / 6; }
-QuadTimes &cubic_times() { return g_cubic_times; }
-QuadTimes &quartic_times() { return g_quartic_times; }
-const FormsDegree &cubic_degree()
-{
-	static const FormsDegree d = { 3, cubic_width, cubic_state_words, cubic_check_words, k_cubic_products, k_cubic_search, k_cubic_check,
-	                               kCubicWalk, cubic_times,
-	                               "the cubic forms of this space take more than 1 GiB", "the cubic forms of this search take more than 1 GiB",
-	                               "cubic search: a point that passed the forms is not consistent (internal error)" };
-	return d;
-}
-const FormsDegree &quartic_degree()
-{
-	static const FormsDegree d = { 4, quartic_width, quartic_state_words, quartic_check_words, k_quartic_products, k_quartic_search,
-	                               k_quartic_check, kQuarticWalk, quartic_times,
-	                               "the quartic forms of this space take more than 1 GiB", "the quartic forms of this search take more than 1 GiB",
-	                               "quartic search: a point that passed the forms is not consistent (internal error)" };
-	return d;
-}
 
 void cubic_reduce(CubicPlan &P, const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n)
 {
-	const i64 S2 = n * (n - 1) / 2, S3 = n * (n - 1) * (n - 2) / 6, S4 = P.arity == 4 ? n * (n - 1) * (n - 2) * (n - 3) / 24 : 0;
-	const int ar = P.arity;
-	quad_reduce(P, origin, basis, d, words, n, S2 + S3 + S4);
-	if (P.r > kCubicMaxRank) return;
+	const int arity = P.arity;
+	quad_reduce(P, origin, basis, d, words, n, binom_sum(n, 2, arity));
+	if (P.r > kFormsMaxRank) return;
 	quad_inputs(P);
 	P.lin0.swap(P.lin); P.qaff0.swap(P.qaff);
 	P.lin.assign(P.lin0.size(), 0); P.qaff.assign(P.qaff0.size(), 0);
-	P.mem.assign((size_t)(ar * std::max<i64>(P.S, 1)), -1);
-	for (i64 s = 0; s < S2; s++) { P.mem[ar * s] = P.pair_i[s]; P.mem[ar * s + 1] = P.pair_j[s]; }
-	i64 s = S2;
-	for (i64 i = 2; i < n; i++) for (i64 j = 1; j < i; j++) for (i64 l = 0; l < j; l++, s++) {
-		P.mem[ar * s] = (int)i; P.mem[ar * s + 1] = (int)j; P.mem[ar * s + 2] = (int)l;
-	}
-	if (S4)
-		for (i64 i = 3; i < n; i++) for (i64 j = 2; j < i; j++) for (i64 l = 1; l < j; l++) for (i64 p = 0; p < l; p++, s++) {
-			P.mem[ar * s] = (int)i; P.mem[ar * s + 1] = (int)j; P.mem[ar * s + 2] = (int)l; P.mem[ar * s + 3] = (int)p;
-		}
+	P.mem.assign((size_t)(arity * std::max<i64>(P.S, 1)), -1);
+	i64 s = 0;
+	for (int size = 2; size <= arity; size++)
+		each_monomial(n, size, [&](const Monomial &mm, i64) { std::copy(mm.begin(), mm.begin() + size, &P.mem[arity * s++]); });
 	P.R = P.r;
 	P.amap.assign((size_t)(std::max<i64>(P.r, 1) * P.W), 0);
 	for (i64 a = 0; a < P.r; a++) qflip(&P.amap[a * P.W], a + 1);
@@ -4719,29 +4709,19 @@ void cubic_compose(CubicPlan &P)
 	for (i64 s = 0; s < P.S; s++) cubic_compose_form(P, &P.qaff0[s * P.W], &P.qaff[s * P.W]);
 }
 
-// the host twin of k_cubic_products + k_cubic_forms (gf2bv_cubic_plan never touches a device): polynomial multiplication, monomial by
-// monomial, through a decode table of the layout
-// (quartic_forms_host: the same body at arity 4, the twin of k_quartic_products + k_cubic_forms)
+// the host twin of k_forms_products<A> + k_forms_sum at the plan's arity (gf2bv_*_plan never touches a device): polynomial
+// multiplication, monomial by monomial, through a decode table of the layout
 void cubic_forms_host(const CubicPlan &P, i64 fw, std::vector<u64> &F)
 {
 	const int ar = P.arity;
-	const i64 R = P.R, W = P.W, nb = ar == 4 ? quartic_width(R) : cubic_width(R), o2 = 1 + R, o3 = o2 + R * (R - 1) / 2, o4 = cubic_width(R);
-	std::vector<std::array<int, 4>> dec((size_t)nb, std::array<int, 4>{-1, -1, -1, -1});
-	for (i64 k = 0; k < R; k++) dec[1 + k] = {(int)k, -1, -1, -1};
-	for (i64 i = 1, q = o2; i < R; i++) for (i64 j = 0; j < i; j++, q++) dec[q] = {(int)i, (int)j, -1, -1};
-	for (i64 i = 2, q = o3; i < R; i++) for (i64 j = 1; j < i; j++) for (i64 l = 0; l < j; l++, q++) dec[q] = {(int)i, (int)j, (int)l, -1};
-	if (ar == 4)
-		for (i64 i = 3, q = o4; i < R; i++) for (i64 j = 2; j < i; j++) for (i64 l = 1; l < j; l++) for (i64 p = 0; p < l; p++, q++)
-			dec[q] = {(int)i, (int)j, (int)l, (int)p};
-	auto with = [&](std::array<int, 4> mm, int v) -> i64 {      // the bit of the monomial mm (at most arity - 1 members) times x_v
-		if (mm[0] != v && mm[1] != v && mm[2] != v) { mm[3] = v; std::sort(mm.begin(), mm.end(), std::greater<int>()); }
-		if (mm[0] < 0) return 0;
-		if (mm[1] < 0) return 1 + mm[0];
-		if (mm[2] < 0) return o2 + (i64)mm[0] * (mm[0] - 1) / 2 + mm[1];
-		const i64 t3 = (i64)mm[0] * (mm[0] - 1) * (mm[0] - 2) / 6 + (i64)mm[1] * (mm[1] - 1) / 2 + mm[2];
-		if (mm[3] < 0) return o3 + t3;
-		return o4 + (i64)mm[0] * (mm[0] - 1) * (mm[0] - 2) * (mm[0] - 3) / 24 + (i64)mm[1] * (mm[1] - 1) * (mm[1] - 2) / 6
-		       + (i64)mm[2] * (mm[2] - 1) / 2 + mm[3];
+	const i64 R = P.R, W = P.W;
+	std::vector<Monomial> dec((size_t)binom_sum(R, 0, ar));
+	for (int size = 0; size <= ar; size++)
+		each_monomial(R, size, [&](const Monomial &mm, i64 at) { dec[binom_sum(R, 0, size - 1) + at] = mm; });
+	auto with = [&](Monomial mm, int v) -> i64 {               // the bit of the monomial mm times x_v; mm has at most arity - 1 members
+		                                                           // (a product of fewer than arity forms), so its last slot is free
+		if (std::find(mm.begin(), mm.end(), v) == mm.end()) { mm[kMaxArity - 1] = v; std::sort(mm.begin(), mm.end(), std::greater<int>()); }
+		return monomial_bit(R, mm);
 	};
 	auto mul = [&](const std::vector<u64> &f, const u64 *aff, std::vector<u64> &out) {      // f of degree <= 2 times an affine form
 		std::fill(out.begin(), out.end(), 0);
@@ -4781,7 +4761,7 @@ int cubic_forms_device(const CubicPlan &P, ProductsKernel products, i64 fw, std:
 	HIPCHK(hipMemcpyAsync(dsi.p, P.sup_idx.data(), P.sup_idx.size() * 4, hipMemcpyHostToDevice, st));
 	products<<<dim3((unsigned)P.S), dim3(256), 0, st>>>(dl.as<u64>(), dq.as<u64>(), dm.as<int>(), (int)P.R, (int)P.W, (int)fw, dv.as<u64>());
 	HIPCHK(hipGetLastError());
-	k_cubic_forms<<<dim3((unsigned)P.m0), dim3(256), 0, st>>>(dv.as<u64>(), dso.as<i64>(), dsi.as<int>(), (int)fw, dout.as<u64>());
+	k_forms_sum<<<dim3((unsigned)P.m0), dim3(256), 0, st>>>(dv.as<u64>(), dso.as<i64>(), dsi.as<int>(), (int)fw, dout.as<u64>());
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipMemcpyAsync(F.data(), dout.p, (size_t)(P.m0 * fw) * 8, hipMemcpyDeviceToHost, st));
 	HIPCHK(hipStreamSynchronize(st));
@@ -4841,27 +4821,27 @@ bool cubic_affine_round(CubicPlan &P, i64 fw, const std::vector<u64> &F)
 	return true;
 }
 
-int forms_plan_build(const FormsDegree &D, CubicPlan &P, const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n, int device,
-                     hipStream_t st)
+template <class D>
+int forms_plan_build(CubicPlan &P, const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n, int device, hipStream_t st)
 {
 	auto t0 = std::chrono::steady_clock::now();
 	cubic_reduce(P, origin, basis, d, words, n);
-	D.times().reduce += ms_since(t0);
-	if (P.r > kCubicMaxRank) { P.reff = -1; return GF2BV_OK; }
+	D::times().reduce += ms_since(t0);
+	if (P.r > kFormsMaxRank) { P.reff = -1; return GF2BV_OK; }
 	std::vector<u64> F;
 	i64 fw = 1;
 	for (;;) {
 		t0 = std::chrono::steady_clock::now();
 		cubic_compose(P);
-		fw = (D.width(P.R) + 63) / 64;
-		if ((P.S + P.m0) * fw * 8 > kCubicFormsBytes) return fail(GF2BV_ERR_NOMEM, D.nomem_build);
+		fw = (D::width(P.R) + 63) / 64;
+		if ((P.S + P.m0) * fw * 8 > kFormsBytes) return fail(GF2BV_ERR_NOMEM, D::kNomemBuildText);
 		if (device < 0) cubic_forms_host(P, fw, F);
-		else { int rc = cubic_forms_device(P, D.products, fw, F, device, st); if (rc) return rc; }
-		D.times().forms += ms_since(t0);
+		else { int rc = cubic_forms_device(P, D::kProducts, fw, F, device, st); if (rc) return rc; }
+		D::times().forms += ms_since(t0);
 		t0 = std::chrono::steady_clock::now();
 		P.rounds++;
 		const bool changed = cubic_affine_round(P, fw, F);
-		D.times().affine += ms_since(t0);
+		D::times().affine += ms_since(t0);
 		if (P.inconsistent) { P.reff = 0; P.fw = 1; P.m = 1; P.forms.assign(1, 1); return GF2BV_OK; }
 		if (!changed) break;
 	}
@@ -4872,21 +4852,12 @@ int forms_plan_build(const FormsDegree &D, CubicPlan &P, const u64 *origin, cons
 	if (P.forms.empty()) P.forms.assign((size_t)fw, 0);
 	return GF2BV_OK;
 }
-int cubic_plan_build(CubicPlan &P, const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n, int device, hipStream_t st)
-{
-	return forms_plan_build(cubic_degree(), P, origin, basis, d, words, n, device, st);
-}
-int quartic_plan_build(QuarticPlan &P, const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n, int device, hipStream_t st)
-{
-	return forms_plan_build(quartic_degree(), P, origin, basis, d, words, n, device, st);
-}
 
-// the point of the space that effective assignment y (reff <= 64 bits) extends to; c_orig: its coefficients (dw words)
-// (quartic_point: the same body, the products of a QuarticPlan having up to four members)
-bool cubic_point(const CubicPlan &P, u64 y, u64 *x, u64 *c_orig)
+// the point of the space that effective assignment y[0] (reff <= 64 bits) extends to; c_orig: its coefficients (dw words)
+bool cubic_point(const CubicPlan &P, const u64 *y, u64 *x, u64 *c_orig)
 {
 	const i64 r = P.r, W = P.W, words = P.words;
-	const u64 ye[2] = {1ull | (y << 1), y >> 63};
+	const u64 ye[2] = {1ull | (y[0] << 1), y[0] >> 63};
 	std::copy(P.origin.begin(), P.origin.end(), x);
 	std::fill(c_orig, c_orig + P.dw, 0);
 	for (i64 a = 0; a < r; a++) {
@@ -4908,16 +4879,15 @@ bool cubic_point(const CubicPlan &P, u64 y, u64 *x, u64 *c_orig)
 	return true;
 }
 
-// every common zero of m cubic forms (equation-int layout, fw words) in R <= kCubicMaxEnum variables (total, ys: search_two_pass).  Only
-// the forms outside the first pass go into E: with none left the driver reads the candidates as the zeros
-int forms_search_device(const FormsDegree &D, const u64 *forms, i64 m, i64 fw, int R, int device, hipStream_t st, std::vector<u64> &ys,
-                        u64 *total)
+// every common zero of m forms of degree D::kArity (equation-int layout, fw words) in R <= kFormsMaxEnum variables (total, ys:
+// search_two_pass).  Only the forms outside the first pass go into E: with none left the driver reads the candidates as the zeros
+template <class D>
+int forms_search_device(const u64 *forms, i64 m, i64 fw, int R, int device, hipStream_t st, std::vector<u64> &ys, u64 *total)
 {
 	ys.clear();
 	if (m == 0) { search_whole_cube(R, ys, total); return GF2BV_OK; }
-	const i64 nb = D.width(R), o2 = 1 + R, o3 = o2 + (i64)R * (R - 1) / 2, o4 = cubic_width(R);
-	const i64 ew = D.check_words(R);
-	if (m * ew * 8 > kCubicFormsBytes) return fail(GF2BV_ERR_NOMEM, D.nomem_search);
+	const i64 nb = D::width(R), ew = D::check_words(R);
+	if (m * ew * 8 > kFormsBytes) return fail(GF2BV_ERR_NOMEM, D::kNomemSearchText);
 	const std::vector<i64> chosen = first_independent_forms(forms, m, fw);
 	// the second pass tests the forms the first did not hold (a chosen form vanishes at every candidate; a zero form everywhere)
 	std::vector<char> in_first((size_t)m, 0);
@@ -4925,96 +4895,84 @@ int forms_search_device(const FormsDegree &D, const u64 *forms, i64 m, i64 fw, i
 	std::vector<i64> rest;
 	for (i64 f = 0; f < m; f++) if (!in_first[f] && !qzero(forms + f * fw, fw)) rest.push_back(f);
 	const i64 mr = (i64)rest.size();
+	// where bit q of a form goes in k_forms_check's layout: the largest member of its monomial is the bit, and the word is 1 + the bit
+	// of the other members' monomial, one size smaller (the constant: bit 0 of word 0).  Built once a call, and only when a form is left
+	// for the second pass
+	std::vector<std::pair<i64, int>> slot(mr ? (size_t)nb : 0, {0, 0});
+	for (int size = 1; mr && size <= D::kArity; size++)
+		each_monomial(R, size, [&](const Monomial &mm, i64 at) {
+			Monomial others;
+			others.fill(-1);
+			std::copy(mm.begin() + 1, mm.end(), others.begin());
+			slot[binom_sum(R, 0, size - 1) + at] = {1 + monomial_bit(R, others), mm[0]};
+		});
 	std::vector<u64> tab((size_t)nb, 0), E((size_t)(std::max<i64>(mr, 1) * ew), 0);
-	for (i64 g = 0; g < mr; g++) {                 // in k_cubic_check's layout
+	for (i64 g = 0; g < mr; g++) {
 		const u64 *src = forms + rest[g] * fw;
-		u64 *e = &E[g * ew];
-		e[0] = src[0] & 1;
-		for (i64 k = 0; k < R; k++) if (qbit(src, 1 + k)) e[1] |= 1ull << k;
-		for (i64 k = 1, q = o2; k < R; k++) for (i64 j = 0; j < k; j++, q++) if (qbit(src, q)) e[2 + j] |= 1ull << k;
-		for (i64 l = 2, q = o3; l < R; l++) for (i64 k = 1; k < l; k++) for (i64 j = 0; j < k; j++, q++)
-			if (qbit(src, q)) e[2 + R + k * (k - 1) / 2 + j] |= 1ull << l;
-		if (D.arity == 4)
-			for (i64 p = 3, q = o4; p < R; p++) for (i64 l = 2; l < p; l++) for (i64 k = 1; k < l; k++) for (i64 j = 0; j < k; j++, q++)
-				if (qbit(src, q)) e[o3 + 1 + l * (l - 1) * (l - 2) / 6 + k * (k - 1) / 2 + j] |= 1ull << p;
+		for (i64 q = 0; q < nb; q++) if (qbit(src, q)) E[g * ew + slot[q].first] |= 1ull << slot[q].second;
 	}
 	for (size_t c = 0; c < chosen.size(); c++) {   // the chosen ones bit-sliced: bit c of every word; tab is indexed like a form's bits
 		const u64 *src = forms + chosen[c] * fw;
 		for (i64 q = 0; q < nb; q++) if (qbit(src, q)) tab[q] |= 1ull << c;
 	}
-	const int L = std::min(R, D.walk);
-	const size_t lds = (size_t)64 * 8 * D.state_words(L), lds_max = (size_t)64 * 8 * D.state_words(D.walk);
-	if (lds_max > 65536) {                         // (k_quartic_search only: 149 KiB at its full walk; raised once, to the kernel's maximum)
+	const int L = std::min(R, D::kWalk);
+	constexpr size_t lds_max = (size_t)64 * 8 * D::state_words(D::kWalk);
+	const size_t lds = (size_t)64 * 8 * D::state_words(L);
+	if constexpr (lds_max > 65536) {               // (k_quartic_search only: 149 KiB at its full walk; raised once, to the kernel's maximum)
 		static std::mutex mu;
 		static std::map<int, bool> raised;         // device -> the > 64 KiB dynamic-LDS attribute has been raised there
 		std::lock_guard<std::mutex> lk(mu);
 		if (!raised[device]) {
-			HIPCHK(hipFuncSetAttribute((const void *)D.search, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+			HIPCHK(hipFuncSetAttribute((const void *)D::kSearch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
 			raised[device] = true;
 		}
 	}
-	return search_two_pass({ tab, E, mr, D.search, D.check, R, L, 64, lds, D.times() }, device, st, ys, total);
-}
-int cubic_search_device(const u64 *forms, i64 m, i64 fw, int R, int device, hipStream_t st, std::vector<u64> &ys, u64 *total)
-{
-	return forms_search_device(cubic_degree(), forms, m, fw, R, device, st, ys, total);
-}
-int quartic_search_device(const u64 *forms, i64 m, i64 fw, int R, int device, hipStream_t st, std::vector<u64> &ys, u64 *total)
-{
-	return forms_search_device(quartic_degree(), forms, m, fw, R, device, st, ys, total);
+	return search_two_pass({ tab, E, mr, D::kSearch, D::kCheck, R, L, 64, lds, D::times() }, device, st, ys, total);
 }
 
 // every consistent point of the space and its coefficients: quad_collect without the relinearisation level
-int forms_collect(const FormsDegree &D, CubicPlan &P, const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n, int max_enum, int device,
-                  hipStream_t st, std::vector<u64> &pts, std::vector<u64> &coef, u64 *total, i64 *lin_rank, bool *gave_up)
+template <class D>
+int forms_collect(const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n, int max_enum, int device, hipStream_t st,
+                  std::vector<u64> &pts, std::vector<u64> &coef, u64 *total, i64 *lin_rank, bool *gave_up)
 {
 	pts.clear(); coef.clear(); *total = 0;
-	int rc = forms_plan_build(D, P, origin, basis, d, words, n, device, st);
-	D.times().levels = P.rounds;
+	CubicPlan P = D::plan();
+	int rc = forms_plan_build<D>(P, origin, basis, d, words, n, device, st);
+	D::times().levels = P.rounds;
 	*lin_rank = P.r;
 	if (rc) return rc;
 	if (P.reff < 0 || (!P.inconsistent && P.reff > max_enum)) { *gave_up = true; return GF2BV_OK; }
 	if (P.inconsistent) return GF2BV_OK;
 	std::vector<u64> ys;
 	auto t0 = std::chrono::steady_clock::now();
-	rc = forms_search_device(D, P.forms.data(), P.m, P.fw, (int)P.reff, device, st, ys, total);
-	D.times().search += ms_since(t0);
+	rc = forms_search_device<D>(P.forms.data(), P.m, P.fw, (int)P.reff, device, st, ys, total);
+	D::times().search += ms_since(t0);
 	if (rc) return rc;
 	if ((i64)*total > kQuadMaxPoints) return GF2BV_OK;
 	const i64 np = (i64)ys.size();
 	pts.assign((size_t)(np * words), 0);
 	coef.assign((size_t)(np * P.dw), 0);
 	for (i64 k = 0; k < np; k++)
-		if (!cubic_point(P, ys[k], &pts[k * words], &coef[k * P.dw])) return fail(GF2BV_ERR_HIP, D.bad_point);
+		if (!cubic_point(P, &ys[k], &pts[k * words], &coef[k * P.dw])) return fail(GF2BV_ERR_HIP, D::kBadPointText);
 	return GF2BV_OK;
 }
-int cubic_collect(const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n, int max_enum, int device, hipStream_t st,
-                  std::vector<u64> &pts, std::vector<u64> &coef, u64 *total, i64 *lin_rank, bool *gave_up)
-{
-	CubicPlan P;
-	return forms_collect(cubic_degree(), P, origin, basis, d, words, n, max_enum, device, st, pts, coef, total, lin_rank, gave_up);
-}
-int quartic_collect(const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n, int max_enum, int device, hipStream_t st,
-                    std::vector<u64> &pts, std::vector<u64> &coef, u64 *total, i64 *lin_rank, bool *gave_up)
-{
-	QuarticPlan P;
-	return forms_collect(quartic_degree(), P, origin, basis, d, words, n, max_enum, device, st, pts, coef, total, lin_rank, gave_up);
-}
 
-// ---- the entries of both searches: each body once, over what a degree is --------------------------------------------------------
-// Plan: the plan type.  kMaxLin, kLinText, cols, kWordsText: the space check.  kPointWords: the words of an assignment a point is
-// read from, 0 for as many as cover r_eff bits.  width: the bits of a form over R variables.  build, point, search, collect: the plan
-// build, the point function, the device search and the collection of every consistent point.  times: the QuadTimes it writes
+// ---- what a degree is, once: the entries below and the bodies above take it as D ---------------------------------------------------
+// Plan, plan(): the plan type and a fresh plan of the degree.  kArity: members of a product coordinate at most; the sizes follow from it (binom_sum): cols, the columns of a
+// space over n linear coordinates, and width, the bits of a form over R variables.  kMaxLin, kLinText, kWordsText: the space check.
+// kPointWords: the words of an assignment a point is read from, 0 for as many as cover r_eff bits.  build, point, search, collect:
+// the plan build, the point function, the device search and the collection of every consistent point.  times: the QuadTimes it writes
 struct QuadDegree {
 	using Plan = QuadPlan;
+	static Plan plan() { return Plan(); }
+	static constexpr int kArity = 2, kMaxEnum = kQuadMaxEnum;
 	static constexpr i64 kMaxLin = 46340, kPointWords = 0;
-	static constexpr int kMaxEnum = kQuadMaxEnum;
 	static constexpr const char *kLinText = "n_lin must be 1..46340", *kWordsText = "words does not cover n_lin + n_lin(n_lin-1)/2 columns";
-	static i64 cols(i64 n) { return n + n * (n - 1) / 2; }
-	static i64 width(i64 R) { return 1 + R + R * (R - 1) / 2; }
+	static constexpr i64 cols(i64 n) { return binom_sum(n, 1, kArity); }
+	static constexpr i64 width(i64 R) { return binom_sum(R, 0, kArity); }
 	static QuadTimes &times() { return g_quad_times; }
 	static constexpr auto build = quad_plan_build;
-	static bool point(const Plan &P, const u64 *y, u64 *x, u64 *c) { return quad_point(P, y, x, c); }
+	static constexpr auto point = quad_point;
 	static constexpr auto search = quad_search_device;
 	static int collect(const u64 *origin, const u64 *basis, i64 d, i64 words, i64 n, int max_enum, int device, hipStream_t st,
 	                   std::vector<u64> &pts, std::vector<u64> &coef, u64 *total, i64 *lin_rank, bool *gave_up)
@@ -5022,34 +4980,54 @@ struct QuadDegree {
 		return quad_collect(origin, basis, d, words, n, max_enum, device, st, 0, 0, pts, coef, total, lin_rank, gave_up);
 	}
 };
-struct CubicDegree {
-	using Plan = CubicPlan;
-	static constexpr i64 kMaxLin = 2000, kPointWords = 1;
-	static constexpr int kMaxEnum = kCubicMaxEnum;
-	static constexpr const char *kLinText = "n_lin must be 1..2000", *kWordsText = "words does not cover n_lin + C(n_lin,2) + C(n_lin,3) columns";
-	static i64 cols(i64 n) { return n + n * (n - 1) / 2 + n * (n - 1) * (n - 2) / 6; }
-	static i64 width(i64 R) { return cubic_width(R); }
+// Degrees 3 and 4 share their bodies (forms_plan_build, cubic_point, forms_search_device, forms_collect), so FormsDegree<A> computes
+// what follows from A and FormsFacts<A> states the rest: the space check, the walk and its tuned search kernel, the times, the messages.
+// state_words: words of LDS a lane of the search kernel keeps at a walk of L variables.  check_words: words of a form in k_forms_check's
+// layout.  A further degree is a FormsFacts, kMaxArity raised to it, and a level in each of form_value, qs_c / qs_off / qs_root under
+// k_forms_products and its search kernel
+template <int A> struct FormsFacts;
+template <> struct FormsFacts<3> {
+	static constexpr i64 kMaxLin = 2000;
+	static constexpr int kWalk = kCubicWalk;
+	static constexpr SearchKernel kSearch = k_cubic_search;
 	static QuadTimes &times() { return g_cubic_times; }
-	static constexpr auto build = cubic_plan_build;
-	static bool point(const Plan &P, const u64 *y, u64 *x, u64 *c) { return cubic_point(P, y[0], x, c); }
-	static constexpr auto search = cubic_search_device;
-	static constexpr auto collect = cubic_collect;
+	static constexpr const char *kLinText = "n_lin must be 1..2000", *kWordsText = "words does not cover n_lin + C(n_lin,2) + C(n_lin,3) columns",
+	                            *kNomemBuildText = "the cubic forms of this space take more than 1 GiB",
+	                            *kNomemSearchText = "the cubic forms of this search take more than 1 GiB",
+	                            *kBadPointText = "cubic search: a point that passed the forms is not consistent (internal error)";
 };
-struct QuarticDegree {
-	using Plan = QuarticPlan;
-	static constexpr i64 kMaxLin = 450, kPointWords = 1;
-	static constexpr int kMaxEnum = kQuarticMaxEnum;
-	static constexpr const char *kLinText = "n_lin must be 1..450",
-	                            *kWordsText = "words does not cover n_lin + C(n_lin,2) + C(n_lin,3) + C(n_lin,4) columns";
-	static i64 cols(i64 n) { return CubicDegree::cols(n) + n * (n - 1) * (n - 2) * (n - 3) / 24; }
-	static i64 width(i64 R) { return quartic_width(R); }
+template <> struct FormsFacts<4> {
+	static constexpr i64 kMaxLin = 450;
+	static constexpr int kWalk = kQuarticWalk;
+	static constexpr SearchKernel kSearch = k_quartic_search;
 	static QuadTimes &times() { return g_quartic_times; }
-	static constexpr auto build = quartic_plan_build;
-	static bool point(const Plan &P, const u64 *y, u64 *x, u64 *c) { return cubic_point(P, y[0], x, c); }
-	static constexpr auto search = quartic_search_device;
-	static constexpr auto collect = quartic_collect;
+	static constexpr const char *kLinText = "n_lin must be 1..450",
+	                            *kWordsText = "words does not cover n_lin + C(n_lin,2) + C(n_lin,3) + C(n_lin,4) columns",
+	                            *kNomemBuildText = "the quartic forms of this space take more than 1 GiB",
+	                            *kNomemSearchText = "the quartic forms of this search take more than 1 GiB",
+	                            *kBadPointText = "quartic search: a point that passed the forms is not consistent (internal error)";
 };
-static_assert((size_t)64 * 8 * quartic_state_words(kQuarticWalk) <= 160 * 1024, "the walk's state fits a CU's LDS");
+template <int A>
+struct FormsDegree : FormsFacts<A> {
+	static_assert(A >= 3 && A <= kMaxArity, "a Monomial holds kMaxArity members");
+	using Plan = CubicPlan;
+	static Plan plan() { return Plan(A); }
+	static constexpr int kArity = A, kMaxEnum = kFormsMaxEnum;
+	static constexpr i64 kPointWords = 1;
+	static constexpr i64 cols(i64 n) { return binom_sum(n, 1, A); }
+	static constexpr i64 width(i64 R) { return binom_sum(R, 0, A); }
+	static constexpr i64 state_words(i64 L) { return binom_sum(L, 1, A - 1); }
+	static constexpr i64 check_words(i64 R) { return 1 + binom_sum(R, 0, A - 1); }
+	static constexpr ProductsKernel kProducts = k_forms_products<A>;
+	static constexpr CheckKernel kCheck = k_forms_check<A>;
+	static constexpr auto build = forms_plan_build<FormsDegree>;
+	static constexpr auto point = cubic_point;
+	static constexpr auto search = forms_search_device<FormsDegree>;
+	static constexpr auto collect = forms_collect<FormsDegree>;
+};
+using CubicDegree = FormsDegree<3>;
+using QuarticDegree = FormsDegree<4>;
+static_assert((size_t)64 * 8 * QuarticDegree::state_words(kQuarticWalk) <= 160 * 1024, "the walk's state fits a CU's LDS");
 static_assert(QuadDegree::kMaxEnum == 40 && CubicDegree::kMaxEnum == 40 && QuarticDegree::kMaxEnum == 40, "the entries' messages name 40");
 
 template <class D>
@@ -5078,7 +5056,7 @@ int search_plan(const uint64_t *origin_, const uint64_t *basis_, int64_t dimensi
 		HIPCHK(pool().stream(&st, device, 0));
 		keep.reset(st);
 	}
-	typename D::Plan P;
+	typename D::Plan P = D::plan();
 	rc = D::build(P, origin, basis, dimension, words, n_lin, device, st);
 	if (rc) return rc;
 	quad_plan_export(P, r, r_eff, m, form_words, forms_, forms_cap);
@@ -5096,7 +5074,7 @@ int search_points(const uint64_t *origin_, const uint64_t *basis_, int64_t dimen
 	if (rc) return rc;
 	if (nys < 0 || (nys > 0 && (!ys || !out_words))) return fail(GF2BV_ERR_ARG, "null pointer");
 	if (D::kPointWords && y_words < D::kPointWords) return fail(GF2BV_ERR_ARG, "y_words does not cover r_eff bits");
-	typename D::Plan P;
+	typename D::Plan P = D::plan();
 	rc = D::build(P, origin, basis, dimension, words, n_lin, -1, nullptr);
 	if (rc) return rc;
 	if (P.reff < 0 || P.inconsistent) return fail(GF2BV_ERR_ARG, "the space has no forms to map from");

@@ -691,7 +691,7 @@ def quad_last_times() -> dict:
 
 def cubic_plan(origin: int, basis, n_lin: int, device: int | None = None) -> dict:
     """gf2bv_cubic_plan (host only): r, r_eff (-1: r above 64, not reduced), and the forms as equation ints of a PackedCubicSystem of
-    r_eff unknowns.  With a device: gf2bv_cubic_plan_device, the forms built by k_cubic_products / k_cubic_forms on that device."""
+    r_eff unknowns.  With a device: gf2bv_cubic_plan_device, the forms built by k_forms_products<3> / k_forms_sum on that device."""
     return _search_plan("cubic", origin, basis, n_lin, device)
 
 
@@ -712,7 +712,7 @@ def cubic_last_times() -> dict:
 
 def quartic_plan(origin: int, basis, n_lin: int, device: int | None = None) -> dict:
     """gf2bv_quartic_plan (host only): r, r_eff (-1: r above 64, not reduced), and the forms as equation ints of a PackedQuarticSystem
-    of r_eff unknowns.  With a device: gf2bv_quartic_plan_device, the forms built by k_quartic_products / k_cubic_forms on that device."""
+    of r_eff unknowns.  With a device: gf2bv_quartic_plan_device, the forms built by k_forms_products<4> / k_forms_sum on that device."""
     return _search_plan("quartic", origin, basis, n_lin, device)
 
 

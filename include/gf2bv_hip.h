@@ -349,7 +349,7 @@ void gf2bv_quad_last_times(double *out8);
  * space is reduced to CUBIC forms in r_eff variables whose common zeros are exactly the consistent points.
  * The entries mirror the quadratic ones above one for one -- same arguments, same results, same order of the points, the same
  * 2^22 cap on collected points, max_enum 0..40, points released with gf2bv_quad_free -- with these differences:
- *  - r (the rank of the projection onto the linear coordinates) is reduced up to kCubicMaxRank = 64: a point of the forms is one word.
+ *  - r (the rank of the projection onto the linear coordinates) is reduced up to kFormsMaxRank = 64: a point of the forms is one word.
  *    Above it gf2bv_cubic_search gives up (*count = -1) and gf2bv_cubic_plan says r_eff = -1.
  *  - There is no relinearisation level: r_eff > max_enum gives up.  (r_eff <= r <= n_lin: with n_lin <= max_enum it never does.)
  *  - The forms are the equation ints of a PackedCubicSystem of r_eff unknowns: bit 0 the constant, bit 1 + k unknown k, bit

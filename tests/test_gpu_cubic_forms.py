@@ -1,10 +1,10 @@
-"""The kernels under search_all_xl / search_all_cubic -- k_cubic_products, k_cubic_forms, k_cubic_search, k_cubic_check -- on the
+"""The kernels under search_all_xl / search_all_cubic -- k_forms_products<3>, k_forms_sum, k_cubic_search, k_forms_check<3> -- on the
 MI355X against the host reference of tests/cubic_forms.py (set-of-monomials products and numpy; tests/test_cubic_search_cpu.py
 checks it where no GPU exists).
 
 Every search case calls hip.cubic_forms_search and compares (count, zeros) exactly with a zero set that is known by construction
 (forms written where their zeros are obvious, then carried through a random invertible affine map, so that they are dense in every
-unknown and every degree, the lanes' high unknowns included) or with a numpy walk.  The launch shapes of cubic_search_device:
+unknown and every degree, the lanes' high unknowns included) or with a numpy walk.  The launch shapes of forms_search_device:
 L = min(R, 12) low unknowns walked in Gray order, H = R - L high ones fixed per lane, one wavefront per workgroup -- so every R is
 its own shape: H = 0 with a single live lane up to R = 12, a partial workgroup up to R = 17, whole workgroups from R = 18."""
 import functools
@@ -59,7 +59,7 @@ def _lane_case(R: int) -> tuple:
 
 
 def test_lane_cases_cover_the_form_counts():
-    """m = 1, 63, 64, 65 and 140 (k_cubic_check: forms over the 64 lanes of a wave), forms in natural and in shuffled order"""
+    """m = 1, 63, 64, 65 and 140 (k_forms_check<3>: forms over the 64 lanes of a wave), forms in natural and in shuffled order"""
     ms = {R: len(_lane_case(R)[0]) for R in range(R_MAX + 1)}
     assert {1, 63, 64, 65, 140} <= set(ms.values()), ms
     assert [len(_lane_case(R)[1]) for R in (0, 1, 2, 3)] == [1, 1, 2, 7]
@@ -120,7 +120,7 @@ def test_seventy_copies_of_one_form_first():
 def test_candidate_cap(nz, fused):
     """R = 30.  In y the first 64 forms are y_k for k in Z = {22 .. 22 + nz - 1}, then products y_k y_l y_0 (k in Z, l in 1 .. 21): 64
     independent forms whose common zeros are the subspace y_Z = 0.  |Z| = 8: exactly 2^22 first-pass candidates, which the list
-    still holds (k_cubic_check); |Z| = 7: 2^23, twice what it holds (the fused pass).  The forms behind them leave the 29 points of
+    still holds (k_forms_check<3>); |Z| = 7: 2^23, twice what it holds (the fused pass).  The forms behind them leave the 29 points of
     weight <= 2 on y_0 .. y_6 with y_7 .. y_21 = 0 in both cases."""
     R = 30
     rng = random.Random(5400 + nz)
@@ -163,7 +163,7 @@ def test_point_cap_exceeded():
         hip.cubic_forms_search([f], 24, max_out=16)
 
 
-# -- k_cubic_products / k_cubic_forms against their host twin -----------------------------------------------------------------------
+# -- k_forms_products<3> / k_forms_sum against their host twin -----------------------------------------------------------------------
 def _rank(vecs) -> int:
     piv = {}
     for v in vecs:
@@ -201,7 +201,7 @@ PLAN_CASES = [(5, 0, 4, 3), (9, 0, 0, 0), (12, 10, 3, 40), (12, 11, 0, 0), (13, 
 
 @pytest.mark.parametrize("n,r,k,kbits", PLAN_CASES, ids=lambda v: str(v))
 def test_forms_kernels_equal_host_twin(n, r, k, kbits):
-    """hip.cubic_plan with a device (k_cubic_products: Moebius sums per monomial; k_cubic_forms: XOR over the supports) == without
+    """hip.cubic_plan with a device (k_forms_products<3>: Moebius sums per monomial; k_forms_sum: XOR over the supports) == without
     (cubic_forms_host: monomial-by-monomial products), the whole dict.  What pins the twin itself is the brute force of
     tests/test_cubic_search_cpu.py at n <= 10."""
     rng = random.Random(5600 + 7 * n + r + k)

@@ -1,4 +1,4 @@
-"""The three kernels under search_all / search_one -- k_quad_forms, k_quad_search, k_quad_check -- on the MI355X against the
+"""The three kernels under search_all / search_one -- k_quad_forms, k_quad_search, k_forms_check<2> -- on the MI355X against the
 host reference of tests/quad_forms.py (plain ints and numpy; tests/test_quad_forms_cpu.py checks it where no GPU exists).
 
 Every search case calls hip.quad_forms_search and compares (count, zeros) exactly with a zero set that is known by construction
@@ -65,7 +65,7 @@ def _lane_case(R: int) -> tuple:
 
 
 def test_lane_cases_cover_the_form_counts():
-    """m = 1, 63, 64, 65 and one value above 128 (k_quad_check: forms over the 64 lanes of a wave), zero sets of 8 .. a few hundred"""
+    """m = 1, 63, 64, 65 and one value above 128 (k_forms_check<2>: forms over the 64 lanes of a wave), zero sets of 8 .. a few hundred"""
     ms = {R: len(_lane_case(R)[0]) for R in LANE_CASES}
     assert {1, 63, 64, 65} <= set(ms.values()) and max(ms.values()) > 128, ms
     assert all(8 <= len(_lane_case(R)[1]) <= 400 for R in LANE_CASES if R > 3)
@@ -124,7 +124,7 @@ def test_seventy_copies_of_one_form_first():
 def test_candidate_cap(nz, fused):
     """R = 30.  In y the first 64 forms are y_k for k in Z = {22 .. 22 + nz - 1}, then products y_k y_l (k in Z, l < 22): 64
     independent forms whose common zeros are the subspace y_Z = 0.  |Z| = 8: exactly 2^22 first-pass candidates, which the list
-    still holds (k_quad_check strides them over 8192 waves); |Z| = 7: 2^23, twice what it holds (the fused pass).  The forms behind them leave the 23 points of weight <= 1 on y_0 .. y_21 in both cases."""
+    still holds (k_forms_check<2> strides them over 8192 waves); |Z| = 7: 2^23, twice what it holds (the fused pass).  The forms behind them leave the 23 points of weight <= 1 on y_0 .. y_21 in both cases."""
     R = 30
     rng = random.Random(4300 + nz)
     dm = QF.DenseMap(rng, R)

@@ -1,5 +1,5 @@
-"""The kernels under search_all_xl4 / search_all_quartic -- k_quartic_products (with k_cubic_forms), k_quartic_search,
-k_quartic_check -- on the MI355X against the host reference of tests/quartic_forms.py (set-of-monomials products and numpy;
+"""The kernels under search_all_xl4 / search_all_quartic -- k_forms_products<4> (with k_forms_sum), k_quartic_search,
+k_forms_check<4> -- on the MI355X against the host reference of tests/quartic_forms.py (set-of-monomials products and numpy;
 tests/test_quartic_search_cpu.py checks it where no GPU exists).
 
 Every search case calls hip.quartic_forms_search and compares (count, zeros) exactly with a zero set that is known by construction
@@ -65,7 +65,7 @@ def _lane_case(R: int) -> tuple:
 
 
 def test_lane_cases_cover_the_form_counts():
-    """m = 1, 63, 64, 65 and 140 (k_quartic_check: forms over the 64 lanes of a wave), forms in natural and in shuffled order"""
+    """m = 1, 63, 64, 65 and 140 (k_forms_check<4>: forms over the 64 lanes of a wave), forms in natural and in shuffled order"""
     ms = {R: len(_lane_case(R)[0]) for R in range(R_MAX + 1)}
     assert {1, 63, 64, 65, 140} <= set(ms.values()), ms
     assert [len(_lane_case(R)[1]) for R in (0, 1, 2, 3, 4)] == [1, 1, 2, 4, 15]
@@ -131,7 +131,7 @@ def test_seventy_copies_of_one_form_first():
 def test_candidate_cap(nz, fused):
     """R = 30.  In y the first 64 forms are y_k for k in Z = {22 .. 22 + nz - 1}, then four-fold products y_k y_l y_1 y_0 (k in Z, l in
     2 .. 21): 64 independent forms whose common zeros are the subspace y_Z = 0.  |Z| = 8: exactly 2^22 first-pass candidates, which
-    the list still holds (k_quartic_check); |Z| = 7: 2^23, twice what it holds (the fused pass).  The forms behind them leave the 64
+    the list still holds (k_forms_check<4>); |Z| = 7: 2^23, twice what it holds (the fused pass).  The forms behind them leave the 64
     points of weight <= 3 on y_0 .. y_6 with y_7 .. y_21 = 0 in both cases."""
     R = 30
     rng = random.Random(6400 + nz)
@@ -174,7 +174,7 @@ def test_point_cap_exceeded():
         hip.quartic_forms_search([f], 24, max_out=16)
 
 
-# -- k_quartic_products / k_cubic_forms against their host twin ---------------------------------------------------------------------
+# -- k_forms_products<4> / k_forms_sum against their host twin ---------------------------------------------------------------------
 def _rank(vecs) -> int:
     piv = {}
     for v in vecs:
@@ -214,7 +214,7 @@ PLAN_CASES = [(5, 0, 4, 3), (9, 0, 0, 0), (9, 7, 3, 40), (12, 9, 0, 0), (12, 10,
 
 @pytest.mark.parametrize("n,r,k,kbits", PLAN_CASES, ids=lambda v: str(v))
 def test_forms_kernels_equal_host_twin(n, r, k, kbits):
-    """hip.quartic_plan with a device (k_quartic_products: Moebius sums per monomial; k_cubic_forms: XOR over the supports) == without
+    """hip.quartic_plan with a device (k_forms_products<4>: Moebius sums per monomial; k_forms_sum: XOR over the supports) == without
     (the host twin: monomial-by-monomial products), the whole dict.  What pins the twin itself is the brute force of
     tests/test_quartic_search_cpu.py at n <= 8."""
     rng = random.Random(6600 + 7 * n + r + k)

@@ -108,8 +108,8 @@ def versus_walk(count: int):
 
 if __name__ == "__main__":
     say(f"tools/cubic_search_time.py on one MI355X (build {hip.build_id()}).  Medians of 5 warm runs in one process [min .. max].")
-    say("Phase times are gf2bv_cubic_last_times() in ms: reduction, forms build (k_cubic_products + k_cubic_forms, every round), affine")
-    say("elimination, device search (k_cubic_search + k_cubic_check), total library time; levels = rounds of the affine elimination.")
+    say("Phase times are gf2bv_cubic_last_times() in ms: reduction, forms build (k_forms_products<3> + k_forms_sum, every round), affine")
+    say("elimination, device search (k_cubic_search + k_forms_check<3>), total library time; levels = rounds of the affine elimination.")
     for R in (28, 32, 36):
         rate(R)
     rate_once(40)

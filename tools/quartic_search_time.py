@@ -149,9 +149,9 @@ def main(argv):
              "5 warm runs [min .. max].",
              "R ..: the call time of gf2bv_quartic_forms_search / gf2bv_cubic_forms_search on 64 dense forms (table build, search kernel; "
              "no second pass).",
-             "Phase times are gf2bv_quartic_last_times() in ms: reduction, forms build (k_quartic_products + k_cubic_forms, every round), "
+             "Phase times are gf2bv_quartic_last_times() in ms: reduction, forms build (k_forms_products<4> + k_forms_sum, every round), "
              "affine elimination,",
-             "device search (k_quartic_search + k_quartic_check), total library time; levels = rounds of the affine elimination."]
+             "device search (k_quartic_search + k_forms_check<4>), total library time; levels = rounds of the affine elimination."]
     print("\n".join(lines), flush=True)
     runs = [(name, ROOT) for name in argv[2:] or CASES]
     ok = True
