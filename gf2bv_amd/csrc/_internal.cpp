@@ -865,21 +865,41 @@ bool factor_open(FactorObject *self)
 	return false;
 }
 
-PyObject *factor_rank(FactorObject *self, void *) { return factor_open(self) ? PyLong_FromLongLong(gf2bv_factor_rank(self->h)) : nullptr; }
+// The library's getters take the handle's mutex, which an append or a solve on another thread holds for its whole run: the GIL is
+// dropped around them like around every other call, so that the wait stalls this thread alone.
+template <class F>
+int64_t factor_get(gf2bv_factor *h, F &&get)
+{
+	int64_t v;
+	Py_BEGIN_ALLOW_THREADS
+	v = get(h);
+	Py_END_ALLOW_THREADS
+	return v;
+}
+
+PyObject *factor_rank(FactorObject *self, void *)
+{
+	return factor_open(self) ? PyLong_FromLongLong(factor_get(self->h, [](gf2bv_factor *h) { return gf2bv_factor_rank(h); })) : nullptr;
+}
 PyObject *factor_rows(FactorObject *self, void *) { return PyLong_FromLongLong(self->rows); }
 PyObject *factor_cols(FactorObject *self, void *) { return PyLong_FromLongLong(self->cols); }
 PyObject *factor_mode(FactorObject *self, void *) { return PyLong_FromLong(self->mode); }
 PyObject *factor_device(FactorObject *self, void *) { return PyLong_FromLong(self->device); }
 PyObject *factor_device_bytes(FactorObject *self, void *)
 {
-	return factor_open(self) ? PyLong_FromLongLong(gf2bv_factor_device_bytes(self->h)) : nullptr;
+	return factor_open(self) ? PyLong_FromLongLong(factor_get(self->h, [](gf2bv_factor *h) { return gf2bv_factor_device_bytes(h); })) : nullptr;
 }
+// ONE locked call into a buffer of cols entries pre-filled with -1: an append on another thread may raise the rank between two calls,
+// so the count comes from what was written, and (count, pivots) is a state the handle really was in
 PyObject *factor_pivots(FactorObject *self, void *)
 {
 	if (!factor_open(self)) return nullptr;
-	const int64_t rank = gf2bv_factor_rank(self->h);
-	std::vector<int32_t> piv((size_t)std::max<int64_t>(1, rank));
-	gf2bv_factor_pivots(self->h, piv.data());
+	std::vector<int32_t> piv((size_t)std::max<int64_t>(1, self->cols), -1);
+	int32_t *out = piv.data();
+	const int64_t rc = factor_get(self->h, [out](gf2bv_factor *h) { return (int64_t)gf2bv_factor_pivots(h, out); });
+	if (rc != GF2BV_OK) return raise_rc((int)rc, "pivots");
+	int64_t rank = 0;
+	while (rank < (int64_t)piv.size() && piv[(size_t)rank] >= 0) rank++;
 	PyObject *t = PyTuple_New(rank);
 	if (!t) return nullptr;
 	for (int64_t i = 0; i < rank; i++) {

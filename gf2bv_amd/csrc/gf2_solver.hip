@@ -2431,7 +2431,7 @@ int solve_rhs(const MatrixInput &in, const u64 *rhs, bool rhs_on_device, i64 nrh
 }  // namespace
 
 struct gf2bv_factor {
-	std::mutex mu;                    // one call on a handle at a time (the binding drops the GIL)
+	mutable std::mutex mu;            // one call on a handle at a time, getters included (the binding drops the GIL)
 	Solver S;                         // M = [U | slots | T], arena (pivots, urow, panel records), streams
 	i64 rows = 0, cols = 0, tw0 = 0, rw = 0, cw = 0;
 	int mode = 0, device = 0;
@@ -2460,6 +2460,7 @@ struct gf2bv_factor {
 namespace {
 
 constexpr i64 kFactorSlots = 64;      // right-hand sides per solve pass (the slot columns cols .. cols + 63)
+const char *kFailedHandle = "the handle is unusable: an append failed after it had started to change it";
 
 // what a back-substitution took from the pool goes back (the handle keeps its solver between calls)
 void release_backsub(Solver &S)
@@ -2608,6 +2609,9 @@ int factor_pass(gf2bv_factor *h, const u64 *d_rhs, i64 np, i64 rhs_stride, hipEv
 int factor_solve(gf2bv_factor *h, const u64 *rhs, bool on_device, i64 nrhs, i64 rhs_words, hipStream_t stream, gf2bv_result **out)
 {
 	std::lock_guard<std::mutex> lk(h->mu);
+	// (checked again under the lock: an append on another thread may have finished between check_factor_args and here)
+	if (h->failed) return fail(GF2BV_ERR_ARG, kFailedHandle);
+	if (rhs_words < h->rw) return fail(GF2BV_ERR_ARG, "rhs_words does not cover one bit per row");
 	const auto t0 = std::chrono::steady_clock::now();
 	Solver &S = h->S;
 	S.kn.refresh();
@@ -2683,8 +2687,6 @@ struct AppendBufs {
 	int4 *items = nullptr;
 	hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
 };
-
-const char *kFailedHandle = "the handle is unusable: an append failed after it had started to change it";
 
 int check_append_args(const gf2bv_factor *h, const MatrixInput &in, i64 k)
 {
@@ -2814,6 +2816,7 @@ int append_chunk(gf2bv_factor *h, i64 r0, i64 k, const AppendBufs &B, double ms[
 int factor_append(gf2bv_factor *h, const MatrixInput &in, i64 k, hipStream_t stream)
 {
 	std::lock_guard<std::mutex> lk(h->mu);
+	if (h->failed) return fail(GF2BV_ERR_ARG, kFailedHandle);      // (again under the lock, as factor_solve does)
 	Solver &S = h->S;
 	S.kn.refresh();
 	HIPCHK(hipSetDevice(h->device));
@@ -3301,15 +3304,29 @@ int gf2bv_factor_solve_device(gf2bv_factor *h, const void *d_rhs, int64_t nrhs, 
 	});
 }
 
-int64_t gf2bv_factor_rank(const gf2bv_factor *h) { return h && !h->failed ? h->rank : -1; }
+// The getters take the handle's mutex like every other call: an append on another thread replaces rank, rows, piv and device_bytes.
+int64_t gf2bv_factor_rank(const gf2bv_factor *h)
+{
+	if (!h) return -1;
+	std::lock_guard<std::mutex> lk(h->mu);
+	return !h->failed ? h->rank : -1;
+}
+// One locked copy: the entries written are one state of the handle.  Their number can only be known together with them (an append
+// may raise the rank between two calls), so `o` has room for cols entries and the caller pre-fills it to count what was written.
 int gf2bv_factor_pivots(const gf2bv_factor *h, int32_t *o)
 {
-	if (!h || (!o && !h->piv.empty())) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (!h || !o) return fail(GF2BV_ERR_ARG, "null pointer");
+	std::lock_guard<std::mutex> lk(h->mu);
 	if (h->failed) return fail(GF2BV_ERR_ARG, kFailedHandle);
 	if (!h->piv.empty()) memcpy(o, h->piv.data(), sizeof(int32_t) * h->piv.size());
 	return GF2BV_OK;
 }
-int64_t gf2bv_factor_device_bytes(const gf2bv_factor *h) { return h ? h->device_bytes : -1; }
+int64_t gf2bv_factor_device_bytes(const gf2bv_factor *h)
+{
+	if (!h) return -1;
+	std::lock_guard<std::mutex> lk(h->mu);
+	return h->device_bytes;
+}
 void gf2bv_factor_free(gf2bv_factor *h)
 {
 	if (!h) return;
@@ -3352,7 +3369,12 @@ int gf2bv_factor_append_device(gf2bv_factor *h, const void *d_aug, int64_t rows,
 	});
 }
 
-int64_t gf2bv_factor_rows(const gf2bv_factor *h) { return h && !h->failed ? h->rows : -1; }
+int64_t gf2bv_factor_rows(const gf2bv_factor *h)
+{
+	if (!h) return -1;
+	std::lock_guard<std::mutex> lk(h->mu);
+	return !h->failed ? h->rows : -1;
+}
 
 int gf2bv_factor_copy(gf2bv_factor *h, gf2bv_factor **out)
 {

@@ -504,9 +504,11 @@ class Factor:
 
     @property
     def pivots(self) -> np.ndarray:
-        piv = np.zeros(max(self.rank, 1), dtype=np.int32)
+        """the pivot columns of one state of the handle: ONE locked call into a buffer of cols entries pre-filled with -1 (an
+        append on another thread may raise the rank between two calls, so the count comes from what was written)"""
+        piv = np.full(max(self.cols, 1), -1, dtype=np.int32)
         _check(lib().gf2bv_factor_pivots(self._handle(), piv.ctypes.data))
-        return piv[:self.rank]
+        return piv[:int(np.count_nonzero(piv >= 0))].copy()
 
     @property
     def device_bytes(self) -> int:

@@ -22,6 +22,13 @@
  * returns all of them to the device, and an allocation the device refuses -- the library's own or
  * gf2bv_device_alloc -- frees them and is repeated once).  Matches the reference releasing the GIL around the
  * whole factor/solve/kernel section (_internal.c:429-492).
+ * Handles: a gf2bv_factor may be used from several threads; its calls -- solves, appends, copies and the getters (rank, rows,
+ * pivots, device_bytes) -- take a mutex inside the handle and run one at a time, so a getter beside an append sees the state
+ * before or after it, never a mixture.  gf2bv_factor_free waits for a call that is running, but racing it against other calls on
+ * the same handle is a caller error (a call that arrives after it uses freed memory).  gf2bv_space and gf2bv_slab handles have no
+ * lock and own one set of device and pinned buffers each: they belong to one thread at a time (different handles on different
+ * threads are fine).  gf2bv_result handles are immutable once returned.  No GF2BV_* environment variable may change while another
+ * thread is inside the library.
  */
 #ifndef GF2BV_HIP_H
 #define GF2BV_HIP_H
@@ -163,7 +170,10 @@ int gf2bv_factor_solve(gf2bv_factor *h, const uint64_t *rhs, int64_t nrhs, int64
 int gf2bv_factor_solve_device(gf2bv_factor *h, const void *d_rhs, int64_t nrhs, int64_t rhs_words, void *stream,
                               int time_kernels, gf2bv_result **out);
 int64_t gf2bv_factor_rank(const gf2bv_factor *h);
-int     gf2bv_factor_pivots(const gf2bv_factor *h, int32_t *out);      /* rank entries */
+/* Writes the handle's pivot columns, `rank` entries, in one locked copy.  An append on another thread can raise the rank between
+ * gf2bv_factor_rank and this call, so `out` must have room for cols entries (the rank never exceeds cols); a caller that shares the
+ * handle pre-fills it with -1 and counts what was written -- that count and those entries are one state of the handle. */
+int     gf2bv_factor_pivots(const gf2bv_factor *h, int32_t *out);
 int64_t gf2bv_factor_device_bytes(const gf2bv_factor *h);              /* device memory the handle holds */
 void    gf2bv_factor_free(gf2bv_factor *h);
 /* Equations appended to a kept factorization.  After appending B1, ..., Bm to a handle made from A, the handle behaves as
