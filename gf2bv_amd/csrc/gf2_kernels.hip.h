@@ -121,6 +121,11 @@ struct SolveState {
 	int fast_pub;
 	int sp_chunk;        // k_block_sparse: 0 = the "first 64 rows with a bit in the panel" attempt completed the last panel it was tried on
 	int sp_nz;           // k_block_sparse: alive rows with a non-zero window that its last launch counted (the host picks the pool size by it)
+	// statistics of k_block_sparse (gf2bv_stats::sparse_*), written by thread 0 where it writes the fields above
+	int sp_blocks[3];    // blocks it published, by pool size (1024 / 4096 / 6144 rows)
+	int sp_first64, sp_absorb, sp_rounds;      // panels of published blocks by selection: (A) from the first 64 entries, (A) with find_absorb, (B)
+	int sp_why;          // the reason of its last give-up, 1..5 (the numbers give_up() carries; the host, which meets every give-up, tallies them)
+	int sp_nz_max;       // the largest sp_nz of the solve
 };
 
 // Hand-over between the panel stream and the bulk stream through memory instead of events.  An event wait costs a
@@ -1450,13 +1455,15 @@ struct SparseLds {
 	int wsum[16], min_free, min_zero, ok, chunk_ok;
 	int cnts[129];                           // compaction of a panel's entries: [slot][wavefront] counts -> offsets, [128] = their sum
 	unsigned char colof[GF2_SP_NE];           // compacted entry -> basis column + 1 it supplies (selection on wavefront 0)
+	unsigned char how[GF2_GMAX];              // statistics: how panel g was selected (0 = (A) first 64 entries, 1 = (A) with find_absorb, 2 = (B)), until publish
 };
 #ifdef GF2_SPARSE_DEBUG
 __device__ unsigned long long gf2_sparse_probe[8];      // ticks (100 MHz) in: pool, selection, gj, tables + narrow, publish
 #endif
-// NT threads x CPT candidates per thread = the pool.  <256, 4> (1024 rows; one wavefront per SIMD at 124 registers and 22 KiB of LDS:
-// the kernel fits beside a bulk-update workgroup, like every panel kernel must) is what the host launches first; <512, 8> (4096
-// rows) after a give-up (examples/mt.py with 9 bits or one bit per output: 1100-3700 rows carry a bit in a block's window).
+// NT threads x CPT candidates per thread = the pool.  <256, 4> (1024 rows; one wavefront per SIMD at 117 registers and 23392 bytes of
+// LDS: the kernel fits beside a bulk-update workgroup, like every panel kernel must) is what the host launches first; <512, 8> (4096
+// rows, 173 registers, 35680 bytes) after a give-up (examples/mt.py with 9 bits or one bit per output: 1100-3700 rows carry a bit in
+// a block's window); <1024, 6> (6144 rows, 128 registers and 48 bytes of scratch per lane, 43872 bytes) after two.
 template <int NT, int CPT>
 __global__ void __launch_bounds__(NT)
 k_block_sparse(u64 *__restrict__ M, i64 rows, i64 srows, int j0, int gb, int fast_only, int blk,
@@ -1485,9 +1492,9 @@ k_block_sparse(u64 *__restrict__ M, i64 rows, i64 srows, int j0, int gb, int fas
 	const int first = st->first, r0 = st->rank;
 	if (st->poison) return;
 #ifdef GF2_SPARSE_DEBUG
-	auto give_up = [&](int why = 0, long long detail = 0) { if (t == 0) { st->fast_off = 1; if (fast_only) st->poison = blk + 1; printf("k_block_sparse<%d,%d> block %d gives up: reason %d detail %lld first %d\n", NT, CPT, blk, why, detail, first); } };
+	auto give_up = [&](int why = 0, long long detail = 0) { if (t == 0) { st->fast_off = 1; if (fast_only) st->poison = blk + 1; st->sp_why = why; printf("k_block_sparse<%d,%d> block %d gives up: reason %d detail %lld first %d\n", NT, CPT, blk, why, detail, first); } };
 #else
-	auto give_up = [&](int why = 0, long long detail = 0) { (void)why; (void)detail; if (t == 0) { st->fast_off = 1; if (fast_only) st->poison = blk + 1; } };
+	auto give_up = [&](int why = 0, long long detail = 0) { (void)detail; if (t == 0) { st->fast_off = 1; if (fast_only) st->poison = blk + 1; st->sp_why = why; } };
 #endif
 	if (gb != GF2_GMAX) { give_up(1); return; }
 	// ---- the pool: mask words in passes of one word per thread (a run of candidate rows spreads over neighbouring threads) ----
@@ -1524,7 +1531,7 @@ k_block_sparse(u64 *__restrict__ M, i64 rows, i64 srows, int j0, int gb, int fas
 		if (z && zmin == 0x7fffffff) zmin = (int)wbase + ctz64(z);
 	}
 	if (zmin != 0x7fffffff) atomicMin(&F.min_zero, zmin);
-	if (t == 0) st->sp_nz = base;
+	if (t == 0) { st->sp_nz = base; if (base > st->sp_nz_max) st->sp_nz_max = base; }
 	__syncthreads();
 	const int have_c = base < NC ? base : NC;
 	if (have_c < 64 * GF2_GMAX) { give_up(2, have_c); return; }      // (uniform) fewer candidates than pivots
@@ -1546,6 +1553,10 @@ k_block_sparse(u64 *__restrict__ M, i64 rows, i64 srows, int j0, int gb, int fas
 	u64 Pk[GF2_GMAX] = { 0, 0, 0, 0 };
 	bool try_chunk = st->sp_chunk == 0;
 	SP_PROBE(0);
+	// a panel that cannot be completed leaves the loop for the ONE give-up behind it (a return from inside the loop at each of the three
+	// places cost 20 registers in every instantiation)
+	int bail = 0;
+	long long bail_detail = 0;
 #pragma unroll 1
 	for (int g = 0; g < GF2_GMAX; g++) {
 		// ---- selection: 64 independent candidates of panel g ----
@@ -1606,7 +1617,7 @@ k_block_sparse(u64 *__restrict__ M, i64 rows, i64 srows, int j0, int gb, int fas
 					selw[pos[k]] = w;
 				}
 			}
-		if (basec < 64) { give_up(5, basec); return; }       // (uniform) fewer rows with a bit in the panel than it has columns
+		if (basec < 64) { bail = 5; bail_detail = basec; break; }       // (uniform) fewer rows with a bit in the panel than it has columns
 		}
 		// (A) wavefront 0: the first 64 entries through gj_columns (column-wise, ~3.7 us: complete for systems whose rows come in runs
 		// that determine a panel and for anything dense), then the following chunks of 64 entries through the TARGETED completion of
@@ -1619,6 +1630,7 @@ k_block_sparse(u64 *__restrict__ M, i64 rows, i64 srows, int j0, int gb, int fas
 				FindState S;
 				S.bw = 0; S.bc = 0; S.have = 0; S.nslots = 0; S.colslots = false; S.srow = 0;
 				(void)gj_columns(S, lane < ne ? selw[lane] : 0ull, lane, lane);
+				if (lane == 0) F.how[g] = S.nslots == 64 ? 0 : 1;
 				for (int c0 = 64; c0 < ne && S.nslots < 64; c0 += 64)
 					(void)find_absorb(S, c0 + lane < ne ? selw[c0 + lane] : 0ull, c0 + lane, ~0ull, lane, (int *)nullptr, 0, 64);
 				if (lane == 0) F.chunk_ok = S.nslots == 64;
@@ -1648,7 +1660,7 @@ k_block_sparse(u64 *__restrict__ M, i64 rows, i64 srows, int j0, int gb, int fas
 		// (B) rounds: every candidate's word reduced by the echelon basis so far (lowest pivot first), the first candidate with each
 		// new lowest bit joins the basis
 		if (t < 64) F.prop[t] = 0x7fffffff;
-		if (t == 0) F.have = 0;
+		if (t == 0) { F.have = 0; F.how[g] = 2; }
 		u64 xr[CPT];
 		unsigned ownk = 0;
 		u64 owncols = 0;                                      // 8 bits per candidate: the basis column it took
@@ -1695,7 +1707,7 @@ k_block_sparse(u64 *__restrict__ M, i64 rows, i64 srows, int j0, int gb, int fas
 			hv = nh;
 		}
 		SP_PROBE(1);
-		if (hv != ~0ull) { give_up(3, 1000000ll * g + 10000ll * __popcll(hv) + base); return; }              // (uniform) the pool does not hold 64 independent rows for this panel
+		if (hv != ~0ull) { bail = 3; bail_detail = 1000000ll * g + 10000ll * __popcll(hv) + base; break; }              // (uniform) the pool does not hold 64 independent rows for this panel
 		// the chosen rows: current words and rows by basis column; they are this panel's sources
 #pragma unroll
 		for (int k = 0; k < CPT; k++)
@@ -1721,7 +1733,7 @@ k_block_sparse(u64 *__restrict__ M, i64 rows, i64 srows, int j0, int gb, int fas
 		if (t < 64) F.srow_all[g][t] = F.srcrow[t];
 		__syncthreads();
 		SP_PROBE(2);
-		if (!F.ok) { give_up(4, g); return; }
+		if (!F.ok) { bail = 4; bail_detail = g; break; }
 		// the pivot rows' window words right of the panel = comb x source words (nibble tables of the 64 sources)
 		const bool use = e_ >= g;
 		if (tab_thread) L.Pb[e_][sl] = use ? F.srcw[F.srcs[g][sl]][e_] : 0ull;
@@ -1762,6 +1774,7 @@ k_block_sparse(u64 *__restrict__ M, i64 rows, i64 srows, int j0, int gb, int fas
 		}
 		SP_PROBE(3);
 	}
+	if (bail) { give_up(bail, bail_detail); return; }          // (uniform)
 	// ---- every panel is complete: publish the block (as k_block_fast does) ----
 	{
 		int mf = 0x7fffffff;
@@ -1806,6 +1819,9 @@ k_block_sparse(u64 *__restrict__ M, i64 rows, i64 srows, int j0, int gb, int fas
 		st->fast_done = blk + 1;
 		st->fast_blocks = st->fast_blocks + 1;
 		st->sp_chunk = try_chunk ? 0 : ((st->sp_chunk + 1) & 7);      // (after a miss: the rounds for seven blocks, then another try)
+		st->sp_blocks[NT == 256 ? 0 : NT == 512 ? 1 : 2]++;
+#pragma unroll
+		for (int g = 0; g < GF2_GMAX; g++) { const int h = F.how[g]; if (h == 0) st->sp_first64++; else if (h == 1) st->sp_absorb++; else st->sp_rounds++; }
 	}
 	SP_PROBE(4);
 }

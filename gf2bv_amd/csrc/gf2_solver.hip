@@ -647,7 +647,8 @@ struct SolverPlan {
 	// sparse systems (round 5): blocks the dense one-launch search cannot take go through k_block_sparse -- candidates = the alive rows
 	// with a non-zero window, from the bit masks the look-ahead leaves in wmask (allowed at all: kn.sparse_fast)
 	bool sparse_on = false;       // this solve has switched to it (after block 0 went the general way)
-	int sparse_giveups = 0;
+	int sparse_giveups = 0;       // blocks handed back to the general steps, both resume paths of enqueue_forward together
+	int sparse_why[5] = {};       // ... by the kernel's reason 1..5 (SolveState::sp_why)
 	int sparse_tier = 0;          // pool size of k_block_sparse: 0 = 1024 rows (beside the bulk update), 1 = 4096, 2 = 6144
 	int narrow_rpt = 1;           // row blocks of 256 per narrow workgroup of a panel step (set in solver_alloc)
 	i64 ys = 0;
@@ -1398,7 +1399,8 @@ int enqueue_forward(Solver &S)
 	// Sparse systems (round 5): when block 0 did NOT take the dense search, the following full blocks get k_block_sparse + k_narrow_all
 	// instead of the G + 1 general panel steps (one-level schedules only; the look-ahead of every block leaves the masks the next
 	// block's pool is taken from).  A block it cannot take poisons the panel path like a failed optimistic block: the host resumes
-	// there with the general steps for THAT block and goes on sparse behind it (three times at most, then general to the end).
+	// there with the general steps for THAT block and goes on sparse behind it -- twice; the THIRD give-up of a solve, whichever of the
+	// two resume paths below meets it, switches the search off and the rest runs general (gf2bv_stats::sparse_giveups).
 	const bool may_sparse = may_probe && S.kn.sparse_fast && S.tl_K == 0;
 	int general_only = -1;                      // (resume) this one block takes the general steps whatever the mode
 	auto sparse_ok = [&](int blk) { return S.sparse_on && blk != general_only && fast_block_possible(S, block_geom(S, blk)); };
@@ -1414,6 +1416,13 @@ int enqueue_forward(Solver &S)
 		HIPCHK(hipMemsetAsync(&S.st->poison, 0, sizeof(int), S.sA));
 		S.sync_base += S.nblocks + 1;
 		return GF2BV_OK;
+	};
+	// a block the sparse search handed back (hst.poison read, either resume path): counted, by the kernel's reason too; the third of a
+	// solve switches the search off.  Returns whether the search stays on.
+	auto sparse_gave_up = [&]() {
+		if (hst.sp_why >= 1 && hst.sp_why <= 5) S.sparse_why[hst.sp_why - 1]++;
+		if (++S.sparse_giveups >= 3) S.sparse_on = false;
+		return S.sparse_on;
 	};
 	// the first block of each pool size is looked at before anything is enqueued behind it: a pool that cannot serve the system (too
 	// many rows carry a bit in a window) costs one block, not a poisoned pipeline of all the blocks behind it
@@ -1434,7 +1443,7 @@ int enqueue_forward(Solver &S)
 			const int want = hst.sp_nz > 3400 ? 2 : 0;
 			if (hst.poison) {
 				if ((r = recover(blk))) return r;
-				if (++S.sparse_giveups >= 3) S.sparse_on = false; else sparse_probes = 1;      // (the larger pools get one look each, too)
+				if (sparse_gave_up()) sparse_probes = 1;      // (the larger pools get one look each, too)
 				S.sparse_tier = std::min(2, std::max(S.sparse_tier + 1, want));
 				general_only = blk;
 				if ((r = enqueue_block_panel(S, blk, false, false))) return r;
@@ -1524,7 +1533,7 @@ int enqueue_forward(Solver &S)
 			const int pb = hst.poison - 1;
 			if ((rc = recover(pb))) return rc;
 			optimistic = false;
-			if (S.sparse_on && ++S.sparse_giveups > 3) S.sparse_on = false;
+			if (S.sparse_on) (void)sparse_gave_up();
 			S.sparse_tier = std::min(2, S.sparse_tier + 1);
 			general_only = pb;
 			// (the poisoned block's window is in place; the blocks behind it take their masks from the look-aheads again)
@@ -1818,6 +1827,11 @@ void fill_stats(const Solver &S, gf2bv_result *R)
 	st.gang_systems = S.view ? S.gang_nsys : S.nsys;
 	st.search_handovers = hst.self_giveups;
 	st.fast_blocks = hst.fast_blocks;
+	for (int i = 0; i < 3; i++) st.sparse_blocks[i] = hst.sp_blocks[i];
+	st.sparse_panels_first64 = hst.sp_first64; st.sparse_panels_absorb = hst.sp_absorb; st.sparse_panels_rounds = hst.sp_rounds;
+	st.sparse_giveups = S.sparse_giveups;
+	for (int i = 0; i < 5; i++) st.sparse_giveup_why[i] = S.sparse_why[i];
+	st.sparse_nz_max = hst.sp_nz_max;
 	{
 		const int G = S.impl->G;
 		for (int b = 0; b < S.nblocks; b++) {

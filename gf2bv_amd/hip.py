@@ -77,10 +77,18 @@ class Stats(ctypes.Structure):
         ("search_handovers", ctypes.c_int32), ("fast_blocks", ctypes.c_int32),
         ("hbm_words", ctypes.c_double), ("bulk_launches", ctypes.c_int32), ("outer_blocks", ctypes.c_int32),
         ("handover_retries", ctypes.c_int32), ("small_path", ctypes.c_int32),
+        ("sparse_blocks", ctypes.c_int32 * 3), ("sparse_panels_first64", ctypes.c_int32), ("sparse_panels_absorb", ctypes.c_int32),
+        ("sparse_panels_rounds", ctypes.c_int32), ("sparse_giveups", ctypes.c_int32), ("sparse_giveup_why", ctypes.c_int32 * 5),
+        ("sparse_nz_max", ctypes.c_int32),
     ]
 
     def as_dict(self) -> dict:
-        return {name: getattr(self, name) for name, _ in self._fields_}
+        """fields by name; the array fields as lists"""
+        out = {}
+        for name, ctype in self._fields_:
+            v = getattr(self, name)
+            out[name] = list(v) if issubclass(ctype, ctypes.Array) else v
+        return out
 
 
 class HipError(RuntimeError):

@@ -86,6 +86,21 @@ typedef struct gf2bv_stats {
 	                              made with events (the device stays on events for this process); 0 normally        */
 	int32_t small_path;        /* 1: solved by the one-launch kernel for systems that fit the LDS of one workgroup (k_small_solve; the
 	                              phase times and sweep counters above are then 0 except ms_total); GF2BV_SMALL=0 disables that path */
+	/* the one-launch block search of sparse systems (k_block_sparse; single systems whose first block the dense search refuses): which
+	 * of its branches ran.  All 0 when it never ran (GF2BV_SPARSE_FAST=0, gangs, two-level plans, dense systems). */
+	int32_t sparse_blocks[3];        /* blocks it factorised, by the size of its candidate pool: 1024 / 4096 / 6144 rows (fast_blocks counts
+	                                    these and the dense search's)                                                                   */
+	int32_t sparse_panels_first64;   /* panels of those blocks whose 64 pivot rows were the first 64 pool rows with a bit in the panel     */
+	int32_t sparse_panels_absorb;    /* ... that needed more of the first 512 such rows (at least one find_absorb chunk)                   */
+	int32_t sparse_panels_rounds;    /* ... that were selected by the rounds over the whole pool                                           */
+	int32_t sparse_giveups;          /* blocks the host handed back to the general panel steps after the search gave up on them (the probed
+	                                    first block of a pool size and the resume after a poisoned pipeline together); the third switches
+	                                    the search off for the rest of the solve                                                          */
+	int32_t sparse_giveup_why[5];    /* the search's give-ups by reason 1..5: [0] not a full block, [1] fewer than 256 rows with a non-zero
+	                                    window in reach, [2] the pool lacks 64 independent rows for a panel, [3] the chosen rows were not
+	                                    independent after all, [4] fewer than 64 pool rows have a bit in a panel                           */
+	int32_t sparse_nz_max;           /* the most alive rows with a non-zero window one of its launches counted (above the pool size: that
+	                                    pool was truncated)                                                                             */
 } gf2bv_stats;
 
 /* ---- library / device ------------------------------------------------------------------ */

@@ -181,13 +181,45 @@ def test_nlfsr_state_recovery(name):
 
 
 @pytest.mark.parametrize("bs,samples", H.MT_VARIANTS)
-def test_mt19937_state_recovery(bs, samples):
+def test_mt19937_state_recovery(bs, samples, _heuristics):
     """examples/mt.py: all six variants, sol == state of random.Random(3142)."""
     lin, zeros, state, out = H.mt19937_system(bs, samples)
     sol = lin.solve_one(zeros)
     assert sol == state
     rng = H.MT19937(sol)
     assert all(rng.getrandbits(bs) == o for o in out)
+    # which pool of k_block_sparse the variant needs (gf2bv_stats::sparse_blocks by pool size: 1024 / 4096 / 6144 rows)
+    st = _mt_stats(bs, samples, _heuristics, lin, zeros)
+    assert st["handover_retries"] == 0
+    if _heuristics == "plain":                        # (no optimistic enqueue: the search is never switched on)
+        assert st["sparse_blocks"] == [0, 0, 0] and st["sparse_giveups"] == 0
+    else:
+        assert sum(st["sparse_blocks"]) > 0
+        if bs == 1:
+            assert st["sparse_blocks"][2] > 0         # one bit per output: 4500-5000 rows carry a bit in a block's window
+
+
+_MT_STATS = {}
+
+
+def _mt_stats(bs, samples, heuristics, lin=None, zeros=None):
+    """stats of the variant's system through solve_words, once per variant and leg"""
+    if (bs, samples, heuristics) not in _MT_STATS:
+        if lin is None:
+            lin, zeros, _, _ = H.mt19937_system(bs, samples)
+        eqs = H.padded_eqs(lin, zeros)
+        st = hip.solve_words(O.eqs_to_aug(eqs, lin._cols), len(eqs), lin._cols, 0).stats
+        print(f"[mt19937] {heuristics} {bs} bits x {samples or 'all'}: sparse pools {st['sparse_blocks']} give-ups {st['sparse_giveups']} "
+              f"{st['sparse_giveup_why']} nz_max {st['sparse_nz_max']} fast_blocks {st['fast_blocks']}")
+        _MT_STATS[(bs, samples, heuristics)] = st
+    return _MT_STATS[(bs, samples, heuristics)]
+
+
+def test_mt19937_some_variant_runs_the_middle_pool(_heuristics):
+    """Behind test_mt19937_state_recovery, whose solves it shares: the middle pool of k_block_sparse (4096 rows) is run by at least one
+    of the six variants, so the recoveries exercise all three instantiations."""
+    pools = {bs: _mt_stats(bs, samples, _heuristics)["sparse_blocks"] for bs, samples in H.MT_VARIANTS}
+    assert any(p[1] > 0 for p in pools.values()) == (_heuristics == "default"), pools      # (GF2BV_PLAIN=1: the search is never switched on)
 
 
 def test_synthetic_generator_device_equals_host():

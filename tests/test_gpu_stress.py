@@ -173,8 +173,9 @@ def test_sparse_block_search(monkeypatch, sparse):
         for mode in ((0, 1) if i < 3 else (i % 2,)):
             got = hip.solve_words(aug, rows, cols, mode)
             _same(got, O.solve_words(aug, rows, cols, mode), mode)
-            took += got.stats["fast_blocks"]
-    assert took > 0 or sparse == "0"           # (GF2BV_SPARSE_FAST=0: the dense search may still take the densest systems' later blocks)
+            took += sum(got.stats["sparse_blocks"])       # (not fast_blocks: the dense search counts there too, and may take the densest systems' later blocks)
+            assert sparse == "1" or got.stats["sparse_blocks"] == [0, 0, 0] and got.stats["sparse_giveups"] == 0
+    assert (took > 0) == (sparse == "1")
 
 
 @pytest.mark.parametrize("knob,value", [("GF2BV_STREAM_PAIRS", "0"), ("GF2BV_PLAIN", "1"), ("GF2BV_STREAM_PAIRS", "1")])
