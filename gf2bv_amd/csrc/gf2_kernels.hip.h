@@ -126,6 +126,14 @@ struct SolveState {
 	int sp_first64, sp_absorb, sp_rounds;      // panels of published blocks by selection: (A) from the first 64 entries, (A) with find_absorb, (B)
 	int sp_why;          // the reason of its last give-up, 1..5 (the numbers give_up() carries; the host, which meets every give-up, tallies them)
 	int sp_nz_max;       // the largest sp_nz of the solve
+	// statistics of search_panel (gf2bv_stats::general_*): functions of the data, never of timing.  Added (relaxed, agent scope) by the
+	// publisher's lane 0 beside its stores to rank / first / wide -- for a panel that unit 0 publishes itself by the last unit to arrive,
+	// which has nothing else left to do -- and by a group's last arriver for its group record
+	int gs_unit0, gs_adopt, gs_merge;      // published panels by where the basis came from: unit 0's record, another unit's or a group's, a merge
+	int gs_wide, gs_two_level;             // panels searched with every unit / that arrived group by group
+	int gs_group_adopt, gs_group_merge;    // group records: a complete member's, merged
+	int gs_gj_kept, gs_gj_redone;          // adopted records whose first chunk went through gj_columns: result kept / redone row-wise
+	int gs_chunks;                         // 64-row chunks the adopted records' units scanned
 };
 
 // Hand-over between the panel stream and the bulk stream through memory instead of events.  An event wait costs a
@@ -150,12 +158,14 @@ struct SyncFlags {
 struct DoneSignal { unsigned *count; int *flag; int value; };
 
 // Scratch of one search unit (wavefront).
+#define FU_GJ_KEPT 2          // FindUnit::pad: the unit's first chunk went through gj_columns and the result was kept / redone row-wise
+#define FU_GJ_REDONE 4
 struct FindUnit {
 	u64 have;
 	int cnt;
 	int first_nonsrc;    // first alive row of the unit's slice that did not become a source
 	int chunks;          // 64-row steps this unit needed
-	int pad;
+	int pad;             // bit 0: unit 0 means to publish this record itself; FU_GJ_*
 	int srow[64];        // slot -> row
 	u64 bc[64];          // pivot bit -> combination mask over slots
 };
@@ -782,7 +792,7 @@ __device__ __forceinline__ void search_panel(const Cand &cand, typename Cand::Ra
 	FindUnit *me = fu + u;
 	FindState S;
 	S.bw = 0; S.bc = 0; S.have = 0; S.nslots = 0; S.colslots = false; S.srow = 0;
-	int first_nonsrc = -1, chunks = 0;
+	int first_nonsrc = -1, chunks = 0, gj = 0;
 #ifdef GF2_STEP_PROBE
 	const bool gf2_probe_on_u = (j - gf) == gf2_probe_j0 && blockIdx.y == 0;
 	const int gf2_probe_step_u = gf;
@@ -807,6 +817,7 @@ __device__ __forceinline__ void search_panel(const Cand &cand, typename Cand::Ra
 				took = gj_columns(S, w, (int)ii, lane);
 				done = S.nslots >= 64 - GF2_FEW_MISSING;
 				if (!done) { S.bw = 0; S.bc = 0; S.have = 0; S.nslots = 0; S.colslots = false; }
+				gj = done ? FU_GJ_KEPT : FU_GJ_REDONE;
 			}
 			if (!done) took = find_absorb(S, w, (int)ii, colmask, lane, me->srow, sparse_mode);
 			chunks++;
@@ -831,7 +842,7 @@ __device__ __forceinline__ void search_panel(const Cand &cand, typename Cand::Ra
 	GF2_ST(&me->bc[lane], S.bc);
 	if (lane == 0) {
 		GF2_ST(&me->have, S.have); GF2_ST(&me->first_nonsrc, first_nonsrc); GF2_ST(&me->chunks, chunks); GF2_ST(&me->cnt, S.nslots);
-		GF2_ST(&me->pad, self ? 1 : 0);
+		GF2_ST(&me->pad, (self ? 1 : 0) | gj);
 		if (self) GF2_ST(&st->claim, 1u);
 	}
 	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // every store above has left this wave
@@ -886,13 +897,17 @@ __device__ __forceinline__ void search_panel(const Cand &cand, typename Cand::Ra
 			GF2_ST(&gu->srow[lane], GF2_LD(&fu[fullv].srow[lane]));
 			if (lane == 0) {
 				GF2_ST(&gu->have, GF2_LD(&fu[fullv].have)); GF2_ST(&gu->chunks, GF2_LD(&fu[fullv].chunks));
-				GF2_ST(&gu->first_nonsrc, first); GF2_ST(&gu->cnt, full);
+				GF2_ST(&gu->first_nonsrc, first); GF2_ST(&gu->cnt, full); GF2_ST(&gu->pad, GF2_LD(&fu[fullv].pad) & ~1);
+				__hip_atomic_fetch_add(&st->gs_group_adopt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 			}
 		} else {
 			FindState T;
 			merge_lists(T, g * GF2_GROUP, gsize, gu->srow);
 			GF2_ST(&gu->bc[lane], T.bc);
-			if (lane == 0) { GF2_ST(&gu->have, T.have); GF2_ST(&gu->chunks, 1 << 20); GF2_ST(&gu->first_nonsrc, first); GF2_ST(&gu->cnt, T.nslots); }
+			if (lane == 0) {
+				GF2_ST(&gu->have, T.have); GF2_ST(&gu->chunks, 1 << 20); GF2_ST(&gu->first_nonsrc, first); GF2_ST(&gu->cnt, T.nslots); GF2_ST(&gu->pad, 0);
+				__hip_atomic_fetch_add(&st->gs_group_merge, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+			}
 		}
 		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 		old = 0;
@@ -909,6 +924,9 @@ __device__ __forceinline__ void search_panel(const Cand &cand, typename Cand::Ra
 
 	u64 mv[GF2_GMAX];                           // a source's multipliers w.r.t. the block's earlier panels
 	int r0, pick = -1, hard, new_first;
+	int pub_chunks = 0, pub_gj = 0;             // statistics: the adopted record's chunks and FU_GJ_* (a merge: 0)
+	// (adds whose result nobody waits for -- no load on the way out of the launch -- and only those that add something)
+	auto count = [](int *c, int v) { if (v) __hip_atomic_fetch_add(c, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
 	int srow;                                   // lane s: row of slot s
 	if (self) {
 		r0 = st->rank;
@@ -941,6 +959,7 @@ __device__ __forceinline__ void search_panel(const Cand &cand, typename Cand::Ra
 			}
 		}
 		pick = 0; hard = chunks > 8; new_first = first_nonsrc;
+		pub_chunks = chunks; pub_gj = gj;
 		GF2_PROBE_UN(3);
 	} else {
 	// ---- last arriver: publish ----
@@ -951,7 +970,7 @@ __device__ __forceinline__ void search_panel(const Cand &cand, typename Cand::Ra
 	const int srow0 = GF2_LD(&fu[0].srow[lane]);
 	const int self0 = GF2_LD(&fu[0].pad);
 	r0 = st->rank;
-	if (idx0 == 0 && cnt0 == full && self0 == 1) {          // unit 0 means to publish its own result ...
+	if (idx0 == 0 && cnt0 == full && (self0 & 1)) {          // unit 0 means to publish its own result ...
 		unsigned left = 0;
 		if (lane == 0) {
 			unsigned expect = 1u;
@@ -960,7 +979,12 @@ __device__ __forceinline__ void search_panel(const Cand &cand, typename Cand::Ra
 			left = (__hip_atomic_compare_exchange_strong(&st->claim, &expect, 2u, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
 			                                             __HIP_MEMORY_SCOPE_AGENT) || expect != 0u) ? 1u : 0u;
 		}
-		if (__builtin_amdgcn_readfirstlane((int)left)) return;
+		if (__builtin_amdgcn_readfirstlane((int)left)) {
+			// statistics of a panel that unit 0 publishes itself: taken here, by the unit nobody waits for (such a record is complete,
+			// column-wise and kept, of a panel that is not wide)
+			if (lane == 0) { count(&st->gs_unit0, 1); count(&st->gs_gj_kept, 1); count(&st->gs_chunks, ch0); }
+			return;
+		}
 	}
 	if (full > 0) {
 		if (cnt0 == full) pick = 0;
@@ -968,7 +992,8 @@ __device__ __forceinline__ void search_panel(const Cand &cand, typename Cand::Ra
 			for (int v = 0; v < nlists; v++)
 				if (GF2_LD(&fu[idx0 + v].cnt) == full) { pick = idx0 + v; break; }
 	}
-	hard = (pick < 0) || ((pick == 0 ? ch0 : GF2_LD(&fu[pick].chunks)) > 8);
+	if (pick >= 0) { pub_chunks = (pick == 0) ? ch0 : GF2_LD(&fu[pick].chunks); pub_gj = (pick == 0) ? self0 : GF2_LD(&fu[pick].pad); }
+	hard = (pick < 0) || pub_chunks > 8;
 	GF2_PROBE_UN(3);
 	if (pick >= 0) {
 		S.have = (pick == 0) ? have0 : GF2_LD(&fu[pick].have);
@@ -1025,6 +1050,14 @@ __device__ __forceinline__ void search_panel(const Cand &cand, typename Cand::Ra
 		st->rank = r0 + p;
 		st->first = new_first;
 		st->wide = hard;
+		// statistics -- not from a unit 0 that publishes itself while another unit is the last to arrive: that one has counted the panel
+		if (!self || old == (unsigned)(units - 1)) {
+			count(pick == 0 ? &st->gs_unit0 : pick > 0 ? &st->gs_adopt : &st->gs_merge, 1);
+			count(&st->gs_wide, wide);
+			count(&st->gs_two_level, idx0 != 0);
+			count(&st->gs_gj_kept, (pub_gj & FU_GJ_KEPT) != 0); count(&st->gs_gj_redone, (pub_gj & FU_GJ_REDONE) != 0);
+			count(&st->gs_chunks, pub_chunks < (1 << 20) ? pub_chunks : 0);       // (a merged group record carries 1 << 20: hard, no unit behind it)
+		}
 		if (blk_first_out) {                               // last panel of a block: row bound for its bulk update; and an
 			*blk_first_out = new_first;                    // easy, full last panel says the next block may be dense again
 			st->fast_off = (!hard && p == 64) ? 0 : 1;

@@ -1832,6 +1832,10 @@ void fill_stats(const Solver &S, gf2bv_result *R)
 	st.sparse_giveups = S.sparse_giveups;
 	for (int i = 0; i < 5; i++) st.sparse_giveup_why[i] = S.sparse_why[i];
 	st.sparse_nz_max = hst.sp_nz_max;
+	st.general_unit0 = hst.gs_unit0; st.general_adopted = hst.gs_adopt; st.general_merged = hst.gs_merge;
+	st.general_wide = hst.gs_wide; st.general_two_level = hst.gs_two_level;
+	st.general_group_adopted = hst.gs_group_adopt; st.general_group_merged = hst.gs_group_merge;
+	st.general_gj_kept = hst.gs_gj_kept; st.general_gj_redone = hst.gs_gj_redone; st.general_chunks = hst.gs_chunks;
 	{
 		const int G = S.impl->G;
 		for (int b = 0; b < S.nblocks; b++) {

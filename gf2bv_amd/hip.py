@@ -80,6 +80,10 @@ class Stats(ctypes.Structure):
         ("sparse_blocks", ctypes.c_int32 * 3), ("sparse_panels_first64", ctypes.c_int32), ("sparse_panels_absorb", ctypes.c_int32),
         ("sparse_panels_rounds", ctypes.c_int32), ("sparse_giveups", ctypes.c_int32), ("sparse_giveup_why", ctypes.c_int32 * 5),
         ("sparse_nz_max", ctypes.c_int32),
+        ("general_unit0", ctypes.c_int32), ("general_adopted", ctypes.c_int32), ("general_merged", ctypes.c_int32),
+        ("general_wide", ctypes.c_int32), ("general_two_level", ctypes.c_int32), ("general_group_adopted", ctypes.c_int32),
+        ("general_group_merged", ctypes.c_int32), ("general_gj_kept", ctypes.c_int32), ("general_gj_redone", ctypes.c_int32),
+        ("general_chunks", ctypes.c_int32),
     ]
 
     def as_dict(self) -> dict:

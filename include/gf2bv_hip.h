@@ -101,6 +101,24 @@ typedef struct gf2bv_stats {
 	                                    independent after all, [4] fewer than 64 pool rows have a bit in a panel                           */
 	int32_t sparse_nz_max;           /* the most alive rows with a non-zero window one of its launches counted (above the pool size: that
 	                                    pool was truncated)                                                                             */
+	/* the general panel search (search_panel of k_panel_step: every panel no one-launch search took): which way each panel was
+	 * published.  Functions of the system alone -- who did the writing is timing and is counted by search_handovers only.  All 0
+	 * where that search never ran (the small path; blocks taken by k_block_fast / k_block_sparse: 4 x fast_blocks panels).
+	 * general_unit0 + general_adopted + general_merged = the panels it published. */
+	int32_t general_unit0;           /* panels whose basis is the first search unit's (complete on its own; the alive bound comes from it)  */
+	int32_t general_adopted;         /* ... is another unit's complete record or, on a two-level arrival, a group's complete record        */
+	int32_t general_merged;          /* ... was rebuilt from the units' (or the groups') source-row lists: no record was complete; every
+	                                    rank-deficient panel                                                                              */
+	int32_t general_wide;            /* panels searched by every unit (the panel before was hard: merged, or its record took > 8 chunks)   */
+	int32_t general_two_level;       /* wide panels of more than 16 units: groups of 16 units form a record each, the publisher chooses
+	                                    among those                                                                                       */
+	int32_t general_group_adopted;   /* group records that are a complete member's                                                        */
+	int32_t general_group_merged;    /* group records merged from the members' lists                                                      */
+	int32_t general_gj_kept;         /* unit0 / adopted panels whose record's first chunk went through the column-wise elimination
+	                                    (gj_columns: >= 48 of 64 candidates with > 12 bits) and kept its result (>= 56 pivots)             */
+	int32_t general_gj_redone;       /* ... and redid the chunk row-wise                                                                  */
+	int32_t general_chunks;          /* 64-row chunks scanned by the units behind the unit0 / adopted panels' records (a group's adopted
+	                                    member included; merges add nothing)                                                              */
 } gf2bv_stats;
 
 /* ---- library / device ------------------------------------------------------------------ */

@@ -57,6 +57,8 @@ def test_case_answers_and_branches(monkeypatch, name, mode):
         assert_same_oracle(got, want, mode)
         assert st["handover_retries"] == 0 and st["small_path"] == 0
         assert st["sparse_blocks"] == [0, 0, 0]
+        # every panel was published by the general search or belongs to a block the dense search took (which adds nothing to general_*)
+        assert st["general_unit0"] + st["general_adopted"] + st["general_merged"] + DC.G * st["fast_blocks"] == (cols + 63) // 64
         assert DC.holds(st, expect) == [], leg
         if optimistic is not None:
             assert expect == case.expect

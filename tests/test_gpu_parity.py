@@ -462,6 +462,7 @@ def test_search_handover_without_co_residency(monkeypatch):
     Same results, and the hand-over path is seen to have run."""
     monkeypatch.setenv("GF2BV_SELF_WAIT_US", "0")
     monkeypatch.setenv("GF2BV_FAST", "0")           # (the one-launch block search would bypass the per-panel searches on these dense systems)
+    from tests.general_cases import COUNTERS as general_counters
     rng = random.Random(77)
     handovers = 0
     for rows, cols, cap in ((3000, 2500, None), (5000, 4097, 4000), (9000, 8200, None)):
@@ -471,6 +472,12 @@ def test_search_handover_without_co_residency(monkeypatch):
             got = hip.solve_words(aug, rows, cols, mode)
             assert_same(got, O.solve_words(aug, rows, cols, mode), mode)
             handovers += got.stats["search_handovers"]
+            # who publishes is timing, how a panel is published is not: the same counts when unit 0 waits as long as it takes
+            with monkeypatch.context() as m:
+                m.setenv("GF2BV_SELF_WAIT_US", "1000000")
+                waited = hip.solve_words(aug, rows, cols, mode).stats
+            assert [got.stats[k] for k in general_counters] == [waited[k] for k in general_counters]
+            assert got.stats["general_unit0"] + got.stats["general_adopted"] + got.stats["general_merged"] == (cols + 63) // 64
     assert handovers > 0
     n, stride = 16384, hip.padded_stride(16384)
     buf = hip.DeviceBuffer(n * stride * 8)

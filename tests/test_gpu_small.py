@@ -87,6 +87,7 @@ def test_structured_systems_on_the_one_launch_path(kind):
         for mode in (0, 1):
             got = hip.solve_words(aug, rows, cols, mode)
             assert got.stats["small_path"] == 1
+            assert not any(v for k, v in got.stats.items() if k.startswith("general_")), "search_panel never ran: its counters stay 0"
             assert_same(got, O.solve_words(aug, rows, cols, mode), mode)
 
 

@@ -54,6 +54,8 @@ def test_case_answers_and_branches(monkeypatch, name, mode):
         _line(name, mode, leg, st)
         assert_same_oracle(got, want, mode)
         assert st["handover_retries"] == 0 and st["small_path"] == 0
+        # every panel was published by the general search or belongs to a block a one-launch search took (which adds nothing to general_*)
+        assert st["general_unit0"] + st["general_adopted"] + st["general_merged"] + SC.G * st["fast_blocks"] == cols // 64
         if leg == "switched off":
             assert all(st[k] == 0 or st[k] == [0] * len(st[k]) for k in COUNTERS), st
         else:
