@@ -603,6 +603,28 @@ struct ArenaLayout {
 	       oprow = 0, Tm = 0, Pc = 0, wmask = 0, stride = 0;
 };
 
+// The three ways a block goes down the panel stream (enqueue_block_panel; block_way picks one):
+//   General      the G + 1 general panel steps, the dense one-launch search in front of them where fast_block_possible
+//   DenseOnly    k_block_fast + the one-pass narrow step only (or the two fused: k_block_fast_narrow)
+//   SparseOnly   k_block_sparse + the one-pass narrow step only
+enum class BlockWay { General, DenseOnly, SparseOnly };
+
+// What changes while the forward pass of a solve is being enqueued: which one-launch search the blocks get, and what the host has
+// learnt from the blocks a search handed back.  One pass per Solver, so the initial values are the pass's.
+struct ForwardRun {
+	// Optimistic enqueue for dense systems: block 0 took the dense search, so the blocks that can take it at all get it alone
+	bool dense_only = false;
+	// Sparse systems (round 5): blocks the dense one-launch search cannot take go through k_block_sparse -- candidates = the alive rows
+	// with a non-zero window, from the bit masks the look-ahead leaves in wmask (allowed at all: kn.sparse_fast)
+	bool sparse_on = false;       // this solve has switched to it (after block 0 went the general way)
+	int tier = 0;                 // pool size of k_block_sparse, an index into kSparsePools: 0 = 1024 rows (beside the bulk update), 1 = 4096, 2 = 6144
+	int giveups = 0, why[5] = {}; // blocks handed back to the general steps (gf2bv_stats::sparse_giveups), and by the kernel's reason 1..5 (SolveState::sp_why)
+	// the first block of each pool size is looked at before anything is enqueued behind it: a pool that cannot serve the system (too
+	// many rows carry a bit in a window) costs one block, not a poisoned pipeline of all the blocks behind it
+	int probes = 1;
+	int general_only = -1;        // (after a hand-back) this one block takes the general steps whatever the mode
+};
+
 // What a solve IS apart from the device and pool resources it holds: the shape, the plan, the counters and the host copies.  Plain
 // values, free to copy -- a gang's views and the copy of a kept factorization start from their original's (make_view, factor_copy).
 struct SolverPlan {
@@ -644,12 +666,7 @@ struct SolverPlan {
 	                              // streaming row accesses (single systems keep plain ones: measured <= 1 % either way in round 4); false: the plain grid
 	int sync_base = 0;            // the counters only grow: a pass that re-enqueues blocks (resume after a poisoned one) counts from here
 	int units = 0;
-	// sparse systems (round 5): blocks the dense one-launch search cannot take go through k_block_sparse -- candidates = the alive rows
-	// with a non-zero window, from the bit masks the look-ahead leaves in wmask (allowed at all: kn.sparse_fast)
-	bool sparse_on = false;       // this solve has switched to it (after block 0 went the general way)
-	int sparse_giveups = 0;       // blocks handed back to the general steps, both resume paths of enqueue_forward together
-	int sparse_why[5] = {};       // ... by the kernel's reason 1..5 (SolveState::sp_why)
-	int sparse_tier = 0;          // pool size of k_block_sparse: 0 = 1024 rows (beside the bulk update), 1 = 4096, 2 = 6144
+	ForwardRun run;               // what the forward pass decides while it is enqueued (fill_stats and the look-ahead read it)
 	int narrow_rpt = 1;           // row blocks of 256 per narrow workgroup of a panel step (set in solver_alloc)
 	i64 ys = 0;
 	int ny = 0;
@@ -1114,13 +1131,28 @@ BlockGeom block_geom(const Solver &S, int b)
 	return g;
 }
 
-// stream A: factorise block b on its compact window -- step s narrows panel s-1 (window half (s-1)&1 -> half s&1)
-// while searching panel s; gb+1 launches; evA[b] = "block b factorised"
-// fast_only: the block gets the one-launch search and the one-pass narrow step only (see enqueue_forward)
 bool fast_block_possible(const Solver &S, const BlockGeom &g)
 {
 	return S.kn.fast && g.gb == GF2_GMAX && (i64)(g.j0 + g.gb) * 64 <= S.cols && S.rows >= GF2_FAST_NC;
 }
+
+// Which way block b goes now.  A one-launch search alone only for a block that can take one at all, and never for the block that was
+// just handed back; the dense one wants enough rows left, too.
+BlockWay block_way(const Solver &S, int b)
+{
+	if (b == S.run.general_only || !fast_block_possible(S, block_geom(S, b))) return BlockWay::General;
+	if (S.run.sparse_on) return BlockWay::SparseOnly;
+	// rows left when the block starts: at most 64 leftover candidates sit below the bound besides the pivots found
+	return S.run.dense_only && S.rows - (i64)b * 64 * S.impl->G >= GF2_FAST_NC + 128 ? BlockWay::DenseOnly : BlockWay::General;
+}
+
+// The pool sizes of k_block_sparse, by ForwardRun::tier (tests/sparse_cases.py: POOLS)
+struct SparsePool { decltype(&k_block_sparse<256, 4>) search; int threads, rows; };
+const SparsePool kSparsePools[] = {
+	{ k_block_sparse<256, 4>, 256, 1024 },       // beside the bulk update
+	{ k_block_sparse<512, 8>, 512, 4096 },       // after a give-up, or when the first block counted more rows than the small pool holds
+	{ k_block_sparse<1024, 6>, 1024, 6144 },     // after two: 1024 threads at 128 registers, the candidates' words partly in scratch: slow, but still ahead of five general steps
+};
 
 // flag hand-over, panel stream: "block b factorised" (its multipliers are complete) -- and, where the look-ahead of block b
 // follows (every block but the last), the wait for the bulk update of block b - 1 that k_prio_window needs
@@ -1132,7 +1164,9 @@ int panel_handover(Solver &S, int b)      // general panel steps: a launch for t
 }
 
 constexpr int kSparseByDensity = 2;      // k_panel_step's search mode: it skips absent columns per chunk, by density (0 never, 1 always)
-int enqueue_block_panel(Solver &S, int b, bool fast_only = false, bool sparse = false)
+// stream A: factorise block b on its compact window -- step s narrows panel s-1 (window half (s-1)&1 -> half s&1)
+// while searching panel s; gb+1 launches; evA[b] = "block b factorised"
+int enqueue_block_panel(Solver &S, int b, BlockWay way = BlockWay::General)
 {
 	const BlockGeom g = block_geom(S, b);
 	const unsigned row_blocks = (unsigned)((S.rows + 255) / 256);
@@ -1140,7 +1174,7 @@ int enqueue_block_panel(Solver &S, int b, bool fast_only = false, bool sparse = 
 	// a one-launch block's last launch announces narrow_done itself (flag_sync) or carries evA[b] as its completion signal
 	const hipEvent_t done = S.flag_sync ? nullptr : S.evA[b];
 	const DoneSignal sig = S.flag_sync ? DoneSignal{ &S.sf->cnt_narrow, &S.sf->narrow_done, S.sync_base + b + 1 } : DoneSignal{};
-	if (fast_only && !sparse && S.kn.fused_narrow && S.nsys == 1) {
+	if (way == BlockWay::DenseOnly && S.kn.fused_narrow && S.nsys == 1) {
 		// search + narrow step in one launch: workgroup 0 searches, the others narrow each panel as soon as it is formed
 		// (single systems: a gang is throughput-bound, and its ~130 x nsys narrowing workgroups would hold their LDS for the whole
 		// search -- measured equal either way, 243 against 242 systems/s of 32768^2: gangs keep the two launches)
@@ -1155,31 +1189,23 @@ int enqueue_block_panel(Solver &S, int b, bool fast_only = false, bool sparse = 
 		HIPCHK(hipGetLastError());
 		return GF2BV_OK;
 	}
-	if (fast_only) {
-		if (!sparse)
-			k_block_fast<<<dim3(1, S.nsys), dim3(256), 0, S.sA>>>(S.M, S.rows, S.srows, g.j0, g.gb, 1, b, (const u64 *)half[0], S.st, S.died,
-			                                                      S.panels, S.aux, S.pivcol, S.urow, S.blk_first + b, S.Pfast, S.ss());
+	if (way == BlockWay::SparseOnly) {
 		// sparse systems: the pool of the search = alive rows with a non-zero window (wmask, left by the look-ahead of the block before)
-		else if (S.sparse_tier == 0)
-			k_block_sparse<256, 4><<<dim3(1, S.nsys), dim3(256), 0, S.sA>>>(S.M, S.rows, S.srows, g.j0, g.gb, 1, b, (const u64 *)half[0], S.st, S.died,
-			                                                                 S.panels, S.aux, S.pivcol, S.urow, S.blk_first + b, (const u64 *)S.wmask, S.ss());
-		else if (S.sparse_tier == 1)             // (after a give-up, or when the first block counted more rows than the small pool holds: 4096 rows)
-			k_block_sparse<512, 8><<<dim3(1, S.nsys), dim3(512), 0, S.sA>>>(S.M, S.rows, S.srows, g.j0, g.gb, 1, b, (const u64 *)half[0], S.st, S.died,
-			                                                                S.panels, S.aux, S.pivcol, S.urow, S.blk_first + b, (const u64 *)S.wmask, S.ss());
-		else          // (after two: 6144 rows -- 1024 threads at 128 registers, the candidates' words partly in scratch: slow, but still ahead of five general steps)
-			k_block_sparse<1024, 6><<<dim3(1, S.nsys), dim3(1024), 0, S.sA>>>(S.M, S.rows, S.srows, g.j0, g.gb, 1, b, (const u64 *)half[0], S.st, S.died,
-			                                                                  S.panels, S.aux, S.pivcol, S.urow, S.blk_first + b, (const u64 *)S.wmask, S.ss());
+		const SparsePool &pool = kSparsePools[S.run.tier];
+		pool.search<<<dim3(1, S.nsys), dim3(pool.threads), 0, S.sA>>>(S.M, S.rows, S.srows, g.j0, g.gb, 1, b, (const u64 *)half[0], S.st, S.died,
+		                                                             S.panels, S.aux, S.pivcol, S.urow, S.blk_first + b, (const u64 *)S.wmask, S.ss());
+	} else if (way == BlockWay::DenseOnly || fast_block_possible(S, g))
+		// dense blocks: all G panels from a few hundred candidate rows in one launch; the general steps behind it find the
+		// block done (or, when it gave up, untouched)
+		k_block_fast<<<dim3(1, S.nsys), dim3(256), 0, S.sA>>>(S.M, S.rows, S.srows, g.j0, g.gb, way == BlockWay::DenseOnly, b, (const u64 *)half[0], S.st, S.died,
+		                                                      S.panels, S.aux, S.pivcol, S.urow, S.blk_first + b, S.Pfast, S.ss());
+	if (way != BlockWay::General) {
 		hipExtLaunchKernelGGL(k_narrow_all, dim3((row_blocks + S.narrow_rpt - 1) / S.narrow_rpt, S.nsys), dim3(256), 0, S.sA, nullptr, done, 0,
 		                      (const u64 *)S.M, S.rows, S.srows, g.j0, b, (const u64 *)half[0], (const SolveState *)S.st, (const int *)S.died,
 		                      (const PanelAux *)S.aux, g.mset, S.impl->T, S.narrow_rpt, sig, S.ss());
 		HIPCHK(hipGetLastError());
 		return GF2BV_OK;
 	}
-	// dense blocks: all G panels from a few hundred candidate rows in one launch; the general steps behind it find the
-	// block done (or, when it gave up, untouched)
-	if (fast_block_possible(S, g))
-		k_block_fast<<<dim3(1, S.nsys), dim3(256), 0, S.sA>>>(S.M, S.rows, S.srows, g.j0, g.gb, 0, b, (const u64 *)half[0], S.st, S.died,
-		                                                      S.panels, S.aux, S.pivcol, S.urow, S.blk_first + b, S.Pfast, S.ss());
 	for (int s = 0; s <= g.gb; s++) {
 		const int gp = s - 1, gf = (s < g.gb) ? s : -1;
 		const i64 c0 = (i64)(g.j0 + std::max(gf, 0)) * 64;
@@ -1263,7 +1289,7 @@ int enqueue_block_prio(Solver &S, int b)
 	}
 	k_prio_window<<<dim3(row_blocks, S.nsys), dim3(256), 0, S.sA>>>(S.M, S.rows, S.srows, g.j0, g.gb, g.wlo, std::max(g.gnext, 1),
 	                                                             S.panels, S.aux, g.mset, S.blk_first + b, S.Wb, S.Uwin,
-	                                                             S.impl->T, S.st, S.ss(), (const int *)S.died, S.sparse_on ? S.wmask : (u64 *)nullptr);
+	                                                             S.impl->T, S.st, S.ss(), (const int *)S.died, S.run.sparse_on ? S.wmask : (u64 *)nullptr);
 	HIPCHK(hipGetLastError());
 	return GF2BV_OK;
 }
@@ -1306,6 +1332,15 @@ int enqueue_check_rhs(Solver &S)
 	return GF2BV_OK;
 }
 
+// Two-level elimination: the row lists and T of the panel that starts at block b0 -- two buffers of each, by panel parity (the
+// previous panel's outer pass may still be reading its own)
+struct OuterBufs { int *prow; u64 *Tm; };
+OuterBufs outer_bufs(const Solver &S, int b0)
+{
+	const size_t parity = (size_t)((b0 / S.tl_K) % S.nlist);
+	return { S.oprow + parity * GF2_OUTER_LISTS, S.Tm + parity * ((size_t)GF2_KMAX * GF2_KMAX * GF2_GMAX * 64 * GF2_GMAX) };
+}
+
 // Two-level elimination, the outer step of the panel of blocks [b0, b1) on the column tiles [t_begin, t_end): pivot rows
 // brought up to date there (k_outer_trsm), then all the panel's blocks applied in one pass (k_update16k).  One workgroup per
 // ITEM (tile, chunk of rows) -- not persistent ones: CUs come free all the time, and the next panel's elimination, whose
@@ -1319,13 +1354,11 @@ int enqueue_outer_prepare(Solver &S, hipStream_t st, int b0, int b1)
 	const int G = S.impl->G;
 	const i64 set_words = (i64)G * mult_rows(S.rows);
 	const int npan = (b1 - b0) * G;
-	// (lists: two buffers by panel parity, T: two as well -- the previous panel's outer pass may still be reading its own)
-	int *gprow = S.oprow + (size_t)((b0 / S.tl_K) % S.nlist) * GF2_OUTER_LISTS;
-	u64 *Tm = S.Tm + (size_t)((b0 / S.tl_K) % S.nlist) * ((size_t)GF2_KMAX * GF2_KMAX * GF2_GMAX * 64 * GF2_GMAX);
-	k_outer_prow<<<dim3(1, S.nsys), dim3(256), 0, st>>>(b0 * G, b1 - b0, S.panels, S.aux, gprow, S.ss());
+	const OuterBufs ob = outer_bufs(S, b0);
+	k_outer_prow<<<dim3(1, S.nsys), dim3(256), 0, st>>>(b0 * G, b1 - b0, S.panels, S.aux, ob.prow, S.ss());
 	if (!S.kn.outer_chain)
 		k_outer_trsm<4, true><<<dim3((unsigned)(npan / 4), S.nsys), dim3(256), 0, st>>>(S.M, S.rows, S.srows, b0 * G, npan, 0, S.panels, S.aux, S.mult,
-		                                                                               set_words, b0 % S.nsets, S.nsets, S.impl->T, Tm, S.ss());
+		                                                                               set_words, b0 % S.nsets, S.nsets, S.impl->T, ob.Tm, S.ss());
 	HIPCHK(hipGetLastError());
 	return GF2BV_OK;
 }
@@ -1338,15 +1371,14 @@ int enqueue_outer_apply(Solver &S, hipStream_t st, int b0, int b1, i64 t_begin, 
 	const i64 nt = t_end - t_begin;
 	if (nt <= 0) return GF2BV_OK;
 	const i64 set_words = (i64)G * mult_rows(S.rows);
-	int *gprow = S.oprow + (size_t)((b0 / S.tl_K) % S.nlist) * GF2_OUTER_LISTS;
+	const OuterBufs ob = outer_bufs(S, b0);
 	const int npan = (b1 - b0) * G;
 	if (S.kn.outer_chain) {
 		const i64 g_begin = t_begin * TW / 4, ng = t_end * TW / 4 - g_begin;
 		k_outer_trsm<4, false><<<dim3((unsigned)ng, S.nsys), dim3(256), 0, st>>>(S.M, S.rows, S.srows, b0 * G, npan, (int)g_begin, S.panels, S.aux,
 		                                                                          S.mult, set_words, b0 % S.nsets, S.nsets, S.impl->T, (u64 *)nullptr, S.ss());
 	} else
-		k_outer_apply<<<dim3((unsigned)nt, S.nsys), dim3(512), 0, st>>>(S.M, S.rows, S.srows, b1 - b0, (const int *)gprow,
-		                                                                (const u64 *)(S.Tm + (size_t)((b0 / S.tl_K) % S.nlist) * ((size_t)GF2_KMAX * GF2_KMAX * GF2_GMAX * 64 * GF2_GMAX)), (int)t_begin, S.ss());
+		k_outer_apply<<<dim3((unsigned)nt, S.nsys), dim3(512), 0, st>>>(S.M, S.rows, S.srows, b1 - b0, (const int *)ob.prow, (const u64 *)ob.Tm, (int)t_begin, S.ss());
 	HIPCHK(hipGetLastError());
 	hipEvent_t ka = nullptr, kb = nullptr;
 	if (S.time_kernels) {
@@ -1360,7 +1392,7 @@ int enqueue_outer_apply(Solver &S, hipStream_t st, int b0, int b1, i64 t_begin, 
 	const i64 nch = std::max<i64>(1, (R64 - est_lo + item_rows - 1) / item_rows);
 	const i64 wgs = std::min<i64>(nch * nt, (i64)1 << 30);
 	hipExtLaunchKernelGGL(k_update16k_wide, dim3((unsigned)wgs, S.nsys), dim3(1024), 0, st, ka, kb, 0,
-	                      S.M, S.rows, S.srows, b1 - b0, (const int *)gprow, (const u64 *)S.mult,
+	                      S.M, S.rows, S.srows, b1 - b0, (const int *)ob.prow, (const u64 *)S.mult,
 	                      set_words, b0 % S.nsets, S.nsets, (const int *)(S.blk_first + b0), (const int *)S.died, b1 * G, (int)t_begin, (int)nt, S.ss(), 1);
 	HIPCHK(hipGetLastError());
 	if (S.kn.debug_sync & 2) HIPCHK(hipDeviceSynchronize());
@@ -1375,172 +1407,164 @@ int enqueue_window_gather(Solver &S, int b)
 	return GF2BV_OK;
 }
 
-int enqueue_forward(Solver &S)
+// The solve's state as the panel stream has left it, on the host (a host wait: everything submitted to the panel stream has run)
+int read_state(Solver &S, SolveState *hst)
 {
-	Trace tr;
-	int rc = enqueue_forward_begin(S, true);
-	if (rc) return rc;
+	HIPCHK(hipMemcpyAsync(hst, S.st, sizeof *hst, hipMemcpyDeviceToHost, S.sA));
+	HIPCHK(hipStreamSynchronize(S.sA));
+	return GF2BV_OK;
+}
+
+// A one-launch search could not take block pb and poisoned the panel path from there on (SolveState::poison, read by the host): every
+// later panel-path kernel has returned at once, the bulk and outer kernels found no pivots for the unpublished blocks and did nothing,
+// and the matrix and the window buffer are exactly as that block needs.  Everything in flight is drained, the plan cut back to what
+// has run and the counters rebased; block pb takes the general steps when the caller enqueues it again, and the blocks behind it the
+// next pool size -- or, where the host looked at the block before anything was enqueued behind it (`rearm`), the largest at once if the
+// search counted more rows than the middle pool holds (`want`); a hand-back met after submission knows no `want` and takes no further
+// look.  Give-ups of the sparse search are counted, by the kernel's reason too; the third of a solve switches it off.
+int hand_back(Solver &S, int pb, const SolveState &hst, int want, bool rearm)
+{
+	if (S.sC) HIPCHK(hipStreamSynchronize(S.sC));
+	HIPCHK(hipStreamSynchronize(S.sB));
+	// (two-level: the outer panels before the poisoned one are complete; the published blocks of the poisoned panel have been
+	// applied to its own tiles by the bulk kernels and to everything right of it by its outer pass -- every tile has seen
+	// exactly the blocks before pb -- so the rest runs as a one-level schedule)
+	if (S.tl_K && pb < S.tl_bend) S.tl_bend = pb / S.tl_K * S.tl_K;
+	S.bulk_waits_outer = false;
+	HIPCHK(hipMemsetAsync(&S.st->poison, 0, sizeof(int), S.sA));
+	S.sync_base += S.nblocks + 1;
+	ForwardRun &run = S.run;
+	run.dense_only = false;
+	if (run.sparse_on) {
+		if (hst.sp_why >= 1 && hst.sp_why <= 5) run.why[hst.sp_why - 1]++;
+		if (++run.giveups >= 3) run.sparse_on = false;
+		if (rearm && run.sparse_on) run.probes = 1;      // (the larger pools get one look each, too)
+	}
+	static_assert(sizeof kSparsePools == 3 * sizeof kSparsePools[0], "ForwardRun::tier indexes kSparsePools; gf2bv_stats::sparse_blocks[3] counts by it");
+	run.tier = std::min(2, std::max(run.tier + 1, want));
+	run.general_only = pb;
+	return GF2BV_OK;
+}
+
+// One block of the forward pass: panel path, bulk path, the next block's window.
+// Sparse systems (round 5): when block 0 did NOT take the dense search, the following full blocks get k_block_sparse + k_narrow_all
+// instead of the G + 1 general panel steps (one-level schedules only; the look-ahead of every block leaves the masks the next
+// block's pool is taken from).  A block it cannot take is handed back like a failed optimistic block: THAT block takes the general
+// steps and the search goes on behind it -- twice; the third give-up of a solve switches it off and the rest runs general.
+int forward_block(Solver &S, int blk)
+{
+	int rc;
+	SolveState hst;
+	const BlockWay way = block_way(S, blk);
+	if ((rc = enqueue_block_panel(S, blk, way))) return rc;
+	if (way == BlockWay::SparseOnly && S.run.probes > 0) {
+		S.run.probes--;
+		if ((rc = read_state(S, &hst))) return rc;
+		// the pool for the blocks behind this one: a search that counted far more rows with a bit in its window than the middle pool
+		// holds goes straight to the largest (MT19937, one bit per output: 4500-5000).  Otherwise the SMALL pool stays while it works,
+		// truncated or not -- it is the one that fits beside the bulk update, and the first 1024 candidate rows usually hold a panel's
+		// pivots (measured: 17 / 1337 / 137 bits per output count 1100-1560 rows and run 7.4 / 6.3 / 6.7 ms on the small pool, 7.9 /
+		// 7.1 / 7.4 on the middle one); a pool that does not gives up and the next size takes over
+		const int want = hst.sp_nz > 3400 ? 2 : 0;
+		if (hst.poison) return (rc = hand_back(S, blk, hst, want, true)) ? rc : forward_block(S, blk);      // (the same block again: general)
+		S.run.tier = std::max(S.run.tier, want);
+	}
+	if ((rc = enqueue_block_bulk(S, blk))) return rc;
+	if ((rc = enqueue_block_prio(S, blk))) return rc;
 	// Optimistic enqueue for dense systems.  k_block_fast decides ON THE DEVICE whether a block goes the fast way, so the
 	// general panel steps have to be enqueued behind it all the same, and on a fast block they are G + 1 empty launches
 	// of ~4.5 us each on the critical path (and, beside an outer pass, ~500 workgroups each that take CUs from it).  One look
 	// at the device settles it for the usual case: block 0 is enqueued both ways and the host waits for its panel path (a
 	// ~50 us stall, once per solve); if the fast search took it, the blocks that can take it at all (full blocks with enough
-	// rows left) get k_block_fast + k_narrow_all only.  Should the search give up on one of them after all, it poisons the
-	// panel path from there on (SolveState::poison): every later panel-path kernel returns at once, the bulk and outer kernels
-	// find no pivots for the unpublished blocks and do nothing, and the host resumes from that block with both paths and the
-	// one-level schedule -- the matrix and the window buffer are exactly as that block needs.
-	bool optimistic = false;
-	SolveState hst{};
-	const bool may_probe = S.kn.fast && S.optimistic && S.nsys == 1 && S.world == 1 && S.nblocks >= 8 && fast_block_possible(S, block_geom(S, 0));
-	auto fast_only_ok = [&](int blk) {
-		// rows left when the block starts: at most 64 leftover candidates sit below the bound besides the pivots found
-		return fast_block_possible(S, block_geom(S, blk)) && S.rows - (i64)blk * 64 * S.impl->G >= GF2_FAST_NC + 128;
-	};
-	// Sparse systems (round 5): when block 0 did NOT take the dense search, the following full blocks get k_block_sparse + k_narrow_all
-	// instead of the G + 1 general panel steps (one-level schedules only; the look-ahead of every block leaves the masks the next
-	// block's pool is taken from).  A block it cannot take poisons the panel path like a failed optimistic block: the host resumes
-	// there with the general steps for THAT block and goes on sparse behind it -- twice; the THIRD give-up of a solve, whichever of the
-	// two resume paths below meets it, switches the search off and the rest runs general (gf2bv_stats::sparse_giveups).
-	const bool may_sparse = may_probe && S.kn.sparse_fast && S.tl_K == 0;
-	int general_only = -1;                      // (resume) this one block takes the general steps whatever the mode
-	auto sparse_ok = [&](int blk) { return S.sparse_on && blk != general_only && fast_block_possible(S, block_geom(S, blk)); };
-	// after a poisoned block pb: everything in flight drained, the plan cut back to what has run, the counters rebased
-	auto recover = [&](int pb) -> int {
-		if (S.sC) HIPCHK(hipStreamSynchronize(S.sC));
-		HIPCHK(hipStreamSynchronize(S.sB));
-		// (two-level: the outer panels before the poisoned one are complete; the published blocks of the poisoned panel have been
-		// applied to its own tiles by the bulk kernels and to everything right of it by its outer pass -- every tile has seen
-		// exactly the blocks before pb -- so the rest runs as a one-level schedule)
-		if (S.tl_K && pb < S.tl_bend) S.tl_bend = pb / S.tl_K * S.tl_K;
-		S.bulk_waits_outer = false;
-		HIPCHK(hipMemsetAsync(&S.st->poison, 0, sizeof(int), S.sA));
-		S.sync_base += S.nblocks + 1;
-		return GF2BV_OK;
-	};
-	// a block the sparse search handed back (hst.poison read, either resume path): counted, by the kernel's reason too; the third of a
-	// solve switches the search off.  Returns whether the search stays on.
-	auto sparse_gave_up = [&]() {
-		if (hst.sp_why >= 1 && hst.sp_why <= 5) S.sparse_why[hst.sp_why - 1]++;
-		if (++S.sparse_giveups >= 3) S.sparse_on = false;
-		return S.sparse_on;
-	};
-	// the first block of each pool size is looked at before anything is enqueued behind it: a pool that cannot serve the system (too
-	// many rows carry a bit in a window) costs one block, not a poisoned pipeline of all the blocks behind it
-	int sparse_probes = 1;
-	auto one_block = [&](int blk) -> int {
-		int r;
-		bool sp = sparse_ok(blk);
-		if ((r = enqueue_block_panel(S, blk, sp || (optimistic && fast_only_ok(blk)), sp))) return r;
-		if (sp && sparse_probes > 0) {
-			sparse_probes--;
-			HIPCHK(hipMemcpyAsync(&hst, S.st, sizeof hst, hipMemcpyDeviceToHost, S.sA));
-			HIPCHK(hipStreamSynchronize(S.sA));
-			// the pool for the blocks behind this one: a search that counted far more rows with a bit in its window than the middle pool
-			// holds goes straight to the largest (MT19937, one bit per output: 4500-5000).  Otherwise the SMALL pool stays while it works,
-			// truncated or not -- it is the one that fits beside the bulk update, and the first 1024 candidate rows usually hold a panel's
-			// pivots (measured: 17 / 1337 / 137 bits per output count 1100-1560 rows and run 7.4 / 6.3 / 6.7 ms on the small pool, 7.9 /
-			// 7.1 / 7.4 on the middle one); a pool that does not gives up and the next size takes over
-			const int want = hst.sp_nz > 3400 ? 2 : 0;
-			if (hst.poison) {
-				if ((r = recover(blk))) return r;
-				if (sparse_gave_up()) sparse_probes = 1;      // (the larger pools get one look each, too)
-				S.sparse_tier = std::min(2, std::max(S.sparse_tier + 1, want));
-				general_only = blk;
-				if ((r = enqueue_block_panel(S, blk, false, false))) return r;
-			} else S.sparse_tier = std::max(S.sparse_tier, want);
+	// rows left) get k_block_fast + k_narrow_all only.  Should the search give up on one of them after all, the host resumes
+	// from that block (hand_back) with both paths and the one-level schedule.
+	if (blk == 0 && S.kn.fast && S.optimistic && S.nsys == 1 && S.world == 1 && S.nblocks >= 8 && fast_block_possible(S, block_geom(S, 0))) {
+		if ((rc = read_state(S, &hst))) return rc;
+		S.run.dense_only = hst.fast_done == 1;
+		if (!S.run.dense_only && S.kn.sparse_fast && S.tl_K == 0 && S.nblocks > 1) {
+			// block 1's window is in place (the look-ahead above ran without masks): its masks by a launch of their own
+			S.run.sparse_on = true;
+			k_window_masks<<<dim3((unsigned)((S.rows + 255) / 256), S.nsys), dim3(256), 0, S.sA>>>((const u64 *)S.Wb, S.rows, block_geom(S, 1).gb, (const int *)S.died,
+			                                                                                      S.wmask, (const SolveState *)S.st, S.ss());
+			HIPCHK(hipGetLastError());
 		}
-		if ((r = enqueue_block_bulk(S, blk))) return r;
-		if ((r = enqueue_block_prio(S, blk))) return r;
-		if (blk == 0 && may_probe) {
-			HIPCHK(hipMemcpyAsync(&hst, S.st, sizeof hst, hipMemcpyDeviceToHost, S.sA));
-			HIPCHK(hipStreamSynchronize(S.sA));
-			optimistic = hst.fast_done == 1;
-			if (!optimistic && may_sparse && S.nblocks > 1) {
-				// block 1's window is in place (the look-ahead above ran without masks): its masks by a launch of their own
-				S.sparse_on = true;
-				const BlockGeom g1 = block_geom(S, 1);
-				k_window_masks<<<dim3((unsigned)((S.rows + 255) / 256), S.nsys), dim3(256), 0, S.sA>>>((const u64 *)S.Wb, S.rows, g1.gb, (const int *)S.died, S.wmask,
-				                                                                                      (const SolveState *)S.st, S.ss());
-				HIPCHK(hipGetLastError());
-			}
-		}
-		return GF2BV_OK;
-	};
-	int b = 0;
-	// Two-level part (large single systems, plan_two_level): outer panels of tl_K blocks.  Inside a panel the blocks run
-	// exactly as in the one-level loop below -- panel and bulk stream, look-ahead from block to block -- with the bulk kernels
-	// confined to the panel's own tiles (tile_hi).  The outer step of panel p goes to a THIRD stream in two parts: first the
-	// tiles of panel p + 1 (a small launch), behind which that panel's first window is gathered and its elimination starts,
-	// then everything right of them, one workgroup per item so that the next panel's kernels find CUs while it runs.  What
-	// the two meet in: the multiplier sets (2 K of them: panel parity), the pivot marks (k_update16k takes "alive behind
-	// panel p", not "alive now") and disjoint tiles.
-	if (S.tl_K) {
-		const int G = S.impl->G;
-		hipStream_t so = S.sC ? S.sC : S.sB;           // (GF2BV_SERIAL: one stream, everything in order)
-		bool big_recorded = false;                     // evBig holds the end of the previous panel's pass (side launches)
-		for (int p0 = 0; p0 < S.tl_bend; p0 += S.tl_K) {
-			const int p1 = p0 + S.tl_K;
-			if (p0 > 0) {
-				HIPCHK(hipStreamWaitEvent(S.sA, S.evPri, 0));
-				if ((rc = enqueue_window_gather(S, p0))) return rc;
-			}
-			S.tile_hi = (i64)p1 * G / TW;
-			for (b = p0; b < p1; b++)
-				if ((rc = one_block(b))) return rc;
-			S.tile_hi = S.ntiles;
-			// the outer step needs the panel's records and multipliers (panel stream), not its bulk updates (other tiles)
-			if ((rc = enqueue_outer_prepare(S, S.sA, p0, p1))) return rc;
-			HIPCHK(hipEventRecord(S.evPanelDone, S.sA));
-			HIPCHK(hipStreamWaitEvent(so, S.evPanelDone, 0));
-			const i64 t_out = S.ntiles;
-			const i64 t0 = (i64)p1 * G / TW, t1 = std::min<i64>(t_out, t0 + (i64)S.tl_K * G / TW);
-			// (late round 5) the outer step on the NEXT panel's tiles -- a short launch on an underused chip, ~0.3 ms -- goes to the
-			// inner elimination's bulk stream, idle at this point, and runs BESIDE the start of the pass proper instead of before it:
-			// it needs the previous pass complete (evBig; it used to follow it in stream order) and this panel's T; the pass proper
-			// needs T alone (disjoint tiles).  No new stream.
-			const bool side = S.kn.outer_side && S.sB != so && S.sB != S.sA;
-			if (side) {
-				HIPCHK(hipStreamWaitEvent(S.sB, S.evPanelDone, 0));
-				if (big_recorded) HIPCHK(hipStreamWaitEvent(S.sB, S.evBig, 0));
-				if ((rc = enqueue_outer_apply(S, S.sB, p0, p1, t0, t1))) return rc;
-				HIPCHK(hipEventRecord(S.evPri, S.sB));
-				if ((rc = enqueue_outer_apply(S, so, p0, p1, t1, t_out))) return rc;
-			} else {
-				if ((rc = enqueue_outer_apply(S, so, p0, p1, t0, t1))) return rc;
-				HIPCHK(hipEventRecord(S.evPri, so));
-				if ((rc = enqueue_outer_apply(S, so, p0, p1, t1, t_out))) return rc;
-			}
-			// (round 6, VERDICT item 2a: P = T x S of the NEXT panel started behind the first chunk of this pass, beside its rest -- built,
-			// bit-exact, no gain: the launch is LDS table work like the pass itself, not idle chip time.  profiles/r06_outer_early.txt)
-			HIPCHK(hipEventRecord(S.evBig, so));
-			big_recorded = true;
-		}
-		HIPCHK(hipEventRecord(S.evOuter, so));
-		b = S.tl_bend;
-		HIPCHK(hipStreamWaitEvent(S.sA, S.evPri, 0));
-		if (b < S.nblocks && (rc = enqueue_window_gather(S, b))) return rc;
-		S.bulk_waits_outer = S.sC != nullptr;          // the one-level bulk updates behind it touch every trailing tile
 	}
-	for (; b < S.nblocks; b++)
-		if ((rc = one_block(b))) return rc;
+	return GF2BV_OK;
+}
+
+// Two-level part (large single systems, plan_two_level): outer panels of tl_K blocks.  Inside a panel the blocks run
+// exactly as in the one-level loop -- panel and bulk stream, look-ahead from block to block -- with the bulk kernels
+// confined to the panel's own tiles (tile_hi).  The outer step of panel p goes to a THIRD stream in two parts: first the
+// tiles of panel p + 1 (a small launch), behind which that panel's first window is gathered and its elimination starts,
+// then everything right of them, one workgroup per item so that the next panel's kernels find CUs while it runs.  What
+// the two meet in: the multiplier sets (2 K of them: panel parity), the pivot marks (k_update16k takes "alive behind
+// panel p", not "alive now") and disjoint tiles.  Leaves the window of block tl_bend, the first of the one-level part, in place.
+int enqueue_outer_panels(Solver &S)
+{
+	int rc;
+	const int G = S.impl->G;
+	hipStream_t so = S.sC ? S.sC : S.sB;           // (GF2BV_SERIAL: one stream, everything in order)
+	bool big_recorded = false;                     // evBig holds the end of the previous panel's pass (side launches)
+	for (int p0 = 0; p0 < S.tl_bend; p0 += S.tl_K) {
+		const int p1 = p0 + S.tl_K;
+		if (p0 > 0) {
+			HIPCHK(hipStreamWaitEvent(S.sA, S.evPri, 0));
+			if ((rc = enqueue_window_gather(S, p0))) return rc;
+		}
+		S.tile_hi = (i64)p1 * G / TW;
+		for (int b = p0; b < p1; b++)
+			if ((rc = forward_block(S, b))) return rc;
+		S.tile_hi = S.ntiles;
+		// the outer step needs the panel's records and multipliers (panel stream), not its bulk updates (other tiles)
+		if ((rc = enqueue_outer_prepare(S, S.sA, p0, p1))) return rc;
+		HIPCHK(hipEventRecord(S.evPanelDone, S.sA));
+		HIPCHK(hipStreamWaitEvent(so, S.evPanelDone, 0));
+		const i64 t0 = (i64)p1 * G / TW, t1 = std::min<i64>(S.ntiles, t0 + (i64)S.tl_K * G / TW);
+		// (late round 5) the outer step on the NEXT panel's tiles -- a short launch on an underused chip, ~0.3 ms -- goes to the
+		// inner elimination's bulk stream, idle at this point, and runs BESIDE the start of the pass proper instead of before it:
+		// it needs the previous pass complete (evBig; it used to follow it in stream order) and this panel's T; the pass proper
+		// needs T alone (disjoint tiles).  No new stream.
+		hipStream_t sn = S.kn.outer_side && S.sB != so && S.sB != S.sA ? S.sB : so;
+		if (sn != so) {
+			HIPCHK(hipStreamWaitEvent(sn, S.evPanelDone, 0));
+			if (big_recorded) HIPCHK(hipStreamWaitEvent(sn, S.evBig, 0));
+		}
+		if ((rc = enqueue_outer_apply(S, sn, p0, p1, t0, t1))) return rc;
+		HIPCHK(hipEventRecord(S.evPri, sn));
+		if ((rc = enqueue_outer_apply(S, so, p0, p1, t1, S.ntiles))) return rc;
+		// (round 6, VERDICT item 2a: P = T x S of the NEXT panel started behind the first chunk of this pass, beside its rest -- built,
+		// bit-exact, no gain: the launch is LDS table work like the pass itself, not idle chip time.  profiles/r06_outer_early.txt)
+		HIPCHK(hipEventRecord(S.evBig, so));
+		big_recorded = true;
+	}
+	HIPCHK(hipEventRecord(S.evOuter, so));
+	HIPCHK(hipStreamWaitEvent(S.sA, S.evPri, 0));
+	if (S.tl_bend < S.nblocks && (rc = enqueue_window_gather(S, S.tl_bend))) return rc;
+	S.bulk_waits_outer = S.sC != nullptr;          // the one-level bulk updates behind it touch every trailing tile
+	return GF2BV_OK;
+}
+
+int enqueue_forward(Solver &S)
+{
+	Trace tr;
+	int rc = enqueue_forward_begin(S, true);
+	if (rc) return rc;
+	if (S.tl_K && (rc = enqueue_outer_panels(S))) return rc;
+	for (int b = S.tl_K ? S.tl_bend : 0; b < S.nblocks; b++)
+		if ((rc = forward_block(S, b))) return rc;
 	if ((rc = enqueue_forward_join(S))) return rc;
 	tr.mark(S.kn, "forward: all blocks submitted");          // (host side only: the device is still working; what follows waits for it)
-	while (optimistic || S.sparse_on) {
-		HIPCHK(hipMemcpyAsync(&hst, S.st, sizeof hst, hipMemcpyDeviceToHost, S.sA));
-		HIPCHK(hipStreamSynchronize(S.sA));
+	// everything is submitted: a block a search handed back shows only now -- resume there, join again, look again
+	while (S.run.dense_only || S.run.sparse_on) {
+		SolveState hst;
+		if ((rc = read_state(S, &hst))) return rc;
 		if (!hst.poison) break;
-		{                                               // a block the fast search could not take: resume there, both paths
-			const int pb = hst.poison - 1;
-			if ((rc = recover(pb))) return rc;
-			optimistic = false;
-			if (S.sparse_on) (void)sparse_gave_up();
-			S.sparse_tier = std::min(2, S.sparse_tier + 1);
-			general_only = pb;
-			// (the poisoned block's window is in place; the blocks behind it take their masks from the look-aheads again)
-			for (b = pb; b < S.nblocks; b++)
-				if ((rc = one_block(b))) return rc;
-			if ((rc = enqueue_forward_join(S))) return rc;
-		}
+		const int pb = hst.poison - 1;
+		if ((rc = hand_back(S, pb, hst, 0, false))) return rc;
+		// (the poisoned block's window is in place; the blocks behind it take their masks from the look-aheads again)
+		for (int b = pb; b < S.nblocks; b++)
+			if ((rc = forward_block(S, b))) return rc;
+		if ((rc = enqueue_forward_join(S))) return rc;
 	}
 	return enqueue_check_rhs(S);
 }
@@ -1829,8 +1853,8 @@ void fill_stats(const Solver &S, gf2bv_result *R)
 	st.fast_blocks = hst.fast_blocks;
 	for (int i = 0; i < 3; i++) st.sparse_blocks[i] = hst.sp_blocks[i];
 	st.sparse_panels_first64 = hst.sp_first64; st.sparse_panels_absorb = hst.sp_absorb; st.sparse_panels_rounds = hst.sp_rounds;
-	st.sparse_giveups = S.sparse_giveups;
-	for (int i = 0; i < 5; i++) st.sparse_giveup_why[i] = S.sparse_why[i];
+	st.sparse_giveups = S.run.giveups;
+	for (int i = 0; i < 5; i++) st.sparse_giveup_why[i] = S.run.why[i];
 	st.sparse_nz_max = hst.sp_nz_max;
 	st.general_unit0 = hst.gs_unit0; st.general_adopted = hst.gs_adopt; st.general_merged = hst.gs_merge;
 	st.general_wide = hst.gs_wide; st.general_two_level = hst.gs_two_level;

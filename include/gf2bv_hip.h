@@ -93,8 +93,8 @@ typedef struct gf2bv_stats {
 	int32_t sparse_panels_first64;   /* panels of those blocks whose 64 pivot rows were the first 64 pool rows with a bit in the panel     */
 	int32_t sparse_panels_absorb;    /* ... that needed more of the first 512 such rows (at least one find_absorb chunk)                   */
 	int32_t sparse_panels_rounds;    /* ... that were selected by the rounds over the whole pool                                           */
-	int32_t sparse_giveups;          /* blocks the host handed back to the general panel steps after the search gave up on them (the probed
-	                                    first block of a pool size and the resume after a poisoned pipeline together); the third switches
+	int32_t sparse_giveups;          /* blocks the host handed back to the general panel steps after the search gave up on them (behind the
+	                                    probed first block of a pool size or after everything was submitted, alike); the third switches
 	                                    the search off for the rest of the solve                                                          */
 	int32_t sparse_giveup_why[5];    /* the search's give-ups by reason 1..5: [0] not a full block, [1] fewer than 256 rows with a non-zero
 	                                    window in reach, [2] the pool lacks 64 independent rows for a panel, [3] the chosen rows were not

@@ -10,7 +10,7 @@ their window holds: all-zero rows and the next block's home rows (zero in this w
 Every block's home rows are exactly 256 independent rows (255 + a dependent one in the three `giveup_panel*` cases), which all die
 whoever eliminates the block; every extra row is an all-zero row, which never dies.  So the rows that are alive when a block starts do
 not depend on what the general path picked, and `simulate` -- compaction, density gate, gj_columns, column-slot find_absorb, the narrow
-step of the unused candidates, new_first, iterated over the blocks with the host's rules of enqueue_forward / enqueue_block_panel --
+step of the unused candidates, new_first, iterated over the blocks with the host's rules of forward_block / block_way --
 arrives at gf2bv_stats::fast_blocks.  Where the general path's `fast_off` verdict (k_panel_step's publish: an easy, full last panel)
 cannot be read off the construction, the model runs both ways; the count is `("==", v)` where both agree and `(">=", low)` otherwise.
 
@@ -30,7 +30,7 @@ from tests.sparse_cases import DENSE_BITS, DENSE_WORDS, FAST_NC, G, MIN_BLOCKS, 
 
 FEW_MISSING = 8                 # GF2_FEW_MISSING: columns a main chunk may leave to the targeted completion
 REACH = 8 * 256                 # block_fast_body: the compaction looks at 8 rounds x 256 rows from the alive bound
-FAST_ONLY_ROWS = FAST_NC + 128  # enqueue_forward: fast_only_ok wants `rows - 256 blk >= 448`
+FAST_ONLY_ROWS = FAST_NC + 128  # block_way: the dense search alone wants `rows - 256 blk >= 448`
 FEW_UNITS = 8                   # GF2_FEW_UNITS: search units of an easy general panel; unit 0's slice starts at the alive bound
 HARD_CHUNKS = 8                 # search_panel: a publisher that scanned more than 8 chunks of 64 rows calls the panel hard
 GAP = "gap"                     # build_block: a candidate slot that belongs to whatever follows the block (zero in its window)

@@ -5,7 +5,7 @@ changed by the elimination of another panel and causes no fill-in, so a system m
 window k_block_sparse meets at block b is exactly what was written here.  Its pool is the alive rows with a non-zero window in row
 order: the rows written for the block's four panels, in the order they were written.  Depth in the pool, the rank of the first 64 and
 the first 512 entries of a panel and the rank of the truncated pool on a panel can therefore be read off the construction with an
-integer echelon basis (`rank_of`), and `predict` walks the branches of the kernel and of the host's two resume paths over them.
+integer echelon basis (`rank_of`), and `predict` walks the branches of the kernel and of the host's hand-backs (hand_back: probed, or met after submission) over them.
 
 Every case carries the counters it expects (gf2bv_stats::sparse_*): `("==", v)` where the construction fixes the value, `(">=", v)`
 where it only bounds it.  tests/test_sparse_cases_cpu.py checks the preconditions and that `predict` arrives at the exact ones;
@@ -17,14 +17,14 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-POOLS = (1024, 4096, 6144)      # k_block_sparse<256, 4> / <512, 8> / <1024, 6>: NT x CPT candidates (enqueue_block_panel, by sparse_tier)
+POOLS = (1024, 4096, 6144)      # kSparsePools, by ForwardRun::tier: k_block_sparse<256, 4> / <512, 8> / <1024, 6>, NT x CPT candidates
 SP_NE = 512                     # GF2_SP_NE: entries of a panel that selection (A) looks at
 SP_NW = 1024                    # GF2_SP_NW: mask words (of 64 rows) the pool is gathered from, counted from the alive bound's word
-NZ_LARGEST = 3400               # enqueue_forward: `hst.sp_nz > 3400` on a probed block sends the blocks behind it to the largest pool
+NZ_LARGEST = 3400               # forward_block: `hst.sp_nz > 3400` on a probed block sends the blocks behind it to the largest pool
 CYCLE = 8                       # SolveState::sp_chunk `& 7`: after a miss of (A) seven blocks go straight to the rounds (B)
-STRIKES = 3                     # enqueue_forward: the third give-up of a solve switches the search off
+STRIKES = 3                     # hand_back: the third give-up of a solve switches the search off
 FAST_NC = 320                   # GF2_FAST_NC: rows a system needs for any one-launch search (fast_block_possible)
-MIN_BLOCKS = 8                  # enqueue_forward: may_probe wants `nblocks >= 8`
+MIN_BLOCKS = 8                  # forward_block: the look at block 0 wants `nblocks >= 8`
 G = 4                           # GF2_GMAX: panels of a block
 DENSE_WORDS, DENSE_BITS = 48, 12      # k_block_fast: it takes a panel when 48 of the 64 candidate words have more than 12 bits
 TWO_LEVEL_MIN_BYTES = 1 << 29   # plan_two_level: `min_bytes = 0.5 * 1073741824.0` of trailing matrix before outer panels are planned
@@ -245,7 +245,7 @@ class Case:
         raise KeyError(b)
 
     def check_preconditions(self) -> None:
-        """what enqueue_forward wants before it lets k_block_sparse at a block"""
+        """what forward_block and block_way want before they let k_block_sparse at a block"""
         rows = self.coefficient_rows()
         aug = self.aug()
         assert aug.ndim == 2 and aug.shape[0] == len(rows), "a single system: one rows x words matrix (a gang never takes the search)"
@@ -264,7 +264,7 @@ class Case:
 
 
 def predict(case: Case) -> dict:
-    """The branches k_block_sparse and the host's two resume paths take over a diagonal case, from ranks and depths alone: the counters
+    """The branches k_block_sparse and the host's hand-backs (probed, or met after submission) take over a diagonal case, from ranks and depths alone: the counters
     of gf2bv_stats::sparse_* and, per block, what happened ("trace")."""
     assert case.diagonal
     st = {"sparse_blocks": [0, 0, 0], "sparse_panels_first64": 0, "sparse_panels_absorb": 0, "sparse_panels_rounds": 0,
@@ -445,10 +445,22 @@ def all_cases() -> list:
     C.append(_case("straight_to_largest", 2304, 53, lambda b, r: front_loaded_block(r, 3300) if b == 1 else easy_block(r),
                    {"sparse_blocks": eq([1, 0, 7]), "sparse_panels_first64": eq(32), "sparse_panels_absorb": eq(0),
                     "sparse_panels_rounds": eq(0), "sparse_nz_max": eq(3556), **NO_GIVEUP}))
+    # ... and 5000 deep on the probed block itself: the small pool gives up having counted more than NZ_LARGEST rows, and the search
+    # skips the middle pool (a probed hand-back raises the pool to max(next, wanted), not by one)
+    C.append(_case("escalate_skip_middle", 2304, 54, lambda b, r: deep_block(r, 5000) if b in (1, 2) else easy_block(r),
+                   {"sparse_blocks": eq([0, 0, 7]), "sparse_panels_first64": eq(3), "sparse_panels_absorb": eq(0),
+                    "sparse_panels_rounds": eq(25), "sparse_giveups": eq(1), "sparse_giveup_why": eq([0, 0, 1, 0, 0]),
+                    "sparse_nz_max": eq(5001)}))
     # pipelined resume: blocks 1..4 easy, block 5 needs depth 1500 -- found after everything was submitted; the middle pool behind it
     C.append(_case("pipelined", 2304, 61, lambda b, r: deep_block(r, 1500) if b == 5 else easy_block(r),
                    {"sparse_blocks": eq([4, 3, 0]), "sparse_panels_first64": eq(28), "sparse_panels_absorb": eq(0),
                     "sparse_panels_rounds": eq(0), "sparse_giveups": eq(1), "sparse_giveup_why": eq([0, 0, 1, 0, 0])}))
+    # ... 5000 deep, twice: a hand-back found after submission raises the pool by one whatever was counted, so block 5 brings the
+    # middle pool, block 6 gives up on that one (pipelined again: no probe is re-armed) and brings the largest -- two give-ups
+    C.append(_case("pipelined_deep", 2304, 62, lambda b, r: deep_block(r, 5000) if b in (5, 6) else easy_block(r),
+                   {"sparse_blocks": eq([4, 0, 2]), "sparse_panels_first64": eq(24), "sparse_panels_absorb": eq(0),
+                    "sparse_panels_rounds": eq(0), "sparse_giveups": eq(2), "sparse_giveup_why": eq([0, 0, 2, 0, 0]),
+                    "sparse_nz_max": eq(5001)}))
     # three strikes: blocks no pool completes, in a row; after the third give-up the rest runs general.  Probed (blocks 1..3: each is
     # the first block of its pool size) and pipelined (block 1 passes its probe; 2..4 are found after everything was submitted)
     C.append(_case("strikes_probed", 2304, 71, lambda b, r: deficient_block(r) if b in (1, 2, 3) else easy_block(r),
@@ -504,7 +516,7 @@ def cases() -> dict:
 
 
 NAMES = ["first64", "absorb_100", "absorb_511", "absorb_512", "cycle", "truncated", "escalate_middle", "escalate_largest",
-         "straight_to_largest", "pipelined", "strikes_probed", "strikes_pipelined", "reasons_5_and_2", "alive_top", "alive_reverse",
+         "straight_to_largest", "escalate_skip_middle", "pipelined", "pipelined_deep", "strikes_probed", "strikes_pipelined", "reasons_5_and_2", "alive_top", "alive_reverse",
          "alive_min_free", "alive_min_free_row_in_two_blocks", "beyond_window", "inconsistent", "shuffled_fill_in_light", "shuffled_fill_in_heavy"]
 
 

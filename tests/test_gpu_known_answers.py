@@ -22,7 +22,7 @@ def _need_gpu():
 
 @pytest.fixture(autouse=True, params=["default", "plain"])
 def heuristics(request, monkeypatch):
-    """Every test twice, as in test_gpu_parity.py: as shipped (optimistic enqueue of fast blocks, cut back by recover() when the
+    """Every test twice, as in test_gpu_parity.py: as shipped (optimistic enqueue of fast blocks, cut back by hand_back() when the
     search gives up inside an outer panel) and with GF2BV_PLAIN=1 (both panel paths for every block)."""
     if request.param == "plain":
         monkeypatch.setenv("GF2BV_PLAIN", "1")
@@ -144,7 +144,7 @@ def placement(name, rows, cols, seed):
 def expected_outer_blocks(rows, cols, free, mode):
     """Blocks the outer panels took.  Plain mode: the plan less the blocks without a pivot (the outer pass skips them).  Default mode:
     the one-launch search takes block 0 of a dense system, the later fast blocks are enqueued without the general steps, and the
-    first block it cannot take (a free column) poisons the panel path: recover() cuts the plan back to that block's outer panel.
+    first block it cannot take (a free column) poisons the panel path: hand_back() cuts the plan back to that block's outer panel.
     With a free column in block 0 nothing is enqueued optimistically, and the plain rule holds."""
     K, bend, nb = KA.plan_two_level(rows, cols)
     if not K:

@@ -1,6 +1,6 @@
 """k_block_sparse branch by branch: the built systems of tests/sparse_cases.py through hip.solve_words as shipped.  Per case and mode the
 oracle's answers (status, rank, pivots, origin, basis and its order) AND the counters that say which branch ran
-(gf2bv_stats::sparse_*: pool size, selection outcome per panel, give-ups by reason and by resume path) -- exact where the construction
+(gf2bv_stats::sparse_*: pool size, selection outcome per panel, give-ups by reason, probed or met after submission) -- exact where the construction
 fixes them.  The same systems with the search switched off (all its counters zero) and with events instead of flags; three of them
 through a kept factorization, which replays slot_row / comb / src_mult as this kernel wrote them."""
 import functools
