@@ -4236,7 +4236,8 @@ k_space_enumerate(const u64 *__restrict__ origin, const u64 *__restrict__ basis,
 // one wavefront was round 3's attempt (1.15 ms for 640 x 256: a barrier and ten LDS round trips per COLUMN, removed).
 //
 // Input: row-major words (src, stride) or CPython digits (digits / off / bpd, as k_pack_digits).  Output, one buffer
-// (all of it copied back in one piece): out[0] = rank, out[1] = inconsistent, out[2] = number of free columns written;
+// (all of it copied back in one piece): out[0] = rank, out[1] = inconsistent, out[2] = number of free columns written,
+// out[3] = passes that ran | the kinds of pass among them << 16 (below);
 // int32 pivcols[cols] from byte 16; then from the next 8-byte boundary cw words of origin and, want_basis, nfree x cw
 // words Y -- row j belongs to the j-th pivot-less column in ascending order.
 #define GF2_SMALL_MAXCOLS 1023
@@ -4273,6 +4274,13 @@ k_small_solve(const u64 *__restrict__ src, i64 stride, const uint32_t *__restric
 	SmallLds &L = *reinterpret_cast<SmallLds *>(TC + (size_t)256 * ws);
 	const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
 	constexpr int NW = NT / 64;
+	// Which branches the passes took (gf2bv_stats.small_passes / small_pass_kinds, out[3]): uniform values, no part of the probe.
+	// npass: passes that ran (at most 64 per panel: each finds a pivot).  kinds: bit 0 / 1 a panel's first pass took the bit loops
+	// (at most 4 new pivots) / the tables, bit 2 / 3 the same for a later pass of a panel, bit 4 a pass that left candidates out
+	// (ncand > 64), bit 5 a pass with fewer than 64.  Functions of the data only for systems built for it (tests/small_cases.py):
+	// which 64 candidates a pass takes, and with them its pivots and every later pass, depends on which wavefront's atomicAdd
+	// arrives first.
+	unsigned npass = 0, kinds = 0;
 	// ---- load: bits above column `cols` (the RHS) are ignored (_internal.c:414) ----
 	const u64 topmask = (((cols + 1) & 63) ? ((1ull << ((cols + 1) & 63)) - 1) : ~0ull);
 	// (four items per thread in flight: offsets of all four first, then their digits -- at most four per word for 30-bit digits --
@@ -4330,6 +4338,7 @@ k_small_solve(const u64 *__restrict__ src, i64 stride, const uint32_t *__restric
 
 	for (int q = 0; q < npan; q++) {
 		const u64 colmask = (cols - 64 * q >= 64) ? ~0ull : ((1ull << (cols - 64 * q)) - 1);
+		unsigned later = 0;                             // 0: the panel's first pass, 2: a later one (the shift of its kind bit)
 		for (;;) {
 			// ---- candidates: rows that are no pivots and have a bit in a pivot-less column of the panel (any 64 of them) ----
 			if (t == 0) { L.ncand = 0; L.newmask = 0; }
@@ -4352,6 +4361,9 @@ k_small_solve(const u64 *__restrict__ src, i64 stride, const uint32_t *__restric
 			SMALL_PROBE(1);
 			if (n == 0) break;                          // (uniform) the panel is complete
 			pt[7]++;
+			npass++;
+			if (L.ncand > 64) kinds |= 16u;
+			if (n < 64) kinds |= 32u;
 			// ---- wavefront 0: the candidates' words of this panel against each other, column by column ----
 			if (wv == 0) {
 				const int r = lane < n ? L.list[lane] : 0;
@@ -4382,7 +4394,10 @@ k_small_solve(const u64 *__restrict__ src, i64 stride, const uint32_t *__restric
 			__syncthreads();
 			SMALL_PROBE(2);
 			const u64 nm = L.newmask;
-			if (__popcll(nm) <= 4) {
+			const bool few = __popcll(nm) <= 4;
+			kinds |= (few ? 1u : 2u) << later;
+			later = 2;
+			if (few) {
 				// ---- a pass that found a handful of pivots (a dense panel's second pass: the one or two columns the first 64
 				// candidates left open): every combination has at most five bits, every row takes at most four pivot rows -- bit
 				// loops on the rows themselves, no tables ----
@@ -4515,7 +4530,7 @@ k_small_solve(const u64 *__restrict__ src, i64 stride, const uint32_t *__restric
 	int *pivcols = reinterpret_cast<int *>(out + 4);
 	u64 *origin = reinterpret_cast<u64 *>(out + 4 + ((cols + 1) & ~1));
 	u64 *Y = origin + cw;
-	if (t == 0) { out[0] = (unsigned)rank; out[1] = (unsigned)L.bad; out[2] = (unsigned)(want_basis && !L.bad ? nfree : 0); out[3] = 0; }
+	if (t == 0) { out[0] = (unsigned)rank; out[1] = (unsigned)L.bad; out[2] = (unsigned)(want_basis && !L.bad ? nfree : 0); out[3] = npass | kinds << 16; }
 	for (int c = t; c < cols; c += NT) {
 		const int q = c >> 6, b = c & 63;
 		if ((L.have[q] >> b) & 1) pivcols[L.base[q] + __popcll(L.have[q] & ((1ull << b) - 1))] = c;

@@ -2326,6 +2326,7 @@ int small_solve(const Knobs &kn, const MatrixInput &in, i64 rows, i64 cols, int 
 	s.rank = rank; s.dimension = R->dim; s.status = R->status;
 	s.n_panels = (int)cw; s.gang_systems = 1; s.tile_words = 0;
 	s.small_path = 1;
+	s.small_passes = (int32_t)(ho[3] & 0xFFFFu); s.small_pass_kinds = (int32_t)(ho[3] >> 16);
 	s.ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
 	*out = R.release();
 	return GF2BV_OK;

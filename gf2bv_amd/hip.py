@@ -84,6 +84,7 @@ class Stats(ctypes.Structure):
         ("general_wide", ctypes.c_int32), ("general_two_level", ctypes.c_int32), ("general_group_adopted", ctypes.c_int32),
         ("general_group_merged", ctypes.c_int32), ("general_gj_kept", ctypes.c_int32), ("general_gj_redone", ctypes.c_int32),
         ("general_chunks", ctypes.c_int32),
+        ("small_passes", ctypes.c_int32), ("small_pass_kinds", ctypes.c_int32),
     ]
 
     def as_dict(self) -> dict:

@@ -119,6 +119,13 @@ typedef struct gf2bv_stats {
 	int32_t general_gj_redone;       /* ... and redid the chunk row-wise                                                                  */
 	int32_t general_chunks;          /* 64-row chunks scanned by the units behind the unit0 / adopted panels' records (a group's adopted
 	                                    member included; merges add nothing)                                                              */
+	/* the one-launch small solve (k_small_solve): which branches its passes took.  Both 0 where small_path is 0.  A pass takes up to 64
+	 * candidate rows of a panel, whichever wavefronts' atomicAdd arrive first, so for random systems both depend on timing; they are
+	 * functions of the data only for systems built so that every arrival order gives the same passes (tests/small_cases.py). */
+	int32_t small_passes;            /* passes that ran, over all panels (a pass that finds no candidate ends its panel and is not counted)   */
+	int32_t small_pass_kinds;        /* bit mask over those passes: 1 a panel's first pass found at most 4 new pivots (bit loops on the rows),
+	                                    2 a panel's first pass found more (nibble tables), 4 / 8 the same for a later pass of a panel,
+	                                    16 a pass saw more than 64 candidates (the rest were left out), 32 a pass saw fewer than 64            */
 } gf2bv_stats;
 
 /* ---- library / device ------------------------------------------------------------------ */

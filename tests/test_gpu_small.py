@@ -72,6 +72,10 @@ def test_one_launch_path_equals_oracle_and_blocked_path(shape, monkeypatch):
             for g in got:
                 assert_same(g, want, mode)
                 assert g.stats["small_path"] == (int(small) if _eligible(rows, cols) else 0), (small, g.stats)
+                if g.stats["small_path"] == 0:
+                    assert g.stats["small_passes"] == 0 and g.stats["small_pass_kinds"] == 0          # the blocked path counts no passes
+                elif g.rank > 0:
+                    assert g.stats["small_passes"] >= 1 and g.stats["small_pass_kinds"] & 15
     assert np.array_equal(buf.download().reshape(wide.shape), wide)          # the input is never modified
     buf.free()
 
@@ -86,7 +90,7 @@ def test_structured_systems_on_the_one_launch_path(kind):
         aug = O.eqs_to_aug(eqs, cols)
         for mode in (0, 1):
             got = hip.solve_words(aug, rows, cols, mode)
-            assert got.stats["small_path"] == 1
+            assert got.stats["small_path"] == 1 and (got.stats["small_passes"] >= 1 or got.rank == 0)
             assert not any(v for k, v in got.stats.items() if k.startswith("general_")), "search_panel never ran: its counters stay 0"
             assert_same(got, O.solve_words(aug, rows, cols, mode), mode)
 
@@ -131,7 +135,7 @@ def test_device_resident_small_system_is_ordered_after_its_producer():
     for seed in range(60):
         hip.synth_device(buf.ptr, rows, cols, stride, 900 + seed)            # asynchronous, null stream
         got = hip.solve_device(buf.ptr, rows, cols, stride, 1)
-        assert got.stats["small_path"] == 1
+        assert got.stats["small_path"] == 1 and got.stats["small_passes"] >= 1
         assert_same(got, O.solve_words(O.gen_synthetic(rows, cols, 900 + seed), rows, cols, 1), 1)
     buf.free()
 
