@@ -1906,6 +1906,68 @@ PyObject *py_space_from_ints(PyObject *, PyObject *const *args, Py_ssize_t nargs
 	return (PyObject *)sp;
 }
 
+// m4ri_compose_packed(a, ra, n, b, nb[, device]) -> bytearray: the forms `a` (ra x ceil((n + 1) / 64) 64-bit words, m4ri_solve_packed's
+// bit order) with the images `b` (n x ceil((nb + 1) / 64) words: row g replaces unknown g) substituted on the device
+// (gf2bv_compose_words); the result is ra x ceil((nb + 1) / 64) words.  New entry, no counterpart in the reference.
+// m4ri_power_packed(b, n, k[, device]) -> bytearray: the self-map `b` (n x ceil((n + 1) / 64) words) substituted into itself k times by
+// square-and-multiply on the device (gf2bv_compose_power_words); k a buffer of little-endian 64-bit words, at least one.
+bool packed_forms(HeldBuffer &hb, PyObject *buf, Py_ssize_t rows, Py_ssize_t unknowns, const char *what)
+{
+	if (!hb.take(buf, PyBUF_C_CONTIGUOUS)) return false;
+	if (rows < 0 || unknowns < 1 || unknowns >= PY_SSIZE_T_MAX / 16 || hb.view.len != rows * ((unknowns + 64) / 64) * 8) {
+		PyErr_Format(PyExc_ValueError, "%s must hold rows x ceil((unknowns + 1) / 64) 64-bit words", what);
+		return false;
+	}
+	return true;
+}
+
+template <class F>
+PyObject *composed_rows(const char *what, Py_ssize_t rows, Py_ssize_t words, F &&call)
+{
+	PyObject *out = PyByteArray_FromStringAndSize(nullptr, rows * words * 8);
+	if (!out) return nullptr;
+	uint64_t *dst = reinterpret_cast<uint64_t *>(PyByteArray_AS_STRING(out));
+	int rc;
+	std::string msg;
+	Py_BEGIN_ALLOW_THREADS
+	rc = call(dst);
+	if (rc) msg = gf2bv_last_error();
+	Py_END_ALLOW_THREADS
+	if (rc) { Py_DECREF(out); return raise_rc(rc, what, msg.c_str()); }
+	return out;
+}
+
+PyObject *py_m4ri_compose_packed(PyObject *, PyObject *const *args, Py_ssize_t nargs)
+{
+	int device;
+	if (!entry_device("m4ri_compose_packed", 5, args, nargs, &device)) return nullptr;
+	const Py_ssize_t ra = PyLong_AsSsize_t(args[1]), n = PyLong_AsSsize_t(args[2]), nb = PyLong_AsSsize_t(args[4]);
+	if (PyErr_Occurred()) return nullptr;
+	HeldBuffer a, b;
+	if (!packed_forms(a, args[0], ra, n, "a") || !packed_forms(b, args[3], n, nb, "b")) return nullptr;
+	const Py_ssize_t wa = (n + 64) / 64, wb = (nb + 64) / 64;
+	static const uint64_t none = 0;               // (no rows: the library still wants a pointer)
+	return composed_rows("composition", ra, wb, [&](uint64_t *dst) {
+		return gf2bv_compose_words(ra ? static_cast<const uint64_t *>(a.view.buf) : &none, ra, wa, n, static_cast<const uint64_t *>(b.view.buf), wb, nb,
+		                           ra ? dst : const_cast<uint64_t *>(&none), wb, device);
+	});
+}
+
+PyObject *py_m4ri_power_packed(PyObject *, PyObject *const *args, Py_ssize_t nargs)
+{
+	int device;
+	if (!entry_device("m4ri_power_packed", 3, args, nargs, &device)) return nullptr;
+	const Py_ssize_t n = PyLong_AsSsize_t(args[1]);
+	if (PyErr_Occurred()) return nullptr;
+	HeldBuffer b, k;
+	if (!packed_forms(b, args[0], n, n, "b") || !k.take(args[2], PyBUF_C_CONTIGUOUS)) return nullptr;
+	if (k.view.len < 8 || k.view.len % 8) { PyErr_SetString(PyExc_ValueError, "k must hold at least one 64-bit word"); return nullptr; }
+	const Py_ssize_t w = (n + 64) / 64;
+	return composed_rows("power", n, w, [&](uint64_t *dst) {
+		return gf2bv_compose_power_words(static_cast<const uint64_t *>(b.view.buf), w, n, static_cast<const uint64_t *>(k.view.buf), k.view.len / 8, dst, w, device);
+	});
+}
+
 PyObject *py_device_count(PyObject *, PyObject *) { return PyLong_FromLong(gf2bv_device_count()); }
 PyObject *py_get_default_device(PyObject *, PyObject *) { return PyLong_FromLong(default_device()); }
 PyObject *py_set_default_device(PyObject *, PyObject *arg)
@@ -1930,6 +1992,10 @@ PyMethodDef module_methods[] = {
 	 "m4ri_solve(equations, cols, mode, device=None)\n--\n\nSolve the linear system on the MI355X; None when inconsistent."},
 	{"m4ri_solve_packed", FAST(py_m4ri_solve_packed), METH_FASTCALL,
 	 "m4ri_solve_packed(buffer, rows, words, cols, mode, device=None)\n--\n\nm4ri_solve on equations already packed as rows x words 64-bit words (equation-int bit order)."},
+	{"m4ri_compose_packed", FAST(py_m4ri_compose_packed), METH_FASTCALL,
+	 "m4ri_compose_packed(a, ra, n, b, nb, device=None)\n--\n\nThe packed forms a (ra rows over n unknowns) with the packed images b (n rows over nb unknowns) substituted on the GPU: a bytearray of ra x ceil((nb + 1) / 64) 64-bit words."},
+	{"m4ri_power_packed", FAST(py_m4ri_power_packed), METH_FASTCALL,
+	 "m4ri_power_packed(b, n, k, device=None)\n--\n\nThe packed self-map b (n rows over n unknowns) substituted into itself k times (k: little-endian 64-bit words) by square-and-multiply on the GPU: a bytearray of n x ceil((n + 1) / 64) words."},
 	{"m4ri_solve_quad_packed", FAST(py_m4ri_solve_quad_packed), METH_FASTCALL,
 	 "m4ri_solve_quad_packed(lin, term_off, ta, tb, n_lin, rows, mode, device=None)\n--\n\nm4ri_solve on a quadratic system kept factored (linear forms and products of two linear forms, packed 64-bit words): expanded into the linearised matrix on the GPU."},
 	{"m4ri_solve_xl3", FAST(py_m4ri_solve_xl<3>), METH_FASTCALL,

@@ -6201,3 +6201,222 @@ k_quartic_search(const u64 *__restrict__ tab, int R, int L, u64 nlanes, u64 *__r
 		}
 	}
 }
+
+
+// ==========================================================================================
+// COMPOSITION: substitute affine maps into affine forms, C = A x B~ over GF(2)
+// ==========================================================================================
+// Forms A: ra rows over n unknowns in the equation-int order (bit 0 = constant, bit 1 + g = unknown g).  Images B: n rows over nb
+// unknowns, row g = the form that replaces unknown g.  B~ = B with the unit form (bit 0 alone) in front as row 0, so bit k of an A row
+// selects row k of B~ and the constant is no special case:  C[r] = XOR over the set bits k of A[r] of B~[k].  The unit row is never
+// read from memory: the table build writes it.
+//
+// k_update16's nearest relative -- the same tables, turned round: there a workgroup streams rows through HBM and the tables change per
+// block; here the ROWS stay (their 16-byte C segments are accumulators in registers, GF2_CMP_RPL rows per lane) and the TABLES
+// stream past them.  C is cut into 16-byte column tiles and A's bits into slices of GF2_CMP_S = 256; for its tile and one slice a
+// workgroup builds 32 byte tables of 256 entries x 16 B (128 KiB) from the 256 rows of B~ (zero rows past n: a K tail leaves tables
+// whose entries repeat), and every lane XORs 32 ds_read_b128 lookups per row into that row's accumulator.  The slice loop is the
+// outer loop; C is written ONCE at the end with plain 16-byte stores -- a read-XOR-write of C per slice would put n / 256 round trips
+// of C through HBM where this has one store, and needs neither atomics nor an order between workgroups: every C segment has exactly
+// one writer whatever the grid, so the result is the same bits for every grid.
+//
+// LDS layout (k_update16's): two pages of 16 tables = the slice's two 128-bit halves; slot `idx` of a page = 256 B = [entry idx of
+// table 0 | ... | table 15] = all 64 banks once; table t = byte t of the half.  ds_read_b128 is serviced 16 lanes at a time, and each
+// of its four lane groups holds 16 different rq = lane & 15 (consecutive lanes = consecutive rows); at step s = 8 s_hi + s_lo of a
+// page a row reads table 8 (s_hi ^ rq_hi) + ((s_lo + rq_lo) & 7), rq_lo = rq & 7, rq_hi = rq >> 3: a bijection of rq for every s, so
+// the 16 lanes of a group read 16 different 16-byte slots of one 256-byte bank row -- conflict-free by layout.  The bulk update gets
+// its multipliers stored in that order; here A is the caller's, so a lane swaps the two words of a half by rq_hi and rotates them by
+// 8 rq_lo bits once per row and slice (a handful of VALU operations against 32 lookups), and the lookup address is one v_perm_b32.
+//
+// A's 32 bytes per row and slice are requested a whole slice AHEAD, and B~'s rows too: what bounds the kernel is the A operand -- a
+// quarter of a cache line per lane, 64 lines per wavefront load -- and not the tables (at 19968 square: 5.07 ms with A requested at
+// the top of its slice, 2.82 ms with A made up in registers, 4.53 ms as it stands).  Bits
+// of A above n and of B above nb are masked where they are read.  An odd word count of C leaves a half tile: its second word is a
+// table of zeros and is stored as zero (the stride is even, so the word exists).  The workgroups of tile 0 also zero the words of
+// their rows between the last tile and the stride.
+// Grid: one line of (column tiles) x (row groups of GF2_CMP_NT x GF2_CMP_RPL = 4096 rows), tiles fastest: neighbours in the line
+// share their A rows.  MT19937's twist map (19969 bits square): 157 x 5 = 785 workgroups on 256 CUs; small shapes are one workgroup.
+#define GF2_CMP_S 256                  /* bits of A per slice: 32 byte tables */
+#define GF2_CMP_NT 512                 /* threads: 2 waves per SIMD at up to 256 VGPRs */
+#define GF2_CMP_RPL 8                  /* rows per lane: 8 x 4 accumulator registers, 8 x 8 registers of A in flight over a table build */
+#define GF2_CMP_RG (GF2_CMP_NT * GF2_CMP_RPL)
+#define GF2_CMP_LDS (2 * 256 * 16 * 16 + 256 * 16)      /* tables + the staged rows of B~ */
+
+// the bits of word w that lie below `bits`
+__host__ __device__ __forceinline__ u64 cmp_word_mask(i64 w, i64 bits)
+{
+	const i64 live = bits - 64 * w;
+	return live <= 0 ? 0ull : live >= 64 ? ~0ull : (1ull << live) - 1;
+}
+
+__global__ void __launch_bounds__(GF2_CMP_NT)
+k_compose(const u64 *__restrict__ A, i64 ra, i64 a_stride, i64 n, const u64 *__restrict__ B, i64 b_stride, i64 nb,
+          u64 *__restrict__ C, i64 c_stride, i64 tiles)
+{
+	constexpr int NT = GF2_CMP_NT, RPL = GF2_CMP_RPL;
+	__shared__ __attribute__((aligned(256))) uint4 tab[2 * 256 * 16];      // 128 KiB: [page][entry][table]
+	__shared__ uint4 stage[256];                    // the tile's segment of the slice's 256 rows of B~
+	const int tid = threadIdx.x, lane = tid & 63;
+	const i64 tile = (i64)blockIdx.x % tiles;
+	const i64 row0 = (i64)blockIdx.x / tiles * GF2_CMP_RG;
+	const i64 wa = (n + 1 + 63) >> 6, wb = (nb + 1 + 63) >> 6;
+	const i64 nslices = (n + 1 + GF2_CMP_S - 1) / GF2_CMP_S;
+	const unsigned tab_at = (unsigned)(size_t)tab;      // (0 where the compiler puts the tables first: the add below folds away)
+	const u64 bm0 = 2 * tile < wb ? cmp_word_mask(2 * tile, nb + 1) : 0, bm1 = 2 * tile + 1 < wb ? cmp_word_mask(2 * tile + 1, nb + 1) : 0;
+
+	// lane constants: byte s % 3 of KC[s / 3] = 16 * (table read at step s), byte 3 = 1 (the page bit of page 1)
+	const int rq_lo = lane & 7, rq_hi = (lane >> 3) & 1;
+	unsigned KC[6];
+#pragma unroll
+	for (int v = 0; v < 6; v++) {
+		unsigned k = 1u << 24;
+#pragma unroll
+		for (int b = 0; b < 3; b++) {
+			const int s = 3 * v + b;
+			if (s < 16) k |= (unsigned)(16 * (8 * ((s >> 3) ^ rq_hi) + (((s & 7) + rq_lo) & 7))) << (8 * b);
+		}
+		KC[v] = k;
+	}
+
+	uint4 acc[RPL];
+#pragma unroll
+	for (int j = 0; j < RPL; j++) acc[j] = make_uint4(0, 0, 0, 0);
+
+	// this thread's row of B~ in slice s, the tile's two words of it (threads 0 .. 255)
+	u64 bw0 = 0, bw1 = 0;
+	auto load_b = [&](i64 s) {
+		const i64 k = s * GF2_CMP_S + tid;          // row of B~: 0 the unit form, k the image of unknown k - 1, none past n
+		bw0 = 0; bw1 = 0;
+		if (tid >= 256) return;
+		if (k == 0) bw0 = tile == 0 ? 1 : 0;
+		else if (k <= n) {
+			const u64 *br = B + (k - 1) * b_stride;
+			if (bm0) bw0 = br[2 * tile] & bm0;
+			if (bm1) bw1 = br[2 * tile + 1] & bm1;
+		}
+	};
+	load_b(0);
+
+	// A slice's 32 bytes of a row of this lane.  A lane's 32 bytes are a quarter of a cache line and every lane of a wavefront is in
+	// another line: these loads are the slowest thing the kernel does.  So they are requested a whole slice ahead -- row j's as soon as
+	// row j's fields of the current slice have been formed -- and travel under the rest of that slice's lookups and the next build.
+	uint4 ar[RPL][2];
+	auto load_a = [&](int j, i64 s) {
+		// no control flow around the loads: a row past the end re-reads the last row (never stored), a word pair past the last word
+		// re-reads pair 0 (masked to nothing where the fields are formed).  w is even and below wa <= the even stride: the pair lies
+		// inside the row
+		i64 row = row0 + (i64)j * NT + tid;
+		row = row < ra ? row : ra - 1;
+#pragma unroll
+		for (int p = 0; p < 2; p++) {
+			const i64 w = 4 * s + 2 * p;
+			ar[j][p] = *reinterpret_cast<const uint4 *>(A + row * a_stride + (w < wa ? w : 0));
+		}
+	};
+#pragma unroll
+	for (int j = 0; j < RPL; j++) load_a(j, 0);
+
+	for (i64 s = 0; s < nslices; s++) {
+		if (s) __syncthreads();                     // the previous slice's lookups are done with the tables
+		// ---- tables ----
+		if (tid < 256) stage[tid] = make_uint4((unsigned)bw0, (unsigned)(bw0 >> 32), (unsigned)bw1, (unsigned)(bw1 >> 32));
+		__syncthreads();
+		if (s + 1 < nslices) load_b(s + 1);         // the next slice's rows of B~ travel under this slice's build and lookups
+		// pass 0: the entries whose index has bits in one nibble only, straight from the staged rows (<= 4 of them)
+		for (int it = tid; it < 2 * 31 * 16; it += NT) {
+			const int sub = it & 15, e = (it >> 4) % 31, grp = (it >> 4) / 31;
+			const int idx = e <= 15 ? e : (e - 15) << 4;
+			const uint4 *st = stage + 128 * grp + 8 * sub;
+			uint4 a = make_uint4(0, 0, 0, 0);
+			int bits = idx;
+			while (bits) {
+				const int l = __ffs(bits) - 1; bits &= bits - 1;
+				a = xor4(a, st[l]);
+			}
+			tab[grp * 4096 + idx * 16 + sub] = a;
+		}
+		__syncthreads();
+		// pass 1: the mixed ones = low-nibble entry ^ high-nibble entry
+		for (int it = tid; it < 2 * 225 * 16; it += NT) {
+			const int sub = it & 15, k = (it >> 4) % 225, grp = (it >> 4) / 225;
+			const int lo = 1 + k % 15, hi = (1 + k / 15) << 4;
+			uint4 *tb = tab + grp * 4096 + sub;
+			tb[(lo | hi) * 16] = xor4(tb[lo * 16], tb[hi * 16]);
+		}
+		__syncthreads();
+
+		// ---- lookups ----
+		// the live bits of the slice's four words (uniform); per row the lookup fields: the words of a half swapped by rq_hi and rotated
+		// by rq_lo bytes -- and, its 32 bytes used up, the row's request for the next slice
+		u64 am[4];
+#pragma unroll
+		for (int q = 0; q < 4; q++) am[q] = cmp_word_mask(4 * s + q, n + 1);
+		auto fields = [&](unsigned *m, int j) {
+#pragma unroll
+			for (int p = 0; p < 2; p++) {
+				const u64 a0 = (((u64)ar[j][p].y << 32) | ar[j][p].x) & am[2 * p], a1 = (((u64)ar[j][p].w << 32) | ar[j][p].z) & am[2 * p + 1];
+				const u64 u0 = mult_rot(rq_hi ? a1 : a0, rq_lo), u1 = mult_rot(rq_hi ? a0 : a1, rq_lo);
+				m[4 * p + 0] = (unsigned)u0; m[4 * p + 1] = (unsigned)(u0 >> 32);
+				m[4 * p + 2] = (unsigned)u1; m[4 * p + 3] = (unsigned)(u1 >> 32);
+			}
+			load_a(j, s + 1);
+		};
+		// round r = 0..3 of a row: the 8 lookups of (page r >> 1, word r & 1)
+		auto issue = [&](u32x4 *v, const unsigned *m, int r) {
+			const int grp = r >> 1, hf = r & 1;
+#pragma unroll
+			for (int k = 0; k < 8; k++) {
+				const int st = 8 * hf + k;
+				// {byte 0: lane constant of step st, byte 1: the field, byte 2: page, byte 3: 0} in one v_perm_b32
+				// (selector codes 0-3 = bytes of the second source, 4-7 = bytes of the first, 12 = 0x00)
+				const unsigned sel = (unsigned)(st % 3) | ((4u + (unsigned)(k & 3)) << 8) | ((grp ? 3u : 12u) << 16) | (12u << 24);
+				const unsigned at = __builtin_amdgcn_perm(m[2 * (2 * grp + hf) + (k >> 2)], KC[st / 3], sel) + tab_at;
+				v[k] = *(lds_u4_ptr)(size_t)at;
+			}
+		};
+		auto fold = [&](uint4 &a, const u32x4 *v) {
+#pragma unroll
+			for (int h = 0; h < 4; h++) {
+				a.x = __builtin_amdgcn_bitop3_b32(a.x, v[2 * h].x, v[2 * h + 1].x, 0x96);
+				a.y = __builtin_amdgcn_bitop3_b32(a.y, v[2 * h].y, v[2 * h + 1].y, 0x96);
+				a.z = __builtin_amdgcn_bitop3_b32(a.z, v[2 * h].z, v[2 * h + 1].z, 0x96);
+				a.w = __builtin_amdgcn_bitop3_b32(a.w, v[2 * h].w, v[2 * h + 1].w, 0x96);
+			}
+		};
+		// the lookups of round r + 1 -- also across the row boundary -- are issued before the XORs of round r
+		u32x4 va[8], vb[8];
+		unsigned mw[2][8];
+		fields(mw[0], 0);
+		issue(va, mw[0], 0);
+#pragma unroll
+		for (int j = 0; j < RPL; j++) {
+			const unsigned *m = mw[j & 1];
+			issue(vb, m, 1); fold(acc[j], va);
+			issue(va, m, 2); fold(acc[j], vb);
+			issue(vb, m, 3); fold(acc[j], va);
+			if (j + 1 < RPL) { fields(mw[(j + 1) & 1], j + 1); issue(va, mw[(j + 1) & 1], 0); }
+			fold(acc[j], vb);
+		}
+	}
+
+	// ---- C, once ----
+#pragma unroll
+	for (int j = 0; j < RPL; j++) {
+		const i64 row = row0 + (i64)j * NT + tid;
+		if (row >= ra) continue;
+		u64 *cr = C + row * c_stride;
+		*reinterpret_cast<uint4 *>(cr + 2 * tile) = acc[j];
+		if (tile == 0)
+			for (i64 w = 2 * tiles; w < c_stride; w += 2) *reinterpret_cast<uint4 *>(cr + w) = make_uint4(0, 0, 0, 0);
+	}
+}
+
+// rows first .. first + rows - 1 of the identity map's B~ (row k = bit k alone), `stride` words apart
+__global__ void k_compose_identity(u64 *__restrict__ out, i64 rows, i64 stride, i64 first)
+{
+	const i64 total = rows * stride;
+	for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (i64)gridDim.x * blockDim.x) {
+		const i64 bit = first + i / stride, w = i % stride;
+		out[i] = (bit >> 6) == w ? 1ull << (bit & 63) : 0ull;
+	}
+}

@@ -6489,3 +6489,257 @@ int gf2bv_xl4_cubic_guess_chunk_device(int64_t m, int64_t n_lin, int64_t nguess,
 int64_t gf2bv_xl4_quartic_root(int64_t u) { return u < 0 ? -1 : xl_quart_root(u); }
 
 }  // extern "C"
+
+// ---- composition: affine maps substituted into affine forms, and powers of a self-map (k_compose) -------------------------------
+namespace {
+
+struct ComposeTimes { double upload = 0, kernels = 0, download = 0; i64 products = 0; };
+thread_local ComposeTimes g_compose_times;
+
+inline i64 form_words(i64 unknowns) { return (unknowns + 1 + 63) / 64; }
+
+// ra forms over n unknowns into images over nb unknowns: the rules every entry shares; no pointer is looked at
+int check_compose(i64 ra, i64 n, i64 nb)
+{
+	if (ra < 0) return fail(GF2BV_ERR_ARG, "ra must not be negative");
+	if (n < 1 || nb < 1) return fail(GF2BV_ERR_ARG, "n and nb must be at least 1");
+	if (n + 1 >= (1ll << 31) - 64 || nb + 1 >= (1ll << 31) - 64) return fail(GF2BV_ERR_ARG, "n + 1 and nb + 1 must stay below 2^31 - 64");
+	const i64 tiles = (form_words(nb) + GF2_TW - 1) / GF2_TW, groups = (std::max<i64>(ra, 1) + GF2_CMP_RG - 1) / GF2_CMP_RG;
+	if (tiles * groups >= (1ll << 31)) return fail(GF2BV_ERR_ARG, "column tiles x row groups of the product must stay below 2^31");
+	return GF2BV_OK;
+}
+
+// a device matrix of the device entries: 16-byte aligned, an even stride that covers the width
+int check_device_rows(const void *p, i64 stride, i64 width, const char *what)
+{
+	if (stride % 2 != 0 || stride < width || ((uintptr_t)p & 15)) return fail(GF2BV_ERR_ARG, what);
+	return GF2BV_OK;
+}
+
+// (device pointers, already checked) one product on `st`: d_b is the n image rows, the kernel supplies the unit row
+int enqueue_compose(const u64 *d_a, i64 ra, i64 a_stride, i64 n, const u64 *d_b, i64 b_stride, i64 nb, u64 *d_out, i64 out_stride, hipStream_t st)
+{
+	if (ra == 0) return GF2BV_OK;
+	const i64 tiles = (form_words(nb) + GF2_TW - 1) / GF2_TW, groups = (ra + GF2_CMP_RG - 1) / GF2_CMP_RG;
+	hipLaunchKernelGGL(k_compose, dim3((unsigned)(tiles * groups)), dim3(GF2_CMP_NT), 0, st, d_a, ra, a_stride, n, d_b, b_stride, nb, d_out,
+	                   out_stride, tiles);
+	HIPCHK(hipGetLastError());
+	g_compose_times.products++;
+	return GF2BV_OK;
+}
+
+int enqueue_identity(u64 *d_out, i64 rows, i64 stride, i64 first, hipStream_t st)
+{
+	const unsigned blocks = (unsigned)std::min<i64>((rows * stride + 255) / 256, 4096);
+	hipLaunchKernelGGL(k_compose_identity, dim3(blocks), dim3(256), 0, st, d_out, rows, stride, first);
+	HIPCHK(hipGetLastError());
+	return GF2BV_OK;
+}
+
+// The buffers and the stream of an entry that stages: a refused buffer is GF2BV_ERR_NOMEM, and on every return path the stream is
+// synchronised before a buffer goes back to the pool (Scratch) and goes back itself after that (PoolStream: declared first)
+struct ComposeStage {
+	PoolStream ps;
+	Scratch scratch;
+	hipStream_t st = nullptr;          // the pool's stream, or the caller's
+	hipEvent_t ev[4] = {};
+	int open(int device, hipStream_t given, bool own)
+	{
+		ps.device = device;
+		if (own) { HIPCHK(pool().stream(&ps.st, device, 0)); st = ps.st; }
+		else st = given;
+		scratch.sync_first = st;
+		for (hipEvent_t &e : ev) HIPCHK(scratch.event(&e));
+		return GF2BV_OK;
+	}
+	int alloc(u64 **out, i64 words)
+	{
+		const hipError_t e = scratch.alloc((void **)out, sizeof(u64) * (size_t)words, ps.device);
+		if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(GF2BV_ERR_NOMEM, "the forms, the images or the product do not fit on the device"); }
+		if (e != hipSuccess) return fail(GF2BV_ERR_HIP, "composition buffers", e);
+		return GF2BV_OK;
+	}
+	int mark(int i) { HIPCHK(hipEventRecord(ev[i], st)); return GF2BV_OK; }
+	// after the stream has been synchronised: the times between the four marks
+	int times()
+	{
+		float up = 0, ke = 0, dn = 0;
+		HIPCHK(hipEventElapsedTime(&up, ev[0], ev[1]));
+		HIPCHK(hipEventElapsedTime(&ke, ev[1], ev[2]));
+		HIPCHK(hipEventElapsedTime(&dn, ev[2], ev[3]));
+		g_compose_times.upload = up; g_compose_times.kernels = ke; g_compose_times.download = dn;
+		return GF2BV_OK;
+	}
+};
+
+// host rows `stride` words apart <-> device rows `ds` words apart, `width` words of each
+int copy_rows(void *dst, i64 dst_stride, const void *src, i64 src_stride, i64 width, i64 rows, hipMemcpyKind kind, hipStream_t st)
+{
+	if (rows == 0) return GF2BV_OK;
+	HIPCHK(hipMemcpy2DAsync(dst, (size_t)dst_stride * 8, src, (size_t)src_stride * 8, (size_t)width * 8, (size_t)rows, kind, st));
+	return GF2BV_OK;
+}
+
+// Square-and-multiply on the device, most significant bit first.  d_base: the n image rows of the map, bs words apart.  cur, tmp:
+// (n + 1) x ws words each, B~ of the running power with its unit row (the products write it: the unit row of A selects the unit row).
+// The running power starts as the identity; a set bit multiplies by the base (the first one: identity o base, which also drops the
+// base's bits above n), every later bit squares first: bit_length - 1 + popcount products, none for k = 0.  The LAST product writes
+// rows 1 .. n straight to d_out (os words apart); k = 0 writes the identity's there.  d_out null: the result stays in the buffer the
+// last product does not read, rows ws words apart, and *where says where.
+int enqueue_power(const u64 *d_base, i64 bs, i64 n, const uint64_t *k, i64 knw, u64 *cur, u64 *tmp, i64 ws, u64 *d_out, i64 os, hipStream_t st,
+                  const u64 **where = nullptr)
+{
+	i64 top = -1, pop = 0;
+	for (i64 i = 0; i < 64 * knw; i++)
+		if ((k[i >> 6] >> (i & 63)) & 1) { top = i; pop++; }
+	i64 left = top < 0 ? 0 : top + pop;
+	const bool stay = !d_out;
+	if (stay) { d_out = tmp + ws; os = ws; }
+	if (where) *where = d_out;
+	if (left == 0) return enqueue_identity(d_out, n, os, 1, st);
+	int rc = enqueue_identity(cur, n + 1, ws, 0, st);
+	auto product = [&](const u64 *b, i64 b_stride) {
+		if (rc) return;
+		if (--left == 0) {
+			if (stay) d_out = tmp + ws;
+			if (where) *where = d_out;
+			rc = enqueue_compose(cur + ws, n, ws, n, b, b_stride, n, d_out, os, st);
+		}
+		else { rc = enqueue_compose(cur, n + 1, ws, n, b, b_stride, n, tmp, ws, st); std::swap(cur, tmp); }
+	};
+	for (i64 i = top; i >= 0; i--) {
+		if (i < top) product(cur + ws, ws);
+		if ((k[i >> 6] >> (i & 63)) & 1) product(d_base, bs);
+	}
+	return rc;
+}
+
+int check_power(const void *b, i64 b_stride, i64 n, const uint64_t *k, i64 knw, const void *out, i64 out_stride)
+{
+	if (!b || !k || !out) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (knw < 1) return fail(GF2BV_ERR_ARG, "k_nwords must be at least 1");
+	if (int rc = check_compose(n + 1, n, n)) return rc;
+	if (b_stride < form_words(n) || out_stride < form_words(n)) return fail(GF2BV_ERR_ARG, "a stride does not cover n + 1 bits");
+	return GF2BV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gf2bv_compose_shape(int32_t out[4])
+{
+	if (!out) return fail(GF2BV_ERR_ARG, "null pointer");
+	out[0] = GF2_CMP_S; out[1] = GF2_CMP_RG; out[2] = GF2_TW; out[3] = GF2_CMP_LDS;
+	return GF2BV_OK;
+}
+
+void gf2bv_compose_last_times(double ms[4])
+{
+	const ComposeTimes &t = g_compose_times;
+	ms[0] = t.upload; ms[1] = t.kernels; ms[2] = t.download; ms[3] = (double)t.products;
+}
+
+int gf2bv_compose_device(const void *d_a, int64_t ra, int64_t a_stride, int64_t n, const void *d_b, int64_t b_stride, int64_t nb,
+                         void *d_out, int64_t out_stride, int device, void *stream)
+{
+	return catching([&]() -> int {
+	if (!d_a || !d_b || !d_out) return fail(GF2BV_ERR_ARG, "null pointer");
+	int rc = check_compose(ra, n, nb);
+	if (!rc) rc = check_device_rows(d_a, a_stride, form_words(n), "d_a needs 16-byte alignment and an even a_stride covering n + 1 bits");
+	if (!rc) rc = check_device_rows(d_b, b_stride, form_words(nb), "d_b needs 16-byte alignment and an even b_stride covering nb + 1 bits");
+	if (!rc) rc = check_device_rows(d_out, out_stride, form_words(nb), "d_out needs 16-byte alignment and an even out_stride covering nb + 1 bits");
+	if (!rc) rc = check_device(device);
+	if (rc) return rc;
+	g_compose_times = ComposeTimes();
+	return enqueue_compose((const u64 *)d_a, ra, a_stride, n, (const u64 *)d_b, b_stride, nb, (u64 *)d_out, out_stride, (hipStream_t)stream);
+	});
+}
+
+int gf2bv_compose_words(const uint64_t *a, int64_t ra, int64_t a_stride, int64_t n, const uint64_t *b, int64_t b_stride, int64_t nb,
+                        uint64_t *out, int64_t out_stride, int device)
+{
+	return catching([&]() -> int {
+	if (!a || !b || !out) return fail(GF2BV_ERR_ARG, "null pointer");
+	int rc = check_compose(ra, n, nb);
+	if (rc) return rc;
+	const i64 wa = form_words(n), wb = form_words(nb);
+	if (a_stride < wa) return fail(GF2BV_ERR_ARG, "a_stride does not cover n + 1 bits");
+	if (b_stride < wb || out_stride < wb) return fail(GF2BV_ERR_ARG, "b_stride or out_stride does not cover nb + 1 bits");
+	if ((rc = check_device(device))) return rc;
+	g_compose_times = ComposeTimes();
+	if (ra == 0) return GF2BV_OK;
+	const i64 das = round_up(wa, 2), dbs = round_up(wb, 2);
+	ComposeStage sg;
+	u64 *d_a = nullptr, *d_b = nullptr, *d_out = nullptr;
+	if ((rc = sg.open(device, nullptr, true))) return rc;
+	if ((rc = sg.alloc(&d_a, ra * das)) || (rc = sg.alloc(&d_b, n * dbs)) || (rc = sg.alloc(&d_out, ra * dbs))) return rc;
+	if ((rc = sg.mark(0))) return rc;
+	if ((rc = copy_rows(d_a, das, a, a_stride, wa, ra, hipMemcpyHostToDevice, sg.st))) return rc;
+	if ((rc = copy_rows(d_b, dbs, b, b_stride, wb, n, hipMemcpyHostToDevice, sg.st))) return rc;
+	if ((rc = sg.mark(1))) return rc;
+	if ((rc = enqueue_compose(d_a, ra, das, n, d_b, dbs, nb, d_out, dbs, sg.st))) return rc;
+	if ((rc = sg.mark(2))) return rc;
+	if ((rc = copy_rows(out, out_stride, d_out, dbs, wb, ra, hipMemcpyDeviceToHost, sg.st))) return rc;
+	if ((rc = sg.mark(3))) return rc;
+	HIPCHK(hipStreamSynchronize(sg.st));
+	if (out_stride > wb)
+		for (i64 r = 0; r < ra; r++) memset(out + r * out_stride + wb, 0, sizeof(u64) * (size_t)(out_stride - wb));
+	return sg.times();
+	});
+}
+
+int gf2bv_compose_power_device(const void *d_b, int64_t b_stride, int64_t n, const uint64_t *k_words, int64_t k_nwords, void *d_out,
+                               int64_t out_stride, int device, void *stream)
+{
+	return catching([&]() -> int {
+	int rc = check_power(d_b, b_stride, n, k_words, k_nwords, d_out, out_stride);
+	if (!rc) rc = check_device_rows(d_b, b_stride, form_words(n), "d_b needs 16-byte alignment and an even b_stride covering n + 1 bits");
+	if (!rc) rc = check_device_rows(d_out, out_stride, form_words(n), "d_out needs 16-byte alignment and an even out_stride covering n + 1 bits");
+	if (!rc) rc = check_device(device);
+	if (rc) return rc;
+	g_compose_times = ComposeTimes();
+	const i64 ws = round_up(form_words(n), 2);
+	ComposeStage sg;
+	u64 *base = nullptr, *cur = nullptr, *tmp = nullptr;
+	if ((rc = sg.open(device, (hipStream_t)stream, false))) return rc;
+	if ((rc = sg.alloc(&base, (n + 1) * ws)) || (rc = sg.alloc(&cur, (n + 1) * ws)) || (rc = sg.alloc(&tmp, (n + 1) * ws))) return rc;
+	for (int i = 0; i < 2; i++) if ((rc = sg.mark(i))) return rc;
+	// (the map is copied: d_out may be d_b, and the caller's rows are not read after the copy)
+	if ((rc = copy_rows(base + ws, ws, d_b, b_stride, form_words(n), n, hipMemcpyDeviceToDevice, sg.st))) return rc;
+	if ((rc = enqueue_power(base + ws, ws, n, k_words, k_nwords, cur, tmp, ws, (u64 *)d_out, out_stride, sg.st))) return rc;
+	for (int i = 2; i < 4; i++) if ((rc = sg.mark(i))) return rc;
+	HIPCHK(hipStreamSynchronize(sg.st));           // the three buffers go back to the pool: the host waits
+	return sg.times();
+	});
+}
+
+int gf2bv_compose_power_words(const uint64_t *b, int64_t b_stride, int64_t n, const uint64_t *k_words, int64_t k_nwords, uint64_t *out,
+                              int64_t out_stride, int device)
+{
+	return catching([&]() -> int {
+	int rc = check_power(b, b_stride, n, k_words, k_nwords, out, out_stride);
+	if (!rc) rc = check_device(device);
+	if (rc) return rc;
+	g_compose_times = ComposeTimes();
+	const i64 w = form_words(n), ws = round_up(w, 2);
+	ComposeStage sg;
+	u64 *base = nullptr, *cur = nullptr, *tmp = nullptr;
+	const u64 *d_out = nullptr;
+	if ((rc = sg.open(device, nullptr, true))) return rc;
+	if ((rc = sg.alloc(&base, (n + 1) * ws)) || (rc = sg.alloc(&cur, (n + 1) * ws)) || (rc = sg.alloc(&tmp, (n + 1) * ws))) return rc;
+	if ((rc = sg.mark(0))) return rc;
+	if ((rc = copy_rows(base + ws, ws, b, b_stride, w, n, hipMemcpyHostToDevice, sg.st))) return rc;
+	if ((rc = sg.mark(1))) return rc;
+	if ((rc = enqueue_power(base + ws, ws, n, k_words, k_nwords, cur, tmp, ws, nullptr, 0, sg.st, &d_out))) return rc;
+	if ((rc = sg.mark(2))) return rc;
+	if ((rc = copy_rows(out, out_stride, d_out, ws, w, n, hipMemcpyDeviceToHost, sg.st))) return rc;
+	if ((rc = sg.mark(3))) return rc;
+	HIPCHK(hipStreamSynchronize(sg.st));
+	if (out_stride > w)
+		for (i64 r = 0; r < n; r++) memset(out + r * out_stride + w, 0, sizeof(u64) * (size_t)(out_stride - w));
+	return sg.times();
+	});
+}
+
+}  // extern "C"

@@ -56,6 +56,8 @@ EXPORTS = [
     "gf2bv_slab_payload_bytes", "gf2bv_slab_factor", "gf2bv_slab_apply", "gf2bv_slab_factor_on", "gf2bv_slab_apply_on",
     "gf2bv_slab_finish_local", "gf2bv_slab_solve",
     "gf2bv_slab_close",
+    "gf2bv_compose_words", "gf2bv_compose_device", "gf2bv_compose_power_words", "gf2bv_compose_power_device", "gf2bv_compose_shape",
+    "gf2bv_compose_last_times",
     "gf2bv_synth_device", "gf2bv_residual_device",
     "gf2bv_stream_ceiling_device", "gf2bv_lds_clock_device", "gf2bv_kernel_resources",
     "gf2bv_device_alloc", "gf2bv_device_free", "gf2bv_device_upload", "gf2bv_device_download",
@@ -244,6 +246,13 @@ def lib():
         L.gf2bv_slab_solve.argtypes = [vp, pp]
         L.gf2bv_slab_close.argtypes = [vp]
         L.gf2bv_slab_close.restype = None
+        L.gf2bv_compose_words.argtypes = [vp, i64, i64, i64, vp, i64, i64, vp, i64, i32]
+        L.gf2bv_compose_device.argtypes = [vp, i64, i64, i64, vp, i64, i64, vp, i64, i32, vp]
+        L.gf2bv_compose_power_words.argtypes = [vp, i64, i64, vp, i64, vp, i64, i32]
+        L.gf2bv_compose_power_device.argtypes = [vp, i64, i64, vp, i64, vp, i64, i32, vp]
+        L.gf2bv_compose_shape.argtypes = [vp]
+        L.gf2bv_compose_last_times.argtypes = [vp]
+        L.gf2bv_compose_last_times.restype = None
         L.gf2bv_synth_device.argtypes = [vp, i64, i64, i64, ctypes.c_uint64, i32, vp]
         L.gf2bv_residual_device.argtypes = [vp, i64, i64, i64, vp, i32, vp, ctypes.POINTER(i64)]
         L.gf2bv_stream_ceiling_device.argtypes = [i32, i64, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
@@ -857,6 +866,80 @@ def solve_rhs_quad_terms(lin, term_off, ta, tb, n_lin: int, rhs: np.ndarray, row
     rc = lib().gf2bv_solve_rhs_quad_terms(*_ptrs(lin, term_off, ta, tb), len(lin), rows, n_lin,
                                           rhs.ctypes.data, nrhs, rhs.shape[1], mode, device, hs)
     return _take_all(hs, nrhs, rc, mode)
+
+
+# ---- composition: affine maps substituted into affine forms, powers of a self-map (gf2bv_compose_*) --------------------------------
+def form_words(unknowns: int) -> int:
+    """64-bit words of an affine form over `unknowns` unknowns: the constant and one bit each"""
+    return (unknowns + 1 + 63) // 64
+
+
+def exponent_words(k: int) -> np.ndarray:
+    """a non-negative int as little-endian uint64 words, at least one (the exponent of gf2bv_compose_power_*)"""
+    k = int(k)
+    if k < 0:
+        raise ValueError("the exponent must not be negative")
+    nw = max(1, (k.bit_length() + 63) // 64)
+    return np.frombuffer(k.to_bytes(8 * nw, "little"), dtype=np.uint64).copy()
+
+
+def compose_shape() -> dict:
+    """gf2bv_compose_shape (no device): k_compose's bits of `a` per table slice, rows per workgroup, words per column tile, LDS bytes"""
+    v = (ctypes.c_int32 * 4)()
+    _check(lib().gf2bv_compose_shape(v))
+    return dict(zip(("slice_bits", "rows_per_workgroup", "tile_words", "lds_bytes"), (int(x) for x in v)))
+
+
+def compose_last_times() -> dict:
+    """this thread's last composition entry: upload, kernels, download in ms, and the number of products"""
+    v = (ctypes.c_double * 4)()
+    lib().gf2bv_compose_last_times(v)
+    return {"ms_upload": v[0], "ms_kernels": v[1], "ms_download": v[2], "products": int(v[3])}
+
+
+def _forms(x, unknowns: int, what: str) -> np.ndarray:
+    x = np.ascontiguousarray(x, dtype=np.uint64)
+    if x.ndim != 2 or x.shape[1] < form_words(unknowns):
+        raise ValueError(f"{what} must be a 2-D uint64 array of at least {form_words(unknowns)} words a row")
+    return x
+
+
+def compose_words(a, n: int, b, nb: int, stride_words: int | None = None, device: int = 0) -> np.ndarray:
+    """The forms a ([ra, >= ceil((n + 1) / 64)] uint64, bit 0 the constant, bit 1 + g unknown g) with the images b ([n, >= ceil((nb + 1) / 64)],
+    row g replaces unknown g) substituted on the device: [ra, stride_words] uint64 over nb unknowns (gf2bv_compose_words)."""
+    a, b = _forms(a, n, "a"), _forms(b, nb, "b")
+    if len(b) != n:
+        raise ValueError("b needs one image row per unknown of a")
+    stride = form_words(nb) if stride_words is None else stride_words
+    out = np.empty((len(a), max(stride, 0)), dtype=np.uint64)
+    _check(lib().gf2bv_compose_words(a.ctypes.data if len(a) else out.ctypes.data, len(a), a.shape[1], n, b.ctypes.data, b.shape[1], nb,
+                                     out.ctypes.data, stride, device))
+    return out
+
+
+def compose_device(d_a: int, ra: int, a_stride: int, n: int, d_b: int, b_stride: int, nb: int, d_out: int, out_stride: int,
+                   device: int = 0, stream: int = 0) -> None:
+    """compose_words with everything resident in device memory: the kernel is enqueued on `stream` and the call returns."""
+    _check(lib().gf2bv_compose_device(d_a, ra, a_stride, n, d_b, b_stride, nb, d_out, out_stride, device, stream or None))
+
+
+def compose_power_words(b, n: int, k: int, stride_words: int | None = None, device: int = 0) -> np.ndarray:
+    """The self-map b ([n, >= ceil((n + 1) / 64)] uint64) substituted into itself k times by square-and-multiply on the device:
+    [n, stride_words] uint64; k = 0 the identity (gf2bv_compose_power_words)."""
+    b, kw = _forms(b, n, "b"), exponent_words(k)
+    if len(b) != n:
+        raise ValueError("b needs one image row per unknown")
+    stride = form_words(n) if stride_words is None else stride_words
+    out = np.empty((n, max(stride, 0)), dtype=np.uint64)
+    _check(lib().gf2bv_compose_power_words(b.ctypes.data, b.shape[1], n, kw.ctypes.data, len(kw), out.ctypes.data, stride, device))
+    return out
+
+
+def compose_power_device(d_b: int, b_stride: int, n: int, k: int, d_out: int, out_stride: int, device: int = 0, stream: int = 0) -> None:
+    """compose_power_words on device memory: works on `stream` behind what is queued there and waits for it (its buffers go back to
+    the pool); d_out may be d_b."""
+    kw = exponent_words(k)
+    _check(lib().gf2bv_compose_power_device(d_b, b_stride, n, kw.ctypes.data, len(kw), d_out, out_stride, device, stream or None))
 
 
 def _sys_row_off(sys_row_off, nrows: int) -> np.ndarray:

@@ -793,6 +793,41 @@ int gf2bv_solve_xl4_cubic_guess_terms(const uint64_t *lin, const int64_t *off2, 
 int64_t gf2bv_xl4_cubic_guess_chunk(int64_t m, int64_t n_lin, int64_t nguess, int64_t free_bytes);
 int gf2bv_xl4_cubic_guess_chunk_device(int64_t m, int64_t n_lin, int64_t nguess, int device, int64_t *chunk);
 
+/* ---- composition: affine maps substituted into affine forms, and powers of a self-map, on the device (k_compose) -----------
+ * Every form is in the equation-int order: bit 0 the constant, bit 1 + g unknown g, little-endian 64-bit words.
+ *   a[ra][>= Wa]   forms over n unknowns, Wa = ceil((n + 1) / 64); bits above n are ignored,
+ *   b[n][>= Wb]    images over nb unknowns, Wb = ceil((nb + 1) / 64): row g is the affine form that replaces unknown g; bits
+ *                  above nb are ignored and come out zero.
+ * out[r] = (bit 0 of a[r]) x 1 ^ XOR over the g with bit 1 + g of a[r] set, of b[g]: ra rows of Wb words over nb unknowns -- the
+ * GF(2) matrix product a x b~, b~ = b with the unit form (bit 0 alone) in front as row 0.  The entries supply the unit row
+ * themselves.  Words Wb .. out_stride - 1 of every output row are written as zero.  ra == 0 is legal and writes nothing.
+ * gf2bv_compose_words: host pointers; upload, kernel, download on a stream of the pool.
+ * gf2bv_compose_device: everything in device memory; the kernel is enqueued on `stream` (a HIP stream handle or NULL) and the call
+ * returns, as gf2bv_quad_expand_device does; no pointer is kept.  d_a, d_b, d_out 16-byte aligned, their strides even; d_out must
+ * not overlap d_a or d_b.
+ * gf2bv_compose_power_*: b a self-map (n rows over n unknowns); out = the n image rows of b substituted into itself k times -- k = 0
+ * the identity (image g = unknown g), k = 1 b itself with its bits above n dropped.  k = k_words[0 .. k_nwords), little-endian.
+ * Square-and-multiply on the device: three (n + 1) x stride buffers of the pool stay resident, nothing comes back to the host
+ * between the products, bit_length(k) - 1 + popcount(k) of them.  gf2bv_compose_power_device works on `stream` behind what is
+ * queued there, copies d_b first (d_out may be d_b) and WAITS for the stream before it returns: its buffers go back to the pool.
+ * gf2bv_compose_shape (no device): out[0] the bits of `a` per table slice, out[1] the rows of a workgroup, out[2] the words of a
+ * column tile, out[3] the kernel's LDS bytes.
+ * gf2bv_compose_last_times: this thread's last composition entry -- ms[0] upload, ms[1] kernels, ms[2] download (milliseconds; zero
+ * for gf2bv_compose_device, which waits for nothing), ms[3] the number of products.
+ * Argument errors (null pointers, ra < 0, n < 1 or nb < 1, n + 1 or nb + 1 >= 2^31 - 64, a stride below its width, an odd or
+ * unaligned device matrix, k_nwords < 1) return GF2BV_ERR_ARG before any device is touched; buffers that do not fit are
+ * GF2BV_ERR_NOMEM with nothing left allocated. */
+int gf2bv_compose_words(const uint64_t *a, int64_t ra, int64_t a_stride, int64_t n, const uint64_t *b, int64_t b_stride, int64_t nb,
+                        uint64_t *out, int64_t out_stride, int device);
+int gf2bv_compose_device(const void *d_a, int64_t ra, int64_t a_stride, int64_t n, const void *d_b, int64_t b_stride, int64_t nb,
+                         void *d_out, int64_t out_stride, int device, void *stream);
+int gf2bv_compose_power_words(const uint64_t *b, int64_t b_stride, int64_t n, const uint64_t *k_words, int64_t k_nwords, uint64_t *out,
+                              int64_t out_stride, int device);
+int gf2bv_compose_power_device(const void *d_b, int64_t b_stride, int64_t n, const uint64_t *k_words, int64_t k_nwords, void *d_out,
+                               int64_t out_stride, int device, void *stream);
+int gf2bv_compose_shape(int32_t out[4]);
+void gf2bv_compose_last_times(double ms[4]);
+
 /* ---- synthetic systems + independent residual check (bench / tests) ----------------------- */
 /* word w of row r = mix64(mix64(seed) ^ ((r<<20)|w)); planted solution = pseudo-row 0xFFFFF;
  * RHS = <row, planted>.  Writes rows x stride_words words at d_aug. */
