@@ -18,7 +18,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <map>
 #include <memory>
 #include <new>
@@ -319,6 +318,8 @@ struct Pool {
 		}
 		for (void *q : drop) (void)hipFree(q);
 	}
+	// streams and events handed out and not yet returned, per device (gf2bv_pool_in_use; the buffers are `live` and `big_live`)
+	std::map<int, i64> streams_out, events_out;
 	hipError_t event(hipEvent_t *e, bool timing)
 	{
 		int device = 0;
@@ -326,9 +327,11 @@ struct Pool {
 		{
 			std::lock_guard<std::mutex> lk(mu);
 			auto &v = events[{device, timing ? 1 : 0}];
-			if (!v.empty()) { *e = v.back(); v.pop_back(); return hipSuccess; }
+			if (!v.empty()) { *e = v.back(); v.pop_back(); events_out[device]++; return hipSuccess; }
 		}
-		return timing ? hipEventCreate(e) : hipEventCreateWithFlags(e, hipEventDisableTiming);
+		const hipError_t err = timing ? hipEventCreate(e) : hipEventCreateWithFlags(e, hipEventDisableTiming);
+		if (err == hipSuccess) { std::lock_guard<std::mutex> lk(mu); events_out[device]++; }
+		return err;
 	}
 	void release_event(hipEvent_t e, bool timing)
 	{
@@ -336,6 +339,7 @@ struct Pool {
 		int device = 0;
 		(void)hipGetDevice(&device);
 		std::lock_guard<std::mutex> lk(mu);
+		events_out[device]--;
 		auto &v = events[{device, timing ? 1 : 0}];
 		if (v.size() < 8192) v.push_back(e); else (void)hipEventDestroy(e);
 	}
@@ -348,17 +352,19 @@ struct Pool {
 		{
 			std::lock_guard<std::mutex> lk(mu);
 			auto &v = streams[{device, cls}];
-			if (!v.empty()) { *s = v.back(); v.pop_back(); return hipSuccess; }
+			if (!v.empty()) { *s = v.back(); v.pop_back(); streams_out[device]++; return hipSuccess; }
 		}
-		if (!low) return hipStreamCreateWithFlags(s, hipStreamNonBlocking);
 		int lo = 0, hi = 0;
-		(void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-		return hipStreamCreateWithPriority(s, hipStreamNonBlocking, lo);
+		if (low) (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
+		const hipError_t err = low ? hipStreamCreateWithPriority(s, hipStreamNonBlocking, lo) : hipStreamCreateWithFlags(s, hipStreamNonBlocking);
+		if (err == hipSuccess) { std::lock_guard<std::mutex> lk(mu); streams_out[device]++; }
+		return err;
 	}
 	void release_stream(hipStream_t s, int device, int cls)
 	{
 		if (!s) return;
 		std::lock_guard<std::mutex> lk(mu);
+		streams_out[device]--;
 		streams[{device, cls}].push_back(s);
 	}
 	// A low-priority stream for the bulk side of a solve whose panel path runs on `a` (round 5).  Not every pair of streams is equal on
@@ -382,49 +388,7 @@ struct Pool {
 	// does: on a good pair it ends after NB x ~24 us (measured 187-192 us for 8 blocks), on a bad one after NB x ~55 us (439-446): each
 	// block's panel kernels wait for the hold before them.  (A first probe -- when does the last of 80 panel-shaped workgroups begin
 	// beside two holds: 3 us or 36 -- saw only some of the bad pairs; this one agreed with the solve on 38 of 38 pairs.)
-	hipError_t probe_pair(hipStream_t a, hipStream_t b, int device, int *ok, const Knobs &kn, int depth = 0)
-	{
-		*ok = 1;
-		constexpr int NB = 6;
-		unsigned long long *q = nullptr, hq[2 * NB + 2];
-		int *fl = nullptr;
-		hipError_t e = alloc((void **)&q, sizeof hq, device);
-		if (e != hipSuccess) return e;
-		struct Free { Pool *p; void *q; ~Free() { p->release(q); } } g1{ this, q };
-		if ((e = alloc((void **)&fl, sizeof(int) * 2 * NB, device)) != hipSuccess) return e;
-		Free g2{ this, fl };
-		if ((e = hipMemsetAsync(fl, 0, sizeof(int) * 2 * NB, a)) != hipSuccess) return e;
-		if ((e = hipMemsetAsync(q, 0, sizeof hq, a)) != hipSuccess) return e;
-		if ((e = hipStreamSynchronize(a)) != hipSuccess) return e;
-		if ((e = hipStreamSynchronize(b)) != hipSuccess) return e;
-		int cus = 256;
-		(void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-		k_probe_stamp_panel<<<dim3(1), dim3(256), 0, a>>>(q + 2 * NB);
-		for (int i = 0; i < NB; i++) {
-			k_probe_panel_work<<<dim3(1), dim3(256), 0, a>>>(q + 2 * i, 1000ull);
-			k_probe_panel_work<<<dim3(1), dim3(256), 0, a>>>(q + 2 * i + 1, 1000ull);
-			k_probe_set<<<dim3(1), dim3(1), 0, a>>>(fl + i);
-			k_probe_wait<<<dim3(1), dim3(1), 0, b>>>(fl + i, fl + NB + i, 200000ull);
-			k_probe_hold_bulk<<<dim3((unsigned)cus), dim3(512), 0, b>>>(q + 2 * NB + 1, 4000ull);
-		}
-		if ((e = hipGetLastError()) != hipSuccess) return e;
-		if ((e = hipStreamSynchronize(a)) != hipSuccess) return e;
-		if ((e = hipStreamSynchronize(b)) != hipSuccess) return e;
-		if ((e = hipMemcpy(hq, q, sizeof hq, hipMemcpyDeviceToHost)) != hipSuccess) return e;
-		const double chain_us = ((double)hq[2 * NB - 1] - (double)hq[2 * NB]) / 100.0;
-		*ok = chain_us < 37.0 * NB;
-		// a verdict near the threshold (good pairs measure ~24 us per probe block, bad ones ~55: other work on the device can push a
-		// probe either way) is not kept on one sample: the pair is measured again, twice at most, and the FASTER run decides -- a
-		// neighbour can only slow a probe down
-		if (depth < 2 && chain_us > 0.75 * 37.0 * NB && chain_us < 1.5 * 37.0 * NB) {
-			int again = 1;
-			if (probe_pair(a, b, device, &again, kn, depth + 1) == hipSuccess) *ok = *ok || again;
-		}
-		if (kn.trace)
-			fprintf(stderr, "[gf2bv trace] stream pair %p / %p: the panel chain of %d probe blocks took %.1f us (%s)\n", (void *)a, (void *)b, NB, chain_us,
-			        *ok ? "good" : "waits for the bulk stream");
-		return hipSuccess;
-	}
+	hipError_t probe_pair(hipStream_t a, hipStream_t b, int device, int *ok, const Knobs &kn);
 	// cls: the class the stream comes from and goes back to (1, or 3 for a batch call's gangs); also: the panel streams of the solves that
 	// will run beside this one (all idle now) -- the stream has to get on with them as well.
 	hipError_t low_stream_for(const Knobs &kn, hipStream_t a, int device, hipStream_t *out, int cls = 1, const std::vector<hipStream_t> &also = {})
@@ -459,12 +423,15 @@ struct Pool {
 					if (low_created[device] >= kMaxLow) break;
 					low_created[device]++;
 				}
+				else streams_out[device]++;             // (a rejected candidate goes back through release_stream)
 			}
 			if (known_good) { *out = c; break; }
 			if (!c) {
 				int lo = 0, hi = 0;
 				(void)hipDeviceGetStreamPriorityRange(&lo, &hi);
 				if ((err = hipStreamCreateWithPriority(&c, hipStreamNonBlocking, lo)) != hipSuccess) break;
+				std::lock_guard<std::mutex> lk(mu);
+				streams_out[device]++;
 			}
 			int all_ok = 1;
 			for (hipStream_t x : with) {
@@ -500,12 +467,108 @@ Pool &pool()
 }
 // A pool buffer for an entry that tells "does not fit" from a failure: out of device memory is GF2BV_ERR_NOMEM with the message
 // `nomem` (and the runtime's sticky error cleared), any other error GF2BV_ERR_HIP with `what`.
-int alloc_or_nomem(void **out, size_t bytes, int device, const char *nomem, const char *what)
+int nomem_or_hip(hipError_t e, const char *nomem, const char *what)
 {
-	const hipError_t e = pool().alloc(out, bytes, device);
 	if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(GF2BV_ERR_NOMEM, nomem); }
 	if (e != hipSuccess) return fail(GF2BV_ERR_HIP, what, e);
 	return GF2BV_OK;
+}
+// (a buffer that a Solver or a kept handle owns: not scope-held)
+int alloc_or_nomem(void **out, size_t bytes, int device, const char *nomem, const char *what) { return nomem_or_hip(pool().alloc(out, bytes, device), nomem, what); }
+
+// What one scope borrows from the pool: at most one stream -- the pool's, of class `cls`, or the caller's, which is waited for and
+// never returned -- and any number of buffers and events.  THE rule of giving back, on every return path (every HIPCHK is an early
+// return, and work may be in flight then): the stream and every stream named with wait_for() are synchronised, then the buffers go
+// back, then the events, then the stream, to the class it came from.
+struct Held {
+	const int device;
+	hipStream_t st = nullptr;
+	explicit Held(int device) : device(device) {}
+	Held(int device, hipStream_t callers) : device(device) { on(callers); }
+	Held(const Held &) = delete;
+	~Held()
+	{
+		for (hipStream_t s : waits) (void)hipStreamSynchronize(s);
+		for (void *p : bufs) pool().release(p);
+		for (const auto &e : events) pool().release_event(e.first, e.second);
+		if (cls >= 0) pool().release_stream(st, device, cls);
+	}
+	hipError_t stream(int from_cls)                // a stream of the pool
+	{
+		const hipError_t e = pool().stream(&st, device, from_cls);
+		if (e == hipSuccess) { cls = from_cls; waits.push_back(st); }
+		return e;
+	}
+	void on(hipStream_t callers) { st = callers; waits.push_back(st); }       // (null: the null stream)
+	void wait_for(hipStream_t s) { waits.push_back(s); }
+	hipError_t get(void **out, size_t bytes)
+	{
+		const hipError_t e = pool().alloc(out, bytes, device);
+		if (e == hipSuccess) bufs.push_back(*out);
+		return e;
+	}
+	int alloc(void **out, size_t bytes, const char *nomem, const char *what) { return nomem_or_hip(get(out, bytes), nomem, what); }
+	hipError_t event(hipEvent_t *ev, bool timing = true)
+	{
+		const hipError_t e = pool().event(ev, timing);
+		if (e == hipSuccess) events.push_back({ *ev, timing });
+		return e;
+	}
+private:
+	int cls = -1;                                  // the pool class `st` goes back to; -1: not the pool's
+	std::vector<hipStream_t> waits;
+	std::vector<void *> bufs;
+	std::vector<std::pair<hipEvent_t, bool>> events;
+};
+
+hipError_t Pool::probe_pair(hipStream_t a, hipStream_t b, int device, int *ok, const Knobs &kn)
+{
+	*ok = 1;
+	constexpr int NB = 6;
+	constexpr double limit_us = 37.0 * NB;
+	unsigned long long *q = nullptr, hq[2 * NB + 2];
+	int *fl = nullptr;
+	Held H(device, a); H.wait_for(b);
+	hipError_t e;
+	auto bad = [&](hipError_t x) { return (e = x) != hipSuccess; };
+	if (bad(H.get((void **)&q, sizeof hq)) || bad(H.get((void **)&fl, sizeof(int) * 2 * NB))) return e;
+	int cus = 256;
+	(void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+	auto measure = [&](double *chain_us) -> hipError_t {
+		if (bad(hipMemsetAsync(fl, 0, sizeof(int) * 2 * NB, a)) || bad(hipMemsetAsync(q, 0, sizeof hq, a))) return e;
+		if (bad(hipStreamSynchronize(a)) || bad(hipStreamSynchronize(b))) return e;
+		k_probe_stamp_panel<<<dim3(1), dim3(256), 0, a>>>(q + 2 * NB);
+		for (int i = 0; i < NB; i++) {
+			k_probe_panel_work<<<dim3(1), dim3(256), 0, a>>>(q + 2 * i, 1000ull);
+			k_probe_panel_work<<<dim3(1), dim3(256), 0, a>>>(q + 2 * i + 1, 1000ull);
+			k_probe_set<<<dim3(1), dim3(1), 0, a>>>(fl + i);
+			k_probe_wait<<<dim3(1), dim3(1), 0, b>>>(fl + i, fl + NB + i, 200000ull);
+			k_probe_hold_bulk<<<dim3((unsigned)cus), dim3(512), 0, b>>>(q + 2 * NB + 1, 4000ull);
+		}
+		if (bad(hipGetLastError()) || bad(hipStreamSynchronize(a)) || bad(hipStreamSynchronize(b))) return e;
+		if (bad(hipMemcpy(hq, q, sizeof hq, hipMemcpyDeviceToHost))) return e;
+		*chain_us = ((double)hq[2 * NB - 1] - (double)hq[2 * NB]) / 100.0;
+		return hipSuccess;
+	};
+	// a verdict near the threshold (good pairs measure ~24 us per probe block, bad ones ~55: other work on the device can push a
+	// probe either way) is not kept on one sample: the pair is measured again, three times in all at most, and the FASTER run
+	// decides -- a neighbour can only slow a probe down.  A repeat that cannot run decides nothing.
+	bool good = false;
+	for (int k = 0; k < 3; k++) {
+		double chain_us = 0;
+		if (bad(measure(&chain_us))) {
+			if (k == 0) return e;
+			(void)hipGetLastError();
+			break;
+		}
+		good = good || chain_us < limit_us;
+		if (kn.trace)
+			fprintf(stderr, "[gf2bv trace] stream pair %p / %p: the panel chain of %d probe blocks took %.1f us (%s)\n", (void *)a, (void *)b, NB, chain_us,
+			        chain_us < limit_us ? "good" : "waits for the bulk stream");
+		if (!(chain_us > 0.75 * limit_us && chain_us < 1.5 * limit_us)) break;
+	}
+	*ok = good;
+	return hipSuccess;
 }
 
 // ---- kernel configurations -----------------------------------------------------------------
@@ -815,31 +878,6 @@ struct gf2bv_result {
 
 namespace {
 
-// Pool resources of an entry point that must go back on every return path (error paths included).
-struct Scratch {
-	std::vector<void *> bufs;
-	std::vector<hipEvent_t> timing_events;
-	hipStream_t sync_first = nullptr;          // synchronised before anything is released (work may still be in flight)
-	~Scratch()
-	{
-		if (sync_first) (void)hipStreamSynchronize(sync_first);
-		for (void *p : bufs) pool().release(p);
-		for (hipEvent_t e : timing_events) pool().release_event(e, true);
-	}
-	hipError_t alloc(void **out, size_t bytes, int device)
-	{
-		hipError_t e = pool().alloc(out, bytes, device);
-		if (e == hipSuccess) bufs.push_back(*out);
-		return e;
-	}
-	hipError_t event(hipEvent_t *ev)
-	{
-		hipError_t e = pool().event(ev, true);
-		if (e == hipSuccess) timing_events.push_back(*ev);
-		return e;
-	}
-};
-
 int check_device(int device)
 {
 	int n = 0;
@@ -997,8 +1035,8 @@ int streams_run_concurrently(const Knobs &kn, int device, hipStream_t a, hipStre
 	if (it != known.end()) { *ok = it->second; return GF2BV_OK; }
 	if (kn.flag_sync == 2) { *ok = 1; return GF2BV_OK; }      // (taken for granted until a gate times out: exercises the time-out / retry path)
 	int *d = nullptr;
-	HIPCHK(pool().alloc((void **)&d, 2 * sizeof(int), device));
-	struct Free { int *p; ~Free() { pool().release(p); } } guard{d};
+	Held H(device, a); H.wait_for(b);
+	HIPCHK(H.get((void **)&d, 2 * sizeof(int)));
 	HIPCHK(hipMemsetAsync(d, 0, 2 * sizeof(int), a));
 	HIPCHK(hipStreamSynchronize(a));
 	HIPCHK(hipStreamSynchronize(b));
@@ -1025,8 +1063,8 @@ int xcd_dispatch_is_round_robin(int device, hipStream_t st, int *ok)
 	auto it = known.find(device);
 	if (it != known.end()) { *ok = it->second; return GF2BV_OK; }
 	int *d = nullptr;
-	HIPCHK(pool().alloc((void **)&d, 64 * sizeof(int), device));
-	struct Free { int *p; ~Free() { pool().release(p); } } guard{d};
+	Held H(device, st);
+	HIPCHK(H.get((void **)&d, 64 * sizeof(int)));
 	int h[64];
 	int good = 1;
 	for (int rep = 0; rep < 2 && good; rep++) {          // (twice: the second launch starts where the first one left the dispatcher)
@@ -2062,19 +2100,12 @@ int run_gangs(const Knobs &kn, int device, i64 nsys, i64 gang, hipEvent_t ready,
 	const i64 ngangs = (nsys + gang - 1) / gang;
 	std::atomic<i64> next_gang{0};
 	auto work = [&]() -> int {
-		struct Mine {
-			int device; hipStream_t st = nullptr; void *buf = nullptr;
-			~Mine()
-			{
-				if (st) (void)hipStreamSynchronize(st);
-				pool().release(buf);
-				pool().release_stream(st, device, 2);
-			}
-		} W{ device };
+		Held W(device);
+		void *buf = nullptr;
 		HIPCHK(hipSetDevice(device));
-		HIPCHK(pool().stream(&W.st, device, 2));
+		HIPCHK(W.stream(2));
 		HIPCHK(hipStreamWaitEvent(W.st, ready, 0));
-		if (worker_bytes) HIPCHK(pool().alloc(&W.buf, worker_bytes, device));
+		if (worker_bytes) HIPCHK(W.get(&buf, worker_bytes));
 		for (i64 q; (q = next_gang.fetch_add(1)) < ngangs;) {
 			const i64 s0 = q * gang;
 			const int ns = (int)std::min<i64>(gang, nsys - s0);
@@ -2087,7 +2118,7 @@ int run_gangs(const Knobs &kn, int device, i64 nsys, i64 gang, hipEvent_t ready,
 				S.device = device;
 				S.sA = W.st;
 				S.nsys = ns;
-				const int r = stage(S, s0, ns, W.buf);
+				const int r = stage(S, s0, ns, buf);
 				return r ? r : solve_gang(S, &out[s0]);
 			});
 			if (rc) return rc;
@@ -2249,10 +2280,10 @@ int small_solve(const Knobs &kn, const MatrixInput &in, i64 rows, i64 cols, int 
 	if (rc) return rc;
 	// Stream: a matrix that already lives on the device is whatever `stream` (NULL = the null stream) has produced -- the launch goes
 	// onto that very stream, as on the blocked path.  Host inputs depend on nothing: a pool stream of their own (non-blocking).
-	hipStream_t st = stream;
-	bool own_stream = false;
-	if (!st && !in.d_words) { HIPCHK(pool().stream(&st, device, false)); own_stream = true; }
-	struct Back { hipStream_t st; int device; bool own; void *d_in; ~Back() { if (own) pool().release_stream(st, device, false); pool().release(d_in); } } back{ st, device, own_stream, nullptr };
+	Held H(device);
+	if (!stream && !in.d_words) HIPCHK(H.stream(0)); else H.on(stream);
+	const hipStream_t st = H.st;
+	void *d_in = nullptr;
 	const u64 *d_src = in.d_words;
 	i64 d_stride = in.stride;
 	const uint32_t *d_dig = nullptr;
@@ -2261,8 +2292,8 @@ int small_solve(const Knobs &kn, const MatrixInput &in, i64 rows, i64 cols, int 
 	// 2-6 us less than a host-to-device copy in front of the launch: profiles/r04_small.txt).  GF2BV_SMALL_ZC=0 / 1 forces either.
 	const bool zero_copy = kn.small_zc >= 0 ? kn.small_zc != 0 : in_bytes <= ((size_t)32 << 10);
 	if (in_bytes) {
-		if (!zero_copy) HIPCHK(pool().alloc(&back.d_in, in_bytes, device));
-		char *d_base = zero_copy ? G.h_in : (char *)back.d_in;
+		if (!zero_copy) HIPCHK(H.get(&d_in, in_bytes));
+		char *d_base = zero_copy ? G.h_in : (char *)d_in;
 		if (in.h_off) {
 			memcpy(G.h_in, in.h_off, sizeof(i64) * (size_t)(rows + 1));
 			if (ndig) memcpy(G.h_in + sizeof(i64) * (size_t)(rows + 1), in.h_digits, sizeof(uint32_t) * (size_t)ndig);
@@ -2272,7 +2303,7 @@ int small_solve(const Knobs &kn, const MatrixInput &in, i64 rows, i64 cols, int 
 			for (i64 r = 0; r < rows; r++) memcpy(G.h_in + sizeof(u64) * (size_t)(r * wt), in.h_words + r * in.stride, sizeof(u64) * (size_t)wt);
 			d_src = (const u64 *)d_base; d_stride = wt;
 		}
-		if (!zero_copy) HIPCHK(hipMemcpyAsync(back.d_in, G.h_in, in_bytes, hipMemcpyHostToDevice, st));
+		if (!zero_copy) HIPCHK(hipMemcpyAsync(d_in, G.h_in, in_bytes, hipMemcpyHostToDevice, st));
 	}
 	// 16 wavefronts: every phase but wavefront 0's column loop is a few dependent LDS round trips per item, i.e. latency --
 	// 640 x 256: 143 us with 256 threads (profiles/r04_small.txt)
@@ -2356,15 +2387,15 @@ int check_rhs_args(i64 rows, i64 cols, const void *rhs, bool on_device, i64 nrhs
 // tiles (k_pack_digits puts the affine term at column `cols`; the callers overwrite it), or the words that hold coefficients -- and
 // only those -- copied into tiles (the words right of them are zero-filled)
 // (M: where row 0 goes -- an append packs its rows below the kept ones by passing S.M + row0 x TW)
-int pack_coefficients(const MatrixInput &in, i64 rows, i64 cols, i64 ntiles, i64 srows, int device, hipStream_t st, Scratch &scratch, u64 *M)
+int pack_coefficients(const MatrixInput &in, i64 rows, i64 cols, i64 ntiles, i64 srows, hipStream_t st, Held &held, u64 *M)
 {
 	const i64 cw = (cols + 63) / 64, rw = (rows + 63) / 64;
 	if (in.h_off) {
 		const i64 ndig = in.h_off[rows];
 		uint32_t *d_dig = nullptr;
 		i64 *d_off = nullptr;
-		HIPCHK(scratch.alloc((void **)&d_dig, sizeof(uint32_t) * std::max<i64>(1, ndig), device));
-		HIPCHK(scratch.alloc((void **)&d_off, sizeof(i64) * (rows + 1), device));
+		HIPCHK(held.get((void **)&d_dig, sizeof(uint32_t) * std::max<i64>(1, ndig)));
+		HIPCHK(held.get((void **)&d_off, sizeof(i64) * (rows + 1)));
 		if (ndig) HIPCHK(hipMemcpyAsync(d_dig, in.h_digits, sizeof(uint32_t) * ndig, hipMemcpyHostToDevice, st));
 		HIPCHK(hipMemcpyAsync(d_off, in.h_off, sizeof(i64) * (rows + 1), hipMemcpyHostToDevice, st));
 		k_pack_digits<<<dim3((unsigned)((ntiles * TW + 255) / 256), (unsigned)std::min<i64>(rows, 65535)), dim3(256), 0, st>>>(
@@ -2375,7 +2406,7 @@ int pack_coefficients(const MatrixInput &in, i64 rows, i64 cols, i64 ntiles, i64
 		if (in.h_words) {
 			sstride = round_up(cw, 2);
 			u64 *tmp = nullptr;
-			HIPCHK(scratch.alloc((void **)&tmp, sizeof(u64) * rows * sstride, device));
+			HIPCHK(held.get((void **)&tmp, sizeof(u64) * rows * sstride));
 			HIPCHK(hipMemcpy2DAsync(tmp, sstride * 8, in.h_words, in.stride * 8, cw * 8, rows, hipMemcpyHostToDevice, st));
 			src = tmp;
 		}
@@ -2402,20 +2433,19 @@ int solve_rhs(const MatrixInput &in, const u64 *rhs, bool rhs_on_device, i64 nrh
 	S.stride = in.h_off ? ntiles * TW : in.stride;
 	if (int rc = alloc_or_nomem((void **)&S.M, sizeof(u64) * ntiles * TW * srows + kOuterSlackBytes, device,
 	                            "the matrix widened by the right-hand sides does not fit on the device", "working matrix")) return rc;
-	Scratch scratch;                  // (declared after S: released first, after synchronising the solve's stream)
-	scratch.sync_first = S.sA;
-	HIPCHK(scratch.alloc((void **)&S.rhs_bad, sizeof(u64) * nmw, device));
+	Held held(device, S.sA);                // (declared after S: what the entry holds goes back before what the solver owns)
+	HIPCHK(held.get((void **)&S.rhs_bad, sizeof(u64) * nmw));
 	hipEvent_t p0, p1;
-	HIPCHK(scratch.event(&p0)); HIPCHK(scratch.event(&p1));
+	HIPCHK(held.event(&p0)); HIPCHK(held.event(&p1));
 	HIPCHK(hipEventRecord(p0, S.sA));
 	HIPCHK(hipMemsetAsync(S.rhs_bad, 0, sizeof(u64) * nmw, S.sA));
 	int rc;
-	if ((rc = pack_coefficients(in, rows, cols, ntiles, srows, S.device, S.sA, scratch, S.M))) return rc;
+	if ((rc = pack_coefficients(in, rows, cols, ntiles, srows, S.sA, held, S.M))) return rc;
 	const u64 *d_rhs = rhs;
 	i64 rhs_stride = rhs_words;
 	if (!rhs_on_device) {             // (only the words that hold rows go up)
 		u64 *d = nullptr;
-		HIPCHK(scratch.alloc((void **)&d, sizeof(u64) * nrhs * rw, device));
+		HIPCHK(held.get((void **)&d, sizeof(u64) * nrhs * rw));
 		HIPCHK(hipMemcpy2DAsync(d, rw * 8, rhs, rhs_words * 8, rw * 8, nrhs, hipMemcpyHostToDevice, S.sA));
 		d_rhs = d; rhs_stride = rw;
 	}
@@ -2556,18 +2586,16 @@ int factor_matrix(const MatrixInput &in, i64 rows, i64 cols, int mode, int devic
 	// Ordering contract: the matrix is whatever `stream` (the caller's stream, NULL = the null stream) has produced when this
 	// call is made.  S.sA is one of the library's own non-blocking streams, which is not ordered against any other stream by
 	// itself: it waits for an event recorded on `stream` here.
+	Held held(device, S.sA);
 	if (in.d_words) {
 		hipEvent_t e = nullptr;
-		HIPCHK(pool().event(&e, false));
+		HIPCHK(held.event(&e, false));
 		HIPCHK(hipEventRecord(e, stream));
 		HIPCHK(hipStreamWaitEvent(S.sA, e, 0));
-		pool().release_event(e, false);
 	}
 	if (int rc = alloc_or_nomem((void **)&S.M, sizeof(u64) * ntiles * TW * srows + kOuterSlackBytes, device,
 	                            "the factorization (the matrix and its row transform, about twice the matrix) does not fit on the device", "working matrix")) return rc;
-	Scratch scratch;
-	scratch.sync_first = S.sA;
-	int rc = pack_coefficients(in, rows, cols, ntiles, srows, S.device, S.sA, scratch, S.M);
+	int rc = pack_coefficients(in, rows, cols, ntiles, srows, S.sA, held, S.M);
 	if (rc) return rc;
 	k_factor_init<<<dim3((unsigned)((rows + 255) / 256), (unsigned)std::min<i64>(wt - (cols >> 6), 64)), dim3(256), 0, S.sA>>>(
 		rows, cols, srows, tw0, rw, S.M);
@@ -2660,14 +2688,13 @@ int factor_solve(gf2bv_factor *h, const u64 *rhs, bool on_device, i64 nrhs, i64 
 	S.kn.refresh();
 	HIPCHK(hipSetDevice(h->device));
 	const i64 rw = h->rw, C = kFactorSlots;
-	Scratch scratch;
-	scratch.sync_first = S.sA;
+	Held held(h->device, S.sA);
 	u64 *acc = nullptr, *bad = nullptr, *d = nullptr;
-	HIPCHK(scratch.alloc((void **)&acc, sizeof(u64) * std::max<i64>(1, h->rows), h->device));
-	HIPCHK(scratch.alloc((void **)&bad, sizeof(u64), h->device));
-	if (!on_device) HIPCHK(scratch.alloc((void **)&d, sizeof(u64) * C * rw, h->device));
+	HIPCHK(held.get((void **)&acc, sizeof(u64) * std::max<i64>(1, h->rows)));
+	HIPCHK(held.get((void **)&bad, sizeof(u64)));
+	if (!on_device) HIPCHK(held.get((void **)&d, sizeof(u64) * C * rw));
 	hipEvent_t ev[5];
-	for (hipEvent_t &e : ev) HIPCHK(scratch.event(&e));
+	for (hipEvent_t &e : ev) HIPCHK(held.event(&e));
 	// Ordering contract: the right-hand sides are whatever `stream` (the caller's stream, NULL = the null stream) has produced
 	// when this call is made.  S.sA is one of the library's own non-blocking streams, which is not ordered against any other
 	// stream by itself: it waits for an event recorded on `stream` here.
@@ -2869,8 +2896,6 @@ int factor_append(gf2bv_factor *h, const MatrixInput &in, i64 k, hipStream_t str
 	const i64 srows2 = grow ? slab_rows(cap) : S.srows, ntiles2 = grow ? tiles_for(h->tw0 + (cap + 63) / 64) : S.ntiles;
 	double ms[5] = {0, 0, 0, 0, 0};
 	// everything the append allocates is taken before the handle is touched: an argument error or a refusal leaves it as it was
-	Scratch scratch;
-	scratch.sync_first = S.sA;
 	u64 *M2 = S.M;
 	int *died2 = S.died;
 	if (grow) {
@@ -2884,18 +2909,19 @@ int factor_append(gf2bv_factor *h, const MatrixInput &in, i64 k, hipStream_t str
 		u64 *M; int *died; bool own;
 		~Grown() { if (own) { pool().release(M); pool().release(died); } }
 	} grown{ M2, died2, grow };
+	Held held(h->device, S.sA);             // (declared after `grown`: the stream is waited for before the grown buffers go back)
 	const i64 kc = std::min(k, kAppendChunk);
 	const i64 nfw = (cols + 63) / 64, ldw = nfw + (kc + 63) / 64;
 	AppendBufs B;
-	HIPCHK(scratch.alloc((void **)&B.snap, sizeof(u64) * 2 * kAppendChunk, h->device));
-	HIPCHK(scratch.alloc((void **)&B.W, sizeof(u64) * kc * ldw, h->device));
-	HIPCHK(scratch.alloc((void **)&B.fc, sizeof(int) * cols, h->device));
-	HIPCHK(scratch.alloc((void **)&B.out, sizeof(int) * (2 * kAppendChunk + 1), h->device));
-	HIPCHK(scratch.alloc((void **)&B.items, sizeof(int4) * cols, h->device));
-	for (int **p : { &B.nb, &B.nr, &B.drow, &B.dval }) HIPCHK(scratch.alloc((void **)p, sizeof(int) * kAppendChunk, h->device));
-	for (hipEvent_t &e : B.ev) HIPCHK(scratch.event(&e));
+	HIPCHK(held.get((void **)&B.snap, sizeof(u64) * 2 * kAppendChunk));
+	HIPCHK(held.get((void **)&B.W, sizeof(u64) * kc * ldw));
+	HIPCHK(held.get((void **)&B.fc, sizeof(int) * cols));
+	HIPCHK(held.get((void **)&B.out, sizeof(int) * (2 * kAppendChunk + 1)));
+	HIPCHK(held.get((void **)&B.items, sizeof(int4) * cols));
+	for (int **p : { &B.nb, &B.nr, &B.drow, &B.dval }) HIPCHK(held.get((void **)p, sizeof(int) * kAppendChunk));
+	for (hipEvent_t &e : B.ev) HIPCHK(held.event(&e));
 	hipEvent_t g0, g1;
-	HIPCHK(scratch.event(&g0)); HIPCHK(scratch.event(&g1));
+	HIPCHK(held.event(&g0)); HIPCHK(held.event(&g1));
 	// Ordering contract: the appended rows are whatever `stream` (the caller's stream, NULL = the null stream) has produced when
 	// this call is made.  S.sA is one of the library's own non-blocking streams, which is not ordered against any other stream by
 	// itself: it waits for an event recorded on `stream` here.
@@ -2911,7 +2937,7 @@ int factor_append(gf2bv_factor *h, const MatrixInput &in, i64 k, hipStream_t str
 		HIPCHK(hipGetLastError());
 	}
 	HIPCHK(hipMemsetAsync(died2 + rows, GF2_NEVER & 0xff, sizeof(int) * k, S.sA));
-	if (int rc = pack_coefficients(in, k, cols, ntiles2, srows2, h->device, S.sA, scratch, M2 + rows * TW)) return rc;
+	if (int rc = pack_coefficients(in, k, cols, ntiles2, srows2, S.sA, held, M2 + rows * TW)) return rc;
 	k_append_init<<<dim3((unsigned)((k + 255) / 256), (unsigned)std::min<i64>(h->tw0 + rw2 - (cols >> 6), 64)), dim3(256), 0, S.sA>>>(
 		rows, k, cols, srows2, h->tw0, h->tw0 + rw2, M2);
 	HIPCHK(hipGetLastError());
@@ -3062,13 +3088,11 @@ int gf2bv_solve_batch_device(void *d_aug, int64_t nsys, int64_t sys_stride_words
 	// Ordering contract: the matrices are whatever `stream` (the caller's stream, NULL = the null stream) has
 	// produced when this call is made.  The gangs run on the library's own non-blocking streams, which are not
 	// ordered against any other stream by themselves: each waits for an event recorded on `stream` here.
-	struct Ready {
-		hipEvent_t ev = nullptr;
-		~Ready() { pool().release_event(ev, false); }
-	} ready;
-	HIPCHK(pool().event(&ready.ev, false));
-	HIPCHK(hipEventRecord(ready.ev, (hipStream_t)stream));
-	return run_gangs(kn, device, nsys, gang, ready.ev, 0, out, [&](Solver &S, i64 s0, int, void *) -> int {
+	Held held(device);
+	hipEvent_t ready = nullptr;
+	HIPCHK(held.event(&ready, false));
+	HIPCHK(hipEventRecord(ready, (hipStream_t)stream));
+	return run_gangs(kn, device, nsys, gang, ready, 0, out, [&](Solver &S, i64 s0, int, void *) -> int {
 		S.src = (const u64 *)d_aug + s0 * sys_stride_words;
 		S.src_sys_words = sys_stride_words;
 		S.rows = rows; S.cols = cols; S.stride = stride_words; S.mode = mode;
@@ -3099,10 +3123,9 @@ int gf2bv_solve_words(const uint64_t *aug, int64_t rows, int64_t cols, int64_t s
 	S.stride = wt;
 	HIPCHK(pool().alloc((void **)&S.tmp_src, sizeof(u64) * std::max<i64>(1, rows) * S.stride, device));
 	S.src = S.tmp_src;
-	Scratch scratch;                  // (declared after S: released first, after synchronising the solve's stream)
-	scratch.sync_first = S.sA;
+	Held held(device, S.sA);                // (declared after S: what the entry holds goes back before what the solver owns)
 	hipEvent_t p0, p1;
-	HIPCHK(scratch.event(&p0)); HIPCHK(scratch.event(&p1));
+	HIPCHK(held.event(&p0)); HIPCHK(held.event(&p1));
 	HIPCHK(hipEventRecord(p0, S.sA));
 	if (rows > 0)
 		HIPCHK(hipMemcpy2DAsync(S.tmp_src, S.stride * 8, aug, stride_words * 8, wt * 8, rows, hipMemcpyHostToDevice, S.sA));
@@ -3137,29 +3160,21 @@ int gf2bv_solve_batch_digits(const uint32_t *digits, const int64_t *digit_off, i
 	// threads, as in gf2bv_solve_batch_device -- one gang's upload and pack run under the other's elimination, and two latency-bound
 	// gangs of sparse systems overlap; before: one upload of everything, then the gangs one after the other on one stream -- 16 MT19937
 	// recovery systems 43 ms, 15 of them the upload).  Every gang packs its own systems straight into tile-major slabs.
-	struct Staged {
-		i64 *off = nullptr; hipStream_t st = nullptr; hipEvent_t ready = nullptr; int device = 0;
-		~Staged()
-		{
-			if (st) (void)hipStreamSynchronize(st);
-			pool().release(off);
-			pool().release_event(ready, false);
-			if (st) pool().release_stream(st, device, 2);
-		}
-	} G;
-	G.device = device;
-	HIPCHK(pool().stream(&G.st, device, 2));
-	HIPCHK(pool().alloc((void **)&G.off, sizeof(i64) * (nrows_all + 1), device));
-	HIPCHK(hipMemcpyAsync(G.off, digit_off, sizeof(i64) * (nrows_all + 1), hipMemcpyHostToDevice, G.st));
-	HIPCHK(pool().event(&G.ready, false));
-	HIPCHK(hipEventRecord(G.ready, G.st));
+	Held G(device);
+	i64 *d_off = nullptr;
+	hipEvent_t ready = nullptr;
+	HIPCHK(G.stream(2));
+	HIPCHK(G.get((void **)&d_off, sizeof(i64) * (nrows_all + 1)));
+	HIPCHK(hipMemcpyAsync(d_off, digit_off, sizeof(i64) * (nrows_all + 1), hipMemcpyHostToDevice, G.st));
+	HIPCHK(G.event(&ready, false));
+	HIPCHK(hipEventRecord(ready, G.st));
 	const Knobs kn = Knobs::read();
 	const i64 gang = pick_gang(kn, nsys, rows, cols);
 	const i64 ngangs = (nsys + gang - 1) / gang;
 	i64 max_dig = 1;
 	for (i64 q = 0; q < ngangs; q++)
 		max_dig = std::max<i64>(max_dig, digit_off[std::min<i64>(nsys, (q + 1) * gang) * rows] - digit_off[q * gang * rows]);
-	return run_gangs(kn, device, nsys, gang, G.ready, sizeof(uint32_t) * max_dig, out, [&](Solver &S, i64 s0, int ns, void *buf) -> int {
+	return run_gangs(kn, device, nsys, gang, ready, sizeof(uint32_t) * max_dig, out, [&](Solver &S, i64 s0, int ns, void *buf) -> int {
 		uint32_t *dig = (uint32_t *)buf;
 		const i64 d0 = digit_off[s0 * rows], nd = digit_off[(s0 + ns) * rows] - d0;
 		if (nd) HIPCHK(hipMemcpyAsync(dig, digits + d0, sizeof(uint32_t) * nd, hipMemcpyHostToDevice, S.sA));
@@ -3168,7 +3183,7 @@ int gf2bv_solve_batch_digits(const uint32_t *digits, const int64_t *digit_off, i
 		HIPCHK(pool().alloc((void **)&S.M, sizeof(u64) * m_stride * S.nsys + kOuterSlackBytes, device));
 		if (rows * ntiles * TW > 0)
 			k_pack_digits<<<dim3((unsigned)((ntiles * TW + 255) / 256), (unsigned)std::min<i64>(rows, 65535), S.nsys), dim3(256), 0, S.sA>>>(
-				dig, G.off + s0 * rows, bits_per_digit, (i64)rows, (i64)cols, ntiles * TW, srows, S.M, SysStride{m_stride, 0}, d0);
+				dig, d_off + s0 * rows, bits_per_digit, (i64)rows, (i64)cols, ntiles * TW, srows, S.M, SysStride{m_stride, 0}, d0);
 		HIPCHK(hipGetLastError());
 		return GF2BV_OK;
 	});
@@ -3219,12 +3234,11 @@ int gf2bv_solve_digits(const uint32_t *digits, const int64_t *digit_off, int bit
 	const i64 ntiles = tiles_for((cols + 1 + 63) / 64), srows = slab_rows(rows);
 	S.stride = ntiles * TW;
 	HIPCHK(pool().alloc((void **)&S.M, sizeof(u64) * ntiles * TW * srows + kOuterSlackBytes, device));     // packed straight into tiles
-	Scratch scratch;                  // digits, offsets and the pack events go back to the pool on every path
-	scratch.sync_first = S.sA;
+	Held held(device, S.sA);                // digits, offsets and the pack events go back to the pool on every path
 	hipEvent_t p0, p1;
-	HIPCHK(scratch.event(&p0)); HIPCHK(scratch.event(&p1));
+	HIPCHK(held.event(&p0)); HIPCHK(held.event(&p1));
 	HIPCHK(hipEventRecord(p0, S.sA));
-	if ((rc = pack_coefficients(in, rows, cols, ntiles, srows, S.device, S.sA, scratch, S.M))) return rc;
+	if ((rc = pack_coefficients(in, rows, cols, ntiles, srows, S.sA, held, S.M))) return rc;
 	HIPCHK(hipEventRecord(p1, S.sA));
 	rc = solver_enqueue(S);
 	if (rc == GF2BV_OK) {
@@ -3894,9 +3908,9 @@ int gf2bv_lds_clock_device(int device, double *shader_mhz, double *lds_bytes_per
 	if (rc) return rc;
 	unsigned long long *d = nullptr, h[3] = { 0, 0, 0 };
 	unsigned *sink = nullptr;
-	struct Free { unsigned long long *&d; unsigned *&sink; ~Free() { pool().release(d); pool().release(sink); } } guard{ d, sink };     // (error paths too)
-	HIPCHK(pool().alloc((void **)&d, sizeof h, device));
-	HIPCHK(pool().alloc((void **)&sink, 64, device));
+	Held H(device, nullptr);                    // (the kernels run on the null stream)
+	HIPCHK(H.get((void **)&d, sizeof h));
+	HIPCHK(H.get((void **)&sink, 64));
 	int cus = 256;
 	(void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
 	k_lds_clock<<<dim3(cus), dim3(512)>>>(d, 2000, sink);                   // warm-up (clocks ramp)
@@ -4029,6 +4043,15 @@ int64_t gf2bv_pool_idle_bytes(int device)
 	if (bf != P.big_free.end()) for (const Pool::Big &b : bf->second) bytes += b.bytes;
 	for (auto &kv : P.free_bufs) if (kv.first.first == device) bytes += kv.first.second * kv.second.size();
 	return (int64_t)bytes;
+}
+int gf2bv_pool_in_use(int device, int64_t out[3])
+{
+	if (device < 0 || !out) return -1;
+	Pool &P = pool();
+	std::lock_guard<std::mutex> lk(P.mu);
+	out[0] = 0; out[1] = P.streams_out[device]; out[2] = P.events_out[device];
+	for (const auto *m : { &P.live, &P.big_live }) for (const auto &kv : *m) out[0] += kv.second.first == device;
+	return 0;
 }
 int gf2bv_device_free(int device, void *d_ptr)
 {
@@ -4369,33 +4392,30 @@ bool quad_point(const QuadPlan &P, const u64 *y, u64 *x, u64 *c_orig)
 	return true;
 }
 
-struct QDev {                                      // a pool buffer, released at scope end
-	void *p = nullptr;
-	~QDev() { pool().release(p); }
-	hipError_t get(size_t bytes, int device) { pool().release(p); p = nullptr; return pool().alloc(&p, bytes, device); }
-	template <class X> X *as() const { return static_cast<X *>(p); }
-};
+// a host vector into a buffer of the holder, on the holder's stream
+template <class T>
+hipError_t upload(Held &H, T **d, const std::vector<T> &h)
+{
+	const hipError_t e = H.get((void **)d, h.size() * sizeof(T));
+	return e != hipSuccess ? e : hipMemcpyAsync(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, H.st);
+}
 
 int quad_forms_device(QuadPlan &P, int device, hipStream_t st)
 {
 	const i64 r = P.r, W = P.W, cells = (r + 1) * W;
 	P.M.assign((size_t)(std::max<i64>(P.m0, 1) * cells), 0);
 	if (P.m0 == 0) return GF2BV_OK;
-	QDev dl, dq, dpi, dpj, dso, dsi, dout;
-	HIPCHK(dl.get(P.lin.size() * 8, device)); HIPCHK(dq.get(P.qaff.size() * 8, device));
-	HIPCHK(dpi.get(P.pair_i.size() * 4, device)); HIPCHK(dpj.get(P.pair_j.size() * 4, device));
-	HIPCHK(dso.get(P.sup_off.size() * 8, device)); HIPCHK(dsi.get(P.sup_idx.size() * 4, device));
-	HIPCHK(dout.get(P.M.size() * 8, device));
-	HIPCHK(hipMemcpyAsync(dl.p, P.lin.data(), P.lin.size() * 8, hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpyAsync(dq.p, P.qaff.data(), P.qaff.size() * 8, hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpyAsync(dpi.p, P.pair_i.data(), P.pair_i.size() * 4, hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpyAsync(dpj.p, P.pair_j.data(), P.pair_j.size() * 4, hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpyAsync(dso.p, P.sup_off.data(), P.sup_off.size() * 8, hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpyAsync(dsi.p, P.sup_idx.data(), P.sup_idx.size() * 4, hipMemcpyHostToDevice, st));
-	k_quad_forms<<<dim3((unsigned)P.m0), dim3(256), (size_t)cells * 8, st>>>(dl.as<u64>(), dq.as<u64>(), dpi.as<int>(), dpj.as<int>(),
-	                                                                         dso.as<i64>(), dsi.as<int>(), (int)r, (int)W, dout.as<u64>());
+	Held H(device, st);
+	u64 *dl, *dq, *dout;
+	int *dpi, *dpj, *dsi;
+	i64 *dso;
+	HIPCHK(upload(H, &dl, P.lin)); HIPCHK(upload(H, &dq, P.qaff));
+	HIPCHK(upload(H, &dpi, P.pair_i)); HIPCHK(upload(H, &dpj, P.pair_j));
+	HIPCHK(upload(H, &dso, P.sup_off)); HIPCHK(upload(H, &dsi, P.sup_idx));
+	HIPCHK(H.get((void **)&dout, P.M.size() * 8));
+	k_quad_forms<<<dim3((unsigned)P.m0), dim3(256), (size_t)cells * 8, st>>>(dl, dq, dpi, dpj, dso, dsi, (int)r, (int)W, dout);
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpyAsync(P.M.data(), dout.p, P.M.size() * 8, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipMemcpyAsync(P.M.data(), dout, P.M.size() * 8, hipMemcpyDeviceToHost, st));
 	HIPCHK(hipStreamSynchronize(st));
 	return GF2BV_OK;
 }
@@ -4451,36 +4471,35 @@ int search_two_pass(const SearchPasses &s, int device, hipStream_t st, std::vect
 	const u64 nlanes = 1ull << (R - L);
 	const dim3 grid((unsigned)((nlanes + s.block - 1) / s.block)), block(s.block);
 	const u64 ocap = (u64)kQuadMaxPoints, cap = (u64)kQuadMaxCand;
-	QDev dtab, dE, dcand, dcnt, dout;
-	HIPCHK(dtab.get(s.tab.size() * 8, device)); HIPCHK(dE.get(s.E.size() * 8, device)); HIPCHK(dcnt.get(16, device));
-	HIPCHK(hipMemcpyAsync(dtab.p, s.tab.data(), s.tab.size() * 8, hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpyAsync(dE.p, s.E.data(), s.E.size() * 8, hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemsetAsync(dcnt.p, 0, 16, st));
-	HIPCHK(dcand.get(cap * 8, device));
-	HIPCHK(dout.get(ocap * 8, device));
-	s.search<<<grid, block, s.lds, st>>>(dtab.as<u64>(), R, L, nlanes, dcand.as<u64>(), cap, dcnt.as<unsigned long long>(), nullptr, 0);
+	Held H(device, st);
+	u64 *dtab, *dE, *dcand, *dout;
+	unsigned long long *dcnt;
+	HIPCHK(upload(H, &dtab, s.tab)); HIPCHK(upload(H, &dE, s.E));
+	HIPCHK(H.get((void **)&dcnt, 16));
+	HIPCHK(hipMemsetAsync(dcnt, 0, 16, st));
+	HIPCHK(H.get((void **)&dcand, cap * 8));
+	HIPCHK(H.get((void **)&dout, ocap * 8));
+	s.search<<<grid, block, s.lds, st>>>(dtab, R, L, nlanes, dcand, cap, dcnt, nullptr, 0);
 	HIPCHK(hipGetLastError());
 	u64 cnt[2] = {0, 0};
-	HIPCHK(hipMemcpyAsync(cnt, dcnt.p, 8, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipMemcpyAsync(cnt, dcnt, 8, hipMemcpyDeviceToHost, st));
 	HIPCHK(hipStreamSynchronize(st));
 	s.times.candidates += (i64)cnt[0];
-	const void *found = dout.p;
+	const void *found = dout;
 	if (s.mE == 0) {
 		cnt[1] = cnt[0];                           // every form was in the first pass: its candidates are the zeros (cap == ocap)
-		found = dcand.p;
+		found = dcand;
 	} else if (cnt[0] > cap) {
 		// more candidates than can be kept: search again, each lane testing its candidates against the forms of E itself
-		s.search<<<grid, block, s.lds, st>>>(dtab.as<u64>(), R, L, nlanes, dout.as<u64>(), ocap, dcnt.as<unsigned long long>() + 1,
-		                                     dE.as<u64>(), s.mE);
+		s.search<<<grid, block, s.lds, st>>>(dtab, R, L, nlanes, dout, ocap, dcnt + 1, dE, s.mE);
 		HIPCHK(hipGetLastError());
 	} else if (cnt[0]) {
 		const u64 waves = std::min<u64>(cnt[0], 8192);
-		s.check<<<dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st>>>(dE.as<u64>(), s.mE, R, dcand.as<u64>(), cnt[0], dout.as<u64>(),
-		                                                               ocap, dcnt.as<unsigned long long>() + 1);
+		s.check<<<dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st>>>(dE, s.mE, R, dcand, cnt[0], dout, ocap, dcnt + 1);
 		HIPCHK(hipGetLastError());
 	}
 	if (s.mE) {
-		HIPCHK(hipMemcpyAsync(cnt + 1, dcnt.as<u64>() + 1, 8, hipMemcpyDeviceToHost, st));
+		HIPCHK(hipMemcpyAsync(cnt + 1, dcnt + 1, 8, hipMemcpyDeviceToHost, st));
 		HIPCHK(hipStreamSynchronize(st));
 	}
 	*total = cnt[1];
@@ -4619,22 +4638,22 @@ void quad_plan_export(const QuadPlan &P, int64_t *r, int64_t *r_eff, int64_t *m,
 
 // What gf2bv_quad_search_alloc and gf2bv_cubic_search_alloc do once their arguments are checked: the pool stream, `collect` (every
 // consistent point with its coefficients in the space's basis), AffineSpace order, the first max_solutions points in a malloc'ed buffer
-using CollectFn = std::function<int(hipStream_t, std::vector<u64> &, std::vector<u64> &, u64 *, bool *)>;
+// (collect: int(hipStream_t, std::vector<u64> &pts, std::vector<u64> &coef, u64 *total, bool *gave_up))
+template <class Collect>
 int search_alloc(QuadTimes &times, int64_t dimension, int64_t words, int64_t max_solutions, int device, int64_t *count, int64_t *lin_rank,
-                 uint64_t **out_words, const CollectFn &collect)
+                 uint64_t **out_words, Collect &&collect)
 {
 	*count = 0; *lin_rank = 0; *out_words = nullptr;
 	int rc = check_device(device);
 	if (rc) return rc;
 	times = QuadTimes();
 	const auto t0 = std::chrono::steady_clock::now();
-	hipStream_t st = nullptr;
-	HIPCHK(pool().stream(&st, device, 0));
-	std::unique_ptr<void, std::function<void(void *)>> keep(st, [&](void *) { pool().release_stream(st, device, 0); });
+	Held H(device);
+	HIPCHK(H.stream(0));
 	std::vector<u64> pts, coef;
 	u64 total = 0;
 	bool gave_up = false;
-	rc = collect(st, pts, coef, &total, &gave_up);
+	rc = collect(H.st, pts, coef, &total, &gave_up);
 	times.total = ms_since(t0);
 	if (rc) return rc;
 	if (gave_up) { *count = -1; return GF2BV_OK; }
@@ -4815,20 +4834,18 @@ int cubic_forms_device(const CubicPlan &P, ProductsKernel products, i64 fw, std:
 {
 	F.assign((size_t)(std::max<i64>(P.m0, 1) * fw), 0);
 	if (P.m0 == 0) return GF2BV_OK;
-	QDev dl, dq, dm, dso, dsi, dv, dout;
-	HIPCHK(dl.get(P.lin.size() * 8, device)); HIPCHK(dq.get(P.qaff.size() * 8, device)); HIPCHK(dm.get(P.mem.size() * 4, device));
-	HIPCHK(dso.get(P.sup_off.size() * 8, device)); HIPCHK(dsi.get(P.sup_idx.size() * 4, device));
-	HIPCHK(dv.get((size_t)(P.S * fw) * 8, device)); HIPCHK(dout.get((size_t)(P.m0 * fw) * 8, device));
-	HIPCHK(hipMemcpyAsync(dl.p, P.lin.data(), P.lin.size() * 8, hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpyAsync(dq.p, P.qaff.data(), P.qaff.size() * 8, hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpyAsync(dm.p, P.mem.data(), P.mem.size() * 4, hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpyAsync(dso.p, P.sup_off.data(), P.sup_off.size() * 8, hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpyAsync(dsi.p, P.sup_idx.data(), P.sup_idx.size() * 4, hipMemcpyHostToDevice, st));
-	products<<<dim3((unsigned)P.S), dim3(256), 0, st>>>(dl.as<u64>(), dq.as<u64>(), dm.as<int>(), (int)P.R, (int)P.W, (int)fw, dv.as<u64>());
+	Held H(device, st);
+	u64 *dl, *dq, *dv, *dout;
+	int *dm, *dsi;
+	i64 *dso;
+	HIPCHK(upload(H, &dl, P.lin)); HIPCHK(upload(H, &dq, P.qaff)); HIPCHK(upload(H, &dm, P.mem));
+	HIPCHK(upload(H, &dso, P.sup_off)); HIPCHK(upload(H, &dsi, P.sup_idx));
+	HIPCHK(H.get((void **)&dv, (size_t)(P.S * fw) * 8)); HIPCHK(H.get((void **)&dout, (size_t)(P.m0 * fw) * 8));
+	products<<<dim3((unsigned)P.S), dim3(256), 0, st>>>(dl, dq, dm, (int)P.R, (int)P.W, (int)fw, dv);
 	HIPCHK(hipGetLastError());
-	k_forms_sum<<<dim3((unsigned)P.m0), dim3(256), 0, st>>>(dv.as<u64>(), dso.as<i64>(), dsi.as<int>(), (int)fw, dout.as<u64>());
+	k_forms_sum<<<dim3((unsigned)P.m0), dim3(256), 0, st>>>(dv, dso, dsi, (int)fw, dout);
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpyAsync(F.data(), dout.p, (size_t)(P.m0 * fw) * 8, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipMemcpyAsync(F.data(), dout, (size_t)(P.m0 * fw) * 8, hipMemcpyDeviceToHost, st));
 	HIPCHK(hipStreamSynchronize(st));
 	return GF2BV_OK;
 }
@@ -5114,15 +5131,13 @@ int search_plan(const uint64_t *origin_, const uint64_t *basis_, int64_t dimensi
 	int rc = check_space<D>(origin, basis, dimension, words, n_lin);
 	if (rc) return rc;
 	if (!r || !r_eff || !m || !form_words) return fail(GF2BV_ERR_ARG, "null pointer");
-	hipStream_t st = nullptr;
-	std::unique_ptr<void, std::function<void(void *)>> keep(nullptr, [&](void *) { pool().release_stream(st, device, 0); });
+	Held H(device);
 	if (on_device) {
 		if ((rc = check_device(device))) return rc;
-		HIPCHK(pool().stream(&st, device, 0));
-		keep.reset(st);
+		HIPCHK(H.stream(0));
 	}
 	typename D::Plan P = D::plan();
-	rc = D::build(P, origin, basis, dimension, words, n_lin, device, st);
+	rc = D::build(P, origin, basis, dimension, words, n_lin, device, H.st);
 	if (rc) return rc;
 	quad_plan_export(P, r, r_eff, m, form_words, forms_, forms_cap);
 	return GF2BV_OK;
@@ -5161,12 +5176,11 @@ int search_forms(const uint64_t *forms_, int64_t m, int64_t r_eff, int device, i
 	*count = 0;
 	int rc = check_device(device);
 	if (rc) return rc;
-	hipStream_t st = nullptr;
-	HIPCHK(pool().stream(&st, device, 0));
-	std::unique_ptr<void, std::function<void(void *)>> keep(st, [&](void *) { pool().release_stream(st, device, 0); });
+	Held H(device);
+	HIPCHK(H.stream(0));
 	std::vector<u64> ys;
 	u64 total = 0;
-	rc = D::search(forms, m, (D::width(r_eff) + 63) / 64, (int)r_eff, device, st, ys, &total);
+	rc = D::search(forms, m, (D::width(r_eff) + 63) / 64, (int)r_eff, device, H.st, ys, &total);
 	if (rc) return rc;
 	*count = (int64_t)total;
 	if ((i64)total > kQuadMaxPoints && max_out > 0) return fail(GF2BV_ERR_NOMEM, "more common zeros than can be collected");
@@ -5703,19 +5717,11 @@ int enqueue_specialise(const GuessShape &s, const u64 *d_quad, i64 quad_stride, 
 // What one assignment's system holds on the device while a solve entry runs: its specialised rows and its padded expansion
 i64 guess_system_bytes(const XlShape &x) { return 8 * (x.m * round_up(x.wsrc(), 2) + x.rows * round_up(x.wt(), 2)); }
 
-struct PoolStream {                    // a stream of the pool for the length of an entry
-	hipStream_t st = nullptr;
-	int device = 0;
-	~PoolStream() { pool().release_stream(st, device, 0); }
-};
-
 // A factored system of host memory (checked) staged on the device for the length of an entry: the terms uploaded and expanded into
-// d_aug (q.rows x ds words a system) on ONE pool stream, where the entry underneath is ordered behind the expansion.  On every return
-// path the stream is synchronised before a buffer goes back to the pool (Scratch) and goes back itself after that (PoolStream:
-// declared first, destroyed last): a handle has its own copy by then, a result is on the host.
+// d_aug (q.rows x ds words a system) on ONE pool stream, where the entry underneath is ordered behind the expansion.  Stream and
+// buffers go back by the holder's rule: a handle has its own copy by then, a result is on the host.
 struct QuadStage {
-	PoolStream ps;
-	Scratch scratch;
+	Held held;
 	const bool nomem;                  // a refused pool buffer is GF2BV_ERR_NOMEM (the expanded rows of a large system or batch may not fit; an
 	                                   // append tells a refusal, which leaves the handle as it was, from a failure that does not); the two
 	                                   // first entries, gf2bv_quad_expand_words and gf2bv_solve_quad_terms, keep their GF2BV_ERR_HIP
@@ -5725,31 +5731,25 @@ struct QuadStage {
 	i64 xs = 0;
 	u64 *d_spec = nullptr;             // hybrid XL: the rows in d_aug specialised for na assignments (specialise), ss words a row, m x ss a system
 	i64 ss = 0;
-	explicit QuadStage(int device, bool nomem = true) : nomem(nomem) { ps.device = device; }
+	explicit QuadStage(int device, bool nomem = true) : held(device), nomem(nomem) {}
 
 	int open()                         // the stream, once
 	{
-		if (ps.st) return GF2BV_OK;
-		HIPCHK(pool().stream(&ps.st, ps.device, 0));
-		scratch.sync_first = ps.st;
+		if (!held.st) HIPCHK(held.stream(0));
 		return GF2BV_OK;
 	}
 
 	int alloc(void **out, size_t bytes)
 	{
-		const hipError_t e = scratch.alloc(out, bytes, ps.device);
-		if (e == hipErrorOutOfMemory && nomem) {
-			(void)hipGetLastError();
-			return fail(GF2BV_ERR_NOMEM, "the factored rows or their expansion do not fit on the device");
-		}
-		if (e != hipSuccess) return fail(GF2BV_ERR_HIP, "expansion buffers", e);
-		return GF2BV_OK;
+		if (nomem) return held.alloc(out, bytes, "the factored rows or their expansion do not fit on the device", "expansion buffers");
+		const hipError_t e = held.get(out, bytes);
+		return e == hipSuccess ? GF2BV_OK : fail(GF2BV_ERR_HIP, "expansion buffers", e);
 	}
 	template <class T>
 	int upload(T **d, const T *h, size_t bytes)
 	{
 		if (int rc = alloc((void **)d, bytes)) return rc;
-		if (bytes) HIPCHK(hipMemcpyAsync(*d, h, bytes, hipMemcpyHostToDevice, ps.st));
+		if (bytes) HIPCHK(hipMemcpyAsync(*d, h, bytes, hipMemcpyHostToDevice, held.st));
 		return GF2BV_OK;
 	}
 	// Upload of the term groups and expansion (the kernel of t.degree()), with rows `stride` words apart rounded up to an even `ds`; sys_off:
@@ -5773,8 +5773,8 @@ struct QuadStage {
 		if (!rc) rc = alloc((void **)&d_aug, sizeof(u64) * (size_t)(nsys * t.rows * ds));
 		if (!rc && rhs) rc = upload(&d_rhs, rhs, rhs_bytes);
 		if (rc) return rc;
-		if (sys_off) return enqueue_quad_expand_batch(t, d_sys, nsys, d_aug, ds, t.rows * ds, ps.st);
-		return enqueue_expand(t, d_aug, ds, ps.st);
+		if (sys_off) return enqueue_quad_expand_batch(t, d_sys, nsys, d_aug, ds, t.rows * ds, held.st);
+		return enqueue_expand(t, d_aug, ds, held.st);
 	}
 	// Quadratic rows that are expanded already (host memory, `stride` words apart) into d_aug as they are
 	int upload_rows(const u64 *quad, i64 m, i64 stride)
@@ -5789,14 +5789,14 @@ struct QuadStage {
 	{
 		xs = round_up(stride, 2);
 		if (int rc = alloc((void **)&d_xl, sizeof(u64) * (size_t)(x.rows * xs))) return rc;
-		return enqueue_xl_expand(x, d_aug, ds, d_xl, xs, ps.st);
+		return enqueue_xl_expand(x, d_aug, ds, d_xl, xs, held.st);
 	}
 	// The rows in d_aug specialised for every assignment of `g` into d_spec, rows `stride` words apart
 	int specialise(const GuessShape &g, i64 stride)
 	{
 		ss = stride;
 		if (int rc = alloc((void **)&d_spec, sizeof(u64) * (size_t)(g.na * g.m * ss))) return rc;
-		return enqueue_specialise(g, d_aug, ds, d_spec, ss, g.m * ss, ps.st);
+		return enqueue_specialise(g, d_aug, ds, d_spec, ss, g.m * ss, held.st);
 	}
 	// The XL expansions (x.degree, x.src) of nsys systems of x.m quadratic or cubic rows in d_spec (system s at s x spec_sys words) into d_xl, system s at
 	// s x x.rows x xs
@@ -5804,13 +5804,13 @@ struct QuadStage {
 	{
 		xs = round_up(stride, 2);
 		if (int rc = alloc((void **)&d_xl, sizeof(u64) * (size_t)(nsys * x.rows * xs))) return rc;
-		return enqueue_xl_expand_batch(x, d_spec, spec_sys, ss, nsys, d_xl, xs, x.rows * xs, ps.st);
+		return enqueue_xl_expand_batch(x, d_spec, spec_sys, ss, nsys, d_xl, xs, x.rows * xs, held.st);
 	}
 	// `nrows` rows of the expansion (`xl`: of the XL expansion) into host memory, `stride` words apart; the host waits
 	int download(void *out, i64 stride, i64 nrows, bool xl = false)
 	{
-		HIPCHK(hipMemcpy2DAsync(out, stride * 8, xl ? d_xl : d_aug, (xl ? xs : ds) * 8, stride * 8, nrows, hipMemcpyDeviceToHost, ps.st));
-		HIPCHK(hipStreamSynchronize(ps.st));
+		HIPCHK(hipMemcpy2DAsync(out, stride * 8, xl ? d_xl : d_aug, (xl ? xs : ds) * 8, stride * 8, nrows, hipMemcpyDeviceToHost, held.st));
+		HIPCHK(hipStreamSynchronize(held.st));
 		return GF2BV_OK;
 	}
 };
@@ -5836,7 +5836,7 @@ int solve_guess_staged(QuadStage &stage, const GuessShape &g, int mode, int devi
 	int rc = stage.specialise(g, round_up(g.x.wsrc(), 2));
 	if (!rc) rc = stage.expand_xl_batch(g.x, g.na, g.m * stage.ss, g.x.wt());
 	if (rc) return rc;
-	rc = gf2bv_solve_batch_device(stage.d_xl, g.na, g.x.rows * stage.xs, g.x.rows, g.x.cols(), stage.xs, mode, device, stage.ps.st, 0, out);
+	rc = gf2bv_solve_batch_device(stage.d_xl, g.na, g.x.rows * stage.xs, g.x.rows, g.x.cols(), stage.xs, mode, device, stage.held.st, 0, out);
 	if (rc)
 		for (i64 s = 0; s < g.na; s++) { gf2bv_result_free(out[s]); out[s] = nullptr; }
 	return rc;
@@ -5890,7 +5890,7 @@ static int solve_terms(const Terms &t, int mode, int device, gf2bv_result **out,
 	if (rc) return rc;
 	QuadStage stage(device, nomem);
 	if ((rc = stage.expand(t, t.wt()))) return rc;
-	return gf2bv_solve_device(stage.d_aug, t.rows, t.cols(), stage.ds, mode, device, stage.ps.st, 0, out);
+	return gf2bv_solve_device(stage.d_aug, t.rows, t.cols(), stage.ds, mode, device, stage.held.st, 0, out);
 	});
 }
 
@@ -5992,7 +5992,7 @@ int gf2bv_factor_quad_terms(const uint64_t *lin, const int64_t *term_off, const 
 	if (rc) return rc;
 	QuadStage stage(device);
 	if ((rc = stage.expand(q, q.wt()))) return rc;
-	return gf2bv_factor_device(stage.d_aug, rows, q.cols(), stage.ds, mode, device, stage.ps.st, out);
+	return gf2bv_factor_device(stage.d_aug, rows, q.cols(), stage.ds, mode, device, stage.held.st, out);
 	});
 }
 
@@ -6013,7 +6013,7 @@ int gf2bv_factor_append_quad_terms(gf2bv_factor *h, const uint64_t *lin, const i
 	// of them leaves the handle as it was)
 	QuadStage stage(h->device);
 	if ((rc = stage.expand(q, q.wt()))) return rc;
-	return gf2bv_factor_append_device(h, stage.d_aug, rows, stage.ds, stage.ps.st);
+	return gf2bv_factor_append_device(h, stage.d_aug, rows, stage.ds, stage.held.st);
 	});
 }
 
@@ -6033,7 +6033,7 @@ int gf2bv_solve_rhs_quad_terms(const uint64_t *lin, const int64_t *term_off, con
 	QuadStage stage(device);
 	if ((rc = stage.expand(q, q.wt(), nullptr, 1, reinterpret_cast<const u64 *>(rhs), sizeof(u64) * (size_t)(nrhs * rhs_words)))) return rc;
 	// (the constant the expansion leaves in column `cols` is ignored there: the caller's rhs holds the constants)
-	return gf2bv_solve_rhs_device(stage.d_aug, rows, q.cols(), stage.ds, stage.d_rhs, nrhs, rhs_words, mode, device, stage.ps.st, 0, out);
+	return gf2bv_solve_rhs_device(stage.d_aug, rows, q.cols(), stage.ds, stage.d_rhs, nrhs, rhs_words, mode, device, stage.held.st, 0, out);
 	});
 }
 
@@ -6074,7 +6074,7 @@ int gf2bv_solve_batch_quad_terms(const uint64_t *lin, const int64_t *term_off, c
 	QuadStage stage(device);
 	if ((rc = stage.expand(q, q.wt(), sys_off, nsys))) return rc;
 	// (the gangs run on streams of their own, behind an event gf2bv_solve_batch_device records on this one)
-	return gf2bv_solve_batch_device(stage.d_aug, nsys, rows * stage.ds, rows, q.cols(), stage.ds, mode, device, stage.ps.st, 0, out);
+	return gf2bv_solve_batch_device(stage.d_aug, nsys, rows * stage.ds, rows, q.cols(), stage.ds, mode, device, stage.held.st, 0, out);
 	});
 }
 
@@ -6128,7 +6128,7 @@ static int solve_xl_words(int degree, int src, const uint64_t *quad, int64_t m, 
 	QuadStage stage(device);
 	if ((rc = stage.upload_rows(reinterpret_cast<const u64 *>(quad), m, quad_stride_words))) return rc;
 	if ((rc = stage.expand_xl(x, x.wt()))) return rc;
-	return gf2bv_solve_device(stage.d_xl, x.rows, x.cols(), stage.xs, mode, device, stage.ps.st, 0, out);
+	return gf2bv_solve_device(stage.d_xl, x.rows, x.cols(), stage.xs, mode, device, stage.held.st, 0, out);
 	});
 }
 
@@ -6148,7 +6148,7 @@ static int solve_xl_terms(int degree, const Terms &t, int mode, int device, gf2b
 	QuadStage stage(device);
 	if ((rc = stage.expand(t, t.wt()))) return rc;
 	if ((rc = stage.expand_xl(x, x.wt()))) return rc;
-	return gf2bv_solve_device(stage.d_xl, x.rows, x.cols(), stage.xs, mode, device, stage.ps.st, 0, out);
+	return gf2bv_solve_device(stage.d_xl, x.rows, x.cols(), stage.xs, mode, device, stage.held.st, 0, out);
 	});
 }
 
@@ -6185,8 +6185,8 @@ static int specialise_words(int src, const uint64_t *quad, int64_t m, int64_t qu
 	QuadStage stage(device);
 	if ((rc = stage.upload_rows(reinterpret_cast<const u64 *>(quad), m, quad_stride_words))) return rc;
 	if ((rc = stage.specialise(g, out_stride_words))) return rc;          // (the caller's stride, odd or even: the rows come back as they are)
-	HIPCHK(hipMemcpyAsync(out, stage.d_spec, sizeof(u64) * (size_t)(na * m * out_stride_words), hipMemcpyDeviceToHost, stage.ps.st));
-	HIPCHK(hipStreamSynchronize(stage.ps.st));
+	HIPCHK(hipMemcpyAsync(out, stage.d_spec, sizeof(u64) * (size_t)(na * m * out_stride_words), hipMemcpyDeviceToHost, stage.held.st));
+	HIPCHK(hipStreamSynchronize(stage.held.st));
 	return GF2BV_OK;
 	});
 }
@@ -6225,12 +6225,12 @@ static int xl_expand_batch_words(int degree, int src, const uint64_t *quad, int6
 	                       m ? sizeof(u64) * (size_t)((nsys - 1) * quad_sys_stride_words + m * quad_stride_words) : 0))) return rc;
 	if ((rc = stage.expand_xl_batch(x, nsys, quad_sys_stride_words, stride_words))) return rc;
 	if (sys_stride_words == rows * stride_words)
-		HIPCHK(hipMemcpy2DAsync(out_aug, stride_words * 8, stage.d_xl, stage.xs * 8, stride_words * 8, nsys * rows, hipMemcpyDeviceToHost, stage.ps.st));
+		HIPCHK(hipMemcpy2DAsync(out_aug, stride_words * 8, stage.d_xl, stage.xs * 8, stride_words * 8, nsys * rows, hipMemcpyDeviceToHost, stage.held.st));
 	else
 		for (i64 s = 0; s < nsys; s++)
 			HIPCHK(hipMemcpy2DAsync(out_aug + s * sys_stride_words, stride_words * 8, stage.d_xl + s * rows * stage.xs, stage.xs * 8,
-			                        stride_words * 8, rows, hipMemcpyDeviceToHost, stage.ps.st));
-	HIPCHK(hipStreamSynchronize(stage.ps.st));
+			                        stride_words * 8, rows, hipMemcpyDeviceToHost, stage.held.st));
+	HIPCHK(hipStreamSynchronize(stage.held.st));
 	return GF2BV_OK;
 	});
 }
@@ -6536,30 +6536,22 @@ int enqueue_identity(u64 *d_out, i64 rows, i64 stride, i64 first, hipStream_t st
 	return GF2BV_OK;
 }
 
-// The buffers and the stream of an entry that stages: a refused buffer is GF2BV_ERR_NOMEM, and on every return path the stream is
-// synchronised before a buffer goes back to the pool (Scratch) and goes back itself after that (PoolStream: declared first)
+// The buffers and the stream of an entry that stages: a refused buffer is GF2BV_ERR_NOMEM, and everything goes back by the holder's rule
 struct ComposeStage {
-	PoolStream ps;
-	Scratch scratch;
-	hipStream_t st = nullptr;          // the pool's stream, or the caller's
+	Held held;                         // its stream: the pool's, or the caller's
 	hipEvent_t ev[4] = {};
-	int open(int device, hipStream_t given, bool own)
+	explicit ComposeStage(int device) : held(device) {}
+	int open(hipStream_t given, bool own)
 	{
-		ps.device = device;
-		if (own) { HIPCHK(pool().stream(&ps.st, device, 0)); st = ps.st; }
-		else st = given;
-		scratch.sync_first = st;
-		for (hipEvent_t &e : ev) HIPCHK(scratch.event(&e));
+		if (own) HIPCHK(held.stream(0)); else held.on(given);
+		for (hipEvent_t &e : ev) HIPCHK(held.event(&e));
 		return GF2BV_OK;
 	}
 	int alloc(u64 **out, i64 words)
 	{
-		const hipError_t e = scratch.alloc((void **)out, sizeof(u64) * (size_t)words, ps.device);
-		if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(GF2BV_ERR_NOMEM, "the forms, the images or the product do not fit on the device"); }
-		if (e != hipSuccess) return fail(GF2BV_ERR_HIP, "composition buffers", e);
-		return GF2BV_OK;
+		return held.alloc((void **)out, sizeof(u64) * (size_t)words, "the forms, the images or the product do not fit on the device", "composition buffers");
 	}
-	int mark(int i) { HIPCHK(hipEventRecord(ev[i], st)); return GF2BV_OK; }
+	int mark(int i) { HIPCHK(hipEventRecord(ev[i], held.st)); return GF2BV_OK; }
 	// after the stream has been synchronised: the times between the four marks
 	int times()
 	{
@@ -6670,19 +6662,19 @@ int gf2bv_compose_words(const uint64_t *a, int64_t ra, int64_t a_stride, int64_t
 	g_compose_times = ComposeTimes();
 	if (ra == 0) return GF2BV_OK;
 	const i64 das = round_up(wa, 2), dbs = round_up(wb, 2);
-	ComposeStage sg;
+	ComposeStage sg(device);
 	u64 *d_a = nullptr, *d_b = nullptr, *d_out = nullptr;
-	if ((rc = sg.open(device, nullptr, true))) return rc;
+	if ((rc = sg.open(nullptr, true))) return rc;
 	if ((rc = sg.alloc(&d_a, ra * das)) || (rc = sg.alloc(&d_b, n * dbs)) || (rc = sg.alloc(&d_out, ra * dbs))) return rc;
 	if ((rc = sg.mark(0))) return rc;
-	if ((rc = copy_rows(d_a, das, a, a_stride, wa, ra, hipMemcpyHostToDevice, sg.st))) return rc;
-	if ((rc = copy_rows(d_b, dbs, b, b_stride, wb, n, hipMemcpyHostToDevice, sg.st))) return rc;
+	if ((rc = copy_rows(d_a, das, a, a_stride, wa, ra, hipMemcpyHostToDevice, sg.held.st))) return rc;
+	if ((rc = copy_rows(d_b, dbs, b, b_stride, wb, n, hipMemcpyHostToDevice, sg.held.st))) return rc;
 	if ((rc = sg.mark(1))) return rc;
-	if ((rc = enqueue_compose(d_a, ra, das, n, d_b, dbs, nb, d_out, dbs, sg.st))) return rc;
+	if ((rc = enqueue_compose(d_a, ra, das, n, d_b, dbs, nb, d_out, dbs, sg.held.st))) return rc;
 	if ((rc = sg.mark(2))) return rc;
-	if ((rc = copy_rows(out, out_stride, d_out, dbs, wb, ra, hipMemcpyDeviceToHost, sg.st))) return rc;
+	if ((rc = copy_rows(out, out_stride, d_out, dbs, wb, ra, hipMemcpyDeviceToHost, sg.held.st))) return rc;
 	if ((rc = sg.mark(3))) return rc;
-	HIPCHK(hipStreamSynchronize(sg.st));
+	HIPCHK(hipStreamSynchronize(sg.held.st));
 	if (out_stride > wb)
 		for (i64 r = 0; r < ra; r++) memset(out + r * out_stride + wb, 0, sizeof(u64) * (size_t)(out_stride - wb));
 	return sg.times();
@@ -6700,16 +6692,16 @@ int gf2bv_compose_power_device(const void *d_b, int64_t b_stride, int64_t n, con
 	if (rc) return rc;
 	g_compose_times = ComposeTimes();
 	const i64 ws = round_up(form_words(n), 2);
-	ComposeStage sg;
+	ComposeStage sg(device);
 	u64 *base = nullptr, *cur = nullptr, *tmp = nullptr;
-	if ((rc = sg.open(device, (hipStream_t)stream, false))) return rc;
+	if ((rc = sg.open((hipStream_t)stream, false))) return rc;
 	if ((rc = sg.alloc(&base, (n + 1) * ws)) || (rc = sg.alloc(&cur, (n + 1) * ws)) || (rc = sg.alloc(&tmp, (n + 1) * ws))) return rc;
 	for (int i = 0; i < 2; i++) if ((rc = sg.mark(i))) return rc;
 	// (the map is copied: d_out may be d_b, and the caller's rows are not read after the copy)
-	if ((rc = copy_rows(base + ws, ws, d_b, b_stride, form_words(n), n, hipMemcpyDeviceToDevice, sg.st))) return rc;
-	if ((rc = enqueue_power(base + ws, ws, n, k_words, k_nwords, cur, tmp, ws, (u64 *)d_out, out_stride, sg.st))) return rc;
+	if ((rc = copy_rows(base + ws, ws, d_b, b_stride, form_words(n), n, hipMemcpyDeviceToDevice, sg.held.st))) return rc;
+	if ((rc = enqueue_power(base + ws, ws, n, k_words, k_nwords, cur, tmp, ws, (u64 *)d_out, out_stride, sg.held.st))) return rc;
 	for (int i = 2; i < 4; i++) if ((rc = sg.mark(i))) return rc;
-	HIPCHK(hipStreamSynchronize(sg.st));           // the three buffers go back to the pool: the host waits
+	HIPCHK(hipStreamSynchronize(sg.held.st));           // the three buffers go back to the pool: the host waits
 	return sg.times();
 	});
 }
@@ -6723,19 +6715,19 @@ int gf2bv_compose_power_words(const uint64_t *b, int64_t b_stride, int64_t n, co
 	if (rc) return rc;
 	g_compose_times = ComposeTimes();
 	const i64 w = form_words(n), ws = round_up(w, 2);
-	ComposeStage sg;
+	ComposeStage sg(device);
 	u64 *base = nullptr, *cur = nullptr, *tmp = nullptr;
 	const u64 *d_out = nullptr;
-	if ((rc = sg.open(device, nullptr, true))) return rc;
+	if ((rc = sg.open(nullptr, true))) return rc;
 	if ((rc = sg.alloc(&base, (n + 1) * ws)) || (rc = sg.alloc(&cur, (n + 1) * ws)) || (rc = sg.alloc(&tmp, (n + 1) * ws))) return rc;
 	if ((rc = sg.mark(0))) return rc;
-	if ((rc = copy_rows(base + ws, ws, b, b_stride, w, n, hipMemcpyHostToDevice, sg.st))) return rc;
+	if ((rc = copy_rows(base + ws, ws, b, b_stride, w, n, hipMemcpyHostToDevice, sg.held.st))) return rc;
 	if ((rc = sg.mark(1))) return rc;
-	if ((rc = enqueue_power(base + ws, ws, n, k_words, k_nwords, cur, tmp, ws, nullptr, 0, sg.st, &d_out))) return rc;
+	if ((rc = enqueue_power(base + ws, ws, n, k_words, k_nwords, cur, tmp, ws, nullptr, 0, sg.held.st, &d_out))) return rc;
 	if ((rc = sg.mark(2))) return rc;
-	if ((rc = copy_rows(out, out_stride, d_out, ws, w, n, hipMemcpyDeviceToHost, sg.st))) return rc;
+	if ((rc = copy_rows(out, out_stride, d_out, ws, w, n, hipMemcpyDeviceToHost, sg.held.st))) return rc;
 	if ((rc = sg.mark(3))) return rc;
-	HIPCHK(hipStreamSynchronize(sg.st));
+	HIPCHK(hipStreamSynchronize(sg.held.st));
 	if (out_stride > w)
 		for (i64 r = 0; r < n; r++) memset(out + r * out_stride + w, 0, sizeof(u64) * (size_t)(out_stride - w));
 	return sg.times();

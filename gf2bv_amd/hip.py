@@ -61,7 +61,7 @@ EXPORTS = [
     "gf2bv_synth_device", "gf2bv_residual_device",
     "gf2bv_stream_ceiling_device", "gf2bv_lds_clock_device", "gf2bv_kernel_resources",
     "gf2bv_device_alloc", "gf2bv_device_free", "gf2bv_device_upload", "gf2bv_device_download",
-    "gf2bv_pool_trim", "gf2bv_pool_idle_bytes", "gf2bv_host_alloc", "gf2bv_host_free", "gf2bv_host_pool_trim", "gf2bv_plan_gang",
+    "gf2bv_pool_trim", "gf2bv_pool_idle_bytes", "gf2bv_pool_in_use", "gf2bv_host_alloc", "gf2bv_host_free", "gf2bv_host_pool_trim", "gf2bv_plan_gang",
     "gf2bv_knob_dump",
 ]
 
@@ -274,6 +274,7 @@ def lib():
         L.gf2bv_pool_trim.restype = i64
         L.gf2bv_pool_idle_bytes.argtypes = [i32]
         L.gf2bv_pool_idle_bytes.restype = i64
+        L.gf2bv_pool_in_use.argtypes = [i32, ctypes.POINTER(i64)]
         _lib = L
     return _lib
 
@@ -1501,6 +1502,15 @@ def host_pool_trim() -> int:
 def pool_idle_bytes(device: int = 0) -> int:
     """Bytes of idle buffers the pool keeps on `device` right now."""
     return int(lib().gf2bv_pool_idle_bytes(device))
+
+
+def pool_in_use(device: int = 0) -> dict:
+    """What the pool has handed out on `device` and not yet got back (gf2bv_pool_in_use): {"buffers", "streams", "events"}.
+    Between calls these count only what kept handles own.  No GPU needed."""
+    out = (ctypes.c_int64 * 3)()
+    if lib().gf2bv_pool_in_use(device, out) != 0:
+        raise ValueError("device must not be negative")
+    return {"buffers": int(out[0]), "streams": int(out[1]), "events": int(out[2])}
 
 
 class DeviceBuffer:

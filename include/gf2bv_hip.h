@@ -885,6 +885,11 @@ int64_t gf2bv_host_pool_trim(void);
 int64_t gf2bv_pool_trim(int device);
 /* Bytes of idle buffers the pool currently keeps on `device` (what gf2bv_pool_trim would free). */
 int64_t gf2bv_pool_idle_bytes(int device);
+/* What the pool has handed out on `device` and not yet got back: out[0] buffers, out[1] streams, out[2] events.  An entry gives back
+ * everything it took before it returns, so between calls these count only what kept handles (gf2bv_factor, gf2bv_space, gf2bv_slab)
+ * own; while another thread is inside the library they are a snapshot of its work.  Returns 0, or -1 for device < 0 or a null
+ * `out`; no device is touched. */
+int gf2bv_pool_in_use(int device, int64_t out[3]);
 /* The gang size gf2bv_solve_batch_* would choose for `nsys` systems of rows x cols with `free_bytes` of device memory free: a pure
  * function, no device is touched (bench.py --dry-run-ranks: every rank's plan of the multi-GPU batch job, testable without GPUs). */
 int64_t gf2bv_plan_gang(int64_t nsys, int64_t rows, int64_t cols, int64_t free_bytes);

@@ -236,6 +236,11 @@ def test_round5_entry_points_without_a_device():
         p = ctypes.c_void_p()
         assert L.gf2bv_host_alloc(1 << 20, ctypes.byref(p)) == 2 and not p.value
     assert L.gf2bv_pool_idle_bytes(-1) == -1
+    out = (ctypes.c_int64 * 3)(7, 7, 7)
+    assert L.gf2bv_pool_in_use(-1, out) == -1 and L.gf2bv_pool_in_use(0, None) == -1 and list(out) == [7, 7, 7]
+    if hip.device_count() == 0:                    # (nothing has been handed out where there is no device)
+        assert L.gf2bv_pool_in_use(0, out) == 0 and list(out) == [0, 0, 0]
+        assert hip.pool_in_use(0) == {"buffers": 0, "streams": 0, "events": 0}
     L.gf2bv_host_free(None)
     assert L.gf2bv_host_pool_trim() >= 0
     from oracle import gf2_oracle as O
