@@ -21,7 +21,7 @@ def __getattr__(name):
         import importlib
         mod = importlib.import_module(".packed", __name__)
         return mod if name == "packed" else getattr(mod, name)
-    if name in ("substitute", "power", "compose"):         # (on PackedBitVecs: numpy as well)
+    if name in ("substitute", "power", "unroll", "compose"):         # (on PackedBitVecs: numpy as well)
         import importlib
         mod = importlib.import_module(".compose", __name__)
         return mod if name == "compose" else getattr(mod, name)
@@ -34,5 +34,5 @@ __all__ = [
     "PackedQuadBitVec", "PackedQuadraticSystem", "PackedQuarticBitVec", "PackedQuarticSystem", "QuadraticSystem", "Zeros",
     "eqs_to_sage_mat_helper", "m4ri_solve", "mul_bit_quad", "power", "search_all_cubic", "search_all_quartic", "search_all_xl",
     "search_all_xl4", "search_one_cubic", "search_one_quartic", "search_one_xl", "search_one_xl4", "substitute",
-    "to_bits", "tuple_where", "xor_tuple",
+    "to_bits", "tuple_where", "unroll", "xor_tuple",
 ]

@@ -14,7 +14,7 @@ from typing import Sequence
 
 import numpy as np
 
-from ._internal import m4ri_compose_packed, m4ri_power_packed
+from ._internal import m4ri_compose_packed, m4ri_power_packed, m4ri_unroll_packed
 from .bitvec import BitVec
 from .packed import PackedBitVec, _TermsBitVec
 
@@ -91,3 +91,31 @@ def power(images: Sequence, k: int, device=None) -> tuple:
     args = (b, n, kw) + (() if device is None else (device,))
     rows = np.frombuffer(m4ri_power_packed(*args), dtype=np.uint64).reshape(n, b.shape[1])
     return _split(rows, widths)
+
+
+def unroll(exprs, images: Sequence, count: int, *, start: int = 0, step: int = 1, device=None) -> list:
+    """The bits ``exprs`` (a PackedBitVec or a sequence of them, over the n unknowns of the self-map ``images``) watched while the model
+    steps: a list of ``count`` items, item i = ``substitute(exprs, power(images, start + i * step))`` with the structure of ``exprs`` -- the
+    whole "step the symbolic model, read the taps" loop as ceil(log2 count) doublings on the device.  The items are views into one array."""
+    single = isinstance(exprs, (BitVec, _TermsBitVec))
+    eparts = [_rows_of(v, "exprs") for v in ((exprs,) if single else exprs)]
+    _, b = _image_rows(images)
+    n, w = len(b), b.shape[1]
+    if w != (n + 1 + 63) // 64:
+        raise ValueError(f"unroll needs a square map: {n} image bits are over forms of {w} words, not of {(n + 1 + 63) // 64}")
+    for p in eparts:
+        if p.shape[1] != w:
+            raise ValueError(f"exprs are {p.shape[1]} words wide, forms over the {n} unknowns that images replace are {w}")
+    count, start, step = int(count), int(start), int(step)
+    if count < 0 or start < 0:
+        raise ValueError("count and start of unroll must not be negative")
+    if step < 1:
+        raise ValueError("step of unroll must be at least 1")
+    if count == 0:
+        return []
+    ewidths = [len(p) for p in eparts]
+    a = np.ascontiguousarray(np.concatenate(eparts)) if eparts else np.zeros((0, w), dtype=np.uint64)
+    args = (a, len(a), n, b, _exponent_words(start), _exponent_words(step), count) + (() if device is None else (device,))
+    rows = np.frombuffer(m4ri_unroll_packed(*args), dtype=np.uint64).reshape(count, len(a), w)
+    items = [_split(rows[i], ewidths) for i in range(count)]
+    return [it[0] for it in items] if single else items

@@ -1968,6 +1968,34 @@ PyObject *py_m4ri_power_packed(PyObject *, PyObject *const *args, Py_ssize_t nar
 	});
 }
 
+// m4ri_unroll_packed(a, ra, n, b, start_words, step_words, count[, device]) -> bytearray: the forms `a` (ra x ceil((n + 1) / 64) words)
+// watched while the self-map `b` steps -- count x ra rows, time-major, row i x ra + r = a[r] with b substituted start + i x step times
+// (gf2bv_compose_unroll_words); start and step are buffers of little-endian 64-bit words, at least one each.
+PyObject *py_m4ri_unroll_packed(PyObject *, PyObject *const *args, Py_ssize_t nargs)
+{
+	int device;
+	if (!entry_device("m4ri_unroll_packed", 7, args, nargs, &device)) return nullptr;
+	const Py_ssize_t ra = PyLong_AsSsize_t(args[1]), n = PyLong_AsSsize_t(args[2]), count = PyLong_AsSsize_t(args[6]);
+	if (PyErr_Occurred()) return nullptr;
+	HeldBuffer a, b, start, step;
+	if (!packed_forms(a, args[0], ra, n, "a") || !packed_forms(b, args[3], n, n, "b")) return nullptr;
+	if (!start.take(args[4], PyBUF_C_CONTIGUOUS) || !step.take(args[5], PyBUF_C_CONTIGUOUS)) return nullptr;
+	if (start.view.len < 8 || start.view.len % 8 || step.view.len < 8 || step.view.len % 8) {
+		PyErr_SetString(PyExc_ValueError, "start and step must hold at least one 64-bit word each");
+		return nullptr;
+	}
+	const Py_ssize_t w = (n + 64) / 64;
+	if (count < 0 || (ra > 0 && count > PY_SSIZE_T_MAX / 8 / w / ra)) { PyErr_SetString(PyExc_ValueError, "count must not be negative, and count x ra rows must fit in memory"); return nullptr; }
+	static const uint64_t none = 0;               // (no rows: the library still wants a pointer)
+	const bool empty = ra == 0 || count == 0;
+	return composed_rows("unrolling", count * ra, w, [&](uint64_t *dst) {
+		return gf2bv_compose_unroll_words(ra ? static_cast<const uint64_t *>(a.view.buf) : &none, ra, w, n, static_cast<const uint64_t *>(b.view.buf), w,
+		                                  static_cast<const uint64_t *>(start.view.buf), start.view.len / 8,
+		                                  static_cast<const uint64_t *>(step.view.buf), step.view.len / 8, count,
+		                                  empty ? const_cast<uint64_t *>(&none) : dst, w, device);
+	});
+}
+
 PyObject *py_device_count(PyObject *, PyObject *) { return PyLong_FromLong(gf2bv_device_count()); }
 PyObject *py_get_default_device(PyObject *, PyObject *) { return PyLong_FromLong(default_device()); }
 PyObject *py_set_default_device(PyObject *, PyObject *arg)
@@ -1996,6 +2024,8 @@ PyMethodDef module_methods[] = {
 	 "m4ri_compose_packed(a, ra, n, b, nb, device=None)\n--\n\nThe packed forms a (ra rows over n unknowns) with the packed images b (n rows over nb unknowns) substituted on the GPU: a bytearray of ra x ceil((nb + 1) / 64) 64-bit words."},
 	{"m4ri_power_packed", FAST(py_m4ri_power_packed), METH_FASTCALL,
 	 "m4ri_power_packed(b, n, k, device=None)\n--\n\nThe packed self-map b (n rows over n unknowns) substituted into itself k times (k: little-endian 64-bit words) by square-and-multiply on the GPU: a bytearray of n x ceil((n + 1) / 64) words."},
+	{"m4ri_unroll_packed", FAST(py_m4ri_unroll_packed), METH_FASTCALL,
+	 "m4ri_unroll_packed(a, ra, n, b, start_words, step_words, count, device=None)\n--\n\nThe packed forms a (ra rows over n unknowns) watched while the packed self-map b steps on the GPU: a bytearray of count x ra x ceil((n + 1) / 64) words, time-major -- row i x ra + r is a[r] with b substituted start + i x step times (start, step: little-endian 64-bit words)."},
 	{"m4ri_solve_quad_packed", FAST(py_m4ri_solve_quad_packed), METH_FASTCALL,
 	 "m4ri_solve_quad_packed(lin, term_off, ta, tb, n_lin, rows, mode, device=None)\n--\n\nm4ri_solve on a quadratic system kept factored (linear forms and products of two linear forms, packed 64-bit words): expanded into the linearised matrix on the GPU."},
 	{"m4ri_solve_xl3", FAST(py_m4ri_solve_xl<3>), METH_FASTCALL,

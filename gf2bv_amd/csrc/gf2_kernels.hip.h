@@ -6420,3 +6420,14 @@ __global__ void k_compose_identity(u64 *__restrict__ out, i64 rows, i64 stride, 
 		out[i] = (bit >> 6) == w ? 1ull << (bit & 63) : 0ull;
 	}
 }
+
+// `rows` forms over n unknowns copied from src to dst (dst_stride words apart) as a product with the identity map would leave them:
+// the bits above n cleared, the words from ceil((n + 1) / 64) up to the stride zero.  src is read below its form width only.
+__global__ void k_compose_copy(const u64 *__restrict__ src, i64 src_stride, u64 *__restrict__ dst, i64 dst_stride, i64 rows, i64 n)
+{
+	const i64 total = rows * dst_stride, wf = (n + 1 + 63) >> 6;
+	for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (i64)gridDim.x * blockDim.x) {
+		const i64 r = i / dst_stride, w = i % dst_stride;
+		dst[i] = w < wf ? src[r * src_stride + w] & cmp_word_mask(w, n + 1) : 0ull;
+	}
+}

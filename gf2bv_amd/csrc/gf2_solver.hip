@@ -6615,6 +6615,86 @@ int check_power(const void *b, i64 b_stride, i64 n, const uint64_t *k, i64 knw, 
 	return GF2BV_OK;
 }
 
+bool words_are_zero(const uint64_t *k, i64 knw)
+{
+	for (i64 i = 0; i < knw; i++) if (k[i]) return false;
+	return true;
+}
+
+// the time steps of the largest block of the doubling schedule: block h holds min(h, count - h) of them
+i64 unroll_largest_block(i64 count)
+{
+	i64 big = count > 0 ? 1 : 0;
+	for (i64 h = 1; h < count; h *= 2) big = std::max(big, std::min(h, count - h));
+	return big;
+}
+
+int check_unroll(const void *a, i64 ra, i64 a_stride, i64 n, const void *b, i64 b_stride, const uint64_t *start, i64 snw, const uint64_t *step,
+                 i64 pnw, i64 count, const void *out, i64 out_stride)
+{
+	if (!a || !b || !start || !step || !out) return fail(GF2BV_ERR_ARG, "null pointer");
+	if (count < 0) return fail(GF2BV_ERR_ARG, "count must not be negative");
+	if (snw < 1 || pnw < 1) return fail(GF2BV_ERR_ARG, "start_nwords and step_nwords must be at least 1");
+	if (int rc = check_compose(ra, n, n)) return rc;
+	if (int rc = check_compose(n + 1, n, n)) return rc;
+	if (words_are_zero(step, pnw)) return fail(GF2BV_ERR_ARG, "step must be at least 1");
+	if (a_stride < form_words(n) || b_stride < form_words(n) || out_stride < form_words(n)) return fail(GF2BV_ERR_ARG, "a stride does not cover n + 1 bits");
+	if (ra > 0 && count > 0) {
+		// the products read and write blocks of whole time steps: the largest one has to be a legal product, and the rows one allocation
+		if (count > (1ll << 62) / ra) return fail(GF2BV_ERR_ARG, "count x ra is beyond what one product can take");
+		if (int rc = check_compose(unroll_largest_block(count) * ra, n, n)) return rc;
+		if (count * ra > (1ll << 59) / out_stride) return fail(GF2BV_ERR_ARG, "count x ra rows of out_stride words are beyond the address space");
+	}
+	return GF2BV_OK;
+}
+
+int enqueue_copy(const u64 *d_src, i64 src_stride, u64 *d_dst, i64 dst_stride, i64 rows, i64 n, hipStream_t st)
+{
+	if (rows == 0) return GF2BV_OK;
+	const unsigned blocks = (unsigned)std::min<i64>((rows * dst_stride + 255) / 256, 4096);
+	hipLaunchKernelGGL(k_compose_copy, dim3(blocks), dim3(256), 0, st, d_src, src_stride, d_dst, dst_stride, rows, n);
+	HIPCHK(hipGetLastError());
+	return GF2BV_OK;
+}
+
+// The unrolling schedule on `st`, everything resident (device pointers, already checked; ra >= 1, count >= 1).  base, cur, tmp: power's
+// three (n + 1) x ws buffers, the map's n rows at base + ws.  d_out: count x ra rows, os words apart, time-major.
+//   block 0 = a o b^start: start = 0 a masked copy of a (no product); otherwise b^start by enqueue_power and one product.  It comes
+//     first because enqueue_power needs both work buffers beside the base, and the step map below stays in one of them;
+//   S = b^step by enqueue_power (step = 1: b where it lies, no product);
+//   doubling, P = S, h = 1: rows of the times [h, min(2h, count)) = rows of the times [0, min(h, count - h)) o P, read from and written
+//     to d_out -- a block is whole time steps, so the rows of a product land time-major where they belong and nothing is reordered --
+//     then P = P o P into a buffer that P is not in, unless this was the last block.
+// The product kernel zeroes the words between a row's last tile and its stride, the copy kernel does the same.
+int enqueue_unroll(const u64 *d_a, i64 ra, i64 as, i64 n, u64 *base, u64 *cur, u64 *tmp, i64 ws, const uint64_t *start, i64 snw,
+                   const uint64_t *step, i64 pnw, i64 count, u64 *d_out, i64 os, hipStream_t st)
+{
+	int rc;
+	if (words_are_zero(start, snw)) { if ((rc = enqueue_copy(d_a, as, d_out, os, ra, n, st))) return rc; }
+	else {
+		const u64 *at = nullptr;
+		if ((rc = enqueue_power(base + ws, ws, n, start, snw, cur, tmp, ws, nullptr, 0, st, &at))) return rc;
+		if ((rc = enqueue_compose(d_a, ra, as, n, at, ws, n, d_out, os, st))) return rc;
+	}
+	const u64 *P = base + ws;
+	u64 *other = cur;                              // a buffer that P is not in
+	const bool unit_step = step[0] == 1 && words_are_zero(step + 1, pnw - 1);
+	if (!unit_step) {
+		if ((rc = enqueue_power(base + ws, ws, n, step, pnw, cur, tmp, ws, nullptr, 0, st, &P))) return rc;
+		other = P == cur + ws ? tmp : cur;
+	}
+	for (i64 h = 1; h < count; h *= 2) {
+		const i64 steps = std::min(h, count - h);
+		if ((rc = enqueue_compose(d_out, steps * ra, os, n, P, ws, n, d_out + h * ra * os, os, st))) return rc;
+		if (2 * h >= count) break;
+		if ((rc = enqueue_compose(P, n, ws, n, P, ws, n, other + ws, ws, st))) return rc;
+		u64 *was = const_cast<u64 *>(P) - ws;
+		P = other + ws;
+		other = was;
+	}
+	return GF2BV_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -6730,6 +6810,66 @@ int gf2bv_compose_power_words(const uint64_t *b, int64_t b_stride, int64_t n, co
 	HIPCHK(hipStreamSynchronize(sg.held.st));
 	if (out_stride > w)
 		for (i64 r = 0; r < n; r++) memset(out + r * out_stride + w, 0, sizeof(u64) * (size_t)(out_stride - w));
+	return sg.times();
+	});
+}
+
+int gf2bv_compose_unroll_device(const void *d_a, int64_t ra, int64_t a_stride, int64_t n, const void *d_b, int64_t b_stride,
+                                const uint64_t *start_words, int64_t start_nwords, const uint64_t *step_words, int64_t step_nwords,
+                                int64_t count, void *d_out, int64_t out_stride, int device, void *stream)
+{
+	return catching([&]() -> int {
+	int rc = check_unroll(d_a, ra, a_stride, n, d_b, b_stride, start_words, start_nwords, step_words, step_nwords, count, d_out, out_stride);
+	if (!rc) rc = check_device_rows(d_a, a_stride, form_words(n), "d_a needs 16-byte alignment and an even a_stride covering n + 1 bits");
+	if (!rc) rc = check_device_rows(d_b, b_stride, form_words(n), "d_b needs 16-byte alignment and an even b_stride covering n + 1 bits");
+	if (!rc) rc = check_device_rows(d_out, out_stride, form_words(n), "d_out needs 16-byte alignment and an even out_stride covering n + 1 bits");
+	if (!rc) rc = check_device(device);
+	if (rc) return rc;
+	g_compose_times = ComposeTimes();
+	if (ra == 0 || count == 0) return GF2BV_OK;
+	const i64 ws = round_up(form_words(n), 2);
+	ComposeStage sg(device);
+	u64 *base = nullptr, *cur = nullptr, *tmp = nullptr;
+	if ((rc = sg.open((hipStream_t)stream, false))) return rc;
+	if ((rc = sg.alloc(&base, (n + 1) * ws)) || (rc = sg.alloc(&cur, (n + 1) * ws)) || (rc = sg.alloc(&tmp, (n + 1) * ws))) return rc;
+	for (int i = 0; i < 2; i++) if ((rc = sg.mark(i))) return rc;
+	// (the map is copied before anything else: the caller's rows are not read after the copy)
+	if ((rc = copy_rows(base + ws, ws, d_b, b_stride, form_words(n), n, hipMemcpyDeviceToDevice, sg.held.st))) return rc;
+	if ((rc = enqueue_unroll((const u64 *)d_a, ra, a_stride, n, base, cur, tmp, ws, start_words, start_nwords, step_words, step_nwords, count,
+	                         (u64 *)d_out, out_stride, sg.held.st))) return rc;
+	for (int i = 2; i < 4; i++) if ((rc = sg.mark(i))) return rc;
+	HIPCHK(hipStreamSynchronize(sg.held.st));           // the three buffers go back to the pool: the host waits
+	return sg.times();
+	});
+}
+
+int gf2bv_compose_unroll_words(const uint64_t *a, int64_t ra, int64_t a_stride, int64_t n, const uint64_t *b, int64_t b_stride,
+                               const uint64_t *start_words, int64_t start_nwords, const uint64_t *step_words, int64_t step_nwords,
+                               int64_t count, uint64_t *out, int64_t out_stride, int device)
+{
+	return catching([&]() -> int {
+	int rc = check_unroll(a, ra, a_stride, n, b, b_stride, start_words, start_nwords, step_words, step_nwords, count, out, out_stride);
+	if (!rc) rc = check_device(device);
+	if (rc) return rc;
+	g_compose_times = ComposeTimes();
+	if (ra == 0 || count == 0) return GF2BV_OK;
+	const i64 w = form_words(n), ws = round_up(w, 2), rows = count * ra;
+	ComposeStage sg(device);
+	u64 *base = nullptr, *cur = nullptr, *tmp = nullptr, *d_a = nullptr, *d_out = nullptr;
+	if ((rc = sg.open(nullptr, true))) return rc;
+	if ((rc = sg.alloc(&base, (n + 1) * ws)) || (rc = sg.alloc(&cur, (n + 1) * ws)) || (rc = sg.alloc(&tmp, (n + 1) * ws))) return rc;
+	if ((rc = sg.alloc(&d_a, ra * ws)) || (rc = sg.alloc(&d_out, rows * ws))) return rc;
+	if ((rc = sg.mark(0))) return rc;
+	if ((rc = copy_rows(base + ws, ws, b, b_stride, w, n, hipMemcpyHostToDevice, sg.held.st))) return rc;
+	if ((rc = copy_rows(d_a, ws, a, a_stride, w, ra, hipMemcpyHostToDevice, sg.held.st))) return rc;
+	if ((rc = sg.mark(1))) return rc;
+	if ((rc = enqueue_unroll(d_a, ra, ws, n, base, cur, tmp, ws, start_words, start_nwords, step_words, step_nwords, count, d_out, ws, sg.held.st))) return rc;
+	if ((rc = sg.mark(2))) return rc;
+	if ((rc = copy_rows(out, out_stride, d_out, ws, w, rows, hipMemcpyDeviceToHost, sg.held.st))) return rc;
+	if ((rc = sg.mark(3))) return rc;
+	HIPCHK(hipStreamSynchronize(sg.held.st));
+	if (out_stride > w)
+		for (i64 r = 0; r < rows; r++) memset(out + r * out_stride + w, 0, sizeof(u64) * (size_t)(out_stride - w));
 	return sg.times();
 	});
 }

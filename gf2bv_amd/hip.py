@@ -57,7 +57,7 @@ EXPORTS = [
     "gf2bv_slab_finish_local", "gf2bv_slab_solve",
     "gf2bv_slab_close",
     "gf2bv_compose_words", "gf2bv_compose_device", "gf2bv_compose_power_words", "gf2bv_compose_power_device", "gf2bv_compose_shape",
-    "gf2bv_compose_last_times",
+    "gf2bv_compose_last_times", "gf2bv_compose_unroll_words", "gf2bv_compose_unroll_device",
     "gf2bv_synth_device", "gf2bv_residual_device",
     "gf2bv_stream_ceiling_device", "gf2bv_lds_clock_device", "gf2bv_kernel_resources",
     "gf2bv_device_alloc", "gf2bv_device_free", "gf2bv_device_upload", "gf2bv_device_download",
@@ -250,6 +250,8 @@ def lib():
         L.gf2bv_compose_device.argtypes = [vp, i64, i64, i64, vp, i64, i64, vp, i64, i32, vp]
         L.gf2bv_compose_power_words.argtypes = [vp, i64, i64, vp, i64, vp, i64, i32]
         L.gf2bv_compose_power_device.argtypes = [vp, i64, i64, vp, i64, vp, i64, i32, vp]
+        L.gf2bv_compose_unroll_words.argtypes = [vp, i64, i64, i64, vp, i64, vp, i64, vp, i64, i64, vp, i64, i32]
+        L.gf2bv_compose_unroll_device.argtypes = [vp, i64, i64, i64, vp, i64, vp, i64, vp, i64, i64, vp, i64, i32, vp]
         L.gf2bv_compose_shape.argtypes = [vp]
         L.gf2bv_compose_last_times.argtypes = [vp]
         L.gf2bv_compose_last_times.restype = None
@@ -941,6 +943,33 @@ def compose_power_device(d_b: int, b_stride: int, n: int, k: int, d_out: int, ou
     the pool); d_out may be d_b."""
     kw = exponent_words(k)
     _check(lib().gf2bv_compose_power_device(d_b, b_stride, n, kw.ctypes.data, len(kw), d_out, out_stride, device, stream or None))
+
+
+def compose_unroll_words(a, n: int, b, count: int, start: int = 0, step: int = 1, stride_words: int | None = None,
+                         device: int = 0) -> np.ndarray:
+    """The forms a ([ra, >= ceil((n + 1) / 64)] uint64) watched while the self-map b ([n, >= ceil((n + 1) / 64)]) steps on the device:
+    [count * ra, stride_words] uint64, time-major -- row i * ra + r is a[r] with b substituted start + i * step times
+    (gf2bv_compose_unroll_words)."""
+    a, b = _forms(a, n, "a"), _forms(b, n, "b")
+    if len(b) != n:
+        raise ValueError("b needs one image row per unknown")
+    sw, pw = exponent_words(start), exponent_words(step)
+    stride = form_words(n) if stride_words is None else stride_words
+    out = np.empty((max(count, 0) * len(a), max(stride, 0)), dtype=np.uint64)
+    # (no rows: the library still wants pointers)
+    _check(lib().gf2bv_compose_unroll_words(a.ctypes.data if len(a) else b.ctypes.data, len(a), a.shape[1], n, b.ctypes.data, b.shape[1],
+                                            sw.ctypes.data, len(sw), pw.ctypes.data, len(pw), count,
+                                            out.ctypes.data if out.size else b.ctypes.data, stride, device))
+    return out
+
+
+def compose_unroll_device(d_a: int, ra: int, a_stride: int, n: int, d_b: int, b_stride: int, count: int, d_out: int, out_stride: int,
+                          start: int = 0, step: int = 1, device: int = 0, stream: int = 0) -> None:
+    """compose_unroll_words on device memory: count * ra rows at d_out, out_stride words apart.  Works on `stream` behind what is queued
+    there and waits for it (its buffers go back to the pool); d_out must not overlap d_a or d_b."""
+    sw, pw = exponent_words(start), exponent_words(step)
+    _check(lib().gf2bv_compose_unroll_device(d_a, ra, a_stride, n, d_b, b_stride, sw.ctypes.data, len(sw), pw.ctypes.data, len(pw), count,
+                                             d_out, out_stride, device, stream or None))
 
 
 def _sys_row_off(sys_row_off, nrows: int) -> np.ndarray:

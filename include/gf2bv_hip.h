@@ -814,9 +814,22 @@ int gf2bv_xl4_cubic_guess_chunk_device(int64_t m, int64_t n_lin, int64_t nguess,
  * column tile, out[3] the kernel's LDS bytes.
  * gf2bv_compose_last_times: this thread's last composition entry -- ms[0] upload, ms[1] kernels, ms[2] download (milliseconds; zero
  * for gf2bv_compose_device, which waits for nothing), ms[3] the number of products.
- * Argument errors (null pointers, ra < 0, n < 1 or nb < 1, n + 1 or nb + 1 >= 2^31 - 64, a stride below its width, an odd or
- * unaligned device matrix, k_nwords < 1) return GF2BV_ERR_ARG before any device is touched; buffers that do not fit are
- * GF2BV_ERR_NOMEM with nothing left allocated. */
+ * gf2bv_compose_unroll_*: a model stepped on the device.  b a self-map as for the power entries, a[ra] forms over its n unknowns;
+ * out has count x ra rows, time-major: row i x ra + r = a[r] with b substituted start + i x step times (a o b^(start + i x step)),
+ * i = 0 .. count - 1.  start >= 0 and step >= 1 are little-endian word arrays as k is.  count == 0 or ra == 0 is legal and writes
+ * nothing.  The schedule is fixed: block 0 = a o b^start (start = 0: a copied with its bits above n cleared, no product; otherwise
+ * b^start by square-and-multiply and one product), S = b^step (step = 1: b, no product), then doubling with P = S, h = 1: the rows
+ * of the times [h, min(2h, count)) = the rows of the times [0, min(h, count - h)) o P, written straight to their place in out, and
+ * P = P o P while 2h < count.  With pw(k) = bit_length(k) - 1 + popcount(k), pw(0) = 0, that is
+ * (step > 1 ? pw(step) : 0) + (start > 0 ? pw(start) + 1 : 0) + (count >= 2 ? 2 ceil(log2 count) - 1 : 0) products.  Power's three
+ * buffers and, for gf2bv_compose_unroll_words, the count x ra output rows stay resident; nothing comes back to the host between the
+ * products and the count is not cut into chunks.  gf2bv_compose_unroll_device works on `stream` behind what is queued there, copies
+ * d_b before anything else and WAITS for the stream before it returns; its blocks are read from and written to d_out, which must not
+ * overlap d_a or d_b.
+ * Argument errors (null pointers, ra < 0, count < 0, n < 1 or nb < 1, n + 1 or nb + 1 >= 2^31 - 64, a stride below its width, an odd
+ * or unaligned device matrix, k_nwords, start_nwords or step_nwords < 1, step = 0, a largest block of the schedule that is no legal
+ * product) return GF2BV_ERR_ARG before any device is touched; buffers that do not fit are GF2BV_ERR_NOMEM with nothing left
+ * allocated. */
 int gf2bv_compose_words(const uint64_t *a, int64_t ra, int64_t a_stride, int64_t n, const uint64_t *b, int64_t b_stride, int64_t nb,
                         uint64_t *out, int64_t out_stride, int device);
 int gf2bv_compose_device(const void *d_a, int64_t ra, int64_t a_stride, int64_t n, const void *d_b, int64_t b_stride, int64_t nb,
@@ -825,6 +838,12 @@ int gf2bv_compose_power_words(const uint64_t *b, int64_t b_stride, int64_t n, co
                               int64_t out_stride, int device);
 int gf2bv_compose_power_device(const void *d_b, int64_t b_stride, int64_t n, const uint64_t *k_words, int64_t k_nwords, void *d_out,
                                int64_t out_stride, int device, void *stream);
+int gf2bv_compose_unroll_words(const uint64_t *a, int64_t ra, int64_t a_stride, int64_t n, const uint64_t *b, int64_t b_stride,
+                               const uint64_t *start_words, int64_t start_nwords, const uint64_t *step_words, int64_t step_nwords,
+                               int64_t count, uint64_t *out, int64_t out_stride, int device);
+int gf2bv_compose_unroll_device(const void *d_a, int64_t ra, int64_t a_stride, int64_t n, const void *d_b, int64_t b_stride,
+                                const uint64_t *start_words, int64_t start_nwords, const uint64_t *step_words, int64_t step_nwords,
+                                int64_t count, void *d_out, int64_t out_stride, int device, void *stream);
 int gf2bv_compose_shape(int32_t out[4]);
 void gf2bv_compose_last_times(double ms[4]);
 
