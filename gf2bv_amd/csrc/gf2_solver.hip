@@ -705,7 +705,6 @@ struct SolverPlan {
 	i64 m_stride = 0, src_sys_words = 0;
 	ArenaLayout lay;              // (a view: of its one system, stride 0)
 	bool view = false;            // a non-owning window on one system of a gang (back-substitution, export)
-	bool own_bs = true;           // (a view) Y / ycols / out are its own; false: `out` points into the gang's (enqueue_backward_gang)
 	SysStride ss() const { return SysStride{ m_stride, (i64)lay.stride }; }
 	int mode = 0;
 	// many right-hand sides of one matrix (gf2bv_solve_rhs_*): right-hand side j is column cols + j, k_check_rhs_many leaves
@@ -731,9 +730,6 @@ struct SolverPlan {
 	int units = 0;
 	ForwardRun run;               // what the forward pass decides while it is enqueued (fill_stats and the look-ahead read it)
 	int narrow_rpt = 1;           // row blocks of 256 per narrow workgroup of a panel step (set in solver_alloc)
-	i64 ys = 0;
-	int ny = 0;
-	int h_ycol = 0;               // (host copy of the gang's one right-hand-side column: lives as long as the copy may)
 	i64 maxr = 0;
 	int npanels = 0, nblocks = 0;
 	i64 wt = 0, cw = 0;
@@ -800,6 +796,28 @@ struct ArenaPtrs {
 	}
 };
 
+// What one back-substitution on a Solver owns or borrows, and its shape.  backsub_begin() alone fills it (a gang's view: borrow());
+// release() alone gives it back -- at the next begin, where a kept handle is done with a pass, or with the Solver.
+struct BackSub {
+	std::vector<int> cols;        // the columns solved for, ny of them: ycols is uploaded from here, so it lives as long as the copy may
+	int *ycols = nullptr;
+	u64 *out = nullptr;           // the solutions, max(1, cw) words each: one per column (a gang: one per system)
+	u64 *Y = nullptr;             // Y sweeps: the selected columns of U as a bit matrix, ys words per pivot; parity chain: the diagonal blocks of U
+	u64 *Minv = nullptr;          // inverted diagonal blocks (k_bs_inv -> k_bs_near2)
+	int ny = 0;
+	i64 ys = 0;
+	bool borrowed = false;        // (a view) `out` points into its gang's: nothing here is this one's to return
+	bool held() const { return ycols || out || Y || Minv; }
+	void borrow(const BackSub &gang, int s, i64 cwx) { out = gang.out + (i64)s * cwx; ny = 1; borrowed = true; }
+	// nothing goes back to the pool while the chain on sA may still be using it
+	void release(hipStream_t sA)
+	{
+		if (held() && sA) (void)hipStreamSynchronize(sA);
+		if (!borrowed) for (void *p : { (void *)Y, (void *)ycols, (void *)out, (void *)Minv }) pool().release(p);
+		*this = BackSub();
+	}
+};
+
 // The device and pool resources a solve holds (or, a view, borrows), the flags that say whose they are and the caller's own src and
 // rhs_bad: never copied with the plan; Solver::release() alone gives back what is owned and resets the rest.
 struct SolverHandles {
@@ -809,7 +827,6 @@ struct SolverHandles {
 	bool ext_M = false;           // the working matrix belongs to the caller (slab solves: a tensor the ranks exchange tiles of)
 	const u64 *src = nullptr;     // caller's row-major matrix on the device (stride words per row)
 	u64 *tmp_src = nullptr;       // row-major staging buffer when the input came from the host
-	u64 *Minv = nullptr;          // inverted diagonal blocks of the back-substitution (k_bs_inv -> k_bs_near2)
 	u64 *rhs_bad = nullptr;       // (the caller's: see nrhs)
 	void *arena = nullptr;        // the side arrays of all nsys systems (ArenaPtrs: those of system 0)
 	hipStream_t sC = nullptr;     // outer passes: panel p's runs BESIDE the inner elimination of panel p + 1 (sA + sB)
@@ -817,9 +834,7 @@ struct SolverHandles {
 	                              // 262144^2 -0.8 %, but a fourth stream that cost later batch calls of the process their overlap; removed in
 	                              // round 6, profiles/r05_outer_shapes.txt)
 	hipEvent_t evOuter = nullptr, evPri = nullptr, evPanelDone = nullptr, evBig = nullptr;
-	u64 *Y = nullptr;
-	int *ycols = nullptr;
-	u64 *out = nullptr;
+	BackSub bs;                   // the back-substitution in flight, if any
 	hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
 	std::vector<hipEvent_t> evA, evPrio, kev, waitPrio;     // waitPrio[b]: the event that means "bulk of block b complete"
 	hipEvent_t evx = nullptr;
@@ -837,12 +852,11 @@ struct Solver : SolverPlan, ArenaPtrs, SolverHandles {
 	// An owner gives everything back once its streams are idle; a view (make_view) what it acquired, and lets go of what it borrowed.
 	void release()
 	{
-		if (!arena && !M && !tmp_src && !Y && !ycols && !out && !sA && !sB && !ev0) return;     // nothing held
+		if (!arena && !M && !tmp_src && !bs.held() && !sA && !sB && !ev0) return;     // nothing held
 		(void)hipSetDevice(device);
 		Pool &P = pool();
+		bs.release(sA);
 		if (view) {
-			if (sA && (Y || ycols || out)) (void)hipStreamSynchronize(sA);
-			if (own_bs) for (void *p : { (void *)Y, (void *)ycols, (void *)out, (void *)Minv }) P.release(p);
 			P.release_event(ev2, true);
 			P.release_event(evx, true);
 			arena = nullptr; M = nullptr; sA = sB = nullptr; ev0 = ev1 = ev3 = nullptr;          // (borrowed)
@@ -851,7 +865,7 @@ struct Solver : SolverPlan, ArenaPtrs, SolverHandles {
 			if (sC) (void)hipStreamSynchronize(sC);
 			if (sB) (void)hipStreamSynchronize(sB);
 			if (arena || M) (void)hipStreamSynchronize(sA);
-			for (void *p : { arena, (void *)Y, (void *)ycols, (void *)out, (void *)Minv, (void *)(ext_M ? nullptr : M), (void *)tmp_src }) P.release(p);
+			for (void *p : { arena, (void *)(ext_M ? nullptr : M), (void *)tmp_src }) P.release(p);
 			for (hipEvent_t e : { ev0, ev1, ev2, ev3, evx }) P.release_event(e, true);
 			for (hipEvent_t e : { evOuter, evPri, evPanelDone, evBig }) P.release_event(e, false);
 			if (sC) P.release_stream(sC, device, nsys > 1 ? 3 : 1);
@@ -1607,18 +1621,33 @@ int enqueue_forward(Solver &S)
 	return enqueue_check_rhs(S);
 }
 
-// back-substitution on Y = selected columns of U (RHS [+ free columns]); then scatter.
-int enqueue_backward(Solver &S, const std::vector<int> &ycols_host)
+// The one way into a back-substitution of the columns `cols` on S (each of its nsys systems): what an earlier one on this Solver
+// still holds goes back first; then the columns are kept and uploaded, and the solutions are cleared.  Every buffer is S.bs's from
+// the moment it exists, so a failure part-way leaves nothing that the next begin or the Solver's release does not return.
+int backsub_begin(Solver &S, const std::vector<int> &cols)
 {
-	S.ny = (int)ycols_host.size();
-	const i64 nyw = (S.ny + 63) / 64;
-	S.ys = round_up(nyw, YTW);
-	HIPCHK(pool().alloc((void **)&S.ycols, sizeof(int) * S.ny, S.device));
-	HIPCHK(hipMemcpyAsync(S.ycols, ycols_host.data(), sizeof(int) * S.ny, hipMemcpyHostToDevice, S.sA));
-	HIPCHK(pool().alloc((void **)&S.Y, sizeof(u64) * std::max<i64>(1, S.maxr) * S.ys, S.device));
-	HIPCHK(hipMemsetAsync(S.Y, 0, sizeof(u64) * std::max<i64>(1, S.maxr) * S.ys, S.sA));
-	HIPCHK(pool().alloc((void **)&S.out, sizeof(u64) * S.ny * std::max<i64>(1, S.cw), S.device));
-	HIPCHK(hipMemsetAsync(S.out, 0, sizeof(u64) * S.ny * std::max<i64>(1, S.cw), S.sA));
+	BackSub &B = S.bs;
+	B.release(S.sA);
+	B.cols = cols;
+	B.ny = (int)cols.size();
+	const size_t out_bytes = sizeof(u64) * B.ny * std::max<i64>(1, S.cw) * S.nsys;
+	HIPCHK(pool().alloc((void **)&B.ycols, sizeof(int) * B.ny, S.device));
+	HIPCHK(hipMemcpyAsync(B.ycols, B.cols.data(), sizeof(int) * B.ny, hipMemcpyHostToDevice, S.sA));
+	HIPCHK(pool().alloc((void **)&B.out, out_bytes, S.device));
+	HIPCHK(hipMemsetAsync(B.out, 0, out_bytes, S.sA));
+	return GF2BV_OK;
+}
+
+// back-substitution on Y = selected columns of U (RHS [+ free columns]); then scatter.
+int enqueue_backward(Solver &S, const std::vector<int> &cols)
+{
+	int rc = backsub_begin(S, cols);
+	if (rc) return rc;
+	BackSub &B = S.bs;
+	const i64 nyw = (B.ny + 63) / 64;
+	B.ys = round_up(nyw, YTW);
+	HIPCHK(pool().alloc((void **)&B.Y, sizeof(u64) * std::max<i64>(1, S.maxr) * B.ys, S.device));
+	HIPCHK(hipMemsetAsync(B.Y, 0, sizeof(u64) * std::max<i64>(1, S.maxr) * B.ys, S.sA));
 	u64 *bmult = S.mult;              // forward multipliers are dead by now
 	const int rpb = 2048;
 	if (S.maxr > 0) {
@@ -1627,20 +1656,20 @@ int enqueue_backward(Solver &S, const std::vector<int> &ycols_host)
 		for (i64 k0 = 0; k0 < S.maxr; k0 += kchunk) {
 			const i64 waves = std::min(kchunk, S.maxr - k0) * nyw;
 			k_extract_y<<<dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, S.sA>>>(S.M, S.srows, S.st, S.urow, S.pivcol,
-			                                                                      S.ycols, S.ny, S.Y, S.ys, k0);
+			                                                                      B.ycols, B.ny, B.Y, B.ys, k0);
 		}
-		const int ytiles = (int)(S.ys / YTW);
+		const int ytiles = (int)(B.ys / YTW);
 		for (int q = S.npanels - 1; q >= 1; q--) {
 			const i64 bound = std::min<i64>((i64)64 * q, S.maxr);      // pivots before panel q
 			int g = (int)std::min<i64>(1024, (bound + 255) / 256);
 			k_gather_mult_u<<<dim3(g), dim3(256), 0, S.sA>>>(S.M, S.srows, q, S.panels + q, S.urow, bmult);
 			const i64 nrb = (bound + rpb - 1) / rpb;
-			HIPCHK(launch_ysweep(dim3((unsigned)(ytiles * nrb)), S.sA, S.Y, S.ys, S.maxr, S.panels + q, bmult, ytiles, rpb));
+			HIPCHK(launch_ysweep(dim3((unsigned)(ytiles * nrb)), S.sA, B.Y, B.ys, S.maxr, S.panels + q, bmult, ytiles, rpb));
 		}
 		for (i64 k0 = 0; k0 < S.maxr; k0 += kchunk << 6) {
 			const i64 thr = std::min(kchunk << 6, S.maxr - k0) * nyw;
-			k_scatter_solution<<<dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, S.sA>>>(S.Y, S.ys, S.st, S.pivcol, S.ny,
-			                                                                              S.out, std::max<i64>(1, S.cw), k0);
+			k_scatter_solution<<<dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, S.sA>>>(B.Y, B.ys, S.st, S.pivcol, B.ny,
+			                                                                              B.out, std::max<i64>(1, S.cw), k0);
 		}
 	}
 	HIPCHK(hipGetLastError());
@@ -1651,26 +1680,32 @@ int enqueue_backward(Solver &S, const std::vector<int> &ycols_host)
 // Blocked parity back-substitution straight into the solution words (no Y matrix), for up to GF2_BSV
 // right-hand sides at once: solve_one (the RHS column) and small kernel bases (the free columns + RHS).
 // U is streamed once for all of them.
-int enqueue_backward_parity(Solver &S, const std::vector<int> &ycols_host)
+// A gang (S.nsys > 1) runs the same chain once for all its systems, blockIdx.y = system -- 2 x ceil(npanels / 16) launches for the
+// gang instead of as many per system (a 32768^2 system's chain is 64 launches of 6 + 13 us: 1.2 ms during which one workgroup
+// walks a diagonal block; 24 of them in a row were 15 % of a gang's wall time, profiles/r04_batch_budget.txt).  The gang owns the
+// buffers, system s finds its solution at out + s * cw (BackSub::borrow).  One column per system then, and no inverted blocks:
+// k_bs_near2 takes no system stride.
+int enqueue_backward_parity(Solver &S, const std::vector<int> &cols)
 {
-	S.ny = (int)ycols_host.size();
+	if (S.nsys > 1 && cols.size() != 1) return fail(GF2BV_ERR_ARG, "a gang's back-substitution solves for one column per system");
+	int rc = backsub_begin(S, cols);
+	if (rc) return rc;
+	BackSub &B = S.bs;
 	const i64 cw = std::max<i64>(1, S.cw);
-	HIPCHK(pool().alloc((void **)&S.ycols, sizeof(int) * S.ny, S.device));
-	HIPCHK(hipMemcpyAsync(S.ycols, ycols_host.data(), sizeof(int) * S.ny, hipMemcpyHostToDevice, S.sA));
-	HIPCHK(pool().alloc((void **)&S.out, sizeof(u64) * S.ny * cw, S.device));
-	HIPCHK(hipMemsetAsync(S.out, 0, sizeof(u64) * S.ny * cw, S.sA));
+	const unsigned nsys = (unsigned)S.nsys;
 	unsigned char *accv = reinterpret_cast<unsigned char *>(S.mult);     // forward multipliers are dead by now (2*G*8 bytes per row)
 	const i64 nacc = std::max<i64>(1, S.maxr);
 	// the diagonal blocks of U, gathered by the whole chip into compact form for the serial walk of k_bs_near
-	HIPCHK(pool().alloc((void **)&S.Y, sizeof(u64) * 64 * 16 * std::max(1, S.npanels), S.device));
+	const i64 dgw = (i64)64 * 16 * std::max(1, S.npanels);
+	HIPCHK(pool().alloc((void **)&B.Y, sizeof(u64) * dgw * nsys, S.device));
 	if (S.npanels > 0)
-		k_bs_diag<<<dim3(S.npanels), dim3(256), 0, S.sA>>>(S.M, S.srows, S.npanels, S.panels, S.urow, S.Y, SysStride{0, 0}, (i64)0);
+		k_bs_diag<<<dim3(S.npanels, nsys), dim3(256), 0, S.sA>>>(S.M, S.srows, S.npanels, S.panels, S.urow, B.Y, S.ss(), dgw);
 	// Round 4: from sixteen groups (16384 columns) up the diagonal blocks are inverted up front (k_bs_inv, all groups in one launch, ~90 us) and the
 	// serial walk of a link (k_bs_near, 12 us) becomes a matrix-vector product (k_bs_near2, ~4 us).  GF2BV_BS_INV=0 / 1: never / always.
 	const int ngroups = (S.npanels + GF2_BSG - 1) / GF2_BSG;
-	const bool inv = S.kn.bs_inv >= 0 ? S.kn.bs_inv != 0 && ngroups >= 1 : ngroups >= 16;
+	const bool inv = nsys == 1 && (S.kn.bs_inv >= 0 ? S.kn.bs_inv != 0 && ngroups >= 1 : ngroups >= 16);
 	if (inv) {
-		HIPCHK(pool().alloc((void **)&S.Minv, sizeof(u64) * (size_t)ngroups * 16 * 64 * 16, S.device));
+		HIPCHK(pool().alloc((void **)&B.Minv, sizeof(u64) * (size_t)ngroups * 16 * 64 * 16, S.device));
 		static std::mutex mu;
 		static std::map<int, bool> raised;          // device -> the > 64 KiB dynamic-LDS attribute has been raised there
 		{
@@ -1680,22 +1715,21 @@ int enqueue_backward_parity(Solver &S, const std::vector<int> &ycols_host)
 				raised[S.device] = true;
 			}
 		}
-		k_bs_inv<<<dim3(ngroups), dim3(1024), GF2_BSINV_LDS, S.sA>>>(S.Y, S.npanels, S.panels, S.pivcol, S.Minv);
+		k_bs_inv<<<dim3(ngroups), dim3(1024), GF2_BSINV_LDS, S.sA>>>(B.Y, S.npanels, S.panels, S.pivcol, B.Minv);
 	}
 	// right-hand sides in groups of GF2_BSV (U is streamed once per group; the groups are independent)
-	for (int v0 = 0; v0 < S.ny; v0 += GF2_BSV) {
-		const int nv = std::min(GF2_BSV, S.ny - v0);
+	for (int v0 = 0; v0 < B.ny; v0 += GF2_BSV) {
+		const int nv = std::min(GF2_BSV, B.ny - v0);
+		u64 *X = B.out + (i64)v0 * cw;
 		for (int qb = S.npanels; qb > 0; qb -= GF2_BSG) {
 			const int qa = std::max(0, qb - GF2_BSG);
 			const int waves = (qb - qa) * 64;
-			k_bs_far<<<dim3((waves + 3) / 4), dim3(256), 0, S.sA>>>(S.M, S.srows, cw, qa, qb, S.panels, S.urow, S.pivcol, S.ycols + v0, nv,
-			                                                        S.out + (i64)v0 * cw, accv, nacc, SysStride{0, 0}, (i64)0);
+			k_bs_far<<<dim3((waves + 3) / 4, nsys), dim3(256), 0, S.sA>>>(S.M, S.srows, cw, qa, qb, S.panels, S.urow, S.pivcol, B.ycols + v0, nv,
+			                                                              X, accv, nacc, S.ss(), cw);
 			if (inv)
-				k_bs_near2<<<dim3(1), dim3(1024), 0, S.sA>>>(cw, qa, qb, S.panels, S.pivcol, nv, S.out + (i64)v0 * cw, accv, nacc, S.Minv,
-				                                             (S.npanels - qb) / GF2_BSG);
+				k_bs_near2<<<dim3(1), dim3(1024), 0, S.sA>>>(cw, qa, qb, S.panels, S.pivcol, nv, X, accv, nacc, B.Minv, (S.npanels - qb) / GF2_BSG);
 			else
-				k_bs_near<<<dim3(1), dim3(256), 0, S.sA>>>(S.Y, cw, qa, qb, S.panels, S.pivcol, nv, S.out + (i64)v0 * cw, accv, nacc,
-				                                           SysStride{0, 0}, (i64)0, (i64)0);
+				k_bs_near<<<dim3(1, nsys), dim3(256), 0, S.sA>>>(B.Y, cw, qa, qb, S.panels, S.pivcol, nv, X, accv, nacc, S.ss(), dgw, cw);
 		}
 	}
 	HIPCHK(hipGetLastError());
@@ -1703,44 +1737,13 @@ int enqueue_backward_parity(Solver &S, const std::vector<int> &ycols_host)
 	return GF2BV_OK;
 }
 
-// solve_one of a whole gang: the same three kernels with blockIdx.y = system -- one chain of 2 x ceil(npanels / 16) launches
-// for the gang instead of one per system (a 32768^2 system's chain is 64 launches of 6 + 13 us: 1.2 ms during which one
-// workgroup walks a diagonal block; 24 of them in a row were 15 % of a gang's wall time, profiles/r04_batch_budget.txt).
-// The gang owns ycols / out / Y; system s finds its solution at out + s * cw (the views point there, own_bs = false).
-int enqueue_backward_gang(Solver &S)
-{
-	S.ny = 1;
-	const i64 cw = std::max<i64>(1, S.cw);
-	S.h_ycol = (int)S.cols;
-	HIPCHK(pool().alloc((void **)&S.ycols, sizeof(int), S.device));
-	HIPCHK(hipMemcpyAsync(S.ycols, &S.h_ycol, sizeof(int), hipMemcpyHostToDevice, S.sA));
-	HIPCHK(pool().alloc((void **)&S.out, sizeof(u64) * cw * S.nsys, S.device));
-	HIPCHK(hipMemsetAsync(S.out, 0, sizeof(u64) * cw * S.nsys, S.sA));
-	unsigned char *accv = reinterpret_cast<unsigned char *>(S.mult);     // forward multipliers are dead by now
-	const i64 nacc = std::max<i64>(1, S.maxr);
-	const i64 dgw = (i64)64 * 16 * std::max(1, S.npanels);
-	HIPCHK(pool().alloc((void **)&S.Y, sizeof(u64) * dgw * S.nsys, S.device));
-	if (S.npanels > 0)
-		k_bs_diag<<<dim3(S.npanels, S.nsys), dim3(256), 0, S.sA>>>(S.M, S.srows, S.npanels, S.panels, S.urow, S.Y, S.ss(), dgw);
-	for (int qb = S.npanels; qb > 0; qb -= GF2_BSG) {
-		const int qa = std::max(0, qb - GF2_BSG);
-		const int waves = (qb - qa) * 64;
-		k_bs_far<<<dim3((waves + 3) / 4, S.nsys), dim3(256), 0, S.sA>>>(S.M, S.srows, cw, qa, qb, S.panels, S.urow, S.pivcol, S.ycols, 1,
-		                                                                S.out, accv, nacc, S.ss(), cw);
-		k_bs_near<<<dim3(1, S.nsys), dim3(256), 0, S.sA>>>(S.Y, cw, qa, qb, S.panels, S.pivcol, 1, S.out, accv, nacc, S.ss(), dgw, cw);
-	}
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(S.ev2, S.sA));
-	return GF2BV_OK;
-}
-
-// Back-substitution of the columns ycols: up to GF2_BS_MAXRHS of them (kernel dimensions of the reference's use: solve_all
+// Back-substitution of the columns cols: up to GF2_BS_MAXRHS of them (kernel dimensions of the reference's use: solve_all
 // caps at 16) the parity path, GF2_BSV of them per pass over U; more: the table sweeps over the bit matrix Y (one pass over Y
 // per panel whatever the dimension).  GF2BV_YSWEEP sends every count to the sweeps (the general path, for cross-checking).
-int enqueue_backsub(Solver &S, const std::vector<int> &ycols)
+int enqueue_backsub(Solver &S, const std::vector<int> &cols)
 {
-	if ((i64)ycols.size() <= GF2_BS_MAXRHS && !S.kn.ysweep) return enqueue_backward_parity(S, ycols);
-	return enqueue_backward(S, ycols);
+	if ((i64)cols.size() <= GF2_BS_MAXRHS && !S.kn.ysweep) return enqueue_backward_parity(S, cols);
+	return enqueue_backward(S, cols);
 }
 
 int solver_enqueue(Solver &S)
@@ -1783,10 +1786,10 @@ int load_free_order(Solver &S)
 // pivot columns), then S.evx.
 int enqueue_export(Solver &S)
 {
-	HIPCHK(pool().event(&S.evx, true));
+	if (!S.evx) HIPCHK(pool().event(&S.evx, true));
 	HIPCHK(hipMemcpyAsync(&S.hst, S.st, sizeof S.hst, hipMemcpyDeviceToHost, S.sA));
-	S.hout.resize((size_t)S.ny * std::max<i64>(1, S.cw));
-	HIPCHK(hipMemcpyAsync(S.hout.data(), S.out, sizeof(u64) * S.hout.size(), hipMemcpyDeviceToHost, S.sA));
+	S.hout.resize((size_t)S.bs.ny * std::max<i64>(1, S.cw));
+	HIPCHK(hipMemcpyAsync(S.hout.data(), S.bs.out, sizeof(u64) * S.hout.size(), hipMemcpyDeviceToHost, S.sA));
 	S.hp.resize(std::max(1, S.npanels));
 	HIPCHK(hipMemcpyAsync(S.hp.data(), S.panels, sizeof(PanelRec) * S.hp.size(), hipMemcpyDeviceToHost, S.sA));
 	S.hpiv.resize(std::max<i64>(1, S.maxr));
@@ -1864,7 +1867,7 @@ int finish_end(Solver &S, gf2bv_result **out)
 	const SolveState &hst = S.hst;
 	const i64 cwx = std::max<i64>(1, S.cw);
 	S.hpiv.resize(hst.rank);
-	std::unique_ptr<gf2bv_result> R = new_result(!hst.inconsistent, S.cols, S.hpiv.data(), hst.rank, S.hout.data() + (size_t)((S.ny - 1) * cwx));
+	std::unique_ptr<gf2bv_result> R = new_result(!hst.inconsistent, S.cols, S.hpiv.data(), hst.rank, S.hout.data() + (size_t)((S.bs.ny - 1) * cwx));
 	if (!hst.inconsistent && S.mode == GF2BV_MODE_AFFINE_SPACE) R->basis = basis_rows(S.hout.data(), S.cw, S.free_order, R->dim);
 	fill_stats(S, R.get());
 	tr.mark(S.kn, "finish: result");
@@ -1957,7 +1960,7 @@ int solver_finish(Solver &S, gf2bv_result **out)
 
 // A non-owning window on system s of a gang: the gang's plan for one system, that system's matrix and side arrays.
 // Back-substitution and export then run per system, unchanged.  Borrowed: the streams sA and sB and the timing events ev0, ev1,
-// ev3.  Its own: ev2, evx and whatever its back-substitution allocates (unless own_bs is cleared: enqueue_backward_gang).
+// ev3.  Its own: ev2, evx and whatever its back-substitution allocates (unless it borrows the gang's: BackSub::borrow).
 int make_view(const Solver &S, int s, Solver &V)
 {
 	V.plan() = S.plan();
@@ -1995,10 +1998,10 @@ int solve_gang(Solver &S, gf2bv_result **out)
 				if (rc) return rc;
 			}
 		else {
-			rc = enqueue_backward_gang(S);
+			rc = enqueue_backward_parity(S, { (int)S.cols });
 			if (rc) return rc;
 			for (int s = 0; s < S.nsys; s++) {
-				V[s].out = S.out + (i64)s * std::max<i64>(1, S.cw); V[s].ny = 1; V[s].own_bs = false;
+				V[s].bs.borrow(S.bs, s, std::max<i64>(1, S.cw));
 				HIPCHK(hipEventRecord(V[s].ev2, S.sA));
 			}
 		}
@@ -2535,16 +2538,14 @@ namespace {
 constexpr i64 kFactorSlots = 64;      // right-hand sides per solve pass (the slot columns cols .. cols + 63)
 const char *kFailedHandle = "the handle is unusable: an append failed after it had started to change it";
 
-// what a back-substitution took from the pool goes back (the handle keeps its solver between calls)
-void release_backsub(Solver &S)
-{
-	(void)hipStreamSynchronize(S.sA);
-	for (void *p : { (void *)S.Y, (void *)S.ycols, (void *)S.out, (void *)S.Minv }) pool().release(p);
-	S.Y = nullptr; S.ycols = nullptr; S.out = nullptr; S.Minv = nullptr;
-}
+// A kept handle keeps its solver between calls: what a back-substitution on it took from the pool goes back on every return path
+struct BackSubScope {
+	Solver &S;
+	~BackSubScope() { S.bs.release(S.sA); }
+};
 
 // The kernel basis of a kept factorization (mode 1) from its pivots: the free columns in M4RI's order, one back-substitution over
-// them.  The caller gives back what the back-substitution took (release_backsub).
+// them.
 int factor_basis(gf2bv_factor *h, std::vector<u64> &basis)
 {
 	Solver &S = h->S;
@@ -2553,9 +2554,10 @@ int factor_basis(gf2bv_factor *h, std::vector<u64> &basis)
 	if (rc) return rc;
 	const i64 dim = h->cols - h->rank;
 	if (!dim) return GF2BV_OK;
+	BackSubScope scope{ S };
 	if ((rc = enqueue_backsub(S, S.free_order))) return rc;
 	std::vector<u64> hout((size_t)(dim * std::max<i64>(1, h->cw)));
-	HIPCHK(hipMemcpyAsync(hout.data(), S.out, sizeof(u64) * hout.size(), hipMemcpyDeviceToHost, S.sA));
+	HIPCHK(hipMemcpyAsync(hout.data(), S.bs.out, sizeof(u64) * hout.size(), hipMemcpyDeviceToHost, S.sA));
 	HIPCHK(hipStreamSynchronize(S.sA));
 	basis = basis_rows(hout.data(), h->cw, S.free_order, dim);
 	return GF2BV_OK;
@@ -2625,7 +2627,6 @@ int factor_matrix(const MatrixInput &in, i64 rows, i64 cols, int mode, int devic
 		(void)hipGetLastError();      // (fill_stats' elapsed times of events a factorization does not record)
 		h->fst = R.stats;
 	}
-	release_backsub(S);
 	h->device_bytes = factor_device_bytes(h.get());
 	*out = h.release();
 	return GF2BV_OK;
@@ -2650,16 +2651,16 @@ int factor_pass(gf2bv_factor *h, const u64 *d_rhs, i64 np, i64 rhs_stride, hipEv
 	HIPCHK(hipEventRecord(ev[2], S.sA));
 	std::vector<int> yc((size_t)np);
 	for (i64 j = 0; j < np; j++) yc[(size_t)j] = (int)(cols + j);
+	BackSubScope scope{ S };
 	int rc = enqueue_backsub(S, yc);
 	if (rc) return rc;
 	HIPCHK(hipEventRecord(ev[3], S.sA));
 	std::vector<u64> hout((size_t)(np * cwx));
 	u64 hbad = 0;
-	HIPCHK(hipMemcpyAsync(hout.data(), S.out, sizeof(u64) * hout.size(), hipMemcpyDeviceToHost, S.sA));
+	HIPCHK(hipMemcpyAsync(hout.data(), S.bs.out, sizeof(u64) * hout.size(), hipMemcpyDeviceToHost, S.sA));
 	HIPCHK(hipMemcpyAsync(&hbad, bad, sizeof(u64), hipMemcpyDeviceToHost, S.sA));
 	HIPCHK(hipEventRecord(ev[4], S.sA));
 	HIPCHK(hipStreamSynchronize(S.sA));
-	release_backsub(S);
 	float ms[4] = {0, 0, 0, 0};
 	for (int i = 0; i < 4; i++) (void)hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]);
 	const float total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -2964,7 +2965,6 @@ int factor_append(gf2bv_factor *h, const MatrixInput &in, i64 k, hipStream_t str
 		if (h->mode == GF2BV_MODE_AFFINE_SPACE) {
 			const auto tb = std::chrono::steady_clock::now();
 			if (int rc = factor_basis(h, basis)) return rc;
-			if (cols - h->rank) release_backsub(S);      // (a back-substitution ran)
 			ms[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb).count();
 		}
 		h->basis = std::move(basis);
@@ -2975,7 +2975,6 @@ int factor_append(gf2bv_factor *h, const MatrixInput &in, i64 k, hipStream_t str
 		return GF2BV_OK;
 	};
 	if (int rc = rest()) {
-		release_backsub(S);
 		h->failed = true;
 		const std::string why = g_err;
 		return fail(GF2BV_ERR_HIP, (std::string(kFailedHandle) + ": " + why).c_str());

@@ -202,9 +202,9 @@ def test_stream_pair_knobs_change_nothing_but_speed(monkeypatch, knob, value):
 
 @pytest.mark.parametrize("inv", ["1", "0"])
 def test_back_substitution_with_inverted_diagonal_blocks(monkeypatch, inv):
-    """Round 4: from four groups of 16 panels up the back-substitution inverts the diagonal blocks up front (k_bs_inv) and a link
-    of its chain is one launch (k_bs_step: far part, then X = Minv x a by the last workgroup to arrive) -- GF2BV_BS_INV=1 forces
-    that path onto every size, =0 the two-launch chain with the serial walk (k_bs_far + k_bs_near).  Shapes with a short first
+    """Round 4: from 16 groups of 16 panels up the back-substitution inverts the diagonal blocks up front (k_bs_inv) and a link
+    of its chain is two launches (k_bs_far: the far part, then k_bs_near2: X = Minv x a) -- GF2BV_BS_INV=1 forces
+    that path onto every size, =0 the chain with the serial walk in its second launch (k_bs_far + k_bs_near).  Shapes with a short first
     group, one group, rank caps (panels with few or no pivots), rows >> cols, inconsistent systems, kernel bases of 0 ... 40
     vectors (several passes of 8 right-hand sides), both modes, against the oracle."""
     monkeypatch.setenv("GF2BV_BS_INV", inv)
