@@ -416,6 +416,8 @@ __global__ void __launch_bounds__(256) k_probe_stamp_panel(unsigned long long *s
 	if (threadIdx.x == 0) *stamp = wall_clock64();
 	if (mid[(threadIdx.x + 1) & 255] == 0xffffffffu) *stamp = 0;
 }
+// The clock at this point of a stream: what the bulk-update stamps of a timed solve are relative to (k_update16: t_first / t_last)
+__global__ void __launch_bounds__(64) k_stamp_clock(unsigned long long *out) { if (threadIdx.x == 0) *out = wall_clock64(); }
 // Which XCD does workgroup b of a one-dimensional launch land on?  (XCC_ID, hardware register 20 of the gfx940 family, bits 3:0.)
 // The gang bulk update places a system per XCD on the ASSUMPTION b -> XCD b % 8 (k_update16: xcd_nsys); the host checks it once per
 // device with this kernel and falls back to the plain grid where it does not hold (another partition mode, a driver that dispatches
@@ -2587,12 +2589,16 @@ typedef __attribute__((address_space(3))) const u32x4 *lds_u4_ptr;
 // row ARE re-read (once per tile) and should keep their place in the XCD's L2: 192 x 32768^2 3.51 -> 3.34 ms per system
 // (loads alone 3.44, stores alone 3.58; profiles/r04_batch_scans.txt).  Single systems keep plain accesses: the kernels
 // behind a pass (TRSM, look-ahead, table builds) find their rows in L2 / MALL (65536^2 41 -> 51 ms with streaming stores, round 2).
+#ifdef GF2_MB_SERPENTINE
+__device__ int gf2_mb_rev;             // tools/microbench_update16.hip: the direction of the launches that follow
+#endif
 template <int NT, bool HALF, int DEPTH, bool PIPE, int LB, bool STREAM = false>
 __global__ void __launch_bounds__(LB)
 k_update16(u64 *__restrict__ M, i64 rows, i64 srows, int j0, int gb, int wlo,
            const PanelRec *__restrict__ panels, const PanelAux *__restrict__ aux,
            const u64 *__restrict__ mult4, const int *__restrict__ blk_first,
-           int tile_begin, int ntiles, int world, int wrank, const uint4 *__restrict__ Pc, SysStride ss, int xcd_nsys)
+           int tile_begin, int ntiles, int world, int wrank, const uint4 *__restrict__ Pc, SysStride ss, int xcd_nsys,
+           unsigned long long *__restrict__ t_first, unsigned long long *__restrict__ t_last)
 {
 	// Which system, which span.  A gang's launch is normally (spans, systems); with xcd_nsys > 0 (a gang of a multiple of 8
 	// systems, round 4) it is ONE line of spans x systems workgroups decoded so that all workgroups of a system sit on ONE
@@ -2627,7 +2633,14 @@ k_update16(u64 *__restrict__ M, i64 rows, i64 srows, int j0, int gb, int wlo,
 
 	int anyp = 0;
 	for (int g = 0; g < gb; g++) anyp |= panels[j0 + g].p;
-	if (!anyp) return;
+	// Timed solves (t_first: this launch's pair of stamps, null otherwise): when the launch's first workgroup began and its last one
+	// ended, on the 100 MHz clock -- the host reads them after the solve instead of bracketing every launch with events.  Every
+	// launch leaves both, also one that finds no pivots: a slot without them means a launch that did not run.
+	if (t_first && threadIdx.x == 0) atomicMin(t_first, wall_clock64());
+	if (!anyp) {
+		if (t_first && threadIdx.x == 0) atomicMax(t_last, wall_clock64());
+		return;
+	}
 	// Work = (tile, row) pairs, tile-major, rows from the alive bound (rounded down to a wavefront's 64) to the
 	// padded end; every workgroup takes one contiguous span (see k_update) in steps of NW x 64 rows.
 	const i64 rlo = (i64)(*blk_first) & ~(i64)63;
@@ -2637,8 +2650,16 @@ k_update16(u64 *__restrict__ M, i64 rows, i64 srows, int j0, int gb, int wlo,
 	const i64 total = (i64)ntiles * R;
 	i64 chunk = (total + gx - 1) / gx;
 	chunk = (chunk + ALIGN - 1) / ALIGN * ALIGN;
+	// [pos, pend) is what is left of the chunk; spans come off its front.  tools/microbench_update16.hip (-DGF2_MB_SERPENTINE) can
+	// also walk it backwards -- spans off the back, a span's batches in descending row order -- to cost alternating pass directions
+	// (profiles/bulk_stream_time.txt: no gain); the solver has one direction and `rev` folds away.
+#ifdef GF2_MB_SERPENTINE
+	const int rev = gf2_mb_rev;
+#else
+	constexpr int rev = 0;
+#endif
 	i64 pos = (i64)bx * chunk;
-	const i64 pend = (pos + chunk < total) ? pos + chunk : total;
+	i64 pend = (pos + chunk < total) ? pos + chunk : total;
 
 	// lane constants: byte s % 3 of KC[s / 3] = 16 * (table read at step s), byte 3 = 1 (the page bit of group 1)
 	unsigned KC[6];
@@ -2663,10 +2684,11 @@ k_update16(u64 *__restrict__ M, i64 rows, i64 srows, int j0, int gb, int wlo,
 	unsigned sgx = 0, sgy = 0, sgz = 0, sgw = 0;
 	bool have_staged = false;
 	for (bool first_span = true; pos < pend; first_span = false) {
-		const int ct = (int)(pos / R);
-		const i64 r0 = pos - (i64)ct * R;
-		const i64 span = (R - r0 < pend - pos) ? R - r0 : pend - pos;
-		pos += span;
+		const int ct = (int)((rev ? pend - 1 : pos) / R);
+		const i64 sbeg = (rev && pos < (i64)ct * R) ? (i64)ct * R : pos;      // (backwards: the part of tile ct at the chunk's end)
+		const i64 r0 = sbeg - (i64)ct * R;
+		const i64 span = rev ? pend - sbeg : ((R - r0 < pend - pos) ? R - r0 : pend - pos);
+		if (rev) pend = sbeg; else pos += span;
 		const i64 tile = owned_item(ct, tile_begin, GF2_OWN_LOG - 1, world, wrank);     // (column-slab solve: the tiles this rank owns)
 		const i64 rbeg = rlo + r0;
 		if (rbeg >= R64) continue;
@@ -2679,7 +2701,8 @@ k_update16(u64 *__restrict__ M, i64 rows, i64 srows, int j0, int gb, int wlo,
 		if (rbeg + ((nsteps - 1) * NW + wv) * 64 >= rend) nb--;
 		struct Bt { uint4 d, m0, m1; i64 row; };
 		auto load = [&](Bt &H, i64 i) {
-			const i64 ic = i < nb ? i : nb - 1;         // (a prefetch past the end re-reads the last batch: no control flow around loads)
+			const i64 il = i < nb ? i : nb - 1;         // (a prefetch past the end re-reads the last batch: no control flow around loads)
+			const i64 ic = rev ? nb - 1 - il : il;
 			const i64 row = rbeg + (ic * NW + wv) * 64 + lane;
 			H.row = row;
 			// (the two 16-byte halves of a row's multipliers side by side: as two contiguous planes -- every load then whole
@@ -2754,7 +2777,7 @@ k_update16(u64 *__restrict__ M, i64 rows, i64 srows, int j0, int gb, int wlo,
 		// the pivot rows of the next span's tile (pivot rows are never changed by this launch: zero multipliers)
 		have_staged = false;
 		if (pos < pend) {
-			const i64 ntile = owned_item((int)(pos / R), tile_begin, GF2_OWN_LOG - 1, world, wrank);
+			const i64 ntile = owned_item((int)((rev ? pend - 1 : pos) / R), tile_begin, GF2_OWN_LOG - 1, world, wrank);
 			if (threadIdx.x < GF2_GMAX * 64) {
 				uint4 nx;
 				if (Pc) nx = Pc[ntile * (GF2_GMAX * 64) + threadIdx.x];
@@ -2841,6 +2864,10 @@ k_update16(u64 *__restrict__ M, i64 rows, i64 srows, int j0, int gb, int wlo,
 			}
 		}
 	}       // spans
+	if (t_first) {
+		__syncthreads();
+		if (threadIdx.x == 0) atomicMax(t_last, wall_clock64());
+	}
 }
 
 

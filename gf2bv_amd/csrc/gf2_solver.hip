@@ -580,7 +580,8 @@ void forget_concurrency(int device);
 struct UpdateImpl {
 	int G, T, lds_bytes, threads;
 	hipError_t (*update)(dim3, hipStream_t, u64 *, i64, i64, int, int, int, const PanelRec *, const PanelAux *,
-	                     const u64 *, const int *, int, int, int, int, int, bool, const uint4 *, SysStride, hipEvent_t, hipEvent_t, int);
+	                     const u64 *, const int *, int, int, int, int, int, bool, const uint4 *, SysStride, hipEvent_t, hipEvent_t, int,
+	                     unsigned long long *, unsigned long long *);
 };
 
 // 16-byte tiles: G = 4 panels, T = 8 byte fields per panel.  nw_lo < 0 selects the HALF instance (only the tile's second
@@ -589,7 +590,7 @@ template <int NT, int DEPTH, bool PIPE, int LB>
 hipError_t launch_update16(dim3 grid, hipStream_t s, u64 *M, i64 rows, i64 srows, int j0, int gb, int wlo,
                            const PanelRec *panels, const PanelAux *aux, const u64 *multset, const int *blk_first,
                            int tile_begin, int ntiles, int world, int wrank, int nw_lo, bool stream_rows, const uint4 *Pc, SysStride ss,
-                           hipEvent_t begun, hipEvent_t done, int xcd_nsys)
+                           hipEvent_t begun, hipEvent_t done, int xcd_nsys, unsigned long long *t_first, unsigned long long *t_last)
 {
 	if (xcd_nsys > 0) grid = dim3(grid.x * grid.y);          // one line of workgroups, decoded in the kernel (a system per XCD)
 	{
@@ -598,19 +599,19 @@ hipError_t launch_update16(dim3 grid, hipStream_t s, u64 *M, i64 rows, i64 srows
 		if (stream_rows && NT == 512 && DEPTH == 3 && PIPE && LB == 512) {
 			if (nw_lo < 0)
 				hipExtLaunchKernelGGL((k_update16<512, true, 3, true, 512, true>), grid, dim3(512), 0, s, begun, done, 0, M, rows, srows, j0, gb, wlo,
-				                      panels, aux, multset, blk_first, tile_begin, ntiles, world, wrank, Pc, ss, xcd_nsys);
+				                      panels, aux, multset, blk_first, tile_begin, ntiles, world, wrank, Pc, ss, xcd_nsys, t_first, t_last);
 			else
 				hipExtLaunchKernelGGL((k_update16<512, false, 3, true, 512, true>), grid, dim3(512), 0, s, begun, done, 0, M, rows, srows, j0, gb, wlo,
-				                      panels, aux, multset, blk_first, tile_begin, ntiles, world, wrank, Pc, ss, xcd_nsys);
+				                      panels, aux, multset, blk_first, tile_begin, ntiles, world, wrank, Pc, ss, xcd_nsys, t_first, t_last);
 			return hipGetLastError();
 		}
 	}
 	if (nw_lo < 0)
 		hipExtLaunchKernelGGL((k_update16<NT, true, DEPTH, PIPE, LB>), grid, dim3(NT), 0, s, begun, done, 0, M, rows, srows, j0, gb, wlo,
-		                      panels, aux, multset, blk_first, tile_begin, ntiles, world, wrank, Pc, ss, xcd_nsys);
+		                      panels, aux, multset, blk_first, tile_begin, ntiles, world, wrank, Pc, ss, xcd_nsys, t_first, t_last);
 	else
 		hipExtLaunchKernelGGL((k_update16<NT, false, DEPTH, PIPE, LB>), grid, dim3(NT), 0, s, begun, done, 0, M, rows, srows, j0, gb, wlo,
-		                      panels, aux, multset, blk_first, tile_begin, ntiles, world, wrank, Pc, ss, xcd_nsys);
+		                      panels, aux, multset, blk_first, tile_begin, ntiles, world, wrank, Pc, ss, xcd_nsys, t_first, t_last);
 	return hipGetLastError();
 }
 #define UPDATE16_IMPL(NT, D, P, LB) { 4, 8, 2 * 256 * 256 + GF2_GMAX * 64 * 20, NT, launch_update16<NT, D, P, LB> }
@@ -838,6 +839,14 @@ struct SolverHandles {
 	hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
 	std::vector<hipEvent_t> evA, evPrio, kev, waitPrio;     // waitPrio[b]: the event that means "bulk of block b complete"
 	hipEvent_t evx = nullptr;
+	// time_kernels: the bulk-update launches stamp the clock themselves (k_update16: t_first / t_last) -- first[0] is the clock at
+	// ev0, launch i owns first[i] and last[i] = stamps[stamp_cap + i].  kev keeps the launches that have no slot: the outer passes
+	// of a two-level plan, and whatever a solve with many resumed blocks launches beyond stamp_cap.
+	unsigned long long *stamps = nullptr;
+	int n_stamps = 0, stamp_cap = 0;
+	// what sweep_intervals read, kept for the next asker (a solve with many right-hand sides fills the stats of every result)
+	mutable std::vector<std::pair<float, float>> sweep_iv;
+	mutable int sweep_read = 0;       // 0: not read yet, 1: read, -1: read, and a slot or the copy was bad
 };
 
 // One solve: its plan, its side arrays and its resources.  Every resource has one owner, so a Solver is not copied: what starts
@@ -865,7 +874,7 @@ struct Solver : SolverPlan, ArenaPtrs, SolverHandles {
 			if (sC) (void)hipStreamSynchronize(sC);
 			if (sB) (void)hipStreamSynchronize(sB);
 			if (arena || M) (void)hipStreamSynchronize(sA);
-			for (void *p : { arena, (void *)(ext_M ? nullptr : M), (void *)tmp_src }) P.release(p);
+			for (void *p : { arena, (void *)(ext_M ? nullptr : M), (void *)tmp_src, (void *)stamps }) P.release(p);
 			for (hipEvent_t e : { ev0, ev1, ev2, ev3, evx }) P.release_event(e, true);
 			for (hipEvent_t e : { evOuter, evPri, evPanelDone, evBig }) P.release_event(e, false);
 			if (sC) P.release_stream(sC, device, nsys > 1 ? 3 : 1);
@@ -1134,24 +1143,37 @@ int launch_trsm(Solver &S, hipStream_t st, int j0, int gb, int wlo, int nw_lo, i
 	return GF2BV_OK;
 }
 
+// The stamp slot of the next timed launch: slot 0 is the clock at ev0, launch i takes slot i, and none is left (-1: that launch
+// is bracketed by events) once `cap` are handed out.
+constexpr int stamp_slot(int handed_out, int cap) { return handed_out >= 1 && handed_out < cap ? handed_out : -1; }
+static_assert(stamp_slot(1, 66) == 1 && stamp_slot(65, 66) == 65, "slots 1 .. cap - 1 go to launches");
+static_assert(stamp_slot(66, 66) == -1 && stamp_slot(67, 66) == -1, "a launch beyond the slots gets none: its last stamp would lie outside the buffer");
+static_assert(stamp_slot(0, 66) == -1, "slot 0 is the base clock's");
+
 // One bulk-update launch of block b on the `ntiles` owned tiles from tile_begin on; `last`: it carries the hand-off
 // ("bulk of block b complete") and *handoff receives that event.
 int launch_update_timed(Solver &S, hipStream_t st, int b, int j0, int gb, int wlo, u64 *mset, int tile_begin, int ntiles,
                         int nw_lo, bool last, hipEvent_t *handoff)
 {
+	// time_kernels: the launch stamps the clock itself; a launch beyond the slots (many resumed blocks) is bracketed by events
 	hipEvent_t ka = nullptr, kb = nullptr;
-	if (S.time_kernels) {
+	unsigned long long *t_first = nullptr, *t_last = nullptr;
+	if (S.time_kernels && !S.stamps) return fail(GF2BV_ERR_HIP, "a timed bulk update without stamp slots (enqueue_forward_begin makes them)");
+	if (const int slot = S.time_kernels ? stamp_slot(S.n_stamps, S.stamp_cap) : -1; slot > 0) {
+		t_first = S.stamps + slot; t_last = t_first + S.stamp_cap;
+		S.n_stamps++;
+	} else if (S.time_kernels) {
 		HIPCHK(pool().event(&ka, true)); HIPCHK(pool().event(&kb, true));
 		S.kev.push_back(ka); S.kev.push_back(kb);
 	}
 	const i64 est_rows = std::max<i64>(256, S.rows - (i64)j0 * 64);      // alive rows of a dense system (the kernel uses the true bound)
 	const bool pin = S.xcd_pin && S.nsys >= 8 && S.nsys % 8 == 0;
 	const int wgs = pick_update_wgs(est_rows, ntiles, S.nsys, pin ? S.kn.xcd_wgs : 0);
-	// the launch's own start / completion signals (hipExtLaunchKernel) carry the timing events or the hand-off: no marker packets, ~1 % at every size
-	const hipEvent_t begun = ka, done = S.time_kernels ? kb : (last && !S.flag_sync ? S.evPrio[b] : nullptr);
+	// the launch's own start / completion signals (hipExtLaunchKernel) carry the hand-off (or the timing events): no marker packets, ~1 % at every size
+	const hipEvent_t begun = ka, done = kb ? kb : (last && !S.flag_sync ? S.evPrio[b] : nullptr);
 	HIPCHK(S.impl->update(dim3((unsigned)wgs, S.nsys), st, S.M, S.rows, S.srows, j0, gb, wlo, S.panels, S.aux, mset,
 	                      S.blk_first + b, tile_begin, ntiles, S.world, S.wrank, nw_lo, pin && S.kn.gang_nt,
-	                      (const uint4 *)S.Pc, S.ss(), begun, done, pin ? S.nsys : 0));
+	                      (const uint4 *)S.Pc, S.ss(), begun, done, pin ? S.nsys : 0, t_first, t_last));
 	if (last && !S.flag_sync) *handoff = done;
 	return GF2BV_OK;
 }
@@ -1348,6 +1370,16 @@ int enqueue_block_prio(Solver &S, int b)
 
 int enqueue_forward_begin(Solver &S, bool gather_first_window)
 {
+	if (S.time_kernels && !S.stamps) {
+		// a slot per bulk-update launch: one per block, the HALF tile's, and room for blocks that are enqueued again
+		S.stamp_cap = 2 * S.nblocks + 64;
+		HIPCHK(pool().alloc((void **)&S.stamps, sizeof(unsigned long long) * 2 * S.stamp_cap, S.device));
+		HIPCHK(hipMemsetAsync(S.stamps, 0xff, sizeof(unsigned long long) * S.stamp_cap, S.sA));                      // first: minima
+		HIPCHK(hipMemsetAsync(S.stamps + S.stamp_cap, 0, sizeof(unsigned long long) * S.stamp_cap, S.sA));          // last: maxima
+		k_stamp_clock<<<dim3(1), dim3(64), 0, S.sA>>>(S.stamps);
+		HIPCHK(hipGetLastError());
+		S.n_stamps = 1;
+	}
 	HIPCHK(hipEventRecord(S.ev0, S.sA));
 	HIPCHK(hipStreamWaitEvent(S.sB, S.ev0, 0));     // sB starts after the setup memsets on sA
 	if (S.npanels > 0 && gather_first_window) {
@@ -1855,6 +1887,36 @@ std::vector<u64> basis_rows(const u64 *hout, i64 cw, const std::vector<int> &fre
 
 void fill_stats(const Solver &S, gf2bv_result *R);
 
+// When every bulk-update launch of a finished timed solve ran, in ms from ev0: one copy of the stamps the launches left (the
+// clock runs at 100 MHz), and the event pairs of the launches that have no slot.  *ok = false: the stamps could not be read, or a
+// slot that was handed out is not a launch's (every launch leaves both stamps, behind the clock at ev0) -- the caller then reports a
+// NEGATIVE ms_sweep and not a sum that misses launches.
+std::vector<std::pair<float, float>> sweep_intervals(const Solver &S, bool *ok)
+{
+	if (S.sweep_read) { *ok = S.sweep_read > 0; return S.sweep_iv; }
+	std::vector<std::pair<float, float>> iv;
+	*ok = true;
+	if (S.stamps && S.n_stamps > 1) {
+		std::vector<unsigned long long> h(2 * (size_t)S.stamp_cap);
+		if (hipMemcpyAsync(h.data(), S.stamps, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost, S.sA) == hipSuccess
+		    && hipStreamSynchronize(S.sA) == hipSuccess) {
+			for (int i = 1; i < S.n_stamps; i++) {
+				const unsigned long long first = h[i], last = h[S.stamp_cap + i];
+				if (first == ~0ull || last < first || first < h[0]) { *ok = false; continue; }
+				iv.push_back({ (float)((double)(first - h[0]) * 1e-5), (float)((double)(last - h[0]) * 1e-5) });
+			}
+		} else { (void)hipGetLastError(); *ok = false; }
+	}
+	for (size_t i = 0; i + 1 < S.kev.size(); i += 2) {
+		float ms = 0, at = 0;
+		(void)hipEventElapsedTime(&ms, S.kev[i], S.kev[i + 1]);
+		if (hipEventElapsedTime(&at, S.ev0, S.kev[i]) != hipSuccess) { (void)hipGetLastError(); at = iv.empty() ? 0.f : iv.back().second; }
+		iv.push_back({ at, at + ms });
+	}
+	S.sweep_iv = iv; S.sweep_read = *ok ? 1 : -1;
+	return iv;
+}
+
 // Export, second half: wait for the copies and build the result object.
 int finish_end(Solver &S, gf2bv_result **out)
 {
@@ -1932,13 +1994,8 @@ void fill_stats(const Solver &S, gf2bv_result *R)
 		// ms_sweep = the time during which AT LEAST ONE bulk-update launch was running: launches of one stream add up as before
 		// (every one-level plan), launches that run side by side -- the two halves of an outer pass on their two streams, the next
 		// panel's inner updates beside them -- count once (summed, the split pass of late round 5 would be counted twice)
-		std::vector<std::pair<float, float>> iv;
-		for (size_t i = 0; i + 1 < S.kev.size(); i += 2) {
-			float ms = 0, at = 0;
-			(void)hipEventElapsedTime(&ms, S.kev[i], S.kev[i + 1]);
-			if (hipEventElapsedTime(&at, S.ev0, S.kev[i]) != hipSuccess) { (void)hipGetLastError(); at = iv.empty() ? 0.f : iv.back().second; }
-			iv.push_back({ at, at + ms });
-		}
+		bool stamps_ok = true;
+		std::vector<std::pair<float, float>> iv = sweep_intervals(S, &stamps_ok);
 		std::sort(iv.begin(), iv.end());
 		float lo = 0, hi = -1;
 		for (const auto &v : iv) {
@@ -1947,6 +2004,7 @@ void fill_stats(const Solver &S, gf2bv_result *R)
 			else { st.ms_sweep += hi - lo; lo = v.first; hi = v.second; }
 		}
 		if (hi >= 0) st.ms_sweep += hi - lo;
+		if (!stamps_ok) st.ms_sweep = -1.f;
 	}
 	st.ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - S.t_begin).count();
 }
@@ -2016,11 +2074,9 @@ int solve_gang(Solver &S, gf2bv_result **out)
 	}
 	if (S.time_kernels) {        // one set of bulk-update launches served the whole gang: every member reports the gang's time
 		float total = 0;
-		for (size_t i = 0; i + 1 < S.kev.size(); i += 2) {
-			float ms = 0;
-			(void)hipEventElapsedTime(&ms, S.kev[i], S.kev[i + 1]);
-			total += ms;
-		}
+		bool stamps_ok = true;
+		for (const auto &v : sweep_intervals(S, &stamps_ok)) total += v.second - v.first;
+		if (!stamps_ok) total = -1.f;
 		for (int s = 0; s < S.nsys; s++) out[s]->stats.ms_sweep = total;
 	}
 	return GF2BV_OK;
